@@ -300,6 +300,31 @@ def prof_report(L):
     return {names.raw[i * 32:(i + 1) * 32].split(b"\0")[0].decode(): (ms[i] / max(cnt[i], 1), int(cnt[i])) for i in range(nk)}
 
 
+DUMP_COLUMNS = 768        # --dump-outputs sample: four (36, 60, 768) fp64 arrays and the rest stay under DUMP_LIMIT
+DUMP_LIMIT = 64 << 20
+
+
+def dump_columns(ncol):
+    """Column indices written by --dump-outputs: all of them, or a fixed seeded sample (sorted) of DUMP_COLUMNS."""
+    if ncol <= DUMP_COLUMNS:
+        return np.arange(ncol)
+    return np.sort(np.random.default_rng(20240611).choice(ncol, DUMP_COLUMNS, replace=False))
+
+
+def dump_outputs(dump_dir, arrays, ncol):
+    """--dump-outputs: the arrays the timed path handed its caller in its last step, as <dump_dir>/<name>.npy in the
+    precision of the run.  Every array has the column as its last axis; all are cut to the same dump_columns(ncol)."""
+    import torch
+    cols = torch.from_numpy(dump_columns(ncol))
+    out = {name: a.index_select(a.dim() - 1, cols.to(a.device)).cpu().numpy() for name, a in arrays.items()}
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT:
+        raise SystemExit("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_LIMIT))
+    os.makedirs(dump_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(dump_dir, name + ".npy"), a)
+
+
 def lw_measure(pkg, lw_file, ncol, dtype, steps, warmup, device=0):
     """One LW gas_optics + rte_lw workload beside the headline (another table and / or precision): value, ms per step,
     per-kernel HIP-event times, fraction of the HBM roofline at the API-boundary accounting of the precision, and the
@@ -403,6 +428,9 @@ def main():
     ap.add_argument("--fortran-sample", type=int, default=200000,
                     help="columns of the side measurement through the Fortran type-bound API in device-resident mode "
                          "(ecckd_driver: host arrays in, fluxes out, tau and sources stay in HBM; 0 = skip)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (gas-optics outputs and fluxes; rank "
+                         "0's columns) as DIR/<name>.npy; above %d columns a fixed seeded sample of them" % DUMP_COLUMNS)
     args = ap.parse_args()
     if args.gpus > 1 and "RANK" not in os.environ:
         return self_launch(args.gpus)
@@ -423,6 +451,18 @@ def main():
         if world == 1 and args.gpus > 1:
             raise SystemExit("bench.py --gpus %d must be launched through torch.distributed.run" % args.gpus)
     if not torch.cuda.is_available():
+        if "RANK" in os.environ and world > 1:
+            # torch.distributed.run stops every other rank as soon as one exits: each rank reports first, then they
+            # leave together (gloo barrier, bounded), so that every rank's message gets out
+            print("bench.py needs a GPU (no CPU fallback)", file=sys.stderr, flush=True)
+            import datetime
+            try:
+                dist.init_process_group("gloo", rank=rank, world_size=world, timeout=datetime.timedelta(seconds=60))
+                dist.barrier()
+                dist.destroy_process_group()
+            except Exception:   # a peer that never came: leave anyway
+                pass
+            raise SystemExit(1)
         raise SystemExit("bench.py needs a GPU (no CPU fallback)")
     if args.rehearse_on_one_gpu:
         local_rank = 0
@@ -481,6 +521,10 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     L.ecckd_prof_enable(0)
+    if args.dump_outputs and rank == 0:   # before any side measurement reuses these buffers
+        dump_outputs(args.dump_outputs, {"tau": op.tau, "lay_source": src.lay_source, "lev_source_inc": src.lev_source_inc,
+                                         "lev_source_dec": src.lev_source_dec, "sfc_source": src.sfc_source,
+                                         "flux_up": fl.flux_up, "flux_dn": fl.flux_dn}, ncol)
 
     # per-kernel HIP-event durations recorded inside the timed region
     kern = prof_report(L)
@@ -758,10 +802,11 @@ def main():
 
 
 def main_sw(args):
-    print(json.dumps(sw_measure(args.ncol, args.steps, args.warmup, args.solver_option, fused=not args.no_side, dtype=args.dtype)), flush=True)
+    print(json.dumps(sw_measure(args.ncol, args.steps, args.warmup, args.solver_option, fused=not args.no_side, dtype=args.dtype,
+                                dump_dir=args.dump_outputs)), flush=True)
 
 
-def sw_measure(ncol, steps, warmup, solver_option=(), fused=True, dtype="f64"):
+def sw_measure(ncol, steps, warmup, solver_option=(), fused=True, dtype="f64", dump_dir=None):
     """Secondary line: SW wide-tol0.05 (27 g-points), gas_optics (tau, ssa, g) + rte_sw two-stream, fp64 (or fp32),
     single GPU.  Algorithmic bytes: tau, ssa, g written once and read once = 48 B/cell (+ per-column terms)."""
     import types
@@ -830,6 +875,9 @@ def sw_measure(ncol, steps, warmup, solver_option=(), fused=True, dtype="f64"):
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     L.ecckd_prof_enable(0)
+    if dump_dir:
+        dump_outputs(dump_dir, {"tau": op.tau, "ssa": op.ssa, "g": op.g, "toa_src": toa,
+                                "flux_up": fl.flux_up, "flux_dn": fl.flux_dn}, ncol)
     names_b = C.create_string_buffer(8 * 32)
     ms = (C.c_double * 8)()
     cnt = (C.c_longlong * 8)()
