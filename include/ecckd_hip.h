@@ -281,7 +281,7 @@ int ecckd_rte_sw(int device, int ncol, int nlay, int ngpt, int top_at_1, const d
 /* Single-precision flavours of the shortwave pair and of ecckd_rte_lw_inc_flux (a host built with RTE-RRTMGP's
  * RTE_USE_SP: wp = real32, src/gas_optics_ecckd.f90:6).  Every data array is float, arithmetic is float, the g-point
  * sums are accumulated in double and rounded once.  ecckd_gas_optics_sw_f32: one-pass gas lists (all ecCKD files);
- * ecckd_rte_sw_f32: the layer-systolic solver (at most 60 layers). */
+ * ecckd_rte_sw_f32 (and ecckd_rte_sw_byband_f32): any layer count, with the solver "sw_solver" picks as for fp64. */
 int ecckd_gas_optics_sw_f32(const ecckd_model_t *model, int ncol, int nlay, const float *plev, const float *tlay,
                             int ngas, const char *gas_names, const float *const *vmr,
                             const long long *vmr_col_stride, const long long *vmr_lay_stride,
@@ -305,8 +305,14 @@ int ecckd_rte_lw_inc_flux_f32(int device, int ncol, int nlay, int ngpt, int top_
  * toa_src = solar_irradiance(g)), so a host that only needs fluxes moves the TOTAL optical depth alone: gas optics
  * writes tau (8 B/cell) and the solver evaluates those same expressions while it reads it (8 B/cell) -- 16 instead of
  * 48 B per (column, layer, g-point).  Same arithmetic per cell: fluxes bit-identical to ecckd_gas_optics_sw +
- * ecckd_rte_sw.  tau lives in library-owned stream-ordered scratch.  Fast arithmetic mode, layer-systolic solver
- * (at most 60 layers); ECCKD_DEVICE or ECCKD_HOST.
+ * ecckd_rte_sw.  tau lives in library-owned stream-ordered scratch.  Fast arithmetic mode; any layer count, with the
+ * solver ecckd_rte_sw takes for the shape ("sw_solver"), so the bits match at every depth; ECCKD_DEVICE or ECCKD_HOST.
+ * With ECCKD_DEVICE, tau sits at the start of the stream's scratch block and the solver's room follows it.  A host
+ * that owns the block (ecckd_set_stream_scratch) sizes it as align256(ncol*nlay*ngpt*sizeof(real)) (align256: round
+ * up to a multiple of 256 bytes) plus
+ *   layer-systolic solver ("sw_solver" = 0, nlay <= 60): ecckd_rte_sw_tail_scratch_bytes(device, ncol, nlay, ngpt);
+ *   two-pass solver (every other call): max(ecckd_rte_sw_scratch_bytes(ncol, nlay, ngpt),
+ *                                           ecckd_rte_sw_tail_scratch_bytes(device, ncol, nlay, ngpt)).
  *   toa_scale(ncol) or NULL: toa(i,g) = solar_irradiance(g)*toa_scale(i) -- the drivers' rescaling to the file's total
  *   solar irradiance (ecckd_rfmip_sw.F90:126-133); mu0(ncol), sfc_alb_dir/dif(nband,ncol) as ecckd_rte_sw;
  *   flux_dir may be NULL.
@@ -445,9 +451,12 @@ int ecckd_get_arithmetic(void);
  *                            solver: calls that do not fill one round of its persistent grid, one g-point group per wave
  *   "sw_solver"              0 (default): layer-systolic solver (kernels_rte_sw_sys.hip: the two-stream coefficients are
  *                            computed once and stay in registers between the sweeps, the layers of a column are spread
- *                            over the waves of a block; at most 60 layers, no scratch ring); 1: two-pass kernel (any
- *                            layer count; reads tau / ssa / g twice, scratch ring).  The same arithmetic per (column,
- *                            g-point); the g-point sums are ordered differently (sequential / shuffle tree)
+ *                            over the waves of a block; at most 60 layers, no scratch ring; deeper calls take the
+ *                            two-pass kernel); 1: two-pass kernel (any layer count; reads tau / ssa / g twice, scratch
+ *                            ring) for every call.  Either value serves every shortwave entry point (fp64, fp32,
+ *                            by band, ecckd_sw_fluxes).  The same two-stream coefficients per (column, g-point);
+ *                            the fast mode's adding recurrences and the g-point sums differ in order (sequential /
+ *                            shuffle tree): the two agree to the last bits
  *   "gas_merge_scalars"      fast arithmetic mode, fp64: 1 (default) the gases of gas_desc given as ONE number for the call
  *                            (vmr pointer NULL + vmr_scalar; get_vmr broadcasts them, src/gas_optics_ecckd.f90:351) and
  *                            the none_ composite share one table sum_k m_k*coefficient_k, m_k = vmr | vmr - reference | 1,
@@ -472,7 +481,9 @@ int ecckd_get_solver_option(const char *name, double *value);
  * block (replay those on one stream), and a graph must be destroyed before ecckd_release_scratch.
  * --------------------------------------------------------------------------------------- */
 size_t ecckd_rte_lw_scratch_bytes(int ncol, int nlay, int ngpt);
-size_t ecckd_rte_sw_scratch_bytes(int ncol, int nlay, int ngpt);   /* (two-pass solver: "sw_solver" = 1, or more than 60 layers) */
+size_t ecckd_rte_sw_scratch_bytes(int ncol, int nlay, int ngpt);   /* (two-pass solver: "sw_solver" = 1, or more than 60 layers;
+                                                                     an upper bound for fp32 as well; ecckd_sw_fluxes adds
+                                                                     its optical depth: see the fused shortwave path) */
 /* What the tail splits ("lw_tail_split", "sw_tail_split") of a call of this shape would take on top, with the
  * solver options as they are now (0: the call would not split). */
 size_t ecckd_rte_lw_tail_scratch_bytes(int device, int ncol, int nlay, int ngpt, int n_gauss_angles, int single_precision);

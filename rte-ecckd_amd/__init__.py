@@ -748,7 +748,9 @@ class GasOpticsEcckd:
         """``ecckd_sw_fluxes`` (float32 arrays: ``_f32``): gas optics + rte_sw in one call for hosts that only need
         broadband fluxes -- the total optical depth alone goes through (library-owned) memory, the solver derives
         ssa, g = 0 and the incoming beam from plev and the model's tables as gas_optics_ext does.  ``toa_scale``
-        ``(ncol,)``: the drivers' rescaling of the incoming beam (total solar irradiance), or None."""
+        ``(ncol,)``: the drivers' rescaling of the incoming beam (total solar irradiance), or None.  Any layer count and
+        either ``"sw_solver"``; the fast arithmetic mode only.  The solver is the one ``rte_sw`` takes for the same shape,
+        so the fluxes equal those of ``gas_optics`` + ``rte_sw`` bit for bit."""
         nlay, ncol = tlay.shape
         nband = self.get_nband()
         f32 = _is_f32(plev)
@@ -837,7 +839,9 @@ def rte_lw(optical_props, top_at_1, sources, sfc_emis, fluxes, n_gauss_angles=1,
 
 def rte_sw(optical_props, top_at_1, mu0, toa_flux, sfc_alb_dir, sfc_alb_dif, fluxes, device=None):
     """``rte_sw(optical_props, top_at_1, mu0, toa_flux, sfc_alb_dir, sfc_alb_dif, fluxes)``
-    (ecckd_rfmip_sw.F90:148-154).  Albedos are ``(ncol, nband)`` in numpy order."""
+    (ecckd_rfmip_sw.F90:148-154).  Albedos are ``(ncol, nband)`` in numpy order.  float32 arrays take
+    ``ecckd_rte_sw_f32`` (``_byband_f32`` for by-band fluxes).  Any layer count: up to 60 layers the layer-systolic
+    solver (``"sw_solver"`` 0, the default), otherwise the two-pass kernel (include/ecckd_hip.h, ``"sw_solver"``)."""
     if not isinstance(optical_props, OpticalProps2str):
         return "rte_sw: two-stream optical properties required"
     ng, nlay, ncol = optical_props.tau.shape

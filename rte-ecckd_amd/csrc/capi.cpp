@@ -193,7 +193,9 @@ thread_local int g_band_override = -1;
 // set by ecckd_sw_fluxes around ecckd_rte_sw: the solver derives ssa / g / toa itself (RteSwArgs::derive)
 struct SwDerive { const double *plev, *rayleigh, *solar, *toa_scale; double gw; };
 thread_local const SwDerive *g_sw_derive = nullptr;
-thread_local double *g_sw_partials = nullptr;   // ... and the room for the solver's partial sums inside the caller's scratch block   // set by ecckd_rte_lw_shared_levels around ecckd_rte_lw
+// ... and the solver's room inside ecckd_sw_fluxes' own scratch block (sw_fluxes_solver_bytes): the partial sums of the
+// layer-systolic solver, or the scratch ring of the two-pass solver with its partial sums behind it
+thread_local double *g_sw_scratch = nullptr;
 // ecckd_gas_optics_plan(): when set, gas_optical_depth_dev() records its decisions here and launches nothing
 struct PlanRecord {
   const int *is_scalar = nullptr;   // per gas of the list: its mole fraction would be passed as one number
@@ -620,6 +622,16 @@ size_t ecckd_rte_sw_tail_scratch_bytes(int device, int ncol, int nlay, int ngpt)
   long first = -1;
   size_t at = 0;
   return ecckd::rte_sw_tail_plan(a, &first, &at);
+}
+// What ecckd_sw_fluxes needs behind the optical depth in its scratch block for the solver it will take (the sizing
+// rule of include/ecckd_hip.h): the layer-systolic solver's partial sums, or the two-pass solver's ring and partial sums.
+static size_t sw_fluxes_solver_bytes(int device, int ncol, int nlay, int ngpt) {
+  ecckd::RteSwArgs a{};
+  a.ncol = ncol; a.nlay = nlay; a.ng = ngpt;
+  const size_t tail = ecckd_rte_sw_tail_scratch_bytes(device, ncol, nlay, ngpt);
+  if (g_opt.sw_solver.load() == 0 && ecckd::rte_sw_sys_applies(a)) return tail;
+  const size_t ring = ecckd_rte_sw_scratch_bytes(ncol, nlay, ngpt);
+  return tail > ring ? tail : ring;
 }
 size_t ecckd_rte_lw_tail_scratch_bytes(int device, int ncol, int nlay, int ngpt, int n_gauss_angles, int single_precision) {
   if (ncol <= 0 || nlay <= 0 || ngpt <= 0 || device < 0 || device >= 16 || !g_opt.lw_tail_split.load()) return 0;
@@ -1334,16 +1346,27 @@ int ecckd_rte_sw(int device, int ncol, int nlay, int ngpt, int top_at_1, const d
   ScratchLease lease;   // (held until the kernels of this call have been launched)
   const int cus = simd_slots(device) / 4;
   a.use_sys = g_opt.sw_solver.load() == 0 && ecckd::rte_sw_sys_applies(a) && cus > 0;
-  if ((a.f32 || a.derive) && !a.use_sys)
-    return fail("ecckd_rte_sw: single precision and the fused shortwave path need the layer-systolic solver (sw_solver = 0, at most 60 layers)");
   if (a.use_sys) {
     // layer-systolic solver: no scratch ring; the g-point chunks of the last part-empty round go through partial sums
     if (g_opt.sw_tail_split.load()) {
       const size_t need = ecckd::rte_sw_sys_plan(a, cus);
       if (need) {
-        if (g_sw_derive) a.partials = g_sw_partials;   // (ecckd_sw_fluxes sized its block with ecckd_rte_sw_tail_scratch_bytes)
+        if (g_sw_derive) a.partials = g_sw_scratch;   // (ecckd_sw_fluxes sized its block with sw_fluxes_solver_bytes)
         else if (void *sp = stream_scratch_optional(device, launch_stream, need, lease)) a.partials = static_cast<double *>(sp);
         if (!a.partials) { a.sys_tail_first = -1; a.sys_gchunk = 0; }
+      }
+    }
+  } else if (g_sw_derive) {
+    // two-pass solver inside ecckd_sw_fluxes: the stream's scratch block holds the optical depth, so the ring and the
+    // partial sums come from the room behind it (sw_fluxes_solver_bytes), never from stream_scratch
+    a.scratch = g_sw_scratch;
+    if (!a.scratch) return fail("ecckd_rte_sw: the fused shortwave path has no room for the two-pass solver's scratch ring");
+    if (g_opt.sw_tail_split.load()) {
+      long first = -1;
+      size_t partials_at = 0;
+      if (ecckd::rte_sw_tail_plan(a, &first, &partials_at)) {
+        a.partials = reinterpret_cast<double *>(reinterpret_cast<char *>(g_sw_scratch) + partials_at);
+        a.tail_first = first;
       }
     }
   } else {
@@ -1734,8 +1757,6 @@ int ecckd_sw_fluxes(const ecckd_model_t *m, int ncol, int nlay, const double *pl
   if (!plev || !tlay || !mu0 || !sfc_alb_dir || !sfc_alb_dif || !flux_up || !flux_dn || (ngas > 0 && !gas_names))
     return fail("ecckd_sw_fluxes: null argument");
   if (g_arith.load() != 0) return fail("ecckd_sw_fluxes: needs the fast arithmetic mode (ecckd_set_arithmetic(0))");
-  if (nlay > 60 || g_opt.sw_solver.load() != 0)
-    return fail("ecckd_sw_fluxes: needs the layer-systolic shortwave solver (sw_solver = 0, at most 60 layers)");
   HIPCHK(hipSetDevice(m->device));
   if (ncol == 0) return 0;
   const GasDesc gd{ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar};
@@ -1750,30 +1771,30 @@ int ecckd_sw_fluxes(const ecckd_model_t *m, int ncol, int nlay, const double *pl
   };
   if (memspace == ECCKD_DEVICE) {
     hipStream_t st = static_cast<hipStream_t>(stream);
-    void *tau_p = nullptr;   // tau lives in the stream's scratch block between the two kernels; the solver's partial sums behind it
+    void *tau_p = nullptr;   // tau lives in the stream's scratch block between the two kernels; the solver's room behind it
     ScratchLease lease;
     const size_t tau_bytes = align256(n3 * esz());
-    const size_t tail = ecckd_rte_sw_tail_scratch_bytes(m->device, ncol, nlay, m->ng);
-    if (stream_scratch(m->device, st, tau_bytes + tail, &tau_p, lease)) return 1;
+    const size_t solver = sw_fluxes_solver_bytes(m->device, ncol, nlay, m->ng);
+    if (stream_scratch(m->device, st, tau_bytes + solver, &tau_p, lease)) return 1;
     double *d_tau = static_cast<double *>(tau_p);
     // gas_optics_ext's tau (:449-456) without ssa / g: the total optical depth, gases + Rayleigh
     if (gas_optical_depth_dev(m, ncol, nlay, plev, tlay, gd, d_tau, true, nullptr, nullptr, nullptr, nullptr, st)) return 1;
     const SwDerive dv{plev, tabs(m->off_rayleigh), tabs(m->off_solar), toa_scale, gw};
     Scope scope(&dv);
-    g_sw_partials = tail ? reinterpret_cast<double *>(static_cast<char *>(tau_p) + tau_bytes) : nullptr;
+    g_sw_scratch = solver ? reinterpret_cast<double *>(static_cast<char *>(tau_p) + tau_bytes) : nullptr;
     const int rc = ecckd_rte_sw(m->device, ncol, nlay, m->ng, top_at_1, d_tau, nullptr, nullptr, mu0, nullptr, m->nband,
                                 m->band2gpt.data(), sfc_alb_dir, sfc_alb_dif, flux_up, flux_dn, flux_dir, ECCKD_DEVICE, stream);
-    g_sw_partials = nullptr;
+    g_sw_scratch = nullptr;
     return rc;
   }
   if (memspace != ECCKD_HOST) return fail("ecckd: bad memspace");
   ecckd_model *mm = const_cast<ecckd_model *>(m);
   std::lock_guard<std::mutex> lock(mm->mu);
   hipStream_t s = mm->host_stream;
-  const size_t tail = ecckd_rte_sw_tail_scratch_bytes(m->device, ncol, nlay, m->ng);
+  const size_t solver = sw_fluxes_solver_bytes(m->device, ncol, nlay, m->ng);
   const size_t need = align256(n2l * esz()) * 4 + align256(n2 * esz()) + align256((size_t)ncol * esz()) * 2 +
                       staged_gas_bytes(gd, ncol, nlay) + align256((size_t)ncol * m->nband * esz()) * 2 + align256(n3 * esz()) +
-                      align256(tail);
+                      align256(solver);
   if (need > mm->arena_bytes) {
     HIPCHK(hipStreamSynchronize(s));
     if (mm->arena) { HIPCHK(hipFree(mm->arena)); mm->arena = nullptr; mm->arena_bytes = 0; }
@@ -1791,14 +1812,14 @@ int ecckd_sw_fluxes(const ecckd_model_t *m, int ncol, int nlay, const double *pl
   StagedGases sg;
   if (stage_gases(gd, ncol, nlay, b, s, sg)) return 1;
   double *d_tau = b.take(n3);
-  double *d_part = tail ? b.take((tail + esz() - 1) / esz()) : nullptr;
+  double *d_solver = solver ? b.take((solver + esz() - 1) / esz()) : nullptr;
   if (gas_optical_depth_dev(m, ncol, nlay, d_plev, d_tlay, sg.gd, d_tau, true, nullptr, nullptr, nullptr, nullptr, s)) return 1;
   const SwDerive dv{d_plev, tabs(m->off_rayleigh), tabs(m->off_solar), toa_scale ? d_scale : nullptr, gw};
   Scope scope(&dv);
-  g_sw_partials = d_part;
+  g_sw_scratch = d_solver;
   const int rc = ecckd_rte_sw(m->device, ncol, nlay, m->ng, top_at_1, d_tau, nullptr, nullptr, d_mu0, nullptr, m->nband,
                               m->band2gpt.data(), d_ad, d_af, d_up, d_dn, flux_dir ? d_dir : nullptr, ECCKD_DEVICE, s);
-  g_sw_partials = nullptr;
+  g_sw_scratch = nullptr;
   if (rc) return 1;
   if (d2h(flux_up, d_up, n2l, s) || d2h(flux_dn, d_dn, n2l, s)) return 1;
   if (flux_dir && d2h(flux_dir, d_dir, n2l, s)) return 1;

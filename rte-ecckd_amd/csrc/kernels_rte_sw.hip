@@ -14,6 +14,8 @@
 // RECOMPUTE note at the kernel for what is stored and what is computed twice.
 // (Registers cannot hold it next to a useful occupancy: the coefficient arithmetic is ~250 fp64
 // instructions per cell and needs several waves per SIMD to issue at rate.)
+// Any layer count and both precisions: the route of every call the layer-systolic solver does not serve (more than 60
+// layers, or "sw_solver" = 1), the fused shortwave path (DERIVE) included.
 #include <type_traits>
 
 #include "kernels.hpp"
@@ -73,10 +75,21 @@ __device__ __forceinline__ void acc_add(double *p, double v, bool owner) {
 // needs as well (24 + 48 + 48 = 120 B/cell).  The kernel is bound by that traffic, not by the
 // arithmetic (0.25 VALU wave-instr/clk/CU of 0.81 available at this occupancy): measured 4.52 ms
 // stored vs 3.85 ms recomputed per 1e5 columns x 27 g-points (recomputed: 52 % of the fp64 VALU rate).
-template <int CW, bool RECOMPUTE, bool FAST, bool CLAMP>
-__global__ void __launch_bounds__(64, ECCKD_SW_WAVES_PER_SIMD) rte_sw_kernel(const RteSwArgs a) {
+//
+// real: storage and arithmetic type of everything per cell (inputs, two-stream arithmetic, scratch ring, outputs); the
+// g-point sums, the LDS accumulators and the tail partials are double whatever `real` is, as in rte_sw_sys_kernel.
+// DERIVE: fused shortwave path (RteSwArgs::derive): tau is the total optical depth and ssa / g / toa come from
+// rte_sw_sys_kernel's expressions (src/gas_optics_ecckd.f90:313-317,455-472); the lane's layer slots then prefetch the two
+// level pressures of a layer in place of its ssa and g.
+// The kernels (rte_sw_kernel, below) are thin entries to this body.
+template <typename real, int CW, bool RECOMPUTE, bool FAST, bool CLAMP, bool DERIVE>
+__device__ __forceinline__ void rte_sw_body(const RteSwArgs &a) {
   constexpr int GW = 64 / CW;
+  // (fp32 DERIVE: the correctly rounded fp32 division of ssa makes three layers in flight spill; two do not)
+  constexpr int PF = (DERIVE && sizeof(real) == 4) ? 2 : kPF;
   extern __shared__ double acc[];   // [3][nlay+1][CW]: up, dn, dir
+  auto P = [](const double *p) { return reinterpret_cast<const real *>(p); };
+  auto Q = [](double *p) { return reinterpret_cast<real *>(p); };
   const int lane = threadIdx.x;
   const int cl = lane % CW, gs = lane / CW;
   const bool owner = gs == 0;
@@ -87,12 +100,14 @@ __global__ void __launch_bounds__(64, ECCKD_SW_WAVES_PER_SIMD) rte_sw_kernel(con
   // scratch ring of this wave: level arrays (albedo, normalised source) first, then -- unless they
   // are recomputed -- the four layer arrays; each [index][64 lanes]
   constexpr int NLAYARR = RECOMPUTE ? 0 : 4;
-  double *sc = a.scratch + (long)blockIdx.x * ((long)NLAYARR * nlay + 2L * nlev) * 64 + lane;
-  double *sAlb = sc, *sSrc = sc + 64L * nlev;
-  double *sA = sSrc + 64L * nlev, *sB = sA + 64L * nlay, *sC = sB + 64L * nlay, *sTn = sC + 64L * nlay;
+  // (elements of `real`: the fp32 ring takes half of what rte_sw_scratch_bytes provides)
+  real *sc = Q(a.scratch) + (long)blockIdx.x * ((long)NLAYARR * nlay + 2L * nlev) * 64 + lane;
+  real *sAlb = sc, *sSrc = sc + 64L * nlev;
+  real *sA = sSrc + 64L * nlev, *sB = sA + 64L * nlay, *sC = sB + 64L * nlay, *sTn = sC + 64L * nlay;
   const int ngroups = (ng + GW - 1) / GW;
   const long ntiles = ((long)ncol + CW - 1) / CW;
-  const double k_floor = a.k_floor;
+  const real k_floor = (real)a.k_floor;
+  const real gw = (real)a.gw;
 
   // Work units (see rte_sw_tail_plan): units [0, tail_first) are whole tiles; beyond that a unit is ONE g-point group
   // of a tail tile and leaves its sums in `partials` for rte_sw_tail_reduce.
@@ -111,8 +126,9 @@ __global__ void __launch_bounds__(64, ECCKD_SW_WAVES_PER_SIMD) rte_sw_kernel(con
     const bool valid = col < ncol;
     const long cc = valid ? col : (long)ncol - 1;
     for (int i = lane; i < 3 * nlev * CW; i += 64) acc[i] = 0.;
-    const double mu0 = a.mu0[cc];
-    const double mu0_inv = 1. / mu0;
+    const real mu0 = P(a.mu0)[cc];
+    const real mu0_inv = real(1) / mu0;
+    const real tscale = (DERIVE && a.toa_scale) ? P(a.toa_scale)[cc] : real(1);
 
     for (int gi = g0; gi < g1; ++gi) {
       const int g = gi * GW + gs;
@@ -121,37 +137,50 @@ __global__ void __launch_bounds__(64, ECCKD_SW_WAVES_PER_SIMD) rte_sw_kernel(con
       const double keep = gact ? 1. : 0.;
       const long base = cc + (long)ncol * nlay * gg;
       const int band = a.gpt2band[gg];
+      const real ray = DERIVE ? P(a.rayleigh)[gg] : real(0);
+      // optical properties of layer sl (counted from the top) into prefetch slot d.  DERIVE: pssa / pg take plev at the
+      // layer's two levels, turned into ssa by props() once they have arrived
+      auto fetch = [&](int sl, real &t, real &x, real &y) __attribute__((always_inline)) {
+        const long lm = lay0 + lstep * sl;   // layer index in memory
+        const long q = base + (long)ncol * lm;
+        t = P(a.tau)[q];
+        if constexpr (DERIVE) { x = P(a.plev)[cc + (long)ncol * lm]; y = P(a.plev)[cc + (long)ncol * (lm + 1)]; }
+        else { x = P(a.ssa)[q]; y = P(a.g)[q]; }
+      };
+      // two-stream coefficients of a cell from its prefetch slot
+      auto props = [&](real ctau, real x, real y) __attribute__((always_inline)) {
+        if constexpr (DERIVE) {
+          const real moles = (y - x) * gw;                     // :313-314
+          const real cssa = (moles * ray) / ctau;              // :316, :459-460 (IEEE division in every mode)
+          return two_stream<real, FAST, CLAMP, true>(ctau, cssa, real(0), mu0, mu0_inv, k_floor);   // g = 0
+        }
+        else
+          return __all(y == real(0)) ? two_stream<real, FAST, CLAMP, true>(ctau, x, y, mu0, mu0_inv, k_floor)
+                                     : two_stream<real, FAST, CLAMP, false>(ctau, x, y, mu0, mu0_inv, k_floor);
+      };
 
       // ---- pass 1, bottom -> top: two-stream coefficients (sw_two_stream) and the adding
       // recurrences (albedo, source of upward radiation).  The direct beam is not known yet on the
       // way up, so the source is carried normalised by the direct flux at its own level:
       //   src(l) = nsrc(l) * F_dir(l),  F_dir(l+1) = Tnoscat(l) * F_dir(l)
-      double albedo = a.alb_dif[band + (long)a.nband * cc];
-      double nsrc = a.alb_dir[band + (long)a.nband * cc];   // src_sfc = F_dir(sfc) * sfc_alb_dir
+      real albedo = P(a.alb_dif)[band + (long)a.nband * cc];
+      real nsrc = P(a.alb_dir)[band + (long)a.nband * cc];   // src_sfc = F_dir(sfc) * sfc_alb_dir
       sAlb[64L * nlay] = albedo;
       sSrc[64L * nlay] = nsrc;
-      // (the optical properties of layer s - kPF are requested before the arithmetic of layer s: the
+      // (the optical properties of layer s - PF are requested before the arithmetic of layer s: the
       // loop is a serial recurrence and the compiler does not pipeline it)
-      double ptau[kPF], pssa[kPF], pg[kPF];
+      real ptau[PF], pssa[PF], pg[PF];
 #pragma unroll
-      for (int d = 0; d < kPF; ++d) {
-        const int sl = nlay - 1 - d > 0 ? nlay - 1 - d : 0;
-        const long q = base + (long)ncol * (lay0 + lstep * sl);
-        ptau[d] = a.tau[q]; pssa[d] = a.ssa[q]; pg[d] = a.g[q];
-      }
+      for (int d = 0; d < PF; ++d) fetch(nlay - 1 - d > 0 ? nlay - 1 - d : 0, ptau[d], pssa[d], pg[d]);
       // The layer loop is unrolled by the prefetch depth so that every layer has a FIXED slot of the prefetch registers:
       // shifting the slots along (ptau[d] = ptau[d + 1]) reads registers whose loads are still in flight and made the
-      // compiler wait with vmcnt(0) in every iteration -- one layer of loads in flight instead of kPF (round 2).
+      // compiler wait with vmcnt(0) in every iteration -- one layer of loads in flight instead of PF (round 2).
       auto layer1 = [&](int s, auto slot_c) __attribute__((always_inline)) {
         constexpr int d = decltype(slot_c)::value;
-        const double ctau = ptau[d], cssa = pssa[d], cg = pg[d];
-        {
-          const long q = base + (long)ncol * (lay0 + lstep * (s - kPF > 0 ? s - kPF : 0));
-          ptau[d] = a.tau[q]; pssa[d] = a.ssa[q]; pg[d] = a.g[q];
-        }
-        const TwoStream ts = __all(cg == 0.) ? two_stream<double, FAST, CLAMP, true>(ctau, cssa, cg, mu0, mu0_inv, k_floor)
-                                             : two_stream<double, FAST, CLAMP, false>(ctau, cssa, cg, mu0, mu0_inv, k_floor);
-        const double denom = rcp<FAST>(1. - ts.Rdif * albedo);                             // adding, Eq 10
+        const real ctau = ptau[d], cx = pssa[d], cy = pg[d];
+        fetch(s - PF > 0 ? s - PF : 0, ptau[d], pssa[d], pg[d]);
+        const TwoStreamT<real> ts = props(ctau, cx, cy);
+        const real denom = rcp<FAST>(real(1) - ts.Rdif * albedo);                          // adding, Eq 10
         if (!RECOMPUTE) {
           sA[64L * s] = ts.Tdif * denom;
           sB[64L * s] = ts.Rdif * denom;
@@ -166,69 +195,63 @@ __global__ void __launch_bounds__(64, ECCKD_SW_WAVES_PER_SIMD) rte_sw_kernel(con
       };
       {
         int s = nlay - 1;
-        for (; s >= kPF - 1; s -= kPF)                 // whole groups: slot d serves layer s - d
-          static_for_sw<0, kPF>([&](auto dc) __attribute__((always_inline)) { layer1(s - decltype(dc)::value, dc); });
-        static_for_sw<0, kPF>([&](auto dc) __attribute__((always_inline)) {   // the last, partial group
+        for (; s >= PF - 1; s -= PF)                 // whole groups: slot d serves layer s - d
+          static_for_sw<0, PF>([&](auto dc) __attribute__((always_inline)) { layer1(s - decltype(dc)::value, dc); });
+        static_for_sw<0, PF>([&](auto dc) __attribute__((always_inline)) {   // the last, partial group
           if (s - decltype(dc)::value >= 0) layer1(s - decltype(dc)::value, dc);
         });
       }
 
       // ---- pass 2, top -> bottom: direct beam and fluxes (Eq 12, 13) ----
-      double fdir = a.toa[cc + (long)ncol * gg] * mu0;
-      double fdn = 0.;
+      const real toa = DERIVE ? P(a.solar)[gg] * tscale : P(a.toa)[cc + (long)ncol * gg];   // :468-472
+      real fdir = toa * mu0;
+      real fdn = real(0);
       {
-        const double fup = fdn * albedo + nsrc * fdir;
-        const double vu = gsum<CW>(keep * fup), vd = gsum<CW>(keep * (fdn + fdir)), vr = gsum<CW>(keep * fdir);
+        const real fup = fdn * albedo + nsrc * fdir;
+        const double vu = gsum<CW>(keep * (double)fup), vd = gsum<CW>(keep * (double)(fdn + fdir)), vr = gsum<CW>(keep * (double)fdir);
         acc_add(&acc_up[cl], vu, owner);
         acc_add(&acc_dn[cl], vd, owner);
         acc_add(&acc_dir[cl], vr, owner);
       }
-      double palb[kPF], pnsrc[kPF];
+      real palb[PF], pnsrc[PF];
 #pragma unroll
-      for (int d = 0; d < kPF; ++d) {
+      for (int d = 0; d < PF; ++d) {
         const int sl = d < nlay ? d : nlay - 1;
         palb[d] = sAlb[64L * (sl + 1)]; pnsrc[d] = sSrc[64L * (sl + 1)];
-        if (RECOMPUTE) {
-          const long q = base + (long)ncol * (lay0 + lstep * sl);
-          ptau[d] = a.tau[q]; pssa[d] = a.ssa[q]; pg[d] = a.g[q];
-        }
+        if (RECOMPUTE) fetch(sl, ptau[d], pssa[d], pg[d]);
       }
       auto layer2 = [&](int s, auto slot_c) __attribute__((always_inline)) {   // (fixed prefetch slots: see pass 1)
         constexpr int d = decltype(slot_c)::value;
-        const double alb_next = palb[d], nsrc_next = pnsrc[d];
-        const double ctau = ptau[d], cssa = pssa[d], cg = pg[d];
+        const real alb_next = palb[d], nsrc_next = pnsrc[d];
+        const real ctau = ptau[d], cx = pssa[d], cy = pg[d];
         {
-          const int sn = s + kPF < nlay ? s + kPF : nlay - 1;
+          const int sn = s + PF < nlay ? s + PF : nlay - 1;
           palb[d] = sAlb[64L * (sn + 1)]; pnsrc[d] = sSrc[64L * (sn + 1)];
-          if (RECOMPUTE) {
-            const long q = base + (long)ncol * (lay0 + lstep * sn);
-            ptau[d] = a.tau[q]; pssa[d] = a.ssa[q]; pg[d] = a.g[q];
-          }
+          if (RECOMPUTE) fetch(sn, ptau[d], pssa[d], pg[d]);
         }
-        double A, B, C, Tn;
+        real A, B, C, Tn;
         if (RECOMPUTE) {
-          const TwoStream ts = __all(cg == 0.) ? two_stream<double, FAST, CLAMP, true>(ctau, cssa, cg, mu0, mu0_inv, k_floor)
-                                               : two_stream<double, FAST, CLAMP, false>(ctau, cssa, cg, mu0, mu0_inv, k_floor);
-          const double denom = rcp<FAST>(1. - ts.Rdif * alb_next);     // the same expression as in pass 1: same bits
+          const TwoStreamT<real> ts = props(ctau, cx, cy);
+          const real denom = rcp<FAST>(real(1) - ts.Rdif * alb_next);  // the same expression as in pass 1: same bits
           A = ts.Tdif * denom; B = ts.Rdif * denom; C = ts.Tdir * denom; Tn = ts.Tnoscat;
         } else {
           A = sA[64L * s]; B = sB[64L * s]; C = sC[64L * s]; Tn = sTn[64L * s];
         }
-        const double fdir_next = Tn * fdir;
-        const double src_next = nsrc_next * fdir_next;
+        const real fdir_next = Tn * fdir;
+        const real src_next = nsrc_next * fdir_next;
         fdn = A * fdn + B * src_next + C * fdir;
-        const double fup = fdn * alb_next + src_next;
+        const real fup = fdn * alb_next + src_next;
         fdir = fdir_next;
-        const double vu = gsum<CW>(keep * fup), vd = gsum<CW>(keep * (fdn + fdir)), vr = gsum<CW>(keep * fdir);
+        const double vu = gsum<CW>(keep * (double)fup), vd = gsum<CW>(keep * (double)(fdn + fdir)), vr = gsum<CW>(keep * (double)fdir);
         acc_add(&acc_up[(s + 1) * CW + cl], vu, owner);
         acc_add(&acc_dn[(s + 1) * CW + cl], vd, owner);
         acc_add(&acc_dir[(s + 1) * CW + cl], vr, owner);
       };
       {
         int s = 0;
-        for (; s + kPF <= nlay; s += kPF)              // whole groups: slot d serves layer s + d
-          static_for_sw<0, kPF>([&](auto dc) __attribute__((always_inline)) { layer2(s + decltype(dc)::value, dc); });
-        static_for_sw<0, kPF>([&](auto dc) __attribute__((always_inline)) {   // the last, partial group
+        for (; s + PF <= nlay; s += PF)              // whole groups: slot d serves layer s + d
+          static_for_sw<0, PF>([&](auto dc) __attribute__((always_inline)) { layer2(s + decltype(dc)::value, dc); });
+        static_for_sw<0, PF>([&](auto dc) __attribute__((always_inline)) {   // the last, partial group
           if (s + decltype(dc)::value < nlay) layer2(s + decltype(dc)::value, dc);
         });
       }
@@ -244,12 +267,23 @@ __global__ void __launch_bounds__(64, ECCKD_SW_WAVES_PER_SIMD) rte_sw_kernel(con
     } else if (valid) {
       for (int s = gs; s < nlev; s += GW) {
         const long q = col + (long)ncol * (lev0 + lstep * s);
-        a.flux_up[q] = acc_up[s * CW + cl];
-        a.flux_dn[q] = acc_dn[s * CW + cl];
-        if (a.flux_dir) a.flux_dir[q] = acc_dir[s * CW + cl];
+        Q(a.flux_up)[q] = (real)acc_up[s * CW + cl];
+        Q(a.flux_dn)[q] = (real)acc_dn[s * CW + cl];
+        if (a.flux_dir) Q(a.flux_dir)[q] = (real)acc_dir[s * CW + cl];
       }
     }
   }
+}
+
+// fp64, ssa / g / toa read from memory: the instantiations the API path has always taken, under their own names
+template <int CW, bool RECOMPUTE, bool FAST, bool CLAMP>
+__global__ void __launch_bounds__(64, ECCKD_SW_WAVES_PER_SIMD) rte_sw_kernel(const RteSwArgs a) {
+  rte_sw_body<double, CW, RECOMPUTE, FAST, CLAMP, false>(a);
+}
+// single precision, and the fused form (DERIVE) in either precision
+template <typename real, int CW, bool RECOMPUTE, bool FAST, bool CLAMP, bool DERIVE>
+__global__ void __launch_bounds__(64, ECCKD_SW_WAVES_PER_SIMD) rte_sw_kernel(const RteSwArgs a) {
+  rte_sw_body<real, CW, RECOMPUTE, FAST, CLAMP, DERIVE>(a);
 }
 
 // Sums the per-group partial fluxes of the tail tiles in group order: the order in which a whole-tile wave adds the
@@ -337,12 +371,31 @@ size_t rte_sw_tail_plan(const RteSwArgs &a, long *tail_first, size_t *partials_a
   return *partials_at + part;
 }
 
+namespace {
+// The instantiations a call can take: fp64 in both arithmetic modes through the 4-parameter kernel; single precision in
+// both modes; the fused form (DERIVE) in the fast mode only (ecckd_sw_fluxes refuses reference-order arithmetic).
+typedef void (*RteSwKernel)(const RteSwArgs);
+template <typename real, bool DERIVE>
+RteSwKernel rte_sw_kernel_for(const RteSwArgs &a) {
+  constexpr int CW = ECCKD_SW_CW;
+  if constexpr (std::is_same<real, double>::value && !DERIVE)
+    return a.dir_clamp ? (a.exact_division ? rte_sw_kernel<CW, kSwRecompute, false, true> : rte_sw_kernel<CW, kSwRecompute, true, true>)
+                       : (a.exact_division ? rte_sw_kernel<CW, kSwRecompute, false, false> : rte_sw_kernel<CW, kSwRecompute, true, false>);
+  else if constexpr (DERIVE)
+    return a.exact_division ? nullptr
+                            : (a.dir_clamp ? rte_sw_kernel<real, CW, kSwRecompute, true, true, true> : rte_sw_kernel<real, CW, kSwRecompute, true, false, true>);
+  else
+    return a.dir_clamp ? (a.exact_division ? rte_sw_kernel<real, CW, kSwRecompute, false, true, false> : rte_sw_kernel<real, CW, kSwRecompute, true, true, false>)
+                       : (a.exact_division ? rte_sw_kernel<real, CW, kSwRecompute, false, false, false> : rte_sw_kernel<real, CW, kSwRecompute, true, false, false>);
+}
+}  // namespace
+
 hipError_t launch_rte_sw(const RteSwArgs &a, hipStream_t s) {
   if (a.ncol <= 0) return hipSuccess;
-  if (a.f32 || a.derive) return hipErrorInvalidValue;   // single precision / fused form: layer-systolic solver only
   constexpr int CW = ECCKD_SW_CW;
-  auto k = a.dir_clamp ? (a.exact_division ? rte_sw_kernel<CW, kSwRecompute, false, true> : rte_sw_kernel<CW, kSwRecompute, true, true>)
-                       : (a.exact_division ? rte_sw_kernel<CW, kSwRecompute, false, false> : rte_sw_kernel<CW, kSwRecompute, true, false>);
+  auto k = a.f32 ? (a.derive ? rte_sw_kernel_for<float, true>(a) : rte_sw_kernel_for<float, false>(a))
+                 : (a.derive ? rte_sw_kernel_for<double, true>(a) : rte_sw_kernel_for<double, false>(a));
+  if (!k) return hipErrorInvalidValue;
   const size_t lds = sizeof(double) * 3 * (size_t)(a.nlay + 1) * CW;
   if (lds > (size_t)kLdsBudget) return hipErrorInvalidValue;
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k),

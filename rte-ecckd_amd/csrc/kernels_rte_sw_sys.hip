@@ -3,9 +3,12 @@
 //
 // Replaces RTE-RRTMGP's rte_sw as the reference calls it (example/rfmip-rad-irf/ecckd_rfmip_sw.F90:148-154):
 // sw_two_stream, sw_source_2str, adding, flux_dn = diffuse + direct, ty_fluxes_broadband%reduce
-// [RTE-ext: SURVEY.md Appendix B.2].  Same arithmetic per (column, g-point) as kernels_rte_sw.hip -- same
-// expressions in the same order, shared sw_two_stream.hpp -- so a (column, g-point) pair gets the same bits from
-// either kernel; the g-point sum is taken in g-point order 1..ngpt here (what sum_broadband does).
+// [RTE-ext: SURVEY.md Appendix B.2].  The two-stream coefficients are those of kernels_rte_sw.hip (shared
+// sw_two_stream.hpp).  In the reference-order arithmetic mode the adding recurrences are the same expressions in the
+// same order too, so a (column, g-point) pair gets the same bits from either kernel.  In the fast mode the U sweep
+// hands its pair on in a division-free (projective) form and the sweeps use FMA chains (ECCKD_SYS_PROJ,
+// ECCKD_SYS_FMA_CHAIN below): the two kernels then agree to the last bits only.  The g-point sum is taken in g-point
+// order 1..ngpt here (what sum_broadband does).
 //
 // Why another form.  The adding method needs the coefficients of every layer twice, bottom -> top (albedo and
 // source of the stack below) and top -> bottom (fluxes).  kernels_rte_sw.hip gives a lane one (column, g-point) and

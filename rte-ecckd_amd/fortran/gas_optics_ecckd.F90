@@ -551,7 +551,8 @@ contains
   !! loop computes with ecckd%gas_optics(...), the rescaling of toa_flux and rte_sw(...) (ecckd_rfmip_sw.F90:118-154) --
   !! through the fused path of the library (ecckd_sw_fluxes: only the total optical depth goes through GPU memory; the
   !! solver derives ssa, g = 0 and the incoming beam as gas_optics_ext does, src/gas_optics_ecckd.f90:455-472).  Host
-  !! arrays in, host fluxes out; at most 60 layers.  flux_* are (ncol, nlay+1), the albedos (nband, ncol); toa_scale(ncol)
+  !! arrays in, host fluxes out; any layer count (the solver rte_sw takes for the shape: layer-systolic up to 60 layers,
+  !! two-pass beyond).  flux_* are (ncol, nlay+1), the albedos (nband, ncol); toa_scale(ncol)
   !! multiplies the incoming beam of a column (the drivers' total-solar-irradiance rescaling); flux_dir is optional.
   function sw_fluxes(this, plev, tlay, gas_desc, top_at_1, mu0, sfc_alb_dir, sfc_alb_dif, flux_up, flux_dn, flux_dir, toa_scale) &
       result(error_msg)
