@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import helpers
+from helpers import edge_columns, orography_ramp
 from conftest import LW_FSCK, LW_RRTMGP, SW_WIDE
 from rte_ecckd_amd import synthetic
 
@@ -33,25 +34,6 @@ def lw(pkg, gpu, oracle_mod):
     return k, oracle_mod.CkdModel(LW_FSCK)
 
 
-def edge_columns(press_min, ncol=96):
-    """Synthetic columns pushed through every branch of the gas optics."""
-    c = synthetic.columns(1000, ncol, press_min)
-    c = {k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in c.items()}
-    c["h2o"][:, 0:8] = 1e-9                       # below the first h2o LUT node
-    c["h2o"][:, 8:12] = 0.2                       # above the last node
-    c["ch4"][12:20] = 1e-7                        # below reference -> negative -> clamped
-    c["n2o"][12:20] = 1e-8
-    c["tlev"][:, 20:24] = 100.0; c["tlay"][:, 20:24] = 100.0; c["tsfc"][20:24] = 110.0   # below Planck table
-    c["tlev"][:, 24:28] = 400.0; c["tlay"][:, 24:28] = 400.0; c["tsfc"][24:28] = 360.0   # above it (extrapolates)
-    c["plev"][:, 28:32] *= 1e-3                   # far below the pressure grid
-    c["plev"][:, 32:36] *= 3.0                    # above it
-    c["plev"][:, 36:40] *= np.linspace(0.3, 1.0, 4)[None, :]   # wide pressure spread inside one tile
-    c["tlay"][:, 40:44] += 80.0                   # outside the 6-node T grid
-    c["tlay"][:, 44:48] -= 80.0
-    c["cfc11"][48:52] = 0.0
-    return c
-
-
 def check_lw(pkg, k, m, oracle_mod, cols, device, names=None, overrides=None):
     err, tau, lay, inc, dec, sfc = helpers.run_lw_gas_optics(pkg, k, cols, device, names, overrides)
     assert err == ""
@@ -74,19 +56,6 @@ def test_lw_gas_optics_ragged_sizes(pkg, gpu, oracle_mod, lw, ncol):
 def test_lw_gas_optics_edge_branches(pkg, gpu, oracle_mod, lw):
     k, m = lw
     check_lw(pkg, k, m, oracle_mod, edge_columns(k.get_press_min()), gpu)
-
-
-def orography_ramp(press_min, ncol=2048, c0=40):
-    """Surface pressure ramps smoothly from 50 to 103 kPa across the columns: at the lower layers a
-    4096-column segment spans more pressure rows than the LDS slab holds, so the fused kernel walks it once
-    per slab position; most waves sit in one position, a few straddle two."""
-    c = synthetic.columns(c0, ncol, press_min)
-    c = {k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in c.items()}
-    ps = np.linspace(50000.0, 103000.0, ncol)
-    eta = (np.arange(61, dtype=np.float64) / 60) ** 2
-    ptop = c["plev"][0, 0]
-    c["plev"] = np.ascontiguousarray(ptop + (ps[None, :] - ptop) * eta[:, None])
-    return c
 
 
 @pytest.mark.parametrize("ncol", [2048, 3000])

@@ -12,6 +12,7 @@ import threading
 import numpy as np
 import pytest
 
+from helpers import SW_NAMES   # (test_gpu_sw_any_depth imports it from here)
 from test_gpu_round2 import T, FLUX_ATOL
 
 pytestmark = pytest.mark.gpu
@@ -204,7 +205,6 @@ def test_host_threads_share_the_solver_scratch(pkg, gpu, oracle_mod):
 # ------------------------------------------------------------------------------------------------
 # fused shortwave path (ecckd_sw_fluxes), single precision outside the longwave fused path
 # ------------------------------------------------------------------------------------------------
-SW_NAMES = ["co2", "ch4", "n2o", "o2", "h2o", "o3"]
 
 
 @pytest.fixture(scope="module")
