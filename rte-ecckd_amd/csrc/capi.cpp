@@ -6,6 +6,7 @@
 
 #include <atomic>
 #include <cmath>
+#include <cstdint>
 #include <cstdlib>
 #include <cstring>
 #include <map>
@@ -182,32 +183,40 @@ int simd_slots(int device) {
 
 size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
 
-// Single precision: the *_f32 entry points set this for the duration of the call; every staging
-// helper below sizes its copies with esz() and the kernels are launched with f32 = 1.  Data pointers
-// keep their `double *` static type on the way through (they are only passed on, never indexed).
-thread_local int g_f32 = 0;
-thread_local int g_shared_levels = 0;
-thread_local const double *g_inc_flux = nullptr;   // set by ecckd_rte_lw_inc_flux around ecckd_rte_lw
-// set by the *_byband entry points around the per-band solver calls: band of every g-point of the sub-range
-thread_local int g_band_override = -1;
-// set by ecckd_sw_fluxes around ecckd_rte_sw: the solver derives ssa / g / toa itself (RteSwArgs::derive)
-struct SwDerive { const double *plev, *rayleigh, *solar, *toa_scale; double gw; };
-thread_local const SwDerive *g_sw_derive = nullptr;
-// ... and the solver's room inside ecckd_sw_fluxes' own scratch block (sw_fluxes_solver_bytes): the partial sums of the
-// layer-systolic solver, or the scratch ring of the two-pass solver with its partial sums behind it
-thread_local double *g_sw_scratch = nullptr;
-// ecckd_gas_optics_plan(): when set, gas_optical_depth_dev() records its decisions here and launches nothing
+// Single precision: the *_f32 entry points cast their float pointers to `double *` (dp) and pass f32 = true down;
+// every staging helper below takes that flag to size its copies and the kernels are launched with f32 = 1.  Data
+// pointers keep their `double *` static type on the way through (they are only passed on, never indexed).
+size_t esz(bool f32) { return f32 ? sizeof(float) : sizeof(double); }
+inline const double *dp(const float *p) { return reinterpret_cast<const double *>(p); }
+inline double *dp(float *p) { return reinterpret_cast<double *>(p); }
+
+// ecckd_sw_fluxes: the shortwave solver derives ssa / g / toa itself (RteSwArgs::derive) and works in `room` inside
+// ecckd_sw_fluxes' own scratch block (sw_fluxes_solver_bytes): the partial sums of the layer-systolic solver, or the
+// scratch ring of the two-pass solver with its partial sums behind it
+struct SwDerive { const double *plev, *rayleigh, *solar, *toa_scale; double gw; double *room; };
+// What a public entry point asks of the solver implementations besides its arguments.
+struct Call {
+  bool f32 = false;
+  int band = -1;                      // the per-band solvers: band of every g-point of the sub-range (else band2gpt)
+  bool shared_levels = false;         // ecckd_rte_lw_shared_levels
+  const SwDerive *derive = nullptr;   // ecckd_sw_fluxes
+};
+// ecckd_gas_optics_plan(): gas_optical_depth_dev() given one records its decisions here and launches nothing
 struct PlanRecord {
   const int *is_scalar = nullptr;   // per gas of the list: its mole fraction would be passed as one number
   int npass = 0, first_fused = 0, planck_fused = 0;
   ecckd::FusedPlan first;
 };
-thread_local PlanRecord *g_plan = nullptr;
-size_t esz() { return g_f32 ? sizeof(float) : sizeof(double); }
-struct F32Scope {
-  F32Scope() { g_f32 = 1; }
-  ~F32Scope() { g_f32 = 0; }
-};
+
+// :107 / :314  1./(gravity*0.001*dry_air_molar_mass) with default-real literals (:51-52); with wp = float in single
+// precision
+double gw(bool f32) {
+  return f32 ? (double)(1.f / (9.80665f * 0.001f * 28.970f)) : 1. / ((double)9.80665f * (double)0.001f * (double)28.970f);
+}
+// the model table at `off` (in elements), in the fp64 image or its float32 copy
+const double *table(const ecckd_model *m, size_t off, bool f32) {
+  return f32 ? reinterpret_cast<const double *>(m->dbuf32 + off) : m->dbuf + off;
+}
 
 // Arithmetic mode (ecckd_set_arithmetic): 0 = fast (fused kernel, re-associated FMAs),
 // 1 = reference order (kernels_tau.hip + kernels_planck.hip, bit-faithful expression order).
@@ -239,6 +248,12 @@ struct SolverOptions {
 };
 SolverOptions g_opt;
 
+// lw_tau_thresh in effect: the option, or sqrt(epsilon(1._wp)) of the working precision
+double lw_tau_thresh(bool f32) {
+  const double t = g_opt.lw_tau_thresh.load();
+  return t > 0. ? t : (f32 ? std::sqrt(1.1920928955078125e-07) : std::sqrt(2.220446049250313e-16));
+}
+
 // ---- optional per-kernel timing with HIP events on the launch stream (ecckd_prof_*) ----
 struct ProfRec { const char *name; hipEvent_t start, stop; };
 std::mutex g_prof_mu;
@@ -266,11 +281,12 @@ struct ProfScope {
 // Bump allocator over an Arena block.
 struct Bump {
   char *base;
+  size_t es;   // element size: esz()
   size_t off = 0;
-  explicit Bump(void *b) : base(static_cast<char *>(b)) {}
+  Bump(void *b, bool f32) : base(static_cast<char *>(b)), es(esz(f32)) {}
   double *take(size_t nelem) {
     double *r = reinterpret_cast<double *>(base + off);
-    off += align256(nelem * esz());
+    off += align256(nelem * es);
     return r;
   }
 };
@@ -295,10 +311,34 @@ struct PlanckSide {
   double *lay_source, *lev_inc, *lev_dec, *sfc_source;
 };
 
+// Planck kernel arguments (fp64) for the sources of `pl`
+ecckd::PlanckArgs planck_args(const ecckd_model *m, int ncol, int nlay, const double *tlay, const PlanckSide &pl) {
+  ecckd::PlanckArgs p{};
+  p.ncol = ncol; p.nlay = nlay; p.ng = m->ng; p.ntp = m->ntp;
+  p.planck = m->dbuf + m->off_planck;
+  p.t0 = m->temperature_planck[0];                                  // :272
+  p.dt = m->temperature_planck[1] - m->temperature_planck[0];      // :271
+  p.tlay = tlay; p.tlev = pl.tlev; p.tsfc = pl.tsfc;
+  p.lay_source = pl.lay_source; p.lev_source_inc = pl.lev_inc; p.lev_source_dec = pl.lev_dec;
+  p.sfc_source = pl.sfc_source;
+  return p;
+}
+
+// :407-424 on device pointers; the fast arithmetic mode takes the kernel with paired 16-byte stores (same bits)
+int planck_sources_dev(const ecckd_model *m, int ncol, int nlay, const double *tlay, const PlanckSide &pl,
+                       hipStream_t stream) {
+  ecckd::PlanckArgs p = planck_args(m, ncol, nlay, tlay, pl);
+  ProfScope prof("planck", stream);
+  if (g_arith.load() == 0) HIPCHK(ecckd::launch_planck_pair(p, 0, stream));
+  else HIPCHK(ecckd::launch_planck(p, stream));
+  return 0;
+}
+
 // gas_optical_depth (src/gas_optics_ecckd.f90:323-376) on device pointers.  `sw` selects the
 // gas_optics_ext epilogue (:455-460).  When `pl` is given and the fast arithmetic mode is on, the
-// Planck sources (:407-424) are produced by the same launch and *planck_done is set.
-int gas_optical_depth_dev(const ecckd_model *m, int ncol, int nlay, const double *plev,
+// Planck sources (:407-424) are produced by the same launch and *planck_done is set.  With `plan`
+// given, the decisions are recorded there and nothing is launched.
+int gas_optical_depth_dev(const ecckd_model *m, bool f32, PlanRecord *plan, int ncol, int nlay, const double *plev,
                           const double *tlay, const GasDesc &gd, double *tau, bool sw, double *ssa,
                           double *g, const PlanckSide *pl, bool *planck_done, hipStream_t stream) {
   using namespace ecckd;
@@ -314,13 +354,13 @@ int gas_optical_depth_dev(const ecckd_model *m, int ncol, int nlay, const double
     const ecckd_model::Gas &t = m->gas[i];
     if (t.composite_only && !first_calc) continue;   // :365-367
     SeqGas e{};
-    e.coef = g_f32 ? reinterpret_cast<const double *>(m->dbuf32 + t.dev_off) : m->dbuf + t.dev_off;
+    e.coef = table(m, t.dev_off, f32);
     e.vmr = gd.vmr ? gd.vmr[j] : nullptr;
     e.cs = gd.cs ? gd.cs[j] : 0;
     e.ls = gd.ls ? gd.ls[j] : 0;
     e.scalar = gd.scalar ? gd.scalar[j] : 0.;
-    if (g_plan) {   // no data in a plan call: an array gas gets a (never dereferenced) non-null marker, a scalar one 1.0
-      const bool sc = g_plan->is_scalar && g_plan->is_scalar[j];
+    if (plan) {   // no data in a plan call: an array gas gets a (never dereferenced) non-null marker, a scalar one 1.0
+      const bool sc = plan->is_scalar && plan->is_scalar[j];
       e.vmr = sc ? nullptr : reinterpret_cast<const double *>(sizeof(double));
       e.scalar = 1.;
     }
@@ -348,14 +388,12 @@ int gas_optical_depth_dev(const ecckd_model *m, int ncol, int nlay, const double
     TauArgs &a = fa.tau;
     a.ncol = ncol; a.nlay = nlay; a.ng = m->ng; a.np = m->np; a.nt = m->nt;
     a.plev = plev; a.tlay = tlay;
-    a.temperature = g_f32 ? reinterpret_cast<const double *>(m->dbuf32 + m->off_temperature) : m->dbuf + m->off_temperature;
-    a.zero = g_f32 ? reinterpret_cast<const double *>(m->dbuf32 + m->off_zero) : m->dbuf + m->off_zero;
+    a.temperature = table(m, m->off_temperature, f32);
+    a.zero = table(m, m->off_zero, f32);
     a.lp0 = m->log_pressure[0];                               // :104
     a.dlp = m->log_pressure[1] - m->log_pressure[0];          // :105
     a.dt = m->temperature[m->np] - m->temperature[0];         // :106 T(1,2)-T(1,1)
-    // :107  1./(gravity*0.001*dry_air_molar_mass) with default-real literals (:51-52)
-    a.gw = 1. / ((double)9.80665f * (double)0.001f * (double)28.970f);
-    if (g_f32) a.gw = (double)(1.f / (9.80665f * 0.001f * 28.970f));   // the same expression with wp = float
+    a.gw = gw(f32);                                           // :107
     a.lut = -1;
     a.merge_slot = -1;
     a.nmerge = 0;
@@ -378,24 +416,24 @@ int gas_optical_depth_dev(const ecckd_model *m, int ncol, int nlay, const double
     a.tau = tau;
     const bool last = pos >= seq.size();
     if (sw && last) {
-      a.rayleigh = g_f32 ? reinterpret_cast<const double *>(m->dbuf32 + m->off_rayleigh) : m->dbuf + m->off_rayleigh;
+      a.rayleigh = table(m, m->off_rayleigh, f32);
       a.ssa = ssa;
       a.g = g;
     }
     if (fast) {
       fa.mode = (sw && last) ? 2 : 0;
       // (fp64 only: in single precision the two-slot instantiation measured 5 % slower than the seven-slot one it replaces)
-      if (g_opt.gas_merge_scalars.load() && !g_f32) merge_scalar_gases(a, g_f32);
+      if (g_opt.gas_merge_scalars.load() && !f32) merge_scalar_gases(a, f32);
       const int nv_lut = a.lut >= 0 ? a.seq[a.lut].nv : 0;
       // Planck sources ride along with the first pass when the table, or a window of it, fits next
       // to >= 3 slab rows
       int pass_clamp = 0;
       for (int k = 0; k < a.nseq; ++k) pass_clamp |= a.seq[k].clamp;
       if (pl && first_pass && !sw &&
-          fused_planck_rows(a.ng, a.np, a.nt, a.nbil, nv_lut, m->ntp, pass_clamp, g_f32) > 0) {
+          fused_planck_rows(a.ng, a.np, a.nt, a.nbil, nv_lut, m->ntp, pass_clamp, f32) > 0) {
         fa.mode = 1;
         fa.ntp = m->ntp;
-        fa.planck = g_f32 ? reinterpret_cast<const double *>(m->dbuf32 + m->off_planck) : m->dbuf + m->off_planck;
+        fa.planck = table(m, m->off_planck, f32);
         fa.pt0 = m->temperature_planck[0];                                  // :272
         fa.pdt = m->temperature_planck[1] - m->temperature_planck[0];      // :271
         fa.tlev = pl->tlev; fa.tsfc = pl->tsfc;
@@ -403,28 +441,28 @@ int gas_optical_depth_dev(const ecckd_model *m, int ncol, int nlay, const double
         fa.lev_source_dec = pl->lev_dec; fa.sfc_source = pl->sfc_source;
         if (planck_done) *planck_done = true;
       }
-      fa.f32 = g_f32;
+      fa.f32 = f32;
       // fp64 over the float32 image of the tables in LDS ("gas_slab_f32": 0 never, 1 always, 2 where the probe finds the
       // columns spread over many pressure rows); the probe's counter is a word that belongs to this stream
       ScratchLease flag_lease;
-      fa.slab32 = (!g_f32 && !g_plan && m->f32_exact && fa.mode == 1) ? g_opt.gas_slab_f32.load() : 0;
+      fa.slab32 = (!f32 && !plan && m->f32_exact && fa.mode == 1) ? g_opt.gas_slab_f32.load() : 0;
       if (fa.slab32 == 2) fa.choose_buf = static_cast<int *>(stream_scratch_optional(m->device, stream, 256, flag_lease, g_flag_pool));
-      if (g_f32 && ((fa.mode != 1 && fa.mode != 2) || !last || !first_pass))
+      if (f32 && ((fa.mode != 1 && fa.mode != 2) || !last || !first_pass))
         return fail("ecckd: single precision is implemented for one-pass gas optics (fused longwave, shortwave); this "
                     "model / gas list needs the multi-pass or unfused path");
-      if (g_plan) {
+      if (plan) {
         FusedPlan fp;
         HIPCHK(prepare_gas_fused(fa, fp));
-        if (g_plan->npass == 0) { g_plan->first_fused = 1; g_plan->planck_fused = fa.mode == 1; g_plan->first = fp; }
-        ++g_plan->npass;
+        if (plan->npass == 0) { plan->first_fused = 1; plan->planck_fused = fa.mode == 1; plan->first = fp; }
+        ++plan->npass;
       } else {
-        ProfScope prof(fa.mode == 1 ? (g_f32 ? "gas_lw_fused_f32" : "gas_lw_fused") : "tau", stream);
+        ProfScope prof(fa.mode == 1 ? (f32 ? "gas_lw_fused_f32" : "gas_lw_fused") : "tau", stream);
         HIPCHK(launch_gas_fused(fa, stream));
       }
     } else {
-      if (g_f32) return fail("ecckd: single precision needs the fast arithmetic mode (ecckd_set_arithmetic(0))");
-      if (g_plan) {
-        ++g_plan->npass;
+      if (f32) return fail("ecckd: single precision needs the fast arithmetic mode (ecckd_set_arithmetic(0))");
+      if (plan) {
+        ++plan->npass;
       } else {
         ProfScope prof("tau", stream);
         HIPCHK(launch_tau(a, stream));
@@ -459,9 +497,9 @@ struct StagedGases {
   std::vector<const double *> ptr;
   GasDesc gd;
 };
-size_t staged_gas_bytes(const GasDesc &gd, int ncol, int nlay) {
+size_t staged_gas_bytes(const GasDesc &gd, int ncol, int nlay, bool f32) {
   size_t b = 0;
-  for (int j = 0; j < gd.ngas; ++j) b += align256(vmr_extent(gd, j, ncol, nlay) * esz());
+  for (int j = 0; j < gd.ngas; ++j) b += align256(vmr_extent(gd, j, ncol, nlay) * esz(f32));
   return b;
 }
 int stage_gases(const GasDesc &gd, int ncol, int nlay, Bump &bump, hipStream_t s, StagedGases &out) {
@@ -470,7 +508,7 @@ int stage_gases(const GasDesc &gd, int ncol, int nlay, Bump &bump, hipStream_t s
     const size_t n = vmr_extent(gd, j, ncol, nlay);
     if (!n) continue;
     double *d = bump.take(n);
-    HIPCHK(hipMemcpyAsync(d, gd.vmr[j], n * esz(), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d, gd.vmr[j], n * bump.es, hipMemcpyHostToDevice, s));
     out.ptr[j] = d;
   }
   out.gd = gd;
@@ -478,14 +516,48 @@ int stage_gases(const GasDesc &gd, int ncol, int nlay, Bump &bump, hipStream_t s
   return 0;
 }
 
-int h2d(double *d, const double *h, size_t n, hipStream_t s) {
-  HIPCHK(hipMemcpyAsync(d, h, n * esz(), hipMemcpyHostToDevice, s));
+int h2d(double *d, const double *h, size_t n, bool f32, hipStream_t s) {
+  HIPCHK(hipMemcpyAsync(d, h, n * esz(f32), hipMemcpyHostToDevice, s));
   return 0;
 }
-int d2h(double *h, const double *d, size_t n, hipStream_t s) {
-  HIPCHK(hipMemcpyAsync(h, d, n * esz(), hipMemcpyDeviceToHost, s));
+int d2h(double *h, const double *d, size_t n, bool f32, hipStream_t s) {
+  HIPCHK(hipMemcpyAsync(h, d, n * esz(f32), hipMemcpyDeviceToHost, s));
   return 0;
 }
+
+// Grows the model's staging arena (caller holds m->mu); the host stream may still read the old block
+int grow_arena(ecckd_model *m, size_t need) {
+  if (need <= m->arena_bytes) return 0;
+  HIPCHK(hipStreamSynchronize(m->host_stream));
+  if (m->arena) { HIPCHK(hipFree(m->arena)); m->arena = nullptr; m->arena_bytes = 0; }
+  HIPCHK(hipMalloc(&m->arena, need));
+  m->arena_bytes = need;
+  return 0;
+}
+
+// out(:) = sum over planes of planes(:, b) on the host, in the precision of T
+template <class T> void sum_planes_host(const T *planes, int nplanes, size_t n, T *out) {
+  for (size_t i = 0; i < n; ++i) {
+    T acc = 0;
+    for (int b = 0; b < nplanes; ++b) acc += planes[(size_t)b * n + i];
+    out[i] = acc;
+  }
+}
+
+// out(:) = sum over planes of planes(:, b), on the device or on the host
+int sum_planes(const double *planes, int nplanes, size_t n, double *out, bool f32, int memspace, void *stream) {
+  if (memspace == ECCKD_DEVICE) {
+    HIPCHK(ecckd::launch_sum_planes(planes, nplanes, n, out, f32, static_cast<hipStream_t>(stream)));
+    return 0;
+  }
+  if (f32)   // (the single-precision flavours: float data behind the double pointers)
+    sum_planes_host(reinterpret_cast<const float *>(planes), nplanes, n, reinterpret_cast<float *>(out));
+  else
+    sum_planes_host(planes, nplanes, n, out);
+  return 0;
+}
+// p + n elements of the precision of the call (float data sits behind the double pointers of the _f32 flavours)
+template <class T> T *el(T *p, size_t n, bool f32) { return reinterpret_cast<T *>(reinterpret_cast<uintptr_t>(p) + n * esz(f32)); }
 
 int fill_band_map(int ngpt, int nband, const int *band2gpt, unsigned char *gpt2band) {
   if (ngpt < 1 || ngpt > 256) return fail("ecckd: ngpt must be in 1..256");
@@ -591,7 +663,7 @@ int ecckd_set_solver_option(const char *name, double value) {
 int ecckd_get_solver_option(const char *name, double *value) {
   if (!name || !value) return fail("ecckd_get_solver_option: null argument");
   const std::string n(name);
-  if (n == "lw_tau_thresh") { const double t = g_opt.lw_tau_thresh.load(); *value = t > 0. ? t : std::sqrt(2.220446049250313e-16); }
+  if (n == "lw_tau_thresh") *value = lw_tau_thresh(false);
   else if (n == "lw_series_terms") *value = g_opt.lw_series_terms.load();
   else if (n == "lw_inc_flux_isotropic") *value = g_opt.lw_inc_flux_isotropic.load();
   else if (n == "sw_k_floor") *value = g_opt.sw_k_floor.load();
@@ -920,31 +992,18 @@ int ecckd_model_get_device(const ecckd_model_t *m) { return m ? m->device : -1; 
 
 // ------------------------------------ gas optics -----------------------------------------
 
-static int gas_optics_lw_dev(const ecckd_model *m, int ncol, int nlay, const double *plev,
+static int gas_optics_lw_dev(const ecckd_model *m, bool f32, int ncol, int nlay, const double *plev,
                              const double *tlay, const double *tsfc, const double *tlev,
                              const GasDesc &gd, double *tau, double *lay_source, double *lev_inc,
                              double *lev_dec, double *sfc_source, hipStream_t stream) {
   const PlanckSide pl{tlev, tsfc, lay_source, lev_inc, lev_dec, sfc_source};
   bool planck_done = false;
-  if (gas_optical_depth_dev(m, ncol, nlay, plev, tlay, gd, tau, false, nullptr, nullptr, &pl, &planck_done, stream))
+  if (gas_optical_depth_dev(m, f32, nullptr, ncol, nlay, plev, tlay, gd, tau, false, nullptr, nullptr, &pl, &planck_done,
+                            stream))
     return 1;   // :401
   if (planck_done) return 0;
-  if (g_f32) return fail("ecckd: single precision is implemented for the fused longwave gas optics only");
-  ecckd::PlanckArgs p{};
-  p.ncol = ncol; p.nlay = nlay; p.ng = m->ng; p.ntp = m->ntp;
-  p.planck = m->dbuf + m->off_planck;
-  p.t0 = m->temperature_planck[0];                                  // :272
-  p.dt = m->temperature_planck[1] - m->temperature_planck[0];      // :271
-  p.tlay = tlay; p.tlev = tlev; p.tsfc = tsfc;
-  p.lay_source = lay_source; p.lev_source_inc = lev_inc; p.lev_source_dec = lev_dec;
-  p.sfc_source = sfc_source;
-  {
-    ProfScope prof("planck", stream);
-    // :407-424; the fast arithmetic mode takes the kernel with paired 16-byte stores (same bits)
-    if (g_arith.load() == 0) HIPCHK(ecckd::launch_planck_pair(p, 0, stream));
-    else HIPCHK(ecckd::launch_planck(p, stream));
-  }
-  return 0;
+  if (f32) return fail("ecckd: single precision is implemented for the fused longwave gas optics only");
+  return planck_sources_dev(m, ncol, nlay, tlay, pl, stream);
 }
 
 int ecckd_planck_sources(const ecckd_model_t *m, int ncol, int nlay, const double *tlay, const double *tlev,
@@ -957,18 +1016,8 @@ int ecckd_planck_sources(const ecckd_model_t *m, int ncol, int nlay, const doubl
   if (tlev && (!lev_source_inc || !lev_source_dec)) return fail("ecckd_planck_sources: null level sources");
   HIPCHK(hipSetDevice(m->device));
   if (ncol == 0) return 0;
-  ecckd::PlanckArgs p{};
-  p.ncol = ncol; p.nlay = nlay; p.ng = m->ng; p.ntp = m->ntp;
-  p.planck = m->dbuf + m->off_planck;
-  p.t0 = m->temperature_planck[0];                                  // :272
-  p.dt = m->temperature_planck[1] - m->temperature_planck[0];      // :271
-  p.tlay = tlay; p.tlev = tlev; p.tsfc = tsfc;
-  p.lay_source = lay_source; p.lev_source_inc = lev_source_inc; p.lev_source_dec = lev_source_dec;
-  p.sfc_source = sfc_source;
-  ProfScope prof("planck", static_cast<hipStream_t>(stream));
-  if (g_arith.load() == 0) HIPCHK(ecckd::launch_planck_pair(p, 0, static_cast<hipStream_t>(stream)));
-  else HIPCHK(ecckd::launch_planck(p, static_cast<hipStream_t>(stream)));
-  return 0;
+  const PlanckSide pl{tlev, tsfc, lay_source, lev_source_inc, lev_source_dec, sfc_source};
+  return planck_sources_dev(m, ncol, nlay, tlay, pl, static_cast<hipStream_t>(stream));
 }
 
 int ecckd_gas_optics_plan(const ecckd_model_t *m, int ncol, int nlay, int single_precision, int ngas,
@@ -992,13 +1041,9 @@ int ecckd_gas_optics_plan_ex(const ecckd_model_t *m, int ncol, int nlay, int sin
   const GasDesc gd{ngas, gas_names, nullptr, nullptr, nullptr, nullptr};
   const PlanckSide pl{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   const bool lw = m->has_planck;
-  struct Guard {
-    explicit Guard(PlanRecord *r, int f32) { g_plan = r; g_f32 = f32; }
-    ~Guard() { g_plan = nullptr; g_f32 = 0; }
-  } guard(&rec, single_precision ? 1 : 0);
   bool planck_done = false;
-  if (gas_optical_depth_dev(m, ncol, nlay, nullptr, nullptr, gd, nullptr, !lw, nullptr, nullptr, lw ? &pl : nullptr,
-                            &planck_done, nullptr))
+  if (gas_optical_depth_dev(m, single_precision != 0, &rec, ncol, nlay, nullptr, nullptr, gd, nullptr, !lw, nullptr,
+                            nullptr, lw ? &pl : nullptr, &planck_done, nullptr))
     return 1;
   plan[0] = rec.npass;
   plan[1] = rec.first_fused;
@@ -1014,13 +1059,11 @@ int ecckd_gas_optics_plan_ex(const ecckd_model_t *m, int ncol, int nlay, int sin
   return 0;
 }
 
-int ecckd_gas_optics_lw(const ecckd_model_t *m, int ncol, int nlay, const double *plev,
-                        const double *tlay, const double *tsfc, const double *tlev, int ngas,
-                        const char *gas_names, const double *const *vmr,
-                        const long long *vmr_col_stride, const long long *vmr_lay_stride,
-                        const double *vmr_scalar, double *tau, double *lay_source,
-                        double *lev_source_inc, double *lev_source_dec, double *sfc_source,
-                        int memspace, void *stream) {
+static int gas_optics_lw_impl(bool f32, const ecckd_model_t *m, int ncol, int nlay, const double *plev, const double *tlay,
+                              const double *tsfc, const double *tlev, int ngas, const char *gas_names,
+                              const double *const *vmr, const long long *vmr_col_stride, const long long *vmr_lay_stride,
+                              const double *vmr_scalar, double *tau, double *lay_source, double *lev_source_inc,
+                              double *lev_source_dec, double *sfc_source, int memspace, void *stream) {
   if (check_model(m) || check_gas_optics_dims(ncol, nlay)) return 1;
   if (!m->has_planck) return fail("ecckd_gas_optics_lw: model has no Planck table (shortwave model?)");
   if (!plev || !tlay || !tsfc || !tau || !lay_source || !sfc_source || (ngas > 0 && !gas_names))
@@ -1032,7 +1075,7 @@ int ecckd_gas_optics_lw(const ecckd_model_t *m, int ncol, int nlay, const double
   if (ncol == 0) return tlev ? 0 : fail("tlev is required for ecckd");
 
   if (memspace == ECCKD_DEVICE) {
-    if (gas_optics_lw_dev(m, ncol, nlay, plev, tlay, tsfc, tlev, gd, tau, lay_source, lev_source_inc,
+    if (gas_optics_lw_dev(m, f32, ncol, nlay, plev, tlay, tsfc, tlev, gd, tau, lay_source, lev_source_inc,
                           lev_source_dec, sfc_source, static_cast<hipStream_t>(stream)))
       return 1;
     return tlev ? 0 : fail("tlev is required for ecckd");   // :414-417
@@ -1045,19 +1088,15 @@ int ecckd_gas_optics_lw(const ecckd_model_t *m, int ncol, int nlay, const double
   ecckd_model *mm = const_cast<ecckd_model *>(m);
   std::lock_guard<std::mutex> lock(mm->mu);
   hipStream_t s = mm->host_stream;
-  size_t need = align256(n2l * esz()) * 2 + align256(n2 * esz()) + align256((size_t)ncol * esz()) +
-                staged_gas_bytes(gd, ncol, nlay);
-  if (!mixed) need += align256(n3 * esz()) * 4 + align256((size_t)ncol * m->ng * esz());
-  if (need > mm->arena_bytes) {
-    HIPCHK(hipStreamSynchronize(s));
-    if (mm->arena) { HIPCHK(hipFree(mm->arena)); mm->arena = nullptr; mm->arena_bytes = 0; }
-    HIPCHK(hipMalloc(&mm->arena, need));
-    mm->arena_bytes = need;
-  }
-  Bump b(mm->arena);
+  const size_t es = esz(f32);
+  size_t need = align256(n2l * es) * 2 + align256(n2 * es) + align256((size_t)ncol * es) +
+                staged_gas_bytes(gd, ncol, nlay, f32);
+  if (!mixed) need += align256(n3 * es) * 4 + align256((size_t)ncol * m->ng * es);
+  if (grow_arena(mm, need)) return 1;
+  Bump b(mm->arena, f32);
   double *d_plev = b.take(n2l), *d_tlev = b.take(n2l), *d_tlay = b.take(n2), *d_tsfc = b.take(ncol);
-  if (h2d(d_plev, plev, n2l, s) || h2d(d_tlay, tlay, n2, s) || h2d(d_tsfc, tsfc, ncol, s)) return 1;
-  if (tlev && h2d(d_tlev, tlev, n2l, s)) return 1;
+  if (h2d(d_plev, plev, n2l, f32, s) || h2d(d_tlay, tlay, n2, f32, s) || h2d(d_tsfc, tsfc, ncol, f32, s)) return 1;
+  if (tlev && h2d(d_tlev, tlev, n2l, f32, s)) return 1;
   StagedGases sg;
   if (stage_gases(gd, ncol, nlay, b, s, sg)) return 1;
   double *d_tau = tau, *d_lay = lay_source, *d_inc = lev_source_inc, *d_dec = lev_source_dec, *d_sfc = sfc_source;
@@ -1065,17 +1104,29 @@ int ecckd_gas_optics_lw(const ecckd_model_t *m, int ncol, int nlay, const double
     d_tau = b.take(n3); d_lay = b.take(n3); d_inc = b.take(n3); d_dec = b.take(n3);
     d_sfc = b.take((size_t)ncol * m->ng);
   }
-  if (gas_optics_lw_dev(m, ncol, nlay, d_plev, d_tlay, d_tsfc, tlev ? d_tlev : nullptr, sg.gd, d_tau,
+  if (gas_optics_lw_dev(m, f32, ncol, nlay, d_plev, d_tlay, d_tsfc, tlev ? d_tlev : nullptr, sg.gd, d_tau,
                         d_lay, d_inc, d_dec, d_sfc, s))
     return 1;
   if (!mixed) {
-    if (d2h(tau, d_tau, n3, s) || d2h(lay_source, d_lay, n3, s) ||
-        d2h(sfc_source, d_sfc, (size_t)ncol * m->ng, s))
+    if (d2h(tau, d_tau, n3, f32, s) || d2h(lay_source, d_lay, n3, f32, s) ||
+        d2h(sfc_source, d_sfc, (size_t)ncol * m->ng, f32, s))
       return 1;
-    if (tlev && (d2h(lev_source_inc, d_inc, n3, s) || d2h(lev_source_dec, d_dec, n3, s))) return 1;
+    if (tlev && (d2h(lev_source_inc, d_inc, n3, f32, s) || d2h(lev_source_dec, d_dec, n3, f32, s))) return 1;
   }
   HIPCHK(hipStreamSynchronize(s));   // (mixed too: the solver call that follows runs on another stream)
   return tlev ? 0 : fail("tlev is required for ecckd");
+}
+
+int ecckd_gas_optics_lw(const ecckd_model_t *m, int ncol, int nlay, const double *plev,
+                        const double *tlay, const double *tsfc, const double *tlev, int ngas,
+                        const char *gas_names, const double *const *vmr,
+                        const long long *vmr_col_stride, const long long *vmr_lay_stride,
+                        const double *vmr_scalar, double *tau, double *lay_source,
+                        double *lev_source_inc, double *lev_source_dec, double *sfc_source,
+                        int memspace, void *stream) {
+  return gas_optics_lw_impl(false, m, ncol, nlay, plev, tlay, tsfc, tlev, ngas, gas_names, vmr, vmr_col_stride,
+                            vmr_lay_stride, vmr_scalar, tau, lay_source, lev_source_inc, lev_source_dec, sfc_source,
+                            memspace, stream);
 }
 
 int ecckd_gas_optics_lw_f32(const ecckd_model_t *m, int ncol, int nlay, const float *plev, const float *tlay,
@@ -1084,33 +1135,28 @@ int ecckd_gas_optics_lw_f32(const ecckd_model_t *m, int ncol, int nlay, const fl
                             const long long *vmr_lay_stride, const double *vmr_scalar, float *tau,
                             float *lay_source, float *lev_source_inc, float *lev_source_dec,
                             float *sfc_source, int memspace, void *stream) {
-  F32Scope scope;
-  auto c = [](const float *p) { return reinterpret_cast<const double *>(p); };
-  auto w = [](float *p) { return reinterpret_cast<double *>(p); };
-  return ecckd_gas_optics_lw(m, ncol, nlay, c(plev), c(tlay), c(tsfc), c(tlev), ngas, gas_names,
-                             reinterpret_cast<const double *const *>(vmr), vmr_col_stride, vmr_lay_stride,
-                             vmr_scalar, w(tau), w(lay_source), w(lev_source_inc), w(lev_source_dec),
-                             w(sfc_source), memspace, stream);
+  return gas_optics_lw_impl(true, m, ncol, nlay, dp(plev), dp(tlay), dp(tsfc), dp(tlev), ngas, gas_names,
+                            reinterpret_cast<const double *const *>(vmr), vmr_col_stride, vmr_lay_stride, vmr_scalar,
+                            dp(tau), dp(lay_source), dp(lev_source_inc), dp(lev_source_dec), dp(sfc_source), memspace,
+                            stream);
 }
 
-static int gas_optics_sw_dev(const ecckd_model *m, int ncol, int nlay, const double *plev,
+static int gas_optics_sw_dev(const ecckd_model *m, bool f32, int ncol, int nlay, const double *plev,
                              const double *tlay, const GasDesc &gd, double *tau, double *ssa,
                              double *g, double *toa_src, hipStream_t stream) {
   const bool two_stream = ssa && g;
-  if (gas_optical_depth_dev(m, ncol, nlay, plev, tlay, gd, tau, true, two_stream ? ssa : nullptr,
+  if (gas_optical_depth_dev(m, f32, nullptr, ncol, nlay, plev, tlay, gd, tau, true, two_stream ? ssa : nullptr,
                             two_stream ? g : nullptr, nullptr, nullptr, stream))   // :449-460
     return 1;
   if (!two_stream) return 0;   // caller reports :461-463 after tau has been written
-  HIPCHK(ecckd::launch_toa_src(g_f32 ? reinterpret_cast<const double *>(m->dbuf32 + m->off_solar) : m->dbuf + m->off_solar, ncol,
-                               m->ng, toa_src, g_f32, stream));   // :468-472
+  HIPCHK(ecckd::launch_toa_src(table(m, m->off_solar, f32), ncol, m->ng, toa_src, f32, stream));   // :468-472
   return 0;
 }
 
-int ecckd_gas_optics_sw(const ecckd_model_t *m, int ncol, int nlay, const double *plev,
-                        const double *tlay, int ngas, const char *gas_names,
-                        const double *const *vmr, const long long *vmr_col_stride,
-                        const long long *vmr_lay_stride, const double *vmr_scalar, double *tau,
-                        double *ssa, double *g, double *toa_src, int memspace, void *stream) {
+static int gas_optics_sw_impl(bool f32, const ecckd_model_t *m, int ncol, int nlay, const double *plev, const double *tlay,
+                              int ngas, const char *gas_names, const double *const *vmr, const long long *vmr_col_stride,
+                              const long long *vmr_lay_stride, const double *vmr_scalar, double *tau, double *ssa,
+                              double *g, double *toa_src, int memspace, void *stream) {
   if (check_model(m) || check_gas_optics_dims(ncol, nlay)) return 1;
   if (!m->has_solar) return fail("ecckd_gas_optics_sw: model has no solar table (longwave model?)");
   if (!plev || !tlay || !tau || (ngas > 0 && !gas_names)) return fail("ecckd_gas_optics_sw: null argument");
@@ -1123,7 +1169,7 @@ int ecckd_gas_optics_sw(const ecckd_model_t *m, int ncol, int nlay, const double
   if (ncol == 0) return two_stream ? 0 : fail(kNot2str);
 
   if (memspace == ECCKD_DEVICE) {
-    if (gas_optics_sw_dev(m, ncol, nlay, plev, tlay, gd, tau, ssa, g, toa_src, static_cast<hipStream_t>(stream)))
+    if (gas_optics_sw_dev(m, f32, ncol, nlay, plev, tlay, gd, tau, ssa, g, toa_src, static_cast<hipStream_t>(stream)))
       return 1;
     return two_stream ? 0 : fail(kNot2str);
   }
@@ -1133,33 +1179,47 @@ int ecckd_gas_optics_sw(const ecckd_model_t *m, int ncol, int nlay, const double
   ecckd_model *mm = const_cast<ecckd_model *>(m);
   std::lock_guard<std::mutex> lock(mm->mu);
   hipStream_t s = mm->host_stream;
-  size_t need = align256(n2l * esz()) + align256(n2 * esz()) + staged_gas_bytes(gd, ncol, nlay) +
-                align256((size_t)ncol * m->ng * esz());
-  if (!mixed) need += align256(n3 * esz()) * 3;
-  if (need > mm->arena_bytes) {
-    HIPCHK(hipStreamSynchronize(s));
-    if (mm->arena) { HIPCHK(hipFree(mm->arena)); mm->arena = nullptr; mm->arena_bytes = 0; }
-    HIPCHK(hipMalloc(&mm->arena, need));
-    mm->arena_bytes = need;
-  }
-  Bump b(mm->arena);
+  const size_t es = esz(f32);
+  size_t need = align256(n2l * es) + align256(n2 * es) + staged_gas_bytes(gd, ncol, nlay, f32) +
+                align256((size_t)ncol * m->ng * es);
+  if (!mixed) need += align256(n3 * es) * 3;
+  if (grow_arena(mm, need)) return 1;
+  Bump b(mm->arena, f32);
   double *d_plev = b.take(n2l), *d_tlay = b.take(n2);
-  if (h2d(d_plev, plev, n2l, s) || h2d(d_tlay, tlay, n2, s)) return 1;
+  if (h2d(d_plev, plev, n2l, f32, s) || h2d(d_tlay, tlay, n2, f32, s)) return 1;
   StagedGases sg;
   if (stage_gases(gd, ncol, nlay, b, s, sg)) return 1;
   double *d_toa = b.take((size_t)ncol * m->ng);
   double *d_tau = tau, *d_ssa = ssa, *d_g = g;
   if (!mixed) { d_tau = b.take(n3); d_ssa = b.take(n3); d_g = b.take(n3); }
-  if (gas_optics_sw_dev(m, ncol, nlay, d_plev, d_tlay, sg.gd, d_tau, two_stream ? d_ssa : nullptr,
+  if (gas_optics_sw_dev(m, f32, ncol, nlay, d_plev, d_tlay, sg.gd, d_tau, two_stream ? d_ssa : nullptr,
                         two_stream ? d_g : nullptr, d_toa, s))
     return 1;
   if (!mixed) {
-    if (d2h(tau, d_tau, n3, s)) return 1;
-    if (two_stream && (d2h(ssa, d_ssa, n3, s) || d2h(g, d_g, n3, s))) return 1;
+    if (d2h(tau, d_tau, n3, f32, s)) return 1;
+    if (two_stream && (d2h(ssa, d_ssa, n3, f32, s) || d2h(g, d_g, n3, f32, s))) return 1;
   }
-  if (two_stream && d2h(toa_src, d_toa, (size_t)ncol * m->ng, s)) return 1;
+  if (two_stream && d2h(toa_src, d_toa, (size_t)ncol * m->ng, f32, s)) return 1;
   HIPCHK(hipStreamSynchronize(s));
   return two_stream ? 0 : fail(kNot2str);
+}
+
+int ecckd_gas_optics_sw(const ecckd_model_t *m, int ncol, int nlay, const double *plev,
+                        const double *tlay, int ngas, const char *gas_names,
+                        const double *const *vmr, const long long *vmr_col_stride,
+                        const long long *vmr_lay_stride, const double *vmr_scalar, double *tau,
+                        double *ssa, double *g, double *toa_src, int memspace, void *stream) {
+  return gas_optics_sw_impl(false, m, ncol, nlay, plev, tlay, ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride,
+                            vmr_scalar, tau, ssa, g, toa_src, memspace, stream);
+}
+
+int ecckd_gas_optics_sw_f32(const ecckd_model_t *m, int ncol, int nlay, const float *plev, const float *tlay, int ngas,
+                            const char *gas_names, const float *const *vmr, const long long *vmr_col_stride,
+                            const long long *vmr_lay_stride, const double *vmr_scalar, float *tau, float *ssa, float *g,
+                            float *toa_src, int memspace, void *stream) {
+  return gas_optics_sw_impl(true, m, ncol, nlay, dp(plev), dp(tlay), ngas, gas_names,
+                            reinterpret_cast<const double *const *>(vmr), vmr_col_stride, vmr_lay_stride, vmr_scalar,
+                            dp(tau), dp(ssa), dp(g), dp(toa_src), memspace, stream);
 }
 
 // -------------------------------------- solvers ------------------------------------------
@@ -1175,6 +1235,20 @@ static const double kGaussWts[4][4] = {{0.5, 0., 0., 0.},
                                        {0.2009319137, 0.2292411064, 0.0698269799, 0.},
                                        {0.1355069134, 0.2034645680, 0.1298475476, 0.0311809710}};
 
+// The longwave solver's switches (ecckd_set_solver_option) and its n_gauss_angles quadrature angles
+static void fill_lw_options(ecckd::RteLwArgs &a, int n_gauss_angles, bool f32) {
+  a.nmus = n_gauss_angles;
+  a.tau_thresh = lw_tau_thresh(f32);
+  a.series3 = g_opt.lw_series_terms.load() == 3;
+  a.inc_isotropic = g_opt.lw_inc_flux_isotropic.load();
+  a.use_split = g_opt.lw_solver.load();
+  a.split_seg = g_opt.lw_split_seg.load();
+  for (int k = 0; k < n_gauss_angles; ++k) {
+    a.Ds[k] = kGaussDs[n_gauss_angles - 1][k];
+    a.wts[k] = kGaussWts[n_gauss_angles - 1][k];
+  }
+}
+
 static int check_device(int device) {
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
@@ -1184,36 +1258,24 @@ static int check_device(int device) {
   return 0;
 }
 
-int ecckd_rte_lw(int device, int ncol, int nlay, int ngpt, int top_at_1, int n_gauss_angles,
-                 const double *tau, const double *lay_source, const double *lev_source_inc,
-                 const double *lev_source_dec, const double *sfc_source, int nband,
-                 const int *band2gpt, const double *sfc_emis, double *flux_up, double *flux_dn,
-                 int memspace, void *stream) {
+static int rte_lw_impl(const Call &c, int device, int ncol, int nlay, int ngpt, int top_at_1, int n_gauss_angles,
+                       const double *tau, const double *lay_source, const double *lev_source_inc, const double *lev_source_dec,
+                       const double *sfc_source, int nband, const int *band2gpt, const double *sfc_emis,
+                       const double *inc_flux, double *flux_up, double *flux_dn, int memspace, void *stream) {
   if (check_dims(ncol, nlay)) return 1;
   if (n_gauss_angles < 1 || n_gauss_angles > 4) return fail("rte_lw: have to ask for at least one quadrature point and no more than 4");
   if (!tau || !lay_source || !lev_source_inc || !lev_source_dec || !sfc_source || !sfc_emis || !flux_up || !flux_dn)
     return fail("ecckd_rte_lw: null argument");
   ecckd::RteLwArgs a{};
-  if (g_band_override >= 0) std::memset(a.gpt2band, g_band_override, sizeof a.gpt2band);
+  if (c.band >= 0) std::memset(a.gpt2band, c.band, sizeof a.gpt2band);
   else if (fill_band_map(ngpt, nband, band2gpt, a.gpt2band)) return 1;
   if (check_device(device)) return 1;
   if (ncol == 0) return 0;
-  a.ncol = ncol; a.nlay = nlay; a.ng = ngpt; a.top_at_1 = top_at_1 ? 1 : 0; a.nmus = n_gauss_angles;
+  a.ncol = ncol; a.nlay = nlay; a.ng = ngpt; a.top_at_1 = top_at_1 ? 1 : 0;
   a.nband = nband;
-  a.f32 = g_f32;
-  a.shared_levels = g_shared_levels;
-  {
-    const double t = g_opt.lw_tau_thresh.load();
-    a.tau_thresh = t > 0. ? t : (g_f32 ? std::sqrt(1.1920928955078125e-07) : std::sqrt(2.220446049250313e-16));   // sqrt(epsilon(1._wp))
-    a.series3 = g_opt.lw_series_terms.load() == 3;
-    a.inc_isotropic = g_opt.lw_inc_flux_isotropic.load();
-    a.use_split = g_opt.lw_solver.load();
-    a.split_seg = g_opt.lw_split_seg.load();
-  }
-  for (int k = 0; k < n_gauss_angles; ++k) {
-    a.Ds[k] = kGaussDs[n_gauss_angles - 1][k];
-    a.wts[k] = kGaussWts[n_gauss_angles - 1][k];
-  }
+  a.f32 = c.f32;
+  a.shared_levels = c.shared_levels;
+  fill_lw_options(a, n_gauss_angles, c.f32);
   const size_t n3 = (size_t)ncol * nlay * ngpt, n2l = (size_t)ncol * (nlay + 1);
   const size_t scratch = ecckd::rte_lw_scratch_bytes(ncol, nlay, ngpt);
   const hipStream_t launch_stream = memspace == ECCKD_DEVICE ? static_cast<hipStream_t>(stream) : nullptr;
@@ -1236,7 +1298,7 @@ int ecckd_rte_lw(int device, int ncol, int nlay, int ngpt, int top_at_1, int n_g
     a.tau = tau; a.lay_source = lay_source; a.lev_source_inc = lev_source_inc;
     a.lev_source_dec = lev_source_dec; a.sfc_source = sfc_source; a.sfc_emis = sfc_emis;
     a.flux_up = flux_up; a.flux_dn = flux_dn;
-    a.inc_flux = g_inc_flux;
+    a.inc_flux = inc_flux;
     {
       ProfScope prof("rte_lw", launch_stream);
       HIPCHK(ecckd::launch_rte_lw(a, launch_stream));
@@ -1249,11 +1311,12 @@ int ecckd_rte_lw(int device, int ncol, int nlay, int ngpt, int top_at_1, int n_g
   const bool mixed = memspace == ECCKD_MIXED;
   Arena &ar = g_solver_arena[device];
   std::lock_guard<std::mutex> lock(ar.mu);
-  const size_t need = (mixed ? 0 : align256(n3 * esz()) * 4 + align256((size_t)ncol * ngpt * esz())) +
-                      align256((size_t)ncol * ngpt * esz()) + align256((size_t)ncol * nband * esz()) +
-                      align256(n2l * esz()) * 2;
+  const size_t es = esz(c.f32);
+  const size_t need = (mixed ? 0 : align256(n3 * es) * 4 + align256((size_t)ncol * ngpt * es)) +
+                      align256((size_t)ncol * ngpt * es) + align256((size_t)ncol * nband * es) +
+                      align256(n2l * es) * 2;
   if (ar.ensure(need)) return 1;
-  Bump b(ar.p);
+  Bump b(ar.p, c.f32);
   hipStream_t s = nullptr;
   if (mixed) {
     a.tau = tau; a.lay_source = lay_source; a.lev_source_inc = lev_source_inc; a.lev_source_dec = lev_source_dec;
@@ -1261,33 +1324,39 @@ int ecckd_rte_lw(int device, int ncol, int nlay, int ngpt, int top_at_1, int n_g
   } else {
     double *d_tau = b.take(n3), *d_lay = b.take(n3), *d_inc = b.take(n3), *d_dec = b.take(n3);
     double *d_sfc = b.take((size_t)ncol * ngpt);
-    if (h2d(d_tau, tau, n3, s) || h2d(d_lay, lay_source, n3, s) || h2d(d_inc, lev_source_inc, n3, s) ||
-        h2d(d_dec, lev_source_dec, n3, s) || h2d(d_sfc, sfc_source, (size_t)ncol * ngpt, s))
+    if (h2d(d_tau, tau, n3, c.f32, s) || h2d(d_lay, lay_source, n3, c.f32, s) || h2d(d_inc, lev_source_inc, n3, c.f32, s) ||
+        h2d(d_dec, lev_source_dec, n3, c.f32, s) || h2d(d_sfc, sfc_source, (size_t)ncol * ngpt, c.f32, s))
       return 1;
     a.tau = d_tau; a.lay_source = d_lay; a.lev_source_inc = d_inc; a.lev_source_dec = d_dec; a.sfc_source = d_sfc;
   }
   double *d_emis = b.take((size_t)ncol * nband), *d_up = b.take(n2l), *d_dn = b.take(n2l);
   double *d_incf = b.take((size_t)ncol * ngpt);
-  if (h2d(d_emis, sfc_emis, (size_t)ncol * nband, s)) return 1;
-  if (g_inc_flux && h2d(d_incf, g_inc_flux, (size_t)ncol * ngpt, s)) return 1;
+  if (h2d(d_emis, sfc_emis, (size_t)ncol * nband, c.f32, s)) return 1;
+  if (inc_flux && h2d(d_incf, inc_flux, (size_t)ncol * ngpt, c.f32, s)) return 1;
   a.sfc_emis = d_emis; a.flux_up = d_up; a.flux_dn = d_dn;
-  a.inc_flux = g_inc_flux ? d_incf : nullptr;
+  a.inc_flux = inc_flux ? d_incf : nullptr;
   HIPCHK(ecckd::launch_rte_lw(a, s));
-  if (d2h(flux_up, d_up, n2l, s) || d2h(flux_dn, d_dn, n2l, s)) return 1;
+  if (d2h(flux_up, d_up, n2l, c.f32, s) || d2h(flux_dn, d_dn, n2l, c.f32, s)) return 1;
   HIPCHK(hipStreamSynchronize(s));
   return 0;
+}
+
+int ecckd_rte_lw(int device, int ncol, int nlay, int ngpt, int top_at_1, int n_gauss_angles,
+                 const double *tau, const double *lay_source, const double *lev_source_inc,
+                 const double *lev_source_dec, const double *sfc_source, int nband,
+                 const int *band2gpt, const double *sfc_emis, double *flux_up, double *flux_dn,
+                 int memspace, void *stream) {
+  return rte_lw_impl(Call{}, device, ncol, nlay, ngpt, top_at_1, n_gauss_angles, tau, lay_source, lev_source_inc,
+                     lev_source_dec, sfc_source, nband, band2gpt, sfc_emis, nullptr, flux_up, flux_dn, memspace, stream);
 }
 
 int ecckd_rte_lw_f32(int device, int ncol, int nlay, int ngpt, int top_at_1, int n_gauss_angles, const float *tau,
                      const float *lay_source, const float *lev_source_inc, const float *lev_source_dec,
                      const float *sfc_source, int nband, const int *band2gpt, const float *sfc_emis,
                      float *flux_up, float *flux_dn, int memspace, void *stream) {
-  F32Scope scope;
-  auto c = [](const float *p) { return reinterpret_cast<const double *>(p); };
-  auto w = [](float *p) { return reinterpret_cast<double *>(p); };
-  return ecckd_rte_lw(device, ncol, nlay, ngpt, top_at_1, n_gauss_angles, c(tau), c(lay_source), c(lev_source_inc),
-                      c(lev_source_dec), c(sfc_source), nband, band2gpt, c(sfc_emis), w(flux_up), w(flux_dn),
-                      memspace, stream);
+  return rte_lw_impl(Call{true}, device, ncol, nlay, ngpt, top_at_1, n_gauss_angles, dp(tau), dp(lay_source),
+                     dp(lev_source_inc), dp(lev_source_dec), dp(sfc_source), nband, band2gpt, dp(sfc_emis), nullptr,
+                     dp(flux_up), dp(flux_dn), memspace, stream);
 }
 
 int ecckd_rte_lw_shared_levels(int device, int ncol, int nlay, int ngpt, int top_at_1, int n_gauss_angles,
@@ -1295,12 +1364,9 @@ int ecckd_rte_lw_shared_levels(int device, int ncol, int nlay, int ngpt, int top
                                const double *lev_source_dec, const double *sfc_source, int nband,
                                const int *band2gpt, const double *sfc_emis, double *flux_up, double *flux_dn,
                                int memspace, void *stream) {
-  struct Scope {
-    Scope() { g_shared_levels = 1; }
-    ~Scope() { g_shared_levels = 0; }
-  } scope;
-  return ecckd_rte_lw(device, ncol, nlay, ngpt, top_at_1, n_gauss_angles, tau, lay_source, lev_source_inc,
-                      lev_source_dec, sfc_source, nband, band2gpt, sfc_emis, flux_up, flux_dn, memspace, stream);
+  return rte_lw_impl(Call{false, -1, /*shared_levels*/ true}, device, ncol, nlay, ngpt, top_at_1, n_gauss_angles, tau,
+                     lay_source, lev_source_inc, lev_source_dec, sfc_source, nband, band2gpt, sfc_emis, nullptr,
+                     flux_up, flux_dn, memspace, stream);
 }
 
 int ecckd_rte_lw_inc_flux(int device, int ncol, int nlay, int ngpt, int top_at_1, int n_gauss_angles,
@@ -1308,24 +1374,28 @@ int ecckd_rte_lw_inc_flux(int device, int ncol, int nlay, int ngpt, int top_at_1
                           const double *lev_source_dec, const double *sfc_source, int nband,
                           const int *band2gpt, const double *sfc_emis, const double *inc_flux, double *flux_up,
                           double *flux_dn, int memspace, void *stream) {
-  struct Scope {
-    explicit Scope(const double *p) { g_inc_flux = p; }
-    ~Scope() { g_inc_flux = nullptr; }
-  } scope(inc_flux);
-  return ecckd_rte_lw(device, ncol, nlay, ngpt, top_at_1, n_gauss_angles, tau, lay_source, lev_source_inc,
-                      lev_source_dec, sfc_source, nband, band2gpt, sfc_emis, flux_up, flux_dn, memspace, stream);
+  return rte_lw_impl(Call{}, device, ncol, nlay, ngpt, top_at_1, n_gauss_angles, tau, lay_source, lev_source_inc,
+                     lev_source_dec, sfc_source, nband, band2gpt, sfc_emis, inc_flux, flux_up, flux_dn, memspace, stream);
 }
 
-int ecckd_rte_sw(int device, int ncol, int nlay, int ngpt, int top_at_1, const double *tau,
-                 const double *ssa, const double *g, const double *mu0, const double *toa_flux,
-                 int nband, const int *band2gpt, const double *sfc_alb_dir,
-                 const double *sfc_alb_dif, double *flux_up, double *flux_dn, double *flux_dir,
-                 int memspace, void *stream) {
+int ecckd_rte_lw_inc_flux_f32(int device, int ncol, int nlay, int ngpt, int top_at_1, int n_gauss_angles, const float *tau,
+                              const float *lay_source, const float *lev_source_inc, const float *lev_source_dec,
+                              const float *sfc_source, int nband, const int *band2gpt, const float *sfc_emis,
+                              const float *inc_flux, float *flux_up, float *flux_dn, int memspace, void *stream) {
+  return rte_lw_impl(Call{true}, device, ncol, nlay, ngpt, top_at_1, n_gauss_angles, dp(tau), dp(lay_source),
+                     dp(lev_source_inc), dp(lev_source_dec), dp(sfc_source), nband, band2gpt, dp(sfc_emis), dp(inc_flux),
+                     dp(flux_up), dp(flux_dn), memspace, stream);
+}
+
+static int rte_sw_impl(const Call &c, int device, int ncol, int nlay, int ngpt, int top_at_1, const double *tau,
+                       const double *ssa, const double *g, const double *mu0, const double *toa_flux, int nband,
+                       const int *band2gpt, const double *sfc_alb_dir, const double *sfc_alb_dif, double *flux_up,
+                       double *flux_dn, double *flux_dir, int memspace, void *stream) {
   if (check_dims(ncol, nlay)) return 1;
-  if (!tau || !mu0 || !sfc_alb_dir || !sfc_alb_dif || !flux_up || !flux_dn || (!g_sw_derive && (!ssa || !g || !toa_flux)))
+  if (!tau || !mu0 || !sfc_alb_dir || !sfc_alb_dif || !flux_up || !flux_dn || (!c.derive && (!ssa || !g || !toa_flux)))
     return fail("ecckd_rte_sw: null argument");
   ecckd::RteSwArgs a{};
-  if (g_band_override >= 0) std::memset(a.gpt2band, g_band_override, sizeof a.gpt2band);
+  if (c.band >= 0) std::memset(a.gpt2band, c.band, sizeof a.gpt2band);
   else if (fill_band_map(ngpt, nband, band2gpt, a.gpt2band)) return 1;
   if (check_device(device)) return 1;
   if (ncol == 0) return 0;
@@ -1335,11 +1405,12 @@ int ecckd_rte_sw(int device, int ncol, int nlay, int ngpt, int top_at_1, const d
   // (fast arithmetic mode: sw_sqrt() of sw_two_stream.hpp takes normal numbers; a subnormal floor changes nothing a flux can show)
   if (!a.exact_division && a.k_floor < 2.2250738585072014e-308) a.k_floor = 2.2250738585072014e-308;
   a.dir_clamp = g_opt.sw_dir_clamp.load();
-  a.f32 = g_f32;
-  if (g_sw_derive) {   // ecckd_sw_fluxes: ssa / g / toa derived inside the solver (RteSwArgs::derive)
+  a.f32 = c.f32;
+  const SwDerive *dv = c.derive;
+  if (dv) {   // ecckd_sw_fluxes: ssa / g / toa derived inside the solver (RteSwArgs::derive)
     a.derive = 1;
-    a.plev = g_sw_derive->plev; a.rayleigh = g_sw_derive->rayleigh; a.solar = g_sw_derive->solar; a.gw = g_sw_derive->gw;
-    a.toa_scale = g_sw_derive->toa_scale;
+    a.plev = dv->plev; a.rayleigh = dv->rayleigh; a.solar = dv->solar; a.gw = dv->gw;
+    a.toa_scale = dv->toa_scale;
   }
   const size_t n3 = (size_t)ncol * nlay * ngpt, n2l = (size_t)ncol * (nlay + 1);
   const hipStream_t launch_stream = memspace == ECCKD_DEVICE ? static_cast<hipStream_t>(stream) : nullptr;
@@ -1351,21 +1422,21 @@ int ecckd_rte_sw(int device, int ncol, int nlay, int ngpt, int top_at_1, const d
     if (g_opt.sw_tail_split.load()) {
       const size_t need = ecckd::rte_sw_sys_plan(a, cus);
       if (need) {
-        if (g_sw_derive) a.partials = g_sw_scratch;   // (ecckd_sw_fluxes sized its block with sw_fluxes_solver_bytes)
+        if (dv) a.partials = dv->room;   // (ecckd_sw_fluxes sized its block with sw_fluxes_solver_bytes)
         else if (void *sp = stream_scratch_optional(device, launch_stream, need, lease)) a.partials = static_cast<double *>(sp);
         if (!a.partials) { a.sys_tail_first = -1; a.sys_gchunk = 0; }
       }
     }
-  } else if (g_sw_derive) {
+  } else if (dv) {
     // two-pass solver inside ecckd_sw_fluxes: the stream's scratch block holds the optical depth, so the ring and the
     // partial sums come from the room behind it (sw_fluxes_solver_bytes), never from stream_scratch
-    a.scratch = g_sw_scratch;
+    a.scratch = dv->room;
     if (!a.scratch) return fail("ecckd_rte_sw: the fused shortwave path has no room for the two-pass solver's scratch ring");
     if (g_opt.sw_tail_split.load()) {
       long first = -1;
       size_t partials_at = 0;
       if (ecckd::rte_sw_tail_plan(a, &first, &partials_at)) {
-        a.partials = reinterpret_cast<double *>(reinterpret_cast<char *>(g_sw_scratch) + partials_at);
+        a.partials = reinterpret_cast<double *>(reinterpret_cast<char *>(dv->room) + partials_at);
         a.tail_first = first;
       }
     }
@@ -1404,46 +1475,60 @@ int ecckd_rte_sw(int device, int ncol, int nlay, int ngpt, int top_at_1, const d
   const bool mixed = memspace == ECCKD_MIXED;   // tau, ssa, g: device buffers; everything else host
   Arena &ar = g_solver_arena[device];
   std::lock_guard<std::mutex> lock(ar.mu);
-  const size_t need = (mixed ? 0 : align256(n3 * esz()) * 3) + align256((size_t)ncol * esz()) +
-                      align256((size_t)ncol * ngpt * esz()) + align256((size_t)ncol * nband * esz()) * 2 +
-                      align256(n2l * esz()) * 3;
+  const size_t es = esz(c.f32);
+  const size_t need = (mixed ? 0 : align256(n3 * es) * 3) + align256((size_t)ncol * es) +
+                      align256((size_t)ncol * ngpt * es) + align256((size_t)ncol * nband * es) * 2 +
+                      align256(n2l * es) * 3;
   if (ar.ensure(need)) return 1;
-  Bump b(ar.p);
+  Bump b(ar.p, c.f32);
   hipStream_t s = nullptr;
   if (mixed) {
     a.tau = tau; a.ssa = ssa; a.g = g;
   } else {
     double *d_tau = b.take(n3), *d_ssa = b.take(n3), *d_g = b.take(n3);
-    if (h2d(d_tau, tau, n3, s) || h2d(d_ssa, ssa, n3, s) || h2d(d_g, g, n3, s)) return 1;
+    if (h2d(d_tau, tau, n3, c.f32, s) || h2d(d_ssa, ssa, n3, c.f32, s) || h2d(d_g, g, n3, c.f32, s)) return 1;
     a.tau = d_tau; a.ssa = d_ssa; a.g = d_g;
   }
   double *d_mu0 = b.take(ncol);
   double *d_toa = b.take((size_t)ncol * ngpt), *d_ad = b.take((size_t)ncol * nband), *d_af = b.take((size_t)ncol * nband);
   double *d_up = b.take(n2l), *d_dn = b.take(n2l), *d_dir = b.take(n2l);
-  if (h2d(d_mu0, mu0, ncol, s) || h2d(d_toa, toa_flux, (size_t)ncol * ngpt, s) ||
-      h2d(d_ad, sfc_alb_dir, (size_t)ncol * nband, s) || h2d(d_af, sfc_alb_dif, (size_t)ncol * nband, s))
+  if (h2d(d_mu0, mu0, ncol, c.f32, s) || h2d(d_toa, toa_flux, (size_t)ncol * ngpt, c.f32, s) ||
+      h2d(d_ad, sfc_alb_dir, (size_t)ncol * nband, c.f32, s) || h2d(d_af, sfc_alb_dif, (size_t)ncol * nband, c.f32, s))
     return 1;
   a.mu0 = d_mu0; a.toa = d_toa; a.alb_dir = d_ad; a.alb_dif = d_af;
   a.flux_up = d_up; a.flux_dn = d_dn; a.flux_dir = flux_dir ? d_dir : nullptr;
   HIPCHK(launch(s));
-  if (d2h(flux_up, d_up, n2l, s) || d2h(flux_dn, d_dn, n2l, s)) return 1;
-  if (flux_dir && d2h(flux_dir, d_dir, n2l, s)) return 1;
+  if (d2h(flux_up, d_up, n2l, c.f32, s) || d2h(flux_dn, d_dn, n2l, c.f32, s)) return 1;
+  if (flux_dir && d2h(flux_dir, d_dir, n2l, c.f32, s)) return 1;
   HIPCHK(hipStreamSynchronize(s));
   return 0;
 }
 
+int ecckd_rte_sw(int device, int ncol, int nlay, int ngpt, int top_at_1, const double *tau,
+                 const double *ssa, const double *g, const double *mu0, const double *toa_flux,
+                 int nband, const int *band2gpt, const double *sfc_alb_dir,
+                 const double *sfc_alb_dif, double *flux_up, double *flux_dn, double *flux_dir,
+                 int memspace, void *stream) {
+  return rte_sw_impl(Call{}, device, ncol, nlay, ngpt, top_at_1, tau, ssa, g, mu0, toa_flux, nband, band2gpt,
+                     sfc_alb_dir, sfc_alb_dif, flux_up, flux_dn, flux_dir, memspace, stream);
+}
+
+int ecckd_rte_sw_f32(int device, int ncol, int nlay, int ngpt, int top_at_1, const float *tau, const float *ssa, const float *g,
+                     const float *mu0, const float *toa_flux, int nband, const int *band2gpt, const float *sfc_alb_dir,
+                     const float *sfc_alb_dif, float *flux_up, float *flux_dn, float *flux_dir, int memspace, void *stream) {
+  return rte_sw_impl(Call{true}, device, ncol, nlay, ngpt, top_at_1, dp(tau), dp(ssa), dp(g), dp(mu0), dp(toa_flux), nband,
+                     band2gpt, dp(sfc_alb_dir), dp(sfc_alb_dif), dp(flux_up), dp(flux_dn), dp(flux_dir), memspace, stream);
+}
+
 // ---- RTE-RRTMGP's kernel-level interfaces: spectral fluxes (ncol,nlay+1,ngpt), sum_broadband ----
 
-namespace {
-void fill_gpt_options(ecckd::RteGptArgs &a) {
-  const double t = g_opt.lw_tau_thresh.load();
-  a.tau_thresh = t > 0. ? t : std::sqrt(2.220446049250313e-16);
+static void fill_gpt_options(ecckd::RteGptArgs &a) {
+  a.tau_thresh = lw_tau_thresh(false);
   a.series3 = g_opt.lw_series_terms.load() == 3;
   a.inc_isotropic = g_opt.lw_inc_flux_isotropic.load();
   a.k_floor = g_opt.sw_k_floor.load();
   a.dir_clamp = g_opt.sw_dir_clamp.load();
 }
-}  // namespace
 
 int ecckd_lw_solver_noscat_gpt(int device, int ncol, int nlay, int ngpt, int top_at_1, int nmus, const double *Ds,
                                const double *weights, const double *tau, const double *lay_source,
@@ -1473,18 +1558,18 @@ int ecckd_lw_solver_noscat_gpt(int device, int ncol, int nlay, int ngpt, int top
   Arena &ar = g_solver_arena[device];
   std::lock_guard<std::mutex> lock(ar.mu);
   if (ar.ensure(align256(n3 * 8) * 4 + align256(n2 * 8) * 3 + align256(nf * 8) * 2)) return 1;
-  Bump b(ar.p);
+  Bump b(ar.p, false);
   double *d_tau = b.take(n3), *d_lay = b.take(n3), *d_inc = b.take(n3), *d_dec = b.take(n3);
   double *d_emis = b.take(n2), *d_src = b.take(n2), *d_incf = b.take(n2), *d_up = b.take(nf), *d_dn = b.take(nf);
   hipStream_t s = nullptr;
-  if (h2d(d_tau, tau, n3, s) || h2d(d_lay, lay_source, n3, s) || h2d(d_inc, lev_source_inc, n3, s) ||
-      h2d(d_dec, lev_source_dec, n3, s) || h2d(d_emis, sfc_emis, n2, s) || h2d(d_src, sfc_src, n2, s))
+  if (h2d(d_tau, tau, n3, false, s) || h2d(d_lay, lay_source, n3, false, s) || h2d(d_inc, lev_source_inc, n3, false, s) ||
+      h2d(d_dec, lev_source_dec, n3, false, s) || h2d(d_emis, sfc_emis, n2, false, s) || h2d(d_src, sfc_src, n2, false, s))
     return 1;
-  if (inc_flux && h2d(d_incf, inc_flux, n2, s)) return 1;
+  if (inc_flux && h2d(d_incf, inc_flux, n2, false, s)) return 1;
   a.tau = d_tau; a.lay_source = d_lay; a.lev_source_inc = d_inc; a.lev_source_dec = d_dec; a.sfc_emis = d_emis;
   a.sfc_src = d_src; a.inc_flux = inc_flux ? d_incf : nullptr; a.flux_up = d_up; a.flux_dn = d_dn;
   HIPCHK(ecckd::launch_lw_gpt(a, s));
-  if (d2h(gpt_flux_up, d_up, nf, s) || d2h(gpt_flux_dn, d_dn, nf, s)) return 1;
+  if (d2h(gpt_flux_up, d_up, nf, false, s) || d2h(gpt_flux_dn, d_dn, nf, false, s)) return 1;
   HIPCHK(hipStreamSynchronize(s));
   return 0;
 }
@@ -1514,20 +1599,20 @@ int ecckd_sw_solver_2stream_gpt(int device, int ncol, int nlay, int ngpt, int to
   Arena &ar = g_solver_arena[device];
   std::lock_guard<std::mutex> lock(ar.mu);
   if (ar.ensure(align256(n3 * 8) * 3 + align256((size_t)ncol * 8) + align256(n2 * 8) * 4 + align256(nf * 8) * 3)) return 1;
-  Bump b(ar.p);
+  Bump b(ar.p, false);
   double *d_tau = b.take(n3), *d_ssa = b.take(n3), *d_g = b.take(n3), *d_mu0 = b.take(ncol);
   double *d_top = b.take(n2), *d_dif = b.take(n2), *d_ad = b.take(n2), *d_af = b.take(n2);
   double *d_up = b.take(nf), *d_dn = b.take(nf), *d_dir = b.take(nf);
   hipStream_t s = nullptr;
-  if (h2d(d_tau, tau, n3, s) || h2d(d_ssa, ssa, n3, s) || h2d(d_g, g, n3, s) || h2d(d_mu0, mu0, ncol, s) ||
-      h2d(d_top, flux_dir_top, n2, s) || h2d(d_ad, sfc_alb_dir, n2, s) || h2d(d_af, sfc_alb_dif, n2, s))
+  if (h2d(d_tau, tau, n3, false, s) || h2d(d_ssa, ssa, n3, false, s) || h2d(d_g, g, n3, false, s) || h2d(d_mu0, mu0, ncol, false, s) ||
+      h2d(d_top, flux_dir_top, n2, false, s) || h2d(d_ad, sfc_alb_dir, n2, false, s) || h2d(d_af, sfc_alb_dif, n2, false, s))
     return 1;
-  if (inc_flux_dif && h2d(d_dif, inc_flux_dif, n2, s)) return 1;
+  if (inc_flux_dif && h2d(d_dif, inc_flux_dif, n2, false, s)) return 1;
   a.tau = d_tau; a.ssa = d_ssa; a.g = d_g; a.mu0 = d_mu0; a.fdir_top = d_top; a.inc_dif = inc_flux_dif ? d_dif : nullptr;
   a.alb_dir = d_ad; a.alb_dif = d_af; a.flux_up = d_up; a.flux_dn = d_dn; a.flux_dir = gpt_flux_dir ? d_dir : nullptr;
   HIPCHK(ecckd::launch_sw_gpt(a, s));
-  if (d2h(gpt_flux_up, d_up, nf, s) || d2h(gpt_flux_dn, d_dn, nf, s)) return 1;
-  if (gpt_flux_dir && d2h(gpt_flux_dir, d_dir, nf, s)) return 1;
+  if (d2h(gpt_flux_up, d_up, nf, false, s) || d2h(gpt_flux_dn, d_dn, nf, false, s)) return 1;
+  if (gpt_flux_dir && d2h(gpt_flux_dir, d_dir, nf, false, s)) return 1;
   HIPCHK(hipStreamSynchronize(s));
   return 0;
 }
@@ -1539,11 +1624,7 @@ int ecckd_sum_broadband(int device, int ncol, int nlev, int ngpt, const double *
   const size_t n = (size_t)ncol * nlev;
   if (n == 0) return 0;
   if (memspace == ECCKD_HOST) {   // a sum over ngpt planes: not worth a round trip over the bus
-    for (size_t i = 0; i < n; ++i) {
-      double acc = 0.;
-      for (int k = 0; k < ngpt; ++k) acc += spectral_flux[(size_t)k * n + i];
-      broadband_flux[i] = acc;
-    }
+    sum_planes_host(spectral_flux, ngpt, n, broadband_flux);
     return 0;
   }
   if (memspace != ECCKD_DEVICE) return fail("ecckd: bad memspace");
@@ -1564,7 +1645,7 @@ int ecckd_gas_optics_lw_tau(const ecckd_model_t *m, int ncol, int nlay, const do
   HIPCHK(hipSetDevice(m->device));
   if (ncol == 0) return 0;
   const GasDesc gd{ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar};
-  return gas_optical_depth_dev(m, ncol, nlay, plev, tlay, gd, tau, false, nullptr, nullptr, nullptr, nullptr,
+  return gas_optical_depth_dev(m, false, nullptr, ncol, nlay, plev, tlay, gd, tau, false, nullptr, nullptr, nullptr, nullptr,
                                static_cast<hipStream_t>(stream));
 }
 
@@ -1585,20 +1666,10 @@ static int rte_lw_fused_dev(const ecckd_model *m, int ncol, int nlay, int top_at
                             const double *inc_flux, double *flux_up, double *flux_dn, double *scratch, hipStream_t stream) {
   ecckd::RteLwArgs a{};
   if (fill_band_map(m->ng, m->nband, m->band2gpt.data(), a.gpt2band)) return 1;
-  a.ncol = ncol; a.nlay = nlay; a.ng = m->ng; a.top_at_1 = top_at_1 ? 1 : 0; a.nmus = n_gauss_angles;
+  a.ncol = ncol; a.nlay = nlay; a.ng = m->ng; a.top_at_1 = top_at_1 ? 1 : 0;
   a.nband = m->nband;
-  {
-    const double t = g_opt.lw_tau_thresh.load();
-    a.tau_thresh = t > 0. ? t : std::sqrt(2.220446049250313e-16);
-    a.series3 = g_opt.lw_series_terms.load() == 3;
-    a.inc_isotropic = g_opt.lw_inc_flux_isotropic.load();
-    a.use_split = 1;
-    a.split_seg = g_opt.lw_split_seg.load();
-  }
-  for (int k = 0; k < n_gauss_angles; ++k) {
-    a.Ds[k] = kGaussDs[n_gauss_angles - 1][k];
-    a.wts[k] = kGaussWts[n_gauss_angles - 1][k];
-  }
+  fill_lw_options(a, n_gauss_angles, false);
+  a.use_split = 1;
   a.tau = tau; a.sfc_emis = sfc_emis; a.inc_flux = inc_flux; a.flux_up = flux_up; a.flux_dn = flux_dn;
   if (fused_lw_kernels_apply(m, nlay)) {
     ProfScope prof("rte_lw_fused", stream);
@@ -1610,13 +1681,7 @@ static int rte_lw_fused_dev(const ecckd_model *m, int ncol, int nlay, int top_at
   if (!scratch) return fail("ecckd: internal: the fused longwave solver needs scratch for this layer count");
   const size_t n3 = (size_t)ncol * nlay * m->ng;
   double *lay = scratch, *inc = lay + n3, *dec = inc + n3, *sfc = dec + n3, *ring = sfc + (((size_t)ncol * m->ng + 31) & ~(size_t)31);
-  ecckd::PlanckArgs p{};
-  p.ncol = ncol; p.nlay = nlay; p.ng = m->ng; p.ntp = m->ntp;
-  p.planck = m->dbuf + m->off_planck;
-  p.t0 = m->temperature_planck[0];
-  p.dt = m->temperature_planck[1] - m->temperature_planck[0];
-  p.tlay = tlay; p.tlev = tlev; p.tsfc = tsfc;
-  p.lay_source = lay; p.lev_source_inc = inc; p.lev_source_dec = dec; p.sfc_source = sfc;
+  ecckd::PlanckArgs p = planck_args(m, ncol, nlay, tlay, PlanckSide{tlev, tsfc, lay, inc, dec, sfc});
   {
     ProfScope prof("planck", stream);
     HIPCHK(ecckd::launch_planck(p, stream));
@@ -1672,7 +1737,7 @@ int ecckd_lw_fluxes(const ecckd_model_t *m, int ncol, int nlay, const double *pl
     const size_t extra = fused_scratch_doubles(m, ncol, nlay);
     if (stream_scratch(m->device, st, (n3 + 32 + extra) * sizeof(double), &tau_p, lease)) return 1;
     double *d_tau = static_cast<double *>(tau_p);
-    if (gas_optical_depth_dev(m, ncol, nlay, plev, tlay, gd, d_tau, false, nullptr, nullptr, nullptr, nullptr, st)) return 1;
+    if (gas_optical_depth_dev(m, false, nullptr, ncol, nlay, plev, tlay, gd, d_tau, false, nullptr, nullptr, nullptr, nullptr, st)) return 1;
     return rte_lw_fused_dev(m, ncol, nlay, top_at_1, n_gauss_angles, d_tau, tlay, tlev, tsfc, sfc_emis, inc_flux, flux_up,
                             flux_dn, extra ? d_tau + ((n3 + 31) & ~(size_t)31) : nullptr, st);
   }
@@ -1680,78 +1745,38 @@ int ecckd_lw_fluxes(const ecckd_model_t *m, int ncol, int nlay, const double *pl
   ecckd_model *mm = const_cast<ecckd_model *>(m);
   std::lock_guard<std::mutex> lock(mm->mu);
   hipStream_t s = mm->host_stream;
-  const size_t need = align256(n2l * 8) * 4 + align256(n2 * 8) + align256((size_t)ncol * 8) + staged_gas_bytes(gd, ncol, nlay) +
+  const size_t need = align256(n2l * 8) * 4 + align256(n2 * 8) + align256((size_t)ncol * 8) + staged_gas_bytes(gd, ncol, nlay, false) +
                       align256((size_t)ncol * m->nband * 8) + align256((size_t)ncol * m->ng * 8) + align256(n3 * 8) +
                       align256(fused_scratch_doubles(m, ncol, nlay) * 8);
-  if (need > mm->arena_bytes) {
-    HIPCHK(hipStreamSynchronize(s));
-    if (mm->arena) { HIPCHK(hipFree(mm->arena)); mm->arena = nullptr; mm->arena_bytes = 0; }
-    HIPCHK(hipMalloc(&mm->arena, need));
-    mm->arena_bytes = need;
-  }
-  Bump b(mm->arena);
+  if (grow_arena(mm, need)) return 1;
+  Bump b(mm->arena, false);
   double *d_plev = b.take(n2l), *d_tlev = b.take(n2l), *d_tlay = b.take(n2), *d_tsfc = b.take(ncol);
   double *d_up = b.take(n2l), *d_dn = b.take(n2l), *d_emis = b.take((size_t)ncol * m->nband), *d_incf = b.take((size_t)ncol * m->ng);
-  if (h2d(d_plev, plev, n2l, s) || h2d(d_tlay, tlay, n2, s) || h2d(d_tsfc, tsfc, ncol, s) || h2d(d_tlev, tlev, n2l, s) ||
-      h2d(d_emis, sfc_emis, (size_t)ncol * m->nband, s))
+  if (h2d(d_plev, plev, n2l, false, s) || h2d(d_tlay, tlay, n2, false, s) || h2d(d_tsfc, tsfc, ncol, false, s) ||
+      h2d(d_tlev, tlev, n2l, false, s) || h2d(d_emis, sfc_emis, (size_t)ncol * m->nband, false, s))
     return 1;
-  if (inc_flux && h2d(d_incf, inc_flux, (size_t)ncol * m->ng, s)) return 1;
+  if (inc_flux && h2d(d_incf, inc_flux, (size_t)ncol * m->ng, false, s)) return 1;
   StagedGases sg;
   if (stage_gases(gd, ncol, nlay, b, s, sg)) return 1;
   double *d_tau = b.take(n3);
   const size_t extra = fused_scratch_doubles(m, ncol, nlay);
   double *d_extra = extra ? b.take(extra) : nullptr;
-  if (gas_optical_depth_dev(m, ncol, nlay, d_plev, d_tlay, sg.gd, d_tau, false, nullptr, nullptr, nullptr, nullptr, s)) return 1;
+  if (gas_optical_depth_dev(m, false, nullptr, ncol, nlay, d_plev, d_tlay, sg.gd, d_tau, false, nullptr, nullptr, nullptr, nullptr, s)) return 1;
   if (rte_lw_fused_dev(m, ncol, nlay, top_at_1, n_gauss_angles, d_tau, d_tlay, d_tlev, d_tsfc, d_emis, inc_flux ? d_incf : nullptr,
                        d_up, d_dn, d_extra, s))
     return 1;
-  if (d2h(flux_up, d_up, n2l, s) || d2h(flux_dn, d_dn, n2l, s)) return 1;
+  if (d2h(flux_up, d_up, n2l, false, s) || d2h(flux_dn, d_dn, n2l, false, s)) return 1;
   HIPCHK(hipStreamSynchronize(s));
   return 0;
 }
 
-// ---- single-precision flavours of the shortwave pair and of the incident-flux longwave solver ----
-
-int ecckd_gas_optics_sw_f32(const ecckd_model_t *m, int ncol, int nlay, const float *plev, const float *tlay, int ngas,
-                            const char *gas_names, const float *const *vmr, const long long *vmr_col_stride,
-                            const long long *vmr_lay_stride, const double *vmr_scalar, float *tau, float *ssa, float *g,
-                            float *toa_src, int memspace, void *stream) {
-  F32Scope scope;
-  auto c = [](const float *p) { return reinterpret_cast<const double *>(p); };
-  auto w = [](float *p) { return reinterpret_cast<double *>(p); };
-  return ecckd_gas_optics_sw(m, ncol, nlay, c(plev), c(tlay), ngas, gas_names, reinterpret_cast<const double *const *>(vmr),
-                             vmr_col_stride, vmr_lay_stride, vmr_scalar, w(tau), w(ssa), w(g), w(toa_src), memspace, stream);
-}
-
-int ecckd_rte_sw_f32(int device, int ncol, int nlay, int ngpt, int top_at_1, const float *tau, const float *ssa, const float *g,
-                     const float *mu0, const float *toa_flux, int nband, const int *band2gpt, const float *sfc_alb_dir,
-                     const float *sfc_alb_dif, float *flux_up, float *flux_dn, float *flux_dir, int memspace, void *stream) {
-  F32Scope scope;
-  auto c = [](const float *p) { return reinterpret_cast<const double *>(p); };
-  auto w = [](float *p) { return reinterpret_cast<double *>(p); };
-  return ecckd_rte_sw(device, ncol, nlay, ngpt, top_at_1, c(tau), c(ssa), c(g), c(mu0), c(toa_flux), nband, band2gpt,
-                      c(sfc_alb_dir), c(sfc_alb_dif), w(flux_up), w(flux_dn), w(flux_dir), memspace, stream);
-}
-
-int ecckd_rte_lw_inc_flux_f32(int device, int ncol, int nlay, int ngpt, int top_at_1, int n_gauss_angles, const float *tau,
-                              const float *lay_source, const float *lev_source_inc, const float *lev_source_dec,
-                              const float *sfc_source, int nband, const int *band2gpt, const float *sfc_emis,
-                              const float *inc_flux, float *flux_up, float *flux_dn, int memspace, void *stream) {
-  F32Scope scope;
-  auto c = [](const float *p) { return reinterpret_cast<const double *>(p); };
-  auto w = [](float *p) { return reinterpret_cast<double *>(p); };
-  return ecckd_rte_lw_inc_flux(device, ncol, nlay, ngpt, top_at_1, n_gauss_angles, c(tau), c(lay_source), c(lev_source_inc),
-                               c(lev_source_dec), c(sfc_source), nband, band2gpt, c(sfc_emis), c(inc_flux), w(flux_up),
-                               w(flux_dn), memspace, stream);
-}
-
 // ---- fused shortwave: total optical depth only between the kernels (SURVEY 8(f) rank 4 for the shortwave) ----
 
-int ecckd_sw_fluxes(const ecckd_model_t *m, int ncol, int nlay, const double *plev, const double *tlay, int ngas,
-                    const char *gas_names, const double *const *vmr, const long long *vmr_col_stride,
-                    const long long *vmr_lay_stride, const double *vmr_scalar, int top_at_1, const double *mu0,
-                    const double *toa_scale, const double *sfc_alb_dir, const double *sfc_alb_dif, double *flux_up,
-                    double *flux_dn, double *flux_dir, int memspace, void *stream) {
+static int sw_fluxes_impl(bool f32, const ecckd_model_t *m, int ncol, int nlay, const double *plev, const double *tlay,
+                          int ngas, const char *gas_names, const double *const *vmr, const long long *vmr_col_stride,
+                          const long long *vmr_lay_stride, const double *vmr_scalar, int top_at_1, const double *mu0,
+                          const double *toa_scale, const double *sfc_alb_dir, const double *sfc_alb_dif, double *flux_up,
+                          double *flux_dn, double *flux_dir, int memspace, void *stream) {
   if (check_model(m) || check_gas_optics_dims(ncol, nlay)) return 1;
   if (!m->has_solar) return fail("ecckd_sw_fluxes: model has no solar table (longwave model?)");
   if (!plev || !tlay || !mu0 || !sfc_alb_dir || !sfc_alb_dif || !flux_up || !flux_dn || (ngas > 0 && !gas_names))
@@ -1761,70 +1786,65 @@ int ecckd_sw_fluxes(const ecckd_model_t *m, int ncol, int nlay, const double *pl
   if (ncol == 0) return 0;
   const GasDesc gd{ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar};
   const size_t n2 = (size_t)ncol * nlay, n2l = (size_t)ncol * (nlay + 1), n3 = n2 * m->ng;
-  // :107 / :314 with default-real literals (:51-52), as gas_optical_depth_dev computes it
-  double gw = 1. / ((double)9.80665f * (double)0.001f * (double)28.970f);
-  if (g_f32) gw = (double)(1.f / (9.80665f * 0.001f * 28.970f));
-  auto tabs = [&](size_t off) { return g_f32 ? reinterpret_cast<const double *>(m->dbuf32 + off) : m->dbuf + off; };
-  struct Scope {
-    explicit Scope(const SwDerive *d) { g_sw_derive = d; }
-    ~Scope() { g_sw_derive = nullptr; }
-  };
+  const size_t es = esz(f32);
+  const double *rayleigh = table(m, m->off_rayleigh, f32), *solar = table(m, m->off_solar, f32);
   if (memspace == ECCKD_DEVICE) {
     hipStream_t st = static_cast<hipStream_t>(stream);
     void *tau_p = nullptr;   // tau lives in the stream's scratch block between the two kernels; the solver's room behind it
     ScratchLease lease;
-    const size_t tau_bytes = align256(n3 * esz());
+    const size_t tau_bytes = align256(n3 * es);
     const size_t solver = sw_fluxes_solver_bytes(m->device, ncol, nlay, m->ng);
     if (stream_scratch(m->device, st, tau_bytes + solver, &tau_p, lease)) return 1;
     double *d_tau = static_cast<double *>(tau_p);
     // gas_optics_ext's tau (:449-456) without ssa / g: the total optical depth, gases + Rayleigh
-    if (gas_optical_depth_dev(m, ncol, nlay, plev, tlay, gd, d_tau, true, nullptr, nullptr, nullptr, nullptr, st)) return 1;
-    const SwDerive dv{plev, tabs(m->off_rayleigh), tabs(m->off_solar), toa_scale, gw};
-    Scope scope(&dv);
-    g_sw_scratch = solver ? reinterpret_cast<double *>(static_cast<char *>(tau_p) + tau_bytes) : nullptr;
-    const int rc = ecckd_rte_sw(m->device, ncol, nlay, m->ng, top_at_1, d_tau, nullptr, nullptr, mu0, nullptr, m->nband,
-                                m->band2gpt.data(), sfc_alb_dir, sfc_alb_dif, flux_up, flux_dn, flux_dir, ECCKD_DEVICE, stream);
-    g_sw_scratch = nullptr;
-    return rc;
+    if (gas_optical_depth_dev(m, f32, nullptr, ncol, nlay, plev, tlay, gd, d_tau, true, nullptr, nullptr, nullptr, nullptr, st))
+      return 1;
+    const SwDerive dv{plev, rayleigh, solar, toa_scale, gw(f32),
+                      solver ? reinterpret_cast<double *>(static_cast<char *>(tau_p) + tau_bytes) : nullptr};
+    return rte_sw_impl(Call{f32, -1, false, &dv}, m->device, ncol, nlay, m->ng, top_at_1, d_tau, nullptr, nullptr, mu0,
+                       nullptr, m->nband, m->band2gpt.data(), sfc_alb_dir, sfc_alb_dif, flux_up, flux_dn, flux_dir,
+                       ECCKD_DEVICE, stream);
   }
   if (memspace != ECCKD_HOST) return fail("ecckd: bad memspace");
   ecckd_model *mm = const_cast<ecckd_model *>(m);
   std::lock_guard<std::mutex> lock(mm->mu);
   hipStream_t s = mm->host_stream;
   const size_t solver = sw_fluxes_solver_bytes(m->device, ncol, nlay, m->ng);
-  const size_t need = align256(n2l * esz()) * 4 + align256(n2 * esz()) + align256((size_t)ncol * esz()) * 2 +
-                      staged_gas_bytes(gd, ncol, nlay) + align256((size_t)ncol * m->nband * esz()) * 2 + align256(n3 * esz()) +
+  const size_t need = align256(n2l * es) * 4 + align256(n2 * es) + align256((size_t)ncol * es) * 2 +
+                      staged_gas_bytes(gd, ncol, nlay, f32) + align256((size_t)ncol * m->nband * es) * 2 + align256(n3 * es) +
                       align256(solver);
-  if (need > mm->arena_bytes) {
-    HIPCHK(hipStreamSynchronize(s));
-    if (mm->arena) { HIPCHK(hipFree(mm->arena)); mm->arena = nullptr; mm->arena_bytes = 0; }
-    HIPCHK(hipMalloc(&mm->arena, need));
-    mm->arena_bytes = need;
-  }
-  Bump b(mm->arena);
+  if (grow_arena(mm, need)) return 1;
+  Bump b(mm->arena, f32);
   double *d_plev = b.take(n2l), *d_tlay = b.take(n2), *d_mu0 = b.take(ncol), *d_scale = b.take(ncol);
   double *d_up = b.take(n2l), *d_dn = b.take(n2l), *d_dir = b.take(n2l);
   double *d_ad = b.take((size_t)ncol * m->nband), *d_af = b.take((size_t)ncol * m->nband);
-  if (h2d(d_plev, plev, n2l, s) || h2d(d_tlay, tlay, n2, s) || h2d(d_mu0, mu0, ncol, s) ||
-      h2d(d_ad, sfc_alb_dir, (size_t)ncol * m->nband, s) || h2d(d_af, sfc_alb_dif, (size_t)ncol * m->nband, s))
+  if (h2d(d_plev, plev, n2l, f32, s) || h2d(d_tlay, tlay, n2, f32, s) || h2d(d_mu0, mu0, ncol, f32, s) ||
+      h2d(d_ad, sfc_alb_dir, (size_t)ncol * m->nband, f32, s) || h2d(d_af, sfc_alb_dif, (size_t)ncol * m->nband, f32, s))
     return 1;
-  if (toa_scale && h2d(d_scale, toa_scale, ncol, s)) return 1;
+  if (toa_scale && h2d(d_scale, toa_scale, ncol, f32, s)) return 1;
   StagedGases sg;
   if (stage_gases(gd, ncol, nlay, b, s, sg)) return 1;
   double *d_tau = b.take(n3);
-  double *d_solver = solver ? b.take((solver + esz() - 1) / esz()) : nullptr;
-  if (gas_optical_depth_dev(m, ncol, nlay, d_plev, d_tlay, sg.gd, d_tau, true, nullptr, nullptr, nullptr, nullptr, s)) return 1;
-  const SwDerive dv{d_plev, tabs(m->off_rayleigh), tabs(m->off_solar), toa_scale ? d_scale : nullptr, gw};
-  Scope scope(&dv);
-  g_sw_scratch = d_solver;
-  const int rc = ecckd_rte_sw(m->device, ncol, nlay, m->ng, top_at_1, d_tau, nullptr, nullptr, d_mu0, nullptr, m->nband,
-                              m->band2gpt.data(), d_ad, d_af, d_up, d_dn, flux_dir ? d_dir : nullptr, ECCKD_DEVICE, s);
-  g_sw_scratch = nullptr;
-  if (rc) return 1;
-  if (d2h(flux_up, d_up, n2l, s) || d2h(flux_dn, d_dn, n2l, s)) return 1;
-  if (flux_dir && d2h(flux_dir, d_dir, n2l, s)) return 1;
+  double *d_solver = solver ? b.take((solver + es - 1) / es) : nullptr;
+  if (gas_optical_depth_dev(m, f32, nullptr, ncol, nlay, d_plev, d_tlay, sg.gd, d_tau, true, nullptr, nullptr, nullptr, nullptr, s))
+    return 1;
+  const SwDerive dv{d_plev, rayleigh, solar, toa_scale ? d_scale : nullptr, gw(f32), d_solver};
+  if (rte_sw_impl(Call{f32, -1, false, &dv}, m->device, ncol, nlay, m->ng, top_at_1, d_tau, nullptr, nullptr, d_mu0, nullptr,
+                  m->nband, m->band2gpt.data(), d_ad, d_af, d_up, d_dn, flux_dir ? d_dir : nullptr, ECCKD_DEVICE, s))
+    return 1;
+  if (d2h(flux_up, d_up, n2l, f32, s) || d2h(flux_dn, d_dn, n2l, f32, s)) return 1;
+  if (flux_dir && d2h(flux_dir, d_dir, n2l, f32, s)) return 1;
   HIPCHK(hipStreamSynchronize(s));
   return 0;
+}
+
+int ecckd_sw_fluxes(const ecckd_model_t *m, int ncol, int nlay, const double *plev, const double *tlay, int ngas,
+                    const char *gas_names, const double *const *vmr, const long long *vmr_col_stride,
+                    const long long *vmr_lay_stride, const double *vmr_scalar, int top_at_1, const double *mu0,
+                    const double *toa_scale, const double *sfc_alb_dir, const double *sfc_alb_dif, double *flux_up,
+                    double *flux_dn, double *flux_dir, int memspace, void *stream) {
+  return sw_fluxes_impl(false, m, ncol, nlay, plev, tlay, ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar,
+                        top_at_1, mu0, toa_scale, sfc_alb_dir, sfc_alb_dif, flux_up, flux_dn, flux_dir, memspace, stream);
 }
 
 int ecckd_sw_fluxes_f32(const ecckd_model_t *m, int ncol, int nlay, const float *plev, const float *tlay, int ngas,
@@ -1832,80 +1852,43 @@ int ecckd_sw_fluxes_f32(const ecckd_model_t *m, int ncol, int nlay, const float 
                         const long long *vmr_lay_stride, const double *vmr_scalar, int top_at_1, const float *mu0,
                         const float *toa_scale, const float *sfc_alb_dir, const float *sfc_alb_dif, float *flux_up,
                         float *flux_dn, float *flux_dir, int memspace, void *stream) {
-  F32Scope scope;
-  auto c = [](const float *p) { return reinterpret_cast<const double *>(p); };
-  auto w = [](float *p) { return reinterpret_cast<double *>(p); };
-  return ecckd_sw_fluxes(m, ncol, nlay, c(plev), c(tlay), ngas, gas_names, reinterpret_cast<const double *const *>(vmr),
-                         vmr_col_stride, vmr_lay_stride, vmr_scalar, top_at_1, c(mu0), c(toa_scale), c(sfc_alb_dir),
-                         c(sfc_alb_dif), w(flux_up), w(flux_dn), w(flux_dir), memspace, stream);
+  return sw_fluxes_impl(true, m, ncol, nlay, dp(plev), dp(tlay), ngas, gas_names, reinterpret_cast<const double *const *>(vmr),
+                        vmr_col_stride, vmr_lay_stride, vmr_scalar, top_at_1, dp(mu0), dp(toa_scale), dp(sfc_alb_dir),
+                        dp(sfc_alb_dif), dp(flux_up), dp(flux_dn), dp(flux_dir), memspace, stream);
 }
 
 // ---- spectral (per-band) fluxes: ty_fluxes_byband of RTE-RRTMGP ----
-namespace {
-struct BandScope {
-  explicit BandScope(int b) { g_band_override = b; }
-  ~BandScope() { g_band_override = -1; }
-};
-// out(:) = sum over planes of planes(:, b), on the device or on the host
-int sum_planes(const double *planes, int nplanes, size_t n, double *out, int memspace, void *stream) {
-  if (memspace == ECCKD_DEVICE) {
-    HIPCHK(ecckd::launch_sum_planes(planes, nplanes, n, out, g_f32, static_cast<hipStream_t>(stream)));
-    return 0;
-  }
-  if (g_f32) {   // (the single-precision flavours: float data behind the double pointers)
-    const float *pf = reinterpret_cast<const float *>(planes);
-    float *of = reinterpret_cast<float *>(out);
-    for (size_t i = 0; i < n; ++i) {
-      float acc = 0.f;
-      for (int b = 0; b < nplanes; ++b) acc += pf[(size_t)b * n + i];
-      of[i] = acc;
-    }
-    return 0;
-  }
-  for (size_t i = 0; i < n; ++i) {
-    double acc = 0.;
-    for (int b = 0; b < nplanes; ++b) acc += planes[(size_t)b * n + i];
-    out[i] = acc;
-  }
-  return 0;
-}
-// p + n elements of the precision of the call (float data sits behind the double pointers of the _f32 flavours)
-inline const double *el(const double *p, size_t n) {
-  return g_f32 ? reinterpret_cast<const double *>(reinterpret_cast<const float *>(p) + n) : p + n;
-}
-inline double *elw(double *p, size_t n) { return g_f32 ? reinterpret_cast<double *>(reinterpret_cast<float *>(p) + n) : p + n; }
-}  // namespace
 
-int ecckd_rte_lw_byband(int device, int ncol, int nlay, int ngpt, int top_at_1, int n_gauss_angles,
-                        const double *tau, const double *lay_source, const double *lev_source_inc,
-                        const double *lev_source_dec, const double *sfc_source, int nband, const int *band2gpt,
-                        const double *sfc_emis, double *bnd_flux_up, double *bnd_flux_dn, double *flux_up,
-                        double *flux_dn, int memspace, void *stream) {
+// One solver pass per band over its (contiguous) g-points, each told its band (Call::band) instead of a band2gpt map
+static int rte_lw_byband_impl(bool f32, int device, int ncol, int nlay, int ngpt, int top_at_1, int n_gauss_angles,
+                              const double *tau, const double *lay_source, const double *lev_source_inc,
+                              const double *lev_source_dec, const double *sfc_source, int nband, const int *band2gpt,
+                              const double *sfc_emis, double *bnd_flux_up, double *bnd_flux_dn, double *flux_up,
+                              double *flux_dn, int memspace, void *stream) {
   if (check_dims(ncol, nlay)) return 1;
   unsigned char map[256];
   if (fill_band_map(ngpt, nband, band2gpt, map)) return 1;
   if (!bnd_flux_up || !bnd_flux_dn) return fail("ecckd_rte_lw_byband: null argument");
   const size_t n3 = (size_t)ncol * nlay, n2l = (size_t)ncol * (nlay + 1);
-  for (int b = 0; b < nband; ++b) {   // one solver pass per band over its (contiguous) g-points
+  for (int b = 0; b < nband; ++b) {
     const int g0 = band2gpt[2 * b] - 1, n = band2gpt[2 * b + 1] - g0;
-    const int one_band[2] = {1, n};
-    BandScope scope(b);
-    if (ecckd_rte_lw(device, ncol, nlay, n, top_at_1, n_gauss_angles, el(tau, n3 * g0), el(lay_source, n3 * g0),
-                     el(lev_source_inc, n3 * g0), el(lev_source_dec, n3 * g0), el(sfc_source, (size_t)ncol * g0), nband,
-                     one_band, sfc_emis, elw(bnd_flux_up, n2l * b), elw(bnd_flux_dn, n2l * b), memspace, stream))
+    if (rte_lw_impl(Call{f32, b}, device, ncol, nlay, n, top_at_1, n_gauss_angles, el(tau, n3 * g0, f32),
+                    el(lay_source, n3 * g0, f32), el(lev_source_inc, n3 * g0, f32), el(lev_source_dec, n3 * g0, f32),
+                    el(sfc_source, (size_t)ncol * g0, f32), nband, nullptr, sfc_emis, nullptr,
+                    el(bnd_flux_up, n2l * b, f32), el(bnd_flux_dn, n2l * b, f32), memspace, stream))
       return 1;
   }
   if (ncol == 0) return 0;
-  if (flux_up && sum_planes(bnd_flux_up, nband, n2l, flux_up, memspace, stream)) return 1;
-  if (flux_dn && sum_planes(bnd_flux_dn, nband, n2l, flux_dn, memspace, stream)) return 1;
+  if (flux_up && sum_planes(bnd_flux_up, nband, n2l, flux_up, f32, memspace, stream)) return 1;
+  if (flux_dn && sum_planes(bnd_flux_dn, nband, n2l, flux_dn, f32, memspace, stream)) return 1;
   return 0;
 }
 
-int ecckd_rte_sw_byband(int device, int ncol, int nlay, int ngpt, int top_at_1, const double *tau,
-                        const double *ssa, const double *g, const double *mu0, const double *toa_flux, int nband,
-                        const int *band2gpt, const double *sfc_alb_dir, const double *sfc_alb_dif,
-                        double *bnd_flux_up, double *bnd_flux_dn, double *bnd_flux_dir, double *flux_up,
-                        double *flux_dn, double *flux_dir, int memspace, void *stream) {
+static int rte_sw_byband_impl(bool f32, int device, int ncol, int nlay, int ngpt, int top_at_1, const double *tau,
+                              const double *ssa, const double *g, const double *mu0, const double *toa_flux, int nband,
+                              const int *band2gpt, const double *sfc_alb_dir, const double *sfc_alb_dif,
+                              double *bnd_flux_up, double *bnd_flux_dn, double *bnd_flux_dir, double *flux_up,
+                              double *flux_dn, double *flux_dir, int memspace, void *stream) {
   if (check_dims(ncol, nlay)) return 1;
   unsigned char map[256];
   if (fill_band_map(ngpt, nband, band2gpt, map)) return 1;
@@ -1914,18 +1897,37 @@ int ecckd_rte_sw_byband(int device, int ncol, int nlay, int ngpt, int top_at_1, 
   const size_t n3 = (size_t)ncol * nlay, n2l = (size_t)ncol * (nlay + 1);
   for (int b = 0; b < nband; ++b) {
     const int g0 = band2gpt[2 * b] - 1, n = band2gpt[2 * b + 1] - g0;
-    const int one_band[2] = {1, n};
-    BandScope scope(b);
-    if (ecckd_rte_sw(device, ncol, nlay, n, top_at_1, el(tau, n3 * g0), el(ssa, n3 * g0), el(g, n3 * g0), mu0,
-                     el(toa_flux, (size_t)ncol * g0), nband, one_band, sfc_alb_dir, sfc_alb_dif, elw(bnd_flux_up, n2l * b),
-                     elw(bnd_flux_dn, n2l * b), bnd_flux_dir ? elw(bnd_flux_dir, n2l * b) : nullptr, memspace, stream))
+    if (rte_sw_impl(Call{f32, b}, device, ncol, nlay, n, top_at_1, el(tau, n3 * g0, f32), el(ssa, n3 * g0, f32),
+                    el(g, n3 * g0, f32), mu0, el(toa_flux, (size_t)ncol * g0, f32), nband, nullptr, sfc_alb_dir,
+                    sfc_alb_dif, el(bnd_flux_up, n2l * b, f32), el(bnd_flux_dn, n2l * b, f32),
+                    bnd_flux_dir ? el(bnd_flux_dir, n2l * b, f32) : nullptr, memspace, stream))
       return 1;
   }
   if (ncol == 0) return 0;
-  if (flux_up && sum_planes(bnd_flux_up, nband, n2l, flux_up, memspace, stream)) return 1;
-  if (flux_dn && sum_planes(bnd_flux_dn, nband, n2l, flux_dn, memspace, stream)) return 1;
-  if (flux_dir && sum_planes(bnd_flux_dir, nband, n2l, flux_dir, memspace, stream)) return 1;
+  if (flux_up && sum_planes(bnd_flux_up, nband, n2l, flux_up, f32, memspace, stream)) return 1;
+  if (flux_dn && sum_planes(bnd_flux_dn, nband, n2l, flux_dn, f32, memspace, stream)) return 1;
+  if (flux_dir && sum_planes(bnd_flux_dir, nband, n2l, flux_dir, f32, memspace, stream)) return 1;
   return 0;
+}
+
+int ecckd_rte_lw_byband(int device, int ncol, int nlay, int ngpt, int top_at_1, int n_gauss_angles,
+                        const double *tau, const double *lay_source, const double *lev_source_inc,
+                        const double *lev_source_dec, const double *sfc_source, int nband, const int *band2gpt,
+                        const double *sfc_emis, double *bnd_flux_up, double *bnd_flux_dn, double *flux_up,
+                        double *flux_dn, int memspace, void *stream) {
+  return rte_lw_byband_impl(false, device, ncol, nlay, ngpt, top_at_1, n_gauss_angles, tau, lay_source, lev_source_inc,
+                            lev_source_dec, sfc_source, nband, band2gpt, sfc_emis, bnd_flux_up, bnd_flux_dn, flux_up,
+                            flux_dn, memspace, stream);
+}
+
+int ecckd_rte_sw_byband(int device, int ncol, int nlay, int ngpt, int top_at_1, const double *tau,
+                        const double *ssa, const double *g, const double *mu0, const double *toa_flux, int nband,
+                        const int *band2gpt, const double *sfc_alb_dir, const double *sfc_alb_dif,
+                        double *bnd_flux_up, double *bnd_flux_dn, double *bnd_flux_dir, double *flux_up,
+                        double *flux_dn, double *flux_dir, int memspace, void *stream) {
+  return rte_sw_byband_impl(false, device, ncol, nlay, ngpt, top_at_1, tau, ssa, g, mu0, toa_flux, nband, band2gpt,
+                            sfc_alb_dir, sfc_alb_dif, bnd_flux_up, bnd_flux_dn, bnd_flux_dir, flux_up, flux_dn, flux_dir,
+                            memspace, stream);
 }
 
 // Single-precision flavours of the per-band solvers (the reference is precision-generic through `wp`).
@@ -1933,24 +1935,18 @@ int ecckd_rte_lw_byband_f32(int device, int ncol, int nlay, int ngpt, int top_at
                             const float *lay_source, const float *lev_source_inc, const float *lev_source_dec,
                             const float *sfc_source, int nband, const int *band2gpt, const float *sfc_emis,
                             float *bnd_flux_up, float *bnd_flux_dn, float *flux_up, float *flux_dn, int memspace, void *stream) {
-  F32Scope scope;
-  auto c = [](const float *p) { return reinterpret_cast<const double *>(p); };
-  auto w = [](float *p) { return reinterpret_cast<double *>(p); };
-  return ecckd_rte_lw_byband(device, ncol, nlay, ngpt, top_at_1, n_gauss_angles, c(tau), c(lay_source), c(lev_source_inc),
-                             c(lev_source_dec), c(sfc_source), nband, band2gpt, c(sfc_emis), w(bnd_flux_up), w(bnd_flux_dn),
-                             w(flux_up), w(flux_dn), memspace, stream);
+  return rte_lw_byband_impl(true, device, ncol, nlay, ngpt, top_at_1, n_gauss_angles, dp(tau), dp(lay_source),
+                            dp(lev_source_inc), dp(lev_source_dec), dp(sfc_source), nband, band2gpt, dp(sfc_emis),
+                            dp(bnd_flux_up), dp(bnd_flux_dn), dp(flux_up), dp(flux_dn), memspace, stream);
 }
 
 int ecckd_rte_sw_byband_f32(int device, int ncol, int nlay, int ngpt, int top_at_1, const float *tau, const float *ssa,
                             const float *g, const float *mu0, const float *toa_flux, int nband, const int *band2gpt,
                             const float *sfc_alb_dir, const float *sfc_alb_dif, float *bnd_flux_up, float *bnd_flux_dn,
                             float *bnd_flux_dir, float *flux_up, float *flux_dn, float *flux_dir, int memspace, void *stream) {
-  F32Scope scope;
-  auto c = [](const float *p) { return reinterpret_cast<const double *>(p); };
-  auto w = [](float *p) { return reinterpret_cast<double *>(p); };
-  return ecckd_rte_sw_byband(device, ncol, nlay, ngpt, top_at_1, c(tau), c(ssa), c(g), c(mu0), c(toa_flux), nband, band2gpt,
-                             c(sfc_alb_dir), c(sfc_alb_dif), w(bnd_flux_up), w(bnd_flux_dn), w(bnd_flux_dir), w(flux_up),
-                             w(flux_dn), w(flux_dir), memspace, stream);
+  return rte_sw_byband_impl(true, device, ncol, nlay, ngpt, top_at_1, dp(tau), dp(ssa), dp(g), dp(mu0), dp(toa_flux), nband,
+                            band2gpt, dp(sfc_alb_dir), dp(sfc_alb_dif), dp(bnd_flux_up), dp(bnd_flux_dn), dp(bnd_flux_dir),
+                            dp(flux_up), dp(flux_dn), dp(flux_dir), memspace, stream);
 }
 
 }  // extern "C"
