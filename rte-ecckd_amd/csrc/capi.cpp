@@ -222,12 +222,6 @@ const double *table(const ecckd_model *m, size_t off, bool f32) {
 // 1 = reference order (kernels_tau.hip + kernels_planck.hip, bit-faithful expression order).
 std::atomic<int> g_arith{0};
 
-#ifndef ECCKD_LW_DEFAULT_SOLVER
-#define ECCKD_LW_DEFAULT_SOLVER 0
-#endif
-#ifndef ECCKD_GAS_SLAB_F32_DEFAULT
-#define ECCKD_GAS_SLAB_F32_DEFAULT 2
-#endif
 // Version switches of the (un-pinned) RTE-RRTMGP solvers, ecckd_set_solver_option.  Process-wide, read once
 // per call; the defaults are the v1.5-era forms the oracle restates.
 struct SolverOptions {
@@ -237,13 +231,13 @@ struct SolverOptions {
   std::atomic<double> sw_k_floor{1.e-12};
   std::atomic<int> sw_dir_clamp{0};
   // implementation choices (same results to ~1e-16 relative): which fp64 / 60-layer longwave solver runs
-  std::atomic<int> lw_solver{ECCKD_LW_DEFAULT_SOLVER};   // 0 register-resident (kernels_rte_lw.hip), 1 layer-split
+  std::atomic<int> lw_solver{0};   // 0 register-resident (kernels_rte_lw.hip), 1 layer-split
   std::atomic<int> lw_split_seg{10};
   // ... and whether the call-constant gases of a pass share one slab slot (merge_scalar_gases(); ~1e-16 relative on tau)
   std::atomic<int> gas_merge_scalars{1};
   std::atomic<int> lw_tail_split{1};
   std::atomic<int> sw_tail_split{1};
-  std::atomic<int> gas_slab_f32{ECCKD_GAS_SLAB_F32_DEFAULT};   // fp64 gas optics over the float32 image of the tables in LDS
+  std::atomic<int> gas_slab_f32{2};   // fp64 gas optics over the float32 image of the tables in LDS (2: auto)
   std::atomic<int> sw_solver{0};   // 0 layer-systolic (kernels_rte_sw_sys.hip; up to 60 layers), 1 per-lane two-pass kernel
 };
 SolverOptions g_opt;

@@ -73,27 +73,14 @@ __device__ __forceinline__ void static_for(F &&f) {
 
 // Order of the items of a chunk.  Item INDICES are: [0, NLI) look_up_table gas (g-pair p, vmr plane h: index 2p + h),
 // [NLI, NLI+NBI) bilinear slots, then NPI Planck items (g-pair p: index p; first layer only: NP2 + p).  Every g-pair ends
-// in stores: tau once its last slot is in, three or four source planes per Planck item.  ECCKD_FUSED_INTERLEAVE:
-//   0  slot-major: all look_up_table items, all bilinear items (slot outer, g-pair inner), all Planck items -- the stores
-//      of a chunk come as one burst of 16-20 KiB per wave at its end;
-//   1  (default) the same with the Planck items spread between the bilinear items: -0.4 % in fp64, -5.5 % in fp32;
-//   2  g-pair-major: per g-pair its look_up_table items, its slots, its Planck item(s) -- four stores every tenth item;
-//      the slot addresses stay live across the pairs and the 8-g-point double instantiation spills 29 VGPRs: measured
-//      equal to 1 in fp64 and 2 % slower in fp32 (round 2, same box).
-// The arithmetic per g-point is the same in every order (look_up_table gas first, then the slots in order).
+// in stores: tau once its last slot is in, three or four source planes per Planck item.  The sequence: all look_up_table
+// items, then the bilinear items (slot outer, g-pair inner) with the Planck items spread between them.  Against all
+// Planck items at the end (the stores of a chunk in one burst of 16-20 KiB per wave) that measured -0.4 % in fp64 and
+// -5.5 % in fp32; g-pair-major order (four stores every tenth item) spilled 29 VGPRs in the 8-g-point double
+// instantiation and measured equal in fp64, 2 % slower in fp32 (round 2, same box).
 // seq_item(pos) = index of the item at position pos of the chunk's sequence; bil_slot / bil_pair decode a bilinear index.
-#ifndef ECCKD_FUSED_INTERLEAVE
-#define ECCKD_FUSED_INTERLEAVE 1
-#endif
-constexpr int seq_item(int pos, int NLI, int NBI, int NPI, int NP2) {
-  if (ECCKD_FUSED_INTERLEAVE == 2) {
-    const int NB = NBI / NP2, npl = NPI / NP2, per_pair = 2 + NB + npl;
-    const int p = pos / per_pair, r = pos % per_pair;
-    if (r < 2) return 2 * p + r;
-    if (r < 2 + NB) return NLI + p * NB + (r - 2);
-    return NLI + NBI + (r - 2 - NB) * NP2 + p;
-  }
-  if (ECCKD_FUSED_INTERLEAVE == 0 || NPI == 0 || pos < NLI) return pos;
+constexpr int seq_item(int pos, int NLI, int NBI, int NPI) {
+  if (NPI == 0 || pos < NLI) return pos;
   int r = pos - NLI, b = 0, k = 0;   // r-th item after the look_up_table items
   for (int q = 0;; ++q) {
     // Planck item k follows bilinear item ((2k+1)*NBI)/(2*NPI) - 1
@@ -102,8 +89,8 @@ constexpr int seq_item(int pos, int NLI, int NBI, int NPI, int NP2) {
     if (planck_next) ++k; else ++b;
   }
 }
-constexpr int bil_slot(int b, int NB, int NP2) { return ECCKD_FUSED_INTERLEAVE == 2 ? b % NB : b / NP2; }
-constexpr int bil_pair(int b, int NB, int NP2) { return ECCKD_FUSED_INTERLEAVE == 2 ? b / NB : b % NP2; }
+constexpr int bil_slot(int b, int NP2) { return b / NP2; }
+constexpr int bil_pair(int b, int NP2) { return b % NP2; }
 
 template <typename real> __device__ __forceinline__ real selmin(real a, real b) { return a < b ? a : b; }
 template <typename real> __device__ __forceinline__ real selmax(real a, real b) { return a > b ? a : b; }
@@ -145,11 +132,7 @@ template <typename real> __device__ __forceinline__ PPoint<real> pressure_point(
 }
 
 enum { MODE_TAU = 0, MODE_LW = 1, MODE_SW = 2 };
-#ifndef ECCKD_FUSED_BLOCK_LW_ONLY   // (A/B builds: every mode in the 512-thread blocks of the longwave mode)
 constexpr int fused_block(int mode) { return mode == MODE_LW ? kBlock : kBlockSw; }
-#else
-constexpr int fused_block(int) { return kBlock; }
-#endif
 
 // "gas_slab_f32" = auto.  The fp64 slab holds R = 3 pressure rows next to the Planck table, the float32 image R = 8; the
 // widening costs 9 % where 3 rows do (measured, round 3: 13.6 against 12.6 ms at 1e6 columns) and saves a factor 3.4
@@ -579,14 +562,14 @@ __global__ void __launch_bounds__(BLOCK, (BLOCK > 512 ? 3 : sizeof(real) == 4 ? 
           real lutp[2] = {real(0), real(0)};
           static_for<0, NIT + 1>([&](auto pos_c) __attribute__((always_inline)) {
             constexpr int pos = decltype(pos_c)::value;                       // position in the sequence
-            constexpr int it = pos < NIT ? seq_item(pos, NLI, NBI, NPI, NP2) : NIT;    // item read at this position
+            constexpr int it = pos < NIT ? seq_item(pos, NLI, NBI, NPI) : NIT;    // item read at this position
             // ---------------- issue the reads of item `it` ----------------
             if constexpr (it < NLI) {                       // look_up_table gas: g-points 2*pr, 2*pr+1, vmr plane h
               constexpr int g = 2 * (it / 2), h = it & 1;
               double2_t *b = buf[pos & 1];
               b[0] = ld2b(al[4 * h], g); b[1] = ld2b(al[4 * h + 1], g); b[2] = ld2b(al[4 * h + 2], g); b[3] = ld2b(al[4 * h + 3], g);
             } else if constexpr (it < NLI + NBI) {          // one bilinear slot, one g-pair
-              constexpr int so = bil_slot(it - NLI, NB, NP2) * GC + 2 * bil_pair(it - NLI, NB, NP2);
+              constexpr int so = bil_slot(it - NLI, NP2) * GC + 2 * bil_pair(it - NLI, NP2);
               double2_t *b = buf[pos & 1];
               b[0] = ld2b(ab[0], so); b[1] = ld2b(ab[1], so); b[2] = ld2b(ab[2], so); b[3] = ld2b(ab[3], so);
             } else if constexpr (it < NIT) {                // Planck sources of one g-pair
@@ -603,7 +586,7 @@ __global__ void __launch_bounds__(BLOCK, (BLOCK > 512 ? 3 : sizeof(real) == 4 ? 
             }
             // ---------------- arithmetic of item `it - 1` ----------------
             if constexpr (pos >= 1) {
-              constexpr int pi_ = seq_item(pos - 1, NLI, NBI, NPI, NP2);       // the item read at the previous position
+              constexpr int pi_ = seq_item(pos - 1, NLI, NBI, NPI);       // the item read at the previous position
               const double2_t *b = buf[(pos - 1) & 1];
               if constexpr (pi_ < NLI) {
                 const int g0 = 2 * (pi_ / 2);
@@ -627,7 +610,7 @@ __global__ void __launch_bounds__(BLOCK, (BLOCK > 512 ? 3 : sizeof(real) == 4 ? 
                   }
                 }
               } else if constexpr (pi_ < NLI + NBI) {
-                constexpr int s = bil_slot(pi_ - NLI, NB, NP2), g0 = 2 * bil_pair(pi_ - NLI, NB, NP2);
+                constexpr int s = bil_slot(pi_ - NLI, NP2), g0 = 2 * bil_pair(pi_ - NLI, NP2);
 #pragma unroll
                 for (int q = 0; q < 2; ++q) {
                   real v = a00 * (real)b[0][q];
@@ -636,12 +619,10 @@ __global__ void __launch_bounds__(BLOCK, (BLOCK > 512 ? 3 : sizeof(real) == 4 ? 
                   else acc[g0 + q] = fma(W[s], v, acc[g0 + q]);
                   asm volatile("" : "+v"(acc[g0 + q]));
                 }
-                // tau is complete: of the whole chunk after its last bilinear item, or (g-pair-major order) of this
-                // g-pair after its last slot
-                constexpr bool pair_major = ECCKD_FUSED_INTERLEAVE == 2;
-                if (pair_major ? s == NB - 1 : pi_ == NLI + NBI - 1) {
+                // tau of the whole chunk is complete after its last bilinear item
+                if (pi_ == NLI + NBI - 1) {
 #pragma unroll
-                  for (int g = pair_major ? g0 : 0; g < (pair_major ? g0 + 2 : GC); g += 2) {
+                  for (int g = 0; g < GC; g += 2) {
                     // planes of this pair that exist: both, or (g-point counts that are not a multiple of the chunk) only the
                     // first one -- then the half-wave that holds it stores alone -- or none
                     const int npl = FULL ? 2 : ng - (gb + g);
@@ -804,14 +785,10 @@ hipError_t launch_mode(const FusedArgs &a, size_t lds, int NBsel, bool anyclamp,
   const int ng = a.tau.ng;
   if (anyclamp && ng % 4 == 0) return launch_one<real, 4, kTauPassGases, true, true, MODE>(a, lds, s);
   if (anyclamp) return launch_one<real, 4, kTauPassGases, false, true, MODE>(a, lds, s);
-#ifndef ECCKD_FUSED_NOGC8   // (experiment: chunks of four g-points only)
   if (NBsel == 2 && ng % 8 == 0) return launch_one<real, 8, 2, true, false, MODE>(a, lds, s);
-#endif
   if (NBsel == 2 && ng % 4 == 0) return launch_one<real, 4, 2, true, false, MODE>(a, lds, s);
   if (NBsel == 2) return launch_one<real, 4, 2, false, false, MODE>(a, lds, s);
-#ifndef ECCKD_FUSED_NOGC8
   if (NBsel == 7 && ng % 8 == 0) return launch_one<real, 8, 7, true, false, MODE>(a, lds, s);
-#endif
   if (NBsel == 7 && ng % 4 == 0) return launch_one<real, 4, 7, true, false, MODE>(a, lds, s);
   if (NBsel == 5 && ng % 4 == 0) return launch_one<real, 4, 5, true, false, MODE>(a, lds, s);
   if (NBsel == 5) return launch_one<real, 4, 5, false, false, MODE>(a, lds, s);
@@ -831,28 +808,12 @@ bool slab32_applies(int mode, int ng, int nbil, bool anyclamp) {
 
 void pick_shape(int ng, int nbil, bool anyclamp, int *GC, int *NB) {
   const int nb = pick_nb(nbil);
-#ifdef ECCKD_FUSED_NOGC8
-  if (ng % 8 == 0) ng += 4;
-#endif
   if (anyclamp) { *GC = 4; *NB = kTauPassGases; }
   else if (nb == 2) { *GC = ng % 8 == 0 ? 8 : 4; *NB = 2; }
   else if (nb == 7 && ng % 8 == 0) { *GC = 8; *NB = 7; }
   else if (nb == 7 && ng % 4 == 0) { *GC = 4; *NB = 7; }
   else if (nb == 5) { *GC = 4; *NB = 5; }
   else { *GC = 4; *NB = kTauPassGases; }
-}
-
-// LDS a block may take: all of a CU's (one block per CU), or ECCKD_FUSED_LDS_KB for experiments with several blocks per CU
-size_t lds_budget(int f32 = 0) {
-#ifdef ECCKD_F32_LDS_KB      // (experiment: two single-precision blocks per CU)
-  if (f32 == 1) return (size_t)ECCKD_F32_LDS_KB * 1024;
-#endif
-  (void)f32;
-#ifdef ECCKD_FUSED_LDS_KB
-  return (size_t)ECCKD_FUSED_LDS_KB * 1024;
-#else
-  return (size_t)kLdsBudget;
-#endif
 }
 
 }  // namespace
@@ -867,15 +828,11 @@ int fused_slab_rows(int ng, int np, int nt, int nbil, int nv_lut, int pl_rows, i
   pick_shape(ng, nbil, anyclamp != 0, &GC, &NB);
   const int ngp = (ng + GC - 1) / GC * GC;
   const size_t esz = f32 ? sizeof(float) : sizeof(double);
-  const size_t budget = lds_budget(f32);
   int R = 0;
   for (int r = 2; r <= np; ++r) {
-    if (esz * (size_t)f_layout(ngp, np, nt, nbil, NB, nv_lut, r, pl_rows, f32 == 2 ? 2 : 1, block / 64).total <= budget) R = r;
+    if (esz * (size_t)f_layout(ngp, np, nt, nbil, NB, nv_lut, r, pl_rows, f32 == 2 ? 2 : 1, block / 64).total <= (size_t)kLdsBudget) R = r;
     else break;
   }
-#ifdef ECCKD_FUSED_MAXROWS   // (experiments: cap the slab)
-  if (R > ECCKD_FUSED_MAXROWS) R = ECCKD_FUSED_MAXROWS;
-#endif
   return R >= min_rows ? R : 0;
 }
 
@@ -1012,7 +969,7 @@ hipError_t prepare_gas_fused(FusedArgs &a, FusedPlan &plan) {
   t.R = fused_slab_rows(t.ng, t.np, t.nt, t.nbil, nv_lut, a.pw, 0, anyclamp, store, block);
   const size_t lds = (store ? sizeof(float) : sizeof(double)) *
                      (size_t)f_layout(ngp, t.np, t.nt, t.nbil, NB, nv_lut, t.R, a.pw, store == 2 ? 2 : 1, block / 64).total;
-  if (lds > lds_budget(store)) return hipErrorInvalidValue;
+  if (lds > (size_t)kLdsBudget) return hipErrorInvalidValue;
   // one block per CU (LDS-bound): a block count that is a multiple of the 256 CUs keeps the last
   // round of blocks full
   const long ntiles = ((long)t.ncol + block - 1) / block;

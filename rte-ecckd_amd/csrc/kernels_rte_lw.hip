@@ -73,16 +73,12 @@ __device__ __forceinline__ real gsum(real v) {
 // gfx950 (193 clocks per wave instruction, tools/ubench_atomic.hip) against 6-13 clocks for
 // ds_add_f64, and the broadband sum is the better for it.
 // Every lane issues the atomic and non-owners add +0.0, which leaves the sum bit-identical whatever
-// order the LDS unit serialises them in.  Exec-masking the owners (ECCKD_LW_MASKED) makes the
+// order the LDS unit serialises them in.  Exec-masking the owners makes the
 // atomic itself cheaper (10.0 against 12.9 clocks at 4 waves per CU) but the exec juggling costs
 // more than that in the kernel: measured 2-5 % slower.
 template <typename real>
 __device__ __forceinline__ void acc_add(double *p, real v, bool owner) {
-#ifdef ECCKD_LW_MASKED
-  if (owner) __hip_atomic_fetch_add(p, (double)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-#else
   __hip_atomic_fetch_add(p, owner ? (double)v : 0., __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-#endif
 }
 
 // OFF32 (the exact-layer-count variants): the inputs of a g-point group are addressed as a wave-uniform pointer to the
@@ -203,17 +199,11 @@ __global__ void __launch_bounds__(64) rte_lw_kernel(const RteLwArgs a) {
         asm volatile("" : "+v"(vo));
         return;
       }
-#ifndef ECCKD_LW_PLAIN_LOADS   // nontemporal: read-once streams
+      // nontemporal: read-once streams
       ptau[slot] = __builtin_nontemporal_load(P(a.tau) + qn);
       play[slot] = __builtin_nontemporal_load(P(a.lay_source) + qn);
       pbdn[slot] = __builtin_nontemporal_load(Bdn + qn);
       if (!SHARED) pbup[slot] = __builtin_nontemporal_load(Bup + qn);
-#else
-      ptau[slot] = P(a.tau)[qn];
-      play[slot] = P(a.lay_source)[qn];
-      pbdn[slot] = Bdn[qn];
-      if (!SHARED) pbup[slot] = Bup[qn];
-#endif
       if (!PAD || present(abs_layer(sl + 1))) qn += qstep;
       asm volatile("" : "+v"(qn));
     };
@@ -393,12 +383,10 @@ hipError_t launch_ser(const RteLwArgs &a, hipStream_t s) {
 template <typename real, int NL, int CW, bool EXACT, bool OVER, bool SHARED>
 hipError_t launch_one(const RteLwArgs &a, hipStream_t s) {
   if constexpr (EXACT) {   // 32-bit lane offsets when the planes of a g-point group span less than 4 GiB (see OFF32)
-#ifndef ECCKD_LW_NO_OFF32
-    // (ECCKD_LW_NO_OFF32 in the environment: tests run the 64-bit form, which only calls beyond 4.4e6 columns take otherwise)
+    // (the environment hook lets tests run the 64-bit form, which only calls beyond 4.4e6 columns take otherwise)
     if ((double)a.ncol * a.nlay * (64 / CW) * sizeof(real) < 4294967296. && !getenv("ECCKD_LW_NO_OFF32"))
       return a.series3 ? launch_ser<real, NL, CW, EXACT, OVER, SHARED, true, true>(a, s)
                        : launch_ser<real, NL, CW, EXACT, OVER, SHARED, false, true>(a, s);
-#endif
   }
   return a.series3 ? launch_ser<real, NL, CW, EXACT, OVER, SHARED, true>(a, s)
                    : launch_ser<real, NL, CW, EXACT, OVER, SHARED, false>(a, s);

@@ -9,9 +9,9 @@
 // share a column are summed with a wave shuffle butterfly into wave-private LDS accumulators.
 // Two passes per (column, g-point): bottom->top computes the two-stream coefficients and runs the
 // adding recurrences with the source normalised by the direct beam (which is only known on the way
-// down); top->bottom propagates the direct beam and the fluxes.  What the second pass needs goes
-// through a per-wave global scratch ring ([array][level][lane], 512 B coalesced rows); see the
-// RECOMPUTE note at the kernel for what is stored and what is computed twice.
+// down); top->bottom propagates the direct beam and the fluxes.  The per-level albedo and source go
+// through a per-wave global scratch ring ([array][level][lane], 512 B coalesced rows); the second pass
+// recomputes the two-stream coefficients (see rte_sw_body for why).
 // (Registers cannot hold it next to a useful occupancy: the coefficient arithmetic is ~250 fp64
 // instructions per cell and needs several waves per SIMD to issue at rate.)
 // Any layer count and both precisions: the route of every call the layer-systolic solver does not serve (more than 60
@@ -53,10 +53,6 @@ __device__ __forceinline__ double gsum(double v) {
 #ifndef ECCKD_SW_CW
 #define ECCKD_SW_CW 16
 #endif
-#ifndef ECCKD_SW_RECOMPUTE
-#define ECCKD_SW_RECOMPUTE 1
-#endif
-constexpr bool kSwRecompute = ECCKD_SW_RECOMPUTE != 0;
 #ifndef ECCKD_SW_PF
 #define ECCKD_SW_PF 3
 #endif
@@ -69,12 +65,11 @@ __device__ __forceinline__ void acc_add(double *p, double v, bool owner) {
   __hip_atomic_fetch_add(p, owner ? v : 0., __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
 }
 
-// RECOMPUTE = true: pass 2 reads tau/ssa/g again and recomputes the two-stream coefficients; only the
-// two per-level quantities go through the scratch ring (24 + 16 + 24 + 16 = 80 B/cell of traffic,
-// twice the arithmetic).  RECOMPUTE = false: pass 1 stores the four per-layer products pass 2
-// needs as well (24 + 48 + 48 = 120 B/cell).  The kernel is bound by that traffic, not by the
-// arithmetic (0.25 VALU wave-instr/clk/CU of 0.81 available at this occupancy): measured 4.52 ms
-// stored vs 3.85 ms recomputed per 1e5 columns x 27 g-points (recomputed: 52 % of the fp64 VALU rate).
+// Pass 2 reads tau/ssa/g again and recomputes the two-stream coefficients; only the two per-level
+// quantities go through the scratch ring (24 + 16 + 24 + 16 = 80 B/cell of traffic, twice the
+// arithmetic).  Storing the four per-layer products pass 2 needs as well costs 120 B/cell, and the
+// kernel is bound by that traffic, not by the arithmetic: measured 4.52 ms stored vs 3.85 ms
+// recomputed per 1e5 columns x 27 g-points (recomputed: 52 % of the fp64 VALU rate).
 //
 // real: storage and arithmetic type of everything per cell (inputs, two-stream arithmetic, scratch ring, outputs); the
 // g-point sums, the LDS accumulators and the tail partials are double whatever `real` is, as in rte_sw_sys_kernel.
@@ -82,7 +77,7 @@ __device__ __forceinline__ void acc_add(double *p, double v, bool owner) {
 // rte_sw_sys_kernel's expressions (src/gas_optics_ecckd.f90:313-317,455-472); the lane's layer slots then prefetch the two
 // level pressures of a layer in place of its ssa and g.
 // The kernels (rte_sw_kernel, below) are thin entries to this body.
-template <typename real, int CW, bool RECOMPUTE, bool FAST, bool CLAMP, bool DERIVE>
+template <typename real, int CW, bool FAST, bool CLAMP, bool DERIVE>
 __device__ __forceinline__ void rte_sw_body(const RteSwArgs &a) {
   constexpr int GW = 64 / CW;
   // (fp32 DERIVE: the correctly rounded fp32 division of ssa makes three layers in flight spill; two do not)
@@ -97,13 +92,10 @@ __device__ __forceinline__ void rte_sw_body(const RteSwArgs &a) {
   double *acc_up = acc, *acc_dn = acc + nlev * CW, *acc_dir = acc + 2 * nlev * CW;
   const long lay0 = a.top_at_1 ? 0 : nlay - 1, lev0 = a.top_at_1 ? 0 : nlay;
   const long lstep = a.top_at_1 ? 1 : -1;
-  // scratch ring of this wave: level arrays (albedo, normalised source) first, then -- unless they
-  // are recomputed -- the four layer arrays; each [index][64 lanes]
-  constexpr int NLAYARR = RECOMPUTE ? 0 : 4;
+  // scratch ring of this wave: the level arrays albedo and normalised source, each [level][64 lanes]
   // (elements of `real`: the fp32 ring takes half of what rte_sw_scratch_bytes provides)
-  real *sc = Q(a.scratch) + (long)blockIdx.x * ((long)NLAYARR * nlay + 2L * nlev) * 64 + lane;
+  real *sc = Q(a.scratch) + (long)blockIdx.x * (2L * nlev) * 64 + lane;
   real *sAlb = sc, *sSrc = sc + 64L * nlev;
-  real *sA = sSrc + 64L * nlev, *sB = sA + 64L * nlay, *sC = sB + 64L * nlay, *sTn = sC + 64L * nlay;
   const int ngroups = (ng + GW - 1) / GW;
   const long ntiles = ((long)ncol + CW - 1) / CW;
   const real k_floor = (real)a.k_floor;
@@ -181,12 +173,6 @@ __device__ __forceinline__ void rte_sw_body(const RteSwArgs &a) {
         fetch(s - PF > 0 ? s - PF : 0, ptau[d], pssa[d], pg[d]);
         const TwoStreamT<real> ts = props(ctau, cx, cy);
         const real denom = rcp<FAST>(real(1) - ts.Rdif * albedo);                          // adding, Eq 10
-        if (!RECOMPUTE) {
-          sA[64L * s] = ts.Tdif * denom;
-          sB[64L * s] = ts.Rdif * denom;
-          sC[64L * s] = ts.Tdir * denom;
-          sTn[64L * s] = ts.Tnoscat;
-        }
         // Eq 11 divided by F_dir(l): src_up = Rdir*F_dir(l), src_dn = Tdir*F_dir(l), src(l+1) = nsrc*Tnoscat*F_dir(l)
         nsrc = ts.Rdir + ts.Tdif * denom * (nsrc * ts.Tnoscat + albedo * ts.Tdir);
         albedo = ts.Rdif + ts.Tdif * ts.Tdif * albedo * denom;                        // Eq 9
@@ -218,7 +204,7 @@ __device__ __forceinline__ void rte_sw_body(const RteSwArgs &a) {
       for (int d = 0; d < PF; ++d) {
         const int sl = d < nlay ? d : nlay - 1;
         palb[d] = sAlb[64L * (sl + 1)]; pnsrc[d] = sSrc[64L * (sl + 1)];
-        if (RECOMPUTE) fetch(sl, ptau[d], pssa[d], pg[d]);
+        fetch(sl, ptau[d], pssa[d], pg[d]);
       }
       auto layer2 = [&](int s, auto slot_c) __attribute__((always_inline)) {   // (fixed prefetch slots: see pass 1)
         constexpr int d = decltype(slot_c)::value;
@@ -227,16 +213,11 @@ __device__ __forceinline__ void rte_sw_body(const RteSwArgs &a) {
         {
           const int sn = s + PF < nlay ? s + PF : nlay - 1;
           palb[d] = sAlb[64L * (sn + 1)]; pnsrc[d] = sSrc[64L * (sn + 1)];
-          if (RECOMPUTE) fetch(sn, ptau[d], pssa[d], pg[d]);
+          fetch(sn, ptau[d], pssa[d], pg[d]);
         }
-        real A, B, C, Tn;
-        if (RECOMPUTE) {
-          const TwoStreamT<real> ts = props(ctau, cx, cy);
-          const real denom = rcp<FAST>(real(1) - ts.Rdif * alb_next);  // the same expression as in pass 1: same bits
-          A = ts.Tdif * denom; B = ts.Rdif * denom; C = ts.Tdir * denom; Tn = ts.Tnoscat;
-        } else {
-          A = sA[64L * s]; B = sB[64L * s]; C = sC[64L * s]; Tn = sTn[64L * s];
-        }
+        const TwoStreamT<real> ts = props(ctau, cx, cy);
+        const real denom = rcp<FAST>(real(1) - ts.Rdif * alb_next);  // the same expression as in pass 1: same bits
+        const real A = ts.Tdif * denom, B = ts.Rdif * denom, C = ts.Tdir * denom, Tn = ts.Tnoscat;
         const real fdir_next = Tn * fdir;
         const real src_next = nsrc_next * fdir_next;
         fdn = A * fdn + B * src_next + C * fdir;
@@ -276,14 +257,14 @@ __device__ __forceinline__ void rte_sw_body(const RteSwArgs &a) {
 }
 
 // fp64, ssa / g / toa read from memory: the instantiations the API path has always taken, under their own names
-template <int CW, bool RECOMPUTE, bool FAST, bool CLAMP>
+template <int CW, bool FAST, bool CLAMP>
 __global__ void __launch_bounds__(64, ECCKD_SW_WAVES_PER_SIMD) rte_sw_kernel(const RteSwArgs a) {
-  rte_sw_body<double, CW, RECOMPUTE, FAST, CLAMP, false>(a);
+  rte_sw_body<double, CW, FAST, CLAMP, false>(a);
 }
 // single precision, and the fused form (DERIVE) in either precision
-template <typename real, int CW, bool RECOMPUTE, bool FAST, bool CLAMP, bool DERIVE>
+template <typename real, int CW, bool FAST, bool CLAMP, bool DERIVE>
 __global__ void __launch_bounds__(64, ECCKD_SW_WAVES_PER_SIMD) rte_sw_kernel(const RteSwArgs a) {
-  rte_sw_body<real, CW, RECOMPUTE, FAST, CLAMP, DERIVE>(a);
+  rte_sw_body<real, CW, FAST, CLAMP, DERIVE>(a);
 }
 
 // Sums the per-group partial fluxes of the tail tiles in group order: the order in which a whole-tile wave adds the
@@ -333,12 +314,12 @@ size_t rte_sw_scratch_bytes(int ncol, int nlay, int ng) {
   (void)ng;
   long tiles = ((long)ncol + ECCKD_SW_CW - 1) / ECCKD_SW_CW;
   if (tiles > kSwWaves) tiles = kSwWaves;
-  return sizeof(double) * (size_t)((kSwRecompute ? 0L : 4L) * nlay + 2L * (nlay + 1)) * 64 * (size_t)tiles;
+  return sizeof(double) * (size_t)(2L * (nlay + 1)) * 64 * (size_t)tiles;
 }
 
 namespace {
 size_t sw_ring_bytes(int nlay, long blocks) {
-  return sizeof(double) * (size_t)((kSwRecompute ? 0L : 4L) * nlay + 2L * (nlay + 1)) * 64 * (size_t)blocks;
+  return sizeof(double) * (size_t)(2L * (nlay + 1)) * 64 * (size_t)blocks;
 }
 }  // namespace
 
@@ -372,21 +353,21 @@ size_t rte_sw_tail_plan(const RteSwArgs &a, long *tail_first, size_t *partials_a
 }
 
 namespace {
-// The instantiations a call can take: fp64 in both arithmetic modes through the 4-parameter kernel; single precision in
+// The instantiations a call can take: fp64 in both arithmetic modes through the 3-parameter kernel; single precision in
 // both modes; the fused form (DERIVE) in the fast mode only (ecckd_sw_fluxes refuses reference-order arithmetic).
 typedef void (*RteSwKernel)(const RteSwArgs);
 template <typename real, bool DERIVE>
 RteSwKernel rte_sw_kernel_for(const RteSwArgs &a) {
   constexpr int CW = ECCKD_SW_CW;
   if constexpr (std::is_same<real, double>::value && !DERIVE)
-    return a.dir_clamp ? (a.exact_division ? rte_sw_kernel<CW, kSwRecompute, false, true> : rte_sw_kernel<CW, kSwRecompute, true, true>)
-                       : (a.exact_division ? rte_sw_kernel<CW, kSwRecompute, false, false> : rte_sw_kernel<CW, kSwRecompute, true, false>);
+    return a.dir_clamp ? (a.exact_division ? rte_sw_kernel<CW, false, true> : rte_sw_kernel<CW, true, true>)
+                       : (a.exact_division ? rte_sw_kernel<CW, false, false> : rte_sw_kernel<CW, true, false>);
   else if constexpr (DERIVE)
     return a.exact_division ? nullptr
-                            : (a.dir_clamp ? rte_sw_kernel<real, CW, kSwRecompute, true, true, true> : rte_sw_kernel<real, CW, kSwRecompute, true, false, true>);
+                            : (a.dir_clamp ? rte_sw_kernel<real, CW, true, true, true> : rte_sw_kernel<real, CW, true, false, true>);
   else
-    return a.dir_clamp ? (a.exact_division ? rte_sw_kernel<real, CW, kSwRecompute, false, true, false> : rte_sw_kernel<real, CW, kSwRecompute, true, true, false>)
-                       : (a.exact_division ? rte_sw_kernel<real, CW, kSwRecompute, false, false, false> : rte_sw_kernel<real, CW, kSwRecompute, true, false, false>);
+    return a.dir_clamp ? (a.exact_division ? rte_sw_kernel<real, CW, false, true, false> : rte_sw_kernel<real, CW, true, true, false>)
+                       : (a.exact_division ? rte_sw_kernel<real, CW, false, false, false> : rte_sw_kernel<real, CW, true, false, false>);
 }
 }  // namespace
 

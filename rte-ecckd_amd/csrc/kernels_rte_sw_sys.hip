@@ -6,9 +6,9 @@
 // [RTE-ext: SURVEY.md Appendix B.2].  The two-stream coefficients are those of kernels_rte_sw.hip (shared
 // sw_two_stream.hpp).  In the reference-order arithmetic mode the adding recurrences are the same expressions in the
 // same order too, so a (column, g-point) pair gets the same bits from either kernel.  In the fast mode the U sweep
-// hands its pair on in a division-free (projective) form and the sweeps use FMA chains (ECCKD_SYS_PROJ,
-// ECCKD_SYS_FMA_CHAIN below): the two kernels then agree to the last bits only.  The g-point sum is taken in g-point
-// order 1..ngpt here (what sum_broadband does).
+// hands its pair on in a division-free (projective) form and the sweeps use FMA chains (see the sweeps below): the two
+// kernels then agree to the last bits only.  The g-point sum is taken in g-point order 1..ngpt here (what
+// sum_broadband does).
 //
 // Why another form.  The adding method needs the coefficients of every layer twice, bottom -> top (albedo and
 // source of the stack below) and top -> bottom (fluxes).  kernels_rte_sw.hip gives a lane one (column, g-point) and
@@ -45,34 +45,11 @@ namespace {
 constexpr int kSysWaves = ECCKD_SYS_WAVES;   // waves per block: three per SIMD (<= 168 VGPRs), one block per CU
 constexpr int kSysLPW = ECCKD_SYS_LPW;       // layers per wave
 constexpr int kSysMaxLay = kSysWaves * kSysLPW;
-#ifndef ECCKD_SYS_FMA_CHAIN
-#define ECCKD_SYS_FMA_CHAIN 1
-#endif
-constexpr bool kSysFmaChain = ECCKD_SYS_FMA_CHAIN != 0;
-// Fast arithmetic mode, what a wave does while it holds the token (see the sweeps below):
-//   ECCKD_SYS_PROJ  U: the pair handed upwards comes from a division-free (projective) form of the adding recurrence -- two
-//                   dependent operations per layer instead of six -- and the wave's own per-layer values, which only its D
-//                   needs, are computed after the token has moved on;
-//   ECCKD_SYS_DPRE  D: everything that does not depend on the incoming pair is multiplied out before the token arrives
-//                   (direct-beam transmittances as prefix products): one dependent FMA per layer on the way to the hand-off.
-//                   Worth 6 % while the sweeps set the pace; with the one-round hand-off, the polling priority and the
-//                   leaner coefficients the kernel runs within 4 % of its instruction stream without the waits, and the three
-//                   extra instructions per cell cost more than the shorter D sweep returns (1.57 -> 1.54 ms without it,
-//                   profiles/r03_ab_sw20.txt, r03_ab_sw21.txt): off by default, kept as a build option.
-#ifndef ECCKD_SYS_PROJ
-#define ECCKD_SYS_PROJ 1
-#endif
-#ifndef ECCKD_SYS_DPRE
-#define ECCKD_SYS_DPRE 0
-#endif
 constexpr int kSysSpinLimit = 1 << 22;   // polls of a flag before the block gives up (a lost hand-off never hangs the GPU)
-
-#ifdef ECCKD_SYS_TIMING   // (variant build only: s_memtime stamps of one g-point step of block 0, read back by tools/sys_timing.py)
-__device__ long long g_sys_times[kSysWaves][8];
-#define SYS_STAMP(i) do { if (blockIdx.x == 0 && unit == blockIdx.x + gridDim.x && g == g_begin + 10 && lane == 0) g_sys_times[w][i] = (long long)__builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define SYS_STAMP(i) do {} while (0)
-#endif
+// s_setprio of the wave that holds the token, and of the next wave in line while it polls: the sweeps are the critical
+// path of the block and issue ahead of the coefficient arithmetic of the other waves of the SIMD (without it +10 %,
+// profiles/r03_ab_sw15.txt)
+constexpr int kSysTokenPrio = 3;
 
 struct SysLds {
   int flag_u[kSysWaves];   // sequence number of the (albedo, source) pair waiting in hand-off slot w
@@ -90,31 +67,18 @@ __device__ __forceinline__ void static_for_sys(F &&f) {
 }
 
 // Hand-off between neighbouring waves of a block: the pair of values of every lane in an LDS slot, then a flag word
-// with the sequence number of the step (release); the consumer polls the flag -- one broadcast dword per poll -- and
-// reads its pair after it (acquire).  Measured in round 3 (same box, 1e5 columns, kernel times): this form 1.75 ms;
-// no flag, the slot's own "empty" NaN mark polled instead (one LDS round trip less, but every poll moves 1 KiB per wave
-// and eleven waves poll) 1.84; that with long naps ended by the producer's s_wakeup 1.87; s_sleep 0 / 1 / 2 between
-// the polls: no difference.
+// with the sequence number of the step; the consumer polls the flag -- one broadcast dword per poll.  Measured in
+// round 3 (same box, 1e5 columns, kernel times): a flag 1.75 ms; no flag, the slot's own "empty" NaN mark polled
+// instead (one LDS round trip less, but every poll moves 1 KiB per wave and eleven waves poll) 1.84; that with long
+// naps ended by the producer's s_wakeup 1.87; s_sleep 0 / 1 / 2 between the polls: no difference.
 #ifndef ECCKD_SYS_SLEEP
 #define ECCKD_SYS_SLEEP 2   // x 64 clocks
 #endif
-#ifndef ECCKD_SYS_LIGHT_FENCES
-#define ECCKD_SYS_LIGHT_FENCES 0
-#endif
-// Waits until *flag == seq (set by another wave of this block with publish()).  Wave-uniform: every lane reads the same
+// Waits until *flag == seq (set by give_token in another wave of this block).  Wave-uniform: every lane reads the same
 // word and the comparison is scalar.
 __device__ __forceinline__ void wait_flag(int *flag, int seq, int *abort_) {
-#ifdef ECCKD_SYS_DEBUG_NOWAIT   // (timing experiments only: the work of the sweeps without their serial dependence)
-  return;
-#endif
   int spins = 0;
-#if ECCKD_SYS_LIGHT_FENCES
-  // (LDS executes the DS instructions of a wave in order: the producer's flag store cannot overtake its data stores and
-  // this wave's data reads cannot overtake the flag read whose value it has waited for -- compiler fences are enough)
-  while (__builtin_amdgcn_readfirstlane(__hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) != seq) {
-#else
   while (__builtin_amdgcn_readfirstlane(__hip_atomic_load(flag, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP)) != seq) {
-#endif
     __builtin_amdgcn_s_sleep(ECCKD_SYS_SLEEP);
     if ((++spins & 63) == 0) {
       if (__builtin_amdgcn_readfirstlane(__hip_atomic_load(abort_, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP))) return;
@@ -124,37 +88,16 @@ __device__ __forceinline__ void wait_flag(int *flag, int seq, int *abort_) {
       }
     }
   }
-#if ECCKD_SYS_LIGHT_FENCES
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#endif
-}
-__device__ __forceinline__ void publish(int *flag, int seq) {
-#if ECCKD_SYS_LIGHT_FENCES
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __hip_atomic_store(flag, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#else
-  __hip_atomic_store(flag, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-#endif
 }
 
 // The token of a sweep: the pair of values of every lane in the receiving wave's LDS slot (one 16-byte word per lane in
-// fp64), then the slot's flag word with the sequence number of the step.  ECCKD_SYS_HANDOFF:
-//   0  (until late in round 3) release store of the flag behind an s_waitcnt on the data; the receiver polls the flag
-//      with a nap between polls and reads its pair afterwards: three LDS round trips between "the sender is done" and
-//      "the receiver computes" -- measured ~500 clocks per hand-off, 24 hand-offs per g-point step, half the step;
-//   1  the LDS executes the DS instructions of a wave in order, so (i) the sender issues data and flag back to back and
-//      (ii) the receiver asks for flag AND data in one round (flag first): a flag that reads `seq` vouches for the data read
-//      behind it.  So that eleven waiting waves do not crowd the LDS queue with 1 KiB polls (the sentinel experiment of
-//      §5.4), a wave first naps on the flag of the wave the token comes FROM -- only the next wave in line polls its slot.
-#ifndef ECCKD_SYS_HANDOFF
-#define ECCKD_SYS_HANDOFF 1
-#endif
-#ifndef ECCKD_SYS_POLL_PRIO
-#define ECCKD_SYS_POLL_PRIO 3
-#endif
-#ifndef ECCKD_SYS_SLEEP2
-#define ECCKD_SYS_SLEEP2 0   // nap between the polls of the next wave in line (x 64 clocks; 0: none)
-#endif
+// fp64), then the slot's flag word with the sequence number of the step.  The LDS executes the DS instructions of a wave
+// in order, so (i) the sender issues data and flag back to back and (ii) the receiver asks for flag AND data in one round
+// (flag first): a flag that reads `seq` vouches for the data read behind it.  (A release store of the flag behind an
+// s_waitcnt on the data, polled and then followed by the read of the pair, took three LDS round trips per hand-off --
+// ~500 clocks, 24 hand-offs per g-point step, half the step: 1.57 -> 1.50 ms, profiles/r03_ab_sw13.txt.)  So that eleven
+// waiting waves do not crowd the LDS queue with 1 KiB polls (the sentinel experiment of §5.4), a wave first naps on the
+// flag of the wave the token comes FROM -- only the next wave in line polls its slot.
 template <typename real> struct SysPair { typedef real type __attribute__((ext_vector_type(2))); };
 
 // near: flag word of the wave the token comes from (nullptr: that wave starts the sweep), flag / slot: this wave's own.
@@ -163,29 +106,16 @@ __device__ __forceinline__ typename SysPair<real>::type take_token(int *near, in
   typedef typename SysPair<real>::type pair_t;
   typedef __attribute__((address_space(3))) const volatile pair_t lds_pair;
   typedef __attribute__((address_space(3))) const volatile int lds_int;
-#if ECCKD_SYS_HANDOFF == 0
-  (void)near;
-  wait_flag(flag, seq, abort_);
-  return *(lds_pair *)slot;
-#else
-#ifdef ECCKD_SYS_DEBUG_NOWAIT
-  return *(lds_pair *)slot;
-#endif
   if (near) wait_flag(near, seq, abort_);
-#if ECCKD_SYS_POLL_PRIO && !defined(ECCKD_SYS_NOPRIO)
   // the next wave in line polls at the token holder's priority: its poll is not queued behind the coefficient arithmetic
   // of the other waves of its SIMD (-3 %; profiles/r03_ab_sw17.txt, r03_ab_sw18.txt)
-  __builtin_amdgcn_s_setprio(ECCKD_SYS_POLL_PRIO);
-#endif
+  __builtin_amdgcn_s_setprio(kSysTokenPrio);
   int spins = 0;
   pair_t v;
   for (;;) {
     const int f = *(lds_int *)flag;   // (volatile: the two reads stay in this order, one s_waitcnt behind both)
     v = *(lds_pair *)slot;
     if (__builtin_amdgcn_readfirstlane(f) == seq) break;
-#if ECCKD_SYS_SLEEP2
-    __builtin_amdgcn_s_sleep(ECCKD_SYS_SLEEP2);
-#endif
     if ((++spins & 255) == 0) {
       if (__builtin_amdgcn_readfirstlane(__hip_atomic_load(abort_, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP))) break;
       if (spins > kSysSpinLimit) {
@@ -196,7 +126,6 @@ __device__ __forceinline__ typename SysPair<real>::type take_token(int *near, in
   }
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
   return v;
-#endif
 }
 template <typename real>
 __device__ __forceinline__ void give_token(int *flag, real *slot, real a, real b, int seq) {
@@ -206,12 +135,8 @@ __device__ __forceinline__ void give_token(int *flag, real *slot, real a, real b
   pair_t v;
   v[0] = a; v[1] = b;
   *(lds_pair *)slot = v;
-#if ECCKD_SYS_HANDOFF == 0
-  publish(flag, seq);
-#else
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   *(lds_int *)flag = seq;
-#endif
 }
 
 // 1/x for the adding recurrence of the fast arithmetic mode: rcp<true> of sw_two_stream.hpp (hardware reciprocal and one
@@ -369,7 +294,6 @@ __global__ void __launch_bounds__(64 * kSysWaves) rte_sw_sys_kernel(const RteSwA
       real albedo = real(0), nsrc = real(0);
       if (step) {
         ++seq;
-        SYS_STAMP(0);
         // ---- P ----
         if (parking) {
 #pragma unroll
@@ -382,35 +306,28 @@ __global__ void __launch_bounds__(64 * kSysWaves) rte_sw_sys_kernel(const RteSwA
             st[l][0] = ts.Rdif; st[l][1] = ts.Tdif; st[l][2] = ts.Rdir; st[l][3] = ts.Tdir; st[l][4] = ts.Tnoscat;
           });
         }
-        SYS_STAMP(1);
       }
       if (step) {
         if (!parking && g + 1 < g_end) load_props(g + 1);   // in flight during the sweeps
 
         // ---- U: adding, bottom -> top.  The source is carried normalised by the direct beam at its own level (the
         // beam is only known on the way down): src(l) = nsrc(l) * F_dir(l), F_dir(l+1) = Tnoscat(l) * F_dir(l) ----
-        SYS_STAMP(2);
         typename SysPair<real>::type tok;
         tok[0] = pb0; tok[1] = pb1;
         if (!bottom_wave) tok = take_token<real>(w + 1 < nwa - 1 ? &ctl->flag_u[w + 1] : nullptr, &ctl->flag_u[w], slot_u, seq, &ctl->abort_);
-        SYS_STAMP(3);
-#ifndef ECCKD_SYS_NOPRIO
-        // the sweeps are the critical path of the block: the wave that holds the token issues ahead of the waves of
-        // its SIMD that are still computing coefficients
-        __builtin_amdgcn_s_setprio(3);
-#endif
+        __builtin_amdgcn_s_setprio(kSysTokenPrio);   // (the token holder: see kSysTokenPrio)
         albedo = tok[0];
         nsrc = tok[1];
         if (bottom_wave && g + 1 < g_end) load_albedos(g + 1);
-        constexpr bool kProj = FAST && kSysFmaChain && ECCKD_SYS_PROJ != 0;
-        constexpr bool kDpre = FAST && kSysFmaChain && ECCKD_SYS_DPRE != 0;
-        if constexpr (kProj) {
+        if constexpr (FAST) {
           // The pair for the wave above, ahead of everything else.  With albedo = p/q and nsrc = s/q the recurrence
           //   albedo' = Rdif + Tdif^2 albedo / (1 - Rdif albedo),  nsrc' = Rdir + Tdif (nsrc Tn + albedo Tdir) / (1 - Rdif albedo)
           // is linear in (p, q, s):  q' = q - Rdif p,  p' = Rdif q' + Tdif^2 p,  s' = Rdir q' + Tdif Tn s + Tdif Tdir p,
           // two dependent operations per layer (p -> q' -> p'; s trails by a constant) and ONE reciprocal per wave instead
           // of one per layer.  q' / q = 1 - Rdif albedo lies in (0, 1]: five layers cannot underflow, and the pair is
-          // handed on normalised (q = 1).  The values differ from the per-layer form below in the last bits only.
+          // handed on normalised (q = 1).  The values differ from the per-layer form below in the last bits only.  The
+          // wave's own per-layer values, which only its D needs, follow after the token has moved on (without this
+          // form +4 %, profiles/r03_ab_sw20.txt).
           if (!top_wave) {
             real p = albedo, q = real(1), sN = nsrc;
 #pragma unroll
@@ -425,10 +342,7 @@ __global__ void __launch_bounds__(64 * kSysWaves) rte_sw_sys_kernel(const RteSwA
             }
             const real rq = rcp_chain(q);
             give_token<real>(&ctl->flag_u[w - 1], slot_u_above, p * rq, sN * rq, seq);
-            SYS_STAMP(7);
-#ifndef ECCKD_SYS_NOPRIO
             __builtin_amdgcn_s_setprio(0);
-#endif
           }
         }
         real dn[LPW];
@@ -437,12 +351,12 @@ __global__ void __launch_bounds__(64 * kSysWaves) rte_sw_sys_kernel(const RteSwA
           if (FULL || l < nl) {
             const real Rdif = st[l][0], Tdif = st[l][1], Rdir = st[l][2], Tdir = st[l][3], Tn = st[l][4];
             // adding, Eq 10 / 11 / 9.  Eq 11 is divided by F_dir(l): src_up = Rdir*F_dir(l), src_dn = Tdir*F_dir(l),
-            // src(l+1) = nsrc*Tnoscat*F_dir(l).  Fast arithmetic mode (kSysFmaChain): the multiply-add pairs of the recurrence
+            // src(l+1) = nsrc*Tnoscat*F_dir(l).  Fast arithmetic mode: the multiply-add pairs of the recurrence
             // are FMAs -- the wave that holds the token issues one fp64 instruction every ~10 clocks, and every instruction
             // less shortens the critical path of the block: -5.5 % on the kernel, fluxes unchanged to 1e-13 W m-2.  The
             // reference-order mode rounds every operation on its own, as kernels_rte_sw.hip does.
             real denom, A;
-            if constexpr (FAST && kSysFmaChain) {
+            if constexpr (FAST) {
               denom = rcp_chain(fma(-Rdif, albedo, real(1)));
               A = Tdif * denom;
               dn[l] = denom;
@@ -462,35 +376,14 @@ __global__ void __launch_bounds__(64 * kSysWaves) rte_sw_sys_kernel(const RteSwA
             st[l][1] = A;
           }
         }
-        if (!kProj && !top_wave) {
+        if (!FAST && !top_wave) {
           give_token<real>(&ctl->flag_u[w - 1], slot_u_above, albedo, nsrc, seq);
-#ifndef ECCKD_SYS_NOPRIO
           __builtin_amdgcn_s_setprio(0);   // (waiting for the token to come back down)
-#endif
         }
-#ifndef ECCKD_SYS_NOPRIO
-        if (kProj && top_wave) __builtin_amdgcn_s_setprio(0);
-#endif
-        if constexpr (kDpre) {
-          // D-form of a layer: Y, A, albedo below, P, -, normalised source below, with P(l) = product of the direct-beam
-          // transmittances of this wave's layers above and including l, and Y = B nsrc_below P(l) + C P(l-1): the diffuse
-          // flux below layer l is A fdn + Y fdir_in, the beam P(l) fdir_in -- fdir_in the beam that arrives with the token.
-          real Pacc = real(1);
+        if (FAST && top_wave) __builtin_amdgcn_s_setprio(0);
 #pragma unroll
-          for (int l = 0; l < LPW; ++l) {
-            if (FULL || l < nl) {
-              const real B = st[l][0] * dn[l], C = st[l][3] * dn[l];
-              const real Pn = Pacc * st[l][4];
-              st[l][0] = fma(B * st[l][5], Pn, C * Pacc);
-              st[l][3] = Pn;
-              Pacc = Pn;
-            }
-          }
-        } else {
-#pragma unroll
-          for (int l = 0; l < LPW; ++l) {
-            if (FULL || l < nl) { st[l][0] = st[l][0] * dn[l]; st[l][3] = st[l][3] * dn[l]; }
-          }
+        for (int l = 0; l < LPW; ++l) {
+          if (FULL || l < nl) { st[l][0] = st[l][0] * dn[l]; st[l][3] = st[l][3] * dn[l]; }
         }
       }
       // ---- the lower waves: coefficients of the next g-point while the token is away ----
@@ -503,57 +396,29 @@ __global__ void __launch_bounds__(64 * kSysWaves) rte_sw_sys_kernel(const RteSwA
       }
       if (step) {
         // ---- D: direct beam and fluxes, top -> bottom (Eq 12, 13) ----
-        SYS_STAMP(4);
         typename SysPair<real>::type tokd;
         tokd[0] = real(0); tokd[1] = real(0);
         if (!top_wave) tokd = take_token<real>(w > 1 ? &ctl->flag_d[w - 1] : nullptr, &ctl->flag_d[w], slot_d, seq, &ctl->abort_);
         const real h_fdn = tokd[0], h_dir = tokd[1];
-        SYS_STAMP(5);
-#ifndef ECCKD_SYS_NOPRIO
-        __builtin_amdgcn_s_setprio(3);
-#endif
+        __builtin_amdgcn_s_setprio(kSysTokenPrio);
         real fdir = top_wave ? ptoa * mu0 : h_dir;
         real fdn = top_wave ? real(0) : h_fdn;
         if (top_wave && g + 1 < g_end) load_toa(g + 1);
         const real fup0 = fdn * albedo + nsrc * fdir, fdn0 = fdn + fdir, fdir0 = fdir;   // level 0 (top wave)
         real fu[LPW], fd[LPW], fr[LPW];
-        constexpr bool kDpreD = FAST && kSysFmaChain && ECCKD_SYS_DPRE != 0;
-        if constexpr (kDpreD) {
-          const real fdir_in = fdir;
-          real Plast = real(1);
-#pragma unroll
-          for (int l = 0; l < LPW; ++l) {
-            if (FULL || l < nl) {
-              fdn = fma(st[l][1], fdn, st[l][0] * fdir_in);   // Eq 12: the one dependent operation per layer
-              fd[l] = fdn;
-              Plast = st[l][3];
-            }
-          }
-          if (!bottom_wave) {
-            give_token<real>(&ctl->flag_d[w + 1], slot_d_below, fdn, Plast * fdir_in, seq);
-          }
-#ifndef ECCKD_SYS_NOPRIO
-          __builtin_amdgcn_s_setprio(0);
-#endif
-#pragma unroll
-          for (int l = 0; l < LPW; ++l) {
-            if (FULL || l < nl) {
-              const real fdir_next = st[l][3] * fdir_in;
-              fu[l] = fma(fd[l], st[l][2], st[l][5] * fdir_next);   // Eq 13
-              fd[l] = fd[l] + fdir_next;
-              fr[l] = fdir_next;
-            }
-          }
-        }
 #pragma unroll
         for (int l = 0; l < LPW; ++l) {
-          if (!kDpreD && (FULL || l < nl)) {
+          if (FULL || l < nl) {
             const real B = st[l][0], A = st[l][1], alb_next = st[l][2], C = st[l][3], Tn = st[l][4], nsrc_next = st[l][5];
             const real fdir_next = Tn * fdir;
             const real src_next = nsrc_next * fdir_next;
-            if constexpr (FAST && kSysFmaChain) {
+            if constexpr (FAST) {
               // Eq 12 with denom multiplied in, associated so that the recurrence of the diffuse flux is ONE dependent
-              // operation per layer (the direct-beam terms run ahead of it): a dependent fp64 operation costs ~20 clocks
+              // operation per layer (the direct-beam terms run ahead of it): a dependent fp64 operation costs ~20 clocks.
+              // (Multiplying out everything that does not depend on the incoming pair before the token arrives --
+              // direct-beam transmittances as prefix products -- was worth 6 % while the sweeps set the pace; against the
+              // one-round hand-off its three extra instructions per cell cost more than the shorter sweep returns: 1.57
+              // -> 1.54 ms without it, profiles/r03_ab_sw20.txt, r03_ab_sw21.txt.)
               fdn = fma(A, fdn, fma(B, src_next, C * fdir));
               fu[l] = fma(fdn, alb_next, src_next);                          // Eq 13
             } else {
@@ -565,12 +430,10 @@ __global__ void __launch_bounds__(64 * kSysWaves) rte_sw_sys_kernel(const RteSwA
             fr[l] = fdir;
           }
         }
-        if (!kDpreD && !bottom_wave) {
+        if (!bottom_wave) {
           give_token<real>(&ctl->flag_d[w + 1], slot_d_below, fdn, fdir, seq);
         }
-#ifndef ECCKD_SYS_NOPRIO
-        if (!kDpreD) __builtin_amdgcn_s_setprio(0);
-#endif
+        __builtin_amdgcn_s_setprio(0);
         // the token has moved on: now the sums (one fire-and-forget ds_add_f64 each; every lane owns its words)
         if (top_wave) {
           __hip_atomic_fetch_add(&acc_up[lane], (double)fup0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
@@ -585,7 +448,6 @@ __global__ void __launch_bounds__(64 * kSysWaves) rte_sw_sys_kernel(const RteSwA
             if (a.flux_dir) __hip_atomic_fetch_add(&my_dir[(l + 1) * 64], (double)fr[l], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
           }
         }
-        SYS_STAMP(6);
       }
     }
 
@@ -629,9 +491,6 @@ hipError_t launch_sys2(RteSwArgs a, long blocks, hipStream_t s) {
   if (base > (size_t)kLdsBudget) return hipErrorInvalidValue;
   const int nwa = (a.nlay + kSysLPW - 1) / kSysLPW;
   long npark = (long)(((size_t)kLdsBudget - base) / sys_park_bytes(a.f32));
-#ifdef ECCKD_SYS_NPARK
-  if (npark > ECCKD_SYS_NPARK) npark = ECCKD_SYS_NPARK;
-#endif
   if (npark > nwa) npark = nwa;
   a.sys_npark = (int)npark;
   a.sys_park_at = (unsigned)base;
@@ -647,12 +506,6 @@ hipError_t launch_sys(const RteSwArgs &a, long blocks, hipStream_t s) {
 }
 
 }  // namespace
-
-#ifdef ECCKD_SYS_TIMING
-extern "C" int ecckd_debug_sys_times(long long *out) {
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_sys_times), sizeof(long long) * kSysWaves * 8);
-}
-#endif
 
 bool rte_sw_sys_applies(const RteSwArgs &a) { return a.nlay >= 1 && a.nlay <= kSysMaxLay && a.ncol > 0; }
 

@@ -5,7 +5,7 @@
 // epilogue of gas_optics_ext (:293-319, :455-460).
 //
 // Mapping (gfx950): lane -> column (coalesced 512 B wave stores into the column-fastest
-// output), block = 1024 columns of ONE layer, grid.y = layer.  At a fixed layer the columns of
+// output), block = 768 columns of ONE layer, grid.y = layer.  At a fixed layer the columns of
 // a tile differ in pressure index by at most a few rows, so the block stages a slab of R
 // consecutive pressure rows of every active table in LDS (rows padded to an odd number of
 // doubles: lanes that differ in (ip,it,iv) fall on different banks) and the g-point loop reads
@@ -21,19 +21,10 @@ namespace ecckd {
 
 namespace {
 
-#ifndef ECCKD_TAU_BLOCK
-#define ECCKD_TAU_BLOCK 768
-#endif
-#ifndef ECCKD_TAU_GC
-#define ECCKD_TAU_GC (ECCKD_TAU_BLOCK >= 1024 ? 8 : (ECCKD_TAU_BLOCK > 512 ? 16 : 32))
-#endif
 #ifndef ECCKD_TAU_SPAN
 #define ECCKD_TAU_SPAN 4
 #endif
-#ifndef ECCKD_TAU_VOLATILE
-#define ECCKD_TAU_VOLATILE 1
-#endif
-constexpr int kTauBlock = ECCKD_TAU_BLOCK;
+constexpr int kTauBlock = 768;
 constexpr int kTauWaves = kTauBlock / 64;
 // g-points whose LDS reads and arithmetic the scheduler may interleave (bounds live registers)
 constexpr int kSpan = ECCKD_TAU_SPAN;
@@ -103,11 +94,7 @@ __global__ void __launch_bounds__(kTauBlock) tau_kernel(const TauArgs a) {
   const int nv_lut = a.lut >= 0 ? a.seq[a.lut].nv : 0;
   const SlabLayout L = slab_layout(ng, np, nt, a.nbil, nv_lut, R);
   int *red = reinterpret_cast<int *>(lds + L.red);
-#if ECCKD_TAU_VOLATILE
   typedef __attribute__((address_space(3))) const volatile double lds_cvd;
-#else
-  typedef __attribute__((address_space(3))) const double lds_cvd;
-#endif
   lds_cvd *lds_v = (lds_cvd *)lds;
 
   for (int i = tid; i < np; i += kTauBlock) lds[L.tb + i] = a.temperature[i];
@@ -265,7 +252,7 @@ __global__ void __launch_bounds__(kTauBlock) tau_kernel(const TauArgs a) {
             if (fast) {
               const int o = L.lut + (ipl + R * ((it0 - 1) + nt * (iv0 - 1))) * L.SL + gb;
               const int dP = L.SL, dT = R * L.SL, dV = R * nt * L.SL;
-// volatile (optional): keeps single ds_read_b64 instead of paired ds_read2_b64
+// volatile: keeps single ds_read_b64 instead of paired ds_read2_b64
 #define LDS_LD(x) (lds_v[x])
               ECCKD_TRILINEAR(LDS_LD, o, dP, dT, dV, kSpanLut)
             } else {
@@ -371,23 +358,11 @@ hipError_t launch_tau(TauArgs &a, hipStream_t s) {
   if (chunks < 1) chunks = 1;
   a.col_chunks = (int)chunks;
   if (a.nseq > kTauPassGases) return hipErrorInvalidValue;
-  // g-points per register chunk: ECCKD_TAU_GC (32 -> exact instantiations for 32/36/27 g-points)
-#if ECCKD_TAU_GC == 8
-  if (a.ng % 8 == 0) return launch_gc<8, true>(a, lds, anyclamp, s);
-  if (a.ng % 9 == 0) return launch_gc<9, true>(a, lds, anyclamp, s);
-  return launch_gc<8, false>(a, lds, anyclamp, s);
-#elif ECCKD_TAU_GC == 16
+  // g-points per register chunk: 16 (18 or 9 where they divide the g-point count and 16 does not)
   if (a.ng % 16 == 0) return launch_gc<16, true>(a, lds, anyclamp, s);
   if (a.ng % 18 == 0) return launch_gc<18, true>(a, lds, anyclamp, s);
   if (a.ng % 9 == 0) return launch_gc<9, true>(a, lds, anyclamp, s);
   return launch_gc<16, false>(a, lds, anyclamp, s);
-#else
-  if (a.ng % 32 == 0) return launch_gc<32, true>(a, lds, anyclamp, s);
-  if (a.ng % 36 == 0) return launch_gc<36, true>(a, lds, anyclamp, s);
-  if (a.ng % 27 == 0) return launch_gc<27, true>(a, lds, anyclamp, s);
-  if (a.ng % 16 == 0) return launch_gc<16, true>(a, lds, anyclamp, s);
-  return launch_gc<16, false>(a, lds, anyclamp, s);
-#endif
 }
 
 }  // namespace ecckd

@@ -19,9 +19,6 @@ namespace {
 // against 22.  A NaN argument gives exp(-1100) = 0 (v_max_f64 returns its other operand): the callers' NaN reaches the
 // fluxes through the optical depth itself (omt / tl, tl * (...)), see lw_source_noscat below each call.
 __device__ __forceinline__ double lw_exp(double x) {
-#ifdef ECCKD_LW_OLD_MATH   // (A/B builds: the device library's exp and the compiler's `/`)
-  return exp(x);
-#endif
   x = __builtin_fmin(__builtin_fmax(x, -1100.), 1100.);
   const double n = __builtin_rint(x * 0x1.71547652b82fep+0);   // log2(e)
   double r = fma(n, -0x1.62e42fee00000p-1, x);                // ln2, upper 32 bits: n * hi is exact
@@ -51,9 +48,6 @@ __device__ __forceinline__ float lw_exp(float x) { return expf(x); }
 // where `/` gives less: both vanish against the flux.  A NaN divisor becomes 1e290 here (v_min_f64 returns its other
 // operand) and reaches the fluxes through the series branch, which the select takes for it.
 __device__ __forceinline__ double lw_div(double x, double d) {
-#ifdef ECCKD_LW_OLD_MATH
-  return x / d;
-#endif
   d = __builtin_fmin(d, 1e290);
   double r = __builtin_amdgcn_rcp(d);
   r = fma(fma(-d, r, 1.), r, r);

@@ -34,12 +34,9 @@ __device__ __forceinline__ float rcp(float x) {
 // sqrt, whose scaling of subnormal / huge arguments and special-case selects this argument never needs: x = max((g1-g2)(g1+g2),
 // k_floor) lies in [k_floor, 4], and the host raises a subnormal k_floor to the smallest normal number in this mode.
 // NaN stays NaN.
-#ifndef ECCKD_SW_LEAN_SQRT
-#define ECCKD_SW_LEAN_SQRT 1
-#endif
 template <bool FAST>
 __device__ __forceinline__ double sw_sqrt(double x) {
-  if (!FAST || !ECCKD_SW_LEAN_SQRT) return sqrt(x);
+  if (!FAST) return sqrt(x);
   const double y = __builtin_amdgcn_rsq(x);
   double g = x * y, h = 0.5 * y;
   double r = fma(-h, g, 0.5);
@@ -59,12 +56,9 @@ __device__ __forceinline__ float sw_sqrt(float x) { return sqrtf(x); }
 // powers overflow): 20 instructions against 22, any optical depth up to inf gives what exp() gives, a NaN stays a NaN
 // (the compare is false for it).  Arguments above +709 (a negative optical depth) give inf through v_ldexp_f64 up to
 // 1e15 and are not meaningful beyond.
-#ifndef ECCKD_SW_LEAN_EXP
-#define ECCKD_SW_LEAN_EXP 1
-#endif
 template <bool FAST>
 __device__ __forceinline__ double sw_exp(double x) {
-  if (!FAST || !ECCKD_SW_LEAN_EXP) return exp(x);
+  if (!FAST) return exp(x);
   x = x < -1100. ? -1100. : x;
   const double n = __builtin_rint(x * 0x1.71547652b82fep+0);   // log2(e)
   double r = fma(n, -0x1.62e42fee00000p-1, x);                // ln2, upper 32 bits: n * hi is exact

@@ -113,24 +113,16 @@ __device__ __forceinline__ void store_pair(real *&base, long plane2, unsigned vo
   // raw buffer over the whole address range above `base` (offsets are checked against 2^32 - 1 on the host side:
   // launch_gas_fused); word 3 = DATA_FORMAT_32, the value untyped buffer accesses use on gfx9
   const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)base, 0, -1, 0x00020000);
-#ifndef ECCKD_PLAIN_STORES    // nontemporal: the outputs are written once and read by the next kernel
-  constexpr int aux = 2;
-#else
-  constexpr int aux = 0;
-#endif
+  constexpr int aux = 2;   // nontemporal: the outputs are written once and read by the next kernel
   if (!masked) {
     pair_exchange(v0, v1);
     real2_t out;
     out[0] = v0;
     out[1] = v1;
-#ifndef ECCKD_DEBUG_NOSTORE   // (compile-time switch for timing experiments: arithmetic without stores)
     if (nplanes >= 2 || !upper) {
       if constexpr (sizeof(real) == 8) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(uint4_t, out), rsrc, (int)voff, 0, aux);
       else __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(uint2_t, out), rsrc, (int)voff, 0, aux);
     }
-#else
-    asm volatile("" :: "v"(out));
-#endif
   } else if (active) {
     const int plane_bytes = (int)((plane2 / 2) * (long)sizeof(real));
     if constexpr (sizeof(real) == 8) {

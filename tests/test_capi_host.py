@@ -342,5 +342,5 @@ def test_code_object_resources(pkg):
     assert len(head32) == 1 and head32[0]["spill_vgpr"] == 0 and kernel_resources.waves_per_simd(head32[0]) == 2
     sys_sw = [k for n, k in ks.items() if "rte_sw_sys_kernel<double, true, false, false, true>" in n]
     assert len(sys_sw) == 1 and kernel_resources.waves_per_simd(sys_sw[0]) == 3     # 12 waves per block, one block per CU
-    sw = [k for n, k in ks.items() if "rte_sw_kernel<16, true, true, false>" in n]
+    sw = [k for n, k in ks.items() if "rte_sw_kernel<16, true, false>" in n]
     assert len(sw) == 1 and kernel_resources.waves_per_simd(sw[0]) == 3       # 143 VGPRs: 12 waves per CU
