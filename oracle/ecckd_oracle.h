@@ -17,8 +17,9 @@
  *   rte_sw      same library: sw_two_stream, sw_source_2str, adding.
  *
  * Pinning status:
- *   gas optics  pinned by the six known-answer values SURVEY.md §8(a) records from a run
- *               of the unmodified reference module (tests/test_oracle_kat.py).
+ *   gas optics  pinned bit for bit to the unmodified reference module, built from source
+ *               into oracle/_ref by oracle.build_ref() (tests/test_oracle_vs_reference.py), and
+ *               to the six known-answer values SURVEY.md §8(a) records (tests/test_oracle.py).
  *   solvers     PARITY UNPINNED: the reference holds no fixtures for fluxes and the solver
  *               source is not in /root/reference; only analytic known-answer tests apply.
  */

@@ -1,5 +1,7 @@
 """ctypes binding of the CPU oracle (oracle/ecckd_oracle.c) plus a Python restatement of
-``load_and_init`` (example/rfmip-rad-irf/mo_load_coefficients.F90:19-203).
+``load_and_init`` (example/rfmip-rad-irf/mo_load_coefficients.F90:19-203), and of the
+reference's own gas-optics module built from a reference checkout into
+``oracle/_ref/libecckd_ref.so`` (``build_ref``, ``ref_gas_optics_int``, ``ref_gas_optics_ext``).
 
 TEST INFRASTRUCTURE ONLY.  Imported by tests/, ``__graft_entry__.smoke()`` and the
 ``cpu_baseline`` leg of bench.py -- never by the product package.
@@ -16,6 +18,7 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = os.path.join(_HERE, "libecckd_oracle.so")
+REF_LIB = os.path.join(_HERE, "_ref", "libecckd_ref.so")
 MAX_GASES = 16
 NONE_, LINEAR, LOOK_UP_TABLE, RELATIVE_LINEAR = 0, 1, 2, 3
 
@@ -44,6 +47,25 @@ class _GasConcs(C.Structure):
 def build():
     """Compile the oracle with gcc (oracle/Makefile)."""
     subprocess.check_call(["make", "-s", "-C", _HERE])
+
+
+def ref_source_dir():
+    """The reference checkout the module is built from: $REF_DIR, else a sibling ``reference``."""
+    return os.environ.get("REF_DIR", os.path.join(os.path.dirname(os.path.dirname(_HERE)), "reference"))
+
+
+def build_ref():
+    """Compile the reference's gas-optics module, unmodified and in place, with the stand-ins of
+    oracle/ref into oracle/_ref/libecckd_ref.so (oracle/Makefile) and return its path.  Without a
+    reference checkout or a Fortran compiler, returns None and leaves an existing oracle/_ref/
+    as it is (a library built elsewhere travels with the tree)."""
+    ref = ref_source_dir()
+    fc = os.environ.get("FC", "/opt/rocm/bin/amdflang")
+    if not (os.path.isfile(os.path.join(ref, "src", "gas_optics_ecckd.f90")) and os.path.exists(fc)):
+        return None
+    subprocess.check_call(["make", "-s", "-C", _HERE, "REF_DIR=" + os.path.abspath(ref), "FC=" + fc,
+                           "_ref/libecckd_ref.so"])
+    return REF_LIB
 
 
 _lib = None
@@ -244,6 +266,96 @@ def gas_optics_ext(model, plev, tlay, gases, two_stream=True):
     err = C.create_string_buffer(128)
     lib().oracle_gas_optics_ext(C.byref(m), ncol, nlay, _p(plev), _p(tlay), C.byref(gc.c), _p(tau),
                                 _p(ssa), _p(g), _p(toa), err)
+    return tau, ssa, g, toa, err.value.decode()
+
+
+# --------------------------------------------------------------------------------------
+# The reference module itself (oracle/ref/ref_harness.f90), same signatures as above.
+# --------------------------------------------------------------------------------------
+_ref = None
+_ref_model = None     # the CkdModel the library's one saved ty_gas_optics_ecckd holds
+
+
+def ref_lib():
+    """Load oracle/_ref/libecckd_ref.so; raises OSError if it has not been built."""
+    global _ref
+    if _ref is None:
+        _ref = C.CDLL(REF_LIB)
+        _ref.ecckd_ref_add_gas.argtypes = [C.c_char_p] + [C.c_int] * 6 + [_dp, _dp, C.c_double]
+    return _ref
+
+
+def _ref_load(model):
+    """Fill the reference's ty_gas_optics_ecckd with what load_and_init leaves in it for `model`."""
+    global _ref_model
+    L = ref_lib()
+    if _ref_model is model:
+        return L
+    _ref_model = None
+    sw = model.shortwave
+    L.ecckd_ref_init(model.ng, model.np_, model.nt, 0 if sw else model.ntp, _p(model.log_pressure),
+                     _p(model.temperature), _p(model.planck_function), _p(model.temperature_planck),
+                     _p(model.solar_irradiance), _p(model.rayleigh))
+    for name, t in zip(model.gas, model.tables):
+        L.ecckd_ref_add_gas(name.encode().ljust(32, b"\0"), model.ng, model.np_, model.nt, t["nv"], t["code"],
+                            int(t["composite_only"]), _p(t["coefficient"]), _p(t["mole_fraction"]),
+                            t["reference_mole_fraction"])
+    _ref_model = model
+    return L
+
+
+def _ref_concs(gases, ncol, nlay):
+    """Names (32 bytes each) and the (ngas, nlay, ncol) vmr field get_vmr returns for every gas."""
+    gases = list(gases)
+    names = b"".join(n.encode().ljust(32, b"\0") for n, _, _, _ in gases)
+    vmr = np.empty((len(gases), nlay, ncol))
+    idx_c, idx_l = np.arange(ncol)[None, :], np.arange(nlay)[:, None]
+    for q, (_, a, cs, ls) in enumerate(gases):
+        vmr[q] = _f64(a).ravel()[idx_c * int(cs) + idx_l * int(ls)]
+    return names, vmr
+
+
+def ref_limits(model):
+    """(get_press_min, get_press_max, get_temp_min, get_temp_max) of the reference module."""
+    out = np.empty(4)
+    _ref_load(model).ecckd_ref_limits(_p(out))
+    return tuple(float(v) for v in out)
+
+
+def ref_gas_optics_int(model, plev, tlay, tsfc, gases, tlev):
+    """The reference's gas_optics_int; returns what gas_optics_int returns.  Without tlev, the
+    level sources are whatever the reference left in them (it returns before writing them)."""
+    plev, tlay, tsfc = _f64(plev), _f64(tlay), _f64(tsfc)
+    nlay, ncol = tlay.shape
+    ng = model.ng
+    L = _ref_load(model)
+    names, vmr = _ref_concs(gases, ncol, nlay)
+    tau = np.zeros((ng, nlay, ncol))
+    lay, inc, dec = np.zeros_like(tau), np.zeros_like(tau), np.zeros_like(tau)
+    sfc = np.zeros((ng, ncol))
+    err = C.create_string_buffer(129)
+    tl = _f64(tlev) if tlev is not None else np.zeros((nlay + 1, ncol))
+    L.ecckd_ref_gas_optics_int(ncol, nlay, vmr.shape[0], names, _p(vmr), _p(plev), _p(tlay), _p(tsfc),
+                               int(tlev is not None), _p(tl), _p(tau), _p(lay), _p(inc), _p(dec), _p(sfc), err)
+    return tau, lay, inc, dec, sfc, err.value.decode()
+
+
+def ref_gas_optics_ext(model, plev, tlay, gases, two_stream=True):
+    """The reference's gas_optics_ext with a ty_optical_props_2str (two_stream) or a
+    ty_optical_props_1scl; returns what gas_optics_ext returns (ssa, g None for 1scl)."""
+    plev, tlay = _f64(plev), _f64(tlay)
+    nlay, ncol = tlay.shape
+    ng = model.ng
+    L = _ref_load(model)
+    names, vmr = _ref_concs(gases, ncol, nlay)
+    tau = np.zeros((ng, nlay, ncol))
+    ssa, g = np.zeros_like(tau), np.zeros_like(tau)
+    toa = np.zeros((ng, ncol))
+    err = C.create_string_buffer(129)
+    L.ecckd_ref_gas_optics_ext(ncol, nlay, vmr.shape[0], names, _p(vmr), _p(plev), _p(tlay), int(bool(two_stream)),
+                               _p(tau), _p(ssa), _p(g), _p(toa), err)
+    if not two_stream:
+        ssa = g = None
     return tau, ssa, g, toa, err.value.decode()
 
 

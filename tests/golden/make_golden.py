@@ -1,7 +1,9 @@
 """Writes tests/golden/lw_fsck_synth16.npz from the CPU oracle (oracle/ecckd_oracle.c), which is
-itself pinned bit-for-bit by the reference-run values in kat_survey.json.  The reference's own
-Fortran cannot be built or run in this environment (it needs RTE-RRTMGP), so these vectors are
-oracle outputs, not reference outputs -- DESIGN.md "Oracle" says what that means for parity.
+itself pinned bit for bit to the reference's gas-optics module built from source (oracle/_ref;
+tests/test_oracle_vs_reference.py, which also checks this file's gas-optics arrays against that
+module).  The fluxes come from the oracle's restatement of the RTE-RRTMGP solvers, which stay
+unpinned -- DESIGN.md "Oracle" says what that means for parity.  make_golden_ref.py writes the
+reference module's own outputs (ref_*.npz).
 
     python tests/golden/make_golden.py
 """

@@ -1,5 +1,6 @@
 """Shared test plumbing: product-side objects built from the synthetic generator."""
 import math
+import os
 
 import numpy as np
 
@@ -310,3 +311,94 @@ def lw_flux_changes(oracle_mod, case, top_at_1, nmus, ref, seams, **oracle_kw):
         out["tau0@%d" % l] = change(run(t, top_at_1))
     out["flip"] = change(run(case["tau"], not top_at_1))
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# Columns that take every branch of the reference's gas optics once (tests/test_oracle_vs_reference.py,
+# tests/golden/make_golden_ref.py).  Each column is named after the branch it takes.
+# ------------------------------------------------------------------------------------------------
+BRANCH_COLUMNS = ("synthetic0", "synthetic1", "p_below_grid", "p_above_110kPa", "t_above_grid", "t_below_grid",
+                  "planck_below_120K", "planck_at_120K", "planck_at_350K", "planck_above_350K", "h2o_below_lut",
+                  "h2o_above_lut", "h2o_zero", "rel_lin_below_ref", "rel_lin_at_ref", "rel_lin_above_ref",
+                  "zero_thickness", "wide_p_spread", "synthetic2", "synthetic3")
+
+
+def branch_columns(m, nlay=60, bottom_first=False, c0=3000):
+    """One synthetic column per name in BRANCH_COLUMNS, altered to take that branch of
+    src/gas_optics_ecckd.f90 in `m` (a CkdModel): the p and T clamps (:122-140, 1.0001), the h2o
+    mole-fraction clamps (:153-160, 1.001) and h2o = 0, the relative-linear gases below, exactly at
+    and above their reference mole fraction (:145-146; below it the per-gas clamp :234-238 zeroes
+    them), Planck temperatures below, at both ends of and above temperature_planck (:275-285),
+    zero-thickness layers (simple_weight = 0: tau = 0, and ssa = 0/0 in the shortwave).
+    bottom_first: levels stored surface first (simple_weight < 0).  No NaN anywhere: the reference
+    would index its tables with int(NaN)."""
+    press_min = float(np.exp(m.log_pressure[0]))
+    ncol = len(BRANCH_COLUMNS)
+    c = synthetic.columns(c0, ncol, press_min, nlay=nlay)
+    c = {k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in c.items()}
+    col = {n: i for i, n in enumerate(BRANCH_COLUMNS)}
+    for n in ("ch4", "n2o", "cfc11", "cfc12", "co2"):
+        c[n] = np.full(ncol, c[n]) if np.isscalar(c[n]) else c[n]
+    c["plev"][:, col["p_below_grid"]] *= 5e-6       # the whole column above the grid top
+    c["plev"][:, col["p_above_110kPa"]] *= 1.5
+    c["tlay"][:, col["t_above_grid"]] += 120.0      # the T grid is 5 x 20 K wide
+    c["tlay"][:, col["t_below_grid"]] -= 120.0
+    if m.temperature_planck is not None:
+        tp0, tp1 = float(m.temperature_planck[0]), float(m.temperature_planck[-1])
+        for name, t, ts in (("planck_below_120K", 100.0, 110.0), ("planck_at_120K", tp0, tp0),
+                            ("planck_at_350K", tp1, tp1), ("planck_above_350K", 400.0, 360.0)):
+            c["tlev"][:, col[name]] = t
+            c["tlay"][:, col[name]] = t
+            c["tsfc"][col[name]] = ts
+    h2o = m.tables[m.gas.index("h2o")]["mole_fraction"]
+    c["h2o"][:, col["h2o_below_lut"]] = 0.1 * h2o[0]
+    c["h2o"][:, col["h2o_above_lut"]] = 4.0 * h2o[-1]
+    c["h2o"][:, col["h2o_zero"]] = 0.0
+    for name, t in zip(m.gas, m.tables):
+        if t["code"] == 3 and name in c:
+            ref = t["reference_mole_fraction"]
+            c[name][col["rel_lin_below_ref"]] = 0.5 * ref
+            c[name][col["rel_lin_at_ref"]] = ref
+            c[name][col["rel_lin_above_ref"]] = 2.0 * ref
+    z = col["zero_thickness"]
+    c["plev"][1, z] = c["plev"][0, z]                         # the top layer
+    c["plev"][nlay // 3 + 1:nlay // 3 + 4, z] = c["plev"][nlay // 3, z]   # three layers in the middle
+    c["plev"][:, col["wide_p_spread"]] *= np.linspace(0.3, 1.4, nlay + 1)
+    c["plev"][:, col["wide_p_spread"]] = np.maximum.accumulate(c["plev"][:, col["wide_p_spread"]])
+    if bottom_first:
+        for k in ("plev", "tlev", "tlay", "h2o", "o3"):
+            c[k] = np.ascontiguousarray(c[k][::-1])
+    return c
+
+
+# ------------------------------------------------------------------------------------------------
+# Reference fixtures: inputs and outputs of the reference's own gas-optics module on the branch columns
+# (tests/golden/make_golden_ref.py writes them; the GPU suite reads them without the reference tree).
+# ------------------------------------------------------------------------------------------------
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+REF_FIXTURE_SETS = (("lw_fsck", 60), ("lw_rrtmgp", 30), ("sw_wide", 60), ("lw_fsck", 137))
+REF_FIXTURE_GASES = synthetic.GAS_ORDER + ["n2"]     # RFMIP order, no2 (unknown to the tables), then n2
+WELL_MIXED = dict(co2=420e-6, ch4=1.9e-6, n2o=3.3e-7, cfc11=2.3e-10, cfc12=5.2e-10, o2=0.209)   # ch4 below its reference
+
+
+def ref_fixture_path(key, nlay):
+    return os.path.join(GOLDEN, "ref_%s_%d.npz" % (key, nlay))
+
+
+def load_ref_fixture(key, nlay):
+    """(cols, outputs, column names) of one reference fixture.  cols as synthetic.columns gives them (scalar gases
+    as floats); outputs in the shapes and order gas_optics returns them: longwave (tau, lay_source, lev_source_inc,
+    lev_source_dec, sfc_source), shortwave (tau, ssa, g, toa_src)."""
+    z = np.load(ref_fixture_path(key, nlay))
+    cols = {}
+    for k in ("plev", "tlev", "tlay", "tsfc", "h2o", "o3") + tuple(REF_FIXTURE_GASES):
+        if k in z.files:
+            v = z[k]
+            cols[k] = float(v) if v.ndim == 0 else np.ascontiguousarray(v)
+    if key.startswith("sw"):
+        out = tuple(z[k] for k in ("tau", "ssa", "g", "toa_src"))
+    else:
+        lev = z["lev_source"]
+        out = (z["tau"], z["lay_source"], np.ascontiguousarray(lev[:, 1:]), np.ascontiguousarray(lev[:, :-1]),
+               z["sfc_source"])
+    return cols, out, [str(n) for n in z["columns"]]

@@ -1,12 +1,16 @@
 """CPU tests of the oracle itself: it is pinned against the known-answer values that SURVEY.md
-§8(a) records from the unmodified reference module, checked against the committed golden
-fixture, and the solver half (parity unpinned: RTE-RRTMGP is absent) against analytic cases."""
+§8(a) records from the unmodified reference module and against the reference module's outputs
+committed under tests/golden/ (ref_*.npz, make_golden_ref.py), checked against the committed
+golden fixture, and the solver half (parity unpinned: RTE-RRTMGP is absent) against analytic
+cases.  The gas optics is compared with a live build of the reference module, bit for bit over
+every branch, in test_oracle_vs_reference.py."""
 import json
 import os
 
 import numpy as np
 import pytest
 
+import helpers
 from conftest import LW_FSCK, LW_RRTMGP, SW_WIDE
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -111,6 +115,25 @@ def test_golden_fixture(oracle_mod):
     for name, a in (("tau", tau), ("lay_source", lay), ("lev_source_inc", inc), ("sfc_source", sfc),
                     ("flux_up", fu), ("flux_dn", fd)):
         assert np.array_equal(z[name], a), name
+
+
+@pytest.mark.parametrize("key,nlay", helpers.REF_FIXTURE_SETS)
+def test_reference_fixtures_match_oracle(oracle_mod, key, nlay):
+    """tests/golden/ref_*.npz hold the reference module's outputs (make_golden_ref.py): the oracle
+    reproduces them bit for bit, NaN cells (ssa = 0/0 of zero-thickness layers) included."""
+    path = {"lw_fsck": LW_FSCK, "lw_rrtmgp": LW_RRTMGP, "sw_wide": SW_WIDE}[key]
+    m = oracle_mod.CkdModel(path)
+    cols, ref, names = helpers.load_ref_fixture(key, nlay)
+    items = helpers.oracle_gas_items(cols, helpers.REF_FIXTURE_GASES)
+    if m.shortwave:
+        got = oracle_mod.gas_optics_ext(m, cols["plev"], cols["tlay"], items)
+        assert got[4] == "" and np.isnan(ref[1]).any()
+    else:
+        got = oracle_mod.gas_optics_int(m, cols["plev"], cols["tlay"], cols["tsfc"], items, cols["tlev"])
+        assert got[5] == ""
+    assert len(names) == cols["plev"].shape[1] and any(n.endswith("bottom_first") for n in names)
+    for a, b in zip(got, ref):
+        assert np.array_equal(np.ascontiguousarray(a).view(np.uint64), np.ascontiguousarray(b).view(np.uint64))
 
 
 # ---------------------------- solver: analytic known answers ----------------------------
