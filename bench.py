@@ -7,7 +7,12 @@ inputs and the four (ncol,nlay,ngpt) intermediates resident in HBM.  Columns are
 N GPUs = N column ranges (rank r generates columns [r*ncol, (r+1)*ncol)), no data-path
 collective: weak scaling.  See DESIGN.md "Measurement".
 
+A plain run sets up, warms up, times the steps, writes --dump-outputs if asked and prints one JSON line.  --full adds
+everything else beside it: the spot check against the CPU oracle, the CPU baseline and the side measurements (solver
+variants, fused paths, BASELINE configs[1]-[4], host-array and Fortran paths), each as before.
+
   python bench.py --gpus 1 --steps 10 --warmup 2
+  python bench.py --gpus 1 --steps 10 --warmup 2 --full
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
 """
@@ -403,6 +408,10 @@ def main():
     ap.add_argument("--ncol", type=int, default=None,
                     help="synthetic columns per GPU (default: 1e6, the north_star target size; with --gpus 8: 1.25e6 = "
                          "BASELINE configs[3], 1e7 columns sharded over 8 GPUs)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the timed steps, also run the oracle spot check, the CPU baseline and the side "
+                         "measurements (the options below tune or skip them); without it the line carries the timed "
+                         "steps and what their own profile gives (per-kernel times, rooflines) only")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline budget of the all-cores leg (0 = skip)")
     ap.add_argument("--host-sample", type=int, default=20000,
                     help="columns of the PCIe-inclusive side measurement through the ECCKD_HOST memory space "
@@ -418,7 +427,7 @@ def main():
                          "per-gas kernels in the reference's expression order")
     ap.add_argument("--mode", choices=["lw", "sw"], default="lw",
                     help="lw = headline metric; sw = secondary line (BASELINE configs[2]: gas_optics + rte_sw)")
-    ap.add_argument("--no-side", action="store_true", help="skip every side measurement (profiling passes)")
+    ap.add_argument("--no-side", action="store_true", help="with --full: skip every side measurement (profiling passes)")
     ap.add_argument("--solver-option", action="append", default=[], metavar="NAME=VALUE",
                     help="ecckd_set_solver_option before the run (A/B of implementation choices, e.g. lw_tail_split=0)")
     ap.add_argument("--rehearse-on-one-gpu", action="store_true",
@@ -566,16 +575,18 @@ def main():
                         "alg_bytes_per_launch": per_kernel[dom]["alg_bytes_per_launch"]}
         total_b = (bpc["tau"] + bpc["planck"] + bpc["rte_lw"]) * ncol
         pipe = total_b / (ms_per_step * 1e-3) / 1e9
-        # spot check of the timed configuration against the CPU oracle (64 columns)
-        sys.path.insert(0, os.path.join(ROOT, "oracle"))
-        import oracle
-        m = oracle.CkdModel(lw_file)
-        cols = synthetic.columns(0, 64, press_min)
-        tau, lay, inc, dec, sfc, _ = oracle.gas_optics_int(m, cols["plev"], cols["tlay"], cols["tsfc"],
-                                                           synthetic.gas_items(cols), cols["tlev"])
-        fu, fd = oracle.rte_lw(tau, lay, inc, dec, np.repeat(cols["sfc_emis"][None, :], ng, 0), sfc)
-        dflux = max(float(np.max(np.abs(fl.flux_up[:, :64].double().cpu().numpy() - fu))),
-                    float(np.max(np.abs(fl.flux_dn[:, :64].double().cpu().numpy() - fd))))
+        dflux = None
+        if args.full:
+            # spot check of the timed configuration against the CPU oracle (64 columns)
+            sys.path.insert(0, os.path.join(ROOT, "oracle"))
+            import oracle
+            m = oracle.CkdModel(lw_file)
+            cols = synthetic.columns(0, 64, press_min)
+            tau, lay, inc, dec, sfc, _ = oracle.gas_optics_int(m, cols["plev"], cols["tlay"], cols["tsfc"],
+                                                               synthetic.gas_items(cols), cols["tlev"])
+            fu, fd = oracle.rte_lw(tau, lay, inc, dec, np.repeat(cols["sfc_emis"][None, :], ng, 0), sfc)
+            dflux = max(float(np.max(np.abs(fl.flux_up[:, :64].double().cpu().numpy() - fu))),
+                        float(np.max(np.abs(fl.flux_dn[:, :64].double().cpu().numpy() - fd))))
         if world == 8 and ncol == 1250000:
             what = "BASELINE configs[3]: 1e7 synthetic columns, column-range sharded 1.25e6 per GPU over 8 GPUs"
         elif ncol == 1000000:
@@ -601,10 +612,11 @@ def main():
                                   "frac": pipe / HBM_PEAK_GBS, "alg_bytes_per_cell": total_b / ncol / (nlay * ng),
                                   "note": "all kernels of one step, per GPU"},
             "kernels": per_kernel,
-            "check_max_abs_flux_diff_vs_oracle_Wm2": dflux,
+            "check_max_abs_flux_diff_vs_oracle_Wm2": dflux, "full": args.full,
         }
-        side = world == 1 and not args.no_side
-        if args.cpu_seconds > 0 and world == 1:
+        # everything below is --full only: without it each of these keys stays None
+        side = args.full and world == 1 and not args.no_side
+        if args.full and args.cpu_seconds > 0 and world == 1:
             out["cpu_baseline"] = cpu_baseline(args, press_min)
         else:
             out["cpu_baseline"] = None
@@ -802,13 +814,16 @@ def main():
 
 
 def main_sw(args):
-    print(json.dumps(sw_measure(args.ncol, args.steps, args.warmup, args.solver_option, fused=not args.no_side, dtype=args.dtype,
-                                dump_dir=args.dump_outputs)), flush=True)
+    out = sw_measure(args.ncol, args.steps, args.warmup, args.solver_option, fused=args.full and not args.no_side,
+                     dtype=args.dtype, dump_dir=args.dump_outputs, check=args.full)
+    out["full"] = args.full
+    print(json.dumps(out), flush=True)
 
 
-def sw_measure(ncol, steps, warmup, solver_option=(), fused=True, dtype="f64", dump_dir=None):
+def sw_measure(ncol, steps, warmup, solver_option=(), fused=True, dtype="f64", dump_dir=None, check=True):
     """Secondary line: SW wide-tol0.05 (27 g-points), gas_optics (tau, ssa, g) + rte_sw two-stream, fp64 (or fp32),
-    single GPU.  Algorithmic bytes: tau, ssa, g written once and read once = 48 B/cell (+ per-column terms)."""
+    single GPU.  Algorithmic bytes: tau, ssa, g written once and read once = 48 B/cell (+ per-column terms).
+    fused: also time the fused path beside the pair; check: spot check of 64 columns against the CPU oracle."""
     import types
     args = types.SimpleNamespace(ncol=ncol, steps=steps, warmup=warmup, solver_option=list(solver_option))
     import torch
@@ -943,18 +958,20 @@ def sw_measure(ncol, steps, warmup, solver_option=(), fused=True, dtype="f64", d
                      "note": "fp64 FMA (2 flop), MUL, ADD, transcendental wave-instructions x 64 lanes from SQ_INSTS_VALU_*_F64; "
                              "measured sustained fp64 issue on this chip: 0.86 wave-instructions/clk/CU (tools/ubench.hip)",
                      "source": csrc}
-    # spot check against the CPU oracle
-    sys.path.insert(0, os.path.join(ROOT, "oracle"))
-    import oracle
-    m = oracle.CkdModel(sw_file)
-    cols = synthetic.columns(0, 64, k.get_press_min(), shortwave=True)
-    items = [(n, np.atleast_1d(np.asarray(cols[n], dtype=np.float64)), 0 if np.isscalar(cols[n]) else 1,
-              0 if (np.isscalar(cols[n]) or cols[n].ndim == 1) else 64) for n in names]
-    tau, ssa, g, toa_o, _ = oracle.gas_optics_ext(m, cols["plev"], cols["tlay"], items)
-    a2 = np.repeat(cols["albedo"][None], ng, 0)
-    fu, fd, _ = oracle.rte_sw(tau, ssa, g, cols["mu0"], toa_o, a2, a2)
-    dflux = max(float(np.max(np.abs(fl.flux_up[:, :64].double().cpu().numpy() - fu))),
-                float(np.max(np.abs(fl.flux_dn[:, :64].double().cpu().numpy() - fd))))
+    dflux = None
+    if check:
+        # spot check against the CPU oracle
+        sys.path.insert(0, os.path.join(ROOT, "oracle"))
+        import oracle
+        m = oracle.CkdModel(sw_file)
+        cols = synthetic.columns(0, 64, k.get_press_min(), shortwave=True)
+        items = [(n, np.atleast_1d(np.asarray(cols[n], dtype=np.float64)), 0 if np.isscalar(cols[n]) else 1,
+                  0 if (np.isscalar(cols[n]) or cols[n].ndim == 1) else 64) for n in names]
+        tau, ssa, g, toa_o, _ = oracle.gas_optics_ext(m, cols["plev"], cols["tlay"], items)
+        a2 = np.repeat(cols["albedo"][None], ng, 0)
+        fu, fd, _ = oracle.rte_sw(tau, ssa, g, cols["mu0"], toa_o, a2, a2)
+        dflux = max(float(np.max(np.abs(fl.flux_up[:, :64].double().cpu().numpy() - fu))),
+                    float(np.max(np.abs(fl.flux_dn[:, :64].double().cpu().numpy() - fd))))
     return ({
         "metric": "Mcol*lay*gpt/s SW gas_optics+rte_sw", "value": cells * args.steps / elapsed / 1e6,
         "unit": "Mcol*lay*gpt/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,

@@ -60,3 +60,22 @@ def test_sw_dump_small_run_keeps_every_column(pkg, gpu, tmp_path):
     assert sorted(a) == sorted(SW_NAMES)
     for n in SW_NAMES:
         assert a[n].dtype == np.float64 and a[n].shape[-1] == 300 and np.all(np.isfinite(a[n])), n
+
+
+@pytest.mark.parametrize("mode", ["lw", "sw"])
+def test_plain_run_leaves_the_extras_to_full(pkg, gpu, tmp_path, mode):
+    """Without --full a run times its steps and prints the line: no oracle spot check, no CPU baseline, no side
+    measurement (the bench tests that read those pass --full)."""
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--mode", mode,
+           "--ncol", "2000"]
+    r = subprocess.run(cmd, capture_output=True, text=True, env=env, cwd=str(tmp_path), timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["full"] is False and d["steps"] == 2 and d["ms_per_step"] > 0 and d["value"] > 0 and d["kernels"]
+    assert d["check_max_abs_flux_diff_vs_oracle_Wm2"] is None and d["cpu_baseline"] is None
+    extras = ("fused_sw",) if mode == "sw" else ("rte_lw_shared_levels", "lw_solver_variants", "well_mixed_scalars", "fused_lw",
+                                                 "host_memspace", "fortran_device_resident")
+    assert all(d[key] is None for key in extras), {key: d[key] for key in extras}

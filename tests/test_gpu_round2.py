@@ -693,7 +693,7 @@ def test_bench_two_ranks_rehearsal(pkg, gpu, tmp_path):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29517", os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--ncol", "60000",
-           "--cpu-seconds", "0", "--no-side", "--rehearse-on-one-gpu"]
+           "--full", "--cpu-seconds", "0", "--no-side", "--rehearse-on-one-gpu"]
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, cwd=str(tmp_path), timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -415,7 +415,7 @@ def test_bench_launches_its_own_ranks(pkg, gpu, tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k2: v for k2, v in os.environ.items() if k2 not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--ncol", "60000",
-           "--cpu-seconds", "0", "--no-side", "--rehearse-on-one-gpu"]
+           "--full", "--cpu-seconds", "0", "--no-side", "--rehearse-on-one-gpu"]
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, cwd=str(tmp_path), timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -558,7 +558,7 @@ def test_bench_rccl_branch_with_one_rank(pkg, gpu, tmp_path):
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = env.get("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", "29541", os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--ncol", "60000",
-           "--cpu-seconds", "0", "--no-side"]
+           "--full", "--cpu-seconds", "0", "--no-side"]
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, cwd=str(tmp_path), timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

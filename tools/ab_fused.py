@@ -1,9 +1,9 @@
 import glob, json, os, subprocess, sys
-root = "/root/repo"
+root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for rep in range(2):
     for lib in sorted(glob.glob(os.path.join(root, "variants_tmp", "lib_v*.so"))):
         env = dict(os.environ, ECCKD_LIB=lib)
-        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "5", "--warmup", "2", "--cpu-seconds", "0",
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "5", "--warmup", "2", "--full", "--cpu-seconds", "0",
                               "--host-sample", "0", "--fortran-sample", "0"], env=env, capture_output=True, text=True)
         try:
             d = json.loads(out.stdout.strip().splitlines()[-1])

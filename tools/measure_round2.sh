@@ -8,9 +8,9 @@ set -e
 tag=$1
 export TMPDIR=/tmp
 o=gpurun_out
-P="--cpu-seconds 0 --no-side"
+P="--full --cpu-seconds 0 --no-side"
 if [ "$2" != "extra" ]; then
-python bench.py --steps 10 --warmup 2 > $o/${tag}_bench.json 2> $o/${tag}_bench.err
+python bench.py --steps 10 --warmup 2 --full > $o/${tag}_bench.json 2> $o/${tag}_bench.err
 echo "bench done"
 rocprofv3 --kernel-trace --stats --output-format csv -d $o/${tag}_prof -- python3 bench.py --steps 10 --warmup 2 $P > $o/${tag}_bench_prof.json 2> $o/${tag}_bench_prof.err
 for c in FETCH_SIZE WRITE_SIZE; do
@@ -23,13 +23,13 @@ python tools/pmc_summary.py "synthetic 300000 columns x 60 layers x 32 g-points,
 echo "lw passes done"
 # ---- SW pair (BASELINE configs[2], 1e5 columns) ----
 S="--mode sw --ncol 100000"
-python bench.py $S --steps 10 --warmup 2 --cpu-seconds 0 > $o/${tag}_bench_sw.json 2> $o/${tag}_bench_sw.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $o/${tag}_prof_sw -- python3 bench.py $S --steps 10 --warmup 2 --cpu-seconds 0 > /dev/null 2> $o/${tag}_prof_sw.err
+python bench.py $S --steps 10 --warmup 2 --full --cpu-seconds 0 > $o/${tag}_bench_sw.json 2> $o/${tag}_bench_sw.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $o/${tag}_prof_sw -- python3 bench.py $S --steps 10 --warmup 2 --full --cpu-seconds 0 > /dev/null 2> $o/${tag}_prof_sw.err
 for c in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --pmc $c --output-format csv -d $o/${tag}_pmcsw_$c -- python3 bench.py $S --steps 2 --warmup 1 --cpu-seconds 0 > /dev/null 2> $o/${tag}_pmcsw_$c.err
+  rocprofv3 --pmc $c --output-format csv -d $o/${tag}_pmcsw_$c -- python3 bench.py $S --steps 2 --warmup 1 --full --cpu-seconds 0 > /dev/null 2> $o/${tag}_pmcsw_$c.err
 done
-rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS --output-format csv -d $o/${tag}_pmcsw_sq1 -- python3 bench.py $S --steps 2 --warmup 1 --cpu-seconds 0 > /dev/null 2> $o/${tag}_pmcsw_sq1.err
-rocprofv3 --pmc SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_TRANS_F64 SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR --output-format csv -d $o/${tag}_pmcsw_sq2 -- python3 bench.py $S --steps 2 --warmup 1 --cpu-seconds 0 > /dev/null 2> $o/${tag}_pmcsw_sq2.err
+rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS --output-format csv -d $o/${tag}_pmcsw_sq1 -- python3 bench.py $S --steps 2 --warmup 1 --full --cpu-seconds 0 > /dev/null 2> $o/${tag}_pmcsw_sq1.err
+rocprofv3 --pmc SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_TRANS_F64 SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR --output-format csv -d $o/${tag}_pmcsw_sq2 -- python3 bench.py $S --steps 2 --warmup 1 --full --cpu-seconds 0 > /dev/null 2> $o/${tag}_pmcsw_sq2.err
 python tools/pmc_summary.py "synthetic 100000 columns x 60 layers x 27 g-points, SW wide-tol0.05, fp64" 100000 $o/${tag}_pmcsw_FETCH_SIZE $o/${tag}_pmcsw_WRITE_SIZE $o/${tag}_pmcsw_sq1 $o/${tag}_pmcsw_sq2 > $o/${tag}_pmc_sw.json
 echo "sw passes done"
 fi

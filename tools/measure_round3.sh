@@ -7,8 +7,8 @@ set -e
 tag=$1
 export TMPDIR=/tmp
 o=gpurun_out
-P="--cpu-seconds 0 --no-side"
-python bench.py --steps 10 --warmup 2 > $o/${tag}_bench.json 2> $o/${tag}_bench.err
+P="--full --cpu-seconds 0 --no-side"
+python bench.py --steps 10 --warmup 2 --full > $o/${tag}_bench.json 2> $o/${tag}_bench.err
 echo "bench done"
 rocprofv3 --kernel-trace --stats --output-format csv -d $o/${tag}_prof -- python3 bench.py --steps 10 --warmup 2 $P > $o/${tag}_bench_prof.json 2> $o/${tag}_bench_prof.err
 for c in FETCH_SIZE WRITE_SIZE; do
@@ -17,8 +17,8 @@ done
 python tools/pmc_summary.py "synthetic 1000000 columns x 60 layers x 32 g-points, LW fsck-tol0.0161, fp64" 1000000 $o/${tag}_pmc_FETCH_SIZE $o/${tag}_pmc_WRITE_SIZE > $o/${tag}_hbm_traffic.json
 echo "lw passes done"
 S="--mode sw --ncol 100000"
-python bench.py $S --steps 10 --warmup 2 > $o/${tag}_bench_sw.json 2> $o/${tag}_bench_sw.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $o/${tag}_prof_sw -- python3 bench.py $S --steps 10 --warmup 2 > /dev/null 2> $o/${tag}_prof_sw.err
+python bench.py $S --steps 10 --warmup 2 --full > $o/${tag}_bench_sw.json 2> $o/${tag}_bench_sw.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $o/${tag}_prof_sw -- python3 bench.py $S --steps 10 --warmup 2 --full > /dev/null 2> $o/${tag}_prof_sw.err
 # (counter passes with --no-side: the API pair only -- the fused path's gas-optics launches carry the same kernel name)
 for c in FETCH_SIZE WRITE_SIZE; do
   rocprofv3 --pmc $c --output-format csv -d $o/${tag}_pmcsw_$c -- python3 bench.py $S --no-side --steps 2 --warmup 1 > /dev/null 2> $o/${tag}_pmcsw_$c.err
