@@ -329,6 +329,66 @@ int ecckd_sw_fluxes_f32(const ecckd_model_t *model, int ncol, int nlay, const fl
                         const float *toa_scale, const float *sfc_alb_dir, const float *sfc_alb_dif, float *flux_up,
                         float *flux_dn, float *flux_dir, int memspace, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * All-sky: particulate (cloud, aerosol) optical properties between gas_optics and the solvers.  A host model carries
+ * them on the model's BANDS, (ncol,nlay,nband); the reference's drivers have no such path (clear-sky RFMIP only), so
+ * there is no counterpart call in the reference tree: the calls restate RTE-RRTMGP's ty_optical_props%delta_scale and
+ * %increment [RTE-ext: mo_optical_props_kernels.F90 of the v1.5 era; the library is not in the reference tree], which
+ * every all-sky RTE-RRTMGP driver calls between gas_optics and rte_sw / rte_lw.  Arrays are (ncol,nlay,n), column fastest,
+ * n = g-points or bands; eps = 3*tiny(real); memspace ECCKD_DEVICE (asynchronous on `stream`) or ECCKD_HOST; fp64 and _f32.
+ *
+ * ecckd_delta_scale  [delta_scale_2str_k; with `forward`: delta_scale_2str_f_k], in place:
+ *     f = forward ? forward : g*g;  wf = ssa*f;  tau = tau*(1-wf);  ssa = (ssa-wf)/max(eps,1-wf);  g = (g-f)/max(eps,1-f)
+ *   forward(ncol,nlay,n) or NULL.  Values of `forward` outside [0,1] are an error with ECCKD_HOST arrays (checked before
+ *   anything is launched) and give undefined results with ECCKD_DEVICE arrays (not checked: the call stays asynchronous).
+ *
+ * ecckd_increment  op1 += op2 in place; which pointers are NULL picks the combination (ssa and g go together):
+ *     ssa1 NULL, ssa2 NULL  [increment_1scalar_by_1scalar]  tau1 = tau1 + tau2
+ *     ssa1 NULL, ssa2 set   [increment_1scalar_by_2stream]  tau1 = tau1 + tau2*(1-ssa2)     (absorption only: what a
+ *                                                            no-scattering longwave solver wants)
+ *     ssa1 set,  ssa2 NULL  [increment_2stream_by_1scalar]  tau12 = tau1+tau2;  ssa1 = tau1*ssa1/max(eps,tau12);  tau1 = tau12
+ *     ssa1 set,  ssa2 set   [increment_2stream_by_2stream]  tau12 = tau1+tau2;  tauscat12 = tau1*ssa1 + tau2*ssa2;
+ *                                                            g1 = (tau1*ssa1*g1 + tau2*ssa2*g2)/max(eps,tauscat12);
+ *                                                            ssa1 = tauscat12/max(eps,tau12);  tau1 = tau12
+ *   nband = 0: op2 is on the same ngpt points (band2gpt ignored).  nband > 0 [the inc_*_bybnd forms]: op2 is
+ *   (ncol,nlay,nband) and band2gpt(2,nband) -- host memory, 1-based, inclusive, as ecckd_model_get_band2gpt returns it --
+ *   spreads each band over its g-points; the bands must tile 1..ngpt in ascending order (at most 256 bands, 65535
+ *   g-points).  ssa without g, or a band table that does not tile, is refused with a message before any launch.
+ *   Longwave all-sky: ecckd_gas_optics_lw, ecckd_increment(tau, NULL, NULL, nband, band2gpt, tau_c, ssa_c, g_c),
+ *   ecckd_rte_lw.  Clouds plus aerosols: add them up on the band grid first (nband planes), then increment once.
+ * --------------------------------------------------------------------------------------- */
+int ecckd_delta_scale(int device, int ncol, int nlay, int n, double *tau, double *ssa, double *g, const double *forward,
+                      int memspace, void *stream);
+int ecckd_delta_scale_f32(int device, int ncol, int nlay, int n, float *tau, float *ssa, float *g, const float *forward,
+                          int memspace, void *stream);
+int ecckd_increment(int device, int ncol, int nlay, int ngpt, double *tau1, double *ssa1, double *g1, int nband,
+                    const int *band2gpt, const double *tau2, const double *ssa2, const double *g2, int memspace, void *stream);
+int ecckd_increment_f32(int device, int ncol, int nlay, int ngpt, float *tau1, float *ssa1, float *g1, int nband,
+                        const int *band2gpt, const float *tau2, const float *ssa2, const float *g2, int memspace, void *stream);
+
+/* Fused all-sky shortwave: ecckd_sw_fluxes with the combined particulate properties tau_p, ssa_p, g_p (ncol,nlay,nband_p)
+ * on the model's bands (nband_p must equal ecckd_model_get_nband).  Gas optics writes the GAS total optical depth into
+ * stream scratch as for ecckd_sw_fluxes; where the solver forms ssa = moles*ray/tau and g = 0 there, it forms here, with the
+ * layer's band triple (tp, sp, gp) [increment_2stream_by_2stream with op1 = the gas optics]:
+ *     tau_r = moles*ray;  ts = tau_r + tp*sp;  tau12 = tau + tp;
+ *     g = (tp*sp*gp)/max(eps,ts);  ssa = ts/max(eps,tau12);  tau = tau12
+ * so no per-g-point ssa or g array exists in memory.  delta_scale = 1: the library first delta-scales a COPY of the triple
+ * with f = g*g [delta_scale_2str_k]; the caller's arrays are never written.  fp64, fast arithmetic mode only (reference-order
+ * mode is refused with a message), any layer count, ECCKD_DEVICE or ECCKD_HOST, toa_scale as ecckd_sw_fluxes.  The solver
+ * is the one ecckd_sw_fluxes takes for the shape ("sw_solver": layer-systolic up to 60 layers, else two-pass).  Fluxes agree
+ * with ecckd_gas_optics_sw + ecckd_increment + ecckd_rte_sw to rounding, not bit for bit (ssa is formed in a different order).
+ * Scratch (ECCKD_DEVICE; a host that owns the stream's block, ecckd_set_stream_scratch, sizes it so): what ecckd_sw_fluxes
+ * needs for the shape (the fused shortwave path, above: align256(ncol*nlay*ngpt*8) plus the solver's term)
+ *   + (delta_scale ? 3*align256(ncol*nlay*nband*8) : 0)
+ * in that order: optical depth, solver room, the three scaled band planes.  The planes belong to the stream's block, so the capture rules of the solver scratch hold:
+ * capture after one warm-up call on the stream, or with a caller-owned block. */
+int ecckd_sw_fluxes_allsky(const ecckd_model_t *model, int ncol, int nlay, const double *plev, const double *tlay, int ngas,
+                           const char *gas_names, const double *const *vmr, const long long *vmr_col_stride,
+                           const long long *vmr_lay_stride, const double *vmr_scalar, int top_at_1, const double *mu0,
+                           const double *toa_scale, const double *sfc_alb_dir, const double *sfc_alb_dif, int nband_p,
+                           const double *tau_p, const double *ssa_p, const double *g_p, int delta_scale, double *flux_up,
+                           double *flux_dn, double *flux_dir, int memspace, void *stream);
+
 /* Spectral (per-band) fluxes: what RTE-RRTMGP callers get by passing a ty_fluxes_byband to rte_lw /
  * rte_sw instead of the ty_fluxes_broadband the reference drivers use (ecckd_rfmip_lw.F90:108-109).
  * bnd_flux_*(ncol,nlay+1,nband) = sum over the g-points of each band (one solver pass per band over its

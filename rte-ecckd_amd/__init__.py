@@ -34,7 +34,7 @@ HOST, DEVICE = 0, 1
 NAME_LEN = 32
 
 _SOURCES = ["kernels_gas_fused.hip", "kernels_tau.hip", "kernels_planck.hip", "kernels_rte_lw.hip", "kernels_rte_lw_split.hip",
-            "kernels_rte_sw.hip", "kernels_rte_sw_sys.hip", "kernels_rte_gpt.hip",
+            "kernels_rte_sw.hip", "kernels_rte_sw_sys.hip", "kernels_rte_gpt.hip", "kernels_optical_props.hip",
             "capi.cpp", "nc_capi.cpp", "model.cpp", "cdf1.cpp"]
 _HEADERS = ["kernels.hpp", "wave_pair.hpp", "sw_two_stream.hpp", "sw_two_stream_body.inc", "lw_layer.hpp", "model.hpp", "cdf1.hpp", os.path.join("..", "..", "include", "ecckd_hip.h"),
             os.path.join("..", "..", "include", "ecckd_nc.h"), os.path.join("..", "..", "include", "rte_kernels_hip.h")]
@@ -417,6 +417,12 @@ class OpticalProps1scl:
     def get_ngpt(self):
         return self.tau.shape[0]
 
+    def increment(self, other, band2gpt=None):
+        """``self += other`` (RTE-RRTMGP's ``op%increment``; ``ecckd_increment`` / ``_f32``): ``other`` one- or
+        two-stream, on the same g-points, or -- with ``band2gpt`` ``(nband, 2)``, 1-based inclusive -- on bands
+        ``(nband, nlay, ncol)``.  Returns the error message ('' = success)."""
+        return _increment(self, other, band2gpt)
+
 
 class OpticalProps2str(OpticalProps1scl):
     """``ty_optical_props_2str``: tau, ssa, g."""
@@ -431,6 +437,31 @@ class OpticalProps2str(OpticalProps1scl):
         self.ssa = _empty_like_space(tuple(self.tau.shape), self.tau)
         self.g = _empty_like_space(tuple(self.tau.shape), self.tau)
         return ""
+
+    def alloc_2str_bands(self, ncol, nlay, spectral_desc, like=None):
+        """Two-stream properties on the BANDS of ``spectral_desc``: ``(nband, nlay, ncol)`` arrays (cloud / aerosol
+        optics as a host model carries them)."""
+        self.band2gpt = spectral_desc.get_band2gpt()
+        nb = spectral_desc.get_nband()
+        self.tau = _empty_like_space((nb, nlay, ncol), like if like is not None else np.empty(0))
+        self.ssa = _empty_like_space(tuple(self.tau.shape), self.tau)
+        self.g = _empty_like_space(tuple(self.tau.shape), self.tau)
+        return ""
+
+    def delta_scale(self, forward=None):
+        """In-place delta scaling (``ecckd_delta_scale`` / ``_f32``) with the forward-scattering fraction ``forward``
+        (same shape), or ``g*g``.  Returns the error message ('' = success)."""
+        n, nlay, ncol = self.tau.shape
+        f32 = _is_f32(self.tau)
+        try:
+            space = _space_of([self.tau, self.ssa, self.g, forward])
+            P = lambda a, what: _ptr(a, (n, nlay, ncol), what, f32)
+            args = (P(self.tau, "tau"), P(self.ssa, "ssa"), P(self.g, "g"), P(forward, "forward"))
+        except (TypeError, ValueError) as e:
+            return str(e)
+        rc = (lib().ecckd_delta_scale_f32 if f32 else lib().ecckd_delta_scale)(
+            int(_device_of(self.tau)), ncol, nlay, n, *args, space, _stream(space))
+        return last_error() if rc else ""
 
 
 class SourceFuncLW:
@@ -744,6 +775,35 @@ class GasOpticsEcckd:
             P(toa_src, (ng, ncol), "toa_src"), space, _stream(space))
         return last_error() if rc else ""
 
+    def sw_fluxes_allsky(self, plev, tlay, gas_desc, top_at_1, mu0, sfc_alb_dir, sfc_alb_dif, particles, fluxes,
+                         delta_scale=True, toa_scale=None):
+        """``ecckd_sw_fluxes_allsky``: ``sw_fluxes`` with the combined particulate optical properties ``particles``
+        (an ``OpticalProps2str`` on the model's bands, ``alloc_2str_bands``) added to the gas optics inside the solver;
+        ``delta_scale``: the library delta-scales a copy of them (f = g*g) first, ``particles`` is never written.
+        float64, fast arithmetic mode."""
+        nlay, ncol = tlay.shape
+        nband = self.get_nband()
+        try:
+            space = _space_of([plev, tlay, mu0, toa_scale, sfc_alb_dir, sfc_alb_dif, fluxes.flux_up, fluxes.flux_dn,
+                               particles.tau, particles.ssa, particles.g])
+            n, names, ptrs, cs, ls, sc, keep = self._gas_args(gas_desc, ncol, nlay, space)
+            nbp = int(particles.tau.shape[0])
+            shp = (nbp, nlay, ncol)
+            part = (_ptr(particles.tau, shp, "particles.tau"), _ptr(particles.ssa, shp, "particles.ssa"),
+                    _ptr(particles.g, shp, "particles.g"))
+        except KeyError as e:
+            return str(e.args[0])
+        except (TypeError, ValueError) as e:
+            return str(e)
+        rc = lib().ecckd_sw_fluxes_allsky(
+            self._need(), ncol, nlay, _ptr(plev, (nlay + 1, ncol), "plev"), _ptr(tlay, (nlay, ncol), "tlay"), n, names, ptrs,
+            cs, ls, sc, int(bool(top_at_1)), _ptr(mu0, (ncol,), "mu0"), _ptr(toa_scale, (ncol,), "toa_scale"),
+            _ptr(sfc_alb_dir, (ncol, nband), "sfc_alb_dir"), _ptr(sfc_alb_dif, (ncol, nband), "sfc_alb_dif"), nbp, *part,
+            int(bool(delta_scale)), _ptr(fluxes.flux_up, (nlay + 1, ncol), "flux_up"),
+            _ptr(fluxes.flux_dn, (nlay + 1, ncol), "flux_dn"), _ptr(fluxes.flux_dn_dir, (nlay + 1, ncol), "flux_dn_dir"),
+            space, _stream(space))
+        return last_error() if rc else ""
+
     def sw_fluxes(self, plev, tlay, gas_desc, top_at_1, mu0, sfc_alb_dir, sfc_alb_dif, fluxes, toa_scale=None):
         """``ecckd_sw_fluxes`` (float32 arrays: ``_f32``): gas optics + rte_sw in one call for hosts that only need
         broadband fluxes -- the total optical depth alone goes through (library-owned) memory, the solver derives
@@ -776,6 +836,30 @@ def _device_of(a):
     if _is_torch(a) and a.is_cuda:
         return a.device.index if a.device.index is not None else 0
     return 0
+
+
+def _increment(op1, op2, band2gpt):
+    """``ecckd_increment`` / ``_f32`` on the Python containers (OpticalProps1scl.increment)."""
+    ng, nlay, ncol = op1.tau.shape
+    f32 = _is_f32(op1.tau)
+    two1, two2 = isinstance(op1, OpticalProps2str), isinstance(op2, OpticalProps2str)
+    try:
+        space = _space_of([op1.tau, op2.tau] + ([op1.ssa, op1.g] if two1 else []) + ([op2.ssa, op2.g] if two2 else []))
+        if band2gpt is None:
+            nband, b2g, n2 = 0, None, ng
+        else:
+            b2g = np.ascontiguousarray(band2gpt, dtype=np.int32)
+            nband = n2 = b2g.shape[0]
+        P1 = lambda a, what: _ptr(a, (ng, nlay, ncol), what, f32)
+        P2 = lambda a, what: _ptr(a, (n2, nlay, ncol), what, f32)
+        a1 = (P1(op1.tau, "tau"), P1(op1.ssa, "ssa") if two1 else None, P1(op1.g, "g") if two1 else None)
+        a2 = (P2(op2.tau, "other.tau"), P2(op2.ssa, "other.ssa") if two2 else None, P2(op2.g, "other.g") if two2 else None)
+    except (TypeError, ValueError) as e:
+        return str(e)
+    rc = (lib().ecckd_increment_f32 if f32 else lib().ecckd_increment)(
+        int(_device_of(op1.tau)), ncol, nlay, ng, *a1, nband, C.c_void_p(b2g.ctypes.data) if b2g is not None else None, *a2,
+        space, _stream(space))
+    return last_error() if rc else ""
 
 
 def rte_lw(optical_props, top_at_1, sources, sfc_emis, fluxes, n_gauss_angles=1, device=None,

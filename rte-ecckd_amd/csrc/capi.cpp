@@ -193,7 +193,11 @@ inline double *dp(float *p) { return reinterpret_cast<double *>(p); }
 // ecckd_sw_fluxes: the shortwave solver derives ssa / g / toa itself (RteSwArgs::derive) and works in `room` inside
 // ecckd_sw_fluxes' own scratch block (sw_fluxes_solver_bytes): the partial sums of the layer-systolic solver, or the
 // scratch ring of the two-pass solver with its partial sums behind it
-struct SwDerive { const double *plev, *rayleigh, *solar, *toa_scale; double gw; double *room; };
+// part_*: ecckd_sw_fluxes_allsky -- the particulate band optics the solver adds to the gas optics (RteSwArgs::allsky), or null
+struct SwDerive {
+  const double *plev, *rayleigh, *solar, *toa_scale; double gw; double *room;
+  const double *part_tau = nullptr, *part_ssa = nullptr, *part_g = nullptr;
+};
 // What a public entry point asks of the solver implementations besides its arguments.
 struct Call {
   bool f32 = false;
@@ -1405,6 +1409,7 @@ static int rte_sw_impl(const Call &c, int device, int ncol, int nlay, int ngpt, 
     a.derive = 1;
     a.plev = dv->plev; a.rayleigh = dv->rayleigh; a.solar = dv->solar; a.gw = dv->gw;
     a.toa_scale = dv->toa_scale;
+    if (dv->part_tau) { a.allsky = 1; a.part_tau = dv->part_tau; a.part_ssa = dv->part_ssa; a.part_g = dv->part_g; }
   }
   const size_t n3 = (size_t)ncol * nlay * ngpt, n2l = (size_t)ncol * (nlay + 1);
   const hipStream_t launch_stream = memspace == ECCKD_DEVICE ? static_cast<hipStream_t>(stream) : nullptr;
@@ -1766,11 +1771,15 @@ int ecckd_lw_fluxes(const ecckd_model_t *m, int ncol, int nlay, const double *pl
 
 // ---- fused shortwave: total optical depth only between the kernels (SURVEY 8(f) rank 4 for the shortwave) ----
 
+// ecckd_sw_fluxes_allsky: the combined particulate optical properties on the model's bands, (ncol,nlay,nband) each, in the
+// memory space of the call; delta_scale: the library delta-scales a copy (f = g*g) first
+struct SwParticles { const double *tau, *ssa, *g; int delta_scale; };
+
 static int sw_fluxes_impl(bool f32, const ecckd_model_t *m, int ncol, int nlay, const double *plev, const double *tlay,
                           int ngas, const char *gas_names, const double *const *vmr, const long long *vmr_col_stride,
                           const long long *vmr_lay_stride, const double *vmr_scalar, int top_at_1, const double *mu0,
                           const double *toa_scale, const double *sfc_alb_dir, const double *sfc_alb_dif, double *flux_up,
-                          double *flux_dn, double *flux_dir, int memspace, void *stream) {
+                          double *flux_dn, double *flux_dir, int memspace, void *stream, const SwParticles *pt = nullptr) {
   if (check_model(m) || check_gas_optics_dims(ncol, nlay)) return 1;
   if (!m->has_solar) return fail("ecckd_sw_fluxes: model has no solar table (longwave model?)");
   if (!plev || !tlay || !mu0 || !sfc_alb_dir || !sfc_alb_dif || !flux_up || !flux_dn || (ngas > 0 && !gas_names))
@@ -1788,13 +1797,26 @@ static int sw_fluxes_impl(bool f32, const ecckd_model_t *m, int ncol, int nlay, 
     ScratchLease lease;
     const size_t tau_bytes = align256(n3 * es);
     const size_t solver = sw_fluxes_solver_bytes(m->device, ncol, nlay, m->ng);
-    if (stream_scratch(m->device, st, tau_bytes + solver, &tau_p, lease)) return 1;
+    // all-sky with delta scaling: three band planes behind the solver's room hold the scaled copy (the caller's arrays are
+    // never written); they are part of the stream's block, so the capture rules of stream_scratch cover them
+    const size_t plane = align256(n2 * m->nband * es);
+    const size_t planes = pt && pt->delta_scale ? 3 * plane : 0;
+    if (stream_scratch(m->device, st, tau_bytes + solver + planes, &tau_p, lease)) return 1;
     double *d_tau = static_cast<double *>(tau_p);
+    SwParticles dp_ = pt ? *pt : SwParticles{};
+    if (planes) {
+      char *p0 = static_cast<char *>(tau_p) + tau_bytes + solver;
+      double *q_tau = reinterpret_cast<double *>(p0), *q_ssa = reinterpret_cast<double *>(p0 + plane), *q_g = reinterpret_cast<double *>(p0 + 2 * plane);
+      ProfScope prof("delta_scale", st);
+      HIPCHK(ecckd::launch_delta_scale(n2 * m->nband, pt->tau, pt->ssa, pt->g, nullptr, q_tau, q_ssa, q_g, 0, st));
+      dp_.tau = q_tau; dp_.ssa = q_ssa; dp_.g = q_g;
+    }
     // gas_optics_ext's tau (:449-456) without ssa / g: the total optical depth, gases + Rayleigh
     if (gas_optical_depth_dev(m, f32, nullptr, ncol, nlay, plev, tlay, gd, d_tau, true, nullptr, nullptr, nullptr, nullptr, st))
       return 1;
-    const SwDerive dv{plev, rayleigh, solar, toa_scale, gw(f32),
-                      solver ? reinterpret_cast<double *>(static_cast<char *>(tau_p) + tau_bytes) : nullptr};
+    SwDerive dv{plev, rayleigh, solar, toa_scale, gw(f32),
+                solver ? reinterpret_cast<double *>(static_cast<char *>(tau_p) + tau_bytes) : nullptr};
+    if (pt) { dv.part_tau = dp_.tau; dv.part_ssa = dp_.ssa; dv.part_g = dp_.g; }
     return rte_sw_impl(Call{f32, -1, false, &dv}, m->device, ncol, nlay, m->ng, top_at_1, d_tau, nullptr, nullptr, mu0,
                        nullptr, m->nband, m->band2gpt.data(), sfc_alb_dir, sfc_alb_dif, flux_up, flux_dn, flux_dir,
                        ECCKD_DEVICE, stream);
@@ -1804,7 +1826,8 @@ static int sw_fluxes_impl(bool f32, const ecckd_model_t *m, int ncol, int nlay, 
   std::lock_guard<std::mutex> lock(mm->mu);
   hipStream_t s = mm->host_stream;
   const size_t solver = sw_fluxes_solver_bytes(m->device, ncol, nlay, m->ng);
-  const size_t need = align256(n2l * es) * 4 + align256(n2 * es) + align256((size_t)ncol * es) * 2 +
+  const size_t nb3 = n2 * m->nband;
+  const size_t need = (pt ? align256(nb3 * es) * 3 : 0) + align256(n2l * es) * 4 + align256(n2 * es) + align256((size_t)ncol * es) * 2 +
                       staged_gas_bytes(gd, ncol, nlay, f32) + align256((size_t)ncol * m->nband * es) * 2 + align256(n3 * es) +
                       align256(solver);
   if (grow_arena(mm, need)) return 1;
@@ -1822,7 +1845,13 @@ static int sw_fluxes_impl(bool f32, const ecckd_model_t *m, int ncol, int nlay, 
   double *d_solver = solver ? b.take((solver + es - 1) / es) : nullptr;
   if (gas_optical_depth_dev(m, f32, nullptr, ncol, nlay, d_plev, d_tlay, sg.gd, d_tau, true, nullptr, nullptr, nullptr, nullptr, s))
     return 1;
-  const SwDerive dv{d_plev, rayleigh, solar, toa_scale ? d_scale : nullptr, gw(f32), d_solver};
+  SwDerive dv{d_plev, rayleigh, solar, toa_scale ? d_scale : nullptr, gw(f32), d_solver};
+  if (pt) {   // staged copies of the band optics, delta-scaled in place (they are the library's own)
+    double *q_tau = b.take(nb3), *q_ssa = b.take(nb3), *q_g = b.take(nb3);
+    if (h2d(q_tau, pt->tau, nb3, f32, s) || h2d(q_ssa, pt->ssa, nb3, f32, s) || h2d(q_g, pt->g, nb3, f32, s)) return 1;
+    if (pt->delta_scale) HIPCHK(ecckd::launch_delta_scale(nb3, q_tau, q_ssa, q_g, nullptr, q_tau, q_ssa, q_g, 0, s));
+    dv.part_tau = q_tau; dv.part_ssa = q_ssa; dv.part_g = q_g;
+  }
   if (rte_sw_impl(Call{f32, -1, false, &dv}, m->device, ncol, nlay, m->ng, top_at_1, d_tau, nullptr, nullptr, d_mu0, nullptr,
                   m->nband, m->band2gpt.data(), d_ad, d_af, d_up, d_dn, flux_dir ? d_dir : nullptr, ECCKD_DEVICE, s))
     return 1;
@@ -1839,6 +1868,140 @@ int ecckd_sw_fluxes(const ecckd_model_t *m, int ncol, int nlay, const double *pl
                     double *flux_dn, double *flux_dir, int memspace, void *stream) {
   return sw_fluxes_impl(false, m, ncol, nlay, plev, tlay, ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar,
                         top_at_1, mu0, toa_scale, sfc_alb_dir, sfc_alb_dif, flux_up, flux_dn, flux_dir, memspace, stream);
+}
+
+int ecckd_sw_fluxes_allsky(const ecckd_model_t *m, int ncol, int nlay, const double *plev, const double *tlay, int ngas,
+                           const char *gas_names, const double *const *vmr, const long long *vmr_col_stride,
+                           const long long *vmr_lay_stride, const double *vmr_scalar, int top_at_1, const double *mu0,
+                           const double *toa_scale, const double *sfc_alb_dir, const double *sfc_alb_dif, int nband_p,
+                           const double *tau_p, const double *ssa_p, const double *g_p, int delta_scale, double *flux_up,
+                           double *flux_dn, double *flux_dir, int memspace, void *stream) {
+  // refusals that need no device come first: a host-only model answers them too
+  if (!m) return fail("ecckd: null model");
+  if (nband_p != m->nband)
+    return fail("ecckd_sw_fluxes_allsky: nband_p = " + std::to_string(nband_p) + " but the model has " + std::to_string(m->nband) +
+                " bands (particulate properties live on the model's bands)");
+  if (!tau_p || !ssa_p || !g_p) return fail("ecckd_sw_fluxes_allsky: null argument (tau_p, ssa_p and g_p are all required)");
+  if (delta_scale != 0 && delta_scale != 1) return fail("ecckd_sw_fluxes_allsky: delta_scale must be 0 or 1");
+  if (g_arith.load() != 0) return fail("ecckd_sw_fluxes_allsky: needs the fast arithmetic mode (ecckd_set_arithmetic(0))");
+  const SwParticles pt{tau_p, ssa_p, g_p, delta_scale};
+  return sw_fluxes_impl(false, m, ncol, nlay, plev, tlay, ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar,
+                        top_at_1, mu0, toa_scale, sfc_alb_dir, sfc_alb_dif, flux_up, flux_dn, flux_dir, memspace, stream, &pt);
+}
+
+// ---- element-wise operations on optical properties (kernels_optical_props.hip) ----
+
+static int delta_scale_impl(bool f32, int device, int ncol, int nlay, int n, double *tau, double *ssa, double *g,
+                            const double *forward, int memspace, void *stream) {
+  if (check_dims(ncol, nlay)) return 1;
+  if (n < 1) return fail("ecckd_delta_scale: n must be at least 1");
+  if (!tau || !ssa || !g) return fail("ecckd_delta_scale: null argument (two-stream properties: tau, ssa and g)");
+  if (memspace != ECCKD_DEVICE && memspace != ECCKD_HOST) return fail("ecckd: bad memspace");
+  const size_t n3 = (size_t)ncol * nlay * n;
+  if (forward && memspace == ECCKD_HOST) {
+    bool ok = true;
+    if (f32) { const float *f = reinterpret_cast<const float *>(forward); for (size_t i = 0; i < n3 && ok; ++i) ok = f[i] >= 0.f && f[i] <= 1.f; }
+    else for (size_t i = 0; i < n3 && ok; ++i) ok = forward[i] >= 0. && forward[i] <= 1.;
+    if (!ok) return fail("ecckd_delta_scale: forward scattering fraction outside [0, 1]");
+  }
+  if (check_device(device)) return 1;
+  if (ncol == 0) return 0;
+  if (memspace == ECCKD_DEVICE) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    ProfScope prof("delta_scale", st);
+    HIPCHK(ecckd::launch_delta_scale(n3, tau, ssa, g, forward, tau, ssa, g, f32, st));
+    return 0;
+  }
+  Arena &ar = g_solver_arena[device];
+  std::lock_guard<std::mutex> lock(ar.mu);
+  if (ar.ensure(align256(n3 * esz(f32)) * 4)) return 1;
+  Bump b(ar.p, f32);
+  hipStream_t s = nullptr;
+  double *d_tau = b.take(n3), *d_ssa = b.take(n3), *d_g = b.take(n3), *d_f = forward ? b.take(n3) : nullptr;
+  if (h2d(d_tau, tau, n3, f32, s) || h2d(d_ssa, ssa, n3, f32, s) || h2d(d_g, g, n3, f32, s)) return 1;
+  if (forward && h2d(d_f, forward, n3, f32, s)) return 1;
+  HIPCHK(ecckd::launch_delta_scale(n3, d_tau, d_ssa, d_g, d_f, d_tau, d_ssa, d_g, f32, s));
+  if (d2h(tau, d_tau, n3, f32, s) || d2h(ssa, d_ssa, n3, f32, s) || d2h(g, d_g, n3, f32, s)) return 1;
+  HIPCHK(hipStreamSynchronize(s));
+  return 0;
+}
+
+int ecckd_delta_scale(int device, int ncol, int nlay, int n, double *tau, double *ssa, double *g, const double *forward,
+                      int memspace, void *stream) {
+  return delta_scale_impl(false, device, ncol, nlay, n, tau, ssa, g, forward, memspace, stream);
+}
+int ecckd_delta_scale_f32(int device, int ncol, int nlay, int n, float *tau, float *ssa, float *g, const float *forward,
+                          int memspace, void *stream) {
+  return delta_scale_impl(true, device, ncol, nlay, n, dp(tau), dp(ssa), dp(g), dp(forward), memspace, stream);
+}
+
+static int increment_impl(bool f32, int device, int ncol, int nlay, int ngpt, double *tau1, double *ssa1, double *g1, int nband,
+                          const int *band2gpt, const double *tau2, const double *ssa2, const double *g2, int memspace,
+                          void *stream) {
+  if (check_dims(ncol, nlay)) return 1;
+  if (ngpt < 1) return fail("ecckd_increment: ngpt must be at least 1");
+  if (!tau1 || !tau2) return fail("ecckd_increment: null argument (tau1 and tau2 are required)");
+  if ((ssa1 == nullptr) != (g1 == nullptr))
+    return fail("ecckd_increment: op1 has ssa without g or g without ssa (pass both: two-stream, or neither: one-stream)");
+  if ((ssa2 == nullptr) != (g2 == nullptr))
+    return fail("ecckd_increment: op2 has ssa without g or g without ssa (pass both: two-stream, or neither: one-stream)");
+  ecckd::OptPropsArgs a{};
+  if (nband < 0) return fail("ecckd_increment: nband must not be negative");
+  if (nband > 0) {
+    if (!band2gpt) return fail("ecckd_increment: band2gpt is required with nband > 0");
+    if (nband > 256 || ngpt > 65535) return fail("ecckd_increment: at most 256 bands and 65535 g-points");
+    int next = 1;   // bands in ascending order, each starting where the one before ended: they tile 1..ngpt
+    for (int bnd = 0; bnd < nband; ++bnd) {
+      const int lo = band2gpt[2 * bnd], hi = band2gpt[2 * bnd + 1];
+      if (lo != next || hi < lo || hi > ngpt)
+        return fail("ecckd_increment: band2gpt does not tile 1..ngpt (band " + std::to_string(bnd + 1) + " covers " +
+                    std::to_string(lo) + ".." + std::to_string(hi) + ", expected to start at " + std::to_string(next) + ")");
+      a.band_first[bnd] = (unsigned short)(lo - 1);
+      next = hi + 1;
+    }
+    if (next != ngpt + 1) return fail("ecckd_increment: band2gpt does not tile 1..ngpt (the last band ends at " + std::to_string(next - 1) + ")");
+    a.band_first[nband] = (unsigned short)ngpt;
+  }
+  if (memspace != ECCKD_DEVICE && memspace != ECCKD_HOST) return fail("ecckd: bad memspace");
+  if (check_device(device)) return 1;
+  if (ncol == 0) return 0;
+  a.ncol = ncol; a.nlay = nlay; a.ng = ngpt; a.nband = nband; a.f32 = f32;
+  const size_t n1 = (size_t)ncol * nlay * ngpt, n2 = (size_t)ncol * nlay * (nband > 0 ? nband : ngpt);
+  if (memspace == ECCKD_DEVICE) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    a.tau1 = tau1; a.ssa1 = ssa1; a.g1 = g1; a.tau2 = tau2; a.ssa2 = ssa2; a.g2 = g2;
+    ProfScope prof("increment", st);
+    HIPCHK(ecckd::launch_increment(a, st));
+    return 0;
+  }
+  Arena &ar = g_solver_arena[device];
+  std::lock_guard<std::mutex> lock(ar.mu);
+  const size_t es = esz(f32);
+  if (ar.ensure(align256(n1 * es) * (ssa1 ? 3 : 1) + align256(n2 * es) * (ssa2 ? 3 : 1))) return 1;
+  Bump b(ar.p, f32);
+  hipStream_t s = nullptr;
+  double *d_t1 = b.take(n1), *d_s1 = ssa1 ? b.take(n1) : nullptr, *d_g1 = ssa1 ? b.take(n1) : nullptr;
+  double *d_t2 = b.take(n2), *d_s2 = ssa2 ? b.take(n2) : nullptr, *d_g2 = ssa2 ? b.take(n2) : nullptr;
+  if (h2d(d_t1, tau1, n1, f32, s) || h2d(d_t2, tau2, n2, f32, s)) return 1;
+  if (ssa1 && (h2d(d_s1, ssa1, n1, f32, s) || h2d(d_g1, g1, n1, f32, s))) return 1;
+  if (ssa2 && (h2d(d_s2, ssa2, n2, f32, s) || h2d(d_g2, g2, n2, f32, s))) return 1;
+  a.tau1 = d_t1; a.ssa1 = d_s1; a.g1 = d_g1; a.tau2 = d_t2; a.ssa2 = d_s2; a.g2 = d_g2;
+  HIPCHK(ecckd::launch_increment(a, s));
+  if (d2h(tau1, d_t1, n1, f32, s)) return 1;
+  if (ssa1 && d2h(ssa1, d_s1, n1, f32, s)) return 1;
+  if (ssa1 && ssa2 && d2h(g1, d_g1, n1, f32, s)) return 1;   // (g1 changes only when op2 scatters)
+  HIPCHK(hipStreamSynchronize(s));
+  return 0;
+}
+
+int ecckd_increment(int device, int ncol, int nlay, int ngpt, double *tau1, double *ssa1, double *g1, int nband,
+                    const int *band2gpt, const double *tau2, const double *ssa2, const double *g2, int memspace, void *stream) {
+  return increment_impl(false, device, ncol, nlay, ngpt, tau1, ssa1, g1, nband, band2gpt, tau2, ssa2, g2, memspace, stream);
+}
+int ecckd_increment_f32(int device, int ncol, int nlay, int ngpt, float *tau1, float *ssa1, float *g1, int nband,
+                        const int *band2gpt, const float *tau2, const float *ssa2, const float *g2, int memspace, void *stream) {
+  return increment_impl(true, device, ncol, nlay, ngpt, dp(tau1), dp(ssa1), dp(g1), nband, band2gpt, dp(tau2), dp(ssa2), dp(g2),
+                        memspace, stream);
 }
 
 int ecckd_sw_fluxes_f32(const ecckd_model_t *m, int ncol, int nlay, const float *plev, const float *tlay, int ngas,

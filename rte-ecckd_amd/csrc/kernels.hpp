@@ -158,7 +158,32 @@ struct RteSwArgs {
   const double *plev = nullptr, *rayleigh = nullptr, *solar = nullptr;   // plev(ncol,nlay+1) device; (ng) device tables
   const double *toa_scale = nullptr;   // (ncol) or null: toa(i,g) = solar(g)*toa_scale(i), the driver's TSI rescaling (ecckd_rfmip_sw.F90:126-133)
   double gw = 0.;
+  // Fused all-sky shortwave path (ecckd_sw_fluxes_allsky; derive != 0 as well): the particulate optical properties of the
+  // layer on the model's bands, part_tau / part_ssa / part_g (ncol,nlay,nband), are added to the gas optics inside the
+  // solver with the expressions of RTE-RRTMGP's increment_2stream_by_2stream (see kernels_optical_props.hip)
+  int allsky = 0;
+  const double *part_tau = nullptr, *part_ssa = nullptr, *part_g = nullptr;
 };
+
+// Element-wise operations on optical properties (kernels_optical_props.hip): RTE-RRTMGP's delta_scale_2str_k / _f_k and
+// the increment_* kernels (by g-point and by band).  Arrays (ncol,nlay,n), column fastest; f32: float data behind the pointers.
+struct OptPropsArgs {
+  int ncol, nlay, ng;
+  int nband;                   // 0: op2 on the same ng points; > 0: op2 is (ncol,nlay,nband)
+  int f32;
+  double *tau1, *ssa1, *g1;    // ssa1 / g1 null: op1 is one-stream
+  const double *tau2, *ssa2, *g2;   // ssa2 / g2 null: op2 is one-stream
+  unsigned short band_first[257];   // nband > 0: band b covers the 0-based g-points [band_first[b], band_first[b+1])
+};
+// eps = 3 * tiny(1._wp): the floor of the denominators in those kernels (and where the all-sky solver forms ssa and g)
+template <typename real> __host__ __device__ constexpr real op_eps() {
+  return sizeof(real) == 4 ? real(3) * real(1.17549435e-38f) : real(3) * real(2.2250738585072014e-308);
+}
+hipError_t launch_increment(const OptPropsArgs &a, hipStream_t s);
+// (tau, ssa, g) of n cells delta-scaled into (tau_out, ssa_out, g_out) -- the same pointers for the in-place call;
+// forward: the forward-scattering fraction f per cell, or null: f = g*g
+hipError_t launch_delta_scale(size_t n, const double *tau, const double *ssa, const double *g, const double *forward, double *tau_out,
+                              double *ssa_out, double *g_out, int f32, hipStream_t s);
 
 // Spectral-output solvers (kernels_rte_gpt.hip): RTE-RRTMGP's kernel-level interfaces.  LW uses tau, lay_source,
 // lev_source_*, sfc_emis(ncol,ng), sfc_src(ncol,ng), inc_flux(ncol,ng)|null, Ds/wts; SW uses tau, ssa, g, mu0(ncol),

@@ -76,12 +76,20 @@ __device__ __forceinline__ void acc_add(double *p, double v, bool owner) {
 // DERIVE: fused shortwave path (RteSwArgs::derive): tau is the total optical depth and ssa / g / toa come from
 // rte_sw_sys_kernel's expressions (src/gas_optics_ecckd.f90:313-317,455-472); the lane's layer slots then prefetch the two
 // level pressures of a layer in place of its ssa and g.
-// The kernels (rte_sw_kernel, below) are thin entries to this body.
-template <typename real, int CW, bool FAST, bool CLAMP, bool DERIVE>
+// ALLSKY (with DERIVE; ecckd_sw_fluxes_allsky): the layer's particulate triple on the cell's band (RteSwArgs::part_*) rides
+// in the prefetch slot too and is added to the gas optics where ssa is formed -- RTE-RRTMGP's increment_2stream_by_2stream
+// with op1 = (tau, moles*ray/tau, 0): no per-g-point ssa or g exists in memory.  A lane walks all layers of one g-point before the
+// next, so the triple cannot stay in registers across the g-points of a band as it could in a layer-resident solver: it is
+// requested per (layer, g-point), three band-plane loads beside the layer's tau and its two pressures.
+// The kernels (rte_sw_kernel and rte_sw_allsky_kernel, below) are thin entries to this body.
+template <typename real> struct SwPart { real t, s, g; };
+template <typename real, int CW, bool FAST, bool CLAMP, bool DERIVE, bool ALLSKY = false>
 __device__ __forceinline__ void rte_sw_body(const RteSwArgs &a) {
+  static_assert(DERIVE || !ALLSKY, "the all-sky form extends the fused (DERIVE) form");
   constexpr int GW = 64 / CW;
   // (fp32 DERIVE: the correctly rounded fp32 division of ssa makes three layers in flight spill; two do not)
-  constexpr int PF = (DERIVE && sizeof(real) == 4) ? 2 : kPF;
+  // (ALLSKY: three more values per layer in flight; with three layers the 168 registers of three waves per SIMD spill)
+  constexpr int PF = ((DERIVE && sizeof(real) == 4) || ALLSKY) ? 2 : kPF;
   extern __shared__ double acc[];   // [3][nlay+1][CW]: up, dn, dir
   auto P = [](const double *p) { return reinterpret_cast<const real *>(p); };
   auto Q = [](double *p) { return reinterpret_cast<real *>(p); };
@@ -132,16 +140,29 @@ __device__ __forceinline__ void rte_sw_body(const RteSwArgs &a) {
       const real ray = DERIVE ? P(a.rayleigh)[gg] : real(0);
       // optical properties of layer sl (counted from the top) into prefetch slot d.  DERIVE: pssa / pg take plev at the
       // layer's two levels, turned into ssa by props() once they have arrived
-      auto fetch = [&](int sl, real &t, real &x, real &y) __attribute__((always_inline)) {
+      auto fetch = [&](int sl, real &t, real &x, real &y, SwPart<real> &pp) __attribute__((always_inline)) {
         const long lm = lay0 + lstep * sl;   // layer index in memory
         const long q = base + (long)ncol * lm;
         t = P(a.tau)[q];
+        if constexpr (ALLSKY) {
+          const long qb = cc + (long)ncol * (lm + (long)nlay * band);
+          pp.t = P(a.part_tau)[qb]; pp.s = P(a.part_ssa)[qb]; pp.g = P(a.part_g)[qb];
+        }
         if constexpr (DERIVE) { x = P(a.plev)[cc + (long)ncol * lm]; y = P(a.plev)[cc + (long)ncol * (lm + 1)]; }
         else { x = P(a.ssa)[q]; y = P(a.g)[q]; }
       };
       // two-stream coefficients of a cell from its prefetch slot
-      auto props = [&](real ctau, real x, real y) __attribute__((always_inline)) {
-        if constexpr (DERIVE) {
+      auto props = [&](real ctau, real x, real y, const SwPart<real> &pp) __attribute__((always_inline)) {
+        if constexpr (ALLSKY) {
+          constexpr real eps = op_eps<real>();
+          const real tau_r = ((y - x) * gw) * ray;             // :313-316: the Rayleigh optical depth, tau*ssa of the gas optics
+          const real tsp = pp.t * pp.s;
+          const real ts = tau_r + tsp, tau12 = ctau + pp.t;    // increment_2stream_by_2stream
+          const real cg = (tsp * pp.g) / (ts > eps ? ts : eps);
+          const real cssa = ts / (tau12 > eps ? tau12 : eps);
+          return two_stream<real, FAST, CLAMP, false>(tau12, cssa, cg, mu0, mu0_inv, k_floor);
+        }
+        else if constexpr (DERIVE) {
           const real moles = (y - x) * gw;                     // :313-314
           const real cssa = (moles * ray) / ctau;              // :316, :459-460 (IEEE division in every mode)
           return two_stream<real, FAST, CLAMP, true>(ctau, cssa, real(0), mu0, mu0_inv, k_floor);   // g = 0
@@ -162,16 +183,18 @@ __device__ __forceinline__ void rte_sw_body(const RteSwArgs &a) {
       // (the optical properties of layer s - PF are requested before the arithmetic of layer s: the
       // loop is a serial recurrence and the compiler does not pipeline it)
       real ptau[PF], pssa[PF], pg[PF];
+      SwPart<real> ppart[PF];   // (ALLSKY only)
 #pragma unroll
-      for (int d = 0; d < PF; ++d) fetch(nlay - 1 - d > 0 ? nlay - 1 - d : 0, ptau[d], pssa[d], pg[d]);
+      for (int d = 0; d < PF; ++d) fetch(nlay - 1 - d > 0 ? nlay - 1 - d : 0, ptau[d], pssa[d], pg[d], ppart[d]);
       // The layer loop is unrolled by the prefetch depth so that every layer has a FIXED slot of the prefetch registers:
       // shifting the slots along (ptau[d] = ptau[d + 1]) reads registers whose loads are still in flight and made the
       // compiler wait with vmcnt(0) in every iteration -- one layer of loads in flight instead of PF (round 2).
       auto layer1 = [&](int s, auto slot_c) __attribute__((always_inline)) {
         constexpr int d = decltype(slot_c)::value;
         const real ctau = ptau[d], cx = pssa[d], cy = pg[d];
-        fetch(s - PF > 0 ? s - PF : 0, ptau[d], pssa[d], pg[d]);
-        const TwoStreamT<real> ts = props(ctau, cx, cy);
+        const SwPart<real> cp = ppart[d];
+        fetch(s - PF > 0 ? s - PF : 0, ptau[d], pssa[d], pg[d], ppart[d]);
+        const TwoStreamT<real> ts = props(ctau, cx, cy, cp);
         const real denom = rcp<FAST>(real(1) - ts.Rdif * albedo);                          // adding, Eq 10
         // Eq 11 divided by F_dir(l): src_up = Rdir*F_dir(l), src_dn = Tdir*F_dir(l), src(l+1) = nsrc*Tnoscat*F_dir(l)
         nsrc = ts.Rdir + ts.Tdif * denom * (nsrc * ts.Tnoscat + albedo * ts.Tdir);
@@ -204,18 +227,19 @@ __device__ __forceinline__ void rte_sw_body(const RteSwArgs &a) {
       for (int d = 0; d < PF; ++d) {
         const int sl = d < nlay ? d : nlay - 1;
         palb[d] = sAlb[64L * (sl + 1)]; pnsrc[d] = sSrc[64L * (sl + 1)];
-        fetch(sl, ptau[d], pssa[d], pg[d]);
+        fetch(sl, ptau[d], pssa[d], pg[d], ppart[d]);
       }
       auto layer2 = [&](int s, auto slot_c) __attribute__((always_inline)) {   // (fixed prefetch slots: see pass 1)
         constexpr int d = decltype(slot_c)::value;
         const real alb_next = palb[d], nsrc_next = pnsrc[d];
         const real ctau = ptau[d], cx = pssa[d], cy = pg[d];
+        const SwPart<real> cp = ppart[d];
         {
           const int sn = s + PF < nlay ? s + PF : nlay - 1;
           palb[d] = sAlb[64L * (sn + 1)]; pnsrc[d] = sSrc[64L * (sn + 1)];
-          fetch(sn, ptau[d], pssa[d], pg[d]);
+          fetch(sn, ptau[d], pssa[d], pg[d], ppart[d]);
         }
-        const TwoStreamT<real> ts = props(ctau, cx, cy);
+        const TwoStreamT<real> ts = props(ctau, cx, cy, cp);
         const real denom = rcp<FAST>(real(1) - ts.Rdif * alb_next);  // the same expression as in pass 1: same bits
         const real A = ts.Tdif * denom, B = ts.Rdif * denom, C = ts.Tdir * denom, Tn = ts.Tnoscat;
         const real fdir_next = Tn * fdir;
@@ -265,6 +289,13 @@ __global__ void __launch_bounds__(64, ECCKD_SW_WAVES_PER_SIMD) rte_sw_kernel(con
 template <typename real, int CW, bool FAST, bool CLAMP, bool DERIVE>
 __global__ void __launch_bounds__(64, ECCKD_SW_WAVES_PER_SIMD) rte_sw_kernel(const RteSwArgs a) {
   rte_sw_body<real, CW, FAST, CLAMP, DERIVE>(a);
+}
+
+// fused all-sky form (fp64, fast arithmetic mode): its own name, so that the figures of the clear-sky instantiations can be
+// told apart in the code object (tools/kernel_resources.py)
+template <int CW, bool CLAMP>
+__global__ void __launch_bounds__(64, ECCKD_SW_WAVES_PER_SIMD) rte_sw_allsky_kernel(const RteSwArgs a) {
+  rte_sw_body<double, CW, true, CLAMP, true, true>(a);
 }
 
 // Sums the per-group partial fluxes of the tail tiles in group order: the order in which a whole-tile wave adds the
@@ -374,7 +405,10 @@ RteSwKernel rte_sw_kernel_for(const RteSwArgs &a) {
 hipError_t launch_rte_sw(const RteSwArgs &a, hipStream_t s) {
   if (a.ncol <= 0) return hipSuccess;
   constexpr int CW = ECCKD_SW_CW;
-  auto k = a.f32 ? (a.derive ? rte_sw_kernel_for<float, true>(a) : rte_sw_kernel_for<float, false>(a))
+  // (the all-sky form exists in fp64 and the fast arithmetic mode only; ecckd_sw_fluxes_allsky refuses the rest with a message)
+  if (a.allsky && (a.f32 || a.exact_division || !a.derive)) return hipErrorInvalidValue;
+  auto k = a.allsky ? (a.dir_clamp ? rte_sw_allsky_kernel<CW, true> : rte_sw_allsky_kernel<CW, false>)
+           : a.f32 ? (a.derive ? rte_sw_kernel_for<float, true>(a) : rte_sw_kernel_for<float, false>(a))
                  : (a.derive ? rte_sw_kernel_for<double, true>(a) : rte_sw_kernel_for<double, false>(a));
   if (!k) return hipErrorInvalidValue;
   const size_t lds = sizeof(double) * 3 * (size_t)(a.nlay + 1) * CW;

@@ -146,8 +146,14 @@ __device__ __forceinline__ float rcp_chain(float x) { return rcp<true>(x); }
 
 // real: storage and arithmetic type.  FAST / CLAMP: as rte_sw_kernel.  DERIVE: fused shortwave path (RteSwArgs::derive).
 // FULL: every wave that owns layers owns LPW of them (nlay a multiple of LPW): no per-layer branches.
-template <typename real, bool FAST, bool CLAMP, bool DERIVE, bool FULL>
-__global__ void __launch_bounds__(64 * kSysWaves) rte_sw_sys_kernel(const RteSwArgs a) {
+// ALLSKY (with DERIVE; ecckd_sw_fluxes_allsky): the particulate triple of each of the wave's layers on the band of the
+// g-point (RteSwArgs::part_*) stays in registers and is requested again only where the band changes (5 times in 27
+// g-points); the coefficients add it to the gas optics with RTE-RRTMGP's increment_2stream_by_2stream, op1 = (tau,
+// moles*ray/tau, 0), as rte_sw_body does.
+// The kernels (rte_sw_sys_kernel, rte_sw_sys_allsky_kernel, below) are thin entries to this body.
+template <typename real, bool FAST, bool CLAMP, bool DERIVE, bool FULL, bool ALLSKY = false>
+__device__ __forceinline__ void rte_sw_sys_body(const RteSwArgs &a) {
+  static_assert(DERIVE || !ALLSKY, "the all-sky form extends the fused (DERIVE) form");
   constexpr int LPW = kSysLPW, NW = kSysWaves;
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
   const int lane = threadIdx.x & 63;
@@ -233,6 +239,7 @@ __global__ void __launch_bounds__(64 * kSysWaves) rte_sw_sys_kernel(const RteSwA
     const unsigned co = (unsigned)cc * (unsigned)sizeof(real);
     auto at = [&](const real *row) -> real { return *reinterpret_cast<greal_t *>((gcchar_t *)row + co); };
     real ptau[LPW], pssa[LPW], pg[LPW], pb0 = real(0), pb1 = real(0), ptoa = real(0);
+    real ppt[LPW], pps[LPW], ppg[LPW];   // ALLSKY: particulate tau, ssa, g of the wave's layers on the current band
     // boundary values of the column at one g-point: surface albedos (bottom wave), incoming beam (top wave).  Each is
     // requested for g + 1 right after the sweep of g has read it -- NOT together with the optical properties, which the
     // parking waves request a g-point further ahead.
@@ -254,6 +261,18 @@ __global__ void __launch_bounds__(64 * kSysWaves) rte_sw_sys_kernel(const RteSwA
           if (!DERIVE) { pssa[l] = at(P(a.ssa) + row); pg[l] = at(P(a.g) + row); }
         }
       }
+      if constexpr (ALLSKY) {
+        const int band = bandmap[g];
+        if (g == g_begin || band != bandmap[g - 1]) {   // (wave-uniform)
+#pragma unroll
+          for (int l = 0; l < LPW; ++l) {
+            if (l < nl) {
+              const long row = (long)ncol * ((lay0 + lstep * (s0 + l)) + (long)nlay * band);
+              ppt[l] = at(P(a.part_tau) + row); pps[l] = at(P(a.part_ssa) + row); ppg[l] = at(P(a.part_g) + row);
+            }
+          }
+        }
+      }
     };
     if (bottom_wave) load_albedos(g_begin);
     if (top_wave) load_toa(g_begin);
@@ -269,12 +288,21 @@ __global__ void __launch_bounds__(64 * kSysWaves) rte_sw_sys_kernel(const RteSwA
       for (int l = 0; l < LPW; ++l) {
         if (FULL || l < nl) {
           real cssa, cg;
+          if constexpr (ALLSKY) {
+            constexpr real eps = op_eps<real>();
+            const real tsp = ppt[l] * pps[l];
+            const real tsc = moles[l] * ray + tsp, tau12 = ptau[l] + ppt[l];   // increment_2stream_by_2stream
+            cg = (tsp * ppg[l]) / (tsc > eps ? tsc : eps);
+            cssa = tsc / (tau12 > eps ? tau12 : eps);
+            put(l, two_stream<real, FAST, CLAMP, false>(tau12, cssa, cg, mu0, mu0_inv, k_floor));
+          } else {
           if (DERIVE) { cssa = (moles[l] * ray) / ptau[l]; cg = real(0); }   // :316, :459-460
           else { cssa = pssa[l]; cg = pg[l]; }
           const TwoStreamT<real> ts = (DERIVE || __all(cg == real(0)))
                                           ? two_stream<real, FAST, CLAMP, true>(ptau[l], cssa, cg, mu0, mu0_inv, k_floor)
                                           : two_stream<real, FAST, CLAMP, false>(ptau[l], cssa, cg, mu0, mu0_inv, k_floor);
           put(l, ts);
+          }
         }
         // one cell after the other: left alone, the scheduler interleaves the five independent evaluations and their
         // temporaries no longer fit the register file (hundreds of spills)
@@ -476,6 +504,16 @@ __global__ void __launch_bounds__(64 * kSysWaves) rte_sw_sys_kernel(const RteSwA
   }
 }
 
+template <typename real, bool FAST, bool CLAMP, bool DERIVE, bool FULL>
+__global__ void __launch_bounds__(64 * kSysWaves) rte_sw_sys_kernel(const RteSwArgs a) {
+  rte_sw_sys_body<real, FAST, CLAMP, DERIVE, FULL>(a);
+}
+// fused all-sky form (fp64, fast arithmetic mode), under its own name
+template <bool CLAMP, bool FULL>
+__global__ void __launch_bounds__(64 * kSysWaves) rte_sw_sys_allsky_kernel(const RteSwArgs a) {
+  rte_sw_sys_body<double, true, CLAMP, true, FULL, true>(a);
+}
+
 // LDS of a block: control words and band map (384 B), hand-off slots, accumulators (up, dn and, if asked for, dir), and
 // behind them the parking areas: as many of the lower waves as fit keep the coefficients of the next g-point there.
 size_t sys_lds_base(int nlay, int f32, bool with_dir) {
@@ -487,6 +525,10 @@ template <typename real, bool DERIVE, bool FULL>
 hipError_t launch_sys2(RteSwArgs a, long blocks, hipStream_t s) {
   auto k = a.dir_clamp ? (a.exact_division ? rte_sw_sys_kernel<real, false, true, DERIVE, FULL> : rte_sw_sys_kernel<real, true, true, DERIVE, FULL>)
                        : (a.exact_division ? rte_sw_sys_kernel<real, false, false, DERIVE, FULL> : rte_sw_sys_kernel<real, true, false, DERIVE, FULL>);
+  if (a.allsky) {   // (fp64, fast arithmetic mode, DERIVE: ecckd_sw_fluxes_allsky refuses the rest with a message)
+    if (a.f32 || a.exact_division || !a.derive) return hipErrorInvalidValue;
+    k = a.dir_clamp ? rte_sw_sys_allsky_kernel<true, FULL> : rte_sw_sys_allsky_kernel<false, FULL>;
+  }
   const size_t base = (sys_lds_base(a.nlay, a.f32, a.flux_dir != nullptr) + 15) & ~(size_t)15;
   if (base > (size_t)kLdsBudget) return hipErrorInvalidValue;
   const int nwa = (a.nlay + kSysLPW - 1) / kSysLPW;

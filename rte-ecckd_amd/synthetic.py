@@ -64,6 +64,37 @@ def columns(c0, ncol, press_min, nlay=NLAY, shortwave=False):
     return out
 
 
+F_CLD_KIND, F_CLD_TAU, F_CLD_SSA, F_CLD_G = range(15, 19)
+
+
+def clouds(c0, ncol, nlay, nband):
+    """Particulate (cloud) optical properties on ``nband`` bands for columns ``c0 .. c0+ncol-1``, top layer first:
+    a dict of float64 arrays ``tau``, ``ssa``, ``g`` of shape ``(nband, nlay, ncol)`` plus ``cloudy`` ``(ncol,)``.
+    The column's ``uniform(c, F_CLD_KIND, 0)`` picks its kind -- below 0.3 a liquid-like low cloud (layers at
+    0.75-0.9 of the grid, optically thick), 0.3-0.5 an ice-like high cloud (0.3-0.45 of the grid, thin), 0.5-0.6
+    both, otherwise clear (``tau`` = 0 in every layer) -- so cloudy and clear columns alternate irregularly.
+    ``tau`` lies in [0, 30], ``ssa`` in [0.6, 1) and falls with the band index, ``g`` in [0.7, 0.9).  ``ssa`` and
+    ``g`` are defined in clear cells too (their values cannot matter where ``tau`` = 0)."""
+    c = np.arange(c0, c0 + ncol, dtype=np.uint64)[None, None, :]
+    jm = np.arange(1, nlay + 1, dtype=np.uint64)[None, :, None]
+    band_pos = (np.arange(nband, dtype=np.float64)[:, None, None] + 1.0) / nband   # (0, 1]: the last band absorbs most
+    kind = uniform(c, F_CLD_KIND, 0)
+    lay = np.arange(nlay)[None, :, None]
+
+    def slab(lo, hi):   # layers [lo*nlay, hi*nlay), at least one
+        l0 = int(lo * nlay)
+        return (lay >= l0) & (lay < max(l0 + 1, int(hi * nlay)))
+
+    liquid = ((kind < 0.3) | ((kind >= 0.5) & (kind < 0.6))) & slab(0.75, 0.9)
+    ice = (kind >= 0.3) & (kind < 0.6) & slab(0.3, 0.45) & ~liquid
+    u_tau, u_ssa, u_g = uniform(c, F_CLD_TAU, jm), uniform(c, F_CLD_SSA, jm), uniform(c, F_CLD_G, jm)
+    tau = np.where(liquid, 30.0 * u_tau ** 2, np.where(ice, 3.0 * u_tau, 0.0)) * (0.9 + 0.1 * band_pos)
+    ssa = 1.0 - 0.4 * band_pos * (0.5 + 0.5 * u_ssa)
+    g = np.where(liquid, 0.8, 0.7) + 0.1 * u_g + 0.0 * band_pos
+    return dict(tau=np.ascontiguousarray(tau), ssa=np.ascontiguousarray(ssa), g=np.ascontiguousarray(g),
+                cloudy=np.ascontiguousarray((kind < 0.6)[0, 0]))
+
+
 def gas_items(cols):
     """[(name, array, col_stride, lay_stride)] in GAS_ORDER for oracle-style consumers: full
     arrays are (nlay,ncol) -> strides (1,ncol); per-column arrays (1,0); scalars (0,0)."""
