@@ -389,6 +389,32 @@ int ecckd_sw_fluxes_allsky(const ecckd_model_t *model, int ncol, int nlay, const
                            const double *tau_p, const double *ssa_p, const double *g_p, int delta_scale, double *flux_up,
                            double *flux_dn, double *flux_dir, int memspace, void *stream);
 
+/* Fused all-sky longwave: ecckd_lw_fluxes with the combined particulate properties tau_p, ssa_p (ncol,nlay,nband_p) on the
+ * model's bands (nband_p must equal ecckd_model_get_nband), in `memspace`, in the layer order of tlay.  The solver sees
+ *     ssa_p set:   tau = tau_gas + tau_p*(1 - ssa_p)   [increment_1scalar_by_2stream, by band: absorption only]
+ *     ssa_p NULL:  tau = tau_gas + tau_p               [increment_1scalar_by_1scalar, by band: one-stream particles]
+ * spelt operation by operation as ecckd_increment spells them, so the fluxes equal those of ecckd_gas_optics_lw_tau +
+ * ecckd_increment + ecckd_rte_lw_fused BIT FOR BIT.  There is no asymmetry argument and no delta scaling: a no-scattering
+ * solver uses neither.  At 60 layers (both shipped longwave files) the Planck-recomputing layer-split solver adds the
+ * layer's band value where it reads tau -- a few loads per (column, layer, band), no pass over the g-point arrays; any other
+ * layer count, or a Planck table that does not fit LDS, takes the general route of ecckd_lw_fluxes with the by-band
+ * increment kernel run on the scratch tau between gas optics and the solver (the rate of the API pair).
+ * fp64, fast arithmetic mode only; n_gauss_angles 1..4; inc_flux or NULL; top_at_1 concerns the solver alone, as in
+ * ecckd_lw_fluxes.  ECCKD_DEVICE is asynchronous on `stream`; ECCKD_HOST stages through the model's arena.  tau_p / ssa_p
+ * are never written.  Refused with a message before any device is asked for, in this order: nband_p differs from the
+ * model's band count; tau_p NULL; reference-order arithmetic mode; a model without a Planck table; tlev NULL; a host-only
+ * model.
+ * Scratch (ECCKD_DEVICE): exactly what ecckd_lw_fluxes takes from the stream's block for the shape -- the band planes are
+ * read in place, nothing is staged.  At 60 layers with the fused kernels that is (ncol*nlay*ngpt + 32)*8 bytes (the gas
+ * optical depth); a host that owns the block (ecckd_set_stream_scratch) sizes it so, and the capture rules of
+ * ecckd_lw_fluxes hold unchanged: capture after one warm-up call on the stream, or with a caller-owned block. */
+int ecckd_lw_fluxes_allsky(const ecckd_model_t *model, int ncol, int nlay, const double *plev, const double *tlay,
+                           const double *tsfc, const double *tlev, int ngas, const char *gas_names,
+                           const double *const *vmr, const long long *vmr_col_stride, const long long *vmr_lay_stride,
+                           const double *vmr_scalar, int top_at_1, int n_gauss_angles, const double *sfc_emis,
+                           const double *inc_flux, int nband_p, const double *tau_p, const double *ssa_p,
+                           double *flux_up, double *flux_dn, int memspace, void *stream);
+
 /* Spectral (per-band) fluxes: what RTE-RRTMGP callers get by passing a ty_fluxes_byband to rte_lw /
  * rte_sw instead of the ty_fluxes_broadband the reference drivers use (ecckd_rfmip_lw.F90:108-109).
  * bnd_flux_*(ncol,nlay+1,nband) = sum over the g-points of each band (one solver pass per band over its

@@ -173,6 +173,10 @@ def lib():
     L.ecckd_rte_lw_tail_scratch_bytes.argtypes = [C.c_int] * 6
     L.ecckd_set_stream_scratch.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]
     L.ecckd_release_scratch.argtypes = [C.c_int]
+    if hasattr(L, "ecckd_lw_fluxes_allsky"):   # (ECCKD_LIB may name an older build: tools/bench_lw_allsky.py --parent-lib)
+        L.ecckd_lw_fluxes_allsky.argtypes = ([C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_char_p] +
+                                             [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int] +
+                                             [C.c_void_p] * 4 + [C.c_int, C.c_void_p])
     _lib = L
     return L
 
@@ -412,6 +416,14 @@ class OpticalProps1scl:
         self.band2gpt = spectral_desc.get_band2gpt()
         ng = spectral_desc.get_ngpt()
         self.tau = _empty_like_space((ng, nlay, ncol), like if like is not None else np.empty(0))
+        return ""
+
+    def alloc_1scl_bands(self, ncol, nlay, spectral_desc, like=None):
+        """One-stream properties on the BANDS of ``spectral_desc``: a ``(nband, nlay, ncol)`` array (longwave aerosol
+        optics as a host model carries them)."""
+        self.band2gpt = spectral_desc.get_band2gpt()
+        nb = spectral_desc.get_nband()
+        self.tau = _empty_like_space((nb, nlay, ncol), like if like is not None else np.empty(0))
         return ""
 
     def get_ngpt(self):
@@ -753,6 +765,34 @@ class GasOpticsEcckd:
                                    int(n_gauss_angles), _ptr(sfc_emis, (ncol, self.get_nband()), "sfc_emis"),
                                    _ptr(inc_flux, (ng, ncol), "inc_flux"), _ptr(fluxes.flux_up, (nlay + 1, ncol), "flux_up"),
                                    _ptr(fluxes.flux_dn, (nlay + 1, ncol), "flux_dn"), space, _stream(space))
+        return last_error() if rc else ""
+
+    def lw_fluxes_allsky(self, plev, tlay, tsfc, tlev, gas_desc, top_at_1, sfc_emis, particles, fluxes, n_gauss_angles=1,
+                         inc_flux=None):
+        """``ecckd_lw_fluxes_allsky``: ``lw_fluxes`` with the combined particulate optical properties ``particles`` on
+        the model's bands added to the gas optical depth inside the solver: an ``OpticalProps2str``
+        (``alloc_2str_bands``; absorption optical depth ``tau*(1 - ssa)``, its ``g`` is ignored) or an
+        ``OpticalProps1scl`` (``alloc_1scl_bands``; ``tau`` as it is).  ``particles`` is never written.  float64, fast
+        arithmetic mode; numpy or device tensors.  Returns the error message ('' = success)."""
+        nlay, ncol = tlay.shape
+        ng = self.get_ngpt()
+        ssa = getattr(particles, "ssa", None)
+        try:
+            space = _space_of([plev, tlay, tsfc, tlev, sfc_emis, inc_flux, fluxes.flux_up, fluxes.flux_dn, particles.tau, ssa])
+            n, names, ptrs, cs, ls, sc, keep = self._gas_args(gas_desc, ncol, nlay, space)
+            nbp = 0 if particles.tau is None else int(particles.tau.shape[0])
+            shp = (nbp, nlay, ncol)
+            part = (_ptr(particles.tau, shp, "particles.tau"), _ptr(ssa, shp, "particles.ssa"))
+        except KeyError as e:
+            return str(e.args[0])
+        except (TypeError, ValueError) as e:
+            return str(e)
+        rc = lib().ecckd_lw_fluxes_allsky(
+            self._need(), ncol, nlay, _ptr(plev, (nlay + 1, ncol), "plev"), _ptr(tlay, (nlay, ncol), "tlay"),
+            _ptr(tsfc, (ncol,), "tsfc"), _ptr(tlev, (nlay + 1, ncol), "tlev"), n, names, ptrs, cs, ls, sc, int(bool(top_at_1)),
+            int(n_gauss_angles), _ptr(sfc_emis, (ncol, self.get_nband()), "sfc_emis"), _ptr(inc_flux, (ng, ncol), "inc_flux"),
+            nbp, *part, _ptr(fluxes.flux_up, (nlay + 1, ncol), "flux_up"), _ptr(fluxes.flux_dn, (nlay + 1, ncol), "flux_dn"),
+            space, _stream(space))
         return last_error() if rc else ""
 
     def gas_optics_ext(self, play, plev, tlay, gas_desc, optical_props, toa_src, col_dry=None):

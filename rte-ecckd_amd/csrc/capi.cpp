@@ -1660,9 +1660,16 @@ static size_t fused_scratch_doubles(const ecckd_model *m, int ncol, int nlay) {
   return 3 * n3 + (size_t)ncol * m->ng + 32 + ecckd::rte_lw_scratch_bytes(ncol, nlay, m->ng) / sizeof(double);
 }
 
+// ecckd_lw_fluxes_allsky: the combined particulate optical properties on the model's bands, (ncol,nlay,nband) each, on the
+// device; ssa == nullptr: one-stream particles
+struct LwParticles { const double *tau, *ssa; };
+
+// `pt` (60-layer route only): the band planes the solver adds to tau as it reads it; the general route gets a tau that
+// launch_increment has incremented already
 static int rte_lw_fused_dev(const ecckd_model *m, int ncol, int nlay, int top_at_1, int n_gauss_angles, const double *tau,
                             const double *tlay, const double *tlev, const double *tsfc, const double *sfc_emis,
-                            const double *inc_flux, double *flux_up, double *flux_dn, double *scratch, hipStream_t stream) {
+                            const double *inc_flux, double *flux_up, double *flux_dn, double *scratch, hipStream_t stream,
+                            const LwParticles *pt = nullptr) {
   ecckd::RteLwArgs a{};
   if (fill_band_map(m->ng, m->nband, m->band2gpt.data(), a.gpt2band)) return 1;
   a.ncol = ncol; a.nlay = nlay; a.ng = m->ng; a.top_at_1 = top_at_1 ? 1 : 0;
@@ -1671,6 +1678,7 @@ static int rte_lw_fused_dev(const ecckd_model *m, int ncol, int nlay, int top_at
   a.use_split = 1;
   a.tau = tau; a.sfc_emis = sfc_emis; a.inc_flux = inc_flux; a.flux_up = flux_up; a.flux_dn = flux_dn;
   if (fused_lw_kernels_apply(m, nlay)) {
+    if (pt) { a.part_tau = pt->tau; a.part_ssa = pt->ssa; a.part_1scl = pt->ssa ? 0 : 1; }
     ProfScope prof("rte_lw_fused", stream);
     HIPCHK(ecckd::launch_rte_lw_planck(a, m->dbuf + m->off_planck, m->ntp, m->temperature_planck[0],
                                        m->temperature_planck[1] - m->temperature_planck[0], tlay, tlev, tsfc, stream));
@@ -1714,11 +1722,31 @@ int ecckd_rte_lw_fused(const ecckd_model_t *m, int ncol, int nlay, int top_at_1,
                           flux_dn, static_cast<double *>(sp), st);
 }
 
-int ecckd_lw_fluxes(const ecckd_model_t *m, int ncol, int nlay, const double *plev, const double *tlay, const double *tsfc,
-                    const double *tlev, int ngas, const char *gas_names, const double *const *vmr,
-                    const long long *vmr_col_stride, const long long *vmr_lay_stride, const double *vmr_scalar, int top_at_1,
-                    int n_gauss_angles, const double *sfc_emis, const double *inc_flux, double *flux_up, double *flux_dn,
-                    int memspace, void *stream) {
+// General route of the all-sky call (any layer count): tau += the particles' (absorption) optical depth by band, the
+// one-stream-op1 increment kernel of ecckd_increment on the scratch tau between gas optics and the solver
+static int lw_increment_dev(const ecckd_model *m, int ncol, int nlay, double *tau, const LwParticles &pt, hipStream_t stream) {
+  ecckd::OptPropsArgs o{};
+  o.ncol = ncol; o.nlay = nlay; o.ng = m->ng; o.nband = m->nband; o.f32 = 0;
+  int next = 1;   // the increment kernel wants bands in ascending order that tile 1..ngpt, as ecckd_increment checks
+  for (int b = 0; b < m->nband; ++b) {
+    if (m->band2gpt[2 * b] != next || m->band2gpt[2 * b + 1] < next)
+      return fail("ecckd_lw_fluxes_allsky: the model's band2gpt does not tile 1..ngpt in ascending order");
+    o.band_first[b] = (unsigned short)(next - 1);
+    next = m->band2gpt[2 * b + 1] + 1;
+  }
+  if (next != m->ng + 1) return fail("ecckd_lw_fluxes_allsky: the model's band2gpt does not tile 1..ngpt in ascending order");
+  o.band_first[m->nband] = (unsigned short)m->ng;
+  o.tau1 = tau; o.tau2 = pt.tau; o.ssa2 = pt.ssa; o.g2 = pt.ssa;   // (g2 marks op2 as two-stream; 1scl += 2str never reads it)
+  ProfScope prof("increment", stream);
+  HIPCHK(ecckd::launch_increment(o, stream));
+  return 0;
+}
+
+static int lw_fluxes_impl(const ecckd_model_t *m, int ncol, int nlay, const double *plev, const double *tlay, const double *tsfc,
+                          const double *tlev, int ngas, const char *gas_names, const double *const *vmr,
+                          const long long *vmr_col_stride, const long long *vmr_lay_stride, const double *vmr_scalar, int top_at_1,
+                          int n_gauss_angles, const double *sfc_emis, const double *inc_flux, double *flux_up, double *flux_dn,
+                          int memspace, void *stream, const LwParticles *pt = nullptr) {
   if (check_model(m) || check_gas_optics_dims(ncol, nlay)) return 1;
   if (!m->has_planck) return fail("ecckd_lw_fluxes: model has no Planck table (shortwave model?)");
   if (n_gauss_angles < 1 || n_gauss_angles > 4) return fail("rte_lw: have to ask for at least one quadrature point and no more than 4");
@@ -1737,8 +1765,9 @@ int ecckd_lw_fluxes(const ecckd_model_t *m, int ncol, int nlay, const double *pl
     if (stream_scratch(m->device, st, (n3 + 32 + extra) * sizeof(double), &tau_p, lease)) return 1;
     double *d_tau = static_cast<double *>(tau_p);
     if (gas_optical_depth_dev(m, false, nullptr, ncol, nlay, plev, tlay, gd, d_tau, false, nullptr, nullptr, nullptr, nullptr, st)) return 1;
+    if (pt && !fused_lw_kernels_apply(m, nlay) && lw_increment_dev(m, ncol, nlay, d_tau, *pt, st)) return 1;
     return rte_lw_fused_dev(m, ncol, nlay, top_at_1, n_gauss_angles, d_tau, tlay, tlev, tsfc, sfc_emis, inc_flux, flux_up,
-                            flux_dn, extra ? d_tau + ((n3 + 31) & ~(size_t)31) : nullptr, st);
+                            flux_dn, extra ? d_tau + ((n3 + 31) & ~(size_t)31) : nullptr, st, pt);
   }
   if (memspace != ECCKD_HOST) return fail("ecckd: bad memspace");
   ecckd_model *mm = const_cast<ecckd_model *>(m);
@@ -1746,7 +1775,7 @@ int ecckd_lw_fluxes(const ecckd_model_t *m, int ncol, int nlay, const double *pl
   hipStream_t s = mm->host_stream;
   const size_t need = align256(n2l * 8) * 4 + align256(n2 * 8) + align256((size_t)ncol * 8) + staged_gas_bytes(gd, ncol, nlay, false) +
                       align256((size_t)ncol * m->nband * 8) + align256((size_t)ncol * m->ng * 8) + align256(n3 * 8) +
-                      align256(fused_scratch_doubles(m, ncol, nlay) * 8);
+                      align256(fused_scratch_doubles(m, ncol, nlay) * 8) + (pt ? align256(n2 * m->nband * 8) * (pt->ssa ? 2 : 1) : 0);
   if (grow_arena(mm, need)) return 1;
   Bump b(mm->arena, false);
   double *d_plev = b.take(n2l), *d_tlev = b.take(n2l), *d_tlay = b.take(n2), *d_tsfc = b.take(ncol);
@@ -1760,13 +1789,50 @@ int ecckd_lw_fluxes(const ecckd_model_t *m, int ncol, int nlay, const double *pl
   double *d_tau = b.take(n3);
   const size_t extra = fused_scratch_doubles(m, ncol, nlay);
   double *d_extra = extra ? b.take(extra) : nullptr;
+  LwParticles dp_{};
+  if (pt) {   // staged copies of the band optics
+    const size_t nb3 = n2 * m->nband;
+    double *q_tau = b.take(nb3), *q_ssa = pt->ssa ? b.take(nb3) : nullptr;
+    if (h2d(q_tau, pt->tau, nb3, false, s) || (pt->ssa && h2d(q_ssa, pt->ssa, nb3, false, s))) return 1;
+    dp_ = LwParticles{q_tau, q_ssa};
+  }
   if (gas_optical_depth_dev(m, false, nullptr, ncol, nlay, d_plev, d_tlay, sg.gd, d_tau, false, nullptr, nullptr, nullptr, nullptr, s)) return 1;
+  if (pt && !fused_lw_kernels_apply(m, nlay) && lw_increment_dev(m, ncol, nlay, d_tau, dp_, s)) return 1;
   if (rte_lw_fused_dev(m, ncol, nlay, top_at_1, n_gauss_angles, d_tau, d_tlay, d_tlev, d_tsfc, d_emis, inc_flux ? d_incf : nullptr,
-                       d_up, d_dn, d_extra, s))
+                       d_up, d_dn, d_extra, s, pt ? &dp_ : nullptr))
     return 1;
   if (d2h(flux_up, d_up, n2l, false, s) || d2h(flux_dn, d_dn, n2l, false, s)) return 1;
   HIPCHK(hipStreamSynchronize(s));
   return 0;
+}
+
+int ecckd_lw_fluxes(const ecckd_model_t *m, int ncol, int nlay, const double *plev, const double *tlay, const double *tsfc,
+                    const double *tlev, int ngas, const char *gas_names, const double *const *vmr,
+                    const long long *vmr_col_stride, const long long *vmr_lay_stride, const double *vmr_scalar, int top_at_1,
+                    int n_gauss_angles, const double *sfc_emis, const double *inc_flux, double *flux_up, double *flux_dn,
+                    int memspace, void *stream) {
+  return lw_fluxes_impl(m, ncol, nlay, plev, tlay, tsfc, tlev, ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar,
+                        top_at_1, n_gauss_angles, sfc_emis, inc_flux, flux_up, flux_dn, memspace, stream);
+}
+
+int ecckd_lw_fluxes_allsky(const ecckd_model_t *m, int ncol, int nlay, const double *plev, const double *tlay, const double *tsfc,
+                           const double *tlev, int ngas, const char *gas_names, const double *const *vmr,
+                           const long long *vmr_col_stride, const long long *vmr_lay_stride, const double *vmr_scalar,
+                           int top_at_1, int n_gauss_angles, const double *sfc_emis, const double *inc_flux, int nband_p,
+                           const double *tau_p, const double *ssa_p, double *flux_up, double *flux_dn, int memspace,
+                           void *stream) {
+  // refusals that need no device come first: a host-only model answers them too
+  if (!m) return fail("ecckd: null model");
+  if (nband_p != m->nband)
+    return fail("ecckd_lw_fluxes_allsky: nband_p = " + std::to_string(nband_p) + " but the model has " + std::to_string(m->nband) +
+                " bands (particulate properties live on the model's bands)");
+  if (!tau_p) return fail("ecckd_lw_fluxes_allsky: null argument (tau_p is required; ssa_p may be null: one-stream particles)");
+  if (g_arith.load() != 0) return fail("ecckd_lw_fluxes_allsky: needs the fast arithmetic mode (ecckd_set_arithmetic(0))");
+  if (!m->has_planck) return fail("ecckd_lw_fluxes_allsky: model has no Planck table (shortwave model?)");
+  if (!tlev) return fail("tlev is required for ecckd");
+  const LwParticles pt{tau_p, ssa_p};
+  return lw_fluxes_impl(m, ncol, nlay, plev, tlay, tsfc, tlev, ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar,
+                        top_at_1, n_gauss_angles, sfc_emis, inc_flux, flux_up, flux_dn, memspace, stream, &pt);
 }
 
 // ---- fused shortwave: total optical depth only between the kernels (SURVEY 8(f) rank 4 for the shortwave) ----

@@ -125,6 +125,12 @@ struct RteLwArgs {
   // tail split (rte_lw_tail_plan): tiles from tail_first on are solved one g-pair iteration per wave; -1: none
   long tail_first = -1;
   double *partials = nullptr;  // [tail tile][iteration][dn, up][nlay+1][columns per tile]
+  // Fused all-sky longwave path (ecckd_lw_fluxes_allsky; launch_rte_lw_planck only): the particulate optical properties of
+  // the layer on the model's bands, part_tau / part_ssa (ncol,nlay,nband), are added to the gas optical depth inside the
+  // solver: tau + part_tau * (1 - part_ssa), or tau + part_tau with part_1scl (one-stream particles; part_ssa unused) --
+  // RTE-RRTMGP's increment_1scalar_by_2stream / _by_1scalar, spelt as in kernels_optical_props.hip
+  const double *part_tau = nullptr, *part_ssa = nullptr;
+  int part_1scl = 0;
 };
 
 struct RteSwArgs {

@@ -83,10 +83,17 @@ __device__ __forceinline__ double planck_at(const PlanckTab &P, const double *ta
 constexpr int split_groups(bool planck) { return planck ? 2 : 1; }
 __host__ __device__ constexpr int planck_stride(int ng) { return ng | 1; }   // odd number of doubles per row
 
-template <int SEG, int NW, int CW, bool SHARED, bool SER3, bool PLANCK, int WPS>
-__global__ void __launch_bounds__(64 * NW * split_groups(PLANCK), WPS) rte_lw_split_kernel(const RteLwArgs a, const PlanckTab pt,
-                                                                                          const double *tlay, const double *tlev,
-                                                                                          const double *tsfc) {
+// The kernel text, shared by the clear-sky kernel (SKY = 0: rte_lw_split_kernel) and the all-sky form of the
+// Planck-recomputing solver (rte_lw_split_allsky_kernel).  SKY = 1 / 2: the particulate optical depth of the layer on the
+// model's bands, a.part_tau (ncol,nlay,nband), is added to the gas optical depth in front of tl = tau * D -- as it is
+// (1: one-stream particles, increment_1scalar_by_1scalar) or as the absorption optical depth part_tau * (1 - part_ssa)
+// (2: two-stream particles, increment_1scalar_by_2stream), the expressions of kernels_optical_props.hip operation by
+// operation.  The two g-points of a wave may sit in different bands, so the band offset is per lane; the band values ride
+// in prefetch slots next to ptau[] (one load per (layer, iteration) from planes that stay in L2).
+template <int SEG, int NW, int CW, bool SHARED, bool SER3, bool PLANCK, int SKY>
+__device__ __forceinline__ void rte_lw_split_body(const RteLwArgs &a, const PlanckTab &pt, const double *tlay, const double *tlev,
+                                                  const double *tsfc) {
+  static_assert(SKY == 0 || PLANCK, "the all-sky form extends the Planck-recomputing solver");
   constexpr int GW = 64 / CW;
   constexpr int NL = SEG * NW;
   constexpr int NG = split_groups(PLANCK);
@@ -135,6 +142,8 @@ __global__ void __launch_bounds__(64 * NW * split_groups(PLANCK), WPS) rte_lw_sp
     double ptau[kSplitPF];
     [[maybe_unused]] double play_[PLANCK ? 1 : kSplitPF], pbdn[PLANCK ? 1 : kSplitPF], pbup[(PLANCK || SHARED) ? 1 : kSplitPF];
     [[maybe_unused]] double ptl[PLANCK ? kSplitPF : 1], ptv[PLANCK ? kSplitPF : 1];   // PLANCK: tlay(l), tlev(far edge of l)
+    [[maybe_unused]] double ppt[SKY ? kSplitPF : 1], pps[SKY == 2 ? kSplitPF : 1];   // SKY: part_tau(l), part_ssa(l) of the lane's band
+    [[maybe_unused]] long qb = 0;      // SKY: offset of the lane's band plane
     long qn = 0;
     const long qstep = (long)ncol * lstep;
     [[maybe_unused]] long q2 = 0;      // PLANCK: offset into tlay / tlev rows (no g dimension)
@@ -149,6 +158,7 @@ __global__ void __launch_bounds__(64 * NW * split_groups(PLANCK), WPS) rte_lw_sp
         q2 = cc + (long)ncol * (lay0 + lstep * s0);
         // level at the near (upper, in walking order) edge of the first layer of the segment
         near_first = tlev[cc + (long)ncol * (lev0 + lstep * s0)];
+        if (SKY) qb = (long)ncol * NL * a.gpt2band[gg];
       } else if (SHARED) {
         near_first = __builtin_nontemporal_load(Bup + qn);
       }
@@ -158,6 +168,8 @@ __global__ void __launch_bounds__(64 * NW * split_groups(PLANCK), WPS) rte_lw_sp
       if (PLANCK) {
         ptl[slot] = tlay[q2];
         ptv[slot] = tlev[q2 + (a.top_at_1 ? (long)ncol : 0)];   // far edge of the layer: level index l+1 (top_at_1) or l
+        if (SKY) ppt[slot] = a.part_tau[q2 + qb];
+        if (SKY == 2) pps[slot] = a.part_ssa[q2 + qb];
         q2 += qstep;
       } else {
         play_[slot] = __builtin_nontemporal_load(a.lay_source + qn);
@@ -186,7 +198,9 @@ __global__ void __launch_bounds__(64 * NW * split_groups(PLANCK), WPS) rte_lw_sp
       [[maybe_unused]] double carry = PLANCK ? planck_at(pt, ptab, pstride, near_first, gg, pi_f32, rpi_f32) : near_first;
 #pragma unroll
       for (int s = 0; s < SEG; ++s) {
-        const double tau = ptau[s % kSplitPF];
+        double tau = ptau[s % kSplitPF];
+        if (SKY == 1) tau = tau + ppt[s % kSplitPF];
+        if (SKY == 2) tau = tau + ppt[s % kSplitPF] * (1. - pps[s % kSplitPF]);
         double lay, bdn, bup;
         if (PLANCK) {
           lay = planck_at(pt, ptab, pstride, ptl[s % kSplitPF], gg, pi_f32, rpi_f32);
@@ -286,10 +300,29 @@ __global__ void __launch_bounds__(64 * NW * split_groups(PLANCK), WPS) rte_lw_sp
   }
 }
 
-template <int SEG, int NW, int CW, bool SHARED, bool SER3, bool PLANCK, int WPS = ECCKD_SPLIT_WAVES_PER_SIMD>
+template <int SEG, int NW, int CW, bool SHARED, bool SER3, bool PLANCK, int WPS>
+__global__ void __launch_bounds__(64 * NW * split_groups(PLANCK), WPS) rte_lw_split_kernel(const RteLwArgs a, const PlanckTab pt,
+                                                                                          const double *tlay, const double *tlev,
+                                                                                          const double *tsfc) {
+  rte_lw_split_body<SEG, NW, CW, SHARED, SER3, PLANCK, 0>(a, pt, tlay, tlev, tsfc);
+}
+
+// All-sky form of the Planck-recomputing solver.  TWOSTR: the particles carry part_ssa (absorption optical depth), else
+// part_tau is added as it is.
+template <int SEG, int NW, int CW, bool SER3, bool TWOSTR, int WPS>
+__global__ void __launch_bounds__(64 * NW * split_groups(true), WPS) rte_lw_split_allsky_kernel(const RteLwArgs a, const PlanckTab pt,
+                                                                                               const double *tlay, const double *tlev,
+                                                                                               const double *tsfc) {
+  rte_lw_split_body<SEG, NW, CW, false, SER3, true, TWOSTR ? 2 : 1>(a, pt, tlay, tlev, tsfc);
+}
+
+// SKY: 0 the clear-sky kernel, 1 / 2 the all-sky form with one- / two-stream particles (PLANCK only)
+template <int SEG, int NW, int CW, bool SHARED, bool SER3, bool PLANCK, int WPS = ECCKD_SPLIT_WAVES_PER_SIMD, int SKY = 0>
 hipError_t launch_split(const RteLwArgs &a, const PlanckTab &pt, const double *tlay, const double *tlev, const double *tsfc,
                         hipStream_t s) {
-  auto k = rte_lw_split_kernel<SEG, NW, CW, SHARED, SER3, PLANCK, WPS>;
+  void (*k)(const RteLwArgs, const PlanckTab, const double *, const double *, const double *);
+  if constexpr (SKY != 0) k = rte_lw_split_allsky_kernel<SEG, NW, CW, SER3, SKY == 2, WPS>;
+  else k = rte_lw_split_kernel<SEG, NW, CW, SHARED, SER3, PLANCK, WPS>;
   constexpr int NG = split_groups(PLANCK);
   const size_t lds = sizeof(double) * (NG * (2 * (size_t)(SEG * NW + 1) * CW + 2 * NW * 3 * 64) +
                                        (PLANCK ? (size_t)pt.ntp * planck_stride(a.ng) : 0));
@@ -322,6 +355,11 @@ static hipError_t launch_seg(const RteLwArgs &a, const PlanckTab &pt, const doub
                              hipStream_t s) {
   // The Planck-recomputing form needs 244 VGPRs: 15 layers per wave, two waves per SIMD (three spill 25-54 registers)
   if constexpr (PLANCK) {
+    // all-sky (a.part_tau): the band planes ride in prefetch slots; still two waves per SIMD without a spill
+    if (a.part_tau) {
+      if (a.part_1scl || !a.part_ssa) return launch_split<15, 4, 32, SHARED, SER3, PLANCK, 2, 1>(a, pt, tlay, tlev, tsfc, s);
+      return launch_split<15, 4, 32, SHARED, SER3, PLANCK, 2, 2>(a, pt, tlay, tlev, tsfc, s);
+    }
     return launch_split<15, 4, 32, SHARED, SER3, PLANCK, 2>(a, pt, tlay, tlev, tsfc, s);
   } else {
   switch (a.split_seg) {   // layers per wave: 10 (6 waves per block, 157 VGPRs, 12 waves per CU), 12 or 15

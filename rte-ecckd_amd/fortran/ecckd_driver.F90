@@ -2,13 +2,18 @@
 ! example/rfmip-rad-irf/ecckd_rfmip_lw.F90:107-136 and ecckd_rfmip_sw.F90:112-162: load the ecCKD
 ! file, then per column block gas_optics() followed by rte_lw()/rte_sw(), fluxes out.
 !
-!   ecckd_driver lw|sw  <ecckd_file.nc>  <input.bin>  <output.bin>  [block_size] [n_quad_angles] [device_resident 0|1] [repeats] [byband 0|1] [fused 0|1]
+!   ecckd_driver lw|sw  <ecckd_file.nc>  <input.bin>  <output.bin>  [block_size] [n_quad_angles] [device_resident 0|1] [repeats] [byband 0|1] [fused 0|1] [particles.bin]
 !
 ! device_resident = 1: optical_props / source are the device twins of mo_ecckd_device (tau and the sources stay in
 ! HBM between gas_optics and the solver; ECCKD_MIXED memory space of the C ABI).
 ! repeats: the block loop is run that many times and the best wall time is printed ("loop_seconds", bench.py reads it).
 ! fused = 1: one call ecckd%lw_fluxes(...) / ecckd%sw_fluxes(...) per block instead of gas_optics + rte_lw / rte_sw (the library's
 !            fused paths).
+! particles.bin (needs fused = 1): all-sky -- the combined cloud / aerosol optical properties on the model's bands; one
+!            call ecckd%lw_fluxes_allsky(...) / ecckd%sw_fluxes_allsky(...) per block on a contiguous copy of its columns.
+!            Little-endian: int32 nband, has_ssa_g, delta_scale; then float64 tau(ncol,nlay,nband) and, if has_ssa_g /= 0,
+!            ssa and g of the same shape (the longwave ignores g and delta_scale; without ssa the particles are one-stream,
+!            longwave only).
 ! byband = 1: fluxes go through ty_fluxes_byband (per-band arrays; their sum over bands must reproduce the broadband
 ! fluxes, which are what output.bin holds either way).
 !
@@ -44,6 +49,10 @@ program ecckd_driver
   real(wp), dimension(:,:,:), allocatable :: vmr
   real(wp), dimension(:,:), allocatable, target :: flux_up, flux_dn
   real(wp), dimension(:,:), allocatable :: sfc_spec, sfc_spec2, toa
+  character(len=512) :: part_path
+  logical :: allsky = .false.
+  integer(int32) :: nband_p, has_ssa_g, delta_flag
+  real(wp), dimension(:,:,:), allocatable :: tau_p, ssa_p, g_p
   type(ty_gas_optics_ecckd) :: ecckd
   type(ty_gas_concs), dimension(:), allocatable :: gas_concs   ! one per block, filled before the loop (mo_rfmip_io.F90:177-263)
   class(ty_source_func_lw), allocatable :: source
@@ -54,7 +63,7 @@ program ecckd_driver
   class(ty_fluxes_broadband), pointer :: fluxes
 
   if (command_argument_count() < 4) then
-    write(error_unit, *) "usage: ecckd_driver lw|sw ecckd_file input.bin output.bin [block_size] [n_quad_angles]"
+    call usage()
     stop 1
   end if
   ! ECCKD_SOLVER_OPTION=name=value in the environment: one solver option set through the Fortran binding
@@ -99,6 +108,15 @@ program ecckd_driver
     call get_command_argument(10, arg)
     read(arg, *) fused
   end if
+  if (command_argument_count() >= 11) then
+    call get_command_argument(11, part_path)
+    allsky = len_trim(part_path) > 0
+  end if
+  if (allsky .and. fused == 0) then
+    write(error_unit, "(a)") " ecckd_driver: a particle file needs fused = 1 (lw_fluxes_allsky / sw_fluxes_allsky)"
+    call usage()
+    stop 1
+  end if
   if (byband /= 0) then
     fluxes => fluxes_band
   else
@@ -130,6 +148,19 @@ program ecckd_driver
   read(u) vmr
   close(u)
   play = 0.5_wp * (plev(:, 1:nlay) + plev(:, 2:nlay + 1))
+  if (allsky) then
+    open(newunit=u, file=trim(part_path), access="stream", form="unformatted", status="old")
+    read(u) nband_p, has_ssa_g, delta_flag
+    allocate(tau_p(ncol, nlay, nband_p))
+    read(u) tau_p
+    if (has_ssa_g /= 0) then
+      allocate(ssa_p(ncol, nlay, nband_p), g_p(ncol, nlay, nband_p))
+      read(u) ssa_p, g_p
+    else if (.not. lw) then
+      call stop_on_err("ecckd_driver: shortwave particles need ssa and g (has_ssa_g = 1)")
+    end if
+    close(u)
+  end if
   if (block_size <= 0) block_size = ncol
 
   call stop_on_err(ecckd%load(trim(ecckd_path)))
@@ -176,7 +207,17 @@ program ecckd_driver
         sfc_spec(ibnd, i) = bc1(c0 + i - 1)
       end do
     end do
-    if (lw .and. fused /= 0) then
+    if (lw .and. allsky) then
+      if (has_ssa_g /= 0) then
+        call stop_on_err(ecckd%lw_fluxes_allsky(plev(c0:c1, :), tlay(c0:c1, :), tsfc(c0:c1), tlev(c0:c1, :), gas_concs(b), &
+                                                top_at_1, sfc_spec, tau_p(c0:c1, :, :), flux_up(c0:c1, :), flux_dn(c0:c1, :), &
+                                                ssa_p=ssa_p(c0:c1, :, :), n_gauss_angles=n_quad_angles))
+      else
+        call stop_on_err(ecckd%lw_fluxes_allsky(plev(c0:c1, :), tlay(c0:c1, :), tsfc(c0:c1), tlev(c0:c1, :), gas_concs(b), &
+                                                top_at_1, sfc_spec, tau_p(c0:c1, :, :), flux_up(c0:c1, :), flux_dn(c0:c1, :), &
+                                                n_gauss_angles=n_quad_angles))
+      end if
+    else if (lw .and. fused /= 0) then
       call stop_on_err(ecckd%lw_fluxes(plev(c0:c1, :), tlay(c0:c1, :), tsfc(c0:c1), tlev(c0:c1, :), gas_concs(b), top_at_1, &
                                        sfc_spec, flux_up(c0:c1, :), flux_dn(c0:c1, :), n_gauss_angles=n_quad_angles))
     else if (lw) then
@@ -197,8 +238,14 @@ program ecckd_driver
         sfc_spec(:, i) = bc2(c0 + i - 1)                     ! albedo, direct = diffuse (ecckd_rfmip_sw.F90:136-141)
         sfc_spec2(:, i) = bc2(c0 + i - 1)
       end do
+      if (allsky) then
+        call stop_on_err(ecckd%sw_fluxes_allsky(plev(c0:c1, :), tlay(c0:c1, :), gas_concs(b), top_at_1, bc1(c0:c1), sfc_spec, &
+                                                sfc_spec2, tau_p(c0:c1, :, :), ssa_p(c0:c1, :, :), g_p(c0:c1, :, :), &
+                                                delta_flag /= 0, flux_up(c0:c1, :), flux_dn(c0:c1, :)))
+      else
       call stop_on_err(ecckd%sw_fluxes(plev(c0:c1, :), tlay(c0:c1, :), gas_concs(b), top_at_1, bc1(c0:c1), sfc_spec, sfc_spec2, &
                                        flux_up(c0:c1, :), flux_dn(c0:c1, :)))
+      end if
     else
       if (allocated(sfc_spec2)) deallocate(sfc_spec2)
       if (allocated(toa)) deallocate(toa)
@@ -233,6 +280,11 @@ program ecckd_driver
   write(error_unit, *) "ecckd_driver: ", ncol, " columns in ", nblocks, " blocks done"
 
 contains
+  subroutine usage()
+    write(error_unit, "(a)") " usage: ecckd_driver lw|sw ecckd_file input.bin output.bin [block_size] [n_quad_angles]"
+    write(error_unit, "(a)") "        [device_resident 0|1] [repeats] [byband 0|1] [fused 0|1] [particles.bin]"
+  end subroutine usage
+
   subroutine stop_on_err(msg)                                ! mo_simple_netcdf.F90:331-339
     character(len=*), intent(in) :: msg
     if (len_trim(msg) > 0) then

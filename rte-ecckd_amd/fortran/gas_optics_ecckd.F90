@@ -54,6 +54,8 @@ module gas_optics_ecckd
     procedure, public :: gas_optics_ext
     procedure, public :: lw_fluxes          !< extension: gas_optics + rte_lw in one call (fused longwave path)
     procedure, public :: sw_fluxes          !< extension: gas_optics + rte_sw in one call (fused shortwave path)
+    procedure, public :: lw_fluxes_allsky   !< extension: lw_fluxes with particulate optics on the model's bands
+    procedure, public :: sw_fluxes_allsky   !< extension: sw_fluxes with particulate optics on the model's bands
   end type ty_gas_optics_ecckd
 
   interface
@@ -198,6 +200,38 @@ module gas_optics_ecckd
       type(c_ptr), value :: stream
       integer(c_int) :: rc
     end function c_sw_fluxes
+    function c_lw_fluxes_allsky(model, ncol, nlay, plev, tlay, tsfc, tlev, ngas, gas_names, vmr, cs, ls, scalar, top_at_1, nmus, &
+                                sfc_emis, inc_flux, nband_p, tau_p, ssa_p, flux_up, flux_dn, memspace, stream) &
+        bind(C, name="ecckd_lw_fluxes_allsky") result(rc)
+      import c_ptr, c_int, c_double, c_char, c_long_long
+      type(c_ptr), value :: model
+      integer(c_int), value :: ncol, nlay, ngas, top_at_1, nmus, nband_p, memspace
+      real(c_double), dimension(*), intent(in) :: plev, tlay, tsfc, tlev, sfc_emis, tau_p
+      character(kind=c_char), dimension(*), intent(in) :: gas_names
+      type(c_ptr), dimension(*), intent(in) :: vmr
+      integer(c_long_long), dimension(*), intent(in) :: cs, ls
+      real(c_double), dimension(*), intent(in) :: scalar
+      type(c_ptr), value :: inc_flux, ssa_p
+      real(c_double), dimension(*), intent(inout) :: flux_up, flux_dn
+      type(c_ptr), value :: stream
+      integer(c_int) :: rc
+    end function c_lw_fluxes_allsky
+    function c_sw_fluxes_allsky(model, ncol, nlay, plev, tlay, ngas, gas_names, vmr, cs, ls, scalar, top_at_1, mu0, toa_scale, &
+                                sfc_alb_dir, sfc_alb_dif, nband_p, tau_p, ssa_p, g_p, delta_scale, flux_up, flux_dn, flux_dir, &
+                                memspace, stream) bind(C, name="ecckd_sw_fluxes_allsky") result(rc)
+      import c_ptr, c_int, c_double, c_char, c_long_long
+      type(c_ptr), value :: model
+      integer(c_int), value :: ncol, nlay, ngas, top_at_1, nband_p, delta_scale, memspace
+      real(c_double), dimension(*), intent(in) :: plev, tlay, mu0, sfc_alb_dir, sfc_alb_dif, tau_p, ssa_p, g_p
+      character(kind=c_char), dimension(*), intent(in) :: gas_names
+      type(c_ptr), dimension(*), intent(in) :: vmr
+      integer(c_long_long), dimension(*), intent(in) :: cs, ls
+      real(c_double), dimension(*), intent(in) :: scalar
+      type(c_ptr), value :: toa_scale, flux_dir
+      real(c_double), dimension(*), intent(inout) :: flux_up, flux_dn
+      type(c_ptr), value :: stream
+      integer(c_int) :: rc
+    end function c_sw_fluxes_allsky
   end interface
 
   public :: c_error_message, c_loc_3d, c_loc_2d
@@ -608,6 +642,137 @@ contains
     flux_dn = dn
     if (present(flux_dir)) flux_dir = dir
   end function sw_fluxes
+
+  !> Extension: lw_fluxes with the combined particulate (cloud, aerosol) optical properties on the model's bands,
+  !! tau_p / ssa_p (ncol, nlay, nband), added to the gas optical depth inside the solver (ecckd_lw_fluxes_allsky):
+  !! tau_gas + tau_p*(1 - ssa_p) with ssa_p [increment_1scalar_by_2stream, by band], tau_gas + tau_p without it
+  !! [increment_1scalar_by_1scalar: one-stream particles].  Host arrays in, host fluxes out; the particulate arrays are
+  !! never written.  flux_up / flux_dn are (ncol, nlay+1), sfc_emis (nband, ncol).
+  function lw_fluxes_allsky(this, plev, tlay, tsfc, tlev, gas_desc, top_at_1, sfc_emis, tau_p, flux_up, flux_dn, ssa_p, &
+                            n_gauss_angles) result(error_msg)
+    class(ty_gas_optics_ecckd), intent(in) :: this
+    real(wp), dimension(:,:), intent(in) :: plev, tlay, tlev
+    real(wp), dimension(:), intent(in) :: tsfc
+    type(ty_gas_concs), intent(in) :: gas_desc
+    logical, intent(in) :: top_at_1
+    real(wp), dimension(:,:), intent(in) :: sfc_emis
+    real(wp), dimension(:,:,:), intent(in) :: tau_p
+    real(wp), dimension(:,:), intent(inout) :: flux_up, flux_dn
+    real(wp), dimension(:,:,:), intent(in), optional :: ssa_p
+    integer, intent(in), optional :: n_gauss_angles
+    character(len=128) :: error_msg
+    character(kind=c_char), dimension(:), allocatable :: names
+    type(c_ptr), dimension(:), allocatable :: ptr
+    integer(c_long_long), dimension(:), allocatable :: cs, ls
+    real(c_double), dimension(:), allocatable :: scalar
+    real(wp), dimension(:,:), allocatable :: up, dn
+    real(wp), dimension(:,:,:), allocatable, target :: ssa
+    type(c_ptr) :: ssa_c
+    integer :: ncol, nlay, n, nmus
+    integer(c_int) :: rc
+    ncol = size(tlay, 1)
+    nlay = size(tlay, 2)
+    nmus = 1
+    if (present(n_gauss_angles)) nmus = n_gauss_angles
+    error_msg = marshal_gases(this, gas_desc, ncol, nlay, names, ptr, cs, ls, scalar)
+    if (trim(error_msg) /= "") return
+    if (size(sfc_emis, 1) /= this%get_nband() .or. size(sfc_emis, 2) /= ncol) then
+      error_msg = "lw_fluxes_allsky: sfc_emis inconsistently sized"
+      return
+    end if
+    if (size(tau_p, 1) /= ncol .or. size(tau_p, 2) /= nlay) then
+      error_msg = "lw_fluxes_allsky: tau_p inconsistently sized"
+      return
+    end if
+    ssa_c = c_null_ptr
+    if (present(ssa_p)) then
+      if (any(shape(ssa_p) /= shape(tau_p))) then
+        error_msg = "lw_fluxes_allsky: ssa_p inconsistently sized"
+        return
+      end if
+      allocate(ssa(size(ssa_p, 1), size(ssa_p, 2), size(ssa_p, 3)))
+      ssa = ssa_p
+      if (size(ssa) > 0) ssa_c = c_loc(ssa(1, 1, 1))
+    end if
+    n = gas_desc%get_num_gases()
+    allocate(up(ncol, nlay + 1), dn(ncol, nlay + 1))
+    rc = c_lw_fluxes_allsky(this%handle, int(ncol, c_int), int(nlay, c_int), plev, tlay, tsfc, tlev, int(n, c_int), names, ptr, &
+                            cs, ls, scalar, merge(1_c_int, 0_c_int, top_at_1), int(nmus, c_int), sfc_emis, c_null_ptr, &
+                            int(size(tau_p, 3), c_int), tau_p, ssa_c, up, dn, ECCKD_HOST, c_null_ptr)
+    if (rc /= 0) then
+      error_msg = c_error_message()
+      return
+    end if
+    flux_up = up
+    flux_dn = dn
+  end function lw_fluxes_allsky
+
+  !> Extension: sw_fluxes with the combined particulate optical properties on the model's bands, tau_p / ssa_p / g_p
+  !! (ncol, nlay, nband), added to the gas optics inside the solver (ecckd_sw_fluxes_allsky) [increment_2stream_by_2stream];
+  !! delta_scale: the library first delta-scales a copy of them with f = g*g.  Host arrays in, host fluxes out; the
+  !! particulate arrays are never written.  The other arguments are those of sw_fluxes.
+  function sw_fluxes_allsky(this, plev, tlay, gas_desc, top_at_1, mu0, sfc_alb_dir, sfc_alb_dif, tau_p, ssa_p, g_p, delta_scale, &
+                            flux_up, flux_dn, flux_dir, toa_scale) result(error_msg)
+    class(ty_gas_optics_ecckd), intent(in) :: this
+    real(wp), dimension(:,:), intent(in) :: plev, tlay
+    type(ty_gas_concs), intent(in) :: gas_desc
+    logical, intent(in) :: top_at_1
+    real(wp), dimension(:), intent(in) :: mu0
+    real(wp), dimension(:,:), intent(in) :: sfc_alb_dir, sfc_alb_dif
+    real(wp), dimension(:,:,:), intent(in) :: tau_p, ssa_p, g_p
+    logical, intent(in) :: delta_scale
+    real(wp), dimension(:,:), intent(inout) :: flux_up, flux_dn
+    real(wp), dimension(:,:), intent(inout), optional :: flux_dir
+    real(wp), dimension(:), intent(in), optional, target :: toa_scale
+    character(len=128) :: error_msg
+    character(kind=c_char), dimension(:), allocatable :: names
+    type(c_ptr), dimension(:), allocatable :: ptr
+    integer(c_long_long), dimension(:), allocatable :: cs, ls
+    real(c_double), dimension(:), allocatable :: scalar
+    real(wp), dimension(:,:), allocatable, target :: up, dn, dir
+    real(wp), dimension(:), allocatable, target :: scale
+    type(c_ptr) :: scale_p, dir_p
+    integer :: ncol, nlay, n
+    integer(c_int) :: rc
+    ncol = size(tlay, 1)
+    nlay = size(tlay, 2)
+    error_msg = marshal_gases(this, gas_desc, ncol, nlay, names, ptr, cs, ls, scalar)
+    if (trim(error_msg) /= "") return
+    if (size(sfc_alb_dir, 1) /= this%get_nband() .or. size(sfc_alb_dir, 2) /= ncol .or. &
+        size(sfc_alb_dif, 1) /= this%get_nband() .or. size(sfc_alb_dif, 2) /= ncol) then
+      error_msg = "sw_fluxes_allsky: surface albedos inconsistently sized"
+      return
+    end if
+    if (size(tau_p, 1) /= ncol .or. size(tau_p, 2) /= nlay .or. any(shape(ssa_p) /= shape(tau_p)) .or. &
+        any(shape(g_p) /= shape(tau_p))) then
+      error_msg = "sw_fluxes_allsky: tau_p, ssa_p, g_p inconsistently sized"
+      return
+    end if
+    n = gas_desc%get_num_gases()
+    allocate(up(ncol, nlay + 1), dn(ncol, nlay + 1))
+    scale_p = c_null_ptr
+    dir_p = c_null_ptr
+    if (present(toa_scale)) then
+      allocate(scale(ncol))
+      scale = toa_scale
+      scale_p = c_loc(scale(1))
+    end if
+    if (present(flux_dir)) then
+      allocate(dir(ncol, nlay + 1))
+      dir_p = c_loc(dir(1, 1))
+    end if
+    rc = c_sw_fluxes_allsky(this%handle, int(ncol, c_int), int(nlay, c_int), plev, tlay, int(n, c_int), names, ptr, cs, ls, &
+                            scalar, merge(1_c_int, 0_c_int, top_at_1), mu0, scale_p, sfc_alb_dir, sfc_alb_dif, &
+                            int(size(tau_p, 3), c_int), tau_p, ssa_p, g_p, merge(1_c_int, 0_c_int, delta_scale), up, dn, dir_p, &
+                            ECCKD_HOST, c_null_ptr)
+    if (rc /= 0) then
+      error_msg = c_error_message()
+      return
+    end if
+    flux_up = up
+    flux_dn = dn
+    if (present(flux_dir)) flux_dir = dir
+  end function sw_fluxes_allsky
 
   function c_loc_3d(a) result(p)
     real(wp), dimension(:,:,:), intent(in), target, contiguous :: a
