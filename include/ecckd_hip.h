@@ -415,6 +415,81 @@ int ecckd_lw_fluxes_allsky(const ecckd_model_t *model, int ncol, int nlay, const
                            const double *inc_flux, int nband_p, const double *tau_p, const double *ssa_p,
                            double *flux_up, double *flux_dn, int memspace, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * McICA cloud sampling (Pincus et al. 2003): cloud fraction through the all-sky calls.  The calls above treat a cloudy
+ * layer as overcast.  A host with a cloud fraction draws a per-g-point cloud mask from it under an overlap assumption and
+ * the particulate optical depth of the (layer, g-point) cells that came out clear is taken as zero.
+ *
+ * A cloud mask is ONE `unsigned long long` per (column, layer): array (ncol,nlay), column fastest, in the layer order of
+ * tlay; bit g (0-based g-point) set = that g-point sees the layer's particles.  It serves at most 64 g-points (every ecCKD
+ * file: 27, 32, 36); every call below refuses ngpt > 64 with a message before anything is launched.
+ *
+ * ecckd_cloud_mask_sample: the definition is this project's own.  It restates the rank-carrying generator of Raisanen et
+ * al. (2004), on which RTE-RRTMGP's mo_cloud_sampling (sampled_mask_max_ran, sampled_mask_exp_ran) is built, from the
+ * published description; RTE-RRTMGP is not part of the reference tree, so PARITY WITH IT IS UNPINNED.  The random numbers
+ * are made in the kernel by a counter-based generator, so the mask of a column depends on (seed, global column index,
+ * layer, g-point) only -- not on the launch shape, the block a host cuts its columns into, or the GPU a column range is
+ * sharded to; col0 = global index of the call's first column.  (An array of caller-made randoms is deliberately not taken.)
+ *   - Philox4x32-10 (Salmon et al. 2011; multipliers 0xD2511F53, 0xCD9E8D57, Weyl constants 0x9E3779B9, 0xBB67AE85).
+ *     For the global column c = col0 + i, layer l (0-based, array order) and g-point g (0-based):
+ *         counter = (c & 0xffffffff, c >> 32, l, (g >> 2) | (s << 31)),  key = (seed & 0xffffffff, seed >> 32),
+ *         draw = (output word (g & 3) >> 8) * 2^-24        (exact in fp64, in [0,1))
+ *     s = 0 gives u(c,l,g), s = 1 gives v(c,l,g).
+ *   - correlation of the rank between layers l-1 and l:  a(l) = 0 if l = 0 or either layer's cloud_frac is not > 0 (a clear
+ *     layer -- zero, negative or NaN -- decorrelates: the "-random" part); else 1 (ECCKD_OVERLAP_MAX_RAN) or overlap_param(i, l-1) (ECCKD_OVERLAP_EXP_RAN)
+ *   - rank:  r(l,g) = v(c,l,g) < a(l) ? r(l-1,g) : u(c,l,g)
+ *   - bit g of mask(i,l) = cloud_frac(i,l) > 0 && r(l,g) >= 1 - cloud_frac(i,l)   (subtraction and comparison in fp64)
+ *     Bits ngpt..63 are 0.  A NaN cloud fraction gives a clear layer; cloud_frac = 1 is always cloudy.
+ *   Everything is integer arithmetic plus exact fp64 operations: the words are reproducible bit for bit
+ *   (tests/mcica_helpers.py).  overlap_param (ncol,nlay-1) is read with ECCKD_OVERLAP_EXP_RAN only (else pass NULL).
+ *   cloud_frac or overlap_param outside [0,1]: an error with ECCKD_HOST arrays (checked before anything is launched),
+ *   undefined with ECCKD_DEVICE arrays (not checked: the call stays asynchronous) -- the rule of ecckd_delta_scale's `forward`.
+ *   Refused with a message, in this order: ngpt > 64; ngpt < 1; unknown overlap; ECCKD_OVERLAP_EXP_RAN without
+ *   overlap_param; bad ncol / nlay; cloud_frac or mask NULL; bad memspace; host values outside [0,1]; no device.
+ *   fp64 only.  ECCKD_DEVICE is asynchronous on `stream` and uses no scratch; ECCKD_HOST stages and synchronises.
+ *
+ * ecckd_increment_masked (+ _f32): ecckd_increment with `mask` (ncol,nlay) in `memspace`.  Where bit g is clear the cell is
+ * incremented AS IF tau2 WERE +0 THERE (what RTE-RRTMGP's draw_samples followed by increment computes), spelt with the
+ * operations of ecckd_increment; ssa2 / g2 are still read, so a non-finite value in a masked-out cell propagates as it
+ * would through 0*x.  All four combinations, on g-points and by band.  mask NULL: ecckd_increment.  ngpt > 64 with a mask
+ * is refused first, then ecckd_increment's own list.
+ *
+ * ecckd_sw_fluxes_allsky_mcica / ecckd_lw_fluxes_allsky_mcica: the fused all-sky calls with `cloud_mask` (ncol,nlay) in
+ * `memspace`.  The particulate optical depth a cell uses is  bit ? tau_p : 0  in front of the expressions of the unmasked
+ * call -- one select per cell, nothing else changes; with delta_scale = 1 the band triple is scaled first (independent of
+ * the mask), then masked.  cloud_mask NULL forwards to the unmasked call.  Longwave: fluxes equal ecckd_gas_optics_lw_tau +
+ * ecckd_increment_masked + ecckd_rte_lw_fused BIT FOR BIT (60 layers: masked layer-split kernel; any other layer count: the
+ * masked by-band increment on the scratch optical depth).  Shortwave: the masked forms of the layer-systolic (up to 60
+ * layers) and two-pass solvers; agreement with the composed calls to rounding, as for the unmasked call.  Refused with a
+ * message: a model of more than 64 g-points first, then the unmasked call's own list in its order.  Scratch sizes and
+ * capture rules are those of the unmasked calls (the mask is read in place).  Parity with RTE-RRTMGP unpinned, as above.
+ * --------------------------------------------------------------------------------------- */
+#define ECCKD_OVERLAP_MAX_RAN 0
+#define ECCKD_OVERLAP_EXP_RAN 1
+int ecckd_cloud_mask_sample(int device, int ncol, int nlay, int ngpt, int overlap, const double *cloud_frac,
+                            const double *overlap_param, unsigned long long seed, long long col0, unsigned long long *mask,
+                            int memspace, void *stream);
+int ecckd_increment_masked(int device, int ncol, int nlay, int ngpt, double *tau1, double *ssa1, double *g1, int nband,
+                           const int *band2gpt, const double *tau2, const double *ssa2, const double *g2,
+                           const unsigned long long *mask, int memspace, void *stream);
+int ecckd_increment_masked_f32(int device, int ncol, int nlay, int ngpt, float *tau1, float *ssa1, float *g1, int nband,
+                               const int *band2gpt, const float *tau2, const float *ssa2, const float *g2,
+                               const unsigned long long *mask, int memspace, void *stream);
+int ecckd_sw_fluxes_allsky_mcica(const ecckd_model_t *model, int ncol, int nlay, const double *plev, const double *tlay, int ngas,
+                                 const char *gas_names, const double *const *vmr, const long long *vmr_col_stride,
+                                 const long long *vmr_lay_stride, const double *vmr_scalar, int top_at_1, const double *mu0,
+                                 const double *toa_scale, const double *sfc_alb_dir, const double *sfc_alb_dif, int nband_p,
+                                 const double *tau_p, const double *ssa_p, const double *g_p, int delta_scale,
+                                 const unsigned long long *cloud_mask, double *flux_up, double *flux_dn, double *flux_dir,
+                                 int memspace, void *stream);
+int ecckd_lw_fluxes_allsky_mcica(const ecckd_model_t *model, int ncol, int nlay, const double *plev, const double *tlay,
+                                 const double *tsfc, const double *tlev, int ngas, const char *gas_names,
+                                 const double *const *vmr, const long long *vmr_col_stride, const long long *vmr_lay_stride,
+                                 const double *vmr_scalar, int top_at_1, int n_gauss_angles, const double *sfc_emis,
+                                 const double *inc_flux, int nband_p, const double *tau_p, const double *ssa_p,
+                                 const unsigned long long *cloud_mask, double *flux_up, double *flux_dn, int memspace,
+                                 void *stream);
+
 /* Spectral (per-band) fluxes: what RTE-RRTMGP callers get by passing a ty_fluxes_byband to rte_lw /
  * rte_sw instead of the ty_fluxes_broadband the reference drivers use (ecckd_rfmip_lw.F90:108-109).
  * bnd_flux_*(ncol,nlay+1,nband) = sum over the g-points of each band (one solver pass per band over its

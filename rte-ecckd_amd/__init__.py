@@ -35,6 +35,7 @@ NAME_LEN = 32
 
 _SOURCES = ["kernels_gas_fused.hip", "kernels_tau.hip", "kernels_planck.hip", "kernels_rte_lw.hip", "kernels_rte_lw_split.hip",
             "kernels_rte_sw.hip", "kernels_rte_sw_sys.hip", "kernels_rte_gpt.hip", "kernels_optical_props.hip",
+            "kernels_cloud_sampling.hip",
             "capi.cpp", "nc_capi.cpp", "model.cpp", "cdf1.cpp"]
 _HEADERS = ["kernels.hpp", "wave_pair.hpp", "sw_two_stream.hpp", "sw_two_stream_body.inc", "lw_layer.hpp", "model.hpp", "cdf1.hpp", os.path.join("..", "..", "include", "ecckd_hip.h"),
             os.path.join("..", "..", "include", "ecckd_nc.h"), os.path.join("..", "..", "include", "rte_kernels_hip.h")]
@@ -177,6 +178,17 @@ def lib():
         L.ecckd_lw_fluxes_allsky.argtypes = ([C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_char_p] +
                                              [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int] +
                                              [C.c_void_p] * 4 + [C.c_int, C.c_void_p])
+    if hasattr(L, "ecckd_cloud_mask_sample"):   # (the McICA calls: 64-bit seed / col0 and the mask pointer need prototypes)
+        L.ecckd_cloud_mask_sample.argtypes = [C.c_int] * 5 + [C.c_void_p, C.c_void_p, C.c_ulonglong, C.c_longlong, C.c_void_p,
+                                                              C.c_int, C.c_void_p]
+        for f in ("ecckd_increment_masked", "ecckd_increment_masked_f32"):
+            getattr(L, f).argtypes = [C.c_int] * 4 + [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.c_void_p]
+        L.ecckd_lw_fluxes_allsky_mcica.argtypes = ([C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_char_p] +
+                                                   [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int] +
+                                                   [C.c_void_p] * 5 + [C.c_int, C.c_void_p])
+        L.ecckd_sw_fluxes_allsky_mcica.argtypes = ([C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 2 + [C.c_int, C.c_char_p] +
+                                                   [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 3 +
+                                                   [C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_void_p])
     _lib = L
     return L
 
@@ -325,6 +337,61 @@ def _empty_like_space(shape, like):
     return np.empty(shape, dtype=np.float32 if _is_f32(like) else np.float64)
 
 
+def _mask_ptr(mask, nlay, ncol, space):
+    """Data pointer of a cloud mask ``(nlay, ncol)``: numpy uint64 (host) or a torch int64 device tensor (same bits)."""
+    if mask is None:
+        return None
+    if _is_torch(mask):
+        import torch
+        if space != DEVICE or not mask.is_cuda:
+            raise TypeError("cloud_mask: mixing host and device arrays in one call")
+        if mask.dtype != torch.int64 or not mask.is_contiguous():
+            raise TypeError("cloud_mask: need a contiguous int64 tensor (the bits of the uint64 words)")
+        if tuple(mask.shape) != (nlay, ncol):
+            raise ValueError("cloud_mask: shape %s, expected %s" % (tuple(mask.shape), (nlay, ncol)))
+        return C.c_void_p(mask.data_ptr())
+    if space != HOST:
+        raise TypeError("cloud_mask: mixing host and device arrays in one call")
+    if not isinstance(mask, np.ndarray) or mask.dtype != np.uint64 or not mask.flags.c_contiguous:
+        raise TypeError("cloud_mask: need a C-contiguous uint64 ndarray")
+    if mask.shape != (nlay, ncol):
+        raise ValueError("cloud_mask: shape %s, expected %s" % (mask.shape, (nlay, ncol)))
+    return C.c_void_p(mask.ctypes.data)
+
+
+_OVERLAP = {"max_ran": 0, "exp_ran": 1}
+
+
+def sample_cloud_mask(cloud_frac, ngpt, overlap="max_ran", overlap_param=None, seed=0, col0=0, device=0):
+    """McICA cloud mask (``ecckd_cloud_mask_sample``; the definition is in include/ecckd_hip.h): ``cloud_frac``
+    ``(nlay, ncol)`` float64, ``overlap`` ``"max_ran"`` or ``"exp_ran"`` (then ``overlap_param`` ``(nlay-1, ncol)``),
+    ``col0`` the global index of the first column.  numpy arrays give a ``uint64 (nlay, ncol)`` array; torch device tensors
+    give an ``int64`` tensor with the same bits, asynchronously on the current stream (``device`` is then the tensor's).
+    Bit g of a word set = g-point g sees the layer's cloud.  Raises ValueError with the library's message."""
+    nlay, ncol = cloud_frac.shape
+    code = _OVERLAP.get(overlap, overlap) if isinstance(overlap, str) else overlap
+    if not isinstance(code, int):
+        raise ValueError("sample_cloud_mask: unknown overlap %r (one of %s)" % (overlap, sorted(_OVERLAP)))
+    try:
+        space = _space_of([cloud_frac, overlap_param])
+        cf = _ptr(cloud_frac, (nlay, ncol), "cloud_frac")
+        al = _ptr(overlap_param, (max(nlay - 1, 0), ncol), "overlap_param")
+    except TypeError as e:
+        raise ValueError(str(e))
+    if space == DEVICE:
+        import torch
+        mask = torch.empty((nlay, ncol), dtype=torch.int64, device=cloud_frac.device)
+        mp, device = C.c_void_p(mask.data_ptr()), _device_of(cloud_frac)
+    else:
+        mask = np.zeros((nlay, ncol), dtype=np.uint64)
+        mp = C.c_void_p(mask.ctypes.data)
+    rc = lib().ecckd_cloud_mask_sample(int(device), ncol, nlay, int(ngpt), int(code), cf, al, int(seed) & (2**64 - 1), int(col0),
+                                       mp, space, _stream(space))
+    if rc:
+        raise ValueError(last_error())
+    return mask
+
+
 # ------------------------------------------------------------------------------------------
 # RTE-RRTMGP data types, as far as the reference touches them
 # ------------------------------------------------------------------------------------------
@@ -429,11 +496,13 @@ class OpticalProps1scl:
     def get_ngpt(self):
         return self.tau.shape[0]
 
-    def increment(self, other, band2gpt=None):
+    def increment(self, other, band2gpt=None, cloud_mask=None):
         """``self += other`` (RTE-RRTMGP's ``op%increment``; ``ecckd_increment`` / ``_f32``): ``other`` one- or
         two-stream, on the same g-points, or -- with ``band2gpt`` ``(nband, 2)``, 1-based inclusive -- on bands
-        ``(nband, nlay, ncol)``.  Returns the error message ('' = success)."""
-        return _increment(self, other, band2gpt)
+        ``(nband, nlay, ncol)``.  ``cloud_mask`` ``(nlay, ncol)`` (``sample_cloud_mask``; ``ecckd_increment_masked``):
+        where bit g of a word is clear, g-point g is incremented as if ``other.tau`` were 0 there.
+        Returns the error message ('' = success)."""
+        return _increment(self, other, band2gpt, cloud_mask)
 
 
 class OpticalProps2str(OpticalProps1scl):
@@ -768,12 +837,14 @@ class GasOpticsEcckd:
         return last_error() if rc else ""
 
     def lw_fluxes_allsky(self, plev, tlay, tsfc, tlev, gas_desc, top_at_1, sfc_emis, particles, fluxes, n_gauss_angles=1,
-                         inc_flux=None):
+                         inc_flux=None, cloud_mask=None):
         """``ecckd_lw_fluxes_allsky``: ``lw_fluxes`` with the combined particulate optical properties ``particles`` on
         the model's bands added to the gas optical depth inside the solver: an ``OpticalProps2str``
         (``alloc_2str_bands``; absorption optical depth ``tau*(1 - ssa)``, its ``g`` is ignored) or an
         ``OpticalProps1scl`` (``alloc_1scl_bands``; ``tau`` as it is).  ``particles`` is never written.  float64, fast
-        arithmetic mode; numpy or device tensors.  Returns the error message ('' = success)."""
+        arithmetic mode; numpy or device tensors.  ``cloud_mask`` ``(nlay, ncol)`` (``sample_cloud_mask``;
+        ``ecckd_lw_fluxes_allsky_mcica``): a g-point whose bit is clear sees no particles in that layer.
+        Returns the error message ('' = success)."""
         nlay, ncol = tlay.shape
         ng = self.get_ngpt()
         ssa = getattr(particles, "ssa", None)
@@ -783,11 +854,13 @@ class GasOpticsEcckd:
             nbp = 0 if particles.tau is None else int(particles.tau.shape[0])
             shp = (nbp, nlay, ncol)
             part = (_ptr(particles.tau, shp, "particles.tau"), _ptr(ssa, shp, "particles.ssa"))
+            if cloud_mask is not None:
+                part = part + (_mask_ptr(cloud_mask, nlay, ncol, space),)
         except KeyError as e:
             return str(e.args[0])
         except (TypeError, ValueError) as e:
             return str(e)
-        rc = lib().ecckd_lw_fluxes_allsky(
+        rc = (lib().ecckd_lw_fluxes_allsky if cloud_mask is None else lib().ecckd_lw_fluxes_allsky_mcica)(
             self._need(), ncol, nlay, _ptr(plev, (nlay + 1, ncol), "plev"), _ptr(tlay, (nlay, ncol), "tlay"),
             _ptr(tsfc, (ncol,), "tsfc"), _ptr(tlev, (nlay + 1, ncol), "tlev"), n, names, ptrs, cs, ls, sc, int(bool(top_at_1)),
             int(n_gauss_angles), _ptr(sfc_emis, (ncol, self.get_nband()), "sfc_emis"), _ptr(inc_flux, (ng, ncol), "inc_flux"),
@@ -816,16 +889,20 @@ class GasOpticsEcckd:
         return last_error() if rc else ""
 
     def sw_fluxes_allsky(self, plev, tlay, gas_desc, top_at_1, mu0, sfc_alb_dir, sfc_alb_dif, particles, fluxes,
-                         delta_scale=True, toa_scale=None):
+                         delta_scale=True, toa_scale=None, cloud_mask=None):
         """``ecckd_sw_fluxes_allsky``: ``sw_fluxes`` with the combined particulate optical properties ``particles``
         (an ``OpticalProps2str`` on the model's bands, ``alloc_2str_bands``) added to the gas optics inside the solver;
         ``delta_scale``: the library delta-scales a copy of them (f = g*g) first, ``particles`` is never written.
-        float64, fast arithmetic mode."""
+        float64, fast arithmetic mode.  ``cloud_mask`` ``(nlay, ncol)`` (``sample_cloud_mask``;
+        ``ecckd_sw_fluxes_allsky_mcica``): a g-point whose bit is clear sees no particles in that layer."""
         nlay, ncol = tlay.shape
         nband = self.get_nband()
+        mp = ()
         try:
             space = _space_of([plev, tlay, mu0, toa_scale, sfc_alb_dir, sfc_alb_dif, fluxes.flux_up, fluxes.flux_dn,
                                particles.tau, particles.ssa, particles.g])
+            if cloud_mask is not None:
+                mp = (_mask_ptr(cloud_mask, nlay, ncol, space),)
             n, names, ptrs, cs, ls, sc, keep = self._gas_args(gas_desc, ncol, nlay, space)
             nbp = int(particles.tau.shape[0])
             shp = (nbp, nlay, ncol)
@@ -835,11 +912,11 @@ class GasOpticsEcckd:
             return str(e.args[0])
         except (TypeError, ValueError) as e:
             return str(e)
-        rc = lib().ecckd_sw_fluxes_allsky(
+        rc = (lib().ecckd_sw_fluxes_allsky if cloud_mask is None else lib().ecckd_sw_fluxes_allsky_mcica)(
             self._need(), ncol, nlay, _ptr(plev, (nlay + 1, ncol), "plev"), _ptr(tlay, (nlay, ncol), "tlay"), n, names, ptrs,
             cs, ls, sc, int(bool(top_at_1)), _ptr(mu0, (ncol,), "mu0"), _ptr(toa_scale, (ncol,), "toa_scale"),
             _ptr(sfc_alb_dir, (ncol, nband), "sfc_alb_dir"), _ptr(sfc_alb_dif, (ncol, nband), "sfc_alb_dif"), nbp, *part,
-            int(bool(delta_scale)), _ptr(fluxes.flux_up, (nlay + 1, ncol), "flux_up"),
+            int(bool(delta_scale)), *mp, _ptr(fluxes.flux_up, (nlay + 1, ncol), "flux_up"),
             _ptr(fluxes.flux_dn, (nlay + 1, ncol), "flux_dn"), _ptr(fluxes.flux_dn_dir, (nlay + 1, ncol), "flux_dn_dir"),
             space, _stream(space))
         return last_error() if rc else ""
@@ -878,8 +955,8 @@ def _device_of(a):
     return 0
 
 
-def _increment(op1, op2, band2gpt):
-    """``ecckd_increment`` / ``_f32`` on the Python containers (OpticalProps1scl.increment)."""
+def _increment(op1, op2, band2gpt, cloud_mask=None):
+    """``ecckd_increment`` / ``_f32`` (with a mask: ``ecckd_increment_masked``) on the Python containers."""
     ng, nlay, ncol = op1.tau.shape
     f32 = _is_f32(op1.tau)
     two1, two2 = isinstance(op1, OpticalProps2str), isinstance(op2, OpticalProps2str)
@@ -894,11 +971,16 @@ def _increment(op1, op2, band2gpt):
         P2 = lambda a, what: _ptr(a, (n2, nlay, ncol), what, f32)
         a1 = (P1(op1.tau, "tau"), P1(op1.ssa, "ssa") if two1 else None, P1(op1.g, "g") if two1 else None)
         a2 = (P2(op2.tau, "other.tau"), P2(op2.ssa, "other.ssa") if two2 else None, P2(op2.g, "other.g") if two2 else None)
+        mp = _mask_ptr(cloud_mask, nlay, ncol, space)
     except (TypeError, ValueError) as e:
         return str(e)
-    rc = (lib().ecckd_increment_f32 if f32 else lib().ecckd_increment)(
-        int(_device_of(op1.tau)), ncol, nlay, ng, *a1, nband, C.c_void_p(b2g.ctypes.data) if b2g is not None else None, *a2,
-        space, _stream(space))
+    b2p = C.c_void_p(b2g.ctypes.data) if b2g is not None else None
+    if cloud_mask is not None:
+        rc = (lib().ecckd_increment_masked_f32 if f32 else lib().ecckd_increment_masked)(
+            int(_device_of(op1.tau)), ncol, nlay, ng, *a1, nband, b2p, *a2, mp, space, _stream(space))
+    else:
+        rc = (lib().ecckd_increment_f32 if f32 else lib().ecckd_increment)(
+            int(_device_of(op1.tau)), ncol, nlay, ng, *a1, nband, b2p, *a2, space, _stream(space))
     return last_error() if rc else ""
 
 

@@ -197,6 +197,7 @@ inline double *dp(float *p) { return reinterpret_cast<double *>(p); }
 struct SwDerive {
   const double *plev, *rayleigh, *solar, *toa_scale; double gw; double *room;
   const double *part_tau = nullptr, *part_ssa = nullptr, *part_g = nullptr;
+  const unsigned long long *part_mask = nullptr;   // ecckd_sw_fluxes_allsky_mcica (RteSwArgs::part_mask), or null
 };
 // What a public entry point asks of the solver implementations besides its arguments.
 struct Call {
@@ -1409,7 +1410,7 @@ static int rte_sw_impl(const Call &c, int device, int ncol, int nlay, int ngpt, 
     a.derive = 1;
     a.plev = dv->plev; a.rayleigh = dv->rayleigh; a.solar = dv->solar; a.gw = dv->gw;
     a.toa_scale = dv->toa_scale;
-    if (dv->part_tau) { a.allsky = 1; a.part_tau = dv->part_tau; a.part_ssa = dv->part_ssa; a.part_g = dv->part_g; }
+    if (dv->part_tau) { a.allsky = 1; a.part_tau = dv->part_tau; a.part_ssa = dv->part_ssa; a.part_g = dv->part_g; a.part_mask = dv->part_mask; }
   }
   const size_t n3 = (size_t)ncol * nlay * ngpt, n2l = (size_t)ncol * (nlay + 1);
   const hipStream_t launch_stream = memspace == ECCKD_DEVICE ? static_cast<hipStream_t>(stream) : nullptr;
@@ -1662,7 +1663,9 @@ static size_t fused_scratch_doubles(const ecckd_model *m, int ncol, int nlay) {
 
 // ecckd_lw_fluxes_allsky: the combined particulate optical properties on the model's bands, (ncol,nlay,nband) each, on the
 // device; ssa == nullptr: one-stream particles
-struct LwParticles { const double *tau, *ssa; };
+static const char kMaskTooWide[] = ": a cloud mask is one 64-bit word per (column, layer): at most 64 g-points, not ";
+// mask: ecckd_lw_fluxes_allsky_mcica -- the cloud mask (ncol,nlay), in the memory space of the call, or null
+struct LwParticles { const double *tau, *ssa; const unsigned long long *mask = nullptr; };
 
 // `pt` (60-layer route only): the band planes the solver adds to tau as it reads it; the general route gets a tau that
 // launch_increment has incremented already
@@ -1678,7 +1681,7 @@ static int rte_lw_fused_dev(const ecckd_model *m, int ncol, int nlay, int top_at
   a.use_split = 1;
   a.tau = tau; a.sfc_emis = sfc_emis; a.inc_flux = inc_flux; a.flux_up = flux_up; a.flux_dn = flux_dn;
   if (fused_lw_kernels_apply(m, nlay)) {
-    if (pt) { a.part_tau = pt->tau; a.part_ssa = pt->ssa; a.part_1scl = pt->ssa ? 0 : 1; }
+    if (pt) { a.part_tau = pt->tau; a.part_ssa = pt->ssa; a.part_1scl = pt->ssa ? 0 : 1; a.part_mask = pt->mask; }
     ProfScope prof("rte_lw_fused", stream);
     HIPCHK(ecckd::launch_rte_lw_planck(a, m->dbuf + m->off_planck, m->ntp, m->temperature_planck[0],
                                        m->temperature_planck[1] - m->temperature_planck[0], tlay, tlev, tsfc, stream));
@@ -1737,6 +1740,7 @@ static int lw_increment_dev(const ecckd_model *m, int ncol, int nlay, double *ta
   if (next != m->ng + 1) return fail("ecckd_lw_fluxes_allsky: the model's band2gpt does not tile 1..ngpt in ascending order");
   o.band_first[m->nband] = (unsigned short)m->ng;
   o.tau1 = tau; o.tau2 = pt.tau; o.ssa2 = pt.ssa; o.g2 = pt.ssa;   // (g2 marks op2 as two-stream; 1scl += 2str never reads it)
+  o.mask = pt.mask;   // (McICA: the masked by-band increment)
   ProfScope prof("increment", stream);
   HIPCHK(ecckd::launch_increment(o, stream));
   return 0;
@@ -1775,7 +1779,8 @@ static int lw_fluxes_impl(const ecckd_model_t *m, int ncol, int nlay, const doub
   hipStream_t s = mm->host_stream;
   const size_t need = align256(n2l * 8) * 4 + align256(n2 * 8) + align256((size_t)ncol * 8) + staged_gas_bytes(gd, ncol, nlay, false) +
                       align256((size_t)ncol * m->nband * 8) + align256((size_t)ncol * m->ng * 8) + align256(n3 * 8) +
-                      align256(fused_scratch_doubles(m, ncol, nlay) * 8) + (pt ? align256(n2 * m->nband * 8) * (pt->ssa ? 2 : 1) : 0);
+                      align256(fused_scratch_doubles(m, ncol, nlay) * 8) + (pt ? align256(n2 * m->nband * 8) * (pt->ssa ? 2 : 1) : 0) +
+                      (pt && pt->mask ? align256(n2 * 8) : 0);
   if (grow_arena(mm, need)) return 1;
   Bump b(mm->arena, false);
   double *d_plev = b.take(n2l), *d_tlev = b.take(n2l), *d_tlay = b.take(n2), *d_tsfc = b.take(ncol);
@@ -1795,6 +1800,11 @@ static int lw_fluxes_impl(const ecckd_model_t *m, int ncol, int nlay, const doub
     double *q_tau = b.take(nb3), *q_ssa = pt->ssa ? b.take(nb3) : nullptr;
     if (h2d(q_tau, pt->tau, nb3, false, s) || (pt->ssa && h2d(q_ssa, pt->ssa, nb3, false, s))) return 1;
     dp_ = LwParticles{q_tau, q_ssa};
+    if (pt->mask) {   // (8-byte words: staged like an array of doubles)
+      double *q_mask = b.take(n2);
+      if (h2d(q_mask, reinterpret_cast<const double *>(pt->mask), n2, false, s)) return 1;
+      dp_.mask = reinterpret_cast<const unsigned long long *>(q_mask);
+    }
   }
   if (gas_optical_depth_dev(m, false, nullptr, ncol, nlay, d_plev, d_tlay, sg.gd, d_tau, false, nullptr, nullptr, nullptr, nullptr, s)) return 1;
   if (pt && !fused_lw_kernels_apply(m, nlay) && lw_increment_dev(m, ncol, nlay, d_tau, dp_, s)) return 1;
@@ -1815,14 +1825,18 @@ int ecckd_lw_fluxes(const ecckd_model_t *m, int ncol, int nlay, const double *pl
                         top_at_1, n_gauss_angles, sfc_emis, inc_flux, flux_up, flux_dn, memspace, stream);
 }
 
-int ecckd_lw_fluxes_allsky(const ecckd_model_t *m, int ncol, int nlay, const double *plev, const double *tlay, const double *tsfc,
-                           const double *tlev, int ngas, const char *gas_names, const double *const *vmr,
-                           const long long *vmr_col_stride, const long long *vmr_lay_stride, const double *vmr_scalar,
-                           int top_at_1, int n_gauss_angles, const double *sfc_emis, const double *inc_flux, int nband_p,
-                           const double *tau_p, const double *ssa_p, double *flux_up, double *flux_dn, int memspace,
-                           void *stream) {
-  // refusals that need no device come first: a host-only model answers them too
+// The one refusal list of the fused all-sky longwave calls.  cloud_mask (ecckd_lw_fluxes_allsky_mcica), or null: with a
+// mask, a model of more than 64 g-points is refused first.  Refusals that need no device come first: a host-only model
+// answers them too.
+static int lw_fluxes_allsky_impl(const ecckd_model_t *m, int ncol, int nlay, const double *plev, const double *tlay,
+                                 const double *tsfc, const double *tlev, int ngas, const char *gas_names,
+                                 const double *const *vmr, const long long *vmr_col_stride, const long long *vmr_lay_stride,
+                                 const double *vmr_scalar, int top_at_1, int n_gauss_angles, const double *sfc_emis,
+                                 const double *inc_flux, int nband_p, const double *tau_p, const double *ssa_p,
+                                 const unsigned long long *cloud_mask, double *flux_up, double *flux_dn, int memspace,
+                                 void *stream) {
   if (!m) return fail("ecckd: null model");
+  if (cloud_mask && m->ng > 64) return fail("ecckd_lw_fluxes_allsky_mcica" + std::string(kMaskTooWide) + std::to_string(m->ng));
   if (nband_p != m->nband)
     return fail("ecckd_lw_fluxes_allsky: nband_p = " + std::to_string(nband_p) + " but the model has " + std::to_string(m->nband) +
                 " bands (particulate properties live on the model's bands)");
@@ -1830,16 +1844,40 @@ int ecckd_lw_fluxes_allsky(const ecckd_model_t *m, int ncol, int nlay, const dou
   if (g_arith.load() != 0) return fail("ecckd_lw_fluxes_allsky: needs the fast arithmetic mode (ecckd_set_arithmetic(0))");
   if (!m->has_planck) return fail("ecckd_lw_fluxes_allsky: model has no Planck table (shortwave model?)");
   if (!tlev) return fail("tlev is required for ecckd");
-  const LwParticles pt{tau_p, ssa_p};
+  const LwParticles pt{tau_p, ssa_p, cloud_mask};
   return lw_fluxes_impl(m, ncol, nlay, plev, tlay, tsfc, tlev, ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar,
                         top_at_1, n_gauss_angles, sfc_emis, inc_flux, flux_up, flux_dn, memspace, stream, &pt);
+}
+
+int ecckd_lw_fluxes_allsky(const ecckd_model_t *m, int ncol, int nlay, const double *plev, const double *tlay, const double *tsfc,
+                           const double *tlev, int ngas, const char *gas_names, const double *const *vmr,
+                           const long long *vmr_col_stride, const long long *vmr_lay_stride, const double *vmr_scalar,
+                           int top_at_1, int n_gauss_angles, const double *sfc_emis, const double *inc_flux, int nband_p,
+                           const double *tau_p, const double *ssa_p, double *flux_up, double *flux_dn, int memspace,
+                           void *stream) {
+  return lw_fluxes_allsky_impl(m, ncol, nlay, plev, tlay, tsfc, tlev, ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride,
+                               vmr_scalar, top_at_1, n_gauss_angles, sfc_emis, inc_flux, nband_p, tau_p, ssa_p, nullptr, flux_up,
+                               flux_dn, memspace, stream);
+}
+
+int ecckd_lw_fluxes_allsky_mcica(const ecckd_model_t *m, int ncol, int nlay, const double *plev, const double *tlay,
+                                 const double *tsfc, const double *tlev, int ngas, const char *gas_names,
+                                 const double *const *vmr, const long long *vmr_col_stride, const long long *vmr_lay_stride,
+                                 const double *vmr_scalar, int top_at_1, int n_gauss_angles, const double *sfc_emis,
+                                 const double *inc_flux, int nband_p, const double *tau_p, const double *ssa_p,
+                                 const unsigned long long *cloud_mask, double *flux_up, double *flux_dn, int memspace,
+                                 void *stream) {
+  return lw_fluxes_allsky_impl(m, ncol, nlay, plev, tlay, tsfc, tlev, ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride,
+                               vmr_scalar, top_at_1, n_gauss_angles, sfc_emis, inc_flux, nband_p, tau_p, ssa_p, cloud_mask, flux_up,
+                               flux_dn, memspace, stream);
 }
 
 // ---- fused shortwave: total optical depth only between the kernels (SURVEY 8(f) rank 4 for the shortwave) ----
 
 // ecckd_sw_fluxes_allsky: the combined particulate optical properties on the model's bands, (ncol,nlay,nband) each, in the
 // memory space of the call; delta_scale: the library delta-scales a copy (f = g*g) first
-struct SwParticles { const double *tau, *ssa, *g; int delta_scale; };
+// mask: ecckd_sw_fluxes_allsky_mcica -- the cloud mask (ncol,nlay), in the memory space of the call, or null
+struct SwParticles { const double *tau, *ssa, *g; int delta_scale; const unsigned long long *mask = nullptr; };
 
 static int sw_fluxes_impl(bool f32, const ecckd_model_t *m, int ncol, int nlay, const double *plev, const double *tlay,
                           int ngas, const char *gas_names, const double *const *vmr, const long long *vmr_col_stride,
@@ -1882,7 +1920,7 @@ static int sw_fluxes_impl(bool f32, const ecckd_model_t *m, int ncol, int nlay, 
       return 1;
     SwDerive dv{plev, rayleigh, solar, toa_scale, gw(f32),
                 solver ? reinterpret_cast<double *>(static_cast<char *>(tau_p) + tau_bytes) : nullptr};
-    if (pt) { dv.part_tau = dp_.tau; dv.part_ssa = dp_.ssa; dv.part_g = dp_.g; }
+    if (pt) { dv.part_tau = dp_.tau; dv.part_ssa = dp_.ssa; dv.part_g = dp_.g; dv.part_mask = dp_.mask; }   // (the mask is read in place)
     return rte_sw_impl(Call{f32, -1, false, &dv}, m->device, ncol, nlay, m->ng, top_at_1, d_tau, nullptr, nullptr, mu0,
                        nullptr, m->nband, m->band2gpt.data(), sfc_alb_dir, sfc_alb_dif, flux_up, flux_dn, flux_dir,
                        ECCKD_DEVICE, stream);
@@ -1893,7 +1931,7 @@ static int sw_fluxes_impl(bool f32, const ecckd_model_t *m, int ncol, int nlay, 
   hipStream_t s = mm->host_stream;
   const size_t solver = sw_fluxes_solver_bytes(m->device, ncol, nlay, m->ng);
   const size_t nb3 = n2 * m->nband;
-  const size_t need = (pt ? align256(nb3 * es) * 3 : 0) + align256(n2l * es) * 4 + align256(n2 * es) + align256((size_t)ncol * es) * 2 +
+  const size_t need = (pt ? align256(nb3 * es) * 3 : 0) + (pt && pt->mask ? align256(n2 * 8) : 0) + align256(n2l * es) * 4 + align256(n2 * es) + align256((size_t)ncol * es) * 2 +
                       staged_gas_bytes(gd, ncol, nlay, f32) + align256((size_t)ncol * m->nband * es) * 2 + align256(n3 * es) +
                       align256(solver);
   if (grow_arena(mm, need)) return 1;
@@ -1917,6 +1955,11 @@ static int sw_fluxes_impl(bool f32, const ecckd_model_t *m, int ncol, int nlay, 
     if (h2d(q_tau, pt->tau, nb3, f32, s) || h2d(q_ssa, pt->ssa, nb3, f32, s) || h2d(q_g, pt->g, nb3, f32, s)) return 1;
     if (pt->delta_scale) HIPCHK(ecckd::launch_delta_scale(nb3, q_tau, q_ssa, q_g, nullptr, q_tau, q_ssa, q_g, 0, s));
     dv.part_tau = q_tau; dv.part_ssa = q_ssa; dv.part_g = q_g;
+    if (pt->mask) {   // (8-byte words whatever the precision: a room of its own, copied as bytes)
+      double *q_mask = b.take((n2 * 8 + es - 1) / es);
+      HIPCHK(hipMemcpyAsync(q_mask, pt->mask, n2 * 8, hipMemcpyHostToDevice, s));
+      dv.part_mask = reinterpret_cast<const unsigned long long *>(q_mask);
+    }
   }
   if (rte_sw_impl(Call{f32, -1, false, &dv}, m->device, ncol, nlay, m->ng, top_at_1, d_tau, nullptr, nullptr, d_mu0, nullptr,
                   m->nband, m->band2gpt.data(), d_ad, d_af, d_up, d_dn, flux_dir ? d_dir : nullptr, ECCKD_DEVICE, s))
@@ -1936,23 +1979,48 @@ int ecckd_sw_fluxes(const ecckd_model_t *m, int ncol, int nlay, const double *pl
                         top_at_1, mu0, toa_scale, sfc_alb_dir, sfc_alb_dif, flux_up, flux_dn, flux_dir, memspace, stream);
 }
 
-int ecckd_sw_fluxes_allsky(const ecckd_model_t *m, int ncol, int nlay, const double *plev, const double *tlay, int ngas,
-                           const char *gas_names, const double *const *vmr, const long long *vmr_col_stride,
-                           const long long *vmr_lay_stride, const double *vmr_scalar, int top_at_1, const double *mu0,
-                           const double *toa_scale, const double *sfc_alb_dir, const double *sfc_alb_dif, int nband_p,
-                           const double *tau_p, const double *ssa_p, const double *g_p, int delta_scale, double *flux_up,
-                           double *flux_dn, double *flux_dir, int memspace, void *stream) {
-  // refusals that need no device come first: a host-only model answers them too
+// The one refusal list of the fused all-sky shortwave calls; cloud_mask as in lw_fluxes_allsky_impl.
+static int sw_fluxes_allsky_impl(const ecckd_model_t *m, int ncol, int nlay, const double *plev, const double *tlay, int ngas,
+                                 const char *gas_names, const double *const *vmr, const long long *vmr_col_stride,
+                                 const long long *vmr_lay_stride, const double *vmr_scalar, int top_at_1, const double *mu0,
+                                 const double *toa_scale, const double *sfc_alb_dir, const double *sfc_alb_dif, int nband_p,
+                                 const double *tau_p, const double *ssa_p, const double *g_p, int delta_scale,
+                                 const unsigned long long *cloud_mask, double *flux_up, double *flux_dn, double *flux_dir,
+                                 int memspace, void *stream) {
   if (!m) return fail("ecckd: null model");
+  if (cloud_mask && m->ng > 64) return fail("ecckd_sw_fluxes_allsky_mcica" + std::string(kMaskTooWide) + std::to_string(m->ng));
   if (nband_p != m->nband)
     return fail("ecckd_sw_fluxes_allsky: nband_p = " + std::to_string(nband_p) + " but the model has " + std::to_string(m->nband) +
                 " bands (particulate properties live on the model's bands)");
   if (!tau_p || !ssa_p || !g_p) return fail("ecckd_sw_fluxes_allsky: null argument (tau_p, ssa_p and g_p are all required)");
   if (delta_scale != 0 && delta_scale != 1) return fail("ecckd_sw_fluxes_allsky: delta_scale must be 0 or 1");
   if (g_arith.load() != 0) return fail("ecckd_sw_fluxes_allsky: needs the fast arithmetic mode (ecckd_set_arithmetic(0))");
-  const SwParticles pt{tau_p, ssa_p, g_p, delta_scale};
+  const SwParticles pt{tau_p, ssa_p, g_p, delta_scale, cloud_mask};
   return sw_fluxes_impl(false, m, ncol, nlay, plev, tlay, ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar,
                         top_at_1, mu0, toa_scale, sfc_alb_dir, sfc_alb_dif, flux_up, flux_dn, flux_dir, memspace, stream, &pt);
+}
+
+int ecckd_sw_fluxes_allsky(const ecckd_model_t *m, int ncol, int nlay, const double *plev, const double *tlay, int ngas,
+                           const char *gas_names, const double *const *vmr, const long long *vmr_col_stride,
+                           const long long *vmr_lay_stride, const double *vmr_scalar, int top_at_1, const double *mu0,
+                           const double *toa_scale, const double *sfc_alb_dir, const double *sfc_alb_dif, int nband_p,
+                           const double *tau_p, const double *ssa_p, const double *g_p, int delta_scale, double *flux_up,
+                           double *flux_dn, double *flux_dir, int memspace, void *stream) {
+  return sw_fluxes_allsky_impl(m, ncol, nlay, plev, tlay, ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar,
+                               top_at_1, mu0, toa_scale, sfc_alb_dir, sfc_alb_dif, nband_p, tau_p, ssa_p, g_p, delta_scale, nullptr,
+                               flux_up, flux_dn, flux_dir, memspace, stream);
+}
+
+int ecckd_sw_fluxes_allsky_mcica(const ecckd_model_t *m, int ncol, int nlay, const double *plev, const double *tlay, int ngas,
+                                 const char *gas_names, const double *const *vmr, const long long *vmr_col_stride,
+                                 const long long *vmr_lay_stride, const double *vmr_scalar, int top_at_1, const double *mu0,
+                                 const double *toa_scale, const double *sfc_alb_dir, const double *sfc_alb_dif, int nband_p,
+                                 const double *tau_p, const double *ssa_p, const double *g_p, int delta_scale,
+                                 const unsigned long long *cloud_mask, double *flux_up, double *flux_dn, double *flux_dir,
+                                 int memspace, void *stream) {
+  return sw_fluxes_allsky_impl(m, ncol, nlay, plev, tlay, ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar,
+                               top_at_1, mu0, toa_scale, sfc_alb_dir, sfc_alb_dif, nband_p, tau_p, ssa_p, g_p, delta_scale,
+                               cloud_mask, flux_up, flux_dn, flux_dir, memspace, stream);
 }
 
 // ---- element-wise operations on optical properties (kernels_optical_props.hip) ----
@@ -2001,9 +2069,11 @@ int ecckd_delta_scale_f32(int device, int ncol, int nlay, int n, float *tau, flo
   return delta_scale_impl(true, device, ncol, nlay, n, dp(tau), dp(ssa), dp(g), dp(forward), memspace, stream);
 }
 
+// mask: ecckd_increment_masked -- one word per (column, layer) in `memspace`, or null
 static int increment_impl(bool f32, int device, int ncol, int nlay, int ngpt, double *tau1, double *ssa1, double *g1, int nband,
                           const int *band2gpt, const double *tau2, const double *ssa2, const double *g2, int memspace,
-                          void *stream) {
+                          void *stream, const unsigned long long *mask = nullptr) {
+  if (mask && ngpt > 64) return fail("ecckd_increment_masked" + std::string(kMaskTooWide) + std::to_string(ngpt));
   if (check_dims(ncol, nlay)) return 1;
   if (ngpt < 1) return fail("ecckd_increment: ngpt must be at least 1");
   if (!tau1 || !tau2) return fail("ecckd_increment: null argument (tau1 and tau2 are required)");
@@ -2035,7 +2105,7 @@ static int increment_impl(bool f32, int device, int ncol, int nlay, int ngpt, do
   const size_t n1 = (size_t)ncol * nlay * ngpt, n2 = (size_t)ncol * nlay * (nband > 0 ? nband : ngpt);
   if (memspace == ECCKD_DEVICE) {
     hipStream_t st = static_cast<hipStream_t>(stream);
-    a.tau1 = tau1; a.ssa1 = ssa1; a.g1 = g1; a.tau2 = tau2; a.ssa2 = ssa2; a.g2 = g2;
+    a.tau1 = tau1; a.ssa1 = ssa1; a.g1 = g1; a.tau2 = tau2; a.ssa2 = ssa2; a.g2 = g2; a.mask = mask;
     ProfScope prof("increment", st);
     HIPCHK(ecckd::launch_increment(a, st));
     return 0;
@@ -2043,9 +2113,15 @@ static int increment_impl(bool f32, int device, int ncol, int nlay, int ngpt, do
   Arena &ar = g_solver_arena[device];
   std::lock_guard<std::mutex> lock(ar.mu);
   const size_t es = esz(f32);
-  if (ar.ensure(align256(n1 * es) * (ssa1 ? 3 : 1) + align256(n2 * es) * (ssa2 ? 3 : 1))) return 1;
+  const size_t nm = mask ? (size_t)ncol * nlay : 0;
+  if (ar.ensure(align256(n1 * es) * (ssa1 ? 3 : 1) + align256(n2 * es) * (ssa2 ? 3 : 1) + align256(nm * 8))) return 1;
   Bump b(ar.p, f32);
   hipStream_t s = nullptr;
+  if (mask) {   // (8-byte words whatever the precision: copied as bytes)
+    double *d_m = b.take((nm * 8 + es - 1) / es);
+    HIPCHK(hipMemcpyAsync(d_m, mask, nm * 8, hipMemcpyHostToDevice, s));
+    a.mask = reinterpret_cast<const unsigned long long *>(d_m);
+  }
   double *d_t1 = b.take(n1), *d_s1 = ssa1 ? b.take(n1) : nullptr, *d_g1 = ssa1 ? b.take(n1) : nullptr;
   double *d_t2 = b.take(n2), *d_s2 = ssa2 ? b.take(n2) : nullptr, *d_g2 = ssa2 ? b.take(n2) : nullptr;
   if (h2d(d_t1, tau1, n1, f32, s) || h2d(d_t2, tau2, n2, f32, s)) return 1;
@@ -2068,6 +2144,61 @@ int ecckd_increment_f32(int device, int ncol, int nlay, int ngpt, float *tau1, f
                         const int *band2gpt, const float *tau2, const float *ssa2, const float *g2, int memspace, void *stream) {
   return increment_impl(true, device, ncol, nlay, ngpt, dp(tau1), dp(ssa1), dp(g1), nband, band2gpt, dp(tau2), dp(ssa2), dp(g2),
                         memspace, stream);
+}
+
+int ecckd_increment_masked(int device, int ncol, int nlay, int ngpt, double *tau1, double *ssa1, double *g1, int nband,
+                           const int *band2gpt, const double *tau2, const double *ssa2, const double *g2,
+                           const unsigned long long *mask, int memspace, void *stream) {
+  return increment_impl(false, device, ncol, nlay, ngpt, tau1, ssa1, g1, nband, band2gpt, tau2, ssa2, g2, memspace, stream, mask);
+}
+int ecckd_increment_masked_f32(int device, int ncol, int nlay, int ngpt, float *tau1, float *ssa1, float *g1, int nband,
+                               const int *band2gpt, const float *tau2, const float *ssa2, const float *g2,
+                               const unsigned long long *mask, int memspace, void *stream) {
+  return increment_impl(true, device, ncol, nlay, ngpt, dp(tau1), dp(ssa1), dp(g1), nband, band2gpt, dp(tau2), dp(ssa2), dp(g2),
+                        memspace, stream, mask);
+}
+
+// ---- McICA cloud sampling (kernels_cloud_sampling.hip) ----
+
+int ecckd_cloud_mask_sample(int device, int ncol, int nlay, int ngpt, int overlap, const double *cloud_frac,
+                            const double *overlap_param, unsigned long long seed, long long col0, unsigned long long *mask,
+                            int memspace, void *stream) {
+  if (ngpt > 64) return fail("ecckd_cloud_mask_sample" + std::string(kMaskTooWide) + std::to_string(ngpt));
+  if (ngpt < 1) return fail("ecckd_cloud_mask_sample: ngpt must be at least 1");
+  if (overlap != ECCKD_OVERLAP_MAX_RAN && overlap != ECCKD_OVERLAP_EXP_RAN)
+    return fail("ecckd_cloud_mask_sample: unknown overlap " + std::to_string(overlap) +
+                " (ECCKD_OVERLAP_MAX_RAN = 0, ECCKD_OVERLAP_EXP_RAN = 1)");
+  const bool exp_ran = overlap == ECCKD_OVERLAP_EXP_RAN;
+  if (exp_ran && !overlap_param && nlay > 1) return fail("ecckd_cloud_mask_sample: ECCKD_OVERLAP_EXP_RAN needs overlap_param");
+  if (check_dims(ncol, nlay)) return 1;
+  if (!cloud_frac || !mask) return fail("ecckd_cloud_mask_sample: null argument (cloud_frac and mask are required)");
+  if (memspace != ECCKD_DEVICE && memspace != ECCKD_HOST) return fail("ecckd: bad memspace");
+  const size_t n2 = (size_t)ncol * nlay, np = exp_ran && nlay > 1 ? (size_t)ncol * (nlay - 1) : 0;
+  if (memspace == ECCKD_HOST) {   // (a NaN fraction is a clear layer, a NaN parameter no correlation: neither is refused)
+    for (size_t i = 0; i < n2; ++i)
+      if (cloud_frac[i] < 0. || cloud_frac[i] > 1.) return fail("ecckd_cloud_mask_sample: cloud fraction outside [0, 1]");
+    for (size_t i = 0; i < np; ++i)
+      if (overlap_param[i] < 0. || overlap_param[i] > 1.) return fail("ecckd_cloud_mask_sample: overlap parameter outside [0, 1]");
+  }
+  if (check_device(device)) return 1;
+  if (ncol == 0) return 0;
+  if (memspace == ECCKD_DEVICE) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    ProfScope prof("cloud_mask_sample", st);
+    HIPCHK(ecckd::launch_cloud_mask_sample(ncol, nlay, ngpt, exp_ran, cloud_frac, np ? overlap_param : nullptr, seed, col0, mask, st));
+    return 0;
+  }
+  Arena &ar = g_solver_arena[device];
+  std::lock_guard<std::mutex> lock(ar.mu);
+  if (ar.ensure(align256(n2 * 8) * 2 + align256(np * 8))) return 1;
+  Bump b(ar.p, false);
+  hipStream_t s = nullptr;
+  double *d_cf = b.take(n2), *d_mask = b.take(n2), *d_al = np ? b.take(np) : nullptr;
+  if (h2d(d_cf, cloud_frac, n2, false, s) || (np && h2d(d_al, overlap_param, np, false, s))) return 1;
+  HIPCHK(ecckd::launch_cloud_mask_sample(ncol, nlay, ngpt, exp_ran, d_cf, d_al, seed, col0, reinterpret_cast<unsigned long long *>(d_mask), s));
+  if (d2h(reinterpret_cast<double *>(mask), d_mask, n2, false, s)) return 1;
+  HIPCHK(hipStreamSynchronize(s));
+  return 0;
 }
 
 int ecckd_sw_fluxes_f32(const ecckd_model_t *m, int ncol, int nlay, const float *plev, const float *tlay, int ngas,

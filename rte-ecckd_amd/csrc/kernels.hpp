@@ -131,6 +131,9 @@ struct RteLwArgs {
   // RTE-RRTMGP's increment_1scalar_by_2stream / _by_1scalar, spelt as in kernels_optical_props.hip
   const double *part_tau = nullptr, *part_ssa = nullptr;
   int part_1scl = 0;
+  // McICA (ecckd_lw_fluxes_allsky_mcica): one word per (column, layer), bit g set = g-point g sees the layer's particles;
+  // where it is clear the cell uses part_tau = 0.  Null: every g-point sees them (the unmasked kernels).
+  const unsigned long long *part_mask = nullptr;
 };
 
 struct RteSwArgs {
@@ -169,6 +172,8 @@ struct RteSwArgs {
   // solver with the expressions of RTE-RRTMGP's increment_2stream_by_2stream (see kernels_optical_props.hip)
   int allsky = 0;
   const double *part_tau = nullptr, *part_ssa = nullptr, *part_g = nullptr;
+  // McICA (ecckd_sw_fluxes_allsky_mcica): as RteLwArgs::part_mask
+  const unsigned long long *part_mask = nullptr;
 };
 
 // Element-wise operations on optical properties (kernels_optical_props.hip): RTE-RRTMGP's delta_scale_2str_k / _f_k and
@@ -180,6 +185,9 @@ struct OptPropsArgs {
   double *tau1, *ssa1, *g1;    // ssa1 / g1 null: op1 is one-stream
   const double *tau2, *ssa2, *g2;   // ssa2 / g2 null: op2 is one-stream
   unsigned short band_first[257];   // nband > 0: band b covers the 0-based g-points [band_first[b], band_first[b+1])
+  // ecckd_increment_masked: one word per (column, layer), bit g clear = the cell is incremented as if tau2 were +0 there
+  // (ng <= 64); null: the unmasked kernels
+  const unsigned long long *mask = nullptr;
 };
 // eps = 3 * tiny(1._wp): the floor of the denominators in those kernels (and where the all-sky solver forms ssa and g)
 template <typename real> __host__ __device__ constexpr real op_eps() {
@@ -190,6 +198,11 @@ hipError_t launch_increment(const OptPropsArgs &a, hipStream_t s);
 // forward: the forward-scattering fraction f per cell, or null: f = g*g
 hipError_t launch_delta_scale(size_t n, const double *tau, const double *ssa, const double *g, const double *forward, double *tau_out,
                               double *ssa_out, double *g_out, int f32, hipStream_t s);
+
+// McICA cloud mask (kernels_cloud_sampling.hip; the definition is in include/ecckd_hip.h, ecckd_cloud_mask_sample):
+// cloud_frac (ncol,nlay), overlap_param (ncol,nlay-1; exp_ran only), mask (ncol,nlay); 1 <= ngpt <= 64
+hipError_t launch_cloud_mask_sample(int ncol, int nlay, int ngpt, int exp_ran, const double *cloud_frac, const double *overlap_param,
+                                    unsigned long long seed, long long col0, unsigned long long *mask, hipStream_t s);
 
 // Spectral-output solvers (kernels_rte_gpt.hip): RTE-RRTMGP's kernel-level interfaces.  LW uses tau, lay_source,
 // lev_source_*, sfc_emis(ncol,ng), sfc_src(ncol,ng), inc_flux(ncol,ng)|null, Ds/wts; SW uses tau, ssa, g, mu0(ncol),

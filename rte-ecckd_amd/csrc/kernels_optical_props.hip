@@ -25,26 +25,39 @@ constexpr int kOpBlock = 256;
 constexpr int kOpMaxBlocks = 8192;   // 32 blocks of 256 threads per CU (a full CU of waves four times over; not tuned)
 
 // OP1_2STR / OP2_2STR: which side carries ssa and g.  BYBAND: op2 lives on bands (OptPropsArgs::band_first).
-template <typename real, bool OP1_2STR, bool OP2_2STR, bool BYBAND>
-__global__ void __launch_bounds__(kOpBlock) increment_kernel(const OptPropsArgs a) {
+// MASKED (increment_masked_kernel; ecckd_increment_masked): where bit g of the cell's word a.mask(column, layer) is clear
+// the g-point is incremented as if tau2 were +0 there -- the same operations on a zero optical depth (what RTE-RRTMGP's
+// draw_samples followed by increment computes), so ssa2 / g2 are still read and multiplied.
+// The kernels (increment_kernel, increment_masked_kernel, below) are thin entries to this body.
+template <typename real, bool OP1_2STR, bool OP2_2STR, bool BYBAND, bool MASKED>
+__device__ __forceinline__ void increment_body(const OptPropsArgs &a) {
   const size_t n2 = (size_t)a.ncol * a.nlay;
   real *tau1 = reinterpret_cast<real *>(a.tau1), *ssa1 = reinterpret_cast<real *>(a.ssa1), *g1 = reinterpret_cast<real *>(a.g1);
   const real *tau2 = reinterpret_cast<const real *>(a.tau2), *ssa2 = reinterpret_cast<const real *>(a.ssa2),
              *g2 = reinterpret_cast<const real *>(a.g2);
   const int nouter = BYBAND ? a.nband : a.ng;
   for (size_t cell = (size_t)blockIdx.x * kOpBlock + threadIdx.x; cell < n2; cell += (size_t)gridDim.x * kOpBlock) {
+    [[maybe_unused]] unsigned long long word = 0ull;
+    if constexpr (MASKED) word = a.mask[cell];
     for (int b = 0; b < nouter; ++b) {
       const size_t q2 = cell + n2 * b;
-      const real t2 = tau2[q2];
+      const real t2_in = tau2[q2];
       real s2 = real(0), gg2 = real(0);
       if constexpr (OP2_2STR) { s2 = ssa2[q2]; if constexpr (OP1_2STR) gg2 = g2[q2]; }
       // what the band contributes to every one of its g-points
-      const real tabs2 = OP2_2STR ? t2 * (real(1) - s2) : t2;   // 1scl += 2str: absorption optical depth
-      const real tscat2 = t2 * s2;
-      const real tsg2 = tscat2 * gg2;
+      const real tabs2_in = OP2_2STR ? t2_in * (real(1) - s2) : t2_in;   // 1scl += 2str: absorption optical depth
+      const real tscat2_in = t2_in * s2;
+      const real tsg2_in = tscat2_in * gg2;
+      // MASKED: ... and to the g-points that do not see it: the same products of a zero optical depth
+      [[maybe_unused]] const real tabs2_0 = OP2_2STR ? real(0) * (real(1) - s2) : real(0);
+      [[maybe_unused]] const real tscat2_0 = real(0) * s2;
+      [[maybe_unused]] const real tsg2_0 = tscat2_0 * gg2;
       const int glo = BYBAND ? a.band_first[b] : b, ghi = BYBAND ? a.band_first[b + 1] : b + 1;
       for (int g = glo; g < ghi; ++g) {
         const size_t q = cell + n2 * g;
+        const bool seen = MASKED ? ((word >> g) & 1ull) != 0ull : true;
+        const real t2 = seen ? t2_in : real(0), tabs2 = seen ? tabs2_in : tabs2_0;
+        const real tscat2 = seen ? tscat2_in : tscat2_0, tsg2 = seen ? tsg2_in : tsg2_0;
         if constexpr (!OP1_2STR) {
           tau1[q] = tau1[q] + tabs2;
         } else if constexpr (!OP2_2STR) {
@@ -64,6 +77,15 @@ __global__ void __launch_bounds__(kOpBlock) increment_kernel(const OptPropsArgs 
       }
     }
   }
+}
+
+template <typename real, bool OP1_2STR, bool OP2_2STR, bool BYBAND>
+__global__ void __launch_bounds__(kOpBlock) increment_kernel(const OptPropsArgs a) {
+  increment_body<real, OP1_2STR, OP2_2STR, BYBAND, false>(a);
+}
+template <typename real, bool OP1_2STR, bool OP2_2STR, bool BYBAND>
+__global__ void __launch_bounds__(kOpBlock) increment_masked_kernel(const OptPropsArgs a) {
+  increment_body<real, OP1_2STR, OP2_2STR, BYBAND, true>(a);
 }
 
 template <typename real, bool FORWARD>
@@ -93,6 +115,12 @@ hipError_t launch_increment_t(const OptPropsArgs &a, hipStream_t s) {
   else if (!one) k = bb ? increment_kernel<real, false, true, true> : increment_kernel<real, false, true, false>;
   else if (!two) k = bb ? increment_kernel<real, true, false, true> : increment_kernel<real, true, false, false>;
   else k = bb ? increment_kernel<real, true, true, true> : increment_kernel<real, true, true, false>;
+  if (a.mask) {
+    if (!one && !two) k = bb ? increment_masked_kernel<real, false, false, true> : increment_masked_kernel<real, false, false, false>;
+    else if (!one) k = bb ? increment_masked_kernel<real, false, true, true> : increment_masked_kernel<real, false, true, false>;
+    else if (!two) k = bb ? increment_masked_kernel<real, true, false, true> : increment_masked_kernel<real, true, false, false>;
+    else k = bb ? increment_masked_kernel<real, true, true, true> : increment_masked_kernel<real, true, true, false>;
+  }
   hipLaunchKernelGGL(k, dim3(op_blocks((size_t)a.ncol * a.nlay)), dim3(kOpBlock), 0, s, a);
   return hipGetLastError();
 }
@@ -115,6 +143,7 @@ hipError_t launch_delta_scale_t(size_t n, const double *tau, const double *ssa, 
 
 hipError_t launch_increment(const OptPropsArgs &a, hipStream_t s) {
   if (a.ncol <= 0 || a.nlay <= 0 || a.ng <= 0) return hipSuccess;
+  if (a.mask && a.ng > 64) return hipErrorInvalidValue;
   return a.f32 ? launch_increment_t<float>(a, s) : launch_increment_t<double>(a, s);
 }
 

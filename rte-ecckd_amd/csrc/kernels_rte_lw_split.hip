@@ -90,10 +90,15 @@ __host__ __device__ constexpr int planck_stride(int ng) { return ng | 1; }   // 
 // (2: two-stream particles, increment_1scalar_by_2stream), the expressions of kernels_optical_props.hip operation by
 // operation.  The two g-points of a wave may sit in different bands, so the band offset is per lane; the band values ride
 // in prefetch slots next to ptau[] (one load per (layer, iteration) from planes that stay in L2).
-template <int SEG, int NW, int CW, bool SHARED, bool SER3, bool PLANCK, int SKY>
+// MASK (with SKY; rte_lw_split_mcica_kernel, ecckd_lw_fluxes_allsky_mcica): a.part_mask holds one 64-bit word per
+// (column, layer); where bit g is clear the cell uses part_tau = 0 in front of the expressions above -- one select per
+// cell.  The lane's g-point is fixed for an iteration, so a prefetch slot carries only the 32-bit half of the word that
+// holds it.
+template <int SEG, int NW, int CW, bool SHARED, bool SER3, bool PLANCK, int SKY, bool MASK = false>
 __device__ __forceinline__ void rte_lw_split_body(const RteLwArgs &a, const PlanckTab &pt, const double *tlay, const double *tlev,
                                                   const double *tsfc) {
   static_assert(SKY == 0 || PLANCK, "the all-sky form extends the Planck-recomputing solver");
+  static_assert(SKY != 0 || !MASK, "a cloud mask belongs to the all-sky form");
   constexpr int GW = 64 / CW;
   constexpr int NL = SEG * NW;
   constexpr int NG = split_groups(PLANCK);
@@ -144,6 +149,9 @@ __device__ __forceinline__ void rte_lw_split_body(const RteLwArgs &a, const Plan
     [[maybe_unused]] double ptl[PLANCK ? kSplitPF : 1], ptv[PLANCK ? kSplitPF : 1];   // PLANCK: tlay(l), tlev(far edge of l)
     [[maybe_unused]] double ppt[SKY ? kSplitPF : 1], pps[SKY == 2 ? kSplitPF : 1];   // SKY: part_tau(l), part_ssa(l) of the lane's band
     [[maybe_unused]] long qb = 0;      // SKY: offset of the lane's band plane
+    [[maybe_unused]] unsigned pmk[MASK ? kSplitPF : 1];   // MASK: the half of part_mask(column, l) that holds the lane's g-point
+    [[maybe_unused]] int mhalf = 0, mbit = 0;             // MASK: which half, and the bit inside it
+    [[maybe_unused]] const unsigned *mask32 = reinterpret_cast<const unsigned *>(a.part_mask);
     long qn = 0;
     const long qstep = (long)ncol * lstep;
     [[maybe_unused]] long q2 = 0;      // PLANCK: offset into tlay / tlev rows (no g dimension)
@@ -159,6 +167,7 @@ __device__ __forceinline__ void rte_lw_split_body(const RteLwArgs &a, const Plan
         // level at the near (upper, in walking order) edge of the first layer of the segment
         near_first = tlev[cc + (long)ncol * (lev0 + lstep * s0)];
         if (SKY) qb = (long)ncol * NL * a.gpt2band[gg];
+        if (MASK) mhalf = gg >> 5;
       } else if (SHARED) {
         near_first = __builtin_nontemporal_load(Bup + qn);
       }
@@ -170,6 +179,7 @@ __device__ __forceinline__ void rte_lw_split_body(const RteLwArgs &a, const Plan
         ptv[slot] = tlev[q2 + (a.top_at_1 ? (long)ncol : 0)];   // far edge of the layer: level index l+1 (top_at_1) or l
         if (SKY) ppt[slot] = a.part_tau[q2 + qb];
         if (SKY == 2) pps[slot] = a.part_ssa[q2 + qb];
+        if (MASK) pmk[slot] = mask32[2 * q2 + mhalf];
         q2 += qstep;
       } else {
         play_[slot] = __builtin_nontemporal_load(a.lay_source + qn);
@@ -190,6 +200,7 @@ __device__ __forceinline__ void rte_lw_split_body(const RteLwArgs &a, const Plan
       const bool gact = g < ng;
       const int gg = gact ? g : ng - 1;
       const double D = a.Ds[k];
+      if (MASK) mbit = gg & 31;   // (pair_start(it + 1), below, moves mhalf on while this iteration's slots are used up)
       const double wfac = gact ? 2. * pi * a.wts[k] : 0.;
 
       // ---------------- phase 1: this wave's SEG layers ----------------
@@ -199,8 +210,11 @@ __device__ __forceinline__ void rte_lw_split_body(const RteLwArgs &a, const Plan
 #pragma unroll
       for (int s = 0; s < SEG; ++s) {
         double tau = ptau[s % kSplitPF];
-        if (SKY == 1) tau = tau + ppt[s % kSplitPF];
-        if (SKY == 2) tau = tau + ppt[s % kSplitPF] * (1. - pps[s % kSplitPF]);
+        [[maybe_unused]] double tp = 0.;
+        if (SKY) tp = ppt[s % kSplitPF];
+        if (MASK) tp = (pmk[s % kSplitPF] >> mbit) & 1u ? tp : 0.;
+        if (SKY == 1) tau = tau + tp;
+        if (SKY == 2) tau = tau + tp * (1. - pps[s % kSplitPF]);
         double lay, bdn, bup;
         if (PLANCK) {
           lay = planck_at(pt, ptab, pstride, ptl[s % kSplitPF], gg, pi_f32, rpi_f32);
@@ -316,12 +330,21 @@ __global__ void __launch_bounds__(64 * NW * split_groups(true), WPS) rte_lw_spli
   rte_lw_split_body<SEG, NW, CW, false, SER3, true, TWOSTR ? 2 : 1>(a, pt, tlay, tlev, tsfc);
 }
 
-// SKY: 0 the clear-sky kernel, 1 / 2 the all-sky form with one- / two-stream particles (PLANCK only)
-template <int SEG, int NW, int CW, bool SHARED, bool SER3, bool PLANCK, int WPS = ECCKD_SPLIT_WAVES_PER_SIMD, int SKY = 0>
+// ... with a McICA cloud mask (RteLwArgs::part_mask), under its own name
+template <int SEG, int NW, int CW, bool SER3, bool TWOSTR, int WPS>
+__global__ void __launch_bounds__(64 * NW * split_groups(true), WPS) rte_lw_split_mcica_kernel(const RteLwArgs a, const PlanckTab pt,
+                                                                                              const double *tlay, const double *tlev,
+                                                                                              const double *tsfc) {
+  rte_lw_split_body<SEG, NW, CW, false, SER3, true, TWOSTR ? 2 : 1, true>(a, pt, tlay, tlev, tsfc);
+}
+
+// SKY: 0 the clear-sky kernel, 1 / 2 the all-sky form with one- / two-stream particles (PLANCK only); MASK: with a.part_mask
+template <int SEG, int NW, int CW, bool SHARED, bool SER3, bool PLANCK, int WPS = ECCKD_SPLIT_WAVES_PER_SIMD, int SKY = 0, bool MASK = false>
 hipError_t launch_split(const RteLwArgs &a, const PlanckTab &pt, const double *tlay, const double *tlev, const double *tsfc,
                         hipStream_t s) {
   void (*k)(const RteLwArgs, const PlanckTab, const double *, const double *, const double *);
-  if constexpr (SKY != 0) k = rte_lw_split_allsky_kernel<SEG, NW, CW, SER3, SKY == 2, WPS>;
+  if constexpr (SKY != 0 && MASK) k = rte_lw_split_mcica_kernel<SEG, NW, CW, SER3, SKY == 2, WPS>;
+  else if constexpr (SKY != 0) k = rte_lw_split_allsky_kernel<SEG, NW, CW, SER3, SKY == 2, WPS>;
   else k = rte_lw_split_kernel<SEG, NW, CW, SHARED, SER3, PLANCK, WPS>;
   constexpr int NG = split_groups(PLANCK);
   const size_t lds = sizeof(double) * (NG * (2 * (size_t)(SEG * NW + 1) * CW + 2 * NW * 3 * 64) +
@@ -356,6 +379,11 @@ static hipError_t launch_seg(const RteLwArgs &a, const PlanckTab &pt, const doub
   // The Planck-recomputing form needs 244 VGPRs: 15 layers per wave, two waves per SIMD (three spill 25-54 registers)
   if constexpr (PLANCK) {
     // all-sky (a.part_tau): the band planes ride in prefetch slots; still two waves per SIMD without a spill
+    if (a.part_tau && a.part_mask) {   // McICA: 249 / 241 VGPRs, no spill
+      if (a.ng > 64) return hipErrorInvalidValue;
+      if (a.part_1scl || !a.part_ssa) return launch_split<15, 4, 32, SHARED, SER3, PLANCK, 2, 1, true>(a, pt, tlay, tlev, tsfc, s);
+      return launch_split<15, 4, 32, SHARED, SER3, PLANCK, 2, 2, true>(a, pt, tlay, tlev, tsfc, s);
+    }
     if (a.part_tau) {
       if (a.part_1scl || !a.part_ssa) return launch_split<15, 4, 32, SHARED, SER3, PLANCK, 2, 1>(a, pt, tlay, tlev, tsfc, s);
       return launch_split<15, 4, 32, SHARED, SER3, PLANCK, 2, 2>(a, pt, tlay, tlev, tsfc, s);

@@ -81,11 +81,15 @@ __device__ __forceinline__ void acc_add(double *p, double v, bool owner) {
 // with op1 = (tau, moles*ray/tau, 0): no per-g-point ssa or g exists in memory.  A lane walks all layers of one g-point before the
 // next, so the triple cannot stay in registers across the g-points of a band as it could in a layer-resident solver: it is
 // requested per (layer, g-point), three band-plane loads beside the layer's tau and its two pressures.
-// The kernels (rte_sw_kernel and rte_sw_allsky_kernel, below) are thin entries to this body.
-template <typename real> struct SwPart { real t, s, g; };
-template <typename real, int CW, bool FAST, bool CLAMP, bool DERIVE, bool ALLSKY = false>
+// MASK (with ALLSKY; ecckd_sw_fluxes_allsky_mcica): the 32-bit half of the layer's cloud-mask word (RteSwArgs::part_mask,
+// one 64-bit word per (column, layer)) that holds the lane's g-point rides with the triple; where the bit is clear the
+// cell uses a particulate optical depth of 0 in front of the same expressions.
+// The kernels (rte_sw_kernel, rte_sw_allsky_kernel and rte_sw_mcica_kernel, below) are thin entries to this body.
+template <typename real> struct SwPart { real t, s, g; unsigned m; };
+template <typename real, int CW, bool FAST, bool CLAMP, bool DERIVE, bool ALLSKY = false, bool MASK = false>
 __device__ __forceinline__ void rte_sw_body(const RteSwArgs &a) {
   static_assert(DERIVE || !ALLSKY, "the all-sky form extends the fused (DERIVE) form");
+  static_assert(ALLSKY || !MASK, "a cloud mask belongs to the all-sky form");
   constexpr int GW = 64 / CW;
   // (fp32 DERIVE: the correctly rounded fp32 division of ssa makes three layers in flight spill; two do not)
   // (ALLSKY: three more values per layer in flight; with three layers the 168 registers of three waves per SIMD spill)
@@ -147,6 +151,7 @@ __device__ __forceinline__ void rte_sw_body(const RteSwArgs &a) {
         if constexpr (ALLSKY) {
           const long qb = cc + (long)ncol * (lm + (long)nlay * band);
           pp.t = P(a.part_tau)[qb]; pp.s = P(a.part_ssa)[qb]; pp.g = P(a.part_g)[qb];
+          if constexpr (MASK) pp.m = reinterpret_cast<const unsigned *>(a.part_mask)[2 * (cc + (long)ncol * lm) + (gg >> 5)];
         }
         if constexpr (DERIVE) { x = P(a.plev)[cc + (long)ncol * lm]; y = P(a.plev)[cc + (long)ncol * (lm + 1)]; }
         else { x = P(a.ssa)[q]; y = P(a.g)[q]; }
@@ -156,8 +161,10 @@ __device__ __forceinline__ void rte_sw_body(const RteSwArgs &a) {
         if constexpr (ALLSKY) {
           constexpr real eps = op_eps<real>();
           const real tau_r = ((y - x) * gw) * ray;             // :313-316: the Rayleigh optical depth, tau*ssa of the gas optics
-          const real tsp = pp.t * pp.s;
-          const real ts = tau_r + tsp, tau12 = ctau + pp.t;    // increment_2stream_by_2stream
+          real tp = pp.t;
+          if constexpr (MASK) tp = (pp.m >> (gg & 31)) & 1u ? tp : real(0);
+          const real tsp = tp * pp.s;
+          const real ts = tau_r + tsp, tau12 = ctau + tp;      // increment_2stream_by_2stream
           const real cg = (tsp * pp.g) / (ts > eps ? ts : eps);
           const real cssa = ts / (tau12 > eps ? tau12 : eps);
           return two_stream<real, FAST, CLAMP, false>(tau12, cssa, cg, mu0, mu0_inv, k_floor);
@@ -298,6 +305,12 @@ __global__ void __launch_bounds__(64, ECCKD_SW_WAVES_PER_SIMD) rte_sw_allsky_ker
   rte_sw_body<double, CW, true, CLAMP, true, true>(a);
 }
 
+// ... with a McICA cloud mask (RteSwArgs::part_mask), under its own name
+template <int CW, bool CLAMP>
+__global__ void __launch_bounds__(64, ECCKD_SW_WAVES_PER_SIMD) rte_sw_mcica_kernel(const RteSwArgs a) {
+  rte_sw_body<double, CW, true, CLAMP, true, true, true>(a);
+}
+
 // Sums the per-group partial fluxes of the tail tiles in group order: the order in which a whole-tile wave adds the
 // same values to accumulators that start at +0, hence the same bits (see rte_lw_tail_reduce, kernels_rte_lw.hip).
 template <typename real>
@@ -407,7 +420,9 @@ hipError_t launch_rte_sw(const RteSwArgs &a, hipStream_t s) {
   constexpr int CW = ECCKD_SW_CW;
   // (the all-sky form exists in fp64 and the fast arithmetic mode only; ecckd_sw_fluxes_allsky refuses the rest with a message)
   if (a.allsky && (a.f32 || a.exact_division || !a.derive)) return hipErrorInvalidValue;
-  auto k = a.allsky ? (a.dir_clamp ? rte_sw_allsky_kernel<CW, true> : rte_sw_allsky_kernel<CW, false>)
+  if (a.allsky && a.part_mask && a.ng > 64) return hipErrorInvalidValue;
+  auto k = a.allsky && a.part_mask ? (a.dir_clamp ? rte_sw_mcica_kernel<CW, true> : rte_sw_mcica_kernel<CW, false>)
+           : a.allsky ? (a.dir_clamp ? rte_sw_allsky_kernel<CW, true> : rte_sw_allsky_kernel<CW, false>)
            : a.f32 ? (a.derive ? rte_sw_kernel_for<float, true>(a) : rte_sw_kernel_for<float, false>(a))
                  : (a.derive ? rte_sw_kernel_for<double, true>(a) : rte_sw_kernel_for<double, false>(a));
   if (!k) return hipErrorInvalidValue;

@@ -150,10 +150,15 @@ __device__ __forceinline__ float rcp_chain(float x) { return rcp<true>(x); }
 // g-point (RteSwArgs::part_*) stays in registers and is requested again only where the band changes (5 times in 27
 // g-points); the coefficients add it to the gas optics with RTE-RRTMGP's increment_2stream_by_2stream, op1 = (tau,
 // moles*ray/tau, 0), as rte_sw_body does.
-// The kernels (rte_sw_sys_kernel, rte_sw_sys_allsky_kernel, below) are thin entries to this body.
-template <typename real, bool FAST, bool CLAMP, bool DERIVE, bool FULL, bool ALLSKY = false>
+// MASK (with ALLSKY; ecckd_sw_fluxes_allsky_mcica): RteSwArgs::part_mask holds one 64-bit word per (column, layer); where
+// bit g is clear the cell uses a particulate optical depth of 0 in front of the same expressions.  The 32-bit half of the
+// word that holds the g-point is requested per g-point next to ptau (one dword per layer, from words that stay in L2), so
+// nothing about the mask lives across g-points; the g-point is wave-uniform, so the test is one v_and and a select.
+// The kernels (rte_sw_sys_kernel, rte_sw_sys_allsky_kernel, rte_sw_sys_mcica_kernel, below) are thin entries to this body.
+template <typename real, bool FAST, bool CLAMP, bool DERIVE, bool FULL, bool ALLSKY = false, bool MASK = false>
 __device__ __forceinline__ void rte_sw_sys_body(const RteSwArgs &a) {
   static_assert(DERIVE || !ALLSKY, "the all-sky form extends the fused (DERIVE) form");
+  static_assert(ALLSKY || !MASK, "a cloud mask belongs to the all-sky form");
   constexpr int LPW = kSysLPW, NW = kSysWaves;
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
   const int lane = threadIdx.x & 63;
@@ -240,6 +245,7 @@ __device__ __forceinline__ void rte_sw_sys_body(const RteSwArgs &a) {
     auto at = [&](const real *row) -> real { return *reinterpret_cast<greal_t *>((gcchar_t *)row + co); };
     real ptau[LPW], pssa[LPW], pg[LPW], pb0 = real(0), pb1 = real(0), ptoa = real(0);
     real ppt[LPW], pps[LPW], ppg[LPW];   // ALLSKY: particulate tau, ssa, g of the wave's layers on the current band
+    [[maybe_unused]] unsigned pmk[MASK ? LPW : 1];   // MASK: the half of the layers' mask words that holds the g-point of ptau
     // boundary values of the column at one g-point: surface albedos (bottom wave), incoming beam (top wave).  Each is
     // requested for g + 1 right after the sweep of g has read it -- NOT together with the optical properties, which the
     // parking waves request a g-point further ahead.
@@ -259,6 +265,11 @@ __device__ __forceinline__ void rte_sw_sys_body(const RteSwArgs &a) {
           const long row = (long)ncol * ((lay0 + lstep * (s0 + l)) + (long)nlay * g);
           ptau[l] = at(P(a.tau) + row);
           if (!DERIVE) { pssa[l] = at(P(a.ssa) + row); pg[l] = at(P(a.g) + row); }
+          if constexpr (MASK) {
+            typedef __attribute__((address_space(1))) const unsigned guint_t;
+            const unsigned *mrow = reinterpret_cast<const unsigned *>(a.part_mask + (long)ncol * (lay0 + lstep * (s0 + l))) + (g >> 5);
+            pmk[l] = *reinterpret_cast<guint_t *>((gcchar_t *)mrow + (unsigned)cc * 8u);
+          }
         }
       }
       if constexpr (ALLSKY) {
@@ -290,8 +301,10 @@ __device__ __forceinline__ void rte_sw_sys_body(const RteSwArgs &a) {
           real cssa, cg;
           if constexpr (ALLSKY) {
             constexpr real eps = op_eps<real>();
-            const real tsp = ppt[l] * pps[l];
-            const real tsc = moles[l] * ray + tsp, tau12 = ptau[l] + ppt[l];   // increment_2stream_by_2stream
+            real tp = ppt[l];
+            if constexpr (MASK) tp = (pmk[l] >> (g & 31)) & 1u ? tp : real(0);
+            const real tsp = tp * pps[l];
+            const real tsc = moles[l] * ray + tsp, tau12 = ptau[l] + tp;   // increment_2stream_by_2stream
             cg = (tsp * ppg[l]) / (tsc > eps ? tsc : eps);
             cssa = tsc / (tau12 > eps ? tau12 : eps);
             put(l, two_stream<real, FAST, CLAMP, false>(tau12, cssa, cg, mu0, mu0_inv, k_floor));
@@ -514,6 +527,12 @@ __global__ void __launch_bounds__(64 * kSysWaves) rte_sw_sys_allsky_kernel(const
   rte_sw_sys_body<double, true, CLAMP, true, FULL, true>(a);
 }
 
+// ... with a McICA cloud mask (RteSwArgs::part_mask), under its own name
+template <bool CLAMP, bool FULL>
+__global__ void __launch_bounds__(64 * kSysWaves) rte_sw_sys_mcica_kernel(const RteSwArgs a) {
+  rte_sw_sys_body<double, true, CLAMP, true, FULL, true, true>(a);
+}
+
 // LDS of a block: control words and band map (384 B), hand-off slots, accumulators (up, dn and, if asked for, dir), and
 // behind them the parking areas: as many of the lower waves as fit keep the coefficients of the next g-point there.
 size_t sys_lds_base(int nlay, int f32, bool with_dir) {
@@ -528,6 +547,10 @@ hipError_t launch_sys2(RteSwArgs a, long blocks, hipStream_t s) {
   if (a.allsky) {   // (fp64, fast arithmetic mode, DERIVE: ecckd_sw_fluxes_allsky refuses the rest with a message)
     if (a.f32 || a.exact_division || !a.derive) return hipErrorInvalidValue;
     k = a.dir_clamp ? rte_sw_sys_allsky_kernel<true, FULL> : rte_sw_sys_allsky_kernel<false, FULL>;
+    if (a.part_mask) {
+      if (a.ng > 64) return hipErrorInvalidValue;
+      k = a.dir_clamp ? rte_sw_sys_mcica_kernel<true, FULL> : rte_sw_sys_mcica_kernel<false, FULL>;
+    }
   }
   const size_t base = (sys_lds_base(a.nlay, a.f32, a.flux_dir != nullptr) + 15) & ~(size_t)15;
   if (base > (size_t)kLdsBudget) return hipErrorInvalidValue;

@@ -2,7 +2,7 @@
 ! example/rfmip-rad-irf/ecckd_rfmip_lw.F90:107-136 and ecckd_rfmip_sw.F90:112-162: load the ecCKD
 ! file, then per column block gas_optics() followed by rte_lw()/rte_sw(), fluxes out.
 !
-!   ecckd_driver lw|sw  <ecckd_file.nc>  <input.bin>  <output.bin>  [block_size] [n_quad_angles] [device_resident 0|1] [repeats] [byband 0|1] [fused 0|1] [particles.bin]
+!   ecckd_driver lw|sw  <ecckd_file.nc>  <input.bin>  <output.bin>  [block_size] [n_quad_angles] [device_resident 0|1] [repeats] [byband 0|1] [fused 0|1] [particles.bin] [cloudfrac.bin]
 !
 ! device_resident = 1: optical_props / source are the device twins of mo_ecckd_device (tau and the sources stay in
 ! HBM between gas_optics and the solver; ECCKD_MIXED memory space of the C ABI).
@@ -14,6 +14,10 @@
 !            Little-endian: int32 nband, has_ssa_g, delta_scale; then float64 tau(ncol,nlay,nband) and, if has_ssa_g /= 0,
 !            ssa and g of the same shape (the longwave ignores g and delta_scale; without ssa the particles are one-stream,
 !            longwave only).
+! cloudfrac.bin (needs particles.bin): McICA -- per block, ecckd%sample_cloud_mask(...) with col0 = the block's 0-based
+!            column offset, and the mask goes to the all-sky call (cloud_mask=).  Little-endian: int32 overlap (0 maximum-
+!            random, 1 exponential-random), int64 seed, float64 cloud_frac(ncol,nlay) and, for overlap 1,
+!            overlap_param(ncol,nlay-1).
 ! byband = 1: fluxes go through ty_fluxes_byband (per-band arrays; their sum over bands must reproduce the broadband
 ! fluxes, which are what output.bin holds either way).
 !
@@ -23,8 +27,8 @@
 ! vmr(ncol,nlay).  output.bin: flux_up(ncol,nlay+1), flux_dn(ncol,nlay+1).
 ! (The RFMIP netCDF files the reference drivers read are an FTP download and not available here.)
 program ecckd_driver
-  use, intrinsic :: iso_fortran_env, only: error_unit, int32
-  use gas_optics_ecckd, only: ty_gas_optics_ecckd
+  use, intrinsic :: iso_fortran_env, only: error_unit, int32, int64
+  use gas_optics_ecckd, only: ty_gas_optics_ecckd, ECCKD_OVERLAP_EXP_RAN
   use mo_fluxes, only: ty_fluxes_broadband
   use mo_fluxes_byband, only: ty_fluxes_byband
   use mo_gas_concentrations, only: ty_gas_concs
@@ -51,6 +55,12 @@ program ecckd_driver
   real(wp), dimension(:,:), allocatable :: sfc_spec, sfc_spec2, toa
   character(len=512) :: part_path
   logical :: allsky = .false.
+  character(len=512) :: frac_path
+  logical :: mcica = .false.
+  integer(int32) :: overlap
+  integer(int64) :: seed
+  real(wp), dimension(:,:), allocatable :: cloud_frac, overlap_param
+  integer(int64), dimension(:,:), allocatable :: mask_b   ! the block's mask; unallocated (= absent) without cloudfrac.bin
   integer(int32) :: nband_p, has_ssa_g, delta_flag
   real(wp), dimension(:,:,:), allocatable :: tau_p, ssa_p, g_p
   type(ty_gas_optics_ecckd) :: ecckd
@@ -112,6 +122,15 @@ program ecckd_driver
     call get_command_argument(11, part_path)
     allsky = len_trim(part_path) > 0
   end if
+  if (command_argument_count() >= 12) then
+    call get_command_argument(12, frac_path)
+    mcica = len_trim(frac_path) > 0
+  end if
+  if (mcica .and. .not. allsky) then
+    write(error_unit, "(a)") " ecckd_driver: a cloud-fraction file needs a particle file (particles.bin)"
+    call usage()
+    stop 1
+  end if
   if (allsky .and. fused == 0) then
     write(error_unit, "(a)") " ecckd_driver: a particle file needs fused = 1 (lw_fluxes_allsky / sw_fluxes_allsky)"
     call usage()
@@ -161,6 +180,17 @@ program ecckd_driver
     end if
     close(u)
   end if
+  if (mcica) then
+    open(newunit=u, file=trim(frac_path), access="stream", form="unformatted", status="old")
+    read(u) overlap, seed
+    allocate(cloud_frac(ncol, nlay))
+    read(u) cloud_frac
+    if (overlap == ECCKD_OVERLAP_EXP_RAN) then
+      allocate(overlap_param(ncol, max(nlay - 1, 0)))
+      read(u) overlap_param
+    end if
+    close(u)
+  end if
   if (block_size <= 0) block_size = ncol
 
   call stop_on_err(ecckd%load(trim(ecckd_path)))
@@ -207,15 +237,25 @@ program ecckd_driver
         sfc_spec(ibnd, i) = bc1(c0 + i - 1)
       end do
     end do
+    if (mcica) then   ! the mask of a column depends on its global index, not on the blocking: col0 = c0 - 1
+      if (allocated(mask_b)) deallocate(mask_b)
+      allocate(mask_b(nc, nlay))
+      if (overlap == ECCKD_OVERLAP_EXP_RAN) then
+        call stop_on_err(ecckd%sample_cloud_mask(cloud_frac(c0:c1, :), int(overlap), seed, int(c0 - 1, int64), mask_b, &
+                                                 overlap_param=overlap_param(c0:c1, :)))
+      else
+        call stop_on_err(ecckd%sample_cloud_mask(cloud_frac(c0:c1, :), int(overlap), seed, int(c0 - 1, int64), mask_b))
+      end if
+    end if
     if (lw .and. allsky) then
       if (has_ssa_g /= 0) then
         call stop_on_err(ecckd%lw_fluxes_allsky(plev(c0:c1, :), tlay(c0:c1, :), tsfc(c0:c1), tlev(c0:c1, :), gas_concs(b), &
                                                 top_at_1, sfc_spec, tau_p(c0:c1, :, :), flux_up(c0:c1, :), flux_dn(c0:c1, :), &
-                                                ssa_p=ssa_p(c0:c1, :, :), n_gauss_angles=n_quad_angles))
+                                                ssa_p=ssa_p(c0:c1, :, :), n_gauss_angles=n_quad_angles, cloud_mask=mask_b))
       else
         call stop_on_err(ecckd%lw_fluxes_allsky(plev(c0:c1, :), tlay(c0:c1, :), tsfc(c0:c1), tlev(c0:c1, :), gas_concs(b), &
                                                 top_at_1, sfc_spec, tau_p(c0:c1, :, :), flux_up(c0:c1, :), flux_dn(c0:c1, :), &
-                                                n_gauss_angles=n_quad_angles))
+                                                n_gauss_angles=n_quad_angles, cloud_mask=mask_b))
       end if
     else if (lw .and. fused /= 0) then
       call stop_on_err(ecckd%lw_fluxes(plev(c0:c1, :), tlay(c0:c1, :), tsfc(c0:c1), tlev(c0:c1, :), gas_concs(b), top_at_1, &
@@ -241,7 +281,7 @@ program ecckd_driver
       if (allsky) then
         call stop_on_err(ecckd%sw_fluxes_allsky(plev(c0:c1, :), tlay(c0:c1, :), gas_concs(b), top_at_1, bc1(c0:c1), sfc_spec, &
                                                 sfc_spec2, tau_p(c0:c1, :, :), ssa_p(c0:c1, :, :), g_p(c0:c1, :, :), &
-                                                delta_flag /= 0, flux_up(c0:c1, :), flux_dn(c0:c1, :)))
+                                                delta_flag /= 0, flux_up(c0:c1, :), flux_dn(c0:c1, :), cloud_mask=mask_b))
       else
       call stop_on_err(ecckd%sw_fluxes(plev(c0:c1, :), tlay(c0:c1, :), gas_concs(b), top_at_1, bc1(c0:c1), sfc_spec, sfc_spec2, &
                                        flux_up(c0:c1, :), flux_dn(c0:c1, :)))
@@ -282,7 +322,7 @@ program ecckd_driver
 contains
   subroutine usage()
     write(error_unit, "(a)") " usage: ecckd_driver lw|sw ecckd_file input.bin output.bin [block_size] [n_quad_angles]"
-    write(error_unit, "(a)") "        [device_resident 0|1] [repeats] [byband 0|1] [fused 0|1] [particles.bin]"
+    write(error_unit, "(a)") "        [device_resident 0|1] [repeats] [byband 0|1] [fused 0|1] [particles.bin] [cloudfrac.bin]"
   end subroutine usage
 
   subroutine stop_on_err(msg)                                ! mo_simple_netcdf.F90:331-339

@@ -56,6 +56,7 @@ module gas_optics_ecckd
     procedure, public :: sw_fluxes          !< extension: gas_optics + rte_sw in one call (fused shortwave path)
     procedure, public :: lw_fluxes_allsky   !< extension: lw_fluxes with particulate optics on the model's bands
     procedure, public :: sw_fluxes_allsky   !< extension: sw_fluxes with particulate optics on the model's bands
+    procedure, public :: sample_cloud_mask  !< extension: McICA cloud mask from cloud fractions (ecckd_cloud_mask_sample)
   end type ty_gas_optics_ecckd
 
   interface
@@ -232,7 +233,60 @@ module gas_optics_ecckd
       type(c_ptr), value :: stream
       integer(c_int) :: rc
     end function c_sw_fluxes_allsky
+    function c_lw_fluxes_allsky_mcica(model, ncol, nlay, plev, tlay, tsfc, tlev, ngas, gas_names, vmr, cs, ls, scalar, top_at_1, &
+                                      nmus, sfc_emis, inc_flux, nband_p, tau_p, ssa_p, cloud_mask, flux_up, flux_dn, memspace, &
+                                      stream) bind(C, name="ecckd_lw_fluxes_allsky_mcica") result(rc)
+      import c_ptr, c_int, c_double, c_char, c_long_long, c_int64_t
+      type(c_ptr), value :: model
+      integer(c_int), value :: ncol, nlay, ngas, top_at_1, nmus, nband_p, memspace
+      real(c_double), dimension(*), intent(in) :: plev, tlay, tsfc, tlev, sfc_emis, tau_p
+      character(kind=c_char), dimension(*), intent(in) :: gas_names
+      type(c_ptr), dimension(*), intent(in) :: vmr
+      integer(c_long_long), dimension(*), intent(in) :: cs, ls
+      real(c_double), dimension(*), intent(in) :: scalar
+      type(c_ptr), value :: inc_flux, ssa_p
+      integer(c_int64_t), dimension(*), intent(in) :: cloud_mask
+      real(c_double), dimension(*), intent(inout) :: flux_up, flux_dn
+      type(c_ptr), value :: stream
+      integer(c_int) :: rc
+    end function c_lw_fluxes_allsky_mcica
+    function c_sw_fluxes_allsky_mcica(model, ncol, nlay, plev, tlay, ngas, gas_names, vmr, cs, ls, scalar, top_at_1, mu0, &
+                                      toa_scale, sfc_alb_dir, sfc_alb_dif, nband_p, tau_p, ssa_p, g_p, delta_scale, cloud_mask, &
+                                      flux_up, flux_dn, flux_dir, memspace, stream) &
+        bind(C, name="ecckd_sw_fluxes_allsky_mcica") result(rc)
+      import c_ptr, c_int, c_double, c_char, c_long_long, c_int64_t
+      type(c_ptr), value :: model
+      integer(c_int), value :: ncol, nlay, ngas, top_at_1, nband_p, delta_scale, memspace
+      real(c_double), dimension(*), intent(in) :: plev, tlay, mu0, sfc_alb_dir, sfc_alb_dif, tau_p, ssa_p, g_p
+      character(kind=c_char), dimension(*), intent(in) :: gas_names
+      type(c_ptr), dimension(*), intent(in) :: vmr
+      integer(c_long_long), dimension(*), intent(in) :: cs, ls
+      real(c_double), dimension(*), intent(in) :: scalar
+      type(c_ptr), value :: toa_scale, flux_dir
+      integer(c_int64_t), dimension(*), intent(in) :: cloud_mask
+      real(c_double), dimension(*), intent(inout) :: flux_up, flux_dn
+      type(c_ptr), value :: stream
+      integer(c_int) :: rc
+    end function c_sw_fluxes_allsky_mcica
+    function c_cloud_mask_sample(device, ncol, nlay, ngpt, overlap, cloud_frac, overlap_param, seed, col0, mask, memspace, &
+                                 stream) bind(C, name="ecckd_cloud_mask_sample") result(rc)
+      import c_ptr, c_int, c_double, c_int64_t
+      integer(c_int), value :: device, ncol, nlay, ngpt, overlap, memspace
+      real(c_double), dimension(*), intent(in) :: cloud_frac
+      type(c_ptr), value :: overlap_param
+      integer(c_int64_t), value :: seed, col0           ! (seed: the bits of the C unsigned 64-bit word)
+      integer(c_int64_t), dimension(*), intent(inout) :: mask
+      type(c_ptr), value :: stream
+      integer(c_int) :: rc
+    end function c_cloud_mask_sample
+    function c_model_device(model) bind(C, name="ecckd_model_get_device") result(dev)
+      import c_ptr, c_int
+      type(c_ptr), value :: model
+      integer(c_int) :: dev
+    end function c_model_device
   end interface
+
+  integer, parameter, public :: ECCKD_OVERLAP_MAX_RAN = 0, ECCKD_OVERLAP_EXP_RAN = 1
 
   public :: c_error_message, c_loc_3d, c_loc_2d
 
@@ -648,8 +702,10 @@ contains
   !! tau_gas + tau_p*(1 - ssa_p) with ssa_p [increment_1scalar_by_2stream, by band], tau_gas + tau_p without it
   !! [increment_1scalar_by_1scalar: one-stream particles].  Host arrays in, host fluxes out; the particulate arrays are
   !! never written.  flux_up / flux_dn are (ncol, nlay+1), sfc_emis (nband, ncol).
+  !! cloud_mask (ncol, nlay), from sample_cloud_mask (ecckd_lw_fluxes_allsky_mcica): a g-point whose bit is clear sees no
+  !! particles in that layer.
   function lw_fluxes_allsky(this, plev, tlay, tsfc, tlev, gas_desc, top_at_1, sfc_emis, tau_p, flux_up, flux_dn, ssa_p, &
-                            n_gauss_angles) result(error_msg)
+                            n_gauss_angles, cloud_mask) result(error_msg)
     class(ty_gas_optics_ecckd), intent(in) :: this
     real(wp), dimension(:,:), intent(in) :: plev, tlay, tlev
     real(wp), dimension(:), intent(in) :: tsfc
@@ -660,6 +716,7 @@ contains
     real(wp), dimension(:,:), intent(inout) :: flux_up, flux_dn
     real(wp), dimension(:,:,:), intent(in), optional :: ssa_p
     integer, intent(in), optional :: n_gauss_angles
+    integer(c_int64_t), dimension(:,:), intent(in), optional :: cloud_mask
     character(len=128) :: error_msg
     character(kind=c_char), dimension(:), allocatable :: names
     type(c_ptr), dimension(:), allocatable :: ptr
@@ -696,9 +753,20 @@ contains
     end if
     n = gas_desc%get_num_gases()
     allocate(up(ncol, nlay + 1), dn(ncol, nlay + 1))
+    if (present(cloud_mask)) then
+      if (size(cloud_mask, 1) /= ncol .or. size(cloud_mask, 2) /= nlay) then
+        error_msg = "lw_fluxes_allsky: cloud_mask inconsistently sized"
+        return
+      end if
+      rc = c_lw_fluxes_allsky_mcica(this%handle, int(ncol, c_int), int(nlay, c_int), plev, tlay, tsfc, tlev, int(n, c_int), names, &
+                                    ptr, cs, ls, scalar, merge(1_c_int, 0_c_int, top_at_1), int(nmus, c_int), sfc_emis, &
+                                    c_null_ptr, int(size(tau_p, 3), c_int), tau_p, ssa_c, cloud_mask, up, dn, ECCKD_HOST, &
+                                    c_null_ptr)
+    else
     rc = c_lw_fluxes_allsky(this%handle, int(ncol, c_int), int(nlay, c_int), plev, tlay, tsfc, tlev, int(n, c_int), names, ptr, &
                             cs, ls, scalar, merge(1_c_int, 0_c_int, top_at_1), int(nmus, c_int), sfc_emis, c_null_ptr, &
                             int(size(tau_p, 3), c_int), tau_p, ssa_c, up, dn, ECCKD_HOST, c_null_ptr)
+    end if
     if (rc /= 0) then
       error_msg = c_error_message()
       return
@@ -711,8 +779,10 @@ contains
   !! (ncol, nlay, nband), added to the gas optics inside the solver (ecckd_sw_fluxes_allsky) [increment_2stream_by_2stream];
   !! delta_scale: the library first delta-scales a copy of them with f = g*g.  Host arrays in, host fluxes out; the
   !! particulate arrays are never written.  The other arguments are those of sw_fluxes.
+  !! cloud_mask (ncol, nlay), from sample_cloud_mask (ecckd_sw_fluxes_allsky_mcica): a g-point whose bit is clear sees no
+  !! particles in that layer.
   function sw_fluxes_allsky(this, plev, tlay, gas_desc, top_at_1, mu0, sfc_alb_dir, sfc_alb_dif, tau_p, ssa_p, g_p, delta_scale, &
-                            flux_up, flux_dn, flux_dir, toa_scale) result(error_msg)
+                            flux_up, flux_dn, flux_dir, toa_scale, cloud_mask) result(error_msg)
     class(ty_gas_optics_ecckd), intent(in) :: this
     real(wp), dimension(:,:), intent(in) :: plev, tlay
     type(ty_gas_concs), intent(in) :: gas_desc
@@ -724,6 +794,7 @@ contains
     real(wp), dimension(:,:), intent(inout) :: flux_up, flux_dn
     real(wp), dimension(:,:), intent(inout), optional :: flux_dir
     real(wp), dimension(:), intent(in), optional, target :: toa_scale
+    integer(c_int64_t), dimension(:,:), intent(in), optional :: cloud_mask
     character(len=128) :: error_msg
     character(kind=c_char), dimension(:), allocatable :: names
     type(c_ptr), dimension(:), allocatable :: ptr
@@ -761,10 +832,21 @@ contains
       allocate(dir(ncol, nlay + 1))
       dir_p = c_loc(dir(1, 1))
     end if
+    if (present(cloud_mask)) then
+      if (size(cloud_mask, 1) /= ncol .or. size(cloud_mask, 2) /= nlay) then
+        error_msg = "sw_fluxes_allsky: cloud_mask inconsistently sized"
+        return
+      end if
+      rc = c_sw_fluxes_allsky_mcica(this%handle, int(ncol, c_int), int(nlay, c_int), plev, tlay, int(n, c_int), names, ptr, cs, &
+                                    ls, scalar, merge(1_c_int, 0_c_int, top_at_1), mu0, scale_p, sfc_alb_dir, sfc_alb_dif, &
+                                    int(size(tau_p, 3), c_int), tau_p, ssa_p, g_p, merge(1_c_int, 0_c_int, delta_scale), &
+                                    cloud_mask, up, dn, dir_p, ECCKD_HOST, c_null_ptr)
+    else
     rc = c_sw_fluxes_allsky(this%handle, int(ncol, c_int), int(nlay, c_int), plev, tlay, int(n, c_int), names, ptr, cs, ls, &
                             scalar, merge(1_c_int, 0_c_int, top_at_1), mu0, scale_p, sfc_alb_dir, sfc_alb_dif, &
                             int(size(tau_p, 3), c_int), tau_p, ssa_p, g_p, merge(1_c_int, 0_c_int, delta_scale), up, dn, dir_p, &
                             ECCKD_HOST, c_null_ptr)
+    end if
     if (rc /= 0) then
       error_msg = c_error_message()
       return
@@ -773,6 +855,51 @@ contains
     flux_dn = dn
     if (present(flux_dir)) flux_dir = dir
   end function sw_fluxes_allsky
+
+  !> Extension: the McICA cloud mask of ecckd_cloud_mask_sample (the definition is in include/ecckd_hip.h; parity with
+  !! RTE-RRTMGP's mo_cloud_sampling is unpinned) for this model's g-points: cloud_frac (ncol, nlay) in the layer order of
+  !! tlay, overlap ECCKD_OVERLAP_MAX_RAN or ECCKD_OVERLAP_EXP_RAN (then overlap_param (ncol, nlay-1)), col0 the global
+  !! 0-based index of the first column (a host that works in blocks passes its block offset, so that the mask of a column
+  !! does not depend on the blocking).  cloud_mask (ncol, nlay): bit g-1 of a word set = g-point g sees the layer's cloud.
+  function sample_cloud_mask(this, cloud_frac, overlap, seed, col0, cloud_mask, overlap_param) result(error_msg)
+    class(ty_gas_optics_ecckd), intent(in) :: this
+    real(wp), dimension(:,:), intent(in) :: cloud_frac
+    integer, intent(in) :: overlap
+    integer(c_int64_t), intent(in) :: seed, col0
+    integer(c_int64_t), dimension(:,:), intent(inout) :: cloud_mask
+    real(wp), dimension(:,:), intent(in), optional :: overlap_param
+    character(len=128) :: error_msg
+    real(wp), dimension(:,:), allocatable, target :: alpha
+    integer(c_int64_t), dimension(:,:), allocatable :: words
+    type(c_ptr) :: alpha_p
+    integer :: ncol, nlay
+    integer(c_int) :: rc
+    error_msg = ""
+    ncol = size(cloud_frac, 1)
+    nlay = size(cloud_frac, 2)
+    if (size(cloud_mask, 1) /= ncol .or. size(cloud_mask, 2) /= nlay) then
+      error_msg = "sample_cloud_mask: cloud_mask inconsistently sized"
+      return
+    end if
+    alpha_p = c_null_ptr
+    if (present(overlap_param)) then
+      if (size(overlap_param, 1) /= ncol .or. size(overlap_param, 2) /= nlay - 1) then
+        error_msg = "sample_cloud_mask: overlap_param inconsistently sized"
+        return
+      end if
+      allocate(alpha(ncol, max(nlay - 1, 1)))
+      alpha(:, 1:nlay - 1) = overlap_param
+      alpha_p = c_loc(alpha(1, 1))
+    end if
+    allocate(words(ncol, nlay))
+    rc = c_cloud_mask_sample(c_model_device(this%handle), int(ncol, c_int), int(nlay, c_int), int(this%get_ngpt(), c_int), &
+                             int(overlap, c_int), cloud_frac, alpha_p, seed, col0, words, ECCKD_HOST, c_null_ptr)
+    if (rc /= 0) then
+      error_msg = c_error_message()
+      return
+    end if
+    cloud_mask = words
+  end function sample_cloud_mask
 
   function c_loc_3d(a) result(p)
     real(wp), dimension(:,:,:), intent(in), target, contiguous :: a

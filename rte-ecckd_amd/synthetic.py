@@ -95,6 +95,18 @@ def clouds(c0, ncol, nlay, nband):
                 cloudy=np.ascontiguousarray((kind < 0.6)[0, 0]))
 
 
+F_CLD_FRAC = 19
+
+
+def cloud_fraction(c0, ncol, nlay):
+    """Layer cloud fractions ``(nlay, ncol)`` for columns ``c0 .. c0+ncol-1``, top layer first: in (0, 1] on exactly the
+    layers where ``clouds`` has ``tau`` > 0, 0 elsewhere (input of ``sample_cloud_mask``)."""
+    c = np.arange(c0, c0 + ncol, dtype=np.uint64)[None, :]
+    jm = np.arange(1, nlay + 1, dtype=np.uint64)[:, None]
+    has_cloud = clouds(c0, ncol, nlay, 1)["tau"][0] > 0.0
+    return np.ascontiguousarray(np.where(has_cloud, 1.0 - uniform(c, F_CLD_FRAC, jm), 0.0))
+
+
 def gas_items(cols):
     """[(name, array, col_stride, lay_stride)] in GAS_ORDER for oracle-style consumers: full
     arrays are (nlay,ncol) -> strides (1,ncol); per-column arrays (1,0); scalars (0,0)."""
