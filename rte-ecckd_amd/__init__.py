@@ -189,6 +189,13 @@ def lib():
         L.ecckd_sw_fluxes_allsky_mcica.argtypes = ([C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 2 + [C.c_int, C.c_char_p] +
                                                    [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 3 +
                                                    [C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_void_p])
+    if hasattr(L, "ecckd_lw_fluxes_clear_allsky"):   # (an older build lacks them: tools/bench_both_skies.py --parent-lib)
+        L.ecckd_lw_fluxes_clear_allsky.argtypes = ([C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_char_p] +
+                                                   [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int] +
+                                                   [C.c_void_p] * 7 + [C.c_int, C.c_void_p])
+        L.ecckd_sw_fluxes_clear_allsky.argtypes = ([C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 2 + [C.c_int, C.c_char_p] +
+                                                   [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 3 +
+                                                   [C.c_int] + [C.c_void_p] * 7 + [C.c_int, C.c_void_p])
     _lib = L
     return L
 
@@ -866,6 +873,69 @@ class GasOpticsEcckd:
             int(n_gauss_angles), _ptr(sfc_emis, (ncol, self.get_nband()), "sfc_emis"), _ptr(inc_flux, (ng, ncol), "inc_flux"),
             nbp, *part, _ptr(fluxes.flux_up, (nlay + 1, ncol), "flux_up"), _ptr(fluxes.flux_dn, (nlay + 1, ncol), "flux_dn"),
             space, _stream(space))
+        return last_error() if rc else ""
+
+    def lw_fluxes_clear_allsky(self, plev, tlay, tsfc, tlev, gas_desc, top_at_1, sfc_emis, particles, fluxes, fluxes_clear,
+                               n_gauss_angles=1, inc_flux=None, cloud_mask=None):
+        """``ecckd_lw_fluxes_clear_allsky``: one gas-optics pass, then both skies -- ``fluxes_clear`` receives what
+        ``lw_fluxes`` writes and ``fluxes`` what ``lw_fluxes_allsky(..., cloud_mask=cloud_mask)`` writes, bit for bit.
+        ``particles`` and ``cloud_mask`` as for ``lw_fluxes_allsky``; neither is written.  float64, fast arithmetic mode;
+        numpy or device tensors.  Returns the error message ('' = success)."""
+        nlay, ncol = tlay.shape
+        ng = self.get_ngpt()
+        ssa = getattr(particles, "ssa", None)
+        try:
+            space = _space_of([plev, tlay, tsfc, tlev, sfc_emis, inc_flux, fluxes.flux_up, fluxes.flux_dn, fluxes_clear.flux_up,
+                               fluxes_clear.flux_dn, particles.tau, ssa])
+            n, names, ptrs, cs, ls, sc, keep = self._gas_args(gas_desc, ncol, nlay, space)
+            nbp = 0 if particles.tau is None else int(particles.tau.shape[0])
+            shp = (nbp, nlay, ncol)
+            part = (_ptr(particles.tau, shp, "particles.tau"), _ptr(ssa, shp, "particles.ssa"),
+                    None if cloud_mask is None else _mask_ptr(cloud_mask, nlay, ncol, space))
+            out = tuple(_ptr(a, (nlay + 1, ncol), what) for a, what in (
+                (fluxes.flux_up, "flux_up"), (fluxes.flux_dn, "flux_dn"), (fluxes_clear.flux_up, "flux_up_clear"),
+                (fluxes_clear.flux_dn, "flux_dn_clear")))
+        except KeyError as e:
+            return str(e.args[0])
+        except (TypeError, ValueError) as e:
+            return str(e)
+        rc = lib().ecckd_lw_fluxes_clear_allsky(
+            self._need(), ncol, nlay, _ptr(plev, (nlay + 1, ncol), "plev"), _ptr(tlay, (nlay, ncol), "tlay"),
+            _ptr(tsfc, (ncol,), "tsfc"), _ptr(tlev, (nlay + 1, ncol), "tlev"), n, names, ptrs, cs, ls, sc, int(bool(top_at_1)),
+            int(n_gauss_angles), _ptr(sfc_emis, (ncol, self.get_nband()), "sfc_emis"), _ptr(inc_flux, (ng, ncol), "inc_flux"),
+            nbp, *part, *out, space, _stream(space))
+        return last_error() if rc else ""
+
+    def sw_fluxes_clear_allsky(self, plev, tlay, gas_desc, top_at_1, mu0, sfc_alb_dir, sfc_alb_dif, particles, fluxes,
+                               fluxes_clear, delta_scale=True, toa_scale=None, cloud_mask=None):
+        """``ecckd_sw_fluxes_clear_allsky``: one gas-optics pass, then both skies -- ``fluxes_clear`` receives what
+        ``sw_fluxes`` writes and ``fluxes`` what ``sw_fluxes_allsky(..., cloud_mask=cloud_mask)`` writes, bit for bit.
+        ``flux_dn_dir`` of either may be None independently of the other.  float64, fast arithmetic mode; numpy or device
+        tensors.  Returns the error message ('' = success)."""
+        nlay, ncol = tlay.shape
+        nband = self.get_nband()
+        try:
+            space = _space_of([plev, tlay, mu0, toa_scale, sfc_alb_dir, sfc_alb_dif, fluxes.flux_up, fluxes.flux_dn,
+                               fluxes_clear.flux_up, fluxes_clear.flux_dn, particles.tau, particles.ssa, particles.g])
+            mp = None if cloud_mask is None else _mask_ptr(cloud_mask, nlay, ncol, space)
+            n, names, ptrs, cs, ls, sc, keep = self._gas_args(gas_desc, ncol, nlay, space)
+            nbp = int(particles.tau.shape[0])
+            shp = (nbp, nlay, ncol)
+            part = (_ptr(particles.tau, shp, "particles.tau"), _ptr(particles.ssa, shp, "particles.ssa"),
+                    _ptr(particles.g, shp, "particles.g"))
+            out = tuple(_ptr(a, (nlay + 1, ncol), what) for a, what in (
+                (fluxes.flux_up, "flux_up"), (fluxes.flux_dn, "flux_dn"), (fluxes.flux_dn_dir, "flux_dn_dir"),
+                (fluxes_clear.flux_up, "flux_up_clear"), (fluxes_clear.flux_dn, "flux_dn_clear"),
+                (fluxes_clear.flux_dn_dir, "flux_dn_dir_clear")))
+        except KeyError as e:
+            return str(e.args[0])
+        except (TypeError, ValueError) as e:
+            return str(e)
+        rc = lib().ecckd_sw_fluxes_clear_allsky(
+            self._need(), ncol, nlay, _ptr(plev, (nlay + 1, ncol), "plev"), _ptr(tlay, (nlay, ncol), "tlay"), n, names, ptrs,
+            cs, ls, sc, int(bool(top_at_1)), _ptr(mu0, (ncol,), "mu0"), _ptr(toa_scale, (ncol,), "toa_scale"),
+            _ptr(sfc_alb_dir, (ncol, nband), "sfc_alb_dir"), _ptr(sfc_alb_dif, (ncol, nband), "sfc_alb_dif"), nbp, *part,
+            int(bool(delta_scale)), mp, *out, space, _stream(space))
         return last_error() if rc else ""
 
     def gas_optics_ext(self, play, plev, tlay, gas_desc, optical_props, toa_src, col_dry=None):

@@ -244,6 +244,10 @@ struct SolverOptions {
   std::atomic<int> sw_tail_split{1};
   std::atomic<int> gas_slab_f32{2};   // fp64 gas optics over the float32 image of the tables in LDS (2: auto)
   std::atomic<int> sw_solver{0};   // 0 layer-systolic (kernels_rte_sw_sys.hip; up to 60 layers), 1 per-lane two-pass kernel
+  // ecckd_lw_fluxes_clear_allsky at 60 layers: 0 the clear-sky and the all-sky kernel one after the other, 1 the dual-sky
+  // kernel (rte_lw_split_both_kernel); same bits.  1: its min-max range lies below that of 0 at every 60-layer shape and
+  // configuration measured (profiles/both_skies.json)
+  std::atomic<int> lw_both_skies{1};
 };
 SolverOptions g_opt;
 
@@ -649,13 +653,17 @@ int ecckd_set_solver_option(const char *name, double value) {
     if (value != 0. && value != 1.) return fail("ecckd_set_solver_option: sw_solver must be 0 (layer-systolic) or 1 (two-pass per lane)");
     g_opt.sw_solver.store((int)value);
   }
+  else if (n == "lw_both_skies") {
+    if (value != 0. && value != 1.) return fail("ecckd_set_solver_option: lw_both_skies must be 0 (two launches) or 1 (dual-sky kernel)");
+    g_opt.lw_both_skies.store((int)value);
+  }
   else if (n == "gas_slab_f32") {
     if (value != 0. && value != 1. && value != 2.) return fail("ecckd_set_solver_option: gas_slab_f32 must be 0 (never), 1 (always) or 2 (auto)");
     g_opt.gas_slab_f32.store((int)value);
   }
   else return fail("ecckd_set_solver_option: unknown option '" + n + "' (lw_tau_thresh, lw_series_terms, "
                    "lw_inc_flux_isotropic, sw_k_floor, sw_dir_clamp, lw_solver, lw_split_seg, gas_merge_scalars, lw_tail_split, "
-                   "sw_tail_split, sw_solver, gas_slab_f32)");
+                   "sw_tail_split, sw_solver, gas_slab_f32, lw_both_skies)");
   return 0;
 }
 
@@ -674,6 +682,7 @@ int ecckd_get_solver_option(const char *name, double *value) {
   else if (n == "sw_tail_split") *value = g_opt.sw_tail_split.load();
   else if (n == "sw_solver") *value = g_opt.sw_solver.load();
   else if (n == "gas_slab_f32") *value = g_opt.gas_slab_f32.load();
+  else if (n == "lw_both_skies") *value = g_opt.lw_both_skies.load();
   else return fail("ecckd_get_solver_option: unknown option '" + n + "'");
   return 0;
 }
@@ -1667,12 +1676,16 @@ static const char kMaskTooWide[] = ": a cloud mask is one 64-bit word per (colum
 // mask: ecckd_lw_fluxes_allsky_mcica -- the cloud mask (ncol,nlay), in the memory space of the call, or null
 struct LwParticles { const double *tau, *ssa; const unsigned long long *mask = nullptr; };
 
+// ecckd_*_fluxes_clear_allsky: where the clear-sky fluxes go (dir: shortwave only, may be null), in the memory space of the call
+struct ClearFluxes { double *up, *dn, *dir; };
+
+// `both` (60-layer route with `pt` only): the dual-sky kernel, clear-sky fluxes to *both and all-sky fluxes to flux_up / flux_dn
 // `pt` (60-layer route only): the band planes the solver adds to tau as it reads it; the general route gets a tau that
 // launch_increment has incremented already
 static int rte_lw_fused_dev(const ecckd_model *m, int ncol, int nlay, int top_at_1, int n_gauss_angles, const double *tau,
                             const double *tlay, const double *tlev, const double *tsfc, const double *sfc_emis,
                             const double *inc_flux, double *flux_up, double *flux_dn, double *scratch, hipStream_t stream,
-                            const LwParticles *pt = nullptr) {
+                            const LwParticles *pt = nullptr, const ClearFluxes *both = nullptr, bool sources_in_scratch = false) {
   ecckd::RteLwArgs a{};
   if (fill_band_map(m->ng, m->nband, m->band2gpt.data(), a.gpt2band)) return 1;
   a.ncol = ncol; a.nlay = nlay; a.ng = m->ng; a.top_at_1 = top_at_1 ? 1 : 0;
@@ -1684,15 +1697,17 @@ static int rte_lw_fused_dev(const ecckd_model *m, int ncol, int nlay, int top_at
     if (pt) { a.part_tau = pt->tau; a.part_ssa = pt->ssa; a.part_1scl = pt->ssa ? 0 : 1; a.part_mask = pt->mask; }
     ProfScope prof("rte_lw_fused", stream);
     HIPCHK(ecckd::launch_rte_lw_planck(a, m->dbuf + m->off_planck, m->ntp, m->temperature_planck[0],
-                                       m->temperature_planck[1] - m->temperature_planck[0], tlay, tlev, tsfc, stream));
+                                       m->temperature_planck[1] - m->temperature_planck[0], tlay, tlev, tsfc, stream,
+                                       both ? both->up : nullptr, both ? both->dn : nullptr));
     return 0;
   }
+  if (both) return fail("ecckd: internal: the dual-sky longwave kernel serves 60 layers only");
   // general route (any layer count): sources through scratch, one value per level
   if (!scratch) return fail("ecckd: internal: the fused longwave solver needs scratch for this layer count");
   const size_t n3 = (size_t)ncol * nlay * m->ng;
   double *lay = scratch, *inc = lay + n3, *dec = inc + n3, *sfc = dec + n3, *ring = sfc + (((size_t)ncol * m->ng + 31) & ~(size_t)31);
   ecckd::PlanckArgs p = planck_args(m, ncol, nlay, tlay, PlanckSide{tlev, tsfc, lay, inc, dec, sfc});
-  {
+  if (!sources_in_scratch) {   // (the all-sky pass of ecckd_lw_fluxes_clear_allsky finds the clear pass's sources there)
     ProfScope prof("planck", stream);
     HIPCHK(ecckd::launch_planck(p, stream));
   }
@@ -1746,11 +1761,31 @@ static int lw_increment_dev(const ecckd_model *m, int ncol, int nlay, double *ta
   return 0;
 }
 
+// ecckd_lw_fluxes_clear_allsky behind the gas optics: both skies from the one scratch tau.  60 layers: the clear-sky and the
+// all-sky kernel one after the other, or the dual-sky kernel ("lw_both_skies").  Any other layer count: Planck sources into
+// scratch once, the clear pass, the by-band increment in place, the solver again -- the clear pass has to see tau before
+// the increment.
+static int lw_both_skies_dev(const ecckd_model *m, int ncol, int nlay, int top_at_1, int n_gauss_angles, double *tau,
+                             const double *tlay, const double *tlev, const double *tsfc, const double *sfc_emis,
+                             const double *inc_flux, double *flux_up, double *flux_dn, double *scratch, hipStream_t stream,
+                             const LwParticles &pt, const ClearFluxes &clr) {
+  const bool fused = fused_lw_kernels_apply(m, nlay);
+  if (fused && g_opt.lw_both_skies.load() == 1)
+    return rte_lw_fused_dev(m, ncol, nlay, top_at_1, n_gauss_angles, tau, tlay, tlev, tsfc, sfc_emis, inc_flux, flux_up, flux_dn,
+                            scratch, stream, &pt, &clr);
+  if (rte_lw_fused_dev(m, ncol, nlay, top_at_1, n_gauss_angles, tau, tlay, tlev, tsfc, sfc_emis, inc_flux, clr.up, clr.dn, scratch,
+                       stream))
+    return 1;
+  if (!fused && lw_increment_dev(m, ncol, nlay, tau, pt, stream)) return 1;
+  return rte_lw_fused_dev(m, ncol, nlay, top_at_1, n_gauss_angles, tau, tlay, tlev, tsfc, sfc_emis, inc_flux, flux_up, flux_dn,
+                          scratch, stream, &pt, nullptr, !fused);
+}
+
 static int lw_fluxes_impl(const ecckd_model_t *m, int ncol, int nlay, const double *plev, const double *tlay, const double *tsfc,
                           const double *tlev, int ngas, const char *gas_names, const double *const *vmr,
                           const long long *vmr_col_stride, const long long *vmr_lay_stride, const double *vmr_scalar, int top_at_1,
                           int n_gauss_angles, const double *sfc_emis, const double *inc_flux, double *flux_up, double *flux_dn,
-                          int memspace, void *stream, const LwParticles *pt = nullptr) {
+                          int memspace, void *stream, const LwParticles *pt = nullptr, const ClearFluxes *clr = nullptr) {
   if (check_model(m) || check_gas_optics_dims(ncol, nlay)) return 1;
   if (!m->has_planck) return fail("ecckd_lw_fluxes: model has no Planck table (shortwave model?)");
   if (n_gauss_angles < 1 || n_gauss_angles > 4) return fail("rte_lw: have to ask for at least one quadrature point and no more than 4");
@@ -1769,9 +1804,12 @@ static int lw_fluxes_impl(const ecckd_model_t *m, int ncol, int nlay, const doub
     if (stream_scratch(m->device, st, (n3 + 32 + extra) * sizeof(double), &tau_p, lease)) return 1;
     double *d_tau = static_cast<double *>(tau_p);
     if (gas_optical_depth_dev(m, false, nullptr, ncol, nlay, plev, tlay, gd, d_tau, false, nullptr, nullptr, nullptr, nullptr, st)) return 1;
+    double *d_extra = extra ? d_tau + ((n3 + 31) & ~(size_t)31) : nullptr;
+    if (clr) return lw_both_skies_dev(m, ncol, nlay, top_at_1, n_gauss_angles, d_tau, tlay, tlev, tsfc, sfc_emis, inc_flux, flux_up,
+                                      flux_dn, d_extra, st, *pt, *clr);
     if (pt && !fused_lw_kernels_apply(m, nlay) && lw_increment_dev(m, ncol, nlay, d_tau, *pt, st)) return 1;
     return rte_lw_fused_dev(m, ncol, nlay, top_at_1, n_gauss_angles, d_tau, tlay, tlev, tsfc, sfc_emis, inc_flux, flux_up,
-                            flux_dn, extra ? d_tau + ((n3 + 31) & ~(size_t)31) : nullptr, st, pt);
+                            flux_dn, d_extra, st, pt);
   }
   if (memspace != ECCKD_HOST) return fail("ecckd: bad memspace");
   ecckd_model *mm = const_cast<ecckd_model *>(m);
@@ -1780,10 +1818,11 @@ static int lw_fluxes_impl(const ecckd_model_t *m, int ncol, int nlay, const doub
   const size_t need = align256(n2l * 8) * 4 + align256(n2 * 8) + align256((size_t)ncol * 8) + staged_gas_bytes(gd, ncol, nlay, false) +
                       align256((size_t)ncol * m->nband * 8) + align256((size_t)ncol * m->ng * 8) + align256(n3 * 8) +
                       align256(fused_scratch_doubles(m, ncol, nlay) * 8) + (pt ? align256(n2 * m->nband * 8) * (pt->ssa ? 2 : 1) : 0) +
-                      (pt && pt->mask ? align256(n2 * 8) : 0);
+                      (pt && pt->mask ? align256(n2 * 8) : 0) + (clr ? align256(n2l * 8) * 2 : 0);
   if (grow_arena(mm, need)) return 1;
   Bump b(mm->arena, false);
   double *d_plev = b.take(n2l), *d_tlev = b.take(n2l), *d_tlay = b.take(n2), *d_tsfc = b.take(ncol);
+  double *d_upc = clr ? b.take(n2l) : nullptr, *d_dnc = clr ? b.take(n2l) : nullptr;
   double *d_up = b.take(n2l), *d_dn = b.take(n2l), *d_emis = b.take((size_t)ncol * m->nband), *d_incf = b.take((size_t)ncol * m->ng);
   if (h2d(d_plev, plev, n2l, false, s) || h2d(d_tlay, tlay, n2, false, s) || h2d(d_tsfc, tsfc, ncol, false, s) ||
       h2d(d_tlev, tlev, n2l, false, s) || h2d(d_emis, sfc_emis, (size_t)ncol * m->nband, false, s))
@@ -1807,10 +1846,17 @@ static int lw_fluxes_impl(const ecckd_model_t *m, int ncol, int nlay, const doub
     }
   }
   if (gas_optical_depth_dev(m, false, nullptr, ncol, nlay, d_plev, d_tlay, sg.gd, d_tau, false, nullptr, nullptr, nullptr, nullptr, s)) return 1;
-  if (pt && !fused_lw_kernels_apply(m, nlay) && lw_increment_dev(m, ncol, nlay, d_tau, dp_, s)) return 1;
-  if (rte_lw_fused_dev(m, ncol, nlay, top_at_1, n_gauss_angles, d_tau, d_tlay, d_tlev, d_tsfc, d_emis, inc_flux ? d_incf : nullptr,
-                       d_up, d_dn, d_extra, s, pt ? &dp_ : nullptr))
-    return 1;
+  if (clr) {
+    if (lw_both_skies_dev(m, ncol, nlay, top_at_1, n_gauss_angles, d_tau, d_tlay, d_tlev, d_tsfc, d_emis, inc_flux ? d_incf : nullptr,
+                          d_up, d_dn, d_extra, s, dp_, ClearFluxes{d_upc, d_dnc, nullptr}))
+      return 1;
+    if (d2h(clr->up, d_upc, n2l, false, s) || d2h(clr->dn, d_dnc, n2l, false, s)) return 1;
+  } else {
+    if (pt && !fused_lw_kernels_apply(m, nlay) && lw_increment_dev(m, ncol, nlay, d_tau, dp_, s)) return 1;
+    if (rte_lw_fused_dev(m, ncol, nlay, top_at_1, n_gauss_angles, d_tau, d_tlay, d_tlev, d_tsfc, d_emis,
+                         inc_flux ? d_incf : nullptr, d_up, d_dn, d_extra, s, pt ? &dp_ : nullptr))
+      return 1;
+  }
   if (d2h(flux_up, d_up, n2l, false, s) || d2h(flux_dn, d_dn, n2l, false, s)) return 1;
   HIPCHK(hipStreamSynchronize(s));
   return 0;
@@ -1834,7 +1880,7 @@ static int lw_fluxes_allsky_impl(const ecckd_model_t *m, int ncol, int nlay, con
                                  const double *vmr_scalar, int top_at_1, int n_gauss_angles, const double *sfc_emis,
                                  const double *inc_flux, int nband_p, const double *tau_p, const double *ssa_p,
                                  const unsigned long long *cloud_mask, double *flux_up, double *flux_dn, int memspace,
-                                 void *stream) {
+                                 void *stream, const ClearFluxes *clr = nullptr) {
   if (!m) return fail("ecckd: null model");
   if (cloud_mask && m->ng > 64) return fail("ecckd_lw_fluxes_allsky_mcica" + std::string(kMaskTooWide) + std::to_string(m->ng));
   if (nband_p != m->nband)
@@ -1844,9 +1890,28 @@ static int lw_fluxes_allsky_impl(const ecckd_model_t *m, int ncol, int nlay, con
   if (g_arith.load() != 0) return fail("ecckd_lw_fluxes_allsky: needs the fast arithmetic mode (ecckd_set_arithmetic(0))");
   if (!m->has_planck) return fail("ecckd_lw_fluxes_allsky: model has no Planck table (shortwave model?)");
   if (!tlev) return fail("tlev is required for ecckd");
+  if (clr) {
+    if (!clr->up || !clr->dn)
+      return fail("ecckd_lw_fluxes_clear_allsky: null argument (flux_up_clear and flux_dn_clear are both required)");
+    if (clr->up == flux_up || clr->up == flux_dn || clr->dn == flux_up || clr->dn == flux_dn)
+      return fail("ecckd_lw_fluxes_clear_allsky: a clear-sky output must not be an all-sky output (the two sets of fluxes need arrays of their own)");
+  }
   const LwParticles pt{tau_p, ssa_p, cloud_mask};
   return lw_fluxes_impl(m, ncol, nlay, plev, tlay, tsfc, tlev, ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar,
-                        top_at_1, n_gauss_angles, sfc_emis, inc_flux, flux_up, flux_dn, memspace, stream, &pt);
+                        top_at_1, n_gauss_angles, sfc_emis, inc_flux, flux_up, flux_dn, memspace, stream, &pt, clr);
+}
+
+int ecckd_lw_fluxes_clear_allsky(const ecckd_model_t *m, int ncol, int nlay, const double *plev, const double *tlay,
+                                 const double *tsfc, const double *tlev, int ngas, const char *gas_names,
+                                 const double *const *vmr, const long long *vmr_col_stride, const long long *vmr_lay_stride,
+                                 const double *vmr_scalar, int top_at_1, int n_gauss_angles, const double *sfc_emis,
+                                 const double *inc_flux, int nband_p, const double *tau_p, const double *ssa_p,
+                                 const unsigned long long *cloud_mask, double *flux_up, double *flux_dn, double *flux_up_clear,
+                                 double *flux_dn_clear, int memspace, void *stream) {
+  const ClearFluxes clr{flux_up_clear, flux_dn_clear, nullptr};
+  return lw_fluxes_allsky_impl(m, ncol, nlay, plev, tlay, tsfc, tlev, ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride,
+                               vmr_scalar, top_at_1, n_gauss_angles, sfc_emis, inc_flux, nband_p, tau_p, ssa_p, cloud_mask, flux_up,
+                               flux_dn, memspace, stream, &clr);
 }
 
 int ecckd_lw_fluxes_allsky(const ecckd_model_t *m, int ncol, int nlay, const double *plev, const double *tlay, const double *tsfc,
@@ -1883,7 +1948,8 @@ static int sw_fluxes_impl(bool f32, const ecckd_model_t *m, int ncol, int nlay, 
                           int ngas, const char *gas_names, const double *const *vmr, const long long *vmr_col_stride,
                           const long long *vmr_lay_stride, const double *vmr_scalar, int top_at_1, const double *mu0,
                           const double *toa_scale, const double *sfc_alb_dir, const double *sfc_alb_dif, double *flux_up,
-                          double *flux_dn, double *flux_dir, int memspace, void *stream, const SwParticles *pt = nullptr) {
+                          double *flux_dn, double *flux_dir, int memspace, void *stream, const SwParticles *pt = nullptr,
+                          const ClearFluxes *clr = nullptr) {
   if (check_model(m) || check_gas_optics_dims(ncol, nlay)) return 1;
   if (!m->has_solar) return fail("ecckd_sw_fluxes: model has no solar table (longwave model?)");
   if (!plev || !tlay || !mu0 || !sfc_alb_dir || !sfc_alb_dif || !flux_up || !flux_dn || (ngas > 0 && !gas_names))
@@ -1920,6 +1986,11 @@ static int sw_fluxes_impl(bool f32, const ecckd_model_t *m, int ncol, int nlay, 
       return 1;
     SwDerive dv{plev, rayleigh, solar, toa_scale, gw(f32),
                 solver ? reinterpret_cast<double *>(static_cast<char *>(tau_p) + tau_bytes) : nullptr};
+    // ecckd_sw_fluxes_clear_allsky: the clear-sky solver of ecckd_sw_fluxes first, on the same tau and in the same room
+    if (clr && rte_sw_impl(Call{f32, -1, false, &dv}, m->device, ncol, nlay, m->ng, top_at_1, d_tau, nullptr, nullptr, mu0,
+                           nullptr, m->nband, m->band2gpt.data(), sfc_alb_dir, sfc_alb_dif, clr->up, clr->dn, clr->dir,
+                           ECCKD_DEVICE, stream))
+      return 1;
     if (pt) { dv.part_tau = dp_.tau; dv.part_ssa = dp_.ssa; dv.part_g = dp_.g; dv.part_mask = dp_.mask; }   // (the mask is read in place)
     return rte_sw_impl(Call{f32, -1, false, &dv}, m->device, ncol, nlay, m->ng, top_at_1, d_tau, nullptr, nullptr, mu0,
                        nullptr, m->nband, m->band2gpt.data(), sfc_alb_dir, sfc_alb_dif, flux_up, flux_dn, flux_dir,
@@ -1933,10 +2004,11 @@ static int sw_fluxes_impl(bool f32, const ecckd_model_t *m, int ncol, int nlay, 
   const size_t nb3 = n2 * m->nband;
   const size_t need = (pt ? align256(nb3 * es) * 3 : 0) + (pt && pt->mask ? align256(n2 * 8) : 0) + align256(n2l * es) * 4 + align256(n2 * es) + align256((size_t)ncol * es) * 2 +
                       staged_gas_bytes(gd, ncol, nlay, f32) + align256((size_t)ncol * m->nband * es) * 2 + align256(n3 * es) +
-                      align256(solver);
+                      align256(solver) + (clr ? align256(n2l * es) * 3 : 0);
   if (grow_arena(mm, need)) return 1;
   Bump b(mm->arena, f32);
   double *d_plev = b.take(n2l), *d_tlay = b.take(n2), *d_mu0 = b.take(ncol), *d_scale = b.take(ncol);
+  double *d_upc = clr ? b.take(n2l) : nullptr, *d_dnc = clr ? b.take(n2l) : nullptr, *d_dirc = clr ? b.take(n2l) : nullptr;
   double *d_up = b.take(n2l), *d_dn = b.take(n2l), *d_dir = b.take(n2l);
   double *d_ad = b.take((size_t)ncol * m->nband), *d_af = b.take((size_t)ncol * m->nband);
   if (h2d(d_plev, plev, n2l, f32, s) || h2d(d_tlay, tlay, n2, f32, s) || h2d(d_mu0, mu0, ncol, f32, s) ||
@@ -1950,6 +2022,13 @@ static int sw_fluxes_impl(bool f32, const ecckd_model_t *m, int ncol, int nlay, 
   if (gas_optical_depth_dev(m, f32, nullptr, ncol, nlay, d_plev, d_tlay, sg.gd, d_tau, true, nullptr, nullptr, nullptr, nullptr, s))
     return 1;
   SwDerive dv{d_plev, rayleigh, solar, toa_scale ? d_scale : nullptr, gw(f32), d_solver};
+  if (clr) {   // the clear-sky solver first, as on the device route
+    if (rte_sw_impl(Call{f32, -1, false, &dv}, m->device, ncol, nlay, m->ng, top_at_1, d_tau, nullptr, nullptr, d_mu0, nullptr,
+                    m->nband, m->band2gpt.data(), d_ad, d_af, d_upc, d_dnc, clr->dir ? d_dirc : nullptr, ECCKD_DEVICE, s))
+      return 1;
+    if (d2h(clr->up, d_upc, n2l, f32, s) || d2h(clr->dn, d_dnc, n2l, f32, s)) return 1;
+    if (clr->dir && d2h(clr->dir, d_dirc, n2l, f32, s)) return 1;
+  }
   if (pt) {   // staged copies of the band optics, delta-scaled in place (they are the library's own)
     double *q_tau = b.take(nb3), *q_ssa = b.take(nb3), *q_g = b.take(nb3);
     if (h2d(q_tau, pt->tau, nb3, f32, s) || h2d(q_ssa, pt->ssa, nb3, f32, s) || h2d(q_g, pt->g, nb3, f32, s)) return 1;
@@ -1986,7 +2065,7 @@ static int sw_fluxes_allsky_impl(const ecckd_model_t *m, int ncol, int nlay, con
                                  const double *toa_scale, const double *sfc_alb_dir, const double *sfc_alb_dif, int nband_p,
                                  const double *tau_p, const double *ssa_p, const double *g_p, int delta_scale,
                                  const unsigned long long *cloud_mask, double *flux_up, double *flux_dn, double *flux_dir,
-                                 int memspace, void *stream) {
+                                 int memspace, void *stream, const ClearFluxes *clr = nullptr) {
   if (!m) return fail("ecckd: null model");
   if (cloud_mask && m->ng > 64) return fail("ecckd_sw_fluxes_allsky_mcica" + std::string(kMaskTooWide) + std::to_string(m->ng));
   if (nband_p != m->nband)
@@ -1995,9 +2074,32 @@ static int sw_fluxes_allsky_impl(const ecckd_model_t *m, int ncol, int nlay, con
   if (!tau_p || !ssa_p || !g_p) return fail("ecckd_sw_fluxes_allsky: null argument (tau_p, ssa_p and g_p are all required)");
   if (delta_scale != 0 && delta_scale != 1) return fail("ecckd_sw_fluxes_allsky: delta_scale must be 0 or 1");
   if (g_arith.load() != 0) return fail("ecckd_sw_fluxes_allsky: needs the fast arithmetic mode (ecckd_set_arithmetic(0))");
+  if (clr) {
+    if (!clr->up || !clr->dn)
+      return fail("ecckd_sw_fluxes_clear_allsky: null argument (flux_up_clear and flux_dn_clear are both required; flux_dir_clear may be null)");
+    double *const all[3] = {flux_up, flux_dn, flux_dir}, *const clear[3] = {clr->up, clr->dn, clr->dir};
+    for (double *c : clear)
+      for (double *f : all)
+        if (c && c == f)
+          return fail("ecckd_sw_fluxes_clear_allsky: a clear-sky output must not be an all-sky output (the two sets of fluxes need arrays of their own)");
+  }
   const SwParticles pt{tau_p, ssa_p, g_p, delta_scale, cloud_mask};
   return sw_fluxes_impl(false, m, ncol, nlay, plev, tlay, ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar,
-                        top_at_1, mu0, toa_scale, sfc_alb_dir, sfc_alb_dif, flux_up, flux_dn, flux_dir, memspace, stream, &pt);
+                        top_at_1, mu0, toa_scale, sfc_alb_dir, sfc_alb_dif, flux_up, flux_dn, flux_dir, memspace, stream, &pt, clr);
+}
+
+int ecckd_sw_fluxes_clear_allsky(const ecckd_model_t *m, int ncol, int nlay, const double *plev, const double *tlay, int ngas,
+                                 const char *gas_names, const double *const *vmr, const long long *vmr_col_stride,
+                                 const long long *vmr_lay_stride, const double *vmr_scalar, int top_at_1, const double *mu0,
+                                 const double *toa_scale, const double *sfc_alb_dir, const double *sfc_alb_dif, int nband_p,
+                                 const double *tau_p, const double *ssa_p, const double *g_p, int delta_scale,
+                                 const unsigned long long *cloud_mask, double *flux_up, double *flux_dn, double *flux_dir,
+                                 double *flux_up_clear, double *flux_dn_clear, double *flux_dir_clear, int memspace,
+                                 void *stream) {
+  const ClearFluxes clr{flux_up_clear, flux_dn_clear, flux_dir_clear};
+  return sw_fluxes_allsky_impl(m, ncol, nlay, plev, tlay, ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar,
+                               top_at_1, mu0, toa_scale, sfc_alb_dir, sfc_alb_dif, nband_p, tau_p, ssa_p, g_p, delta_scale,
+                               cloud_mask, flux_up, flux_dn, flux_dir, memspace, stream, &clr);
 }
 
 int ecckd_sw_fluxes_allsky(const ecckd_model_t *m, int ncol, int nlay, const double *plev, const double *tlay, int ngas,

@@ -259,8 +259,11 @@ bool rte_lw_planck_fits(int ng, int ntp);   // the Planck-recomputing form: does
 hipError_t launch_rte_lw_split(const RteLwArgs &a, hipStream_t s);
 // ... with the Planck sources recomputed in the solver from tlay(ncol,nlay), tlev(ncol,nlay+1), tsfc(ncol) and the
 // model's table planck(ng,ntp) (a.lay_source / lev_source_* / sfc_source are not read)
+// flux_up_clear / flux_dn_clear (both or neither; with a.part_tau): the dual-sky kernel, which walks the clear sky and the
+// all sky in one pass and stores the clear-sky fluxes there
 hipError_t launch_rte_lw_planck(const RteLwArgs &a, const double *planck, int ntp, double t0, double dt, const double *tlay,
-                                const double *tlev, const double *tsfc, hipStream_t s);
+                                const double *tlev, const double *tsfc, hipStream_t s, double *flux_up_clear = nullptr,
+                                double *flux_dn_clear = nullptr);
 hipError_t launch_rte_sw(const RteSwArgs &a, hipStream_t s);
 // layer-systolic shortwave solver (kernels_rte_sw_sys.hip): any precision, nlay <= 60
 bool rte_sw_sys_applies(const RteSwArgs &a);

@@ -94,22 +94,34 @@ __host__ __device__ constexpr int planck_stride(int ng) { return ng | 1; }   // 
 // (column, layer); where bit g is clear the cell uses part_tau = 0 in front of the expressions above -- one select per
 // cell.  The lane's g-point is fixed for an iteration, so a prefetch slot carries only the 32-bit half of the word that
 // holds it.
-template <int SEG, int NW, int CW, bool SHARED, bool SER3, bool PLANCK, int SKY, bool MASK = false>
+// BOTH (with SKY; rte_lw_split_both_kernel, ecckd_lw_fluxes_clear_allsky): the dual-sky form.  One group per block walks
+// the clear sky (the gas optical depth as it is read) and the all sky of its tile in one pass: the three Planck sources of
+// a cell and the surface source are evaluated once, everything that hangs on the optical depth -- t, sdn, su, the
+// composites, the exchange and the accumulators -- exists twice, and the clear-sky fluxes go to flux_up_clear /
+// flux_dn_clear.  The second exchange and accumulator set takes the LDS of the second group, and the block's four waves
+// sit one per SIMD with the whole register file.  Each sky's per-cell expressions and the order in which a level's
+// accumulator receives its g-points are those of the single-sky kernels: the fluxes are theirs bit for bit.
+template <int SEG, int NW, int CW, bool SHARED, bool SER3, bool PLANCK, int SKY, bool MASK = false, bool BOTH = false>
 __device__ __forceinline__ void rte_lw_split_body(const RteLwArgs &a, const PlanckTab &pt, const double *tlay, const double *tlev,
-                                                  const double *tsfc) {
+                                                  const double *tsfc, [[maybe_unused]] double *flux_up_clear = nullptr,
+                                                  [[maybe_unused]] double *flux_dn_clear = nullptr) {
   static_assert(SKY == 0 || PLANCK, "the all-sky form extends the Planck-recomputing solver");
   static_assert(SKY != 0 || !MASK, "a cloud mask belongs to the all-sky form");
+  static_assert(SKY != 0 || !BOTH, "the dual-sky form extends the all-sky form");
   constexpr int GW = 64 / CW;
   constexpr int NL = SEG * NW;
-  constexpr int NG = split_groups(PLANCK);
+  constexpr int NG = BOTH ? 1 : split_groups(PLANCK);
   constexpr int kSplitPF = split_pf(PLANCK);
-  constexpr int kGroupDoubles = 2 * (NL + 1) * CW + 2 * NW * 3 * 64;
+  constexpr int kSkyDoubles = 2 * (NL + 1) * CW + 2 * NW * 3 * 64;   // accumulators and exchange of one sky
+  constexpr int kGroupDoubles = (BOTH ? 2 : 1) * kSkyDoubles;
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int grp = (tid >> 6) / NW, w = (tid >> 6) % NW, gtid = tid - grp * 64 * NW;
   double *acc_dn = reinterpret_cast<double *>(lds_raw) + grp * kGroupDoubles;   // [NL+1][CW]
   double *acc_up = acc_dn + (NL + 1) * CW;                                         // [NL+1][CW]
   double *xch = acc_up + (NL + 1) * CW;                                            // [2][NW][3][64]
+  // BOTH: the clear sky's set behind the all sky's, laid out alike
+  [[maybe_unused]] double *acc_dn_c = acc_dn + kSkyDoubles, *acc_up_c = acc_up + kSkyDoubles, *xch_c = xch + kSkyDoubles;
   [[maybe_unused]] const int pstride = PLANCK ? planck_stride(a.ng) : 0;
   [[maybe_unused]] double *ptab = reinterpret_cast<double *>(lds_raw) + NG * kGroupDoubles;   // PLANCK: [ntp][pstride]
   if (PLANCK) {
@@ -134,6 +146,8 @@ __device__ __forceinline__ void rte_lw_split_body(const RteLwArgs &a, const Plan
   const int s0 = w * SEG;   // first layer of this wave, in walking order from the top
 
   for (int i = gtid; i < 2 * (NL + 1) * CW; i += 64 * NW) acc_dn[i] = 0.;
+  if (BOTH)
+    for (int i = gtid; i < 2 * (NL + 1) * CW; i += 64 * NW) acc_dn_c[i] = 0.;
   __syncthreads();
 
   // every group of the block walks the same number of tiles (block barriers inside): a group whose tile lies beyond the
@@ -206,10 +220,13 @@ __device__ __forceinline__ void rte_lw_split_body(const RteLwArgs &a, const Plan
       // ---------------- phase 1: this wave's SEG layers ----------------
       double T[SEG], SDN[SEG], SU[SEG];
       double Tq = 1., Dq = 0.;
+      [[maybe_unused]] double Tc[BOTH ? SEG : 1], SDNc[BOTH ? SEG : 1], SUc[BOTH ? SEG : 1];   // BOTH: the clear sky's
+      [[maybe_unused]] double Tqc = 1., Dqc = 0.;
       [[maybe_unused]] double carry = PLANCK ? planck_at(pt, ptab, pstride, near_first, gg, pi_f32, rpi_f32) : near_first;
 #pragma unroll
       for (int s = 0; s < SEG; ++s) {
         double tau = ptau[s % kSplitPF];
+        [[maybe_unused]] const double tau_c = tau;   // BOTH: the gas optical depth alone
         [[maybe_unused]] double tp = 0.;
         if (SKY) tp = ppt[s % kSplitPF];
         if (MASK) tp = (pmk[s % kSplitPF] >> mbit) & 1u ? tp : 0.;
@@ -241,11 +258,30 @@ __device__ __forceinline__ void rte_lw_split_body(const RteLwArgs &a, const Plan
         T[s] = t; SDN[s] = sdn; SU[s] = su;
         Dq = t * Dq + sdn;
         Tq = Tq * t;
+        if (BOTH) {   // the same cell under the clear sky: the expressions above on tau_c
+          const double tlc = tau_c * D;
+          const double tc = lw_exp(-tlc);
+          const double omtc = 1. - tc;
+          const double factc_big = lw_div(omtc, tlc) - tc;
+          const double factc_small = SER3 ? tlc * (0.5 + tlc * (-1. / 3. + tlc * (1. / 8.))) : tlc * (0.5 - 1. / 3. * tlc);
+          const double factc = tlc > tau_thresh ? factc_big : factc_small;
+          const double sdnc = omtc * bdn + 2. * factc * (lay - bdn);
+          double suc = omtc * bup + 2. * factc * (lay - bup);
+          asm volatile("" : "+v"(suc));
+          Tc[s] = tc; SDNc[s] = sdnc; SUc[s] = suc;
+          Dqc = tc * Dqc + sdnc;
+          Tqc = Tqc * tc;
+        }
         if (SHARED || PLANCK) carry = bdn;
       }
       double Uq = 0.;
 #pragma unroll
       for (int s = SEG - 1; s >= 0; --s) Uq = T[s] * Uq + SU[s];
+      [[maybe_unused]] double Uqc = 0.;
+      if (BOTH) {
+#pragma unroll
+        for (int s = SEG - 1; s >= 0; --s) Uqc = Tc[s] * Uqc + SUc[s];
+      }
       // the next pair's first layers start streaming now
       if (it + 1 < niter) {
         pair_start(it + 1);
@@ -256,6 +292,12 @@ __device__ __forceinline__ void rte_lw_split_body(const RteLwArgs &a, const Plan
       x[(w * 3 + 0) * 64 + lane] = Tq;
       x[(w * 3 + 1) * 64 + lane] = Dq;
       x[(w * 3 + 2) * 64 + lane] = Uq;
+      [[maybe_unused]] double *xc = xch_c + (it & 1) * (NW * 3 * 64);
+      if (BOTH) {
+        xc[(w * 3 + 0) * 64 + lane] = Tqc;
+        xc[(w * 3 + 1) * 64 + lane] = Dqc;
+        xc[(w * 3 + 2) * 64 + lane] = Uqc;
+      }
       __syncthreads();
 
       // ---------------- phase 2: boundary intensities of this segment, then both sweeps ----------------
@@ -264,6 +306,7 @@ __device__ __forceinline__ void rte_lw_split_body(const RteLwArgs &a, const Plan
         const double f = a.inc_flux[cc + (long)ncol * gg];
         I = a.inc_isotropic ? f / pi : f / (2. * pi * a.wts[k]);
       }
+      [[maybe_unused]] const double Itop = I;
       double Iin = I;
 #pragma unroll
       for (int q = 0; q < NW; ++q) {
@@ -295,6 +338,35 @@ __device__ __forceinline__ void rte_lw_split_body(const RteLwArgs &a, const Plan
         U = T[s] * U + SU[s];
       }
       if (w == 0) acc_add(&acc_up[cl], gsum<CW>(wfac * U), owner);
+      if (BOTH) {   // phase 2 once more, on the clear sky's composites into the clear sky's accumulators
+        double Ic = Itop, Iinc = Itop;
+#pragma unroll
+        for (int q = 0; q < NW; ++q) {
+          if (q == w) Iinc = Ic;
+          Ic = xc[(q * 3 + 0) * 64 + lane] * Ic + xc[(q * 3 + 1) * 64 + lane];
+        }
+        double Uc = Ic * (1. - eps) + eps * sfc_src;   // surface
+        double Uinc = Uc;
+#pragma unroll
+        for (int q = NW - 1; q >= 0; --q) {
+          if (q == w) Uinc = Uc;
+          Uc = xc[(q * 3 + 0) * 64 + lane] * Uc + xc[(q * 3 + 2) * 64 + lane];
+        }
+        Ic = Iinc;
+#pragma unroll
+        for (int s = 0; s < SEG; ++s) {
+          acc_add(&acc_dn_c[(s0 + s) * CW + cl], gsum<CW>(wfac * Ic), owner);
+          Ic = Tc[s] * Ic + SDNc[s];
+        }
+        if (w == NW - 1) acc_add(&acc_dn_c[NL * CW + cl], gsum<CW>(wfac * Ic), owner);
+        Uc = Uinc;
+#pragma unroll
+        for (int s = SEG - 1; s >= 0; --s) {
+          acc_add(&acc_up_c[(s0 + s + 1) * CW + cl], gsum<CW>(wfac * Uc), owner);
+          Uc = Tc[s] * Uc + SUc[s];
+        }
+        if (w == 0) acc_add(&acc_up_c[cl], gsum<CW>(wfac * Uc), owner);
+      }
     }
 
     // broadband fluxes of the tile: level s-th from the top -> lev0 + lstep*s
@@ -306,9 +378,17 @@ __device__ __forceinline__ void rte_lw_split_body(const RteLwArgs &a, const Plan
         const long q = cg + (long)ncol * (lev0 + lstep * s);
         a.flux_dn[q] = acc_dn[i];
         a.flux_up[q] = acc_up[i];
+        if (BOTH) {
+          flux_dn_clear[q] = acc_dn_c[i];
+          flux_up_clear[q] = acc_up_c[i];
+        }
       }
       acc_dn[i] = 0.;
       acc_up[i] = 0.;
+      if (BOTH) {
+        acc_dn_c[i] = 0.;
+        acc_up_c[i] = 0.;
+      }
     }
     __syncthreads();
   }
@@ -336,6 +416,36 @@ __global__ void __launch_bounds__(64 * NW * split_groups(true), WPS) rte_lw_spli
                                                                                               const double *tlay, const double *tlev,
                                                                                               const double *tsfc) {
   rte_lw_split_body<SEG, NW, CW, false, SER3, true, TWOSTR ? 2 : 1, true>(a, pt, tlay, tlev, tsfc);
+}
+
+// The dual-sky form (BOTH of rte_lw_split_body): clear-sky and all-sky fluxes of a tile in one pass, one group per block and
+// one wave per SIMD.  MASK: with a McICA cloud mask.
+template <int SEG, int NW, int CW, bool SER3, bool TWOSTR, bool MASK>
+__global__ void __launch_bounds__(64 * NW, 1) rte_lw_split_both_kernel(const RteLwArgs a, const PlanckTab pt, const double *tlay,
+                                                                       const double *tlev, const double *tsfc,
+                                                                       double *flux_up_clear, double *flux_dn_clear) {
+  rte_lw_split_body<SEG, NW, CW, false, SER3, true, TWOSTR ? 2 : 1, MASK, true>(a, pt, tlay, tlev, tsfc, flux_up_clear, flux_dn_clear);
+}
+
+template <int SEG, int NW, int CW, bool SER3, bool TWOSTR, bool MASK>
+hipError_t launch_split_both(const RteLwArgs &a, const PlanckTab &pt, const double *tlay, const double *tlev, const double *tsfc,
+                             double *flux_up_clear, double *flux_dn_clear, hipStream_t s) {
+  auto k = rte_lw_split_both_kernel<SEG, NW, CW, SER3, TWOSTR, MASK>;
+  // two skies of one group: the accumulators and exchange of the single-sky kernels' two groups
+  const size_t lds = sizeof(double) * (2 * (2 * (size_t)(SEG * NW + 1) * CW + 2 * NW * 3 * 64) + (size_t)pt.ntp * planck_stride(a.ng));
+  if (lds > (size_t)kLdsBudget) return hipErrorInvalidValue;
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (e != hipSuccess) return e;
+  long blocks = ((long)a.ncol + CW - 1) / CW;
+  // One block is resident per CU (its LDS), so 256 * 4 blocks are four rounds; past the cap a block walks tiles by grid
+  // stride and reloads neither the Planck table nor its code.  A block here carries one tile per iteration where the
+  // single-sky kernels carry two, so at equal block count the longest block runs ceil(tiles / 1024) tiles: 4 against a mean
+  // of 3.05 at 1e5 columns (the tail is one tile, a quarter of a round), 31 against 30.5 at 1e6.  The timings of DESIGN
+  // section 5.5c were taken with this cap.
+  const long cap = 256L * 4;
+  if (blocks > cap) blocks = cap;
+  hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(64 * NW), lds, s, a, pt, tlay, tlev, tsfc, flux_up_clear, flux_dn_clear);
+  return hipGetLastError();
 }
 
 // SKY: 0 the clear-sky kernel, 1 / 2 the all-sky form with one- / two-stream particles (PLANCK only); MASK: with a.part_mask
@@ -407,10 +517,29 @@ hipError_t launch_rte_lw_split(const RteLwArgs &a, hipStream_t s) {
                    : launch_seg<false, false, false>(a, none, nullptr, nullptr, nullptr, s);
 }
 
+template <bool SER3>
+static hipError_t launch_both(const RteLwArgs &a, const PlanckTab &pt, const double *tlay, const double *tlev, const double *tsfc,
+                              double *up_c, double *dn_c, hipStream_t s) {
+  const bool two = !(a.part_1scl || !a.part_ssa);
+  if (a.part_mask) {
+    if (a.ng > 64) return hipErrorInvalidValue;
+    return two ? launch_split_both<15, 4, 32, SER3, true, true>(a, pt, tlay, tlev, tsfc, up_c, dn_c, s)
+               : launch_split_both<15, 4, 32, SER3, false, true>(a, pt, tlay, tlev, tsfc, up_c, dn_c, s);
+  }
+  return two ? launch_split_both<15, 4, 32, SER3, true, false>(a, pt, tlay, tlev, tsfc, up_c, dn_c, s)
+             : launch_split_both<15, 4, 32, SER3, false, false>(a, pt, tlay, tlev, tsfc, up_c, dn_c, s);
+}
+
 hipError_t launch_rte_lw_planck(const RteLwArgs &a, const double *planck, int ntp, double t0, double dt, const double *tlay,
-                                const double *tlev, const double *tsfc, hipStream_t s) {
+                                const double *tlev, const double *tsfc, hipStream_t s, double *flux_up_clear,
+                                double *flux_dn_clear) {
   if (a.f32 || a.nlay != 60 || a.ncol <= 0) return hipErrorInvalidValue;
   const PlanckTab pt{planck, t0, dt, 1. / dt, ntp, a.ng};
+  if (flux_up_clear || flux_dn_clear) {   // the dual-sky kernel (ecckd_lw_fluxes_clear_allsky, "lw_both_skies" = 1)
+    if (!flux_up_clear || !flux_dn_clear || !a.part_tau) return hipErrorInvalidValue;
+    return a.series3 ? launch_both<true>(a, pt, tlay, tlev, tsfc, flux_up_clear, flux_dn_clear, s)
+                     : launch_both<false>(a, pt, tlay, tlev, tsfc, flux_up_clear, flux_dn_clear, s);
+  }
   return a.series3 ? launch_seg<false, true, true>(a, pt, tlay, tlev, tsfc, s)
                    : launch_seg<false, false, true>(a, pt, tlay, tlev, tsfc, s);
 }

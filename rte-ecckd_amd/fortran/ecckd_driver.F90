@@ -2,7 +2,7 @@
 ! example/rfmip-rad-irf/ecckd_rfmip_lw.F90:107-136 and ecckd_rfmip_sw.F90:112-162: load the ecCKD
 ! file, then per column block gas_optics() followed by rte_lw()/rte_sw(), fluxes out.
 !
-!   ecckd_driver lw|sw  <ecckd_file.nc>  <input.bin>  <output.bin>  [block_size] [n_quad_angles] [device_resident 0|1] [repeats] [byband 0|1] [fused 0|1] [particles.bin] [cloudfrac.bin]
+!   ecckd_driver lw|sw  <ecckd_file.nc>  <input.bin>  <output.bin>  [block_size] [n_quad_angles] [device_resident 0|1] [repeats] [byband 0|1] [fused 0|1] [particles.bin] [cloudfrac.bin] [clear.bin]
 !
 ! device_resident = 1: optical_props / source are the device twins of mo_ecckd_device (tau and the sources stay in
 ! HBM between gas_optics and the solver; ECCKD_MIXED memory space of the C ABI).
@@ -18,6 +18,10 @@
 !            column offset, and the mask goes to the all-sky call (cloud_mask=).  Little-endian: int32 overlap (0 maximum-
 !            random, 1 exponential-random), int64 seed, float64 cloud_frac(ncol,nlay) and, for overlap 1,
 !            overlap_param(ncol,nlay-1).
+! clear.bin (needs fused = 1 and particles.bin): a second output file, in the layout of output.bin, with the clear-sky fluxes
+!            of the same columns -- the all-sky call is made with flux_up_clear / flux_dn_clear, so both skies come from one
+!            gas-optics pass per block (ecckd_lw_fluxes_clear_allsky / ecckd_sw_fluxes_clear_allsky).  An empty string for
+!            cloudfrac.bin (or any file argument) means "none".
 ! byband = 1: fluxes go through ty_fluxes_byband (per-band arrays; their sum over bands must reproduce the broadband
 ! fluxes, which are what output.bin holds either way).
 !
@@ -57,6 +61,9 @@ program ecckd_driver
   logical :: allsky = .false.
   character(len=512) :: frac_path
   logical :: mcica = .false.
+  character(len=512) :: clear_path
+  logical :: both = .false.
+  real(wp), dimension(:,:), allocatable :: clear_up, clear_dn
   integer(int32) :: overlap
   integer(int64) :: seed
   real(wp), dimension(:,:), allocatable :: cloud_frac, overlap_param
@@ -125,6 +132,15 @@ program ecckd_driver
   if (command_argument_count() >= 12) then
     call get_command_argument(12, frac_path)
     mcica = len_trim(frac_path) > 0
+  end if
+  if (command_argument_count() >= 13) then
+    call get_command_argument(13, clear_path)
+    both = len_trim(clear_path) > 0
+  end if
+  if (both .and. .not. (allsky .and. fused /= 0)) then
+    write(error_unit, "(a)") " ecckd_driver: a clear-sky output file needs fused = 1 and a particle file (particles.bin)"
+    call usage()
+    stop 1
   end if
   if (mcica .and. .not. allsky) then
     write(error_unit, "(a)") " ecckd_driver: a cloud-fraction file needs a particle file (particles.bin)"
@@ -198,6 +214,7 @@ program ecckd_driver
   nbnd = ecckd%get_nband()
   top_at_1 = play(1, 1) < play(1, nlay)                   ! ecckd_rfmip_lw.F90:85
   allocate(flux_up(ncol, nlay + 1), flux_dn(ncol, nlay + 1))
+  if (both) allocate(clear_up(ncol, nlay + 1), clear_dn(ncol, nlay + 1))
   nblocks = (ncol + block_size - 1) / block_size
 
   ! gas concentrations per block, as read_and_block_gases_ty prepares them before the reference's loop
@@ -247,7 +264,19 @@ program ecckd_driver
         call stop_on_err(ecckd%sample_cloud_mask(cloud_frac(c0:c1, :), int(overlap), seed, int(c0 - 1, int64), mask_b))
       end if
     end if
-    if (lw .and. allsky) then
+    if (lw .and. both) then
+      if (has_ssa_g /= 0) then
+        call stop_on_err(ecckd%lw_fluxes_allsky(plev(c0:c1, :), tlay(c0:c1, :), tsfc(c0:c1), tlev(c0:c1, :), gas_concs(b), &
+                                                top_at_1, sfc_spec, tau_p(c0:c1, :, :), flux_up(c0:c1, :), flux_dn(c0:c1, :), &
+                                                ssa_p=ssa_p(c0:c1, :, :), n_gauss_angles=n_quad_angles, cloud_mask=mask_b, &
+                                                flux_up_clear=clear_up(c0:c1, :), flux_dn_clear=clear_dn(c0:c1, :)))
+      else
+        call stop_on_err(ecckd%lw_fluxes_allsky(plev(c0:c1, :), tlay(c0:c1, :), tsfc(c0:c1), tlev(c0:c1, :), gas_concs(b), &
+                                                top_at_1, sfc_spec, tau_p(c0:c1, :, :), flux_up(c0:c1, :), flux_dn(c0:c1, :), &
+                                                n_gauss_angles=n_quad_angles, cloud_mask=mask_b, &
+                                                flux_up_clear=clear_up(c0:c1, :), flux_dn_clear=clear_dn(c0:c1, :)))
+      end if
+    else if (lw .and. allsky) then
       if (has_ssa_g /= 0) then
         call stop_on_err(ecckd%lw_fluxes_allsky(plev(c0:c1, :), tlay(c0:c1, :), tsfc(c0:c1), tlev(c0:c1, :), gas_concs(b), &
                                                 top_at_1, sfc_spec, tau_p(c0:c1, :, :), flux_up(c0:c1, :), flux_dn(c0:c1, :), &
@@ -278,7 +307,12 @@ program ecckd_driver
         sfc_spec(:, i) = bc2(c0 + i - 1)                     ! albedo, direct = diffuse (ecckd_rfmip_sw.F90:136-141)
         sfc_spec2(:, i) = bc2(c0 + i - 1)
       end do
-      if (allsky) then
+      if (both) then
+        call stop_on_err(ecckd%sw_fluxes_allsky(plev(c0:c1, :), tlay(c0:c1, :), gas_concs(b), top_at_1, bc1(c0:c1), sfc_spec, &
+                                                sfc_spec2, tau_p(c0:c1, :, :), ssa_p(c0:c1, :, :), g_p(c0:c1, :, :), &
+                                                delta_flag /= 0, flux_up(c0:c1, :), flux_dn(c0:c1, :), cloud_mask=mask_b, &
+                                                flux_up_clear=clear_up(c0:c1, :), flux_dn_clear=clear_dn(c0:c1, :)))
+      else if (allsky) then
         call stop_on_err(ecckd%sw_fluxes_allsky(plev(c0:c1, :), tlay(c0:c1, :), gas_concs(b), top_at_1, bc1(c0:c1), sfc_spec, &
                                                 sfc_spec2, tau_p(c0:c1, :, :), ssa_p(c0:c1, :, :), g_p(c0:c1, :, :), &
                                                 delta_flag /= 0, flux_up(c0:c1, :), flux_dn(c0:c1, :), cloud_mask=mask_b))
@@ -316,6 +350,11 @@ program ecckd_driver
   open(newunit=u, file=trim(out_path), access="stream", form="unformatted", status="replace")
   write(u) flux_up, flux_dn
   close(u)
+  if (both) then
+    open(newunit=u, file=trim(clear_path), access="stream", form="unformatted", status="replace")
+    write(u) clear_up, clear_dn
+    close(u)
+  end if
   call ecckd%finalize()
   write(error_unit, *) "ecckd_driver: ", ncol, " columns in ", nblocks, " blocks done"
 
@@ -323,6 +362,7 @@ contains
   subroutine usage()
     write(error_unit, "(a)") " usage: ecckd_driver lw|sw ecckd_file input.bin output.bin [block_size] [n_quad_angles]"
     write(error_unit, "(a)") "        [device_resident 0|1] [repeats] [byband 0|1] [fused 0|1] [particles.bin] [cloudfrac.bin]"
+    write(error_unit, "(a)") "        [clear.bin: clear-sky fluxes of the same columns; needs fused = 1 and particles.bin]"
   end subroutine usage
 
   subroutine stop_on_err(msg)                                ! mo_simple_netcdf.F90:331-339

@@ -268,6 +268,40 @@ module gas_optics_ecckd
       type(c_ptr), value :: stream
       integer(c_int) :: rc
     end function c_sw_fluxes_allsky_mcica
+    function c_lw_fluxes_clear_allsky(model, ncol, nlay, plev, tlay, tsfc, tlev, ngas, gas_names, vmr, cs, ls, scalar, top_at_1, &
+                                      nmus, sfc_emis, inc_flux, nband_p, tau_p, ssa_p, cloud_mask, flux_up, flux_dn, &
+                                      flux_up_clear, flux_dn_clear, memspace, stream) &
+        bind(C, name="ecckd_lw_fluxes_clear_allsky") result(rc)
+      import c_ptr, c_int, c_double, c_char, c_long_long
+      type(c_ptr), value :: model
+      integer(c_int), value :: ncol, nlay, ngas, top_at_1, nmus, nband_p, memspace
+      real(c_double), dimension(*), intent(in) :: plev, tlay, tsfc, tlev, sfc_emis, tau_p
+      character(kind=c_char), dimension(*), intent(in) :: gas_names
+      type(c_ptr), dimension(*), intent(in) :: vmr
+      integer(c_long_long), dimension(*), intent(in) :: cs, ls
+      real(c_double), dimension(*), intent(in) :: scalar
+      type(c_ptr), value :: inc_flux, ssa_p, cloud_mask
+      real(c_double), dimension(*), intent(inout) :: flux_up, flux_dn, flux_up_clear, flux_dn_clear
+      type(c_ptr), value :: stream
+      integer(c_int) :: rc
+    end function c_lw_fluxes_clear_allsky
+    function c_sw_fluxes_clear_allsky(model, ncol, nlay, plev, tlay, ngas, gas_names, vmr, cs, ls, scalar, top_at_1, mu0, &
+                                      toa_scale, sfc_alb_dir, sfc_alb_dif, nband_p, tau_p, ssa_p, g_p, delta_scale, cloud_mask, &
+                                      flux_up, flux_dn, flux_dir, flux_up_clear, flux_dn_clear, flux_dir_clear, memspace, &
+                                      stream) bind(C, name="ecckd_sw_fluxes_clear_allsky") result(rc)
+      import c_ptr, c_int, c_double, c_char, c_long_long
+      type(c_ptr), value :: model
+      integer(c_int), value :: ncol, nlay, ngas, top_at_1, nband_p, delta_scale, memspace
+      real(c_double), dimension(*), intent(in) :: plev, tlay, mu0, sfc_alb_dir, sfc_alb_dif, tau_p, ssa_p, g_p
+      character(kind=c_char), dimension(*), intent(in) :: gas_names
+      type(c_ptr), dimension(*), intent(in) :: vmr
+      integer(c_long_long), dimension(*), intent(in) :: cs, ls
+      real(c_double), dimension(*), intent(in) :: scalar
+      type(c_ptr), value :: toa_scale, flux_dir, flux_dir_clear, cloud_mask
+      real(c_double), dimension(*), intent(inout) :: flux_up, flux_dn, flux_up_clear, flux_dn_clear
+      type(c_ptr), value :: stream
+      integer(c_int) :: rc
+    end function c_sw_fluxes_clear_allsky
     function c_cloud_mask_sample(device, ncol, nlay, ngpt, overlap, cloud_frac, overlap_param, seed, col0, mask, memspace, &
                                  stream) bind(C, name="ecckd_cloud_mask_sample") result(rc)
       import c_ptr, c_int, c_double, c_int64_t
@@ -704,8 +738,10 @@ contains
   !! never written.  flux_up / flux_dn are (ncol, nlay+1), sfc_emis (nband, ncol).
   !! cloud_mask (ncol, nlay), from sample_cloud_mask (ecckd_lw_fluxes_allsky_mcica): a g-point whose bit is clear sees no
   !! particles in that layer.
+  !! flux_up_clear / flux_dn_clear (ncol, nlay+1), both or neither: the clear-sky fluxes of the same columns from the same
+  !! gas-optics pass (ecckd_lw_fluxes_clear_allsky) -- what lw_fluxes returns, bit for bit.
   function lw_fluxes_allsky(this, plev, tlay, tsfc, tlev, gas_desc, top_at_1, sfc_emis, tau_p, flux_up, flux_dn, ssa_p, &
-                            n_gauss_angles, cloud_mask) result(error_msg)
+                            n_gauss_angles, cloud_mask, flux_up_clear, flux_dn_clear) result(error_msg)
     class(ty_gas_optics_ecckd), intent(in) :: this
     real(wp), dimension(:,:), intent(in) :: plev, tlay, tlev
     real(wp), dimension(:), intent(in) :: tsfc
@@ -717,14 +753,16 @@ contains
     real(wp), dimension(:,:,:), intent(in), optional :: ssa_p
     integer, intent(in), optional :: n_gauss_angles
     integer(c_int64_t), dimension(:,:), intent(in), optional :: cloud_mask
+    real(wp), dimension(:,:), intent(inout), optional :: flux_up_clear, flux_dn_clear
     character(len=128) :: error_msg
     character(kind=c_char), dimension(:), allocatable :: names
     type(c_ptr), dimension(:), allocatable :: ptr
     integer(c_long_long), dimension(:), allocatable :: cs, ls
     real(c_double), dimension(:), allocatable :: scalar
-    real(wp), dimension(:,:), allocatable :: up, dn
+    real(wp), dimension(:,:), allocatable :: up, dn, upc, dnc
     real(wp), dimension(:,:,:), allocatable, target :: ssa
-    type(c_ptr) :: ssa_c
+    integer(c_int64_t), dimension(:,:), allocatable, target :: mask
+    type(c_ptr) :: ssa_c, mask_c
     integer :: ncol, nlay, n, nmus
     integer(c_int) :: rc
     ncol = size(tlay, 1)
@@ -753,7 +791,31 @@ contains
     end if
     n = gas_desc%get_num_gases()
     allocate(up(ncol, nlay + 1), dn(ncol, nlay + 1))
-    if (present(cloud_mask)) then
+    if (present(flux_up_clear) .neqv. present(flux_dn_clear)) then
+      error_msg = "lw_fluxes_allsky: flux_up_clear and flux_dn_clear go together"
+      return
+    end if
+    if (present(flux_up_clear)) then   ! both skies from one gas-optics pass
+      mask_c = c_null_ptr
+      if (present(cloud_mask)) then
+        if (size(cloud_mask, 1) /= ncol .or. size(cloud_mask, 2) /= nlay) then
+          error_msg = "lw_fluxes_allsky: cloud_mask inconsistently sized"
+          return
+        end if
+        allocate(mask(ncol, nlay))
+        mask = cloud_mask
+        if (size(mask) > 0) mask_c = c_loc(mask(1, 1))
+      end if
+      allocate(upc(ncol, nlay + 1), dnc(ncol, nlay + 1))
+      rc = c_lw_fluxes_clear_allsky(this%handle, int(ncol, c_int), int(nlay, c_int), plev, tlay, tsfc, tlev, int(n, c_int), names, &
+                                    ptr, cs, ls, scalar, merge(1_c_int, 0_c_int, top_at_1), int(nmus, c_int), sfc_emis, &
+                                    c_null_ptr, int(size(tau_p, 3), c_int), tau_p, ssa_c, mask_c, up, dn, upc, dnc, ECCKD_HOST, &
+                                    c_null_ptr)
+      if (rc == 0) then
+        flux_up_clear = upc
+        flux_dn_clear = dnc
+      end if
+    else if (present(cloud_mask)) then
       if (size(cloud_mask, 1) /= ncol .or. size(cloud_mask, 2) /= nlay) then
         error_msg = "lw_fluxes_allsky: cloud_mask inconsistently sized"
         return
@@ -781,8 +843,11 @@ contains
   !! particulate arrays are never written.  The other arguments are those of sw_fluxes.
   !! cloud_mask (ncol, nlay), from sample_cloud_mask (ecckd_sw_fluxes_allsky_mcica): a g-point whose bit is clear sees no
   !! particles in that layer.
+  !! flux_up_clear / flux_dn_clear (both or neither) and, optionally with them, flux_dir_clear: the clear-sky fluxes of the
+  !! same columns from the same gas-optics pass (ecckd_sw_fluxes_clear_allsky) -- what sw_fluxes returns, bit for bit.
   function sw_fluxes_allsky(this, plev, tlay, gas_desc, top_at_1, mu0, sfc_alb_dir, sfc_alb_dif, tau_p, ssa_p, g_p, delta_scale, &
-                            flux_up, flux_dn, flux_dir, toa_scale, cloud_mask) result(error_msg)
+                            flux_up, flux_dn, flux_dir, toa_scale, cloud_mask, flux_up_clear, flux_dn_clear, flux_dir_clear) &
+      result(error_msg)
     class(ty_gas_optics_ecckd), intent(in) :: this
     real(wp), dimension(:,:), intent(in) :: plev, tlay
     type(ty_gas_concs), intent(in) :: gas_desc
@@ -795,14 +860,16 @@ contains
     real(wp), dimension(:,:), intent(inout), optional :: flux_dir
     real(wp), dimension(:), intent(in), optional, target :: toa_scale
     integer(c_int64_t), dimension(:,:), intent(in), optional :: cloud_mask
+    real(wp), dimension(:,:), intent(inout), optional :: flux_up_clear, flux_dn_clear, flux_dir_clear
     character(len=128) :: error_msg
     character(kind=c_char), dimension(:), allocatable :: names
     type(c_ptr), dimension(:), allocatable :: ptr
     integer(c_long_long), dimension(:), allocatable :: cs, ls
     real(c_double), dimension(:), allocatable :: scalar
-    real(wp), dimension(:,:), allocatable, target :: up, dn, dir
+    real(wp), dimension(:,:), allocatable, target :: up, dn, dir, upc, dnc, dirc
     real(wp), dimension(:), allocatable, target :: scale
-    type(c_ptr) :: scale_p, dir_p
+    integer(c_int64_t), dimension(:,:), allocatable, target :: mask
+    type(c_ptr) :: scale_p, dir_p, dirc_p, mask_c
     integer :: ncol, nlay, n
     integer(c_int) :: rc
     ncol = size(tlay, 1)
@@ -832,7 +899,37 @@ contains
       allocate(dir(ncol, nlay + 1))
       dir_p = c_loc(dir(1, 1))
     end if
-    if (present(cloud_mask)) then
+    if ((present(flux_up_clear) .neqv. present(flux_dn_clear)) .or. (present(flux_dir_clear) .and. .not. present(flux_up_clear))) then
+      error_msg = "sw_fluxes_allsky: flux_up_clear and flux_dn_clear go together (flux_dir_clear with them)"
+      return
+    end if
+    if (present(flux_up_clear)) then   ! both skies from one gas-optics pass
+      mask_c = c_null_ptr
+      if (present(cloud_mask)) then
+        if (size(cloud_mask, 1) /= ncol .or. size(cloud_mask, 2) /= nlay) then
+          error_msg = "sw_fluxes_allsky: cloud_mask inconsistently sized"
+          return
+        end if
+        allocate(mask(ncol, nlay))
+        mask = cloud_mask
+        if (size(mask) > 0) mask_c = c_loc(mask(1, 1))
+      end if
+      allocate(upc(ncol, nlay + 1), dnc(ncol, nlay + 1))
+      dirc_p = c_null_ptr
+      if (present(flux_dir_clear)) then
+        allocate(dirc(ncol, nlay + 1))
+        dirc_p = c_loc(dirc(1, 1))
+      end if
+      rc = c_sw_fluxes_clear_allsky(this%handle, int(ncol, c_int), int(nlay, c_int), plev, tlay, int(n, c_int), names, ptr, cs, &
+                                    ls, scalar, merge(1_c_int, 0_c_int, top_at_1), mu0, scale_p, sfc_alb_dir, sfc_alb_dif, &
+                                    int(size(tau_p, 3), c_int), tau_p, ssa_p, g_p, merge(1_c_int, 0_c_int, delta_scale), &
+                                    mask_c, up, dn, dir_p, upc, dnc, dirc_p, ECCKD_HOST, c_null_ptr)
+      if (rc == 0) then
+        flux_up_clear = upc
+        flux_dn_clear = dnc
+        if (present(flux_dir_clear)) flux_dir_clear = dirc
+      end if
+    else if (present(cloud_mask)) then
       if (size(cloud_mask, 1) /= ncol .or. size(cloud_mask, 2) /= nlay) then
         error_msg = "sw_fluxes_allsky: cloud_mask inconsistently sized"
         return
