@@ -634,6 +634,10 @@ int ecckd_get_arithmetic(void);
  *   "lw_inc_flux_isotropic"  0: I_dn(top) = inc_flux/(2 pi w_k) per angle (default);
  *                            1: inc_flux/pi (flux_dn(top) == inc_flux with any number of angles)
  *   "sw_k_floor"             k = sqrt(max((gamma1-gamma2)(gamma1+gamma2), sw_k_floor)), default 1e-12
+ *                            (the single-precision solvers, unless it is set to 1e-6 or more, bound a cell of optical
+ *                            depth tau by min(1e-6, 1e-4 / tau^2) instead: at 1e-12 float resolves nothing of a
+ *                            conservative layer, ssa == 1 -- fluxes 8-12 W m-2 off, with the bound within 0.01 W m-2;
+ *                            ecckd_get_solver_option reports the option as it was set)
  *   "sw_dir_clamp"           1: Rdir = max(0,min(Rdir,1-Tnoscat)), Tdir = max(0,min(Tdir,1-Tnoscat-Rdir))
  *                            (v1.6+); 0: no clamp (default)
  * Implementation choices through the same call (results agree to ~1e-16 relative; bench.py prints them too):

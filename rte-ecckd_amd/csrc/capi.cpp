@@ -1395,6 +1395,9 @@ int ecckd_rte_lw_inc_flux_f32(int device, int ncol, int nlay, int ngpt, int top_
                      dp(flux_up), dp(flux_dn), memspace, stream);
 }
 
+static const double kSwKFloorF32 = 1.e-6;      // lower bound of "sw_k_floor" in the single-precision shortwave solvers ...
+static const double kSwKFloorTauF32 = 1.e-4;   // ... which a cell of optical depth tau lowers to this / tau^2 (k tau = 1e-2)
+
 static int rte_sw_impl(const Call &c, int device, int ncol, int nlay, int ngpt, int top_at_1, const double *tau,
                        const double *ssa, const double *g, const double *mu0, const double *toa_flux, int nband,
                        const int *band2gpt, const double *sfc_alb_dir, const double *sfc_alb_dif, double *flux_up,
@@ -1412,6 +1415,15 @@ static int rte_sw_impl(const Call &c, int device, int ncol, int nlay, int ngpt, 
   a.k_floor = g_opt.sw_k_floor.load();
   // (fast arithmetic mode: sw_sqrt() of sw_two_stream.hpp takes normal numbers; a subnormal floor changes nothing a flux can show)
   if (!a.exact_division && a.k_floor < 2.2250738585072014e-308) a.k_floor = 2.2250738585072014e-308;
+  // single precision: a conservative layer (ssa == 1, as float rounds anything above 1 - 3e-8) sits on the floor, and with
+  // k = 1e-6 float keeps no digit of 1 - exp(-2 k tau): fluxes 8-12 W m-2 from the solution of the k = 0 equations.
+  // Rounding costs about eps / (k tau) of a cell's reflectance, the floor (k tau)^2 / 12: what counts is k tau, and 5e-3 to
+  // 1e-2 serves both (tests/test_gpu_solver_truth.py: 0.01 W m-2 for tau <= 5 with k^2 = 1e-6).  A constant 1e-6 would reach
+  // too far in thick cells: (g1-g2)(g1+g2) = 2 (1-w) (2 - w/2 - 1.5 w g) is below it for 1 - w < 3.4e-7 at g = 0 but for
+  // 1 - w < 2.2e-6 at g = 0.85, and raising k of three cloud layers of tau = 100, ssa = 1 - 1e-6, g = 0.85 from 6.7e-4 to 1e-3
+  // moves the fluxes by 9.5 W m-2 (measured in fp64 with that floor).  So the bound of a cell is min(1e-6, 1e-4 / tau^2): 1e-6
+  // up to tau = 10, k tau = 1e-2 beyond.  A "sw_k_floor" of 1e-6 or more holds in every cell as it is set.
+  if (c.f32 && a.k_floor < kSwKFloorF32) { a.k_floor = kSwKFloorF32; a.k_floor_tau = kSwKFloorTauF32; }
   a.dir_clamp = g_opt.sw_dir_clamp.load();
   a.f32 = c.f32;
   const SwDerive *dv = c.derive;

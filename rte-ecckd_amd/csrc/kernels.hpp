@@ -147,6 +147,7 @@ struct RteSwArgs {
   int exact_division;          // 1 (reference-order arithmetic mode): IEEE `/`; 0: reciprocal + Newton steps
   // version switches (ecckd_set_solver_option)
   double k_floor;              // lower bound of (gamma1-gamma2)(gamma1+gamma2) under the square root (1e-12)
+  double k_floor_tau = 0.;     // > 0 (single precision, default floor): a cell's bound is min(k_floor, k_floor_tau / tau^2)
   int dir_clamp;               // 1: Rdir/Tdir energy clamps of later RTE-RRTMGP releases
   // tail split (rte_sw_tail_plan): tiles from tail_first on are solved one g-point group per wave; -1: none
   long tail_first = -1;

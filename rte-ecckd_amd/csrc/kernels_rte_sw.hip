@@ -111,6 +111,7 @@ __device__ __forceinline__ void rte_sw_body(const RteSwArgs &a) {
   const int ngroups = (ng + GW - 1) / GW;
   const long ntiles = ((long)ncol + CW - 1) / CW;
   const real k_floor = (real)a.k_floor;
+  const real k_floor_tau = (real)a.k_floor_tau;
   const real gw = (real)a.gw;
 
   // Work units (see rte_sw_tail_plan): units [0, tail_first) are whole tiles; beyond that a unit is ONE g-point group
@@ -167,16 +168,16 @@ __device__ __forceinline__ void rte_sw_body(const RteSwArgs &a) {
           const real ts = tau_r + tsp, tau12 = ctau + tp;      // increment_2stream_by_2stream
           const real cg = (tsp * pp.g) / (ts > eps ? ts : eps);
           const real cssa = ts / (tau12 > eps ? tau12 : eps);
-          return two_stream<real, FAST, CLAMP, false>(tau12, cssa, cg, mu0, mu0_inv, k_floor);
+          return two_stream<real, FAST, CLAMP, false>(tau12, cssa, cg, mu0, mu0_inv, k_floor, k_floor_tau);
         }
         else if constexpr (DERIVE) {
           const real moles = (y - x) * gw;                     // :313-314
           const real cssa = (moles * ray) / ctau;              // :316, :459-460 (IEEE division in every mode)
-          return two_stream<real, FAST, CLAMP, true>(ctau, cssa, real(0), mu0, mu0_inv, k_floor);   // g = 0
+          return two_stream<real, FAST, CLAMP, true>(ctau, cssa, real(0), mu0, mu0_inv, k_floor, k_floor_tau);   // g = 0
         }
         else
-          return __all(y == real(0)) ? two_stream<real, FAST, CLAMP, true>(ctau, x, y, mu0, mu0_inv, k_floor)
-                                     : two_stream<real, FAST, CLAMP, false>(ctau, x, y, mu0, mu0_inv, k_floor);
+          return __all(y == real(0)) ? two_stream<real, FAST, CLAMP, true>(ctau, x, y, mu0, mu0_inv, k_floor, k_floor_tau)
+                                     : two_stream<real, FAST, CLAMP, false>(ctau, x, y, mu0, mu0_inv, k_floor, k_floor_tau);
       };
 
       // ---- pass 1, bottom -> top: two-stream coefficients (sw_two_stream) and the adding

@@ -186,6 +186,7 @@ __device__ __forceinline__ void rte_sw_sys_body(const RteSwArgs &a) {
   real *slot_u = hand + (((long)w * 2 + 0) * 64 + lane) * 2, *slot_d = hand + (((long)w * 2 + 1) * 64 + lane) * 2;
   real *slot_u_above = slot_u - 4 * 64, *slot_d_below = slot_d + 4 * 64;
   const real k_floor = (real)a.k_floor;
+  const real k_floor_tau = (real)a.k_floor_tau;
   const real gw = (real)a.gw;
   double *my_up = acc_up + s0 * 64 + lane, *my_dn = acc_dn + s0 * 64 + lane, *my_dir = acc_dir + s0 * 64 + lane;
 
@@ -307,13 +308,13 @@ __device__ __forceinline__ void rte_sw_sys_body(const RteSwArgs &a) {
             const real tsc = moles[l] * ray + tsp, tau12 = ptau[l] + tp;   // increment_2stream_by_2stream
             cg = (tsp * ppg[l]) / (tsc > eps ? tsc : eps);
             cssa = tsc / (tau12 > eps ? tau12 : eps);
-            put(l, two_stream<real, FAST, CLAMP, false>(tau12, cssa, cg, mu0, mu0_inv, k_floor));
+            put(l, two_stream<real, FAST, CLAMP, false>(tau12, cssa, cg, mu0, mu0_inv, k_floor, k_floor_tau));
           } else {
           if (DERIVE) { cssa = (moles[l] * ray) / ptau[l]; cg = real(0); }   // :316, :459-460
           else { cssa = pssa[l]; cg = pg[l]; }
           const TwoStreamT<real> ts = (DERIVE || __all(cg == real(0)))
-                                          ? two_stream<real, FAST, CLAMP, true>(ptau[l], cssa, cg, mu0, mu0_inv, k_floor)
-                                          : two_stream<real, FAST, CLAMP, false>(ptau[l], cssa, cg, mu0, mu0_inv, k_floor);
+                                          ? two_stream<real, FAST, CLAMP, true>(ptau[l], cssa, cg, mu0, mu0_inv, k_floor, k_floor_tau)
+                                          : two_stream<real, FAST, CLAMP, false>(ptau[l], cssa, cg, mu0, mu0_inv, k_floor, k_floor_tau);
           put(l, ts);
           }
         }

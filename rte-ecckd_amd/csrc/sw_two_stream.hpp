@@ -89,7 +89,8 @@ template <> __device__ __forceinline__ float sw_eps<float>() { return 1.19209289
 // operation is exact (x * 1, x + 0, (2 - 0) / 4), so the same bits as the general form for finite mu0 (mu0 = inf or NaN:
 // 3*mu0*0 is NaN in the general form, 0 here -- such a column is NaN through exp(-tau/mu0) / toa*mu0 either way).
 template <typename real, bool FAST, bool CLAMP, bool G0>
-__device__ __forceinline__ TwoStreamT<real> two_stream(real tau, real w0, real gq_in, real mu0, real mu0_inv, real k_floor) {
+__device__ __forceinline__ TwoStreamT<real> two_stream(real tau, real w0, real gq_in, real mu0, real mu0_inv, real k_floor,
+                                                       real k_floor_tau) {
 #include "sw_two_stream_body.inc"
 }
 // (The same body under `#pragma clang fp contract(fast)` -- multiply-add pairs fused, ~20 % fewer fp64 instructions -- was

@@ -9,7 +9,12 @@
   const real alpha1 = gamma1 * gamma4 + gamma2 * gamma3;
   const real alpha2 = G0 ? alpha1 : gamma1 * gamma3 + gamma2 * gamma4;   // (G0: the same products, the sum commutes)
   const real kk0 = (gamma1 - gamma2) * (gamma1 + gamma2);
-  const real k = sw_sqrt<FAST>(kk0 > k_floor ? kk0 : k_floor);   // k_floor = 1e-12 unless ecckd_set_solver_option moved it
+  // k_floor = 1e-12 unless ecckd_set_solver_option moved it.  Single precision with the default (k_floor_tau > 0; capi.cpp,
+  // rte_sw_impl): the bound of a cell is min(k_floor, k_floor_tau / tau^2), at least 1e-12 -- k tau stays at 1e-2 in a thick
+  // cell instead of growing with tau.  (tau = 0 or NaN: k_floor; tau^2 = inf: 1e-12.)
+  real kf = k_floor;
+  if (sizeof(real) == 4 && k_floor_tau > real(0)) kf = fmax(real(1e-12), fmin(k_floor, k_floor_tau / (tau * tau)));
+  const real k = sw_sqrt<FAST>(kk0 > kf ? kk0 : kf);
   const real exp_minusktau = sw_exp<FAST>(-tau * k);
   const real exp_minus2ktau = exp_minusktau * exp_minusktau;
   real RT_term = rcp<FAST>(k * (real(1) + exp_minus2ktau) + gamma1 * (real(1) - exp_minus2ktau));

@@ -77,7 +77,10 @@ def precision_limited_columns(tau, ssa, mu0, toa, above=0.05):
 
 
 def _direct_terms(dt, tau, ssa, mu0):
-    """Rdir, Tdir of sw_two_stream (g = 0) in precision dt."""
+    """Rdir, Tdir of sw_two_stream (g = 0) in precision dt.  (k^2 is floored at 1e-12 in both precisions here; the
+    single-precision solvers floor it at min(1e-6, 1e-4 / tau^2), kSwKFloorF32 of capi.cpp.  That differs only in cells with ssa within
+    1e-7 of 1, which this emulation therefore flags more readily than the solver errs: it only picks the columns that
+    check_f32_bars holds to the wider bar.)"""
     t, w, mu = tau.astype(dt), ssa.astype(dt), mu0.astype(dt)[None, None, :]
     g1, g2 = (dt(8) - w * dt(5)) * dt(.25), dt(3) * w * dt(.25)
     k = np.sqrt(np.maximum((g1 - g2) * (g1 + g2), dt(1e-12)))
