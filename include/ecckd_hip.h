@@ -532,6 +532,73 @@ int ecckd_sw_fluxes_clear_allsky(const ecckd_model_t *model, int ncol, int nlay,
                                  double *flux_up_clear, double *flux_dn_clear, double *flux_dir_clear, int memspace,
                                  void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Longwave surface-temperature Jacobian: the derivative of the upward flux profile with respect to the surface
+ * temperature, RTE-RRTMGP's optional flux_up_Jac(ncol,nlay+1) of rte_lw (from sources%sfc_source_Jac) and, divided by its
+ * surface value, ecRad's lw_derivatives.  A host gets it with the fluxes of the same call instead of calling the fluxes
+ * twice, at tsfc and at tsfc + 1.  fp64.  [Parity with RTE-RRTMGP is unpinned, as for everything else about the solvers.]
+ *
+ *   sfc_source_jac(i,g) = B_g(tsfc(i) + 1) - B_g(tsfc(i)),  B = calculate_planck_function (src/gas_optics_ecckd.f90:275-288,
+ *     the division by the f32 pi included), evaluated with the expressions that give sfc_source: tsfc + 1.0 as one fp64
+ *     addition, two separately rounded Planck values, one fp64 subtraction (RRTMGP's convention: delta_Tsurf = 1 K in
+ *     compute_Planck_source).  Units of sfc_source, per kelvin.
+ *   flux_up_jac(i,lev) = sum_g sum_k 2 pi w_k J_kg(lev):
+ *     at the surface level      J = sfc_emis(band(g), i) * sfc_source_jac(i,g),
+ *     at the level above layer l  J = t_k(l) * J(level below),  t_k(l) = exp(-tau(i,l,g) * D_k),
+ *     with the transmissivity the flux solver forms (the same exp, bit for bit) on the optical depth that sky's solver sees:
+ *     gas only, or gas incremented by the (masked) particles exactly as the flux pass increments it.  Quadrature, 2 pi w_k
+ *     scaling, g-point lanes of weight 0 and layout are those of flux_up: (ncol,nlay+1), indexed by top_at_1.  W m-2 K-1.
+ *     It does not depend on inc_flux, on the layer and level sources, or on "lw_tau_thresh" / "lw_series_terms".
+ *     ecRad's lw_derivatives(lev) = flux_up_jac(lev) / flux_up_jac(surface).
+ *   The solver is linear in its sources, so flux_up_jac is the flux_up of rte_lw with lay_source = lev_source_inc =
+ *   lev_source_dec = 0, no inc_flux and sfc_source = sfc_source_jac (the tests pin it to the oracle's rte_lw run that way).
+ *
+ * ecckd_planck_sfc_source_jac: sfc_source_jac(ncol,ngpt) from tsfc(ncol).  ECCKD_DEVICE: asynchronous on `stream`, no
+ *   scratch; ECCKD_HOST: staged.  Refusals: those of ecckd_planck_sources for its arguments.
+ * ecckd_rte_lw_jac: ecckd_rte_lw_inc_flux (inc_flux may be NULL) plus flux_up_jac.  ECCKD_HOST or ECCKD_DEVICE, any layer
+ *   count.  flux_up / flux_dn are bit for bit those of ecckd_rte_lw_inc_flux with the same arguments (the same solver is
+ *   launched, unchanged); flux_up_jac comes from a kernel of its own that reads tau once.  sfc_source_jac or flux_up_jac
+ *   NULL, or flux_up_jac equal to a flux output, is refused with a message before any launch.  No scratch beyond what
+ *   ecckd_rte_lw takes.
+ * ecckd_lw_fluxes_jac: the superset of the four fused longwave calls.  tau_p NULL (with nband_p 0, ssa_p and cloud_mask
+ *   NULL, no clear-sky outputs): the clear sky of ecckd_lw_fluxes; tau_p given: ecckd_lw_fluxes_allsky (cloud_mask NULL) or
+ *   ecckd_lw_fluxes_allsky_mcica; flux_up_clear and flux_dn_clear given as well: ecckd_lw_fluxes_clear_allsky.  flux_up /
+ *   flux_dn (and flux_*_clear) are BIT FOR BIT what that existing call writes, at every layer count, in both orientations
+ *   and for every value of the solver options: its kernels are launched unchanged.  flux_up_jac is the Jacobian of the sky
+ *   that flux_up holds (the all sky when particles are given); NULL: the existing call and nothing else.
+ *   60 layers, "lw_jac_inline" = 1 (the default): the Jacobian form of the layer-split kernel (rte_lw_split_jac_kernel)
+ *   carries the surface term through the up sweep it runs anyway -- one multiply and one accumulator add per (cell, angle);
+ *   its third accumulator plane leaves room for one group per block, one wave per SIMD.  With the clear-sky outputs the call
+ *   takes the two launches of "lw_both_skies" = 0 and the all-sky launch is the Jacobian form (the dual-sky kernel has none;
+ *   the fluxes are the same bits either way).
+ *   Otherwise ("lw_jac_inline" = 0, any other layer count, a Planck table that does not fit LDS): the stand-alone Jacobian
+ *   kernel runs behind the flux pass(es) on the scratch optical depth and forms sfc_source_jac itself from tsfc and the
+ *   Planck table.  At 60 layers the flux kernel adds the particles as it reads tau and leaves the scratch as gas optics wrote
+ *   it, so the stand-alone kernel reads the band planes and the mask as well and applies them with the flux kernel's
+ *   expressions; at any other layer count it finds tau incremented in place (both skies: behind the second pass).
+ *   The two routes sum the g-points and angles of a level in different orders: they agree to rounding (1e-14 W m-2 K-1).
+ *   Refused in this order: the existing call's list in its order; flux_up_jac equal to another output pointer; nband_p,
+ *   ssa_p, cloud_mask or a clear-sky output without tau_p.
+ *   Scratch (ECCKD_DEVICE): exactly that of the corresponding existing call -- nothing (ncol,ngpt) is staged -- so a
+ *   caller-owned block sized for it serves and the capture rules are unchanged.
+ * Out of scope: single precision; per-band or spectral Jacobians; the Jacobian in ecckd_lw_solver_noscat_gpt /
+ *   librte_kernels_hip; the dual-sky kernel with a Jacobian; ECCKD_MIXED.
+ * --------------------------------------------------------------------------------------- */
+int ecckd_planck_sfc_source_jac(const ecckd_model_t *model, int ncol, const double *tsfc, double *sfc_source_jac, int memspace,
+                                void *stream);
+int ecckd_rte_lw_jac(int device, int ncol, int nlay, int ngpt, int top_at_1, int n_gauss_angles, const double *tau,
+                     const double *lay_source, const double *lev_source_inc, const double *lev_source_dec,
+                     const double *sfc_source, const double *sfc_source_jac, int nband, const int *band2gpt,
+                     const double *sfc_emis, const double *inc_flux, double *flux_up, double *flux_dn, double *flux_up_jac,
+                     int memspace, void *stream);
+int ecckd_lw_fluxes_jac(const ecckd_model_t *model, int ncol, int nlay, const double *plev, const double *tlay,
+                        const double *tsfc, const double *tlev, int ngas, const char *gas_names, const double *const *vmr,
+                        const long long *vmr_col_stride, const long long *vmr_lay_stride, const double *vmr_scalar,
+                        int top_at_1, int n_gauss_angles, const double *sfc_emis, const double *inc_flux, int nband_p,
+                        const double *tau_p, const double *ssa_p, const unsigned long long *cloud_mask, double *flux_up,
+                        double *flux_dn, double *flux_up_clear, double *flux_dn_clear, double *flux_up_jac, int memspace,
+                        void *stream);
+
 /* Spectral (per-band) fluxes: what RTE-RRTMGP callers get by passing a ty_fluxes_byband to rte_lw /
  * rte_sw instead of the ty_fluxes_broadband the reference drivers use (ecckd_rfmip_lw.F90:108-109).
  * bnd_flux_*(ncol,nlay+1,nband) = sum over the g-points of each band (one solver pass per band over its
@@ -668,6 +735,11 @@ int ecckd_get_arithmetic(void);
  *                            one after the other on the same optical depth; 1 (default: 1.09-1.11x faster than 0 at 1e5 columns,
  *                            1.04-1.05x at 1e6) the dual-sky kernel (rte_lw_split_both_kernel: Planck sources once per cell,
  *                            both skies in one pass, one wave per SIMD).  Bit-identical fluxes
+ *   "lw_jac_inline"          ecckd_lw_fluxes_jac at 60 layers: 1 (default: 1.22-1.29x the time of the call without the
+ *                            Jacobian, against 1.33-1.39x for 0, at 1e5 and 1e6 columns) flux_up_jac from the Jacobian form
+ *                            of the layer-split kernel (rte_lw_split_jac_kernel); 0 the flux kernel, then the stand-alone
+ *                            Jacobian kernel on the scratch optical depth.  Bit-identical fluxes; the Jacobians agree to
+ *                            rounding
  *   "gas_merge_scalars"      fast arithmetic mode, fp64: 1 (default) the gases of gas_desc given as ONE number for the call
  *                            (vmr pointer NULL + vmr_scalar; get_vmr broadcasts them, src/gas_optics_ecckd.f90:351) and
  *                            the none_ composite share one table sum_k m_k*coefficient_k, m_k = vmr | vmr - reference | 1,

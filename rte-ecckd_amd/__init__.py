@@ -34,10 +34,11 @@ HOST, DEVICE = 0, 1
 NAME_LEN = 32
 
 _SOURCES = ["kernels_gas_fused.hip", "kernels_tau.hip", "kernels_planck.hip", "kernels_rte_lw.hip", "kernels_rte_lw_split.hip",
+            "kernels_rte_lw_jac.hip",
             "kernels_rte_sw.hip", "kernels_rte_sw_sys.hip", "kernels_rte_gpt.hip", "kernels_optical_props.hip",
             "kernels_cloud_sampling.hip",
             "capi.cpp", "nc_capi.cpp", "model.cpp", "cdf1.cpp"]
-_HEADERS = ["kernels.hpp", "wave_pair.hpp", "sw_two_stream.hpp", "sw_two_stream_body.inc", "lw_layer.hpp", "model.hpp", "cdf1.hpp", os.path.join("..", "..", "include", "ecckd_hip.h"),
+_HEADERS = ["kernels.hpp", "wave_pair.hpp", "sw_two_stream.hpp", "sw_two_stream_body.inc", "lw_layer.hpp", "planck_at.hpp", "model.hpp", "cdf1.hpp", os.path.join("..", "..", "include", "ecckd_hip.h"),
             os.path.join("..", "..", "include", "ecckd_nc.h"), os.path.join("..", "..", "include", "rte_kernels_hip.h")]
 # second library: RTE-RRTMGP's kernel-level bind(C) names over the C ABI of the first (include/rte_kernels_hip.h)
 RTE_KERNELS_LIB = os.path.join(_HERE, "librte_kernels_hip.so")
@@ -196,6 +197,12 @@ def lib():
         L.ecckd_sw_fluxes_clear_allsky.argtypes = ([C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 2 + [C.c_int, C.c_char_p] +
                                                    [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 3 +
                                                    [C.c_int] + [C.c_void_p] * 7 + [C.c_int, C.c_void_p])
+    if hasattr(L, "ecckd_lw_fluxes_jac"):   # (an older build lacks them: tools/bench_lw_jac.py --parent-lib)
+        L.ecckd_planck_sfc_source_jac.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.ecckd_rte_lw_jac.argtypes = [C.c_int] * 6 + [C.c_void_p] * 6 + [C.c_int] + [C.c_void_p] * 6 + [C.c_int, C.c_void_p]
+        L.ecckd_lw_fluxes_jac.argtypes = ([C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_char_p] +
+                                          [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int] +
+                                          [C.c_void_p] * 8 + [C.c_int, C.c_void_p])
     _lib = L
     return L
 
@@ -553,10 +560,10 @@ class OpticalProps2str(OpticalProps1scl):
 
 
 class SourceFuncLW:
-    """``ty_source_func_lw``: lay_source, lev_source_inc, lev_source_dec, sfc_source."""
+    """``ty_source_func_lw``: lay_source, lev_source_inc, lev_source_dec, sfc_source, sfc_source_jac."""
 
     def __init__(self):
-        self.lay_source = self.lev_source_inc = self.lev_source_dec = self.sfc_source = None
+        self.lay_source = self.lev_source_inc = self.lev_source_dec = self.sfc_source = self.sfc_source_jac = None
         self.levels_shared = False   # True after ecckd's gas_optics: one value per level (:419-424)
 
     def alloc(self, ncol, nlay, spectral_desc, like=None):
@@ -566,6 +573,7 @@ class SourceFuncLW:
         self.lev_source_inc = _empty_like_space((ng, nlay, ncol), like)
         self.lev_source_dec = _empty_like_space((ng, nlay, ncol), like)
         self.sfc_source = _empty_like_space((ng, ncol), like)
+        self.sfc_source_jac = _empty_like_space((ng, ncol), like)   # (planck_sfc_source_jac fills it; float64 only)
         return ""
 
 
@@ -799,6 +807,21 @@ class GasOpticsEcckd:
             _ptr(sources.sfc_source, (ng, ncol), "sfc_source"), space, _stream(space))
         return last_error() if rc else ""
 
+    def planck_sfc_source_jac(self, tsfc, sources):
+        """``ecckd_planck_sfc_source_jac``: ``sources.sfc_source_jac`` ``(ngpt, ncol)`` = B(tsfc + 1) - B(tsfc), the
+        surface term of the longwave surface-temperature Jacobian (``rte_lw(..., flux_up_jac=)``).  float64; numpy or
+        device tensors.  Returns the error message ('' = success)."""
+        ncol = int(tsfc.shape[0]) if getattr(tsfc, "ndim", 0) == 1 else -1
+        try:
+            space = _space_of([tsfc, sources.sfc_source_jac])
+            args = (_ptr(tsfc, (ncol,), "tsfc"), _ptr(sources.sfc_source_jac, (self.get_ngpt(), ncol), "sfc_source_jac"))
+        except (TypeError, ValueError) as e:
+            return str(e)
+        if args[0] is None or args[1] is None:
+            return "planck_sfc_source_jac: tsfc and sources.sfc_source_jac are required"
+        rc = lib().ecckd_planck_sfc_source_jac(self._need(), ncol, *args, space, _stream(space))
+        return last_error() if rc else ""
+
     def gas_optics_tau(self, plev, tlay, gas_desc, optical_props):
         """``ecckd_gas_optics_lw_tau``: gas_optical_depth alone (tau only), device tensors."""
         nlay, ncol = tlay.shape
@@ -825,9 +848,47 @@ class GasOpticsEcckd:
                                       _ptr(fluxes.flux_dn, (nlay + 1, ncol), "flux_dn"), space, _stream(space))
         return last_error() if rc else ""
 
-    def lw_fluxes(self, plev, tlay, tsfc, tlev, gas_desc, top_at_1, sfc_emis, fluxes, n_gauss_angles=1, inc_flux=None):
+    def _lw_fluxes_jac(self, plev, tlay, tsfc, tlev, gas_desc, top_at_1, sfc_emis, particles, fluxes, fluxes_clear,
+                       n_gauss_angles, inc_flux, cloud_mask, flux_up_jac):
+        """``ecckd_lw_fluxes_jac`` behind ``lw_fluxes`` / ``lw_fluxes_allsky`` / ``lw_fluxes_clear_allsky`` with
+        ``flux_up_jac``: shape and dtype errors are answered here and never reach the library."""
+        nlay, ncol = tlay.shape
+        ng = self.get_ngpt()
+        ptau = None if particles is None else particles.tau
+        ssa = None if particles is None else getattr(particles, "ssa", None)
+        clear = [] if fluxes_clear is None else [fluxes_clear.flux_up, fluxes_clear.flux_dn]
+        try:
+            space = _space_of([plev, tlay, tsfc, tlev, sfc_emis, inc_flux, fluxes.flux_up, fluxes.flux_dn, flux_up_jac, ptau, ssa] +
+                              clear)
+            n, names, ptrs, cs, ls, sc, keep = self._gas_args(gas_desc, ncol, nlay, space)
+            nbp = 0 if ptau is None else int(ptau.shape[0])
+            shp = (nbp, nlay, ncol)
+            part = (_ptr(ptau, shp, "particles.tau"), _ptr(ssa, shp, "particles.ssa"),
+                    None if cloud_mask is None else _mask_ptr(cloud_mask, nlay, ncol, space))
+            lev = (nlay + 1, ncol)
+            out = (_ptr(fluxes.flux_up, lev, "flux_up"), _ptr(fluxes.flux_dn, lev, "flux_dn"),
+                   None if fluxes_clear is None else _ptr(fluxes_clear.flux_up, lev, "flux_up_clear"),
+                   None if fluxes_clear is None else _ptr(fluxes_clear.flux_dn, lev, "flux_dn_clear"),
+                   _ptr(flux_up_jac, lev, "flux_up_jac"))
+            inp = (_ptr(plev, lev, "plev"), _ptr(tlay, (nlay, ncol), "tlay"), _ptr(tsfc, (ncol,), "tsfc"), _ptr(tlev, lev, "tlev"))
+            emis = (_ptr(sfc_emis, (ncol, self.get_nband()), "sfc_emis"), _ptr(inc_flux, (ng, ncol), "inc_flux"))
+        except KeyError as e:
+            return str(e.args[0])
+        except (TypeError, ValueError) as e:
+            return str(e)
+        rc = lib().ecckd_lw_fluxes_jac(self._need(), ncol, nlay, *inp, n, names, ptrs, cs, ls, sc, int(bool(top_at_1)),
+                                       int(n_gauss_angles), *emis, nbp, *part, *out, space, _stream(space))
+        return last_error() if rc else ""
+
+    def lw_fluxes(self, plev, tlay, tsfc, tlev, gas_desc, top_at_1, sfc_emis, fluxes, n_gauss_angles=1, inc_flux=None,
+                  flux_up_jac=None):
         """``ecckd_lw_fluxes``: gas optics + rte_lw in one call for hosts that only need broadband fluxes (tau in
-        library-owned scratch, sources recomputed in the solver); numpy or device tensors."""
+        library-owned scratch, sources recomputed in the solver); numpy or device tensors.  ``flux_up_jac``
+        ``(nlay+1, ncol)`` float64 (``ecckd_lw_fluxes_jac``): receives the derivative of ``flux_up`` with respect to the
+        surface temperature, W m-2 K-1; the fluxes are the same bits with and without it."""
+        if flux_up_jac is not None:
+            return self._lw_fluxes_jac(plev, tlay, tsfc, tlev, gas_desc, top_at_1, sfc_emis, None, fluxes, None, n_gauss_angles,
+                                       inc_flux, None, flux_up_jac)
         nlay, ncol = tlay.shape
         ng = self.get_ngpt()
         try:
@@ -844,14 +905,18 @@ class GasOpticsEcckd:
         return last_error() if rc else ""
 
     def lw_fluxes_allsky(self, plev, tlay, tsfc, tlev, gas_desc, top_at_1, sfc_emis, particles, fluxes, n_gauss_angles=1,
-                         inc_flux=None, cloud_mask=None):
+                         inc_flux=None, cloud_mask=None, flux_up_jac=None):
         """``ecckd_lw_fluxes_allsky``: ``lw_fluxes`` with the combined particulate optical properties ``particles`` on
         the model's bands added to the gas optical depth inside the solver: an ``OpticalProps2str``
         (``alloc_2str_bands``; absorption optical depth ``tau*(1 - ssa)``, its ``g`` is ignored) or an
         ``OpticalProps1scl`` (``alloc_1scl_bands``; ``tau`` as it is).  ``particles`` is never written.  float64, fast
         arithmetic mode; numpy or device tensors.  ``cloud_mask`` ``(nlay, ncol)`` (``sample_cloud_mask``;
         ``ecckd_lw_fluxes_allsky_mcica``): a g-point whose bit is clear sees no particles in that layer.
-        Returns the error message ('' = success)."""
+        ``flux_up_jac`` ``(nlay+1, ncol)`` (``ecckd_lw_fluxes_jac``): the surface-temperature Jacobian of the all-sky
+        ``flux_up``.  Returns the error message ('' = success)."""
+        if flux_up_jac is not None:
+            return self._lw_fluxes_jac(plev, tlay, tsfc, tlev, gas_desc, top_at_1, sfc_emis, particles, fluxes, None,
+                                       n_gauss_angles, inc_flux, cloud_mask, flux_up_jac)
         nlay, ncol = tlay.shape
         ng = self.get_ngpt()
         ssa = getattr(particles, "ssa", None)
@@ -880,7 +945,8 @@ class GasOpticsEcckd:
         """``ecckd_lw_fluxes_clear_allsky``: one gas-optics pass, then both skies -- ``fluxes_clear`` receives what
         ``lw_fluxes`` writes and ``fluxes`` what ``lw_fluxes_allsky(..., cloud_mask=cloud_mask)`` writes, bit for bit.
         ``particles`` and ``cloud_mask`` as for ``lw_fluxes_allsky``; neither is written.  float64, fast arithmetic mode;
-        numpy or device tensors.  Returns the error message ('' = success)."""
+        numpy or device tensors.  Returns the error message ('' = success).  With the surface-temperature Jacobian:
+        ``lw_fluxes_clear_allsky_jac``."""
         nlay, ncol = tlay.shape
         ng = self.get_ngpt()
         ssa = getattr(particles, "ssa", None)
@@ -905,6 +971,16 @@ class GasOpticsEcckd:
             int(n_gauss_angles), _ptr(sfc_emis, (ncol, self.get_nband()), "sfc_emis"), _ptr(inc_flux, (ng, ncol), "inc_flux"),
             nbp, *part, *out, space, _stream(space))
         return last_error() if rc else ""
+
+    def lw_fluxes_clear_allsky_jac(self, plev, tlay, tsfc, tlev, gas_desc, top_at_1, sfc_emis, particles, fluxes, fluxes_clear,
+                                   flux_up_jac, n_gauss_angles=1, inc_flux=None, cloud_mask=None):
+        """``lw_fluxes_clear_allsky`` plus ``flux_up_jac`` ``(nlay+1, ncol)`` float64 (``ecckd_lw_fluxes_jac``): the
+        surface-temperature Jacobian of the all-sky ``flux_up``.  (A method of its own: the argument list of
+        ``lw_fluxes_clear_allsky`` is fixed.)  Every flux array holds the bits ``lw_fluxes_clear_allsky`` writes."""
+        if flux_up_jac is None:
+            return "lw_fluxes_clear_allsky_jac: flux_up_jac is required"
+        return self._lw_fluxes_jac(plev, tlay, tsfc, tlev, gas_desc, top_at_1, sfc_emis, particles, fluxes, fluxes_clear,
+                                   n_gauss_angles, inc_flux, cloud_mask, flux_up_jac)
 
     def sw_fluxes_clear_allsky(self, plev, tlay, gas_desc, top_at_1, mu0, sfc_alb_dir, sfc_alb_dif, particles, fluxes,
                                fluxes_clear, delta_scale=True, toa_scale=None, cloud_mask=None):
@@ -1055,17 +1131,41 @@ def _increment(op1, op2, band2gpt, cloud_mask=None):
 
 
 def rte_lw(optical_props, top_at_1, sources, sfc_emis, fluxes, n_gauss_angles=1, device=None,
-           shared_levels=False, inc_flux=None):
+           shared_levels=False, inc_flux=None, flux_up_jac=None):
     """``rte_lw(optical_props, top_at_1, sources, sfc_emis(nband,ncol), fluxes, n_gauss_angles=)``
     (ecckd_rfmip_lw.F90:130-135).  ``sfc_emis`` is ``(ncol, nband)`` in numpy order.  float32 arrays
     take the single-precision entry point.  ``shared_levels=True`` asserts that the level sources hold
     one value per level (``sources.levels_shared``, set by ecckd's gas_optics) and takes
     ``ecckd_rte_lw_shared_levels`` (fp64 only).  ``inc_flux`` ``(ngpt, ncol)``: incident diffuse flux at the
-    top of the domain (rte_lw's optional argument; ``ecckd_rte_lw_inc_flux`` / ``_f32``, generic solver)."""
+    top of the domain (rte_lw's optional argument; ``ecckd_rte_lw_inc_flux`` / ``_f32``, generic solver).
+    ``flux_up_jac`` ``(nlay+1, ncol)`` float64 (rte_lw's optional ``flux_up_Jac``; ``ecckd_rte_lw_jac``): receives the
+    derivative of ``flux_up`` with respect to the surface temperature from ``sources.sfc_source_jac``
+    (``GasOpticsEcckd.planck_sfc_source_jac``); the fluxes are those of the call without it, bit for bit."""
     ng, nlay, ncol = optical_props.tau.shape
     b2g = np.ascontiguousarray(optical_props.band2gpt, dtype=np.int32)
     nband = b2g.shape[0]
     f32 = _is_f32(optical_props.tau)
+    if flux_up_jac is not None:
+        if f32 or shared_levels or isinstance(fluxes, FluxesByband):
+            return "rte_lw: flux_up_jac is implemented for float64 broadband fluxes of the generic solver"
+        if sources.sfc_source_jac is None:
+            return "rte_lw: flux_up_jac needs sources.sfc_source_jac (planck_sfc_source_jac)"
+        try:
+            space = _space_of([optical_props.tau, sources.lay_source, sources.sfc_source_jac, sfc_emis, inc_flux, fluxes.flux_up,
+                               fluxes.flux_dn, flux_up_jac])
+            a3 = [_ptr(a, (ng, nlay, ncol), w) for a, w in ((optical_props.tau, "tau"), (sources.lay_source, "lay_source"),
+                                                            (sources.lev_source_inc, "lev_source_inc"),
+                                                            (sources.lev_source_dec, "lev_source_dec"))]
+            a2 = [_ptr(sources.sfc_source, (ng, ncol), "sfc_source"), _ptr(sources.sfc_source_jac, (ng, ncol), "sfc_source_jac")]
+            out = [_ptr(a, (nlay + 1, ncol), w) for a, w in ((fluxes.flux_up, "flux_up"), (fluxes.flux_dn, "flux_dn"),
+                                                             (flux_up_jac, "flux_up_jac"))]
+            emis = [_ptr(sfc_emis, (ncol, nband), "sfc_emis"), _ptr(inc_flux, (ng, ncol), "inc_flux")]
+        except (TypeError, ValueError) as e:
+            return str(e)
+        dev = _device_of(optical_props.tau) if device is None else device
+        rc = lib().ecckd_rte_lw_jac(int(dev), ncol, nlay, ng, int(bool(top_at_1)), int(n_gauss_angles), *a3, *a2, nband,
+                                    C.c_void_p(b2g.ctypes.data), *emis, *out, space, _stream(space))
+        return last_error() if rc else ""
     space = _space_of([optical_props.tau, sources.lay_source, sfc_emis, fluxes.flux_up, fluxes.flux_dn])
     dev = _device_of(optical_props.tau) if device is None else device
     if isinstance(fluxes, FluxesByband):

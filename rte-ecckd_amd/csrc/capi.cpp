@@ -248,6 +248,7 @@ struct SolverOptions {
   // kernel (rte_lw_split_both_kernel); same bits.  1: its min-max range lies below that of 0 at every 60-layer shape and
   // configuration measured (profiles/both_skies.json)
   std::atomic<int> lw_both_skies{1};
+  std::atomic<int> lw_jac_inline{1};   // (the inline form lies wholly below the stand-alone route at every 60-layer shape)
 };
 SolverOptions g_opt;
 
@@ -657,13 +658,17 @@ int ecckd_set_solver_option(const char *name, double value) {
     if (value != 0. && value != 1.) return fail("ecckd_set_solver_option: lw_both_skies must be 0 (two launches) or 1 (dual-sky kernel)");
     g_opt.lw_both_skies.store((int)value);
   }
+  else if (n == "lw_jac_inline") {
+    if (value != 0. && value != 1.) return fail("ecckd_set_solver_option: lw_jac_inline must be 0 (stand-alone Jacobian kernel) or 1 (inside the layer-split kernel)");
+    g_opt.lw_jac_inline.store((int)value);
+  }
   else if (n == "gas_slab_f32") {
     if (value != 0. && value != 1. && value != 2.) return fail("ecckd_set_solver_option: gas_slab_f32 must be 0 (never), 1 (always) or 2 (auto)");
     g_opt.gas_slab_f32.store((int)value);
   }
   else return fail("ecckd_set_solver_option: unknown option '" + n + "' (lw_tau_thresh, lw_series_terms, "
                    "lw_inc_flux_isotropic, sw_k_floor, sw_dir_clamp, lw_solver, lw_split_seg, gas_merge_scalars, lw_tail_split, "
-                   "sw_tail_split, sw_solver, gas_slab_f32, lw_both_skies)");
+                   "sw_tail_split, sw_solver, gas_slab_f32, lw_both_skies, lw_jac_inline)");
   return 0;
 }
 
@@ -683,6 +688,7 @@ int ecckd_get_solver_option(const char *name, double *value) {
   else if (n == "sw_solver") *value = g_opt.sw_solver.load();
   else if (n == "gas_slab_f32") *value = g_opt.gas_slab_f32.load();
   else if (n == "lw_both_skies") *value = g_opt.lw_both_skies.load();
+  else if (n == "lw_jac_inline") *value = g_opt.lw_jac_inline.load();
   else return fail("ecckd_get_solver_option: unknown option '" + n + "'");
   return 0;
 }
@@ -1026,6 +1032,35 @@ int ecckd_planck_sources(const ecckd_model_t *m, int ncol, int nlay, const doubl
   if (ncol == 0) return 0;
   const PlanckSide pl{tlev, tsfc, lay_source, lev_source_inc, lev_source_dec, sfc_source};
   return planck_sources_dev(m, ncol, nlay, tlay, pl, static_cast<hipStream_t>(stream));
+}
+
+int ecckd_planck_sfc_source_jac(const ecckd_model_t *m, int ncol, const double *tsfc, double *sfc_source_jac, int memspace,
+                                void *stream) {
+  if (check_model(m) || check_gas_optics_dims(ncol, 1)) return 1;
+  if (!m->has_planck) return fail("ecckd_planck_sfc_source_jac: model has no Planck table (shortwave model?)");
+  if (memspace != ECCKD_DEVICE && memspace != ECCKD_HOST) return fail("ecckd_planck_sfc_source_jac: bad memspace (ECCKD_HOST or ECCKD_DEVICE)");
+  if (!tsfc || !sfc_source_jac) return fail("ecckd_planck_sfc_source_jac: null argument");
+  HIPCHK(hipSetDevice(m->device));
+  if (ncol == 0) return 0;
+  const double t0 = m->temperature_planck[0], dt = m->temperature_planck[1] - m->temperature_planck[0];
+  if (memspace == ECCKD_DEVICE) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    ProfScope prof("planck_sfc_jac", st);
+    HIPCHK(ecckd::launch_planck_sfc_jac(m->dbuf + m->off_planck, m->ng, m->ntp, t0, dt, ncol, tsfc, sfc_source_jac, st));
+    return 0;
+  }
+  ecckd_model *mm = const_cast<ecckd_model *>(m);
+  std::lock_guard<std::mutex> lock(mm->mu);
+  hipStream_t s = mm->host_stream;
+  const size_t nout = (size_t)ncol * m->ng;
+  if (grow_arena(mm, align256((size_t)ncol * 8) + align256(nout * 8))) return 1;
+  Bump b(mm->arena, false);
+  double *d_tsfc = b.take(ncol), *d_out = b.take(nout);
+  if (h2d(d_tsfc, tsfc, ncol, false, s)) return 1;
+  HIPCHK(ecckd::launch_planck_sfc_jac(m->dbuf + m->off_planck, m->ng, m->ntp, t0, dt, ncol, d_tsfc, d_out, s));
+  if (d2h(sfc_source_jac, d_out, nout, false, s)) return 1;
+  HIPCHK(hipStreamSynchronize(s));
+  return 0;
 }
 
 int ecckd_gas_optics_plan(const ecckd_model_t *m, int ncol, int nlay, int single_precision, int ngas,
@@ -1395,6 +1430,60 @@ int ecckd_rte_lw_inc_flux_f32(int device, int ncol, int nlay, int ngpt, int top_
                      dp(flux_up), dp(flux_dn), memspace, stream);
 }
 
+// The Jacobian kernel's arguments for a solver call: the quadrature of fill_lw_options, nothing of the version switches
+static void fill_jac_args(ecckd::RteLwJacArgs &j, int ncol, int nlay, int ngpt, int top_at_1, int n_gauss_angles, int nband) {
+  j.ncol = ncol; j.nlay = nlay; j.ng = ngpt; j.top_at_1 = top_at_1 ? 1 : 0; j.nmus = n_gauss_angles; j.nband = nband;
+  for (int k = 0; k < n_gauss_angles; ++k) {
+    j.Ds[k] = kGaussDs[n_gauss_angles - 1][k];
+    j.wts[k] = kGaussWts[n_gauss_angles - 1][k];
+  }
+}
+
+int ecckd_rte_lw_jac(int device, int ncol, int nlay, int ngpt, int top_at_1, int n_gauss_angles, const double *tau,
+                     const double *lay_source, const double *lev_source_inc, const double *lev_source_dec,
+                     const double *sfc_source, const double *sfc_source_jac, int nband, const int *band2gpt,
+                     const double *sfc_emis, const double *inc_flux, double *flux_up, double *flux_dn, double *flux_up_jac,
+                     int memspace, void *stream) {
+  // the refusals of ecckd_rte_lw_inc_flux that need no device, then this call's own, all before the first launch
+  if (check_dims(ncol, nlay)) return 1;
+  if (n_gauss_angles < 1 || n_gauss_angles > 4) return fail("rte_lw: have to ask for at least one quadrature point and no more than 4");
+  if (!tau || !lay_source || !lev_source_inc || !lev_source_dec || !sfc_source || !sfc_emis || !flux_up || !flux_dn)
+    return fail("ecckd_rte_lw: null argument");
+  if (!sfc_source_jac || !flux_up_jac) return fail("ecckd_rte_lw_jac: null argument (sfc_source_jac and flux_up_jac are required)");
+  if (flux_up_jac == flux_up || flux_up_jac == flux_dn) return fail("ecckd_rte_lw_jac: flux_up_jac must not be one of the flux outputs");
+  if (memspace != ECCKD_HOST && memspace != ECCKD_DEVICE) return fail("ecckd_rte_lw_jac: bad memspace (ECCKD_HOST or ECCKD_DEVICE)");
+  ecckd::RteLwJacArgs j{};
+  if (fill_band_map(ngpt, nband, band2gpt, j.gpt2band)) return 1;
+  if (rte_lw_impl(Call{}, device, ncol, nlay, ngpt, top_at_1, n_gauss_angles, tau, lay_source, lev_source_inc, lev_source_dec,
+                  sfc_source, nband, band2gpt, sfc_emis, inc_flux, flux_up, flux_dn, memspace, stream))
+    return 1;
+  if (ncol == 0) return 0;
+  fill_jac_args(j, ncol, nlay, ngpt, top_at_1, n_gauss_angles, nband);
+  const size_t n3 = (size_t)ncol * nlay * ngpt, n2l = (size_t)ncol * (nlay + 1);
+  if (memspace == ECCKD_DEVICE) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    j.tau = tau; j.sfc_source_jac = sfc_source_jac; j.sfc_emis = sfc_emis; j.flux_up_jac = flux_up_jac;
+    ProfScope prof("rte_lw_jac", st);
+    HIPCHK(ecckd::launch_rte_lw_jac(j, nullptr, 0, 0., 1., st));
+    return 0;
+  }
+  // host arrays: staged in the solver arena, which rte_lw_impl has sized for more than this
+  Arena &ar = g_solver_arena[device];
+  std::lock_guard<std::mutex> lock(ar.mu);
+  if (ar.ensure(align256(n3 * 8) + align256((size_t)ncol * ngpt * 8) + align256((size_t)ncol * nband * 8) + align256(n2l * 8))) return 1;
+  Bump b(ar.p, false);
+  hipStream_t s = nullptr;
+  double *d_tau = b.take(n3), *d_sj = b.take((size_t)ncol * ngpt), *d_emis = b.take((size_t)ncol * nband), *d_jac = b.take(n2l);
+  if (h2d(d_tau, tau, n3, false, s) || h2d(d_sj, sfc_source_jac, (size_t)ncol * ngpt, false, s) ||
+      h2d(d_emis, sfc_emis, (size_t)ncol * nband, false, s))
+    return 1;
+  j.tau = d_tau; j.sfc_source_jac = d_sj; j.sfc_emis = d_emis; j.flux_up_jac = d_jac;
+  HIPCHK(ecckd::launch_rte_lw_jac(j, nullptr, 0, 0., 1., s));
+  if (d2h(flux_up_jac, d_jac, n2l, false, s)) return 1;
+  HIPCHK(hipStreamSynchronize(s));
+  return 0;
+}
+
 static const double kSwKFloorF32 = 1.e-6;      // lower bound of "sw_k_floor" in the single-precision shortwave solvers ...
 static const double kSwKFloorTauF32 = 1.e-4;   // ... which a cell of optical depth tau lowers to this / tau^2 (k tau = 1e-2)
 
@@ -1694,10 +1783,12 @@ struct ClearFluxes { double *up, *dn, *dir; };
 // `both` (60-layer route with `pt` only): the dual-sky kernel, clear-sky fluxes to *both and all-sky fluxes to flux_up / flux_dn
 // `pt` (60-layer route only): the band planes the solver adds to tau as it reads it; the general route gets a tau that
 // launch_increment has incremented already
+// `jac_inline` (60-layer route, without `both`): the Jacobian form of the kernel, which stores flux_up_jac there as well
 static int rte_lw_fused_dev(const ecckd_model *m, int ncol, int nlay, int top_at_1, int n_gauss_angles, const double *tau,
                             const double *tlay, const double *tlev, const double *tsfc, const double *sfc_emis,
                             const double *inc_flux, double *flux_up, double *flux_dn, double *scratch, hipStream_t stream,
-                            const LwParticles *pt = nullptr, const ClearFluxes *both = nullptr, bool sources_in_scratch = false) {
+                            const LwParticles *pt = nullptr, const ClearFluxes *both = nullptr, bool sources_in_scratch = false,
+                            double *jac_inline = nullptr) {
   ecckd::RteLwArgs a{};
   if (fill_band_map(m->ng, m->nband, m->band2gpt.data(), a.gpt2band)) return 1;
   a.ncol = ncol; a.nlay = nlay; a.ng = m->ng; a.top_at_1 = top_at_1 ? 1 : 0;
@@ -1710,10 +1801,10 @@ static int rte_lw_fused_dev(const ecckd_model *m, int ncol, int nlay, int top_at
     ProfScope prof("rte_lw_fused", stream);
     HIPCHK(ecckd::launch_rte_lw_planck(a, m->dbuf + m->off_planck, m->ntp, m->temperature_planck[0],
                                        m->temperature_planck[1] - m->temperature_planck[0], tlay, tlev, tsfc, stream,
-                                       both ? both->up : nullptr, both ? both->dn : nullptr));
+                                       both ? both->up : nullptr, both ? both->dn : nullptr, jac_inline));
     return 0;
   }
-  if (both) return fail("ecckd: internal: the dual-sky longwave kernel serves 60 layers only");
+  if (both || jac_inline) return fail("ecckd: internal: the dual-sky and the Jacobian longwave kernels serve 60 layers only");
   // general route (any layer count): sources through scratch, one value per level
   if (!scratch) return fail("ecckd: internal: the fused longwave solver needs scratch for this layer count");
   const size_t n3 = (size_t)ncol * nlay * m->ng;
@@ -1780,9 +1871,10 @@ static int lw_increment_dev(const ecckd_model *m, int ncol, int nlay, double *ta
 static int lw_both_skies_dev(const ecckd_model *m, int ncol, int nlay, int top_at_1, int n_gauss_angles, double *tau,
                              const double *tlay, const double *tlev, const double *tsfc, const double *sfc_emis,
                              const double *inc_flux, double *flux_up, double *flux_dn, double *scratch, hipStream_t stream,
-                             const LwParticles &pt, const ClearFluxes &clr) {
+                             const LwParticles &pt, const ClearFluxes &clr, double *jac_inline = nullptr) {
   const bool fused = fused_lw_kernels_apply(m, nlay);
-  if (fused && g_opt.lw_both_skies.load() == 1)
+  // (jac_inline: the dual-sky kernel has no Jacobian form -- two launches, the all-sky one the Jacobian kernel; same fluxes)
+  if (fused && g_opt.lw_both_skies.load() == 1 && !jac_inline)
     return rte_lw_fused_dev(m, ncol, nlay, top_at_1, n_gauss_angles, tau, tlay, tlev, tsfc, sfc_emis, inc_flux, flux_up, flux_dn,
                             scratch, stream, &pt, &clr);
   if (rte_lw_fused_dev(m, ncol, nlay, top_at_1, n_gauss_angles, tau, tlay, tlev, tsfc, sfc_emis, inc_flux, clr.up, clr.dn, scratch,
@@ -1790,24 +1882,57 @@ static int lw_both_skies_dev(const ecckd_model *m, int ncol, int nlay, int top_a
     return 1;
   if (!fused && lw_increment_dev(m, ncol, nlay, tau, pt, stream)) return 1;
   return rte_lw_fused_dev(m, ncol, nlay, top_at_1, n_gauss_angles, tau, tlay, tlev, tsfc, sfc_emis, inc_flux, flux_up, flux_dn,
-                          scratch, stream, &pt, nullptr, !fused);
+                          scratch, stream, &pt, nullptr, !fused, jac_inline);
+}
+
+// ecckd_lw_fluxes_jac: where the Jacobian goes (in the memory space of the call; null: none), and whether the call named
+// particles, a mask or clear-sky outputs without tau_p (refused behind the existing call's list)
+struct LwJac { double *jac; bool stray; };
+
+// flux_up_jac behind the flux pass(es) of a fused call, from the scratch tau: the stand-alone Jacobian kernel with the
+// surface term formed from tsfc and the Planck table.  On the 60-layer route the flux kernel has added the particles as it
+// read tau, so the Jacobian kernel does the same (`pt`); on the general route tau was incremented in place.
+static int lw_jac_dev(const ecckd_model *m, int ncol, int nlay, int top_at_1, int n_gauss_angles, const double *tau,
+                      const double *tsfc, const double *sfc_emis, const LwParticles *pt, double *jac, hipStream_t stream) {
+  ecckd::RteLwJacArgs j{};
+  if (fill_band_map(m->ng, m->nband, m->band2gpt.data(), j.gpt2band)) return 1;
+  fill_jac_args(j, ncol, nlay, m->ng, top_at_1, n_gauss_angles, m->nband);
+  j.tau = tau; j.tsfc = tsfc; j.sfc_emis = sfc_emis; j.flux_up_jac = jac;
+  if (pt && fused_lw_kernels_apply(m, nlay)) { j.part_tau = pt->tau; j.part_ssa = pt->ssa; j.part_mask = pt->mask; }
+  ProfScope prof("rte_lw_jac", stream);
+  HIPCHK(ecckd::launch_rte_lw_jac(j, m->dbuf + m->off_planck, m->ntp, m->temperature_planck[0],
+                                  m->temperature_planck[1] - m->temperature_planck[0], stream));
+  return 0;
+}
+
+static int lw_jac_aliased(const double *jac, const double *flux_up, const double *flux_dn, const ClearFluxes *clr) {
+  if (jac && (jac == flux_up || jac == flux_dn || (clr && (jac == clr->up || jac == clr->dn))))
+    return fail("ecckd_lw_fluxes_jac: flux_up_jac must not be another output (it needs an array of its own)");
+  return 0;
 }
 
 static int lw_fluxes_impl(const ecckd_model_t *m, int ncol, int nlay, const double *plev, const double *tlay, const double *tsfc,
                           const double *tlev, int ngas, const char *gas_names, const double *const *vmr,
                           const long long *vmr_col_stride, const long long *vmr_lay_stride, const double *vmr_scalar, int top_at_1,
                           int n_gauss_angles, const double *sfc_emis, const double *inc_flux, double *flux_up, double *flux_dn,
-                          int memspace, void *stream, const LwParticles *pt = nullptr, const ClearFluxes *clr = nullptr) {
+                          int memspace, void *stream, const LwParticles *pt = nullptr, const ClearFluxes *clr = nullptr,
+                          const LwJac *jx = nullptr) {
   if (check_model(m) || check_gas_optics_dims(ncol, nlay)) return 1;
   if (!m->has_planck) return fail("ecckd_lw_fluxes: model has no Planck table (shortwave model?)");
   if (n_gauss_angles < 1 || n_gauss_angles > 4) return fail("rte_lw: have to ask for at least one quadrature point and no more than 4");
   if (!plev || !tlay || !tsfc || !sfc_emis || !flux_up || !flux_dn || (ngas > 0 && !gas_names)) return fail("ecckd_lw_fluxes: null argument");
   if (!tlev) return fail("tlev is required for ecckd");
   if (g_arith.load() != 0) return fail("ecckd_lw_fluxes: needs the fast arithmetic mode (ecckd_set_arithmetic(0))");
+  double *jac = jx ? jx->jac : nullptr;
+  if (lw_jac_aliased(jac, flux_up, flux_dn, clr)) return 1;   // (the all-sky forms have answered this already)
+  if (jx && jx->stray)
+    return fail("ecckd_lw_fluxes_jac: nband_p, cloud_mask and the clear-sky outputs belong to particles: without tau_p they must be 0 / null");
   HIPCHK(hipSetDevice(m->device));
   if (ncol == 0) return 0;
   const GasDesc gd{ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar};
   const size_t n2 = (size_t)ncol * nlay, n2l = (size_t)ncol * (nlay + 1), n3 = n2 * m->ng;
+  // the Jacobian inside the 60-layer flux kernel ("lw_jac_inline" = 1), or from the stand-alone kernel behind the flux pass
+  const bool jac_in = jac && fused_lw_kernels_apply(m, nlay) && g_opt.lw_jac_inline.load() == 1;
   if (memspace == ECCKD_DEVICE) {
     hipStream_t st = static_cast<hipStream_t>(stream);
     void *tau_p = nullptr;   // tau lives in the stream's scratch block between the two kernels
@@ -1817,11 +1942,18 @@ static int lw_fluxes_impl(const ecckd_model_t *m, int ncol, int nlay, const doub
     double *d_tau = static_cast<double *>(tau_p);
     if (gas_optical_depth_dev(m, false, nullptr, ncol, nlay, plev, tlay, gd, d_tau, false, nullptr, nullptr, nullptr, nullptr, st)) return 1;
     double *d_extra = extra ? d_tau + ((n3 + 31) & ~(size_t)31) : nullptr;
-    if (clr) return lw_both_skies_dev(m, ncol, nlay, top_at_1, n_gauss_angles, d_tau, tlay, tlev, tsfc, sfc_emis, inc_flux, flux_up,
-                                      flux_dn, d_extra, st, *pt, *clr);
-    if (pt && !fused_lw_kernels_apply(m, nlay) && lw_increment_dev(m, ncol, nlay, d_tau, *pt, st)) return 1;
-    return rte_lw_fused_dev(m, ncol, nlay, top_at_1, n_gauss_angles, d_tau, tlay, tlev, tsfc, sfc_emis, inc_flux, flux_up,
-                            flux_dn, d_extra, st, pt);
+    if (clr) {
+      if (lw_both_skies_dev(m, ncol, nlay, top_at_1, n_gauss_angles, d_tau, tlay, tlev, tsfc, sfc_emis, inc_flux, flux_up,
+                            flux_dn, d_extra, st, *pt, *clr, jac_in ? jac : nullptr))
+        return 1;
+    } else {
+      if (pt && !fused_lw_kernels_apply(m, nlay) && lw_increment_dev(m, ncol, nlay, d_tau, *pt, st)) return 1;
+      if (rte_lw_fused_dev(m, ncol, nlay, top_at_1, n_gauss_angles, d_tau, tlay, tlev, tsfc, sfc_emis, inc_flux, flux_up,
+                           flux_dn, d_extra, st, pt, nullptr, false, jac_in ? jac : nullptr))
+        return 1;
+    }
+    // (both skies, general route: behind the second solver pass, on the tau that pass saw)
+    return jac && !jac_in ? lw_jac_dev(m, ncol, nlay, top_at_1, n_gauss_angles, d_tau, tsfc, sfc_emis, pt, jac, st) : 0;
   }
   if (memspace != ECCKD_HOST) return fail("ecckd: bad memspace");
   ecckd_model *mm = const_cast<ecckd_model *>(m);
@@ -1830,11 +1962,11 @@ static int lw_fluxes_impl(const ecckd_model_t *m, int ncol, int nlay, const doub
   const size_t need = align256(n2l * 8) * 4 + align256(n2 * 8) + align256((size_t)ncol * 8) + staged_gas_bytes(gd, ncol, nlay, false) +
                       align256((size_t)ncol * m->nband * 8) + align256((size_t)ncol * m->ng * 8) + align256(n3 * 8) +
                       align256(fused_scratch_doubles(m, ncol, nlay) * 8) + (pt ? align256(n2 * m->nband * 8) * (pt->ssa ? 2 : 1) : 0) +
-                      (pt && pt->mask ? align256(n2 * 8) : 0) + (clr ? align256(n2l * 8) * 2 : 0);
+                      (pt && pt->mask ? align256(n2 * 8) : 0) + (clr ? align256(n2l * 8) * 2 : 0) + (jac ? align256(n2l * 8) : 0);
   if (grow_arena(mm, need)) return 1;
   Bump b(mm->arena, false);
   double *d_plev = b.take(n2l), *d_tlev = b.take(n2l), *d_tlay = b.take(n2), *d_tsfc = b.take(ncol);
-  double *d_upc = clr ? b.take(n2l) : nullptr, *d_dnc = clr ? b.take(n2l) : nullptr;
+  double *d_upc = clr ? b.take(n2l) : nullptr, *d_dnc = clr ? b.take(n2l) : nullptr, *d_jac = jac ? b.take(n2l) : nullptr;
   double *d_up = b.take(n2l), *d_dn = b.take(n2l), *d_emis = b.take((size_t)ncol * m->nband), *d_incf = b.take((size_t)ncol * m->ng);
   if (h2d(d_plev, plev, n2l, false, s) || h2d(d_tlay, tlay, n2, false, s) || h2d(d_tsfc, tsfc, ncol, false, s) ||
       h2d(d_tlev, tlev, n2l, false, s) || h2d(d_emis, sfc_emis, (size_t)ncol * m->nband, false, s))
@@ -1860,14 +1992,19 @@ static int lw_fluxes_impl(const ecckd_model_t *m, int ncol, int nlay, const doub
   if (gas_optical_depth_dev(m, false, nullptr, ncol, nlay, d_plev, d_tlay, sg.gd, d_tau, false, nullptr, nullptr, nullptr, nullptr, s)) return 1;
   if (clr) {
     if (lw_both_skies_dev(m, ncol, nlay, top_at_1, n_gauss_angles, d_tau, d_tlay, d_tlev, d_tsfc, d_emis, inc_flux ? d_incf : nullptr,
-                          d_up, d_dn, d_extra, s, dp_, ClearFluxes{d_upc, d_dnc, nullptr}))
+                          d_up, d_dn, d_extra, s, dp_, ClearFluxes{d_upc, d_dnc, nullptr}, jac_in ? d_jac : nullptr))
       return 1;
     if (d2h(clr->up, d_upc, n2l, false, s) || d2h(clr->dn, d_dnc, n2l, false, s)) return 1;
   } else {
     if (pt && !fused_lw_kernels_apply(m, nlay) && lw_increment_dev(m, ncol, nlay, d_tau, dp_, s)) return 1;
     if (rte_lw_fused_dev(m, ncol, nlay, top_at_1, n_gauss_angles, d_tau, d_tlay, d_tlev, d_tsfc, d_emis,
-                         inc_flux ? d_incf : nullptr, d_up, d_dn, d_extra, s, pt ? &dp_ : nullptr))
+                         inc_flux ? d_incf : nullptr, d_up, d_dn, d_extra, s, pt ? &dp_ : nullptr, nullptr, false,
+                         jac_in ? d_jac : nullptr))
       return 1;
+  }
+  if (jac) {
+    if (!jac_in && lw_jac_dev(m, ncol, nlay, top_at_1, n_gauss_angles, d_tau, d_tsfc, d_emis, pt ? &dp_ : nullptr, d_jac, s)) return 1;
+    if (d2h(jac, d_jac, n2l, false, s)) return 1;
   }
   if (d2h(flux_up, d_up, n2l, false, s) || d2h(flux_dn, d_dn, n2l, false, s)) return 1;
   HIPCHK(hipStreamSynchronize(s));
@@ -1892,7 +2029,7 @@ static int lw_fluxes_allsky_impl(const ecckd_model_t *m, int ncol, int nlay, con
                                  const double *vmr_scalar, int top_at_1, int n_gauss_angles, const double *sfc_emis,
                                  const double *inc_flux, int nband_p, const double *tau_p, const double *ssa_p,
                                  const unsigned long long *cloud_mask, double *flux_up, double *flux_dn, int memspace,
-                                 void *stream, const ClearFluxes *clr = nullptr) {
+                                 void *stream, const ClearFluxes *clr = nullptr, const LwJac *jx = nullptr) {
   if (!m) return fail("ecckd: null model");
   if (cloud_mask && m->ng > 64) return fail("ecckd_lw_fluxes_allsky_mcica" + std::string(kMaskTooWide) + std::to_string(m->ng));
   if (nband_p != m->nband)
@@ -1908,9 +2045,10 @@ static int lw_fluxes_allsky_impl(const ecckd_model_t *m, int ncol, int nlay, con
     if (clr->up == flux_up || clr->up == flux_dn || clr->dn == flux_up || clr->dn == flux_dn)
       return fail("ecckd_lw_fluxes_clear_allsky: a clear-sky output must not be an all-sky output (the two sets of fluxes need arrays of their own)");
   }
+  if (lw_jac_aliased(jx ? jx->jac : nullptr, flux_up, flux_dn, clr)) return 1;   // (before any device is asked for, as the list above)
   const LwParticles pt{tau_p, ssa_p, cloud_mask};
   return lw_fluxes_impl(m, ncol, nlay, plev, tlay, tsfc, tlev, ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar,
-                        top_at_1, n_gauss_angles, sfc_emis, inc_flux, flux_up, flux_dn, memspace, stream, &pt, clr);
+                        top_at_1, n_gauss_angles, sfc_emis, inc_flux, flux_up, flux_dn, memspace, stream, &pt, clr, jx);
 }
 
 int ecckd_lw_fluxes_clear_allsky(const ecckd_model_t *m, int ncol, int nlay, const double *plev, const double *tlay,
@@ -1947,6 +2085,26 @@ int ecckd_lw_fluxes_allsky_mcica(const ecckd_model_t *m, int ncol, int nlay, con
   return lw_fluxes_allsky_impl(m, ncol, nlay, plev, tlay, tsfc, tlev, ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride,
                                vmr_scalar, top_at_1, n_gauss_angles, sfc_emis, inc_flux, nband_p, tau_p, ssa_p, cloud_mask, flux_up,
                                flux_dn, memspace, stream);
+}
+
+// The superset of the four fused longwave calls, with flux_up_jac of the sky that flux_up holds (include/ecckd_hip.h)
+int ecckd_lw_fluxes_jac(const ecckd_model_t *m, int ncol, int nlay, const double *plev, const double *tlay, const double *tsfc,
+                        const double *tlev, int ngas, const char *gas_names, const double *const *vmr,
+                        const long long *vmr_col_stride, const long long *vmr_lay_stride, const double *vmr_scalar, int top_at_1,
+                        int n_gauss_angles, const double *sfc_emis, const double *inc_flux, int nband_p, const double *tau_p,
+                        const double *ssa_p, const unsigned long long *cloud_mask, double *flux_up, double *flux_dn,
+                        double *flux_up_clear, double *flux_dn_clear, double *flux_up_jac, int memspace, void *stream) {
+  const bool clear_out = flux_up_clear || flux_dn_clear;
+  if (!tau_p) {   // the clear sky of ecckd_lw_fluxes
+    const LwJac jx{flux_up_jac, nband_p != 0 || ssa_p || cloud_mask || clear_out};
+    return lw_fluxes_impl(m, ncol, nlay, plev, tlay, tsfc, tlev, ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar,
+                          top_at_1, n_gauss_angles, sfc_emis, inc_flux, flux_up, flux_dn, memspace, stream, nullptr, nullptr, &jx);
+  }
+  const LwJac jx{flux_up_jac, false};
+  const ClearFluxes clr{flux_up_clear, flux_dn_clear, nullptr};
+  return lw_fluxes_allsky_impl(m, ncol, nlay, plev, tlay, tsfc, tlev, ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride,
+                               vmr_scalar, top_at_1, n_gauss_angles, sfc_emis, inc_flux, nband_p, tau_p, ssa_p, cloud_mask, flux_up,
+                               flux_dn, memspace, stream, clear_out ? &clr : nullptr, &jx);
 }
 
 // ---- fused shortwave: total optical depth only between the kernels (SURVEY 8(f) rank 4 for the shortwave) ----

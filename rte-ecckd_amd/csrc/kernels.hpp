@@ -136,6 +136,28 @@ struct RteLwArgs {
   const unsigned long long *part_mask = nullptr;
 };
 
+// Longwave surface-temperature Jacobian (kernels_rte_lw_jac.hip): flux_up_jac(ncol,nlay+1) from tau, the surface term and
+// the quadrature of the flux solver.  The surface term is sfc_source_jac(ncol,ng), or -- null -- formed in the kernel from
+// tsfc(ncol) and the model's Planck table.  part_tau / part_ssa / part_mask: as in RteLwArgs (the fused 60-layer route,
+// where the flux kernel adds the particles as it reads tau); null: tau is the optical depth the solver saw.
+struct RteLwJacArgs {
+  int ncol, nlay, ng, top_at_1, nmus;
+  double Ds[4], wts[4];
+  const double *tau;
+  const double *sfc_source_jac, *tsfc;
+  const double *sfc_emis;      // (nband,ncol)
+  int nband;
+  unsigned char gpt2band[256]; // 0-based band of each g-point
+  const double *part_tau = nullptr, *part_ssa = nullptr;
+  const unsigned long long *part_mask = nullptr;
+  double *flux_up_jac;
+  int lev_chunk = 0;           // (set by the launcher) levels whose accumulators one block holds in LDS
+};
+hipError_t launch_rte_lw_jac(const RteLwJacArgs &a, const double *planck, int ntp, double t0, double dt, hipStream_t s);
+// sfc_source_jac(ncol,ng) = B(tsfc + 1) - B(tsfc) from the model's table planck(ng,ntp)
+hipError_t launch_planck_sfc_jac(const double *planck, int ng, int ntp, double t0, double dt, int ncol, const double *tsfc,
+                                 double *sfc_source_jac, hipStream_t s);
+
 struct RteSwArgs {
   int ncol, nlay, ng, top_at_1;
   const double *tau, *ssa, *g, *mu0, *toa;
@@ -262,9 +284,10 @@ hipError_t launch_rte_lw_split(const RteLwArgs &a, hipStream_t s);
 // model's table planck(ng,ntp) (a.lay_source / lev_source_* / sfc_source are not read)
 // flux_up_clear / flux_dn_clear (both or neither; with a.part_tau): the dual-sky kernel, which walks the clear sky and the
 // all sky in one pass and stores the clear-sky fluxes there
+// flux_up_jac (without the clear-sky outputs): the Jacobian form, which also stores the surface-temperature Jacobian of flux_up
 hipError_t launch_rte_lw_planck(const RteLwArgs &a, const double *planck, int ntp, double t0, double dt, const double *tlay,
                                 const double *tlev, const double *tsfc, hipStream_t s, double *flux_up_clear = nullptr,
-                                double *flux_dn_clear = nullptr);
+                                double *flux_dn_clear = nullptr, double *flux_up_jac = nullptr);
 hipError_t launch_rte_sw(const RteSwArgs &a, hipStream_t s);
 // layer-systolic shortwave solver (kernels_rte_sw_sys.hip): any precision, nlay <= 60
 bool rte_sw_sys_applies(const RteSwArgs &a);

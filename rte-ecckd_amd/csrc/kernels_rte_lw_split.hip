@@ -20,6 +20,7 @@
 
 #include "kernels.hpp"
 #include "lw_layer.hpp"
+#include "planck_at.hpp"
 
 namespace ecckd {
 namespace {
@@ -51,32 +52,6 @@ __device__ __forceinline__ void acc_add(double *p, double v, bool owner) {
   __hip_atomic_fetch_add(p, owner ? v : 0., __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 
-// Planck source of one temperature for one g-point (calculate_planck_function, :275-288), table rows from
-// global memory (59 KB: L1/L2 resident).  tp0 = temperature_planck(1), rdt = 1/(temperature_planck(2)-(1)).
-struct PlanckTab { const double *tab; double t0, dt, rdt; int ntp, ng; };
-// `tab` / `stride`: the table the rows are read from -- the model's (ng,ntp) table in global memory (stride ng), or the
-// block's copy in LDS whose rows are padded to an odd number of doubles: the 32 columns of a wave sit in different
-// (neighbouring) rows, and with a stride of 32 doubles they would all hit the same two banks.
-__device__ __forceinline__ double planck_at(const PlanckTab &P, const double *tab, int stride, double T, int g, double pi, double rpi) {
-  double ti = (T - P.t0) * P.rdt;
-  {   // exact quotient (Markstein) so that the row and the weights are the reference's
-    const double rem = fma(-ti, P.dt, T - P.t0);
-    ti = fma(rem, P.rdt, ti);
-  }
-  double v;
-  if (ti >= 0.) {
-    ti = 1. + ti;
-    const int it0 = ti >= (double)(P.ntp - 1) ? P.ntp - 1 : (int)ti;
-    const double w1 = ti - it0, w0 = 1. - w1;
-    const double *r = tab + (it0 - 1) * stride + g;
-    v = w0 * r[0] + w1 * r[stride];
-  } else {
-    v = (T / P.t0) * tab[g];
-  }
-  const double q = v * rpi;   // correctly rounded v / pi
-  return fma(fma(-q, pi, v), rpi, q);
-}
-
 // NG tile groups of NW waves per block.  The Planck-recomputing form runs two groups per block (8 waves) that share one
 // copy of the Planck table in LDS (61-68 KB): read from global memory instead, the two dependent table loads per source
 // leave the kernel latency-bound at its two waves per SIMD (measured 21 ms per 1e6 columns against 11 from LDS).
@@ -101,19 +76,28 @@ __host__ __device__ constexpr int planck_stride(int ng) { return ng | 1; }   // 
 // flux_dn_clear.  The second exchange and accumulator set takes the LDS of the second group, and the block's four waves
 // sit one per SIMD with the whole register file.  Each sky's per-cell expressions and the order in which a level's
 // accumulator receives its g-points are those of the single-sky kernels: the fluxes are theirs bit for bit.
-template <int SEG, int NW, int CW, bool SHARED, bool SER3, bool PLANCK, int SKY, bool MASK = false, bool BOTH = false>
+// JAC (PLANCK forms; rte_lw_split_jac_kernel, ecckd_lw_fluxes_jac with "lw_jac_inline" = 1): the surface-temperature
+// Jacobian of flux_up next to the fluxes.  Its surface term eps * (B(tsfc + 1) - B(tsfc)) is folded through the
+// transmissivities of the waves below (x[(q*3+0)...], already exchanged) and carried through the up sweep with the T[s] the
+// sweep holds in registers: one multiply and one accumulator add per (cell, angle).  The third accumulator plane
+// ([NL+1][CW], 15.6 KB) does not fit next to two groups and the Planck table, so this form runs one group per block and
+// one wave per SIMD like the dual-sky form (59.1 KB + the table).  The flux expressions and the order in which a level's
+// flux accumulators receive their g-points are untouched: the fluxes are the single-sky kernels' bit for bit.
+template <int SEG, int NW, int CW, bool SHARED, bool SER3, bool PLANCK, int SKY, bool MASK = false, bool BOTH = false, bool JAC = false>
 __device__ __forceinline__ void rte_lw_split_body(const RteLwArgs &a, const PlanckTab &pt, const double *tlay, const double *tlev,
                                                   const double *tsfc, [[maybe_unused]] double *flux_up_clear = nullptr,
-                                                  [[maybe_unused]] double *flux_dn_clear = nullptr) {
+                                                  [[maybe_unused]] double *flux_dn_clear = nullptr,
+                                                  [[maybe_unused]] double *flux_up_jac = nullptr) {
   static_assert(SKY == 0 || PLANCK, "the all-sky form extends the Planck-recomputing solver");
   static_assert(SKY != 0 || !MASK, "a cloud mask belongs to the all-sky form");
   static_assert(SKY != 0 || !BOTH, "the dual-sky form extends the all-sky form");
+  static_assert(!JAC || (PLANCK && !BOTH), "the Jacobian form extends the single-sky Planck-recomputing solver");
   constexpr int GW = 64 / CW;
   constexpr int NL = SEG * NW;
-  constexpr int NG = BOTH ? 1 : split_groups(PLANCK);
+  constexpr int NG = (BOTH || JAC) ? 1 : split_groups(PLANCK);
   constexpr int kSplitPF = split_pf(PLANCK);
   constexpr int kSkyDoubles = 2 * (NL + 1) * CW + 2 * NW * 3 * 64;   // accumulators and exchange of one sky
-  constexpr int kGroupDoubles = (BOTH ? 2 : 1) * kSkyDoubles;
+  constexpr int kGroupDoubles = (BOTH ? 2 : 1) * kSkyDoubles + (JAC ? (NL + 1) * CW : 0);
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int grp = (tid >> 6) / NW, w = (tid >> 6) % NW, gtid = tid - grp * 64 * NW;
@@ -122,6 +106,7 @@ __device__ __forceinline__ void rte_lw_split_body(const RteLwArgs &a, const Plan
   double *xch = acc_up + (NL + 1) * CW;                                            // [2][NW][3][64]
   // BOTH: the clear sky's set behind the all sky's, laid out alike
   [[maybe_unused]] double *acc_dn_c = acc_dn + kSkyDoubles, *acc_up_c = acc_up + kSkyDoubles, *xch_c = xch + kSkyDoubles;
+  [[maybe_unused]] double *acc_jac = acc_dn + kSkyDoubles;   // JAC: [NL+1][CW] behind the exchange
   [[maybe_unused]] const int pstride = PLANCK ? planck_stride(a.ng) : 0;
   [[maybe_unused]] double *ptab = reinterpret_cast<double *>(lds_raw) + NG * kGroupDoubles;   // PLANCK: [ntp][pstride]
   if (PLANCK) {
@@ -148,6 +133,8 @@ __device__ __forceinline__ void rte_lw_split_body(const RteLwArgs &a, const Plan
   for (int i = gtid; i < 2 * (NL + 1) * CW; i += 64 * NW) acc_dn[i] = 0.;
   if (BOTH)
     for (int i = gtid; i < 2 * (NL + 1) * CW; i += 64 * NW) acc_dn_c[i] = 0.;
+  if (JAC)
+    for (int i = gtid; i < (NL + 1) * CW; i += 64 * NW) acc_jac[i] = 0.;
   __syncthreads();
 
   // every group of the block walks the same number of tiles (block barriers inside): a group whose tile lies beyond the
@@ -322,6 +309,16 @@ __device__ __forceinline__ void rte_lw_split_body(const RteLwArgs &a, const Plan
         if (q == w) Uin = U;
         U = x[(q * 3 + 0) * 64 + lane] * U + x[(q * 3 + 2) * 64 + lane];
       }
+      [[maybe_unused]] double J = 0.;   // JAC: d(intensity) / d(tsfc) entering this segment from below
+      if (JAC) {
+        double Jq = eps * (planck_at(pt, ptab, pstride, tsfc[cc] + 1., gg, pi_f32, rpi_f32) - sfc_src);
+        J = Jq;
+#pragma unroll
+        for (int q = NW - 1; q >= 0; --q) {
+          if (q == w) J = Jq;
+          Jq = x[(q * 3 + 0) * 64 + lane] * Jq;
+        }
+      }
       // down sweep of the segment: levels s0 .. s0+SEG-1 (the level above each layer); the last wave adds the surface
       I = Iin;
 #pragma unroll
@@ -336,8 +333,13 @@ __device__ __forceinline__ void rte_lw_split_body(const RteLwArgs &a, const Plan
       for (int s = SEG - 1; s >= 0; --s) {
         acc_add(&acc_up[(s0 + s + 1) * CW + cl], gsum<CW>(wfac * U), owner);
         U = T[s] * U + SU[s];
+        if (JAC) {
+          acc_add(&acc_jac[(s0 + s + 1) * CW + cl], gsum<CW>(wfac * J), owner);
+          J = T[s] * J;
+        }
       }
       if (w == 0) acc_add(&acc_up[cl], gsum<CW>(wfac * U), owner);
+      if (JAC && w == 0) acc_add(&acc_jac[cl], gsum<CW>(wfac * J), owner);
       if (BOTH) {   // phase 2 once more, on the clear sky's composites into the clear sky's accumulators
         double Ic = Itop, Iinc = Itop;
 #pragma unroll
@@ -382,9 +384,11 @@ __device__ __forceinline__ void rte_lw_split_body(const RteLwArgs &a, const Plan
           flux_dn_clear[q] = acc_dn_c[i];
           flux_up_clear[q] = acc_up_c[i];
         }
+        if (JAC) flux_up_jac[q] = acc_jac[i];
       }
       acc_dn[i] = 0.;
       acc_up[i] = 0.;
+      if (JAC) acc_jac[i] = 0.;
       if (BOTH) {
         acc_dn_c[i] = 0.;
         acc_up_c[i] = 0.;
@@ -425,6 +429,30 @@ __global__ void __launch_bounds__(64 * NW, 1) rte_lw_split_both_kernel(const Rte
                                                                        const double *tlev, const double *tsfc,
                                                                        double *flux_up_clear, double *flux_dn_clear) {
   rte_lw_split_body<SEG, NW, CW, false, SER3, true, TWOSTR ? 2 : 1, MASK, true>(a, pt, tlay, tlev, tsfc, flux_up_clear, flux_dn_clear);
+}
+
+// The Jacobian form (JAC of rte_lw_split_body): the fluxes of the clear-sky (SKY = 0), all-sky or McICA kernel and
+// flux_up_jac from one pass, one group per block and one wave per SIMD.
+template <int SEG, int NW, int CW, bool SER3, int SKY, bool MASK>
+__global__ void __launch_bounds__(64 * NW, 1) rte_lw_split_jac_kernel(const RteLwArgs a, const PlanckTab pt, const double *tlay,
+                                                                      const double *tlev, const double *tsfc, double *flux_up_jac) {
+  rte_lw_split_body<SEG, NW, CW, false, SER3, true, SKY, MASK, false, true>(a, pt, tlay, tlev, tsfc, nullptr, nullptr, flux_up_jac);
+}
+
+template <int SEG, int NW, int CW, bool SER3, int SKY, bool MASK>
+hipError_t launch_split_jac(const RteLwArgs &a, const PlanckTab &pt, const double *tlay, const double *tlev, const double *tsfc,
+                            double *flux_up_jac, hipStream_t s) {
+  auto k = rte_lw_split_jac_kernel<SEG, NW, CW, SER3, SKY, MASK>;
+  // one group: two flux accumulator planes and the exchange, the Jacobian's plane, the Planck table
+  const size_t lds = sizeof(double) * (3 * (size_t)(SEG * NW + 1) * CW + 2 * NW * 3 * 64 + (size_t)pt.ntp * planck_stride(a.ng));
+  if (lds > (size_t)kLdsBudget) return hipErrorInvalidValue;
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (e != hipSuccess) return e;
+  long blocks = ((long)a.ncol + CW - 1) / CW;
+  const long cap = 256L * 4;   // one block is resident per CU (its LDS); the rest by grid stride, as launch_split_both
+  if (blocks > cap) blocks = cap;
+  hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(64 * NW), lds, s, a, pt, tlay, tlev, tsfc, flux_up_jac);
+  return hipGetLastError();
 }
 
 template <int SEG, int NW, int CW, bool SER3, bool TWOSTR, bool MASK>
@@ -530,11 +558,30 @@ static hipError_t launch_both(const RteLwArgs &a, const PlanckTab &pt, const dou
              : launch_split_both<15, 4, 32, SER3, false, false>(a, pt, tlay, tlev, tsfc, up_c, dn_c, s);
 }
 
+template <bool SER3>
+static hipError_t launch_jac_inline(const RteLwArgs &a, const PlanckTab &pt, const double *tlay, const double *tlev, const double *tsfc,
+                                    double *jac, hipStream_t s) {
+  if (!a.part_tau) return launch_split_jac<15, 4, 32, SER3, 0, false>(a, pt, tlay, tlev, tsfc, jac, s);
+  const bool two = !(a.part_1scl || !a.part_ssa);
+  if (a.part_mask) {
+    if (a.ng > 64) return hipErrorInvalidValue;
+    return two ? launch_split_jac<15, 4, 32, SER3, 2, true>(a, pt, tlay, tlev, tsfc, jac, s)
+               : launch_split_jac<15, 4, 32, SER3, 1, true>(a, pt, tlay, tlev, tsfc, jac, s);
+  }
+  return two ? launch_split_jac<15, 4, 32, SER3, 2, false>(a, pt, tlay, tlev, tsfc, jac, s)
+             : launch_split_jac<15, 4, 32, SER3, 1, false>(a, pt, tlay, tlev, tsfc, jac, s);
+}
+
 hipError_t launch_rte_lw_planck(const RteLwArgs &a, const double *planck, int ntp, double t0, double dt, const double *tlay,
                                 const double *tlev, const double *tsfc, hipStream_t s, double *flux_up_clear,
-                                double *flux_dn_clear) {
+                                double *flux_dn_clear, double *flux_up_jac) {
   if (a.f32 || a.nlay != 60 || a.ncol <= 0) return hipErrorInvalidValue;
   const PlanckTab pt{planck, t0, dt, 1. / dt, ntp, a.ng};
+  if (flux_up_jac) {   // the Jacobian form (ecckd_lw_fluxes_jac, "lw_jac_inline" = 1); the dual-sky kernel has none
+    if (flux_up_clear || flux_dn_clear) return hipErrorInvalidValue;
+    return a.series3 ? launch_jac_inline<true>(a, pt, tlay, tlev, tsfc, flux_up_jac, s)
+                     : launch_jac_inline<false>(a, pt, tlay, tlev, tsfc, flux_up_jac, s);
+  }
   if (flux_up_clear || flux_dn_clear) {   // the dual-sky kernel (ecckd_lw_fluxes_clear_allsky, "lw_both_skies" = 1)
     if (!flux_up_clear || !flux_dn_clear || !a.part_tau) return hipErrorInvalidValue;
     return a.series3 ? launch_both<true>(a, pt, tlay, tlev, tsfc, flux_up_clear, flux_dn_clear, s)

@@ -2,7 +2,7 @@
 ! example/rfmip-rad-irf/ecckd_rfmip_lw.F90:107-136 and ecckd_rfmip_sw.F90:112-162: load the ecCKD
 ! file, then per column block gas_optics() followed by rte_lw()/rte_sw(), fluxes out.
 !
-!   ecckd_driver lw|sw  <ecckd_file.nc>  <input.bin>  <output.bin>  [block_size] [n_quad_angles] [device_resident 0|1] [repeats] [byband 0|1] [fused 0|1] [particles.bin] [cloudfrac.bin] [clear.bin]
+!   ecckd_driver lw|sw  <ecckd_file.nc>  <input.bin>  <output.bin>  [block_size] [n_quad_angles] [device_resident 0|1] [repeats] [byband 0|1] [fused 0|1] [particles.bin] [cloudfrac.bin] [clear.bin] [jac.bin]
 !
 ! device_resident = 1: optical_props / source are the device twins of mo_ecckd_device (tau and the sources stay in
 ! HBM between gas_optics and the solver; ECCKD_MIXED memory space of the C ABI).
@@ -22,6 +22,10 @@
 !            of the same columns -- the all-sky call is made with flux_up_clear / flux_dn_clear, so both skies come from one
 !            gas-optics pass per block (ecckd_lw_fluxes_clear_allsky / ecckd_sw_fluxes_clear_allsky).  An empty string for
 !            cloudfrac.bin (or any file argument) means "none".
+! jac.bin (longwave, host containers: device_resident = 0): a further output file with flux_up_jac(ncol,nlay+1), the derivative
+!            of flux_up with respect to the surface temperature (W m-2 K-1), in the layout of an array of output.bin.
+!            fused = 1: the fused call of the block is made with flux_up_Jac; fused = 0: ecckd%planck_sfc_source_jac fills
+!            sources%sfc_source_Jac behind gas_optics and rte_lw is called with flux_up_Jac.
 ! byband = 1: fluxes go through ty_fluxes_byband (per-band arrays; their sum over bands must reproduce the broadband
 ! fluxes, which are what output.bin holds either way).
 !
@@ -64,6 +68,10 @@ program ecckd_driver
   character(len=512) :: clear_path
   logical :: both = .false.
   real(wp), dimension(:,:), allocatable :: clear_up, clear_dn
+  character(len=512) :: jac_path
+  logical :: with_jac = .false.
+  real(wp), dimension(:,:), allocatable :: jac_up
+  real(wp), dimension(:,:), allocatable :: jac_b   ! the block's Jacobian; unallocated (= absent) without jac.bin
   integer(int32) :: overlap
   integer(int64) :: seed
   real(wp), dimension(:,:), allocatable :: cloud_frac, overlap_param
@@ -136,6 +144,15 @@ program ecckd_driver
   if (command_argument_count() >= 13) then
     call get_command_argument(13, clear_path)
     both = len_trim(clear_path) > 0
+  end if
+  if (command_argument_count() >= 14) then
+    call get_command_argument(14, jac_path)
+    with_jac = len_trim(jac_path) > 0
+  end if
+  if (with_jac .and. (trim(mode) /= "lw" .or. dev_flag /= 0)) then
+    write(error_unit, "(a)") " ecckd_driver: a Jacobian output file needs the longwave and device_resident = 0"
+    call usage()
+    stop 1
   end if
   if (both .and. .not. (allsky .and. fused /= 0)) then
     write(error_unit, "(a)") " ecckd_driver: a clear-sky output file needs fused = 1 and a particle file (particles.bin)"
@@ -215,6 +232,7 @@ program ecckd_driver
   top_at_1 = play(1, 1) < play(1, nlay)                   ! ecckd_rfmip_lw.F90:85
   allocate(flux_up(ncol, nlay + 1), flux_dn(ncol, nlay + 1))
   if (both) allocate(clear_up(ncol, nlay + 1), clear_dn(ncol, nlay + 1))
+  if (with_jac) allocate(jac_up(ncol, nlay + 1))
   nblocks = (ncol + block_size - 1) / block_size
 
   ! gas concentrations per block, as read_and_block_gases_ty prepares them before the reference's loop
@@ -264,31 +282,39 @@ program ecckd_driver
         call stop_on_err(ecckd%sample_cloud_mask(cloud_frac(c0:c1, :), int(overlap), seed, int(c0 - 1, int64), mask_b))
       end if
     end if
+    if (with_jac) then
+      if (allocated(jac_b)) deallocate(jac_b)
+      allocate(jac_b(nc, nlay + 1))
+    end if
     if (lw .and. both) then
       if (has_ssa_g /= 0) then
         call stop_on_err(ecckd%lw_fluxes_allsky(plev(c0:c1, :), tlay(c0:c1, :), tsfc(c0:c1), tlev(c0:c1, :), gas_concs(b), &
                                                 top_at_1, sfc_spec, tau_p(c0:c1, :, :), flux_up(c0:c1, :), flux_dn(c0:c1, :), &
                                                 ssa_p=ssa_p(c0:c1, :, :), n_gauss_angles=n_quad_angles, cloud_mask=mask_b, &
-                                                flux_up_clear=clear_up(c0:c1, :), flux_dn_clear=clear_dn(c0:c1, :)))
+                                                flux_up_clear=clear_up(c0:c1, :), flux_dn_clear=clear_dn(c0:c1, :), &
+                                                flux_up_Jac=jac_b))
       else
         call stop_on_err(ecckd%lw_fluxes_allsky(plev(c0:c1, :), tlay(c0:c1, :), tsfc(c0:c1), tlev(c0:c1, :), gas_concs(b), &
                                                 top_at_1, sfc_spec, tau_p(c0:c1, :, :), flux_up(c0:c1, :), flux_dn(c0:c1, :), &
                                                 n_gauss_angles=n_quad_angles, cloud_mask=mask_b, &
-                                                flux_up_clear=clear_up(c0:c1, :), flux_dn_clear=clear_dn(c0:c1, :)))
+                                                flux_up_clear=clear_up(c0:c1, :), flux_dn_clear=clear_dn(c0:c1, :), &
+                                                flux_up_Jac=jac_b))
       end if
     else if (lw .and. allsky) then
       if (has_ssa_g /= 0) then
         call stop_on_err(ecckd%lw_fluxes_allsky(plev(c0:c1, :), tlay(c0:c1, :), tsfc(c0:c1), tlev(c0:c1, :), gas_concs(b), &
                                                 top_at_1, sfc_spec, tau_p(c0:c1, :, :), flux_up(c0:c1, :), flux_dn(c0:c1, :), &
-                                                ssa_p=ssa_p(c0:c1, :, :), n_gauss_angles=n_quad_angles, cloud_mask=mask_b))
+                                                ssa_p=ssa_p(c0:c1, :, :), n_gauss_angles=n_quad_angles, cloud_mask=mask_b, &
+                                                flux_up_Jac=jac_b))
       else
         call stop_on_err(ecckd%lw_fluxes_allsky(plev(c0:c1, :), tlay(c0:c1, :), tsfc(c0:c1), tlev(c0:c1, :), gas_concs(b), &
                                                 top_at_1, sfc_spec, tau_p(c0:c1, :, :), flux_up(c0:c1, :), flux_dn(c0:c1, :), &
-                                                n_gauss_angles=n_quad_angles, cloud_mask=mask_b))
+                                                n_gauss_angles=n_quad_angles, cloud_mask=mask_b, flux_up_Jac=jac_b))
       end if
     else if (lw .and. fused /= 0) then
       call stop_on_err(ecckd%lw_fluxes(plev(c0:c1, :), tlay(c0:c1, :), tsfc(c0:c1), tlev(c0:c1, :), gas_concs(b), top_at_1, &
-                                       sfc_spec, flux_up(c0:c1, :), flux_dn(c0:c1, :), n_gauss_angles=n_quad_angles))
+                                       sfc_spec, flux_up(c0:c1, :), flux_dn(c0:c1, :), n_gauss_angles=n_quad_angles, &
+                                       flux_up_Jac=jac_b))
     else if (lw) then
       if (nc /= nc_alloc) then                                 ! (the reference allocates once, before its loop: :102-103)
         call stop_on_err(source%alloc(nc, nlay, ecckd))
@@ -298,8 +324,9 @@ program ecckd_driver
       call stop_on_err(ecckd%gas_optics(play(c0:c1, :), plev(c0:c1, :), tlay(c0:c1, :), tsfc(c0:c1), gas_concs(b), &
                                         op1, source, tlev=tlev(c0:c1, :)))
       ! ecckd level sources hold one value per level (src/gas_optics_ecckd.f90:419-424): each level is read once
+      if (with_jac) call stop_on_err(ecckd%planck_sfc_source_jac(tsfc(c0:c1), source))
       call stop_on_err(rte_lw(op1, top_at_1, source, sfc_spec, fluxes, n_gauss_angles=n_quad_angles, &
-                              lev_sources_shared=.true.))
+                              lev_sources_shared=.true., flux_up_Jac=jac_b))
     else if (fused /= 0) then
       if (allocated(sfc_spec2)) deallocate(sfc_spec2)
       allocate(sfc_spec2(nbnd, nc))
@@ -335,6 +362,7 @@ program ecckd_driver
       call stop_on_err(ecckd%gas_optics(play(c0:c1, :), plev(c0:c1, :), tlay(c0:c1, :), gas_concs(b), op2, toa))
       call stop_on_err(rte_sw(op2, top_at_1, bc1(c0:c1), toa, sfc_spec, sfc_spec2, fluxes))
     end if
+    if (with_jac) jac_up(c0:c1, :) = jac_b
     if (byband /= 0) then
       if (maxval(abs(sum(bnd_up, dim=3) - flux_up(c0:c1, :))) > 1.e-9_wp .or. &
           maxval(abs(sum(bnd_dn, dim=3) - flux_dn(c0:c1, :))) > 1.e-9_wp) &
@@ -355,6 +383,11 @@ program ecckd_driver
     write(u) clear_up, clear_dn
     close(u)
   end if
+  if (with_jac) then
+    open(newunit=u, file=trim(jac_path), access="stream", form="unformatted", status="replace")
+    write(u) jac_up
+    close(u)
+  end if
   call ecckd%finalize()
   write(error_unit, *) "ecckd_driver: ", ncol, " columns in ", nblocks, " blocks done"
 
@@ -363,6 +396,7 @@ contains
     write(error_unit, "(a)") " usage: ecckd_driver lw|sw ecckd_file input.bin output.bin [block_size] [n_quad_angles]"
     write(error_unit, "(a)") "        [device_resident 0|1] [repeats] [byband 0|1] [fused 0|1] [particles.bin] [cloudfrac.bin]"
     write(error_unit, "(a)") "        [clear.bin: clear-sky fluxes of the same columns; needs fused = 1 and particles.bin]"
+    write(error_unit, "(a)") "        [jac.bin: flux_up_jac of the same columns; longwave, device_resident = 0]"
   end subroutine usage
 
   subroutine stop_on_err(msg)                                ! mo_simple_netcdf.F90:331-339

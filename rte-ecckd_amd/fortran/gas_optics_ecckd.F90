@@ -52,6 +52,7 @@ module gas_optics_ecckd
     procedure, public :: get_temp_max
     procedure, public :: gas_optics_int
     procedure, public :: gas_optics_ext
+    procedure, public :: planck_sfc_source_jac   !< extension: sources%sfc_source_Jac = B(tsfc + 1) - B(tsfc)
     procedure, public :: lw_fluxes          !< extension: gas_optics + rte_lw in one call (fused longwave path)
     procedure, public :: sw_fluxes          !< extension: gas_optics + rte_sw in one call (fused shortwave path)
     procedure, public :: lw_fluxes_allsky   !< extension: lw_fluxes with particulate optics on the model's bands
@@ -185,6 +186,33 @@ module gas_optics_ecckd
       type(c_ptr), value :: stream
       integer(c_int) :: rc
     end function c_lw_fluxes
+    function c_planck_sfc_source_jac(model, ncol, tsfc, sfc_source_jac, memspace, stream) &
+        bind(C, name="ecckd_planck_sfc_source_jac") result(rc)
+      import c_ptr, c_int, c_double
+      type(c_ptr), value :: model
+      integer(c_int), value :: ncol, memspace
+      real(c_double), dimension(*), intent(in) :: tsfc
+      real(c_double), dimension(*), intent(inout) :: sfc_source_jac
+      type(c_ptr), value :: stream
+      integer(c_int) :: rc
+    end function c_planck_sfc_source_jac
+    ! the superset of the fused longwave calls with flux_up_jac; tau_p / ssa_p / cloud_mask / the clear-sky outputs may be null
+    function c_lw_fluxes_jac(model, ncol, nlay, plev, tlay, tsfc, tlev, ngas, gas_names, vmr, cs, ls, scalar, top_at_1, nmus, &
+                             sfc_emis, inc_flux, nband_p, tau_p, ssa_p, cloud_mask, flux_up, flux_dn, flux_up_clear, &
+                             flux_dn_clear, flux_up_jac, memspace, stream) bind(C, name="ecckd_lw_fluxes_jac") result(rc)
+      import c_ptr, c_int, c_double, c_char, c_long_long
+      type(c_ptr), value :: model
+      integer(c_int), value :: ncol, nlay, ngas, top_at_1, nmus, nband_p, memspace
+      real(c_double), dimension(*), intent(in) :: plev, tlay, tsfc, tlev, sfc_emis
+      character(kind=c_char), dimension(*), intent(in) :: gas_names
+      type(c_ptr), dimension(*), intent(in) :: vmr
+      integer(c_long_long), dimension(*), intent(in) :: cs, ls
+      real(c_double), dimension(*), intent(in) :: scalar
+      type(c_ptr), value :: inc_flux, tau_p, ssa_p, cloud_mask, flux_up_clear, flux_dn_clear
+      real(c_double), dimension(*), intent(inout) :: flux_up, flux_dn, flux_up_jac
+      type(c_ptr), value :: stream
+      integer(c_int) :: rc
+    end function c_lw_fluxes_jac
     function c_sw_fluxes(model, ncol, nlay, plev, tlay, ngas, gas_names, vmr, cs, ls, scalar, top_at_1, mu0, toa_scale, &
                          sfc_alb_dir, sfc_alb_dif, flux_up, flux_dn, flux_dir, memspace, stream) &
         bind(C, name="ecckd_sw_fluxes") result(rc)
@@ -628,7 +656,9 @@ contains
   !! loop computes with ecckd%gas_optics(...) followed by rte_lw(...) (ecckd_rfmip_lw.F90:120-135) -- through the fused
   !! path of the library (ecckd_lw_fluxes: tau stays on the GPU, the Planck sources are recomputed inside the solver).
   !! Host arrays in, host fluxes out (60 layers take the fused kernels, other counts the general route).  flux_up / flux_dn are (ncol, nlay+1), sfc_emis (nband, ncol).
-  function lw_fluxes(this, plev, tlay, tsfc, tlev, gas_desc, top_at_1, sfc_emis, flux_up, flux_dn, n_gauss_angles) &
+  !! flux_up_Jac (ncol, nlay+1): d(flux_up)/d(surface temperature), W m-2 K-1, from the same call (ecckd_lw_fluxes_jac);
+  !! the fluxes are the same bits with and without it.
+  function lw_fluxes(this, plev, tlay, tsfc, tlev, gas_desc, top_at_1, sfc_emis, flux_up, flux_dn, n_gauss_angles, flux_up_Jac) &
       result(error_msg)
     class(ty_gas_optics_ecckd), intent(in) :: this
     real(wp), dimension(:,:), intent(in) :: plev, tlay, tlev
@@ -638,12 +668,13 @@ contains
     real(wp), dimension(:,:), intent(in) :: sfc_emis
     real(wp), dimension(:,:), intent(inout) :: flux_up, flux_dn
     integer, intent(in), optional :: n_gauss_angles
+    real(wp), dimension(:,:), intent(inout), optional :: flux_up_Jac
     character(len=128) :: error_msg
     character(kind=c_char), dimension(:), allocatable :: names
     type(c_ptr), dimension(:), allocatable :: ptr
     integer(c_long_long), dimension(:), allocatable :: cs, ls
     real(c_double), dimension(:), allocatable :: scalar
-    real(wp), dimension(:,:), allocatable :: up, dn
+    real(wp), dimension(:,:), allocatable :: up, dn, jac
     integer :: ncol, nlay, n, nmus
     integer(c_int) :: rc
     ncol = size(tlay, 1)
@@ -658,9 +689,21 @@ contains
     end if
     n = gas_desc%get_num_gases()
     allocate(up(ncol, nlay + 1), dn(ncol, nlay + 1))
+    if (present(flux_up_Jac)) then
+      if (size(flux_up_Jac, 1) /= ncol .or. size(flux_up_Jac, 2) /= nlay + 1) then
+        error_msg = "lw_fluxes: flux_up_Jac inconsistently sized"
+        return
+      end if
+      allocate(jac(ncol, nlay + 1))
+      rc = c_lw_fluxes_jac(this%handle, int(ncol, c_int), int(nlay, c_int), plev, tlay, tsfc, tlev, int(n, c_int), names, ptr, &
+                           cs, ls, scalar, merge(1_c_int, 0_c_int, top_at_1), int(nmus, c_int), sfc_emis, c_null_ptr, 0_c_int, &
+                           c_null_ptr, c_null_ptr, c_null_ptr, up, dn, c_null_ptr, c_null_ptr, jac, ECCKD_HOST, c_null_ptr)
+      if (rc == 0) flux_up_Jac = jac
+    else
     rc = c_lw_fluxes(this%handle, int(ncol, c_int), int(nlay, c_int), plev, tlay, tsfc, tlev, int(n, c_int), names, ptr, cs, &
                      ls, scalar, merge(1_c_int, 0_c_int, top_at_1), int(nmus, c_int), sfc_emis, c_null_ptr, up, dn, &
                      ECCKD_HOST, c_null_ptr)
+    end if
     if (rc /= 0) then
       error_msg = c_error_message()
       return
@@ -668,6 +711,26 @@ contains
     flux_up = up
     flux_dn = dn
   end function lw_fluxes
+
+  !> Extension: sources%sfc_source_Jac(ncol, ngpt) = B(tsfc + 1) - B(tsfc) (ecckd_planck_sfc_source_jac), the surface term
+  !! of rte_lw's flux_up_Jac: RRTMGP's convention, delta_Tsurf = 1 K.  Host arrays; sources must be allocated (alloc).
+  function planck_sfc_source_jac(this, tsfc, sources) result(error_msg)
+    class(ty_gas_optics_ecckd), intent(in) :: this
+    real(wp), dimension(:), intent(in) :: tsfc
+    class(ty_source_func_lw), intent(inout) :: sources
+    character(len=128) :: error_msg
+    error_msg = ""
+    if (.not. allocated(sources%sfc_source_Jac)) then
+      error_msg = "planck_sfc_source_jac: sources%sfc_source_Jac is not allocated (sources%alloc)"
+      return
+    end if
+    if (size(sources%sfc_source_Jac, 1) /= size(tsfc) .or. size(sources%sfc_source_Jac, 2) /= this%get_ngpt()) then
+      error_msg = "planck_sfc_source_jac: sources%sfc_source_Jac inconsistently sized"
+      return
+    end if
+    if (c_planck_sfc_source_jac(this%handle, int(size(tsfc), c_int), tsfc, sources%sfc_source_Jac, ECCKD_HOST, c_null_ptr) /= 0) &
+      error_msg = c_error_message()
+  end function planck_sfc_source_jac
 
   !> Extension (no counterpart in the reference): broadband shortwave fluxes in one call -- what the reference's block
   !! loop computes with ecckd%gas_optics(...), the rescaling of toa_flux and rte_sw(...) (ecckd_rfmip_sw.F90:118-154) --
@@ -740,8 +803,10 @@ contains
   !! particles in that layer.
   !! flux_up_clear / flux_dn_clear (ncol, nlay+1), both or neither: the clear-sky fluxes of the same columns from the same
   !! gas-optics pass (ecckd_lw_fluxes_clear_allsky) -- what lw_fluxes returns, bit for bit.
+  !! flux_up_Jac (ncol, nlay+1): d(flux_up)/d(surface temperature) of the all sky, W m-2 K-1, from the same call
+  !! (ecckd_lw_fluxes_jac); every flux array holds the same bits with and without it.
   function lw_fluxes_allsky(this, plev, tlay, tsfc, tlev, gas_desc, top_at_1, sfc_emis, tau_p, flux_up, flux_dn, ssa_p, &
-                            n_gauss_angles, cloud_mask, flux_up_clear, flux_dn_clear) result(error_msg)
+                            n_gauss_angles, cloud_mask, flux_up_clear, flux_dn_clear, flux_up_Jac) result(error_msg)
     class(ty_gas_optics_ecckd), intent(in) :: this
     real(wp), dimension(:,:), intent(in) :: plev, tlay, tlev
     real(wp), dimension(:), intent(in) :: tsfc
@@ -754,12 +819,16 @@ contains
     integer, intent(in), optional :: n_gauss_angles
     integer(c_int64_t), dimension(:,:), intent(in), optional :: cloud_mask
     real(wp), dimension(:,:), intent(inout), optional :: flux_up_clear, flux_dn_clear
+    real(wp), dimension(:,:), intent(inout), optional :: flux_up_Jac
     character(len=128) :: error_msg
     character(kind=c_char), dimension(:), allocatable :: names
     type(c_ptr), dimension(:), allocatable :: ptr
     integer(c_long_long), dimension(:), allocatable :: cs, ls
     real(c_double), dimension(:), allocatable :: scalar
-    real(wp), dimension(:,:), allocatable :: up, dn, upc, dnc
+    real(wp), dimension(:,:), allocatable :: up, dn, jac
+    real(wp), dimension(:,:), allocatable, target :: upc, dnc
+    real(wp), dimension(:,:,:), allocatable, target :: taup
+    type(c_ptr) :: upc_c, dnc_c, taup_c
     real(wp), dimension(:,:,:), allocatable, target :: ssa
     integer(c_int64_t), dimension(:,:), allocatable, target :: mask
     type(c_ptr) :: ssa_c, mask_c
@@ -795,7 +864,46 @@ contains
       error_msg = "lw_fluxes_allsky: flux_up_clear and flux_dn_clear go together"
       return
     end if
-    if (present(flux_up_clear)) then   ! both skies from one gas-optics pass
+    if (present(flux_up_Jac)) then   ! the superset call: any of mask and clear-sky outputs, plus the Jacobian
+      if (size(flux_up_Jac, 1) /= ncol .or. size(flux_up_Jac, 2) /= nlay + 1) then
+        error_msg = "lw_fluxes_allsky: flux_up_Jac inconsistently sized"
+        return
+      end if
+      mask_c = c_null_ptr
+      if (present(cloud_mask)) then
+        if (size(cloud_mask, 1) /= ncol .or. size(cloud_mask, 2) /= nlay) then
+          error_msg = "lw_fluxes_allsky: cloud_mask inconsistently sized"
+          return
+        end if
+        allocate(mask(ncol, nlay))
+        mask = cloud_mask
+        if (size(mask) > 0) mask_c = c_loc(mask(1, 1))
+      end if
+      upc_c = c_null_ptr
+      dnc_c = c_null_ptr
+      if (present(flux_up_clear)) then
+        allocate(upc(ncol, nlay + 1), dnc(ncol, nlay + 1))
+        if (size(upc) > 0) then
+          upc_c = c_loc(upc(1, 1))
+          dnc_c = c_loc(dnc(1, 1))
+        end if
+      end if
+      allocate(taup(ncol, nlay, size(tau_p, 3)), jac(ncol, nlay + 1))
+      taup = tau_p
+      taup_c = c_null_ptr
+      if (size(taup) > 0) taup_c = c_loc(taup(1, 1, 1))
+      rc = c_lw_fluxes_jac(this%handle, int(ncol, c_int), int(nlay, c_int), plev, tlay, tsfc, tlev, int(n, c_int), names, ptr, &
+                           cs, ls, scalar, merge(1_c_int, 0_c_int, top_at_1), int(nmus, c_int), sfc_emis, c_null_ptr, &
+                           int(size(tau_p, 3), c_int), taup_c, ssa_c, mask_c, up, dn, upc_c, dnc_c, jac, ECCKD_HOST, &
+                           c_null_ptr)
+      if (rc == 0) then
+        flux_up_Jac = jac
+        if (present(flux_up_clear)) then
+          flux_up_clear = upc
+          flux_dn_clear = dnc
+        end if
+      end if
+    else if (present(flux_up_clear)) then   ! both skies from one gas-optics pass
       mask_c = c_null_ptr
       if (present(cloud_mask)) then
         if (size(cloud_mask, 1) /= ncol .or. size(cloud_mask, 2) /= nlay) then

@@ -12,7 +12,8 @@
 !                          get_band_lims_gpoint), ty_optical_props_arry%tau, _1scl%alloc_1scl,
 !                          _2str%ssa,%g,%alloc_2str    (src/gas_optics_ecckd.f90:346,370,456-460)
 !   mo_source_functions    ty_source_func_lw: lay_source, lev_source_inc, lev_source_dec,
-!                          sfc_source, alloc           (:407-424, ecckd_rfmip_lw.F90:102)
+!                          sfc_source, alloc           (:407-424, ecckd_rfmip_lw.F90:102);
+!                          sfc_source_Jac (RTE-RRTMGP's member; filled by ecckd%planck_sfc_source_jac)
 !   mo_fluxes              ty_fluxes_broadband: flux_up, flux_dn, flux_dn_dir pointers
 !                          (ecckd_rfmip_lw.F90:108-109)
 !   mo_fluxes_byband       ty_fluxes_byband: bnd_flux_up, bnd_flux_dn, bnd_flux_dn_dir (ncol,nlev,nband) on top of
@@ -292,6 +293,7 @@ module mo_source_functions
   type, extends(ty_optical_props), public :: ty_source_func_lw
     real(wp), dimension(:,:,:), allocatable :: lay_source, lev_source_inc, lev_source_dec
     real(wp), dimension(:,:), allocatable :: sfc_source
+    real(wp), dimension(:,:), allocatable :: sfc_source_Jac   !< (ncol, ngpt): B(tsfc + 1) - B(tsfc), for rte_lw's flux_up_Jac
   contains
     procedure, public :: alloc
   end type ty_source_func_lw
@@ -307,8 +309,9 @@ contains
     ngpt = this%get_ngpt()
     if (allocated(this%lay_source)) deallocate(this%lay_source, this%lev_source_inc, this%lev_source_dec, &
                                                this%sfc_source)
+    if (allocated(this%sfc_source_Jac)) deallocate(this%sfc_source_Jac)
     allocate(this%lay_source(ncol, nlay, ngpt), this%lev_source_inc(ncol, nlay, ngpt), &
-             this%lev_source_dec(ncol, nlay, ngpt), this%sfc_source(ncol, ngpt))
+             this%lev_source_dec(ncol, nlay, ngpt), this%sfc_source(ncol, ngpt), this%sfc_source_Jac(ncol, ngpt))
   end function alloc
 end module mo_source_functions
 

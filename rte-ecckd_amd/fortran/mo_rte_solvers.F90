@@ -8,7 +8,7 @@
 !     boundary conditions go in and the fluxes come out);
 !   * fluxes may be ty_fluxes_broadband (what the reference drivers pass) or ty_fluxes_byband (spectral output:
 !     one solver pass per band);
-!   * rte_lw takes RTE-RRTMGP's optional inc_flux(ncol,ngpt) and n_gauss_angles.
+!   * rte_lw takes RTE-RRTMGP's optional inc_flux(ncol,ngpt), n_gauss_angles and flux_up_Jac(ncol,nlay+1).
 module mo_rte_lw
   use, intrinsic :: iso_c_binding
   use mo_rte_kind, only: wp
@@ -44,6 +44,19 @@ module mo_rte_lw
       type(c_ptr), value :: stream
       integer(c_int) :: rc
     end function c_rte_lw
+    function c_rte_lw_jac(device, ncol, nlay, ngpt, top_at_1, nmus, tau, lay_source, lev_inc, lev_dec, sfc_source, &
+                          sfc_source_jac, nband, band2gpt, sfc_emis, inc_flux, flux_up, flux_dn, flux_up_jac, memspace, stream) &
+        bind(C, name="ecckd_rte_lw_jac") result(rc)
+      import c_int, c_double, c_ptr
+      integer(c_int), value :: device, ncol, nlay, ngpt, top_at_1, nmus, nband, memspace
+      type(c_ptr), value :: tau, lay_source, lev_inc, lev_dec, sfc_source   ! host (ECCKD_HOST)
+      real(c_double), dimension(*), intent(in) :: sfc_source_jac, sfc_emis
+      type(c_ptr), value :: inc_flux                                         ! host (ncol,ngpt) or null
+      integer(c_int), dimension(*), intent(in) :: band2gpt
+      real(c_double), dimension(*), intent(inout) :: flux_up, flux_dn, flux_up_jac
+      type(c_ptr), value :: stream
+      integer(c_int) :: rc
+    end function c_rte_lw_jac
     function c_rte_lw_shared(device, ncol, nlay, ngpt, top_at_1, nmus, tau, lay_source, lev_inc, lev_dec, sfc_source, &
                       nband, band2gpt, sfc_emis, flux_up, flux_dn, memspace, stream) &
         bind(C, name="ecckd_rte_lw_shared_levels") result(rc)
@@ -83,7 +96,7 @@ contains
   end function rte_set_solver_option
 
   function rte_lw(optical_props, top_at_1, sources, sfc_emis, fluxes, inc_flux, n_gauss_angles, device, &
-                  lev_sources_shared) result(error_msg)
+                  lev_sources_shared, flux_up_Jac) result(error_msg)
     class(ty_optical_props_arry), intent(in) :: optical_props
     logical, intent(in) :: top_at_1
     class(ty_source_func_lw), intent(in) :: sources
@@ -95,7 +108,12 @@ contains
     !> .true.: lev_source_inc(:,l,:) == lev_source_dec(:,l+1,:), as ecckd's gas_optics writes them
     !> (src/gas_optics_ecckd.f90:419-424); each level is then read once (ecckd_rte_lw_shared_levels)
     logical, optional, intent(in) :: lev_sources_shared
+    !> RTE-RRTMGP's optional output: d(flux_up)/d(surface temperature) (ncol, nlay+1), W m-2 K-1, from
+    !> sources%sfc_source_Jac (ecckd%planck_sfc_source_jac).  Host containers and broadband fluxes; the generic solver
+    !> runs (ecckd_rte_lw_jac), so flux_up / flux_dn are those of the call without lev_sources_shared.
+    real(wp), dimension(:,:), intent(inout), optional :: flux_up_Jac
     character(len=128) :: error_msg
+    real(wp), dimension(:,:), allocatable :: jac
     integer :: ncol, nlay, ngpt, nmus, dev, nband
     logical :: shared, in_place
     integer(c_int) :: rc, memspace
@@ -163,6 +181,10 @@ contains
           error_msg = "rte_lw: inc_flux with per-band fluxes is not implemented"
           return
         end if
+        if (present(flux_up_Jac)) then
+          error_msg = "rte_lw: flux_up_Jac with per-band fluxes is not implemented"
+          return
+        end if
         allocate(bup(ncol, nlay + 1, nband), bdn(ncol, nlay + 1, nband), up(ncol, nlay + 1), dn(ncol, nlay + 1))
         rc = c_rte_lw_byband(int(dev, c_int), int(ncol, c_int), int(nlay, c_int), int(ngpt, c_int), &
                              merge(1_c_int, 0_c_int, top_at_1), int(nmus, c_int), p_tau, p_lay, p_inc, p_dec, p_sfc, &
@@ -180,6 +202,34 @@ contains
     end select
     if (.not. associated(fluxes%flux_up) .or. .not. associated(fluxes%flux_dn)) then
       error_msg = "rte_lw: fluxes%flux_up and fluxes%flux_dn must be associated"
+      return
+    end if
+    if (present(flux_up_Jac)) then
+      if (memspace /= ECCKD_HOST) then
+        error_msg = "rte_lw: flux_up_Jac is implemented for the host containers"
+        return
+      end if
+      if (.not. allocated(sources%sfc_source_Jac)) then
+        error_msg = "rte_lw: flux_up_Jac needs sources%sfc_source_Jac (ecckd%planck_sfc_source_jac)"
+        return
+      end if
+      if (size(sources%sfc_source_Jac, 1) /= ncol .or. size(sources%sfc_source_Jac, 2) /= ngpt .or. &
+          size(flux_up_Jac, 1) /= ncol .or. size(flux_up_Jac, 2) /= nlay + 1) then
+        error_msg = "rte_lw: sfc_source_Jac or flux_up_Jac inconsistently sized"
+        return
+      end if
+      allocate(up(ncol, nlay + 1), dn(ncol, nlay + 1), jac(ncol, nlay + 1))
+      rc = c_rte_lw_jac(int(dev, c_int), int(ncol, c_int), int(nlay, c_int), int(ngpt, c_int), &
+                        merge(1_c_int, 0_c_int, top_at_1), int(nmus, c_int), p_tau, p_lay, p_inc, p_dec, p_sfc, &
+                        sources%sfc_source_Jac, int(nband, c_int), int(optical_props%get_band_lims_gpoint(), c_int), &
+                        sfc_emis, p_incf, up, dn, jac, memspace, c_null_ptr)
+      if (rc /= 0) then
+        error_msg = c_error_message()
+        return
+      end if
+      fluxes%flux_up(:, :) = up
+      fluxes%flux_dn(:, :) = dn
+      flux_up_Jac = jac
       return
     end if
     if (is_contiguous(fluxes%flux_up) .and. is_contiguous(fluxes%flux_dn) .and. size(fluxes%flux_up, 1) == ncol .and. &
