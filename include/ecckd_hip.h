@@ -599,6 +599,71 @@ int ecckd_lw_fluxes_jac(const ecckd_model_t *model, int ncol, int nlay, const do
                         double *flux_dn, double *flux_up_clear, double *flux_dn_clear, double *flux_up_jac, int memspace,
                         void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Two-stream longwave: clouds SCATTER.  Every other longwave route of this library is the no-scattering solver and folds
+ * particles into the optical depth as absorption (tau_gas + tau_p*(1 - ssa_p)).  These calls restate RTE-RRTMGP's
+ * lw_solver_2stream of the v1.5 era [RTE-ext: mo_rte_solver_kernels.F90], the route rte_lw takes on ty_optical_props_2str
+ * with use_2stream = .true.; like every solver here, PARITY WITH RTE-RRTMGP IS UNPINNED: the tests pin
+ * the calls to an independent boundary-value solution of the two-stream equations instead.
+ *   Per (column, g-point), layers counted from the top, D = 1.66:
+ *     level source (memory index j = 1..nlay+1, whatever top_at_1): lev(1) = lev_source_dec(1), lev(nlay+1) =
+ *       lev_source_inc(nlay), lev(j) = sqrt(lev_source_dec(j)*lev_source_inc(j-1)); lay_source is an argument, as in RTE, and
+ *       is NEVER READ (it may be NULL);
+ *     gamma1 = D*(1 - 0.5*ssa*(1 + g)), gamma2 = D*0.5*ssa*(1 - g), k = sqrt(max((gamma1-gamma2)*(gamma1+gamma2), 1e-12)),
+ *       e1 = exp(-tau*k), e2 = e1*e1, RT = 1/(k*(1+e2) + gamma1*(1-e2)), Rdif = RT*gamma2*(1-e2), Tdif = RT*2*k*e1;
+ *     tau > 1e-8: Z = (Bb - Bt)/(tau*(gamma1+gamma2)), src_up = pi*((Z+Bt) - Rdif*(-Z+Bt) - Tdif*(Z+Bb)),
+ *       src_dn = pi*((-Z+Bb) - Rdif*(Z+Bb) - Tdif*(-Z+Bt)) with Bt / Bb the level sources above / below; else both 0;
+ *     surface albedo 1 - sfc_emis, source pi*sfc_emis*sfc_source; adding upwards, fluxes downwards from
+ *       flux_dn(top) = inc_flux (0 without one).  No quadrature: n_gauss_angles is not an argument.
+ *   The two constants (1e-12, 1e-8) are RTE's and have no solver option.  Arithmetic follows ecckd_set_arithmetic as
+ *   ecckd_rte_sw does (mode 1: IEEE division, sqrt, exp in the order above; mode 0: reciprocal, square root and exp of the
+ *   shortwave two-stream kernel).  fp64.  A NaN or inf in one column stays in that column.  An infinite tau gives finite
+ *   fluxes in mode 1 (Z = 0) and NaN fluxes for that column in mode 0 (the fast reciprocal of inf is NaN): mode 0 takes
+ *   finite optical depths.
+ * ecckd_rte_lw_2stream: broadband fluxes (ncol,nlay+1).  tau / ssa / g / lev_source_*(ncol,nlay,ngpt), sfc_source(ncol,ngpt),
+ *   sfc_emis(nband,ncol) and band2gpt as ecckd_rte_lw; ngpt <= 256; inc_flux(ncol,ngpt) or NULL.  ECCKD_DEVICE: asynchronous
+ *   on `stream`; the solver's ring (ecckd_rte_lw_2stream_scratch_bytes) comes from the stream's scratch block, so no
+ *   allocation happens once a (shape, stream) pair has been seen and the capture rules are those of ecckd_rte_sw (one
+ *   call before the capture, or ecckd_set_stream_scratch).  ECCKD_HOST: staged, synchronises.  Refused with a message before
+ *   any launch: a null required pointer, bad sizes, a bad memspace, ECCKD_MIXED.
+ * ecckd_lw_solver_2stream_gpt: RTE's kernel-level interface -- spectral fluxes (ncol,nlay+1,ngpt), sfc_emis / sfc_src /
+ *   inc_flux (ncol,ngpt); IEEE arithmetic; a compatibility kernel (one thread per column and g-point).
+ *   librte_kernels_hip exports it as lw_solver_2stream.
+ * ecckd_rte_lw_2stream_scratch_bytes = 8 * 2*(nlay+1)*64 * min(ceil(ncol/16), 4096): one ring of two level arrays per wave.
+ * ecckd_lw_fluxes_allsky_2stream: ecckd_lw_fluxes_allsky with scattering.  Gas optical depth into stream scratch, the
+ *   Planck sources into scratch, then the solver, which loads the layer's band triple (tau_p, ssa_p, g_p)(ncol,nlay,nband_p)
+ *   -- and the cloud-mask word, cloud_mask(ncol,nlay) or NULL, as ecckd_lw_fluxes_allsky_mcica -- beside the gas optical
+ *   depth and forms the cell's (tau, ssa, g) with the operations of ecckd_increment[_masked] by band on (tau_gas, 0, 0):
+ *   no per-g-point ssa or g exists in memory.  flux_up / flux_dn equal, BIT FOR BIT on finite inputs, the composed route
+ *   ecckd_gas_optics_lw_tau, ecckd_planck_sources, ecckd_increment[_masked] by band on (tau, ssa = 0, g = 0),
+ *   ecckd_rte_lw_2stream.  g_p and ssa_p are required (one-stream particles: ecckd_lw_fluxes_allsky).  Fast arithmetic
+ *   mode; any layer count; ECCKD_DEVICE or ECCKD_HOST.  Refused in this order: cloud_mask with more than 64 g-points;
+ *   nband_p different from the model's; tau_p, ssa_p or g_p NULL; reference-order arithmetic; no Planck table; tlev NULL;
+ *   a host-only model.
+ *   Scratch (ECCKD_DEVICE, from the stream's block), with n3 = ncol*nlay*ngpt and r32() rounding up to a multiple of 32:
+ *     8*(r32(n3) + 3*n3 + r32(ncol*ngpt)) + ecckd_rte_lw_2stream_scratch_bytes(ncol, nlay, ngpt)
+ *   in the order optical depth, the three Planck arrays, surface source, ring.
+ * Out of scope: single precision; per-band and Jacobian outputs; both skies in one call; delta scaling inside the fused
+ *   call (the host calls ecckd_delta_scale on its band triple first); RTE's rescaled no-scattering alternative
+ *   (use_2stream = .false. with two-stream properties); ECCKD_MIXED; a tail split for small calls; a Planck-recomputing
+ *   form of the solver; the Fortran type-bound rte_lw(use_2stream=).
+ * --------------------------------------------------------------------------------------- */
+int ecckd_rte_lw_2stream(int device, int ncol, int nlay, int ngpt, int top_at_1, const double *tau, const double *ssa,
+                         const double *g, const double *lay_source, const double *lev_source_inc, const double *lev_source_dec,
+                         const double *sfc_source, int nband, const int *band2gpt, const double *sfc_emis, const double *inc_flux,
+                         double *flux_up, double *flux_dn, int memspace, void *stream);
+int ecckd_lw_solver_2stream_gpt(int device, int ncol, int nlay, int ngpt, int top_at_1, const double *tau, const double *ssa,
+                                const double *g, const double *lay_source, const double *lev_source_inc,
+                                const double *lev_source_dec, const double *sfc_emis, const double *sfc_src,
+                                const double *inc_flux, double *gpt_flux_up, double *gpt_flux_dn, int memspace, void *stream);
+size_t ecckd_rte_lw_2stream_scratch_bytes(int ncol, int nlay, int ngpt);
+int ecckd_lw_fluxes_allsky_2stream(const ecckd_model_t *model, int ncol, int nlay, const double *plev, const double *tlay,
+                                   const double *tsfc, const double *tlev, int ngas, const char *gas_names,
+                                   const double *const *vmr, const long long *vmr_col_stride, const long long *vmr_lay_stride,
+                                   const double *vmr_scalar, int top_at_1, const double *sfc_emis, const double *inc_flux,
+                                   int nband_p, const double *tau_p, const double *ssa_p, const double *g_p,
+                                   const unsigned long long *cloud_mask, double *flux_up, double *flux_dn, int memspace, void *stream);
+
 /* Spectral (per-band) fluxes: what RTE-RRTMGP callers get by passing a ty_fluxes_byband to rte_lw /
  * rte_sw instead of the ty_fluxes_broadband the reference drivers use (ecckd_rfmip_lw.F90:108-109).
  * bnd_flux_*(ncol,nlay+1,nband) = sum over the g-points of each band (one solver pass per band over its

@@ -1,6 +1,6 @@
 /*
  * rte_kernels_hip.h -- librte_kernels_hip.so: RTE-RRTMGP's solver KERNELS under their own bind(C) names, implemented
- * on the MI355X by librte_ecckd_hip.so (ecckd_lw_solver_noscat_gpt, ecckd_sw_solver_2stream_gpt, ecckd_sum_broadband).
+ * on the MI355X by librte_ecckd_hip.so (ecckd_lw_solver_noscat_gpt, ecckd_lw_solver_2stream_gpt, ecckd_sw_solver_2stream_gpt, ecckd_sum_broadband).
  *
  * What it replaces [RTE-ext -- the library is an un-vendored dependency of the reference (Makefile:19,33;
  * .github/workflows/continuous-integration.yml:98-112), so these signatures are restated from the public v1.5-era
@@ -9,6 +9,9 @@
  *
  *   subroutine lw_solver_noscat_GaussQuad(ncol, nlay, ngpt, top_at_1, nmus, Ds, weights, tau, lay_source,
  *                lev_source_inc, lev_source_dec, sfc_emis, sfc_src, flux_up, flux_dn) bind(C, name="lw_solver_noscat_GaussQuad")
+ *   subroutine lw_solver_2stream(ncol, nlay, ngpt, top_at_1, tau, ssa, g, lay_source, lev_source_inc, lev_source_dec,
+ *                sfc_emis, sfc_src, flux_up, flux_dn) bind(C, name="lw_solver_2stream")   [lay_source is never read;
+ *                declared in rte_kernels_lw_2stream_hip.h, which this header includes]
  *   subroutine sw_solver_2stream(ncol, nlay, ngpt, top_at_1, tau, ssa, g, mu0, sfc_alb_dir, sfc_alb_dif,
  *                flux_up, flux_dn, flux_dir) bind(C, name="sw_solver_2stream")
  *   subroutine sum_broadband(ncol, nlev, ngpt, spectral_flux, broadband_flux) bind(C, name="sum_broadband")
@@ -26,6 +29,7 @@
 #ifndef RTE_KERNELS_HIP_H
 #define RTE_KERNELS_HIP_H
 #include <stdbool.h>
+#include "rte_kernels_lw_2stream_hip.h"   /* lw_solver_2stream (two-stream longwave: clouds scatter) */
 #ifdef __cplusplus
 extern "C" {
 #endif

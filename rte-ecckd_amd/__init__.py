@@ -34,12 +34,13 @@ HOST, DEVICE = 0, 1
 NAME_LEN = 32
 
 _SOURCES = ["kernels_gas_fused.hip", "kernels_tau.hip", "kernels_planck.hip", "kernels_rte_lw.hip", "kernels_rte_lw_split.hip",
-            "kernels_rte_lw_jac.hip",
+            "kernels_rte_lw_jac.hip", "kernels_rte_lw_2str.hip",
             "kernels_rte_sw.hip", "kernels_rte_sw_sys.hip", "kernels_rte_gpt.hip", "kernels_optical_props.hip",
             "kernels_cloud_sampling.hip",
             "capi.cpp", "nc_capi.cpp", "model.cpp", "cdf1.cpp"]
-_HEADERS = ["kernels.hpp", "wave_pair.hpp", "sw_two_stream.hpp", "sw_two_stream_body.inc", "lw_layer.hpp", "planck_at.hpp", "model.hpp", "cdf1.hpp", os.path.join("..", "..", "include", "ecckd_hip.h"),
-            os.path.join("..", "..", "include", "ecckd_nc.h"), os.path.join("..", "..", "include", "rte_kernels_hip.h")]
+_HEADERS = ["kernels.hpp", "wave_pair.hpp", "sw_two_stream.hpp", "sw_two_stream_body.inc", "lw_two_stream.hpp", "lw_layer.hpp", "planck_at.hpp", "model.hpp", "cdf1.hpp", os.path.join("..", "..", "include", "ecckd_hip.h"),
+            os.path.join("..", "..", "include", "ecckd_nc.h"), os.path.join("..", "..", "include", "rte_kernels_hip.h"),
+            os.path.join("..", "..", "include", "rte_kernels_lw_2stream_hip.h")]
 # second library: RTE-RRTMGP's kernel-level bind(C) names over the C ABI of the first (include/rte_kernels_hip.h)
 RTE_KERNELS_LIB = os.path.join(_HERE, "librte_kernels_hip.so")
 _RTE_KERNELS_SRC = "rte_kernels_capi.cpp"
@@ -203,6 +204,14 @@ def lib():
         L.ecckd_lw_fluxes_jac.argtypes = ([C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_char_p] +
                                           [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int] +
                                           [C.c_void_p] * 8 + [C.c_int, C.c_void_p])
+    if hasattr(L, "ecckd_rte_lw_2stream"):   # (an older build lacks them: tools/bench_lw_2stream.py --parent-lib)
+        L.ecckd_rte_lw_2stream.argtypes = [C.c_int] * 5 + [C.c_void_p] * 7 + [C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.c_void_p]
+        L.ecckd_lw_solver_2stream_gpt.argtypes = [C.c_int] * 5 + [C.c_void_p] * 11 + [C.c_int, C.c_void_p]
+        L.ecckd_rte_lw_2stream_scratch_bytes.restype = C.c_size_t
+        L.ecckd_rte_lw_2stream_scratch_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
+        L.ecckd_lw_fluxes_allsky_2stream.argtypes = ([C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_char_p] +
+                                                     [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_void_p, C.c_int] +
+                                                     [C.c_void_p] * 6 + [C.c_int, C.c_void_p])
     _lib = L
     return L
 
@@ -266,6 +275,10 @@ def rte_lw_scratch_bytes(ncol, nlay, ngpt):
 
 def rte_sw_tail_scratch_bytes(ncol, nlay, ngpt, device=0):
     return int(lib().ecckd_rte_sw_tail_scratch_bytes(int(device), int(ncol), int(nlay), int(ngpt)))
+
+
+def rte_lw_2stream_scratch_bytes(ncol, nlay, ngpt):
+    return int(lib().ecckd_rte_lw_2stream_scratch_bytes(int(ncol), int(nlay), int(ngpt)))
 
 
 def rte_lw_tail_scratch_bytes(ncol, nlay, ngpt, n_gauss_angles=1, single_precision=False, device=0):
@@ -904,8 +917,40 @@ class GasOpticsEcckd:
                                    _ptr(fluxes.flux_dn, (nlay + 1, ncol), "flux_dn"), space, _stream(space))
         return last_error() if rc else ""
 
+    def _lw_fluxes_allsky_2stream(self, plev, tlay, tsfc, tlev, gas_desc, top_at_1, sfc_emis, particles, fluxes, n_gauss_angles,
+                                  inc_flux, cloud_mask, flux_up_jac):
+        """``ecckd_lw_fluxes_allsky_2stream`` behind ``lw_fluxes_allsky(..., use_2stream=True)``."""
+        who = "lw_fluxes_allsky(use_2stream=True): "
+        if not isinstance(particles, OpticalProps2str) or particles.g is None:
+            return who + "the particles must be two-stream optical properties on the model's bands, with g (alloc_2str_bands)"
+        if flux_up_jac is not None:
+            return who + "flux_up_jac is not implemented"
+        if n_gauss_angles != 1:
+            return who + "the two-stream solver has no quadrature (n_gauss_angles must be 1)"
+        nlay, ncol = tlay.shape
+        ng = self.get_ngpt()
+        try:
+            space = _space_of([plev, tlay, tsfc, tlev, sfc_emis, inc_flux, fluxes.flux_up, fluxes.flux_dn, particles.tau,
+                               particles.ssa, particles.g])
+            n, names, ptrs, cs, ls, sc, keep = self._gas_args(gas_desc, ncol, nlay, space)
+            nbp = 0 if particles.tau is None else int(particles.tau.shape[0])
+            shp = (nbp, nlay, ncol)
+            part = (_ptr(particles.tau, shp, "particles.tau"), _ptr(particles.ssa, shp, "particles.ssa"),
+                    _ptr(particles.g, shp, "particles.g"), _mask_ptr(cloud_mask, nlay, ncol, space))
+            lev = (nlay + 1, ncol)
+            inp = (_ptr(plev, lev, "plev"), _ptr(tlay, (nlay, ncol), "tlay"), _ptr(tsfc, (ncol,), "tsfc"), _ptr(tlev, lev, "tlev"))
+            emis = (_ptr(sfc_emis, (ncol, self.get_nband()), "sfc_emis"), _ptr(inc_flux, (ng, ncol), "inc_flux"))
+            out = (_ptr(fluxes.flux_up, lev, "flux_up"), _ptr(fluxes.flux_dn, lev, "flux_dn"))
+        except KeyError as e:
+            return str(e.args[0])
+        except (TypeError, ValueError) as e:
+            return str(e)
+        rc = lib().ecckd_lw_fluxes_allsky_2stream(self._need(), ncol, nlay, *inp, n, names, ptrs, cs, ls, sc, int(bool(top_at_1)),
+                                                  *emis, nbp, *part, *out, space, _stream(space))
+        return last_error() if rc else ""
+
     def lw_fluxes_allsky(self, plev, tlay, tsfc, tlev, gas_desc, top_at_1, sfc_emis, particles, fluxes, n_gauss_angles=1,
-                         inc_flux=None, cloud_mask=None, flux_up_jac=None):
+                         inc_flux=None, cloud_mask=None, use_2stream=False, flux_up_jac=None):
         """``ecckd_lw_fluxes_allsky``: ``lw_fluxes`` with the combined particulate optical properties ``particles`` on
         the model's bands added to the gas optical depth inside the solver: an ``OpticalProps2str``
         (``alloc_2str_bands``; absorption optical depth ``tau*(1 - ssa)``, its ``g`` is ignored) or an
@@ -913,7 +958,13 @@ class GasOpticsEcckd:
         arithmetic mode; numpy or device tensors.  ``cloud_mask`` ``(nlay, ncol)`` (``sample_cloud_mask``;
         ``ecckd_lw_fluxes_allsky_mcica``): a g-point whose bit is clear sees no particles in that layer.
         ``flux_up_jac`` ``(nlay+1, ncol)`` (``ecckd_lw_fluxes_jac``): the surface-temperature Jacobian of the all-sky
-        ``flux_up``.  Returns the error message ('' = success)."""
+        ``flux_up``.  ``use_2stream=True`` (``ecckd_lw_fluxes_allsky_2stream``): the particles scatter -- the two-stream
+        longwave solver on (``tau``, ``ssa``, ``g``) of a two-stream ``particles`` object on the bands; no quadrature
+        (``n_gauss_angles`` must be 1) and no ``flux_up_jac``; pass both by keyword (``flux_up_jac`` stays the last
+        parameter).  Returns the error message ('' = success)."""
+        if use_2stream:
+            return self._lw_fluxes_allsky_2stream(plev, tlay, tsfc, tlev, gas_desc, top_at_1, sfc_emis, particles, fluxes,
+                                                  n_gauss_angles, inc_flux, cloud_mask, flux_up_jac)
         if flux_up_jac is not None:
             return self._lw_fluxes_jac(plev, tlay, tsfc, tlev, gas_desc, top_at_1, sfc_emis, particles, fluxes, None,
                                        n_gauss_angles, inc_flux, cloud_mask, flux_up_jac)
@@ -1130,8 +1181,45 @@ def _increment(op1, op2, band2gpt, cloud_mask=None):
     return last_error() if rc else ""
 
 
+def _rte_lw_2stream(optical_props, top_at_1, sources, sfc_emis, fluxes, n_gauss_angles, device, shared_levels, inc_flux,
+                    flux_up_jac):
+    """``ecckd_rte_lw_2stream`` behind ``rte_lw(..., use_2stream=True)``."""
+    who = "rte_lw(use_2stream=True): "
+    if not isinstance(optical_props, OpticalProps2str):
+        return who + "two-stream optical properties required (OpticalProps2str)"
+    if _is_f32(optical_props.tau):
+        return who + "implemented for float64 arrays"
+    if shared_levels:
+        return who + "shared_levels belongs to the no-scattering solver"
+    if isinstance(fluxes, FluxesByband):
+        return who + "per-band fluxes are not implemented (broadband fluxes only)"
+    if flux_up_jac is not None:
+        return who + "flux_up_jac is not implemented"
+    if n_gauss_angles != 1:
+        return who + "the two-stream solver has no quadrature (n_gauss_angles must be 1)"
+    ng, nlay, ncol = optical_props.tau.shape
+    b2g = np.ascontiguousarray(optical_props.band2gpt, dtype=np.int32)
+    nband = b2g.shape[0]
+    try:
+        space = _space_of([optical_props.tau, optical_props.ssa, optical_props.g, sources.lev_source_inc, sources.lev_source_dec,
+                           sources.sfc_source, sfc_emis, inc_flux, fluxes.flux_up, fluxes.flux_dn])
+        a3 = [_ptr(a, (ng, nlay, ncol), w) for a, w in ((optical_props.tau, "tau"), (optical_props.ssa, "ssa"), (optical_props.g, "g"),
+                                                        (getattr(sources, "lay_source", None), "lay_source"),
+                                                        (sources.lev_source_inc, "lev_source_inc"),
+                                                        (sources.lev_source_dec, "lev_source_dec"))]
+        sfc = _ptr(sources.sfc_source, (ng, ncol), "sfc_source")
+        rest = [_ptr(sfc_emis, (ncol, nband), "sfc_emis"), _ptr(inc_flux, (ng, ncol), "inc_flux"),
+                _ptr(fluxes.flux_up, (nlay + 1, ncol), "flux_up"), _ptr(fluxes.flux_dn, (nlay + 1, ncol), "flux_dn")]
+    except (TypeError, ValueError) as e:
+        return str(e)
+    dev = _device_of(optical_props.tau) if device is None else device
+    rc = lib().ecckd_rte_lw_2stream(int(dev), ncol, nlay, ng, int(bool(top_at_1)), *a3, sfc, nband, C.c_void_p(b2g.ctypes.data),
+                                    *rest, space, _stream(space))
+    return last_error() if rc else ""
+
+
 def rte_lw(optical_props, top_at_1, sources, sfc_emis, fluxes, n_gauss_angles=1, device=None,
-           shared_levels=False, inc_flux=None, flux_up_jac=None):
+           shared_levels=False, inc_flux=None, use_2stream=False, flux_up_jac=None):
     """``rte_lw(optical_props, top_at_1, sources, sfc_emis(nband,ncol), fluxes, n_gauss_angles=)``
     (ecckd_rfmip_lw.F90:130-135).  ``sfc_emis`` is ``(ncol, nband)`` in numpy order.  float32 arrays
     take the single-precision entry point.  ``shared_levels=True`` asserts that the level sources hold
@@ -1140,7 +1228,15 @@ def rte_lw(optical_props, top_at_1, sources, sfc_emis, fluxes, n_gauss_angles=1,
     top of the domain (rte_lw's optional argument; ``ecckd_rte_lw_inc_flux`` / ``_f32``, generic solver).
     ``flux_up_jac`` ``(nlay+1, ncol)`` float64 (rte_lw's optional ``flux_up_Jac``; ``ecckd_rte_lw_jac``): receives the
     derivative of ``flux_up`` with respect to the surface temperature from ``sources.sfc_source_jac``
-    (``GasOpticsEcckd.planck_sfc_source_jac``); the fluxes are those of the call without it, bit for bit."""
+    (``GasOpticsEcckd.planck_sfc_source_jac``); the fluxes are those of the call without it, bit for bit.
+    ``use_2stream=True`` (rte_lw's ``use_2stream``; ``ecckd_rte_lw_2stream``): the two-stream solver, in which clouds
+    scatter -- an ``OpticalProps2str`` (float64), broadband fluxes, ``inc_flux`` accepted; ``shared_levels``,
+    ``FluxesByband``, ``flux_up_jac``, float32 and ``n_gauss_angles != 1`` are refused with a message.  Parity with
+    RTE-RRTMGP's ``lw_solver_2stream`` is unpinned.  Pass ``use_2stream`` and ``flux_up_jac`` by
+    keyword: ``flux_up_jac`` stays the last parameter (tests/test_lw_jac_host.py pins that), so ``use_2stream`` sits before it."""
+    if use_2stream:
+        return _rte_lw_2stream(optical_props, top_at_1, sources, sfc_emis, fluxes, n_gauss_angles, device, shared_levels,
+                               inc_flux, flux_up_jac)
     ng, nlay, ncol = optical_props.tau.shape
     b2g = np.ascontiguousarray(optical_props.band2gpt, dtype=np.int32)
     nband = b2g.shape[0]

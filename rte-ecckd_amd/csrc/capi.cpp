@@ -1727,6 +1727,108 @@ int ecckd_sw_solver_2stream_gpt(int device, int ncol, int nlay, int ngpt, int to
   return 0;
 }
 
+// ---- two-stream longwave solver (kernels_rte_lw_2str.hip): clouds scatter ----
+
+size_t ecckd_rte_lw_2stream_scratch_bytes(int ncol, int nlay, int ngpt) { return ecckd::rte_lw_2str_scratch_bytes(ncol, nlay, ngpt); }
+
+static int lw_2stream_layers_fit(int nlay) {
+  if (sizeof(double) * 2 * ((size_t)nlay + 1) * 16 > (size_t)ecckd::kLdsBudget)
+    return fail("ecckd_rte_lw_2stream: too many layers for the level accumulators in LDS (nlay = " + std::to_string(nlay) + ")");
+  return 0;
+}
+
+int ecckd_rte_lw_2stream(int device, int ncol, int nlay, int ngpt, int top_at_1, const double *tau, const double *ssa,
+                         const double *g, const double *lay_source, const double *lev_source_inc, const double *lev_source_dec,
+                         const double *sfc_source, int nband, const int *band2gpt, const double *sfc_emis, const double *inc_flux,
+                         double *flux_up, double *flux_dn, int memspace, void *stream) {
+  (void)lay_source;   // an argument as in RTE-RRTMGP's lw_solver_2stream, which never reads it
+  if (check_dims(ncol, nlay)) return 1;
+  if (!tau || !ssa || !g || !lev_source_inc || !lev_source_dec || !sfc_source || !sfc_emis || !flux_up || !flux_dn)
+    return fail("ecckd_rte_lw_2stream: null argument (only lay_source and inc_flux may be null)");
+  ecckd::RteLw2strArgs a{};
+  if (fill_band_map(ngpt, nband, band2gpt, a.gpt2band)) return 1;
+  if (lw_2stream_layers_fit(nlay)) return 1;
+  if (memspace == ECCKD_MIXED) return fail("ecckd_rte_lw_2stream: ECCKD_MIXED is not implemented (ECCKD_DEVICE or ECCKD_HOST)");
+  if (memspace != ECCKD_DEVICE && memspace != ECCKD_HOST) return fail("ecckd: bad memspace");
+  if (check_device(device)) return 1;
+  if (ncol == 0) return 0;
+  a.ncol = ncol; a.nlay = nlay; a.ng = ngpt; a.top_at_1 = top_at_1 ? 1 : 0; a.nband = nband;
+  a.exact_division = g_arith.load() != 0;
+  const size_t n3 = (size_t)ncol * nlay * ngpt, n2l = (size_t)ncol * (nlay + 1), n2g = (size_t)ncol * ngpt;
+  const hipStream_t launch_stream = memspace == ECCKD_DEVICE ? static_cast<hipStream_t>(stream) : nullptr;
+  ScratchLease lease;   // (held until the kernel of this call has been launched)
+  void *sp = nullptr;
+  if (stream_scratch(device, launch_stream, ecckd::rte_lw_2str_scratch_bytes(ncol, nlay, ngpt), &sp, lease)) return 1;
+  a.scratch = static_cast<double *>(sp);
+  if (memspace == ECCKD_DEVICE) {
+    a.tau = tau; a.ssa = ssa; a.g = g; a.lev_source_inc = lev_source_inc; a.lev_source_dec = lev_source_dec;
+    a.sfc_source = sfc_source; a.sfc_emis = sfc_emis; a.inc_flux = inc_flux; a.flux_up = flux_up; a.flux_dn = flux_dn;
+    ProfScope prof("rte_lw_2stream", launch_stream);
+    HIPCHK(ecckd::launch_rte_lw_2str(a, launch_stream));
+    return 0;
+  }
+  Arena &ar = g_solver_arena[device];
+  std::lock_guard<std::mutex> lock(ar.mu);
+  if (ar.ensure(align256(n3 * 8) * 5 + align256(n2g * 8) * 2 + align256((size_t)ncol * nband * 8) + align256(n2l * 8) * 2)) return 1;
+  Bump b(ar.p, false);
+  hipStream_t s = nullptr;
+  double *d_tau = b.take(n3), *d_ssa = b.take(n3), *d_g = b.take(n3), *d_inc = b.take(n3), *d_dec = b.take(n3);
+  double *d_sfc = b.take(n2g), *d_incf = b.take(n2g), *d_emis = b.take((size_t)ncol * nband), *d_up = b.take(n2l), *d_dn = b.take(n2l);
+  if (h2d(d_tau, tau, n3, false, s) || h2d(d_ssa, ssa, n3, false, s) || h2d(d_g, g, n3, false, s) ||
+      h2d(d_inc, lev_source_inc, n3, false, s) || h2d(d_dec, lev_source_dec, n3, false, s) || h2d(d_sfc, sfc_source, n2g, false, s) ||
+      h2d(d_emis, sfc_emis, (size_t)ncol * nband, false, s))
+    return 1;
+  if (inc_flux && h2d(d_incf, inc_flux, n2g, false, s)) return 1;
+  a.tau = d_tau; a.ssa = d_ssa; a.g = d_g; a.lev_source_inc = d_inc; a.lev_source_dec = d_dec; a.sfc_source = d_sfc;
+  a.sfc_emis = d_emis; a.inc_flux = inc_flux ? d_incf : nullptr; a.flux_up = d_up; a.flux_dn = d_dn;
+  HIPCHK(ecckd::launch_rte_lw_2str(a, s));
+  if (d2h(flux_up, d_up, n2l, false, s) || d2h(flux_dn, d_dn, n2l, false, s)) return 1;
+  HIPCHK(hipStreamSynchronize(s));
+  return 0;
+}
+
+int ecckd_lw_solver_2stream_gpt(int device, int ncol, int nlay, int ngpt, int top_at_1, const double *tau, const double *ssa,
+                                const double *g, const double *lay_source, const double *lev_source_inc,
+                                const double *lev_source_dec, const double *sfc_emis, const double *sfc_src,
+                                const double *inc_flux, double *gpt_flux_up, double *gpt_flux_dn, int memspace, void *stream) {
+  (void)lay_source;   // never read, as in RTE-RRTMGP
+  if (check_dims(ncol, nlay)) return 1;
+  if (ngpt < 1) return fail("ecckd_lw_solver_2stream_gpt: bad ngpt");
+  if (!tau || !ssa || !g || !lev_source_inc || !lev_source_dec || !sfc_emis || !sfc_src || !gpt_flux_up || !gpt_flux_dn)
+    return fail("ecckd_lw_solver_2stream_gpt: null argument (only lay_source and inc_flux may be null)");
+  if (memspace != ECCKD_DEVICE && memspace != ECCKD_HOST) return fail("ecckd: bad memspace");
+  if (check_device(device)) return 1;
+  if (ncol == 0) return 0;
+  ecckd::RteGptArgs a{};
+  a.ncol = ncol; a.nlay = nlay; a.ng = ngpt; a.top_at_1 = top_at_1 ? 1 : 0; a.nmus = 1;
+  const size_t n3 = (size_t)ncol * nlay * ngpt, n2 = (size_t)ncol * ngpt, nf = (size_t)ncol * (nlay + 1) * ngpt;
+  if (memspace == ECCKD_DEVICE) {
+    a.tau = tau; a.ssa = ssa; a.g = g; a.lev_source_inc = lev_source_inc; a.lev_source_dec = lev_source_dec;
+    a.sfc_emis = sfc_emis; a.sfc_src = sfc_src; a.inc_flux = inc_flux; a.flux_up = gpt_flux_up; a.flux_dn = gpt_flux_dn;
+    ProfScope prof("lw_2str_gpt", static_cast<hipStream_t>(stream));
+    HIPCHK(ecckd::launch_lw_2str_gpt(a, static_cast<hipStream_t>(stream)));
+    return 0;
+  }
+  Arena &ar = g_solver_arena[device];
+  std::lock_guard<std::mutex> lock(ar.mu);
+  if (ar.ensure(align256(n3 * 8) * 5 + align256(n2 * 8) * 3 + align256(nf * 8) * 2)) return 1;
+  Bump b(ar.p, false);
+  double *d_tau = b.take(n3), *d_ssa = b.take(n3), *d_g = b.take(n3), *d_inc = b.take(n3), *d_dec = b.take(n3);
+  double *d_emis = b.take(n2), *d_src = b.take(n2), *d_incf = b.take(n2), *d_up = b.take(nf), *d_dn = b.take(nf);
+  hipStream_t s = nullptr;
+  if (h2d(d_tau, tau, n3, false, s) || h2d(d_ssa, ssa, n3, false, s) || h2d(d_g, g, n3, false, s) ||
+      h2d(d_inc, lev_source_inc, n3, false, s) || h2d(d_dec, lev_source_dec, n3, false, s) || h2d(d_emis, sfc_emis, n2, false, s) ||
+      h2d(d_src, sfc_src, n2, false, s))
+    return 1;
+  if (inc_flux && h2d(d_incf, inc_flux, n2, false, s)) return 1;
+  a.tau = d_tau; a.ssa = d_ssa; a.g = d_g; a.lev_source_inc = d_inc; a.lev_source_dec = d_dec; a.sfc_emis = d_emis;
+  a.sfc_src = d_src; a.inc_flux = inc_flux ? d_incf : nullptr; a.flux_up = d_up; a.flux_dn = d_dn;
+  HIPCHK(ecckd::launch_lw_2str_gpt(a, s));
+  if (d2h(gpt_flux_up, d_up, nf, false, s) || d2h(gpt_flux_dn, d_dn, nf, false, s)) return 1;
+  HIPCHK(hipStreamSynchronize(s));
+  return 0;
+}
+
 int ecckd_sum_broadband(int device, int ncol, int nlev, int ngpt, const double *spectral_flux, double *broadband_flux,
                         int memspace, void *stream) {
   if (ncol < 0 || nlev < 1 || ngpt < 1) return fail("ecckd_sum_broadband: bad dimensions");
@@ -2085,6 +2187,108 @@ int ecckd_lw_fluxes_allsky_mcica(const ecckd_model_t *m, int ncol, int nlay, con
   return lw_fluxes_allsky_impl(m, ncol, nlay, plev, tlay, tsfc, tlev, ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride,
                                vmr_scalar, top_at_1, n_gauss_angles, sfc_emis, inc_flux, nband_p, tau_p, ssa_p, cloud_mask, flux_up,
                                flux_dn, memspace, stream);
+}
+
+// ---- fused all-sky longwave with scattering clouds: gas optics -> Planck sources -> two-stream solver (PART / MASK) ----
+
+// scratch of the device route, in doubles, in this order: optical depth, the three Planck arrays, the surface source (the
+// two-stream solver's ring follows, ecckd_rte_lw_2stream_scratch_bytes)
+static size_t r32(size_t n) { return (n + 31) & ~(size_t)31; }
+static size_t allsky_2stream_doubles(const ecckd_model *m, int ncol, int nlay) {
+  const size_t n3 = (size_t)ncol * nlay * m->ng;
+  return r32(n3) + 3 * n3 + r32((size_t)ncol * m->ng);
+}
+
+// behind the gas optics, on device pointers: `work` holds tau at its start
+static int lw_allsky_2stream_dev(const ecckd_model *m, int ncol, int nlay, const double *tlay, const double *tlev, const double *tsfc,
+                                 int top_at_1, const double *sfc_emis, const double *inc_flux, const double *tau_p,
+                                 const double *ssa_p, const double *g_p, const unsigned long long *mask, double *flux_up,
+                                 double *flux_dn, double *work, hipStream_t stream) {
+  const size_t n3 = (size_t)ncol * nlay * m->ng;
+  double *tau = work, *lay = tau + r32(n3), *inc = lay + n3, *dec = inc + n3, *sfc = dec + n3, *ring = sfc + r32((size_t)ncol * m->ng);
+  if (planck_sources_dev(m, ncol, nlay, tlay, PlanckSide{tlev, tsfc, lay, inc, dec, sfc}, stream)) return 1;
+  ecckd::RteLw2strArgs a{};
+  if (fill_band_map(m->ng, m->nband, m->band2gpt.data(), a.gpt2band)) return 1;
+  a.ncol = ncol; a.nlay = nlay; a.ng = m->ng; a.top_at_1 = top_at_1 ? 1 : 0; a.nband = m->nband;
+  a.exact_division = 0;
+  a.tau = tau; a.lev_source_inc = inc; a.lev_source_dec = dec; a.sfc_source = sfc; a.sfc_emis = sfc_emis; a.inc_flux = inc_flux;
+  a.part_tau = tau_p; a.part_ssa = ssa_p; a.part_g = g_p; a.part_mask = mask;
+  a.flux_up = flux_up; a.flux_dn = flux_dn; a.scratch = ring;
+  ProfScope prof("rte_lw_2stream_allsky", stream);
+  HIPCHK(ecckd::launch_rte_lw_2str(a, stream));
+  return 0;
+}
+
+int ecckd_lw_fluxes_allsky_2stream(const ecckd_model_t *m, int ncol, int nlay, const double *plev, const double *tlay,
+                                   const double *tsfc, const double *tlev, int ngas, const char *gas_names,
+                                   const double *const *vmr, const long long *vmr_col_stride, const long long *vmr_lay_stride,
+                                   const double *vmr_scalar, int top_at_1, const double *sfc_emis, const double *inc_flux,
+                                   int nband_p, const double *tau_p, const double *ssa_p, const double *g_p,
+                                   const unsigned long long *cloud_mask, double *flux_up, double *flux_dn, int memspace,
+                                   void *stream) {
+  if (!m) return fail("ecckd: null model");
+  if (cloud_mask && m->ng > 64) return fail("ecckd_lw_fluxes_allsky_2stream" + std::string(kMaskTooWide) + std::to_string(m->ng));
+  if (nband_p != m->nband)
+    return fail("ecckd_lw_fluxes_allsky_2stream: nband_p = " + std::to_string(nband_p) + " but the model has " +
+                std::to_string(m->nband) + " bands (particulate properties live on the model's bands)");
+  if (!tau_p || !ssa_p || !g_p)
+    return fail("ecckd_lw_fluxes_allsky_2stream: null argument (tau_p, ssa_p and g_p are required; one-stream particles: ecckd_lw_fluxes_allsky)");
+  if (g_arith.load() != 0) return fail("ecckd_lw_fluxes_allsky_2stream: needs the fast arithmetic mode (ecckd_set_arithmetic(0))");
+  if (!m->has_planck) return fail("ecckd_lw_fluxes_allsky_2stream: model has no Planck table (shortwave model?)");
+  if (!tlev) return fail("tlev is required for ecckd");
+  if (check_model(m) || check_gas_optics_dims(ncol, nlay)) return 1;
+  if (!plev || !tlay || !tsfc || !sfc_emis || !flux_up || !flux_dn || (ngas > 0 && !gas_names))
+    return fail("ecckd_lw_fluxes_allsky_2stream: null argument");
+  if (lw_2stream_layers_fit(nlay)) return 1;
+  if (memspace != ECCKD_DEVICE && memspace != ECCKD_HOST) return fail("ecckd: bad memspace");
+  HIPCHK(hipSetDevice(m->device));
+  if (ncol == 0) return 0;
+  const GasDesc gd{ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar};
+  const size_t n2 = (size_t)ncol * nlay, n2l = (size_t)ncol * (nlay + 1);
+  const size_t work_bytes = allsky_2stream_doubles(m, ncol, nlay) * sizeof(double) + ecckd::rte_lw_2str_scratch_bytes(ncol, nlay, m->ng);
+  if (memspace == ECCKD_DEVICE) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    void *wp = nullptr;
+    ScratchLease lease;
+    if (stream_scratch(m->device, st, work_bytes, &wp, lease)) return 1;
+    double *work = static_cast<double *>(wp);
+    if (gas_optical_depth_dev(m, false, nullptr, ncol, nlay, plev, tlay, gd, work, false, nullptr, nullptr, nullptr, nullptr, st)) return 1;
+    return lw_allsky_2stream_dev(m, ncol, nlay, tlay, tlev, tsfc, top_at_1, sfc_emis, inc_flux, tau_p, ssa_p, g_p, cloud_mask,
+                                 flux_up, flux_dn, work, st);
+  }
+  ecckd_model *mm = const_cast<ecckd_model *>(m);
+  std::lock_guard<std::mutex> lock(mm->mu);
+  hipStream_t s = mm->host_stream;
+  const size_t nb3 = n2 * m->nband;
+  const size_t need = align256(n2l * 8) * 4 + align256(n2 * 8) + align256((size_t)ncol * 8) + staged_gas_bytes(gd, ncol, nlay, false) +
+                      align256((size_t)ncol * m->nband * 8) + align256((size_t)ncol * m->ng * 8) + align256(work_bytes) +
+                      align256(nb3 * 8) * 3 + (cloud_mask ? align256(n2 * 8) : 0);
+  if (grow_arena(mm, need)) return 1;
+  Bump b(mm->arena, false);
+  double *d_plev = b.take(n2l), *d_tlev = b.take(n2l), *d_tlay = b.take(n2), *d_tsfc = b.take(ncol);
+  double *d_up = b.take(n2l), *d_dn = b.take(n2l), *d_emis = b.take((size_t)ncol * m->nband), *d_incf = b.take((size_t)ncol * m->ng);
+  if (h2d(d_plev, plev, n2l, false, s) || h2d(d_tlay, tlay, n2, false, s) || h2d(d_tsfc, tsfc, ncol, false, s) ||
+      h2d(d_tlev, tlev, n2l, false, s) || h2d(d_emis, sfc_emis, (size_t)ncol * m->nband, false, s))
+    return 1;
+  if (inc_flux && h2d(d_incf, inc_flux, (size_t)ncol * m->ng, false, s)) return 1;
+  StagedGases sg;
+  if (stage_gases(gd, ncol, nlay, b, s, sg)) return 1;
+  double *work = b.take(work_bytes / sizeof(double));
+  double *q_tau = b.take(nb3), *q_ssa = b.take(nb3), *q_g = b.take(nb3);
+  if (h2d(q_tau, tau_p, nb3, false, s) || h2d(q_ssa, ssa_p, nb3, false, s) || h2d(q_g, g_p, nb3, false, s)) return 1;
+  const unsigned long long *q_mask = nullptr;
+  if (cloud_mask) {   // (8-byte words: staged like an array of doubles)
+    double *qm = b.take(n2);
+    if (h2d(qm, reinterpret_cast<const double *>(cloud_mask), n2, false, s)) return 1;
+    q_mask = reinterpret_cast<const unsigned long long *>(qm);
+  }
+  if (gas_optical_depth_dev(m, false, nullptr, ncol, nlay, d_plev, d_tlay, sg.gd, work, false, nullptr, nullptr, nullptr, nullptr, s)) return 1;
+  if (lw_allsky_2stream_dev(m, ncol, nlay, d_tlay, d_tlev, d_tsfc, top_at_1, d_emis, inc_flux ? d_incf : nullptr, q_tau, q_ssa, q_g,
+                            q_mask, d_up, d_dn, work, s))
+    return 1;
+  if (d2h(flux_up, d_up, n2l, false, s) || d2h(flux_dn, d_dn, n2l, false, s)) return 1;
+  HIPCHK(hipStreamSynchronize(s));
+  return 0;
 }
 
 // The superset of the four fused longwave calls, with flux_up_jac of the sky that flux_up holds (include/ecckd_hip.h)

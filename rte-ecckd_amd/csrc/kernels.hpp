@@ -199,6 +199,28 @@ struct RteSwArgs {
   const unsigned long long *part_mask = nullptr;
 };
 
+// Two-stream longwave solver (kernels_rte_lw_2str.hip): clouds scatter.  tau / ssa / g / lev_source_* (ncol,nlay,ng),
+// sfc_source(ncol,ng), sfc_emis(nband,ncol), inc_flux(ncol,ng) or null; fp64.  lay_source is not an argument: RTE-RRTMGP's
+// lw_solver_2stream never reads it.
+struct RteLw2strArgs {
+  int ncol, nlay, ng, top_at_1;
+  const double *tau, *ssa, *g, *lev_source_inc, *lev_source_dec, *sfc_source;
+  const double *sfc_emis;      // (nband,ncol)
+  int nband;
+  unsigned char gpt2band[256]; // 0-based band of each g-point
+  const double *inc_flux;
+  double *flux_up, *flux_dn;
+  double *scratch;             // per-wave ring [2][nlay+1][64]: rte_lw_2str_scratch_bytes
+  int exact_division;          // 1 (reference-order arithmetic mode): IEEE `/`, sqrt, exp; 0: rcp / sw_sqrt / sw_exp
+  // Fused all-sky path (ecckd_lw_fluxes_allsky_2stream): `tau` is the gas optical depth, ssa / g are not read; the layer's
+  // particulate triple on the cell's band, part_* (ncol,nlay,nband), is added where the cell's properties are formed, with
+  // the operations of the by-band increment_2stream_by_2stream on op1 = (tau, 0, 0) (kernels_optical_props.hip)
+  const double *part_tau = nullptr, *part_ssa = nullptr, *part_g = nullptr;
+  const unsigned long long *part_mask = nullptr;   // as RteLwArgs::part_mask (ng <= 64)
+};
+size_t rte_lw_2str_scratch_bytes(int ncol, int nlay, int ng);
+hipError_t launch_rte_lw_2str(const RteLw2strArgs &a, hipStream_t s);
+
 // Element-wise operations on optical properties (kernels_optical_props.hip): RTE-RRTMGP's delta_scale_2str_k / _f_k and
 // the increment_* kernels (by g-point and by band).  Arrays (ncol,nlay,n), column fastest; f32: float data behind the pointers.
 struct OptPropsArgs {
@@ -242,6 +264,8 @@ struct RteGptArgs {
 };
 hipError_t launch_lw_gpt(const RteGptArgs &a, hipStream_t s);
 hipError_t launch_sw_gpt(const RteGptArgs &a, hipStream_t s);
+// lw_solver_2stream: tau, ssa, g, lev_source_*, sfc_emis / sfc_src / inc_flux (ncol,ng); lay_source is not read
+hipError_t launch_lw_2str_gpt(const RteGptArgs &a, hipStream_t s);
 
 // Host-side helpers -------------------------------------------------------------------------
 int tau_slab_rows(int ng, int np, int nt, int nbil, int nv_lut);   // R that fits LDS (>= 0)

@@ -10,6 +10,7 @@
 //              pass 2 (top -> surface) reads them back and overwrites them with the fluxes.
 // Arithmetic: the same expressions, in the same order, as the restatement in oracle/ (IEEE division).
 #include "kernels.hpp"
+#include "lw_two_stream.hpp"
 
 namespace ecckd {
 namespace {
@@ -143,6 +144,59 @@ __global__ void __launch_bounds__(256) sw_gpt_kernel(const RteGptArgs a) {
   }
 }
 
+// lw_solver_2stream: clouds scatter.  Pass 1 (surface -> top) parks albedo and source of each level in the OUTPUT arrays
+// flux_up / flux_dn, pass 2 (top -> surface) reads them back and overwrites them with the fluxes; the coefficients are
+// recomputed.  lay_source is not read.  IEEE arithmetic in the spelt order (lw_two_stream.hpp).
+__global__ void __launch_bounds__(256) lw_2str_gpt_kernel(const RteGptArgs a) {
+  const long n = (long)a.ncol * a.ng;
+  const int nlay = a.nlay, nlev = nlay + 1;
+  const long ncol = a.ncol;
+  for (long id = (long)blockIdx.x * blockDim.x + threadIdx.x; id < n; id += (long)gridDim.x * blockDim.x) {
+    const long c = id % ncol, g = id / ncol;
+    const long base3 = c + ncol * nlay * g, basef = c + ncol * nlev * g, base2 = c + ncol * g;
+    const long lay0 = a.top_at_1 ? 0 : nlay - 1, lev0 = a.top_at_1 ? 0 : nlay, lstep = a.top_at_1 ? 1 : -1;
+    auto lev = [&](int s) { return basef + ncol * (lev0 + lstep * s); };
+    auto level_source = [&](int s) {   // level s counted from the top
+      const long jm = lev0 + lstep * s;
+      return lw2_level_source((int)jm, nlay, a.lev_source_dec[base3 + ncol * (jm < nlay ? jm : nlay - 1)],
+                              a.lev_source_inc[base3 + ncol * (jm > 0 ? jm - 1 : 0)]);
+    };
+    auto cell = [&](int s, double Bt, double Bb) {
+      const long q = base3 + ncol * (lay0 + lstep * s);
+      return lw_two_stream<false>(a.tau[q], a.ssa[q], a.g[q], Bt, Bb);
+    };
+    const double inc = a.inc_flux ? a.inc_flux[base2] : 0.;   // (read before pass 1 parks anything in flux_dn)
+    const double emis = a.sfc_emis[base2];
+    double albedo = 1. - emis, src = kLw2Pi * emis * a.sfc_src[base2];
+    a.flux_up[lev(nlay)] = albedo;
+    a.flux_dn[lev(nlay)] = src;
+    double Bb = level_source(nlay);
+    for (int s = nlay - 1; s >= 0; --s) {
+      const double Bt = level_source(s);
+      const Lw2Cell cl = cell(s, Bt, Bb);
+      const double den = 1. / (1. - cl.Rdif * albedo);
+      src = cl.src_up + cl.Tdif * den * (src + albedo * cl.src_dn);
+      albedo = cl.Rdif + cl.Tdif * cl.Tdif * albedo * den;
+      a.flux_up[lev(s)] = albedo;
+      a.flux_dn[lev(s)] = src;
+      Bb = Bt;
+    }
+    double Bt = Bb, fdn = inc;
+    a.flux_up[lev(0)] = fdn * albedo + src;
+    a.flux_dn[lev(0)] = fdn;
+    for (int s = 0; s < nlay; ++s) {
+      const double alb_next = a.flux_up[lev(s + 1)], src_next = a.flux_dn[lev(s + 1)];
+      const double Bn = level_source(s + 1);
+      const Lw2Cell cl = cell(s, Bt, Bn);
+      const double den = 1. / (1. - cl.Rdif * alb_next);
+      fdn = (cl.Tdif * fdn + cl.Rdif * src_next + cl.src_dn) * den;
+      a.flux_up[lev(s + 1)] = fdn * alb_next + src_next;
+      a.flux_dn[lev(s + 1)] = fdn;
+      Bt = Bn;
+    }
+  }
+}
+
 }  // namespace
 
 static unsigned gpt_blocks(long n) {
@@ -159,6 +213,12 @@ hipError_t launch_lw_gpt(const RteGptArgs &a, hipStream_t s) {
 hipError_t launch_sw_gpt(const RteGptArgs &a, hipStream_t s) {
   if (a.ncol <= 0 || a.ng <= 0) return hipSuccess;
   hipLaunchKernelGGL(sw_gpt_kernel, dim3(gpt_blocks((long)a.ncol * a.ng)), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_lw_2str_gpt(const RteGptArgs &a, hipStream_t s) {
+  if (a.ncol <= 0 || a.ng <= 0) return hipSuccess;
+  hipLaunchKernelGGL(lw_2str_gpt_kernel, dim3(gpt_blocks((long)a.ncol * a.ng)), dim3(256), 0, s, a);
   return hipGetLastError();
 }
 

@@ -41,6 +41,18 @@ void lw_solver_noscat_GaussQuad(const int *ncol, const int *nlay, const int *ngp
               "lw_solver_noscat_GaussQuad");
 }
 
+void lw_solver_2stream(const int *ncol, const int *nlay, const int *ngpt, const bool *top_at_1, const double *tau,
+                       const double *ssa, const double *g, const double *lay_source, const double *lev_source_inc,
+                       const double *lev_source_dec, const double *sfc_emis, const double *sfc_src, double *flux_up,
+                       double *flux_dn) {
+  const int top = *top_at_1 ? 0 : *nlay;
+  const std::vector<double> inc = level_plane(flux_dn, *ncol, *nlay + 1, *ngpt, top);   // apply_BC left it there
+  stop_on_err(ecckd_lw_solver_2stream_gpt(device(), *ncol, *nlay, *ngpt, *top_at_1 ? 1 : 0, tau, ssa, g, lay_source,
+                                          lev_source_inc, lev_source_dec, sfc_emis, sfc_src, inc.data(), flux_up, flux_dn,
+                                          ECCKD_HOST, nullptr),
+              "lw_solver_2stream");
+}
+
 void sw_solver_2stream(const int *ncol, const int *nlay, const int *ngpt, const bool *top_at_1, const double *tau,
                        const double *ssa, const double *g, const double *mu0, const double *sfc_alb_dir,
                        const double *sfc_alb_dif, double *flux_up, double *flux_dn, double *flux_dir) {
