@@ -48,18 +48,11 @@ std::string trim_name(const char *p) {
   return std::string(p, n);
 }
 
-// Grow-only device arena used by the ECCKD_HOST flavours.
+// Grow-only device arena of the solver calls on host arrays, one per device (Stage; the model calls use the model's own).
 struct Arena {
   std::mutex mu;
   void *p = nullptr;
   size_t bytes = 0;
-  int ensure(size_t need) {
-    if (need <= bytes) return 0;
-    if (p) { HIPCHK(hipFree(p)); p = nullptr; bytes = 0; }
-    HIPCHK(hipMalloc(&p, need));
-    bytes = need;
-    return 0;
-  }
 };
 Arena g_solver_arena[16];
 
@@ -184,7 +177,7 @@ int simd_slots(int device) {
 size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
 
 // Single precision: the *_f32 entry points cast their float pointers to `double *` (dp) and pass f32 = true down;
-// every staging helper below takes that flag to size its copies and the kernels are launched with f32 = 1.  Data
+// Stage below takes that flag to size its rooms and copies and the kernels are launched with f32 = 1.  Data
 // pointers keep their `double *` static type on the way through (they are only passed on, never indexed).
 size_t esz(bool f32) { return f32 ? sizeof(float) : sizeof(double); }
 inline const double *dp(const float *p) { return reinterpret_cast<const double *>(p); }
@@ -279,19 +272,6 @@ struct ProfScope {
     (void)hipEventRecord(r.stop, s);
     std::lock_guard<std::mutex> lock(g_prof_mu);
     g_prof.push_back(r);
-  }
-};
-
-// Bump allocator over an Arena block.
-struct Bump {
-  char *base;
-  size_t es;   // element size: esz()
-  size_t off = 0;
-  Bump(void *b, bool f32) : base(static_cast<char *>(b)), es(esz(f32)) {}
-  double *take(size_t nelem) {
-    double *r = reinterpret_cast<double *>(base + off);
-    off += align256(nelem * es);
-    return r;
   }
 };
 
@@ -496,48 +476,141 @@ int check_gas_optics_dims(int ncol, int nlay) {
   return 0;
 }
 
-// Copies gas_desc data arrays to the arena and returns the device-side description.
-struct StagedGases {
-  std::vector<const double *> ptr;
-  GasDesc gd;
+// Element counts of the arrays of a call: (ncol), (ncol,nlay), (ncol,nlay+1), and per g-point or band of each
+struct Counts {
+  size_t col, lay, lev, lay_g, col_g, lay_b, col_b;
+  Counts(int ncol, int nlay, int ng, int nband)
+      : col((size_t)ncol), lay(col * nlay), lev(col * (nlay + 1)), lay_g(lay * ng), col_g(col * ng), lay_b(lay * nband),
+        col_b(col * nband) {}
 };
-size_t staged_gas_bytes(const GasDesc &gd, int ncol, int nlay, bool f32) {
-  size_t b = 0;
-  for (int j = 0; j < gd.ngas; ++j) b += align256(vmr_extent(gd, j, ncol, nlay) * esz(f32));
-  return b;
-}
-int stage_gases(const GasDesc &gd, int ncol, int nlay, Bump &bump, hipStream_t s, StagedGases &out) {
-  out.ptr.assign(gd.ngas, nullptr);
-  for (int j = 0; j < gd.ngas; ++j) {
-    const size_t n = vmr_extent(gd, j, ncol, nlay);
-    if (!n) continue;
-    double *d = bump.take(n);
-    HIPCHK(hipMemcpyAsync(d, gd.vmr[j], n * bump.es, hipMemcpyHostToDevice, s));
-    out.ptr[j] = d;
+
+// ---- staging: a call's arrays are declared once, wherever they live ----
+// An entry point hands open() a function that declares every array of the call -- in / out / inout with its element
+// count, kBig for the spectral arrays that ECCKD_MIXED leaves on the device -- and takes the pointers its kernels get.
+// An array that lives on the device comes back as the caller's pointer, untouched.  A host array gets a 256-byte-aligned
+// room of the arena and is copied in; close() copies the outputs back and synchronises once.  A null (optional) pointer
+// stays null and takes no room.  With anything to stage, open() takes the arena's lock and runs the declarations twice:
+// first to add the rooms up, then -- the arena grown to that size, which frees the old block, so before any copy -- to
+// carve them and issue the copies: the statements that carve the arena are the ones that size it.  With ECCKD_DEVICE
+// open() runs them once and close() does nothing: no lock, no allocation, no heap, no synchronisation, capturable.
+// The declarations must do nothing but declare (they run twice); pointers derived from a room are formed after open().
+constexpr bool kBig = true;
+
+class Stage {
+ public:
+  const hipStream_t stream;   // where the call launches: the caller's stream (ECCKD_DEVICE), else the arena's
+
+  // a solver call: the arena of the device and the null stream
+  Stage(int device, int memspace, void *caller_stream, bool f32)
+      : Stage(device, memspace, caller_stream, f32, g_solver_arena[device].mu, g_solver_arena[device].p,
+              g_solver_arena[device].bytes, nullptr) {}
+  // a call on a model: the model's arena and its host stream
+  Stage(ecckd_model *m, int memspace, void *caller_stream, bool f32)
+      : Stage(m->device, memspace, caller_stream, f32, m->mu, m->arena, m->arena_bytes, m->host_stream) {}
+
+  const double *in(const double *p, size_t n, bool big = false) { return static_cast<double *>(place(p, n * es, big, true, false)); }
+  // back = false: a room the kernels write and nobody reads back
+  double *out(double *p, size_t n, bool big = false, bool back = true) { return static_cast<double *>(place(p, n * es, big, false, back)); }
+  double *inout(double *p, size_t n, bool back = true) { return static_cast<double *>(place(p, n * es, false, true, back)); }
+  // cloud masks: 8-byte words whatever the precision of the call
+  const unsigned long long *in(const unsigned long long *p, size_t n) { return static_cast<unsigned long long *>(place(p, n * 8, false, true, false)); }
+  unsigned long long *out(unsigned long long *p, size_t n) { return static_cast<unsigned long long *>(place(p, n * 8, false, false, true)); }
+
+  // The gas description with its concentration arrays staged (the strides and scalars stay as they are)
+  GasDesc gases(const GasDesc &gd, int ncol, int nlay) {
+    if (!host_any) return gd;
+    vmr.assign(gd.ngas, nullptr);
+    for (int j = 0; j < gd.ngas; ++j) vmr[j] = in(gd.vmr ? gd.vmr[j] : nullptr, vmr_extent(gd, j, ncol, nlay));
+    GasDesc d = gd;
+    d.vmr = vmr.data();
+    return d;
   }
-  out.gd = gd;
-  out.gd.vmr = out.ptr.data();
-  return 0;
-}
 
-int h2d(double *d, const double *h, size_t n, bool f32, hipStream_t s) {
-  HIPCHK(hipMemcpyAsync(d, h, n * esz(f32), hipMemcpyHostToDevice, s));
-  return 0;
-}
-int d2h(double *h, const double *d, size_t n, bool f32, hipStream_t s) {
-  HIPCHK(hipMemcpyAsync(h, d, n * esz(f32), hipMemcpyDeviceToHost, s));
-  return 0;
-}
+  // The work block of the call (optical depth between the kernels, sources, rings, scaled planes; the entry point lays it
+  // out, the same way on every route): the scratch block of the caller's stream under the rules of ScratchPool -- the
+  // lease lasts as long as the Stage, past the launches -- or, with host arrays, a room of the arena.  One per call.
+  double *work(size_t bytes) {
+    if (host_any) return static_cast<double *>(room(bytes));
+    void *p = nullptr;
+    if (stream_scratch(device, stream, bytes, &p, lease)) err = 1;
+    return static_cast<double *>(p);
+  }
 
-// Grows the model's staging arena (caller holds m->mu); the host stream may still read the old block
-int grow_arena(ecckd_model *m, size_t need) {
-  if (need <= m->arena_bytes) return 0;
-  HIPCHK(hipStreamSynchronize(m->host_stream));
-  if (m->arena) { HIPCHK(hipFree(m->arena)); m->arena = nullptr; m->arena_bytes = 0; }
-  HIPCHK(hipMalloc(&m->arena, need));
-  m->arena_bytes = need;
-  return 0;
-}
+  template <class F> int open(F &&declare) {
+    if (!host_any) { declare(); return err; }
+    lock = std::unique_lock<std::mutex>(mu);
+    measuring = true;
+    declare();
+    if (err || grow(off)) return 1;
+    measuring = false;
+    off = 0;
+    declare();
+    return err;
+  }
+
+  int close() {
+    if (!host_any) return 0;
+    for (int i = 0; i < nback; ++i)
+      HIPCHK(hipMemcpyAsync(backs[i].host, backs[i].dev, backs[i].bytes, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    return 0;
+  }
+
+ private:
+  Stage(int device_, int memspace, void *caller_stream, bool f32, std::mutex &mu_, void *&arena_, size_t &arena_bytes_,
+        hipStream_t arena_stream)
+      : stream(memspace == ECCKD_DEVICE ? static_cast<hipStream_t>(caller_stream) : arena_stream), device(device_),
+        host_any(memspace != ECCKD_DEVICE), host_big(host_any && memspace != ECCKD_MIXED), es(esz(f32)), mu(mu_),
+        arena(arena_), arena_bytes(arena_bytes_) {}
+
+  // (the lock is held) the model's host stream may still read the old block; the solver arena's null stream needs no such care
+  int grow(size_t need) {
+    if (need <= arena_bytes) return 0;
+    if (stream) HIPCHK(hipStreamSynchronize(stream));
+    if (arena) { HIPCHK(hipFree(arena)); arena = nullptr; arena_bytes = 0; }
+    HIPCHK(hipMalloc(&arena, need));
+    arena_bytes = need;
+    return 0;
+  }
+
+  void *room(size_t bytes) {
+    const size_t at = off;
+    off += align256(bytes);
+    return measuring || !bytes ? nullptr : static_cast<char *>(arena) + at;
+  }
+
+  void *place(const void *p, size_t bytes, bool big, bool copy_in, bool copy_back) {
+    void *const caller = const_cast<void *>(p);
+    if (!p || !bytes || !(big ? host_big : host_any)) return caller;
+    void *d = room(bytes);
+    if (measuring || err) return caller;
+    if (copy_in) {
+      const hipError_t e = hipMemcpyAsync(d, p, bytes, hipMemcpyHostToDevice, stream);
+      if (e != hipSuccess) err = fail(std::string("hipMemcpyAsync (host to device): ") + hipGetErrorString(e));
+    }
+    if (copy_back) {
+      if (nback == kMaxBack) err = fail("ecckd: internal: too many outputs in one staged call");
+      else backs[nback++] = Back{caller, d, bytes};
+    }
+    return d;
+  }
+
+  static constexpr int kMaxBack = 8;
+  struct Back { void *host; const void *dev; size_t bytes; };
+  const int device;
+  const bool host_any, host_big;   // host arrays at all / the kBig arrays too
+  const size_t es;                 // element size of the call: esz()
+  std::mutex &mu;
+  void *&arena;
+  size_t &arena_bytes;
+  std::unique_lock<std::mutex> lock;
+  ScratchLease lease;
+  std::vector<const double *> vmr;   // (host arrays only)
+  Back backs[kMaxBack];
+  int nback = 0, err = 0;
+  size_t off = 0;
+  bool measuring = false;
+};
 
 // out(:) = sum over planes of planes(:, b) on the host, in the precision of T
 template <class T> void sum_planes_host(const T *planes, int nplanes, size_t n, T *out) {
@@ -763,6 +836,8 @@ static int release_pool(ScratchPool &pool, int device) {
   return 0;
 }
 
+// Every launch sits in a ProfScope on the stream it goes to, whatever the memory space of the call: with host arrays the
+// stand-alone solvers and element-wise calls are recorded too (on the arena's stream), as the fused calls always were.
 int ecckd_prof_enable(int on) {
   std::lock_guard<std::mutex> lock(g_prof_mu);
   g_prof_on = on != 0;
@@ -1007,10 +1082,7 @@ int ecckd_model_get_device(const ecckd_model_t *m) { return m ? m->device : -1; 
 // ------------------------------------ gas optics -----------------------------------------
 
 static int gas_optics_lw_dev(const ecckd_model *m, bool f32, int ncol, int nlay, const double *plev,
-                             const double *tlay, const double *tsfc, const double *tlev,
-                             const GasDesc &gd, double *tau, double *lay_source, double *lev_inc,
-                             double *lev_dec, double *sfc_source, hipStream_t stream) {
-  const PlanckSide pl{tlev, tsfc, lay_source, lev_inc, lev_dec, sfc_source};
+                             const double *tlay, const GasDesc &gd, double *tau, const PlanckSide &pl, hipStream_t stream) {
   bool planck_done = false;
   if (gas_optical_depth_dev(m, f32, nullptr, ncol, nlay, plev, tlay, gd, tau, false, nullptr, nullptr, &pl, &planck_done,
                             stream))
@@ -1043,24 +1115,15 @@ int ecckd_planck_sfc_source_jac(const ecckd_model_t *m, int ncol, const double *
   HIPCHK(hipSetDevice(m->device));
   if (ncol == 0) return 0;
   const double t0 = m->temperature_planck[0], dt = m->temperature_planck[1] - m->temperature_planck[0];
-  if (memspace == ECCKD_DEVICE) {
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    ProfScope prof("planck_sfc_jac", st);
-    HIPCHK(ecckd::launch_planck_sfc_jac(m->dbuf + m->off_planck, m->ng, m->ntp, t0, dt, ncol, tsfc, sfc_source_jac, st));
-    return 0;
+  Stage st(const_cast<ecckd_model *>(m), memspace, stream, false);
+  const double *d_tsfc = nullptr;
+  double *d_jac = nullptr;
+  if (st.open([&] { d_tsfc = st.in(tsfc, ncol); d_jac = st.out(sfc_source_jac, (size_t)ncol * m->ng); })) return 1;
+  {
+    ProfScope prof("planck_sfc_jac", st.stream);
+    HIPCHK(ecckd::launch_planck_sfc_jac(m->dbuf + m->off_planck, m->ng, m->ntp, t0, dt, ncol, d_tsfc, d_jac, st.stream));
   }
-  ecckd_model *mm = const_cast<ecckd_model *>(m);
-  std::lock_guard<std::mutex> lock(mm->mu);
-  hipStream_t s = mm->host_stream;
-  const size_t nout = (size_t)ncol * m->ng;
-  if (grow_arena(mm, align256((size_t)ncol * 8) + align256(nout * 8))) return 1;
-  Bump b(mm->arena, false);
-  double *d_tsfc = b.take(ncol), *d_out = b.take(nout);
-  if (h2d(d_tsfc, tsfc, ncol, false, s)) return 1;
-  HIPCHK(ecckd::launch_planck_sfc_jac(m->dbuf + m->off_planck, m->ng, m->ntp, t0, dt, ncol, d_tsfc, d_out, s));
-  if (d2h(sfc_source_jac, d_out, nout, false, s)) return 1;
-  HIPCHK(hipStreamSynchronize(s));
-  return 0;
+  return st.close();
 }
 
 int ecckd_gas_optics_plan(const ecckd_model_t *m, int ncol, int nlay, int single_precision, int ngas,
@@ -1114,50 +1177,30 @@ static int gas_optics_lw_impl(bool f32, const ecckd_model_t *m, int ncol, int nl
   if (tlev && (!lev_source_inc || !lev_source_dec)) return fail("ecckd_gas_optics_lw: null level sources");
   HIPCHK(hipSetDevice(m->device));
   const GasDesc gd{ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar};
-  const size_t n2 = (size_t)ncol * nlay, n2l = (size_t)ncol * (nlay + 1), n3 = n2 * m->ng;
   if (ncol == 0) return tlev ? 0 : fail("tlev is required for ecckd");
-
-  if (memspace == ECCKD_DEVICE) {
-    if (gas_optics_lw_dev(m, f32, ncol, nlay, plev, tlay, tsfc, tlev, gd, tau, lay_source, lev_source_inc,
-                          lev_source_dec, sfc_source, static_cast<hipStream_t>(stream)))
-      return 1;
-    return tlev ? 0 : fail("tlev is required for ecckd");   // :414-417
-  }
-  if (memspace != ECCKD_HOST && memspace != ECCKD_MIXED) return fail("ecckd: bad memspace");
+  if (memspace != ECCKD_DEVICE && memspace != ECCKD_HOST && memspace != ECCKD_MIXED) return fail("ecckd: bad memspace");
   // ECCKD_MIXED: inputs are host arrays (staged here), the (ncol,nlay,ngpt) / (ncol,ngpt) outputs are the caller's
   // device buffers: nothing but ~4 KB per column crosses the bus
-  const bool mixed = memspace == ECCKD_MIXED;
-
-  ecckd_model *mm = const_cast<ecckd_model *>(m);
-  std::lock_guard<std::mutex> lock(mm->mu);
-  hipStream_t s = mm->host_stream;
-  const size_t es = esz(f32);
-  size_t need = align256(n2l * es) * 2 + align256(n2 * es) + align256((size_t)ncol * es) +
-                staged_gas_bytes(gd, ncol, nlay, f32);
-  if (!mixed) need += align256(n3 * es) * 4 + align256((size_t)ncol * m->ng * es);
-  if (grow_arena(mm, need)) return 1;
-  Bump b(mm->arena, f32);
-  double *d_plev = b.take(n2l), *d_tlev = b.take(n2l), *d_tlay = b.take(n2), *d_tsfc = b.take(ncol);
-  if (h2d(d_plev, plev, n2l, f32, s) || h2d(d_tlay, tlay, n2, f32, s) || h2d(d_tsfc, tsfc, ncol, f32, s)) return 1;
-  if (tlev && h2d(d_tlev, tlev, n2l, f32, s)) return 1;
-  StagedGases sg;
-  if (stage_gases(gd, ncol, nlay, b, s, sg)) return 1;
-  double *d_tau = tau, *d_lay = lay_source, *d_inc = lev_source_inc, *d_dec = lev_source_dec, *d_sfc = sfc_source;
-  if (!mixed) {
-    d_tau = b.take(n3); d_lay = b.take(n3); d_inc = b.take(n3); d_dec = b.take(n3);
-    d_sfc = b.take((size_t)ncol * m->ng);
-  }
-  if (gas_optics_lw_dev(m, f32, ncol, nlay, d_plev, d_tlay, d_tsfc, tlev ? d_tlev : nullptr, sg.gd, d_tau,
-                        d_lay, d_inc, d_dec, d_sfc, s))
+  const Counts n(ncol, nlay, m->ng, m->nband);
+  Stage st(const_cast<ecckd_model *>(m), memspace, stream, f32);
+  const double *d_plev = nullptr, *d_tlay = nullptr;
+  PlanckSide pl{};
+  GasDesc d_gd{};
+  double *d_tau = nullptr;
+  if (st.open([&] {
+        d_plev = st.in(plev, n.lev); d_tlay = st.in(tlay, n.lay);
+        pl.tsfc = st.in(tsfc, n.col); pl.tlev = st.in(tlev, n.lev);
+        d_gd = st.gases(gd, ncol, nlay);
+        d_tau = st.out(tau, n.lay_g, kBig);
+        pl.lay_source = st.out(lay_source, n.lay_g, kBig); pl.sfc_source = st.out(sfc_source, n.col_g, kBig);
+        // (without tlev the level sources are not produced: nothing to copy back)
+        pl.lev_inc = st.out(lev_source_inc, n.lay_g, kBig, tlev != nullptr);
+        pl.lev_dec = st.out(lev_source_dec, n.lay_g, kBig, tlev != nullptr);
+      }))
     return 1;
-  if (!mixed) {
-    if (d2h(tau, d_tau, n3, f32, s) || d2h(lay_source, d_lay, n3, f32, s) ||
-        d2h(sfc_source, d_sfc, (size_t)ncol * m->ng, f32, s))
-      return 1;
-    if (tlev && (d2h(lev_source_inc, d_inc, n3, f32, s) || d2h(lev_source_dec, d_dec, n3, f32, s))) return 1;
-  }
-  HIPCHK(hipStreamSynchronize(s));   // (mixed too: the solver call that follows runs on another stream)
-  return tlev ? 0 : fail("tlev is required for ecckd");
+  if (gas_optics_lw_dev(m, f32, ncol, nlay, d_plev, d_tlay, d_gd, d_tau, pl, st.stream)) return 1;
+  if (st.close()) return 1;   // (ECCKD_MIXED synchronises too: the solver call that follows runs on another stream)
+  return tlev ? 0 : fail("tlev is required for ecckd");   // :414-417
 }
 
 int ecckd_gas_optics_lw(const ecckd_model_t *m, int ncol, int nlay, const double *plev,
@@ -1207,43 +1250,25 @@ static int gas_optics_sw_impl(bool f32, const ecckd_model_t *m, int ncol, int nl
   if (two_stream && !toa_src) return fail("ecckd_gas_optics_sw: null toa_src");
   HIPCHK(hipSetDevice(m->device));
   const GasDesc gd{ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar};
-  const size_t n2 = (size_t)ncol * nlay, n2l = (size_t)ncol * (nlay + 1), n3 = n2 * m->ng;
   static const char *kNot2str = "shortwave must use ty_optical_props_2str";   // :462
   if (ncol == 0) return two_stream ? 0 : fail(kNot2str);
-
-  if (memspace == ECCKD_DEVICE) {
-    if (gas_optics_sw_dev(m, f32, ncol, nlay, plev, tlay, gd, tau, ssa, g, toa_src, static_cast<hipStream_t>(stream)))
-      return 1;
-    return two_stream ? 0 : fail(kNot2str);
-  }
-  if (memspace != ECCKD_HOST && memspace != ECCKD_MIXED) return fail("ecckd: bad memspace");
-  const bool mixed = memspace == ECCKD_MIXED;   // tau, ssa, g: caller's device buffers; toa_src and the inputs: host
-
-  ecckd_model *mm = const_cast<ecckd_model *>(m);
-  std::lock_guard<std::mutex> lock(mm->mu);
-  hipStream_t s = mm->host_stream;
-  const size_t es = esz(f32);
-  size_t need = align256(n2l * es) + align256(n2 * es) + staged_gas_bytes(gd, ncol, nlay, f32) +
-                align256((size_t)ncol * m->ng * es);
-  if (!mixed) need += align256(n3 * es) * 3;
-  if (grow_arena(mm, need)) return 1;
-  Bump b(mm->arena, f32);
-  double *d_plev = b.take(n2l), *d_tlay = b.take(n2);
-  if (h2d(d_plev, plev, n2l, f32, s) || h2d(d_tlay, tlay, n2, f32, s)) return 1;
-  StagedGases sg;
-  if (stage_gases(gd, ncol, nlay, b, s, sg)) return 1;
-  double *d_toa = b.take((size_t)ncol * m->ng);
-  double *d_tau = tau, *d_ssa = ssa, *d_g = g;
-  if (!mixed) { d_tau = b.take(n3); d_ssa = b.take(n3); d_g = b.take(n3); }
-  if (gas_optics_sw_dev(m, f32, ncol, nlay, d_plev, d_tlay, sg.gd, d_tau, two_stream ? d_ssa : nullptr,
-                        two_stream ? d_g : nullptr, d_toa, s))
+  if (memspace != ECCKD_DEVICE && memspace != ECCKD_HOST && memspace != ECCKD_MIXED) return fail("ecckd: bad memspace");
+  // ECCKD_MIXED: tau, ssa, g are the caller's device buffers; toa_src and the inputs are host arrays
+  const Counts n(ncol, nlay, m->ng, m->nband);
+  Stage st(const_cast<ecckd_model *>(m), memspace, stream, f32);
+  const double *d_plev = nullptr, *d_tlay = nullptr;
+  GasDesc d_gd{};
+  double *d_tau = nullptr, *d_ssa = nullptr, *d_g = nullptr, *d_toa = nullptr;
+  if (st.open([&] {
+        d_plev = st.in(plev, n.lev); d_tlay = st.in(tlay, n.lay);
+        d_gd = st.gases(gd, ncol, nlay);
+        d_tau = st.out(tau, n.lay_g, kBig);
+        d_ssa = st.out(ssa, n.lay_g, kBig, two_stream); d_g = st.out(g, n.lay_g, kBig, two_stream);
+        d_toa = st.out(toa_src, n.col_g, false, two_stream);
+      }))
     return 1;
-  if (!mixed) {
-    if (d2h(tau, d_tau, n3, f32, s)) return 1;
-    if (two_stream && (d2h(ssa, d_ssa, n3, f32, s) || d2h(g, d_g, n3, f32, s))) return 1;
-  }
-  if (two_stream && d2h(toa_src, d_toa, (size_t)ncol * m->ng, f32, s)) return 1;
-  HIPCHK(hipStreamSynchronize(s));
+  if (gas_optics_sw_dev(m, f32, ncol, nlay, d_plev, d_tlay, d_gd, d_tau, d_ssa, d_g, d_toa, st.stream)) return 1;
+  if (st.close()) return 1;
   return two_stream ? 0 : fail(kNot2str);
 }
 
@@ -1319,69 +1344,40 @@ static int rte_lw_impl(const Call &c, int device, int ncol, int nlay, int ngpt, 
   a.f32 = c.f32;
   a.shared_levels = c.shared_levels;
   fill_lw_options(a, n_gauss_angles, c.f32);
-  const size_t n3 = (size_t)ncol * nlay * ngpt, n2l = (size_t)ncol * (nlay + 1);
   const size_t scratch = ecckd::rte_lw_scratch_bytes(ncol, nlay, ngpt);
-  const hipStream_t launch_stream = memspace == ECCKD_DEVICE ? static_cast<hipStream_t>(stream) : nullptr;
+  Stage st(device, memspace, stream, c.f32);
   ScratchLease lease;   // (held until the kernels of this call have been launched)
   if (scratch) {   // more than 96 layers: stream-ordered scratch ring, no synchronisation (see ScratchPool)
     void *sp = nullptr;
-    if (stream_scratch(device, launch_stream, scratch, &sp, lease)) return 1;
+    if (stream_scratch(device, st.stream, scratch, &sp, lease)) return 1;
     a.scratch = static_cast<double *>(sp);
   } else if (g_opt.lw_tail_split.load()) {   // tail tiles one g-pair per wave (rte_lw_tail_plan); optional, same bits
     long first = -1;
     const size_t need = ecckd::rte_lw_tail_plan(a, simd_slots(device), &first);
     if (need) {
-      if (void *sp = stream_scratch_optional(device, launch_stream, need, lease)) {
+      if (void *sp = stream_scratch_optional(device, st.stream, need, lease)) {
         a.partials = static_cast<double *>(sp);
         a.tail_first = first;
       }
     }
   }
-  if (memspace == ECCKD_DEVICE) {
-    a.tau = tau; a.lay_source = lay_source; a.lev_source_inc = lev_source_inc;
-    a.lev_source_dec = lev_source_dec; a.sfc_source = sfc_source; a.sfc_emis = sfc_emis;
-    a.flux_up = flux_up; a.flux_dn = flux_dn;
-    a.inc_flux = inc_flux;
-    {
-      ProfScope prof("rte_lw", launch_stream);
-      HIPCHK(ecckd::launch_rte_lw(a, launch_stream));
-    }
-    return 0;
-  }
-  if (memspace != ECCKD_HOST && memspace != ECCKD_MIXED) return fail("ecckd: bad memspace");
+  if (memspace != ECCKD_DEVICE && memspace != ECCKD_HOST && memspace != ECCKD_MIXED) return fail("ecckd: bad memspace");
   // ECCKD_MIXED: tau, the three source arrays and sfc_source are device buffers (what gas_optics left there);
   // sfc_emis / inc_flux come from the host and the fluxes go back to it
-  const bool mixed = memspace == ECCKD_MIXED;
-  Arena &ar = g_solver_arena[device];
-  std::lock_guard<std::mutex> lock(ar.mu);
-  const size_t es = esz(c.f32);
-  const size_t need = (mixed ? 0 : align256(n3 * es) * 4 + align256((size_t)ncol * ngpt * es)) +
-                      align256((size_t)ncol * ngpt * es) + align256((size_t)ncol * nband * es) +
-                      align256(n2l * es) * 2;
-  if (ar.ensure(need)) return 1;
-  Bump b(ar.p, c.f32);
-  hipStream_t s = nullptr;
-  if (mixed) {
-    a.tau = tau; a.lay_source = lay_source; a.lev_source_inc = lev_source_inc; a.lev_source_dec = lev_source_dec;
-    a.sfc_source = sfc_source;
-  } else {
-    double *d_tau = b.take(n3), *d_lay = b.take(n3), *d_inc = b.take(n3), *d_dec = b.take(n3);
-    double *d_sfc = b.take((size_t)ncol * ngpt);
-    if (h2d(d_tau, tau, n3, c.f32, s) || h2d(d_lay, lay_source, n3, c.f32, s) || h2d(d_inc, lev_source_inc, n3, c.f32, s) ||
-        h2d(d_dec, lev_source_dec, n3, c.f32, s) || h2d(d_sfc, sfc_source, (size_t)ncol * ngpt, c.f32, s))
-      return 1;
-    a.tau = d_tau; a.lay_source = d_lay; a.lev_source_inc = d_inc; a.lev_source_dec = d_dec; a.sfc_source = d_sfc;
+  const Counts n(ncol, nlay, ngpt, nband);
+  if (st.open([&] {
+        a.tau = st.in(tau, n.lay_g, kBig); a.lay_source = st.in(lay_source, n.lay_g, kBig);
+        a.lev_source_inc = st.in(lev_source_inc, n.lay_g, kBig); a.lev_source_dec = st.in(lev_source_dec, n.lay_g, kBig);
+        a.sfc_source = st.in(sfc_source, n.col_g, kBig);
+        a.sfc_emis = st.in(sfc_emis, n.col_b); a.inc_flux = st.in(inc_flux, n.col_g);
+        a.flux_up = st.out(flux_up, n.lev); a.flux_dn = st.out(flux_dn, n.lev);
+      }))
+    return 1;
+  {
+    ProfScope prof("rte_lw", st.stream);
+    HIPCHK(ecckd::launch_rte_lw(a, st.stream));
   }
-  double *d_emis = b.take((size_t)ncol * nband), *d_up = b.take(n2l), *d_dn = b.take(n2l);
-  double *d_incf = b.take((size_t)ncol * ngpt);
-  if (h2d(d_emis, sfc_emis, (size_t)ncol * nband, c.f32, s)) return 1;
-  if (inc_flux && h2d(d_incf, inc_flux, (size_t)ncol * ngpt, c.f32, s)) return 1;
-  a.sfc_emis = d_emis; a.flux_up = d_up; a.flux_dn = d_dn;
-  a.inc_flux = inc_flux ? d_incf : nullptr;
-  HIPCHK(ecckd::launch_rte_lw(a, s));
-  if (d2h(flux_up, d_up, n2l, c.f32, s) || d2h(flux_dn, d_dn, n2l, c.f32, s)) return 1;
-  HIPCHK(hipStreamSynchronize(s));
-  return 0;
+  return st.close();
 }
 
 int ecckd_rte_lw(int device, int ncol, int nlay, int ngpt, int top_at_1, int n_gauss_angles,
@@ -1459,29 +1455,19 @@ int ecckd_rte_lw_jac(int device, int ncol, int nlay, int ngpt, int top_at_1, int
     return 1;
   if (ncol == 0) return 0;
   fill_jac_args(j, ncol, nlay, ngpt, top_at_1, n_gauss_angles, nband);
-  const size_t n3 = (size_t)ncol * nlay * ngpt, n2l = (size_t)ncol * (nlay + 1);
-  if (memspace == ECCKD_DEVICE) {
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    j.tau = tau; j.sfc_source_jac = sfc_source_jac; j.sfc_emis = sfc_emis; j.flux_up_jac = flux_up_jac;
-    ProfScope prof("rte_lw_jac", st);
-    HIPCHK(ecckd::launch_rte_lw_jac(j, nullptr, 0, 0., 1., st));
-    return 0;
-  }
-  // host arrays: staged in the solver arena, which rte_lw_impl has sized for more than this
-  Arena &ar = g_solver_arena[device];
-  std::lock_guard<std::mutex> lock(ar.mu);
-  if (ar.ensure(align256(n3 * 8) + align256((size_t)ncol * ngpt * 8) + align256((size_t)ncol * nband * 8) + align256(n2l * 8))) return 1;
-  Bump b(ar.p, false);
-  hipStream_t s = nullptr;
-  double *d_tau = b.take(n3), *d_sj = b.take((size_t)ncol * ngpt), *d_emis = b.take((size_t)ncol * nband), *d_jac = b.take(n2l);
-  if (h2d(d_tau, tau, n3, false, s) || h2d(d_sj, sfc_source_jac, (size_t)ncol * ngpt, false, s) ||
-      h2d(d_emis, sfc_emis, (size_t)ncol * nband, false, s))
+  // (host arrays: staged once more, behind the flux call, which has copied its fluxes back and let the arena go)
+  const Counts n(ncol, nlay, ngpt, nband);
+  Stage st(device, memspace, stream, false);
+  if (st.open([&] {
+        j.tau = st.in(tau, n.lay_g); j.sfc_source_jac = st.in(sfc_source_jac, n.col_g); j.sfc_emis = st.in(sfc_emis, n.col_b);
+        j.flux_up_jac = st.out(flux_up_jac, n.lev);
+      }))
     return 1;
-  j.tau = d_tau; j.sfc_source_jac = d_sj; j.sfc_emis = d_emis; j.flux_up_jac = d_jac;
-  HIPCHK(ecckd::launch_rte_lw_jac(j, nullptr, 0, 0., 1., s));
-  if (d2h(flux_up_jac, d_jac, n2l, false, s)) return 1;
-  HIPCHK(hipStreamSynchronize(s));
-  return 0;
+  {
+    ProfScope prof("rte_lw_jac", st.stream);
+    HIPCHK(ecckd::launch_rte_lw_jac(j, nullptr, 0, 0., 1., st.stream));
+  }
+  return st.close();
 }
 
 static const double kSwKFloorF32 = 1.e-6;      // lower bound of "sw_k_floor" in the single-precision shortwave solvers ...
@@ -1522,8 +1508,7 @@ static int rte_sw_impl(const Call &c, int device, int ncol, int nlay, int ngpt, 
     a.toa_scale = dv->toa_scale;
     if (dv->part_tau) { a.allsky = 1; a.part_tau = dv->part_tau; a.part_ssa = dv->part_ssa; a.part_g = dv->part_g; a.part_mask = dv->part_mask; }
   }
-  const size_t n3 = (size_t)ncol * nlay * ngpt, n2l = (size_t)ncol * (nlay + 1);
-  const hipStream_t launch_stream = memspace == ECCKD_DEVICE ? static_cast<hipStream_t>(stream) : nullptr;
+  Stage st(device, memspace, stream, c.f32);
   ScratchLease lease;   // (held until the kernels of this call have been launched)
   const int cus = simd_slots(device) / 4;
   a.use_sys = g_opt.sw_solver.load() == 0 && ecckd::rte_sw_sys_applies(a) && cus > 0;
@@ -1533,7 +1518,7 @@ static int rte_sw_impl(const Call &c, int device, int ncol, int nlay, int ngpt, 
       const size_t need = ecckd::rte_sw_sys_plan(a, cus);
       if (need) {
         if (dv) a.partials = dv->room;   // (ecckd_sw_fluxes sized its block with sw_fluxes_solver_bytes)
-        else if (void *sp = stream_scratch_optional(device, launch_stream, need, lease)) a.partials = static_cast<double *>(sp);
+        else if (void *sp = stream_scratch_optional(device, st.stream, need, lease)) a.partials = static_cast<double *>(sp);
         if (!a.partials) { a.sys_tail_first = -1; a.sys_gchunk = 0; }
       }
     }
@@ -1557,7 +1542,7 @@ static int rte_sw_impl(const Call &c, int device, int ncol, int nlay, int ngpt, 
     size_t partials_at = 0;
     const size_t need = ecckd::rte_sw_tail_plan(a, &first, &partials_at);
     if (need) {
-      if (void *sp = stream_scratch_optional(device, launch_stream, need > scratch ? need : scratch, lease)) {
+      if (void *sp = stream_scratch_optional(device, st.stream, need > scratch ? need : scratch, lease)) {
         a.scratch = static_cast<double *>(sp);
         a.partials = reinterpret_cast<double *>(static_cast<char *>(sp) + partials_at);
         a.tail_first = first;
@@ -1566,52 +1551,25 @@ static int rte_sw_impl(const Call &c, int device, int ncol, int nlay, int ngpt, 
   }
   if (scratch && a.tail_first < 0) {   // stream-ordered scratch ring, no synchronisation (see ScratchPool)
     void *sp = nullptr;
-    if (stream_scratch(device, launch_stream, scratch, &sp, lease)) return 1;
+    if (stream_scratch(device, st.stream, scratch, &sp, lease)) return 1;
     a.scratch = static_cast<double *>(sp);
   }
   }
-  auto launch = [&](hipStream_t st) { return a.use_sys ? ecckd::launch_rte_sw_sys(a, cus, st) : ecckd::launch_rte_sw(a, st); };
-  if (memspace == ECCKD_DEVICE) {
-    a.tau = tau; a.ssa = ssa; a.g = g; a.mu0 = mu0; a.toa = toa_flux;
-    a.alb_dir = sfc_alb_dir; a.alb_dif = sfc_alb_dif;
-    a.flux_up = flux_up; a.flux_dn = flux_dn; a.flux_dir = flux_dir;
-    {
-      ProfScope prof("rte_sw", launch_stream);
-      HIPCHK(launch(launch_stream));
-    }
-    return 0;
-  }
-  if (memspace != ECCKD_HOST && memspace != ECCKD_MIXED) return fail("ecckd: bad memspace");
-  const bool mixed = memspace == ECCKD_MIXED;   // tau, ssa, g: device buffers; everything else host
-  Arena &ar = g_solver_arena[device];
-  std::lock_guard<std::mutex> lock(ar.mu);
-  const size_t es = esz(c.f32);
-  const size_t need = (mixed ? 0 : align256(n3 * es) * 3) + align256((size_t)ncol * es) +
-                      align256((size_t)ncol * ngpt * es) + align256((size_t)ncol * nband * es) * 2 +
-                      align256(n2l * es) * 3;
-  if (ar.ensure(need)) return 1;
-  Bump b(ar.p, c.f32);
-  hipStream_t s = nullptr;
-  if (mixed) {
-    a.tau = tau; a.ssa = ssa; a.g = g;
-  } else {
-    double *d_tau = b.take(n3), *d_ssa = b.take(n3), *d_g = b.take(n3);
-    if (h2d(d_tau, tau, n3, c.f32, s) || h2d(d_ssa, ssa, n3, c.f32, s) || h2d(d_g, g, n3, c.f32, s)) return 1;
-    a.tau = d_tau; a.ssa = d_ssa; a.g = d_g;
-  }
-  double *d_mu0 = b.take(ncol);
-  double *d_toa = b.take((size_t)ncol * ngpt), *d_ad = b.take((size_t)ncol * nband), *d_af = b.take((size_t)ncol * nband);
-  double *d_up = b.take(n2l), *d_dn = b.take(n2l), *d_dir = b.take(n2l);
-  if (h2d(d_mu0, mu0, ncol, c.f32, s) || h2d(d_toa, toa_flux, (size_t)ncol * ngpt, c.f32, s) ||
-      h2d(d_ad, sfc_alb_dir, (size_t)ncol * nband, c.f32, s) || h2d(d_af, sfc_alb_dif, (size_t)ncol * nband, c.f32, s))
+  if (memspace != ECCKD_DEVICE && memspace != ECCKD_HOST && memspace != ECCKD_MIXED) return fail("ecckd: bad memspace");
+  // ECCKD_MIXED: tau, ssa, g are device buffers; everything else is host
+  const Counts n(ncol, nlay, ngpt, nband);
+  if (st.open([&] {
+        a.tau = st.in(tau, n.lay_g, kBig); a.ssa = st.in(ssa, n.lay_g, kBig); a.g = st.in(g, n.lay_g, kBig);
+        a.mu0 = st.in(mu0, n.col); a.toa = st.in(toa_flux, n.col_g);
+        a.alb_dir = st.in(sfc_alb_dir, n.col_b); a.alb_dif = st.in(sfc_alb_dif, n.col_b);
+        a.flux_up = st.out(flux_up, n.lev); a.flux_dn = st.out(flux_dn, n.lev); a.flux_dir = st.out(flux_dir, n.lev);
+      }))
     return 1;
-  a.mu0 = d_mu0; a.toa = d_toa; a.alb_dir = d_ad; a.alb_dif = d_af;
-  a.flux_up = d_up; a.flux_dn = d_dn; a.flux_dir = flux_dir ? d_dir : nullptr;
-  HIPCHK(launch(s));
-  if (d2h(flux_up, d_up, n2l, c.f32, s) || d2h(flux_dn, d_dn, n2l, c.f32, s)) return 1;
-  if (flux_dir && d2h(flux_dir, d_dir, n2l, c.f32, s)) return 1;
-  HIPCHK(hipStreamSynchronize(s));
-  return 0;
+  {
+    ProfScope prof("rte_sw", st.stream);
+    HIPCHK(a.use_sys ? ecckd::launch_rte_sw_sys(a, cus, st.stream) : ecckd::launch_rte_sw(a, st.stream));
+  }
+  return st.close();
 }
 
 int ecckd_rte_sw(int device, int ncol, int nlay, int ngpt, int top_at_1, const double *tau,
@@ -1656,32 +1614,21 @@ int ecckd_lw_solver_noscat_gpt(int device, int ncol, int nlay, int ngpt, int top
   a.ncol = ncol; a.nlay = nlay; a.ng = ngpt; a.top_at_1 = top_at_1 ? 1 : 0; a.nmus = nmus;
   for (int k = 0; k < nmus; ++k) { a.Ds[k] = Ds[k]; a.wts[k] = weights[k]; }
   fill_gpt_options(a);
-  const size_t n3 = (size_t)ncol * nlay * ngpt, n2 = (size_t)ncol * ngpt, nf = (size_t)ncol * (nlay + 1) * ngpt;
-  if (memspace == ECCKD_DEVICE) {
-    a.tau = tau; a.lay_source = lay_source; a.lev_source_inc = lev_source_inc; a.lev_source_dec = lev_source_dec;
-    a.sfc_emis = sfc_emis; a.sfc_src = sfc_src; a.inc_flux = inc_flux; a.flux_up = gpt_flux_up; a.flux_dn = gpt_flux_dn;
-    ProfScope prof("lw_gpt", static_cast<hipStream_t>(stream));
-    HIPCHK(ecckd::launch_lw_gpt(a, static_cast<hipStream_t>(stream)));
-    return 0;
-  }
-  if (memspace != ECCKD_HOST) return fail("ecckd: bad memspace");
-  Arena &ar = g_solver_arena[device];
-  std::lock_guard<std::mutex> lock(ar.mu);
-  if (ar.ensure(align256(n3 * 8) * 4 + align256(n2 * 8) * 3 + align256(nf * 8) * 2)) return 1;
-  Bump b(ar.p, false);
-  double *d_tau = b.take(n3), *d_lay = b.take(n3), *d_inc = b.take(n3), *d_dec = b.take(n3);
-  double *d_emis = b.take(n2), *d_src = b.take(n2), *d_incf = b.take(n2), *d_up = b.take(nf), *d_dn = b.take(nf);
-  hipStream_t s = nullptr;
-  if (h2d(d_tau, tau, n3, false, s) || h2d(d_lay, lay_source, n3, false, s) || h2d(d_inc, lev_source_inc, n3, false, s) ||
-      h2d(d_dec, lev_source_dec, n3, false, s) || h2d(d_emis, sfc_emis, n2, false, s) || h2d(d_src, sfc_src, n2, false, s))
+  if (memspace != ECCKD_DEVICE && memspace != ECCKD_HOST) return fail("ecckd: bad memspace");
+  const Counts n(ncol, nlay, ngpt, 1);
+  Stage st(device, memspace, stream, false);
+  if (st.open([&] {
+        a.tau = st.in(tau, n.lay_g); a.lay_source = st.in(lay_source, n.lay_g);
+        a.lev_source_inc = st.in(lev_source_inc, n.lay_g); a.lev_source_dec = st.in(lev_source_dec, n.lay_g);
+        a.sfc_emis = st.in(sfc_emis, n.col_g); a.sfc_src = st.in(sfc_src, n.col_g); a.inc_flux = st.in(inc_flux, n.col_g);
+        a.flux_up = st.out(gpt_flux_up, n.lev * ngpt); a.flux_dn = st.out(gpt_flux_dn, n.lev * ngpt);
+      }))
     return 1;
-  if (inc_flux && h2d(d_incf, inc_flux, n2, false, s)) return 1;
-  a.tau = d_tau; a.lay_source = d_lay; a.lev_source_inc = d_inc; a.lev_source_dec = d_dec; a.sfc_emis = d_emis;
-  a.sfc_src = d_src; a.inc_flux = inc_flux ? d_incf : nullptr; a.flux_up = d_up; a.flux_dn = d_dn;
-  HIPCHK(ecckd::launch_lw_gpt(a, s));
-  if (d2h(gpt_flux_up, d_up, nf, false, s) || d2h(gpt_flux_dn, d_dn, nf, false, s)) return 1;
-  HIPCHK(hipStreamSynchronize(s));
-  return 0;
+  {
+    ProfScope prof("lw_gpt", st.stream);
+    HIPCHK(ecckd::launch_lw_gpt(a, st.stream));
+  }
+  return st.close();
 }
 
 int ecckd_sw_solver_2stream_gpt(int device, int ncol, int nlay, int ngpt, int top_at_1, const double *tau, const double *ssa,
@@ -1697,34 +1644,22 @@ int ecckd_sw_solver_2stream_gpt(int device, int ncol, int nlay, int ngpt, int to
   ecckd::RteGptArgs a{};
   a.ncol = ncol; a.nlay = nlay; a.ng = ngpt; a.top_at_1 = top_at_1 ? 1 : 0; a.nmus = 1;
   fill_gpt_options(a);
-  const size_t n3 = (size_t)ncol * nlay * ngpt, n2 = (size_t)ncol * ngpt, nf = (size_t)ncol * (nlay + 1) * ngpt;
-  if (memspace == ECCKD_DEVICE) {
-    a.tau = tau; a.ssa = ssa; a.g = g; a.mu0 = mu0; a.fdir_top = flux_dir_top; a.inc_dif = inc_flux_dif;
-    a.alb_dir = sfc_alb_dir; a.alb_dif = sfc_alb_dif; a.flux_up = gpt_flux_up; a.flux_dn = gpt_flux_dn; a.flux_dir = gpt_flux_dir;
-    ProfScope prof("sw_gpt", static_cast<hipStream_t>(stream));
-    HIPCHK(ecckd::launch_sw_gpt(a, static_cast<hipStream_t>(stream)));
-    return 0;
-  }
-  if (memspace != ECCKD_HOST) return fail("ecckd: bad memspace");
-  Arena &ar = g_solver_arena[device];
-  std::lock_guard<std::mutex> lock(ar.mu);
-  if (ar.ensure(align256(n3 * 8) * 3 + align256((size_t)ncol * 8) + align256(n2 * 8) * 4 + align256(nf * 8) * 3)) return 1;
-  Bump b(ar.p, false);
-  double *d_tau = b.take(n3), *d_ssa = b.take(n3), *d_g = b.take(n3), *d_mu0 = b.take(ncol);
-  double *d_top = b.take(n2), *d_dif = b.take(n2), *d_ad = b.take(n2), *d_af = b.take(n2);
-  double *d_up = b.take(nf), *d_dn = b.take(nf), *d_dir = b.take(nf);
-  hipStream_t s = nullptr;
-  if (h2d(d_tau, tau, n3, false, s) || h2d(d_ssa, ssa, n3, false, s) || h2d(d_g, g, n3, false, s) || h2d(d_mu0, mu0, ncol, false, s) ||
-      h2d(d_top, flux_dir_top, n2, false, s) || h2d(d_ad, sfc_alb_dir, n2, false, s) || h2d(d_af, sfc_alb_dif, n2, false, s))
+  if (memspace != ECCKD_DEVICE && memspace != ECCKD_HOST) return fail("ecckd: bad memspace");
+  const Counts n(ncol, nlay, ngpt, 1);
+  Stage st(device, memspace, stream, false);
+  if (st.open([&] {
+        a.tau = st.in(tau, n.lay_g); a.ssa = st.in(ssa, n.lay_g); a.g = st.in(g, n.lay_g); a.mu0 = st.in(mu0, n.col);
+        a.fdir_top = st.in(flux_dir_top, n.col_g); a.inc_dif = st.in(inc_flux_dif, n.col_g);
+        a.alb_dir = st.in(sfc_alb_dir, n.col_g); a.alb_dif = st.in(sfc_alb_dif, n.col_g);
+        a.flux_up = st.out(gpt_flux_up, n.lev * ngpt); a.flux_dn = st.out(gpt_flux_dn, n.lev * ngpt);
+        a.flux_dir = st.out(gpt_flux_dir, n.lev * ngpt);
+      }))
     return 1;
-  if (inc_flux_dif && h2d(d_dif, inc_flux_dif, n2, false, s)) return 1;
-  a.tau = d_tau; a.ssa = d_ssa; a.g = d_g; a.mu0 = d_mu0; a.fdir_top = d_top; a.inc_dif = inc_flux_dif ? d_dif : nullptr;
-  a.alb_dir = d_ad; a.alb_dif = d_af; a.flux_up = d_up; a.flux_dn = d_dn; a.flux_dir = gpt_flux_dir ? d_dir : nullptr;
-  HIPCHK(ecckd::launch_sw_gpt(a, s));
-  if (d2h(gpt_flux_up, d_up, nf, false, s) || d2h(gpt_flux_dn, d_dn, nf, false, s)) return 1;
-  if (gpt_flux_dir && d2h(gpt_flux_dir, d_dir, nf, false, s)) return 1;
-  HIPCHK(hipStreamSynchronize(s));
-  return 0;
+  {
+    ProfScope prof("sw_gpt", st.stream);
+    HIPCHK(ecckd::launch_sw_gpt(a, st.stream));
+  }
+  return st.close();
 }
 
 // ---- two-stream longwave solver (kernels_rte_lw_2str.hip): clouds scatter ----
@@ -1754,37 +1689,24 @@ int ecckd_rte_lw_2stream(int device, int ncol, int nlay, int ngpt, int top_at_1,
   if (ncol == 0) return 0;
   a.ncol = ncol; a.nlay = nlay; a.ng = ngpt; a.top_at_1 = top_at_1 ? 1 : 0; a.nband = nband;
   a.exact_division = g_arith.load() != 0;
-  const size_t n3 = (size_t)ncol * nlay * ngpt, n2l = (size_t)ncol * (nlay + 1), n2g = (size_t)ncol * ngpt;
-  const hipStream_t launch_stream = memspace == ECCKD_DEVICE ? static_cast<hipStream_t>(stream) : nullptr;
+  const Counts n(ncol, nlay, ngpt, nband);
+  Stage st(device, memspace, stream, false);
   ScratchLease lease;   // (held until the kernel of this call has been launched)
   void *sp = nullptr;
-  if (stream_scratch(device, launch_stream, ecckd::rte_lw_2str_scratch_bytes(ncol, nlay, ngpt), &sp, lease)) return 1;
+  if (stream_scratch(device, st.stream, ecckd::rte_lw_2str_scratch_bytes(ncol, nlay, ngpt), &sp, lease)) return 1;
   a.scratch = static_cast<double *>(sp);
-  if (memspace == ECCKD_DEVICE) {
-    a.tau = tau; a.ssa = ssa; a.g = g; a.lev_source_inc = lev_source_inc; a.lev_source_dec = lev_source_dec;
-    a.sfc_source = sfc_source; a.sfc_emis = sfc_emis; a.inc_flux = inc_flux; a.flux_up = flux_up; a.flux_dn = flux_dn;
-    ProfScope prof("rte_lw_2stream", launch_stream);
-    HIPCHK(ecckd::launch_rte_lw_2str(a, launch_stream));
-    return 0;
-  }
-  Arena &ar = g_solver_arena[device];
-  std::lock_guard<std::mutex> lock(ar.mu);
-  if (ar.ensure(align256(n3 * 8) * 5 + align256(n2g * 8) * 2 + align256((size_t)ncol * nband * 8) + align256(n2l * 8) * 2)) return 1;
-  Bump b(ar.p, false);
-  hipStream_t s = nullptr;
-  double *d_tau = b.take(n3), *d_ssa = b.take(n3), *d_g = b.take(n3), *d_inc = b.take(n3), *d_dec = b.take(n3);
-  double *d_sfc = b.take(n2g), *d_incf = b.take(n2g), *d_emis = b.take((size_t)ncol * nband), *d_up = b.take(n2l), *d_dn = b.take(n2l);
-  if (h2d(d_tau, tau, n3, false, s) || h2d(d_ssa, ssa, n3, false, s) || h2d(d_g, g, n3, false, s) ||
-      h2d(d_inc, lev_source_inc, n3, false, s) || h2d(d_dec, lev_source_dec, n3, false, s) || h2d(d_sfc, sfc_source, n2g, false, s) ||
-      h2d(d_emis, sfc_emis, (size_t)ncol * nband, false, s))
+  if (st.open([&] {
+        a.tau = st.in(tau, n.lay_g); a.ssa = st.in(ssa, n.lay_g); a.g = st.in(g, n.lay_g);
+        a.lev_source_inc = st.in(lev_source_inc, n.lay_g); a.lev_source_dec = st.in(lev_source_dec, n.lay_g);
+        a.sfc_source = st.in(sfc_source, n.col_g); a.sfc_emis = st.in(sfc_emis, n.col_b); a.inc_flux = st.in(inc_flux, n.col_g);
+        a.flux_up = st.out(flux_up, n.lev); a.flux_dn = st.out(flux_dn, n.lev);
+      }))
     return 1;
-  if (inc_flux && h2d(d_incf, inc_flux, n2g, false, s)) return 1;
-  a.tau = d_tau; a.ssa = d_ssa; a.g = d_g; a.lev_source_inc = d_inc; a.lev_source_dec = d_dec; a.sfc_source = d_sfc;
-  a.sfc_emis = d_emis; a.inc_flux = inc_flux ? d_incf : nullptr; a.flux_up = d_up; a.flux_dn = d_dn;
-  HIPCHK(ecckd::launch_rte_lw_2str(a, s));
-  if (d2h(flux_up, d_up, n2l, false, s) || d2h(flux_dn, d_dn, n2l, false, s)) return 1;
-  HIPCHK(hipStreamSynchronize(s));
-  return 0;
+  {
+    ProfScope prof("rte_lw_2stream", st.stream);
+    HIPCHK(ecckd::launch_rte_lw_2str(a, st.stream));
+  }
+  return st.close();
 }
 
 int ecckd_lw_solver_2stream_gpt(int device, int ncol, int nlay, int ngpt, int top_at_1, const double *tau, const double *ssa,
@@ -1801,32 +1723,20 @@ int ecckd_lw_solver_2stream_gpt(int device, int ncol, int nlay, int ngpt, int to
   if (ncol == 0) return 0;
   ecckd::RteGptArgs a{};
   a.ncol = ncol; a.nlay = nlay; a.ng = ngpt; a.top_at_1 = top_at_1 ? 1 : 0; a.nmus = 1;
-  const size_t n3 = (size_t)ncol * nlay * ngpt, n2 = (size_t)ncol * ngpt, nf = (size_t)ncol * (nlay + 1) * ngpt;
-  if (memspace == ECCKD_DEVICE) {
-    a.tau = tau; a.ssa = ssa; a.g = g; a.lev_source_inc = lev_source_inc; a.lev_source_dec = lev_source_dec;
-    a.sfc_emis = sfc_emis; a.sfc_src = sfc_src; a.inc_flux = inc_flux; a.flux_up = gpt_flux_up; a.flux_dn = gpt_flux_dn;
-    ProfScope prof("lw_2str_gpt", static_cast<hipStream_t>(stream));
-    HIPCHK(ecckd::launch_lw_2str_gpt(a, static_cast<hipStream_t>(stream)));
-    return 0;
-  }
-  Arena &ar = g_solver_arena[device];
-  std::lock_guard<std::mutex> lock(ar.mu);
-  if (ar.ensure(align256(n3 * 8) * 5 + align256(n2 * 8) * 3 + align256(nf * 8) * 2)) return 1;
-  Bump b(ar.p, false);
-  double *d_tau = b.take(n3), *d_ssa = b.take(n3), *d_g = b.take(n3), *d_inc = b.take(n3), *d_dec = b.take(n3);
-  double *d_emis = b.take(n2), *d_src = b.take(n2), *d_incf = b.take(n2), *d_up = b.take(nf), *d_dn = b.take(nf);
-  hipStream_t s = nullptr;
-  if (h2d(d_tau, tau, n3, false, s) || h2d(d_ssa, ssa, n3, false, s) || h2d(d_g, g, n3, false, s) ||
-      h2d(d_inc, lev_source_inc, n3, false, s) || h2d(d_dec, lev_source_dec, n3, false, s) || h2d(d_emis, sfc_emis, n2, false, s) ||
-      h2d(d_src, sfc_src, n2, false, s))
+  const Counts n(ncol, nlay, ngpt, 1);
+  Stage st(device, memspace, stream, false);
+  if (st.open([&] {
+        a.tau = st.in(tau, n.lay_g); a.ssa = st.in(ssa, n.lay_g); a.g = st.in(g, n.lay_g);
+        a.lev_source_inc = st.in(lev_source_inc, n.lay_g); a.lev_source_dec = st.in(lev_source_dec, n.lay_g);
+        a.sfc_emis = st.in(sfc_emis, n.col_g); a.sfc_src = st.in(sfc_src, n.col_g); a.inc_flux = st.in(inc_flux, n.col_g);
+        a.flux_up = st.out(gpt_flux_up, n.lev * ngpt); a.flux_dn = st.out(gpt_flux_dn, n.lev * ngpt);
+      }))
     return 1;
-  if (inc_flux && h2d(d_incf, inc_flux, n2, false, s)) return 1;
-  a.tau = d_tau; a.ssa = d_ssa; a.g = d_g; a.lev_source_inc = d_inc; a.lev_source_dec = d_dec; a.sfc_emis = d_emis;
-  a.sfc_src = d_src; a.inc_flux = inc_flux ? d_incf : nullptr; a.flux_up = d_up; a.flux_dn = d_dn;
-  HIPCHK(ecckd::launch_lw_2str_gpt(a, s));
-  if (d2h(gpt_flux_up, d_up, nf, false, s) || d2h(gpt_flux_dn, d_dn, nf, false, s)) return 1;
-  HIPCHK(hipStreamSynchronize(s));
-  return 0;
+  {
+    ProfScope prof("lw_2str_gpt", st.stream);
+    HIPCHK(ecckd::launch_lw_2str_gpt(a, st.stream));
+  }
+  return st.close();
 }
 
 int ecckd_sum_broadband(int device, int ncol, int nlev, int ngpt, const double *spectral_flux, double *broadband_flux,
@@ -1860,6 +1770,8 @@ int ecckd_gas_optics_lw_tau(const ecckd_model_t *m, int ncol, int nlay, const do
   return gas_optical_depth_dev(m, false, nullptr, ncol, nlay, plev, tlay, gd, tau, false, nullptr, nullptr, nullptr, nullptr,
                                static_cast<hipStream_t>(stream));
 }
+
+static size_t r32(size_t n) { return (n + 31) & ~(size_t)31; }   // the next multiple of 32 doubles (256 bytes)
 
 // Scratch (in doubles) the fused solver needs besides tau: none at 60 layers (the Planck sources are recomputed inside the
 // layer-split solver); any other layer count takes the general route -- Planck kernel into scratch, then the
@@ -2032,85 +1944,45 @@ static int lw_fluxes_impl(const ecckd_model_t *m, int ncol, int nlay, const doub
   HIPCHK(hipSetDevice(m->device));
   if (ncol == 0) return 0;
   const GasDesc gd{ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar};
-  const size_t n2 = (size_t)ncol * nlay, n2l = (size_t)ncol * (nlay + 1), n3 = n2 * m->ng;
+  if (memspace != ECCKD_DEVICE && memspace != ECCKD_HOST) return fail("ecckd: bad memspace");
+  const Counts n(ncol, nlay, m->ng, m->nband);
   // the Jacobian inside the 60-layer flux kernel ("lw_jac_inline" = 1), or from the stand-alone kernel behind the flux pass
   const bool jac_in = jac && fused_lw_kernels_apply(m, nlay) && g_opt.lw_jac_inline.load() == 1;
-  if (memspace == ECCKD_DEVICE) {
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    void *tau_p = nullptr;   // tau lives in the stream's scratch block between the two kernels
-    ScratchLease lease;
-    const size_t extra = fused_scratch_doubles(m, ncol, nlay);
-    if (stream_scratch(m->device, st, (n3 + 32 + extra) * sizeof(double), &tau_p, lease)) return 1;
-    double *d_tau = static_cast<double *>(tau_p);
-    if (gas_optical_depth_dev(m, false, nullptr, ncol, nlay, plev, tlay, gd, d_tau, false, nullptr, nullptr, nullptr, nullptr, st)) return 1;
-    double *d_extra = extra ? d_tau + ((n3 + 31) & ~(size_t)31) : nullptr;
-    if (clr) {
-      if (lw_both_skies_dev(m, ncol, nlay, top_at_1, n_gauss_angles, d_tau, tlay, tlev, tsfc, sfc_emis, inc_flux, flux_up,
-                            flux_dn, d_extra, st, *pt, *clr, jac_in ? jac : nullptr))
-        return 1;
-    } else {
-      if (pt && !fused_lw_kernels_apply(m, nlay) && lw_increment_dev(m, ncol, nlay, d_tau, *pt, st)) return 1;
-      if (rte_lw_fused_dev(m, ncol, nlay, top_at_1, n_gauss_angles, d_tau, tlay, tlev, tsfc, sfc_emis, inc_flux, flux_up,
-                           flux_dn, d_extra, st, pt, nullptr, false, jac_in ? jac : nullptr))
-        return 1;
-    }
-    // (both skies, general route: behind the second solver pass, on the tau that pass saw)
-    return jac && !jac_in ? lw_jac_dev(m, ncol, nlay, top_at_1, n_gauss_angles, d_tau, tsfc, sfc_emis, pt, jac, st) : 0;
-  }
-  if (memspace != ECCKD_HOST) return fail("ecckd: bad memspace");
-  ecckd_model *mm = const_cast<ecckd_model *>(m);
-  std::lock_guard<std::mutex> lock(mm->mu);
-  hipStream_t s = mm->host_stream;
-  const size_t need = align256(n2l * 8) * 4 + align256(n2 * 8) + align256((size_t)ncol * 8) + staged_gas_bytes(gd, ncol, nlay, false) +
-                      align256((size_t)ncol * m->nband * 8) + align256((size_t)ncol * m->ng * 8) + align256(n3 * 8) +
-                      align256(fused_scratch_doubles(m, ncol, nlay) * 8) + (pt ? align256(n2 * m->nband * 8) * (pt->ssa ? 2 : 1) : 0) +
-                      (pt && pt->mask ? align256(n2 * 8) : 0) + (clr ? align256(n2l * 8) * 2 : 0) + (jac ? align256(n2l * 8) : 0);
-  if (grow_arena(mm, need)) return 1;
-  Bump b(mm->arena, false);
-  double *d_plev = b.take(n2l), *d_tlev = b.take(n2l), *d_tlay = b.take(n2), *d_tsfc = b.take(ncol);
-  double *d_upc = clr ? b.take(n2l) : nullptr, *d_dnc = clr ? b.take(n2l) : nullptr, *d_jac = jac ? b.take(n2l) : nullptr;
-  double *d_up = b.take(n2l), *d_dn = b.take(n2l), *d_emis = b.take((size_t)ncol * m->nband), *d_incf = b.take((size_t)ncol * m->ng);
-  if (h2d(d_plev, plev, n2l, false, s) || h2d(d_tlay, tlay, n2, false, s) || h2d(d_tsfc, tsfc, ncol, false, s) ||
-      h2d(d_tlev, tlev, n2l, false, s) || h2d(d_emis, sfc_emis, (size_t)ncol * m->nband, false, s))
-    return 1;
-  if (inc_flux && h2d(d_incf, inc_flux, (size_t)ncol * m->ng, false, s)) return 1;
-  StagedGases sg;
-  if (stage_gases(gd, ncol, nlay, b, s, sg)) return 1;
-  double *d_tau = b.take(n3);
+  // tau lives in the work block between the kernels; behind it what the general route needs (fused_scratch_doubles)
   const size_t extra = fused_scratch_doubles(m, ncol, nlay);
-  double *d_extra = extra ? b.take(extra) : nullptr;
-  LwParticles dp_{};
-  if (pt) {   // staged copies of the band optics
-    const size_t nb3 = n2 * m->nband;
-    double *q_tau = b.take(nb3), *q_ssa = pt->ssa ? b.take(nb3) : nullptr;
-    if (h2d(q_tau, pt->tau, nb3, false, s) || (pt->ssa && h2d(q_ssa, pt->ssa, nb3, false, s))) return 1;
-    dp_ = LwParticles{q_tau, q_ssa};
-    if (pt->mask) {   // (8-byte words: staged like an array of doubles)
-      double *q_mask = b.take(n2);
-      if (h2d(q_mask, reinterpret_cast<const double *>(pt->mask), n2, false, s)) return 1;
-      dp_.mask = reinterpret_cast<const unsigned long long *>(q_mask);
-    }
-  }
-  if (gas_optical_depth_dev(m, false, nullptr, ncol, nlay, d_plev, d_tlay, sg.gd, d_tau, false, nullptr, nullptr, nullptr, nullptr, s)) return 1;
+  Stage st(const_cast<ecckd_model *>(m), memspace, stream, false);
+  const double *d_plev = nullptr, *d_tlay = nullptr, *d_tsfc = nullptr, *d_tlev = nullptr, *d_emis = nullptr, *d_incf = nullptr;
+  double *d_up = nullptr, *d_dn = nullptr, *d_jac = nullptr, *d_tau = nullptr;
+  GasDesc d_gd{};
+  LwParticles d_pt{};
+  ClearFluxes d_clr{};
+  if (st.open([&] {
+        d_plev = st.in(plev, n.lev); d_tlay = st.in(tlay, n.lay); d_tsfc = st.in(tsfc, n.col); d_tlev = st.in(tlev, n.lev);
+        d_emis = st.in(sfc_emis, n.col_b); d_incf = st.in(inc_flux, n.col_g);
+        d_gd = st.gases(gd, ncol, nlay);
+        if (pt) d_pt = LwParticles{st.in(pt->tau, n.lay_b), st.in(pt->ssa, n.lay_b), st.in(pt->mask, n.lay)};
+        if (clr) d_clr = ClearFluxes{st.out(clr->up, n.lev), st.out(clr->dn, n.lev), nullptr};
+        d_up = st.out(flux_up, n.lev); d_dn = st.out(flux_dn, n.lev); d_jac = st.out(jac, n.lev);
+        d_tau = st.work((n.lay_g + 32 + extra) * sizeof(double));
+      }))
+    return 1;
+  double *d_extra = extra ? d_tau + r32(n.lay_g) : nullptr;
+  const hipStream_t s = st.stream;
+  if (gas_optical_depth_dev(m, false, nullptr, ncol, nlay, d_plev, d_tlay, d_gd, d_tau, false, nullptr, nullptr, nullptr, nullptr, s)) return 1;
   if (clr) {
-    if (lw_both_skies_dev(m, ncol, nlay, top_at_1, n_gauss_angles, d_tau, d_tlay, d_tlev, d_tsfc, d_emis, inc_flux ? d_incf : nullptr,
-                          d_up, d_dn, d_extra, s, dp_, ClearFluxes{d_upc, d_dnc, nullptr}, jac_in ? d_jac : nullptr))
+    if (lw_both_skies_dev(m, ncol, nlay, top_at_1, n_gauss_angles, d_tau, d_tlay, d_tlev, d_tsfc, d_emis, d_incf, d_up, d_dn, d_extra,
+                          s, d_pt, d_clr, jac_in ? d_jac : nullptr))
       return 1;
-    if (d2h(clr->up, d_upc, n2l, false, s) || d2h(clr->dn, d_dnc, n2l, false, s)) return 1;
   } else {
-    if (pt && !fused_lw_kernels_apply(m, nlay) && lw_increment_dev(m, ncol, nlay, d_tau, dp_, s)) return 1;
-    if (rte_lw_fused_dev(m, ncol, nlay, top_at_1, n_gauss_angles, d_tau, d_tlay, d_tlev, d_tsfc, d_emis,
-                         inc_flux ? d_incf : nullptr, d_up, d_dn, d_extra, s, pt ? &dp_ : nullptr, nullptr, false,
-                         jac_in ? d_jac : nullptr))
+    if (pt && !fused_lw_kernels_apply(m, nlay) && lw_increment_dev(m, ncol, nlay, d_tau, d_pt, s)) return 1;
+    if (rte_lw_fused_dev(m, ncol, nlay, top_at_1, n_gauss_angles, d_tau, d_tlay, d_tlev, d_tsfc, d_emis, d_incf, d_up, d_dn, d_extra, s,
+                         pt ? &d_pt : nullptr, nullptr, false, jac_in ? d_jac : nullptr))
       return 1;
   }
-  if (jac) {
-    if (!jac_in && lw_jac_dev(m, ncol, nlay, top_at_1, n_gauss_angles, d_tau, d_tsfc, d_emis, pt ? &dp_ : nullptr, d_jac, s)) return 1;
-    if (d2h(jac, d_jac, n2l, false, s)) return 1;
-  }
-  if (d2h(flux_up, d_up, n2l, false, s) || d2h(flux_dn, d_dn, n2l, false, s)) return 1;
-  HIPCHK(hipStreamSynchronize(s));
-  return 0;
+  // (both skies, general route: behind the second solver pass, on the tau that pass saw)
+  if (jac && !jac_in && lw_jac_dev(m, ncol, nlay, top_at_1, n_gauss_angles, d_tau, d_tsfc, d_emis, pt ? &d_pt : nullptr, d_jac, s))
+    return 1;
+  return st.close();
 }
 
 int ecckd_lw_fluxes(const ecckd_model_t *m, int ncol, int nlay, const double *plev, const double *tlay, const double *tsfc,
@@ -2193,7 +2065,6 @@ int ecckd_lw_fluxes_allsky_mcica(const ecckd_model_t *m, int ncol, int nlay, con
 
 // scratch of the device route, in doubles, in this order: optical depth, the three Planck arrays, the surface source (the
 // two-stream solver's ring follows, ecckd_rte_lw_2stream_scratch_bytes)
-static size_t r32(size_t n) { return (n + 31) & ~(size_t)31; }
 static size_t allsky_2stream_doubles(const ecckd_model *m, int ncol, int nlay) {
   const size_t n3 = (size_t)ncol * nlay * m->ng;
   return r32(n3) + 3 * n3 + r32((size_t)ncol * m->ng);
@@ -2244,51 +2115,29 @@ int ecckd_lw_fluxes_allsky_2stream(const ecckd_model_t *m, int ncol, int nlay, c
   HIPCHK(hipSetDevice(m->device));
   if (ncol == 0) return 0;
   const GasDesc gd{ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar};
-  const size_t n2 = (size_t)ncol * nlay, n2l = (size_t)ncol * (nlay + 1);
+  const Counts n(ncol, nlay, m->ng, m->nband);
   const size_t work_bytes = allsky_2stream_doubles(m, ncol, nlay) * sizeof(double) + ecckd::rte_lw_2str_scratch_bytes(ncol, nlay, m->ng);
-  if (memspace == ECCKD_DEVICE) {
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    void *wp = nullptr;
-    ScratchLease lease;
-    if (stream_scratch(m->device, st, work_bytes, &wp, lease)) return 1;
-    double *work = static_cast<double *>(wp);
-    if (gas_optical_depth_dev(m, false, nullptr, ncol, nlay, plev, tlay, gd, work, false, nullptr, nullptr, nullptr, nullptr, st)) return 1;
-    return lw_allsky_2stream_dev(m, ncol, nlay, tlay, tlev, tsfc, top_at_1, sfc_emis, inc_flux, tau_p, ssa_p, g_p, cloud_mask,
-                                 flux_up, flux_dn, work, st);
-  }
-  ecckd_model *mm = const_cast<ecckd_model *>(m);
-  std::lock_guard<std::mutex> lock(mm->mu);
-  hipStream_t s = mm->host_stream;
-  const size_t nb3 = n2 * m->nband;
-  const size_t need = align256(n2l * 8) * 4 + align256(n2 * 8) + align256((size_t)ncol * 8) + staged_gas_bytes(gd, ncol, nlay, false) +
-                      align256((size_t)ncol * m->nband * 8) + align256((size_t)ncol * m->ng * 8) + align256(work_bytes) +
-                      align256(nb3 * 8) * 3 + (cloud_mask ? align256(n2 * 8) : 0);
-  if (grow_arena(mm, need)) return 1;
-  Bump b(mm->arena, false);
-  double *d_plev = b.take(n2l), *d_tlev = b.take(n2l), *d_tlay = b.take(n2), *d_tsfc = b.take(ncol);
-  double *d_up = b.take(n2l), *d_dn = b.take(n2l), *d_emis = b.take((size_t)ncol * m->nband), *d_incf = b.take((size_t)ncol * m->ng);
-  if (h2d(d_plev, plev, n2l, false, s) || h2d(d_tlay, tlay, n2, false, s) || h2d(d_tsfc, tsfc, ncol, false, s) ||
-      h2d(d_tlev, tlev, n2l, false, s) || h2d(d_emis, sfc_emis, (size_t)ncol * m->nband, false, s))
-    return 1;
-  if (inc_flux && h2d(d_incf, inc_flux, (size_t)ncol * m->ng, false, s)) return 1;
-  StagedGases sg;
-  if (stage_gases(gd, ncol, nlay, b, s, sg)) return 1;
-  double *work = b.take(work_bytes / sizeof(double));
-  double *q_tau = b.take(nb3), *q_ssa = b.take(nb3), *q_g = b.take(nb3);
-  if (h2d(q_tau, tau_p, nb3, false, s) || h2d(q_ssa, ssa_p, nb3, false, s) || h2d(q_g, g_p, nb3, false, s)) return 1;
+  Stage st(const_cast<ecckd_model *>(m), memspace, stream, false);
+  const double *d_plev = nullptr, *d_tlay = nullptr, *d_tsfc = nullptr, *d_tlev = nullptr, *d_emis = nullptr, *d_incf = nullptr;
+  const double *q_tau = nullptr, *q_ssa = nullptr, *q_g = nullptr;
   const unsigned long long *q_mask = nullptr;
-  if (cloud_mask) {   // (8-byte words: staged like an array of doubles)
-    double *qm = b.take(n2);
-    if (h2d(qm, reinterpret_cast<const double *>(cloud_mask), n2, false, s)) return 1;
-    q_mask = reinterpret_cast<const unsigned long long *>(qm);
-  }
-  if (gas_optical_depth_dev(m, false, nullptr, ncol, nlay, d_plev, d_tlay, sg.gd, work, false, nullptr, nullptr, nullptr, nullptr, s)) return 1;
-  if (lw_allsky_2stream_dev(m, ncol, nlay, d_tlay, d_tlev, d_tsfc, top_at_1, d_emis, inc_flux ? d_incf : nullptr, q_tau, q_ssa, q_g,
-                            q_mask, d_up, d_dn, work, s))
+  double *d_up = nullptr, *d_dn = nullptr, *work = nullptr;
+  GasDesc d_gd{};
+  if (st.open([&] {
+        d_plev = st.in(plev, n.lev); d_tlay = st.in(tlay, n.lay); d_tsfc = st.in(tsfc, n.col); d_tlev = st.in(tlev, n.lev);
+        d_emis = st.in(sfc_emis, n.col_b); d_incf = st.in(inc_flux, n.col_g);
+        d_gd = st.gases(gd, ncol, nlay);
+        q_tau = st.in(tau_p, n.lay_b); q_ssa = st.in(ssa_p, n.lay_b); q_g = st.in(g_p, n.lay_b); q_mask = st.in(cloud_mask, n.lay);
+        d_up = st.out(flux_up, n.lev); d_dn = st.out(flux_dn, n.lev);
+        work = st.work(work_bytes);
+      }))
     return 1;
-  if (d2h(flux_up, d_up, n2l, false, s) || d2h(flux_dn, d_dn, n2l, false, s)) return 1;
-  HIPCHK(hipStreamSynchronize(s));
-  return 0;
+  if (gas_optical_depth_dev(m, false, nullptr, ncol, nlay, d_plev, d_tlay, d_gd, work, false, nullptr, nullptr, nullptr, nullptr, st.stream))
+    return 1;
+  if (lw_allsky_2stream_dev(m, ncol, nlay, d_tlay, d_tlev, d_tsfc, top_at_1, d_emis, d_incf, q_tau, q_ssa, q_g, q_mask, d_up, d_dn, work,
+                            st.stream))
+    return 1;
+  return st.close();
 }
 
 // The superset of the four fused longwave calls, with flux_up_jac of the sky that flux_up holds (include/ecckd_hip.h)
@@ -2332,95 +2181,52 @@ static int sw_fluxes_impl(bool f32, const ecckd_model_t *m, int ncol, int nlay, 
   HIPCHK(hipSetDevice(m->device));
   if (ncol == 0) return 0;
   const GasDesc gd{ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar};
-  const size_t n2 = (size_t)ncol * nlay, n2l = (size_t)ncol * (nlay + 1), n3 = n2 * m->ng;
-  const size_t es = esz(f32);
-  const double *rayleigh = table(m, m->off_rayleigh, f32), *solar = table(m, m->off_solar, f32);
-  if (memspace == ECCKD_DEVICE) {
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    void *tau_p = nullptr;   // tau lives in the stream's scratch block between the two kernels; the solver's room behind it
-    ScratchLease lease;
-    const size_t tau_bytes = align256(n3 * es);
-    const size_t solver = sw_fluxes_solver_bytes(m->device, ncol, nlay, m->ng);
-    // all-sky with delta scaling: three band planes behind the solver's room hold the scaled copy (the caller's arrays are
-    // never written); they are part of the stream's block, so the capture rules of stream_scratch cover them
-    const size_t plane = align256(n2 * m->nband * es);
-    const size_t planes = pt && pt->delta_scale ? 3 * plane : 0;
-    if (stream_scratch(m->device, st, tau_bytes + solver + planes, &tau_p, lease)) return 1;
-    double *d_tau = static_cast<double *>(tau_p);
-    SwParticles dp_ = pt ? *pt : SwParticles{};
-    if (planes) {
-      char *p0 = static_cast<char *>(tau_p) + tau_bytes + solver;
-      double *q_tau = reinterpret_cast<double *>(p0), *q_ssa = reinterpret_cast<double *>(p0 + plane), *q_g = reinterpret_cast<double *>(p0 + 2 * plane);
-      ProfScope prof("delta_scale", st);
-      HIPCHK(ecckd::launch_delta_scale(n2 * m->nband, pt->tau, pt->ssa, pt->g, nullptr, q_tau, q_ssa, q_g, 0, st));
-      dp_.tau = q_tau; dp_.ssa = q_ssa; dp_.g = q_g;
-    }
-    // gas_optics_ext's tau (:449-456) without ssa / g: the total optical depth, gases + Rayleigh
-    if (gas_optical_depth_dev(m, f32, nullptr, ncol, nlay, plev, tlay, gd, d_tau, true, nullptr, nullptr, nullptr, nullptr, st))
-      return 1;
-    SwDerive dv{plev, rayleigh, solar, toa_scale, gw(f32),
-                solver ? reinterpret_cast<double *>(static_cast<char *>(tau_p) + tau_bytes) : nullptr};
-    // ecckd_sw_fluxes_clear_allsky: the clear-sky solver of ecckd_sw_fluxes first, on the same tau and in the same room
-    if (clr && rte_sw_impl(Call{f32, -1, false, &dv}, m->device, ncol, nlay, m->ng, top_at_1, d_tau, nullptr, nullptr, mu0,
-                           nullptr, m->nband, m->band2gpt.data(), sfc_alb_dir, sfc_alb_dif, clr->up, clr->dn, clr->dir,
-                           ECCKD_DEVICE, stream))
-      return 1;
-    if (pt) { dv.part_tau = dp_.tau; dv.part_ssa = dp_.ssa; dv.part_g = dp_.g; dv.part_mask = dp_.mask; }   // (the mask is read in place)
-    return rte_sw_impl(Call{f32, -1, false, &dv}, m->device, ncol, nlay, m->ng, top_at_1, d_tau, nullptr, nullptr, mu0,
-                       nullptr, m->nband, m->band2gpt.data(), sfc_alb_dir, sfc_alb_dif, flux_up, flux_dn, flux_dir,
-                       ECCKD_DEVICE, stream);
-  }
-  if (memspace != ECCKD_HOST) return fail("ecckd: bad memspace");
-  ecckd_model *mm = const_cast<ecckd_model *>(m);
-  std::lock_guard<std::mutex> lock(mm->mu);
-  hipStream_t s = mm->host_stream;
+  if (memspace != ECCKD_DEVICE && memspace != ECCKD_HOST) return fail("ecckd: bad memspace");
+  const Counts n(ncol, nlay, m->ng, m->nband);
+  // The work block: tau between the two kernels, the solver's room behind it, and -- all-sky with delta scaling -- three
+  // band planes for the scaled copy of the particles (the caller's arrays are never written).  With device arrays it is
+  // the stream's scratch block, so the capture rules of stream_scratch cover all of it.
+  const size_t tau_bytes = align256(n.lay_g * esz(f32));
   const size_t solver = sw_fluxes_solver_bytes(m->device, ncol, nlay, m->ng);
-  const size_t nb3 = n2 * m->nband;
-  const size_t need = (pt ? align256(nb3 * es) * 3 : 0) + (pt && pt->mask ? align256(n2 * 8) : 0) + align256(n2l * es) * 4 + align256(n2 * es) + align256((size_t)ncol * es) * 2 +
-                      staged_gas_bytes(gd, ncol, nlay, f32) + align256((size_t)ncol * m->nband * es) * 2 + align256(n3 * es) +
-                      align256(solver) + (clr ? align256(n2l * es) * 3 : 0);
-  if (grow_arena(mm, need)) return 1;
-  Bump b(mm->arena, f32);
-  double *d_plev = b.take(n2l), *d_tlay = b.take(n2), *d_mu0 = b.take(ncol), *d_scale = b.take(ncol);
-  double *d_upc = clr ? b.take(n2l) : nullptr, *d_dnc = clr ? b.take(n2l) : nullptr, *d_dirc = clr ? b.take(n2l) : nullptr;
-  double *d_up = b.take(n2l), *d_dn = b.take(n2l), *d_dir = b.take(n2l);
-  double *d_ad = b.take((size_t)ncol * m->nband), *d_af = b.take((size_t)ncol * m->nband);
-  if (h2d(d_plev, plev, n2l, f32, s) || h2d(d_tlay, tlay, n2, f32, s) || h2d(d_mu0, mu0, ncol, f32, s) ||
-      h2d(d_ad, sfc_alb_dir, (size_t)ncol * m->nband, f32, s) || h2d(d_af, sfc_alb_dif, (size_t)ncol * m->nband, f32, s))
+  const size_t plane = pt && pt->delta_scale ? align256(n.lay_b * esz(f32)) : 0;
+  Stage st(const_cast<ecckd_model *>(m), memspace, stream, f32);
+  const double *d_plev = nullptr, *d_tlay = nullptr, *d_mu0 = nullptr, *d_scale = nullptr, *d_ad = nullptr, *d_af = nullptr;
+  double *d_up = nullptr, *d_dn = nullptr, *d_dir = nullptr, *d_tau = nullptr;
+  GasDesc d_gd{};
+  SwParticles d_pt{};
+  ClearFluxes d_clr{};
+  if (st.open([&] {
+        d_plev = st.in(plev, n.lev); d_tlay = st.in(tlay, n.lay); d_mu0 = st.in(mu0, n.col); d_scale = st.in(toa_scale, n.col);
+        d_ad = st.in(sfc_alb_dir, n.col_b); d_af = st.in(sfc_alb_dif, n.col_b);
+        d_gd = st.gases(gd, ncol, nlay);
+        if (pt) d_pt = SwParticles{st.in(pt->tau, n.lay_b), st.in(pt->ssa, n.lay_b), st.in(pt->g, n.lay_b), pt->delta_scale, st.in(pt->mask, n.lay)};
+        if (clr) d_clr = ClearFluxes{st.out(clr->up, n.lev), st.out(clr->dn, n.lev), st.out(clr->dir, n.lev)};
+        d_up = st.out(flux_up, n.lev); d_dn = st.out(flux_dn, n.lev); d_dir = st.out(flux_dir, n.lev);
+        d_tau = st.work(tau_bytes + solver + 3 * plane);
+      }))
     return 1;
-  if (toa_scale && h2d(d_scale, toa_scale, ncol, f32, s)) return 1;
-  StagedGases sg;
-  if (stage_gases(gd, ncol, nlay, b, s, sg)) return 1;
-  double *d_tau = b.take(n3);
-  double *d_solver = solver ? b.take((solver + es - 1) / es) : nullptr;
-  if (gas_optical_depth_dev(m, f32, nullptr, ncol, nlay, d_plev, d_tlay, sg.gd, d_tau, true, nullptr, nullptr, nullptr, nullptr, s))
-    return 1;
-  SwDerive dv{d_plev, rayleigh, solar, toa_scale ? d_scale : nullptr, gw(f32), d_solver};
-  if (clr) {   // the clear-sky solver first, as on the device route
-    if (rte_sw_impl(Call{f32, -1, false, &dv}, m->device, ncol, nlay, m->ng, top_at_1, d_tau, nullptr, nullptr, d_mu0, nullptr,
-                    m->nband, m->band2gpt.data(), d_ad, d_af, d_upc, d_dnc, clr->dir ? d_dirc : nullptr, ECCKD_DEVICE, s))
-      return 1;
-    if (d2h(clr->up, d_upc, n2l, f32, s) || d2h(clr->dn, d_dnc, n2l, f32, s)) return 1;
-    if (clr->dir && d2h(clr->dir, d_dirc, n2l, f32, s)) return 1;
+  char *const room = reinterpret_cast<char *>(d_tau) + tau_bytes;
+  if (plane) {
+    double *q_tau = reinterpret_cast<double *>(room + solver), *q_ssa = reinterpret_cast<double *>(room + solver + plane),
+           *q_g = reinterpret_cast<double *>(room + solver + 2 * plane);
+    ProfScope prof("delta_scale", st.stream);
+    HIPCHK(ecckd::launch_delta_scale(n.lay_b, d_pt.tau, d_pt.ssa, d_pt.g, nullptr, q_tau, q_ssa, q_g, 0, st.stream));
+    d_pt.tau = q_tau; d_pt.ssa = q_ssa; d_pt.g = q_g;
   }
-  if (pt) {   // staged copies of the band optics, delta-scaled in place (they are the library's own)
-    double *q_tau = b.take(nb3), *q_ssa = b.take(nb3), *q_g = b.take(nb3);
-    if (h2d(q_tau, pt->tau, nb3, f32, s) || h2d(q_ssa, pt->ssa, nb3, f32, s) || h2d(q_g, pt->g, nb3, f32, s)) return 1;
-    if (pt->delta_scale) HIPCHK(ecckd::launch_delta_scale(nb3, q_tau, q_ssa, q_g, nullptr, q_tau, q_ssa, q_g, 0, s));
-    dv.part_tau = q_tau; dv.part_ssa = q_ssa; dv.part_g = q_g;
-    if (pt->mask) {   // (8-byte words whatever the precision: a room of its own, copied as bytes)
-      double *q_mask = b.take((n2 * 8 + es - 1) / es);
-      HIPCHK(hipMemcpyAsync(q_mask, pt->mask, n2 * 8, hipMemcpyHostToDevice, s));
-      dv.part_mask = reinterpret_cast<const unsigned long long *>(q_mask);
-    }
-  }
-  if (rte_sw_impl(Call{f32, -1, false, &dv}, m->device, ncol, nlay, m->ng, top_at_1, d_tau, nullptr, nullptr, d_mu0, nullptr,
-                  m->nband, m->band2gpt.data(), d_ad, d_af, d_up, d_dn, flux_dir ? d_dir : nullptr, ECCKD_DEVICE, s))
+  // gas_optics_ext's tau (:449-456) without ssa / g: the total optical depth, gases + Rayleigh
+  if (gas_optical_depth_dev(m, f32, nullptr, ncol, nlay, d_plev, d_tlay, d_gd, d_tau, true, nullptr, nullptr, nullptr, nullptr, st.stream))
     return 1;
-  if (d2h(flux_up, d_up, n2l, f32, s) || d2h(flux_dn, d_dn, n2l, f32, s)) return 1;
-  if (flux_dir && d2h(flux_dir, d_dir, n2l, f32, s)) return 1;
-  HIPCHK(hipStreamSynchronize(s));
-  return 0;
+  SwDerive dv{d_plev, table(m, m->off_rayleigh, f32), table(m, m->off_solar, f32), d_scale, gw(f32),
+              solver ? reinterpret_cast<double *>(room) : nullptr};
+  auto solve = [&](const ClearFluxes &to) {   // (its arrays are on the device by now, whatever the call's memory space)
+    return rte_sw_impl(Call{f32, -1, false, &dv}, m->device, ncol, nlay, m->ng, top_at_1, d_tau, nullptr, nullptr, d_mu0, nullptr,
+                       m->nband, m->band2gpt.data(), d_ad, d_af, to.up, to.dn, to.dir, ECCKD_DEVICE, st.stream);
+  };
+  // ecckd_sw_fluxes_clear_allsky: the clear-sky solver of ecckd_sw_fluxes first, on the same tau and in the same room
+  if (clr && solve(d_clr)) return 1;
+  if (pt) { dv.part_tau = d_pt.tau; dv.part_ssa = d_pt.ssa; dv.part_g = d_pt.g; dv.part_mask = d_pt.mask; }
+  if (solve(ClearFluxes{d_up, d_dn, d_dir})) return 1;
+  return st.close();
 }
 
 int ecckd_sw_fluxes(const ecckd_model_t *m, int ncol, int nlay, const double *plev, const double *tlay, int ngas,
@@ -2516,24 +2322,15 @@ static int delta_scale_impl(bool f32, int device, int ncol, int nlay, int n, dou
   }
   if (check_device(device)) return 1;
   if (ncol == 0) return 0;
-  if (memspace == ECCKD_DEVICE) {
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    ProfScope prof("delta_scale", st);
-    HIPCHK(ecckd::launch_delta_scale(n3, tau, ssa, g, forward, tau, ssa, g, f32, st));
-    return 0;
+  Stage st(device, memspace, stream, f32);
+  double *d_tau = nullptr, *d_ssa = nullptr, *d_g = nullptr;
+  const double *d_f = nullptr;
+  if (st.open([&] { d_tau = st.inout(tau, n3); d_ssa = st.inout(ssa, n3); d_g = st.inout(g, n3); d_f = st.in(forward, n3); })) return 1;
+  {
+    ProfScope prof("delta_scale", st.stream);
+    HIPCHK(ecckd::launch_delta_scale(n3, d_tau, d_ssa, d_g, d_f, d_tau, d_ssa, d_g, f32, st.stream));
   }
-  Arena &ar = g_solver_arena[device];
-  std::lock_guard<std::mutex> lock(ar.mu);
-  if (ar.ensure(align256(n3 * esz(f32)) * 4)) return 1;
-  Bump b(ar.p, f32);
-  hipStream_t s = nullptr;
-  double *d_tau = b.take(n3), *d_ssa = b.take(n3), *d_g = b.take(n3), *d_f = forward ? b.take(n3) : nullptr;
-  if (h2d(d_tau, tau, n3, f32, s) || h2d(d_ssa, ssa, n3, f32, s) || h2d(d_g, g, n3, f32, s)) return 1;
-  if (forward && h2d(d_f, forward, n3, f32, s)) return 1;
-  HIPCHK(ecckd::launch_delta_scale(n3, d_tau, d_ssa, d_g, d_f, d_tau, d_ssa, d_g, f32, s));
-  if (d2h(tau, d_tau, n3, f32, s) || d2h(ssa, d_ssa, n3, f32, s) || d2h(g, d_g, n3, f32, s)) return 1;
-  HIPCHK(hipStreamSynchronize(s));
-  return 0;
+  return st.close();
 }
 
 int ecckd_delta_scale(int device, int ncol, int nlay, int n, double *tau, double *ssa, double *g, const double *forward,
@@ -2579,37 +2376,19 @@ static int increment_impl(bool f32, int device, int ncol, int nlay, int ngpt, do
   if (ncol == 0) return 0;
   a.ncol = ncol; a.nlay = nlay; a.ng = ngpt; a.nband = nband; a.f32 = f32;
   const size_t n1 = (size_t)ncol * nlay * ngpt, n2 = (size_t)ncol * nlay * (nband > 0 ? nband : ngpt);
-  if (memspace == ECCKD_DEVICE) {
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    a.tau1 = tau1; a.ssa1 = ssa1; a.g1 = g1; a.tau2 = tau2; a.ssa2 = ssa2; a.g2 = g2; a.mask = mask;
-    ProfScope prof("increment", st);
-    HIPCHK(ecckd::launch_increment(a, st));
-    return 0;
+  Stage st(device, memspace, stream, f32);
+  if (st.open([&] {
+        a.mask = st.in(mask, (size_t)ncol * nlay);
+        a.tau1 = st.inout(tau1, n1); a.ssa1 = st.inout(ssa1, n1);
+        a.g1 = st.inout(g1, n1, ssa2 != nullptr);   // (g1 changes only when op2 scatters)
+        a.tau2 = st.in(tau2, n2); a.ssa2 = st.in(ssa2, n2); a.g2 = st.in(g2, n2);
+      }))
+    return 1;
+  {
+    ProfScope prof("increment", st.stream);
+    HIPCHK(ecckd::launch_increment(a, st.stream));
   }
-  Arena &ar = g_solver_arena[device];
-  std::lock_guard<std::mutex> lock(ar.mu);
-  const size_t es = esz(f32);
-  const size_t nm = mask ? (size_t)ncol * nlay : 0;
-  if (ar.ensure(align256(n1 * es) * (ssa1 ? 3 : 1) + align256(n2 * es) * (ssa2 ? 3 : 1) + align256(nm * 8))) return 1;
-  Bump b(ar.p, f32);
-  hipStream_t s = nullptr;
-  if (mask) {   // (8-byte words whatever the precision: copied as bytes)
-    double *d_m = b.take((nm * 8 + es - 1) / es);
-    HIPCHK(hipMemcpyAsync(d_m, mask, nm * 8, hipMemcpyHostToDevice, s));
-    a.mask = reinterpret_cast<const unsigned long long *>(d_m);
-  }
-  double *d_t1 = b.take(n1), *d_s1 = ssa1 ? b.take(n1) : nullptr, *d_g1 = ssa1 ? b.take(n1) : nullptr;
-  double *d_t2 = b.take(n2), *d_s2 = ssa2 ? b.take(n2) : nullptr, *d_g2 = ssa2 ? b.take(n2) : nullptr;
-  if (h2d(d_t1, tau1, n1, f32, s) || h2d(d_t2, tau2, n2, f32, s)) return 1;
-  if (ssa1 && (h2d(d_s1, ssa1, n1, f32, s) || h2d(d_g1, g1, n1, f32, s))) return 1;
-  if (ssa2 && (h2d(d_s2, ssa2, n2, f32, s) || h2d(d_g2, g2, n2, f32, s))) return 1;
-  a.tau1 = d_t1; a.ssa1 = d_s1; a.g1 = d_g1; a.tau2 = d_t2; a.ssa2 = d_s2; a.g2 = d_g2;
-  HIPCHK(ecckd::launch_increment(a, s));
-  if (d2h(tau1, d_t1, n1, f32, s)) return 1;
-  if (ssa1 && d2h(ssa1, d_s1, n1, f32, s)) return 1;
-  if (ssa1 && ssa2 && d2h(g1, d_g1, n1, f32, s)) return 1;   // (g1 changes only when op2 scatters)
-  HIPCHK(hipStreamSynchronize(s));
-  return 0;
+  return st.close();
 }
 
 int ecckd_increment(int device, int ncol, int nlay, int ngpt, double *tau1, double *ssa1, double *g1, int nband,
@@ -2658,23 +2437,15 @@ int ecckd_cloud_mask_sample(int device, int ncol, int nlay, int ngpt, int overla
   }
   if (check_device(device)) return 1;
   if (ncol == 0) return 0;
-  if (memspace == ECCKD_DEVICE) {
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    ProfScope prof("cloud_mask_sample", st);
-    HIPCHK(ecckd::launch_cloud_mask_sample(ncol, nlay, ngpt, exp_ran, cloud_frac, np ? overlap_param : nullptr, seed, col0, mask, st));
-    return 0;
+  Stage st(device, memspace, stream, false);
+  const double *d_cf = nullptr, *d_al = nullptr;
+  unsigned long long *d_mask = nullptr;
+  if (st.open([&] { d_cf = st.in(cloud_frac, n2); d_al = st.in(np ? overlap_param : nullptr, np); d_mask = st.out(mask, n2); })) return 1;
+  {
+    ProfScope prof("cloud_mask_sample", st.stream);
+    HIPCHK(ecckd::launch_cloud_mask_sample(ncol, nlay, ngpt, exp_ran, d_cf, d_al, seed, col0, d_mask, st.stream));
   }
-  Arena &ar = g_solver_arena[device];
-  std::lock_guard<std::mutex> lock(ar.mu);
-  if (ar.ensure(align256(n2 * 8) * 2 + align256(np * 8))) return 1;
-  Bump b(ar.p, false);
-  hipStream_t s = nullptr;
-  double *d_cf = b.take(n2), *d_mask = b.take(n2), *d_al = np ? b.take(np) : nullptr;
-  if (h2d(d_cf, cloud_frac, n2, false, s) || (np && h2d(d_al, overlap_param, np, false, s))) return 1;
-  HIPCHK(ecckd::launch_cloud_mask_sample(ncol, nlay, ngpt, exp_ran, d_cf, d_al, seed, col0, reinterpret_cast<unsigned long long *>(d_mask), s));
-  if (d2h(reinterpret_cast<double *>(mask), d_mask, n2, false, s)) return 1;
-  HIPCHK(hipStreamSynchronize(s));
-  return 0;
+  return st.close();
 }
 
 int ecckd_sw_fluxes_f32(const ecckd_model_t *m, int ncol, int nlay, const float *plev, const float *tlay, int ngas,
