@@ -812,6 +812,13 @@ int ecckd_get_arithmetic(void);
  *                            interpolation per gas (same real-number formula; the per-gas clamp :234-238 is kept
  *                            because only gases with m_k >= 0 and tables without negative entries are merged);
  *                            0: every gas interpolated on its own
+ *   "gas_tile_sync"          fused gas-optics kernel (every mode and precision): 1 the waves of a block meet at an execution
+ *                            barrier before every tile of columns, so that they write the tile's output planes together
+ *                            (first-level address translations of a plane shared instead of fetched per wave); 0
+ *                            they run free between the segment boundaries; -1 (default) what measured faster in each mode: 1 in
+ *                            the longwave call (fp64: gas optics + rte_lw 1.0-1.4 % faster at 1e6 columns, 1.2-1.9 % at 1e5;
+ *                            fp32 3-6 %) and in the shortwave call (2.3-2.8 % at 1e5 columns), 0 in
+ *                            ecckd_gas_optics_lw_tau, where it costs 1-2 % of the kernel.  The same bits either way ("Address translation")
  * --------------------------------------------------------------------------------------- */
 int ecckd_set_solver_option(const char *name, double value);
 int ecckd_get_solver_option(const char *name, double *value);

@@ -86,6 +86,7 @@ struct FusedArgs {
   const int *choose;           // (set by launch_gas_fused) the probe's counter, or null: unconditional launch
   int choose_total;            // (set by launch_gas_fused) waves of 64 columns in the call
   int mode;                    // 0 tau only, 1 longwave (tau + Planck sources), 2 shortwave epilogue
+  int tile_sync;               // "gas_tile_sync": 1 = the waves of a block meet at an execution barrier before every tile
   int ntp;
   int pw;                      // Planck rows staged in LDS (ntp, or a window); filled by launch_gas_fused
   const double *planck;        // (ng,ntp) device

@@ -26,6 +26,7 @@
 // doubles.  Per segment of kSeg tiles a pre-pass finds the pressure-row (and Planck-row) range and
 // places the slab; segments spanning more rows than the slab holds are walked once per slab
 // position; waves with a lane outside the staged rows read the tables from global memory.
+#include <cstddef>
 #include <cstdlib>
 #include <type_traits>
 
@@ -384,6 +385,29 @@ __global__ void __launch_bounds__(BLOCK, (BLOCK > 512 ? 3 : sizeof(real) == 4 ? 
     };
 
     for (long tile = seg; tile < seg_end; ++tile) {
+      // "gas_tile_sync": the waves of the block meet once per tile, so that they walk the tile's output planes (4 KiB per
+      // plane and block, 512 B of it per wave) together instead of drifting apart over the segment.  Every wave passes
+      // this barrier exactly once per (segment, slab position, tile), because it stands before anything a wave decides for
+      // itself (the `own` early-out, fast / lowest, masked / first-layer chunk loops) and the trip counts of the three
+      // enclosing loops are the same in every thread of the block:
+      //   seg, seg_end <- t_begin, t_end (blockIdx.x, gridDim.x, ncol: block-uniform) and t.seg (kernel argument);
+      //   npos         <- R (kernel argument) and ipmin, ipmax, which every thread computes with the same operations from
+      //                   the same LDS words redd[0 .. 4 * kWaves) after the block barrier that follows their writes;
+      //   the flag     <- a kernel argument (uniform over the grid).
+      // No wave leaves the kernel before its last tile, and the early return of the "gas_slab_f32" = auto form above is
+      // taken by whole grids.  A bare execution barrier: no LDS is exchanged here, so there is no fence and no wait for the
+      // stores in flight -- in the code object the sequence is s_load_dword, s_waitcnt lgkmcnt(0), s_cmp, s_cbranch,
+      // s_barrier in all 56 instantiations, no vmcnt wait.
+      // The flag is read from the kernel-argument segment once per tile (the kernel's only argument starts at offset 0)
+      // instead of from `a`: as one more scalar held over the tile loop it costs the register allocator, which already
+      // spills 100-250 scalars here, 148 more spilled SGPRs over the instantiations, a VGPR in four of them and scratch in
+      // two; re-read per tile, the listings stay where the parent's are (profiles/gas_tile_sync_kernel_resources_*.txt).
+      {
+        typedef __attribute__((address_space(4))) const char karg_c;
+        typedef __attribute__((address_space(4))) const volatile int karg_i;
+        const int tile_sync = *(karg_i *)((karg_c *)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(FusedArgs, tile_sync));
+        if (tile_sync) __builtin_amdgcn_s_barrier();
+      }
       const long c = tile * kBlock + wcol;   // (see wave_column)
       const bool valid = c < ncol;
       const bool upper = lane >= 32;        // this lane stores plane g+1 of its column pair
