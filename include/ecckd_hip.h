@@ -644,9 +644,9 @@ int ecckd_lw_fluxes_jac(const ecckd_model_t *model, int ncol, int nlay, const do
  *     8*(r32(n3) + 3*n3 + r32(ncol*ngpt)) + ecckd_rte_lw_2stream_scratch_bytes(ncol, nlay, ngpt)
  *   in the order optical depth, the three Planck arrays, surface source, ring.
  * Out of scope: single precision; per-band and Jacobian outputs; both skies in one call; delta scaling inside the fused
- *   call (the host calls ecckd_delta_scale on its band triple first); RTE's rescaled no-scattering alternative
- *   (use_2stream = .false. with two-stream properties); ECCKD_MIXED; a tail split for small calls; a Planck-recomputing
- *   form of the solver; the Fortran type-bound rte_lw(use_2stream=).
+ *   call (the host calls ecckd_delta_scale on its band triple first); ECCKD_MIXED; a tail split for small calls; a
+ *   Planck-recomputing form of the solver; the Fortran type-bound rte_lw(use_2stream=).  (RTE's rescaled no-scattering
+ *   alternative, use_2stream = .false. with two-stream properties, is the next block.)
  * --------------------------------------------------------------------------------------- */
 int ecckd_rte_lw_2stream(int device, int ncol, int nlay, int ngpt, int top_at_1, const double *tau, const double *ssa,
                          const double *g, const double *lay_source, const double *lev_source_inc, const double *lev_source_dec,
@@ -663,6 +663,89 @@ int ecckd_lw_fluxes_allsky_2stream(const ecckd_model_t *model, int ncol, int nla
                                    const double *vmr_scalar, int top_at_1, const double *sfc_emis, const double *inc_flux,
                                    int nband_p, const double *tau_p, const double *ssa_p, const double *g_p,
                                    const unsigned long long *cloud_mask, double *flux_up, double *flux_dn, int memspace, void *stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Rescaled longwave: cheap cloud scattering with the Gauss quadrature.  RTE-RRTMGP's lw_solver_1rescl_GaussQuad of the v1.5
+ * era [RTE-ext: mo_rte_solver_kernels.F90; the method is Tang et al. 2018, J. Atmos. Sci. 75, 2217], the route rte_lw takes
+ * on ty_optical_props_2str WITHOUT use_2stream = .true. -- RTE's default for two-stream properties.  The optical depth is
+ * scaled by 1 - ssa*(1+g)/2, the ordinary no-scattering sweeps run on it, and the radiances receive a back-scattering
+ * adjustment layer by layer.  Like every solver here, PARITY WITH RTE-RRTMGP IS UNPINNED: the
+ * equations below are restated from the public source, and the tests pin the calls to a numpy restatement of them, to the
+ * no-scattering solver in the two limits where they coincide, and to the two-stream solution they approximate.
+ *   Per (column, g-point, quadrature angle k with secant D_k and weight w_k), layers s = 0..nlay-1 counted from the top,
+ *   level s the top of layer s, in this order of operations:
+ *     wb  = (ssa*(1 - g))*0.5        sc = (1 - ssa) + wb        tl = (tau*sc)*D_k        t = exp(-tl)
+ *     Cn  = 0.4*(wb/sc)              CA = Cn*(1 - t*t)
+ *     sdn, sup: lw_source_noscat on tl with lay_source / lev_source_inc / lev_source_dec exactly as ecckd_rte_lw (the
+ *       "lw_tau_thresh" and "lw_series_terms" switches act on tl)
+ *     SUA = sup - Cn*(sdn*t + sup)   SDA = sdn - Cn*(sup*t + sdn)        (formed once, with CA, beside t and sdn)
+ *     sweep 1, top -> surface:  dn0[s+1] = t*dn0[s] + sdn;  dn0[0] from inc_flux as ecckd_rte_lw_inc_flux
+ *                               ("lw_inc_flux_isotropic" included), 0 without one
+ *     surface:                  up[nlay] = dn0[nlay]*(1 - emis) + emis*sfc_source       (the surface sees the unadjusted dn0)
+ *     sweep 2, surface -> top:  up[s]   = t*up[s+1] + (SUA + CA*dn0[s])
+ *     sweep 3, top -> surface:  dn[s+1] = t*dn[s]   + (SDA + CA*up[s+1]);  dn[0] = dn0[0]
+ *     flux = 2*pi*w_k * radiance, summed over angles and g-points as ecckd_rte_lw
+ *   The adjustment of the radiance that leaves a layer uses the radiance that enters the layer from the other side (dn0[s]
+ *   in sweep 2, up[s+1] in sweep 3), so both values of top_at_1 give the same fluxes.  The constant 0.4 (Tang et al.) has no
+ *   solver option.  ssa = g = 1 gives 0/0: unguarded, as in RTE -- the NaN stays in its column, as does any NaN or inf of
+ *   the inputs.  With ssa = 0 the fluxes are those of ecckd_rte_lw_inc_flux; with g = 1 those of ecckd_rte_lw_inc_flux on
+ *   tau*(1 - ssa) (both up to the order of the sums).  fp64.
+ *   Arithmetic: the 60-layer kernels use the exp and the source-function division of the no-scattering solver
+ *   (lw_layer.hpp) and IEEE division for wb/sc; the compatibility kernel is IEEE throughout.  ecckd_set_arithmetic does
+ *   not act on ecckd_rte_lw_rescaled.
+ * ecckd_rte_lw_rescaled: broadband fluxes (ncol,nlay+1); the arguments of ecckd_rte_lw_inc_flux with ssa and g
+ *   (ncol,nlay,ngpt) behind tau; n_gauss_angles 1..4; both orientations; inc_flux or NULL.  60 layers: the layer-split
+ *   kernel with three exchanges per (g-point group, angle) -- 15 layers per wave whatever "lw_split_seg" says, and
+ *   "lw_solver" does not act.  Any other layer count: the compatibility kernel below into stream scratch followed by the
+ *   g-point sum of ecckd_sum_broadband -- SLOW (three passes over the inputs per angle, spectral fluxes through memory).
+ *   ECCKD_DEVICE: asynchronous on `stream`; scratch comes from the stream's block (capture rules of ecckd_rte_sw: one call
+ *   before the capture, or ecckd_set_stream_scratch).  ECCKD_HOST: staged, synchronises.  Refused with a message before any
+ *   launch and before a device is asked for, in this order: bad sizes; n_gauss_angles outside 1..4; a null required pointer
+ *   (only inc_flux may be NULL); a bad band table; ECCKD_MIXED; a bad memspace.
+ * ecckd_rte_lw_rescaled_scratch_bytes = 0 at 60 layers, else 8 * 3*r32(ncol*(nlay+1)*ngpt) with r32() rounding up to a
+ *   multiple of 32: spectral flux_up, spectral flux_dn, and the radiances one sweep leaves for the next.
+ * ecckd_lw_solver_1rescl_gpt: RTE's kernel-level interface, mirroring ecckd_lw_solver_noscat_gpt -- spectral fluxes
+ *   (ncol,nlay+1,ngpt), sfc_emis / sfc_src / inc_flux (ncol,ngpt), nmus angles with Ds and weights; IEEE arithmetic; one
+ *   thread per (column, g-point); any layer count.  It takes 8*r32(ncol*(nlay+1)*ngpt) bytes from the stream's block.
+ * ecckd_lw_fluxes_allsky_rescaled: ecckd_lw_fluxes_allsky with the rescaled solver; the arguments of
+ *   ecckd_lw_fluxes_allsky_2stream plus n_gauss_angles.  Gas optical depth into stream scratch; the solver forms the cell's
+ *   (tau, ssa, g) from it and the layer's band triple (tau_p, ssa_p, g_p)(ncol,nlay,nband_p) -- and the cloud-mask word,
+ *   cloud_mask(ncol,nlay) or NULL, as ecckd_lw_fluxes_allsky_mcica -- with the operations of ecckd_increment[_masked] by band
+ *   on (tau_gas, 0, 0).  At 60 layers (and a Planck table that fits in LDS) no per-g-point ssa or g exists in memory: the
+ *   Planck-recomputing layer-split kernel loads the band triple beside the gas optical depth.  Any other layer count: Planck
+ *   sources, then the by-band increment on (tau, 0, 0), through scratch, then the compatibility route -- SLOW.  flux_up /
+ *   flux_dn equal, BIT FOR BIT on finite inputs and at every layer count, the composed route ecckd_gas_optics_lw_tau,
+ *   ecckd_planck_sources, ecckd_increment[_masked] by band on (tau, ssa = 0, g = 0), ecckd_rte_lw_rescaled.  Fast arithmetic
+ *   mode; ECCKD_DEVICE or ECCKD_HOST; capturable in a graph after one warm-up call on the stream.  Refused in this order:
+ *   cloud_mask with more than 64 g-points; nband_p different from the model's; tau_p, ssa_p or g_p NULL; reference-order
+ *   arithmetic; no Planck table; tlev NULL; n_gauss_angles outside 1..4; a host-only model.
+ * ecckd_lw_fluxes_allsky_rescaled_scratch_bytes (ECCKD_DEVICE, from the stream's block), n3 = r32(ncol*nlay*ngpt):
+ *     60 layers:  8*n3                                              (the gas optical depth)
+ *     otherwise:  8*(6*n3 + r32(ncol*ngpt)) + ecckd_rte_lw_rescaled_scratch_bytes(ncol, nlay, ngpt)
+ *   in the order optical depth, ssa, g, the three Planck arrays, surface source, the solver's planes.
+ * Out of scope: single precision; per-band and Jacobian outputs; both skies in one call; delta scaling inside the fused
+ *   call (the host calls ecckd_delta_scale on its band triple first); ECCKD_MIXED; a tail split for small calls; a fast form
+ *   away from 60 layers; the Fortran type-bound rte_lw; RTE's bind(C) name lw_solver_1rescl_GaussQuad in librte_kernels_hip.
+ * --------------------------------------------------------------------------------------- */
+int ecckd_rte_lw_rescaled(int device, int ncol, int nlay, int ngpt, int top_at_1, int n_gauss_angles, const double *tau,
+                          const double *ssa, const double *g, const double *lay_source, const double *lev_source_inc,
+                          const double *lev_source_dec, const double *sfc_source, int nband, const int *band2gpt,
+                          const double *sfc_emis, const double *inc_flux, double *flux_up, double *flux_dn, int memspace,
+                          void *stream);
+size_t ecckd_rte_lw_rescaled_scratch_bytes(int ncol, int nlay, int ngpt);
+int ecckd_lw_solver_1rescl_gpt(int device, int ncol, int nlay, int ngpt, int top_at_1, int nmus, const double *Ds,
+                               const double *weights, const double *tau, const double *ssa, const double *g,
+                               const double *lay_source, const double *lev_source_inc, const double *lev_source_dec,
+                               const double *sfc_emis, const double *sfc_src, const double *inc_flux, double *gpt_flux_up,
+                               double *gpt_flux_dn, int memspace, void *stream);
+int ecckd_lw_fluxes_allsky_rescaled(const ecckd_model_t *model, int ncol, int nlay, const double *plev, const double *tlay,
+                                    const double *tsfc, const double *tlev, int ngas, const char *gas_names,
+                                    const double *const *vmr, const long long *vmr_col_stride, const long long *vmr_lay_stride,
+                                    const double *vmr_scalar, int top_at_1, int n_gauss_angles, const double *sfc_emis,
+                                    const double *inc_flux, int nband_p, const double *tau_p, const double *ssa_p,
+                                    const double *g_p, const unsigned long long *cloud_mask, double *flux_up, double *flux_dn,
+                                    int memspace, void *stream);
+size_t ecckd_lw_fluxes_allsky_rescaled_scratch_bytes(const ecckd_model_t *model, int ncol, int nlay);
 
 /* Spectral (per-band) fluxes: what RTE-RRTMGP callers get by passing a ty_fluxes_byband to rte_lw /
  * rte_sw instead of the ty_fluxes_broadband the reference drivers use (ecckd_rfmip_lw.F90:108-109).

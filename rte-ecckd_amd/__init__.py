@@ -212,6 +212,16 @@ def lib():
         L.ecckd_lw_fluxes_allsky_2stream.argtypes = ([C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_char_p] +
                                                      [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_void_p, C.c_int] +
                                                      [C.c_void_p] * 6 + [C.c_int, C.c_void_p])
+    if hasattr(L, "ecckd_rte_lw_rescaled"):   # (an older build lacks them: tools/bench_lw_rescaled.py --parent-lib)
+        L.ecckd_rte_lw_rescaled.argtypes = [C.c_int] * 6 + [C.c_void_p] * 7 + [C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.c_void_p]
+        L.ecckd_lw_solver_1rescl_gpt.argtypes = [C.c_int] * 6 + [C.c_void_p] * 13 + [C.c_int, C.c_void_p]
+        L.ecckd_rte_lw_rescaled_scratch_bytes.restype = C.c_size_t
+        L.ecckd_rte_lw_rescaled_scratch_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
+        L.ecckd_lw_fluxes_allsky_rescaled_scratch_bytes.restype = C.c_size_t
+        L.ecckd_lw_fluxes_allsky_rescaled_scratch_bytes.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        L.ecckd_lw_fluxes_allsky_rescaled.argtypes = ([C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_char_p] +
+                                                      [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int] +
+                                                      [C.c_void_p] * 6 + [C.c_int, C.c_void_p])
     _lib = L
     return L
 
@@ -287,6 +297,10 @@ def rte_sw_tail_scratch_bytes(ncol, nlay, ngpt, device=0):
 
 def rte_lw_2stream_scratch_bytes(ncol, nlay, ngpt):
     return int(lib().ecckd_rte_lw_2stream_scratch_bytes(int(ncol), int(nlay), int(ngpt)))
+
+
+def rte_lw_rescaled_scratch_bytes(ncol, nlay, ngpt):
+    return int(lib().ecckd_rte_lw_rescaled_scratch_bytes(int(ncol), int(nlay), int(ngpt)))
 
 
 def rte_lw_tail_scratch_bytes(ncol, nlay, ngpt, n_gauss_angles=1, single_precision=False, device=0):
@@ -957,8 +971,44 @@ class GasOpticsEcckd:
                                                   *emis, nbp, *part, *out, space, _stream(space))
         return last_error() if rc else ""
 
+    def _lw_fluxes_allsky_rescaled(self, plev, tlay, tsfc, tlev, gas_desc, top_at_1, sfc_emis, particles, fluxes, n_gauss_angles,
+                                   inc_flux, cloud_mask, use_2stream, flux_up_jac):
+        """``ecckd_lw_fluxes_allsky_rescaled`` behind ``lw_fluxes_allsky(..., rescaled=True)``."""
+        who = "lw_fluxes_allsky(rescaled=True): "
+        if use_2stream:
+            return who + "rescaled and use_2stream name two different solvers (pass one of them)"
+        if not isinstance(particles, OpticalProps2str) or particles.g is None:
+            return who + "the particles must be two-stream optical properties on the model's bands, with g (alloc_2str_bands)"
+        if flux_up_jac is not None:
+            return who + "flux_up_jac is not implemented"
+        if isinstance(fluxes, FluxesByband):
+            return who + "per-band fluxes are not implemented (broadband fluxes only)"
+        if any(_is_f32(a) for a in (tlay, particles.tau)):
+            return who + "implemented for float64 arrays"
+        nlay, ncol = tlay.shape
+        ng = self.get_ngpt()
+        try:
+            space = _space_of([plev, tlay, tsfc, tlev, sfc_emis, inc_flux, fluxes.flux_up, fluxes.flux_dn, particles.tau,
+                               particles.ssa, particles.g])
+            n, names, ptrs, cs, ls, sc, keep = self._gas_args(gas_desc, ncol, nlay, space)
+            nbp = 0 if particles.tau is None else int(particles.tau.shape[0])
+            shp = (nbp, nlay, ncol)
+            part = (_ptr(particles.tau, shp, "particles.tau"), _ptr(particles.ssa, shp, "particles.ssa"),
+                    _ptr(particles.g, shp, "particles.g"), _mask_ptr(cloud_mask, nlay, ncol, space))
+            lev = (nlay + 1, ncol)
+            inp = (_ptr(plev, lev, "plev"), _ptr(tlay, (nlay, ncol), "tlay"), _ptr(tsfc, (ncol,), "tsfc"), _ptr(tlev, lev, "tlev"))
+            emis = (_ptr(sfc_emis, (ncol, self.get_nband()), "sfc_emis"), _ptr(inc_flux, (ng, ncol), "inc_flux"))
+            out = (_ptr(fluxes.flux_up, lev, "flux_up"), _ptr(fluxes.flux_dn, lev, "flux_dn"))
+        except KeyError as e:
+            return str(e.args[0])
+        except (TypeError, ValueError) as e:
+            return str(e)
+        rc = lib().ecckd_lw_fluxes_allsky_rescaled(self._need(), ncol, nlay, *inp, n, names, ptrs, cs, ls, sc, int(bool(top_at_1)),
+                                                   int(n_gauss_angles), *emis, nbp, *part, *out, space, _stream(space))
+        return last_error() if rc else ""
+
     def lw_fluxes_allsky(self, plev, tlay, tsfc, tlev, gas_desc, top_at_1, sfc_emis, particles, fluxes, n_gauss_angles=1,
-                         inc_flux=None, cloud_mask=None, use_2stream=False, flux_up_jac=None):
+                         inc_flux=None, cloud_mask=None, rescaled=False, use_2stream=False, flux_up_jac=None):
         """``ecckd_lw_fluxes_allsky``: ``lw_fluxes`` with the combined particulate optical properties ``particles`` on
         the model's bands added to the gas optical depth inside the solver: an ``OpticalProps2str``
         (``alloc_2str_bands``; absorption optical depth ``tau*(1 - ssa)``, its ``g`` is ignored) or an
@@ -969,7 +1019,14 @@ class GasOpticsEcckd:
         ``flux_up``.  ``use_2stream=True`` (``ecckd_lw_fluxes_allsky_2stream``): the particles scatter -- the two-stream
         longwave solver on (``tau``, ``ssa``, ``g``) of a two-stream ``particles`` object on the bands; no quadrature
         (``n_gauss_angles`` must be 1) and no ``flux_up_jac``; pass both by keyword (``flux_up_jac`` stays the last
-        parameter).  Returns the error message ('' = success)."""
+        parameter).  ``rescaled=True`` (``ecckd_lw_fluxes_allsky_rescaled``; by keyword): the rescaled no-scattering solver --
+        what RTE-RRTMGP's ``rte_lw`` runs on two-stream properties without ``use_2stream``: cloud scattering as an adjustment of
+        the no-scattering sweeps, with the quadrature (``n_gauss_angles`` 1..4); a two-stream ``particles`` object with ``g``,
+        float64; refused with ``use_2stream=True``, ``flux_up_jac``, ``FluxesByband``.  Returns the error message
+        ('' = success)."""
+        if rescaled:
+            return self._lw_fluxes_allsky_rescaled(plev, tlay, tsfc, tlev, gas_desc, top_at_1, sfc_emis, particles, fluxes,
+                                                   n_gauss_angles, inc_flux, cloud_mask, use_2stream, flux_up_jac)
         if use_2stream:
             return self._lw_fluxes_allsky_2stream(plev, tlay, tsfc, tlev, gas_desc, top_at_1, sfc_emis, particles, fluxes,
                                                   n_gauss_angles, inc_flux, cloud_mask, flux_up_jac)
@@ -1226,8 +1283,70 @@ def _rte_lw_2stream(optical_props, top_at_1, sources, sfc_emis, fluxes, n_gauss_
     return last_error() if rc else ""
 
 
+def _rte_lw_rescaled(optical_props, top_at_1, sources, sfc_emis, fluxes, n_gauss_angles, device, shared_levels, inc_flux,
+                     use_2stream, flux_up_jac):
+    """``ecckd_rte_lw_rescaled`` behind ``rte_lw(..., rescaled=True)``."""
+    who = "rte_lw(rescaled=True): "
+    if use_2stream:
+        return who + "rescaled and use_2stream name two different solvers (pass one of them)"
+    if not isinstance(optical_props, OpticalProps2str):
+        return who + "two-stream optical properties required (OpticalProps2str; an OpticalProps1scl has nothing to rescale)"
+    if _is_f32(optical_props.tau):
+        return who + "implemented for float64 arrays"
+    if shared_levels:
+        return who + "shared_levels is not implemented"
+    if isinstance(fluxes, FluxesByband):
+        return who + "per-band fluxes are not implemented (broadband fluxes only)"
+    if flux_up_jac is not None:
+        return who + "flux_up_jac is not implemented"
+    ng, nlay, ncol = optical_props.tau.shape
+    b2g = np.ascontiguousarray(optical_props.band2gpt, dtype=np.int32)
+    nband = b2g.shape[0]
+    try:
+        space = _space_of([optical_props.tau, optical_props.ssa, optical_props.g, sources.lay_source, sources.lev_source_inc,
+                           sources.lev_source_dec, sources.sfc_source, sfc_emis, inc_flux, fluxes.flux_up, fluxes.flux_dn])
+        a3 = [_ptr(a, (ng, nlay, ncol), w) for a, w in ((optical_props.tau, "tau"), (optical_props.ssa, "ssa"), (optical_props.g, "g"),
+                                                        (sources.lay_source, "lay_source"),
+                                                        (sources.lev_source_inc, "lev_source_inc"),
+                                                        (sources.lev_source_dec, "lev_source_dec"))]
+        sfc = _ptr(sources.sfc_source, (ng, ncol), "sfc_source")
+        rest = [_ptr(sfc_emis, (ncol, nband), "sfc_emis"), _ptr(inc_flux, (ng, ncol), "inc_flux"),
+                _ptr(fluxes.flux_up, (nlay + 1, ncol), "flux_up"), _ptr(fluxes.flux_dn, (nlay + 1, ncol), "flux_dn")]
+    except (TypeError, ValueError) as e:
+        return str(e)
+    dev = _device_of(optical_props.tau) if device is None else device
+    rc = lib().ecckd_rte_lw_rescaled(int(dev), ncol, nlay, ng, int(bool(top_at_1)), int(n_gauss_angles), *a3, sfc, nband,
+                                     C.c_void_p(b2g.ctypes.data), *rest, space, _stream(space))
+    return last_error() if rc else ""
+
+
+def lw_solver_1rescl_gpt(tau, ssa, g, lay_source, lev_source_inc, lev_source_dec, sfc_emis, sfc_src, gpt_flux_up, gpt_flux_dn,
+                         top_at_1=True, Ds=(1.66,), weights=(0.5,), inc_flux=None, device=None):
+    """``ecckd_lw_solver_1rescl_gpt``: RTE-RRTMGP's kernel-level ``lw_solver_1rescl_GaussQuad`` -- the rescaled
+    no-scattering solver with spectral fluxes ``(ngpt, nlay+1, ncol)``; ``sfc_emis`` / ``sfc_src`` / ``inc_flux``
+    ``(ngpt, ncol)``; ``Ds`` and ``weights`` of 1..4 quadrature angles.  float64, numpy or device tensors; the compatibility
+    kernel (any layer count, slow).  Returns the error message ('' = success)."""
+    ng, nlay, ncol = tau.shape
+    D, W = np.ascontiguousarray(Ds, dtype=np.float64), np.ascontiguousarray(weights, dtype=np.float64)
+    if D.shape != W.shape or D.ndim != 1:
+        return "lw_solver_1rescl_gpt: Ds and weights must be two vectors of one length"
+    try:
+        space = _space_of([tau, ssa, g, lay_source, lev_source_inc, lev_source_dec, sfc_emis, sfc_src, inc_flux, gpt_flux_up,
+                           gpt_flux_dn])
+        a3 = [_ptr(a, (ng, nlay, ncol), w) for a, w in ((tau, "tau"), (ssa, "ssa"), (g, "g"), (lay_source, "lay_source"),
+                                                        (lev_source_inc, "lev_source_inc"), (lev_source_dec, "lev_source_dec"))]
+        a2 = [_ptr(a, (ng, ncol), w) for a, w in ((sfc_emis, "sfc_emis"), (sfc_src, "sfc_src"), (inc_flux, "inc_flux"))]
+        out = [_ptr(a, (ng, nlay + 1, ncol), w) for a, w in ((gpt_flux_up, "gpt_flux_up"), (gpt_flux_dn, "gpt_flux_dn"))]
+    except (TypeError, ValueError) as e:
+        return str(e)
+    dev = _device_of(tau) if device is None else device
+    rc = lib().ecckd_lw_solver_1rescl_gpt(int(dev), ncol, nlay, ng, int(bool(top_at_1)), int(D.shape[0]), C.c_void_p(D.ctypes.data),
+                                          C.c_void_p(W.ctypes.data), *a3, *a2, *out, space, _stream(space))
+    return last_error() if rc else ""
+
+
 def rte_lw(optical_props, top_at_1, sources, sfc_emis, fluxes, n_gauss_angles=1, device=None,
-           shared_levels=False, inc_flux=None, use_2stream=False, flux_up_jac=None):
+           shared_levels=False, inc_flux=None, rescaled=False, use_2stream=False, flux_up_jac=None):
     """``rte_lw(optical_props, top_at_1, sources, sfc_emis(nband,ncol), fluxes, n_gauss_angles=)``
     (ecckd_rfmip_lw.F90:130-135).  ``sfc_emis`` is ``(ncol, nband)`` in numpy order.  float32 arrays
     take the single-precision entry point.  ``shared_levels=True`` asserts that the level sources hold
@@ -1241,7 +1360,14 @@ def rte_lw(optical_props, top_at_1, sources, sfc_emis, fluxes, n_gauss_angles=1,
     scatter -- an ``OpticalProps2str`` (float64), broadband fluxes, ``inc_flux`` accepted; ``shared_levels``,
     ``FluxesByband``, ``flux_up_jac``, float32 and ``n_gauss_angles != 1`` are refused with a message.  Parity with
     RTE-RRTMGP's ``lw_solver_2stream`` is unpinned.  Pass ``use_2stream`` and ``flux_up_jac`` by
-    keyword: ``flux_up_jac`` stays the last parameter (tests/test_lw_jac_host.py pins that), so ``use_2stream`` sits before it."""
+    keyword: ``flux_up_jac`` stays the last parameter (tests/test_lw_jac_host.py pins that), so ``use_2stream`` sits before it.
+    ``rescaled=True`` (``ecckd_rte_lw_rescaled``; by keyword): the rescaled no-scattering solver, which RTE-RRTMGP's rte_lw runs
+    on two-stream properties without ``use_2stream`` -- an ``OpticalProps2str`` (float64), ``n_gauss_angles`` 1..4, broadband
+    fluxes, ``inc_flux`` accepted; ``use_2stream=True``, ``flux_up_jac``, ``FluxesByband``, ``shared_levels``, float32 and an
+    ``OpticalProps1scl`` are refused with a message.  Parity with RTE-RRTMGP is unpinned."""
+    if rescaled:
+        return _rte_lw_rescaled(optical_props, top_at_1, sources, sfc_emis, fluxes, n_gauss_angles, device, shared_levels,
+                                inc_flux, use_2stream, flux_up_jac)
     if use_2stream:
         return _rte_lw_2stream(optical_props, top_at_1, sources, sfc_emis, fluxes, n_gauss_angles, device, shared_levels,
                                inc_flux, flux_up_jac)

@@ -1873,7 +1873,9 @@ int ecckd_rte_lw_fused(const ecckd_model_t *m, int ncol, int nlay, int top_at_1,
 
 // General route of the all-sky call (any layer count): tau += the particles' (absorption) optical depth by band, the
 // one-stream-op1 increment kernel of ecckd_increment on the scratch tau between gas optics and the solver
-static int lw_increment_dev(const ecckd_model *m, int ncol, int nlay, double *tau, const LwParticles &pt, hipStream_t stream) {
+// (ssa1 / g1 / g2: ecckd_lw_fluxes_allsky_rescaled -- the two-stream increment on (tau, ssa1, g1) with the band triple)
+static int lw_increment_dev(const ecckd_model *m, int ncol, int nlay, double *tau, const LwParticles &pt, hipStream_t stream,
+                            double *ssa1 = nullptr, double *g1 = nullptr, const double *g2 = nullptr) {
   ecckd::OptPropsArgs o{};
   o.ncol = ncol; o.nlay = nlay; o.ng = m->ng; o.nband = m->nband; o.f32 = 0;
   int next = 1;   // the increment kernel wants bands in ascending order that tile 1..ngpt, as ecckd_increment checks
@@ -1886,6 +1888,7 @@ static int lw_increment_dev(const ecckd_model *m, int ncol, int nlay, double *ta
   if (next != m->ng + 1) return fail("ecckd_lw_fluxes_allsky: the model's band2gpt does not tile 1..ngpt in ascending order");
   o.band_first[m->nband] = (unsigned short)m->ng;
   o.tau1 = tau; o.tau2 = pt.tau; o.ssa2 = pt.ssa; o.g2 = pt.ssa;   // (g2 marks op2 as two-stream; 1scl += 2str never reads it)
+  if (ssa1) { o.ssa1 = ssa1; o.g1 = g1; o.g2 = g2; }
   o.mask = pt.mask;   // (McICA: the masked by-band increment)
   ProfScope prof("increment", stream);
   HIPCHK(ecckd::launch_increment(o, stream));
@@ -2151,6 +2154,211 @@ int ecckd_lw_fluxes_allsky_2stream(const ecckd_model_t *m, int ncol, int nlay, c
   if (lw_allsky_2stream_dev(m, ncol, nlay, d_tlay, d_tlev, d_tsfc, top_at_1, d_emis, d_incf, q_tau, q_ssa, q_g, q_mask, d_up, d_dn, work,
                             st.stream))
     return 1;
+  return st.close();
+}
+
+// ---- rescaled no-scattering longwave solver (RTE-RRTMGP's lw_solver_1rescl_GaussQuad): cheap cloud scattering ----
+
+// bytes of one spectral plane set (ncol,nlay+1,ngpt), rounded as the scratch layouts below place it
+static size_t resc_plane_doubles(int ncol, int nlay, int ngpt) { return r32((size_t)ncol * (nlay + 1) * ngpt); }
+
+size_t ecckd_rte_lw_rescaled_scratch_bytes(int ncol, int nlay, int ngpt) {
+  if (ncol <= 0 || nlay < 1 || ngpt < 1 || nlay == 60) return 0;
+  return sizeof(double) * 3 * resc_plane_doubles(ncol, nlay, ngpt);
+}
+
+static void fill_resc_gpt(ecckd::RteLwRescGptArgs &q, const ecckd::RteLwArgs &a) {
+  q.ncol = a.ncol; q.nlay = a.nlay; q.ng = a.ng; q.top_at_1 = a.top_at_1; q.nmus = a.nmus;
+  for (int k = 0; k < a.nmus; ++k) { q.Ds[k] = a.Ds[k]; q.wts[k] = a.wts[k]; }
+  q.tau = a.tau; q.ssa = a.ssa; q.g = a.g; q.lay_source = a.lay_source; q.lev_source_inc = a.lev_source_inc;
+  q.lev_source_dec = a.lev_source_dec; q.sfc_emis = a.sfc_emis; q.sfc_src = a.sfc_source; q.inc_flux = a.inc_flux;
+  q.nband = a.nband;
+  std::memcpy(q.gpt2band, a.gpt2band, sizeof q.gpt2band);
+  q.tau_thresh = a.tau_thresh; q.series3 = a.series3; q.inc_isotropic = a.inc_isotropic;
+}
+
+// The rescaled solver on device arrays (a.tau / ssa / g, the sources, a.flux_*).  60 layers: the layer-split kernel.  Any
+// other layer count: the compatibility kernel into `spec` (spectral up, spectral dn, work: ecckd_rte_lw_rescaled_scratch_bytes)
+// and the g-point sum of sum_broadband.
+static int lw_rescaled_dev(const ecckd::RteLwArgs &a, double *spec, hipStream_t stream) {
+  if (a.nlay == 60) {
+    ProfScope prof("rte_lw_rescaled", stream);
+    HIPCHK(ecckd::launch_rte_lw_rescaled_split(a, stream));
+    return 0;
+  }
+  if (!spec) return fail("ecckd: internal: the rescaled longwave solver needs scratch for this layer count");
+  const size_t plane = resc_plane_doubles(a.ncol, a.nlay, a.ng), nlev = (size_t)a.ncol * (a.nlay + 1);
+  ecckd::RteLwRescGptArgs q{};
+  fill_resc_gpt(q, a);
+  q.flux_up = spec; q.flux_dn = spec + plane; q.work = spec + 2 * plane;
+  {
+    ProfScope prof("lw_1rescl_gpt", stream);
+    HIPCHK(ecckd::launch_lw_1rescl_gpt(q, stream));
+  }
+  ProfScope prof("sum_broadband", stream);
+  HIPCHK(ecckd::launch_sum_planes(q.flux_up, a.ng, nlev, a.flux_up, 0, stream));
+  HIPCHK(ecckd::launch_sum_planes(q.flux_dn, a.ng, nlev, a.flux_dn, 0, stream));
+  return 0;
+}
+
+int ecckd_rte_lw_rescaled(int device, int ncol, int nlay, int ngpt, int top_at_1, int n_gauss_angles, const double *tau,
+                          const double *ssa, const double *g, const double *lay_source, const double *lev_source_inc,
+                          const double *lev_source_dec, const double *sfc_source, int nband, const int *band2gpt,
+                          const double *sfc_emis, const double *inc_flux, double *flux_up, double *flux_dn, int memspace,
+                          void *stream) {
+  if (check_dims(ncol, nlay)) return 1;
+  if (n_gauss_angles < 1 || n_gauss_angles > 4) return fail("rte_lw: have to ask for at least one quadrature point and no more than 4");
+  if (!tau || !ssa || !g || !lay_source || !lev_source_inc || !lev_source_dec || !sfc_source || !sfc_emis || !flux_up || !flux_dn)
+    return fail("ecckd_rte_lw_rescaled: null argument (only inc_flux may be null)");
+  ecckd::RteLwArgs a{};
+  if (fill_band_map(ngpt, nband, band2gpt, a.gpt2band)) return 1;
+  if (memspace == ECCKD_MIXED) return fail("ecckd_rte_lw_rescaled: ECCKD_MIXED is not implemented (ECCKD_DEVICE or ECCKD_HOST)");
+  if (memspace != ECCKD_DEVICE && memspace != ECCKD_HOST) return fail("ecckd: bad memspace");
+  if (check_device(device)) return 1;
+  if (ncol == 0) return 0;
+  a.ncol = ncol; a.nlay = nlay; a.ng = ngpt; a.top_at_1 = top_at_1 ? 1 : 0; a.nband = nband;
+  fill_lw_options(a, n_gauss_angles, false);
+  const Counts n(ncol, nlay, ngpt, nband);
+  Stage st(device, memspace, stream, false);
+  ScratchLease lease;   // (held until the kernels of this call have been launched)
+  void *sp = nullptr;
+  const size_t scratch = ecckd_rte_lw_rescaled_scratch_bytes(ncol, nlay, ngpt);
+  if (scratch && stream_scratch(device, st.stream, scratch, &sp, lease)) return 1;
+  if (st.open([&] {
+        a.tau = st.in(tau, n.lay_g); a.ssa = st.in(ssa, n.lay_g); a.g = st.in(g, n.lay_g);
+        a.lay_source = st.in(lay_source, n.lay_g); a.lev_source_inc = st.in(lev_source_inc, n.lay_g);
+        a.lev_source_dec = st.in(lev_source_dec, n.lay_g); a.sfc_source = st.in(sfc_source, n.col_g);
+        a.sfc_emis = st.in(sfc_emis, n.col_b); a.inc_flux = st.in(inc_flux, n.col_g);
+        a.flux_up = st.out(flux_up, n.lev); a.flux_dn = st.out(flux_dn, n.lev);
+      }))
+    return 1;
+  if (lw_rescaled_dev(a, static_cast<double *>(sp), st.stream)) return 1;
+  return st.close();
+}
+
+int ecckd_lw_solver_1rescl_gpt(int device, int ncol, int nlay, int ngpt, int top_at_1, int nmus, const double *Ds,
+                               const double *weights, const double *tau, const double *ssa, const double *g,
+                               const double *lay_source, const double *lev_source_inc, const double *lev_source_dec,
+                               const double *sfc_emis, const double *sfc_src, const double *inc_flux, double *gpt_flux_up,
+                               double *gpt_flux_dn, int memspace, void *stream) {
+  if (check_dims(ncol, nlay)) return 1;
+  if (ngpt < 1) return fail("ecckd_lw_solver_1rescl_gpt: bad ngpt");
+  if (nmus < 1 || nmus > 4 || !Ds || !weights) return fail("ecckd_lw_solver_1rescl_gpt: 1..4 quadrature angles with Ds and weights");
+  if (!tau || !ssa || !g || !lay_source || !lev_source_inc || !lev_source_dec || !sfc_emis || !sfc_src || !gpt_flux_up || !gpt_flux_dn)
+    return fail("ecckd_lw_solver_1rescl_gpt: null argument (only inc_flux may be null)");
+  if (memspace != ECCKD_DEVICE && memspace != ECCKD_HOST) return fail("ecckd: bad memspace");
+  if (check_device(device)) return 1;
+  if (ncol == 0) return 0;
+  ecckd::RteLwRescGptArgs a{};
+  a.ncol = ncol; a.nlay = nlay; a.ng = ngpt; a.top_at_1 = top_at_1 ? 1 : 0; a.nmus = nmus;
+  for (int k = 0; k < nmus; ++k) { a.Ds[k] = Ds[k]; a.wts[k] = weights[k]; }
+  a.tau_thresh = lw_tau_thresh(false);
+  a.series3 = g_opt.lw_series_terms.load() == 3;
+  a.inc_isotropic = g_opt.lw_inc_flux_isotropic.load();
+  const Counts n(ncol, nlay, ngpt, 1);
+  Stage st(device, memspace, stream, false);
+  ScratchLease lease;
+  void *sp = nullptr;   // the radiances between the sweeps, one (ncol,nlay+1,ngpt) plane set
+  if (stream_scratch(device, st.stream, sizeof(double) * resc_plane_doubles(ncol, nlay, ngpt), &sp, lease)) return 1;
+  a.work = static_cast<double *>(sp);
+  if (st.open([&] {
+        a.tau = st.in(tau, n.lay_g); a.ssa = st.in(ssa, n.lay_g); a.g = st.in(g, n.lay_g);
+        a.lay_source = st.in(lay_source, n.lay_g); a.lev_source_inc = st.in(lev_source_inc, n.lay_g);
+        a.lev_source_dec = st.in(lev_source_dec, n.lay_g);
+        a.sfc_emis = st.in(sfc_emis, n.col_g); a.sfc_src = st.in(sfc_src, n.col_g); a.inc_flux = st.in(inc_flux, n.col_g);
+        a.flux_up = st.out(gpt_flux_up, n.lev * ngpt); a.flux_dn = st.out(gpt_flux_dn, n.lev * ngpt);
+      }))
+    return 1;
+  {
+    ProfScope prof("lw_1rescl_gpt", st.stream);
+    HIPCHK(ecckd::launch_lw_1rescl_gpt(a, st.stream));
+  }
+  return st.close();
+}
+
+// scratch of the fused call behind the gas optical depth, in doubles: nothing at 60 layers (the Planck-recomputing
+// layer-split kernel); otherwise ssa and g of the cells, the three Planck arrays, the surface source and the solver's planes
+static bool resc_fused_kernel_applies(const ecckd_model *m, int nlay) {
+  return nlay == 60 && ecckd::rte_lw_rescaled_planck_fits(m->ng, m->ntp);
+}
+static size_t allsky_rescaled_doubles(const ecckd_model *m, int ncol, int nlay) {
+  const size_t n3 = r32((size_t)ncol * nlay * m->ng);
+  if (resc_fused_kernel_applies(m, nlay)) return n3;
+  return 6 * n3 + r32((size_t)ncol * m->ng) + 3 * resc_plane_doubles(ncol, nlay, m->ng);
+}
+
+size_t ecckd_lw_fluxes_allsky_rescaled_scratch_bytes(const ecckd_model_t *m, int ncol, int nlay) {
+  if (!m || ncol <= 0 || nlay < 1) return 0;
+  return sizeof(double) * allsky_rescaled_doubles(m, ncol, nlay);
+}
+
+int ecckd_lw_fluxes_allsky_rescaled(const ecckd_model_t *m, int ncol, int nlay, const double *plev, const double *tlay,
+                                    const double *tsfc, const double *tlev, int ngas, const char *gas_names,
+                                    const double *const *vmr, const long long *vmr_col_stride, const long long *vmr_lay_stride,
+                                    const double *vmr_scalar, int top_at_1, int n_gauss_angles, const double *sfc_emis,
+                                    const double *inc_flux, int nband_p, const double *tau_p, const double *ssa_p,
+                                    const double *g_p, const unsigned long long *cloud_mask, double *flux_up, double *flux_dn,
+                                    int memspace, void *stream) {
+  if (!m) return fail("ecckd: null model");
+  if (cloud_mask && m->ng > 64) return fail("ecckd_lw_fluxes_allsky_rescaled" + std::string(kMaskTooWide) + std::to_string(m->ng));
+  if (nband_p != m->nband)
+    return fail("ecckd_lw_fluxes_allsky_rescaled: nband_p = " + std::to_string(nband_p) + " but the model has " +
+                std::to_string(m->nband) + " bands (particulate properties live on the model's bands)");
+  if (!tau_p || !ssa_p || !g_p)
+    return fail("ecckd_lw_fluxes_allsky_rescaled: null argument (tau_p, ssa_p and g_p are required; one-stream particles: ecckd_lw_fluxes_allsky)");
+  if (g_arith.load() != 0) return fail("ecckd_lw_fluxes_allsky_rescaled: needs the fast arithmetic mode (ecckd_set_arithmetic(0))");
+  if (!m->has_planck) return fail("ecckd_lw_fluxes_allsky_rescaled: model has no Planck table (shortwave model?)");
+  if (!tlev) return fail("tlev is required for ecckd");
+  if (n_gauss_angles < 1 || n_gauss_angles > 4) return fail("rte_lw: have to ask for at least one quadrature point and no more than 4");
+  if (check_model(m) || check_gas_optics_dims(ncol, nlay)) return 1;
+  if (!plev || !tlay || !tsfc || !sfc_emis || !flux_up || !flux_dn || (ngas > 0 && !gas_names))
+    return fail("ecckd_lw_fluxes_allsky_rescaled: null argument");
+  if (memspace != ECCKD_DEVICE && memspace != ECCKD_HOST) return fail("ecckd: bad memspace");
+  HIPCHK(hipSetDevice(m->device));
+  if (ncol == 0) return 0;
+  const GasDesc gd{ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar};
+  const Counts n(ncol, nlay, m->ng, m->nband);
+  Stage st(const_cast<ecckd_model *>(m), memspace, stream, false);
+  const double *d_plev = nullptr, *d_tlay = nullptr, *d_tsfc = nullptr, *d_tlev = nullptr;
+  LwParticles d_pt{};
+  const double *q_g = nullptr;
+  double *work = nullptr;
+  GasDesc d_gd{};
+  ecckd::RteLwArgs a{};
+  if (fill_band_map(m->ng, m->nband, m->band2gpt.data(), a.gpt2band)) return 1;
+  a.ncol = ncol; a.nlay = nlay; a.ng = m->ng; a.top_at_1 = top_at_1 ? 1 : 0; a.nband = m->nband;
+  fill_lw_options(a, n_gauss_angles, false);
+  if (st.open([&] {
+        d_plev = st.in(plev, n.lev); d_tlay = st.in(tlay, n.lay); d_tsfc = st.in(tsfc, n.col); d_tlev = st.in(tlev, n.lev);
+        a.sfc_emis = st.in(sfc_emis, n.col_b); a.inc_flux = st.in(inc_flux, n.col_g);
+        d_gd = st.gases(gd, ncol, nlay);
+        d_pt = LwParticles{st.in(tau_p, n.lay_b), st.in(ssa_p, n.lay_b), st.in(cloud_mask, n.lay)};
+        q_g = st.in(g_p, n.lay_b);
+        a.flux_up = st.out(flux_up, n.lev); a.flux_dn = st.out(flux_dn, n.lev);
+        work = st.work(allsky_rescaled_doubles(m, ncol, nlay) * sizeof(double));
+      }))
+    return 1;
+  const hipStream_t s = st.stream;
+  if (gas_optical_depth_dev(m, false, nullptr, ncol, nlay, d_plev, d_tlay, d_gd, work, false, nullptr, nullptr, nullptr, nullptr, s))
+    return 1;
+  a.tau = work;
+  if (resc_fused_kernel_applies(m, nlay)) {   // the band triple and the mask ride into the solver
+    a.part_tau = d_pt.tau; a.part_ssa = d_pt.ssa; a.part_g = q_g; a.part_mask = d_pt.mask;
+    ProfScope prof("rte_lw_rescaled_allsky", s);
+    HIPCHK(ecckd::launch_rte_lw_rescaled_planck(a, m->dbuf + m->off_planck, m->ntp, m->temperature_planck[0],
+                                                m->temperature_planck[1] - m->temperature_planck[0], d_tlay, d_tlev, d_tsfc, s));
+    return st.close();
+  }
+  // any other layer count (slow): Planck sources and the by-band increment on (tau, 0, 0) through scratch, then the
+  // compatibility route of ecckd_rte_lw_rescaled
+  const size_t n3 = r32(n.lay_g);
+  double *ssa = work + n3, *g = ssa + n3, *lay = g + n3, *inc = lay + n3, *dec = inc + n3, *sfc = dec + n3;
+  double *spec = sfc + r32((size_t)ncol * m->ng);
+  if (planck_sources_dev(m, ncol, nlay, d_tlay, PlanckSide{d_tlev, d_tsfc, lay, inc, dec, sfc}, s)) return 1;
+  HIPCHK(hipMemsetAsync(ssa, 0, 2 * n3 * sizeof(double), s));
+  if (lw_increment_dev(m, ncol, nlay, work, d_pt, s, ssa, g, q_g)) return 1;
+  a.ssa = ssa; a.g = g; a.lay_source = lay; a.lev_source_inc = inc; a.lev_source_dec = dec; a.sfc_source = sfc;
+  if (lw_rescaled_dev(a, spec, s)) return 1;
   return st.close();
 }
 

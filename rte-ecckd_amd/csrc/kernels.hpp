@@ -135,6 +135,9 @@ struct RteLwArgs {
   // McICA (ecckd_lw_fluxes_allsky_mcica): one word per (column, layer), bit g set = g-point g sees the layer's particles;
   // where it is clear the cell uses part_tau = 0.  Null: every g-point sees them (the unmasked kernels).
   const unsigned long long *part_mask = nullptr;
+  // Rescaled no-scattering solver (launch_rte_lw_rescaled_split / _planck only; include/ecckd_hip.h, "Rescaled longwave"):
+  // ssa / g (ncol,nlay,ng) beside tau, or -- the Planck-recomputing form -- part_g beside part_tau / part_ssa
+  const double *ssa = nullptr, *g = nullptr, *part_g = nullptr;
 };
 
 // Longwave surface-temperature Jacobian (kernels_rte_lw_jac.hip): flux_up_jac(ncol,nlay+1) from tau, the surface term and
@@ -267,6 +270,20 @@ hipError_t launch_lw_gpt(const RteGptArgs &a, hipStream_t s);
 hipError_t launch_sw_gpt(const RteGptArgs &a, hipStream_t s);
 // lw_solver_2stream: tau, ssa, g, lev_source_*, sfc_emis / sfc_src / inc_flux (ncol,ng); lay_source is not read
 hipError_t launch_lw_2str_gpt(const RteGptArgs &a, hipStream_t s);
+// lw_solver_1rescl_GaussQuad (the rescaled no-scattering solver), spectral fluxes: the compatibility kernel of
+// ecckd_lw_solver_1rescl_gpt and of ecckd_rte_lw_rescaled away from 60 layers.  sfc_emis is (ncol,ng), or -- nband > 0 --
+// (nband,ncol) read through gpt2band.  work (ncol,nlay+1,ng): the radiances one sweep leaves for the next.
+struct RteLwRescGptArgs {
+  int ncol, nlay, ng, top_at_1, nmus;
+  double Ds[4], wts[4];
+  const double *tau, *ssa, *g, *lay_source, *lev_source_inc, *lev_source_dec, *sfc_emis, *sfc_src, *inc_flux;
+  int nband;
+  unsigned char gpt2band[256];
+  double *flux_up, *flux_dn, *work;
+  double tau_thresh;
+  int series3, inc_isotropic;
+};
+hipError_t launch_lw_1rescl_gpt(const RteLwRescGptArgs &a, hipStream_t s);
 
 // Host-side helpers -------------------------------------------------------------------------
 int tau_slab_rows(int ng, int np, int nt, int nbil, int nv_lut);   // R that fits LDS (>= 0)
@@ -313,6 +330,14 @@ hipError_t launch_rte_lw_split(const RteLwArgs &a, hipStream_t s);
 hipError_t launch_rte_lw_planck(const RteLwArgs &a, const double *planck, int ntp, double t0, double dt, const double *tlay,
                                 const double *tlev, const double *tsfc, hipStream_t s, double *flux_up_clear = nullptr,
                                 double *flux_dn_clear = nullptr, double *flux_up_jac = nullptr);
+// The rescaled no-scattering solver in the layer-split form (fp64, 60 layers): three exchanges per iteration.  a.ssa / a.g
+// beside a.tau and the three source arrays ...
+hipError_t launch_rte_lw_rescaled_split(const RteLwArgs &a, hipStream_t s);
+// ... or the Planck-recomputing form: a.tau is the gas optical depth and the cell's (tau, ssa, g) is formed from the band
+// triple a.part_tau / part_ssa / part_g (and a.part_mask) with the operations of the by-band increment_2stream_by_2stream
+bool rte_lw_rescaled_planck_fits(int ng, int ntp);
+hipError_t launch_rte_lw_rescaled_planck(const RteLwArgs &a, const double *planck, int ntp, double t0, double dt,
+                                         const double *tlay, const double *tlev, const double *tsfc, hipStream_t s);
 hipError_t launch_rte_sw(const RteSwArgs &a, hipStream_t s);
 // layer-systolic shortwave solver (kernels_rte_sw_sys.hip): any precision, nlay <= 60
 bool rte_sw_sys_applies(const RteSwArgs &a);

@@ -197,6 +197,81 @@ __global__ void __launch_bounds__(256) lw_2str_gpt_kernel(const RteGptArgs a) {
   }
 }
 
+// lw_solver_1rescl_GaussQuad: the rescaled no-scattering solver (include/ecckd_hip.h, "Rescaled longwave", in the order
+// spelt there; IEEE arithmetic).  Three sweeps per angle, each recomputing the cell; a.work carries the radiances from one
+// sweep to the next by level counted from the top: sweep 1 leaves dn0 there, sweep 2 reads dn0 at the top of its layer and
+// leaves the adjusted upward radiance at the layer's lower level, which sweep 3 reads.  Slow by design: 3 exp per
+// (cell, angle) and 16 B/cell through `work` beside the 48 B of inputs per sweep.
+__global__ void __launch_bounds__(256) lw_1rescl_gpt_kernel(const RteLwRescGptArgs a) {
+  const long n = (long)a.ncol * a.ng;
+  const int nlay = a.nlay, nlev = nlay + 1;
+  const long ncol = a.ncol;
+  const double pi = acos(-1.);
+  for (long id = (long)blockIdx.x * blockDim.x + threadIdx.x; id < n; id += (long)gridDim.x * blockDim.x) {
+    const long c = id % ncol, g = id / ncol;
+    const long base3 = c + ncol * nlay * g, basef = c + ncol * nlev * g, base2 = c + ncol * g;
+    const long lay0 = a.top_at_1 ? 0 : nlay - 1, lev0 = a.top_at_1 ? 0 : nlay, lstep = a.top_at_1 ? 1 : -1;
+    const double *Bdn = a.top_at_1 ? a.lev_source_inc : a.lev_source_dec;
+    const double *Bup = a.top_at_1 ? a.lev_source_dec : a.lev_source_inc;
+    const double eps = a.nband > 0 ? a.sfc_emis[a.gpt2band[g] + (long)a.nband * c] : a.sfc_emis[base2];
+    const double sfc_src = a.sfc_src[base2];
+    const double inc = a.inc_flux ? a.inc_flux[base2] : 0.;
+    double *work = a.work + basef;
+    for (int k = 0; k < a.nmus; ++k) {
+      const double D = a.Ds[k], w = a.wts[k], wfac = 2. * pi * w;
+      auto put = [&](double *arr, int s, double v) {
+        const long q = basef + ncol * (lev0 + lstep * s);
+        arr[q] = k == 0 ? v : arr[q] + v;
+      };
+      // t, sdn of layer s (from the top), and what the two adjusted sweeps need: CA = Cn*(1 - t*t),
+      // sua = sup - Cn*(sdn*t + sup), sda = sdn - Cn*(sup*t + sdn)
+      auto cell = [&](int s, double &t, double &sdn, double &ca, double &sua, double &sda) {
+        const long q = base3 + ncol * (lay0 + lstep * s);
+        const double ssa = a.ssa[q], gq = a.g[q];
+        const double wb = ssa * (1. - gq) * 0.5;
+        const double sc = (1. - ssa) + wb;
+        const double tl = a.tau[q] * sc * D;
+        const double Cn = 0.4 * (wb / sc);
+        t = exp(-tl);
+        const double series = a.series3 ? tl * (0.5 + tl * (-1. / 3. + tl * (1. / 8.))) : tl * (0.5 - 1. / 3. * tl);
+        const double fact = tl > a.tau_thresh ? (1. - t) / tl - t : series;
+        const double lay = a.lay_source[q], bdn = Bdn[q], bup = Bup[q];
+        sdn = (1. - t) * bdn + 2. * fact * (lay - bdn);
+        const double sup = (1. - t) * bup + 2. * fact * (lay - bup);
+        ca = Cn * (1. - t * t);
+        sua = sup - Cn * (sdn * t + sup);
+        sda = sdn - Cn * (sup * t + sdn);
+      };
+      const double I0 = a.inc_flux ? (a.inc_isotropic ? inc / pi : inc / (2. * pi * w)) : 0.;
+      double I = I0;
+      for (int s = 0; s < nlay; ++s) {   // sweep 1: dn0
+        double t, sdn, ca, sua, sda;
+        cell(s, t, sdn, ca, sua, sda);
+        work[ncol * s] = I;
+        I = t * I + sdn;
+      }
+      double U = I * (1. - eps) + eps * sfc_src;   // the surface sees the unadjusted dn0
+      for (int s = nlay - 1; s >= 0; --s) {   // sweep 2: adjusted up
+        double t, sdn, ca, sua, sda;
+        cell(s, t, sdn, ca, sua, sda);
+        put(a.flux_up, s + 1, wfac * U);
+        const double d0 = work[ncol * s];
+        work[ncol * (s + 1)] = U;
+        U = t * U + (sua + ca * d0);
+      }
+      put(a.flux_up, 0, wfac * U);
+      I = I0;
+      for (int s = 0; s < nlay; ++s) {   // sweep 3: adjusted down
+        double t, sdn, ca, sua, sda;
+        cell(s, t, sdn, ca, sua, sda);
+        put(a.flux_dn, s, wfac * I);
+        I = t * I + (sda + ca * work[ncol * (s + 1)]);
+      }
+      put(a.flux_dn, nlay, wfac * I);
+    }
+  }
+}
+
 }  // namespace
 
 static unsigned gpt_blocks(long n) {
@@ -219,6 +294,13 @@ hipError_t launch_sw_gpt(const RteGptArgs &a, hipStream_t s) {
 hipError_t launch_lw_2str_gpt(const RteGptArgs &a, hipStream_t s) {
   if (a.ncol <= 0 || a.ng <= 0) return hipSuccess;
   hipLaunchKernelGGL(lw_2str_gpt_kernel, dim3(gpt_blocks((long)a.ncol * a.ng)), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_lw_1rescl_gpt(const RteLwRescGptArgs &a, hipStream_t s) {
+  if (a.ncol <= 0 || a.ng <= 0) return hipSuccess;
+  if (!a.work) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(lw_1rescl_gpt_kernel, dim3(gpt_blocks((long)a.ncol * a.ng)), dim3(256), 0, s, a);
   return hipGetLastError();
 }
 

@@ -83,7 +83,20 @@ __host__ __device__ constexpr int planck_stride(int ng) { return ng | 1; }   // 
 // ([NL+1][CW], 15.6 KB) does not fit next to two groups and the Planck table, so this form runs one group per block and
 // one wave per SIMD like the dual-sky form (59.1 KB + the table).  The flux expressions and the order in which a level's
 // flux accumulators receive their g-points are untouched: the fluxes are the single-sky kernels' bit for bit.
-template <int SEG, int NW, int CW, bool SHARED, bool SER3, bool PLANCK, int SKY, bool MASK = false, bool BOTH = false, bool JAC = false>
+// RESC (rte_lw_split_rescaled_kernel, ecckd_rte_lw_rescaled; with PLANCK and SKY = 2 rte_lw_split_rescaled_allsky_kernel,
+// ecckd_lw_fluxes_allsky_rescaled): the rescaled no-scattering solver (include/ecckd_hip.h, "Rescaled longwave").  The cell
+// has (tau, ssa, g) -- read from a.tau / a.ssa / a.g, or formed from the gas optical depth and the band triple with the
+// operations of increment_2stream_by_2stream (kernels_optical_props.hip) -- and phase 1 keeps five values per layer: t, sdn,
+// CA = Cn*(1 - t*t), SUA = sup - Cn*(sdn*t + sup) (in SU[]) and SDA = sdn - Cn*(sup*t + sdn).  The three sweeps are three
+// affine recurrences whose sources are known once the sweep before is finished, so phase 2 has three exchanges:
+//   1. (T, D) as above gives dn0 entering the segment; the wave walks dn0 through its layers, SU[s] += CA[s]*dn0[s], and
+//      composes U of the adjusted up sweep;
+//   2. (T, U): the adjusted up sweep, accumulated per level as above, SDA[s] += CA[s]*up[s+1], and D of the adjusted down
+//      sweep (into the slot of the first exchange's D, which every wave has read before the second barrier);
+//   3. (T, D): the adjusted down sweep, accumulated per level as above.
+// One group per block.  No other instantiation changes: every RESC statement sits behind `if constexpr`.
+template <int SEG, int NW, int CW, bool SHARED, bool SER3, bool PLANCK, int SKY, bool MASK = false, bool BOTH = false, bool JAC = false,
+          bool RESC = false>
 __device__ __forceinline__ void rte_lw_split_body(const RteLwArgs &a, const PlanckTab &pt, const double *tlay, const double *tlev,
                                                   const double *tsfc, [[maybe_unused]] double *flux_up_clear = nullptr,
                                                   [[maybe_unused]] double *flux_dn_clear = nullptr,
@@ -92,10 +105,12 @@ __device__ __forceinline__ void rte_lw_split_body(const RteLwArgs &a, const Plan
   static_assert(SKY != 0 || !MASK, "a cloud mask belongs to the all-sky form");
   static_assert(SKY != 0 || !BOTH, "the dual-sky form extends the all-sky form");
   static_assert(!JAC || (PLANCK && !BOTH), "the Jacobian form extends the single-sky Planck-recomputing solver");
+  static_assert(!RESC || (!SHARED && !BOTH && !JAC && (PLANCK ? SKY == 2 : SKY == 0)),
+                "the rescaled form reads arrays, or recomputes Planck sources and takes a two-stream band triple");
   constexpr int GW = 64 / CW;
   constexpr int NL = SEG * NW;
-  constexpr int NG = (BOTH || JAC) ? 1 : split_groups(PLANCK);
-  constexpr int kSplitPF = split_pf(PLANCK);
+  constexpr int NG = (BOTH || JAC || RESC) ? 1 : split_groups(PLANCK);
+  constexpr int kSplitPF = (RESC && !PLANCK) ? 1 : split_pf(PLANCK);   // (RESC on arrays: six arrays in flight per layer, no room for a second layer)
   constexpr int kSkyDoubles = 2 * (NL + 1) * CW + 2 * NW * 3 * 64;   // accumulators and exchange of one sky
   constexpr int kGroupDoubles = (BOTH ? 2 : 1) * kSkyDoubles + (JAC ? (NL + 1) * CW : 0);
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
@@ -150,6 +165,7 @@ __device__ __forceinline__ void rte_lw_split_body(const RteLwArgs &a, const Plan
     [[maybe_unused]] double ptl[PLANCK ? kSplitPF : 1], ptv[PLANCK ? kSplitPF : 1];   // PLANCK: tlay(l), tlev(far edge of l)
     [[maybe_unused]] double ppt[SKY ? kSplitPF : 1], pps[SKY == 2 ? kSplitPF : 1];   // SKY: part_tau(l), part_ssa(l) of the lane's band
     [[maybe_unused]] long qb = 0;      // SKY: offset of the lane's band plane
+    [[maybe_unused]] double pss[RESC && !PLANCK ? kSplitPF : 1], pgg[RESC ? kSplitPF : 1];   // RESC: ssa(l) of the cell (arrays); g(l) of the cell, or part_g(l) of the lane's band
     [[maybe_unused]] unsigned pmk[MASK ? kSplitPF : 1];   // MASK: the half of part_mask(column, l) that holds the lane's g-point
     [[maybe_unused]] int mhalf = 0, mbit = 0;             // MASK: which half, and the bit inside it
     [[maybe_unused]] const unsigned *mask32 = reinterpret_cast<const unsigned *>(a.part_mask);
@@ -180,12 +196,17 @@ __device__ __forceinline__ void rte_lw_split_body(const RteLwArgs &a, const Plan
         ptv[slot] = tlev[q2 + (a.top_at_1 ? (long)ncol : 0)];   // far edge of the layer: level index l+1 (top_at_1) or l
         if (SKY) ppt[slot] = a.part_tau[q2 + qb];
         if (SKY == 2) pps[slot] = a.part_ssa[q2 + qb];
+        if constexpr (RESC) pgg[slot] = a.part_g[q2 + qb];
         if (MASK) pmk[slot] = mask32[2 * q2 + mhalf];
         q2 += qstep;
       } else {
         play_[slot] = __builtin_nontemporal_load(a.lay_source + qn);
         pbdn[slot] = __builtin_nontemporal_load(Bdn + qn);
         if (!SHARED) pbup[slot] = __builtin_nontemporal_load(Bup + qn);
+        if constexpr (RESC) {
+          pss[slot] = __builtin_nontemporal_load(a.ssa + qn);
+          pgg[slot] = __builtin_nontemporal_load(a.g + qn);
+        }
       }
       qn += qstep;
       asm volatile("" : "+v"(qn));
@@ -209,6 +230,7 @@ __device__ __forceinline__ void rte_lw_split_body(const RteLwArgs &a, const Plan
       double Tq = 1., Dq = 0.;
       [[maybe_unused]] double Tc[BOTH ? SEG : 1], SDNc[BOTH ? SEG : 1], SUc[BOTH ? SEG : 1];   // BOTH: the clear sky's
       [[maybe_unused]] double Tqc = 1., Dqc = 0.;
+      [[maybe_unused]] double CA[RESC ? SEG : 1], SDA[RESC ? SEG : 1];   // RESC: Cn*(1 - t*t), and the adjusted down source
       [[maybe_unused]] double carry = PLANCK ? planck_at(pt, ptab, pstride, near_first, gg, pi_f32, rpi_f32) : near_first;
 #pragma unroll
       for (int s = 0; s < SEG; ++s) {
@@ -217,8 +239,33 @@ __device__ __forceinline__ void rte_lw_split_body(const RteLwArgs &a, const Plan
         [[maybe_unused]] double tp = 0.;
         if (SKY) tp = ppt[s % kSplitPF];
         if (MASK) tp = (pmk[s % kSplitPF] >> mbit) & 1u ? tp : 0.;
+        if constexpr (!RESC) {
         if (SKY == 1) tau = tau + tp;
         if (SKY == 2) tau = tau + tp * (1. - pps[s % kSplitPF]);
+        }
+        [[maybe_unused]] double Cn = 0.;
+        if constexpr (RESC) {
+          double cssa, cg;
+          if constexpr (PLANCK) {
+            // increment_body<double, true, true, true, MASK> of kernels_optical_props.hip on op1 = (tau_gas, +0, +0)
+            constexpr double tiny3 = op_eps<double>();
+            const double tscat2 = tp * pps[s % kSplitPF];
+            const double tsg2 = tscat2 * pgg[s % kSplitPF];
+            const double tau12 = tau + tp;
+            const double tscat1 = tau * 0.;
+            const double tauscat12 = tscat1 + tscat2;
+            cg = (tscat1 * 0. + tsg2) / (tauscat12 > tiny3 ? tauscat12 : tiny3);
+            cssa = tauscat12 / (tau12 > tiny3 ? tau12 : tiny3);
+            tau = tau12;
+          } else {
+            cssa = pss[s % kSplitPF];
+            cg = pgg[s % kSplitPF];
+          }
+          const double wb = cssa * (1. - cg) * 0.5;
+          const double sc = (1. - cssa) + wb;
+          tau = tau * sc;
+          Cn = 0.4 * (wb / sc);   // (IEEE division: ssa = g = 1 gives 0/0, a NaN that stays in its column)
+        }
         double lay, bdn, bup;
         if (PLANCK) {
           lay = planck_at(pt, ptab, pstride, ptl[s % kSplitPF], gg, pi_f32, rpi_f32);
@@ -243,6 +290,11 @@ __device__ __forceinline__ void rte_lw_split_body(const RteLwArgs &a, const Plan
         double su = omt * bup + 2. * fact * (lay - bup);
         asm volatile("" : "+v"(su));
         T[s] = t; SDN[s] = sdn; SU[s] = su;
+        if constexpr (RESC) {
+          CA[s] = Cn * (1. - t * t);
+          SU[s] = su - Cn * (sdn * t + su);
+          SDA[s] = sdn - Cn * (su * t + sdn);
+        }
         Dq = t * Dq + sdn;
         Tq = Tq * t;
         if (BOTH) {   // the same cell under the clear sky: the expressions above on tau_c
@@ -262,8 +314,10 @@ __device__ __forceinline__ void rte_lw_split_body(const RteLwArgs &a, const Plan
         if (SHARED || PLANCK) carry = bdn;
       }
       double Uq = 0.;
+      if constexpr (!RESC) {   // (RESC: the up sweep's sources wait for dn0, behind the first exchange)
 #pragma unroll
       for (int s = SEG - 1; s >= 0; --s) Uq = T[s] * Uq + SU[s];
+      }
       [[maybe_unused]] double Uqc = 0.;
       if (BOTH) {
 #pragma unroll
@@ -278,7 +332,7 @@ __device__ __forceinline__ void rte_lw_split_body(const RteLwArgs &a, const Plan
       double *x = xch + (it & 1) * (NW * 3 * 64);
       x[(w * 3 + 0) * 64 + lane] = Tq;
       x[(w * 3 + 1) * 64 + lane] = Dq;
-      x[(w * 3 + 2) * 64 + lane] = Uq;
+      if constexpr (!RESC) x[(w * 3 + 2) * 64 + lane] = Uq;
       [[maybe_unused]] double *xc = xch_c + (it & 1) * (NW * 3 * 64);
       if (BOTH) {
         xc[(w * 3 + 0) * 64 + lane] = Tqc;
@@ -303,6 +357,56 @@ __device__ __forceinline__ void rte_lw_split_body(const RteLwArgs &a, const Plan
       const double eps = a.sfc_emis[a.gpt2band[gg] + (long)a.nband * cc];
       const double sfc_src = PLANCK ? planck_at(pt, ptab, pstride, tsfc[cc], gg, pi_f32, rpi_f32) : a.sfc_source[cc + (long)ncol * gg];
       double U = I * (1. - eps) + eps * sfc_src;   // surface
+      if constexpr (RESC) {
+        // the surface has seen the unadjusted dn0.  dn0 through this segment: the sources of the adjusted up sweep
+        const double Usfc = U;
+        I = Iin;
+#pragma unroll
+        for (int s = 0; s < SEG; ++s) {
+          SU[s] = SU[s] + CA[s] * I;
+          I = T[s] * I + SDN[s];
+        }
+#pragma unroll
+        for (int s = SEG - 1; s >= 0; --s) Uq = T[s] * Uq + SU[s];
+        x[(w * 3 + 2) * 64 + lane] = Uq;
+        __syncthreads();
+        U = Usfc;
+        double Uin = U;
+#pragma unroll
+        for (int q = NW - 1; q >= 0; --q) {
+          if (q == w) Uin = U;
+          U = x[(q * 3 + 0) * 64 + lane] * U + x[(q * 3 + 2) * 64 + lane];
+        }
+        // adjusted up sweep: levels s0+SEG .. s0+1; the radiance entering a layer from below adjusts its down source
+        U = Uin;
+#pragma unroll
+        for (int s = SEG - 1; s >= 0; --s) {
+          acc_add(&acc_up[(s0 + s + 1) * CW + cl], gsum<CW>(wfac * U), owner);
+          SDA[s] = SDA[s] + CA[s] * U;
+          U = T[s] * U + SU[s];
+        }
+        if (w == 0) acc_add(&acc_up[cl], gsum<CW>(wfac * U), owner);
+        double D3 = 0.;
+#pragma unroll
+        for (int s = 0; s < SEG; ++s) D3 = T[s] * D3 + SDA[s];
+        x[(w * 3 + 1) * 64 + lane] = D3;   // (every wave read the first exchange's D before the barrier above)
+        __syncthreads();
+        I = Itop;
+        Iin = I;
+#pragma unroll
+        for (int q = 0; q < NW; ++q) {
+          if (q == w) Iin = I;
+          I = x[(q * 3 + 0) * 64 + lane] * I + x[(q * 3 + 1) * 64 + lane];
+        }
+        // adjusted down sweep: levels s0 .. s0+SEG-1; the last wave adds the surface
+        I = Iin;
+#pragma unroll
+        for (int s = 0; s < SEG; ++s) {
+          acc_add(&acc_dn[(s0 + s) * CW + cl], gsum<CW>(wfac * I), owner);
+          I = T[s] * I + SDA[s];
+        }
+        if (w == NW - 1) acc_add(&acc_dn[NL * CW + cl], gsum<CW>(wfac * I), owner);
+      } else {
       double Uin = U;
 #pragma unroll
       for (int q = NW - 1; q >= 0; --q) {
@@ -340,6 +444,7 @@ __device__ __forceinline__ void rte_lw_split_body(const RteLwArgs &a, const Plan
       }
       if (w == 0) acc_add(&acc_up[cl], gsum<CW>(wfac * U), owner);
       if (JAC && w == 0) acc_add(&acc_jac[cl], gsum<CW>(wfac * J), owner);
+      }
       if (BOTH) {   // phase 2 once more, on the clear sky's composites into the clear sky's accumulators
         double Ic = Itop, Iinc = Itop;
 #pragma unroll
@@ -437,6 +542,55 @@ template <int SEG, int NW, int CW, bool SER3, int SKY, bool MASK>
 __global__ void __launch_bounds__(64 * NW, 1) rte_lw_split_jac_kernel(const RteLwArgs a, const PlanckTab pt, const double *tlay,
                                                                       const double *tlev, const double *tsfc, double *flux_up_jac) {
   rte_lw_split_body<SEG, NW, CW, false, SER3, true, SKY, MASK, false, true>(a, pt, tlay, tlev, tsfc, nullptr, nullptr, flux_up_jac);
+}
+
+// The rescaled forms (RESC of rte_lw_split_body), one group per block: on arrays (tau, ssa, g, three sources) ...
+template <int SEG, int NW, int CW, bool SER3, int WPS>
+__global__ void __launch_bounds__(64 * NW, WPS) rte_lw_split_rescaled_kernel(const RteLwArgs a, const PlanckTab pt) {
+  rte_lw_split_body<SEG, NW, CW, false, SER3, false, 0, false, false, false, true>(a, pt, nullptr, nullptr, nullptr);
+}
+// ... and Planck-recomputing with the two-stream band triple (MASK: and a McICA cloud mask)
+template <int SEG, int NW, int CW, bool SER3, bool MASK, int WPS>
+__global__ void __launch_bounds__(64 * NW, WPS) rte_lw_split_rescaled_allsky_kernel(const RteLwArgs a, const PlanckTab pt,
+                                                                                    const double *tlay, const double *tlev,
+                                                                                    const double *tsfc) {
+  rte_lw_split_body<SEG, NW, CW, false, SER3, true, 2, MASK, false, false, true>(a, pt, tlay, tlev, tsfc);
+}
+
+// Both rescaled forms walk 15 layers per wave with 4 waves per block and 32 columns per tile: the fused call equals the
+// composed one bit for bit only if both compose their segments alike ("lw_split_seg" does not act here).
+constexpr int kRescSeg = 15, kRescNW = 4, kRescCW = 32;
+constexpr int kRescWps = 2;         // arrays: 75 doubles of layer state per lane, two waves per SIMD
+constexpr int kRescWpsPlanck = 1;   // Planck-recomputing: one block per CU (its LDS), one wave per SIMD
+constexpr size_t resc_lds_doubles() { return 2 * (size_t)(kRescSeg * kRescNW + 1) * kRescCW + 2 * kRescNW * 3 * 64; }
+
+template <bool SER3>
+hipError_t launch_rescaled(const RteLwArgs &a, hipStream_t s) {
+  const PlanckTab none{nullptr, 0., 1., 1., 2, a.ng};
+  auto k = rte_lw_split_rescaled_kernel<kRescSeg, kRescNW, kRescCW, SER3, kRescWps>;
+  const size_t lds = sizeof(double) * resc_lds_doubles();
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (e != hipSuccess) return e;
+  long blocks = ((long)a.ncol + kRescCW - 1) / kRescCW;
+  const long cap = 256L * kRescWps * 4;   // four rounds of resident blocks; the rest by grid stride (as launch_split)
+  if (blocks > cap) blocks = cap;
+  hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(64 * kRescNW), lds, s, a, none);
+  return hipGetLastError();
+}
+
+template <bool SER3, bool MASK>
+hipError_t launch_rescaled_planck(const RteLwArgs &a, const PlanckTab &pt, const double *tlay, const double *tlev, const double *tsfc,
+                                  hipStream_t s) {
+  auto k = rte_lw_split_rescaled_allsky_kernel<kRescSeg, kRescNW, kRescCW, SER3, MASK, kRescWpsPlanck>;
+  const size_t lds = sizeof(double) * (resc_lds_doubles() + (size_t)pt.ntp * planck_stride(a.ng));
+  if (lds > (size_t)kLdsBudget) return hipErrorInvalidValue;
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (e != hipSuccess) return e;
+  long blocks = ((long)a.ncol + kRescCW - 1) / kRescCW;
+  const long cap = 256L * 4;   // one block is resident per CU; the rest by grid stride, as launch_split_both
+  if (blocks > cap) blocks = cap;
+  hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(64 * kRescNW), lds, s, a, pt, tlay, tlev, tsfc);
+  return hipGetLastError();
 }
 
 template <int SEG, int NW, int CW, bool SER3, int SKY, bool MASK>
@@ -589,6 +743,27 @@ hipError_t launch_rte_lw_planck(const RteLwArgs &a, const double *planck, int nt
   }
   return a.series3 ? launch_seg<false, true, true>(a, pt, tlay, tlev, tsfc, s)
                    : launch_seg<false, false, true>(a, pt, tlay, tlev, tsfc, s);
+}
+
+hipError_t launch_rte_lw_rescaled_split(const RteLwArgs &a, hipStream_t s) {
+  if (a.f32 || a.nlay != kRescSeg * kRescNW || a.ncol <= 0 || !a.ssa || !a.g) return hipErrorInvalidValue;
+  return a.series3 ? launch_rescaled<true>(a, s) : launch_rescaled<false>(a, s);
+}
+
+bool rte_lw_rescaled_planck_fits(int ng, int ntp) {
+  return sizeof(double) * (resc_lds_doubles() + (size_t)ntp * planck_stride(ng)) <= (size_t)kLdsBudget;
+}
+
+hipError_t launch_rte_lw_rescaled_planck(const RteLwArgs &a, const double *planck, int ntp, double t0, double dt,
+                                         const double *tlay, const double *tlev, const double *tsfc, hipStream_t s) {
+  if (a.f32 || a.nlay != kRescSeg * kRescNW || a.ncol <= 0 || !a.part_tau || !a.part_ssa || !a.part_g) return hipErrorInvalidValue;
+  if (a.part_mask && a.ng > 64) return hipErrorInvalidValue;
+  const PlanckTab pt{planck, t0, dt, 1. / dt, ntp, a.ng};
+  if (a.part_mask)
+    return a.series3 ? launch_rescaled_planck<true, true>(a, pt, tlay, tlev, tsfc, s)
+                     : launch_rescaled_planck<false, true>(a, pt, tlay, tlev, tsfc, s);
+  return a.series3 ? launch_rescaled_planck<true, false>(a, pt, tlay, tlev, tsfc, s)
+                   : launch_rescaled_planck<false, false>(a, pt, tlay, tlev, tsfc, s);
 }
 
 }  // namespace ecckd
