@@ -723,8 +723,8 @@ int ecckd_lw_fluxes_allsky_2stream(const ecckd_model_t *model, int ncol, int nla
  *     60 layers:  8*n3                                              (the gas optical depth)
  *     otherwise:  8*(6*n3 + r32(ncol*ngpt)) + ecckd_rte_lw_rescaled_scratch_bytes(ncol, nlay, ngpt)
  *   in the order optical depth, ssa, g, the three Planck arrays, surface source, the solver's planes.
- * Out of scope: single precision; per-band and Jacobian outputs; both skies in one call; delta scaling inside the fused
- *   call (the host calls ecckd_delta_scale on its band triple first); ECCKD_MIXED; a tail split for small calls; a fast form
+ * Out of scope: single precision; per-band outputs (the Jacobian and both skies in one call: the next block); delta scaling
+ *   inside the fused call (the host calls ecckd_delta_scale on its band triple first); ECCKD_MIXED; a tail split for small calls; a fast form
  *   away from 60 layers; the Fortran type-bound rte_lw; RTE's bind(C) name lw_solver_1rescl_GaussQuad in librte_kernels_hip.
  * --------------------------------------------------------------------------------------- */
 int ecckd_rte_lw_rescaled(int device, int ncol, int nlay, int ngpt, int top_at_1, int n_gauss_angles, const double *tau,
@@ -746,6 +746,69 @@ int ecckd_lw_fluxes_allsky_rescaled(const ecckd_model_t *model, int ncol, int nl
                                     const double *g_p, const unsigned long long *cloud_mask, double *flux_up, double *flux_dn,
                                     int memspace, void *stream);
 size_t ecckd_lw_fluxes_allsky_rescaled_scratch_bytes(const ecckd_model_t *model, int ncol, int nlay);
+
+/* ---------------------------------------------------------------------------------------
+ * Rescaled longwave: clear sky and Jacobian.  What the other fused longwave calls provide, for the rescaled solver: both
+ * skies from one gas-optics pass, and the surface-temperature Jacobian of flux_up (RTE's flux_up_Jac, which its rescaled
+ * solver returns; ecRad's lw_derivatives).  fp64, ECCKD_DEVICE or ECCKD_HOST.
+ *   The Jacobian: the three sweeps of "Rescaled longwave" with every layer, level and incident source zero.  Then dn0 == 0,
+ *   the adjusted up sweep reduces to up[s] = t*up[s+1] (RTE: radn_up_Jac = trans * radn_up_Jac inside the rescaled
+ *   transport), and per (column, g-point, angle k)
+ *     J(surface)             = sfc_emis(band(g), i) * sfc_source_jac(i, g)
+ *     J(level above layer s) = t_k(s) * J(level below),   t_k(s) = lw_exp(-((tau*sc)*D_k)),  sc = (1 - ssa) + (ssa*(1 - g))*0.5
+ *     flux_up_jac(i, lev)    = sum over g and k of 2*pi*w_k * J
+ *   with t_k formed operation by operation as the 60-layer flux kernel forms it on the cell's (tau, ssa, g), sfc_source_jac
+ *   = B(tsfc + 1) - B(tsfc) as ecckd_planck_sfc_source_jac gives it, and the weights, layout and weight-0 lanes of flux_up.
+ *   W m-2 K-1.  Under rescaling flux_dn ALSO depends on the surface temperature, through CA*up[s+1] in sweep 3: that
+ *   derivative is NOT returned, as in RTE (the zero-source run's flux_dn is not zero: up to 0.29 W m-2 K-1 on the test
+ *   columns).  inc_flux does not enter.
+ * ecckd_rte_lw_rescaled_jac: ecckd_rte_lw_rescaled with sfc_source_jac(ncol,ngpt) behind sfc_source and
+ *   flux_up_jac(ncol,nlay+1) behind flux_dn.  flux_up / flux_dn are those of ecckd_rte_lw_rescaled bit for bit (its kernels,
+ *   launched unchanged); the Jacobian comes from the stand-alone Jacobian kernel on (tau, ssa, g) at every layer count (the
+ *   60-layer arrays kernel is at its register limit).  No scratch beyond ecckd_rte_lw_rescaled_scratch_bytes.  Refused before
+ *   any launch and before a device is asked for: the list of ecckd_rte_lw_rescaled in its order, then sfc_source_jac or
+ *   flux_up_jac NULL, then flux_up_jac equal to flux_up or flux_dn.
+ * ecckd_lw_fluxes_rescaled_jac: the superset of ecckd_lw_fluxes_allsky_rescaled, with flux_up_clear, flux_dn_clear and
+ *   flux_up_jac (ncol,nlay+1) behind flux_dn; each may be NULL, and with all three NULL the call IS
+ *   ecckd_lw_fluxes_allsky_rescaled.  flux_up / flux_dn are that call's bit for bit, with cloud_mask, at every layer count
+ *   and in both orientations, whatever else is asked for.
+ *   Clear-sky outputs (together or not at all): bit for bit what ecckd_lw_fluxes writes for the same atmosphere,
+ *   n_gauss_angles and inc_flux, from the one scratch optical depth -- the clear-sky launch of ecckd_lw_fluxes_clear_allsky
+ *   with "lw_both_skies" = 0, in front of the all-sky pass (general route: before the by-band increment, on the Planck
+ *   sources the rescaled route has in scratch).  There is no dual-sky rescaled kernel.
+ *   flux_up_jac: the Jacobian of the ALL sky.  60 layers and "lw_jac_inline" = 1 (the default): inside the rescaled all-sky
+ *   kernel -- the surface term eps*(B(tsfc + 1) - B(tsfc)) folded through the transmissivities of the waves below and
+ *   carried through the adjusted up sweep, a third accumulator plane in LDS; same occupancy (one wave per SIMD), no spill.
+ *   Otherwise the stand-alone kernel behind the flux pass: at 60 layers on the gas optical depth and the (masked) band
+ *   triple with the flux kernel's expressions, on the general route on the (tau, ssa, g) the increment left in scratch.
+ *   The surface term is formed in the kernels from tsfc and the Planck table: nothing of size (ncol,ngpt) is staged.  The two
+ *   routes sum in different orders: they agree to rounding, not bit for bit.
+ *   ecckd_lw_fluxes_rescaled_jac_scratch_bytes(model, ncol, nlay, with_clear): with_clear = 0 equals
+ *   ecckd_lw_fluxes_allsky_rescaled_scratch_bytes (flux_up_jac needs none).  with_clear != 0 adds, behind that block, what
+ *   the clear pass needs on its general route: at 60 layers nothing for a model whose Planck table fits the clear-sky
+ *   layer-split kernel (every shipped model), else 8*r32(3*ncol*nlay*ngpt + ncol*ngpt + 32 + ecckd_rte_lw_scratch_bytes/8);
+ *   at any other layer count 8*r32(ecckd_rte_lw_scratch_bytes(ncol, nlay, ngpt)/8), the solver's ring.  Capturable after one
+ *   warm-up call on the stream, and with ecckd_set_stream_scratch.
+ *   Refused, all before the model is asked for its device: the list of ecckd_lw_fluxes_allsky_rescaled up to the angle
+ *   count, in its order and with its messages; then exactly one clear-sky output NULL; then a clear-sky output equal to an
+ *   all-sky output; then flux_up_jac equal to another output; then a host-only model and the rest of that list.
+ * Out of scope: the two-stream solver (RTE has no Jacobian for it); a dual-sky rescaled kernel; single precision; per-band
+ *   output; ECCKD_MIXED; a fast rescaled form away from 60 layers; the Fortran type-bound interface; a bind(C) name in
+ *   librte_kernels_hip.
+ * --------------------------------------------------------------------------------------- */
+int ecckd_rte_lw_rescaled_jac(int device, int ncol, int nlay, int ngpt, int top_at_1, int n_gauss_angles, const double *tau,
+                              const double *ssa, const double *g, const double *lay_source, const double *lev_source_inc,
+                              const double *lev_source_dec, const double *sfc_source, const double *sfc_source_jac, int nband,
+                              const int *band2gpt, const double *sfc_emis, const double *inc_flux, double *flux_up,
+                              double *flux_dn, double *flux_up_jac, int memspace, void *stream);
+int ecckd_lw_fluxes_rescaled_jac(const ecckd_model_t *model, int ncol, int nlay, const double *plev, const double *tlay,
+                                 const double *tsfc, const double *tlev, int ngas, const char *gas_names,
+                                 const double *const *vmr, const long long *vmr_col_stride, const long long *vmr_lay_stride,
+                                 const double *vmr_scalar, int top_at_1, int n_gauss_angles, const double *sfc_emis,
+                                 const double *inc_flux, int nband_p, const double *tau_p, const double *ssa_p,
+                                 const double *g_p, const unsigned long long *cloud_mask, double *flux_up, double *flux_dn,
+                                 double *flux_up_clear, double *flux_dn_clear, double *flux_up_jac, int memspace, void *stream);
+size_t ecckd_lw_fluxes_rescaled_jac_scratch_bytes(const ecckd_model_t *model, int ncol, int nlay, int with_clear);
 
 /* Spectral (per-band) fluxes: what RTE-RRTMGP callers get by passing a ty_fluxes_byband to rte_lw /
  * rte_sw instead of the ty_fluxes_broadband the reference drivers use (ecckd_rfmip_lw.F90:108-109).

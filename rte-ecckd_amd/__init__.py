@@ -222,6 +222,14 @@ def lib():
         L.ecckd_lw_fluxes_allsky_rescaled.argtypes = ([C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_char_p] +
                                                       [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int] +
                                                       [C.c_void_p] * 6 + [C.c_int, C.c_void_p])
+    if hasattr(L, "ecckd_lw_fluxes_rescaled_jac"):   # (an older build lacks them: tools/bench_lw_rescaled_jac.py --parent-lib)
+        L.ecckd_rte_lw_rescaled_jac.argtypes = ([C.c_int] * 6 + [C.c_void_p] * 8 + [C.c_int] + [C.c_void_p] * 6 +
+                                                [C.c_int, C.c_void_p])
+        L.ecckd_lw_fluxes_rescaled_jac.argtypes = ([C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_char_p] +
+                                                   [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int] +
+                                                   [C.c_void_p] * 9 + [C.c_int, C.c_void_p])
+        L.ecckd_lw_fluxes_rescaled_jac_scratch_bytes.restype = C.c_size_t
+        L.ecckd_lw_fluxes_rescaled_jac_scratch_bytes.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
     _lib = L
     return L
 
@@ -980,7 +988,7 @@ class GasOpticsEcckd:
         if not isinstance(particles, OpticalProps2str) or particles.g is None:
             return who + "the particles must be two-stream optical properties on the model's bands, with g (alloc_2str_bands)"
         if flux_up_jac is not None:
-            return who + "flux_up_jac is not implemented"
+            return who + "flux_up_jac is not implemented for this keyword (lw_fluxes_rescaled returns it)"
         if isinstance(fluxes, FluxesByband):
             return who + "per-band fluxes are not implemented (broadband fluxes only)"
         if any(_is_f32(a) for a in (tlay, particles.tau)):
@@ -1022,8 +1030,8 @@ class GasOpticsEcckd:
         parameter).  ``rescaled=True`` (``ecckd_lw_fluxes_allsky_rescaled``; by keyword): the rescaled no-scattering solver --
         what RTE-RRTMGP's ``rte_lw`` runs on two-stream properties without ``use_2stream``: cloud scattering as an adjustment of
         the no-scattering sweeps, with the quadrature (``n_gauss_angles`` 1..4); a two-stream ``particles`` object with ``g``,
-        float64; refused with ``use_2stream=True``, ``flux_up_jac``, ``FluxesByband``.  Returns the error message
-        ('' = success)."""
+        float64; refused with ``use_2stream=True``, ``flux_up_jac`` (``lw_fluxes_rescaled`` returns it, and the clear sky),
+        ``FluxesByband``.  Returns the error message ('' = success)."""
         if rescaled:
             return self._lw_fluxes_allsky_rescaled(plev, tlay, tsfc, tlev, gas_desc, top_at_1, sfc_emis, particles, fluxes,
                                                    n_gauss_angles, inc_flux, cloud_mask, use_2stream, flux_up_jac)
@@ -1055,6 +1063,51 @@ class GasOpticsEcckd:
             nbp, *part, _ptr(fluxes.flux_up, (nlay + 1, ncol), "flux_up"), _ptr(fluxes.flux_dn, (nlay + 1, ncol), "flux_dn"),
             space, _stream(space))
         return last_error() if rc else ""
+
+    def lw_fluxes_rescaled(self, plev, tlay, tsfc, tlev, gas_desc, top_at_1, sfc_emis, particles, fluxes, fluxes_clear=None,
+                           flux_up_jac=None, n_gauss_angles=1, inc_flux=None, cloud_mask=None):
+        """``ecckd_lw_fluxes_rescaled_jac``: ``lw_fluxes_allsky(..., rescaled=True)`` with, from the same gas-optics pass,
+        the clear sky -- ``fluxes_clear`` receives what ``lw_fluxes`` writes, bit for bit -- and ``flux_up_jac``
+        ``(nlay+1, ncol)``, the surface-temperature Jacobian of the all-sky ``flux_up`` under the rescaled solver, W m-2 K-1
+        (the derivative of ``flux_dn``, which is not zero under rescaling, is not returned).  ``fluxes`` holds the bits of
+        ``lw_fluxes_allsky(..., rescaled=True)`` whatever else is asked for.  ``particles``: a two-stream object on the model's
+        bands with ``g``; float64, fast arithmetic mode; numpy or device tensors.  Returns the error message ('' = success)."""
+        who = "lw_fluxes_rescaled: "
+        if not isinstance(particles, OpticalProps2str) or particles.g is None:
+            return who + "the particles must be two-stream optical properties on the model's bands, with g (alloc_2str_bands)"
+        if isinstance(fluxes, FluxesByband) or isinstance(fluxes_clear, FluxesByband):
+            return who + "per-band fluxes are not implemented (broadband fluxes only)"
+        if any(_is_f32(a) for a in (tlay, particles.tau)):
+            return who + "implemented for float64 arrays"
+        nlay, ncol = tlay.shape
+        ng = self.get_ngpt()
+        clear = [] if fluxes_clear is None else [fluxes_clear.flux_up, fluxes_clear.flux_dn]
+        try:
+            space = _space_of([plev, tlay, tsfc, tlev, sfc_emis, inc_flux, fluxes.flux_up, fluxes.flux_dn, particles.tau,
+                               particles.ssa, particles.g, flux_up_jac] + clear)
+            n, names, ptrs, cs, ls, sc, keep = self._gas_args(gas_desc, ncol, nlay, space)
+            nbp = 0 if particles.tau is None else int(particles.tau.shape[0])
+            shp = (nbp, nlay, ncol)
+            part = (_ptr(particles.tau, shp, "particles.tau"), _ptr(particles.ssa, shp, "particles.ssa"),
+                    _ptr(particles.g, shp, "particles.g"), _mask_ptr(cloud_mask, nlay, ncol, space))
+            lev = (nlay + 1, ncol)
+            inp = (_ptr(plev, lev, "plev"), _ptr(tlay, (nlay, ncol), "tlay"), _ptr(tsfc, (ncol,), "tsfc"), _ptr(tlev, lev, "tlev"))
+            emis = (_ptr(sfc_emis, (ncol, self.get_nband()), "sfc_emis"), _ptr(inc_flux, (ng, ncol), "inc_flux"))
+            out = (_ptr(fluxes.flux_up, lev, "flux_up"), _ptr(fluxes.flux_dn, lev, "flux_dn"),
+                   None if fluxes_clear is None else _ptr(fluxes_clear.flux_up, lev, "flux_up_clear"),
+                   None if fluxes_clear is None else _ptr(fluxes_clear.flux_dn, lev, "flux_dn_clear"),
+                   _ptr(flux_up_jac, lev, "flux_up_jac"))
+        except KeyError as e:
+            return str(e.args[0])
+        except (TypeError, ValueError) as e:
+            return str(e)
+        rc = lib().ecckd_lw_fluxes_rescaled_jac(self._need(), ncol, nlay, *inp, n, names, ptrs, cs, ls, sc, int(bool(top_at_1)),
+                                                int(n_gauss_angles), *emis, nbp, *part, *out, space, _stream(space))
+        return last_error() if rc else ""
+
+    def lw_fluxes_rescaled_scratch_bytes(self, ncol, nlay, with_clear=False):
+        """``ecckd_lw_fluxes_rescaled_jac_scratch_bytes``: the stream scratch of ``lw_fluxes_rescaled`` on device tensors."""
+        return int(lib().ecckd_lw_fluxes_rescaled_jac_scratch_bytes(self._need(), int(ncol), int(nlay), int(bool(with_clear))))
 
     def lw_fluxes_clear_allsky(self, plev, tlay, tsfc, tlev, gas_desc, top_at_1, sfc_emis, particles, fluxes, fluxes_clear,
                                n_gauss_angles=1, inc_flux=None, cloud_mask=None):
@@ -1298,7 +1351,7 @@ def _rte_lw_rescaled(optical_props, top_at_1, sources, sfc_emis, fluxes, n_gauss
     if isinstance(fluxes, FluxesByband):
         return who + "per-band fluxes are not implemented (broadband fluxes only)"
     if flux_up_jac is not None:
-        return who + "flux_up_jac is not implemented"
+        return who + "flux_up_jac is not implemented for this keyword (rte_lw_rescaled_jac returns it)"
     ng, nlay, ncol = optical_props.tau.shape
     b2g = np.ascontiguousarray(optical_props.band2gpt, dtype=np.int32)
     nband = b2g.shape[0]
@@ -1317,6 +1370,47 @@ def _rte_lw_rescaled(optical_props, top_at_1, sources, sfc_emis, fluxes, n_gauss
     dev = _device_of(optical_props.tau) if device is None else device
     rc = lib().ecckd_rte_lw_rescaled(int(dev), ncol, nlay, ng, int(bool(top_at_1)), int(n_gauss_angles), *a3, sfc, nband,
                                      C.c_void_p(b2g.ctypes.data), *rest, space, _stream(space))
+    return last_error() if rc else ""
+
+
+def rte_lw_rescaled_jac(optical_props, top_at_1, sources, sfc_emis, fluxes, flux_up_jac, n_gauss_angles=1, device=None, inc_flux=None):
+    """``ecckd_rte_lw_rescaled_jac``: ``rte_lw(..., rescaled=True)`` plus ``flux_up_jac`` ``(nlay+1, ncol)`` float64, the
+    derivative of ``flux_up`` with respect to the surface temperature under the rescaled solver (rte_lw's ``flux_up_Jac``), from
+    ``sources.sfc_source_jac`` (``GasOpticsEcckd.planck_sfc_source_jac``).  The fluxes are those of ``rte_lw(..., rescaled=True)``
+    bit for bit; the derivative of ``flux_dn`` (not zero under rescaling) is not returned.  An ``OpticalProps2str`` (float64),
+    ``n_gauss_angles`` 1..4, broadband fluxes, ``inc_flux`` accepted (it does not enter the Jacobian); numpy or device tensors.
+    Returns the error message ('' = success)."""
+    who = "rte_lw_rescaled_jac: "
+    if not isinstance(optical_props, OpticalProps2str):
+        return who + "two-stream optical properties required (OpticalProps2str; an OpticalProps1scl has nothing to rescale)"
+    if _is_f32(optical_props.tau):
+        return who + "implemented for float64 arrays"
+    if isinstance(fluxes, FluxesByband):
+        return who + "per-band fluxes are not implemented (broadband fluxes only)"
+    if flux_up_jac is None:
+        return who + "flux_up_jac is required"
+    if getattr(sources, "sfc_source_jac", None) is None:
+        return who + "flux_up_jac needs sources.sfc_source_jac (planck_sfc_source_jac)"
+    ng, nlay, ncol = optical_props.tau.shape
+    b2g = np.ascontiguousarray(optical_props.band2gpt, dtype=np.int32)
+    nband = b2g.shape[0]
+    try:
+        space = _space_of([optical_props.tau, optical_props.ssa, optical_props.g, sources.lay_source, sources.lev_source_inc,
+                           sources.lev_source_dec, sources.sfc_source, sources.sfc_source_jac, sfc_emis, inc_flux, fluxes.flux_up,
+                           fluxes.flux_dn, flux_up_jac])
+        a3 = [_ptr(a, (ng, nlay, ncol), w) for a, w in ((optical_props.tau, "tau"), (optical_props.ssa, "ssa"), (optical_props.g, "g"),
+                                                        (sources.lay_source, "lay_source"),
+                                                        (sources.lev_source_inc, "lev_source_inc"),
+                                                        (sources.lev_source_dec, "lev_source_dec"))]
+        a2 = [_ptr(sources.sfc_source, (ng, ncol), "sfc_source"), _ptr(sources.sfc_source_jac, (ng, ncol), "sfc_source_jac")]
+        rest = [_ptr(sfc_emis, (ncol, nband), "sfc_emis"), _ptr(inc_flux, (ng, ncol), "inc_flux"),
+                _ptr(fluxes.flux_up, (nlay + 1, ncol), "flux_up"), _ptr(fluxes.flux_dn, (nlay + 1, ncol), "flux_dn"),
+                _ptr(flux_up_jac, (nlay + 1, ncol), "flux_up_jac")]
+    except (TypeError, ValueError) as e:
+        return str(e)
+    dev = _device_of(optical_props.tau) if device is None else device
+    rc = lib().ecckd_rte_lw_rescaled_jac(int(dev), ncol, nlay, ng, int(bool(top_at_1)), int(n_gauss_angles), *a3, *a2, nband,
+                                         C.c_void_p(b2g.ctypes.data), *rest, space, _stream(space))
     return last_error() if rc else ""
 
 
@@ -1363,8 +1457,9 @@ def rte_lw(optical_props, top_at_1, sources, sfc_emis, fluxes, n_gauss_angles=1,
     keyword: ``flux_up_jac`` stays the last parameter (tests/test_lw_jac_host.py pins that), so ``use_2stream`` sits before it.
     ``rescaled=True`` (``ecckd_rte_lw_rescaled``; by keyword): the rescaled no-scattering solver, which RTE-RRTMGP's rte_lw runs
     on two-stream properties without ``use_2stream`` -- an ``OpticalProps2str`` (float64), ``n_gauss_angles`` 1..4, broadband
-    fluxes, ``inc_flux`` accepted; ``use_2stream=True``, ``flux_up_jac``, ``FluxesByband``, ``shared_levels``, float32 and an
-    ``OpticalProps1scl`` are refused with a message.  Parity with RTE-RRTMGP is unpinned."""
+    fluxes, ``inc_flux`` accepted; ``use_2stream=True``, ``flux_up_jac`` (``rte_lw_rescaled_jac`` returns it), ``FluxesByband``,
+    ``shared_levels``, float32 and an ``OpticalProps1scl`` are refused with a message.  Parity with RTE-RRTMGP is unpinned
+    (DESIGN.md section 3)."""
     if rescaled:
         return _rte_lw_rescaled(optical_props, top_at_1, sources, sfc_emis, fluxes, n_gauss_angles, device, shared_levels,
                                 inc_flux, use_2stream, flux_up_jac)

@@ -1812,11 +1812,13 @@ struct ClearFluxes { double *up, *dn, *dir; };
 // `pt` (60-layer route only): the band planes the solver adds to tau as it reads it; the general route gets a tau that
 // launch_increment has incremented already
 // `jac_inline` (60-layer route, without `both`): the Jacobian form of the kernel, which stores flux_up_jac there as well
+// `sources` (general route only; ecckd_lw_fluxes_rescaled_jac): the Planck sources are there already, wherever the caller
+// keeps them, and `scratch` is the solver's ring alone
 static int rte_lw_fused_dev(const ecckd_model *m, int ncol, int nlay, int top_at_1, int n_gauss_angles, const double *tau,
                             const double *tlay, const double *tlev, const double *tsfc, const double *sfc_emis,
                             const double *inc_flux, double *flux_up, double *flux_dn, double *scratch, hipStream_t stream,
                             const LwParticles *pt = nullptr, const ClearFluxes *both = nullptr, bool sources_in_scratch = false,
-                            double *jac_inline = nullptr) {
+                            double *jac_inline = nullptr, const PlanckSide *sources = nullptr) {
   ecckd::RteLwArgs a{};
   if (fill_band_map(m->ng, m->nband, m->band2gpt.data(), a.gpt2band)) return 1;
   a.ncol = ncol; a.nlay = nlay; a.ng = m->ng; a.top_at_1 = top_at_1 ? 1 : 0;
@@ -1834,11 +1836,17 @@ static int rte_lw_fused_dev(const ecckd_model *m, int ncol, int nlay, int top_at
   }
   if (both || jac_inline) return fail("ecckd: internal: the dual-sky and the Jacobian longwave kernels serve 60 layers only");
   // general route (any layer count): sources through scratch, one value per level
-  if (!scratch) return fail("ecckd: internal: the fused longwave solver needs scratch for this layer count");
+  if (!scratch && !(sources && !ecckd::rte_lw_scratch_bytes(ncol, nlay, m->ng)))
+    return fail("ecckd: internal: the fused longwave solver needs scratch for this layer count");
   const size_t n3 = (size_t)ncol * nlay * m->ng;
-  double *lay = scratch, *inc = lay + n3, *dec = inc + n3, *sfc = dec + n3, *ring = sfc + (((size_t)ncol * m->ng + 31) & ~(size_t)31);
-  ecckd::PlanckArgs p = planck_args(m, ncol, nlay, tlay, PlanckSide{tlev, tsfc, lay, inc, dec, sfc});
-  if (!sources_in_scratch) {   // (the all-sky pass of ecckd_lw_fluxes_clear_allsky finds the clear pass's sources there)
+  double *lay, *inc, *dec, *sfc, *ring;
+  if (sources) {
+    lay = sources->lay_source; inc = sources->lev_inc; dec = sources->lev_dec; sfc = sources->sfc_source; ring = scratch;
+  } else {
+    lay = scratch; inc = lay + n3; dec = inc + n3; sfc = dec + n3; ring = sfc + (((size_t)ncol * m->ng + 31) & ~(size_t)31);
+  }
+  if (!sources && !sources_in_scratch) {   // (the all-sky pass of ecckd_lw_fluxes_clear_allsky finds the clear pass's sources there)
+    ecckd::PlanckArgs p = planck_args(m, ncol, nlay, tlay, PlanckSide{tlev, tsfc, lay, inc, dec, sfc});
     ProfScope prof("planck", stream);
     HIPCHK(ecckd::launch_planck(p, stream));
   }
@@ -2201,11 +2209,33 @@ static int lw_rescaled_dev(const ecckd::RteLwArgs &a, double *spec, hipStream_t 
   return 0;
 }
 
-int ecckd_rte_lw_rescaled(int device, int ncol, int nlay, int ngpt, int top_at_1, int n_gauss_angles, const double *tau,
-                          const double *ssa, const double *g, const double *lay_source, const double *lev_source_inc,
-                          const double *lev_source_dec, const double *sfc_source, int nband, const int *band2gpt,
-                          const double *sfc_emis, const double *inc_flux, double *flux_up, double *flux_dn, int memspace,
-                          void *stream) {
+// ecckd_rte_lw_rescaled_jac: the surface term and where the Jacobian goes, in the memory space of the call
+struct RescJac { const double *sfc_source_jac; double *flux_up_jac; };
+
+// The rescaled Jacobian on the cell's (tau, ssa, g) on the device, behind the flux pass: the stand-alone kernel.  The surface
+// term is sfc_source_jac(ncol,ng), or -- null -- formed from tsfc and the model's Planck table.
+static int lw_rescaled_jac_dev(const ecckd::RteLwArgs &a, const double *sfc_source_jac, const ecckd_model *m, const double *tsfc,
+                               double *jac, hipStream_t stream) {
+  ecckd::RteLwRescJacArgs j{};
+  std::memcpy(j.gpt2band, a.gpt2band, sizeof j.gpt2band);
+  j.ncol = a.ncol; j.nlay = a.nlay; j.ng = a.ng; j.top_at_1 = a.top_at_1; j.nmus = a.nmus; j.nband = a.nband;
+  for (int k = 0; k < a.nmus; ++k) { j.Ds[k] = a.Ds[k]; j.wts[k] = a.wts[k]; }
+  j.tau = a.tau; j.ssa = a.ssa; j.g = a.g; j.part_tau = a.part_tau; j.part_ssa = a.part_ssa; j.part_g = a.part_g; j.part_mask = a.part_mask;
+  j.sfc_source_jac = sfc_source_jac; j.tsfc = tsfc; j.sfc_emis = a.sfc_emis; j.flux_up_jac = jac;
+  ProfScope prof("rte_lw_rescaled_jac", stream);
+  if (m)
+    HIPCHK(ecckd::launch_rte_lw_rescaled_jac(j, m->dbuf + m->off_planck, m->ntp, m->temperature_planck[0],
+                                             m->temperature_planck[1] - m->temperature_planck[0], stream));
+  else
+    HIPCHK(ecckd::launch_rte_lw_rescaled_jac(j, nullptr, 0, 0., 1., stream));
+  return 0;
+}
+
+static int rte_lw_rescaled_impl(int device, int ncol, int nlay, int ngpt, int top_at_1, int n_gauss_angles, const double *tau,
+                                const double *ssa, const double *g, const double *lay_source, const double *lev_source_inc,
+                                const double *lev_source_dec, const double *sfc_source, int nband, const int *band2gpt,
+                                const double *sfc_emis, const double *inc_flux, double *flux_up, double *flux_dn, int memspace,
+                                void *stream, const RescJac *jx = nullptr) {
   if (check_dims(ncol, nlay)) return 1;
   if (n_gauss_angles < 1 || n_gauss_angles > 4) return fail("rte_lw: have to ask for at least one quadrature point and no more than 4");
   if (!tau || !ssa || !g || !lay_source || !lev_source_inc || !lev_source_dec || !sfc_source || !sfc_emis || !flux_up || !flux_dn)
@@ -2214,6 +2244,12 @@ int ecckd_rte_lw_rescaled(int device, int ncol, int nlay, int ngpt, int top_at_1
   if (fill_band_map(ngpt, nband, band2gpt, a.gpt2band)) return 1;
   if (memspace == ECCKD_MIXED) return fail("ecckd_rte_lw_rescaled: ECCKD_MIXED is not implemented (ECCKD_DEVICE or ECCKD_HOST)");
   if (memspace != ECCKD_DEVICE && memspace != ECCKD_HOST) return fail("ecckd: bad memspace");
+  if (jx) {   // this call's own refusals, behind those of ecckd_rte_lw_rescaled that need no device
+    if (!jx->sfc_source_jac || !jx->flux_up_jac)
+      return fail("ecckd_rte_lw_rescaled_jac: null argument (sfc_source_jac and flux_up_jac are required)");
+    if (jx->flux_up_jac == flux_up || jx->flux_up_jac == flux_dn)
+      return fail("ecckd_rte_lw_rescaled_jac: flux_up_jac must not be one of the flux outputs");
+  }
   if (check_device(device)) return 1;
   if (ncol == 0) return 0;
   a.ncol = ncol; a.nlay = nlay; a.ng = ngpt; a.top_at_1 = top_at_1 ? 1 : 0; a.nband = nband;
@@ -2224,16 +2260,40 @@ int ecckd_rte_lw_rescaled(int device, int ncol, int nlay, int ngpt, int top_at_1
   void *sp = nullptr;
   const size_t scratch = ecckd_rte_lw_rescaled_scratch_bytes(ncol, nlay, ngpt);
   if (scratch && stream_scratch(device, st.stream, scratch, &sp, lease)) return 1;
+  const double *d_sjac = nullptr;
+  double *d_jac = nullptr;
   if (st.open([&] {
         a.tau = st.in(tau, n.lay_g); a.ssa = st.in(ssa, n.lay_g); a.g = st.in(g, n.lay_g);
         a.lay_source = st.in(lay_source, n.lay_g); a.lev_source_inc = st.in(lev_source_inc, n.lay_g);
         a.lev_source_dec = st.in(lev_source_dec, n.lay_g); a.sfc_source = st.in(sfc_source, n.col_g);
         a.sfc_emis = st.in(sfc_emis, n.col_b); a.inc_flux = st.in(inc_flux, n.col_g);
         a.flux_up = st.out(flux_up, n.lev); a.flux_dn = st.out(flux_dn, n.lev);
+        if (jx) { d_sjac = st.in(jx->sfc_source_jac, n.col_g); d_jac = st.out(jx->flux_up_jac, n.lev); }
       }))
     return 1;
   if (lw_rescaled_dev(a, static_cast<double *>(sp), st.stream)) return 1;
+  if (jx && lw_rescaled_jac_dev(a, d_sjac, nullptr, nullptr, d_jac, st.stream)) return 1;
   return st.close();
+}
+
+int ecckd_rte_lw_rescaled(int device, int ncol, int nlay, int ngpt, int top_at_1, int n_gauss_angles, const double *tau,
+                          const double *ssa, const double *g, const double *lay_source, const double *lev_source_inc,
+                          const double *lev_source_dec, const double *sfc_source, int nband, const int *band2gpt,
+                          const double *sfc_emis, const double *inc_flux, double *flux_up, double *flux_dn, int memspace,
+                          void *stream) {
+  return rte_lw_rescaled_impl(device, ncol, nlay, ngpt, top_at_1, n_gauss_angles, tau, ssa, g, lay_source, lev_source_inc,
+                              lev_source_dec, sfc_source, nband, band2gpt, sfc_emis, inc_flux, flux_up, flux_dn, memspace, stream);
+}
+
+int ecckd_rte_lw_rescaled_jac(int device, int ncol, int nlay, int ngpt, int top_at_1, int n_gauss_angles, const double *tau,
+                              const double *ssa, const double *g, const double *lay_source, const double *lev_source_inc,
+                              const double *lev_source_dec, const double *sfc_source, const double *sfc_source_jac, int nband,
+                              const int *band2gpt, const double *sfc_emis, const double *inc_flux, double *flux_up,
+                              double *flux_dn, double *flux_up_jac, int memspace, void *stream) {
+  const RescJac jx{sfc_source_jac, flux_up_jac};
+  return rte_lw_rescaled_impl(device, ncol, nlay, ngpt, top_at_1, n_gauss_angles, tau, ssa, g, lay_source, lev_source_inc,
+                              lev_source_dec, sfc_source, nband, band2gpt, sfc_emis, inc_flux, flux_up, flux_dn, memspace, stream,
+                              &jx);
 }
 
 int ecckd_lw_solver_1rescl_gpt(int device, int ncol, int nlay, int ngpt, int top_at_1, int nmus, const double *Ds,
@@ -2292,13 +2352,32 @@ size_t ecckd_lw_fluxes_allsky_rescaled_scratch_bytes(const ecckd_model_t *m, int
   return sizeof(double) * allsky_rescaled_doubles(m, ncol, nlay);
 }
 
-int ecckd_lw_fluxes_allsky_rescaled(const ecckd_model_t *m, int ncol, int nlay, const double *plev, const double *tlay,
-                                    const double *tsfc, const double *tlev, int ngas, const char *gas_names,
-                                    const double *const *vmr, const long long *vmr_col_stride, const long long *vmr_lay_stride,
-                                    const double *vmr_scalar, int top_at_1, int n_gauss_angles, const double *sfc_emis,
-                                    const double *inc_flux, int nband_p, const double *tau_p, const double *ssa_p,
-                                    const double *g_p, const unsigned long long *cloud_mask, double *flux_up, double *flux_dn,
-                                    int memspace, void *stream) {
+// ecckd_lw_fluxes_rescaled_jac: the optional outputs behind flux_dn, in the memory space of the call (each may be null)
+struct RescExtras { double *up_clear, *dn_clear, *jac; };
+
+// The work block with clear-sky outputs: behind the block of ecckd_lw_fluxes_allsky_rescaled, what the clear pass needs on
+// its general route -- at 60 layers its sources and ring (nothing where the clear-sky layer-split kernel serves the model),
+// otherwise the ring alone (the sources are the rescaled route's)
+static size_t allsky_rescaled_jac_doubles(const ecckd_model *m, int ncol, int nlay, bool with_clear) {
+  const size_t n = allsky_rescaled_doubles(m, ncol, nlay);
+  if (!with_clear) return n;
+  if (resc_fused_kernel_applies(m, nlay)) return n + r32(fused_scratch_doubles(m, ncol, nlay));
+  return n + r32(ecckd::rte_lw_scratch_bytes(ncol, nlay, m->ng) / sizeof(double));
+}
+
+size_t ecckd_lw_fluxes_rescaled_jac_scratch_bytes(const ecckd_model_t *m, int ncol, int nlay, int with_clear) {
+  if (!m || ncol <= 0 || nlay < 1) return 0;
+  return sizeof(double) * allsky_rescaled_jac_doubles(m, ncol, nlay, with_clear != 0);
+}
+
+static int lw_fluxes_allsky_rescaled_impl(const ecckd_model_t *m, int ncol, int nlay, const double *plev, const double *tlay,
+                                          const double *tsfc, const double *tlev, int ngas, const char *gas_names,
+                                          const double *const *vmr, const long long *vmr_col_stride,
+                                          const long long *vmr_lay_stride, const double *vmr_scalar, int top_at_1,
+                                          int n_gauss_angles, const double *sfc_emis, const double *inc_flux, int nband_p,
+                                          const double *tau_p, const double *ssa_p, const double *g_p,
+                                          const unsigned long long *cloud_mask, double *flux_up, double *flux_dn, int memspace,
+                                          void *stream, const RescExtras &x) {
   if (!m) return fail("ecckd: null model");
   if (cloud_mask && m->ng > 64) return fail("ecckd_lw_fluxes_allsky_rescaled" + std::string(kMaskTooWide) + std::to_string(m->ng));
   if (nband_p != m->nband)
@@ -2310,6 +2389,14 @@ int ecckd_lw_fluxes_allsky_rescaled(const ecckd_model_t *m, int ncol, int nlay, 
   if (!m->has_planck) return fail("ecckd_lw_fluxes_allsky_rescaled: model has no Planck table (shortwave model?)");
   if (!tlev) return fail("tlev is required for ecckd");
   if (n_gauss_angles < 1 || n_gauss_angles > 4) return fail("rte_lw: have to ask for at least one quadrature point and no more than 4");
+  // ecckd_lw_fluxes_rescaled_jac's own, behind the refusals above (which a host-only model answers too) and before the model
+  // is asked for its device
+  if ((x.up_clear != nullptr) != (x.dn_clear != nullptr))
+    return fail("ecckd_lw_fluxes_rescaled_jac: null argument (flux_up_clear and flux_dn_clear are given together or not at all)");
+  if (x.up_clear && (x.up_clear == flux_up || x.up_clear == flux_dn || x.dn_clear == flux_up || x.dn_clear == flux_dn))
+    return fail("ecckd_lw_fluxes_rescaled_jac: a clear-sky output must not be an all-sky output (the two sets of fluxes need arrays of their own)");
+  if (x.jac && (x.jac == flux_up || x.jac == flux_dn || x.jac == x.up_clear || x.jac == x.dn_clear))
+    return fail("ecckd_lw_fluxes_rescaled_jac: flux_up_jac must not be another output (it needs an array of its own)");
   if (check_model(m) || check_gas_optics_dims(ncol, nlay)) return 1;
   if (!plev || !tlay || !tsfc || !sfc_emis || !flux_up || !flux_dn || (ngas > 0 && !gas_names))
     return fail("ecckd_lw_fluxes_allsky_rescaled: null argument");
@@ -2318,11 +2405,16 @@ int ecckd_lw_fluxes_allsky_rescaled(const ecckd_model_t *m, int ncol, int nlay, 
   if (ncol == 0) return 0;
   const GasDesc gd{ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar};
   const Counts n(ncol, nlay, m->ng, m->nband);
+  const bool with_clear = x.up_clear != nullptr;
+  const bool resc_fused = resc_fused_kernel_applies(m, nlay);
+  // the Jacobian inside the 60-layer flux kernel ("lw_jac_inline" = 1, and its third accumulator plane fits next to the
+  // model's Planck table), or from the stand-alone kernel behind the flux pass
+  const bool jac_in = x.jac && resc_fused && g_opt.lw_jac_inline.load() == 1 && ecckd::rte_lw_rescaled_planck_fits(m->ng, m->ntp, true);
   Stage st(const_cast<ecckd_model *>(m), memspace, stream, false);
   const double *d_plev = nullptr, *d_tlay = nullptr, *d_tsfc = nullptr, *d_tlev = nullptr;
   LwParticles d_pt{};
   const double *q_g = nullptr;
-  double *work = nullptr;
+  double *work = nullptr, *d_upc = nullptr, *d_dnc = nullptr, *d_jac = nullptr;
   GasDesc d_gd{};
   ecckd::RteLwArgs a{};
   if (fill_band_map(m->ng, m->nband, m->band2gpt.data(), a.gpt2band)) return 1;
@@ -2335,18 +2427,29 @@ int ecckd_lw_fluxes_allsky_rescaled(const ecckd_model_t *m, int ncol, int nlay, 
         d_pt = LwParticles{st.in(tau_p, n.lay_b), st.in(ssa_p, n.lay_b), st.in(cloud_mask, n.lay)};
         q_g = st.in(g_p, n.lay_b);
         a.flux_up = st.out(flux_up, n.lev); a.flux_dn = st.out(flux_dn, n.lev);
-        work = st.work(allsky_rescaled_doubles(m, ncol, nlay) * sizeof(double));
+        d_upc = st.out(x.up_clear, n.lev); d_dnc = st.out(x.dn_clear, n.lev); d_jac = st.out(x.jac, n.lev);
+        work = st.work(allsky_rescaled_jac_doubles(m, ncol, nlay, with_clear) * sizeof(double));
       }))
     return 1;
   const hipStream_t s = st.stream;
   if (gas_optical_depth_dev(m, false, nullptr, ncol, nlay, d_plev, d_tlay, d_gd, work, false, nullptr, nullptr, nullptr, nullptr, s))
     return 1;
   a.tau = work;
-  if (resc_fused_kernel_applies(m, nlay)) {   // the band triple and the mask ride into the solver
+  double *const clear_extra = work + allsky_rescaled_doubles(m, ncol, nlay);   // (with_clear: what the clear pass needs)
+  if (resc_fused) {   // the band triple and the mask ride into the solver
+    // the clear sky first, from the gas optical depth as it stands: the launch of ecckd_lw_fluxes
+    if (with_clear && rte_lw_fused_dev(m, ncol, nlay, top_at_1, n_gauss_angles, work, d_tlay, d_tlev, d_tsfc, a.sfc_emis, a.inc_flux,
+                                       d_upc, d_dnc, fused_scratch_doubles(m, ncol, nlay) ? clear_extra : nullptr, s))
+      return 1;
     a.part_tau = d_pt.tau; a.part_ssa = d_pt.ssa; a.part_g = q_g; a.part_mask = d_pt.mask;
-    ProfScope prof("rte_lw_rescaled_allsky", s);
-    HIPCHK(ecckd::launch_rte_lw_rescaled_planck(a, m->dbuf + m->off_planck, m->ntp, m->temperature_planck[0],
-                                                m->temperature_planck[1] - m->temperature_planck[0], d_tlay, d_tlev, d_tsfc, s));
+    {
+      ProfScope prof("rte_lw_rescaled_allsky", s);
+      HIPCHK(ecckd::launch_rte_lw_rescaled_planck(a, m->dbuf + m->off_planck, m->ntp, m->temperature_planck[0],
+                                                  m->temperature_planck[1] - m->temperature_planck[0], d_tlay, d_tlev, d_tsfc, s,
+                                                  jac_in ? d_jac : nullptr));
+    }
+    // (scratch still holds the gas optical depth: the stand-alone kernel forms the cell's triple as the flux kernel did)
+    if (x.jac && !jac_in && lw_rescaled_jac_dev(a, nullptr, m, d_tsfc, d_jac, s)) return 1;
     return st.close();
   }
   // any other layer count (slow): Planck sources and the by-band increment on (tau, 0, 0) through scratch, then the
@@ -2354,12 +2457,45 @@ int ecckd_lw_fluxes_allsky_rescaled(const ecckd_model_t *m, int ncol, int nlay, 
   const size_t n3 = r32(n.lay_g);
   double *ssa = work + n3, *g = ssa + n3, *lay = g + n3, *inc = lay + n3, *dec = inc + n3, *sfc = dec + n3;
   double *spec = sfc + r32((size_t)ncol * m->ng);
-  if (planck_sources_dev(m, ncol, nlay, d_tlay, PlanckSide{d_tlev, d_tsfc, lay, inc, dec, sfc}, s)) return 1;
+  const PlanckSide src{d_tlev, d_tsfc, lay, inc, dec, sfc};
+  if (planck_sources_dev(m, ncol, nlay, d_tlay, src, s)) return 1;
+  // the clear sky before the by-band increment: the general route of ecckd_lw_fluxes on these sources
+  if (with_clear && rte_lw_fused_dev(m, ncol, nlay, top_at_1, n_gauss_angles, work, d_tlay, d_tlev, d_tsfc, a.sfc_emis, a.inc_flux, d_upc,
+                                     d_dnc, ecckd::rte_lw_scratch_bytes(ncol, nlay, m->ng) ? clear_extra : nullptr, s, nullptr, nullptr,
+                                     false, nullptr, &src))
+    return 1;
   HIPCHK(hipMemsetAsync(ssa, 0, 2 * n3 * sizeof(double), s));
   if (lw_increment_dev(m, ncol, nlay, work, d_pt, s, ssa, g, q_g)) return 1;
   a.ssa = ssa; a.g = g; a.lay_source = lay; a.lev_source_inc = inc; a.lev_source_dec = dec; a.sfc_source = sfc;
   if (lw_rescaled_dev(a, spec, s)) return 1;
+  // on the (tau, ssa, g) the increment left in scratch
+  if (x.jac && lw_rescaled_jac_dev(a, nullptr, m, d_tsfc, d_jac, s)) return 1;
   return st.close();
+}
+
+int ecckd_lw_fluxes_allsky_rescaled(const ecckd_model_t *m, int ncol, int nlay, const double *plev, const double *tlay,
+                                    const double *tsfc, const double *tlev, int ngas, const char *gas_names,
+                                    const double *const *vmr, const long long *vmr_col_stride, const long long *vmr_lay_stride,
+                                    const double *vmr_scalar, int top_at_1, int n_gauss_angles, const double *sfc_emis,
+                                    const double *inc_flux, int nband_p, const double *tau_p, const double *ssa_p,
+                                    const double *g_p, const unsigned long long *cloud_mask, double *flux_up, double *flux_dn,
+                                    int memspace, void *stream) {
+  return lw_fluxes_allsky_rescaled_impl(m, ncol, nlay, plev, tlay, tsfc, tlev, ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride,
+                                        vmr_scalar, top_at_1, n_gauss_angles, sfc_emis, inc_flux, nband_p, tau_p, ssa_p, g_p,
+                                        cloud_mask, flux_up, flux_dn, memspace, stream, RescExtras{nullptr, nullptr, nullptr});
+}
+
+int ecckd_lw_fluxes_rescaled_jac(const ecckd_model_t *m, int ncol, int nlay, const double *plev, const double *tlay,
+                                 const double *tsfc, const double *tlev, int ngas, const char *gas_names,
+                                 const double *const *vmr, const long long *vmr_col_stride, const long long *vmr_lay_stride,
+                                 const double *vmr_scalar, int top_at_1, int n_gauss_angles, const double *sfc_emis,
+                                 const double *inc_flux, int nband_p, const double *tau_p, const double *ssa_p,
+                                 const double *g_p, const unsigned long long *cloud_mask, double *flux_up, double *flux_dn,
+                                 double *flux_up_clear, double *flux_dn_clear, double *flux_up_jac, int memspace, void *stream) {
+  return lw_fluxes_allsky_rescaled_impl(m, ncol, nlay, plev, tlay, tsfc, tlev, ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride,
+                                        vmr_scalar, top_at_1, n_gauss_angles, sfc_emis, inc_flux, nband_p, tau_p, ssa_p, g_p,
+                                        cloud_mask, flux_up, flux_dn, memspace, stream,
+                                        RescExtras{flux_up_clear, flux_dn_clear, flux_up_jac});
 }
 
 // The superset of the four fused longwave calls, with flux_up_jac of the sky that flux_up holds (include/ecckd_hip.h)

@@ -158,6 +158,13 @@ struct RteLwJacArgs {
   int lev_chunk = 0;           // (set by the launcher) levels whose accumulators one block holds in LDS
 };
 hipError_t launch_rte_lw_jac(const RteLwJacArgs &a, const double *planck, int ntp, double t0, double dt, hipStream_t s);
+// ... of the rescaled solver (include/ecckd_hip.h, "Rescaled longwave: clear sky and Jacobian"): ssa / g (ncol,nlay,ng) beside
+// tau, or part_g beside part_tau / part_ssa (tau is the gas optical depth; part_mask optional) -- the transmissivity is that
+// of tau * ((1 - ssa) + (ssa * (1 - g)) * 0.5).  An argument block of its own: the kernels above keep theirs.
+struct RteLwRescJacArgs : RteLwJacArgs {
+  const double *ssa = nullptr, *g = nullptr, *part_g = nullptr;
+};
+hipError_t launch_rte_lw_rescaled_jac(const RteLwRescJacArgs &a, const double *planck, int ntp, double t0, double dt, hipStream_t s);
 // sfc_source_jac(ncol,ng) = B(tsfc + 1) - B(tsfc) from the model's table planck(ng,ntp)
 hipError_t launch_planck_sfc_jac(const double *planck, int ng, int ntp, double t0, double dt, int ncol, const double *tsfc,
                                  double *sfc_source_jac, hipStream_t s);
@@ -335,9 +342,12 @@ hipError_t launch_rte_lw_planck(const RteLwArgs &a, const double *planck, int nt
 hipError_t launch_rte_lw_rescaled_split(const RteLwArgs &a, hipStream_t s);
 // ... or the Planck-recomputing form: a.tau is the gas optical depth and the cell's (tau, ssa, g) is formed from the band
 // triple a.part_tau / part_ssa / part_g (and a.part_mask) with the operations of the by-band increment_2stream_by_2stream
-bool rte_lw_rescaled_planck_fits(int ng, int ntp);
+// flux_up_jac (ncol,nlay+1), or null: the Jacobian form, which stores the surface-temperature Jacobian of flux_up as well
+// (rte_lw_rescaled_planck_fits(..., true): its third accumulator plane fits too)
+bool rte_lw_rescaled_planck_fits(int ng, int ntp, bool jac = false);
 hipError_t launch_rte_lw_rescaled_planck(const RteLwArgs &a, const double *planck, int ntp, double t0, double dt,
-                                         const double *tlay, const double *tlev, const double *tsfc, hipStream_t s);
+                                         const double *tlay, const double *tlev, const double *tsfc, hipStream_t s,
+                                         double *flux_up_jac = nullptr);
 hipError_t launch_rte_sw(const RteSwArgs &a, hipStream_t s);
 // layer-systolic shortwave solver (kernels_rte_sw_sys.hip): any precision, nlay <= 60
 bool rte_sw_sys_applies(const RteSwArgs &a);

@@ -21,6 +21,13 @@
 // SKY / MASK: the particulate optical depth on the model's bands and the McICA mask, applied to the gas optical depth with
 // the expressions of rte_lw_split_body operation by operation (the 60-layer fused route, whose flux kernel leaves the
 // scratch tau as gas optics wrote it).
+// RESC: the rescaled solver's Jacobian (include/ecckd_hip.h, "Rescaled longwave: clear sky and Jacobian").  With every source
+// zero the rescaled transport is J = t_k * J with t_k = lw_exp(-((tau * sc) * D_k)), sc = (1 - ssa) + (ssa * (1 - g)) * 0.5,
+// formed with the expressions of the RESC branch of rte_lw_split_body on the cell's (tau, ssa, g).  Two forms: arrays (SKY =
+// 0: a.ssa and a.g beside a.tau, 24 B per cell -- ecckd_rte_lw_rescaled_jac and the fused general route, whose increment
+// left the cell's triple in scratch), and SKY = 2 with a.part_g and the optional mask (the 60-layer fused route: the cell's
+// triple from the gas optical depth and the band triple with the operations of increment_body<double,true,true,true,MASK>,
+// its two IEEE divisions included).
 #include "kernels.hpp"
 #include "lw_layer.hpp"
 #include "planck_at.hpp"
@@ -32,9 +39,11 @@ constexpr int kJacCW = 32;   // columns per tile
 constexpr int kJacGW = 2;    // g-points per wave
 constexpr int kJacPF = 4;    // layers in flight per lane
 
-template <bool PLANCK, int SKY, bool MASK>
-__global__ void __launch_bounds__(64) rte_lw_jac_kernel(const RteLwJacArgs a, const PlanckTab pt) {
+// The kernel text, shared by rte_lw_jac_kernel (RESC = false) and rte_lw_rescaled_jac_kernel (RESC = true)
+template <bool PLANCK, int SKY, bool MASK, bool RESC, class Args>
+__device__ __forceinline__ void rte_lw_jac_body(const Args &a, const PlanckTab &pt) {
   static_assert(SKY != 0 || !MASK, "a cloud mask belongs to the all-sky form");
+  static_assert(!RESC || SKY == 0 || SKY == 2, "the rescaled form reads the cell's (tau, ssa, g) or forms it from a two-stream band triple");
   constexpr int CW = kJacCW, GW = kJacGW, PF = kJacPF;
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
   double *acc = reinterpret_cast<double *>(lds_raw);   // [levels of a chunk][CW]
@@ -99,12 +108,21 @@ __global__ void __launch_bounds__(64) rte_lw_jac_kernel(const RteLwJacArgs a, co
         double ptau[PF];
         [[maybe_unused]] double ppt[SKY ? PF : 1], pps[SKY == 2 ? PF : 1];
         [[maybe_unused]] unsigned long long pmk[MASK ? PF : 1];
+        [[maybe_unused]] double pss[RESC && SKY == 0 ? PF : 1], pgg[RESC ? PF : 1];   // RESC: ssa(l) of the cell; g(l) of the cell or of the band
         int issued = 0;
         auto issue = [&](int slot) {
           ptau[slot] = __builtin_nontemporal_load(a.tau + qn);
           if (SKY) ppt[slot] = a.part_tau[q2 + qb];
           if (SKY == 2) pps[slot] = a.part_ssa[q2 + qb];
           if (MASK) pmk[slot] = a.part_mask[q2];
+          if constexpr (RESC) {
+            if constexpr (SKY == 0) {
+              pss[slot] = __builtin_nontemporal_load(a.ssa + qn);
+              pgg[slot] = __builtin_nontemporal_load(a.g + qn);
+            } else {
+              pgg[slot] = a.part_g[q2 + qb];
+            }
+          }
           ++issued;
           if (issued < nlay) { qn += qstep; q2 += qstep; }
         };
@@ -122,8 +140,30 @@ __global__ void __launch_bounds__(64) rte_lw_jac_kernel(const RteLwJacArgs a, co
               [[maybe_unused]] double tp = 0.;
               if (SKY) tp = ppt[u];
               if (MASK) tp = (pmk[u] >> gg) & 1ull ? tp : 0.;
+              if constexpr (!RESC) {
               if (SKY == 1) tau = tau + tp;
               if (SKY == 2) tau = tau + tp * (1. - pps[u]);
+              } else {
+                double cssa, cg;
+                if constexpr (SKY == 2) {
+                  // increment_body<double, true, true, true, MASK> of kernels_optical_props.hip on op1 = (tau_gas, +0, +0)
+                  constexpr double tiny3 = op_eps<double>();
+                  const double tscat2 = tp * pps[u];
+                  const double tsg2 = tscat2 * pgg[u];
+                  const double tau12 = tau + tp;
+                  const double tscat1 = tau * 0.;
+                  const double tauscat12 = tscat1 + tscat2;
+                  cg = (tscat1 * 0. + tsg2) / (tauscat12 > tiny3 ? tauscat12 : tiny3);
+                  cssa = tauscat12 / (tau12 > tiny3 ? tau12 : tiny3);
+                  tau = tau12;
+                } else {
+                  cssa = pss[u];
+                  cg = pgg[u];
+                }
+                const double wb = cssa * (1. - cg) * 0.5;
+                const double sc = (1. - cssa) + wb;
+                tau = tau * sc;
+              }
               issue(u);
 #pragma unroll
               for (int k = 0; k < 4; ++k) {
@@ -150,6 +190,18 @@ __global__ void __launch_bounds__(64) rte_lw_jac_kernel(const RteLwJacArgs a, co
   }
 }
 
+template <bool PLANCK, int SKY, bool MASK>
+__global__ void __launch_bounds__(64) rte_lw_jac_kernel(const RteLwJacArgs a, const PlanckTab pt) {
+  rte_lw_jac_body<PLANCK, SKY, MASK, false>(a, pt);
+}
+
+// ... of the rescaled solver, under its own name: SKY = 0 on arrays (tau, ssa, g), SKY = 2 on the gas optical depth and the
+// two-stream band triple (MASK: and a McICA cloud mask)
+template <bool PLANCK, int SKY, bool MASK>
+__global__ void __launch_bounds__(64) rte_lw_rescaled_jac_kernel(const RteLwRescJacArgs a, const PlanckTab pt) {
+  rte_lw_jac_body<PLANCK, SKY, MASK, true>(a, pt);
+}
+
 // sfc_source_jac(i,g) = B_g(tsfc(i) + 1) - B_g(tsfc(i)): one thread per (column, g-point), the table from global memory
 __global__ void __launch_bounds__(256) planck_sfc_jac_kernel(const PlanckTab pt, int ncol, const double *tsfc, double *out) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
@@ -163,6 +215,17 @@ __global__ void __launch_bounds__(256) planck_sfc_jac_kernel(const PlanckTab pt,
   out[i] = b1 - b0;
 }
 
+template <class Args>
+hipError_t launch_jac_kernel(void (*k)(const Args, const PlanckTab), const Args &a, const PlanckTab &pt, hipStream_t s);
+
+template <bool PLANCK>
+hipError_t launch_resc_jac(const RteLwRescJacArgs &a, const PlanckTab &pt, hipStream_t s) {
+  void (*k)(const RteLwRescJacArgs, const PlanckTab);
+  if (a.ssa) k = rte_lw_rescaled_jac_kernel<PLANCK, 0, false>;   // on the cell's (tau, ssa, g)
+  else k = a.part_mask ? rte_lw_rescaled_jac_kernel<PLANCK, 2, true> : rte_lw_rescaled_jac_kernel<PLANCK, 2, false>;
+  return launch_jac_kernel(k, a, pt, s);
+}
+
 template <bool PLANCK>
 hipError_t launch_jac(const RteLwJacArgs &a, const PlanckTab &pt, hipStream_t s) {
   void (*k)(const RteLwJacArgs, const PlanckTab);
@@ -170,7 +233,12 @@ hipError_t launch_jac(const RteLwJacArgs &a, const PlanckTab &pt, hipStream_t s)
   if (a.part_tau && a.part_mask) k = two ? rte_lw_jac_kernel<PLANCK, 2, true> : rte_lw_jac_kernel<PLANCK, 1, true>;
   else if (a.part_tau) k = two ? rte_lw_jac_kernel<PLANCK, 2, false> : rte_lw_jac_kernel<PLANCK, 1, false>;
   else k = rte_lw_jac_kernel<PLANCK, 0, false>;
-  RteLwJacArgs b = a;
+  return launch_jac_kernel(k, a, pt, s);
+}
+
+template <class Args>
+hipError_t launch_jac_kernel(void (*k)(const Args, const PlanckTab), const Args &a, const PlanckTab &pt, hipStream_t s) {
+  Args b = a;
   const int max_lev = kLdsBudget / (int)(sizeof(double) * kJacCW);
   b.lev_chunk = a.nlay + 1 < max_lev ? a.nlay + 1 : max_lev;
   const size_t lds = sizeof(double) * (size_t)b.lev_chunk * kJacCW;
@@ -192,6 +260,18 @@ hipError_t launch_rte_lw_jac(const RteLwJacArgs &a, const double *planck, int nt
   if (a.sfc_source_jac) return launch_jac<false>(a, PlanckTab{nullptr, 0., 1., 1., 2, a.ng}, s);
   if (!a.tsfc || !planck) return hipErrorInvalidValue;
   return launch_jac<true>(a, PlanckTab{planck, t0, dt, 1. / dt, ntp, a.ng}, s);
+}
+
+hipError_t launch_rte_lw_rescaled_jac(const RteLwRescJacArgs &a, const double *planck, int ntp, double t0, double dt, hipStream_t s) {
+  if (a.ncol <= 0) return hipSuccess;
+  if (a.nlay < 1 || a.ng < 1 || a.nmus < 1 || a.nmus > 4 || !a.tau || !a.sfc_emis || !a.flux_up_jac) return hipErrorInvalidValue;
+  // ssa and g together and without particles, or part_g with part_tau and part_ssa (and a mask of at most 64 g-points)
+  if (a.ssa ? (!a.g || a.part_tau || a.part_ssa || a.part_g || a.part_mask) : (a.g || !a.part_tau || !a.part_ssa || !a.part_g))
+    return hipErrorInvalidValue;
+  if (a.part_mask && a.ng > 64) return hipErrorInvalidValue;
+  if (a.sfc_source_jac) return launch_resc_jac<false>(a, PlanckTab{nullptr, 0., 1., 1., 2, a.ng}, s);
+  if (!a.tsfc || !planck) return hipErrorInvalidValue;
+  return launch_resc_jac<true>(a, PlanckTab{planck, t0, dt, 1. / dt, ntp, a.ng}, s);
 }
 
 hipError_t launch_planck_sfc_jac(const double *planck, int ng, int ntp, double t0, double dt, int ncol, const double *tsfc,

@@ -95,6 +95,11 @@ __host__ __device__ constexpr int planck_stride(int ng) { return ng | 1; }   // 
 //      sweep (into the slot of the first exchange's D, which every wave has read before the second barrier);
 //   3. (T, D): the adjusted down sweep, accumulated per level as above.
 // One group per block.  No other instantiation changes: every RESC statement sits behind `if constexpr`.
+// RESC with JAC (PLANCK forms; rte_lw_split_rescaled_jac_kernel, ecckd_lw_fluxes_rescaled_jac with "lw_jac_inline" = 1): with
+// every source zero dn0 == 0 and the adjusted up sweep reduces to up[s] = t * up[s+1], so the Jacobian is the JAC form's:
+// the surface term folded through the exchanged T of the waves below, then carried through the adjusted up sweep behind the
+// second exchange (one multiply and one accumulator add per (cell, angle)).  The third accumulator plane sits behind the
+// exchange area; the flux statements and their order are untouched, so the fluxes are the rescaled kernel's bit for bit.
 template <int SEG, int NW, int CW, bool SHARED, bool SER3, bool PLANCK, int SKY, bool MASK = false, bool BOTH = false, bool JAC = false,
           bool RESC = false>
 __device__ __forceinline__ void rte_lw_split_body(const RteLwArgs &a, const PlanckTab &pt, const double *tlay, const double *tlev,
@@ -105,7 +110,7 @@ __device__ __forceinline__ void rte_lw_split_body(const RteLwArgs &a, const Plan
   static_assert(SKY != 0 || !MASK, "a cloud mask belongs to the all-sky form");
   static_assert(SKY != 0 || !BOTH, "the dual-sky form extends the all-sky form");
   static_assert(!JAC || (PLANCK && !BOTH), "the Jacobian form extends the single-sky Planck-recomputing solver");
-  static_assert(!RESC || (!SHARED && !BOTH && !JAC && (PLANCK ? SKY == 2 : SKY == 0)),
+  static_assert(!RESC || (!SHARED && !BOTH && (!JAC || PLANCK) && (PLANCK ? SKY == 2 : SKY == 0)),
                 "the rescaled form reads arrays, or recomputes Planck sources and takes a two-stream band triple");
   constexpr int GW = 64 / CW;
   constexpr int NL = SEG * NW;
@@ -377,6 +382,16 @@ __device__ __forceinline__ void rte_lw_split_body(const RteLwArgs &a, const Plan
           if (q == w) Uin = U;
           U = x[(q * 3 + 0) * 64 + lane] * U + x[(q * 3 + 2) * 64 + lane];
         }
+        [[maybe_unused]] double J = 0.;   // JAC: d(intensity) / d(tsfc) entering this segment from below
+        if constexpr (JAC) {   // with all sources zero dn0 == 0 and the adjusted up sweep is J = t * J: the fold of the JAC form above
+          double Jq = eps * (planck_at(pt, ptab, pstride, tsfc[cc] + 1., gg, pi_f32, rpi_f32) - sfc_src);
+          J = Jq;
+#pragma unroll
+          for (int q = NW - 1; q >= 0; --q) {
+            if (q == w) J = Jq;
+            Jq = x[(q * 3 + 0) * 64 + lane] * Jq;
+          }
+        }
         // adjusted up sweep: levels s0+SEG .. s0+1; the radiance entering a layer from below adjusts its down source
         U = Uin;
 #pragma unroll
@@ -384,8 +399,15 @@ __device__ __forceinline__ void rte_lw_split_body(const RteLwArgs &a, const Plan
           acc_add(&acc_up[(s0 + s + 1) * CW + cl], gsum<CW>(wfac * U), owner);
           SDA[s] = SDA[s] + CA[s] * U;
           U = T[s] * U + SU[s];
+          if constexpr (JAC) {
+            acc_add(&acc_jac[(s0 + s + 1) * CW + cl], gsum<CW>(wfac * J), owner);
+            J = T[s] * J;
+          }
         }
         if (w == 0) acc_add(&acc_up[cl], gsum<CW>(wfac * U), owner);
+        if constexpr (JAC) {
+          if (w == 0) acc_add(&acc_jac[cl], gsum<CW>(wfac * J), owner);
+        }
         double D3 = 0.;
 #pragma unroll
         for (int s = 0; s < SEG; ++s) D3 = T[s] * D3 + SDA[s];
@@ -557,6 +579,14 @@ __global__ void __launch_bounds__(64 * NW, WPS) rte_lw_split_rescaled_allsky_ker
   rte_lw_split_body<SEG, NW, CW, false, SER3, true, 2, MASK, false, false, true>(a, pt, tlay, tlev, tsfc);
 }
 
+// ... and that form with flux_up_jac of the all sky next to the fluxes (RESC with JAC): one wave per SIMD as it is
+template <int SEG, int NW, int CW, bool SER3, bool MASK>
+__global__ void __launch_bounds__(64 * NW, 1) rte_lw_split_rescaled_jac_kernel(const RteLwArgs a, const PlanckTab pt, const double *tlay,
+                                                                               const double *tlev, const double *tsfc,
+                                                                               double *flux_up_jac) {
+  rte_lw_split_body<SEG, NW, CW, false, SER3, true, 2, MASK, false, true, true>(a, pt, tlay, tlev, tsfc, nullptr, nullptr, flux_up_jac);
+}
+
 // Both rescaled forms walk 15 layers per wave with 4 waves per block and 32 columns per tile: the fused call equals the
 // composed one bit for bit only if both compose their segments alike ("lw_split_seg" does not act here).
 constexpr int kRescSeg = 15, kRescNW = 4, kRescCW = 32;
@@ -590,6 +620,24 @@ hipError_t launch_rescaled_planck(const RteLwArgs &a, const PlanckTab &pt, const
   const long cap = 256L * 4;   // one block is resident per CU; the rest by grid stride, as launch_split_both
   if (blocks > cap) blocks = cap;
   hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(64 * kRescNW), lds, s, a, pt, tlay, tlev, tsfc);
+  return hipGetLastError();
+}
+
+constexpr size_t resc_jac_lds_doubles() { return resc_lds_doubles() + (size_t)(kRescSeg * kRescNW + 1) * kRescCW; }
+
+template <bool SER3, bool MASK>
+hipError_t launch_rescaled_planck_jac(const RteLwArgs &a, const PlanckTab &pt, const double *tlay, const double *tlev,
+                                      const double *tsfc, double *flux_up_jac, hipStream_t s) {
+  auto k = rte_lw_split_rescaled_jac_kernel<kRescSeg, kRescNW, kRescCW, SER3, MASK>;
+  // the rescaled form's accumulators and exchange, the Jacobian's plane, the Planck table
+  const size_t lds = sizeof(double) * (resc_jac_lds_doubles() + (size_t)pt.ntp * planck_stride(a.ng));
+  if (lds > (size_t)kLdsBudget) return hipErrorInvalidValue;
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (e != hipSuccess) return e;
+  long blocks = ((long)a.ncol + kRescCW - 1) / kRescCW;
+  const long cap = 256L * 4;   // as launch_rescaled_planck
+  if (blocks > cap) blocks = cap;
+  hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(64 * kRescNW), lds, s, a, pt, tlay, tlev, tsfc, flux_up_jac);
   return hipGetLastError();
 }
 
@@ -750,15 +798,23 @@ hipError_t launch_rte_lw_rescaled_split(const RteLwArgs &a, hipStream_t s) {
   return a.series3 ? launch_rescaled<true>(a, s) : launch_rescaled<false>(a, s);
 }
 
-bool rte_lw_rescaled_planck_fits(int ng, int ntp) {
-  return sizeof(double) * (resc_lds_doubles() + (size_t)ntp * planck_stride(ng)) <= (size_t)kLdsBudget;
+bool rte_lw_rescaled_planck_fits(int ng, int ntp, bool jac) {
+  return sizeof(double) * ((jac ? resc_jac_lds_doubles() : resc_lds_doubles()) + (size_t)ntp * planck_stride(ng)) <= (size_t)kLdsBudget;
 }
 
 hipError_t launch_rte_lw_rescaled_planck(const RteLwArgs &a, const double *planck, int ntp, double t0, double dt,
-                                         const double *tlay, const double *tlev, const double *tsfc, hipStream_t s) {
+                                         const double *tlay, const double *tlev, const double *tsfc, hipStream_t s,
+                                         double *flux_up_jac) {
   if (a.f32 || a.nlay != kRescSeg * kRescNW || a.ncol <= 0 || !a.part_tau || !a.part_ssa || !a.part_g) return hipErrorInvalidValue;
   if (a.part_mask && a.ng > 64) return hipErrorInvalidValue;
   const PlanckTab pt{planck, t0, dt, 1. / dt, ntp, a.ng};
+  if (flux_up_jac) {   // the Jacobian form (ecckd_lw_fluxes_rescaled_jac, "lw_jac_inline" = 1)
+    if (a.part_mask)
+      return a.series3 ? launch_rescaled_planck_jac<true, true>(a, pt, tlay, tlev, tsfc, flux_up_jac, s)
+                       : launch_rescaled_planck_jac<false, true>(a, pt, tlay, tlev, tsfc, flux_up_jac, s);
+    return a.series3 ? launch_rescaled_planck_jac<true, false>(a, pt, tlay, tlev, tsfc, flux_up_jac, s)
+                     : launch_rescaled_planck_jac<false, false>(a, pt, tlay, tlev, tsfc, flux_up_jac, s);
+  }
   if (a.part_mask)
     return a.series3 ? launch_rescaled_planck<true, true>(a, pt, tlay, tlev, tsfc, s)
                      : launch_rescaled_planck<false, true>(a, pt, tlay, tlev, tsfc, s);
