@@ -837,6 +837,80 @@ int ecckd_rte_sw_byband_f32(int device, int ncol, int nlay, int ngpt, int top_at
                             float *bnd_flux_dir, float *flux_up, float *flux_dn, float *flux_dir, int memspace, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Cloud optics: liquid and ice water paths and effective radii per (column, layer) to the particulate properties on the
+ * model's bands -- the planes the all-sky calls above take as tau_p, ssa_p, g_p (or op2 of ecckd_increment).  A host model
+ * carries water paths and radii, not optical properties; this is the step between them.  The reference's drivers have no
+ * such path (clear-sky RFMIP only), so there is no counterpart call in the reference tree: the call restates the
+ * look-up-table form of RTE-RRTMGP's ty_cloud_optics%cloud_optics [RTE-ext: extensions/cloud_optics/mo_cloud_optics.F90
+ * of the v1.5 era, compute_all_from_table and the combination of the phases in cloud_optics], which every all-sky
+ * RTE-RRTMGP driver calls between gas_optics and increment.  RTE-RRTMGP is not part of the reference tree, so PARITY WITH
+ * IT IS UNPINNED; the definition below is what the tests pin (tests/cloud_optics_ref.py restates it in numpy, and the
+ * results are equal BIT FOR BIT in fp64 and in float: the build has FMA contraction off, every line below is one
+ * correctly rounded IEEE operation in the precision of the call).  The Pade form of ty_cloud_optics is out of scope.
+ *
+ * Tables.  For each phase x in {liq, ice}: lut_ext (mass extinction, m2 g-1), lut_ssa, lut_asy of shape (nsize_x, nband),
+ * size index fastest, covering the effective radii [radx_lwr, radx_upr] (microns) evenly:
+ *     step = (radx_upr - radx_lwr)/(nsize_x - 1).
+ * The ice tables carry a third dimension, (nsize_ice, nband, nrghice); the roughness icergh (1-based) is an argument of
+ * the compute call, not state of the object (per-call state is passed explicitly in this C ABI).
+ * ecckd_cloud_optics_create_lut takes HOST tables and makes the device copy once (device -1: a host-only object whose
+ * getters and refusals work and whose compute call fails).  A slope table[i+1] - table[i] is formed there: it is the same
+ * subtraction.  Refused with a message, in this order: handle NULL; nband < 1; nsize_liq or nsize_ice < 2; nrghice < 1;
+ * radliq_upr <= radliq_lwr; radice_upr <= radice_lwr (a NaN bound too); a NULL table; no such device.
+ *
+ * ecckd_cloud_optics (+ _f32).  clwp, ciwp: water paths (g m-2), reliq, reice: effective radii (microns), all (ncol,nlay);
+ * tau, ssa, g: (ncol,nlay,nband); column fastest.  Per cell and phase, with wp, re, the phase's tables (1-based below) and
+ * nsize, r_lwr, step:
+ *     cloudy = wp > 0                                   (NaN, 0, negative: not cloudy)
+ *     if cloudy:
+ *       s     = (re - r_lwr)/step
+ *       index = min(floor(s)+1, nsize-1), then at least 1        (a NaN s takes index 1)
+ *       fint  = s - (index-1)
+ *       t   = wp * (ext(index) + fint*(ext(index+1)-ext(index)))
+ *       ts  = t  * (ssa(index) + fint*(ssa(index+1)-ssa(index)))
+ *       tsg = ts * (asy(index) + fint*(asy(index+1)-asy(index)))
+ *     else t = ts = tsg = +0       (a select, not a product: re, and a NaN in it, does not reach a clear cell)
+ *   With (lt, lts, ltsg) of the liquid and (it, its, itsg) of the ice, per band:
+ *     two-stream (ssa and g given):   tau = lt+it;  tssa = lts+its;  g = (ltsg+itsg)/max(eps,tssa);  ssa = tssa/max(eps,tau)
+ *     one-scalar (ssa and g NULL):    tau = (lt-lts) + (it-its)                  (the absorption optical depth)
+ *   eps = epsilon(1.0) of the precision (2^-52, 2^-23); max(eps,x) is x where x > eps, else eps.  A clear cell gives
+ *   tau = ssa = g = +0.  The lower clamp of index is this project's addition: it keeps an out-of-range or NaN radius in a
+ *   DEVICE array from reading outside the table -- such a radius extrapolates (fint outside [0,1]) or gives NaN, in that
+ *   cell only, and never faults.  _f32: the tables and the four radius bounds are rounded to float first (the slopes and
+ *   the step are then float operations), everything above in float.
+ *   Refused with a message before anything is launched, in this order: object NULL; icergh outside 1..nrghice; ssa
+ *   without g or g without ssa; bad ncol / nlay; clwp, ciwp, reliq, reice or tau NULL; bad memspace; then, with HOST
+ *   input arrays only (ECCKD_HOST, ECCKD_MIXED), as RTE's check_values does: a cloudy cell whose liquid radius lies
+ *   outside [radliq_lwr, radliq_upr] (or is NaN); the same for ice; a negative liquid water path; a negative ice water
+ *   path; then a host-only object; no device.  With ECCKD_DEVICE arrays the values are not checked (the call stays
+ *   asynchronous; the rule ecckd_delta_scale states for `forward`) and the clamp above applies.
+ *   ECCKD_DEVICE is asynchronous on `stream` and uses no scratch, so it is capture-safe without a warm-up; ECCKD_HOST
+ *   stages through the device and synchronises; ECCKD_MIXED: host inputs, tau / ssa / g device buffers (synchronises).
+ *   Kernel: one lane per cell, bands walked with coalesced plane stores; both phases' tables for the chosen roughness as
+ *   (value, slope) pairs in LDS while they fit 32 KiB per block (five blocks stay resident per CU), that is while
+ *     (ssa ? 3 : 2) * nband * ((nsize_liq-1) + (nsize_ice-1)) * 2*sizeof(real) <= 32768,
+ *   else read in place through L2; a phase no lane of a wave holds is skipped, so clear waves read no table.
+ * --------------------------------------------------------------------------------------- */
+typedef struct ecckd_cloud_lut ecckd_cloud_optics_t; /* replaces type(ty_cloud_optics), LUT form */
+int ecckd_cloud_optics_create_lut(int nband, int nsize_liq, int nsize_ice, int nrghice, double radliq_lwr, double radliq_upr,
+                                  double radice_lwr, double radice_upr, const double *lut_extliq, const double *lut_ssaliq,
+                                  const double *lut_asyliq, const double *lut_extice, const double *lut_ssaice,
+                                  const double *lut_asyice, int device, ecckd_cloud_optics_t **cloud_optics);
+void ecckd_cloud_optics_destroy(ecckd_cloud_optics_t *cloud_optics);
+int ecckd_cloud_optics_get_nband(const ecckd_cloud_optics_t *cloud_optics);
+int ecckd_cloud_optics_get_nrghice(const ecckd_cloud_optics_t *cloud_optics);
+double ecckd_cloud_optics_get_min_radius_liq(const ecckd_cloud_optics_t *cloud_optics);
+double ecckd_cloud_optics_get_max_radius_liq(const ecckd_cloud_optics_t *cloud_optics);
+double ecckd_cloud_optics_get_min_radius_ice(const ecckd_cloud_optics_t *cloud_optics);
+double ecckd_cloud_optics_get_max_radius_ice(const ecckd_cloud_optics_t *cloud_optics);
+int ecckd_cloud_optics(const ecckd_cloud_optics_t *cloud_optics, int ncol, int nlay, const double *clwp, const double *ciwp,
+                       const double *reliq, const double *reice, int icergh, double *tau, double *ssa, double *g, int memspace,
+                       void *stream);
+int ecckd_cloud_optics_f32(const ecckd_cloud_optics_t *cloud_optics, int ncol, int nlay, const float *clwp, const float *ciwp,
+                           const float *reliq, const float *reice, int icergh, float *tau, float *ssa, float *g, int memspace,
+                           void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * Device memory for host languages without a HIP binding of their own (the Fortran shim's device-resident
  * twins of ty_optical_props / ty_source_func_lw own their buffers through these).  to_device: 1 = host to
  * device, 0 = device to host; synchronous.

@@ -9,6 +9,8 @@ This package is a thin mirror of the reference's Fortran interface on top of the
 * :class:`GasConcs`, :class:`OpticalProps1scl`, :class:`OpticalProps2str`,
   :class:`SourceFuncLW`, :class:`FluxesBroadband` <-> the RTE-RRTMGP types the reference
   passes around (only the members it touches);
+* :class:`CloudOptics` <-> RTE-RRTMGP's ``ty_cloud_optics`` (look-up-table form): water paths and effective
+  radii to the particulate properties on the bands, in front of the all-sky calls;
 * :func:`rte_lw`, :func:`rte_sw` <-> RTE-RRTMGP's solvers as called at
   ecckd_rfmip_lw.F90:130-135 and ecckd_rfmip_sw.F90:148-154.
 
@@ -31,12 +33,13 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("ECCKD_LIB", os.path.join(_HERE, "librte_ecckd_hip.so"))   # override: kernel experiments
 HOST, DEVICE = 0, 1
+MIXED = 2   # host inputs, device-resident spectral arrays (ECCKD_MIXED)
 NAME_LEN = 32
 
 _SOURCES = ["kernels_gas_fused.hip", "kernels_tau.hip", "kernels_planck.hip", "kernels_rte_lw.hip", "kernels_rte_lw_split.hip",
             "kernels_rte_lw_jac.hip", "kernels_rte_lw_2str.hip",
             "kernels_rte_sw.hip", "kernels_rte_sw_sys.hip", "kernels_rte_gpt.hip", "kernels_optical_props.hip",
-            "kernels_cloud_sampling.hip",
+            "kernels_cloud_sampling.hip", "kernels_cloud_optics.hip",
             "capi.cpp", "nc_capi.cpp", "model.cpp", "cdf1.cpp"]
 _HEADERS = ["kernels.hpp", "wave_pair.hpp", "sw_two_stream.hpp", "sw_two_stream_body.inc", "lw_two_stream.hpp", "lw_layer.hpp", "planck_at.hpp", "model.hpp", "cdf1.hpp", os.path.join("..", "..", "include", "ecckd_hip.h"),
             os.path.join("..", "..", "include", "ecckd_nc.h"), os.path.join("..", "..", "include", "rte_kernels_hip.h"),
@@ -91,9 +94,11 @@ FORTRAN_BUILD = os.path.join(FORTRAN_DIR, "build")
 FORTRAN_DRIVER = os.path.join(FORTRAN_BUILD, "ecckd_driver")
 RFMIP_LW = os.path.join(FORTRAN_BUILD, "ecckd_rfmip_lw")
 RFMIP_SW = os.path.join(FORTRAN_BUILD, "ecckd_rfmip_sw")
-_FORTRAN_MODULES = ["mo_rte_min.F90", "mo_ecckd_device.F90", "gas_optics_ecckd.F90", "mo_rte_solvers.F90", "rfmip_support.F90"]
+CLOUD_DRIVER = os.path.join(FORTRAN_BUILD, "ecckd_cloud_driver")
+_FORTRAN_MODULES = ["mo_rte_min.F90", "mo_ecckd_device.F90", "gas_optics_ecckd.F90", "mo_rte_solvers.F90", "rfmip_support.F90",
+                    "mo_cloud_optics.F90"]
 _FORTRAN_PROGRAMS = [("ecckd_driver", "ecckd_driver.F90", []), ("ecckd_rfmip_lw", "ecckd_rfmip.F90", []),
-                     ("ecckd_rfmip_sw", "ecckd_rfmip.F90", ["-DSHORTWAVE"])]
+                     ("ecckd_rfmip_sw", "ecckd_rfmip.F90", ["-DSHORTWAVE"]), ("ecckd_cloud_driver", "ecckd_cloud_driver.F90", [])]
 
 
 def build_fortran(force=False, verbose=False):
@@ -230,6 +235,17 @@ def lib():
                                                    [C.c_void_p] * 9 + [C.c_int, C.c_void_p])
         L.ecckd_lw_fluxes_rescaled_jac_scratch_bytes.restype = C.c_size_t
         L.ecckd_lw_fluxes_rescaled_jac_scratch_bytes.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
+    if hasattr(L, "ecckd_cloud_optics"):   # (ECCKD_LIB may name an older build, which lacks them)
+        L.ecckd_cloud_optics_create_lut.argtypes = [C.c_int] * 4 + [C.c_double] * 4 + [C.c_void_p] * 6 + [C.c_int, C.c_void_p]
+        L.ecckd_cloud_optics_destroy.argtypes = [C.c_void_p]
+        L.ecckd_cloud_optics_destroy.restype = None
+        for f in ("nband", "nrghice"):
+            getattr(L, "ecckd_cloud_optics_get_" + f).argtypes = [C.c_void_p]
+        for f in ("min_radius_liq", "max_radius_liq", "min_radius_ice", "max_radius_ice"):
+            getattr(L, "ecckd_cloud_optics_get_" + f).restype = C.c_double
+            getattr(L, "ecckd_cloud_optics_get_" + f).argtypes = [C.c_void_p]
+        for f in ("ecckd_cloud_optics", "ecckd_cloud_optics_f32"):
+            getattr(L, f).argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 3 + [C.c_int, C.c_void_p]
     _lib = L
     return L
 
@@ -599,6 +615,117 @@ class OpticalProps2str(OpticalProps1scl):
             return str(e)
         rc = (lib().ecckd_delta_scale_f32 if f32 else lib().ecckd_delta_scale)(
             int(_device_of(self.tau)), ncol, nlay, n, *args, space, _stream(space))
+        return last_error() if rc else ""
+
+
+class CloudOptics:
+    """``ty_cloud_optics`` (RTE-RRTMGP, extensions/cloud_optics/mo_cloud_optics.F90), look-up-table form, backed by a
+    device-resident table handle: liquid / ice water paths (g m-2) and effective radii (microns) per (column, layer) to
+    the particulate properties on the bands -- what the all-sky calls take as ``particles``.  The definition is in
+    include/ecckd_hip.h (``ecckd_cloud_optics``); parity with RTE-RRTMGP is unpinned.  The Pade form is not provided."""
+
+    def __init__(self):
+        self._h = C.c_void_p(None)
+        self._icergh = 1
+        self._device = -1
+
+    def __del__(self):
+        try:
+            self.finalize()
+        except Exception:
+            pass
+
+    def finalize(self):
+        if self._h:
+            lib().ecckd_cloud_optics_destroy(self._h)
+            self._h = C.c_void_p(None)
+
+    def load_lut(self, band_lims_wvn, radliq_lwr, radliq_upr, radliq_fac, radice_lwr, radice_upr, radice_fac,
+                 lut_extliq, lut_ssaliq, lut_asyliq, lut_extice, lut_ssaice, lut_asyice, device=0):
+        """``load`` (LUT form) with RTE-RRTMGP's argument list.  Host tables, numpy float64: liquid ``(nband, nsize_liq)``,
+        ice ``(nrghice, nband, nsize_ice)`` (the reversed Fortran shapes).  ``band_lims_wvn`` ``(nband, 2)`` or None gives
+        nothing but the band count; ``radliq_fac`` / ``radice_fac`` are accepted and unused, as the LUT form of RTE-RRTMGP
+        leaves them.  ``device`` -1 makes a host-only object.  Returns the error message ('' = success)."""
+        self.finalize()
+        tabs = (lut_extliq, lut_ssaliq, lut_asyliq, lut_extice, lut_ssaice, lut_asyice)
+        for t in tabs:
+            if not isinstance(t, np.ndarray) or t.dtype != np.float64 or not t.flags.c_contiguous:
+                return "cloud_optics%init(): the tables are C-contiguous float64 ndarrays on the host"
+        if lut_extliq.ndim != 2 or lut_extice.ndim != 3:
+            return "cloud_optics%init(): liquid tables are (nband, nsize_liq), ice tables (nrghice, nband, nsize_ice)"
+        if any(t.shape != lut_extliq.shape for t in tabs[:3]) or any(t.shape != lut_extice.shape for t in tabs[3:]):
+            return "cloud_optics%init(): arrays sized inconsistently"
+        nband, nsize_liq = lut_extliq.shape
+        nrghice, nband_ice, nsize_ice = lut_extice.shape
+        if nband_ice != nband or (band_lims_wvn is not None and np.shape(band_lims_wvn)[0] != nband):
+            return "cloud_optics%init(): arrays sized inconsistently"
+        h = C.c_void_p(None)
+        if lib().ecckd_cloud_optics_create_lut(nband, nsize_liq, nsize_ice, nrghice, float(radliq_lwr), float(radliq_upr),
+                                               float(radice_lwr), float(radice_upr),
+                                               *[C.c_void_p(t.ctypes.data) for t in tabs], int(device), C.byref(h)):
+            return last_error()
+        self._h, self._icergh, self._device = h, 1, int(device)
+        return ""
+
+    def set_ice_roughness(self, icergh):
+        """The roughness (1-based) the next calls pass to ``ecckd_cloud_optics``; it is state of this mirror only."""
+        if not self._h:
+            return "cloud_optics%set_ice_roughness(): can't set before initialization"
+        if icergh < 1 or icergh > self.get_num_ice_roughness_types():
+            return "cloud_optics%set_ice_roughness(): must be > 0 and <= nrghice"
+        self._icergh = int(icergh)
+        return ""
+
+    def get_num_ice_roughness_types(self):
+        return lib().ecckd_cloud_optics_get_nrghice(self._h) if self._h else 0
+
+    def get_nband(self):
+        return lib().ecckd_cloud_optics_get_nband(self._h) if self._h else 0
+
+    def get_min_radius_liq(self):
+        return lib().ecckd_cloud_optics_get_min_radius_liq(self._h)
+
+    def get_max_radius_liq(self):
+        return lib().ecckd_cloud_optics_get_max_radius_liq(self._h)
+
+    def get_min_radius_ice(self):
+        return lib().ecckd_cloud_optics_get_min_radius_ice(self._h)
+
+    def get_max_radius_ice(self):
+        return lib().ecckd_cloud_optics_get_max_radius_ice(self._h)
+
+    def cloud_optics(self, clwp, ciwp, reliq, reice, optical_props):
+        """``cloud_optics(clwp, ciwp, reliq, reice, optical_props)``: inputs ``(nlay, ncol)``; ``optical_props`` an
+        :class:`OpticalProps2str` (tau, ssa, g) or :class:`OpticalProps1scl` (absorption optical depth) made by
+        ``alloc_*_bands``, ``(nband, nlay, ncol)``.  numpy arrays (staged), torch device tensors (asynchronous on the
+        current stream), or numpy inputs with device planes.  float32 planes take the ``_f32`` call.
+        Returns the error message ('' = success)."""
+        if not self._h:
+            return "cloud_optics%cloud_optics(): the tables have not been loaded"
+        op = optical_props
+        two = isinstance(op, OpticalProps2str)
+        if op.tau is None or op.tau.ndim != 3:
+            return "cloud_optics%cloud_optics(): optical properties are not allocated (alloc_1scl_bands / alloc_2str_bands)"
+        nband, nlay, ncol = op.tau.shape
+        if nband != self.get_nband():
+            return ("cloud_optics%cloud_optics(): optical properties have " + str(nband) + " bands, the tables " +
+                    str(self.get_nband()))
+        f32 = _is_f32(op.tau)
+        planes = [op.tau] + ([op.ssa, op.g] if two else [])
+        inputs = [clwp, ciwp, reliq, reice]
+        try:
+            space = _space_of(planes)
+            if space == DEVICE and _space_of(inputs) == HOST:
+                space = MIXED
+            elif _space_of(inputs) != space:
+                raise TypeError("mixing host and device arrays in one call")
+            ins = [_ptr(a, (nlay, ncol), n, f32) for a, n in zip(inputs, ("clwp", "ciwp", "reliq", "reice"))]
+            outs = [_ptr(a, (nband, nlay, ncol), n, f32) for a, n in zip(planes, ("tau", "ssa", "g"))] + [None] * (3 - len(planes))
+        except (TypeError, ValueError) as e:
+            return str(e)
+        st = _stream(DEVICE) if space == DEVICE else None
+        rc = (lib().ecckd_cloud_optics_f32 if f32 else lib().ecckd_cloud_optics)(
+            self._h, ncol, nlay, *ins, self._icergh, *outs, space, st)
         return last_error() if rc else ""
 
 

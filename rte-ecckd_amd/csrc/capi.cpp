@@ -661,6 +661,63 @@ int fill_band_map(int ngpt, int nband, const int *band2gpt, unsigned char *gpt2b
 
 }  // namespace
 
+// ---- cloud optics: the object and its host-side helpers (the entry points are below, with kernels_cloud_optics.hip) ----
+// The look-up tables of ty_cloud_optics.  On the device: one buffer of (value, slope) pair images, per precision the liquid
+// image [quantity][band][nsize_liq-1] and, per roughness, the ice image [quantity][band][nsize_ice-1].
+struct ecckd_cloud_lut {
+  int nband = 0, nsize_liq = 0, nsize_ice = 0, nrghice = 0, device = -1;
+  double radliq_lwr = 0., radliq_upr = 0., radice_lwr = 0., radice_upr = 0.;
+  char *dbuf = nullptr;
+  size_t off_liq[2] = {0, 0}, off_ice[2] = {0, 0}, ice_stride[2] = {0, 0};   // bytes; [0] fp64, [1] float
+};
+
+namespace {
+
+// (value, slope) pairs of the rows of `table` (nsize, nrow), size fastest, appended to `out`: the table is rounded to
+// `real` first and the slope is the subtraction table[i+1] - table[i] in `real`
+template <typename real>
+void append_pairs(std::vector<ecckd::CloudLutPair<real>> &out, const double *table, int nsize, size_t nrow) {
+  for (size_t r = 0; r < nrow; ++r)
+    for (int i = 0; i + 1 < nsize; ++i) {
+      const real lo = (real)table[r * nsize + i], hi = (real)table[r * nsize + i + 1];
+      out.push_back(ecckd::CloudLutPair<real>{lo, hi - lo});
+    }
+}
+
+template <typename real>
+std::vector<ecckd::CloudLutPair<real>> cloud_lut_image(int nsize, int nband, int nrgh, const double *ext, const double *ssa,
+                                                       const double *asy) {
+  std::vector<ecckd::CloudLutPair<real>> out;
+  out.reserve((size_t)3 * nrgh * nband * (nsize - 1));
+  const size_t plane = (size_t)nsize * nband;
+  for (int r = 0; r < nrgh; ++r) {
+    append_pairs(out, ext + r * plane, nsize, nband);
+    append_pairs(out, ssa + r * plane, nsize, nband);
+    append_pairs(out, asy + r * plane, nsize, nband);
+  }
+  return out;
+}
+
+// RTE's check_values on host arrays: the first complaint, or null.  Bounds in the precision of the call.
+template <typename real>
+const char *cloud_optics_check_host(const ecckd_cloud_lut &co, size_t n, const real *clwp, const real *ciwp, const real *reliq,
+                                    const real *reice) {
+  const real ll = (real)co.radliq_lwr, lu = (real)co.radliq_upr, il = (real)co.radice_lwr, iu = (real)co.radice_upr;
+  for (size_t i = 0; i < n; ++i)
+    if (clwp[i] > real(0) && !(reliq[i] >= ll && reliq[i] <= lu))
+      return "ecckd_cloud_optics: liquid effective radius out of the table's range in a cloudy cell";
+  for (size_t i = 0; i < n; ++i)
+    if (ciwp[i] > real(0) && !(reice[i] >= il && reice[i] <= iu))
+      return "ecckd_cloud_optics: ice effective radius out of the table's range in a cloudy cell";
+  for (size_t i = 0; i < n; ++i)
+    if (clwp[i] < real(0)) return "ecckd_cloud_optics: negative liquid water path";
+  for (size_t i = 0; i < n; ++i)
+    if (ciwp[i] < real(0)) return "ecckd_cloud_optics: negative ice water path";
+  return nullptr;
+}
+
+}  // namespace
+
 extern "C" {
 
 const char *ecckd_last_error(void) { return g_err.c_str(); }
@@ -2769,6 +2826,131 @@ int ecckd_increment_masked_f32(int device, int ncol, int nlay, int ngpt, float *
                                const unsigned long long *mask, int memspace, void *stream) {
   return increment_impl(true, device, ncol, nlay, ngpt, dp(tau1), dp(ssa1), dp(g1), nband, band2gpt, dp(tau2), dp(ssa2), dp(g2),
                         memspace, stream, mask);
+}
+
+// ---- cloud optics (kernels_cloud_optics.hip): water paths and effective radii to band properties ----
+
+int ecckd_cloud_optics_create_lut(int nband, int nsize_liq, int nsize_ice, int nrghice, double radliq_lwr, double radliq_upr,
+                                  double radice_lwr, double radice_upr, const double *lut_extliq, const double *lut_ssaliq,
+                                  const double *lut_asyliq, const double *lut_extice, const double *lut_ssaice,
+                                  const double *lut_asyice, int device, ecckd_cloud_optics_t **cloud_optics) {
+  if (!cloud_optics) return fail("ecckd_cloud_optics_create_lut: null argument (the handle)");
+  *cloud_optics = nullptr;
+  if (nband < 1) return fail("ecckd_cloud_optics_create_lut: nband must be at least 1");
+  if (nsize_liq < 2 || nsize_ice < 2) return fail("ecckd_cloud_optics_create_lut: a table needs at least 2 sizes");
+  if (nrghice < 1) return fail("ecckd_cloud_optics_create_lut: nrghice must be at least 1");
+  if (!(radliq_upr > radliq_lwr)) return fail("ecckd_cloud_optics_create_lut: radliq_upr must exceed radliq_lwr");
+  if (!(radice_upr > radice_lwr)) return fail("ecckd_cloud_optics_create_lut: radice_upr must exceed radice_lwr");
+  if (!lut_extliq || !lut_ssaliq || !lut_asyliq || !lut_extice || !lut_ssaice || !lut_asyice)
+    return fail("ecckd_cloud_optics_create_lut: null table (ext, ssa and asy of both phases are required)");
+  ecckd_cloud_lut co;
+  co.nband = nband; co.nsize_liq = nsize_liq; co.nsize_ice = nsize_ice; co.nrghice = nrghice;
+  co.radliq_lwr = radliq_lwr; co.radliq_upr = radliq_upr; co.radice_lwr = radice_lwr; co.radice_upr = radice_upr;
+  if (device != -1) {   // (-1: a host-only object: getters and refusals work, the compute call fails)
+    if (check_device(device)) return 1;
+    const auto liq64 = cloud_lut_image<double>(nsize_liq, nband, 1, lut_extliq, lut_ssaliq, lut_asyliq);
+    const auto ice64 = cloud_lut_image<double>(nsize_ice, nband, nrghice, lut_extice, lut_ssaice, lut_asyice);
+    const auto liq32 = cloud_lut_image<float>(nsize_liq, nband, 1, lut_extliq, lut_ssaliq, lut_asyliq);
+    const auto ice32 = cloud_lut_image<float>(nsize_ice, nband, nrghice, lut_extice, lut_ssaice, lut_asyice);
+    co.off_liq[0] = 0;
+    co.off_ice[0] = align256(liq64.size() * 16);
+    co.off_liq[1] = co.off_ice[0] + align256(ice64.size() * 16);
+    co.off_ice[1] = co.off_liq[1] + align256(liq32.size() * 8);
+    co.ice_stride[0] = ice64.size() / nrghice * 16;
+    co.ice_stride[1] = ice32.size() / nrghice * 8;
+    const size_t total = co.off_ice[1] + align256(ice32.size() * 8);
+    std::vector<char> host(total, 0);
+    std::memcpy(host.data() + co.off_liq[0], liq64.data(), liq64.size() * 16);
+    std::memcpy(host.data() + co.off_ice[0], ice64.data(), ice64.size() * 16);
+    std::memcpy(host.data() + co.off_liq[1], liq32.data(), liq32.size() * 8);
+    std::memcpy(host.data() + co.off_ice[1], ice32.data(), ice32.size() * 8);
+    HIPCHK(hipMalloc(reinterpret_cast<void **>(&co.dbuf), total));
+    if (hipMemcpy(co.dbuf, host.data(), total, hipMemcpyHostToDevice) != hipSuccess) {
+      (void)hipFree(co.dbuf);
+      return fail("ecckd_cloud_optics_create_lut: copying the tables to the device failed");
+    }
+    co.device = device;
+  }
+  *cloud_optics = new ecckd_cloud_lut(co);
+  return 0;
+}
+
+void ecckd_cloud_optics_destroy(ecckd_cloud_optics_t *co) {
+  if (!co) return;
+  if (co->device >= 0 && co->dbuf) {
+    (void)hipSetDevice(co->device);
+    (void)hipFree(co->dbuf);
+  }
+  delete co;
+}
+
+int ecckd_cloud_optics_get_nband(const ecckd_cloud_optics_t *co) { return co ? co->nband : 0; }
+int ecckd_cloud_optics_get_nrghice(const ecckd_cloud_optics_t *co) { return co ? co->nrghice : 0; }
+double ecckd_cloud_optics_get_min_radius_liq(const ecckd_cloud_optics_t *co) { return co ? co->radliq_lwr : 0.; }
+double ecckd_cloud_optics_get_max_radius_liq(const ecckd_cloud_optics_t *co) { return co ? co->radliq_upr : 0.; }
+double ecckd_cloud_optics_get_min_radius_ice(const ecckd_cloud_optics_t *co) { return co ? co->radice_lwr : 0.; }
+double ecckd_cloud_optics_get_max_radius_ice(const ecckd_cloud_optics_t *co) { return co ? co->radice_upr : 0.; }
+
+static int cloud_optics_impl(bool f32, const ecckd_cloud_optics_t *co, int ncol, int nlay, const double *clwp, const double *ciwp,
+                             const double *reliq, const double *reice, int icergh, double *tau, double *ssa, double *g,
+                             int memspace, void *stream) {
+  if (!co) return fail("ecckd_cloud_optics: null cloud-optics object");
+  if (icergh < 1 || icergh > co->nrghice)
+    return fail("ecckd_cloud_optics: ice roughness " + std::to_string(icergh) + " outside 1.." + std::to_string(co->nrghice));
+  if ((ssa == nullptr) != (g == nullptr))
+    return fail("ecckd_cloud_optics: ssa without g or g without ssa (pass both: two-stream, or neither: one-scalar)");
+  if (check_dims(ncol, nlay)) return 1;
+  if (!clwp || !ciwp || !reliq || !reice || !tau)
+    return fail("ecckd_cloud_optics: null argument (clwp, ciwp, reliq, reice and tau are required)");
+  if (memspace != ECCKD_DEVICE && memspace != ECCKD_HOST && memspace != ECCKD_MIXED) return fail("ecckd: bad memspace");
+  const size_t n2 = (size_t)ncol * nlay, n3 = n2 * co->nband;
+  if (memspace != ECCKD_DEVICE) {   // (host inputs; device inputs are not checked: the call stays asynchronous)
+    const char *bad = f32 ? cloud_optics_check_host(*co, n2, reinterpret_cast<const float *>(clwp), reinterpret_cast<const float *>(ciwp),
+                                                    reinterpret_cast<const float *>(reliq), reinterpret_cast<const float *>(reice))
+                          : cloud_optics_check_host(*co, n2, clwp, ciwp, reliq, reice);
+    if (bad) return fail(bad);
+  }
+  if (co->device < 0)
+    return fail("ecckd_cloud_optics: host-only object (device -1): no GPU, no compute (there is no CPU fallback)");
+  if (check_device(co->device)) return 1;
+  if (ncol == 0) return 0;
+  ecckd::CloudOpticsArgs a{};
+  a.ncol = ncol; a.nlay = nlay; a.nband = co->nband; a.f32 = f32;
+  a.nsize_liq = co->nsize_liq; a.nsize_ice = co->nsize_ice;
+  a.cus = simd_slots(co->device) / 4;
+  if (f32) {   // bounds rounded to float, the step formed in float
+    const float ll = (float)co->radliq_lwr, il = (float)co->radice_lwr;
+    a.radliq_lwr = ll; a.radliq_step = ((float)co->radliq_upr - ll) / (float)(co->nsize_liq - 1);
+    a.radice_lwr = il; a.radice_step = ((float)co->radice_upr - il) / (float)(co->nsize_ice - 1);
+  } else {
+    a.radliq_lwr = co->radliq_lwr; a.radliq_step = (co->radliq_upr - co->radliq_lwr) / (double)(co->nsize_liq - 1);
+    a.radice_lwr = co->radice_lwr; a.radice_step = (co->radice_upr - co->radice_lwr) / (double)(co->nsize_ice - 1);
+  }
+  a.lut_liq = co->dbuf + co->off_liq[f32];
+  a.lut_ice = co->dbuf + co->off_ice[f32] + (size_t)(icergh - 1) * co->ice_stride[f32];
+  Stage st(co->device, memspace, stream, f32);
+  if (st.open([&] {
+        a.clwp = st.in(clwp, n2); a.ciwp = st.in(ciwp, n2); a.reliq = st.in(reliq, n2); a.reice = st.in(reice, n2);
+        a.tau = st.out(tau, n3, kBig); a.ssa = st.out(ssa, n3, kBig); a.g = st.out(g, n3, kBig);
+      }))
+    return 1;
+  {
+    ProfScope prof("cloud_optics", st.stream);
+    HIPCHK(ecckd::launch_cloud_optics(a, st.stream));
+  }
+  return st.close();
+}
+
+int ecckd_cloud_optics(const ecckd_cloud_optics_t *co, int ncol, int nlay, const double *clwp, const double *ciwp,
+                       const double *reliq, const double *reice, int icergh, double *tau, double *ssa, double *g, int memspace,
+                       void *stream) {
+  return cloud_optics_impl(false, co, ncol, nlay, clwp, ciwp, reliq, reice, icergh, tau, ssa, g, memspace, stream);
+}
+int ecckd_cloud_optics_f32(const ecckd_cloud_optics_t *co, int ncol, int nlay, const float *clwp, const float *ciwp,
+                           const float *reliq, const float *reice, int icergh, float *tau, float *ssa, float *g, int memspace,
+                           void *stream) {
+  return cloud_optics_impl(true, co, ncol, nlay, dp(clwp), dp(ciwp), dp(reliq), dp(reice), icergh, dp(tau), dp(ssa), dp(g),
+                           memspace, stream);
 }
 
 // ---- McICA cloud sampling (kernels_cloud_sampling.hip) ----

@@ -255,6 +255,24 @@ hipError_t launch_increment(const OptPropsArgs &a, hipStream_t s);
 hipError_t launch_delta_scale(size_t n, const double *tau, const double *ssa, const double *g, const double *forward, double *tau_out,
                               double *ssa_out, double *g_out, int f32, hipStream_t s);
 
+// Cloud optics (kernels_cloud_optics.hip; the definition is in include/ecckd_hip.h, ecckd_cloud_optics): water paths and
+// effective radii (ncol,nlay) to band planes (ncol,nlay,nband).  A table row is nsize-1 (value, slope) pairs of the call's
+// precision, slope[i] = table[i+1] - table[i]; a phase's image is [quantity: ext, ssa, asy][band][nsize-1] pairs.
+template <typename real> struct alignas(2 * sizeof(real)) CloudLutPair { real value, slope; };
+constexpr size_t kCloudOpticsLdsBytes = 32768;   // both images at most this large: staged in LDS; else read through L2
+struct CloudOpticsArgs {
+  int ncol, nlay, nband, f32;
+  int cus;                         // compute units of the device (sizes the grid); 0: 256
+  int nsize_liq, nsize_ice;
+  double radliq_lwr, radliq_step, radice_lwr, radice_step;   // (f32: float values, exactly representable here)
+  const void *lut_liq, *lut_ice;   // device images in the call's precision; lut_ice: the chosen roughness
+  const double *clwp, *ciwp, *reliq, *reice;
+  double *tau, *ssa, *g;           // ssa and g null: the one-scalar form
+};
+// bytes of both images as the kernel stages them (the one-scalar form leaves the asymmetry rows out)
+size_t cloud_optics_image_bytes(int nband, int nsize_liq, int nsize_ice, bool two_stream, bool f32);
+hipError_t launch_cloud_optics(const CloudOpticsArgs &a, hipStream_t s);
+
 // McICA cloud mask (kernels_cloud_sampling.hip; the definition is in include/ecckd_hip.h, ecckd_cloud_mask_sample):
 // cloud_frac (ncol,nlay), overlap_param (ncol,nlay-1; exp_ran only), mask (ncol,nlay); 1 <= ngpt <= 64
 hipError_t launch_cloud_mask_sample(int ncol, int nlay, int ngpt, int exp_ran, const double *cloud_frac, const double *overlap_param,

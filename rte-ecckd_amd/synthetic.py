@@ -107,6 +107,55 @@ def cloud_fraction(c0, ncol, nlay):
     return np.ascontiguousarray(np.where(has_cloud, 1.0 - uniform(c, F_CLD_FRAC, jm), 0.0))
 
 
+F_CLD_LWP, F_CLD_IWP, F_CLD_RELIQ, F_CLD_REICE, F_CLD_MIXED = range(20, 25)
+RADLIQ_LWR, RADLIQ_UPR, RADICE_LWR, RADICE_UPR = 2.5, 21.5, 10.0, 180.0   # microns (the ranges of RRTMGP's cloud tables)
+
+
+def cloud_water(c0, ncol, nlay):
+    """What a host model carries instead of ``clouds``: liquid and ice water paths ``clwp``, ``ciwp`` (g m-2) and
+    effective radii ``reliq``, ``reice`` (microns), float64 ``(nlay, ncol)``, for columns ``c0 .. c0+ncol-1``, top layer
+    first.  Water lies on exactly the layers where ``clouds`` has ``tau`` > 0: liquid (5-200 g m-2) in the lower part of
+    the grid (from 0.6 of it down), ice (1-50 g m-2) above, and both in about a third of the liquid cells.  The radii are
+    defined in every cell and lie inside the ranges of ``cloud_lut``."""
+    c = np.arange(c0, c0 + ncol, dtype=np.uint64)[None, :]
+    jm = np.arange(1, nlay + 1, dtype=np.uint64)[:, None]
+    has_cloud = clouds(c0, ncol, nlay, 1)["tau"][0] > 0.0
+    low = np.arange(nlay)[:, None] >= int(0.6 * nlay)
+    mixed = uniform(c, F_CLD_MIXED, jm) < 1.0 / 3.0
+    clwp = np.where(has_cloud & low, 5.0 + 195.0 * uniform(c, F_CLD_LWP, jm), 0.0)
+    ciwp = np.where(has_cloud & (~low | mixed), 1.0 + 49.0 * uniform(c, F_CLD_IWP, jm), 0.0)
+    reliq = RADLIQ_LWR + (RADLIQ_UPR - RADLIQ_LWR) * uniform(c, F_CLD_RELIQ, jm)
+    reice = RADICE_LWR + (RADICE_UPR - RADICE_LWR) * uniform(c, F_CLD_REICE, jm)
+    return tuple(np.ascontiguousarray(a) for a in (clwp, ciwp, reliq, reice))
+
+
+def cloud_lut(nband, nsize_liq, nsize_ice, nrghice):
+    """Smooth analytic cloud-optics tables in the layout of ``CloudOptics.load_lut``: a dict with the radius bounds
+    ``radliq_lwr``, ``radliq_upr``, ``radice_lwr``, ``radice_upr`` (microns), the liquid tables ``lut_extliq``,
+    ``lut_ssaliq``, ``lut_asyliq`` ``(nband, nsize_liq)`` and the ice tables ``lut_extice``, ``lut_ssaice``, ``lut_asyice``
+    ``(nrghice, nband, nsize_ice)``, float64.  ``ext`` (m2 g-1) falls with the size like 1.5/r (liquid) or 1.6/r (ice)
+    times a band factor, ``ssa`` lies in (0.5, 1) and falls with size and band, ``asy`` in (0.7, 0.95) and rises with size;
+    rougher ice is a little less forward-scattering.  Every quantity is strictly monotonic in the size, so the slope is
+    non-zero in every interval and a wrong index or a wrong weight shows."""
+    band = (np.arange(nband, dtype=np.float64)[:, None] + 1.0) / nband   # (0, 1]
+
+    def tables(r_lwr, r_upr, nsize, c_ext, rough):
+        r = np.linspace(r_lwr, r_upr, nsize)[None, :]
+        x = (r - r_lwr) / (r_upr - r_lwr)                                # [0, 1]
+        ext = c_ext / r * (0.8 + 0.4 * band)
+        ssa = 0.99 - 0.4 * band * (0.3 + 0.7 * x) - 0.02 * rough
+        asy = 0.74 + 0.18 * x + 0.02 * band - 0.015 * rough
+        return ext, ssa, asy
+
+    liq = tables(RADLIQ_LWR, RADLIQ_UPR, nsize_liq, 1.5, 0.0)
+    ice = [tables(RADICE_LWR, RADICE_UPR, nsize_ice, 1.6, float(k) / max(1, nrghice)) for k in range(nrghice)]
+    out = dict(radliq_lwr=RADLIQ_LWR, radliq_upr=RADLIQ_UPR, radice_lwr=RADICE_LWR, radice_upr=RADICE_UPR)
+    for i, q in enumerate(("ext", "ssa", "asy")):
+        out["lut_" + q + "liq"] = np.ascontiguousarray(liq[i])
+        out["lut_" + q + "ice"] = np.ascontiguousarray(np.stack([t[i] for t in ice]))
+    return out
+
+
 def gas_items(cols):
     """[(name, array, col_stride, lay_stride)] in GAS_ORDER for oracle-style consumers: full
     arrays are (nlay,ncol) -> strides (1,ncol); per-column arrays (1,0); scalars (0,0)."""
