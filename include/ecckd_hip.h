@@ -1039,6 +1039,11 @@ int ecckd_get_arithmetic(void);
  *                            the longwave call (fp64: gas optics + rte_lw 1.0-1.4 % faster at 1e6 columns, 1.2-1.9 % at 1e5;
  *                            fp32 3-6 %) and in the shortwave call (2.3-2.8 % at 1e5 columns), 0 in
  *                            ecckd_gas_optics_lw_tau, where it costs 1-2 % of the kernel.  The same bits either way ("Address translation")
+ *   "gas_input_ahead"        fused gas-optics kernel, longwave mode (both precisions): 1 a wave loads the per-column inputs of
+ *                            its next tile of columns before it starts the stores of the tile in hand, 0 it loads them at the
+ *                            top of the tile, behind those stores; -1 (default) what measured faster: 1 in fp64 (gas optics + rte_lw
+ *                            0.5-0.9 % faster at 1e6 columns than with 0), 0 in fp32 (where 1 costs 3-4 %).  The shortwave and
+ *                            tau-only modes ignore the option.  The same bits either way ("Layer-edge sources")
  * --------------------------------------------------------------------------------------- */
 int ecckd_set_solver_option(const char *name, double value);
 int ecckd_get_solver_option(const char *name, double *value);

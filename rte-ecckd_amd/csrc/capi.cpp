@@ -240,6 +240,10 @@ struct SolverOptions {
   // run free, -1 (default) = per mode as measured ("Address translation", profiles/gas_tile_sync.json):
   // on in the longwave mode (fp64 and fp32) and in the shortwave mode, off in the tau-only mode
   std::atomic<int> gas_tile_sync{-1};
+  // fused gas-optics kernel, longwave mode (the 512-thread instantiations): 1 = a wave loads the per-column inputs of its next
+  // tile before the chunk loops of the tile in hand (same bits), 0 = at the top of the tile, -1 (default) = per mode as
+  // measured ("Layer-edge sources", profiles/gas_lean.json)
+  std::atomic<int> gas_input_ahead{-1};
   std::atomic<int> sw_solver{0};   // 0 layer-systolic (kernels_rte_sw_sys.hip; up to 60 layers), 1 per-lane two-pass kernel
   // ecckd_lw_fluxes_clear_allsky at 60 layers: 0 the clear-sky and the all-sky kernel one after the other, 1 the dual-sky
   // kernel (rte_lw_split_both_kernel); same bits.  1: its min-max range lies below that of 0 at every 60-layer shape and
@@ -248,6 +252,9 @@ struct SolverOptions {
   std::atomic<int> lw_jac_inline{1};   // (the inline form lies wholly below the stand-alone route at every 60-layer shape)
 };
 SolverOptions g_opt;
+// "gas_input_ahead" = -1: what the measurement chose in fp64 (on: the headline wins) and in fp32 (off: 3 % slower with it);
+// the option only reaches the longwave mode ("Layer-edge sources")
+constexpr int kGasInputAheadDefault[2] = {1, 0};
 
 // lw_tau_thresh in effect: the option, or sqrt(epsilon(1._wp)) of the working precision
 double lw_tau_thresh(bool f32) {
@@ -433,6 +440,8 @@ int gas_optical_depth_dev(const ecckd_model *m, bool f32, PlanRecord *plan, int 
       {
         const int sync = g_opt.gas_tile_sync.load();
         fa.tile_sync = sync >= 0 ? sync : (fa.mode != 0 ? 1 : 0);
+        const int ahead = g_opt.gas_input_ahead.load();
+        fa.input_ahead = ahead >= 0 ? ahead : kGasInputAheadDefault[f32 ? 1 : 0];
       }
       // fp64 over the float32 image of the tables in LDS ("gas_slab_f32": 0 never, 1 always, 2 where the probe finds the
       // columns spread over many pressure rows); the probe's counter is a word that belongs to this stream
@@ -809,9 +818,14 @@ int ecckd_set_solver_option(const char *name, double value) {
       return fail("ecckd_set_solver_option: gas_tile_sync must be 0 (off), 1 (a block barrier per tile) or -1 (the default of each mode)");
     g_opt.gas_tile_sync.store((int)value);
   }
+  else if (n == "gas_input_ahead") {
+    if (value != 0. && value != 1. && value != -1.)
+      return fail("ecckd_set_solver_option: gas_input_ahead must be 0 (inputs loaded at the top of a tile), 1 (a tile ahead) or -1 (the default of each mode)");
+    g_opt.gas_input_ahead.store((int)value);
+  }
   else return fail("ecckd_set_solver_option: unknown option '" + n + "' (lw_tau_thresh, lw_series_terms, "
                    "lw_inc_flux_isotropic, sw_k_floor, sw_dir_clamp, lw_solver, lw_split_seg, gas_merge_scalars, lw_tail_split, "
-                   "sw_tail_split, sw_solver, gas_slab_f32, gas_tile_sync, lw_both_skies, lw_jac_inline)");
+                   "sw_tail_split, sw_solver, gas_slab_f32, gas_tile_sync, gas_input_ahead, lw_both_skies, lw_jac_inline)");
   return 0;
 }
 
@@ -831,6 +845,7 @@ int ecckd_get_solver_option(const char *name, double *value) {
   else if (n == "sw_solver") *value = g_opt.sw_solver.load();
   else if (n == "gas_slab_f32") *value = g_opt.gas_slab_f32.load();
   else if (n == "gas_tile_sync") *value = g_opt.gas_tile_sync.load();
+  else if (n == "gas_input_ahead") *value = g_opt.gas_input_ahead.load();
   else if (n == "lw_both_skies") *value = g_opt.lw_both_skies.load();
   else if (n == "lw_jac_inline") *value = g_opt.lw_jac_inline.load();
   else return fail("ecckd_get_solver_option: unknown option '" + n + "'");

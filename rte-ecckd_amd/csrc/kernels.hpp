@@ -87,6 +87,8 @@ struct FusedArgs {
   int choose_total;            // (set by launch_gas_fused) waves of 64 columns in the call
   int mode;                    // 0 tau only, 1 longwave (tau + Planck sources), 2 shortwave epilogue
   int tile_sync;               // "gas_tile_sync": 1 = the waves of a block meet at an execution barrier before every tile
+  int input_ahead;             // "gas_input_ahead": 1 = a wave loads the per-column inputs of its next tile before the chunk loops
+                               // of the tile in hand (512-thread instantiations; the others ignore it)
   int ntp;
   int pw;                      // Planck rows staged in LDS (ntp, or a window); filled by launch_gas_fused
   const double *planck;        // (ng,ntp) device
@@ -334,6 +336,9 @@ int merge_scalar_gases(TauArgs &t, int f32);
 int fused_slab_rows(int ng, int np, int nt, int nbil, int nv_lut, int pl_rows, int min_rows, int anyclamp, int f32, int block = 0);   // block: threads per block (0: the default 512)
 int fused_planck_rows(int ng, int np, int nt, int nbil, int nv_lut, int ntp, int anyclamp, int f32);
 hipError_t launch_gas_fused(FusedArgs &a, hipStream_t s);
+// planck_edge_kernel (kernels_planck.hip): the sources of a fused longwave launch that belong to no layer -- sfc_source and,
+// with tlev, lev_source_dec of storage layer 0; launch_gas_fused calls it once per longwave call, on the same stream
+hipError_t launch_planck_edge(const FusedArgs &a, hipStream_t s);
 hipError_t launch_planck(PlanckArgs &a, hipStream_t s);
 // the Planck sources as a stand-alone fast kernel (paired 16-byte stores)
 hipError_t launch_planck_pair(const PlanckArgs &a, int f32, hipStream_t s);

@@ -8,7 +8,10 @@
 // Why one kernel: the interpolation is bound by fp64 VALU issue (61 fp64 operations and 21 16-byte
 // LDS reads per cell pair), the Planck sources by HBM stores (24 B/cell).  Run back to back they
 // take the sum; fused, most of the arithmetic hides under the stores (32 B/cell written: tau,
-// lay_source, lev_source_inc, lev_source_dec).
+// lay_source, lev_source_inc, lev_source_dec).  The kernel writes what belongs to a layer: a block of layer j stores
+// lev_source_dec of layer j+1.  The two sources that belong to no layer -- sfc_source and lev_source_dec of the first layer
+// -- are planck_edge_kernel's (kernels_planck.hip), which launch_gas_fused puts on the stream behind this kernel: as work
+// of the blocks of the first layer they cost every block 32 VGPRs, 36 B of scratch and half the compile time.
 //
 // Arithmetic ("fast" mode, the default): the four (eight) interpolation weights of a cell are
 // multiplied out once per (column,layer) and every coefficient costs one FMA,
@@ -73,8 +76,8 @@ __device__ __forceinline__ void static_for(F &&f) {
 }
 
 // Order of the items of a chunk.  Item INDICES are: [0, NLI) look_up_table gas (g-pair p, vmr plane h: index 2p + h),
-// [NLI, NLI+NBI) bilinear slots, then NPI Planck items (g-pair p: index p; first layer only: NP2 + p).  Every g-pair ends
-// in stores: tau once its last slot is in, three or four source planes per Planck item.  The sequence: all look_up_table
+// [NLI, NLI+NBI) bilinear slots, then NPI Planck items (g-pair p: index p).  Every g-pair ends
+// in stores: tau once its last slot is in, three source planes per Planck item.  The sequence: all look_up_table
 // items, then the bilinear items (slot outer, g-pair inner) with the Planck items spread between them.  Against all
 // Planck items at the end (the stores of a chunk in one burst of 16-20 KiB per wave) that measured -0.4 % in fp64 and
 // -5.5 % in fp32; g-pair-major order (four stores every tenth item) spilled 29 VGPRs in the 8-g-point double
@@ -363,11 +366,17 @@ __global__ void __launch_bounds__(BLOCK, (BLOCK > 512 ? 3 : sizeof(real) == 4 ? 
     }
     __syncthreads();
 
-    // The per-column inputs of a tile, one round of global loads.  (Loading them a tile ahead, before
-    // the stores of the tile in flight -- vector memory operations retire in order, so a load issued
-    // after a tile's 64 stores waits for all of them -- measured +1-2 % as long as the 26 extra VGPRs
-    // did not spill; with the slab-position logic in the kernel they do, and it measures -3 %.)
-    real nx_p0, nx_p1, nx_T, nx_W[NB], nx_vlut, nx_Tl0 = real(0), nx_Tl1 = real(0);
+    // The per-column inputs of a tile, one round of global loads: 14 values in the headline shape.
+    // "gas_input_ahead": a wave issues the loads of its NEXT tile once the set-up of the tile in hand has consumed nx_*, and
+    // holds the values across the chunk loops -- vector memory operations retire in order, so a load issued at the top of
+    // a tile, after the previous tile's 64 stores, waits for all of them and then for its own round trip; issued a tile
+    // ahead, only the first wait is left.  It pays while the values stay in registers (round 1: +1-2 %; with first-layer
+    // code in the kernel every later attempt spilled and lost: DESIGN.md section 5.1, section 8), so it is compiled into
+    // the 512-thread instantiations only -- the 768-thread ones sit at their cap of 168 VGPRs.  Beyond the last tile of
+    // the loop the column is clamped (cc32): nothing is read out of bounds, and the values are dropped.
+    constexpr bool kAhead = BLOCK == 512;
+    real nx_p0, nx_p1, nx_T, nx_W[NB], nx_vlut, nx_Tl1 = real(0);
+    bool nx_loaded = false;   // nx_* hold the inputs of the tile about to start (wave-uniform)
     auto load_inputs = [&](long tile) {
       const long c = tile * kBlock + wcol;
       const unsigned cc32 = (unsigned)(c < ncol ? c : (long)ncol - 1);
@@ -378,17 +387,14 @@ __global__ void __launch_bounds__(BLOCK, (BLOCK > 512 ? 3 : sizeof(real) == 4 ? 
 #pragma unroll
       for (int s = 0; s < NB; ++s) nx_W[s] = *reinterpret_cast<greal_t *>(slot_base[s] + cc32 * slot_cs[s]);
       nx_vlut = *reinterpret_cast<greal_t *>(slot_base[NB] + cc32 * slot_cs[NB]);
-      if (MODE == MODE_LW && a.tlev) {
-        nx_Tl0 = at(P(a.tlev) + (long)ncol * j);
-        nx_Tl1 = at(P(a.tlev) + (long)ncol * (j + 1));
-      }
+      if (MODE == MODE_LW && a.tlev) nx_Tl1 = at(P(a.tlev) + (long)ncol * (j + 1));
     };
 
     for (long tile = seg; tile < seg_end; ++tile) {
       // "gas_tile_sync": the waves of the block meet once per tile, so that they walk the tile's output planes (4 KiB per
       // plane and block, 512 B of it per wave) together instead of drifting apart over the segment.  Every wave passes
       // this barrier exactly once per (segment, slab position, tile), because it stands before anything a wave decides for
-      // itself (the `own` early-out, fast / lowest, masked / first-layer chunk loops) and the trip counts of the three
+      // itself (the `own` early-out, fast / lowest, masked or unmasked chunk loop) and the trip counts of the three
       // enclosing loops are the same in every thread of the block:
       //   seg, seg_end <- t_begin, t_end (blockIdx.x, gridDim.x, ncol: block-uniform) and t.seg (kernel argument);
       //   npos         <- R (kernel argument) and ipmin, ipmax, which every thread computes with the same operations from
@@ -402,9 +408,10 @@ __global__ void __launch_bounds__(BLOCK, (BLOCK > 512 ? 3 : sizeof(real) == 4 ? 
       // instead of from `a`: as one more scalar held over the tile loop it costs the register allocator, which already
       // spills 100-250 scalars here, 148 more spilled SGPRs over the instantiations, a VGPR in four of them and scratch in
       // two; re-read per tile, the listings stay where the parent's are (profiles/gas_tile_sync_kernel_resources_*.txt).
+      // "gas_input_ahead" is read the same way, for the same reason.
+      typedef __attribute__((address_space(4))) const char karg_c;
+      typedef __attribute__((address_space(4))) const volatile int karg_i;
       {
-        typedef __attribute__((address_space(4))) const char karg_c;
-        typedef __attribute__((address_space(4))) const volatile int karg_i;
         const int tile_sync = *(karg_i *)((karg_c *)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(FusedArgs, tile_sync));
         if (tile_sync) __builtin_amdgcn_s_barrier();
       }
@@ -412,14 +419,15 @@ __global__ void __launch_bounds__(BLOCK, (BLOCK > 512 ? 3 : sizeof(real) == 4 ? 
       const bool valid = c < ncol;
       const bool upper = lane >= 32;        // this lane stores plane g+1 of its column pair
       const long cc = c < ncol ? c : (long)ncol - 1;
-      // ---- setup: one round of global loads ----
-      load_inputs(tile);
+      // ---- setup: one round of global loads (unless the previous trip issued them) ----
+      if (!(kAhead && nx_loaded)) load_inputs(tile);
+      nx_loaded = false;
       const real p0 = nx_p0, p1 = nx_p1, Tlayer = nx_T;
       real W[NB];        // per-slot vmr, then weight (:143-149); 0 for unused slots
 #pragma unroll
       for (int s = 0; s < NB; ++s) W[s] = nx_W[s];
       real vlut = nx_vlut;
-      const real Tl0 = nx_Tl0, Tl1 = nx_Tl1;
+      const real Tl1 = nx_Tl1;
 
       const PPoint<real> pp = pressure_point<real>(p0, p1, lp0, ud_dlp, np);
       const int ip0 = pp.ip0;
@@ -475,19 +483,17 @@ __global__ void __launch_bounds__(BLOCK, (BLOCK > 512 ? 3 : sizeof(real) == 4 ? 
         if (!ANYCLAMP) x = x < real(0) ? real(0) : x;   // od<0 -> 0 (:234-238) == weight<0 -> 0 for tables >= 0
         W[s] = x;
       }
-      PlPoint<real> qlay{0, 0, real(0), real(0)}, ql0{0, 0, real(0), real(0)}, ql1{0, 0, real(0), real(0)};
+      PlPoint<real> qlay{0, 0, real(0), real(0)}, ql1{0, 0, real(0), real(0)};
       bool inwin = true;
       if (MODE == MODE_LW) {
         qlay = planck_point<real>(Tlayer, pt0, ud_pdt, ntp);
         // level j+1 serves lev_source_inc(:,j,:) AND lev_source_dec(:,j+1,:) (the same level: :419-424), so a
-        // block evaluates ONE level per layer; the top level (lev_source_dec of layer 1) is the extra
-        // work of the blocks of the first layer.
-        ql0 = (a.tlev && j == 0) ? planck_point<real>(Tl0, pt0, ud_pdt, ntp) : qlay;
+        // block evaluates ONE level per layer; the top level (lev_source_dec of layer 1) and the surface source
+        // belong to no layer and are planck_edge_kernel's (kernels_planck.hip).
         ql1 = a.tlev ? planck_point<real>(Tl1, pt0, ud_pdt, ntp) : qlay;
-        const int rmin = min(qlay.row, min(ql0.row, ql1.row)), rmax = max(qlay.row, max(ql0.row, ql1.row));
+        const int rmin = min(qlay.row, ql1.row), rmax = max(qlay.row, ql1.row);
         inwin = rmin >= pw_lo && rmax + 1 <= pw_lo + PW - 1;
         qlay.off = (qlay.row - pw_lo) * L.SP;
-        ql0.off = (ql0.row - pw_lo) * L.SP;
         ql1.off = (ql1.row - pw_lo) * L.SP;
       }
       const real moles = dp * gw;   // :313-314 (SW)
@@ -499,15 +505,22 @@ __global__ void __launch_bounds__(BLOCK, (BLOCK > 512 ? 3 : sizeof(real) == 4 ? 
       const bool fast = !slow_wave;
       const bool active = own && inslab;
       const bool masked_wave = !__all(active);
-      const bool mine = slow_wave ? (lowest && valid) : active;   // lanes whose results this pass stores
       const int ip0_ = ip0, it0_ = it0, iv0_ = iv0;
+
+      if (kAhead) {   // nx_* are consumed: the next tile's inputs, ahead of this tile's stores
+        const int ahead = *(karg_i *)((karg_c *)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(FusedArgs, input_ahead));
+        if (ahead) {
+          load_inputs(tile + 1);
+          nx_loaded = true;
+        }
+      }
 
       if (fast) {
         // The g-point work of a chunk is a static sequence of "items" of at most four 16-byte LDS
         // reads (two consecutive g-points each):
         //   look_up_table gas : (g-pair, vmr plane h)   4 corner reads, 8 FMAs  -> partial / final od
         //   bilinear slot     : (slot, g-pair)          4 corner reads, 10 FMAs
-        //   Planck sources    : (g-pair)                layer + level j+1 (4 reads); first layer only: level j (2)
+        //   Planck sources    : (g-pair)                layer + level j+1 (4 reads)
         // software-pipelined by hand: the reads of item i+1 are issued before the arithmetic of item
         // i.  Reads are volatile (kept in program order, never paired into ds_read2_b64) and every
         // item ends in an empty asm that pins its results, otherwise instruction selection floats
@@ -517,7 +530,7 @@ __global__ void __launch_bounds__(BLOCK, (BLOCK > 512 ? 3 : sizeof(real) == 4 ? 
         constexpr int NP2 = GC / 2;                                  // g-pairs per chunk
         constexpr int NLI = 2 * NP2, NBI = NB * NP2;
         // LDS addresses (in elements): one register per corner row of the cell -- 4 for the bilinear slots, 8 for the
-        // look_up_table gas, 4 (6 in the first layer) for the Planck rows -- advanced once per chunk; everything
+        // look_up_table gas, 4 for the Planck rows -- advanced once per chunk; everything
         // inside a chunk is an immediate offset of the ds_read.  (Until round 2 the slot offset s*ngp was a run-time
         // value: 80 v_add_u32 per chunk of eight g-points.)
         const int ob = L.bil + (ipl + R * (it0 - 1)) * L.SB;
@@ -528,8 +541,7 @@ __global__ void __launch_bounds__(BLOCK, (BLOCK > 512 ? 3 : sizeof(real) == 4 ? 
         int ab[4] = {ES * ob, ES * (ob + dPb), ES * (ob + dTb), ES * (ob + dTb + dPb)};
         int al[8] = {ES * ol, ES * (ol + dPl), ES * (ol + dTl), ES * (ol + dTl + dPl),
                      ES * (ol + dVl), ES * (ol + dVl + dPl), ES * (ol + dVl + dTl), ES * (ol + dVl + dTl + dPl)};
-        int ap[6] = {ES * (L.pl + qlay.off), ES * (L.pl + qlay.off + L.SP), ES * (L.pl + ql1.off), ES * (L.pl + ql1.off + L.SP),
-                     ES * (L.pl + ql0.off), ES * (L.pl + ql0.off + L.SP)};
+        int ap[4] = {ES * (L.pl + qlay.off), ES * (L.pl + qlay.off + L.SP), ES * (L.pl + ql1.off), ES * (L.pl + ql1.off + L.SP)};
         const int cstride = ES * t.nbil * GC;   // a chunk of the bilinear row: [slot][GC]
         // Output addressing: a uniform plane pointer (SGPRs) plus ONE per-lane 32-bit byte
         // offset shared by all four arrays -- the lower half-wave writes column pairs of plane g, the upper
@@ -543,16 +555,14 @@ __global__ void __launch_bounds__(BLOCK, (BLOCK > 512 ? 3 : sizeof(real) == 4 ? 
         real *w_g = MODE == MODE_SW && t.ssa ? Q(t.g) + (long)ncol * j : nullptr;
         real *w_lay = MODE == MODE_LW ? Q(a.lay_source) + (long)ncol * j : nullptr;
         const bool has_next = j + 1 < nlay;
-        real *w_dec0 = MODE == MODE_LW && a.tlev ? Q(a.lev_source_dec) + (long)ncol * j : nullptr;          // first layer
         real *w_decn = MODE == MODE_LW && a.tlev ? Q(a.lev_source_dec) + (long)ncol * (j + 1) : nullptr;    // has_next
         real *w_inc = MODE == MODE_LW && a.tlev ? Q(a.lev_source_inc) + (long)ncol * j : nullptr;
         // Two copies of the chunk loop: with every lane owned (the common case) the stores are the
         // unconditional paired ones; the masked copy is for ragged waves and waves split between
         // slab positions.  A run-time flag instead costs a branch per store and ~2 % of the kernel.
-        auto chunks = [&](auto masked_c, auto first_c) __attribute__((always_inline)) {
+        auto chunks = [&](auto masked_c) __attribute__((always_inline)) {
         constexpr bool masked = decltype(masked_c)::value;
-        constexpr bool FIRST = decltype(first_c)::value;   // blocks of the first layer: the top level too
-        constexpr int NPI = (MODE == MODE_LW) ? (FIRST ? 2 * NP2 : NP2) : 0;
+        constexpr int NPI = (MODE == MODE_LW) ? NP2 : 0;
         constexpr int NIT = NLI + NBI + NPI;
         for (int gb = 0; gb < ngp; gb += GC) {
           real acc[GC];
@@ -581,7 +591,6 @@ __global__ void __launch_bounds__(BLOCK, (BLOCK > 512 ? 3 : sizeof(real) == 4 ? 
           asm volatile("" : "+v"(ab[0]), "+v"(ab[1]), "+v"(ab[2]), "+v"(ab[3]));
           asm volatile("" : "+v"(al[0]), "+v"(al[1]), "+v"(al[2]), "+v"(al[3]), "+v"(al[4]), "+v"(al[5]), "+v"(al[6]), "+v"(al[7]));
           if (MODE == MODE_LW) asm volatile("" : "+v"(ap[0]), "+v"(ap[1]), "+v"(ap[2]), "+v"(ap[3]));
-          if (MODE == MODE_LW && FIRST) asm volatile("" : "+v"(ap[4]), "+v"(ap[5]));
           double2_t buf[2][4];
           real lutp[2] = {real(0), real(0)};
           static_for<0, NIT + 1>([&](auto pos_c) __attribute__((always_inline)) {
@@ -596,17 +605,11 @@ __global__ void __launch_bounds__(BLOCK, (BLOCK > 512 ? 3 : sizeof(real) == 4 ? 
               constexpr int so = bil_slot(it - NLI, NP2) * GC + 2 * bil_pair(it - NLI, NP2);
               double2_t *b = buf[pos & 1];
               b[0] = ld2b(ab[0], so); b[1] = ld2b(ab[1], so); b[2] = ld2b(ab[2], so); b[3] = ld2b(ab[3], so);
-            } else if constexpr (it < NIT) {                // Planck sources of one g-pair
-              constexpr int k = it - NLI - NBI;
+            } else if constexpr (it < NIT) {                // Planck sources of one g-pair: layer and level j+1
+              constexpr int g = 2 * (it - NLI - NBI);
               double2_t *b = buf[pos & 1];
-              if constexpr (k < NP2) {                      // layer and level j+1
-                constexpr int g = 2 * k;
-                b[0] = ld2b(ap[0], g); b[1] = ld2b(ap[1], g);
-                b[2] = ld2b(ap[2], g); b[3] = ld2b(ap[3], g);
-              } else {                                      // first layer: level j
-                constexpr int g = 2 * (k - NP2);
-                b[0] = ld2b(ap[4], g); b[1] = ld2b(ap[5], g);
-              }
+              b[0] = ld2b(ap[0], g); b[1] = ld2b(ap[1], g);
+              b[2] = ld2b(ap[2], g); b[3] = ld2b(ap[3], g);
             }
             // ---------------- arithmetic of item `it - 1` ----------------
             if constexpr (pos >= 1) {
@@ -666,28 +669,20 @@ __global__ void __launch_bounds__(BLOCK, (BLOCK > 512 ? 3 : sizeof(real) == 4 ? 
                   }
                 }
               } else {
-                constexpr int k = pi_ - NLI - NBI;
-                constexpr int g = 2 * (k < NP2 ? k : k - NP2);
+                constexpr int g = 2 * (pi_ - NLI - NBI);
                 const int npl = FULL ? 2 : ng - (gb + g);   // planes of this pair that exist (see the tau stores)
-                if constexpr (k < NP2) {
-                  real vl[2], v1[2];
+                real vl[2], v1[2];
 #pragma unroll
-                  for (int q = 0; q < 2; ++q) {
-                    vl[q] = div_pi(qlay.w0 * (real)b[0][q] + qlay.w1 * (real)b[1][q], pi, rpi);
-                    v1[q] = div_pi(ql1.w0 * (real)b[2][q] + ql1.w1 * (real)b[3][q], pi, rpi);
+                for (int q = 0; q < 2; ++q) {
+                  vl[q] = div_pi(qlay.w0 * (real)b[0][q] + qlay.w1 * (real)b[1][q], pi, rpi);
+                  v1[q] = div_pi(ql1.w0 * (real)b[2][q] + ql1.w1 * (real)b[3][q], pi, rpi);
+                }
+                if (FULL || npl >= 1) {
+                  store_pair<real>(w_lay, plane2, voff, coff, vl[0], vl[1], masked, active, npl, upper);
+                  if (a.tlev) {                                                    // :423-424
+                    store_pair<real>(w_inc, plane2, voff, coff, v1[0], v1[1], masked, active, npl, upper);
+                    if (has_next) store_pair<real>(w_decn, plane2, voff, coff, v1[0], v1[1], masked, active, npl, upper);
                   }
-                  if (FULL || npl >= 1) {
-                    store_pair<real>(w_lay, plane2, voff, coff, vl[0], vl[1], masked, active, npl, upper);
-                    if (a.tlev) {                                                    // :423-424
-                      store_pair<real>(w_inc, plane2, voff, coff, v1[0], v1[1], masked, active, npl, upper);
-                      if (has_next) store_pair<real>(w_decn, plane2, voff, coff, v1[0], v1[1], masked, active, npl, upper);
-                    }
-                  }
-                } else {
-                  real v0[2];
-#pragma unroll
-                  for (int q = 0; q < 2; ++q) v0[q] = div_pi(ql0.w0 * (real)b[0][q] + ql0.w1 * (real)b[1][q], pi, rpi);
-                  if (a.tlev && (FULL || npl >= 1)) store_pair<real>(w_dec0, plane2, voff, coff, v0[0], v0[1], masked, active, npl, upper);
                 }
               }
             }
@@ -697,14 +692,10 @@ __global__ void __launch_bounds__(BLOCK, (BLOCK > 512 ? 3 : sizeof(real) == 4 ? 
 #pragma unroll
           for (int q = 0; q < 8; ++q) al[q] += ES * GC;
 #pragma unroll
-          for (int q = 0; q < 6; ++q) ap[q] += ES * GC;
+          for (int q = 0; q < 4; ++q) ap[q] += ES * GC;
         }
         };
-        if (j == 0) {
-          if (masked_wave) chunks(std::true_type{}, std::true_type{}); else chunks(std::false_type{}, std::true_type{});
-        } else {
-          if (masked_wave) chunks(std::true_type{}, std::false_type{}); else chunks(std::false_type{}, std::false_type{});
-        }
+        if (masked_wave) chunks(std::true_type{}); else chunks(std::false_type{});
       } else if (lowest) {
         // ---- a lane of this wave is outside the staged rows: tables from global memory ----
         // (the indices go through an opaque asm: otherwise the 64-bit address arithmetic of this
@@ -761,25 +752,14 @@ __global__ void __launch_bounds__(BLOCK, (BLOCK > 512 ? 3 : sizeof(real) == 4 ? 
             if (MODE == MODE_LW) {
               const real *pg = P(a.planck) + g;   // table rows from global memory: any row, staged or not
               Q(a.lay_source)[o] = div_pi(qlay.w0 * pg[(long)qlay.row * ng] + qlay.w1 * pg[(long)(qlay.row + 1) * ng], pi, rpi);
-              if (a.tlev) {   // level j+1 -> inc of this layer and dec of the next; the top level by the first layer
+              if (a.tlev) {   // level j+1 -> inc of this layer and dec of the next
                 const real v1 = div_pi(ql1.w0 * pg[(long)ql1.row * ng] + ql1.w1 * pg[(long)(ql1.row + 1) * ng], pi, rpi);
                 Q(a.lev_source_inc)[o] = v1;
                 if (j + 1 < nlay) Q(a.lev_source_dec)[o + ncol] = v1;
-                if (j == 0)
-                  Q(a.lev_source_dec)[o] = div_pi(ql0.w0 * pg[(long)ql0.row * ng] + ql0.w1 * pg[(long)(ql0.row + 1) * ng], pi, rpi);
               }
             }
           }
         }
-      }
-
-      // ---- surface source (:408-413), by the blocks of the first layer ----
-      if (MODE == MODE_LW && j == 0 && mine) {
-        // (table rows from global memory: the surface temperature is not part of the window range)
-        const PlPoint<real> qs = planck_point<real>(P(a.tsfc)[c], pt0, ud_pdt, ntp);
-        const real *p0r = P(a.planck) + (long)qs.row * ng, *p1r = p0r + ng;
-        for (int g = 0; g < ng; ++g)
-          Q(a.sfc_source)[c + (long)ncol * g] = div_pi(qs.w0 * p0r[g] + qs.w1 * p1r[g], pi, rpi);
       }
     }
     }   // slab positions
@@ -1015,7 +995,21 @@ hipError_t prepare_gas_fused(FusedArgs &a, FusedPlan &plan) {
   return hipSuccess;
 }
 
+namespace {
+hipError_t launch_gas_fused_layers(FusedArgs &a, hipStream_t s);
+}
+
+// The longwave mode is two kernels on the stream: gas_fused_kernel for everything that belongs to a layer, then
+// planck_edge_kernel for sfc_source and the top plane of lev_source_dec -- once per call, whichever of the fp64-slab and
+// float32-image forms the spread probe picks.
 hipError_t launch_gas_fused(FusedArgs &a, hipStream_t s) {
+  const hipError_t e = launch_gas_fused_layers(a, s);
+  if (e != hipSuccess || a.mode != MODE_LW) return e;
+  return launch_planck_edge(a, s);   // (a.ud_pdt: filled by prepare_gas_fused)
+}
+
+namespace {
+hipError_t launch_gas_fused_layers(FusedArgs &a, hipStream_t s) {
   FusedPlan plan;
   if (a.slab32 == 2) {   // auto: spread probe, then both forms; the one the probe does not choose returns at once
     FusedArgs b = a;
@@ -1053,5 +1047,6 @@ hipError_t launch_gas_fused(FusedArgs &a, hipStream_t s) {
   if (a.mode == MODE_SW) return launch_mode<double, MODE_SW>(a, plan.lds_bytes, pick_nb(t.nbil), anyclamp, s);
   return launch_mode<double, MODE_TAU>(a, plan.lds_bytes, pick_nb(t.nbil), anyclamp, s);
 }
+}  // namespace
 
 }  // namespace ecckd

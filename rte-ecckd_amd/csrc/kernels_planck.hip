@@ -247,7 +247,72 @@ __global__ void __launch_bounds__(kPpBlock) planck_pair_kernel(const PlanckArgs 
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// The two Planck sources that belong to no layer, beside gas_fused_kernel in the longwave mode (launch_gas_fused):
+// sfc_source(:, g) from tsfc (:408-413) and -- with tlev -- lev_source_dec(:, 1, :) from the first level of the arrays
+// (:419-424; storage layer 0, whatever top_at_1 later says).  The fused kernel used to leave both to the blocks of its
+// first layer, and every block of the other 59 carried the code: a third interpolation point, two LDS address registers, a
+// fifteenth per-tile load, two more copies of the chunk loop and this loop over g-points.
+// Lane -> column, blockIdx.y = 0 the surface, 1 the top level, blockIdx.z a group of 8 g-points; 2 x ng x ncol values,
+// 8-byte nontemporal stores that are coalesced along the columns.  The table's rows come from global memory (L2: 59 KiB for 32 g-points), two g-points per
+// load; interpolation point, expression and order are the fused kernel's (wave_pair.hpp): the same bits.
+constexpr int kPeBlock = 256;
+constexpr int kPeGroup = 8;   // g-points per thread (even)
+
+template <typename real>
+__global__ void __launch_bounds__(kPeBlock) planck_edge_kernel(const real *planck, int ng, int ntp, real t0, const UDiv ud_dt_h, int ncol,
+                                                               int nlay, const real *tsfc, const real *tlev, real *sfc_source,
+                                                               real *lev_source_dec) {
+  typedef real real2_u __attribute__((ext_vector_type(2), aligned(sizeof(real))));   // (a row starts at any element)
+  const long c = (long)blockIdx.x * kPeBlock + threadIdx.x;
+  if (c >= ncol) return;
+  const bool top = blockIdx.y != 0;
+  const UDivT<real> ud_dt = make_udiv_t<real>(ud_dt_h);
+  const real pi = (real)3.14159265359f, rpi = real(1) / pi;   // src/gas_optics_ecckd.f90:53
+  const PlPoint<real> q = planck_point<real>(top ? tlev[c] : tsfc[c], t0, ud_dt, ntp);
+  const real *p0r = planck + (long)q.row * ng, *p1r = p0r + ng;
+  // plane g of the output: sfc_source(c, g), lev_source_dec(c, 0, g)
+  real *out = (top ? lev_source_dec : sfc_source) + c;
+  const long plane = top ? (long)ncol * nlay : (long)ncol;
+  // blockIdx.z: a group of kPeGroup g-points, all of its loads in flight at once (the kernel is a chain of L2 round trips)
+  const int g0 = blockIdx.z * kPeGroup, g1 = g0 + kPeGroup < ng ? g0 + kPeGroup : ng;
+  real2_u b0[kPeGroup / 2], b1[kPeGroup / 2];
+#pragma unroll
+  for (int p = 0; p < kPeGroup / 2; ++p) {
+    const int g = g0 + 2 * p;
+    if (g + 1 < g1) {
+      b0[p] = *reinterpret_cast<const real2_u *>(p0r + g);
+      b1[p] = *reinterpret_cast<const real2_u *>(p1r + g);
+    } else if (g < g1) {   // odd g-point count: the last one alone
+      b0[p][0] = p0r[g]; b0[p][1] = real(0);
+      b1[p][0] = p1r[g]; b1[p][1] = real(0);
+    }
+  }
+#pragma unroll
+  for (int p = 0; p < kPeGroup / 2; ++p) {
+    const int g = g0 + 2 * p;
+    if (g < g1) __builtin_nontemporal_store(div_pi(q.w0 * b0[p][0] + q.w1 * b1[p][0], pi, rpi), out + plane * g);
+    if (g + 1 < g1) __builtin_nontemporal_store(div_pi(q.w0 * b0[p][1] + q.w1 * b1[p][1], pi, rpi), out + plane * (g + 1));
+  }
+}
+
 }  // namespace
+
+// sfc_source and (tlev given) the top plane of lev_source_dec of a fused longwave launch; a.ud_pdt is filled
+hipError_t launch_planck_edge(const FusedArgs &a, hipStream_t s) {
+  const TauArgs &t = a.tau;
+  if (t.ncol <= 0 || t.nlay <= 0) return hipSuccess;
+  const dim3 grid((unsigned)((t.ncol + kPeBlock - 1) / kPeBlock), a.tlev ? 2 : 1, (unsigned)((t.ng + kPeGroup - 1) / kPeGroup));
+  if (a.f32)
+    hipLaunchKernelGGL(planck_edge_kernel<float>, grid, dim3(kPeBlock), 0, s, reinterpret_cast<const float *>(a.planck), t.ng, a.ntp,
+                       (float)a.pt0, a.ud_pdt, t.ncol, t.nlay, reinterpret_cast<const float *>(a.tsfc),
+                       reinterpret_cast<const float *>(a.tlev), reinterpret_cast<float *>(a.sfc_source),
+                       reinterpret_cast<float *>(a.lev_source_dec));
+  else
+    hipLaunchKernelGGL(planck_edge_kernel<double>, grid, dim3(kPeBlock), 0, s, a.planck, t.ng, a.ntp, a.pt0, a.ud_pdt, t.ncol, t.nlay,
+                       a.tsfc, a.tlev, a.sfc_source, a.lev_source_dec);
+  return hipGetLastError();
+}
 
 size_t planck_pair_lds_bytes(int ng, int ntp, int f32) {
   return (f32 ? sizeof(float) : sizeof(double)) * (size_t)ntp * row_stride(ng + (ng & 1));

@@ -36,7 +36,7 @@ def short(name):
         return "rte_sw" + ("_f32" if m.group(1) == "float" else "") + ("_fused" if m.group(2) == "true" else "")
     if "rte_sw_kernel" in name:
         return "rte_sw_two_pass"
-    for key in ("tau_kernel", "planck_kernel", "toa_src_kernel", "lw_gpt_kernel", "sw_gpt_kernel"):
+    for key in ("tau_kernel", "planck_edge_kernel", "planck_kernel", "toa_src_kernel", "lw_gpt_kernel", "sw_gpt_kernel"):
         if key in name:
             return key.replace("_kernel", "")
     return None
