@@ -134,8 +134,40 @@ int ecckd_model_get_device(const ecckd_model_t *model);
  * table once (:358-373).
  * --------------------------------------------------------------------------------------- */
 
+/* ---------------------------------------------------------------------------------------
+ * Level buffer.  ecCKD's Planck level sources hold ONE value per level: the reference fills a
+ * (ncol,nlay+1,ngpt) buffer and copies it into both arrays (src/gas_optics_ecckd.f90:419-424).
+ * An entry point that takes lev_source_inc and lev_source_dec (ncol,nlay,ngpt) treats them as
+ * the two views of ONE array lev(ncol,nlay+1,ngpt) exactly when
+ *     lev_source_inc == lev_source_dec + ncol        (elements of the call's precision).
+ * Then
+ *     lev_source_dec(i,l,g) = lev[i + ncol*(l     + (nlay+1)*g)]
+ *     lev_source_inc(i,l,g) = lev[i + ncol*(l + 1 + (nlay+1)*g)]       (0-based i, l, g)
+ * i.e. both views have a g-plane stride of (nlay+1)*ncol instead of nlay*ncol, and
+ * lev_source_inc(:,l,:) IS lev_source_dec(:,l+1,:) in memory.  Two contiguous arrays of more
+ * than one plane at these addresses would overlap, so nothing else can be meant (with
+ * nlay*ngpt == 1 both readings name the same memory).  No signature changes; nothing has to be
+ * asserted by the caller.  A writer stores each level once, a reader reads it once: 24 instead of
+ * 32 B/cell on either side, and ncol*(nlay-1)*ngpt elements less memory.
+ *   Accept the form (fp64; ECCKD_DEVICE and ECCKD_MIXED):
+ *     ecckd_gas_optics_lw, ecckd_planck_sources (writers);
+ *     ecckd_rte_lw, ecckd_rte_lw_shared_levels, ecckd_rte_lw_inc_flux, ecckd_rte_lw_jac,
+ *     ecckd_rte_lw_byband (readers: the shared-levels kernels, the same fluxes bit for bit).
+ *   Refuse it (non-zero return, nothing written; ecckd_last_error() reads
+ *   "<entry point>: lev_source_inc == lev_source_dec + ncol names one level buffer
+ *   (ncol,nlay+1,ngpt); ... pass two separate arrays"):
+ *     every entry point with ECCKD_HOST ("host arrays (ECCKD_HOST) are not taken in that form"),
+ *     every *_f32 entry point ("single precision does not take that form"),
+ *     ecckd_rte_lw_2stream, ecckd_rte_lw_rescaled, ecckd_rte_lw_rescaled_jac and the *_gpt
+ *     solvers ("this entry point does not take that form").
+ * ecckd_has_level_buffer() returns 1: a caller that loads the library at run time can tell a
+ * build that knows the form from an older one (which would read and write overlapping arrays).
+ * --------------------------------------------------------------------------------------- */
+int ecckd_has_level_buffer(void);
+
 /* gas_optics_int (:381-426): tau, lay_source, lev_source_inc, lev_source_dec are
- * (ncol,nlay,ngpt), sfc_source is (ncol,ngpt).  `play` and `col_dry` are unused by the
+ * (ncol,nlay,ngpt), sfc_source is (ncol,ngpt); the two level arrays may be the views of one
+ * level buffer (above).  `play` and `col_dry` are unused by the
  * reference (:386,:394) and have no parameter.  tlev == NULL reproduces the reference:
  * tau, lay_source and sfc_source are written, then the call fails with
  * "tlev is required for ecckd" (:414-417).  Unlike the reference (:266-269 via :407) the

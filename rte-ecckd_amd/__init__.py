@@ -395,6 +395,24 @@ def _ptr(a, shape=None, what="array", f32=False):
     return C.c_void_p(a.ctypes.data)
 
 
+def _lev_ptrs(sources, shape, f32=False):
+    """Data pointers ``(lev_source_inc, lev_source_dec)`` of a source container for an entry point that takes the level
+    buffer (include/ecckd_hip.h): the pair is accepted when it is exactly the two views of one ``(ngpt, nlay+1, ncol)``
+    float64 tensor -- the data pointers one plane of columns apart, strides ``((nlay+1)*ncol, ncol, 1)`` -- and anything
+    else goes through ``_ptr`` (contiguous arrays only).  A container without ``level_views`` is read by attribute."""
+    views = getattr(sources, "level_views", None)
+    inc, dec = views() if views is not None else (sources.lev_source_inc, sources.lev_source_dec)
+    if inc is not None and dec is not None and not f32 and _is_torch(inc) and _is_torch(dec):
+        import torch
+        ng, nlay, ncol = shape
+        want = ((nlay + 1) * ncol, ncol, 1)
+        if (inc.dtype == torch.float64 and dec.dtype == torch.float64 and tuple(inc.shape) == tuple(shape)
+                and tuple(dec.shape) == tuple(shape) and tuple(inc.stride()) == want and tuple(dec.stride()) == want
+                and inc.data_ptr() - dec.data_ptr() == ncol * 8):
+            return C.c_void_p(inc.data_ptr()), C.c_void_p(dec.data_ptr())
+    return _ptr(inc, shape, "lev_source_inc", f32), _ptr(dec, shape, "lev_source_dec", f32)
+
+
 def _stream(space):
     if space == DEVICE:
         import torch
@@ -730,21 +748,78 @@ class CloudOptics:
 
 
 class SourceFuncLW:
-    """``ty_source_func_lw``: lay_source, lev_source_inc, lev_source_dec, sfc_source, sfc_source_jac."""
+    """``ty_source_func_lw``: lay_source, lev_source_inc, lev_source_dec, sfc_source, sfc_source_jac.
+
+    An allocated float64 device container holds ONE value per level, as ecCKD produces them
+    (src/gas_optics_ecckd.f90:419-424): ``alloc`` makes one tensor ``lev_source`` ``(ngpt, nlay+1, ncol)``, and the two
+    level arrays are its views ``lev_source[:, :-1]`` (dec) and ``lev_source[:, 1:]`` (inc) -- the "level buffer" of
+    include/ecckd_hip.h.  ``gas_optics`` / ``planck_sources`` then store each level once and ``rte_lw`` reads it once.
+    ``level_views()`` returns the two views; the library's own calls go through it.
+
+    Independent level sources (RRTMGP-style: two different values at a level) are assigned as the caller's own arrays,
+    or allocated with ``separate_levels=True``.  So that code written for two independent arrays keeps its meaning --
+    scaling both in place must not scale a level twice -- READING OR ASSIGNING ``lev_source_inc`` / ``lev_source_dec``
+    AS ATTRIBUTES FIRST TURNS THE VIEWS INTO TWO CONTIGUOUS ARRAYS OF THEIR VALUES (``separate_levels()``: one copy, once
+    per container, and the buffer is dropped); from then on the container behaves as one allocated with
+    ``separate_levels=True``.  Entry points that do not take the level buffer (two-stream, rescaled) do the same."""
 
     def __init__(self):
-        self.lay_source = self.lev_source_inc = self.lev_source_dec = self.sfc_source = self.sfc_source_jac = None
+        self.lay_source = self.sfc_source = self.sfc_source_jac = None
+        self._lev = None                 # the level buffer (ngpt, nlay+1, ncol), or None: two separate arrays
+        self._inc = self._dec = None     # the separate arrays (None while the buffer stands)
         self.levels_shared = False   # True after ecckd's gas_optics: one value per level (:419-424)
 
-    def alloc(self, ncol, nlay, spectral_desc, like=None):
+    def alloc(self, ncol, nlay, spectral_desc, like=None, separate_levels=False):
         ng = spectral_desc.get_ngpt()
         like = like if like is not None else np.empty(0)
         self.lay_source = _empty_like_space((ng, nlay, ncol), like)
-        self.lev_source_inc = _empty_like_space((ng, nlay, ncol), like)
-        self.lev_source_dec = _empty_like_space((ng, nlay, ncol), like)
+        self._lev = self._inc = self._dec = None
+        self.levels_shared = False
+        # one level buffer: float64 device tensors, and a library that knows the form (ECCKD_LIB may name an older build)
+        if (not separate_levels and _is_torch(like) and like.is_cuda and not _is_f32(like)
+                and hasattr(lib(), "ecckd_has_level_buffer")):
+            self._lev = _empty_like_space((ng, nlay + 1, ncol), like)
+        else:
+            self._inc = _empty_like_space((ng, nlay, ncol), like)
+            self._dec = _empty_like_space((ng, nlay, ncol), like)
         self.sfc_source = _empty_like_space((ng, ncol), like)
         self.sfc_source_jac = _empty_like_space((ng, ncol), like)   # (planck_sfc_source_jac fills it; float64 only)
         return ""
+
+    @property
+    def lev_source(self):
+        """The level buffer ``(ngpt, nlay+1, ncol)``, or None when the container holds two separate arrays."""
+        return self._lev
+
+    def level_views(self):
+        """``(lev_source_inc, lev_source_dec)`` as they stand: the two views of the level buffer, or the two arrays."""
+        if self._lev is not None:
+            return self._lev[:, 1:], self._lev[:, :-1]
+        return self._inc, self._dec
+
+    def separate_levels(self):
+        """Replace the two views by contiguous copies of their values and drop the buffer (no-op without one)."""
+        if self._lev is not None:
+            inc, dec = self.level_views()
+            self._inc, self._dec = inc.contiguous(), dec.contiguous()
+            self._lev = None
+        return self
+
+    @property
+    def lev_source_inc(self):
+        return self.separate_levels()._inc
+
+    @lev_source_inc.setter
+    def lev_source_inc(self, a):
+        self.separate_levels()._inc = a
+
+    @property
+    def lev_source_dec(self):
+        return self.separate_levels()._dec
+
+    @lev_source_dec.setter
+    def lev_source_dec(self, a):
+        self.separate_levels()._dec = a
 
 
 class FluxesBroadband:
@@ -957,8 +1032,7 @@ class GasOpticsEcckd:
         rc = fn(self._need(), ncol, nlay, P(plev, (nlay + 1, ncol), "plev"), P(tlay, (nlay, ncol), "tlay"),
                 P(tsfc, (ncol,), "tsfc"), P(tlev, (nlay + 1, ncol), "tlev"), n, names, ptrs, cs, ls, sc,
                 P(optical_props.tau, (ng, nlay, ncol), "tau"), P(sources.lay_source, (ng, nlay, ncol), "lay_source"),
-                P(sources.lev_source_inc, (ng, nlay, ncol), "lev_source_inc"),
-                P(sources.lev_source_dec, (ng, nlay, ncol), "lev_source_dec"),
+                *_lev_ptrs(sources, (ng, nlay, ncol), f32),
                 P(sources.sfc_source, (ng, ncol), "sfc_source"), space, _stream(space))
         sources.levels_shared = rc == 0 and tlev is not None
         return last_error() if rc else ""
@@ -972,8 +1046,7 @@ class GasOpticsEcckd:
             self._need(), ncol, nlay, _ptr(tlay, (nlay, ncol), "tlay"),
             None if tlev is None else _ptr(tlev, (nlay + 1, ncol), "tlev"), _ptr(tsfc, (ncol,), "tsfc"),
             _ptr(sources.lay_source, (ng, nlay, ncol), "lay_source"),
-            None if tlev is None else _ptr(sources.lev_source_inc, (ng, nlay, ncol), "lev_source_inc"),
-            None if tlev is None else _ptr(sources.lev_source_dec, (ng, nlay, ncol), "lev_source_dec"),
+            *((None, None) if tlev is None else _lev_ptrs(sources, (ng, nlay, ncol))),
             _ptr(sources.sfc_source, (ng, ncol), "sfc_source"), space, _stream(space))
         return last_error() if rc else ""
 
@@ -1445,6 +1518,8 @@ def _rte_lw_2stream(optical_props, top_at_1, sources, sfc_emis, fluxes, n_gauss_
     ng, nlay, ncol = optical_props.tau.shape
     b2g = np.ascontiguousarray(optical_props.band2gpt, dtype=np.int32)
     nband = b2g.shape[0]
+    if hasattr(sources, "separate_levels"):
+        sources.separate_levels()   # this entry point reads two separate arrays: a level buffer is copied out, once
     try:
         space = _space_of([optical_props.tau, optical_props.ssa, optical_props.g, sources.lev_source_inc, sources.lev_source_dec,
                            sources.sfc_source, sfc_emis, inc_flux, fluxes.flux_up, fluxes.flux_dn])
@@ -1482,6 +1557,8 @@ def _rte_lw_rescaled(optical_props, top_at_1, sources, sfc_emis, fluxes, n_gauss
     ng, nlay, ncol = optical_props.tau.shape
     b2g = np.ascontiguousarray(optical_props.band2gpt, dtype=np.int32)
     nband = b2g.shape[0]
+    if hasattr(sources, "separate_levels"):
+        sources.separate_levels()   # this entry point reads two separate arrays: a level buffer is copied out, once
     try:
         space = _space_of([optical_props.tau, optical_props.ssa, optical_props.g, sources.lay_source, sources.lev_source_inc,
                            sources.lev_source_dec, sources.sfc_source, sfc_emis, inc_flux, fluxes.flux_up, fluxes.flux_dn])
@@ -1521,6 +1598,8 @@ def rte_lw_rescaled_jac(optical_props, top_at_1, sources, sfc_emis, fluxes, flux
     ng, nlay, ncol = optical_props.tau.shape
     b2g = np.ascontiguousarray(optical_props.band2gpt, dtype=np.int32)
     nband = b2g.shape[0]
+    if hasattr(sources, "separate_levels"):
+        sources.separate_levels()   # this entry point reads two separate arrays: a level buffer is copied out, once
     try:
         space = _space_of([optical_props.tau, optical_props.ssa, optical_props.g, sources.lay_source, sources.lev_source_inc,
                            sources.lev_source_dec, sources.sfc_source, sources.sfc_source_jac, sfc_emis, inc_flux, fluxes.flux_up,
@@ -1605,9 +1684,8 @@ def rte_lw(optical_props, top_at_1, sources, sfc_emis, fluxes, n_gauss_angles=1,
         try:
             space = _space_of([optical_props.tau, sources.lay_source, sources.sfc_source_jac, sfc_emis, inc_flux, fluxes.flux_up,
                                fluxes.flux_dn, flux_up_jac])
-            a3 = [_ptr(a, (ng, nlay, ncol), w) for a, w in ((optical_props.tau, "tau"), (sources.lay_source, "lay_source"),
-                                                            (sources.lev_source_inc, "lev_source_inc"),
-                                                            (sources.lev_source_dec, "lev_source_dec"))]
+            a3 = [_ptr(a, (ng, nlay, ncol), w) for a, w in ((optical_props.tau, "tau"), (sources.lay_source, "lay_source"))]
+            a3 += _lev_ptrs(sources, (ng, nlay, ncol))
             a2 = [_ptr(sources.sfc_source, (ng, ncol), "sfc_source"), _ptr(sources.sfc_source_jac, (ng, ncol), "sfc_source_jac")]
             out = [_ptr(a, (nlay + 1, ncol), w) for a, w in ((fluxes.flux_up, "flux_up"), (fluxes.flux_dn, "flux_dn"),
                                                              (flux_up_jac, "flux_up_jac"))]
@@ -1629,8 +1707,7 @@ def rte_lw(optical_props, top_at_1, sources, sfc_emis, fluxes, n_gauss_angles=1,
         rc = (lib().ecckd_rte_lw_byband_f32 if f32 else lib().ecckd_rte_lw_byband)(
             int(dev), ncol, nlay, ng, int(bool(top_at_1)), int(n_gauss_angles), Pb(optical_props.tau),
             Pb(sources.lay_source, (ng, nlay, ncol), "lay_source"),
-            Pb(sources.lev_source_inc, (ng, nlay, ncol), "lev_source_inc"),
-            Pb(sources.lev_source_dec, (ng, nlay, ncol), "lev_source_dec"),
+            *_lev_ptrs(sources, (ng, nlay, ncol), f32),
             Pb(sources.sfc_source, (ng, ncol), "sfc_source"), nband, C.c_void_p(b2g.ctypes.data),
             Pb(sfc_emis, (ncol, nband), "sfc_emis"), Pb(fluxes.bnd_flux_up, (nband, nlay + 1, ncol), "bnd_flux_up"),
             Pb(fluxes.bnd_flux_dn, (nband, nlay + 1, ncol), "bnd_flux_dn"), opt(fluxes.flux_up, "flux_up"),
@@ -1646,8 +1723,7 @@ def rte_lw(optical_props, top_at_1, sources, sfc_emis, fluxes, n_gauss_angles=1,
         rc = (lib().ecckd_rte_lw_inc_flux_f32 if f32 else lib().ecckd_rte_lw_inc_flux)(
             int(dev), ncol, nlay, ng, int(bool(top_at_1)), int(n_gauss_angles), Pi(optical_props.tau),
             Pi(sources.lay_source, (ng, nlay, ncol), "lay_source"),
-            Pi(sources.lev_source_inc, (ng, nlay, ncol), "lev_source_inc"),
-            Pi(sources.lev_source_dec, (ng, nlay, ncol), "lev_source_dec"),
+            *_lev_ptrs(sources, (ng, nlay, ncol), f32),
             Pi(sources.sfc_source, (ng, ncol), "sfc_source"), nband, C.c_void_p(b2g.ctypes.data),
             Pi(sfc_emis, (ncol, nband), "sfc_emis"), Pi(inc_flux, (ng, ncol), "inc_flux"),
             Pi(fluxes.flux_up, (nlay + 1, ncol), "flux_up"), Pi(fluxes.flux_dn, (nlay + 1, ncol), "flux_dn"),
@@ -1657,8 +1733,7 @@ def rte_lw(optical_props, top_at_1, sources, sfc_emis, fluxes, n_gauss_angles=1,
     P = lambda a, shape=None, what="array": _ptr(a, shape, what, f32)
     rc = fn(int(dev), ncol, nlay, ng, int(bool(top_at_1)), int(n_gauss_angles), P(optical_props.tau),
             P(sources.lay_source, (ng, nlay, ncol), "lay_source"),
-            P(sources.lev_source_inc, (ng, nlay, ncol), "lev_source_inc"),
-            P(sources.lev_source_dec, (ng, nlay, ncol), "lev_source_dec"),
+            *_lev_ptrs(sources, (ng, nlay, ncol), f32),
             P(sources.sfc_source, (ng, ncol), "sfc_source"), nband, C.c_void_p(b2g.ctypes.data),
             P(sfc_emis, (ncol, nband), "sfc_emis"), P(fluxes.flux_up, (nlay + 1, ncol), "flux_up"),
             P(fluxes.flux_dn, (nlay + 1, ncol), "flux_dn"), space, _stream(space))

@@ -304,6 +304,7 @@ size_t vmr_extent(const GasDesc &gd, int j, int ncol, int nlay) {
 struct PlanckSide {
   const double *tlev, *tsfc;
   double *lay_source, *lev_inc, *lev_dec, *sfc_source;
+  long long lev_gstride = 0;   // g-plane stride of lev_inc / lev_dec, elements (level_pair()); 0: separate arrays, nlay*ncol
 };
 
 // Planck kernel arguments (fp64) for the sources of `pl`
@@ -316,6 +317,7 @@ ecckd::PlanckArgs planck_args(const ecckd_model *m, int ncol, int nlay, const do
   p.tlay = tlay; p.tlev = pl.tlev; p.tsfc = pl.tsfc;
   p.lay_source = pl.lay_source; p.lev_source_inc = pl.lev_inc; p.lev_source_dec = pl.lev_dec;
   p.sfc_source = pl.sfc_source;
+  p.lev_gstride = pl.lev_gstride;
   return p;
 }
 
@@ -434,6 +436,7 @@ int gas_optical_depth_dev(const ecckd_model *m, bool f32, PlanRecord *plan, int 
         fa.tlev = pl->tlev; fa.tsfc = pl->tsfc;
         fa.lay_source = pl->lay_source; fa.lev_source_inc = pl->lev_inc;
         fa.lev_source_dec = pl->lev_dec; fa.sfc_source = pl->sfc_source;
+        fa.lev_gstride = pl->lev_gstride;
         if (planck_done) *planck_done = true;
       }
       fa.f32 = f32;
@@ -491,6 +494,42 @@ int check_gas_optics_dims(int ncol, int nlay) {
   if (((size_t)ncol * (size_t)nlay + (size_t)ncol) * sizeof(double) >= (size_t)0xFFFFFFF0u)
     return fail("ecckd: ncol*(nlay+1) too large for one call (limit 2^29 elements): split the column range");
   return 0;
+}
+// ... and with one level buffer the level planes are (nlay+1)*ncol apart
+int check_level_buffer_dims(int ncol, int nlay) {
+  if (((size_t)ncol * (size_t)(nlay + 1) + (size_t)ncol) * sizeof(double) >= (size_t)0xFFFFFFF0u)
+    return fail("ecckd: ncol*(nlay+2) too large for one call on a level buffer (limit 2^29 elements): split the column range");
+  return 0;
+}
+
+// Level buffer (include/ecckd_hip.h, "Level buffer"): lev_source_inc == lev_source_dec + ncol, in elements of the call's
+// precision, names the two views of ONE array lev(ncol, nlay+1, ngpt) -- dec(:,l,:) = lev(:,l,:), inc(:,l,:) = lev(:,l+1,:),
+// both with a g-plane stride of (nlay+1)*ncol.  Two contiguous (ncol,nlay,ngpt) arrays at those addresses would overlap, so
+// nothing else can be meant.  Every entry point that takes the pair asks here: the g-plane stride of the two arrays, and
+// whether the levels are physically shared.  `accepts`: the entry point's kernels take the stride; the others, host arrays
+// (Stage copies nlay*ncol*ngpt contiguous elements per array) and single precision refuse the aliased pair.
+struct LevelPair {
+  long long gstride = 0;   // elements
+  bool shared = false;     // one level buffer: a writer stores each level once, a reader may read it once
+};
+int level_pair(const char *who, const void *inc, const void *dec, int ncol, int nlay, bool f32, int memspace, bool accepts,
+               LevelPair *out) {
+  out->gstride = (long long)ncol * nlay;
+  out->shared = false;
+  if (!inc || !dec || ncol <= 0) return 0;
+  if (static_cast<const char *>(inc) != static_cast<const char *>(dec) + (size_t)ncol * esz(f32)) return 0;
+  const std::string lead = std::string(who) + ": lev_source_inc == lev_source_dec + ncol names one level buffer (ncol,nlay+1,ngpt)";
+  if (memspace == ECCKD_HOST) return fail(lead + "; host arrays (ECCKD_HOST) are not taken in that form: pass two separate arrays");
+  if (f32) return fail(lead + "; single precision does not take that form: pass two separate arrays");
+  if (!accepts) return fail(lead + "; this entry point does not take that form: pass two separate arrays");
+  out->gstride = (long long)ncol * (nlay + 1);
+  out->shared = true;
+  return 0;
+}
+// the entry points whose kernels read two separate arrays
+int refuse_level_buffer(const char *who, const void *inc, const void *dec, int ncol, int nlay, int memspace) {
+  LevelPair lp;
+  return level_pair(who, inc, dec, ncol, nlay, false, memspace, false, &lp);
 }
 
 // Element counts of the arrays of a call: (ncol), (ncol,nlay), (ncol,nlay+1), and per g-point or band of each
@@ -1178,6 +1217,8 @@ static int gas_optics_lw_dev(const ecckd_model *m, bool f32, int ncol, int nlay,
   return planck_sources_dev(m, ncol, nlay, tlay, pl, stream);
 }
 
+int ecckd_has_level_buffer(void) { return 1; }
+
 int ecckd_planck_sources(const ecckd_model_t *m, int ncol, int nlay, const double *tlay, const double *tlev,
                          const double *tsfc, double *lay_source, double *lev_source_inc, double *lev_source_dec,
                          double *sfc_source, int memspace, void *stream) {
@@ -1188,7 +1229,10 @@ int ecckd_planck_sources(const ecckd_model_t *m, int ncol, int nlay, const doubl
   if (tlev && (!lev_source_inc || !lev_source_dec)) return fail("ecckd_planck_sources: null level sources");
   HIPCHK(hipSetDevice(m->device));
   if (ncol == 0) return 0;
-  const PlanckSide pl{tlev, tsfc, lay_source, lev_source_inc, lev_source_dec, sfc_source};
+  LevelPair lp;
+  if (level_pair("ecckd_planck_sources", tlev ? lev_source_inc : nullptr, lev_source_dec, ncol, nlay, false, memspace, true, &lp)) return 1;
+  if (lp.shared && check_level_buffer_dims(ncol, nlay)) return 1;
+  const PlanckSide pl{tlev, tsfc, lay_source, lev_source_inc, lev_source_dec, sfc_source, lp.gstride};
   return planck_sources_dev(m, ncol, nlay, tlay, pl, static_cast<hipStream_t>(stream));
 }
 
@@ -1265,6 +1309,9 @@ static int gas_optics_lw_impl(bool f32, const ecckd_model_t *m, int ncol, int nl
   const GasDesc gd{ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar};
   if (ncol == 0) return tlev ? 0 : fail("tlev is required for ecckd");
   if (memspace != ECCKD_DEVICE && memspace != ECCKD_HOST && memspace != ECCKD_MIXED) return fail("ecckd: bad memspace");
+  LevelPair lp;
+  if (level_pair("ecckd_gas_optics_lw", tlev ? lev_source_inc : nullptr, lev_source_dec, ncol, nlay, f32, memspace, true, &lp)) return 1;
+  if (lp.shared && check_level_buffer_dims(ncol, nlay)) return 1;
   // ECCKD_MIXED: inputs are host arrays (staged here), the (ncol,nlay,ngpt) / (ncol,ngpt) outputs are the caller's
   // device buffers: nothing but ~4 KB per column crosses the bus
   const Counts n(ncol, nlay, m->ng, m->nband);
@@ -1284,6 +1331,7 @@ static int gas_optics_lw_impl(bool f32, const ecckd_model_t *m, int ncol, int nl
         pl.lev_dec = st.out(lev_source_dec, n.lay_g, kBig, tlev != nullptr);
       }))
     return 1;
+  pl.lev_gstride = lp.gstride;
   if (gas_optics_lw_dev(m, f32, ncol, nlay, d_plev, d_tlay, d_gd, d_tau, pl, st.stream)) return 1;
   if (st.close()) return 1;   // (ECCKD_MIXED synchronises too: the solver call that follows runs on another stream)
   return tlev ? 0 : fail("tlev is required for ecckd");   // :414-417
@@ -1428,7 +1476,11 @@ static int rte_lw_impl(const Call &c, int device, int ncol, int nlay, int ngpt, 
   a.ncol = ncol; a.nlay = nlay; a.ng = ngpt; a.top_at_1 = top_at_1 ? 1 : 0;
   a.nband = nband;
   a.f32 = c.f32;
-  a.shared_levels = c.shared_levels;
+  // one level buffer behind the two arrays: its levels ARE shared, whichever entry point was called
+  LevelPair lp;
+  if (level_pair("ecckd_rte_lw", lev_source_inc, lev_source_dec, ncol, nlay, c.f32, memspace, true, &lp)) return 1;
+  a.shared_levels = c.shared_levels || lp.shared;
+  a.lev_gstride = lp.gstride;
   fill_lw_options(a, n_gauss_angles, c.f32);
   const size_t scratch = ecckd::rte_lw_scratch_bytes(ncol, nlay, ngpt);
   Stage st(device, memspace, stream, c.f32);
@@ -1694,6 +1746,7 @@ int ecckd_lw_solver_noscat_gpt(int device, int ncol, int nlay, int ngpt, int top
   if (nmus < 1 || nmus > 4 || !Ds || !weights) return fail("ecckd_lw_solver_noscat_gpt: 1..4 quadrature angles with Ds and weights");
   if (!tau || !lay_source || !lev_source_inc || !lev_source_dec || !sfc_emis || !sfc_src || !gpt_flux_up || !gpt_flux_dn)
     return fail("ecckd_lw_solver_noscat_gpt: null argument");
+  if (refuse_level_buffer("ecckd_lw_solver_noscat_gpt", lev_source_inc, lev_source_dec, ncol, nlay, memspace)) return 1;
   if (check_device(device)) return 1;
   if (ncol == 0) return 0;
   ecckd::RteGptArgs a{};
@@ -1766,6 +1819,7 @@ int ecckd_rte_lw_2stream(int device, int ncol, int nlay, int ngpt, int top_at_1,
   if (check_dims(ncol, nlay)) return 1;
   if (!tau || !ssa || !g || !lev_source_inc || !lev_source_dec || !sfc_source || !sfc_emis || !flux_up || !flux_dn)
     return fail("ecckd_rte_lw_2stream: null argument (only lay_source and inc_flux may be null)");
+  if (refuse_level_buffer("ecckd_rte_lw_2stream", lev_source_inc, lev_source_dec, ncol, nlay, memspace)) return 1;
   ecckd::RteLw2strArgs a{};
   if (fill_band_map(ngpt, nband, band2gpt, a.gpt2band)) return 1;
   if (lw_2stream_layers_fit(nlay)) return 1;
@@ -1804,6 +1858,7 @@ int ecckd_lw_solver_2stream_gpt(int device, int ncol, int nlay, int ngpt, int to
   if (ngpt < 1) return fail("ecckd_lw_solver_2stream_gpt: bad ngpt");
   if (!tau || !ssa || !g || !lev_source_inc || !lev_source_dec || !sfc_emis || !sfc_src || !gpt_flux_up || !gpt_flux_dn)
     return fail("ecckd_lw_solver_2stream_gpt: null argument (only lay_source and inc_flux may be null)");
+  if (refuse_level_buffer("ecckd_lw_solver_2stream_gpt", lev_source_inc, lev_source_dec, ncol, nlay, memspace)) return 1;
   if (memspace != ECCKD_DEVICE && memspace != ECCKD_HOST) return fail("ecckd: bad memspace");
   if (check_device(device)) return 1;
   if (ncol == 0) return 0;
@@ -2312,6 +2367,7 @@ static int rte_lw_rescaled_impl(int device, int ncol, int nlay, int ngpt, int to
   if (n_gauss_angles < 1 || n_gauss_angles > 4) return fail("rte_lw: have to ask for at least one quadrature point and no more than 4");
   if (!tau || !ssa || !g || !lay_source || !lev_source_inc || !lev_source_dec || !sfc_source || !sfc_emis || !flux_up || !flux_dn)
     return fail("ecckd_rte_lw_rescaled: null argument (only inc_flux may be null)");
+  if (refuse_level_buffer("ecckd_rte_lw_rescaled", lev_source_inc, lev_source_dec, ncol, nlay, memspace)) return 1;
   ecckd::RteLwArgs a{};
   if (fill_band_map(ngpt, nband, band2gpt, a.gpt2band)) return 1;
   if (memspace == ECCKD_MIXED) return fail("ecckd_rte_lw_rescaled: ECCKD_MIXED is not implemented (ECCKD_DEVICE or ECCKD_HOST)");
@@ -2378,6 +2434,7 @@ int ecckd_lw_solver_1rescl_gpt(int device, int ncol, int nlay, int ngpt, int top
   if (nmus < 1 || nmus > 4 || !Ds || !weights) return fail("ecckd_lw_solver_1rescl_gpt: 1..4 quadrature angles with Ds and weights");
   if (!tau || !ssa || !g || !lay_source || !lev_source_inc || !lev_source_dec || !sfc_emis || !sfc_src || !gpt_flux_up || !gpt_flux_dn)
     return fail("ecckd_lw_solver_1rescl_gpt: null argument (only inc_flux may be null)");
+  if (refuse_level_buffer("ecckd_lw_solver_1rescl_gpt", lev_source_inc, lev_source_dec, ncol, nlay, memspace)) return 1;
   if (memspace != ECCKD_DEVICE && memspace != ECCKD_HOST) return fail("ecckd: bad memspace");
   if (check_device(device)) return 1;
   if (ncol == 0) return 0;
@@ -3026,10 +3083,14 @@ static int rte_lw_byband_impl(bool f32, int device, int ncol, int nlay, int ngpt
   if (fill_band_map(ngpt, nband, band2gpt, map)) return 1;
   if (!bnd_flux_up || !bnd_flux_dn) return fail("ecckd_rte_lw_byband: null argument");
   const size_t n3 = (size_t)ncol * nlay, n2l = (size_t)ncol * (nlay + 1);
+  // (one level buffer: a band's sub-range of the two views is still the pair of views, at the buffer's g-plane stride)
+  LevelPair lp;
+  if (level_pair("ecckd_rte_lw_byband", lev_source_inc, lev_source_dec, ncol, nlay, f32, memspace, true, &lp)) return 1;
+  const size_t nl3 = (size_t)lp.gstride;
   for (int b = 0; b < nband; ++b) {
     const int g0 = band2gpt[2 * b] - 1, n = band2gpt[2 * b + 1] - g0;
     if (rte_lw_impl(Call{f32, b}, device, ncol, nlay, n, top_at_1, n_gauss_angles, el(tau, n3 * g0, f32),
-                    el(lay_source, n3 * g0, f32), el(lev_source_inc, n3 * g0, f32), el(lev_source_dec, n3 * g0, f32),
+                    el(lay_source, n3 * g0, f32), el(lev_source_inc, nl3 * g0, f32), el(lev_source_dec, nl3 * g0, f32),
                     el(sfc_source, (size_t)ncol * g0, f32), nband, nullptr, sfc_emis, nullptr,
                     el(bnd_flux_up, n2l * b, f32), el(bnd_flux_dn, n2l * b, f32), memspace, stream))
       return 1;

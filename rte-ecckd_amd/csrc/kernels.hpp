@@ -95,6 +95,9 @@ struct FusedArgs {
   double pt0, pdt;             // temperature_planck(1), (2)-(1)
   const double *tlev, *tsfc;   // tlev may be nullptr
   double *lay_source, *lev_source_inc, *lev_source_dec, *sfc_source;
+  long long lev_gstride;       // g-plane stride of the two level arrays, elements: nlay*ncol for separate arrays (0 means that),
+                               // (nlay+1)*ncol for the two views of one level buffer (include/ecckd_hip.h, "Level buffer"):
+                               // lev_source_inc == lev_source_dec + ncol, and each level is stored once
 };
 
 struct PlanckArgs {
@@ -104,6 +107,7 @@ struct PlanckArgs {
   const double *tlay, *tlev, *tsfc;    // tlev may be nullptr
   double *lay_source, *lev_source_inc, *lev_source_dec, *sfc_source;
   int lev_chunks;              // grid.y
+  long long lev_gstride;       // as FusedArgs::lev_gstride
 };
 
 struct RteLwArgs {
@@ -117,6 +121,8 @@ struct RteLwArgs {
   double *scratch;             // generic-nlay path only
   int f32;                     // 1: the data pointers address float arrays
   int shared_levels;           // 1: lev_source_inc(:,l,:) == lev_source_dec(:,l+1,:): each level is read once
+  long long lev_gstride = 0;   // g-plane stride of the two level arrays, elements: nlay*ncol (0 means that), or (nlay+1)*ncol
+                               // for the two views of one level buffer (then shared_levels is set: only those kernels take it)
   const double *inc_flux;      // (ncol,ng) incident diffuse flux at the top of the domain, or nullptr (none)
   // version switches of the un-pinned RTE-RRTMGP solver (ecckd_set_solver_option)
   double tau_thresh;           // lw_source_noscat: series below this optical depth (sqrt(epsilon) of the precision)

@@ -9,7 +9,9 @@
 // LDS reads per cell pair), the Planck sources by HBM stores (24 B/cell).  Run back to back they
 // take the sum; fused, most of the arithmetic hides under the stores (32 B/cell written: tau,
 // lay_source, lev_source_inc, lev_source_dec).  The kernel writes what belongs to a layer: a block of layer j stores
-// lev_source_dec of layer j+1.  The two sources that belong to no layer -- sfc_source and lev_source_dec of the first layer
+// lev_source_dec of layer j+1 -- as a second store of the level's value, or, when the two level arrays are the views of
+// one level buffer (include/ecckd_hip.h, "Level buffer"; FusedArgs::lev_gstride), as the SAME store: 24 B/cell written.
+// The two sources that belong to no layer -- sfc_source and lev_source_dec of the first layer
 // -- are planck_edge_kernel's (kernels_planck.hip), which launch_gas_fused puts on the stream behind this kernel: as work
 // of the blocks of the first layer they cost every block 32 VGPRs, 36 B of scratch and half the compile time.
 //
@@ -554,7 +556,15 @@ __global__ void __launch_bounds__(BLOCK, (BLOCK > 512 ? 3 : sizeof(real) == 4 ? 
         real *w_tau = Q(t.tau) + (long)ncol * j, *w_ssa = MODE == MODE_SW && t.ssa ? Q(t.ssa) + (long)ncol * j : nullptr;
         real *w_g = MODE == MODE_SW && t.ssa ? Q(t.g) + (long)ncol * j : nullptr;
         real *w_lay = MODE == MODE_LW ? Q(a.lay_source) + (long)ncol * j : nullptr;
-        const bool has_next = j + 1 < nlay;
+        // The level arrays have their own g-plane stride (FusedArgs::lev_gstride), so level j+1 is stored with its own
+        // running pointer step and its own per-lane offset.  One level buffer (stride (nlay+1)*ncol, lev_source_inc ==
+        // lev_source_dec + ncol): the store through w_inc IS lev_source_dec of layer j+1, and the second store goes.
+        // (fp64 only: the single-precision instantiations keep separate arrays, and the code they had)
+        constexpr bool kLevStride = MODE == MODE_LW && sizeof(real) == 8;
+        const unsigned lplane = kLevStride ? (unsigned)a.lev_gstride : plane;
+        const unsigned voff_lev = kLevStride ? (unsigned)sizeof(real) * ((unsigned)(c - (upper ? 1 : 0)) + (upper ? lplane : 0u)) : voff;
+        const long plane2_lev = 2L * lplane;
+        const bool has_next = j + 1 < nlay && lplane == plane;
         real *w_decn = MODE == MODE_LW && a.tlev ? Q(a.lev_source_dec) + (long)ncol * (j + 1) : nullptr;    // has_next
         real *w_inc = MODE == MODE_LW && a.tlev ? Q(a.lev_source_inc) + (long)ncol * j : nullptr;
         // Two copies of the chunk loop: with every lane owned (the common case) the stores are the
@@ -680,7 +690,7 @@ __global__ void __launch_bounds__(BLOCK, (BLOCK > 512 ? 3 : sizeof(real) == 4 ? 
                 if (FULL || npl >= 1) {
                   store_pair<real>(w_lay, plane2, voff, coff, vl[0], vl[1], masked, active, npl, upper);
                   if (a.tlev) {                                                    // :423-424
-                    store_pair<real>(w_inc, plane2, voff, coff, v1[0], v1[1], masked, active, npl, upper);
+                    store_pair<real>(w_inc, plane2_lev, voff_lev, coff, v1[0], v1[1], masked, active, npl, upper);
                     if (has_next) store_pair<real>(w_decn, plane2, voff, coff, v1[0], v1[1], masked, active, npl, upper);
                   }
                 }
@@ -754,8 +764,9 @@ __global__ void __launch_bounds__(BLOCK, (BLOCK > 512 ? 3 : sizeof(real) == 4 ? 
               Q(a.lay_source)[o] = div_pi(qlay.w0 * pg[(long)qlay.row * ng] + qlay.w1 * pg[(long)(qlay.row + 1) * ng], pi, rpi);
               if (a.tlev) {   // level j+1 -> inc of this layer and dec of the next
                 const real v1 = div_pi(ql1.w0 * pg[(long)ql1.row * ng] + ql1.w1 * pg[(long)(ql1.row + 1) * ng], pi, rpi);
-                Q(a.lev_source_inc)[o] = v1;
-                if (j + 1 < nlay) Q(a.lev_source_dec)[o + ncol] = v1;
+                const long lgs = a.lev_gstride, ol = cc + (long)ncol * j + lgs * g;   // (the level arrays' own g-plane stride)
+                Q(a.lev_source_inc)[ol] = v1;
+                if (j + 1 < nlay && lgs == (long)ncol * nlay) Q(a.lev_source_dec)[ol + ncol] = v1;   // one level buffer: the same word
               }
             }
           }
@@ -950,8 +961,13 @@ hipError_t prepare_gas_fused(FusedArgs &a, FusedPlan &plan) {
   }
   if (t.ncol <= 0 || t.nlay <= 0) { plan.empty = 1; return hipSuccess; }
   if (t.nseq > kTauPassGases) return hipErrorInvalidValue;
-  // store_pair() addresses a plane pair with a 32-bit byte offset
-  if (((size_t)t.ncol * (size_t)t.nlay + (size_t)t.ncol) * (a.f32 ? sizeof(float) : sizeof(double)) >= (size_t)0xFFFFFFF0u)
+  // separate level arrays unless the caller says otherwise (FusedArgs::lev_gstride); no single-precision level buffer
+  const size_t plane = (size_t)t.ncol * (size_t)t.nlay;
+  if (a.lev_gstride <= 0) a.lev_gstride = (long long)plane;
+  if (a.f32 && (size_t)a.lev_gstride != plane) return hipErrorInvalidValue;
+  // store_pair() addresses a plane pair with a 32-bit byte offset: the larger of the two strides counts
+  const size_t widest = (size_t)a.lev_gstride > plane ? (size_t)a.lev_gstride : plane;
+  if ((widest + (size_t)t.ncol) * (a.f32 ? sizeof(float) : sizeof(double)) >= (size_t)0xFFFFFFF0u)
     return hipErrorInvalidValue;
   const int nv_lut = t.lut >= 0 ? t.seq[t.lut].nv : 0;
   bool anyclamp = false;

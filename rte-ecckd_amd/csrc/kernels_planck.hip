@@ -3,7 +3,8 @@
 // Replaces calculate_planck_function and its three call sites in gas_optics_int
 // (src/gas_optics_ecckd.f90:245-289, :407-424).  The reference interpolates tlev into a
 // (ncol,nlay+1,ng) buffer and copies it twice (:419-424); here each level value is computed
-// once and stored to lev_source_dec(:,l,:) and lev_source_inc(:,l-1,:) directly.
+// once and stored to lev_source_dec(:,l,:) and lev_source_inc(:,l-1,:) directly -- which is one store where the two
+// arrays are the views of one level buffer (include/ecckd_hip.h, "Level buffer"; PlanckArgs::lev_gstride).
 //
 // Mapping (gfx950): lane -> column, block = 512 columns x a chunk of levels; the whole Planck
 // table (ntp rows, padded to an odd row length) sits in LDS.  Pure store-bandwidth kernel:
@@ -83,6 +84,8 @@ __global__ void __launch_bounds__(kPlBlock) planck_kernel(const PlanckArgs a) {
   const long c = (long)blockIdx.x * kPlBlock + threadIdx.x;
   if (c >= ncol) return;
   const int nlev = nlay + 1;
+  const long lgs = a.lev_gstride;   // g-plane stride of the level arrays (launch_planck: never 0)
+  const bool levbuf = lgs != (long)ncol * nlay;
   const int l0 = (int)((long)nlev * blockIdx.y / gridDim.y);
   const int l1 = (int)((long)nlev * (blockIdx.y + 1) / gridDim.y);
   double v[GC];
@@ -90,13 +93,19 @@ __global__ void __launch_bounds__(kPlBlock) planck_kernel(const PlanckArgs a) {
   for (int l = l0; l < l1; ++l) {
     if (a.tlev) {   // :419-424
       const PlanckPoint p = planck_point(a.tlev[c + (long)ncol * l], a.t0, a.dt, ntp);
+      const bool inc_too = l > 0 && (!levbuf || l == nlay);
+      // running pointers to level l of plane g: lev_source_dec(c, l, g) and lev_source_inc(c, l - 1, g)
+      double *pdec = a.lev_source_dec + c + (long)ncol * l, *pinc = a.lev_source_inc + c + (long)ncol * (l > 0 ? l - 1 : 0);
       for (int gb = 0; gb < ng; gb += GC) {
         planck_rows<GC>(lds, SR, p, gb, ng, pi, rpi, v);
 #pragma unroll
         for (int g = 0; g < GC; ++g) {
           if (gb + g < ng) {
-            if (l < nlay) a.lev_source_dec[c + (long)ncol * (l + (long)nlay * (gb + g))] = v[g];
-            if (l > 0) a.lev_source_inc[c + (long)ncol * ((l - 1) + (long)nlay * (gb + g))] = v[g];
+            // (one level buffer -- lev_gstride is not the layer arrays' -- : lev_source_inc(:,l-1,:) is the word just stored)
+            if (l < nlay) pdec[0] = v[g];
+            if (inc_too) pinc[0] = v[g];
+            pdec += lgs;
+            pinc += lgs;
           }
         }
       }
@@ -168,6 +177,11 @@ __global__ void __launch_bounds__(kPpBlock) planck_pair_kernel(const PlanckArgs 
   const long plane2 = 2L * plane;
   const unsigned coff = (unsigned)ES * (unsigned)cc;
   const unsigned voff = (unsigned)ES * ((unsigned)(c - (upper ? 1 : 0)) + (upper ? plane : 0u));
+  // the level arrays' own g-plane stride (PlanckArgs::lev_gstride); one level buffer: each level is stored once
+  const unsigned lplane = (unsigned)a.lev_gstride;
+  const long plane2_lev = 2L * lplane;
+  const unsigned voff_lev = (unsigned)ES * ((unsigned)(c - (upper ? 1 : 0)) + (upper ? lplane : 0u));
+  const bool levbuf = lplane != plane;
   const int l0 = (int)((long)nlay * blockIdx.y / gridDim.y), l1 = (int)((long)nlay * (blockIdx.y + 1) / gridDim.y);
   const int npairs = ng / 2;
   typedef __attribute__((address_space(1))) const real greal;
@@ -209,7 +223,7 @@ __global__ void __launch_bounds__(kPpBlock) planck_pair_kernel(const PlanckArgs 
     int a1 = q1.row * SP * ES;
     real *w_inc = Q(a.lev_source_inc) + (long)ncol * j;
     real *w_dec = Q(a.lev_source_dec) + (long)ncol * (j + 1);
-    const bool has_next = j + 1 < nlay;
+    const bool has_next = j + 1 < nlay && !levbuf;
     asm volatile("" : "+v"(alay), "+v"(a1));
 #pragma unroll 4
     for (int p = 0; p < npairs; ++p, alay += 2 * ES, a1 += 2 * ES) {
@@ -217,7 +231,7 @@ __global__ void __launch_bounds__(kPpBlock) planck_pair_kernel(const PlanckArgs 
       interp(qlay, alay, 0, vl);
       interp(q1, a1, 0, v1);
       store_pair<real>(w_lay, plane2, voff, coff, vl[0], vl[1], masked, valid);
-      store_pair<real>(w_inc, plane2, voff, coff, v1[0], v1[1], masked, valid);            // :423-424
+      store_pair<real>(w_inc, plane2_lev, voff_lev, coff, v1[0], v1[1], masked, valid);    // :423-424
       if (has_next) store_pair<real>(w_dec, plane2, voff, coff, v1[0], v1[1], masked, valid);
     }
     if (ng & 1) {   // odd g-point count: the last one alone
@@ -235,7 +249,7 @@ __global__ void __launch_bounds__(kPpBlock) planck_pair_kernel(const PlanckArgs 
       for (int p = 0; p < npairs; ++p, a0 += 2 * ES) {
         real v0[2];
         interp(q0, a0, 0, v0);
-        store_pair<real>(w_dec0, plane2, voff, coff, v0[0], v0[1], masked, valid);
+        store_pair<real>(w_dec0, plane2_lev, voff_lev, coff, v0[0], v0[1], masked, valid);
       }
       if ((ng & 1) && valid) w_dec0[c] = single(q0, a0, 0);
     }
@@ -261,7 +275,7 @@ constexpr int kPeGroup = 8;   // g-points per thread (even)
 
 template <typename real>
 __global__ void __launch_bounds__(kPeBlock) planck_edge_kernel(const real *planck, int ng, int ntp, real t0, const UDiv ud_dt_h, int ncol,
-                                                               int nlay, const real *tsfc, const real *tlev, real *sfc_source,
+                                                               long lev_gstride, const real *tsfc, const real *tlev, real *sfc_source,
                                                                real *lev_source_dec) {
   typedef real real2_u __attribute__((ext_vector_type(2), aligned(sizeof(real))));   // (a row starts at any element)
   const long c = (long)blockIdx.x * kPeBlock + threadIdx.x;
@@ -273,7 +287,7 @@ __global__ void __launch_bounds__(kPeBlock) planck_edge_kernel(const real *planc
   const real *p0r = planck + (long)q.row * ng, *p1r = p0r + ng;
   // plane g of the output: sfc_source(c, g), lev_source_dec(c, 0, g)
   real *out = (top ? lev_source_dec : sfc_source) + c;
-  const long plane = top ? (long)ncol * nlay : (long)ncol;
+  const long plane = top ? lev_gstride : (long)ncol;   // (the level arrays' own g-plane stride: FusedArgs::lev_gstride)
   // blockIdx.z: a group of kPeGroup g-points, all of its loads in flight at once (the kernel is a chain of L2 round trips)
   const int g0 = blockIdx.z * kPeGroup, g1 = g0 + kPeGroup < ng ? g0 + kPeGroup : ng;
   real2_u b0[kPeGroup / 2], b1[kPeGroup / 2];
@@ -302,14 +316,15 @@ __global__ void __launch_bounds__(kPeBlock) planck_edge_kernel(const real *planc
 hipError_t launch_planck_edge(const FusedArgs &a, hipStream_t s) {
   const TauArgs &t = a.tau;
   if (t.ncol <= 0 || t.nlay <= 0) return hipSuccess;
+  const long lgs = a.lev_gstride > 0 ? (long)a.lev_gstride : (long)t.ncol * t.nlay;
   const dim3 grid((unsigned)((t.ncol + kPeBlock - 1) / kPeBlock), a.tlev ? 2 : 1, (unsigned)((t.ng + kPeGroup - 1) / kPeGroup));
   if (a.f32)
     hipLaunchKernelGGL(planck_edge_kernel<float>, grid, dim3(kPeBlock), 0, s, reinterpret_cast<const float *>(a.planck), t.ng, a.ntp,
-                       (float)a.pt0, a.ud_pdt, t.ncol, t.nlay, reinterpret_cast<const float *>(a.tsfc),
+                       (float)a.pt0, a.ud_pdt, t.ncol, lgs, reinterpret_cast<const float *>(a.tsfc),
                        reinterpret_cast<const float *>(a.tlev), reinterpret_cast<float *>(a.sfc_source),
                        reinterpret_cast<float *>(a.lev_source_dec));
   else
-    hipLaunchKernelGGL(planck_edge_kernel<double>, grid, dim3(kPeBlock), 0, s, a.planck, t.ng, a.ntp, a.pt0, a.ud_pdt, t.ncol, t.nlay,
+    hipLaunchKernelGGL(planck_edge_kernel<double>, grid, dim3(kPeBlock), 0, s, a.planck, t.ng, a.ntp, a.pt0, a.ud_pdt, t.ncol, lgs,
                        a.tsfc, a.tlev, a.sfc_source, a.lev_source_dec);
   return hipGetLastError();
 }
@@ -319,11 +334,15 @@ size_t planck_pair_lds_bytes(int ng, int ntp, int f32) {
 }
 
 // The fast Planck kernel; f32 = 1: every data pointer addresses float arrays.
-hipError_t launch_planck_pair(const PlanckArgs &a, int f32, hipStream_t s) {
-  if (a.ncol <= 0) return hipSuccess;
+hipError_t launch_planck_pair(const PlanckArgs &a_in, int f32, hipStream_t s) {
+  if (a_in.ncol <= 0) return hipSuccess;
+  PlanckArgs a = a_in;
+  const size_t plane = (size_t)a.ncol * (size_t)a.nlay;
+  if (a.lev_gstride <= 0) a.lev_gstride = (long long)plane;   // separate level arrays
   const size_t lds = planck_pair_lds_bytes(a.ng, a.ntp, f32);
   if (lds > (size_t)kLdsBudget) return hipErrorInvalidValue;
-  if (((size_t)a.ncol * (size_t)a.nlay + (size_t)a.ncol) * (f32 ? sizeof(float) : sizeof(double)) >= (size_t)0xFFFFFFF0u)
+  const size_t widest = (size_t)a.lev_gstride > plane ? (size_t)a.lev_gstride : plane;
+  if ((widest + (size_t)a.ncol) * (f32 ? sizeof(float) : sizeof(double)) >= (size_t)0xFFFFFFF0u)
     return hipErrorInvalidValue;   // store_pair(): 32-bit byte offsets inside a plane pair
   const int nb = (a.ncol + kPpBlock - 1) / kPpBlock;
   int chunks = 1;
@@ -341,6 +360,7 @@ hipError_t launch_planck_pair(const PlanckArgs &a, int f32, hipStream_t s) {
 
 hipError_t launch_planck(PlanckArgs &a, hipStream_t s) {
   if (a.ncol <= 0) return hipSuccess;
+  if (a.lev_gstride <= 0) a.lev_gstride = (long long)a.ncol * a.nlay;   // separate level arrays
   const size_t lds = sizeof(double) * (size_t)a.ntp * (a.ng | 1);
   if (lds > (size_t)kLdsBudget) return hipErrorInvalidValue;
   const int nb = (a.ncol + kPlBlock - 1) / kPlBlock;

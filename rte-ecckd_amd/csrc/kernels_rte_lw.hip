@@ -29,11 +29,15 @@
 // NL > 0, OVER: nlay > NL.  The bottom NL layers run from registers as above; trans/source_up of
 //   the top nlay - NL layers go through a per-wave global scratch ring (16 B/cell written and read
 //   back for those layers only).
-// SHARED: the caller asserts that the two level-source arrays describe ONE value per level,
+// SHARED: the two level-source arrays describe ONE value per level,
 //   lev_source_inc(:,l,:) == lev_source_dec(:,l+1,:) -- what ecckd's gas optics produces
-//   (src/gas_optics_ecckd.f90:419-424: both are slices of one buffer).  The source at the far edge
-//   of a layer is then the near-edge source of the next one: it is carried in a register and only
-//   the first layer reads the second array (24 instead of 32 B/cell).  Same arithmetic, same bits.
+//   (src/gas_optics_ecckd.f90:419-424: both are slices of one buffer).  Either the caller asserts it
+//   (ecckd_rte_lw_shared_levels) or the two arrays ARE the views of one level buffer (include/ecckd_hip.h,
+//   "Level buffer": lev_source_inc == lev_source_dec + ncol), which the C ABI sees by itself.  The source
+//   at the far edge of a layer is then the near-edge source of the next one: it is carried in a register and
+//   only the first layer reads the second array (24 instead of 32 B/cell).  Same arithmetic, same bits.
+//   The level arrays have a g-plane stride of their own here, RteLwArgs::lev_gstride: nlay*ncol for two
+//   separate arrays, (nlay+1)*ncol for the views of the buffer.
 #include <cstdlib>
 
 #include "kernels.hpp"
@@ -126,6 +130,7 @@ __global__ void __launch_bounds__(64) rte_lw_kernel(const RteLwArgs a) {
   const long lstep = a.top_at_1 ? 1 : -1;
   const real *Bdn = P(a.top_at_1 ? a.lev_source_inc : a.lev_source_dec);
   const real *Bup = P(a.top_at_1 ? a.lev_source_dec : a.lev_source_inc);
+  [[maybe_unused]] const long lgs = a.lev_gstride ? (long)a.lev_gstride : (long)ncol * nlay;   // g-plane stride of Bdn / Bup (SHARED)
   const int ngroups = (ng + GW - 1) / GW;
   const int niter = ngroups * a.nmus;
   const long ntiles = ((long)ncol + CW - 1) / CW;
@@ -168,8 +173,13 @@ __global__ void __launch_bounds__(64) rte_lw_kernel(const RteLwArgs a) {
     [[maybe_unused]] unsigned vo = 0;                                           // OFF32: byte offset of this lane's next request
     [[maybe_unused]] const unsigned vstep = (unsigned)((long)sizeof(real) * qstep);   // (wraps for bottom-up storage)
     [[maybe_unused]] const real *tau_b = nullptr, *lay_b = nullptr, *bdn_b = nullptr, *bup_b = nullptr;   // first plane of the group
-    auto at32 = [&](const real *plane) -> real {
-      return __builtin_nontemporal_load((greal_t *)((gcchar_t *)plane + vo));
+    // SHARED: the level arrays have a g-plane stride of their own (RteLwArgs::lev_gstride: the two views of one level buffer
+    // are (nlay+1)*ncol apart from plane to plane), so they get their own plane base and their own lane offset: `vol` beside
+    // `vo`, or -- 64-bit form -- `ql` added to qn where a level is read.  Both advance by a layer like the others.
+    [[maybe_unused]] unsigned vol = 0;
+    [[maybe_unused]] long ql = 0;
+    auto at32 = [&](const real *plane, unsigned off) -> real {
+      return __builtin_nontemporal_load((greal_t *)((gcchar_t *)plane + off));
     };
     auto pair_start = [&](int it) {
       const int gb = (it / a.nmus) * GW;
@@ -177,32 +187,45 @@ __global__ void __launch_bounds__(64) rte_lw_kernel(const RteLwArgs a) {
       const int gg = g < ng ? g : ng - 1;
       if constexpr (OFF32) {
         const long pl = (long)ncol * nlay * gb;
-        tau_b = P(a.tau) + pl; lay_b = P(a.lay_source) + pl; bdn_b = Bdn + pl; bup_b = Bup + pl;
+        const long pll = SHARED ? lgs * gb : pl;
+        tau_b = P(a.tau) + pl; lay_b = P(a.lay_source) + pl; bdn_b = Bdn + pll; bup_b = Bup + pll;
         vo = (unsigned)sizeof(real) * (unsigned)(cc + (long)ncol * nlay * (gg - gb) + (long)ncol * lay0);
         asm volatile("" : "+v"(vo));
-        if (SHARED) bup_first = at32(bup_b);
+        if (SHARED) {
+          vol = (unsigned)sizeof(real) * (unsigned)(cc + lgs * (gg - gb) + (long)ncol * lay0);
+          asm volatile("" : "+v"(vol));
+          bup_first = at32(bup_b, vol);
+        }
         return;
       }
       qn = cc + (long)ncol * nlay * gg + (long)ncol * (lay0 + lstep * nover);
       asm volatile("" : "+v"(qn));
-      if (SHARED && !OVER) bup_first = __builtin_nontemporal_load(Bup + qn);
+      if (SHARED) {
+        ql = (lgs - (long)ncol * nlay) * gg;
+        asm volatile("" : "+v"(ql));
+      }
+      if (SHARED && !OVER) bup_first = __builtin_nontemporal_load(Bup + qn + ql);
     };
     // `sl` = layer being requested (compile-time in the unrolled code); in the padded variants the
     // offset stops advancing at the last real layer, so absent layers re-read it (finite data).
     auto issue = [&](int slot, int sl) {
       if constexpr (OFF32) {
-        ptau[slot] = at32(tau_b);
-        play[slot] = at32(lay_b);
-        pbdn[slot] = at32(bdn_b);
-        if (!SHARED) pbup[slot] = at32(bup_b);
+        ptau[slot] = at32(tau_b, vo);
+        play[slot] = at32(lay_b, vo);
+        pbdn[slot] = at32(bdn_b, SHARED ? vol : vo);
+        if (!SHARED) pbup[slot] = at32(bup_b, vo);
         vo += vstep;
         asm volatile("" : "+v"(vo));
+        if (SHARED) {
+          vol += vstep;
+          asm volatile("" : "+v"(vol));
+        }
         return;
       }
       // nontemporal: read-once streams
       ptau[slot] = __builtin_nontemporal_load(P(a.tau) + qn);
       play[slot] = __builtin_nontemporal_load(P(a.lay_source) + qn);
-      pbdn[slot] = __builtin_nontemporal_load(Bdn + qn);
+      pbdn[slot] = __builtin_nontemporal_load(Bdn + qn + (SHARED ? ql : 0L));
       if (!SHARED) pbup[slot] = __builtin_nontemporal_load(Bup + qn);
       if (!PAD || present(abs_layer(sl + 1))) qn += qstep;
       asm volatile("" : "+v"(qn));
@@ -211,7 +234,8 @@ __global__ void __launch_bounds__(64) rte_lw_kernel(const RteLwArgs a) {
     // intensity, so the loads for layer s+kPF cannot be hoisted above layer s-1 (without this
     // the scheduler issues dozens of layers of loads up front and spills the register file).
     auto issue_after = [&](int slot, int sl, real &pin) {
-      if constexpr (OFF32) asm volatile("" : "+v"(vo), "+v"(pin));
+      if constexpr (OFF32 && SHARED) asm volatile("" : "+v"(vo), "+v"(vol), "+v"(pin));
+      else if constexpr (OFF32) asm volatile("" : "+v"(vo), "+v"(pin));
       else asm volatile("" : "+v"(qn), "+v"(pin));
       issue(slot, sl);
     };
@@ -265,8 +289,9 @@ __global__ void __launch_bounds__(64) rte_lw_kernel(const RteLwArgs a) {
       if constexpr (OVER) {   // the layers above the register-resident ones: plain loads, scratch ring
         for (int s = 0; s < nover; ++s) {
           const long q = base + (long)ncol * (lay0 + lstep * s);
-          const real bdn = Bdn[q];
-          const real bup = (SHARED && s > 0) ? carry : Bup[q];
+          const long qlev = SHARED ? q + (lgs - (long)ncol * nlay) * gg : q;
+          const real bdn = Bdn[qlev];
+          const real bup = (SHARED && s > 0) ? carry : Bup[qlev];
           real t, su;
           layer(s, P(a.tau)[q], P(a.lay_source)[q], bdn, bup, t, su);
           carry = bdn;
@@ -384,7 +409,9 @@ template <typename real, int NL, int CW, bool EXACT, bool OVER, bool SHARED>
 hipError_t launch_one(const RteLwArgs &a, hipStream_t s) {
   if constexpr (EXACT) {   // 32-bit lane offsets when the planes of a g-point group span less than 4 GiB (see OFF32)
     // (the environment hook lets tests run the 64-bit form, which only calls beyond 4.4e6 columns take otherwise)
-    if ((double)a.ncol * a.nlay * (64 / CW) * sizeof(real) < 4294967296. && !getenv("ECCKD_LW_NO_OFF32"))
+    // (SHARED: the level arrays' planes are lev_gstride apart, a level more than the others' in the buffer form)
+    const double plane = SHARED && a.lev_gstride > (long long)a.ncol * a.nlay ? (double)a.lev_gstride : (double)a.ncol * a.nlay;
+    if (plane * (64 / CW) * sizeof(real) < 4294967296. && !getenv("ECCKD_LW_NO_OFF32"))
       return a.series3 ? launch_ser<real, NL, CW, EXACT, OVER, SHARED, true, true>(a, s)
                        : launch_ser<real, NL, CW, EXACT, OVER, SHARED, false, true>(a, s);
   }

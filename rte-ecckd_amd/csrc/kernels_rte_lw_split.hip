@@ -149,6 +149,9 @@ __device__ __forceinline__ void rte_lw_split_body(const RteLwArgs &a, const Plan
   const int niter = ngroups * a.nmus;
   const long ntiles = ((long)ncol + CW - 1) / CW;
   const int s0 = w * SEG;   // first layer of this wave, in walking order from the top
+  // SHARED: the level arrays have a g-plane stride of their own (RteLwArgs::lev_gstride: NL*ncol, or (NL+1)*ncol for the two
+  // views of one level buffer); dlev is what it exceeds the layer arrays' by: 0 or ncol
+  [[maybe_unused]] const int dlev = SHARED && a.lev_gstride ? (int)((long)a.lev_gstride - (long)ncol * NL) : 0;
 
   for (int i = gtid; i < 2 * (NL + 1) * CW; i += 64 * NW) acc_dn[i] = 0.;
   if (BOTH)
@@ -177,6 +180,7 @@ __device__ __forceinline__ void rte_lw_split_body(const RteLwArgs &a, const Plan
     long qn = 0;
     const long qstep = (long)ncol * lstep;
     [[maybe_unused]] long q2 = 0;      // PLANCK: offset into tlay / tlev rows (no g dimension)
+    [[maybe_unused]] int glev = 0;     // SHARED: the lane's g-point; its plane of the level arrays lies dlev * glev beyond that of the others
     [[maybe_unused]] double near_first = 0.;   // SHARED / PLANCK: near-edge source (temperature) of the segment's first layer
 
     auto pair_start = [&](int it) {
@@ -191,7 +195,9 @@ __device__ __forceinline__ void rte_lw_split_body(const RteLwArgs &a, const Plan
         if (SKY) qb = (long)ncol * NL * a.gpt2band[gg];
         if (MASK) mhalf = gg >> 5;
       } else if (SHARED) {
-        near_first = __builtin_nontemporal_load(Bup + qn);
+        glev = gg;
+        asm volatile("" : "+v"(glev));
+        near_first = __builtin_nontemporal_load(Bup + (qn + (long)dlev * glev));
       }
     };
     auto issue = [&](int slot) {
@@ -206,7 +212,12 @@ __device__ __forceinline__ void rte_lw_split_body(const RteLwArgs &a, const Plan
         q2 += qstep;
       } else {
         play_[slot] = __builtin_nontemporal_load(a.lay_source + qn);
-        pbdn[slot] = __builtin_nontemporal_load(Bdn + qn);
+        if constexpr (SHARED) {
+          asm volatile("" : "+v"(glev));   // (the product below is formed here, in the add, and not kept in a register pair)
+          pbdn[slot] = __builtin_nontemporal_load(Bdn + (qn + (long)dlev * glev));
+        } else {
+          pbdn[slot] = __builtin_nontemporal_load(Bdn + qn);
+        }
         if (!SHARED) pbup[slot] = __builtin_nontemporal_load(Bup + qn);
         if constexpr (RESC) {
           pss[slot] = __builtin_nontemporal_load(a.ssa + qn);
