@@ -943,6 +943,105 @@ int ecckd_cloud_optics_f32(const ecckd_cloud_optics_t *cloud_optics, int ncol, i
                            void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Aerosol optics: aerosol species, particle sizes, layer masses and relative humidity per (column, layer) to the
+ * particulate properties on the model's bands -- the aerosol half of the planes the all-sky calls above take as tau_p,
+ * ssa_p, g_p.  A host model carries tracers, size bins and humidity, not optical properties; this is the step between
+ * them.  The counterpart in RTE-RRTMGP is ty_aerosol_optics_rrtmgp_merra [RTE-ext:
+ * extensions/aerosols/mo_aerosol_optics_rrtmgp_merra.F90: load, aerosol_optics].  RTE-RRTMGP is not part of the reference
+ * tree, so PARITY WITH IT IS UNPINNED; the definition below is this project's own and is what the tests pin
+ * (tests/aerosol_optics_ref.py restates it in numpy, and the results are equal BIT FOR BIT in fp64 and in float: the build
+ * has FMA contraction off, every line below is one correctly rounded IEEE operation in the precision of the call).  It
+ * keeps RTE's table layout, type codes and call shape, and goes beyond it in two ways: several species per call (nspec;
+ * nspec = 1 is RTE's call), summed in registers with each plane stored once, and `accumulate`, which adds the aerosol onto
+ * planes that already hold the clouds ("add them up on the band grid first" then costs no pass of its own).
+ * Out of scope: reading MERRA or any aerosol netCDF file (the host hands over tables); parity with RTE-RRTMGP's bits;
+ * aerosol inside the gas-optics or solver kernels; per-g-point aerosol properties; delta scaling of the aerosol planes
+ * (ecckd_delta_scale serves that).
+ *
+ * Type codes (RTE's): 0 none, 1 dust, 2 sea salt, 3 sulfate, 4 black carbon hydrophilic, 5 black carbon hydrophobic,
+ * 6 organic carbon hydrophilic, 7 organic carbon hydrophobic.
+ * Tables: HOST arrays in Fortran order (first index fastest), nval = 3 in the order mass extinction (m2 kg-1), ssa,
+ * asymmetry:  bin_lims(2,nbin) microns;  rh_levels(nrh) as a fraction;  dust_tbl(nval,nbin,nband);
+ * salt_tbl(nval,nrh,nbin,nband);  sulf_tbl, bcar_rh_tbl, ocar_rh_tbl (nval,nrh,nband);  bcar_tbl, ocar_tbl (nval,nband).
+ * ecckd_aerosol_optics_create_lut makes the device copy once (device -1: a host-only object whose getters and refusals
+ * work and whose compute call fails).  The differences d(i) = rh_levels(i+1) - rh_levels(i) and the slopes
+ * tbl(i+1) - tbl(i) along the humidity are formed there: they are the same subtractions.  Refused with a message, in this
+ * order: handle NULL; nband or nbin < 1; nrh < 2; rh_levels NULL, not strictly increasing, or NaN; bin_lims NULL, a bin with
+ * lims(1,b) >= lims(2,b), or lims(2,b) > lims(1,b+1); a NULL table; no such device.
+ *
+ * ecckd_aerosol_optics (+ _f32).  aero_type (int32), aero_size (microns), aero_mass (kg m-2): (ncol,nlay,nspec);
+ * relhum: (ncol,nlay); tau, ssa, g: (ncol,nlay,nband); column fastest; nspec >= 1.
+ * Per cell, once (1-based):
+ *     i = 1 + number of j in 2..nrh-1 with relhum >= rh_levels(j)          (a NaN takes 1)
+ *     w = (relhum - rh_levels(i)) / d(i)
+ *     w = w > 0 ? w : 0;  w = w < 1 ? w : 1     (below the first / above the last level: the edge value; NaN: 0)
+ * Per species s, with type k, mass m and size r:
+ *     active = 1 <= k <= 7 and m > 0                       (NaN, 0, negative mass: not active)
+ *     dust, salt:  bin = the first b in 1..nbin with bin_lims(1,b) <= r and r < bin_lims(2,b)
+ *                  no such b (NaN too): not active
+ *     for q in ext, ssa, asy at the band:
+ *         humidity-dependent types (2,3,4,6):  v_q = tbl_q(i) + w*(tbl_q(i+1) - tbl_q(i))
+ *         others (1,5,7):                      v_q = tbl_q
+ *     t = m*v_ext;  ts = t*v_ssa;  tsg = ts*v_asy          inactive: t = ts = tsg = +0 (a select, not a product)
+ * Per band, over s = 1..nspec in order, starting from +0:
+ *     T += t;  TS += ts;  TSG += tsg;  A += (t - ts)
+ * Outputs:
+ *     two-stream (ssa and g given):  tau = T;  ssa = TS/max(eps,T);  g = TSG/max(eps,TS)
+ *     one-scalar (ssa and g NULL):   tau = A                                     (the absorption optical depth)
+ *   eps = epsilon(1.0) of the precision (2^-52, 2^-23); max(eps,x) is x where x > eps, else eps, as in cloud optics.
+ *   accumulate = 1: the planes hold op1 on entry.  With (tau2, ssa2, g2) exactly what accumulate = 0 would have stored,
+ *   ecckd_increment's increment_2stream_by_2stream (one-scalar: increment_1scalar_by_1scalar) formulas are applied,
+ *   operation for operation, with that call's own eps (3*tiny):
+ *     tau12 = tau1 + tau2;  tscat1 = tau1*ssa1;  tscat2 = tau2*ssa2;  tsg2 = tscat2*g2;  tauscat12 = tscat1 + tscat2
+ *     g1 = (tscat1*g1 + tsg2)/max(eps,tauscat12);  ssa1 = tauscat12/max(eps,tau12);  tau1 = tau12        (tau1 = tau1 + A)
+ *   so the result is BIT FOR BIT the plain call into fresh planes followed by ecckd_increment on the band grid.
+ *   _f32: the tables, bin limits and levels are rounded to float first (d(i) and the slopes are then float operations),
+ *   everything above in float.
+ *   Refused with a message before anything is launched, in this order: object NULL; nspec < 1; ssa without g or g without
+ *   ssa; bad ncol / nlay; aero_type, aero_size, aero_mass, relhum or tau NULL; accumulate not 0 or 1; bad memspace; then,
+ *   with HOST input arrays only (ECCKD_HOST, ECCKD_MIXED), the value checks: a type outside 0..7; a negative mass; an
+ *   active dust or salt cell whose size lies in no bin; relhum outside [0,1], or NaN, in a cell that has an active
+ *   humidity-dependent species; then a host-only object; no device.  With ECCKD_DEVICE arrays nothing is checked (the call
+ *   stays asynchronous): a type outside 0..7 is "none", and no value can index outside a table -- i is a count bounded by
+ *   the number of levels, the bin comes from comparisons, and an inactive species is not computed.
+ *   ECCKD_DEVICE is asynchronous on `stream` and uses no scratch, so it is capture-safe without a warm-up; ECCKD_HOST
+ *   stages through the device and synchronises; ECCKD_MIXED: host inputs, tau / ssa / g device buffers (synchronises).
+ *   Kernel: one lane per cell, the interval and weight once per cell, the table entry once per species, bands the outer
+ *   and species the inner loop with T, TS, TSG in registers, coalesced plane stores.  The tables are one image of
+ *   (value, slope) pairs, [quantity][band][entry], with
+ *     entries = nbin*nrh + 3*(nrh-1) + 2         (dust nbin; salt nbin*(nrh-1); sulfate, bc, oc hydrophilic nrh-1 each; bc, oc)
+ *     image bytes = (ssa ? 3 : 2) * nband * entries * 2*sizeof(real)
+ *   staged in LDS while image bytes <= 32768 (as for cloud optics), else read in place through L2.  Launch rule: blocks of
+ *   256 cells, min(ceil(ncol*nlay/256), CUs * min(B, floor(163840 / image bytes) on the LDS route)) with B = 8 for nspec <= 2,
+ *   4 for nspec <= 8 and for nspec > 16, 2 for 9 <= nspec <= 16 (the waves per SIMD the kernel is compiled for); the
+ *   remaining cells by grid stride.  Up to 16 species keep their state in registers; more take a slower instantiation
+ *   with the same results.
+ * --------------------------------------------------------------------------------------- */
+#define ECCKD_AERO_NONE 0
+#define ECCKD_AERO_DUST 1
+#define ECCKD_AERO_SALT 2
+#define ECCKD_AERO_SULF 3
+#define ECCKD_AERO_BCAR_RH 4
+#define ECCKD_AERO_BCAR 5
+#define ECCKD_AERO_OCAR_RH 6
+#define ECCKD_AERO_OCAR 7
+typedef struct ecckd_aerosol_lut ecckd_aerosol_optics_t; /* replaces type(ty_aerosol_optics_rrtmgp_merra) */
+int ecckd_aerosol_optics_create_lut(int nband, int nbin, int nrh, const double *bin_lims, const double *rh_levels,
+                                    const double *dust_tbl, const double *salt_tbl, const double *sulf_tbl, const double *bcar_tbl,
+                                    const double *bcar_rh_tbl, const double *ocar_tbl, const double *ocar_rh_tbl, int device,
+                                    ecckd_aerosol_optics_t **aerosol_optics);
+void ecckd_aerosol_optics_destroy(ecckd_aerosol_optics_t *aerosol_optics);
+int ecckd_aerosol_optics_get_nband(const ecckd_aerosol_optics_t *aerosol_optics);
+int ecckd_aerosol_optics_get_nbin(const ecckd_aerosol_optics_t *aerosol_optics);
+int ecckd_aerosol_optics_get_nrh(const ecckd_aerosol_optics_t *aerosol_optics);
+int ecckd_aerosol_optics(const ecckd_aerosol_optics_t *aerosol_optics, int ncol, int nlay, int nspec, const int *aero_type,
+                         const double *aero_size, const double *aero_mass, const double *relhum, int accumulate, double *tau,
+                         double *ssa, double *g, int memspace, void *stream);
+int ecckd_aerosol_optics_f32(const ecckd_aerosol_optics_t *aerosol_optics, int ncol, int nlay, int nspec, const int *aero_type,
+                             const float *aero_size, const float *aero_mass, const float *relhum, int accumulate, float *tau,
+                             float *ssa, float *g, int memspace, void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * Device memory for host languages without a HIP binding of their own (the Fortran shim's device-resident
  * twins of ty_optical_props / ty_source_func_lw own their buffers through these).  to_device: 1 = host to
  * device, 0 = device to host; synchronous.

@@ -11,6 +11,8 @@ This package is a thin mirror of the reference's Fortran interface on top of the
   passes around (only the members it touches);
 * :class:`CloudOptics` <-> RTE-RRTMGP's ``ty_cloud_optics`` (look-up-table form): water paths and effective
   radii to the particulate properties on the bands, in front of the all-sky calls;
+* :class:`AerosolOptics` <-> RTE-RRTMGP's ``ty_aerosol_optics_rrtmgp_merra``: aerosol species, sizes, masses and relative
+  humidity to the particulate properties on the bands, several species per call, optionally added onto the clouds;
 * :func:`rte_lw`, :func:`rte_sw` <-> RTE-RRTMGP's solvers as called at
   ecckd_rfmip_lw.F90:130-135 and ecckd_rfmip_sw.F90:148-154.
 
@@ -39,7 +41,7 @@ NAME_LEN = 32
 _SOURCES = ["kernels_gas_fused.hip", "kernels_tau.hip", "kernels_planck.hip", "kernels_rte_lw.hip", "kernels_rte_lw_split.hip",
             "kernels_rte_lw_jac.hip", "kernels_rte_lw_2str.hip",
             "kernels_rte_sw.hip", "kernels_rte_sw_sys.hip", "kernels_rte_gpt.hip", "kernels_optical_props.hip",
-            "kernels_cloud_sampling.hip", "kernels_cloud_optics.hip",
+            "kernels_cloud_sampling.hip", "kernels_cloud_optics.hip", "kernels_aerosol_optics.hip",
             "capi.cpp", "nc_capi.cpp", "model.cpp", "cdf1.cpp"]
 _HEADERS = ["kernels.hpp", "wave_pair.hpp", "sw_two_stream.hpp", "sw_two_stream_body.inc", "lw_two_stream.hpp", "lw_layer.hpp", "planck_at.hpp", "model.hpp", "cdf1.hpp", os.path.join("..", "..", "include", "ecckd_hip.h"),
             os.path.join("..", "..", "include", "ecckd_nc.h"), os.path.join("..", "..", "include", "rte_kernels_hip.h"),
@@ -95,10 +97,12 @@ FORTRAN_DRIVER = os.path.join(FORTRAN_BUILD, "ecckd_driver")
 RFMIP_LW = os.path.join(FORTRAN_BUILD, "ecckd_rfmip_lw")
 RFMIP_SW = os.path.join(FORTRAN_BUILD, "ecckd_rfmip_sw")
 CLOUD_DRIVER = os.path.join(FORTRAN_BUILD, "ecckd_cloud_driver")
+AEROSOL_DRIVER = os.path.join(FORTRAN_BUILD, "ecckd_aerosol_driver")
 _FORTRAN_MODULES = ["mo_rte_min.F90", "mo_ecckd_device.F90", "gas_optics_ecckd.F90", "mo_rte_solvers.F90", "rfmip_support.F90",
-                    "mo_cloud_optics.F90"]
+                    "mo_cloud_optics.F90", "mo_aerosol_optics.F90"]
 _FORTRAN_PROGRAMS = [("ecckd_driver", "ecckd_driver.F90", []), ("ecckd_rfmip_lw", "ecckd_rfmip.F90", []),
-                     ("ecckd_rfmip_sw", "ecckd_rfmip.F90", ["-DSHORTWAVE"]), ("ecckd_cloud_driver", "ecckd_cloud_driver.F90", [])]
+                     ("ecckd_rfmip_sw", "ecckd_rfmip.F90", ["-DSHORTWAVE"]), ("ecckd_cloud_driver", "ecckd_cloud_driver.F90", []),
+                     ("ecckd_aerosol_driver", "ecckd_aerosol_driver.F90", [])]
 
 
 def build_fortran(force=False, verbose=False):
@@ -246,6 +250,14 @@ def lib():
             getattr(L, "ecckd_cloud_optics_get_" + f).argtypes = [C.c_void_p]
         for f in ("ecckd_cloud_optics", "ecckd_cloud_optics_f32"):
             getattr(L, f).argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 3 + [C.c_int, C.c_void_p]
+    if hasattr(L, "ecckd_aerosol_optics"):   # (ECCKD_LIB may name an older build, which lacks them)
+        L.ecckd_aerosol_optics_create_lut.argtypes = [C.c_int] * 3 + [C.c_void_p] * 9 + [C.c_int, C.c_void_p]
+        L.ecckd_aerosol_optics_destroy.argtypes = [C.c_void_p]
+        L.ecckd_aerosol_optics_destroy.restype = None
+        for f in ("nband", "nbin", "nrh"):
+            getattr(L, "ecckd_aerosol_optics_get_" + f).argtypes = [C.c_void_p]
+        for f in ("ecckd_aerosol_optics", "ecckd_aerosol_optics_f32"):
+            getattr(L, f).argtypes = [C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 3 + [C.c_int, C.c_void_p]
     _lib = L
     return L
 
@@ -391,6 +403,22 @@ def _ptr(a, shape=None, what="array", f32=False):
     if not isinstance(a, np.ndarray) or a.dtype != (np.float32 if f32 else np.float64) or not a.flags.c_contiguous:
         raise TypeError(what + ": need a C-contiguous " + want + " ndarray")
     if shape is not None and tuple(a.shape) != tuple(shape):
+        raise ValueError("%s: shape %s, expected %s" % (what, a.shape, tuple(shape)))
+    return C.c_void_p(a.ctypes.data)
+
+
+def _int32_ptr(a, shape, what):
+    """Data pointer of a C-contiguous int32 array (numpy or torch) of the given shape."""
+    if _is_torch(a):
+        import torch
+        if a.dtype != torch.int32 or not a.is_contiguous():
+            raise TypeError(what + ": need a contiguous int32 tensor")
+        if tuple(a.shape) != tuple(shape):
+            raise ValueError("%s: shape %s, expected %s" % (what, tuple(a.shape), tuple(shape)))
+        return C.c_void_p(a.data_ptr())
+    if not isinstance(a, np.ndarray) or a.dtype != np.int32 or not a.flags.c_contiguous:
+        raise TypeError(what + ": need a C-contiguous int32 ndarray")
+    if tuple(a.shape) != tuple(shape):
         raise ValueError("%s: shape %s, expected %s" % (what, a.shape, tuple(shape)))
     return C.c_void_p(a.ctypes.data)
 
@@ -744,6 +772,112 @@ class CloudOptics:
         st = _stream(DEVICE) if space == DEVICE else None
         rc = (lib().ecckd_cloud_optics_f32 if f32 else lib().ecckd_cloud_optics)(
             self._h, ncol, nlay, *ins, self._icergh, *outs, space, st)
+        return last_error() if rc else ""
+
+
+# aerosol type codes (RTE-RRTMGP's merra_aero_* parameters; ECCKD_AERO_* in include/ecckd_hip.h)
+AERO_NONE, AERO_DUST, AERO_SALT, AERO_SULF, AERO_BCAR_RH, AERO_BCAR, AERO_OCAR_RH, AERO_OCAR = range(8)
+
+
+class AerosolOptics:
+    """``ty_aerosol_optics_rrtmgp_merra`` (RTE-RRTMGP, extensions/aerosols/mo_aerosol_optics_rrtmgp_merra.F90), backed by
+    a device-resident table handle: aerosol type, size (microns), mass (kg m-2) and relative humidity per (column, layer)
+    to the particulate properties on the bands.  Beyond RTE-RRTMGP: several species per call and ``accumulate``.  The
+    definition is in include/ecckd_hip.h (``ecckd_aerosol_optics``); parity with RTE-RRTMGP is unpinned."""
+
+    def __init__(self):
+        self._h = C.c_void_p(None)
+
+    def __del__(self):
+        try:
+            self.finalize()
+        except Exception:
+            pass
+
+    def finalize(self):
+        if self._h:
+            lib().ecckd_aerosol_optics_destroy(self._h)
+            self._h = C.c_void_p(None)
+
+    def load(self, band_lims_wvn, merra_aero_bin_lims, aero_rh, aero_dust_tbl, aero_salt_tbl, aero_sulf_tbl, aero_bcar_tbl,
+             aero_bcar_rh_tbl, aero_ocar_tbl, aero_ocar_rh_tbl, device=0):
+        """``load`` with RTE-RRTMGP's argument list.  Host tables, C-contiguous numpy float64 in the reversed Fortran
+        shapes: ``merra_aero_bin_lims`` ``(nbin, 2)``, ``aero_rh`` ``(nrh,)``, dust ``(nband, nbin, 3)``, salt
+        ``(nband, nbin, nrh, 3)``, sulf / bcar_rh / ocar_rh ``(nband, nrh, 3)``, bcar / ocar ``(nband, 3)``.
+        ``band_lims_wvn`` ``(nband, 2)`` or None gives nothing but the band count.  ``device`` -1 makes a host-only
+        object.  Returns the error message ('' = success)."""
+        self.finalize()
+        tabs = (merra_aero_bin_lims, aero_rh, aero_dust_tbl, aero_salt_tbl, aero_sulf_tbl, aero_bcar_tbl, aero_bcar_rh_tbl,
+                aero_ocar_tbl, aero_ocar_rh_tbl)
+        for t in tabs:
+            if not isinstance(t, np.ndarray) or t.dtype != np.float64 or not t.flags.c_contiguous:
+                return "aerosol_optics%load(): the tables are C-contiguous float64 ndarrays on the host"
+        if (merra_aero_bin_lims.ndim != 2 or aero_rh.ndim != 1 or aero_dust_tbl.ndim != 3 or aero_salt_tbl.ndim != 4
+                or aero_sulf_tbl.ndim != 3 or aero_bcar_tbl.ndim != 2):
+            return ("aerosol_optics%load(): bin limits are (nbin, 2), levels (nrh,), dust (nband, nbin, 3), salt "
+                    "(nband, nbin, nrh, 3), sulf / bcar_rh / ocar_rh (nband, nrh, 3), bcar / ocar (nband, 3)")
+        nbin, nrh, nband = merra_aero_bin_lims.shape[0], aero_rh.shape[0], aero_dust_tbl.shape[0]
+        if (merra_aero_bin_lims.shape != (nbin, 2) or aero_dust_tbl.shape != (nband, nbin, 3)
+                or aero_salt_tbl.shape != (nband, nbin, nrh, 3)
+                or any(t.shape != (nband, nrh, 3) for t in (aero_sulf_tbl, aero_bcar_rh_tbl, aero_ocar_rh_tbl))
+                or any(t.shape != (nband, 3) for t in (aero_bcar_tbl, aero_ocar_tbl))
+                or (band_lims_wvn is not None and np.shape(band_lims_wvn)[0] != nband)):
+            return "aerosol_optics%load(): arrays sized inconsistently"
+        h = C.c_void_p(None)
+        if lib().ecckd_aerosol_optics_create_lut(nband, nbin, nrh, *[C.c_void_p(t.ctypes.data) for t in tabs], int(device),
+                                                 C.byref(h)):
+            return last_error()
+        self._h = h
+        return ""
+
+    def get_nband(self):
+        return lib().ecckd_aerosol_optics_get_nband(self._h) if self._h else 0
+
+    def get_nbin(self):
+        return lib().ecckd_aerosol_optics_get_nbin(self._h) if self._h else 0
+
+    def get_nrh(self):
+        return lib().ecckd_aerosol_optics_get_nrh(self._h) if self._h else 0
+
+    def aerosol_optics(self, aero_type, aero_size, aero_mass, relhum, optical_props, accumulate=False):
+        """``aerosol_optics(aero_type, aero_size, aero_mass, relhum, optical_props)``: the species arrays ``(nlay, ncol)``
+        (RTE-RRTMGP's call) or ``(nspec, nlay, ncol)``, ``aero_type`` int32; ``relhum`` ``(nlay, ncol)``;
+        ``optical_props`` an :class:`OpticalProps2str` (tau, ssa, g) or :class:`OpticalProps1scl` (absorption optical
+        depth) on the bands, ``(nband, nlay, ncol)``.  ``accumulate``: add onto what the planes hold (``increment``'s
+        arithmetic) instead of overwriting them.  numpy arrays or torch host tensors (staged), torch device tensors
+        (asynchronous on the current stream), or host inputs with device planes.  float32 planes take the ``_f32``
+        call.  Returns the error message ('' = success)."""
+        if not self._h:
+            return "aerosol_optics%aerosol_optics(): the tables have not been loaded"
+        op = optical_props
+        two = isinstance(op, OpticalProps2str)
+        if op.tau is None or op.tau.ndim != 3:
+            return "aerosol_optics%aerosol_optics(): optical properties are not allocated (alloc_1scl_bands / alloc_2str_bands)"
+        nband, nlay, ncol = op.tau.shape
+        if nband != self.get_nband():
+            return ("aerosol_optics%aerosol_optics(): optical properties have " + str(nband) + " bands, the tables " +
+                    str(self.get_nband()))
+        if aero_type is None or getattr(aero_type, "ndim", 0) not in (2, 3):
+            return "aerosol_optics%aerosol_optics(): aero_type is (nlay, ncol) or (nspec, nlay, ncol)"
+        nspec = 1 if aero_type.ndim == 2 else int(aero_type.shape[0])
+        shape = (nlay, ncol) if aero_type.ndim == 2 else (nspec, nlay, ncol)
+        f32 = _is_f32(op.tau)
+        planes = [op.tau] + ([op.ssa, op.g] if two else [])
+        inputs = [aero_type, aero_size, aero_mass, relhum]
+        try:
+            space = _space_of(planes)
+            if space == DEVICE and _space_of(inputs) == HOST:
+                space = MIXED
+            elif _space_of(inputs) != space:
+                raise TypeError("mixing host and device arrays in one call")
+            ins = [_int32_ptr(aero_type, shape, "aero_type"), _ptr(aero_size, shape, "aero_size", f32),
+                   _ptr(aero_mass, shape, "aero_mass", f32), _ptr(relhum, (nlay, ncol), "relhum", f32)]
+            outs = [_ptr(a, (nband, nlay, ncol), n, f32) for a, n in zip(planes, ("tau", "ssa", "g"))] + [None] * (3 - len(planes))
+        except (TypeError, ValueError) as e:
+            return str(e)
+        st = _stream(DEVICE) if space == DEVICE else None
+        rc = (lib().ecckd_aerosol_optics_f32 if f32 else lib().ecckd_aerosol_optics)(
+            self._h, ncol, nlay, nspec, *ins, 1 if accumulate else 0, *outs, space, st)
         return last_error() if rc else ""
 
 

@@ -571,6 +571,10 @@ class Stage {
   // cloud masks: 8-byte words whatever the precision of the call
   const unsigned long long *in(const unsigned long long *p, size_t n) { return static_cast<unsigned long long *>(place(p, n * 8, false, true, false)); }
   unsigned long long *out(unsigned long long *p, size_t n) { return static_cast<unsigned long long *>(place(p, n * 8, false, false, true)); }
+  // aerosol type codes: 4-byte integers whatever the precision of the call
+  const int *in(const int *p, size_t n) { return static_cast<int *>(place(p, n * 4, false, true, false)); }
+  // a spectral array the call reads and writes (ECCKD_MIXED leaves it on the device)
+  double *inout_big(double *p, size_t n) { return static_cast<double *>(place(p, n * es, kBig, true, true)); }
 
   // The gas description with its concentration arrays staged (the strides and scalars stay as they are)
   GasDesc gases(const GasDesc &gd, int ncol, int nlay) {
@@ -761,6 +765,89 @@ const char *cloud_optics_check_host(const ecckd_cloud_lut &co, size_t n, const r
     if (clwp[i] < real(0)) return "ecckd_cloud_optics: negative liquid water path";
   for (size_t i = 0; i < n; ++i)
     if (ciwp[i] < real(0)) return "ecckd_cloud_optics: negative ice water path";
+  return nullptr;
+}
+
+}  // namespace
+
+// ---- aerosol optics: the object and its host-side helpers (the entry points are below, with kernels_aerosol_optics.hip) ----
+// The tables of the MERRA-style aerosol optics.  On the device: one buffer holding, per precision, the head (rh_levels,
+// their differences, bin_lims) and the image of (value, slope) pairs laid out as kernels.hpp describes.
+struct ecckd_aerosol_lut {
+  int nband = 0, nbin = 0, nrh = 0, device = -1;
+  std::vector<double> bin_lims, rh_levels;   // host copies: the value checks of host arrays
+  char *dbuf = nullptr;
+  size_t off_head[2] = {0, 0}, off_image[2] = {0, 0};   // bytes; [0] fp64, [1] float
+};
+
+namespace {
+
+struct AerosolTables {
+  const double *dust, *salt, *sulf, *bcar, *bcar_rh, *ocar, *ocar_rh;
+};
+
+// rh_levels, d(i) = levels(i+1) - levels(i), bin_lims, rounded to `real` first
+template <typename real>
+std::vector<real> aerosol_head(int nbin, int nrh, const double *bin_lims, const double *rh_levels) {
+  std::vector<real> out;
+  out.reserve((size_t)2 * nrh - 1 + 2 * nbin);
+  for (int i = 0; i < nrh; ++i) out.push_back((real)rh_levels[i]);
+  for (int i = 0; i + 1 < nrh; ++i) out.push_back((real)rh_levels[i + 1] - (real)rh_levels[i]);
+  for (int i = 0; i < 2 * nbin; ++i) out.push_back((real)bin_lims[i]);
+  return out;
+}
+
+// the image [quantity][band][entry] (kernels.hpp): tables rounded to `real` first, slope = table(i+1) - table(i) in `real`
+template <typename real>
+std::vector<ecckd::CloudLutPair<real>> aerosol_image(int nband, int nbin, int nrh, const AerosolTables &t) {
+  typedef ecckd::CloudLutPair<real> Pair;
+  std::vector<Pair> out;
+  out.reserve((size_t)3 * nband * ecckd::kAoEntries(nbin, nrh));
+  auto rh_row = [&](const double *tbl, size_t at) {   // tbl(q, 1..nrh) at `at`, stride 3
+    for (int i = 0; i + 1 < nrh; ++i) {
+      const real lo = (real)tbl[at + (size_t)3 * i], hi = (real)tbl[at + (size_t)3 * (i + 1)];
+      out.push_back(Pair{lo, hi - lo});
+    }
+  };
+  for (int q = 0; q < 3; ++q)
+    for (int b = 0; b < nband; ++b) {
+      for (int n = 0; n < nbin; ++n) out.push_back(Pair{(real)t.dust[q + 3 * ((size_t)n + (size_t)nbin * b)], real(0)});
+      for (int n = 0; n < nbin; ++n) rh_row(t.salt, q + (size_t)3 * nrh * ((size_t)n + (size_t)nbin * b));
+      rh_row(t.sulf, q + (size_t)3 * nrh * b);
+      rh_row(t.bcar_rh, q + (size_t)3 * nrh * b);
+      rh_row(t.ocar_rh, q + (size_t)3 * nrh * b);
+      out.push_back(Pair{(real)t.bcar[q + (size_t)3 * b], real(0)});
+      out.push_back(Pair{(real)t.ocar[q + (size_t)3 * b], real(0)});
+    }
+  return out;
+}
+
+// the value checks of host arrays: the first complaint, or null.  Limits in the precision of the call.
+template <typename real>
+const char *aerosol_optics_check_host(const ecckd_aerosol_lut &ao, size_t n2, int nspec, const int *type, const real *size,
+                                      const real *mass, const real *relhum) {
+  const size_t n3 = n2 * nspec;
+  auto active = [&](size_t i) { return type[i] >= 1 && type[i] <= 7 && mass[i] > real(0); };
+  auto in_a_bin = [&](real r) {
+    for (int b = 0; b < ao.nbin; ++b)
+      if ((real)ao.bin_lims[2 * b] <= r && r < (real)ao.bin_lims[2 * b + 1]) return true;
+    return false;
+  };
+  for (size_t i = 0; i < n3; ++i)
+    if (type[i] < 0 || type[i] > 7) return "ecckd_aerosol_optics: aerosol type outside 0..7";
+  for (size_t i = 0; i < n3; ++i)
+    if (mass[i] < real(0)) return "ecckd_aerosol_optics: negative aerosol mass";
+  for (size_t i = 0; i < n3; ++i)
+    if (active(i) && type[i] <= 2 && !in_a_bin(size[i]))
+      return "ecckd_aerosol_optics: the size of an active dust or sea-salt cell lies in no bin";
+  for (size_t i = 0; i < n3; ++i) {
+    const int k = type[i];
+    if (active(i) && (k == 2 || k == 3 || k == 4 || k == 6)) {
+      const real rh = relhum[i % n2];
+      if (!(rh >= real(0) && rh <= real(1)))
+        return "ecckd_aerosol_optics: relative humidity outside [0,1] in a cell with an active humidity-dependent species";
+    }
+  }
   return nullptr;
 }
 
@@ -3023,6 +3110,130 @@ int ecckd_cloud_optics_f32(const ecckd_cloud_optics_t *co, int ncol, int nlay, c
                            void *stream) {
   return cloud_optics_impl(true, co, ncol, nlay, dp(clwp), dp(ciwp), dp(reliq), dp(reice), icergh, dp(tau), dp(ssa), dp(g),
                            memspace, stream);
+}
+
+// ---- aerosol optics (kernels_aerosol_optics.hip): species, mass, size and humidity to band properties ----
+
+int ecckd_aerosol_optics_create_lut(int nband, int nbin, int nrh, const double *bin_lims, const double *rh_levels,
+                                    const double *dust_tbl, const double *salt_tbl, const double *sulf_tbl, const double *bcar_tbl,
+                                    const double *bcar_rh_tbl, const double *ocar_tbl, const double *ocar_rh_tbl, int device,
+                                    ecckd_aerosol_optics_t **aerosol_optics) {
+  if (!aerosol_optics) return fail("ecckd_aerosol_optics_create_lut: null argument (the handle)");
+  *aerosol_optics = nullptr;
+  if (nband < 1 || nbin < 1) return fail("ecckd_aerosol_optics_create_lut: nband and nbin must be at least 1");
+  if (nrh < 2) return fail("ecckd_aerosol_optics_create_lut: nrh must be at least 2");
+  if (!rh_levels) return fail("ecckd_aerosol_optics_create_lut: rh_levels null, not strictly increasing, or NaN");
+  for (int i = 0; i + 1 < nrh; ++i)
+    if (!(rh_levels[i + 1] > rh_levels[i]))
+      return fail("ecckd_aerosol_optics_create_lut: rh_levels null, not strictly increasing, or NaN");
+  if (!bin_lims) return fail("ecckd_aerosol_optics_create_lut: bin_lims null, a bin empty or reversed, or bins overlapping");
+  for (int b = 0; b < nbin; ++b)
+    if (!(bin_lims[2 * b] < bin_lims[2 * b + 1]) || (b + 1 < nbin && !(bin_lims[2 * b + 1] <= bin_lims[2 * b + 2])))
+      return fail("ecckd_aerosol_optics_create_lut: bin_lims null, a bin empty or reversed, or bins overlapping");
+  if (!dust_tbl || !salt_tbl || !sulf_tbl || !bcar_tbl || !bcar_rh_tbl || !ocar_tbl || !ocar_rh_tbl)
+    return fail("ecckd_aerosol_optics_create_lut: null table (dust, salt, sulf, bcar, bcar_rh, ocar and ocar_rh are required)");
+  ecckd_aerosol_lut ao;
+  ao.nband = nband; ao.nbin = nbin; ao.nrh = nrh;
+  ao.bin_lims.assign(bin_lims, bin_lims + 2 * (size_t)nbin);
+  ao.rh_levels.assign(rh_levels, rh_levels + nrh);
+  if (device != -1) {   // (-1: a host-only object: getters and refusals work, the compute call fails)
+    if (check_device(device)) return 1;
+    const AerosolTables t{dust_tbl, salt_tbl, sulf_tbl, bcar_tbl, bcar_rh_tbl, ocar_tbl, ocar_rh_tbl};
+    const auto head64 = aerosol_head<double>(nbin, nrh, bin_lims, rh_levels);
+    const auto head32 = aerosol_head<float>(nbin, nrh, bin_lims, rh_levels);
+    const auto img64 = aerosol_image<double>(nband, nbin, nrh, t);
+    const auto img32 = aerosol_image<float>(nband, nbin, nrh, t);
+    ao.off_head[0] = 0;
+    ao.off_image[0] = align256(head64.size() * 8);
+    ao.off_head[1] = ao.off_image[0] + align256(img64.size() * 16);
+    ao.off_image[1] = ao.off_head[1] + align256(head32.size() * 4);
+    const size_t total = ao.off_image[1] + align256(img32.size() * 8);
+    std::vector<char> host(total, 0);
+    std::memcpy(host.data() + ao.off_head[0], head64.data(), head64.size() * 8);
+    std::memcpy(host.data() + ao.off_image[0], img64.data(), img64.size() * 16);
+    std::memcpy(host.data() + ao.off_head[1], head32.data(), head32.size() * 4);
+    std::memcpy(host.data() + ao.off_image[1], img32.data(), img32.size() * 8);
+    HIPCHK(hipMalloc(reinterpret_cast<void **>(&ao.dbuf), total));
+    if (hipMemcpy(ao.dbuf, host.data(), total, hipMemcpyHostToDevice) != hipSuccess) {
+      (void)hipFree(ao.dbuf);
+      return fail("ecckd_aerosol_optics_create_lut: copying the tables to the device failed");
+    }
+    ao.device = device;
+  }
+  *aerosol_optics = new ecckd_aerosol_lut(ao);
+  return 0;
+}
+
+void ecckd_aerosol_optics_destroy(ecckd_aerosol_optics_t *ao) {
+  if (!ao) return;
+  if (ao->device >= 0 && ao->dbuf) {
+    (void)hipSetDevice(ao->device);
+    (void)hipFree(ao->dbuf);
+  }
+  delete ao;
+}
+
+int ecckd_aerosol_optics_get_nband(const ecckd_aerosol_optics_t *ao) { return ao ? ao->nband : 0; }
+int ecckd_aerosol_optics_get_nbin(const ecckd_aerosol_optics_t *ao) { return ao ? ao->nbin : 0; }
+int ecckd_aerosol_optics_get_nrh(const ecckd_aerosol_optics_t *ao) { return ao ? ao->nrh : 0; }
+
+static int aerosol_optics_impl(bool f32, const ecckd_aerosol_optics_t *ao, int ncol, int nlay, int nspec, const int *aero_type,
+                               const double *aero_size, const double *aero_mass, const double *relhum, int accumulate, double *tau,
+                               double *ssa, double *g, int memspace, void *stream) {
+  if (!ao) return fail("ecckd_aerosol_optics: null aerosol-optics object");
+  if (nspec < 1) return fail("ecckd_aerosol_optics: nspec must be at least 1");
+  if ((ssa == nullptr) != (g == nullptr))
+    return fail("ecckd_aerosol_optics: ssa without g or g without ssa (pass both: two-stream, or neither: one-scalar)");
+  if (check_dims(ncol, nlay)) return 1;
+  if (!aero_type || !aero_size || !aero_mass || !relhum || !tau)
+    return fail("ecckd_aerosol_optics: null argument (aero_type, aero_size, aero_mass, relhum and tau are required)");
+  if (accumulate != 0 && accumulate != 1) return fail("ecckd_aerosol_optics: accumulate must be 0 or 1");
+  if (memspace != ECCKD_DEVICE && memspace != ECCKD_HOST && memspace != ECCKD_MIXED) return fail("ecckd: bad memspace");
+  const size_t n2 = (size_t)ncol * nlay, ns = n2 * nspec, n3 = n2 * ao->nband;
+  if (memspace != ECCKD_DEVICE) {   // (host inputs; device inputs are not checked: the call stays asynchronous)
+    const char *bad = f32 ? aerosol_optics_check_host(*ao, n2, nspec, aero_type, reinterpret_cast<const float *>(aero_size),
+                                                      reinterpret_cast<const float *>(aero_mass), reinterpret_cast<const float *>(relhum))
+                          : aerosol_optics_check_host(*ao, n2, nspec, aero_type, aero_size, aero_mass, relhum);
+    if (bad) return fail(bad);
+  }
+  if (ao->device < 0)
+    return fail("ecckd_aerosol_optics: host-only object (device -1): no GPU, no compute (there is no CPU fallback)");
+  if (check_device(ao->device)) return 1;
+  if (ncol == 0) return 0;
+  ecckd::AerosolOpticsArgs a{};
+  a.ncol = ncol; a.nlay = nlay; a.nband = ao->nband; a.nspec = nspec; a.f32 = f32; a.accumulate = accumulate;
+  a.cus = simd_slots(ao->device) / 4;
+  a.nbin = ao->nbin; a.nrh = ao->nrh;
+  a.head = ao->dbuf + ao->off_head[f32];
+  a.image = ao->dbuf + ao->off_image[f32];
+  Stage st(ao->device, memspace, stream, f32);
+  if (st.open([&] {
+        a.type = st.in(aero_type, ns); a.size = st.in(aero_size, ns); a.mass = st.in(aero_mass, ns); a.relhum = st.in(relhum, n2);
+        if (accumulate) {
+          a.tau = st.inout_big(tau, n3); a.ssa = st.inout_big(ssa, n3); a.g = st.inout_big(g, n3);
+        } else {
+          a.tau = st.out(tau, n3, kBig); a.ssa = st.out(ssa, n3, kBig); a.g = st.out(g, n3, kBig);
+        }
+      }))
+    return 1;
+  {
+    ProfScope prof("aerosol_optics", st.stream);
+    HIPCHK(ecckd::launch_aerosol_optics(a, st.stream));
+  }
+  return st.close();
+}
+
+int ecckd_aerosol_optics(const ecckd_aerosol_optics_t *ao, int ncol, int nlay, int nspec, const int *aero_type,
+                         const double *aero_size, const double *aero_mass, const double *relhum, int accumulate, double *tau,
+                         double *ssa, double *g, int memspace, void *stream) {
+  return aerosol_optics_impl(false, ao, ncol, nlay, nspec, aero_type, aero_size, aero_mass, relhum, accumulate, tau, ssa, g,
+                             memspace, stream);
+}
+int ecckd_aerosol_optics_f32(const ecckd_aerosol_optics_t *ao, int ncol, int nlay, int nspec, const int *aero_type,
+                             const float *aero_size, const float *aero_mass, const float *relhum, int accumulate, float *tau,
+                             float *ssa, float *g, int memspace, void *stream) {
+  return aerosol_optics_impl(true, ao, ncol, nlay, nspec, aero_type, dp(aero_size), dp(aero_mass), dp(relhum), accumulate,
+                             dp(tau), dp(ssa), dp(g), memspace, stream);
 }
 
 // ---- McICA cloud sampling (kernels_cloud_sampling.hip) ----

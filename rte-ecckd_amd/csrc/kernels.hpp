@@ -281,6 +281,32 @@ struct CloudOpticsArgs {
 size_t cloud_optics_image_bytes(int nband, int nsize_liq, int nsize_ice, bool two_stream, bool f32);
 hipError_t launch_cloud_optics(const CloudOpticsArgs &a, hipStream_t s);
 
+// Aerosol optics (kernels_aerosol_optics.hip; the definition is in include/ecckd_hip.h, ecckd_aerosol_optics): type, size,
+// mass (ncol,nlay,nspec) and relative humidity (ncol,nlay) to band planes (ncol,nlay,nband), written or -- accumulate --
+// added with ecckd_increment's operations.  The image is [quantity: ext, ssa, asy][band][entry] pairs of the call's
+// precision; the entries of a row: dust[nbin], salt[nbin][nrh-1], sulfate[nrh-1], hydrophilic black carbon[nrh-1],
+// hydrophilic organic carbon[nrh-1], hydrophobic black carbon, hydrophobic organic carbon.  The head: rh_levels[nrh],
+// d[nrh-1] = levels[i+1] - levels[i], bin_lims[2*nbin], in the call's precision.
+__host__ __device__ constexpr int kAoEntries(int nbin, int nrh) { return nbin * nrh + 3 * (nrh - 1) + 2; }
+constexpr size_t kAerosolOpticsLdsBytes = kCloudOpticsLdsBytes;   // the image at most this large: staged in LDS; else L2
+constexpr int kAoMaxRegisterSpecies = 16;  // more species per call take the compatibility instantiation (ns = 0 below)
+// resident blocks of 256 threads per CU (= waves per SIMD the kernel is compiled for) with ns species slots in registers
+__host__ __device__ constexpr int kAoBlocksPerCu(int ns) { return ns >= 1 && ns <= 2 ? 8 : ns <= 8 ? 4 : 2; }
+struct AerosolOpticsArgs {
+  int ncol, nlay, nband, nspec, f32, accumulate;
+  int cus;                         // compute units of the device (sizes the grid); 0: 256
+  int nbin, nrh;
+  const void *head, *image;        // device, in the call's precision
+  const int *type;
+  const double *size, *mass, *relhum;
+  double *tau, *ssa, *g;           // ssa and g null: the one-scalar form
+};
+// bytes of the image as the kernel stages it (the one-scalar form leaves the asymmetry rows out)
+size_t aerosol_optics_image_bytes(int nband, int nbin, int nrh, bool two_stream, bool f32);
+// blocks of 256 threads the call launches: what is resident, at most one block per 256 cells (lds_image_bytes 0: L2 route)
+unsigned aerosol_optics_grid(int ncol, int nlay, int nspec, int cus, size_t lds_image_bytes);
+hipError_t launch_aerosol_optics(const AerosolOpticsArgs &a, hipStream_t s);
+
 // McICA cloud mask (kernels_cloud_sampling.hip; the definition is in include/ecckd_hip.h, ecckd_cloud_mask_sample):
 // cloud_frac (ncol,nlay), overlap_param (ncol,nlay-1; exp_ran only), mask (ncol,nlay); 1 <= ngpt <= 64
 hipError_t launch_cloud_mask_sample(int ncol, int nlay, int ngpt, int exp_ran, const double *cloud_frac, const double *overlap_param,

@@ -156,6 +156,76 @@ def cloud_lut(nband, nsize_liq, nsize_ice, nrghice):
     return out
 
 
+F_AER_COL, F_AER_CELL, F_AER_ODD, F_AER_KIND, F_AER_SIZE, F_AER_MASS, F_AER_RH = range(25, 32)
+AERO_SIZE_LWR, AERO_SIZE_UPR = 0.1, 10.0   # microns: the span of the bins of ``aerosol_lut`` (MERRA's dust bins span it)
+
+
+def aerosol_lut(nband, nbin, nrh):
+    """Smooth analytic aerosol-optics tables in the layout (and with the argument names) of ``AerosolOptics.load``: a dict
+    with ``merra_aero_bin_lims`` ``(nbin, 2)`` (microns; contiguous bins, geometric between 0.1 and 10), ``aero_rh``
+    ``(nrh,)`` (unevenly spaced like MERRA's: the first half of the levels coarse from 0 up to 0.8, the rest fine from
+    0.8 to 0.99), ``aero_dust_tbl`` ``(nband, nbin, 3)``, ``aero_salt_tbl`` ``(nband, nbin, nrh, 3)``, ``aero_sulf_tbl``,
+    ``aero_bcar_rh_tbl``, ``aero_ocar_rh_tbl`` ``(nband, nrh, 3)`` and ``aero_bcar_tbl``, ``aero_ocar_tbl`` ``(nband, 3)``,
+    float64; the last axis is mass extinction (m2 kg-1), ssa, asymmetry.  Every quantity rises strictly with the humidity
+    (hygroscopic growth) and differs between bins, bands and types, so a wrong index, weight, bin or type shows."""
+    edges = AERO_SIZE_LWR * (AERO_SIZE_UPR / AERO_SIZE_LWR) ** (np.arange(nbin + 1, dtype=np.float64) / nbin)
+    lims = np.stack([edges[:-1], edges[1:]], axis=1)
+    ncoarse = nrh // 2
+    rh = np.concatenate([np.linspace(0.0, 0.8, ncoarse, endpoint=False), np.linspace(0.8, 0.99, nrh - ncoarse)])
+    band = ((np.arange(nband, dtype=np.float64) + 1.0) / nband)[:, None, None]   # (0, 1]
+    binpos = (np.arange(nbin, dtype=np.float64) / nbin)[None, :, None]           # [0, 1)
+    hum = rh[None, None, :]
+
+    def table(k, c_ext, growth, ssa0):   # (nband, nbin, nrh, 3) of type code k
+        ext = c_ext * (0.6 + 0.4 * band) / (1.0 + 4.0 * binpos) * (1.0 + growth * hum / (1.05 - hum))
+        ssa = ssa0 - 0.2 * band - 0.02 * binpos + 0.08 * hum
+        asy = 0.6 + 0.03 * k + 0.02 * band + 0.05 * binpos + 0.1 * hum
+        return np.ascontiguousarray(np.stack(np.broadcast_arrays(ext, ssa, asy), axis=-1))
+
+    dust = table(1, 600.0, 0.0, 0.90)
+    salt = table(2, 900.0, 1.0, 0.88)
+    sulf = table(3, 3000.0, 0.8, 0.86)
+    bcar_rh = table(4, 9000.0, 0.3, 0.35)
+    bcar = table(5, 8000.0, 0.0, 0.30)
+    ocar_rh = table(6, 4000.0, 0.5, 0.80)
+    ocar = table(7, 3500.0, 0.0, 0.75)
+    c = np.ascontiguousarray
+    return dict(merra_aero_bin_lims=c(lims), aero_rh=c(rh), aero_dust_tbl=c(dust[:, :, 0, :]), aero_salt_tbl=salt,
+                aero_sulf_tbl=c(sulf[:, 0, :, :]), aero_bcar_tbl=c(bcar[:, 0, 0, :]), aero_bcar_rh_tbl=c(bcar_rh[:, 0, :, :]),
+                aero_ocar_tbl=c(ocar[:, 0, 0, :]), aero_ocar_rh_tbl=c(ocar_rh[:, 0, :, :]))
+
+
+def aerosols(c0, ncol, nlay, nspec):
+    """What a host model carries for its aerosol tracers, for columns ``c0 .. c0+ncol-1``, top layer first: ``aero_type``
+    int32, ``aero_size`` (microns) and ``aero_mass`` (kg m-2), ``(nspec, nlay, ncol)``, and ``relhum`` ``(nlay, ncol)`` in
+    [0, 1).  Plane ``s`` is mostly one type, ``1 + s % 7``: dust lies aloft (0.3-0.7 of the grid) in about 0.4 of the
+    columns, sea salt and sulfate in the lowest third in about 0.6 of them, the carbons in the lower half in about 0.3;
+    inside its slab a species fills four cells in five, and one such cell in ten holds a type drawn from all seven
+    instead.  Every other cell holds none (type 0, mass 0): well over a third of all cells.  Masses are 1e-6 to 1e-4
+    kg m-2; sizes are defined in every cell, log-uniform over the bins of ``aerosol_lut``."""
+    s = np.arange(nspec, dtype=np.uint64)[:, None, None]
+    c = np.arange(c0, c0 + ncol, dtype=np.uint64)[None, None, :]
+    jm = np.arange(1, nlay + 1, dtype=np.uint64)[None, :, None]
+    js = jm | (s << np.uint64(40))                         # one stream position per (species, layer): above the column's bits
+    main = (1 + np.arange(nspec) % 7)[:, None, None]
+    lay = np.arange(nlay)[None, :, None]
+
+    def slab(lo, hi):   # layers [lo*nlay, hi*nlay), at least one
+        l0 = min(int(lo * nlay), nlay - 1)
+        return (lay >= l0) & (lay < max(l0 + 1, int(hi * nlay)))
+
+    where = np.where(main == 1, slab(0.3, 0.7), np.where(main <= 3, slab(2.0 / 3.0, 1.0), slab(0.5, 1.0)))
+    share = np.where(main == 1, 0.4, np.where(main <= 3, 0.6, 0.3))
+    present = where & (uniform(c, F_AER_COL, s) < share) & (uniform(c, F_AER_CELL, js) < 0.8)
+    odd = uniform(c, F_AER_ODD, js) < 0.1
+    other = 1 + np.minimum(6, np.floor(7.0 * uniform(c, F_AER_KIND, js)).astype(np.int64))
+    aero_type = np.where(present, np.where(odd, other, main), 0).astype(np.int32)
+    aero_mass = np.where(present, 1e-6 * 100.0 ** uniform(c, F_AER_MASS, js), 0.0)
+    aero_size = AERO_SIZE_LWR * (AERO_SIZE_UPR / AERO_SIZE_LWR) ** uniform(c, F_AER_SIZE, js)
+    relhum = uniform(c[0], F_AER_RH, jm[0]) ** 0.7
+    return tuple(np.ascontiguousarray(a) for a in (aero_type, aero_size, aero_mass, relhum))
+
+
 def gas_items(cols):
     """[(name, array, col_stride, lay_stride)] in GAS_ORDER for oracle-style consumers: full
     arrays are (nlay,ncol) -> strides (1,ncol); per-column arrays (1,0); scalars (0,0)."""
