@@ -565,6 +565,80 @@ int ecckd_sw_fluxes_clear_allsky(const ecckd_model_t *model, int ncol, int nlay,
                                  void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * The shortwave on the daylit columns only.  Every shortwave call above computes every column it is given; on a global grid
+ * the sun is below the horizon in about half of them.  The reference's driver computes those with mu0 = 1 "for a better
+ * measure of timing" and zeroes their fluxes afterwards (ecckd_rfmip_sw.F90:103-108,143-145,156-161); a production host
+ * compacts the daylit columns in front of the shortwave and scatters the fluxes back.  These calls do that on the device.
+ *
+ * ecckd_daylit_columns (+ _f32: float mu0): day_index(0..nday-1) <- the columns i (0-BASED, ASCENDING) with
+ *   mu0(i) > mu0_min, compared in double; a NaN mu0 is night.  day_index has room for ncol entries, in `memspace`; the entries
+ *   from nday on are unspecified.  *nday is a HOST integer, valid on return: this is the one call of the group that
+ *   synchronises (on `stream`), so it CANNOT BE CAPTURED into a graph (refused with a message on a capturing stream), while
+ *   ecckd_sw_fluxes_daylit with a list made beforehand can.  The list is deterministic (ballot / popcount in the wave, a scan of
+ *   the block counts; no atomic counter).  Scratch (ECCKD_DEVICE): 4*(ceil(ncol/256) + 1) bytes of the stream's block.
+ *
+ * ecckd_gather_columns / ecckd_scatter_columns: for hosts on the unfused route (ecckd_gas_optics_sw + ecckd_increment +
+ *   ecckd_rte_sw).  An array is viewed as (ninner, ncol, nouter), ninner fastest; elem_bytes is 4 or 8 (8: fp64 and the
+ *   64-bit mask words).  ninner = 1 serves every (ncol,nlay[,n]) array (nouter = nlay[*n]), nouter = 1 the (nband,ncol)
+ *   albedos.
+ *     gather:   dst(i,k,o) = src(i,day_index(k),o), k < nday; dst is (ninner, nday, nouter).
+ *     scatter:  dst(i,day_index(k),o) = src(i,k,o), and `fill` in EVERY column of dst that the list does not hold (one pass:
+ *               each element of dst is stored once); src is (ninner, nday, nouter).  fill is stored as a double in 8-byte
+ *               elements and rounded to float in 4-byte elements (0 serves the mask words too).  nday = 0 fills dst.
+ *   The list must be strictly ascending (the scatter finds a column by bisection).  With ECCKD_HOST a list that is not, or
+ *   that leaves [0,ncol), is refused with a message.  A DEVICE list is not checked: the gather clamps an entry outside
+ *   [0,ncol) and the scatter skips it, so no list can make a kernel address memory outside its arrays, but the results for
+ *   such a list are undefined.  Asynchronous on `stream` with ECCKD_DEVICE, no scratch, capturable.
+ *
+ * ecckd_sw_fluxes_daylit: the superset of the fused shortwave calls, on the columns of the list.  After nday and day_index
+ *   the argument list is that of ecckd_sw_fluxes_clear_allsky, and EVERY ARRAY IS DIMENSIONED WITH THE FULL ncol.
+ *     tau_p NULL (then ssa_p, g_p, cloud_mask and the clear-sky outputs NULL too; nband_p ignored): ecckd_sw_fluxes;
+ *     tau_p, ssa_p, g_p given: ecckd_sw_fluxes_allsky, with cloud_mask ecckd_sw_fluxes_allsky_mcica;
+ *     flux_up_clear and flux_dn_clear given (flux_dir_clear optional) as well: ecckd_sw_fluxes_clear_allsky.
+ *   The call gathers every input to nday columns, runs that call's pipeline unchanged on them -- with the solver "sw_solver"
+ *   picks for nday columns, at any layer count -- and scatters each requested output into the caller's (ncol,nlay+1) array,
+ *   with +0 at every level of the columns left out.  The fluxes of a listed column are BIT FOR BIT those of the existing
+ *   call on the gathered columns.  nday = 0 only zeroes the outputs.  An output that is not requested is never written; the
+ *   inputs are never written.  fp64, fast arithmetic mode only; ECCKD_HOST stages through the model's arena; ECCKD_DEVICE is
+ *   asynchronous on `stream`.
+ *   Refused with a message before any device is asked for, in this order: the list of ecckd_sw_fluxes_clear_allsky in its
+ *   order (the particle entries only with tau_p given; tau_p NULL with ssa_p, g_p, cloud_mask or a clear-sky output); nday
+ *   outside 0..ncol; day_index NULL with nday > 0; with ECCKD_HOST a list that is not strictly ascending or that leaves
+ *   [0,ncol); then what ecckd_sw_fluxes refuses.  A device list is not checked (the kernel rule above holds).
+ *   Scratch (ECCKD_DEVICE, from the stream's block; a host that owns the block, ecckd_set_stream_scratch, sizes it so), with
+ *   a256 = align256 and every count taken for nday columns:
+ *     ecckd_sw_fluxes_daylit_scratch_bytes(model, ncol, nday, nlay, ngas_arrays, with_particles, delta_scale, with_mask, with_clear)
+ *       = what the inner call needs for nday columns (the formula at ecckd_sw_fluxes, plus 3*a256(nday*nlay*nband*8) with
+ *         particles and delta_scale)
+ *       + a256(nday*(nlay+1)*8) + a256(nday*nlay*8)                  plev, tlay
+ *       + 2*a256(nday*8) + 2*a256(nband*nday*8)                      mu0, toa_scale (whether given or not), the two albedos
+ *       + ngas_arrays*a256(nday*nlay*8)                              the gas arrays with a non-zero column stride (the others,
+ *                                                                    and the scalars, are read in place)
+ *       + (with_particles ? 3*a256(nday*nlay*nband*8) : 0) + (with_mask ? a256(nday*nlay*8) : 0)
+ *       + (with_clear ? 6 : 3)*a256(nday*(nlay+1)*8)                 the fluxes of the inner call (direct beams whether given or not)
+ *     in that order, the inner call's share first; 0 for nday = 0; ncol does not enter (the scatter works in place).  The
+ *     capture rules of the stream's block apply: capture after one warm-up call on the stream, or with a caller-owned block.
+ * --------------------------------------------------------------------------------------- */
+int ecckd_daylit_columns(int device, int ncol, const double *mu0, double mu0_min, int *day_index, int *nday, int memspace,
+                         void *stream);
+int ecckd_daylit_columns_f32(int device, int ncol, const float *mu0, double mu0_min, int *day_index, int *nday, int memspace,
+                             void *stream);
+int ecckd_gather_columns(int device, int ninner, int ncol, int nouter, int elem_bytes, int nday, const int *day_index,
+                         const void *src, void *dst, int memspace, void *stream);
+int ecckd_scatter_columns(int device, int ninner, int ncol, int nouter, int elem_bytes, int nday, const int *day_index,
+                          const void *src, void *dst, double fill, int memspace, void *stream);
+size_t ecckd_sw_fluxes_daylit_scratch_bytes(const ecckd_model_t *model, int ncol, int nday, int nlay, int ngas_arrays,
+                                            int with_particles, int delta_scale, int with_mask, int with_clear);
+int ecckd_sw_fluxes_daylit(const ecckd_model_t *model, int ncol, int nlay, int nday, const int *day_index, const double *plev,
+                           const double *tlay, int ngas, const char *gas_names, const double *const *vmr,
+                           const long long *vmr_col_stride, const long long *vmr_lay_stride, const double *vmr_scalar,
+                           int top_at_1, const double *mu0, const double *toa_scale, const double *sfc_alb_dir,
+                           const double *sfc_alb_dif, int nband_p, const double *tau_p, const double *ssa_p, const double *g_p,
+                           int delta_scale, const unsigned long long *cloud_mask, double *flux_up, double *flux_dn,
+                           double *flux_dir, double *flux_up_clear, double *flux_dn_clear, double *flux_dir_clear, int memspace,
+                           void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * Longwave surface-temperature Jacobian: the derivative of the upward flux profile with respect to the surface
  * temperature, RTE-RRTMGP's optional flux_up_Jac(ncol,nlay+1) of rte_lw (from sources%sfc_source_Jac) and, divided by its
  * surface value, ecRad's lw_derivatives.  A host gets it with the fluxes of the same call instead of calling the fluxes

@@ -41,7 +41,7 @@ NAME_LEN = 32
 _SOURCES = ["kernels_gas_fused.hip", "kernels_tau.hip", "kernels_planck.hip", "kernels_rte_lw.hip", "kernels_rte_lw_split.hip",
             "kernels_rte_lw_jac.hip", "kernels_rte_lw_2str.hip",
             "kernels_rte_sw.hip", "kernels_rte_sw_sys.hip", "kernels_rte_gpt.hip", "kernels_optical_props.hip",
-            "kernels_cloud_sampling.hip", "kernels_cloud_optics.hip", "kernels_aerosol_optics.hip",
+            "kernels_cloud_sampling.hip", "kernels_cloud_optics.hip", "kernels_aerosol_optics.hip", "kernels_columns.hip",
             "capi.cpp", "nc_capi.cpp", "model.cpp", "cdf1.cpp"]
 _HEADERS = ["kernels.hpp", "wave_pair.hpp", "sw_two_stream.hpp", "sw_two_stream_body.inc", "lw_two_stream.hpp", "lw_layer.hpp", "planck_at.hpp", "model.hpp", "cdf1.hpp", os.path.join("..", "..", "include", "ecckd_hip.h"),
             os.path.join("..", "..", "include", "ecckd_nc.h"), os.path.join("..", "..", "include", "rte_kernels_hip.h"),
@@ -207,6 +207,16 @@ def lib():
         L.ecckd_sw_fluxes_clear_allsky.argtypes = ([C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 2 + [C.c_int, C.c_char_p] +
                                                    [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 3 +
                                                    [C.c_int] + [C.c_void_p] * 7 + [C.c_int, C.c_void_p])
+    if hasattr(L, "ecckd_sw_fluxes_daylit"):   # (an older build lacks them: tools/bench_sw_daylit.py times the parent's library)
+        for f in ("ecckd_daylit_columns", "ecckd_daylit_columns_f32"):
+            getattr(L, f).argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_void_p, C.POINTER(C.c_int), C.c_int, C.c_void_p]
+        L.ecckd_gather_columns.argtypes = [C.c_int] * 6 + [C.c_void_p] * 3 + [C.c_int, C.c_void_p]
+        L.ecckd_scatter_columns.argtypes = [C.c_int] * 6 + [C.c_void_p] * 3 + [C.c_double, C.c_int, C.c_void_p]
+        L.ecckd_sw_fluxes_daylit_scratch_bytes.restype = C.c_size_t
+        L.ecckd_sw_fluxes_daylit_scratch_bytes.argtypes = [C.c_void_p] + [C.c_int] * 8
+        L.ecckd_sw_fluxes_daylit.argtypes = ([C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p] + [C.c_void_p] * 2 +
+                                             [C.c_int, C.c_char_p] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 4 + [C.c_int] +
+                                             [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 7 + [C.c_int, C.c_void_p])
     if hasattr(L, "ecckd_lw_fluxes_jac"):   # (an older build lacks them: tools/bench_lw_jac.py --parent-lib)
         L.ecckd_planck_sfc_source_jac.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.ecckd_rte_lw_jac.argtypes = [C.c_int] * 6 + [C.c_void_p] * 6 + [C.c_int] + [C.c_void_p] * 6 + [C.c_int, C.c_void_p]
@@ -509,6 +519,111 @@ def sample_cloud_mask(cloud_frac, ngpt, overlap="max_ran", overlap_param=None, s
     if rc:
         raise ValueError(last_error())
     return mask
+
+
+# ------------------------------------------------------------------------------------------
+# column compaction: the shortwave on the daylit columns (include/ecckd_hip.h, "The shortwave on the daylit columns only")
+# ------------------------------------------------------------------------------------------
+def daylit_columns(mu0, mu0_min=0.0, device=0):
+    """``ecckd_daylit_columns`` (float32 ``mu0``: ``_f32``): the ascending, 0-based list of the columns with
+    ``mu0 > mu0_min`` (compared in double; NaN is night) and their number, ``(index, nday)``.  ``index`` is an int32 array of
+    ``nday`` entries where ``mu0`` lives: numpy for numpy, a device tensor for a device tensor (``device`` is then the
+    tensor's).  The call synchronises -- ``nday`` is a Python int -- and cannot be captured into a graph; ``sw_fluxes_daylit``
+    with the list can.  Raises ValueError with the library's message."""
+    f32 = _is_f32(mu0)
+    if mu0.ndim != 1:
+        raise ValueError("daylit_columns: mu0 must have one dimension (ncol,)")
+    ncol = int(mu0.shape[0])
+    try:
+        space = _space_of([mu0])
+        mp = _ptr(mu0, (ncol,), "mu0", f32)
+    except TypeError as e:
+        raise ValueError(str(e))
+    if space == DEVICE:
+        import torch
+        index = torch.empty((ncol,), dtype=torch.int32, device=mu0.device)
+        ip, device = C.c_void_p(index.data_ptr()), _device_of(mu0)
+    else:
+        index = np.zeros((ncol,), dtype=np.int32)
+        ip = C.c_void_p(index.ctypes.data)
+    nday = C.c_int(0)
+    rc = (lib().ecckd_daylit_columns_f32 if f32 else lib().ecckd_daylit_columns)(
+        int(device), ncol, mp, float(mu0_min), ip, C.byref(nday), space, _stream(space))
+    if rc:
+        raise ValueError(last_error())
+    return index[:nday.value], nday.value
+
+
+def _raw(a, what):
+    """(data pointer, element size) of a contiguous array of 4- or 8-byte elements (numpy or torch)."""
+    if _is_torch(a):
+        if not a.is_contiguous():
+            raise TypeError(what + ": need a contiguous tensor")
+        size = a.element_size()
+        p = C.c_void_p(a.data_ptr())
+    else:
+        if not isinstance(a, np.ndarray) or not a.flags.c_contiguous:
+            raise TypeError(what + ": need a C-contiguous ndarray")
+        size = a.dtype.itemsize
+        p = C.c_void_p(a.ctypes.data)
+    if size not in (4, 8):
+        raise TypeError(what + ": need 4- or 8-byte elements")
+    return p, size
+
+
+def _column_view(shape, axis):
+    """(ninner, ncol, nouter) of a C-ordered array whose `axis` runs over the columns."""
+    axis = axis % len(shape)
+    return int(np.prod(shape[axis + 1:], dtype=np.int64)), int(shape[axis]), int(np.prod(shape[:axis], dtype=np.int64)), axis
+
+
+def gather_columns(src, index, axis=-1, device=0):
+    """``ecckd_gather_columns``: ``src`` with its column axis ``axis`` reduced to the columns of ``index`` (an int32 list as
+    ``daylit_columns`` returns it), as a new array where ``src`` lives.  Any dtype of 4 or 8 bytes; ``axis = -1`` serves the
+    ``(nlay, ncol)`` and ``(n, nlay, ncol)`` arrays, ``axis = 0`` the ``(ncol, nband)`` albedos.  Raises ValueError with the
+    library's message."""
+    ninner, ncol, nouter, axis = _column_view(src.shape, axis)
+    nday = int(index.shape[0])
+    try:
+        space = _space_of([src, index])
+        sp, size = _raw(src, "src")
+        ip = _int32_ptr(index, (nday,), "index")
+    except TypeError as e:
+        raise ValueError(str(e))
+    shape = tuple(src.shape[:axis]) + (nday,) + tuple(src.shape[axis + 1:])
+    if space == DEVICE:
+        import torch
+        dst = torch.empty(shape, dtype=src.dtype, device=src.device)
+        dp, device = C.c_void_p(dst.data_ptr()), _device_of(src)
+    else:
+        dst = np.empty(shape, dtype=src.dtype)
+        dp = C.c_void_p(dst.ctypes.data)
+    if lib().ecckd_gather_columns(int(device), ninner, ncol, nouter, size, nday, ip, sp, dp, space, _stream(space)):
+        raise ValueError(last_error())
+    return dst
+
+
+def scatter_columns(src, index, dst, axis=-1, fill=0.0, device=0):
+    """``ecckd_scatter_columns``: ``dst[.., index[k], ..] = src[.., k, ..]`` along the column axis ``axis`` and ``fill`` in every
+    column of ``dst`` that ``index`` does not list; ``dst`` is written in full, in one pass.  ``index`` must ascend.  Raises
+    ValueError with the library's message."""
+    ninner, ncol, nouter, axis = _column_view(dst.shape, axis)
+    nday = int(index.shape[0])
+    want = tuple(dst.shape[:axis]) + (nday,) + tuple(dst.shape[axis + 1:])
+    try:
+        space = _space_of([src, index, dst])
+        sp, size = _raw(src, "src")
+        dp, dsize = _raw(dst, "dst")
+        ip = _int32_ptr(index, (nday,), "index")
+    except TypeError as e:
+        raise ValueError(str(e))
+    if tuple(src.shape) != want or src.dtype != dst.dtype or size != dsize:
+        raise ValueError("scatter_columns: src is %s %s, expected %s %s" % (tuple(src.shape), src.dtype, want, dst.dtype))
+    if space == DEVICE:
+        device = _device_of(dst)
+    if lib().ecckd_scatter_columns(int(device), ninner, ncol, nouter, size, nday, ip, sp, dp, float(fill), space, _stream(space)):
+        raise ValueError(last_error())
+    return dst
 
 
 # ------------------------------------------------------------------------------------------
@@ -1592,6 +1707,46 @@ class GasOpticsEcckd:
             P(sfc_alb_dir, (ncol, nband), "sfc_alb_dir"), P(sfc_alb_dif, (ncol, nband), "sfc_alb_dif"),
             P(fluxes.flux_up, (nlay + 1, ncol), "flux_up"), P(fluxes.flux_dn, (nlay + 1, ncol), "flux_dn"),
             P(fluxes.flux_dn_dir, (nlay + 1, ncol), "flux_dn_dir"), space, _stream(space))
+        return last_error() if rc else ""
+
+    def sw_fluxes_daylit(self, plev, tlay, gas_desc, top_at_1, mu0, sfc_alb_dir, sfc_alb_dif, fluxes, particles=None,
+                         fluxes_clear=None, delta_scale=True, toa_scale=None, cloud_mask=None, day_index=None, mu0_min=0.0):
+        """``ecckd_sw_fluxes_daylit``: the shortwave on the daylit columns only.  Every array has the full ``ncol``; the
+        columns of ``day_index`` (an int32 list as ``daylit_columns`` returns it; None: the call selects ``mu0 > mu0_min``
+        first, which synchronises) are gathered, computed by the pipeline of ``sw_fluxes`` (``particles`` None),
+        ``sw_fluxes_allsky`` (``particles``, with ``cloud_mask`` the McICA form) or ``sw_fluxes_clear_allsky`` (``fluxes_clear``
+        as well) -- bit for bit what that call gives on the gathered columns -- and scattered back; every other column of the
+        requested outputs is 0 at every level.  float64, fast arithmetic mode; numpy or device tensors; with device tensors
+        and a list made beforehand the call is asynchronous and can be captured.  Returns the error message ('' = success)."""
+        nlay, ncol = tlay.shape
+        nband = self.get_nband()
+        clear = fluxes_clear if fluxes_clear is not None else FluxesBroadband()
+        part = particles if particles is not None else OpticalProps2str()
+        try:
+            space = _space_of([plev, tlay, mu0, toa_scale, sfc_alb_dir, sfc_alb_dif, fluxes.flux_up, fluxes.flux_dn,
+                               clear.flux_up, clear.flux_dn, part.tau, getattr(part, "ssa", None), getattr(part, "g", None), day_index])
+            if day_index is None:
+                day_index, _ = daylit_columns(mu0, mu0_min)
+            nday = int(day_index.shape[0])
+            ip = _int32_ptr(day_index, (nday,), "day_index") if nday else None
+            mp = None if cloud_mask is None else _mask_ptr(cloud_mask, nlay, ncol, space)
+            n, names, ptrs, cs, ls, sc, keep = self._gas_args(gas_desc, ncol, nlay, space)
+            nbp = int(part.tau.shape[0]) if part.tau is not None else 0
+            shp = (nbp, nlay, ncol)
+            pp = (_ptr(part.tau, shp, "particles.tau"), _ptr(getattr(part, "ssa", None), shp, "particles.ssa"),
+                  _ptr(getattr(part, "g", None), shp, "particles.g"))
+            out = tuple(_ptr(a, (nlay + 1, ncol), what) for a, what in (
+                (fluxes.flux_up, "flux_up"), (fluxes.flux_dn, "flux_dn"), (fluxes.flux_dn_dir, "flux_dn_dir"),
+                (clear.flux_up, "flux_up_clear"), (clear.flux_dn, "flux_dn_clear"), (clear.flux_dn_dir, "flux_dn_dir_clear")))
+        except KeyError as e:
+            return str(e.args[0])
+        except (TypeError, ValueError) as e:
+            return str(e)
+        rc = lib().ecckd_sw_fluxes_daylit(
+            self._need(), ncol, nlay, nday, ip, _ptr(plev, (nlay + 1, ncol), "plev"), _ptr(tlay, (nlay, ncol), "tlay"), n, names,
+            ptrs, cs, ls, sc, int(bool(top_at_1)), _ptr(mu0, (ncol,), "mu0"), _ptr(toa_scale, (ncol,), "toa_scale"),
+            _ptr(sfc_alb_dir, (ncol, nband), "sfc_alb_dir"), _ptr(sfc_alb_dif, (ncol, nband), "sfc_alb_dif"), nbp, *pp,
+            int(bool(delta_scale)), mp, *out, space, _stream(space))
         return last_error() if rc else ""
 
 

@@ -573,6 +573,10 @@ class Stage {
   unsigned long long *out(unsigned long long *p, size_t n) { return static_cast<unsigned long long *>(place(p, n * 8, false, false, true)); }
   // aerosol type codes: 4-byte integers whatever the precision of the call
   const int *in(const int *p, size_t n) { return static_cast<int *>(place(p, n * 4, false, true, false)); }
+  // column lists (ecckd_daylit_columns) and arrays given by their size in bytes (ecckd_gather_columns / _scatter_columns)
+  int *out(int *p, size_t n) { return static_cast<int *>(place(p, n * 4, false, false, true)); }
+  const void *in_bytes(const void *p, size_t bytes) { return place(p, bytes, false, true, false); }
+  void *out_bytes(void *p, size_t bytes) { return place(p, bytes, false, false, true); }
   // a spectral array the call reads and writes (ECCKD_MIXED leaves it on the device)
   double *inout_big(double *p, size_t n) { return static_cast<double *>(place(p, n * es, kBig, true, true)); }
 
@@ -2741,6 +2745,18 @@ int ecckd_lw_fluxes_jac(const ecckd_model_t *m, int ncol, int nlay, const double
 // mask: ecckd_sw_fluxes_allsky_mcica -- the cloud mask (ncol,nlay), in the memory space of the call, or null
 struct SwParticles { const double *tau, *ssa, *g; int delta_scale; const unsigned long long *mask = nullptr; };
 
+// The work block of sw_fluxes_impl: the optical depth, the solver's room, the three scaled band planes (or none)
+struct SwWork {
+  size_t tau_bytes, solver, plane;
+  SwWork(const ecckd_model *m, bool f32, int ncol, int nlay, bool scaled_planes) {
+    const Counts n(ncol, nlay, m->ng, m->nband);
+    tau_bytes = align256(n.lay_g * esz(f32));
+    solver = sw_fluxes_solver_bytes(m->device, ncol, nlay, m->ng);
+    plane = scaled_planes ? align256(n.lay_b * esz(f32)) : 0;
+  }
+  size_t bytes() const { return tau_bytes + solver + 3 * plane; }
+};
+
 static int sw_fluxes_impl(bool f32, const ecckd_model_t *m, int ncol, int nlay, const double *plev, const double *tlay,
                           int ngas, const char *gas_names, const double *const *vmr, const long long *vmr_col_stride,
                           const long long *vmr_lay_stride, const double *vmr_scalar, int top_at_1, const double *mu0,
@@ -2760,9 +2776,8 @@ static int sw_fluxes_impl(bool f32, const ecckd_model_t *m, int ncol, int nlay, 
   // The work block: tau between the two kernels, the solver's room behind it, and -- all-sky with delta scaling -- three
   // band planes for the scaled copy of the particles (the caller's arrays are never written).  With device arrays it is
   // the stream's scratch block, so the capture rules of stream_scratch cover all of it.
-  const size_t tau_bytes = align256(n.lay_g * esz(f32));
-  const size_t solver = sw_fluxes_solver_bytes(m->device, ncol, nlay, m->ng);
-  const size_t plane = pt && pt->delta_scale ? align256(n.lay_b * esz(f32)) : 0;
+  const SwWork work(m, f32, ncol, nlay, pt && pt->delta_scale);
+  const size_t tau_bytes = work.tau_bytes, solver = work.solver, plane = work.plane;
   Stage st(const_cast<ecckd_model *>(m), memspace, stream, f32);
   const double *d_plev = nullptr, *d_tlay = nullptr, *d_mu0 = nullptr, *d_scale = nullptr, *d_ad = nullptr, *d_af = nullptr;
   double *d_up = nullptr, *d_dn = nullptr, *d_dir = nullptr, *d_tau = nullptr;
@@ -2776,7 +2791,7 @@ static int sw_fluxes_impl(bool f32, const ecckd_model_t *m, int ncol, int nlay, 
         if (pt) d_pt = SwParticles{st.in(pt->tau, n.lay_b), st.in(pt->ssa, n.lay_b), st.in(pt->g, n.lay_b), pt->delta_scale, st.in(pt->mask, n.lay)};
         if (clr) d_clr = ClearFluxes{st.out(clr->up, n.lev), st.out(clr->dn, n.lev), st.out(clr->dir, n.lev)};
         d_up = st.out(flux_up, n.lev); d_dn = st.out(flux_dn, n.lev); d_dir = st.out(flux_dir, n.lev);
-        d_tau = st.work(tau_bytes + solver + 3 * plane);
+        d_tau = st.work(work.bytes());
       }))
     return 1;
   char *const room = reinterpret_cast<char *>(d_tau) + tau_bytes;
@@ -2877,6 +2892,274 @@ int ecckd_sw_fluxes_allsky_mcica(const ecckd_model_t *m, int ncol, int nlay, con
   return sw_fluxes_allsky_impl(m, ncol, nlay, plev, tlay, ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar,
                                top_at_1, mu0, toa_scale, sfc_alb_dir, sfc_alb_dif, nband_p, tau_p, ssa_p, g_p, delta_scale,
                                cloud_mask, flux_up, flux_dn, flux_dir, memspace, stream);
+}
+
+// ---- the shortwave on the daylit columns only (kernels_columns.hip): select, gather, solve, scatter ----
+
+// A host list of columns as ecckd_daylit_columns delivers it: strictly ascending, inside [0,ncol)
+static bool column_list_ok(const int *index, int nday, int ncol) {
+  for (int k = 0; k < nday; ++k)
+    if (index[k] < 0 || index[k] >= ncol || (k > 0 && index[k] <= index[k - 1])) return false;
+  return true;
+}
+
+static int daylit_columns_impl(bool f32, int device, int ncol, const void *mu0, double mu0_min, int *day_index, int *nday,
+                               int memspace, void *stream) {
+  if (ncol < 0) return fail("ecckd_daylit_columns: bad ncol");
+  if (!mu0 || !day_index || !nday) return fail("ecckd_daylit_columns: null argument");
+  if (memspace != ECCKD_DEVICE && memspace != ECCKD_HOST) return fail("ecckd: bad memspace");
+  if (check_device(device)) return 1;
+  *nday = 0;
+  if (ncol == 0) return 0;
+  if (memspace == ECCKD_DEVICE && stream_is_capturing(static_cast<hipStream_t>(stream)))
+    return fail("ecckd_daylit_columns: the call returns the count to the host and cannot be captured into a graph (select before "
+                "the capture and capture ecckd_sw_fluxes_daylit with the list)");
+  Stage st(device, memspace, stream, f32);
+  const double *d_mu0 = nullptr;
+  int *d_index = nullptr, *d_work = nullptr;
+  if (st.open([&] {
+        d_mu0 = st.in(static_cast<const double *>(mu0), (size_t)ncol);
+        d_index = st.out(day_index, (size_t)ncol);
+        d_work = reinterpret_cast<int *>(st.work(ecckd::daylit_work_bytes(ncol)));
+      }))
+    return 1;
+  {
+    ProfScope prof("daylit_columns", st.stream);
+    HIPCHK(ecckd::launch_daylit_columns(d_mu0, f32, ncol, mu0_min, d_index, d_work, st.stream));
+  }
+  int count = 0;
+  HIPCHK(hipMemcpyAsync(&count, d_work, sizeof(int), hipMemcpyDeviceToHost, st.stream));
+  if (st.close()) return 1;
+  HIPCHK(hipStreamSynchronize(st.stream));   // (host arrays: close() has synchronised already)
+  *nday = count;
+  return 0;
+}
+
+int ecckd_daylit_columns(int device, int ncol, const double *mu0, double mu0_min, int *day_index, int *nday, int memspace,
+                         void *stream) {
+  return daylit_columns_impl(false, device, ncol, mu0, mu0_min, day_index, nday, memspace, stream);
+}
+int ecckd_daylit_columns_f32(int device, int ncol, const float *mu0, double mu0_min, int *day_index, int *nday, int memspace,
+                             void *stream) {
+  return daylit_columns_impl(true, device, ncol, mu0, mu0_min, day_index, nday, memspace, stream);
+}
+
+// The refusals ecckd_gather_columns and ecckd_scatter_columns share
+static int check_column_move(const char *who, int ninner, int ncol, int nouter, int elem_bytes, int nday, const int *day_index,
+                             const void *src, const void *dst, int memspace) {
+  const std::string w(who);
+  if (ninner < 1 || ncol < 0 || nouter < 1) return fail(w + ": bad ninner / ncol / nouter");
+  if (elem_bytes != 4 && elem_bytes != 8) return fail(w + ": elem_bytes must be 4 or 8");
+  if (nday < 0 || nday > ncol) return fail(w + ": nday = " + std::to_string(nday) + " outside 0.." + std::to_string(ncol));
+  if (nday > 0 && !day_index) return fail(w + ": day_index is NULL with nday > 0");
+  if (nday > 0 && (!src || !dst)) return fail(w + ": null argument");
+  if (memspace != ECCKD_DEVICE && memspace != ECCKD_HOST) return fail("ecckd: bad memspace");
+  if (memspace == ECCKD_HOST && !column_list_ok(day_index, nday, ncol))
+    return fail(w + ": day_index must be strictly ascending and inside [0,ncol)");
+  return 0;
+}
+
+int ecckd_gather_columns(int device, int ninner, int ncol, int nouter, int elem_bytes, int nday, const int *day_index,
+                         const void *src, void *dst, int memspace, void *stream) {
+  if (check_column_move("ecckd_gather_columns", ninner, ncol, nouter, elem_bytes, nday, day_index, src, dst, memspace)) return 1;
+  if (check_device(device)) return 1;
+  if (nday == 0) return 0;
+  Stage st(device, memspace, stream, false);
+  const size_t full = (size_t)ninner * ncol * nouter * elem_bytes, part = (size_t)ninner * nday * nouter * elem_bytes;
+  const int *d_index = nullptr;
+  const void *d_src = nullptr;
+  void *d_dst = nullptr;
+  if (st.open([&] { d_index = st.in(day_index, (size_t)nday); d_src = st.in_bytes(src, full); d_dst = st.out_bytes(dst, part); }))
+    return 1;
+  {
+    ProfScope prof("gather_columns", st.stream);
+    HIPCHK(ecckd::launch_gather_columns(ninner, ncol, nouter, elem_bytes, nday, d_index, d_src, d_dst, st.stream));
+  }
+  return st.close();
+}
+
+int ecckd_scatter_columns(int device, int ninner, int ncol, int nouter, int elem_bytes, int nday, const int *day_index,
+                          const void *src, void *dst, double fill, int memspace, void *stream) {
+  if (check_column_move("ecckd_scatter_columns", ninner, ncol, nouter, elem_bytes, nday, day_index, src, dst, memspace)) return 1;
+  if (!dst && ncol > 0) return fail("ecckd_scatter_columns: null argument");
+  if (check_device(device)) return 1;
+  if (ncol == 0) return 0;
+  Stage st(device, memspace, stream, false);
+  const size_t full = (size_t)ninner * ncol * nouter * elem_bytes, part = (size_t)ninner * nday * nouter * elem_bytes;
+  const int *d_index = nullptr;
+  const void *d_src = nullptr;
+  void *d_dst = nullptr;
+  if (st.open([&] { d_index = st.in(day_index, (size_t)nday); d_src = st.in_bytes(src, part); d_dst = st.out_bytes(dst, full); }))
+    return 1;
+  {
+    ProfScope prof("scatter_columns", st.stream);
+    HIPCHK(ecckd::launch_scatter_columns(ninner, ncol, nouter, elem_bytes, nday, d_index, d_src, d_dst, fill, st.stream));
+  }
+  return st.close();
+}
+
+// The rooms of ecckd_sw_fluxes_daylit behind the inner call's work block (SwWork): every array of the call on nday columns,
+// each rounded up to 256 bytes, in the order of include/ecckd_hip.h.  toa_scale and the direct-beam outputs have their rooms
+// whether or not they are given.
+struct DaylitRooms {
+  size_t lev, lay, col, col_b, lay_b;   // bytes of one room of each kind
+  int ngas_arrays, nflux;
+  bool particles, mask;
+  DaylitRooms(const ecckd_model *m, int nday, int nlay, int ngas_arrays_, bool particles_, bool mask_, bool clear)
+      : ngas_arrays(ngas_arrays_), nflux(clear ? 6 : 3), particles(particles_), mask(mask_) {
+    const Counts n(nday, nlay, m->ng, m->nband);
+    lev = align256(n.lev * 8); lay = align256(n.lay * 8); col = align256(n.col * 8); col_b = align256(n.col_b * 8);
+    lay_b = align256(n.lay_b * 8);
+  }
+  size_t bytes() const {
+    return lev + lay + 2 * col + 2 * col_b + (size_t)ngas_arrays * lay + (particles ? 3 * lay_b : 0) + (mask ? lay : 0) +
+           (size_t)nflux * lev;
+  }
+};
+
+size_t ecckd_sw_fluxes_daylit_scratch_bytes(const ecckd_model_t *m, int ncol, int nday, int nlay, int ngas_arrays,
+                                            int with_particles, int delta_scale, int with_mask, int with_clear) {
+  (void)ncol;   // (the scatter works in place on the caller's arrays: the full column count needs no room)
+  if (!m || !m->finalized || nday <= 0 || nlay <= 0) return 0;
+  if (ngas_arrays < 0) ngas_arrays = 0;
+  const bool part = with_particles != 0;
+  return SwWork(m, false, nday, nlay, part && delta_scale != 0).bytes() +
+         DaylitRooms(m, nday, nlay, ngas_arrays, part, part && with_mask != 0, part && with_clear != 0).bytes();
+}
+
+int ecckd_sw_fluxes_daylit(const ecckd_model_t *m, int ncol, int nlay, int nday, const int *day_index, const double *plev,
+                           const double *tlay, int ngas, const char *gas_names, const double *const *vmr,
+                           const long long *vmr_col_stride, const long long *vmr_lay_stride, const double *vmr_scalar,
+                           int top_at_1, const double *mu0, const double *toa_scale, const double *sfc_alb_dir,
+                           const double *sfc_alb_dif, int nband_p, const double *tau_p, const double *ssa_p, const double *g_p,
+                           int delta_scale, const unsigned long long *cloud_mask, double *flux_up, double *flux_dn,
+                           double *flux_dir, double *flux_up_clear, double *flux_dn_clear, double *flux_dir_clear, int memspace,
+                           void *stream) {
+  // the refusals of sw_fluxes_allsky_impl in its order (those of the particles only with particles), then this call's own
+  if (!m) return fail("ecckd: null model");
+  const bool cloudy = tau_p != nullptr;
+  const bool clear_out = flux_up_clear || flux_dn_clear || flux_dir_clear;
+  if (cloud_mask && m->ng > 64) return fail("ecckd_sw_fluxes_daylit" + std::string(kMaskTooWide) + std::to_string(m->ng));
+  if (cloudy) {
+    if (nband_p != m->nband)
+      return fail("ecckd_sw_fluxes_daylit: nband_p = " + std::to_string(nband_p) + " but the model has " + std::to_string(m->nband) +
+                  " bands (particulate properties live on the model's bands)");
+    if (!ssa_p || !g_p) return fail("ecckd_sw_fluxes_daylit: null argument (tau_p, ssa_p and g_p are given together or not at all)");
+    if (delta_scale != 0 && delta_scale != 1) return fail("ecckd_sw_fluxes_daylit: delta_scale must be 0 or 1");
+  } else if (ssa_p || g_p || cloud_mask || clear_out) {
+    return fail("ecckd_sw_fluxes_daylit: clear sky (tau_p NULL) takes no ssa_p, g_p, cloud_mask or clear-sky outputs");
+  }
+  if (g_arith.load() != 0) return fail("ecckd_sw_fluxes_daylit: needs the fast arithmetic mode (ecckd_set_arithmetic(0))");
+  if (clear_out) {
+    if (!flux_up_clear || !flux_dn_clear)
+      return fail("ecckd_sw_fluxes_daylit: null argument (flux_up_clear and flux_dn_clear are given together or not at all; flux_dir_clear may be null)");
+    double *const all[3] = {flux_up, flux_dn, flux_dir}, *const clear[3] = {flux_up_clear, flux_dn_clear, flux_dir_clear};
+    for (double *c : clear)
+      for (double *f : all)
+        if (c && c == f)
+          return fail("ecckd_sw_fluxes_daylit: a clear-sky output must not be an all-sky output (the two sets of fluxes need arrays of their own)");
+  }
+  if (nday < 0 || nday > ncol)
+    return fail("ecckd_sw_fluxes_daylit: nday = " + std::to_string(nday) + " outside 0.." + std::to_string(ncol));
+  if (nday > 0 && !day_index) return fail("ecckd_sw_fluxes_daylit: day_index is NULL with nday > 0");
+  if (memspace == ECCKD_HOST && !column_list_ok(day_index, nday, ncol))
+    return fail("ecckd_sw_fluxes_daylit: day_index must be strictly ascending and inside [0,ncol)");
+  // ... and those of sw_fluxes_impl, which sees nday columns only (and nothing at all with nday = 0)
+  if (check_model(m) || check_gas_optics_dims(ncol, nlay)) return 1;
+  if (!m->has_solar) return fail("ecckd_sw_fluxes_daylit: model has no solar table (longwave model?)");
+  if (!plev || !tlay || !mu0 || !sfc_alb_dir || !sfc_alb_dif || !flux_up || !flux_dn || (ngas > 0 && !gas_names))
+    return fail("ecckd_sw_fluxes_daylit: null argument");
+  if (memspace != ECCKD_DEVICE && memspace != ECCKD_HOST) return fail("ecckd: bad memspace");
+  HIPCHK(hipSetDevice(m->device));
+  if (ncol == 0) return 0;
+
+  const GasDesc gd{ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar};
+  int ngas_arrays = 0;   // the gas arrays that differ between columns: the others are read in place
+  for (int j = 0; j < ngas && nday > 0; ++j)
+    if (vmr && vmr[j] && vmr_col_stride && vmr_col_stride[j] != 0) ++ngas_arrays;
+  const Counts n(ncol, nlay, m->ng, m->nband);
+  const DaylitRooms rooms(m, nday, nlay, ngas_arrays, cloudy, cloud_mask != nullptr, clear_out);
+  // With device arrays the work block is the stream's scratch block: the inner call asks for the same block and takes its
+  // share from the front, the gathered arrays sit behind it.  With host arrays the gathered arrays are a room of the arena
+  // and the inner call, which then runs on device arrays, takes the scratch block of the model's host stream.
+  const size_t inner_bytes = nday > 0 && memspace == ECCKD_DEVICE ? SwWork(m, false, nday, nlay, cloudy && delta_scale).bytes() : 0;
+  Stage st(const_cast<ecckd_model *>(m), memspace, stream, false);
+  const int *d_index = nullptr;
+  const double *d_plev = nullptr, *d_tlay = nullptr, *d_mu0 = nullptr, *d_scale = nullptr, *d_ad = nullptr, *d_af = nullptr;
+  GasDesc d_gd{};
+  SwParticles d_pt{};
+  double *d_out[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}, *d_work = nullptr;
+  double *const out[6] = {flux_up, flux_dn, flux_dir, flux_up_clear, flux_dn_clear, flux_dir_clear};
+  if (st.open([&] {
+        if (nday > 0) {
+          d_index = st.in(day_index, (size_t)nday);
+          d_plev = st.in(plev, n.lev); d_tlay = st.in(tlay, n.lay); d_mu0 = st.in(mu0, n.col); d_scale = st.in(toa_scale, n.col);
+          d_ad = st.in(sfc_alb_dir, n.col_b); d_af = st.in(sfc_alb_dif, n.col_b);
+          d_gd = st.gases(gd, ncol, nlay);
+          if (cloudy) d_pt = SwParticles{st.in(tau_p, n.lay_b), st.in(ssa_p, n.lay_b), st.in(g_p, n.lay_b), delta_scale, st.in(cloud_mask, n.lay)};
+        }
+        for (int f = 0; f < 6; ++f) d_out[f] = st.out(out[f], n.lev);
+        if (nday > 0) d_work = st.work(inner_bytes + rooms.bytes());
+      }))
+    return 1;
+  const hipStream_t s = st.stream;
+  double *g_out[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  if (nday > 0) {
+    char *at = reinterpret_cast<char *>(d_work) + inner_bytes;
+    auto take = [&at](size_t bytes) { double *p = reinterpret_cast<double *>(at); at += bytes; return p; };
+    double *g_plev = take(rooms.lev), *g_tlay = take(rooms.lay), *g_mu0 = take(rooms.col), *g_scale = take(rooms.col);
+    double *g_ad = take(rooms.col_b), *g_af = take(rooms.col_b);
+    std::vector<const double *> g_vmr(ngas > 0 ? ngas : 1, nullptr);
+    std::vector<long long> g_cs(ngas > 0 ? ngas : 1, 0), g_ls(ngas > 0 ? ngas : 1, 0);
+    {
+      ProfScope prof("daylit_gather", s);
+      // (ninner, ncol, nouter) of each array: planes (1, ncol, n), albedos (nband, ncol, 1)
+      auto gather = [&](int ninner, int nouter, const void *src, void *dst) {
+        return ecckd::launch_gather_columns(ninner, ncol, nouter, 8, nday, d_index, src, dst, s);
+      };
+      HIPCHK(gather(1, nlay + 1, d_plev, g_plev));
+      HIPCHK(gather(1, nlay, d_tlay, g_tlay));
+      HIPCHK(gather(1, 1, d_mu0, g_mu0));
+      if (d_scale) HIPCHK(gather(1, 1, d_scale, g_scale));
+      HIPCHK(gather(m->nband, 1, d_ad, g_ad));
+      HIPCHK(gather(m->nband, 1, d_af, g_af));
+      for (int j = 0; j < ngas; ++j) {
+        g_vmr[j] = d_gd.vmr ? d_gd.vmr[j] : nullptr;
+        g_cs[j] = vmr_col_stride ? vmr_col_stride[j] : 0;
+        g_ls[j] = vmr_lay_stride ? vmr_lay_stride[j] : 0;
+        if (!g_vmr[j] || g_cs[j] == 0) continue;
+        double *room = take(rooms.lay);
+        HIPCHK(ecckd::launch_gather_strided(ncol, nlay, 8, nday, d_index, g_cs[j], g_ls[j], g_vmr[j], room, s));
+        g_vmr[j] = room; g_cs[j] = 1; g_ls[j] = nday;
+      }
+      if (cloudy) {
+        double *g_tau = take(rooms.lay_b), *g_ssa = take(rooms.lay_b), *g_g = take(rooms.lay_b);
+        HIPCHK(gather(1, nlay * m->nband, d_pt.tau, g_tau));
+        HIPCHK(gather(1, nlay * m->nband, d_pt.ssa, g_ssa));
+        HIPCHK(gather(1, nlay * m->nband, d_pt.g, g_g));
+        d_pt.tau = g_tau; d_pt.ssa = g_ssa; d_pt.g = g_g;
+        if (d_pt.mask) {
+          double *g_mask = take(rooms.lay);
+          HIPCHK(gather(1, nlay, d_pt.mask, g_mask));
+          d_pt.mask = reinterpret_cast<const unsigned long long *>(g_mask);
+        }
+      }
+    }
+    for (int f = 0; f < 6; ++f)
+      if (d_out[f]) g_out[f] = take(rooms.lev);
+    const ClearFluxes g_clr{g_out[3], g_out[4], g_out[5]};
+    // the pipeline of the existing calls, unchanged, on nday columns of device arrays
+    if (sw_fluxes_impl(false, m, nday, nlay, g_plev, g_tlay, ngas, gas_names, g_vmr.data(), g_cs.data(), g_ls.data(), vmr_scalar,
+                       top_at_1, g_mu0, d_scale ? g_scale : nullptr, g_ad, g_af, g_out[0], g_out[1], g_out[2], ECCKD_DEVICE, s,
+                       cloudy ? &d_pt : nullptr, clear_out ? &g_clr : nullptr))
+      return 1;
+  }
+  {
+    ProfScope prof("daylit_scatter", s);
+    for (int f = 0; f < 6; ++f)
+      if (d_out[f]) HIPCHK(ecckd::launch_scatter_columns(1, ncol, nlay + 1, 8, nday, d_index, g_out[f], d_out[f], 0., s));
+  }
+  return st.close();
 }
 
 // ---- element-wise operations on optical properties (kernels_optical_props.hip) ----

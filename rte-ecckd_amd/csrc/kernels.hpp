@@ -411,4 +411,21 @@ hipError_t launch_rte_sw_sys(const RteSwArgs &a, int cus, hipStream_t s);
 // partial sums of the tail tiles -> fluxes, in chunk order (kernels_rte_sw.hip)
 hipError_t launch_rte_sw_tail_reduce(const RteSwArgs &a, int nchunks, int cw, long tail_first, long ntail, hipStream_t s);
 
+// Column compaction (kernels_columns.hip).  Arrays are viewed as (ninner, ncol, nouter), ninner fastest; elem_bytes 4 or 8.
+// day_index(ncol capacity) <- the ascending list of columns with mu0 > mu0_min (compared in double; NaN: night); work:
+// daylit_work_bytes(ncol) of device memory, work[0] <- the count, behind it the block offsets.  Deterministic: no atomics.
+int daylit_blocks(int ncol);
+size_t daylit_work_bytes(int ncol);
+hipError_t launch_daylit_columns(const void *mu0, int f32, int ncol, double mu0_min, int *day_index, int *work, hipStream_t s);
+// dst(i,k,o) = src(i,index(k),o), k < nday; an index outside [0,ncol) is clamped
+hipError_t launch_gather_columns(int ninner, int ncol, int nouter, int elem_bytes, int nday, const int *index, const void *src,
+                                 void *dst, hipStream_t s);
+// dst(k,l) = src[index(k)*col_stride + l*lay_stride] (strides in elements): a gas array of the ABI to a dense (nday,nlay)
+hipError_t launch_gather_strided(int ncol, int nlay, int elem_bytes, int nday, const int *index, long long col_stride,
+                                 long long lay_stride, const void *src, void *dst, hipStream_t s);
+// dst(i,index(k),o) = src(i,k,o) and `fill` (as double, or rounded to float for 4-byte elements) in every column of dst
+// that the list does not hold, in one pass over dst; the list must ascend; an index outside [0,ncol) is skipped
+hipError_t launch_scatter_columns(int ninner, int ncol, int nouter, int elem_bytes, int nday, const int *index, const void *src,
+                                  void *dst, double fill, hipStream_t s);
+
 }  // namespace ecckd

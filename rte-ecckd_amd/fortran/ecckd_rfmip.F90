@@ -2,11 +2,17 @@
 ! reference's names and command line (example/rfmip-rad-irf/Makefile:12-40, utils.f90:26-37):
 !
 !     ecckd_rfmip_lw rfmip_file ecckd_file [-f 1|2] [-p 1|2] [-b block] [-n nblocks] [-d]   (default build)
-!     ecckd_rfmip_sw rfmip_file ecckd_file [-f 1|2]          [-b block] [-n nblocks] [-d]   (-DSHORTWAVE)
+!     ecckd_rfmip_sw rfmip_file ecckd_file [-f 1|2]          [-b block] [-n nblocks] [-d] [-l]   (-DSHORTWAVE)
 !
 ! -d: device-resident mode.  optical_props / source are the device twins of mo_ecckd_device: tau and the
 ! sources stay in the GPU's memory between gas_optics and rte_lw / rte_sw, only the atmosphere goes in and the
 ! fluxes come out (the C ABI's ECCKD_MIXED memory space).  Same calls, same fluxes bit for bit.
+!
+! -l (shortwave): the block loop goes through ecckd%sw_fluxes_daylit -- the block's true mu0 and the cosine of the
+! driver's 90-degree limit as mu0_min, so the columns computed are exactly those of usecol, and the file's irradiances as
+! tsi, so the beam is renormalised as below; the library selects, gathers and scatters, and leaves zeros in the others.
+! The mu0 = 1 night columns and the zeroing loop below (what the reference does "for a better measure of timing",
+! ecckd_rfmip_sw.F90:103-108,143-145,156-161) are not used then.
 !
 ! Same steps as ecckd_rfmip_lw.F90:38-140 / ecckd_rfmip_sw.F90:40-166: sizes, output names
 ! r{l,s}{u,d}_Efx_RTE-ecckd_rad-irf_r1i1p<p>f<f>_gn.nc, gas names by forcing index, blocked inputs,
@@ -42,7 +48,7 @@ program ecckd_rfmip
   character(len=32), dimension(6) :: kdist_names, rfmip_names
   integer :: ncol, nlay, nexp, nbnd, nblocks, ndo, block_size, max_blocks, forcing_index, physics_index
   integer :: b, i
-  logical :: top_at_1, device_resident
+  logical :: top_at_1, device_resident, daylit
   real(wp), dimension(:,:,:), allocatable :: p_lay, p_lev, t_lay, t_lev
   real(wp), dimension(:,:,:), allocatable, target :: flux_up, flux_dn
   real(wp), dimension(:,:), allocatable :: bc_spec
@@ -53,6 +59,7 @@ program ecckd_rfmip
   real(wp), parameter :: deg_to_rad = acos(-1._wp) / 180._wp
   real(wp), dimension(:,:), allocatable :: albedo, tsi, sza, toa_flux
   real(wp), dimension(:), allocatable :: mu0, def_tsi
+  real(wp) :: mu0_min
   logical, dimension(:,:), allocatable :: usecol
   integer :: ngpt
   class(ty_optical_props_2str), allocatable :: optical_props
@@ -63,7 +70,7 @@ program ecckd_rfmip
   class(ty_source_func_lw), allocatable :: source
 #endif
 
-  call parse_args(rfmip_path, ecckd_path, forcing_index, physics_index, block_size, max_blocks, device_resident)
+  call parse_args(rfmip_path, ecckd_path, forcing_index, physics_index, block_size, max_blocks, device_resident, daylit)
   call read_size(rfmip_path, ncol, nlay, nexp)
   if (block_size <= 0) block_size = ncol * nexp
   if (mod(ncol * nexp, block_size) /= 0) &
@@ -123,6 +130,8 @@ program ecckd_rfmip
   end if
   call stop_on_err(optical_props%alloc_2str(block_size, nlay, ecckd))
   usecol = sza < 90._wp - 2._wp * spacing(90._wp)                          ! ecckd_rfmip_sw.F90:106-108
+  ! -l: the same predicate on the cosine (cos falls strictly through the limit, so mu0 > mu0_min picks the columns of usecol)
+  mu0_min = cos((90._wp - 2._wp * spacing(90._wp)) * deg_to_rad)
 #else
   if (device_resident) then
     allocate(ty_source_func_lw_dev :: source)
@@ -139,6 +148,15 @@ program ecckd_rfmip
     fluxes%flux_up => flux_up(:, :, b)
     fluxes%flux_dn => flux_dn(:, :, b)
 #ifdef SHORTWAVE
+    if (daylit) then
+      do i = 1, block_size
+        bc_spec(:, i) = albedo(i, b)
+        mu0(i) = cos(sza(i, b) * deg_to_rad)
+      end do
+      call stop_on_err(ecckd%sw_fluxes_daylit(p_lev(:, :, b), t_lay(:, :, b), gases(b), top_at_1, mu0, bc_spec, bc_spec, &
+                                              flux_up(:, :, b), flux_dn(:, :, b), mu0_min=mu0_min, tsi=tsi(:, b)))
+      cycle
+    end if
     call stop_on_err(ecckd%gas_optics(p_lay(:, :, b), p_lev(:, :, b), t_lay(:, :, b), gases(b), optical_props, toa_flux))
     def_tsi = sum(toa_flux, dim=2)                                          ! :126-133 renormalise to the file's TSI
     do i = 1, block_size

@@ -57,6 +57,7 @@ module gas_optics_ecckd
     procedure, public :: sw_fluxes          !< extension: gas_optics + rte_sw in one call (fused shortwave path)
     procedure, public :: lw_fluxes_allsky   !< extension: lw_fluxes with particulate optics on the model's bands
     procedure, public :: sw_fluxes_allsky   !< extension: sw_fluxes with particulate optics on the model's bands
+    procedure, public :: sw_fluxes_daylit   !< extension: sw_fluxes on the columns with mu0 > mu0_min only, zeros in the others
     procedure, public :: sample_cloud_mask  !< extension: McICA cloud mask from cloud fractions (ecckd_cloud_mask_sample)
   end type ty_gas_optics_ecckd
 
@@ -330,6 +331,67 @@ module gas_optics_ecckd
       type(c_ptr), value :: stream
       integer(c_int) :: rc
     end function c_sw_fluxes_clear_allsky
+    function c_daylit_columns(device, ncol, mu0, mu0_min, day_index, nday, memspace, stream) &
+        bind(C, name="ecckd_daylit_columns") result(rc)
+      import c_ptr, c_int, c_double
+      integer(c_int), value :: device, ncol, memspace
+      real(c_double), dimension(*), intent(in) :: mu0
+      real(c_double), value :: mu0_min
+      integer(c_int), dimension(*), intent(inout) :: day_index
+      integer(c_int), intent(out) :: nday
+      type(c_ptr), value :: stream
+      integer(c_int) :: rc
+    end function c_daylit_columns
+    function c_sw_fluxes_daylit(model, ncol, nlay, nday, day_index, plev, tlay, ngas, gas_names, vmr, cs, ls, scalar, top_at_1, &
+                                mu0, toa_scale, sfc_alb_dir, sfc_alb_dif, nband_p, tau_p, ssa_p, g_p, delta_scale, cloud_mask, &
+                                flux_up, flux_dn, flux_dir, flux_up_clear, flux_dn_clear, flux_dir_clear, memspace, stream) &
+        bind(C, name="ecckd_sw_fluxes_daylit") result(rc)
+      import c_ptr, c_int, c_double, c_char, c_long_long
+      type(c_ptr), value :: model
+      integer(c_int), value :: ncol, nlay, nday, ngas, top_at_1, nband_p, delta_scale, memspace
+      integer(c_int), dimension(*), intent(in) :: day_index
+      real(c_double), dimension(*), intent(in) :: plev, tlay, mu0, sfc_alb_dir, sfc_alb_dif
+      character(kind=c_char), dimension(*), intent(in) :: gas_names
+      type(c_ptr), dimension(*), intent(in) :: vmr
+      integer(c_long_long), dimension(*), intent(in) :: cs, ls
+      real(c_double), dimension(*), intent(in) :: scalar
+      type(c_ptr), value :: toa_scale, tau_p, ssa_p, g_p, cloud_mask, flux_dir, flux_up_clear, flux_dn_clear, flux_dir_clear
+      real(c_double), dimension(*), intent(inout) :: flux_up, flux_dn
+      type(c_ptr), value :: stream
+      integer(c_int) :: rc
+    end function c_sw_fluxes_daylit
+    function c_gather_columns(device, ninner, ncol, nouter, elem_bytes, nday, day_index, src, dst, memspace, stream) &
+        bind(C, name="ecckd_gather_columns") result(rc)
+      import c_ptr, c_int, c_double
+      integer(c_int), value :: device, ninner, ncol, nouter, elem_bytes, nday, memspace
+      integer(c_int), dimension(*), intent(in) :: day_index
+      real(c_double), dimension(*), intent(in) :: src      ! (8-byte elements: the binding serves the fp64 arrays)
+      real(c_double), dimension(*), intent(inout) :: dst
+      type(c_ptr), value :: stream
+      integer(c_int) :: rc
+    end function c_gather_columns
+    function c_scatter_columns(device, ninner, ncol, nouter, elem_bytes, nday, day_index, src, dst, fill, memspace, stream) &
+        bind(C, name="ecckd_scatter_columns") result(rc)
+      import c_ptr, c_int, c_double
+      integer(c_int), value :: device, ninner, ncol, nouter, elem_bytes, nday, memspace
+      integer(c_int), dimension(*), intent(in) :: day_index
+      real(c_double), dimension(*), intent(in) :: src
+      real(c_double), dimension(*), intent(inout) :: dst
+      real(c_double), value :: fill
+      type(c_ptr), value :: stream
+      integer(c_int) :: rc
+    end function c_scatter_columns
+    function c_rte_sw_host(device, ncol, nlay, ngpt, top_at_1, tau, ssa, g, mu0, toa, nband, band2gpt, alb_dir, alb_dif, &
+                           flux_up, flux_dn, flux_dir, memspace, stream) bind(C, name="ecckd_rte_sw") result(rc)
+      import c_ptr, c_int, c_double
+      integer(c_int), value :: device, ncol, nlay, ngpt, top_at_1, nband, memspace
+      type(c_ptr), value :: tau, ssa, g
+      real(c_double), dimension(*), intent(in) :: mu0, toa, alb_dir, alb_dif
+      integer(c_int), dimension(*), intent(in) :: band2gpt
+      real(c_double), dimension(*), intent(inout) :: flux_up, flux_dn, flux_dir
+      type(c_ptr), value :: stream
+      integer(c_int) :: rc
+    end function c_rte_sw_host
     function c_cloud_mask_sample(device, ncol, nlay, ngpt, overlap, cloud_frac, overlap_param, seed, col0, mask, memspace, &
                                  stream) bind(C, name="ecckd_cloud_mask_sample") result(rc)
       import c_ptr, c_int, c_double, c_int64_t
@@ -793,6 +855,178 @@ contains
     flux_dn = dn
     if (present(flux_dir)) flux_dir = dir
   end function sw_fluxes
+
+  !> Extension: sw_fluxes on the daylit columns only.  The arguments are those of sw_fluxes, every array with the full ncol,
+  !! and mu0 is the true cosine of the solar zenith angle: the columns with mu0 > mu0_min (default 0; a NaN is night) are
+  !! selected (ecckd_daylit_columns), compacted, computed and scattered back, and every other column of flux_up / flux_dn /
+  !! flux_dir is zero at every level.  The caller handles no column list and sets no placeholder mu0 in the night columns.
+  !!   toa_scale(ncol), or neither: the fused call ecckd_sw_fluxes_daylit -- what sw_fluxes computes for the daylit columns,
+  !!     bit for bit, with the beam solar(g)*toa_scale(i).
+  !!   tsi(ncol): the route of a host on the unfused calls, which is what the reference's block loop is: the inputs are
+  !!     compacted with ecckd_gather_columns, gas_optics and rte_sw run on the daylit columns with the beam renormalised
+  !!     between them exactly as the drivers do it, toa(i,:)*tsi(i)/sum(toa(i,:)) (ecckd_rfmip_sw.F90:126-133), and the fluxes
+  !!     go back through ecckd_scatter_columns -- bit for bit what that block loop gives for the daylit columns.  (The beam
+  !!     of that expression is an array per g-point; no toa_scale reproduces its bits.)
+  function sw_fluxes_daylit(this, plev, tlay, gas_desc, top_at_1, mu0, sfc_alb_dir, sfc_alb_dif, flux_up, flux_dn, flux_dir, &
+                            toa_scale, mu0_min, tsi) result(error_msg)
+    class(ty_gas_optics_ecckd), intent(in) :: this
+    real(wp), dimension(:,:), intent(in) :: plev, tlay
+    type(ty_gas_concs), intent(in) :: gas_desc
+    logical, intent(in) :: top_at_1
+    real(wp), dimension(:), intent(in) :: mu0
+    real(wp), dimension(:,:), intent(in) :: sfc_alb_dir, sfc_alb_dif
+    real(wp), dimension(:,:), intent(inout) :: flux_up, flux_dn
+    real(wp), dimension(:,:), intent(inout), optional :: flux_dir
+    real(wp), dimension(:), intent(in), optional :: toa_scale, tsi
+    real(wp), intent(in), optional :: mu0_min
+    character(len=128) :: error_msg
+    character(kind=c_char), dimension(:), allocatable :: names
+    type(c_ptr), dimension(:), allocatable :: ptr
+    integer(c_long_long), dimension(:), allocatable :: cs, ls
+    real(c_double), dimension(:), allocatable :: scalar
+    real(wp), dimension(:,:), allocatable, target :: up, dn, dir
+    real(wp), dimension(:), allocatable, target :: scale
+    integer(c_int), dimension(:), allocatable :: day_index
+    type(c_ptr) :: scale_p, dir_p
+    integer :: ncol, nlay, n
+    integer(c_int) :: rc, nd
+    real(c_double) :: limit
+    ncol = size(tlay, 1)
+    nlay = size(tlay, 2)
+    error_msg = marshal_gases(this, gas_desc, ncol, nlay, names, ptr, cs, ls, scalar)
+    if (trim(error_msg) /= "") return
+    if (size(sfc_alb_dir, 1) /= this%get_nband() .or. size(sfc_alb_dir, 2) /= ncol .or. &
+        size(sfc_alb_dif, 1) /= this%get_nband() .or. size(sfc_alb_dif, 2) /= ncol) then
+      error_msg = "sw_fluxes_daylit: surface albedos inconsistently sized"
+      return
+    end if
+    if (size(mu0) /= ncol) then
+      error_msg = "sw_fluxes_daylit: mu0 inconsistently sized"
+      return
+    end if
+    if (present(tsi)) then
+      if (present(toa_scale)) then
+        error_msg = "sw_fluxes_daylit: toa_scale and tsi exclude each other"
+        return
+      end if
+      if (size(tsi) /= ncol) then
+        error_msg = "sw_fluxes_daylit: tsi inconsistently sized"
+        return
+      end if
+    end if
+    limit = 0._c_double
+    if (present(mu0_min)) limit = real(mu0_min, c_double)
+    allocate(day_index(max(ncol, 1)))
+    nd = 0
+    rc = c_daylit_columns(c_model_device(this%handle), int(ncol, c_int), mu0, limit, day_index, nd, ECCKD_HOST, c_null_ptr)
+    if (rc /= 0) then
+      error_msg = c_error_message()
+      return
+    end if
+    n = gas_desc%get_num_gases()
+    allocate(up(ncol, nlay + 1), dn(ncol, nlay + 1))
+    scale_p = c_null_ptr
+    dir_p = c_null_ptr
+    if (present(toa_scale)) then
+      allocate(scale(ncol))
+      scale = toa_scale
+      scale_p = c_loc(scale(1))
+    end if
+    if (present(flux_dir)) then
+      allocate(dir(ncol, nlay + 1))
+      dir_p = c_loc(dir(1, 1))
+    end if
+    if (present(tsi) .and. nd > 0) then
+      error_msg = daylit_unfused(this, ncol, nlay, nd, day_index, plev, tlay, gas_desc, top_at_1, mu0, sfc_alb_dir, sfc_alb_dif, &
+                                 tsi, up, dn, dir)
+      if (trim(error_msg) /= "") return
+    else   ! (no daylit column: the fused call only zeroes the outputs)
+      rc = c_sw_fluxes_daylit(this%handle, int(ncol, c_int), int(nlay, c_int), nd, day_index, plev, tlay, int(n, c_int), names, &
+                              ptr, cs, ls, scalar, merge(1_c_int, 0_c_int, top_at_1), mu0, scale_p, sfc_alb_dir, sfc_alb_dif, &
+                              0_c_int, c_null_ptr, c_null_ptr, c_null_ptr, 0_c_int, c_null_ptr, up, dn, dir_p, c_null_ptr, &
+                              c_null_ptr, c_null_ptr, ECCKD_HOST, c_null_ptr)
+      if (rc /= 0) then
+        error_msg = c_error_message()
+        return
+      end if
+    end if
+    flux_up = up
+    flux_dn = dn
+    if (present(flux_dir)) flux_dir = dir
+  end function sw_fluxes_daylit
+
+  !> The tsi route of sw_fluxes_daylit: gather, gas_optics, the drivers' renormalisation of the beam, rte_sw, scatter.
+  !! day_index(1:nd) is the 0-based ascending list; up / dn (and dir, if allocated) are (ncol, nlay+1).
+  function daylit_unfused(this, ncol, nlay, nd, day_index, plev, tlay, gas_desc, top_at_1, mu0, sfc_alb_dir, sfc_alb_dif, tsi, &
+                          up, dn, dir) result(error_msg)
+    class(ty_gas_optics_ecckd), intent(in) :: this
+    integer, intent(in) :: ncol, nlay
+    integer(c_int), intent(in) :: nd
+    integer(c_int), dimension(:), intent(in) :: day_index
+    real(wp), dimension(:,:), intent(in) :: plev, tlay
+    type(ty_gas_concs), intent(in) :: gas_desc
+    logical, intent(in) :: top_at_1
+    real(wp), dimension(:), intent(in) :: mu0, tsi
+    real(wp), dimension(:,:), intent(in) :: sfc_alb_dir, sfc_alb_dif
+    real(wp), dimension(:,:), intent(inout) :: up, dn
+    real(wp), dimension(:,:), allocatable, intent(inout) :: dir
+    character(len=128) :: error_msg
+    type(ty_gas_concs) :: day_gases
+    type(ty_optical_props_2str) :: optical_props
+    real(wp), dimension(:,:), allocatable :: d_plev, d_tlay, d_ad, d_af, toa, d_up, d_dn, d_dir
+    real(wp), dimension(:), allocatable :: d_mu0, d_tsi, def_tsi
+    integer(c_int) :: dev, c, l, k, b, g
+    integer :: i, j, nb, ng
+    dev = c_model_device(this%handle)
+    c = int(ncol, c_int)
+    l = int(nlay, c_int)
+    k = nd
+    nb = this%get_nband()
+    ng = this%get_ngpt()
+    b = int(nb, c_int)
+    g = int(ng, c_int)
+    allocate(d_plev(nd, nlay + 1), d_tlay(nd, nlay), d_mu0(nd), d_tsi(nd), d_ad(nb, nd), d_af(nb, nd), toa(nd, ng), def_tsi(nd), &
+             d_up(nd, nlay + 1), d_dn(nd, nlay + 1), d_dir(nd, nlay + 1))
+    error_msg = ""
+    ! arrays as (ninner, ncol, nouter): the (ncol, n) planes are (1, ncol, n), the albedos (nband, ncol, 1)
+    if (c_gather_columns(dev, 1_c_int, c, l + 1_c_int, 8_c_int, k, day_index, plev, d_plev, ECCKD_HOST, c_null_ptr) /= 0 .or. &
+        c_gather_columns(dev, 1_c_int, c, l, 8_c_int, k, day_index, tlay, d_tlay, ECCKD_HOST, c_null_ptr) /= 0 .or. &
+        c_gather_columns(dev, 1_c_int, c, 1_c_int, 8_c_int, k, day_index, mu0, d_mu0, ECCKD_HOST, c_null_ptr) /= 0 .or. &
+        c_gather_columns(dev, 1_c_int, c, 1_c_int, 8_c_int, k, day_index, tsi, d_tsi, ECCKD_HOST, c_null_ptr) /= 0 .or. &
+        c_gather_columns(dev, b, c, 1_c_int, 8_c_int, k, day_index, sfc_alb_dir, d_ad, ECCKD_HOST, c_null_ptr) /= 0 .or. &
+        c_gather_columns(dev, b, c, 1_c_int, 8_c_int, k, day_index, sfc_alb_dif, d_af, ECCKD_HOST, c_null_ptr) /= 0) then
+      error_msg = c_error_message()
+      return
+    end if
+    day_gases = gas_desc   ! the concentrations that differ between columns, on the daylit columns (the list is 0-based)
+    do j = 1, gas_desc%get_num_gases()
+      if (.not. allocated(gas_desc%concs(j)%conc)) cycle
+      if (size(gas_desc%concs(j)%conc, 1) == ncol) day_gases%concs(j)%conc = gas_desc%concs(j)%conc(day_index(1:nd) + 1, :)
+    end do
+    error_msg = optical_props%alloc_2str(int(nd), nlay, this)
+    if (trim(error_msg) /= "") return
+    error_msg = this%gas_optics_ext(d_tlay, d_plev, d_tlay, day_gases, optical_props, toa)   ! (play is not read)
+    if (trim(error_msg) /= "") return
+    def_tsi = sum(toa, dim=2)                                               ! ecckd_rfmip_sw.F90:126-133
+    do i = 1, nd
+      toa(i, :) = toa(i, :) * d_tsi(i) / def_tsi(i)
+    end do
+    if (c_rte_sw_host(dev, k, l, g, merge(1_c_int, 0_c_int, top_at_1), c_loc_3d(optical_props%tau), c_loc_3d(optical_props%ssa), &
+                      c_loc_3d(optical_props%g), d_mu0, toa, b, int(optical_props%get_band_lims_gpoint(), c_int), d_ad, d_af, &
+                      d_up, d_dn, d_dir, ECCKD_HOST, c_null_ptr) /= 0) then
+      error_msg = c_error_message()
+      return
+    end if
+    if (c_scatter_columns(dev, 1_c_int, c, l + 1_c_int, 8_c_int, k, day_index, d_up, up, 0._c_double, ECCKD_HOST, c_null_ptr) /= 0 .or. &
+        c_scatter_columns(dev, 1_c_int, c, l + 1_c_int, 8_c_int, k, day_index, d_dn, dn, 0._c_double, ECCKD_HOST, c_null_ptr) /= 0) then
+      error_msg = c_error_message()
+      return
+    end if
+    if (allocated(dir)) then
+      if (c_scatter_columns(dev, 1_c_int, c, l + 1_c_int, 8_c_int, k, day_index, d_dir, dir, 0._c_double, ECCKD_HOST, c_null_ptr) /= 0) &
+        error_msg = c_error_message()
+    end if
+  end function daylit_unfused
 
   !> Extension: lw_fluxes with the combined particulate (cloud, aerosol) optical properties on the model's bands,
   !! tau_p / ssa_p (ncol, nlay, nband), added to the gas optical depth inside the solver (ecckd_lw_fluxes_allsky):

@@ -454,6 +454,7 @@ contains
     write(error_unit, "(a)") " " // "-b n - Columns per block (default: all columns in one block; the reference uses 1)."
     write(error_unit, "(a)") " " // "-n n - Process only the first n blocks (the reference processes 1700)."
     write(error_unit, "(a)") " " // "-d - Device-resident optical properties and sources (only inputs and fluxes cross the bus)."
+    write(error_unit, "(a)") " " // "-l - Shortwave: compute the daylit columns only (sw_fluxes_daylit); night columns get zero fluxes."
   end subroutine help
 
   !> Gas names in the k-distribution and in the RFMIP file by forcing index (utils.f90:41-70).
@@ -469,12 +470,12 @@ contains
     end if
   end subroutine determine_gas_names
 
-  !> rfmip_file ecckd_file [-f 1|2] [-p 1|2] [-b block] [-n nblocks] [-h|--help]   (utils.f90:74-134)
-  subroutine parse_args(rfmip_path, ecckd_path, forcing_index, physics_index, block_size, max_blocks, device_resident)
+  !> rfmip_file ecckd_file [-f 1|2] [-p 1|2] [-b block] [-n nblocks] [-d] [-l] [-h|--help]   (utils.f90:74-134)
+  subroutine parse_args(rfmip_path, ecckd_path, forcing_index, physics_index, block_size, max_blocks, device_resident, daylit)
     character(len=*), intent(inout) :: rfmip_path, ecckd_path
     integer, intent(inout) :: forcing_index, physics_index
     integer, intent(inout), optional :: block_size, max_blocks
-    logical, intent(inout), optional :: device_resident
+    logical, intent(inout), optional :: device_resident, daylit
     character(len=512) :: buffer
     integer :: i, npos, nargs
     forcing_index = 1
@@ -482,6 +483,7 @@ contains
     if (present(block_size)) block_size = 0
     if (present(max_blocks)) max_blocks = 0
     if (present(device_resident)) device_resident = .false.
+    if (present(daylit)) daylit = .false.
     nargs = command_argument_count()
     if (nargs < 2) then
       call usage()
@@ -497,6 +499,8 @@ contains
         stop 0
       case ("-d")
         if (present(device_resident)) device_resident = .true.
+      case ("-l")
+        if (present(daylit)) daylit = .true.
       case ("-f", "-p", "-b", "-n")
         if (i + 1 > nargs) then
           call usage()
