@@ -1249,6 +1249,14 @@ int ecckd_get_arithmetic(void);
  *                            top of the tile, behind those stores; -1 (default) what measured faster: 1 in fp64 (gas optics + rte_lw
  *                            0.5-0.9 % faster at 1e6 columns than with 0), 0 in fp32 (where 1 costs 3-4 %).  The shortwave and
  *                            tau-only modes ignore the option.  The same bits either way ("Layer-edge sources")
+ *   "gas_wave_roles"         fp64 longwave gas optics over the fp64 image of the tables: 1 the kernel whose blocks of 768 threads
+ *                            split the work of a tile by kind -- eight waves compute and store the optical depth, four the
+ *                            Planck sources -- wherever it is built (7 or 2 gas slots, g-point count a multiple of 4); 0 never
+ *                            (every wave does all the work of its columns); -1 (default) where it measured faster than the
+ *                            commit before it: the seven-slot shapes (gas optics + rte_lw 2.5 % faster at 1e6 columns with the
+ *                            32-g table, 2.8 % with the 36-g table, 1.5 % at 1e5 columns).  Single precision, the shortwave and
+ *                            tau-only modes and the float32 image ("gas_slab_f32") keep their kernels.  The same bits either way
+ *                            ("Wave roles")
  * --------------------------------------------------------------------------------------- */
 int ecckd_set_solver_option(const char *name, double value);
 int ecckd_get_solver_option(const char *name, double *value);

@@ -38,12 +38,12 @@ HOST, DEVICE = 0, 1
 MIXED = 2   # host inputs, device-resident spectral arrays (ECCKD_MIXED)
 NAME_LEN = 32
 
-_SOURCES = ["kernels_gas_fused.hip", "kernels_tau.hip", "kernels_planck.hip", "kernels_rte_lw.hip", "kernels_rte_lw_split.hip",
+_SOURCES = ["kernels_gas_fused.hip", "kernels_gas_roles.hip", "kernels_tau.hip", "kernels_planck.hip", "kernels_rte_lw.hip", "kernels_rte_lw_split.hip",
             "kernels_rte_lw_jac.hip", "kernels_rte_lw_2str.hip",
             "kernels_rte_sw.hip", "kernels_rte_sw_sys.hip", "kernels_rte_gpt.hip", "kernels_optical_props.hip",
             "kernels_cloud_sampling.hip", "kernels_cloud_optics.hip", "kernels_aerosol_optics.hip", "kernels_columns.hip",
             "capi.cpp", "nc_capi.cpp", "model.cpp", "cdf1.cpp"]
-_HEADERS = ["kernels.hpp", "wave_pair.hpp", "sw_two_stream.hpp", "sw_two_stream_body.inc", "lw_two_stream.hpp", "lw_layer.hpp", "planck_at.hpp", "model.hpp", "cdf1.hpp", os.path.join("..", "..", "include", "ecckd_hip.h"),
+_HEADERS = ["kernels.hpp", "wave_pair.hpp", "gas_fused_body.hpp", "sw_two_stream.hpp", "sw_two_stream_body.inc", "lw_two_stream.hpp", "lw_layer.hpp", "planck_at.hpp", "model.hpp", "cdf1.hpp", os.path.join("..", "..", "include", "ecckd_hip.h"),
             os.path.join("..", "..", "include", "ecckd_nc.h"), os.path.join("..", "..", "include", "rte_kernels_hip.h"),
             os.path.join("..", "..", "include", "rte_kernels_lw_2stream_hip.h")]
 # second library: RTE-RRTMGP's kernel-level bind(C) names over the C ABI of the first (include/rte_kernels_hip.h)
@@ -292,7 +292,7 @@ def get_arithmetic():
 
 SOLVER_OPTIONS = ("lw_tau_thresh", "lw_series_terms", "lw_inc_flux_isotropic", "sw_k_floor", "sw_dir_clamp", "lw_solver",
                   "lw_split_seg", "gas_merge_scalars", "lw_tail_split", "sw_tail_split", "sw_solver", "gas_slab_f32",
-                  "gas_tile_sync", "gas_input_ahead")
+                  "gas_tile_sync", "gas_input_ahead", "gas_wave_roles")
 
 
 def set_solver_option(name, value):

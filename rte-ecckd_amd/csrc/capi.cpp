@@ -244,6 +244,10 @@ struct SolverOptions {
   // tile before the chunk loops of the tile in hand (same bits), 0 = at the top of the tile, -1 (default) = per mode as
   // measured ("Layer-edge sources", profiles/gas_lean.json)
   std::atomic<int> gas_input_ahead{-1};
+  // fp64 longwave gas optics: 1 = gas_roles_kernel (tau waves and source waves share a block of 768 threads; same bits)
+  // wherever it is instantiated, 0 = never (gas_fused_kernel), -1 (default) = per shape as measured against the parent
+  // commit's build ("Wave roles", profiles/gas_wave_roles.json; kernels_gas_roles.hip: gas_roles_default)
+  std::atomic<int> gas_wave_roles{-1};
   std::atomic<int> sw_solver{0};   // 0 layer-systolic (kernels_rte_sw_sys.hip; up to 60 layers), 1 per-lane two-pass kernel
   // ecckd_lw_fluxes_clear_allsky at 60 layers: 0 the clear-sky and the all-sky kernel one after the other, 1 the dual-sky
   // kernel (rte_lw_split_both_kernel); same bits.  1: its min-max range lies below that of 0 at every 60-layer shape and
@@ -445,6 +449,7 @@ int gas_optical_depth_dev(const ecckd_model *m, bool f32, PlanRecord *plan, int 
         fa.tile_sync = sync >= 0 ? sync : (fa.mode != 0 ? 1 : 0);
         const int ahead = g_opt.gas_input_ahead.load();
         fa.input_ahead = ahead >= 0 ? ahead : kGasInputAheadDefault[f32 ? 1 : 0];
+        fa.wave_roles = (fa.mode == 1 && !f32) ? g_opt.gas_wave_roles.load() : 0;   // (prepare_gas_fused resolves it per shape)
       }
       // fp64 over the float32 image of the tables in LDS ("gas_slab_f32": 0 never, 1 always, 2 where the probe finds the
       // columns spread over many pressure rows); the probe's counter is a word that belongs to this stream
@@ -953,9 +958,14 @@ int ecckd_set_solver_option(const char *name, double value) {
       return fail("ecckd_set_solver_option: gas_input_ahead must be 0 (inputs loaded at the top of a tile), 1 (a tile ahead) or -1 (the default of each mode)");
     g_opt.gas_input_ahead.store((int)value);
   }
+  else if (n == "gas_wave_roles") {
+    if (value != 0. && value != 1. && value != -1.)
+      return fail("ecckd_set_solver_option: gas_wave_roles must be 0 (never), 1 (wherever the wave-roles kernel exists) or -1 (the default of each shape)");
+    g_opt.gas_wave_roles.store((int)value);
+  }
   else return fail("ecckd_set_solver_option: unknown option '" + n + "' (lw_tau_thresh, lw_series_terms, "
                    "lw_inc_flux_isotropic, sw_k_floor, sw_dir_clamp, lw_solver, lw_split_seg, gas_merge_scalars, lw_tail_split, "
-                   "sw_tail_split, sw_solver, gas_slab_f32, gas_tile_sync, gas_input_ahead, lw_both_skies, lw_jac_inline)");
+                   "sw_tail_split, sw_solver, gas_slab_f32, gas_tile_sync, gas_input_ahead, gas_wave_roles, lw_both_skies, lw_jac_inline)");
   return 0;
 }
 
@@ -976,6 +986,7 @@ int ecckd_get_solver_option(const char *name, double *value) {
   else if (n == "gas_slab_f32") *value = g_opt.gas_slab_f32.load();
   else if (n == "gas_tile_sync") *value = g_opt.gas_tile_sync.load();
   else if (n == "gas_input_ahead") *value = g_opt.gas_input_ahead.load();
+  else if (n == "gas_wave_roles") *value = g_opt.gas_wave_roles.load();
   else if (n == "lw_both_skies") *value = g_opt.lw_both_skies.load();
   else if (n == "lw_jac_inline") *value = g_opt.lw_jac_inline.load();
   else return fail("ecckd_get_solver_option: unknown option '" + n + "'");

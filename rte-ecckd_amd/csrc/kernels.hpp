@@ -98,6 +98,9 @@ struct FusedArgs {
   long long lev_gstride;       // g-plane stride of the two level arrays, elements: nlay*ncol for separate arrays (0 means that),
                                // (nlay+1)*ncol for the two views of one level buffer (include/ecckd_hip.h, "Level buffer"):
                                // lev_source_inc == lev_source_dec + ncol, and each level is stored once
+  int wave_roles;              // "gas_wave_roles": 1 = gas_roles_kernel (kernels_gas_roles.hip: tau waves and source waves share a
+                               // block) where it exists, -1 = where it is the default of the shape; prepare_gas_fused resolves it
+                               // to 0 or 1 (fp64 longwave over the fp64 slab, the shapes of gas_roles_applies)
 };
 
 struct PlanckArgs {
@@ -368,6 +371,12 @@ int merge_scalar_gases(TauArgs &t, int f32);
 int fused_slab_rows(int ng, int np, int nt, int nbil, int nv_lut, int pl_rows, int min_rows, int anyclamp, int f32, int block = 0);   // block: threads per block (0: the default 512)
 int fused_planck_rows(int ng, int np, int nt, int nbil, int nv_lut, int ntp, int anyclamp, int f32);
 hipError_t launch_gas_fused(FusedArgs &a, hipStream_t s);
+// gas_roles_kernel (kernels_gas_roles.hip), the wave-roles form of the fp64 longwave launch: is there an instantiation for
+// (g-points per chunk, bilinear slots); is it that shape's default ("gas_wave_roles" = -1: decided by measurement,
+// profiles/gas_wave_roles.json); the launch itself (a prepared by prepare_gas_fused with wave_roles = 1)
+bool gas_roles_applies(int GC, int NB);
+bool gas_roles_default(int GC, int NB);
+hipError_t launch_gas_roles(const FusedArgs &a, int GC, int NB, size_t lds_bytes, hipStream_t s);
 // planck_edge_kernel (kernels_planck.hip): the sources of a fused longwave launch that belong to no layer -- sfc_source and,
 // with tlev, lev_source_dec of storage layer 0; launch_gas_fused calls it once per longwave call, on the same stream
 hipError_t launch_planck_edge(const FusedArgs &a, hipStream_t s);

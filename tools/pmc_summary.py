@@ -25,6 +25,8 @@ def short(name):
         if m.group(1) == "double" and m.group(3) == "float":      # fp64 over the float32 image of the tables ("gas_slab_f32"):
             return base + "_slab32"                               # with the option on auto this is the launch that returns at once
         return base + ("_f32" if m.group(1) == "float" else "")
+    if "gas_roles_kernel" in name:      # the wave-roles form of the fp64 longwave launch ("gas_wave_roles")
+        return "gas_lw_roles"
     m = re.search(r"rte_lw_kernel<(\w+), \d+, \d+, \w+, \w+, (\w+), \w+(?:, \w+)?>", name)
     if m:
         return "rte_lw" + ("_f32" if m.group(1) == "float" else "") + ("_shared_levels" if m.group(2) == "true" else "")
