@@ -565,6 +565,105 @@ int ecckd_sw_fluxes_clear_allsky(const ecckd_model_t *model, int ncol, int nlay,
                                  void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Single-precision fused fluxes: longwave, all-sky, McICA, both skies.  For a host built with wp = real32: the argument list
+ * of the fp64 namesake with every `double` data pointer made `float`; vmr_scalar stays `const double *` and cloud_mask stays
+ * `const unsigned long long *`, as in ecckd_sw_fluxes_f32 and ecckd_increment_masked_f32.  ECCKD_DEVICE (asynchronous on
+ * `stream`) or ECCKD_HOST; fast arithmetic mode only; tau_p / ssa_p / g_p and the mask are never written; cloud_mask NULL in
+ * a *_mcica_f32 or *_clear_allsky_f32 call is the unmasked call.  Each call answers the refusal list of its fp64 namesake, in
+ * its order and with its messages, before any device is asked for (a mask with more than 64 g-points first).  No call sets a
+ * thread-local.
+ *
+ * Longwave (ecckd_lw_fluxes_f32, _allsky_f32, _allsky_mcica_f32, _clear_allsky_f32), at every layer count: the
+ * single-precision gas optics writes tau, lay_source, the two level arrays and sfc_source (float) into the work block and the
+ * single-precision register-resident solver follows on them -- 1 to 4 angles, inc_flux and both orientations as
+ * ecckd_rte_lw_inc_flux_f32.  The all-sky forms run rte_lw_allsky_f32_kernel, which adds the layer's particulate optical
+ * depth on the cell's band where it consumes tau: tau + tau_p * (1 - ssa_p) (ssa_p NULL: tau + tau_p), and with a mask
+ * tau + 0 * (1 - ssa_p) where the g-point's bit is clear -- the operations of ecckd_increment_f32 /
+ * ecckd_increment_masked_f32 on one-stream optical properties, one by one.  The fluxes are therefore, BIT FOR BIT,
+ *     ecckd_lw_fluxes_f32            =  ecckd_gas_optics_lw_f32 + ecckd_rte_lw_f32 (ecckd_rte_lw_inc_flux_f32 with inc_flux),
+ *     ecckd_lw_fluxes_allsky_f32     =  ... with ecckd_increment_f32 of tau by the band planes in between,
+ *     ..._allsky_mcica_f32           =  ... with ecckd_increment_masked_f32 in between,
+ * without the read-modify-write pass over tau and without the host owning an (ncol,nlay,ngpt) array.  Both skies: the
+ * clear-sky kernel and then the all-sky kernel on the same arrays (there is no dual-sky kernel).
+ *   Scratch (ECCKD_DEVICE): ecckd_lw_fluxes_f32_scratch_bytes(model, ncol, nlay) bytes of the stream's block, the same for all
+ *   four calls, laid out as: tau, lay_source, lev_source_inc, lev_source_dec, each A = align256(ncol*nlay*ngpt*4) bytes;
+ *   sfc_source, align256(ncol*ngpt*4); the ring of the overflow solver, align256(ecckd_rte_lw_scratch_bytes(ncol, nlay,
+ *   ngpt)) (0 up to 96 layers); align256(n) = n rounded up to a multiple of 256.  The partial sums of the tail split
+ *   (ecckd_rte_lw_tail_scratch_bytes(device, ncol, nlay, ngpt, n_gauss_angles, 1)) follow only where the block has room for
+ *   them -- a library-owned block outside a capture grows to hold them, a caller-owned block of exactly the size above runs
+ *   without the split; the split does not change a bit.  24 bytes per cell go through memory between the kernels.
+ *
+ * Shortwave (ecckd_sw_fluxes_allsky_f32, _allsky_mcica_f32, _clear_allsky_f32): the route of the fp64 calls in float --
+ * delta scaling of a copy of the band triple (ecckd_delta_scale_f32's kernel), the single-precision gas optics (total optical
+ * depth only), then the solver ecckd_rte_sw_f32 takes for the shape (layer-systolic up to 60 layers, two-pass beyond or with
+ * "sw_solver" = 1) in its all-sky / McICA float form, which forms ssa and g of a cell with the expressions of
+ * ecckd_increment_f32 (floor 3*tiny(1._sp)) and keeps the single-precision k floor of ecckd_rte_sw_f32.  Both skies: the
+ * clear-sky solver of ecckd_sw_fluxes_f32 first, on the same optical depth.  As in fp64 the fluxes agree with the composition
+ * ecckd_gas_optics_sw_f32 + ecckd_delta_scale_f32 + ecckd_increment_f32 + ecckd_rte_sw_f32 to rounding, not bit for bit (ssa
+ * is formed in another order); the clear-sky output of _clear_allsky_f32 equals ecckd_sw_fluxes_f32 and its all-sky output
+ * equals ecckd_sw_fluxes_allsky[_mcica]_f32 bit for bit.
+ *   Scratch (ECCKD_DEVICE): ecckd_sw_fluxes_allsky_f32_scratch_bytes(model, ncol, nlay, delta_scale) bytes, laid out as the
+ *   fp64 block: the optical depth, align256(ncol*nlay*ngpt*4); the solver's room S; with delta_scale three planes of
+ *   align256(ncol*nlay*nband*4).  S = ecckd_rte_sw_tail_scratch_bytes(device, ncol, nlay, ngpt) for the layer-systolic
+ *   solver, else the larger of that and ecckd_rte_sw_scratch_bytes(ncol, nlay, ngpt).
+ * The capture rules of the stream scratch hold for both: capture after one warm-up call on the stream, or with a
+ * caller-owned block (ecckd_set_stream_scratch) of the size above.
+ *
+ * Out of scope: the Fortran shim (fp64 throughout); ecckd_sw_fluxes_daylit; the Jacobian, rescaled and two-stream longwave
+ * calls in single precision; per-band outputs; a single-precision Planck-recomputing longwave kernel (8 instead of 24 bytes
+ * per cell between the kernels: the obvious follow-up, not measured); the in-solver addition for the fp64 general route at
+ * layer counts other than 60.
+ * --------------------------------------------------------------------------------------- */
+size_t ecckd_lw_fluxes_f32_scratch_bytes(const ecckd_model_t *model, int ncol, int nlay);
+size_t ecckd_sw_fluxes_allsky_f32_scratch_bytes(const ecckd_model_t *model, int ncol, int nlay, int delta_scale);
+int ecckd_lw_fluxes_f32(const ecckd_model_t *model, int ncol, int nlay, const float *plev, const float *tlay, const float *tsfc,
+                        const float *tlev, int ngas, const char *gas_names, const float *const *vmr,
+                        const long long *vmr_col_stride, const long long *vmr_lay_stride, const double *vmr_scalar, int top_at_1,
+                        int n_gauss_angles, const float *sfc_emis, const float *inc_flux, float *flux_up, float *flux_dn,
+                        int memspace, void *stream);
+int ecckd_lw_fluxes_allsky_f32(const ecckd_model_t *model, int ncol, int nlay, const float *plev, const float *tlay,
+                               const float *tsfc, const float *tlev, int ngas, const char *gas_names, const float *const *vmr,
+                               const long long *vmr_col_stride, const long long *vmr_lay_stride, const double *vmr_scalar,
+                               int top_at_1, int n_gauss_angles, const float *sfc_emis, const float *inc_flux, int nband_p,
+                               const float *tau_p, const float *ssa_p, float *flux_up, float *flux_dn, int memspace,
+                               void *stream);
+int ecckd_lw_fluxes_allsky_mcica_f32(const ecckd_model_t *model, int ncol, int nlay, const float *plev, const float *tlay,
+                                     const float *tsfc, const float *tlev, int ngas, const char *gas_names,
+                                     const float *const *vmr, const long long *vmr_col_stride, const long long *vmr_lay_stride,
+                                     const double *vmr_scalar, int top_at_1, int n_gauss_angles, const float *sfc_emis,
+                                     const float *inc_flux, int nband_p, const float *tau_p, const float *ssa_p,
+                                     const unsigned long long *cloud_mask, float *flux_up, float *flux_dn, int memspace,
+                                     void *stream);
+int ecckd_lw_fluxes_clear_allsky_f32(const ecckd_model_t *model, int ncol, int nlay, const float *plev, const float *tlay,
+                                     const float *tsfc, const float *tlev, int ngas, const char *gas_names,
+                                     const float *const *vmr, const long long *vmr_col_stride, const long long *vmr_lay_stride,
+                                     const double *vmr_scalar, int top_at_1, int n_gauss_angles, const float *sfc_emis,
+                                     const float *inc_flux, int nband_p, const float *tau_p, const float *ssa_p,
+                                     const unsigned long long *cloud_mask, float *flux_up, float *flux_dn, float *flux_up_clear,
+                                     float *flux_dn_clear, int memspace, void *stream);
+int ecckd_sw_fluxes_allsky_f32(const ecckd_model_t *model, int ncol, int nlay, const float *plev, const float *tlay, int ngas,
+                               const char *gas_names, const float *const *vmr, const long long *vmr_col_stride,
+                               const long long *vmr_lay_stride, const double *vmr_scalar, int top_at_1, const float *mu0,
+                               const float *toa_scale, const float *sfc_alb_dir, const float *sfc_alb_dif, int nband_p,
+                               const float *tau_p, const float *ssa_p, const float *g_p, int delta_scale, float *flux_up,
+                               float *flux_dn, float *flux_dir, int memspace, void *stream);
+int ecckd_sw_fluxes_allsky_mcica_f32(const ecckd_model_t *model, int ncol, int nlay, const float *plev, const float *tlay, int ngas,
+                                     const char *gas_names, const float *const *vmr, const long long *vmr_col_stride,
+                                     const long long *vmr_lay_stride, const double *vmr_scalar, int top_at_1, const float *mu0,
+                                     const float *toa_scale, const float *sfc_alb_dir, const float *sfc_alb_dif, int nband_p,
+                                     const float *tau_p, const float *ssa_p, const float *g_p, int delta_scale,
+                                     const unsigned long long *cloud_mask, float *flux_up, float *flux_dn, float *flux_dir,
+                                     int memspace, void *stream);
+int ecckd_sw_fluxes_clear_allsky_f32(const ecckd_model_t *model, int ncol, int nlay, const float *plev, const float *tlay, int ngas,
+                                     const char *gas_names, const float *const *vmr, const long long *vmr_col_stride,
+                                     const long long *vmr_lay_stride, const double *vmr_scalar, int top_at_1, const float *mu0,
+                                     const float *toa_scale, const float *sfc_alb_dir, const float *sfc_alb_dif, int nband_p,
+                                     const float *tau_p, const float *ssa_p, const float *g_p, int delta_scale,
+                                     const unsigned long long *cloud_mask, float *flux_up, float *flux_dn, float *flux_dir,
+                                     float *flux_up_clear, float *flux_dn_clear, float *flux_dir_clear, int memspace,
+                                     void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * The shortwave on the daylit columns only.  Every shortwave call above computes every column it is given; on a global grid
  * the sun is below the horizon in about half of them.  The reference's driver computes those with mu0 = 1 "for a better
  * measure of timing" and zeroes their fluxes afterwards (ecckd_rfmip_sw.F90:103-108,143-145,156-161); a production host

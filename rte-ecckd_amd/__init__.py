@@ -43,7 +43,7 @@ _SOURCES = ["kernels_gas_fused.hip", "kernels_gas_roles.hip", "kernels_tau.hip",
             "kernels_rte_sw.hip", "kernels_rte_sw_sys.hip", "kernels_rte_gpt.hip", "kernels_optical_props.hip",
             "kernels_cloud_sampling.hip", "kernels_cloud_optics.hip", "kernels_aerosol_optics.hip", "kernels_columns.hip",
             "capi.cpp", "nc_capi.cpp", "model.cpp", "cdf1.cpp"]
-_HEADERS = ["kernels.hpp", "wave_pair.hpp", "gas_fused_body.hpp", "sw_two_stream.hpp", "sw_two_stream_body.inc", "lw_two_stream.hpp", "lw_layer.hpp", "planck_at.hpp", "model.hpp", "cdf1.hpp", os.path.join("..", "..", "include", "ecckd_hip.h"),
+_HEADERS = ["kernels.hpp", "wave_pair.hpp", "gas_fused_body.hpp", "sw_two_stream.hpp", "sw_two_stream_body.inc", "rte_lw_body.inc", "lw_two_stream.hpp", "lw_layer.hpp", "planck_at.hpp", "model.hpp", "cdf1.hpp", os.path.join("..", "..", "include", "ecckd_hip.h"),
             os.path.join("..", "..", "include", "ecckd_nc.h"), os.path.join("..", "..", "include", "rte_kernels_hip.h"),
             os.path.join("..", "..", "include", "rte_kernels_lw_2stream_hip.h")]
 # second library: RTE-RRTMGP's kernel-level bind(C) names over the C ABI of the first (include/rte_kernels_hip.h)
@@ -207,6 +207,22 @@ def lib():
         L.ecckd_sw_fluxes_clear_allsky.argtypes = ([C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 2 + [C.c_int, C.c_char_p] +
                                                    [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 3 +
                                                    [C.c_int] + [C.c_void_p] * 7 + [C.c_int, C.c_void_p])
+    if hasattr(L, "ecckd_lw_fluxes_allsky_f32"):   # (an older build lacks them: tools/bench_allsky_f32.py --parent-lib)
+        lw_head = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_char_p] + [C.c_void_p] * 4
+        sw_head = ([C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 2 + [C.c_int, C.c_char_p] + [C.c_void_p] * 4 + [C.c_int] +
+                   [C.c_void_p] * 4)
+        tail = [C.c_int, C.c_void_p]
+        L.ecckd_lw_fluxes_f32.argtypes = lw_head + [C.c_int, C.c_int] + [C.c_void_p] * 4 + tail
+        for f, nptr in (("ecckd_lw_fluxes_allsky_f32", 4), ("ecckd_lw_fluxes_allsky_mcica_f32", 5),
+                        ("ecckd_lw_fluxes_clear_allsky_f32", 7)):
+            getattr(L, f).argtypes = lw_head + [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * nptr + tail
+        for f, nptr in (("ecckd_sw_fluxes_allsky_f32", 3), ("ecckd_sw_fluxes_allsky_mcica_f32", 4),
+                        ("ecckd_sw_fluxes_clear_allsky_f32", 7)):
+            getattr(L, f).argtypes = sw_head + [C.c_int] + [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * nptr + tail
+        L.ecckd_lw_fluxes_f32_scratch_bytes.restype = C.c_size_t
+        L.ecckd_lw_fluxes_f32_scratch_bytes.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        L.ecckd_sw_fluxes_allsky_f32_scratch_bytes.restype = C.c_size_t
+        L.ecckd_sw_fluxes_allsky_f32_scratch_bytes.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
     if hasattr(L, "ecckd_sw_fluxes_daylit"):   # (an older build lacks them: tools/bench_sw_daylit.py times the parent's library)
         for f in ("ecckd_daylit_columns", "ecckd_daylit_columns_f32"):
             getattr(L, f).argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_void_p, C.POINTER(C.c_int), C.c_int, C.c_void_p]
@@ -396,6 +412,31 @@ def _is_f32(a):
         import torch
         return a.dtype == torch.float32
     return isinstance(a, np.ndarray) and a.dtype == np.float32
+
+
+def _call_precision(who, named):
+    """Precision of a fused call from its ``(name, array)`` pairs: ``(f32, "")`` with the precision of the first float32 /
+    float64 array, or ``(f32, message)`` where a later one has the other precision (it is named).  Arrays of any other
+    type are left to the pointer checks."""
+    first = None
+    for name, a in named:
+        if _is_f32(a):
+            p = True
+        elif a is not None and str(getattr(a, "dtype", "")).endswith("float64"):
+            p = False
+        else:
+            continue
+        if first is None:
+            first = (name, p)
+        elif p != first[1]:
+            kind = lambda x: "float32" if x else "float64"
+            return first[1], "%s: mixing float32 and float64 arrays in one call (%s is %s, %s is %s)" % (
+                who, first[0], kind(first[1]), name, kind(p))
+    return (first[1] if first else False), ""
+
+
+def _f64_only(who, what):
+    return "%s: %s is implemented for float64 arrays" % (who, what)
 
 
 def _ptr(a, shape=None, what="array", f32=False):
@@ -1377,23 +1418,32 @@ class GasOpticsEcckd:
         """``ecckd_lw_fluxes``: gas optics + rte_lw in one call for hosts that only need broadband fluxes (tau in
         library-owned scratch, sources recomputed in the solver); numpy or device tensors.  ``flux_up_jac``
         ``(nlay+1, ncol)`` float64 (``ecckd_lw_fluxes_jac``): receives the derivative of ``flux_up`` with respect to the
-        surface temperature, W m-2 K-1; the fluxes are the same bits with and without it."""
+        surface temperature, W m-2 K-1; the fluxes are the same bits with and without it.  float32 arrays (all of them)
+        take ``ecckd_lw_fluxes_f32``: the fluxes of ``gas_optics`` + ``rte_lw`` on float32 arrays, bit for bit; no
+        ``flux_up_jac``."""
+        f32, mixed = _call_precision("lw_fluxes", (("plev", plev), ("tlay", tlay), ("tsfc", tsfc), ("tlev", tlev), ("sfc_emis", sfc_emis),
+                                                   ("inc_flux", inc_flux), ("flux_up", fluxes.flux_up), ("flux_dn", fluxes.flux_dn),
+                                                   ("flux_up_jac", flux_up_jac)))
+        if mixed:
+            return mixed
         if flux_up_jac is not None:
+            if f32:
+                return _f64_only("lw_fluxes", "flux_up_jac")
             return self._lw_fluxes_jac(plev, tlay, tsfc, tlev, gas_desc, top_at_1, sfc_emis, None, fluxes, None, n_gauss_angles,
                                        inc_flux, None, flux_up_jac)
         nlay, ncol = tlay.shape
         ng = self.get_ngpt()
         try:
             space = _space_of([plev, tlay, tsfc, tlev, sfc_emis, inc_flux, fluxes.flux_up, fluxes.flux_dn])
-            n, names, ptrs, cs, ls, sc, keep = self._gas_args(gas_desc, ncol, nlay, space)
+            n, names, ptrs, cs, ls, sc, keep = self._gas_args(gas_desc, ncol, nlay, space, f32)
         except KeyError as e:
             return str(e.args[0])
-        rc = lib().ecckd_lw_fluxes(self._need(), ncol, nlay, _ptr(plev, (nlay + 1, ncol), "plev"),
-                                   _ptr(tlay, (nlay, ncol), "tlay"), _ptr(tsfc, (ncol,), "tsfc"),
-                                   _ptr(tlev, (nlay + 1, ncol), "tlev"), n, names, ptrs, cs, ls, sc, int(bool(top_at_1)),
-                                   int(n_gauss_angles), _ptr(sfc_emis, (ncol, self.get_nband()), "sfc_emis"),
-                                   _ptr(inc_flux, (ng, ncol), "inc_flux"), _ptr(fluxes.flux_up, (nlay + 1, ncol), "flux_up"),
-                                   _ptr(fluxes.flux_dn, (nlay + 1, ncol), "flux_dn"), space, _stream(space))
+        P = lambda a, shape, what: _ptr(a, shape, what, f32)
+        rc = (lib().ecckd_lw_fluxes_f32 if f32 else lib().ecckd_lw_fluxes)(
+            self._need(), ncol, nlay, P(plev, (nlay + 1, ncol), "plev"), P(tlay, (nlay, ncol), "tlay"), P(tsfc, (ncol,), "tsfc"),
+            P(tlev, (nlay + 1, ncol), "tlev"), n, names, ptrs, cs, ls, sc, int(bool(top_at_1)), int(n_gauss_angles),
+            P(sfc_emis, (ncol, self.get_nband()), "sfc_emis"), P(inc_flux, (ng, ncol), "inc_flux"),
+            P(fluxes.flux_up, (nlay + 1, ncol), "flux_up"), P(fluxes.flux_dn, (nlay + 1, ncol), "flux_dn"), space, _stream(space))
         return last_error() if rc else ""
 
     def _lw_fluxes_allsky_2stream(self, plev, tlay, tsfc, tlev, gas_desc, top_at_1, sfc_emis, particles, fluxes, n_gauss_angles,
@@ -1480,7 +1530,20 @@ class GasOpticsEcckd:
         what RTE-RRTMGP's ``rte_lw`` runs on two-stream properties without ``use_2stream``: cloud scattering as an adjustment of
         the no-scattering sweeps, with the quadrature (``n_gauss_angles`` 1..4); a two-stream ``particles`` object with ``g``,
         float64; refused with ``use_2stream=True``, ``flux_up_jac`` (``lw_fluxes_rescaled`` returns it, and the clear sky),
-        ``FluxesByband``.  Returns the error message ('' = success)."""
+        ``FluxesByband``.  float32 arrays (all of them) take ``ecckd_lw_fluxes_allsky_f32`` / ``_mcica_f32``: the fluxes of
+        ``gas_optics`` + ``increment(particles, band2gpt[, cloud_mask])`` + ``rte_lw`` on float32 arrays, bit for bit;
+        ``flux_up_jac``, ``rescaled`` and ``use_2stream`` are float64 only.  Returns the error message ('' = success)."""
+        who = "lw_fluxes_allsky"
+        f32, mixed = _call_precision(who, (
+            ("plev", plev), ("tlay", tlay), ("tsfc", tsfc), ("tlev", tlev), ("sfc_emis", sfc_emis), ("inc_flux", inc_flux),
+            ("particles.tau", particles.tau), ("particles.ssa", getattr(particles, "ssa", None)), ("flux_up", fluxes.flux_up),
+            ("flux_dn", fluxes.flux_dn), ("flux_up_jac", flux_up_jac)))
+        if f32 or mixed:   # (float64 calls with these keywords keep the messages of their own routes)
+            for on, what in ((rescaled, "rescaled=True"), (use_2stream, "use_2stream=True"), (flux_up_jac is not None, "flux_up_jac")):
+                if on:
+                    return mixed or _f64_only(who, what)
+        if mixed:
+            return mixed
         if rescaled:
             return self._lw_fluxes_allsky_rescaled(plev, tlay, tsfc, tlev, gas_desc, top_at_1, sfc_emis, particles, fluxes,
                                                    n_gauss_angles, inc_flux, cloud_mask, use_2stream, flux_up_jac)
@@ -1495,22 +1558,27 @@ class GasOpticsEcckd:
         ssa = getattr(particles, "ssa", None)
         try:
             space = _space_of([plev, tlay, tsfc, tlev, sfc_emis, inc_flux, fluxes.flux_up, fluxes.flux_dn, particles.tau, ssa])
-            n, names, ptrs, cs, ls, sc, keep = self._gas_args(gas_desc, ncol, nlay, space)
+            n, names, ptrs, cs, ls, sc, keep = self._gas_args(gas_desc, ncol, nlay, space, f32)
             nbp = 0 if particles.tau is None else int(particles.tau.shape[0])
             shp = (nbp, nlay, ncol)
-            part = (_ptr(particles.tau, shp, "particles.tau"), _ptr(ssa, shp, "particles.ssa"))
+            part = (_ptr(particles.tau, shp, "particles.tau", f32), _ptr(ssa, shp, "particles.ssa", f32))
             if cloud_mask is not None:
                 part = part + (_mask_ptr(cloud_mask, nlay, ncol, space),)
         except KeyError as e:
             return str(e.args[0])
         except (TypeError, ValueError) as e:
             return str(e)
-        rc = (lib().ecckd_lw_fluxes_allsky if cloud_mask is None else lib().ecckd_lw_fluxes_allsky_mcica)(
-            self._need(), ncol, nlay, _ptr(plev, (nlay + 1, ncol), "plev"), _ptr(tlay, (nlay, ncol), "tlay"),
-            _ptr(tsfc, (ncol,), "tsfc"), _ptr(tlev, (nlay + 1, ncol), "tlev"), n, names, ptrs, cs, ls, sc, int(bool(top_at_1)),
-            int(n_gauss_angles), _ptr(sfc_emis, (ncol, self.get_nband()), "sfc_emis"), _ptr(inc_flux, (ng, ncol), "inc_flux"),
-            nbp, *part, _ptr(fluxes.flux_up, (nlay + 1, ncol), "flux_up"), _ptr(fluxes.flux_dn, (nlay + 1, ncol), "flux_dn"),
-            space, _stream(space))
+        L = lib()
+        if f32:
+            fn = L.ecckd_lw_fluxes_allsky_f32 if cloud_mask is None else L.ecckd_lw_fluxes_allsky_mcica_f32
+        else:
+            fn = L.ecckd_lw_fluxes_allsky if cloud_mask is None else L.ecckd_lw_fluxes_allsky_mcica
+        P = lambda a, shape, what: _ptr(a, shape, what, f32)
+        rc = fn(self._need(), ncol, nlay, P(plev, (nlay + 1, ncol), "plev"), P(tlay, (nlay, ncol), "tlay"),
+                P(tsfc, (ncol,), "tsfc"), P(tlev, (nlay + 1, ncol), "tlev"), n, names, ptrs, cs, ls, sc, int(bool(top_at_1)),
+                int(n_gauss_angles), P(sfc_emis, (ncol, self.get_nband()), "sfc_emis"), P(inc_flux, (ng, ncol), "inc_flux"),
+                nbp, *part, P(fluxes.flux_up, (nlay + 1, ncol), "flux_up"), P(fluxes.flux_dn, (nlay + 1, ncol), "flux_dn"),
+                space, _stream(space))
         return last_error() if rc else ""
 
     def lw_fluxes_rescaled(self, plev, tlay, tsfc, tlev, gas_desc, top_at_1, sfc_emis, particles, fluxes, fluxes_clear=None,
@@ -1563,30 +1631,37 @@ class GasOpticsEcckd:
         """``ecckd_lw_fluxes_clear_allsky``: one gas-optics pass, then both skies -- ``fluxes_clear`` receives what
         ``lw_fluxes`` writes and ``fluxes`` what ``lw_fluxes_allsky(..., cloud_mask=cloud_mask)`` writes, bit for bit.
         ``particles`` and ``cloud_mask`` as for ``lw_fluxes_allsky``; neither is written.  float64, fast arithmetic mode;
-        numpy or device tensors.  Returns the error message ('' = success).  With the surface-temperature Jacobian:
-        ``lw_fluxes_clear_allsky_jac``."""
+        numpy or device tensors.  float32 arrays (all of them) take ``ecckd_lw_fluxes_clear_allsky_f32``.  Returns the
+        error message ('' = success).  With the surface-temperature Jacobian: ``lw_fluxes_clear_allsky_jac`` (float64)."""
         nlay, ncol = tlay.shape
         ng = self.get_ngpt()
         ssa = getattr(particles, "ssa", None)
+        f32, mixed = _call_precision("lw_fluxes_clear_allsky", (
+            ("plev", plev), ("tlay", tlay), ("tsfc", tsfc), ("tlev", tlev), ("sfc_emis", sfc_emis), ("inc_flux", inc_flux),
+            ("particles.tau", particles.tau), ("particles.ssa", ssa), ("flux_up", fluxes.flux_up), ("flux_dn", fluxes.flux_dn),
+            ("flux_up_clear", fluxes_clear.flux_up), ("flux_dn_clear", fluxes_clear.flux_dn)))
+        if mixed:
+            return mixed
+        P = lambda a, shape, what: _ptr(a, shape, what, f32)
         try:
             space = _space_of([plev, tlay, tsfc, tlev, sfc_emis, inc_flux, fluxes.flux_up, fluxes.flux_dn, fluxes_clear.flux_up,
                                fluxes_clear.flux_dn, particles.tau, ssa])
-            n, names, ptrs, cs, ls, sc, keep = self._gas_args(gas_desc, ncol, nlay, space)
+            n, names, ptrs, cs, ls, sc, keep = self._gas_args(gas_desc, ncol, nlay, space, f32)
             nbp = 0 if particles.tau is None else int(particles.tau.shape[0])
             shp = (nbp, nlay, ncol)
-            part = (_ptr(particles.tau, shp, "particles.tau"), _ptr(ssa, shp, "particles.ssa"),
+            part = (P(particles.tau, shp, "particles.tau"), P(ssa, shp, "particles.ssa"),
                     None if cloud_mask is None else _mask_ptr(cloud_mask, nlay, ncol, space))
-            out = tuple(_ptr(a, (nlay + 1, ncol), what) for a, what in (
+            out = tuple(P(a, (nlay + 1, ncol), what) for a, what in (
                 (fluxes.flux_up, "flux_up"), (fluxes.flux_dn, "flux_dn"), (fluxes_clear.flux_up, "flux_up_clear"),
                 (fluxes_clear.flux_dn, "flux_dn_clear")))
         except KeyError as e:
             return str(e.args[0])
         except (TypeError, ValueError) as e:
             return str(e)
-        rc = lib().ecckd_lw_fluxes_clear_allsky(
-            self._need(), ncol, nlay, _ptr(plev, (nlay + 1, ncol), "plev"), _ptr(tlay, (nlay, ncol), "tlay"),
-            _ptr(tsfc, (ncol,), "tsfc"), _ptr(tlev, (nlay + 1, ncol), "tlev"), n, names, ptrs, cs, ls, sc, int(bool(top_at_1)),
-            int(n_gauss_angles), _ptr(sfc_emis, (ncol, self.get_nband()), "sfc_emis"), _ptr(inc_flux, (ng, ncol), "inc_flux"),
+        rc = (lib().ecckd_lw_fluxes_clear_allsky_f32 if f32 else lib().ecckd_lw_fluxes_clear_allsky)(
+            self._need(), ncol, nlay, P(plev, (nlay + 1, ncol), "plev"), P(tlay, (nlay, ncol), "tlay"),
+            P(tsfc, (ncol,), "tsfc"), P(tlev, (nlay + 1, ncol), "tlev"), n, names, ptrs, cs, ls, sc, int(bool(top_at_1)),
+            int(n_gauss_angles), P(sfc_emis, (ncol, self.get_nband()), "sfc_emis"), P(inc_flux, (ng, ncol), "inc_flux"),
             nbp, *part, *out, space, _stream(space))
         return last_error() if rc else ""
 
@@ -1597,6 +1672,8 @@ class GasOpticsEcckd:
         ``lw_fluxes_clear_allsky`` is fixed.)  Every flux array holds the bits ``lw_fluxes_clear_allsky`` writes."""
         if flux_up_jac is None:
             return "lw_fluxes_clear_allsky_jac: flux_up_jac is required"
+        if _is_f32(tlay) or _is_f32(flux_up_jac):
+            return _f64_only("lw_fluxes_clear_allsky_jac", "flux_up_jac")
         return self._lw_fluxes_jac(plev, tlay, tsfc, tlev, gas_desc, top_at_1, sfc_emis, particles, fluxes, fluxes_clear,
                                    n_gauss_angles, inc_flux, cloud_mask, flux_up_jac)
 
@@ -1605,19 +1682,29 @@ class GasOpticsEcckd:
         """``ecckd_sw_fluxes_clear_allsky``: one gas-optics pass, then both skies -- ``fluxes_clear`` receives what
         ``sw_fluxes`` writes and ``fluxes`` what ``sw_fluxes_allsky(..., cloud_mask=cloud_mask)`` writes, bit for bit.
         ``flux_dn_dir`` of either may be None independently of the other.  float64, fast arithmetic mode; numpy or device
-        tensors.  Returns the error message ('' = success)."""
+        tensors.  float32 arrays (all of them) take ``ecckd_sw_fluxes_clear_allsky_f32``.  Returns the error message
+        ('' = success)."""
         nlay, ncol = tlay.shape
         nband = self.get_nband()
+        f32, mixed = _call_precision("sw_fluxes_clear_allsky", (
+            ("plev", plev), ("tlay", tlay), ("mu0", mu0), ("toa_scale", toa_scale), ("sfc_alb_dir", sfc_alb_dir),
+            ("sfc_alb_dif", sfc_alb_dif), ("particles.tau", particles.tau), ("particles.ssa", particles.ssa),
+            ("particles.g", particles.g), ("flux_up", fluxes.flux_up), ("flux_dn", fluxes.flux_dn),
+            ("flux_dn_dir", fluxes.flux_dn_dir), ("flux_up_clear", fluxes_clear.flux_up), ("flux_dn_clear", fluxes_clear.flux_dn),
+            ("flux_dn_dir_clear", fluxes_clear.flux_dn_dir)))
+        if mixed:
+            return mixed
+        P = lambda a, shape, what: _ptr(a, shape, what, f32)
         try:
             space = _space_of([plev, tlay, mu0, toa_scale, sfc_alb_dir, sfc_alb_dif, fluxes.flux_up, fluxes.flux_dn,
                                fluxes_clear.flux_up, fluxes_clear.flux_dn, particles.tau, particles.ssa, particles.g])
             mp = None if cloud_mask is None else _mask_ptr(cloud_mask, nlay, ncol, space)
-            n, names, ptrs, cs, ls, sc, keep = self._gas_args(gas_desc, ncol, nlay, space)
+            n, names, ptrs, cs, ls, sc, keep = self._gas_args(gas_desc, ncol, nlay, space, f32)
             nbp = int(particles.tau.shape[0])
             shp = (nbp, nlay, ncol)
-            part = (_ptr(particles.tau, shp, "particles.tau"), _ptr(particles.ssa, shp, "particles.ssa"),
-                    _ptr(particles.g, shp, "particles.g"))
-            out = tuple(_ptr(a, (nlay + 1, ncol), what) for a, what in (
+            part = (P(particles.tau, shp, "particles.tau"), P(particles.ssa, shp, "particles.ssa"),
+                    P(particles.g, shp, "particles.g"))
+            out = tuple(P(a, (nlay + 1, ncol), what) for a, what in (
                 (fluxes.flux_up, "flux_up"), (fluxes.flux_dn, "flux_dn"), (fluxes.flux_dn_dir, "flux_dn_dir"),
                 (fluxes_clear.flux_up, "flux_up_clear"), (fluxes_clear.flux_dn, "flux_dn_clear"),
                 (fluxes_clear.flux_dn_dir, "flux_dn_dir_clear")))
@@ -1625,10 +1712,10 @@ class GasOpticsEcckd:
             return str(e.args[0])
         except (TypeError, ValueError) as e:
             return str(e)
-        rc = lib().ecckd_sw_fluxes_clear_allsky(
-            self._need(), ncol, nlay, _ptr(plev, (nlay + 1, ncol), "plev"), _ptr(tlay, (nlay, ncol), "tlay"), n, names, ptrs,
-            cs, ls, sc, int(bool(top_at_1)), _ptr(mu0, (ncol,), "mu0"), _ptr(toa_scale, (ncol,), "toa_scale"),
-            _ptr(sfc_alb_dir, (ncol, nband), "sfc_alb_dir"), _ptr(sfc_alb_dif, (ncol, nband), "sfc_alb_dif"), nbp, *part,
+        rc = (lib().ecckd_sw_fluxes_clear_allsky_f32 if f32 else lib().ecckd_sw_fluxes_clear_allsky)(
+            self._need(), ncol, nlay, P(plev, (nlay + 1, ncol), "plev"), P(tlay, (nlay, ncol), "tlay"), n, names, ptrs,
+            cs, ls, sc, int(bool(top_at_1)), P(mu0, (ncol,), "mu0"), P(toa_scale, (ncol,), "toa_scale"),
+            P(sfc_alb_dir, (ncol, nband), "sfc_alb_dir"), P(sfc_alb_dif, (ncol, nband), "sfc_alb_dif"), nbp, *part,
             int(bool(delta_scale)), mp, *out, space, _stream(space))
         return last_error() if rc else ""
 
@@ -1658,30 +1745,45 @@ class GasOpticsEcckd:
         (an ``OpticalProps2str`` on the model's bands, ``alloc_2str_bands``) added to the gas optics inside the solver;
         ``delta_scale``: the library delta-scales a copy of them (f = g*g) first, ``particles`` is never written.
         float64, fast arithmetic mode.  ``cloud_mask`` ``(nlay, ncol)`` (``sample_cloud_mask``;
-        ``ecckd_sw_fluxes_allsky_mcica``): a g-point whose bit is clear sees no particles in that layer."""
+        ``ecckd_sw_fluxes_allsky_mcica``): a g-point whose bit is clear sees no particles in that layer.  float32 arrays
+        (all of them) take ``ecckd_sw_fluxes_allsky_f32`` / ``_mcica_f32``: the same route in single precision, to rounding
+        what ``gas_optics`` + ``delta_scale`` + ``increment`` + ``rte_sw`` give on float32 arrays."""
         nlay, ncol = tlay.shape
         nband = self.get_nband()
         mp = ()
+        f32, mixed = _call_precision("sw_fluxes_allsky", (
+            ("plev", plev), ("tlay", tlay), ("mu0", mu0), ("toa_scale", toa_scale), ("sfc_alb_dir", sfc_alb_dir),
+            ("sfc_alb_dif", sfc_alb_dif), ("particles.tau", particles.tau), ("particles.ssa", particles.ssa),
+            ("particles.g", particles.g), ("flux_up", fluxes.flux_up), ("flux_dn", fluxes.flux_dn),
+            ("flux_dn_dir", fluxes.flux_dn_dir)))
+        if mixed:
+            return mixed
+        P = lambda a, shape, what: _ptr(a, shape, what, f32)
         try:
             space = _space_of([plev, tlay, mu0, toa_scale, sfc_alb_dir, sfc_alb_dif, fluxes.flux_up, fluxes.flux_dn,
                                particles.tau, particles.ssa, particles.g])
             if cloud_mask is not None:
                 mp = (_mask_ptr(cloud_mask, nlay, ncol, space),)
-            n, names, ptrs, cs, ls, sc, keep = self._gas_args(gas_desc, ncol, nlay, space)
+            n, names, ptrs, cs, ls, sc, keep = self._gas_args(gas_desc, ncol, nlay, space, f32)
             nbp = int(particles.tau.shape[0])
             shp = (nbp, nlay, ncol)
-            part = (_ptr(particles.tau, shp, "particles.tau"), _ptr(particles.ssa, shp, "particles.ssa"),
-                    _ptr(particles.g, shp, "particles.g"))
+            part = (P(particles.tau, shp, "particles.tau"), P(particles.ssa, shp, "particles.ssa"),
+                    P(particles.g, shp, "particles.g"))
         except KeyError as e:
             return str(e.args[0])
         except (TypeError, ValueError) as e:
             return str(e)
-        rc = (lib().ecckd_sw_fluxes_allsky if cloud_mask is None else lib().ecckd_sw_fluxes_allsky_mcica)(
-            self._need(), ncol, nlay, _ptr(plev, (nlay + 1, ncol), "plev"), _ptr(tlay, (nlay, ncol), "tlay"), n, names, ptrs,
-            cs, ls, sc, int(bool(top_at_1)), _ptr(mu0, (ncol,), "mu0"), _ptr(toa_scale, (ncol,), "toa_scale"),
-            _ptr(sfc_alb_dir, (ncol, nband), "sfc_alb_dir"), _ptr(sfc_alb_dif, (ncol, nband), "sfc_alb_dif"), nbp, *part,
-            int(bool(delta_scale)), *mp, _ptr(fluxes.flux_up, (nlay + 1, ncol), "flux_up"),
-            _ptr(fluxes.flux_dn, (nlay + 1, ncol), "flux_dn"), _ptr(fluxes.flux_dn_dir, (nlay + 1, ncol), "flux_dn_dir"),
+        L = lib()
+        if f32:
+            fn = L.ecckd_sw_fluxes_allsky_f32 if cloud_mask is None else L.ecckd_sw_fluxes_allsky_mcica_f32
+        else:
+            fn = L.ecckd_sw_fluxes_allsky if cloud_mask is None else L.ecckd_sw_fluxes_allsky_mcica
+        rc = fn(
+            self._need(), ncol, nlay, P(plev, (nlay + 1, ncol), "plev"), P(tlay, (nlay, ncol), "tlay"), n, names, ptrs,
+            cs, ls, sc, int(bool(top_at_1)), P(mu0, (ncol,), "mu0"), P(toa_scale, (ncol,), "toa_scale"),
+            P(sfc_alb_dir, (ncol, nband), "sfc_alb_dir"), P(sfc_alb_dif, (ncol, nband), "sfc_alb_dif"), nbp, *part,
+            int(bool(delta_scale)), *mp, P(fluxes.flux_up, (nlay + 1, ncol), "flux_up"),
+            P(fluxes.flux_dn, (nlay + 1, ncol), "flux_dn"), P(fluxes.flux_dn_dir, (nlay + 1, ncol), "flux_dn_dir"),
             space, _stream(space))
         return last_error() if rc else ""
 
@@ -1718,6 +1820,8 @@ class GasOpticsEcckd:
         as well) -- bit for bit what that call gives on the gathered columns -- and scattered back; every other column of the
         requested outputs is 0 at every level.  float64, fast arithmetic mode; numpy or device tensors; with device tensors
         and a list made beforehand the call is asynchronous and can be captured.  Returns the error message ('' = success)."""
+        if any(_is_f32(a) for a in (plev, tlay, mu0, fluxes.flux_up)):
+            return "sw_fluxes_daylit: implemented for float64 arrays"
         nlay, ncol = tlay.shape
         nband = self.get_nband()
         clear = fluxes_clear if fluxes_clear is not None else FluxesBroadband()

@@ -604,6 +604,16 @@ class Stage {
     if (stream_scratch(device, stream, bytes, &p, lease)) err = 1;
     return static_cast<double *>(p);
   }
+  // ... with `extra` bytes behind it for a use the call can do without (a tail split): *got_extra tells whether they are
+  // there -- always with host arrays; with the stream's block under the rules of stream_scratch_optional
+  double *work(size_t bytes, size_t extra, bool *got_extra) {
+    *got_extra = extra > 0;
+    if (host_any) return static_cast<double *>(room(bytes + extra));
+    if (extra)
+      if (void *p = stream_scratch_optional(device, stream, bytes + extra, lease)) return static_cast<double *>(p);
+    *got_extra = false;
+    return work(bytes);
+  }
 
   template <class F> int open(F &&declare) {
     if (!host_any) { declare(); return err; }
@@ -2179,7 +2189,83 @@ static int lw_jac_aliased(const double *jac, const double *flux_up, const double
   return 0;
 }
 
-static int lw_fluxes_impl(const ecckd_model_t *m, int ncol, int nlay, const double *plev, const double *tlay, const double *tsfc,
+// The work block of the single-precision fused longwave calls (ecckd_lw_fluxes_f32_scratch_bytes), in this order: tau,
+// lay_source, lev_source_inc, lev_source_dec (`cells` bytes each), sfc_source (`sfc`), the ring of the overflow solver
+// (`ring`: beyond 96 layers, else nothing); every part a multiple of 256 bytes.  The partial sums of the tail split follow
+// when the block has room for them.
+struct LwWorkF32 {
+  size_t cells, sfc, ring;
+  LwWorkF32(const ecckd_model *m, int ncol, int nlay) {
+    const Counts n(ncol, nlay, m->ng, m->nband);
+    cells = align256(n.lay_g * sizeof(float));
+    sfc = align256(n.col_g * sizeof(float));
+    ring = align256(ecckd::rte_lw_scratch_bytes(ncol, nlay, m->ng));
+  }
+  size_t bytes() const { return 4 * cells + sfc + ring; }
+};
+
+// ecckd_lw_fluxes_f32 and its all-sky forms behind the refusal lists: the single-precision gas optics writes tau and the
+// Planck sources (two separate level arrays) into the work block, the single-precision register-resident solver follows on
+// them at every layer count -- launch_rte_lw (clear sky), launch_rte_lw_allsky_f32 (`pt`: the particles added where the
+// solver consumes tau), or one after the other on the same arrays (`clr`).  What ecckd_gas_optics_lw_f32 [+
+// ecckd_increment(_masked)_f32] + ecckd_rte_lw(_inc_flux)_f32 compute, bit for bit.
+static int lw_fluxes_f32_run(const ecckd_model *m, int ncol, int nlay, const double *plev, const double *tlay, const double *tsfc,
+                             const double *tlev, const GasDesc &gd, int top_at_1, int n_gauss_angles, const double *sfc_emis,
+                             const double *inc_flux, double *flux_up, double *flux_dn, int memspace, void *stream,
+                             const LwParticles *pt, const ClearFluxes *clr) {
+  const Counts n(ncol, nlay, m->ng, m->nband);
+  ecckd::RteLwArgs a{};
+  if (fill_band_map(m->ng, m->nband, m->band2gpt.data(), a.gpt2band)) return 1;
+  a.ncol = ncol; a.nlay = nlay; a.ng = m->ng; a.top_at_1 = top_at_1 ? 1 : 0; a.nband = m->nband;
+  a.f32 = 1;
+  fill_lw_options(a, n_gauss_angles, true);
+  const LwWorkF32 w(m, ncol, nlay);
+  long tail_first = -1;
+  size_t tail = 0;   // tail tiles one g-pair per wave (rte_lw_tail_plan); optional, same bits
+  if (!w.ring && g_opt.lw_tail_split.load()) tail = ecckd::rte_lw_tail_plan(a, simd_slots(m->device), &tail_first);
+  Stage st(const_cast<ecckd_model *>(m), memspace, stream, true);
+  const double *d_plev = nullptr, *d_tlay = nullptr, *d_tsfc = nullptr, *d_tlev = nullptr;
+  double *d_up = nullptr, *d_dn = nullptr, *d_work = nullptr;
+  GasDesc d_gd{};
+  LwParticles d_pt{};
+  ClearFluxes d_clr{};
+  bool got_tail = false;
+  if (st.open([&] {
+        d_plev = st.in(plev, n.lev); d_tlay = st.in(tlay, n.lay); d_tsfc = st.in(tsfc, n.col); d_tlev = st.in(tlev, n.lev);
+        a.sfc_emis = st.in(sfc_emis, n.col_b); a.inc_flux = st.in(inc_flux, n.col_g);
+        d_gd = st.gases(gd, ncol, nlay);
+        if (pt) d_pt = LwParticles{st.in(pt->tau, n.lay_b), st.in(pt->ssa, n.lay_b), st.in(pt->mask, n.lay)};
+        if (clr) d_clr = ClearFluxes{st.out(clr->up, n.lev), st.out(clr->dn, n.lev), nullptr};
+        d_up = st.out(flux_up, n.lev); d_dn = st.out(flux_dn, n.lev);
+        d_work = st.work(w.bytes(), tail, &got_tail);
+      }))
+    return 1;
+  char *const base = reinterpret_cast<char *>(d_work);
+  auto at = [&](size_t off) { return reinterpret_cast<double *>(base + off); };
+  double *tau = at(0), *lay = at(w.cells), *inc = at(2 * w.cells), *dec = at(3 * w.cells), *sfc = at(4 * w.cells);
+  const hipStream_t s = st.stream;
+  if (gas_optics_lw_dev(m, true, ncol, nlay, d_plev, d_tlay, d_gd, tau, PlanckSide{d_tlev, d_tsfc, lay, inc, dec, sfc}, s)) return 1;
+  a.tau = tau; a.lay_source = lay; a.lev_source_inc = inc; a.lev_source_dec = dec; a.sfc_source = sfc;
+  if (w.ring) a.scratch = at(4 * w.cells + w.sfc);
+  if (tail && got_tail) { a.partials = at(w.bytes()); a.tail_first = tail_first; }
+  if (clr) {
+    a.flux_up = d_clr.up; a.flux_dn = d_clr.dn;
+    ProfScope prof("rte_lw", s);
+    HIPCHK(ecckd::launch_rte_lw(a, s));
+  }
+  a.flux_up = d_up; a.flux_dn = d_dn;
+  if (pt) {
+    a.part_tau = d_pt.tau; a.part_ssa = d_pt.ssa; a.part_1scl = d_pt.ssa ? 0 : 1; a.part_mask = d_pt.mask;
+    ProfScope prof("rte_lw_allsky_f32", s);
+    HIPCHK(ecckd::launch_rte_lw_allsky_f32(a, s));
+  } else {
+    ProfScope prof("rte_lw", s);
+    HIPCHK(ecckd::launch_rte_lw(a, s));
+  }
+  return st.close();
+}
+
+static int lw_fluxes_impl(bool f32, const ecckd_model_t *m, int ncol, int nlay, const double *plev, const double *tlay, const double *tsfc,
                           const double *tlev, int ngas, const char *gas_names, const double *const *vmr,
                           const long long *vmr_col_stride, const long long *vmr_lay_stride, const double *vmr_scalar, int top_at_1,
                           int n_gauss_angles, const double *sfc_emis, const double *inc_flux, double *flux_up, double *flux_dn,
@@ -2199,6 +2285,11 @@ static int lw_fluxes_impl(const ecckd_model_t *m, int ncol, int nlay, const doub
   if (ncol == 0) return 0;
   const GasDesc gd{ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar};
   if (memspace != ECCKD_DEVICE && memspace != ECCKD_HOST) return fail("ecckd: bad memspace");
+  if (f32) {   // (the _f32 entry points: no Jacobian form)
+    if (jx) return fail("ecckd: internal: the single-precision fused longwave calls have no Jacobian form");
+    return lw_fluxes_f32_run(m, ncol, nlay, plev, tlay, tsfc, tlev, gd, top_at_1, n_gauss_angles, sfc_emis, inc_flux, flux_up, flux_dn,
+                             memspace, stream, pt, clr);
+  }
   const Counts n(ncol, nlay, m->ng, m->nband);
   // the Jacobian inside the 60-layer flux kernel ("lw_jac_inline" = 1), or from the stand-alone kernel behind the flux pass
   const bool jac_in = jac && fused_lw_kernels_apply(m, nlay) && g_opt.lw_jac_inline.load() == 1;
@@ -2244,14 +2335,14 @@ int ecckd_lw_fluxes(const ecckd_model_t *m, int ncol, int nlay, const double *pl
                     const long long *vmr_col_stride, const long long *vmr_lay_stride, const double *vmr_scalar, int top_at_1,
                     int n_gauss_angles, const double *sfc_emis, const double *inc_flux, double *flux_up, double *flux_dn,
                     int memspace, void *stream) {
-  return lw_fluxes_impl(m, ncol, nlay, plev, tlay, tsfc, tlev, ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar,
+  return lw_fluxes_impl(false, m, ncol, nlay, plev, tlay, tsfc, tlev, ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar,
                         top_at_1, n_gauss_angles, sfc_emis, inc_flux, flux_up, flux_dn, memspace, stream);
 }
 
 // The one refusal list of the fused all-sky longwave calls.  cloud_mask (ecckd_lw_fluxes_allsky_mcica), or null: with a
 // mask, a model of more than 64 g-points is refused first.  Refusals that need no device come first: a host-only model
 // answers them too.
-static int lw_fluxes_allsky_impl(const ecckd_model_t *m, int ncol, int nlay, const double *plev, const double *tlay,
+static int lw_fluxes_allsky_impl(bool f32, const ecckd_model_t *m, int ncol, int nlay, const double *plev, const double *tlay,
                                  const double *tsfc, const double *tlev, int ngas, const char *gas_names,
                                  const double *const *vmr, const long long *vmr_col_stride, const long long *vmr_lay_stride,
                                  const double *vmr_scalar, int top_at_1, int n_gauss_angles, const double *sfc_emis,
@@ -2275,7 +2366,7 @@ static int lw_fluxes_allsky_impl(const ecckd_model_t *m, int ncol, int nlay, con
   }
   if (lw_jac_aliased(jx ? jx->jac : nullptr, flux_up, flux_dn, clr)) return 1;   // (before any device is asked for, as the list above)
   const LwParticles pt{tau_p, ssa_p, cloud_mask};
-  return lw_fluxes_impl(m, ncol, nlay, plev, tlay, tsfc, tlev, ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar,
+  return lw_fluxes_impl(f32, m, ncol, nlay, plev, tlay, tsfc, tlev, ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar,
                         top_at_1, n_gauss_angles, sfc_emis, inc_flux, flux_up, flux_dn, memspace, stream, &pt, clr, jx);
 }
 
@@ -2287,7 +2378,7 @@ int ecckd_lw_fluxes_clear_allsky(const ecckd_model_t *m, int ncol, int nlay, con
                                  const unsigned long long *cloud_mask, double *flux_up, double *flux_dn, double *flux_up_clear,
                                  double *flux_dn_clear, int memspace, void *stream) {
   const ClearFluxes clr{flux_up_clear, flux_dn_clear, nullptr};
-  return lw_fluxes_allsky_impl(m, ncol, nlay, plev, tlay, tsfc, tlev, ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride,
+  return lw_fluxes_allsky_impl(false, m, ncol, nlay, plev, tlay, tsfc, tlev, ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride,
                                vmr_scalar, top_at_1, n_gauss_angles, sfc_emis, inc_flux, nband_p, tau_p, ssa_p, cloud_mask, flux_up,
                                flux_dn, memspace, stream, &clr);
 }
@@ -2298,7 +2389,7 @@ int ecckd_lw_fluxes_allsky(const ecckd_model_t *m, int ncol, int nlay, const dou
                            int top_at_1, int n_gauss_angles, const double *sfc_emis, const double *inc_flux, int nband_p,
                            const double *tau_p, const double *ssa_p, double *flux_up, double *flux_dn, int memspace,
                            void *stream) {
-  return lw_fluxes_allsky_impl(m, ncol, nlay, plev, tlay, tsfc, tlev, ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride,
+  return lw_fluxes_allsky_impl(false, m, ncol, nlay, plev, tlay, tsfc, tlev, ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride,
                                vmr_scalar, top_at_1, n_gauss_angles, sfc_emis, inc_flux, nband_p, tau_p, ssa_p, nullptr, flux_up,
                                flux_dn, memspace, stream);
 }
@@ -2310,7 +2401,7 @@ int ecckd_lw_fluxes_allsky_mcica(const ecckd_model_t *m, int ncol, int nlay, con
                                  const double *inc_flux, int nband_p, const double *tau_p, const double *ssa_p,
                                  const unsigned long long *cloud_mask, double *flux_up, double *flux_dn, int memspace,
                                  void *stream) {
-  return lw_fluxes_allsky_impl(m, ncol, nlay, plev, tlay, tsfc, tlev, ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride,
+  return lw_fluxes_allsky_impl(false, m, ncol, nlay, plev, tlay, tsfc, tlev, ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride,
                                vmr_scalar, top_at_1, n_gauss_angles, sfc_emis, inc_flux, nband_p, tau_p, ssa_p, cloud_mask, flux_up,
                                flux_dn, memspace, stream);
 }
@@ -2739,12 +2830,12 @@ int ecckd_lw_fluxes_jac(const ecckd_model_t *m, int ncol, int nlay, const double
   const bool clear_out = flux_up_clear || flux_dn_clear;
   if (!tau_p) {   // the clear sky of ecckd_lw_fluxes
     const LwJac jx{flux_up_jac, nband_p != 0 || ssa_p || cloud_mask || clear_out};
-    return lw_fluxes_impl(m, ncol, nlay, plev, tlay, tsfc, tlev, ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar,
+    return lw_fluxes_impl(false, m, ncol, nlay, plev, tlay, tsfc, tlev, ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar,
                           top_at_1, n_gauss_angles, sfc_emis, inc_flux, flux_up, flux_dn, memspace, stream, nullptr, nullptr, &jx);
   }
   const LwJac jx{flux_up_jac, false};
   const ClearFluxes clr{flux_up_clear, flux_dn_clear, nullptr};
-  return lw_fluxes_allsky_impl(m, ncol, nlay, plev, tlay, tsfc, tlev, ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride,
+  return lw_fluxes_allsky_impl(false, m, ncol, nlay, plev, tlay, tsfc, tlev, ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride,
                                vmr_scalar, top_at_1, n_gauss_angles, sfc_emis, inc_flux, nband_p, tau_p, ssa_p, cloud_mask, flux_up,
                                flux_dn, memspace, stream, clear_out ? &clr : nullptr, &jx);
 }
@@ -2810,7 +2901,7 @@ static int sw_fluxes_impl(bool f32, const ecckd_model_t *m, int ncol, int nlay, 
     double *q_tau = reinterpret_cast<double *>(room + solver), *q_ssa = reinterpret_cast<double *>(room + solver + plane),
            *q_g = reinterpret_cast<double *>(room + solver + 2 * plane);
     ProfScope prof("delta_scale", st.stream);
-    HIPCHK(ecckd::launch_delta_scale(n.lay_b, d_pt.tau, d_pt.ssa, d_pt.g, nullptr, q_tau, q_ssa, q_g, 0, st.stream));
+    HIPCHK(ecckd::launch_delta_scale(n.lay_b, d_pt.tau, d_pt.ssa, d_pt.g, nullptr, q_tau, q_ssa, q_g, f32 ? 1 : 0, st.stream));
     d_pt.tau = q_tau; d_pt.ssa = q_ssa; d_pt.g = q_g;
   }
   // gas_optics_ext's tau (:449-456) without ssa / g: the total optical depth, gases + Rayleigh
@@ -2838,8 +2929,9 @@ int ecckd_sw_fluxes(const ecckd_model_t *m, int ncol, int nlay, const double *pl
                         top_at_1, mu0, toa_scale, sfc_alb_dir, sfc_alb_dif, flux_up, flux_dn, flux_dir, memspace, stream);
 }
 
-// The one refusal list of the fused all-sky shortwave calls; cloud_mask as in lw_fluxes_allsky_impl.
-static int sw_fluxes_allsky_impl(const ecckd_model_t *m, int ncol, int nlay, const double *plev, const double *tlay, int ngas,
+// The one refusal list of the fused all-sky shortwave calls; cloud_mask as in lw_fluxes_allsky_impl.  f32: the _f32 entry
+// points (float data behind the double pointers, dp()); the messages are those of the fp64 namesakes.
+static int sw_fluxes_allsky_impl(bool f32, const ecckd_model_t *m, int ncol, int nlay, const double *plev, const double *tlay, int ngas,
                                  const char *gas_names, const double *const *vmr, const long long *vmr_col_stride,
                                  const long long *vmr_lay_stride, const double *vmr_scalar, int top_at_1, const double *mu0,
                                  const double *toa_scale, const double *sfc_alb_dir, const double *sfc_alb_dif, int nband_p,
@@ -2864,7 +2956,7 @@ static int sw_fluxes_allsky_impl(const ecckd_model_t *m, int ncol, int nlay, con
           return fail("ecckd_sw_fluxes_clear_allsky: a clear-sky output must not be an all-sky output (the two sets of fluxes need arrays of their own)");
   }
   const SwParticles pt{tau_p, ssa_p, g_p, delta_scale, cloud_mask};
-  return sw_fluxes_impl(false, m, ncol, nlay, plev, tlay, ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar,
+  return sw_fluxes_impl(f32, m, ncol, nlay, plev, tlay, ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar,
                         top_at_1, mu0, toa_scale, sfc_alb_dir, sfc_alb_dif, flux_up, flux_dn, flux_dir, memspace, stream, &pt, clr);
 }
 
@@ -2877,7 +2969,7 @@ int ecckd_sw_fluxes_clear_allsky(const ecckd_model_t *m, int ncol, int nlay, con
                                  double *flux_up_clear, double *flux_dn_clear, double *flux_dir_clear, int memspace,
                                  void *stream) {
   const ClearFluxes clr{flux_up_clear, flux_dn_clear, flux_dir_clear};
-  return sw_fluxes_allsky_impl(m, ncol, nlay, plev, tlay, ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar,
+  return sw_fluxes_allsky_impl(false, m, ncol, nlay, plev, tlay, ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar,
                                top_at_1, mu0, toa_scale, sfc_alb_dir, sfc_alb_dif, nband_p, tau_p, ssa_p, g_p, delta_scale,
                                cloud_mask, flux_up, flux_dn, flux_dir, memspace, stream, &clr);
 }
@@ -2888,7 +2980,7 @@ int ecckd_sw_fluxes_allsky(const ecckd_model_t *m, int ncol, int nlay, const dou
                            const double *toa_scale, const double *sfc_alb_dir, const double *sfc_alb_dif, int nband_p,
                            const double *tau_p, const double *ssa_p, const double *g_p, int delta_scale, double *flux_up,
                            double *flux_dn, double *flux_dir, int memspace, void *stream) {
-  return sw_fluxes_allsky_impl(m, ncol, nlay, plev, tlay, ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar,
+  return sw_fluxes_allsky_impl(false, m, ncol, nlay, plev, tlay, ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar,
                                top_at_1, mu0, toa_scale, sfc_alb_dir, sfc_alb_dif, nband_p, tau_p, ssa_p, g_p, delta_scale, nullptr,
                                flux_up, flux_dn, flux_dir, memspace, stream);
 }
@@ -2900,7 +2992,7 @@ int ecckd_sw_fluxes_allsky_mcica(const ecckd_model_t *m, int ncol, int nlay, con
                                  const double *tau_p, const double *ssa_p, const double *g_p, int delta_scale,
                                  const unsigned long long *cloud_mask, double *flux_up, double *flux_dn, double *flux_dir,
                                  int memspace, void *stream) {
-  return sw_fluxes_allsky_impl(m, ncol, nlay, plev, tlay, ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar,
+  return sw_fluxes_allsky_impl(false, m, ncol, nlay, plev, tlay, ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar,
                                top_at_1, mu0, toa_scale, sfc_alb_dir, sfc_alb_dif, nband_p, tau_p, ssa_p, g_p, delta_scale,
                                cloud_mask, flux_up, flux_dn, flux_dir, memspace, stream);
 }
@@ -3574,6 +3666,95 @@ int ecckd_sw_fluxes_f32(const ecckd_model_t *m, int ncol, int nlay, const float 
                         vmr_col_stride, vmr_lay_stride, vmr_scalar, top_at_1, dp(mu0), dp(toa_scale), dp(sfc_alb_dir),
                         dp(sfc_alb_dif), dp(flux_up), dp(flux_dn), dp(flux_dir), memspace, stream);
 }
+
+// ---- single-precision fused fluxes: longwave, all-sky, McICA, both skies (the *_impl functions with f32 = true) ----
+
+#define ECCKD_GAS_F32_PARAMS \
+  int ngas, const char *gas_names, const float *const *vmr, const long long *vmr_col_stride, const long long *vmr_lay_stride, \
+      const double *vmr_scalar
+#define ECCKD_GAS_F32_ARGS \
+  ngas, gas_names, reinterpret_cast<const double *const *>(vmr), vmr_col_stride, vmr_lay_stride, vmr_scalar
+
+size_t ecckd_lw_fluxes_f32_scratch_bytes(const ecckd_model_t *m, int ncol, int nlay) {
+  if (!m || ncol <= 0 || nlay <= 0) return 0;
+  return LwWorkF32(m, ncol, nlay).bytes();
+}
+
+size_t ecckd_sw_fluxes_allsky_f32_scratch_bytes(const ecckd_model_t *m, int ncol, int nlay, int delta_scale) {
+  if (!m || ncol <= 0 || nlay <= 0) return 0;
+  return SwWork(m, true, ncol, nlay, delta_scale != 0).bytes();
+}
+
+int ecckd_lw_fluxes_f32(const ecckd_model_t *m, int ncol, int nlay, const float *plev, const float *tlay, const float *tsfc,
+                        const float *tlev, ECCKD_GAS_F32_PARAMS, int top_at_1, int n_gauss_angles, const float *sfc_emis,
+                        const float *inc_flux, float *flux_up, float *flux_dn, int memspace, void *stream) {
+  return lw_fluxes_impl(true, m, ncol, nlay, dp(plev), dp(tlay), dp(tsfc), dp(tlev), ECCKD_GAS_F32_ARGS, top_at_1, n_gauss_angles,
+                        dp(sfc_emis), dp(inc_flux), dp(flux_up), dp(flux_dn), memspace, stream);
+}
+
+int ecckd_lw_fluxes_allsky_f32(const ecckd_model_t *m, int ncol, int nlay, const float *plev, const float *tlay, const float *tsfc,
+                               const float *tlev, ECCKD_GAS_F32_PARAMS, int top_at_1, int n_gauss_angles, const float *sfc_emis,
+                               const float *inc_flux, int nband_p, const float *tau_p, const float *ssa_p, float *flux_up,
+                               float *flux_dn, int memspace, void *stream) {
+  return lw_fluxes_allsky_impl(true, m, ncol, nlay, dp(plev), dp(tlay), dp(tsfc), dp(tlev), ECCKD_GAS_F32_ARGS, top_at_1,
+                               n_gauss_angles, dp(sfc_emis), dp(inc_flux), nband_p, dp(tau_p), dp(ssa_p), nullptr, dp(flux_up),
+                               dp(flux_dn), memspace, stream);
+}
+
+int ecckd_lw_fluxes_allsky_mcica_f32(const ecckd_model_t *m, int ncol, int nlay, const float *plev, const float *tlay,
+                                     const float *tsfc, const float *tlev, ECCKD_GAS_F32_PARAMS, int top_at_1, int n_gauss_angles,
+                                     const float *sfc_emis, const float *inc_flux, int nband_p, const float *tau_p,
+                                     const float *ssa_p, const unsigned long long *cloud_mask, float *flux_up, float *flux_dn,
+                                     int memspace, void *stream) {
+  return lw_fluxes_allsky_impl(true, m, ncol, nlay, dp(plev), dp(tlay), dp(tsfc), dp(tlev), ECCKD_GAS_F32_ARGS, top_at_1,
+                               n_gauss_angles, dp(sfc_emis), dp(inc_flux), nband_p, dp(tau_p), dp(ssa_p), cloud_mask, dp(flux_up),
+                               dp(flux_dn), memspace, stream);
+}
+
+int ecckd_lw_fluxes_clear_allsky_f32(const ecckd_model_t *m, int ncol, int nlay, const float *plev, const float *tlay,
+                                     const float *tsfc, const float *tlev, ECCKD_GAS_F32_PARAMS, int top_at_1, int n_gauss_angles,
+                                     const float *sfc_emis, const float *inc_flux, int nband_p, const float *tau_p,
+                                     const float *ssa_p, const unsigned long long *cloud_mask, float *flux_up, float *flux_dn,
+                                     float *flux_up_clear, float *flux_dn_clear, int memspace, void *stream) {
+  const ClearFluxes clr{dp(flux_up_clear), dp(flux_dn_clear), nullptr};
+  return lw_fluxes_allsky_impl(true, m, ncol, nlay, dp(plev), dp(tlay), dp(tsfc), dp(tlev), ECCKD_GAS_F32_ARGS, top_at_1,
+                               n_gauss_angles, dp(sfc_emis), dp(inc_flux), nband_p, dp(tau_p), dp(ssa_p), cloud_mask, dp(flux_up),
+                               dp(flux_dn), memspace, stream, &clr);
+}
+
+int ecckd_sw_fluxes_allsky_f32(const ecckd_model_t *m, int ncol, int nlay, const float *plev, const float *tlay,
+                               ECCKD_GAS_F32_PARAMS, int top_at_1, const float *mu0, const float *toa_scale,
+                               const float *sfc_alb_dir, const float *sfc_alb_dif, int nband_p, const float *tau_p,
+                               const float *ssa_p, const float *g_p, int delta_scale, float *flux_up, float *flux_dn,
+                               float *flux_dir, int memspace, void *stream) {
+  return sw_fluxes_allsky_impl(true, m, ncol, nlay, dp(plev), dp(tlay), ECCKD_GAS_F32_ARGS, top_at_1, dp(mu0), dp(toa_scale),
+                               dp(sfc_alb_dir), dp(sfc_alb_dif), nband_p, dp(tau_p), dp(ssa_p), dp(g_p), delta_scale, nullptr,
+                               dp(flux_up), dp(flux_dn), dp(flux_dir), memspace, stream);
+}
+
+int ecckd_sw_fluxes_allsky_mcica_f32(const ecckd_model_t *m, int ncol, int nlay, const float *plev, const float *tlay,
+                                     ECCKD_GAS_F32_PARAMS, int top_at_1, const float *mu0, const float *toa_scale,
+                                     const float *sfc_alb_dir, const float *sfc_alb_dif, int nband_p, const float *tau_p,
+                                     const float *ssa_p, const float *g_p, int delta_scale, const unsigned long long *cloud_mask,
+                                     float *flux_up, float *flux_dn, float *flux_dir, int memspace, void *stream) {
+  return sw_fluxes_allsky_impl(true, m, ncol, nlay, dp(plev), dp(tlay), ECCKD_GAS_F32_ARGS, top_at_1, dp(mu0), dp(toa_scale),
+                               dp(sfc_alb_dir), dp(sfc_alb_dif), nband_p, dp(tau_p), dp(ssa_p), dp(g_p), delta_scale, cloud_mask,
+                               dp(flux_up), dp(flux_dn), dp(flux_dir), memspace, stream);
+}
+
+int ecckd_sw_fluxes_clear_allsky_f32(const ecckd_model_t *m, int ncol, int nlay, const float *plev, const float *tlay,
+                                     ECCKD_GAS_F32_PARAMS, int top_at_1, const float *mu0, const float *toa_scale,
+                                     const float *sfc_alb_dir, const float *sfc_alb_dif, int nband_p, const float *tau_p,
+                                     const float *ssa_p, const float *g_p, int delta_scale, const unsigned long long *cloud_mask,
+                                     float *flux_up, float *flux_dn, float *flux_dir, float *flux_up_clear, float *flux_dn_clear,
+                                     float *flux_dir_clear, int memspace, void *stream) {
+  const ClearFluxes clr{dp(flux_up_clear), dp(flux_dn_clear), dp(flux_dir_clear)};
+  return sw_fluxes_allsky_impl(true, m, ncol, nlay, dp(plev), dp(tlay), ECCKD_GAS_F32_ARGS, top_at_1, dp(mu0), dp(toa_scale),
+                               dp(sfc_alb_dir), dp(sfc_alb_dif), nband_p, dp(tau_p), dp(ssa_p), dp(g_p), delta_scale, cloud_mask,
+                               dp(flux_up), dp(flux_dn), dp(flux_dir), memspace, stream, &clr);
+}
+#undef ECCKD_GAS_F32_PARAMS
+#undef ECCKD_GAS_F32_ARGS
 
 // ---- spectral (per-band) fluxes: ty_fluxes_byband of RTE-RRTMGP ----
 

@@ -389,6 +389,9 @@ hipError_t launch_toa_src(const double *solar, int ncol, int ng, double *toa_src
 // out(i) = sum_b planes(i, b): broadband from per-band fluxes
 hipError_t launch_sum_planes(const double *planes, int nplanes, size_t n, double *out, int f32, hipStream_t s);
 hipError_t launch_rte_lw(const RteLwArgs &a, hipStream_t s);
+// the single-precision register-resident solver with a.part_tau / part_ssa / part_mask added where it consumes tau
+// (rte_lw_allsky_f32_kernel; f32 = 1, two separate level arrays, any layer count; ring and tail split as launch_rte_lw)
+hipError_t launch_rte_lw_allsky_f32(const RteLwArgs &a, hipStream_t s);
 // layer-split form (kernels_rte_lw_split.hip): fp64, 60 layers
 bool rte_lw_split_applies(const RteLwArgs &a);
 bool rte_lw_planck_fits(int ng, int ntp);   // the Planck-recomputing form: does the model's table fit in LDS?

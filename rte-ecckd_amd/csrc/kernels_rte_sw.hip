@@ -312,6 +312,17 @@ __global__ void __launch_bounds__(64, ECCKD_SW_WAVES_PER_SIMD) rte_sw_mcica_kern
   rte_sw_body<double, CW, true, CLAMP, true, true, true>(a);
 }
 
+// the single-precision all-sky forms (ecckd_sw_fluxes_allsky_f32 / _mcica_f32), each under its own name: the body forms ssa
+// and g in `real`, with the floor 3 * tiny(1._sp) of ecckd_increment_f32 (op_eps<float>) and the single-precision k floor
+template <int CW, bool CLAMP>
+__global__ void __launch_bounds__(64, ECCKD_SW_WAVES_PER_SIMD) rte_sw_allsky_f32_kernel(const RteSwArgs a) {
+  rte_sw_body<float, CW, true, CLAMP, true, true>(a);
+}
+template <int CW, bool CLAMP>
+__global__ void __launch_bounds__(64, ECCKD_SW_WAVES_PER_SIMD) rte_sw_mcica_f32_kernel(const RteSwArgs a) {
+  rte_sw_body<float, CW, true, CLAMP, true, true, true>(a);
+}
+
 // Sums the per-group partial fluxes of the tail tiles in group order: the order in which a whole-tile wave adds the
 // same values to accumulators that start at +0, hence the same bits (see rte_lw_tail_reduce, kernels_rte_lw.hip).
 template <typename real>
@@ -419,10 +430,12 @@ RteSwKernel rte_sw_kernel_for(const RteSwArgs &a) {
 hipError_t launch_rte_sw(const RteSwArgs &a, hipStream_t s) {
   if (a.ncol <= 0) return hipSuccess;
   constexpr int CW = ECCKD_SW_CW;
-  // (the all-sky form exists in fp64 and the fast arithmetic mode only; ecckd_sw_fluxes_allsky refuses the rest with a message)
-  if (a.allsky && (a.f32 || a.exact_division || !a.derive)) return hipErrorInvalidValue;
+  // (the all-sky form exists in the fast arithmetic mode only; ecckd_sw_fluxes_allsky refuses the rest with a message)
+  if (a.allsky && (a.exact_division || !a.derive)) return hipErrorInvalidValue;
   if (a.allsky && a.part_mask && a.ng > 64) return hipErrorInvalidValue;
-  auto k = a.allsky && a.part_mask ? (a.dir_clamp ? rte_sw_mcica_kernel<CW, true> : rte_sw_mcica_kernel<CW, false>)
+  auto k = a.allsky && a.f32 ? (a.part_mask ? (a.dir_clamp ? rte_sw_mcica_f32_kernel<CW, true> : rte_sw_mcica_f32_kernel<CW, false>)
+                                            : (a.dir_clamp ? rte_sw_allsky_f32_kernel<CW, true> : rte_sw_allsky_f32_kernel<CW, false>))
+           : a.allsky && a.part_mask ? (a.dir_clamp ? rte_sw_mcica_kernel<CW, true> : rte_sw_mcica_kernel<CW, false>)
            : a.allsky ? (a.dir_clamp ? rte_sw_allsky_kernel<CW, true> : rte_sw_allsky_kernel<CW, false>)
            : a.f32 ? (a.derive ? rte_sw_kernel_for<float, true>(a) : rte_sw_kernel_for<float, false>(a))
                  : (a.derive ? rte_sw_kernel_for<double, true>(a) : rte_sw_kernel_for<double, false>(a));

@@ -534,6 +534,17 @@ __global__ void __launch_bounds__(64 * kSysWaves) rte_sw_sys_mcica_kernel(const 
   rte_sw_sys_body<double, true, CLAMP, true, FULL, true, true>(a);
 }
 
+// the single-precision all-sky forms (ecckd_sw_fluxes_allsky_f32 / _mcica_f32), each under its own name: ssa and g are
+// formed in `real` with the floor 3 * tiny(1._sp) of ecckd_increment_f32 (op_eps<float>)
+template <bool CLAMP, bool FULL>
+__global__ void __launch_bounds__(64 * kSysWaves) rte_sw_sys_allsky_f32_kernel(const RteSwArgs a) {
+  rte_sw_sys_body<float, true, CLAMP, true, FULL, true>(a);
+}
+template <bool CLAMP, bool FULL>
+__global__ void __launch_bounds__(64 * kSysWaves) rte_sw_sys_mcica_f32_kernel(const RteSwArgs a) {
+  rte_sw_sys_body<float, true, CLAMP, true, FULL, true, true>(a);
+}
+
 // LDS of a block: control words and band map (384 B), hand-off slots, accumulators (up, dn and, if asked for, dir), and
 // behind them the parking areas: as many of the lower waves as fit keep the coefficients of the next g-point there.
 size_t sys_lds_base(int nlay, int f32, bool with_dir) {
@@ -545,12 +556,15 @@ template <typename real, bool DERIVE, bool FULL>
 hipError_t launch_sys2(RteSwArgs a, long blocks, hipStream_t s) {
   auto k = a.dir_clamp ? (a.exact_division ? rte_sw_sys_kernel<real, false, true, DERIVE, FULL> : rte_sw_sys_kernel<real, true, true, DERIVE, FULL>)
                        : (a.exact_division ? rte_sw_sys_kernel<real, false, false, DERIVE, FULL> : rte_sw_sys_kernel<real, true, false, DERIVE, FULL>);
-  if (a.allsky) {   // (fp64, fast arithmetic mode, DERIVE: ecckd_sw_fluxes_allsky refuses the rest with a message)
-    if (a.f32 || a.exact_division || !a.derive) return hipErrorInvalidValue;
-    k = a.dir_clamp ? rte_sw_sys_allsky_kernel<true, FULL> : rte_sw_sys_allsky_kernel<false, FULL>;
-    if (a.part_mask) {
-      if (a.ng > 64) return hipErrorInvalidValue;
-      k = a.dir_clamp ? rte_sw_sys_mcica_kernel<true, FULL> : rte_sw_sys_mcica_kernel<false, FULL>;
+  if (a.allsky) {   // (fast arithmetic mode, DERIVE: ecckd_sw_fluxes_allsky refuses the rest with a message)
+    if (a.exact_division || !a.derive) return hipErrorInvalidValue;
+    if (a.part_mask && a.ng > 64) return hipErrorInvalidValue;
+    if constexpr (sizeof(real) == 4) {
+      k = a.dir_clamp ? rte_sw_sys_allsky_f32_kernel<true, FULL> : rte_sw_sys_allsky_f32_kernel<false, FULL>;
+      if (a.part_mask) k = a.dir_clamp ? rte_sw_sys_mcica_f32_kernel<true, FULL> : rte_sw_sys_mcica_f32_kernel<false, FULL>;
+    } else {
+      k = a.dir_clamp ? rte_sw_sys_allsky_kernel<true, FULL> : rte_sw_sys_allsky_kernel<false, FULL>;
+      if (a.part_mask) k = a.dir_clamp ? rte_sw_sys_mcica_kernel<true, FULL> : rte_sw_sys_mcica_kernel<false, FULL>;
     }
   }
   const size_t base = (sys_lds_base(a.nlay, a.f32, a.flux_dir != nullptr) + 15) & ~(size_t)15;
