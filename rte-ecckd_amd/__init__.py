@@ -144,6 +144,39 @@ _lib = None
 _dp = C.POINTER(C.c_double)
 
 
+def _fused_prototypes():
+    """``argtypes`` of the fused flux entry points (a ``_f32`` namesake shares its list), from the pieces every one of them is
+    made of: each argument is named, so that the lengths follow from the declarations in include/ecckd_hip.h."""
+    ints, ptrs = (lambda *names: [C.c_int] * len(names)), (lambda *names: [C.c_void_p] * len(names))
+    gas = ints("ngas") + [C.c_char_p] + ptrs("vmr", "col_stride", "lay_stride", "scalar")
+    tail = ints("space") + ptrs("stream")
+    lw = ptrs("model") + ints("ncol", "nlay") + ptrs("plev", "tlay", "tsfc", "tlev") + gas
+    sw = ptrs("model") + ints("ncol", "nlay") + ptrs("plev", "tlay") + gas
+    sw_daylit = ptrs("model") + ints("ncol", "nlay", "nday") + ptrs("day_index", "plev", "tlay") + gas
+    lw_bound = ints("top_at_1", "n_gauss_angles") + ptrs("sfc_emis", "inc_flux")
+    lw_bound_2stream = ints("top_at_1") + ptrs("sfc_emis", "inc_flux")   # (no quadrature)
+    sw_bound = ints("top_at_1") + ptrs("mu0", "toa_scale", "sfc_alb_dir", "sfc_alb_dif")
+    lw_part = ints("nband_p") + ptrs("tau_p", "ssa_p")
+    lw_part_g = ints("nband_p") + ptrs("tau_p", "ssa_p", "g_p")
+    sw_part = ints("nband_p") + ptrs("tau_p", "ssa_p", "g_p") + ints("delta_scale")
+    mask = ptrs("cloud_mask")
+    lw_out, lw_clear, jac = ptrs("flux_up", "flux_dn"), ptrs("flux_up_clear", "flux_dn_clear"), ptrs("flux_up_jac")
+    sw_out, sw_clear = ptrs("flux_up", "flux_dn", "flux_dn_dir"), ptrs("flux_up_clear", "flux_dn_clear", "flux_dn_dir_clear")
+    return {"ecckd_lw_fluxes": lw + lw_bound + lw_out + tail,
+            "ecckd_lw_fluxes_allsky": lw + lw_bound + lw_part + lw_out + tail,
+            "ecckd_lw_fluxes_allsky_mcica": lw + lw_bound + lw_part + mask + lw_out + tail,
+            "ecckd_lw_fluxes_clear_allsky": lw + lw_bound + lw_part + mask + lw_out + lw_clear + tail,
+            "ecckd_lw_fluxes_jac": lw + lw_bound + lw_part + mask + lw_out + lw_clear + jac + tail,
+            "ecckd_lw_fluxes_allsky_2stream": lw + lw_bound_2stream + lw_part_g + mask + lw_out + tail,
+            "ecckd_lw_fluxes_allsky_rescaled": lw + lw_bound + lw_part_g + mask + lw_out + tail,
+            "ecckd_lw_fluxes_rescaled_jac": lw + lw_bound + lw_part_g + mask + lw_out + lw_clear + jac + tail,
+            "ecckd_sw_fluxes": sw + sw_bound + sw_out + tail,
+            "ecckd_sw_fluxes_allsky": sw + sw_bound + sw_part + sw_out + tail,
+            "ecckd_sw_fluxes_allsky_mcica": sw + sw_bound + sw_part + mask + sw_out + tail,
+            "ecckd_sw_fluxes_clear_allsky": sw + sw_bound + sw_part + mask + sw_out + sw_clear + tail,
+            "ecckd_sw_fluxes_daylit": sw_daylit + sw_bound + sw_part + mask + sw_out + sw_clear + tail}
+
+
 def lib():
     """Load librte_ecckd_hip.so (fails loudly if it has not been built)."""
     global _lib
@@ -185,68 +218,37 @@ def lib():
     L.ecckd_rte_lw_tail_scratch_bytes.argtypes = [C.c_int] * 6
     L.ecckd_set_stream_scratch.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]
     L.ecckd_release_scratch.argtypes = [C.c_int]
-    if hasattr(L, "ecckd_lw_fluxes_allsky"):   # (ECCKD_LIB may name an older build: tools/bench_lw_allsky.py --parent-lib)
-        L.ecckd_lw_fluxes_allsky.argtypes = ([C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_char_p] +
-                                             [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int] +
-                                             [C.c_void_p] * 4 + [C.c_int, C.c_void_p])
+    # the fused flux calls, from the named pieces of _fused_prototypes.  (hasattr: ECCKD_LIB may name an older build, which lacks
+    # the later ones -- the --parent-lib mode of the tools/bench_*.py scripts; so for the other guards below)
+    for name, argtypes in _fused_prototypes().items():
+        for f in (name, name + "_f32"):
+            if hasattr(L, f):
+                getattr(L, f).argtypes = argtypes
     if hasattr(L, "ecckd_cloud_mask_sample"):   # (the McICA calls: 64-bit seed / col0 and the mask pointer need prototypes)
         L.ecckd_cloud_mask_sample.argtypes = [C.c_int] * 5 + [C.c_void_p, C.c_void_p, C.c_ulonglong, C.c_longlong, C.c_void_p,
                                                               C.c_int, C.c_void_p]
         for f in ("ecckd_increment_masked", "ecckd_increment_masked_f32"):
             getattr(L, f).argtypes = [C.c_int] * 4 + [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.c_void_p]
-        L.ecckd_lw_fluxes_allsky_mcica.argtypes = ([C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_char_p] +
-                                                   [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int] +
-                                                   [C.c_void_p] * 5 + [C.c_int, C.c_void_p])
-        L.ecckd_sw_fluxes_allsky_mcica.argtypes = ([C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 2 + [C.c_int, C.c_char_p] +
-                                                   [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 3 +
-                                                   [C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_void_p])
-    if hasattr(L, "ecckd_lw_fluxes_clear_allsky"):   # (an older build lacks them: tools/bench_both_skies.py --parent-lib)
-        L.ecckd_lw_fluxes_clear_allsky.argtypes = ([C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_char_p] +
-                                                   [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int] +
-                                                   [C.c_void_p] * 7 + [C.c_int, C.c_void_p])
-        L.ecckd_sw_fluxes_clear_allsky.argtypes = ([C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 2 + [C.c_int, C.c_char_p] +
-                                                   [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 3 +
-                                                   [C.c_int] + [C.c_void_p] * 7 + [C.c_int, C.c_void_p])
-    if hasattr(L, "ecckd_lw_fluxes_allsky_f32"):   # (an older build lacks them: tools/bench_allsky_f32.py --parent-lib)
-        lw_head = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_char_p] + [C.c_void_p] * 4
-        sw_head = ([C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 2 + [C.c_int, C.c_char_p] + [C.c_void_p] * 4 + [C.c_int] +
-                   [C.c_void_p] * 4)
-        tail = [C.c_int, C.c_void_p]
-        L.ecckd_lw_fluxes_f32.argtypes = lw_head + [C.c_int, C.c_int] + [C.c_void_p] * 4 + tail
-        for f, nptr in (("ecckd_lw_fluxes_allsky_f32", 4), ("ecckd_lw_fluxes_allsky_mcica_f32", 5),
-                        ("ecckd_lw_fluxes_clear_allsky_f32", 7)):
-            getattr(L, f).argtypes = lw_head + [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * nptr + tail
-        for f, nptr in (("ecckd_sw_fluxes_allsky_f32", 3), ("ecckd_sw_fluxes_allsky_mcica_f32", 4),
-                        ("ecckd_sw_fluxes_clear_allsky_f32", 7)):
-            getattr(L, f).argtypes = sw_head + [C.c_int] + [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * nptr + tail
+    if hasattr(L, "ecckd_lw_fluxes_f32_scratch_bytes"):   # (an older build lacks them: tools/bench_allsky_f32.py --parent-lib)
         L.ecckd_lw_fluxes_f32_scratch_bytes.restype = C.c_size_t
         L.ecckd_lw_fluxes_f32_scratch_bytes.argtypes = [C.c_void_p, C.c_int, C.c_int]
         L.ecckd_sw_fluxes_allsky_f32_scratch_bytes.restype = C.c_size_t
         L.ecckd_sw_fluxes_allsky_f32_scratch_bytes.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
-    if hasattr(L, "ecckd_sw_fluxes_daylit"):   # (an older build lacks them: tools/bench_sw_daylit.py times the parent's library)
+    if hasattr(L, "ecckd_daylit_columns"):   # (an older build lacks them: tools/bench_sw_daylit.py times the parent's library)
         for f in ("ecckd_daylit_columns", "ecckd_daylit_columns_f32"):
             getattr(L, f).argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_void_p, C.POINTER(C.c_int), C.c_int, C.c_void_p]
         L.ecckd_gather_columns.argtypes = [C.c_int] * 6 + [C.c_void_p] * 3 + [C.c_int, C.c_void_p]
         L.ecckd_scatter_columns.argtypes = [C.c_int] * 6 + [C.c_void_p] * 3 + [C.c_double, C.c_int, C.c_void_p]
         L.ecckd_sw_fluxes_daylit_scratch_bytes.restype = C.c_size_t
         L.ecckd_sw_fluxes_daylit_scratch_bytes.argtypes = [C.c_void_p] + [C.c_int] * 8
-        L.ecckd_sw_fluxes_daylit.argtypes = ([C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p] + [C.c_void_p] * 2 +
-                                             [C.c_int, C.c_char_p] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 4 + [C.c_int] +
-                                             [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 7 + [C.c_int, C.c_void_p])
-    if hasattr(L, "ecckd_lw_fluxes_jac"):   # (an older build lacks them: tools/bench_lw_jac.py --parent-lib)
+    if hasattr(L, "ecckd_planck_sfc_source_jac"):   # (an older build lacks them: tools/bench_lw_jac.py --parent-lib)
         L.ecckd_planck_sfc_source_jac.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.ecckd_rte_lw_jac.argtypes = [C.c_int] * 6 + [C.c_void_p] * 6 + [C.c_int] + [C.c_void_p] * 6 + [C.c_int, C.c_void_p]
-        L.ecckd_lw_fluxes_jac.argtypes = ([C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_char_p] +
-                                          [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int] +
-                                          [C.c_void_p] * 8 + [C.c_int, C.c_void_p])
     if hasattr(L, "ecckd_rte_lw_2stream"):   # (an older build lacks them: tools/bench_lw_2stream.py --parent-lib)
         L.ecckd_rte_lw_2stream.argtypes = [C.c_int] * 5 + [C.c_void_p] * 7 + [C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.c_void_p]
         L.ecckd_lw_solver_2stream_gpt.argtypes = [C.c_int] * 5 + [C.c_void_p] * 11 + [C.c_int, C.c_void_p]
         L.ecckd_rte_lw_2stream_scratch_bytes.restype = C.c_size_t
         L.ecckd_rte_lw_2stream_scratch_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
-        L.ecckd_lw_fluxes_allsky_2stream.argtypes = ([C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_char_p] +
-                                                     [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_void_p, C.c_int] +
-                                                     [C.c_void_p] * 6 + [C.c_int, C.c_void_p])
     if hasattr(L, "ecckd_rte_lw_rescaled"):   # (an older build lacks them: tools/bench_lw_rescaled.py --parent-lib)
         L.ecckd_rte_lw_rescaled.argtypes = [C.c_int] * 6 + [C.c_void_p] * 7 + [C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.c_void_p]
         L.ecckd_lw_solver_1rescl_gpt.argtypes = [C.c_int] * 6 + [C.c_void_p] * 13 + [C.c_int, C.c_void_p]
@@ -254,15 +256,9 @@ def lib():
         L.ecckd_rte_lw_rescaled_scratch_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
         L.ecckd_lw_fluxes_allsky_rescaled_scratch_bytes.restype = C.c_size_t
         L.ecckd_lw_fluxes_allsky_rescaled_scratch_bytes.argtypes = [C.c_void_p, C.c_int, C.c_int]
-        L.ecckd_lw_fluxes_allsky_rescaled.argtypes = ([C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_char_p] +
-                                                      [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int] +
-                                                      [C.c_void_p] * 6 + [C.c_int, C.c_void_p])
-    if hasattr(L, "ecckd_lw_fluxes_rescaled_jac"):   # (an older build lacks them: tools/bench_lw_rescaled_jac.py --parent-lib)
+    if hasattr(L, "ecckd_rte_lw_rescaled_jac"):   # (an older build lacks them: tools/bench_lw_rescaled_jac.py --parent-lib)
         L.ecckd_rte_lw_rescaled_jac.argtypes = ([C.c_int] * 6 + [C.c_void_p] * 8 + [C.c_int] + [C.c_void_p] * 6 +
                                                 [C.c_int, C.c_void_p])
-        L.ecckd_lw_fluxes_rescaled_jac.argtypes = ([C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_char_p] +
-                                                   [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int] +
-                                                   [C.c_void_p] * 9 + [C.c_int, C.c_void_p])
         L.ecckd_lw_fluxes_rescaled_jac_scratch_bytes.restype = C.c_size_t
         L.ecckd_lw_fluxes_rescaled_jac_scratch_bytes.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
     if hasattr(L, "ecckd_cloud_optics"):   # (ECCKD_LIB may name an older build, which lacks them)
@@ -390,18 +386,24 @@ def release_scratch(device=0):
 # ------------------------------------------------------------------------------------------
 # array plumbing: numpy (host) or torch.cuda tensors (device)
 # ------------------------------------------------------------------------------------------
+_F32, _F64 = np.dtype(np.float32), np.dtype(np.float64)   # (dtype objects: comparing against the scalar types converts them every time)
+
+
 def _is_torch(a):
     return type(a).__module__.startswith("torch")
 
 
 def _space_of(arrays):
-    dev = [a for a in arrays if a is not None and _is_torch(a) and a.is_cuda]
-    if not dev:
-        return HOST
+    dev = host = False
     for a in arrays:
-        if a is not None and not (_is_torch(a) and a.is_cuda):
-            raise TypeError("mixing host and device arrays in one call")
-    return DEVICE
+        if a is not None:
+            if _is_torch(a) and a.is_cuda:
+                dev = True
+            else:
+                host = True
+    if dev and host:
+        raise TypeError("mixing host and device arrays in one call")
+    return DEVICE if dev else HOST
 
 
 def _is_f32(a):
@@ -411,7 +413,7 @@ def _is_f32(a):
     if _is_torch(a):
         import torch
         return a.dtype == torch.float32
-    return isinstance(a, np.ndarray) and a.dtype == np.float32
+    return isinstance(a, np.ndarray) and a.dtype == _F32
 
 
 def _call_precision(who, named):
@@ -422,7 +424,7 @@ def _call_precision(who, named):
     for name, a in named:
         if _is_f32(a):
             p = True
-        elif a is not None and str(getattr(a, "dtype", "")).endswith("float64"):
+        elif a is not None and ((isinstance(a, np.ndarray) and a.dtype == _F64) or str(getattr(a, "dtype", "")).endswith("float64")):
             p = False
         else:
             continue
@@ -451,7 +453,7 @@ def _ptr(a, shape=None, what="array", f32=False):
         if shape is not None and tuple(a.shape) != tuple(shape):
             raise ValueError("%s: shape %s, expected %s" % (what, tuple(a.shape), tuple(shape)))
         return C.c_void_p(a.data_ptr())
-    if not isinstance(a, np.ndarray) or a.dtype != (np.float32 if f32 else np.float64) or not a.flags.c_contiguous:
+    if not isinstance(a, np.ndarray) or a.dtype != (_F32 if f32 else _F64) or not a.flags.c_contiguous:
         raise TypeError(what + ": need a C-contiguous " + want + " ndarray")
     if shape is not None and tuple(a.shape) != tuple(shape):
         raise ValueError("%s: shape %s, expected %s" % (what, a.shape, tuple(shape)))
@@ -1129,6 +1131,54 @@ class FluxesByband(FluxesBroadband):
 
 
 # ------------------------------------------------------------------------------------------
+# argument groups of the fused calls (GasOpticsEcckd._fused).  A group is a tuple of slots in the order of the C argument
+# list: an int goes through as it is, ``(name, array, shape)`` becomes the array's data pointer, checked against the shape
+# ------------------------------------------------------------------------------------------
+_LEV, _LAY, _COL, _BAND, _GPT, _PART, _SPEC = range(7)   # (shape: an index into the tuple that _fused makes)
+
+
+def _lw_groups(plev, tlay, tsfc, tlev, top_at_1, n_gauss_angles, sfc_emis, inc_flux):
+    """``head`` and ``boundary`` of a longwave call (``n_gauss_angles`` None: the entry point has no quadrature)."""
+    angles = () if n_gauss_angles is None else (int(n_gauss_angles),)
+    return {"head": (("plev", plev, _LEV), ("tlay", tlay, _LAY), ("tsfc", tsfc, _COL), ("tlev", tlev, _LEV)),
+            "boundary": (int(bool(top_at_1)),) + angles + (("sfc_emis", sfc_emis, _BAND), ("inc_flux", inc_flux, _GPT))}
+
+
+def _sw_groups(plev, tlay, top_at_1, mu0, toa_scale, sfc_alb_dir, sfc_alb_dif):
+    """``head`` and ``boundary`` of a shortwave call."""
+    return {"head": (("plev", plev, _LEV), ("tlay", tlay, _LAY)),
+            "boundary": (int(bool(top_at_1)), ("mu0", mu0, _COL), ("toa_scale", toa_scale, _COL),
+                         ("sfc_alb_dir", sfc_alb_dir, _BAND), ("sfc_alb_dif", sfc_alb_dif, _BAND))}
+
+
+def _particle_slots(tau, ssa, *g, tau_required=False):
+    """``particles``: the band count and the planes of particulate properties on bands (``g`` where the call takes it)."""
+    nbp = int(tau.shape[0]) if tau_required or tau is not None else 0
+    return (nbp, ("particles.tau", tau, _PART), ("particles.ssa", ssa, _PART)) + tuple(("particles.g", a, _PART) for a in g)
+
+
+def _flux_slots(fluxes, suffix="", dn_dir=False):
+    """``outputs``: the arrays of a fluxes object, ``flux_dn_dir`` where the call takes it."""
+    out = (("flux_up" + suffix, fluxes.flux_up, _LEV), ("flux_dn" + suffix, fluxes.flux_dn, _LEV))
+    return out + ((("flux_dn_dir" + suffix, fluxes.flux_dn_dir, _LEV),) if dn_dir else ())
+
+
+_NO_FLUXES = FluxesBroadband()   # (null pointers, where a call may go without its clear-sky fluxes)
+
+
+def _jac_slot(flux_up_jac):
+    return (("flux_up_jac", flux_up_jac, _LEV),)
+
+
+def _named(*groups):
+    """The ``(name, array)`` pairs of groups, for ``_call_precision``."""
+    return [s[:2] for g in groups for s in g if type(s) is tuple]
+
+
+_FUSED_CHECKS = ("gas", "head", "boundary", "particles", "mask", "outputs")
+
+
+# ------------------------------------------------------------------------------------------
 # ty_gas_optics_ecckd
 # ------------------------------------------------------------------------------------------
 class GasOpticsEcckd:
@@ -1355,19 +1405,52 @@ class GasOpticsEcckd:
         rc = lib().ecckd_planck_sfc_source_jac(self._need(), ncol, *args, space, _stream(space))
         return last_error() if rc else ""
 
-    def gas_optics_tau(self, plev, tlay, gas_desc, optical_props):
-        """``ecckd_gas_optics_lw_tau``: gas_optical_depth alone (tau only), device tensors."""
-        nlay, ncol = tlay.shape
+    def _fused(self, fn, f32, returns, gas_desc, head, boundary=(), particles=(), mask=(), outputs=(), columns=None):
+        """One call of an entry point that takes ``(model, ncol, nlay[, nday, day_index], head, gases, boundary, particles, mask,
+        outputs, space, stream)``.  ``head``, ``boundary``, ``particles`` and ``outputs`` are tuples of slots (``_lw_groups`` and
+        its neighbours make them), ``mask`` is ``(cloud_mask,)`` where the entry point takes one, ``columns`` the list of daylit
+        columns or a function that gives it.  The memory space comes from the arrays that are marshalled.  ``returns`` names the
+        groups that are checked first, in its order, and whose ``TypeError`` / ``ValueError`` is answered with its message; the
+        other groups follow in the order of ``_FUSED_CHECKS`` and raise.  A gas that was never set is answered with a message
+        everywhere.  Returns the error message ('' = success)."""
+        nlay, ncol = head[1][1].shape   # (tlay)
         ng = self.get_ngpt()
+        shapes = ((nlay + 1, ncol), (nlay, ncol), (ncol,), (ncol, self.get_nband()), (ng, ncol),
+                  (particles[0] if particles else 0, nlay, ncol), (ng, nlay, ncol))
+        slots = {"head": head, "boundary": boundary, "particles": particles, "outputs": outputs}
+        args = {}
+        group = returns[0] if returns else _FUSED_CHECKS[0]
         try:
-            space = _space_of([plev, tlay, optical_props.tau])
-            n, names, ptrs, cs, ls, sc, keep = self._gas_args(gas_desc, ncol, nlay, space)
+            # (without the mask: _mask_ptr holds it against the space of the others, with a message of its own)
+            space = _space_of([s[1] for s in head + boundary + particles + outputs if type(s) is tuple] +
+                              [None if callable(columns) else columns])
+            for group in returns + _FUSED_CHECKS:
+                if group in args:
+                    continue
+                if group == "gas":
+                    args[group] = self._gas_args(gas_desc, ncol, nlay, space, f32)[:6]
+                elif group == "mask":
+                    args[group] = [_mask_ptr(m, nlay, ncol, space) for m in mask]
+                elif group == "columns":
+                    index = columns() if callable(columns) else columns
+                    nday = int(index.shape[0])
+                    args[group] = (nday, _int32_ptr(index, (nday,), "day_index") if nday else None)
+                else:
+                    args[group] = [s if type(s) is int else _ptr(s[1], shapes[s[2]], s[0], f32) for s in slots[group]]
         except KeyError as e:
             return str(e.args[0])
-        rc = lib().ecckd_gas_optics_lw_tau(self._need(), ncol, nlay, _ptr(plev, (nlay + 1, ncol), "plev"),
-                                           _ptr(tlay, (nlay, ncol), "tlay"), n, names, ptrs, cs, ls, sc,
-                                           _ptr(optical_props.tau, (ng, nlay, ncol), "tau"), space, _stream(space))
+        except (TypeError, ValueError) as e:
+            if group not in returns:
+                raise
+            return str(e)
+        rc = fn(self._need(), ncol, nlay, *args.get("columns", ()), *args["head"], *args["gas"], *args["boundary"],
+                *args["particles"], *args["mask"], *args["outputs"], space, _stream(space))
         return last_error() if rc else ""
+
+    def gas_optics_tau(self, plev, tlay, gas_desc, optical_props):
+        """``ecckd_gas_optics_lw_tau``: gas_optical_depth alone (tau only), device tensors."""
+        return self._fused(lib().ecckd_gas_optics_lw_tau, False, (), gas_desc, (("plev", plev, _LEV), ("tlay", tlay, _LAY)),
+                           outputs=(("tau", optical_props.tau, _SPEC),))
 
     def rte_lw_fused(self, optical_props, top_at_1, tlay, tlev, tsfc, sfc_emis, fluxes, n_gauss_angles=1, inc_flux=None):
         """``ecckd_rte_lw_fused``: rte_lw that recomputes the Planck sources from the temperatures (device tensors)."""
@@ -1385,33 +1468,12 @@ class GasOpticsEcckd:
                        n_gauss_angles, inc_flux, cloud_mask, flux_up_jac):
         """``ecckd_lw_fluxes_jac`` behind ``lw_fluxes`` / ``lw_fluxes_allsky`` / ``lw_fluxes_clear_allsky`` with
         ``flux_up_jac``: shape and dtype errors are answered here and never reach the library."""
-        nlay, ncol = tlay.shape
-        ng = self.get_ngpt()
         ptau = None if particles is None else particles.tau
         ssa = None if particles is None else getattr(particles, "ssa", None)
-        clear = [] if fluxes_clear is None else [fluxes_clear.flux_up, fluxes_clear.flux_dn]
-        try:
-            space = _space_of([plev, tlay, tsfc, tlev, sfc_emis, inc_flux, fluxes.flux_up, fluxes.flux_dn, flux_up_jac, ptau, ssa] +
-                              clear)
-            n, names, ptrs, cs, ls, sc, keep = self._gas_args(gas_desc, ncol, nlay, space)
-            nbp = 0 if ptau is None else int(ptau.shape[0])
-            shp = (nbp, nlay, ncol)
-            part = (_ptr(ptau, shp, "particles.tau"), _ptr(ssa, shp, "particles.ssa"),
-                    None if cloud_mask is None else _mask_ptr(cloud_mask, nlay, ncol, space))
-            lev = (nlay + 1, ncol)
-            out = (_ptr(fluxes.flux_up, lev, "flux_up"), _ptr(fluxes.flux_dn, lev, "flux_dn"),
-                   None if fluxes_clear is None else _ptr(fluxes_clear.flux_up, lev, "flux_up_clear"),
-                   None if fluxes_clear is None else _ptr(fluxes_clear.flux_dn, lev, "flux_dn_clear"),
-                   _ptr(flux_up_jac, lev, "flux_up_jac"))
-            inp = (_ptr(plev, lev, "plev"), _ptr(tlay, (nlay, ncol), "tlay"), _ptr(tsfc, (ncol,), "tsfc"), _ptr(tlev, lev, "tlev"))
-            emis = (_ptr(sfc_emis, (ncol, self.get_nband()), "sfc_emis"), _ptr(inc_flux, (ng, ncol), "inc_flux"))
-        except KeyError as e:
-            return str(e.args[0])
-        except (TypeError, ValueError) as e:
-            return str(e)
-        rc = lib().ecckd_lw_fluxes_jac(self._need(), ncol, nlay, *inp, n, names, ptrs, cs, ls, sc, int(bool(top_at_1)),
-                                       int(n_gauss_angles), *emis, nbp, *part, *out, space, _stream(space))
-        return last_error() if rc else ""
+        return self._fused(lib().ecckd_lw_fluxes_jac, False, ("gas", "particles", "mask", "outputs", "head", "boundary"), gas_desc,
+                           particles=_particle_slots(ptau, ssa), mask=(cloud_mask,),
+                           outputs=_flux_slots(fluxes) + _flux_slots(fluxes_clear or _NO_FLUXES, "_clear") + _jac_slot(flux_up_jac),
+                           **_lw_groups(plev, tlay, tsfc, tlev, top_at_1, n_gauss_angles, sfc_emis, inc_flux))
 
     def lw_fluxes(self, plev, tlay, tsfc, tlev, gas_desc, top_at_1, sfc_emis, fluxes, n_gauss_angles=1, inc_flux=None,
                   flux_up_jac=None):
@@ -1421,9 +1483,8 @@ class GasOpticsEcckd:
         surface temperature, W m-2 K-1; the fluxes are the same bits with and without it.  float32 arrays (all of them)
         take ``ecckd_lw_fluxes_f32``: the fluxes of ``gas_optics`` + ``rte_lw`` on float32 arrays, bit for bit; no
         ``flux_up_jac``."""
-        f32, mixed = _call_precision("lw_fluxes", (("plev", plev), ("tlay", tlay), ("tsfc", tsfc), ("tlev", tlev), ("sfc_emis", sfc_emis),
-                                                   ("inc_flux", inc_flux), ("flux_up", fluxes.flux_up), ("flux_dn", fluxes.flux_dn),
-                                                   ("flux_up_jac", flux_up_jac)))
+        lw, out = _lw_groups(plev, tlay, tsfc, tlev, top_at_1, n_gauss_angles, sfc_emis, inc_flux), _flux_slots(fluxes)
+        f32, mixed = _call_precision("lw_fluxes", _named(lw["head"], lw["boundary"], out, _jac_slot(flux_up_jac)))
         if mixed:
             return mixed
         if flux_up_jac is not None:
@@ -1431,20 +1492,8 @@ class GasOpticsEcckd:
                 return _f64_only("lw_fluxes", "flux_up_jac")
             return self._lw_fluxes_jac(plev, tlay, tsfc, tlev, gas_desc, top_at_1, sfc_emis, None, fluxes, None, n_gauss_angles,
                                        inc_flux, None, flux_up_jac)
-        nlay, ncol = tlay.shape
-        ng = self.get_ngpt()
-        try:
-            space = _space_of([plev, tlay, tsfc, tlev, sfc_emis, inc_flux, fluxes.flux_up, fluxes.flux_dn])
-            n, names, ptrs, cs, ls, sc, keep = self._gas_args(gas_desc, ncol, nlay, space, f32)
-        except KeyError as e:
-            return str(e.args[0])
-        P = lambda a, shape, what: _ptr(a, shape, what, f32)
-        rc = (lib().ecckd_lw_fluxes_f32 if f32 else lib().ecckd_lw_fluxes)(
-            self._need(), ncol, nlay, P(plev, (nlay + 1, ncol), "plev"), P(tlay, (nlay, ncol), "tlay"), P(tsfc, (ncol,), "tsfc"),
-            P(tlev, (nlay + 1, ncol), "tlev"), n, names, ptrs, cs, ls, sc, int(bool(top_at_1)), int(n_gauss_angles),
-            P(sfc_emis, (ncol, self.get_nband()), "sfc_emis"), P(inc_flux, (ng, ncol), "inc_flux"),
-            P(fluxes.flux_up, (nlay + 1, ncol), "flux_up"), P(fluxes.flux_dn, (nlay + 1, ncol), "flux_dn"), space, _stream(space))
-        return last_error() if rc else ""
+        # (returns nothing: a wrong array raises here, where the all-sky calls answer with a message)
+        return self._fused(lib().ecckd_lw_fluxes_f32 if f32 else lib().ecckd_lw_fluxes, f32, (), gas_desc, outputs=out, **lw)
 
     def _lw_fluxes_allsky_2stream(self, plev, tlay, tsfc, tlev, gas_desc, top_at_1, sfc_emis, particles, fluxes, n_gauss_angles,
                                   inc_flux, cloud_mask, flux_up_jac):
@@ -1456,27 +1505,10 @@ class GasOpticsEcckd:
             return who + "flux_up_jac is not implemented"
         if n_gauss_angles != 1:
             return who + "the two-stream solver has no quadrature (n_gauss_angles must be 1)"
-        nlay, ncol = tlay.shape
-        ng = self.get_ngpt()
-        try:
-            space = _space_of([plev, tlay, tsfc, tlev, sfc_emis, inc_flux, fluxes.flux_up, fluxes.flux_dn, particles.tau,
-                               particles.ssa, particles.g])
-            n, names, ptrs, cs, ls, sc, keep = self._gas_args(gas_desc, ncol, nlay, space)
-            nbp = 0 if particles.tau is None else int(particles.tau.shape[0])
-            shp = (nbp, nlay, ncol)
-            part = (_ptr(particles.tau, shp, "particles.tau"), _ptr(particles.ssa, shp, "particles.ssa"),
-                    _ptr(particles.g, shp, "particles.g"), _mask_ptr(cloud_mask, nlay, ncol, space))
-            lev = (nlay + 1, ncol)
-            inp = (_ptr(plev, lev, "plev"), _ptr(tlay, (nlay, ncol), "tlay"), _ptr(tsfc, (ncol,), "tsfc"), _ptr(tlev, lev, "tlev"))
-            emis = (_ptr(sfc_emis, (ncol, self.get_nband()), "sfc_emis"), _ptr(inc_flux, (ng, ncol), "inc_flux"))
-            out = (_ptr(fluxes.flux_up, lev, "flux_up"), _ptr(fluxes.flux_dn, lev, "flux_dn"))
-        except KeyError as e:
-            return str(e.args[0])
-        except (TypeError, ValueError) as e:
-            return str(e)
-        rc = lib().ecckd_lw_fluxes_allsky_2stream(self._need(), ncol, nlay, *inp, n, names, ptrs, cs, ls, sc, int(bool(top_at_1)),
-                                                  *emis, nbp, *part, *out, space, _stream(space))
-        return last_error() if rc else ""
+        return self._fused(lib().ecckd_lw_fluxes_allsky_2stream, False, ("gas", "particles", "mask", "head", "boundary", "outputs"),
+                           gas_desc, particles=_particle_slots(particles.tau, particles.ssa, particles.g),
+                           mask=(cloud_mask,), outputs=_flux_slots(fluxes),
+                           **_lw_groups(plev, tlay, tsfc, tlev, top_at_1, None, sfc_emis, inc_flux))
 
     def _lw_fluxes_allsky_rescaled(self, plev, tlay, tsfc, tlev, gas_desc, top_at_1, sfc_emis, particles, fluxes, n_gauss_angles,
                                    inc_flux, cloud_mask, use_2stream, flux_up_jac):
@@ -1492,27 +1524,10 @@ class GasOpticsEcckd:
             return who + "per-band fluxes are not implemented (broadband fluxes only)"
         if any(_is_f32(a) for a in (tlay, particles.tau)):
             return who + "implemented for float64 arrays"
-        nlay, ncol = tlay.shape
-        ng = self.get_ngpt()
-        try:
-            space = _space_of([plev, tlay, tsfc, tlev, sfc_emis, inc_flux, fluxes.flux_up, fluxes.flux_dn, particles.tau,
-                               particles.ssa, particles.g])
-            n, names, ptrs, cs, ls, sc, keep = self._gas_args(gas_desc, ncol, nlay, space)
-            nbp = 0 if particles.tau is None else int(particles.tau.shape[0])
-            shp = (nbp, nlay, ncol)
-            part = (_ptr(particles.tau, shp, "particles.tau"), _ptr(particles.ssa, shp, "particles.ssa"),
-                    _ptr(particles.g, shp, "particles.g"), _mask_ptr(cloud_mask, nlay, ncol, space))
-            lev = (nlay + 1, ncol)
-            inp = (_ptr(plev, lev, "plev"), _ptr(tlay, (nlay, ncol), "tlay"), _ptr(tsfc, (ncol,), "tsfc"), _ptr(tlev, lev, "tlev"))
-            emis = (_ptr(sfc_emis, (ncol, self.get_nband()), "sfc_emis"), _ptr(inc_flux, (ng, ncol), "inc_flux"))
-            out = (_ptr(fluxes.flux_up, lev, "flux_up"), _ptr(fluxes.flux_dn, lev, "flux_dn"))
-        except KeyError as e:
-            return str(e.args[0])
-        except (TypeError, ValueError) as e:
-            return str(e)
-        rc = lib().ecckd_lw_fluxes_allsky_rescaled(self._need(), ncol, nlay, *inp, n, names, ptrs, cs, ls, sc, int(bool(top_at_1)),
-                                                   int(n_gauss_angles), *emis, nbp, *part, *out, space, _stream(space))
-        return last_error() if rc else ""
+        return self._fused(lib().ecckd_lw_fluxes_allsky_rescaled, False, ("gas", "particles", "mask", "head", "boundary", "outputs"),
+                           gas_desc, particles=_particle_slots(particles.tau, particles.ssa, particles.g),
+                           mask=(cloud_mask,), outputs=_flux_slots(fluxes),
+                           **_lw_groups(plev, tlay, tsfc, tlev, top_at_1, n_gauss_angles, sfc_emis, inc_flux))
 
     def lw_fluxes_allsky(self, plev, tlay, tsfc, tlev, gas_desc, top_at_1, sfc_emis, particles, fluxes, n_gauss_angles=1,
                          inc_flux=None, cloud_mask=None, rescaled=False, use_2stream=False, flux_up_jac=None):
@@ -1534,10 +1549,9 @@ class GasOpticsEcckd:
         ``gas_optics`` + ``increment(particles, band2gpt[, cloud_mask])`` + ``rte_lw`` on float32 arrays, bit for bit;
         ``flux_up_jac``, ``rescaled`` and ``use_2stream`` are float64 only.  Returns the error message ('' = success)."""
         who = "lw_fluxes_allsky"
-        f32, mixed = _call_precision(who, (
-            ("plev", plev), ("tlay", tlay), ("tsfc", tsfc), ("tlev", tlev), ("sfc_emis", sfc_emis), ("inc_flux", inc_flux),
-            ("particles.tau", particles.tau), ("particles.ssa", getattr(particles, "ssa", None)), ("flux_up", fluxes.flux_up),
-            ("flux_dn", fluxes.flux_dn), ("flux_up_jac", flux_up_jac)))
+        lw = _lw_groups(plev, tlay, tsfc, tlev, top_at_1, n_gauss_angles, sfc_emis, inc_flux)
+        part, out = _particle_slots(particles.tau, getattr(particles, "ssa", None)), _flux_slots(fluxes)
+        f32, mixed = _call_precision(who, _named(lw["head"], lw["boundary"], part, out, _jac_slot(flux_up_jac)))
         if f32 or mixed:   # (float64 calls with these keywords keep the messages of their own routes)
             for on, what in ((rescaled, "rescaled=True"), (use_2stream, "use_2stream=True"), (flux_up_jac is not None, "flux_up_jac")):
                 if on:
@@ -1553,33 +1567,14 @@ class GasOpticsEcckd:
         if flux_up_jac is not None:
             return self._lw_fluxes_jac(plev, tlay, tsfc, tlev, gas_desc, top_at_1, sfc_emis, particles, fluxes, None,
                                        n_gauss_angles, inc_flux, cloud_mask, flux_up_jac)
-        nlay, ncol = tlay.shape
-        ng = self.get_ngpt()
-        ssa = getattr(particles, "ssa", None)
-        try:
-            space = _space_of([plev, tlay, tsfc, tlev, sfc_emis, inc_flux, fluxes.flux_up, fluxes.flux_dn, particles.tau, ssa])
-            n, names, ptrs, cs, ls, sc, keep = self._gas_args(gas_desc, ncol, nlay, space, f32)
-            nbp = 0 if particles.tau is None else int(particles.tau.shape[0])
-            shp = (nbp, nlay, ncol)
-            part = (_ptr(particles.tau, shp, "particles.tau", f32), _ptr(ssa, shp, "particles.ssa", f32))
-            if cloud_mask is not None:
-                part = part + (_mask_ptr(cloud_mask, nlay, ncol, space),)
-        except KeyError as e:
-            return str(e.args[0])
-        except (TypeError, ValueError) as e:
-            return str(e)
         L = lib()
         if f32:
             fn = L.ecckd_lw_fluxes_allsky_f32 if cloud_mask is None else L.ecckd_lw_fluxes_allsky_mcica_f32
         else:
             fn = L.ecckd_lw_fluxes_allsky if cloud_mask is None else L.ecckd_lw_fluxes_allsky_mcica
-        P = lambda a, shape, what: _ptr(a, shape, what, f32)
-        rc = fn(self._need(), ncol, nlay, P(plev, (nlay + 1, ncol), "plev"), P(tlay, (nlay, ncol), "tlay"),
-                P(tsfc, (ncol,), "tsfc"), P(tlev, (nlay + 1, ncol), "tlev"), n, names, ptrs, cs, ls, sc, int(bool(top_at_1)),
-                int(n_gauss_angles), P(sfc_emis, (ncol, self.get_nband()), "sfc_emis"), P(inc_flux, (ng, ncol), "inc_flux"),
-                nbp, *part, P(fluxes.flux_up, (nlay + 1, ncol), "flux_up"), P(fluxes.flux_dn, (nlay + 1, ncol), "flux_dn"),
-                space, _stream(space))
-        return last_error() if rc else ""
+        # (the inputs and the outputs are not in `returns`: a wrong one raises, a wrong particle plane or mask is a message)
+        return self._fused(fn, f32, ("gas", "particles", "mask"), gas_desc, particles=part,
+                           mask=() if cloud_mask is None else (cloud_mask,), outputs=out, **lw)
 
     def lw_fluxes_rescaled(self, plev, tlay, tsfc, tlev, gas_desc, top_at_1, sfc_emis, particles, fluxes, fluxes_clear=None,
                            flux_up_jac=None, n_gauss_angles=1, inc_flux=None, cloud_mask=None):
@@ -1596,31 +1591,11 @@ class GasOpticsEcckd:
             return who + "per-band fluxes are not implemented (broadband fluxes only)"
         if any(_is_f32(a) for a in (tlay, particles.tau)):
             return who + "implemented for float64 arrays"
-        nlay, ncol = tlay.shape
-        ng = self.get_ngpt()
-        clear = [] if fluxes_clear is None else [fluxes_clear.flux_up, fluxes_clear.flux_dn]
-        try:
-            space = _space_of([plev, tlay, tsfc, tlev, sfc_emis, inc_flux, fluxes.flux_up, fluxes.flux_dn, particles.tau,
-                               particles.ssa, particles.g, flux_up_jac] + clear)
-            n, names, ptrs, cs, ls, sc, keep = self._gas_args(gas_desc, ncol, nlay, space)
-            nbp = 0 if particles.tau is None else int(particles.tau.shape[0])
-            shp = (nbp, nlay, ncol)
-            part = (_ptr(particles.tau, shp, "particles.tau"), _ptr(particles.ssa, shp, "particles.ssa"),
-                    _ptr(particles.g, shp, "particles.g"), _mask_ptr(cloud_mask, nlay, ncol, space))
-            lev = (nlay + 1, ncol)
-            inp = (_ptr(plev, lev, "plev"), _ptr(tlay, (nlay, ncol), "tlay"), _ptr(tsfc, (ncol,), "tsfc"), _ptr(tlev, lev, "tlev"))
-            emis = (_ptr(sfc_emis, (ncol, self.get_nband()), "sfc_emis"), _ptr(inc_flux, (ng, ncol), "inc_flux"))
-            out = (_ptr(fluxes.flux_up, lev, "flux_up"), _ptr(fluxes.flux_dn, lev, "flux_dn"),
-                   None if fluxes_clear is None else _ptr(fluxes_clear.flux_up, lev, "flux_up_clear"),
-                   None if fluxes_clear is None else _ptr(fluxes_clear.flux_dn, lev, "flux_dn_clear"),
-                   _ptr(flux_up_jac, lev, "flux_up_jac"))
-        except KeyError as e:
-            return str(e.args[0])
-        except (TypeError, ValueError) as e:
-            return str(e)
-        rc = lib().ecckd_lw_fluxes_rescaled_jac(self._need(), ncol, nlay, *inp, n, names, ptrs, cs, ls, sc, int(bool(top_at_1)),
-                                                int(n_gauss_angles), *emis, nbp, *part, *out, space, _stream(space))
-        return last_error() if rc else ""
+        return self._fused(lib().ecckd_lw_fluxes_rescaled_jac, False, ("gas", "particles", "mask", "head", "boundary", "outputs"),
+                           gas_desc, particles=_particle_slots(particles.tau, particles.ssa, particles.g),
+                           mask=(cloud_mask,),
+                           outputs=_flux_slots(fluxes) + _flux_slots(fluxes_clear or _NO_FLUXES, "_clear") + _jac_slot(flux_up_jac),
+                           **_lw_groups(plev, tlay, tsfc, tlev, top_at_1, n_gauss_angles, sfc_emis, inc_flux))
 
     def lw_fluxes_rescaled_scratch_bytes(self, ncol, nlay, with_clear=False):
         """``ecckd_lw_fluxes_rescaled_jac_scratch_bytes``: the stream scratch of ``lw_fluxes_rescaled`` on device tensors."""
@@ -1633,37 +1608,16 @@ class GasOpticsEcckd:
         ``particles`` and ``cloud_mask`` as for ``lw_fluxes_allsky``; neither is written.  float64, fast arithmetic mode;
         numpy or device tensors.  float32 arrays (all of them) take ``ecckd_lw_fluxes_clear_allsky_f32``.  Returns the
         error message ('' = success).  With the surface-temperature Jacobian: ``lw_fluxes_clear_allsky_jac`` (float64)."""
-        nlay, ncol = tlay.shape
-        ng = self.get_ngpt()
-        ssa = getattr(particles, "ssa", None)
-        f32, mixed = _call_precision("lw_fluxes_clear_allsky", (
-            ("plev", plev), ("tlay", tlay), ("tsfc", tsfc), ("tlev", tlev), ("sfc_emis", sfc_emis), ("inc_flux", inc_flux),
-            ("particles.tau", particles.tau), ("particles.ssa", ssa), ("flux_up", fluxes.flux_up), ("flux_dn", fluxes.flux_dn),
-            ("flux_up_clear", fluxes_clear.flux_up), ("flux_dn_clear", fluxes_clear.flux_dn)))
+        lw = _lw_groups(plev, tlay, tsfc, tlev, top_at_1, n_gauss_angles, sfc_emis, inc_flux)
+        part = _particle_slots(particles.tau, getattr(particles, "ssa", None))
+        out = _flux_slots(fluxes) + _flux_slots(fluxes_clear, "_clear")
+        f32, mixed = _call_precision("lw_fluxes_clear_allsky", _named(lw["head"], lw["boundary"], part, out))
         if mixed:
             return mixed
-        P = lambda a, shape, what: _ptr(a, shape, what, f32)
-        try:
-            space = _space_of([plev, tlay, tsfc, tlev, sfc_emis, inc_flux, fluxes.flux_up, fluxes.flux_dn, fluxes_clear.flux_up,
-                               fluxes_clear.flux_dn, particles.tau, ssa])
-            n, names, ptrs, cs, ls, sc, keep = self._gas_args(gas_desc, ncol, nlay, space, f32)
-            nbp = 0 if particles.tau is None else int(particles.tau.shape[0])
-            shp = (nbp, nlay, ncol)
-            part = (P(particles.tau, shp, "particles.tau"), P(ssa, shp, "particles.ssa"),
-                    None if cloud_mask is None else _mask_ptr(cloud_mask, nlay, ncol, space))
-            out = tuple(P(a, (nlay + 1, ncol), what) for a, what in (
-                (fluxes.flux_up, "flux_up"), (fluxes.flux_dn, "flux_dn"), (fluxes_clear.flux_up, "flux_up_clear"),
-                (fluxes_clear.flux_dn, "flux_dn_clear")))
-        except KeyError as e:
-            return str(e.args[0])
-        except (TypeError, ValueError) as e:
-            return str(e)
-        rc = (lib().ecckd_lw_fluxes_clear_allsky_f32 if f32 else lib().ecckd_lw_fluxes_clear_allsky)(
-            self._need(), ncol, nlay, P(plev, (nlay + 1, ncol), "plev"), P(tlay, (nlay, ncol), "tlay"),
-            P(tsfc, (ncol,), "tsfc"), P(tlev, (nlay + 1, ncol), "tlev"), n, names, ptrs, cs, ls, sc, int(bool(top_at_1)),
-            int(n_gauss_angles), P(sfc_emis, (ncol, self.get_nband()), "sfc_emis"), P(inc_flux, (ng, ncol), "inc_flux"),
-            nbp, *part, *out, space, _stream(space))
-        return last_error() if rc else ""
+        # (the inputs are not in `returns`: a wrong one raises, every other wrong array is a message)
+        return self._fused(lib().ecckd_lw_fluxes_clear_allsky_f32 if f32 else lib().ecckd_lw_fluxes_clear_allsky, f32,
+                           ("gas", "particles", "mask", "outputs"), gas_desc, particles=part, mask=(cloud_mask,),
+                           outputs=out, **lw)
 
     def lw_fluxes_clear_allsky_jac(self, plev, tlay, tsfc, tlev, gas_desc, top_at_1, sfc_emis, particles, fluxes, fluxes_clear,
                                    flux_up_jac, n_gauss_angles=1, inc_flux=None, cloud_mask=None):
@@ -1684,60 +1638,26 @@ class GasOpticsEcckd:
         ``flux_dn_dir`` of either may be None independently of the other.  float64, fast arithmetic mode; numpy or device
         tensors.  float32 arrays (all of them) take ``ecckd_sw_fluxes_clear_allsky_f32``.  Returns the error message
         ('' = success)."""
-        nlay, ncol = tlay.shape
-        nband = self.get_nband()
-        f32, mixed = _call_precision("sw_fluxes_clear_allsky", (
-            ("plev", plev), ("tlay", tlay), ("mu0", mu0), ("toa_scale", toa_scale), ("sfc_alb_dir", sfc_alb_dir),
-            ("sfc_alb_dif", sfc_alb_dif), ("particles.tau", particles.tau), ("particles.ssa", particles.ssa),
-            ("particles.g", particles.g), ("flux_up", fluxes.flux_up), ("flux_dn", fluxes.flux_dn),
-            ("flux_dn_dir", fluxes.flux_dn_dir), ("flux_up_clear", fluxes_clear.flux_up), ("flux_dn_clear", fluxes_clear.flux_dn),
-            ("flux_dn_dir_clear", fluxes_clear.flux_dn_dir)))
+        sw = _sw_groups(plev, tlay, top_at_1, mu0, toa_scale, sfc_alb_dir, sfc_alb_dif)
+        # (tau_required: particles without tau raise here, as they always have)
+        part = _particle_slots(particles.tau, particles.ssa, particles.g, tau_required=True)
+        out = _flux_slots(fluxes, dn_dir=True) + _flux_slots(fluxes_clear, "_clear", dn_dir=True)
+        f32, mixed = _call_precision("sw_fluxes_clear_allsky", _named(sw["head"], sw["boundary"], part, out))
         if mixed:
             return mixed
-        P = lambda a, shape, what: _ptr(a, shape, what, f32)
-        try:
-            space = _space_of([plev, tlay, mu0, toa_scale, sfc_alb_dir, sfc_alb_dif, fluxes.flux_up, fluxes.flux_dn,
-                               fluxes_clear.flux_up, fluxes_clear.flux_dn, particles.tau, particles.ssa, particles.g])
-            mp = None if cloud_mask is None else _mask_ptr(cloud_mask, nlay, ncol, space)
-            n, names, ptrs, cs, ls, sc, keep = self._gas_args(gas_desc, ncol, nlay, space, f32)
-            nbp = int(particles.tau.shape[0])
-            shp = (nbp, nlay, ncol)
-            part = (P(particles.tau, shp, "particles.tau"), P(particles.ssa, shp, "particles.ssa"),
-                    P(particles.g, shp, "particles.g"))
-            out = tuple(P(a, (nlay + 1, ncol), what) for a, what in (
-                (fluxes.flux_up, "flux_up"), (fluxes.flux_dn, "flux_dn"), (fluxes.flux_dn_dir, "flux_dn_dir"),
-                (fluxes_clear.flux_up, "flux_up_clear"), (fluxes_clear.flux_dn, "flux_dn_clear"),
-                (fluxes_clear.flux_dn_dir, "flux_dn_dir_clear")))
-        except KeyError as e:
-            return str(e.args[0])
-        except (TypeError, ValueError) as e:
-            return str(e)
-        rc = (lib().ecckd_sw_fluxes_clear_allsky_f32 if f32 else lib().ecckd_sw_fluxes_clear_allsky)(
-            self._need(), ncol, nlay, P(plev, (nlay + 1, ncol), "plev"), P(tlay, (nlay, ncol), "tlay"), n, names, ptrs,
-            cs, ls, sc, int(bool(top_at_1)), P(mu0, (ncol,), "mu0"), P(toa_scale, (ncol,), "toa_scale"),
-            P(sfc_alb_dir, (ncol, nband), "sfc_alb_dir"), P(sfc_alb_dif, (ncol, nband), "sfc_alb_dif"), nbp, *part,
-            int(bool(delta_scale)), mp, *out, space, _stream(space))
-        return last_error() if rc else ""
+        # (the inputs are not in `returns`: a wrong one raises, every other wrong array is a message)
+        return self._fused(lib().ecckd_sw_fluxes_clear_allsky_f32 if f32 else lib().ecckd_sw_fluxes_clear_allsky, f32,
+                           ("mask", "gas", "particles", "outputs"), gas_desc, particles=part + (int(bool(delta_scale)),),
+                           mask=(cloud_mask,), outputs=out, **sw)
 
     def gas_optics_ext(self, play, plev, tlay, gas_desc, optical_props, toa_src, col_dry=None):
-        nlay, ncol = tlay.shape
-        ng = self.get_ngpt()
         """float64 arrays -> ecckd_gas_optics_sw; float32 arrays -> ecckd_gas_optics_sw_f32."""
         two = isinstance(optical_props, OpticalProps2str)
         f32 = _is_f32(plev)
-        try:
-            space = _space_of([plev, tlay, optical_props.tau, toa_src])
-            n, names, ptrs, cs, ls, sc, keep = self._gas_args(gas_desc, ncol, nlay, space, f32)
-        except KeyError as e:
-            return str(e.args[0])
-        P = lambda a, shape, what: _ptr(a, shape, what, f32)
-        rc = (lib().ecckd_gas_optics_sw_f32 if f32 else lib().ecckd_gas_optics_sw)(
-            self._need(), ncol, nlay, P(plev, (nlay + 1, ncol), "plev"), P(tlay, (nlay, ncol), "tlay"),
-            n, names, ptrs, cs, ls, sc, P(optical_props.tau, (ng, nlay, ncol), "tau"),
-            P(optical_props.ssa, (ng, nlay, ncol), "ssa") if two else None,
-            P(optical_props.g, (ng, nlay, ncol), "g") if two else None,
-            P(toa_src, (ng, ncol), "toa_src"), space, _stream(space))
-        return last_error() if rc else ""
+        return self._fused(lib().ecckd_gas_optics_sw_f32 if f32 else lib().ecckd_gas_optics_sw, f32, (), gas_desc,
+                           (("plev", plev, _LEV), ("tlay", tlay, _LAY)),
+                           outputs=(("tau", optical_props.tau, _SPEC), ("ssa", optical_props.ssa if two else None, _SPEC),
+                                    ("g", optical_props.g if two else None, _SPEC), ("toa_src", toa_src, _GPT)))
 
     def sw_fluxes_allsky(self, plev, tlay, gas_desc, top_at_1, mu0, sfc_alb_dir, sfc_alb_dif, particles, fluxes,
                          delta_scale=True, toa_scale=None, cloud_mask=None):
@@ -1748,44 +1668,21 @@ class GasOpticsEcckd:
         ``ecckd_sw_fluxes_allsky_mcica``): a g-point whose bit is clear sees no particles in that layer.  float32 arrays
         (all of them) take ``ecckd_sw_fluxes_allsky_f32`` / ``_mcica_f32``: the same route in single precision, to rounding
         what ``gas_optics`` + ``delta_scale`` + ``increment`` + ``rte_sw`` give on float32 arrays."""
-        nlay, ncol = tlay.shape
-        nband = self.get_nband()
-        mp = ()
-        f32, mixed = _call_precision("sw_fluxes_allsky", (
-            ("plev", plev), ("tlay", tlay), ("mu0", mu0), ("toa_scale", toa_scale), ("sfc_alb_dir", sfc_alb_dir),
-            ("sfc_alb_dif", sfc_alb_dif), ("particles.tau", particles.tau), ("particles.ssa", particles.ssa),
-            ("particles.g", particles.g), ("flux_up", fluxes.flux_up), ("flux_dn", fluxes.flux_dn),
-            ("flux_dn_dir", fluxes.flux_dn_dir)))
+        sw = _sw_groups(plev, tlay, top_at_1, mu0, toa_scale, sfc_alb_dir, sfc_alb_dif)
+        # (tau_required: particles without tau raise here, as they always have)
+        part = _particle_slots(particles.tau, particles.ssa, particles.g, tau_required=True)
+        out = _flux_slots(fluxes, dn_dir=True)
+        f32, mixed = _call_precision("sw_fluxes_allsky", _named(sw["head"], sw["boundary"], part, out))
         if mixed:
             return mixed
-        P = lambda a, shape, what: _ptr(a, shape, what, f32)
-        try:
-            space = _space_of([plev, tlay, mu0, toa_scale, sfc_alb_dir, sfc_alb_dif, fluxes.flux_up, fluxes.flux_dn,
-                               particles.tau, particles.ssa, particles.g])
-            if cloud_mask is not None:
-                mp = (_mask_ptr(cloud_mask, nlay, ncol, space),)
-            n, names, ptrs, cs, ls, sc, keep = self._gas_args(gas_desc, ncol, nlay, space, f32)
-            nbp = int(particles.tau.shape[0])
-            shp = (nbp, nlay, ncol)
-            part = (P(particles.tau, shp, "particles.tau"), P(particles.ssa, shp, "particles.ssa"),
-                    P(particles.g, shp, "particles.g"))
-        except KeyError as e:
-            return str(e.args[0])
-        except (TypeError, ValueError) as e:
-            return str(e)
         L = lib()
         if f32:
             fn = L.ecckd_sw_fluxes_allsky_f32 if cloud_mask is None else L.ecckd_sw_fluxes_allsky_mcica_f32
         else:
             fn = L.ecckd_sw_fluxes_allsky if cloud_mask is None else L.ecckd_sw_fluxes_allsky_mcica
-        rc = fn(
-            self._need(), ncol, nlay, P(plev, (nlay + 1, ncol), "plev"), P(tlay, (nlay, ncol), "tlay"), n, names, ptrs,
-            cs, ls, sc, int(bool(top_at_1)), P(mu0, (ncol,), "mu0"), P(toa_scale, (ncol,), "toa_scale"),
-            P(sfc_alb_dir, (ncol, nband), "sfc_alb_dir"), P(sfc_alb_dif, (ncol, nband), "sfc_alb_dif"), nbp, *part,
-            int(bool(delta_scale)), *mp, P(fluxes.flux_up, (nlay + 1, ncol), "flux_up"),
-            P(fluxes.flux_dn, (nlay + 1, ncol), "flux_dn"), P(fluxes.flux_dn_dir, (nlay + 1, ncol), "flux_dn_dir"),
-            space, _stream(space))
-        return last_error() if rc else ""
+        # (the inputs and the outputs are not in `returns`: a wrong one raises, a wrong particle plane or mask is a message)
+        return self._fused(fn, f32, ("mask", "gas", "particles"), gas_desc, particles=part + (int(bool(delta_scale)),),
+                           mask=() if cloud_mask is None else (cloud_mask,), outputs=out, **sw)
 
     def sw_fluxes(self, plev, tlay, gas_desc, top_at_1, mu0, sfc_alb_dir, sfc_alb_dif, fluxes, toa_scale=None):
         """``ecckd_sw_fluxes`` (float32 arrays: ``_f32``): gas optics + rte_sw in one call for hosts that only need
@@ -1794,22 +1691,11 @@ class GasOpticsEcckd:
         ``(ncol,)``: the drivers' rescaling of the incoming beam (total solar irradiance), or None.  Any layer count and
         either ``"sw_solver"``; the fast arithmetic mode only.  The solver is the one ``rte_sw`` takes for the same shape,
         so the fluxes equal those of ``gas_optics`` + ``rte_sw`` bit for bit."""
-        nlay, ncol = tlay.shape
-        nband = self.get_nband()
-        f32 = _is_f32(plev)
-        try:
-            space = _space_of([plev, tlay, mu0, toa_scale, sfc_alb_dir, sfc_alb_dif, fluxes.flux_up, fluxes.flux_dn])
-            n, names, ptrs, cs, ls, sc, keep = self._gas_args(gas_desc, ncol, nlay, space, f32)
-        except KeyError as e:
-            return str(e.args[0])
-        P = lambda a, shape, what: _ptr(a, shape, what, f32)
-        rc = (lib().ecckd_sw_fluxes_f32 if f32 else lib().ecckd_sw_fluxes)(
-            self._need(), ncol, nlay, P(plev, (nlay + 1, ncol), "plev"), P(tlay, (nlay, ncol), "tlay"), n, names, ptrs, cs,
-            ls, sc, int(bool(top_at_1)), P(mu0, (ncol,), "mu0"), P(toa_scale, (ncol,), "toa_scale"),
-            P(sfc_alb_dir, (ncol, nband), "sfc_alb_dir"), P(sfc_alb_dif, (ncol, nband), "sfc_alb_dif"),
-            P(fluxes.flux_up, (nlay + 1, ncol), "flux_up"), P(fluxes.flux_dn, (nlay + 1, ncol), "flux_dn"),
-            P(fluxes.flux_dn_dir, (nlay + 1, ncol), "flux_dn_dir"), space, _stream(space))
-        return last_error() if rc else ""
+        f32 = _is_f32(plev)   # (from plev alone, where its siblings go through _call_precision)
+        # (returns nothing: a wrong array raises here, where the all-sky calls answer with a message)
+        return self._fused(lib().ecckd_sw_fluxes_f32 if f32 else lib().ecckd_sw_fluxes, f32, (), gas_desc,
+                           outputs=_flux_slots(fluxes, dn_dir=True),
+                           **_sw_groups(plev, tlay, top_at_1, mu0, toa_scale, sfc_alb_dir, sfc_alb_dif))
 
     def sw_fluxes_daylit(self, plev, tlay, gas_desc, top_at_1, mu0, sfc_alb_dir, sfc_alb_dif, fluxes, particles=None,
                          fluxes_clear=None, delta_scale=True, toa_scale=None, cloud_mask=None, day_index=None, mu0_min=0.0):
@@ -1822,36 +1708,14 @@ class GasOpticsEcckd:
         and a list made beforehand the call is asynchronous and can be captured.  Returns the error message ('' = success)."""
         if any(_is_f32(a) for a in (plev, tlay, mu0, fluxes.flux_up)):
             return "sw_fluxes_daylit: implemented for float64 arrays"
-        nlay, ncol = tlay.shape
-        nband = self.get_nband()
-        clear = fluxes_clear if fluxes_clear is not None else FluxesBroadband()
-        part = particles if particles is not None else OpticalProps2str()
-        try:
-            space = _space_of([plev, tlay, mu0, toa_scale, sfc_alb_dir, sfc_alb_dif, fluxes.flux_up, fluxes.flux_dn,
-                               clear.flux_up, clear.flux_dn, part.tau, getattr(part, "ssa", None), getattr(part, "g", None), day_index])
-            if day_index is None:
-                day_index, _ = daylit_columns(mu0, mu0_min)
-            nday = int(day_index.shape[0])
-            ip = _int32_ptr(day_index, (nday,), "day_index") if nday else None
-            mp = None if cloud_mask is None else _mask_ptr(cloud_mask, nlay, ncol, space)
-            n, names, ptrs, cs, ls, sc, keep = self._gas_args(gas_desc, ncol, nlay, space)
-            nbp = int(part.tau.shape[0]) if part.tau is not None else 0
-            shp = (nbp, nlay, ncol)
-            pp = (_ptr(part.tau, shp, "particles.tau"), _ptr(getattr(part, "ssa", None), shp, "particles.ssa"),
-                  _ptr(getattr(part, "g", None), shp, "particles.g"))
-            out = tuple(_ptr(a, (nlay + 1, ncol), what) for a, what in (
-                (fluxes.flux_up, "flux_up"), (fluxes.flux_dn, "flux_dn"), (fluxes.flux_dn_dir, "flux_dn_dir"),
-                (clear.flux_up, "flux_up_clear"), (clear.flux_dn, "flux_dn_clear"), (clear.flux_dn_dir, "flux_dn_dir_clear")))
-        except KeyError as e:
-            return str(e.args[0])
-        except (TypeError, ValueError) as e:
-            return str(e)
-        rc = lib().ecckd_sw_fluxes_daylit(
-            self._need(), ncol, nlay, nday, ip, _ptr(plev, (nlay + 1, ncol), "plev"), _ptr(tlay, (nlay, ncol), "tlay"), n, names,
-            ptrs, cs, ls, sc, int(bool(top_at_1)), _ptr(mu0, (ncol,), "mu0"), _ptr(toa_scale, (ncol,), "toa_scale"),
-            _ptr(sfc_alb_dir, (ncol, nband), "sfc_alb_dir"), _ptr(sfc_alb_dif, (ncol, nband), "sfc_alb_dif"), nbp, *pp,
-            int(bool(delta_scale)), mp, *out, space, _stream(space))
-        return last_error() if rc else ""
+        # (the inputs are not in `returns`: a wrong one raises, every other wrong array is a message.  Without a list the columns
+        # are selected once the memory space is known, and a failure of that call is a message as well)
+        return self._fused(lib().ecckd_sw_fluxes_daylit, False, ("columns", "mask", "gas", "particles", "outputs"), gas_desc,
+                           columns=day_index if day_index is not None else (lambda: daylit_columns(mu0, mu0_min)[0]),
+                           particles=_particle_slots(*[getattr(particles, a, None) for a in ("tau", "ssa", "g")]) +
+                           (int(bool(delta_scale)),), mask=(cloud_mask,),
+                           outputs=_flux_slots(fluxes, dn_dir=True) + _flux_slots(fluxes_clear or _NO_FLUXES, "_clear", dn_dir=True),
+                           **_sw_groups(plev, tlay, top_at_1, mu0, toa_scale, sfc_alb_dir, sfc_alb_dif))
 
 
 # ------------------------------------------------------------------------------------------
