@@ -18,16 +18,15 @@
 //
 // Surface term: from sfc_source_jac(ncol,ng) (ecckd_rte_lw_jac), or -- PLANCK -- B(tsfc + 1) - B(tsfc) from the model's
 // Planck table in global memory (two evaluations per (column, g-point), against nlay cells), the fused calls' form.
-// SKY / MASK: the particulate optical depth on the model's bands and the McICA mask, applied to the gas optical depth with
-// the expressions of rte_lw_split_body operation by operation (the 60-layer fused route, whose flux kernel leaves the
-// scratch tau as gas optics wrote it).
+// SKY / MASK: the particulate optical depth on the model's bands and the McICA mask, applied to the gas optical depth by
+// lw_cell_tau (lw_layer.hpp), the function rte_lw_split_body calls for the same cell (the 60-layer fused route, whose flux
+// kernel leaves the scratch tau as gas optics wrote it).
 // RESC: the rescaled solver's Jacobian (include/ecckd_hip.h, "Rescaled longwave: clear sky and Jacobian").  With every source
-// zero the rescaled transport is J = t_k * J with t_k = lw_exp(-((tau * sc) * D_k)), sc = (1 - ssa) + (ssa * (1 - g)) * 0.5,
-// formed with the expressions of the RESC branch of rte_lw_split_body on the cell's (tau, ssa, g).  Two forms: arrays (SKY =
-// 0: a.ssa and a.g beside a.tau, 24 B per cell -- ecckd_rte_lw_rescaled_jac and the fused general route, whose increment
-// left the cell's triple in scratch), and SKY = 2 with a.part_g and the optional mask (the 60-layer fused route: the cell's
-// triple from the gas optical depth and the band triple with the operations of increment_body<double,true,true,true,MASK>,
-// its two IEEE divisions included).
+// zero the rescaled transport is J = t_k * J with t_k = lw_exp(-((tau * sc) * D_k)), sc = (1 - ssa) + (ssa * (1 - g)) * 0.5:
+// tau * sc comes from lw_cell_rescaled (lw_layer.hpp), which the rescaled form of rte_lw_split_body calls too.  Two forms:
+// arrays (SKY = 0: a.ssa and a.g beside a.tau, 24 B per cell -- ecckd_rte_lw_rescaled_jac and the fused general route, whose
+// increment left the cell's triple in scratch), and SKY = 2 with a.part_g and the optional mask (the 60-layer fused route:
+// the cell's triple from the gas optical depth and the band triple).
 #include "kernels.hpp"
 #include "lw_layer.hpp"
 #include "planck_at.hpp"
@@ -137,33 +136,13 @@ __device__ __forceinline__ void rte_lw_jac_body(const Args &a, const PlanckTab &
             if (s < nwalk) {
               level(s);
               double tau = ptau[u];
-              [[maybe_unused]] double tp = 0.;
-              if (SKY) tp = ppt[u];
-              if (MASK) tp = (pmk[u] >> gg) & 1ull ? tp : 0.;
-              if constexpr (!RESC) {
-              if (SKY == 1) tau = tau + tp;
-              if (SKY == 2) tau = tau + tp * (1. - pps[u]);
-              } else {
-                double cssa, cg;
-                if constexpr (SKY == 2) {
-                  // increment_body<double, true, true, true, MASK> of kernels_optical_props.hip on op1 = (tau_gas, +0, +0)
-                  constexpr double tiny3 = op_eps<double>();
-                  const double tscat2 = tp * pps[u];
-                  const double tsg2 = tscat2 * pgg[u];
-                  const double tau12 = tau + tp;
-                  const double tscat1 = tau * 0.;
-                  const double tauscat12 = tscat1 + tscat2;
-                  cg = (tscat1 * 0. + tsg2) / (tauscat12 > tiny3 ? tauscat12 : tiny3);
-                  cssa = tauscat12 / (tau12 > tiny3 ? tau12 : tiny3);
-                  tau = tau12;
-                } else {
-                  cssa = pss[u];
-                  cg = pgg[u];
-                }
-                const double wb = cssa * (1. - cg) * 0.5;
-                const double sc = (1. - cssa) + wb;
-                tau = tau * sc;
-              }
+              [[maybe_unused]] bool cloudy = true;
+              if constexpr (MASK) cloudy = (pmk[u] >> gg) & 1ull;
+              [[maybe_unused]] double Cn;   // (the rescaled fluxes' adjustment factor: not needed here)
+              if constexpr (RESC && SKY == 2) lw_cell_rescaled<true>(ptau[u], ppt[u], pps[u], pgg[u], cloudy, tau, Cn);
+              else if constexpr (RESC) lw_cell_rescaled<false>(ptau[u], 0., pss[u], pgg[u], true, tau, Cn);
+              else if constexpr (SKY == 2) tau = lw_cell_tau<2>(ptau[u], ppt[u], pps[u], cloudy);
+              else if constexpr (SKY == 1) tau = lw_cell_tau<1>(ptau[u], ppt[u], 0., cloudy);
               issue(u);
 #pragma unroll
               for (int k = 0; k < 4; ++k) {

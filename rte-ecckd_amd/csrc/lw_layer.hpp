@@ -1,5 +1,7 @@
-// lw_layer.hpp -- exp() and `/` of lw_source_noscat / the transmittance of a layer, shared by the longwave solvers
-// (kernels_rte_lw.hip, kernels_rte_lw_split.hip) so that they produce the same bits per cell.
+// lw_layer.hpp -- the per-cell pieces of the longwave solvers, each written once: exp() and `/` of lw_source_noscat, the
+// source function and transmittance of a layer, and the optical depth a cell has under particles, a McICA mask and the
+// rescaling.  Shared by kernels_rte_lw.hip (exp and `/`), kernels_rte_lw_split.hip and kernels_rte_lw_jac.hip so that they
+// produce the same bits per cell.
 // [RTE-ext: the expressions they serve are restated from the public v1.5-era mo_rte_solver_kernels.F90 -- SURVEY.md
 // Appendix B.1; call site example/rfmip-rad-irf/ecckd_rfmip_lw.F90:130-135.]
 //
@@ -8,6 +10,8 @@
 // against 10.4 measured), so every instruction of the per-cell body counts.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include "kernels.hpp"
 
 namespace ecckd {
 namespace {
@@ -56,6 +60,64 @@ __device__ __forceinline__ double lw_div(double x, double d) {
   return fma(fma(-d, q, x), r, q);
 }
 __device__ __forceinline__ float lw_div(float x, float d) { return x / d; }
+
+// Transmittance and the two sources of a layer (lw_source_noscat) from its slant optical depth tl, the
+// layer source and the level sources at its down-sweep far edge (bdn) and its up-sweep far edge (bup).  Both branches of
+// lw_source_noscat's merge() are evaluated and selected (no branch); SER3: the three-term series below tau_thresh.
+// source_up is materialised here: left alone, the optimiser sinks the expression into the up sweep and keeps its five
+// inputs alive per layer instead of the one result.
+template <bool SER3, typename real>
+__device__ __forceinline__ void lw_layer_source(real tl, real tau_thresh, real lay, real bdn, real bup, real &t, real &sdn, real &su_out) {
+  t = lw_exp(-tl);
+  const real omt = real(1) - t;
+  const real fact_big = lw_div(omt, tl) - t;
+  const real fact_small = SER3 ? tl * (real(0.5) + tl * (-real(1) / real(3) + tl * (real(1) / real(8))))
+                               : tl * (real(0.5) - real(1) / real(3) * tl);
+  const real fact = tl > tau_thresh ? fact_big : fact_small;
+  sdn = omt * bdn + real(2) * fact * (lay - bdn);
+  real su = omt * bup + real(2) * fact * (lay - bup);
+  asm volatile("" : "+v"(su));
+  su_out = su;
+}
+
+// Optical depth of a cell of the fused all-sky forms: the gas optical depth plus the particles of the lane's band, as they
+// are (SKY = 1: one-stream particles, increment_1scalar_by_1scalar) or their absorption optical depth part_tau * (1 -
+// part_ssa) (SKY = 2: two-stream particles, increment_1scalar_by_2stream) -- the expressions of kernels_optical_props.hip
+// operation by operation.  cloudy: the McICA mask's bit of the cell (true without a mask); where it is clear the cell uses
+// part_tau = 0 in front of the expressions.  (The flag and not the mask word: the callers carry words of different widths.)
+template <int SKY>
+__device__ __forceinline__ double lw_cell_tau(double tau_gas, double part_tau, double part_ssa, bool cloudy) {
+  static_assert(SKY == 1 || SKY == 2, "one- or two-stream particles");
+  const double tp = cloudy ? part_tau : 0.;
+  return SKY == 1 ? tau_gas + tp : tau_gas + tp * (1. - part_ssa);
+}
+
+// Optical depth of a cell under the rescaled solver (include/ecckd_hip.h, "Rescaled longwave"): tau * sc, and Cn of the
+// adjustment terms, from the cell's (tau, ssa, g).  BAND = false: (tau, ssa, g) are the cell's, as read from arrays (cloudy
+// is not looked at).  BAND = true: tau is the gas optical depth and (part_tau, ssa, g) the triple of the lane's band; the
+// cell's triple is formed with the operations of increment_body<double, true, true, true, MASK> of
+// kernels_optical_props.hip on op1 = (tau_gas, +0, +0), its two IEEE divisions included.
+// (IEEE division in Cn: ssa = g = 1 gives 0/0, a NaN that stays in its column.)
+template <bool BAND>
+__device__ __forceinline__ void lw_cell_rescaled(double tau, double part_tau, double ssa, double g, bool cloudy, double &tau_sc,
+                                                 double &Cn) {
+  if constexpr (BAND) {
+    constexpr double tiny3 = op_eps<double>();
+    const double tp = cloudy ? part_tau : 0.;
+    const double tscat2 = tp * ssa;
+    const double tsg2 = tscat2 * g;
+    const double tau12 = tau + tp;
+    const double tscat1 = tau * 0.;
+    const double tauscat12 = tscat1 + tscat2;
+    g = (tscat1 * 0. + tsg2) / (tauscat12 > tiny3 ? tauscat12 : tiny3);
+    ssa = tauscat12 / (tau12 > tiny3 ? tau12 : tiny3);
+    tau = tau12;
+  }
+  const double wb = ssa * (1. - g) * 0.5;
+  const double sc = (1. - ssa) + wb;
+  tau_sc = tau * sc;
+  Cn = 0.4 * (wb / sc);
+}
 
 }  // namespace
 }  // namespace ecckd

@@ -217,18 +217,8 @@
         const bool act = !PAD || present(s);
         if (PAD) tau = act ? tau : real(0);   // absent layer: trans = 1, both sources 0
         const real tl = tau * D;
-        const real t = lw_exp(-tl);
-        const real omt = real(1) - t;
-        // both branches of lw_source_noscat's merge() are evaluated and selected (no branch)
-        const real fact_big = lw_div(omt, tl) - t;
-        const real fact_small = SER3 ? tl * (real(0.5) + tl * (-real(1) / real(3) + tl * (real(1) / real(8))))
-                                     : tl * (real(0.5) - real(1) / real(3) * tl);
-        const real fact = tl > tau_thresh ? fact_big : fact_small;
-        const real sdn = omt * bdn + real(2) * fact * (lay - bdn);
-        real su = omt * bup + real(2) * fact * (lay - bup);
-        // Materialise source_up here: left alone, the optimiser sinks this expression into the
-        // up sweep and keeps its five inputs alive per layer instead of the one result.
-        asm volatile("" : "+v"(su));
+        real t, sdn, su;
+        lw_layer_source<SER3>(tl, tau_thresh, lay, bdn, bup, t, sdn, su);   // (lw_layer.hpp; source_up is materialised there)
         su_out = su;
         t_out = t;
         const real v = gsum<real, CW>(wfac * I);
