@@ -1215,6 +1215,64 @@ int ecckd_aerosol_optics_f32(const ecckd_aerosol_optics_t *aerosol_optics, int n
                              float *ssa, float *g, int memspace, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Heating rates: the divergence of the net flux across each layer to the temperature tendency in K s-1 -- the last step
+ * of a model's radiation call, after the flux calls above.  A radiation step needs it for up to four flux sets (longwave
+ * and shortwave, clear and all sky), and per band where the host asks for by-band fluxes (ecckd_rte_*_byband).  The
+ * counterpart in RTE-RRTMGP is compute_heating_rate [RTE-ext: extensions/mo_heating_rates.F90], which every all-sky
+ * driver built on it calls after rte_lw / rte_sw.  RTE-RRTMGP is not part of the reference tree, so PARITY WITH IT IS
+ * UNPINNED; the definition below restates its published expression and is what the tests pin (tests/heating_rate_ref.py
+ * restates it in numpy, and the results are equal BIT FOR BIT in fp64 and in float: the build has FMA contraction off,
+ * the quotient is a division, not a product with a reciprocal, and every line below is one correctly rounded IEEE
+ * operation in the precision of the call).
+ * Out of scope: heating rates as an extra output of the fused flux calls or inside the solver kernels (they move about
+ * 1/30 of a flux call's bytes); net-flux or surface / top-of-atmosphere summaries.
+ *
+ * ecckd_heating_rate (+ _f32).  All arrays column fastest.
+ *   flux_up, flux_dn: (ncol,nlay+1,nouter), W m-2.  For shortwave flux_dn is the TOTAL downward flux, direct beam
+ *     included, as ecckd_rte_sw and the fused shortwave calls return it.
+ *   plev: (ncol,nlay+1), Pa; shared by every outer plane.
+ *   cp: (ncol,nlay), J kg-1 K-1, or NULL.  The host's own -- for instance moist -- specific heat per cell; it replaces
+ *     cp_dry, which is then not looked at.
+ *   heating_rate: (ncol,nlay,nouter), K s-1.  It must not alias an input.
+ *   nouter = 1 for broadband fluxes; nouter = nband for the bnd_flux_* arrays of the by-band calls; a host that stacks
+ *     its flux sets (longwave / shortwave, clear / all sky) in one allocation passes any other count.
+ *   grav (m s-2) and cp_dry (J kg-1 K-1) are arguments, not library state; the customary values grav = 9.80665 and
+ *     cp_dry = 1004.64 are the defaults of the Python and Fortran interfaces.
+ * Per cell, with l the layer's index in memory (0-based) and levels l, l+1 its two edges:
+ *     du   = flux_up[l+1] - flux_up[l]
+ *     dd   = flux_dn[l+1] - flux_dn[l]
+ *     dnet = du - dd
+ *     dp   = plev[l+1] - plev[l]
+ *     c    = cp ? cp[l] : cp_dry
+ *     heating_rate[l] = (dnet * grav) / (c * dp)
+ *   There is no top_at_1 argument because the expression does not depend on the orientation: with the levels stored the
+ *   other way round du, dd (so dnet) and dp all change sign exactly -- a - b and b - a round to each other's negation --
+ *   and the quotient of two negated operands is the same quotient.  Reversing the level axis of the inputs therefore
+ *   reverses the layer axis of the result bit for bit.
+ *   dp == 0 or a NaN gives what IEEE gives (an infinity or a NaN; the sign and payload of a NaN are the device's), in
+ *   that cell only.
+ *   _f32: the arrays are float; grav and cp_dry stay double in the signature and are rounded to float once; everything
+ *   above in float.
+ *   Refused with a message before anything is launched, in this order: ncol, nlay or nouter < 1; flux_up, flux_dn, plev or
+ *   heating_rate NULL; grav not finite or not > 0, then -- without cp -- cp_dry not finite or not > 0; bad memspace; no
+ *   such device.  The arrays' values are not checked, in any memory space.
+ *   ECCKD_DEVICE is asynchronous on `stream` and uses no scratch, so it is capture-safe without a warm-up; ECCKD_HOST
+ *   stages through the device and synchronises; ECCKD_MIXED: host inputs, heating_rate a device buffer (synchronises).
+ *   Kernel: lanes along columns, one lane per (column, outer plane) walking the layers with the previous level's two
+ *   fluxes and pressure in registers, so each flux level is loaded once; the planes of a column block run next to each
+ *   other, so the pressures (and cp) leave HBM once and later planes find them in the caches.  64-bit offsets throughout
+ *   (ncol*(nlay+1)*nouter may pass 2^31).  Launch rule: blocks of 256 columns of one plane,
+ *   min(ceil(ncol/256)*nouter, 8*CUs), the rest by grid stride.  Algorithmic bytes:
+ *     sizeof(real) * ncol * ((2*nouter + 1)*(nlay+1) + (nouter + [cp])*nlay)
+ * --------------------------------------------------------------------------------------- */
+int ecckd_heating_rate(int device, int ncol, int nlay, int nouter, const double *flux_up, const double *flux_dn,
+                       const double *plev, double grav, double cp_dry, const double *cp, double *heating_rate,
+                       int memspace, void *stream);
+int ecckd_heating_rate_f32(int device, int ncol, int nlay, int nouter, const float *flux_up, const float *flux_dn,
+                           const float *plev, double grav, double cp_dry, const float *cp, float *heating_rate,
+                           int memspace, void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * Device memory for host languages without a HIP binding of their own (the Fortran shim's device-resident
  * twins of ty_optical_props / ty_source_func_lw own their buffers through these).  to_device: 1 = host to
  * device, 0 = device to host; synchronous.

@@ -14,7 +14,9 @@ This package is a thin mirror of the reference's Fortran interface on top of the
 * :class:`AerosolOptics` <-> RTE-RRTMGP's ``ty_aerosol_optics_rrtmgp_merra``: aerosol species, sizes, masses and relative
   humidity to the particulate properties on the bands, several species per call, optionally added onto the clouds;
 * :func:`rte_lw`, :func:`rte_sw` <-> RTE-RRTMGP's solvers as called at
-  ecckd_rfmip_lw.F90:130-135 and ecckd_rfmip_sw.F90:148-154.
+  ecckd_rfmip_lw.F90:130-135 and ecckd_rfmip_sw.F90:148-154;
+* :func:`heating_rate` <-> RTE-RRTMGP's ``compute_heating_rate``: fluxes and level pressures to the temperature tendency
+  in K s-1, the last step of a radiation call.
 
 Error behaviour follows the reference: the entry points return a message string, empty on
 success.  Arrays are numpy (host: staged through the GPU by the library) or torch CUDA tensors
@@ -42,6 +44,7 @@ _SOURCES = ["kernels_gas_fused.hip", "kernels_gas_roles.hip", "kernels_tau.hip",
             "kernels_rte_lw_jac.hip", "kernels_rte_lw_2str.hip",
             "kernels_rte_sw.hip", "kernels_rte_sw_sys.hip", "kernels_rte_gpt.hip", "kernels_optical_props.hip",
             "kernels_cloud_sampling.hip", "kernels_cloud_optics.hip", "kernels_aerosol_optics.hip", "kernels_columns.hip",
+            "kernels_heating_rate.hip",
             "capi.cpp", "nc_capi.cpp", "model.cpp", "cdf1.cpp"]
 _HEADERS = ["kernels.hpp", "wave_pair.hpp", "gas_fused_body.hpp", "sw_two_stream.hpp", "sw_two_stream_body.inc", "rte_lw_body.inc", "lw_two_stream.hpp", "lw_layer.hpp", "planck_at.hpp", "model.hpp", "cdf1.hpp", os.path.join("..", "..", "include", "ecckd_hip.h"),
             os.path.join("..", "..", "include", "ecckd_nc.h"), os.path.join("..", "..", "include", "rte_kernels_hip.h"),
@@ -98,11 +101,13 @@ RFMIP_LW = os.path.join(FORTRAN_BUILD, "ecckd_rfmip_lw")
 RFMIP_SW = os.path.join(FORTRAN_BUILD, "ecckd_rfmip_sw")
 CLOUD_DRIVER = os.path.join(FORTRAN_BUILD, "ecckd_cloud_driver")
 AEROSOL_DRIVER = os.path.join(FORTRAN_BUILD, "ecckd_aerosol_driver")
+HEATING_DRIVER = os.path.join(FORTRAN_BUILD, "ecckd_heating_driver")
 _FORTRAN_MODULES = ["mo_rte_min.F90", "mo_ecckd_device.F90", "gas_optics_ecckd.F90", "mo_rte_solvers.F90", "rfmip_support.F90",
-                    "mo_cloud_optics.F90", "mo_aerosol_optics.F90"]
+                    "mo_cloud_optics.F90", "mo_aerosol_optics.F90", "mo_heating_rates.F90"]
 _FORTRAN_PROGRAMS = [("ecckd_driver", "ecckd_driver.F90", []), ("ecckd_rfmip_lw", "ecckd_rfmip.F90", []),
                      ("ecckd_rfmip_sw", "ecckd_rfmip.F90", ["-DSHORTWAVE"]), ("ecckd_cloud_driver", "ecckd_cloud_driver.F90", []),
-                     ("ecckd_aerosol_driver", "ecckd_aerosol_driver.F90", [])]
+                     ("ecckd_aerosol_driver", "ecckd_aerosol_driver.F90", []),
+                     ("ecckd_heating_driver", "ecckd_heating_driver.F90", [])]
 
 
 def build_fortran(force=False, verbose=False):
@@ -280,6 +285,9 @@ def lib():
             getattr(L, "ecckd_aerosol_optics_get_" + f).argtypes = [C.c_void_p]
         for f in ("ecckd_aerosol_optics", "ecckd_aerosol_optics_f32"):
             getattr(L, f).argtypes = [C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 3 + [C.c_int, C.c_void_p]
+    if hasattr(L, "ecckd_heating_rate"):   # (ECCKD_LIB may name an older build, which lacks them)
+        for f in ("ecckd_heating_rate", "ecckd_heating_rate_f32"):
+            getattr(L, f).argtypes = [C.c_int] * 4 + [C.c_void_p] * 3 + [C.c_double] * 2 + [C.c_void_p] * 2 + [C.c_int, C.c_void_p]
     _lib = L
     return L
 
@@ -1120,6 +1128,10 @@ class FluxesBroadband:
     def __init__(self, flux_up=None, flux_dn=None, flux_dn_dir=None):
         self.flux_up, self.flux_dn, self.flux_dn_dir = flux_up, flux_dn, flux_dn_dir
 
+    def heating_rate(self, plev, **kw):
+        """:func:`heating_rate` of the broadband ``flux_up`` / ``flux_dn`` (the total downward flux): ``(nlay, ncol)``."""
+        return heating_rate(self.flux_up, self.flux_dn, plev, **kw)
+
 
 class FluxesByband(FluxesBroadband):
     """``ty_fluxes_byband``: bnd_flux_up, bnd_flux_dn (nband,nlay+1,ncol in numpy order) [+ bnd_flux_dn_dir],
@@ -1128,6 +1140,11 @@ class FluxesByband(FluxesBroadband):
     def __init__(self, bnd_flux_up, bnd_flux_dn, bnd_flux_dn_dir=None, flux_up=None, flux_dn=None, flux_dn_dir=None):
         super().__init__(flux_up, flux_dn, flux_dn_dir)
         self.bnd_flux_up, self.bnd_flux_dn, self.bnd_flux_dn_dir = bnd_flux_up, bnd_flux_dn, bnd_flux_dn_dir
+
+    def bnd_heating_rate(self, plev, **kw):
+        """:func:`heating_rate` of the by-band ``bnd_flux_up`` / ``bnd_flux_dn``, one plane per band: ``(nband, nlay, ncol)``
+        (``heating_rate`` of the parent serves the broadband members)."""
+        return heating_rate(self.bnd_flux_up, self.bnd_flux_dn, plev, **kw)
 
 
 # ------------------------------------------------------------------------------------------
@@ -2037,3 +2054,54 @@ def rte_sw(optical_props, top_at_1, mu0, toa_flux, sfc_alb_dir, sfc_alb_dif, flu
         P(fluxes.flux_dn, (nlay + 1, ncol), "flux_dn"),
         P(fluxes.flux_dn_dir, (nlay + 1, ncol), "flux_dn_dir"), space, _stream(space))
     return last_error() if rc else ""
+
+
+# ------------------------------------------------------------------------------------------
+# heating rates (include/ecckd_hip.h, "Heating rates")
+# ------------------------------------------------------------------------------------------
+GRAV, CP_DRY = 9.80665, 1004.64   # m s-2, J kg-1 K-1: the customary constants; arguments of every call, not library state
+
+
+def heating_rate(flux_up, flux_dn, plev, heating_rate=None, cp=None, grav=GRAV, cp_dry=CP_DRY, device=None):
+    """``ecckd_heating_rate`` (RTE-RRTMGP's ``compute_heating_rate``): the divergence of the net flux across each layer as a
+    temperature tendency in K s-1, ``(dnet * grav) / (c * dp)`` operation by operation as include/ecckd_hip.h spells it.
+    ``flux_up``, ``flux_dn``: ``(nlay+1, ncol)`` or ``(nouter, nlay+1, ncol)`` -- the by-band fluxes, or any stack of flux
+    sets; for shortwave ``flux_dn`` is the total, direct beam included.  ``plev``: ``(nlay+1, ncol)``, shared by the planes.
+    ``cp``: ``(nlay, ncol)`` specific heat per cell, replacing ``cp_dry``.  ``heating_rate``: ``(nlay, ncol)`` or
+    ``(nouter, nlay, ncol)``; allocated like ``flux_up`` when not given; it must not alias an input.  There is no
+    ``top_at_1``: the expression does not depend on the orientation.  numpy arrays (staged), torch device tensors
+    (asynchronous on the current stream, capturable), or numpy inputs with a device ``heating_rate``.  float32 arrays take
+    the ``_f32`` call (``grav`` and ``cp_dry`` are rounded to float once); mixed precisions are refused.
+    Returns ``(error_message, heating_rate)``, the message '' on success."""
+    who = "heating_rate"
+    if getattr(flux_up, "ndim", 0) not in (2, 3):
+        return who + ": flux_up must be (nlay+1, ncol) or (nouter, nlay+1, ncol)", heating_rate
+    nlev, ncol = (int(n) for n in flux_up.shape[-2:])
+    outer = tuple(int(n) for n in flux_up.shape[:-2])
+    nouter, nlay = (outer[0] if outer else 1), nlev - 1
+    if nlay < 1 or ncol < 1 or nouter < 1:
+        return who + ": flux_up has shape %s: at least two levels, one column and one plane are needed" % (tuple(flux_up.shape),), heating_rate
+    named = (("flux_up", flux_up), ("flux_dn", flux_dn), ("plev", plev), ("cp", cp), ("heating_rate", heating_rate))
+    f32, err = _call_precision(who, named)
+    if err:
+        return err, heating_rate
+    try:
+        inputs = [flux_up, flux_dn, plev, cp]
+        space = _space_of(inputs)
+        if heating_rate is None:
+            heating_rate = _empty_like_space(outer + (nlay, ncol), flux_up)
+        elif _space_of([heating_rate]) != space:
+            if space != HOST:
+                raise TypeError("mixing host and device arrays in one call")
+            space = MIXED   # host inputs, a device result
+        ptrs = [_ptr(flux_up, outer + (nlev, ncol), "flux_up", f32), _ptr(flux_dn, outer + (nlev, ncol), "flux_dn", f32),
+                _ptr(plev, (nlev, ncol), "plev", f32)]
+        cpp = _ptr(cp, (nlay, ncol), "cp", f32)
+        out = _ptr(heating_rate, outer + (nlay, ncol), "heating_rate", f32)
+    except (TypeError, ValueError) as e:
+        return who + ": " + str(e), heating_rate
+    if device is None:
+        device = _device_of(heating_rate if space == MIXED else flux_up)
+    rc = (lib().ecckd_heating_rate_f32 if f32 else lib().ecckd_heating_rate)(
+        int(device), ncol, nlay, nouter, *ptrs, float(grav), float(cp_dry), cpp, out, space, _stream(space))
+    return (last_error() if rc else ""), heating_rate

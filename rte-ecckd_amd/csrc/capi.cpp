@@ -3622,6 +3622,55 @@ int ecckd_aerosol_optics_f32(const ecckd_aerosol_optics_t *ao, int ncol, int nla
                              dp(tau), dp(ssa), dp(g), memspace, stream);
 }
 
+// ---- heating rates (kernels_heating_rate.hip): flux divergence to K s-1 ----
+
+static int heating_rate_impl(bool f32, int device, int ncol, int nlay, int nouter, const double *flux_up, const double *flux_dn,
+                             const double *plev, double grav, double cp_dry, const double *cp, double *heating_rate, int memspace,
+                             void *stream) {
+  if (ncol < 1 || nlay < 1 || nouter < 1) return fail("ecckd_heating_rate: ncol, nlay and nouter must be at least 1");
+  if (!flux_up || !flux_dn || !plev || !heating_rate)
+    return fail("ecckd_heating_rate: null argument (flux_up, flux_dn, plev and heating_rate are required)");
+  if (!(std::isfinite(grav) && grav > 0.)) return fail("ecckd_heating_rate: grav must be finite and positive");
+  if (!cp && !(std::isfinite(cp_dry) && cp_dry > 0.))
+    return fail("ecckd_heating_rate: cp_dry must be finite and positive (or pass cp per cell)");
+  if (memspace != ECCKD_DEVICE && memspace != ECCKD_HOST && memspace != ECCKD_MIXED) return fail("ecckd: bad memspace");
+  if (check_device(device)) return 1;
+  const size_t lev = (size_t)ncol * ((size_t)nlay + 1), lay = (size_t)ncol * nlay;
+  ecckd::HeatingRateArgs a{};
+  a.ncol = ncol; a.nlay = nlay; a.nouter = nouter; a.f32 = f32;
+  a.cus = simd_slots(device) / 4;
+  if (f32) {   // the constants rounded to float once
+    a.grav = (float)grav; a.cp_dry = (float)cp_dry;
+  } else {
+    a.grav = grav; a.cp_dry = cp_dry;
+  }
+  Stage st(device, memspace, stream, f32);
+  if (st.open([&] {
+        a.flux_up = st.in(flux_up, lev * nouter); a.flux_dn = st.in(flux_dn, lev * nouter); a.plev = st.in(plev, lev);
+        a.cp = st.in(cp, lay);
+        a.heating_rate = st.out(heating_rate, lay * nouter, kBig);
+      }))
+    return 1;
+  {
+    ProfScope prof("heating_rate", st.stream);
+    HIPCHK(ecckd::launch_heating_rate(a, st.stream));
+  }
+  return st.close();
+}
+
+int ecckd_heating_rate(int device, int ncol, int nlay, int nouter, const double *flux_up, const double *flux_dn,
+                       const double *plev, double grav, double cp_dry, const double *cp, double *heating_rate, int memspace,
+                       void *stream) {
+  return heating_rate_impl(false, device, ncol, nlay, nouter, flux_up, flux_dn, plev, grav, cp_dry, cp, heating_rate, memspace,
+                           stream);
+}
+int ecckd_heating_rate_f32(int device, int ncol, int nlay, int nouter, const float *flux_up, const float *flux_dn,
+                           const float *plev, double grav, double cp_dry, const float *cp, float *heating_rate, int memspace,
+                           void *stream) {
+  return heating_rate_impl(true, device, ncol, nlay, nouter, dp(flux_up), dp(flux_dn), dp(plev), grav, cp_dry, dp(cp),
+                           dp(heating_rate), memspace, stream);
+}
+
 // ---- McICA cloud sampling (kernels_cloud_sampling.hip) ----
 
 int ecckd_cloud_mask_sample(int device, int ncol, int nlay, int ngpt, int overlap, const double *cloud_frac,

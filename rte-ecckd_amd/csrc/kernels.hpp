@@ -310,6 +310,20 @@ size_t aerosol_optics_image_bytes(int nband, int nbin, int nrh, bool two_stream,
 unsigned aerosol_optics_grid(int ncol, int nlay, int nspec, int cus, size_t lds_image_bytes);
 hipError_t launch_aerosol_optics(const AerosolOpticsArgs &a, hipStream_t s);
 
+// Heating rates (kernels_heating_rate.hip; the definition is in include/ecckd_hip.h, ecckd_heating_rate): fluxes
+// (ncol,nlay+1,nouter) and pressures (ncol,nlay+1) to the temperature tendency (ncol,nlay,nouter) in K s-1.
+struct HeatingRateArgs {
+  int ncol, nlay, nouter, f32;
+  int cus;                         // compute units of the device (sizes the grid); 0: 256
+  double grav, cp_dry;             // (f32: float values, exactly representable here)
+  const double *flux_up, *flux_dn, *plev;
+  const double *cp;                // (ncol,nlay), or null: cp_dry in every cell
+  double *heating_rate;
+};
+// blocks of 256 threads the call launches: what is resident, at most one block per (256 columns, outer plane)
+unsigned heating_rate_grid(int ncol, int nouter, int cus);
+hipError_t launch_heating_rate(const HeatingRateArgs &a, hipStream_t s);
+
 // McICA cloud mask (kernels_cloud_sampling.hip; the definition is in include/ecckd_hip.h, ecckd_cloud_mask_sample):
 // cloud_frac (ncol,nlay), overlap_param (ncol,nlay-1; exp_ran only), mask (ncol,nlay); 1 <= ngpt <= 64
 hipError_t launch_cloud_mask_sample(int ncol, int nlay, int ngpt, int exp_ran, const double *cloud_frac, const double *overlap_param,
