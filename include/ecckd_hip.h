@@ -1042,6 +1042,97 @@ int ecckd_rte_sw_byband_f32(int device, int ncol, int nlay, int ngpt, int top_at
                             float *bnd_flux_dir, float *flux_up, float *flux_dn, float *flux_dir, int memspace, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Fused per-band fluxes: ty_fluxes_byband from the fused path -- clear sky, all-sky and McICA, longwave and shortwave.
+ * The fused calls above return broadband fluxes; band fluxes (surface shortwave by band, outgoing longwave by band) were
+ * to be had only from ecckd_rte_lw_byband / ecckd_rte_sw_byband, over per-g-point arrays the host holds.  These two calls
+ * take the arguments of the fused calls and return
+ *     bnd_flux_*(ncol,nlay+1,nband):  plane b = sum over the model's g-points band2gpt(1,b)..band2gpt(2,b),  nband =
+ *                                     ecckd_model_get_nband; required (shortwave: bnd_flux_dir may be NULL),
+ *     flux_up / flux_dn / flux_dir (ncol,nlay+1), each optional (NULL): the sum of the band planes in band order, made by
+ *                                     the kernel behind ecckd_rte_*_byband -- the broadband members of a by-band call, NOT
+ *                                     the bits of ecckd_lw_fluxes / ecckd_sw_fluxes, which add the g-points in one chain
+ *                                     (the two agree to rounding).  flux_dir needs bnd_flux_dir, as in ecckd_rte_sw_byband.
+ * Argument order: head, gases, boundary, particles, mask, outputs, memspace, stream.  Particles: nband_p = 0 with NULL
+ * planes and NULL cloud_mask is the clear sky; nband_p = the model's band count is the all sky -- longwave tau_p with ssa_p
+ * (absorption optical depth) or ssa_p NULL (one-stream particles) as ecckd_lw_fluxes_allsky, shortwave the triple tau_p,
+ * ssa_p, g_p with delta_scale 0 / 1 (a library-owned copy is scaled) as ecckd_sw_fluxes_allsky; cloud_mask (ncol,nlay)
+ * words or NULL as the *_mcica calls.  Inputs are never written.  fp64, fast arithmetic mode, ECCKD_DEVICE (asynchronous
+ * on `stream`: one linear sequence of launches, no other stream, no atomics on global memory) or ECCKD_HOST.
+ *
+ * Routes.  Gas optics writes the optical depth into the stream's scratch block exactly as in the broadband fused calls;
+ * then the solver the broadband call takes for the shape runs on BAND WINDOWS: a work unit solves the g-points of one band,
+ * formed into groups from the band's first g-point as a launch over that band's planes alone forms them, and whatever lives
+ * on the model's g-points (optical depth, Planck / solar / Rayleigh tables, inc_flux, the band planes, the mask bit) is read
+ * at the model's g-point.
+ *   Longwave, 60 layers (the Planck table fits LDS): ONE launch for all bands, grid (column tiles, band), of the
+ *     Planck-recomputing layer-split solver in its band-window form (rte_lw_split_bands_kernel: clear, one- / two-stream
+ *     particles, masked); a block stages the window's columns of the Planck table only.  No source array exists in memory.
+ *   Longwave, any other layer count: the general route of ecckd_lw_fluxes -- Planck sources into scratch, the (masked)
+ *     by-band increment in place on the scratch optical depth -- then the register-resident solver ONCE PER BAND on that
+ *     band's planes (the padded 32..96-layer variants, the ring beyond 96 layers; a window is a pointer and a count there,
+ *     the kernels are the parent's).
+ *   Shortwave: ONCE PER BAND, the solver ecckd_sw_fluxes_allsky takes for the shape (layer-systolic up to 60 layers,
+ *     two-pass beyond or with "sw_solver" = 1) on the band's planes of the optical depth and the band's entries of the two
+ *     tables, each launch with the tail plan of its own g-point count (the plans do not change a bit); with a mask the
+ *     band-window forms of the McICA kernels (rte_sw_sys_mcica_bands_kernel, rte_sw_mcica_bands_kernel), which read bit
+ *     (band's first g-point + g).  No per-g-point ssa, g or source array exists in memory.
+ * Measured (one MI355X, tools/bench_flux_bands.py, profiles/flux_bands.json), against the composed
+ * by-band route / against the broadband fused call of the same variant: longwave 16 bands x 36 g, 60 layers (one launch)
+ * 1.17-1.29x faster with particles or a mask, 1.06x (1e5 columns) and 0.97x (1e6: NOT faster) in clear sky / 1.33-1.47x the
+ * broadband call; longwave 137 layers (per band) 0.88-0.89x: SLOWER than the composed route / 1.50-1.61x; shortwave 5 bands x
+ * 27 g (per band) 60 layers 1.19-1.41x faster / 1.13-1.30x, 137 layers 1.00-1.07x / 1.17-1.20x.
+ *
+ * What the planes equal.  Longwave, every variant: the route ecckd_gas_optics_lw -> [ecckd_increment(_masked) by band] ->
+ * ecckd_rte_lw_byband BIT FOR BIT (with inc_flux: ecckd_rte_lw_inc_flux on each band's planes).  Shortwave clear sky without
+ * toa_scale: ecckd_gas_optics_sw -> ecckd_rte_sw_byband bit for bit.  Shortwave all-sky, McICA or with toa_scale: that route
+ * with ecckd_delta_scale / ecckd_increment(_masked) in between, to rounding (ssa is formed in a different order, as in
+ * ecckd_sw_fluxes_allsky; tests/test_gpu_flux_bands.py holds 1e-9 * max(1, max|flux_dn|)).  A model with one band: plane 0
+ * and the broadband members are the bits of ecckd_lw_fluxes / ecckd_lw_fluxes_allsky[_mcica].
+ *
+ * Scratch (ECCKD_DEVICE; a host that owns the stream's block sizes it so; capture after one warm-up call on the stream, or
+ * with a caller-owned block):
+ *   ecckd_lw_flux_bands_scratch_bytes(model, ncol, nlay): what ecckd_lw_fluxes takes -- (ncol*nlay*ngpt + 32)*8 bytes at 60
+ *     layers; on the general route (4*ncol*nlay*ngpt + ncol*ngpt + 64)*8 + ecckd_rte_lw_scratch_bytes(ncol, nlay, ngpt).
+ *   ecckd_sw_flux_bands_scratch_bytes(model, ncol, nlay, delta_scale): the block of ecckd_sw_fluxes_allsky,
+ *     align256(ncol*nlay*ngpt*8) + S + (delta_scale ? 3*align256(ncol*nlay*nband*8) : 0), in that order, where S is the
+ *     largest solver term (ecckd_sw_fluxes: the tail scratch of the layer-systolic solver, else the larger of ring and tail
+ *     scratch) over ngpt and the g-point counts of the bands: a band's launch plans its tail for its own count, and a plan
+ *     a wide launch declines a narrow one may take.  Where the term of ngpt is the largest the block is exactly
+ *     that of ecckd_sw_fluxes_allsky.
+ *   Both return 0 for ncol <= 0, nlay <= 0 or a NULL model; nothing is added for band output (the planes are the caller's).
+ *
+ * Refused with a message that begins with the call's name, before any device is asked for, in this order: NULL model; a
+ * cloud_mask with a model of more than 64 g-points; nband_p neither 0 nor the model's band count; nband_p > 0 with a
+ * required plane NULL (longwave tau_p; shortwave any of the triple); nband_p = 0 with a plane or cloud_mask given;
+ * [shortwave] delta_scale outside {0,1}; reference-order arithmetic mode; a model without a Planck table (longwave) /
+ * without a solar table (shortwave); [longwave] tlev NULL; [longwave] n_gauss_angles outside 1..4; bnd_flux_up or
+ * bnd_flux_dn NULL; [shortwave] flux_dir without bnd_flux_dir; two outputs that are the same array; a memspace other than
+ * ECCKD_DEVICE / ECCKD_HOST (ECCKD_MIXED included); a model that is not finalized; a host-only model; then bad ncol / nlay
+ * and NULL inputs.
+ *
+ * Out of scope: single precision; the rescaled and two-stream longwave solvers and the Jacobian by band; both skies in one
+ * by-band call; ecckd_sw_fluxes_daylit by band; band output restricted to the surface and the top (a host slices the
+ * planes); ecckd_rte_lw_byband / ecckd_rte_sw_byband themselves, which stay as they are; one launch for all bands on the
+ * general longwave route and in the shortwave.
+ * --------------------------------------------------------------------------------------- */
+size_t ecckd_lw_flux_bands_scratch_bytes(const ecckd_model_t *model, int ncol, int nlay);
+int ecckd_lw_flux_bands(const ecckd_model_t *model, int ncol, int nlay, const double *plev, const double *tlay,
+                        const double *tsfc, const double *tlev, int ngas, const char *gas_names,
+                        const double *const *vmr, const long long *vmr_col_stride, const long long *vmr_lay_stride,
+                        const double *vmr_scalar, int top_at_1, int n_gauss_angles, const double *sfc_emis,
+                        const double *inc_flux, int nband_p, const double *tau_p, const double *ssa_p,
+                        const unsigned long long *cloud_mask, double *bnd_flux_up, double *bnd_flux_dn, double *flux_up,
+                        double *flux_dn, int memspace, void *stream);
+size_t ecckd_sw_flux_bands_scratch_bytes(const ecckd_model_t *model, int ncol, int nlay, int delta_scale);
+int ecckd_sw_flux_bands(const ecckd_model_t *model, int ncol, int nlay, const double *plev, const double *tlay, int ngas,
+                        const char *gas_names, const double *const *vmr, const long long *vmr_col_stride,
+                        const long long *vmr_lay_stride, const double *vmr_scalar, int top_at_1, const double *mu0,
+                        const double *toa_scale, const double *sfc_alb_dir, const double *sfc_alb_dif, int nband_p,
+                        const double *tau_p, const double *ssa_p, const double *g_p, int delta_scale,
+                        const unsigned long long *cloud_mask, double *bnd_flux_up, double *bnd_flux_dn, double *bnd_flux_dir,
+                        double *flux_up, double *flux_dn, double *flux_dir, int memspace, void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * Cloud optics: liquid and ice water paths and effective radii per (column, layer) to the particulate properties on the
  * model's bands -- the planes the all-sky calls above take as tau_p, ssa_p, g_p (or op2 of ecckd_increment).  A host model
  * carries water paths and radii, not optical properties; this is the step between them.  The reference's drivers have no

@@ -102,12 +102,14 @@ RFMIP_SW = os.path.join(FORTRAN_BUILD, "ecckd_rfmip_sw")
 CLOUD_DRIVER = os.path.join(FORTRAN_BUILD, "ecckd_cloud_driver")
 AEROSOL_DRIVER = os.path.join(FORTRAN_BUILD, "ecckd_aerosol_driver")
 HEATING_DRIVER = os.path.join(FORTRAN_BUILD, "ecckd_heating_driver")
+BANDS_DRIVER = os.path.join(FORTRAN_BUILD, "ecckd_bands_driver")
 _FORTRAN_MODULES = ["mo_rte_min.F90", "mo_ecckd_device.F90", "gas_optics_ecckd.F90", "mo_rte_solvers.F90", "rfmip_support.F90",
                     "mo_cloud_optics.F90", "mo_aerosol_optics.F90", "mo_heating_rates.F90"]
 _FORTRAN_PROGRAMS = [("ecckd_driver", "ecckd_driver.F90", []), ("ecckd_rfmip_lw", "ecckd_rfmip.F90", []),
                      ("ecckd_rfmip_sw", "ecckd_rfmip.F90", ["-DSHORTWAVE"]), ("ecckd_cloud_driver", "ecckd_cloud_driver.F90", []),
                      ("ecckd_aerosol_driver", "ecckd_aerosol_driver.F90", []),
-                     ("ecckd_heating_driver", "ecckd_heating_driver.F90", [])]
+                     ("ecckd_heating_driver", "ecckd_heating_driver.F90", []),
+                     ("ecckd_bands_driver", "ecckd_bands_driver.F90", [])]
 
 
 def build_fortran(force=False, verbose=False):
@@ -167,7 +169,10 @@ def _fused_prototypes():
     mask = ptrs("cloud_mask")
     lw_out, lw_clear, jac = ptrs("flux_up", "flux_dn"), ptrs("flux_up_clear", "flux_dn_clear"), ptrs("flux_up_jac")
     sw_out, sw_clear = ptrs("flux_up", "flux_dn", "flux_dn_dir"), ptrs("flux_up_clear", "flux_dn_clear", "flux_dn_dir_clear")
-    return {"ecckd_lw_fluxes": lw + lw_bound + lw_out + tail,
+    lw_bands, sw_bands = ptrs("bnd_flux_up", "bnd_flux_dn"), ptrs("bnd_flux_up", "bnd_flux_dn", "bnd_flux_dn_dir")
+    return {"ecckd_lw_flux_bands": lw + lw_bound + lw_part + mask + lw_bands + lw_out + tail,
+            "ecckd_sw_flux_bands": sw + sw_bound + sw_part + mask + sw_bands + sw_out + tail,
+            "ecckd_lw_fluxes": lw + lw_bound + lw_out + tail,
             "ecckd_lw_fluxes_allsky": lw + lw_bound + lw_part + lw_out + tail,
             "ecckd_lw_fluxes_allsky_mcica": lw + lw_bound + lw_part + mask + lw_out + tail,
             "ecckd_lw_fluxes_clear_allsky": lw + lw_bound + lw_part + mask + lw_out + lw_clear + tail,
@@ -239,6 +244,11 @@ def lib():
         L.ecckd_lw_fluxes_f32_scratch_bytes.argtypes = [C.c_void_p, C.c_int, C.c_int]
         L.ecckd_sw_fluxes_allsky_f32_scratch_bytes.restype = C.c_size_t
         L.ecckd_sw_fluxes_allsky_f32_scratch_bytes.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
+    if hasattr(L, "ecckd_lw_flux_bands_scratch_bytes"):   # (an older build lacks them: tools/bench_flux_bands.py --parent-lib)
+        L.ecckd_lw_flux_bands_scratch_bytes.restype = C.c_size_t
+        L.ecckd_lw_flux_bands_scratch_bytes.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        L.ecckd_sw_flux_bands_scratch_bytes.restype = C.c_size_t
+        L.ecckd_sw_flux_bands_scratch_bytes.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
     if hasattr(L, "ecckd_daylit_columns"):   # (an older build lacks them: tools/bench_sw_daylit.py times the parent's library)
         for f in ("ecckd_daylit_columns", "ecckd_daylit_columns_f32"):
             getattr(L, f).argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_void_p, C.POINTER(C.c_int), C.c_int, C.c_void_p]
@@ -1151,7 +1161,7 @@ class FluxesByband(FluxesBroadband):
 # argument groups of the fused calls (GasOpticsEcckd._fused).  A group is a tuple of slots in the order of the C argument
 # list: an int goes through as it is, ``(name, array, shape)`` becomes the array's data pointer, checked against the shape
 # ------------------------------------------------------------------------------------------
-_LEV, _LAY, _COL, _BAND, _GPT, _PART, _SPEC = range(7)   # (shape: an index into the tuple that _fused makes)
+_LEV, _LAY, _COL, _BAND, _GPT, _PART, _SPEC, _BANDLEV = range(8)   # (shape: an index into the tuple that _fused makes)
 
 
 def _lw_groups(plev, tlay, tsfc, tlev, top_at_1, n_gauss_angles, sfc_emis, inc_flux):
@@ -1433,7 +1443,7 @@ class GasOpticsEcckd:
         nlay, ncol = head[1][1].shape   # (tlay)
         ng = self.get_ngpt()
         shapes = ((nlay + 1, ncol), (nlay, ncol), (ncol,), (ncol, self.get_nband()), (ng, ncol),
-                  (particles[0] if particles else 0, nlay, ncol), (ng, nlay, ncol))
+                  (particles[0] if particles else 0, nlay, ncol), (ng, nlay, ncol), (self.get_nband(), nlay + 1, ncol))
         slots = {"head": head, "boundary": boundary, "particles": particles, "outputs": outputs}
         args = {}
         group = returns[0] if returns else _FUSED_CHECKS[0]
@@ -1713,6 +1723,61 @@ class GasOpticsEcckd:
         return self._fused(lib().ecckd_sw_fluxes_f32 if f32 else lib().ecckd_sw_fluxes, f32, (), gas_desc,
                            outputs=_flux_slots(fluxes, dn_dir=True),
                            **_sw_groups(plev, tlay, top_at_1, mu0, toa_scale, sfc_alb_dir, sfc_alb_dif))
+
+    def _flux_bands(self, who, fn, gas_desc, groups, part, cloud_mask, fluxes, dn_dir):
+        """``ecckd_lw_flux_bands`` / ``ecckd_sw_flux_bands`` behind ``lw_fluxes_byband`` / ``sw_fluxes_byband``: every wrong
+        array is answered with a message and never reaches the library."""
+        if not isinstance(fluxes, FluxesByband):
+            return who + ": fluxes must be a FluxesByband (bnd_flux_up and bnd_flux_dn; the broadband members are optional)"
+        bands = (("bnd_flux_up", fluxes.bnd_flux_up, _BANDLEV), ("bnd_flux_dn", fluxes.bnd_flux_dn, _BANDLEV))
+        if dn_dir:
+            bands += (("bnd_flux_dn_dir", fluxes.bnd_flux_dn_dir, _BANDLEV),)
+        out = bands + _flux_slots(fluxes, dn_dir=dn_dir)
+        f32, mixed = _call_precision(who, _named(groups["head"], groups["boundary"], part, out))
+        if mixed:
+            return mixed
+        if f32:
+            return _f64_only(who, "per-band output from the fused path")
+        return self._fused(fn, False, ("gas", "particles", "mask", "outputs", "head", "boundary"), gas_desc, particles=part,
+                           mask=(cloud_mask,), outputs=out, **groups)
+
+    def lw_fluxes_byband(self, plev, tlay, tsfc, tlev, gas_desc, top_at_1, sfc_emis, fluxes, n_gauss_angles=1, inc_flux=None,
+                         particles=None, cloud_mask=None):
+        """``ecckd_lw_flux_bands``: ``lw_fluxes`` / ``lw_fluxes_allsky`` with per-band output.  ``fluxes`` is a
+        ``FluxesByband``: ``bnd_flux_up`` / ``bnd_flux_dn`` ``(nband, nlay+1, ncol)`` receive, per band of the model, the sum
+        over the band's g-points -- bit for bit what ``gas_optics`` + [``increment(particles, band2gpt[, cloud_mask])``] +
+        ``rte_lw`` with a ``FluxesByband`` give, without the host owning a per-g-point array; its ``flux_up`` / ``flux_dn``,
+        where given, receive the sum of the planes in band order.  ``particles``: None (clear sky), an ``OpticalProps2str``
+        (absorption optical depth) or an ``OpticalProps1scl`` on the model's bands; ``cloud_mask`` ``(nlay, ncol)`` with
+        particles only.  float64, fast arithmetic mode; numpy or device tensors.  Returns the error message ('' = success)."""
+        ptau = None if particles is None else particles.tau
+        ssa = None if particles is None else getattr(particles, "ssa", None)
+        return self._flux_bands("lw_fluxes_byband", lib().ecckd_lw_flux_bands, gas_desc,
+                                _lw_groups(plev, tlay, tsfc, tlev, top_at_1, n_gauss_angles, sfc_emis, inc_flux),
+                                _particle_slots(ptau, ssa), cloud_mask, fluxes, False)
+
+    def sw_fluxes_byband(self, plev, tlay, gas_desc, top_at_1, mu0, sfc_alb_dir, sfc_alb_dif, fluxes, particles=None,
+                         delta_scale=True, toa_scale=None, cloud_mask=None):
+        """``ecckd_sw_flux_bands``: ``sw_fluxes`` / ``sw_fluxes_allsky`` with per-band output.  ``fluxes`` is a
+        ``FluxesByband``: ``bnd_flux_up`` / ``bnd_flux_dn`` / ``bnd_flux_dn_dir`` (optional) ``(nband, nlay+1, ncol)``; its
+        broadband members, where given, receive the sum of the planes in band order (``flux_dn_dir`` needs
+        ``bnd_flux_dn_dir``).  Clear sky without ``toa_scale``: the bits of ``gas_optics`` + ``rte_sw`` with a
+        ``FluxesByband``; with ``particles`` (an ``OpticalProps2str`` on the model's bands; ``delta_scale``: a library-owned
+        copy is scaled), ``cloud_mask`` or ``toa_scale``: that composition to rounding, as ``sw_fluxes_allsky``.  float64, fast
+        arithmetic mode; numpy or device tensors.  Returns the error message ('' = success)."""
+        triple = (None, None, None) if particles is None else (particles.tau, getattr(particles, "ssa", None),
+                                                                getattr(particles, "g", None))
+        return self._flux_bands("sw_fluxes_byband", lib().ecckd_sw_flux_bands, gas_desc,
+                                _sw_groups(plev, tlay, top_at_1, mu0, toa_scale, sfc_alb_dir, sfc_alb_dif),
+                                _particle_slots(*triple) + (int(bool(delta_scale)),), cloud_mask, fluxes, True)
+
+    def lw_flux_bands_scratch_bytes(self, ncol, nlay):
+        """``ecckd_lw_flux_bands_scratch_bytes``: the stream scratch of ``lw_fluxes_byband`` on device tensors."""
+        return int(lib().ecckd_lw_flux_bands_scratch_bytes(self._need(), int(ncol), int(nlay)))
+
+    def sw_flux_bands_scratch_bytes(self, ncol, nlay, delta_scale=True):
+        """``ecckd_sw_flux_bands_scratch_bytes``: the stream scratch of ``sw_fluxes_byband`` on device tensors."""
+        return int(lib().ecckd_sw_flux_bands_scratch_bytes(self._need(), int(ncol), int(nlay), int(bool(delta_scale))))
 
     def sw_fluxes_daylit(self, plev, tlay, gas_desc, top_at_1, mu0, sfc_alb_dir, sfc_alb_dif, fluxes, particles=None,
                          fluxes_clear=None, delta_scale=True, toa_scale=None, cloud_mask=None, day_index=None, mu0_min=0.0):

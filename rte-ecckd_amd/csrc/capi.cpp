@@ -191,6 +191,7 @@ struct SwDerive {
   const double *plev, *rayleigh, *solar, *toa_scale; double gw; double *room;
   const double *part_tau = nullptr, *part_ssa = nullptr, *part_g = nullptr;
   const unsigned long long *part_mask = nullptr;   // ecckd_sw_fluxes_allsky_mcica (RteSwArgs::part_mask), or null
+  int mask_first = -1;                             // ecckd_sw_flux_bands: >= 0, the model's g-point of the launch's first (RteSwArgs::mask_first)
 };
 // What a public entry point asks of the solver implementations besides its arguments.
 struct Call {
@@ -1757,6 +1758,7 @@ static int rte_sw_impl(const Call &c, int device, int ncol, int nlay, int ngpt, 
     a.plev = dv->plev; a.rayleigh = dv->rayleigh; a.solar = dv->solar; a.gw = dv->gw;
     a.toa_scale = dv->toa_scale;
     if (dv->part_tau) { a.allsky = 1; a.part_tau = dv->part_tau; a.part_ssa = dv->part_ssa; a.part_g = dv->part_g; a.part_mask = dv->part_mask; }
+    if (dv->part_mask && dv->mask_first >= 0) { a.mask_window = 1; a.mask_first = dv->mask_first; }
   }
   Stage st(device, memspace, stream, c.f32);
   ScratchLease lease;   // (held until the kernels of this call have been launched)
@@ -3899,6 +3901,237 @@ int ecckd_rte_sw_byband_f32(int device, int ncol, int nlay, int ngpt, int top_at
   return rte_sw_byband_impl(true, device, ncol, nlay, ngpt, top_at_1, dp(tau), dp(ssa), dp(g), dp(mu0), dp(toa_flux), nband,
                             band2gpt, dp(sfc_alb_dir), dp(sfc_alb_dif), dp(bnd_flux_up), dp(bnd_flux_dn), dp(bnd_flux_dir),
                             dp(flux_up), dp(flux_dn), dp(flux_dir), memspace, stream);
+}
+
+// ---- per-band fluxes from the fused path (include/ecckd_hip.h, "Fused per-band fluxes") ----
+
+// first[b] = first 0-based g-point of band b, first[nband] = ngpt; the bands must tile 1..ngpt in ascending order
+static int band_windows(const ecckd_model *m, const char *who, unsigned short *first) {
+  int next = 1;
+  for (int b = 0; b < m->nband; ++b) {
+    if (m->band2gpt[2 * b] != next || m->band2gpt[2 * b + 1] < next)
+      return fail(std::string(who) + ": the model's band2gpt does not tile 1..ngpt in ascending order");
+    first[b] = (unsigned short)(next - 1);
+    next = m->band2gpt[2 * b + 1] + 1;
+  }
+  if (next != m->ng + 1) return fail(std::string(who) + ": the model's band2gpt does not tile 1..ngpt in ascending order");
+  first[m->nband] = (unsigned short)m->ng;
+  return 0;
+}
+
+// The refusals the two calls share, in the order of the header; `planes_missing`: a particulate plane the call requires
+// with nband_p = nband is NULL, `planes_given`: any plane is not NULL.
+static int flux_bands_refusals(const std::string &who, const ecckd_model *m, int nband_p, bool planes_missing, bool planes_given,
+                               const unsigned long long *cloud_mask, const char *missing_text) {
+  if (!m) return fail(who + ": null model");
+  if (cloud_mask && m->ng > 64) return fail(who + std::string(kMaskTooWide) + std::to_string(m->ng));
+  if (nband_p != 0 && nband_p != m->nband)
+    return fail(who + ": nband_p = " + std::to_string(nband_p) + " but the model has " + std::to_string(m->nband) +
+                " bands (particulate properties live on the model's bands; 0: clear sky)");
+  if (nband_p != 0 && planes_missing) return fail(who + missing_text);
+  if (nband_p == 0 && (planes_given || cloud_mask))
+    return fail(who + ": nband_p = 0 is the clear sky: the particulate planes and cloud_mask must be null");
+  return 0;
+}
+
+static int flux_bands_outputs_alias(const std::string &who, std::initializer_list<const double *> outs) {
+  for (auto p = outs.begin(); p != outs.end(); ++p)
+    for (auto q = p + 1; q != outs.end(); ++q)
+      if (*p && *p == *q) return fail(who + ": two outputs are the same array (each needs an array of its own)");
+  return 0;
+}
+
+size_t ecckd_lw_flux_bands_scratch_bytes(const ecckd_model_t *m, int ncol, int nlay) {
+  if (!m || ncol <= 0 || nlay <= 0) return 0;
+  return ((size_t)ncol * nlay * m->ng + 32 + fused_scratch_doubles(m, ncol, nlay)) * sizeof(double);
+}
+
+int ecckd_lw_flux_bands(const ecckd_model_t *m, int ncol, int nlay, const double *plev, const double *tlay, const double *tsfc,
+                        const double *tlev, int ngas, const char *gas_names, const double *const *vmr,
+                        const long long *vmr_col_stride, const long long *vmr_lay_stride, const double *vmr_scalar, int top_at_1,
+                        int n_gauss_angles, const double *sfc_emis, const double *inc_flux, int nband_p, const double *tau_p,
+                        const double *ssa_p, const unsigned long long *cloud_mask, double *bnd_flux_up, double *bnd_flux_dn,
+                        double *flux_up, double *flux_dn, int memspace, void *stream) {
+  const std::string who = "ecckd_lw_flux_bands";
+  if (flux_bands_refusals(who, m, nband_p, !tau_p, tau_p || ssa_p, cloud_mask,
+                          ": null argument (tau_p is required with nband_p > 0; ssa_p may be null: one-stream particles)"))
+    return 1;
+  if (g_arith.load() != 0) return fail(who + ": needs the fast arithmetic mode (ecckd_set_arithmetic(0))");
+  if (!m->has_planck) return fail(who + ": model has no Planck table (shortwave model?)");
+  if (!tlev) return fail(who + ": tlev is required for ecckd");
+  if (n_gauss_angles < 1 || n_gauss_angles > 4) return fail(who + ": have to ask for at least one quadrature point and no more than 4");
+  if (!bnd_flux_up || !bnd_flux_dn) return fail(who + ": null argument (bnd_flux_up and bnd_flux_dn are required)");
+  if (flux_bands_outputs_alias(who, {bnd_flux_up, bnd_flux_dn, flux_up, flux_dn})) return 1;
+  if (memspace != ECCKD_DEVICE && memspace != ECCKD_HOST) return fail(who + ": bad memspace (ECCKD_DEVICE or ECCKD_HOST)");
+  if (!m->finalized) return fail(who + ": model is not finalized");
+  if (m->device < 0) return fail(who + ": host-only model (device -1): no GPU, no compute (there is no CPU fallback)");
+  if (check_gas_optics_dims(ncol, nlay)) return 1;
+  if (!plev || !tlay || !tsfc || !sfc_emis || (ngas > 0 && !gas_names)) return fail(who + ": null argument");
+  unsigned short first[257];
+  if (band_windows(m, who.c_str(), first)) return 1;
+  HIPCHK(hipSetDevice(m->device));
+  if (ncol == 0) return 0;
+  const GasDesc gd{ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar};
+  const Counts n(ncol, nlay, m->ng, m->nband);
+  const bool fused = fused_lw_kernels_apply(m, nlay);
+  const size_t extra = fused_scratch_doubles(m, ncol, nlay);
+  Stage st(const_cast<ecckd_model *>(m), memspace, stream, false);
+  const double *d_plev = nullptr, *d_tlay = nullptr, *d_tsfc = nullptr, *d_tlev = nullptr, *d_emis = nullptr, *d_incf = nullptr;
+  double *d_bup = nullptr, *d_bdn = nullptr, *d_up = nullptr, *d_dn = nullptr, *d_tau = nullptr;
+  GasDesc d_gd{};
+  LwParticles d_pt{};
+  if (st.open([&] {
+        d_plev = st.in(plev, n.lev); d_tlay = st.in(tlay, n.lay); d_tsfc = st.in(tsfc, n.col); d_tlev = st.in(tlev, n.lev);
+        d_emis = st.in(sfc_emis, n.col_b); d_incf = st.in(inc_flux, n.col_g);
+        d_gd = st.gases(gd, ncol, nlay);
+        d_pt = LwParticles{st.in(tau_p, n.lay_b), st.in(ssa_p, n.lay_b), st.in(cloud_mask, n.lay)};
+        d_bup = st.out(bnd_flux_up, n.lev * m->nband); d_bdn = st.out(bnd_flux_dn, n.lev * m->nband);
+        d_up = st.out(flux_up, n.lev); d_dn = st.out(flux_dn, n.lev);
+        d_tau = st.work((n.lay_g + 32 + extra) * sizeof(double));
+      }))
+    return 1;
+  const hipStream_t s = st.stream;
+  if (gas_optical_depth_dev(m, false, nullptr, ncol, nlay, d_plev, d_tlay, d_gd, d_tau, false, nullptr, nullptr, nullptr, nullptr, s)) return 1;
+  ecckd::RteLwArgs a{};
+  if (fill_band_map(m->ng, m->nband, m->band2gpt.data(), a.gpt2band)) return 1;
+  a.ncol = ncol; a.nlay = nlay; a.ng = m->ng; a.top_at_1 = top_at_1 ? 1 : 0; a.nband = m->nband;
+  fill_lw_options(a, n_gauss_angles, false);
+  a.tau = d_tau; a.sfc_emis = d_emis; a.inc_flux = d_incf;
+  if (fused) {
+    // 60 layers: the Planck-recomputing layer-split solver in its band-window form, one launch for all bands
+    a.use_split = 1;
+    a.flux_up = d_bup; a.flux_dn = d_bdn;
+    if (d_pt.tau) { a.part_tau = d_pt.tau; a.part_ssa = d_pt.ssa; a.part_1scl = d_pt.ssa ? 0 : 1; a.part_mask = d_pt.mask; }
+    ProfScope prof("rte_lw_fused_bands", s);
+    HIPCHK(ecckd::launch_rte_lw_planck_bands(a, m->dbuf + m->off_planck, m->ntp, m->temperature_planck[0],
+                                             m->temperature_planck[1] - m->temperature_planck[0], d_tlay, d_tlev, d_tsfc, first, s));
+  } else {
+    // general route: Planck sources into scratch, the by-band (masked) increment in place on the scratch optical depth,
+    // then the register-resident solver once per band on that band's planes of the same arrays (a launch of its own:
+    // window = pointer + count, the band told to every g-point of the launch as ecckd_rte_lw_byband does)
+    double *scratch = d_tau + r32(n.lay_g);
+    double *lay = scratch, *inc = lay + n.lay_g, *dec = inc + n.lay_g, *sfc = dec + n.lay_g, *ring = sfc + r32(n.col_g);
+    {
+      ecckd::PlanckArgs p = planck_args(m, ncol, nlay, d_tlay, PlanckSide{d_tlev, d_tsfc, lay, inc, dec, sfc});
+      ProfScope prof("planck", s);
+      HIPCHK(ecckd::launch_planck(p, s));
+    }
+    if (d_pt.tau && lw_increment_dev(m, ncol, nlay, d_tau, d_pt, s)) return 1;
+    a.use_split = 0;
+    a.shared_levels = d_incf ? 0 : 1;
+    a.scratch = ecckd::rte_lw_scratch_bytes(ncol, nlay, m->ng) ? ring : nullptr;
+    ProfScope prof("rte_lw_bands", s);
+    for (int b = 0; b < m->nband; ++b) {
+      const size_t g0 = first[b];
+      ecckd::RteLwArgs w = a;
+      std::memset(w.gpt2band, b, sizeof w.gpt2band);
+      w.ng = first[b + 1] - first[b];
+      w.tau = d_tau + n.lay * g0; w.lay_source = lay + n.lay * g0; w.lev_source_inc = inc + n.lay * g0;
+      w.lev_source_dec = dec + n.lay * g0; w.sfc_source = sfc + n.col * g0;
+      w.inc_flux = d_incf ? d_incf + n.col * g0 : nullptr;
+      w.flux_up = d_bup + n.lev * b; w.flux_dn = d_bdn + n.lev * b;
+      HIPCHK(ecckd::launch_rte_lw(w, s));
+    }
+  }
+  if (d_up) HIPCHK(ecckd::launch_sum_planes(d_bup, m->nband, n.lev, d_up, 0, s));
+  if (d_dn) HIPCHK(ecckd::launch_sum_planes(d_bdn, m->nband, n.lev, d_dn, 0, s));
+  return st.close();
+}
+
+// The shortwave work block: that of ecckd_sw_fluxes_allsky for the shape, the solver's room sized for the widest need of a
+// band's launch (the whole model's where that is larger: the solvers' plans are not monotonic in the g-point count)
+struct SwBandsWork {
+  size_t tau_bytes, solver, plane;
+  SwBandsWork(const ecckd_model *m, int ncol, int nlay, bool scaled_planes) {
+    const SwWork w(m, false, ncol, nlay, scaled_planes);
+    tau_bytes = w.tau_bytes; solver = w.solver; plane = w.plane;
+    for (int b = 0; b < m->nband; ++b) {
+      const size_t need = sw_fluxes_solver_bytes(m->device, ncol, nlay, m->band2gpt[2 * b + 1] - m->band2gpt[2 * b] + 1);
+      if (need > solver) solver = need;
+    }
+  }
+  size_t bytes() const { return tau_bytes + solver + 3 * plane; }
+};
+
+size_t ecckd_sw_flux_bands_scratch_bytes(const ecckd_model_t *m, int ncol, int nlay, int delta_scale) {
+  if (!m || ncol <= 0 || nlay <= 0) return 0;
+  return SwBandsWork(m, ncol, nlay, delta_scale != 0).bytes();
+}
+
+int ecckd_sw_flux_bands(const ecckd_model_t *m, int ncol, int nlay, const double *plev, const double *tlay, int ngas,
+                        const char *gas_names, const double *const *vmr, const long long *vmr_col_stride,
+                        const long long *vmr_lay_stride, const double *vmr_scalar, int top_at_1, const double *mu0,
+                        const double *toa_scale, const double *sfc_alb_dir, const double *sfc_alb_dif, int nband_p,
+                        const double *tau_p, const double *ssa_p, const double *g_p, int delta_scale,
+                        const unsigned long long *cloud_mask, double *bnd_flux_up, double *bnd_flux_dn, double *bnd_flux_dir,
+                        double *flux_up, double *flux_dn, double *flux_dir, int memspace, void *stream) {
+  const std::string who = "ecckd_sw_flux_bands";
+  if (flux_bands_refusals(who, m, nband_p, !tau_p || !ssa_p || !g_p, tau_p || ssa_p || g_p, cloud_mask,
+                          ": null argument (tau_p, ssa_p and g_p are all required with nband_p > 0)"))
+    return 1;
+  if (delta_scale != 0 && delta_scale != 1) return fail(who + ": delta_scale must be 0 or 1");
+  if (g_arith.load() != 0) return fail(who + ": needs the fast arithmetic mode (ecckd_set_arithmetic(0))");
+  if (!m->has_solar) return fail(who + ": model has no solar table (longwave model?)");
+  if (!bnd_flux_up || !bnd_flux_dn) return fail(who + ": null argument (bnd_flux_up and bnd_flux_dn are required; bnd_flux_dir may be null)");
+  if (flux_dir && !bnd_flux_dir) return fail(who + ": flux_dir needs bnd_flux_dir");
+  if (flux_bands_outputs_alias(who, {bnd_flux_up, bnd_flux_dn, bnd_flux_dir, flux_up, flux_dn, flux_dir})) return 1;
+  if (memspace != ECCKD_DEVICE && memspace != ECCKD_HOST) return fail(who + ": bad memspace (ECCKD_DEVICE or ECCKD_HOST)");
+  if (!m->finalized) return fail(who + ": model is not finalized");
+  if (m->device < 0) return fail(who + ": host-only model (device -1): no GPU, no compute (there is no CPU fallback)");
+  if (check_gas_optics_dims(ncol, nlay)) return 1;
+  if (!plev || !tlay || !mu0 || !sfc_alb_dir || !sfc_alb_dif || (ngas > 0 && !gas_names)) return fail(who + ": null argument");
+  unsigned short first[257];
+  if (band_windows(m, who.c_str(), first)) return 1;
+  HIPCHK(hipSetDevice(m->device));
+  if (ncol == 0) return 0;
+  const GasDesc gd{ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar};
+  const Counts n(ncol, nlay, m->ng, m->nband);
+  const bool part = nband_p != 0;
+  const SwBandsWork work(m, ncol, nlay, part && delta_scale);
+  Stage st(const_cast<ecckd_model *>(m), memspace, stream, false);
+  const double *d_plev = nullptr, *d_tlay = nullptr, *d_mu0 = nullptr, *d_scale = nullptr, *d_ad = nullptr, *d_af = nullptr;
+  double *d_bup = nullptr, *d_bdn = nullptr, *d_bdir = nullptr, *d_up = nullptr, *d_dn = nullptr, *d_dir = nullptr, *d_tau = nullptr;
+  GasDesc d_gd{};
+  SwParticles d_pt{};
+  if (st.open([&] {
+        d_plev = st.in(plev, n.lev); d_tlay = st.in(tlay, n.lay); d_mu0 = st.in(mu0, n.col); d_scale = st.in(toa_scale, n.col);
+        d_ad = st.in(sfc_alb_dir, n.col_b); d_af = st.in(sfc_alb_dif, n.col_b);
+        d_gd = st.gases(gd, ncol, nlay);
+        d_pt = SwParticles{st.in(tau_p, n.lay_b), st.in(ssa_p, n.lay_b), st.in(g_p, n.lay_b), delta_scale, st.in(cloud_mask, n.lay)};
+        d_bup = st.out(bnd_flux_up, n.lev * m->nband); d_bdn = st.out(bnd_flux_dn, n.lev * m->nband);
+        d_bdir = st.out(bnd_flux_dir, n.lev * m->nband);
+        d_up = st.out(flux_up, n.lev); d_dn = st.out(flux_dn, n.lev); d_dir = st.out(flux_dir, n.lev);
+        d_tau = st.work(work.bytes());
+      }))
+    return 1;
+  const hipStream_t s = st.stream;
+  char *const room = reinterpret_cast<char *>(d_tau) + work.tau_bytes;
+  if (work.plane) {   // the scaled copy of the band triple, as ecckd_sw_fluxes_allsky makes it
+    double *q_tau = reinterpret_cast<double *>(room + work.solver), *q_ssa = reinterpret_cast<double *>(room + work.solver + work.plane),
+           *q_g = reinterpret_cast<double *>(room + work.solver + 2 * work.plane);
+    ProfScope prof("delta_scale", s);
+    HIPCHK(ecckd::launch_delta_scale(n.lay_b, d_pt.tau, d_pt.ssa, d_pt.g, nullptr, q_tau, q_ssa, q_g, 0, s));
+    d_pt.tau = q_tau; d_pt.ssa = q_ssa; d_pt.g = q_g;
+  }
+  if (gas_optical_depth_dev(m, false, nullptr, ncol, nlay, d_plev, d_tlay, d_gd, d_tau, true, nullptr, nullptr, nullptr, nullptr, s)) return 1;
+  // One solver launch per band on that band's planes of the optical depth, with the band's entries of the Rayleigh and solar
+  // tables: the solver ecckd_sw_fluxes_allsky takes for the shape, told its band as ecckd_rte_sw_byband tells it, and -- with
+  // a mask -- in its band-window form, which reads the mask bit at the model's g-point (SwDerive::mask_first).
+  for (int b = 0; b < m->nband; ++b) {
+    const size_t g0 = first[b];
+    const int count = first[b + 1] - first[b];
+    SwDerive dv{d_plev, table(m, m->off_rayleigh, false) + g0, table(m, m->off_solar, false) + g0, d_scale, gw(false),
+                work.solver ? reinterpret_cast<double *>(room) : nullptr};
+    if (part) { dv.part_tau = d_pt.tau; dv.part_ssa = d_pt.ssa; dv.part_g = d_pt.g; dv.part_mask = d_pt.mask; dv.mask_first = (int)g0; }
+    if (rte_sw_impl(Call{false, b, false, &dv}, m->device, ncol, nlay, count, top_at_1, d_tau + n.lay * g0, nullptr, nullptr, d_mu0,
+                    nullptr, m->nband, nullptr, d_ad, d_af, d_bup + n.lev * b, d_bdn + n.lev * b,
+                    d_bdir ? d_bdir + n.lev * b : nullptr, ECCKD_DEVICE, s))
+      return 1;
+  }
+  if (d_up) HIPCHK(ecckd::launch_sum_planes(d_bup, m->nband, n.lev, d_up, 0, s));
+  if (d_dn) HIPCHK(ecckd::launch_sum_planes(d_bdn, m->nband, n.lev, d_dn, 0, s));
+  if (d_dir) HIPCHK(ecckd::launch_sum_planes(d_bdir, m->nband, n.lev, d_dir, 0, s));
+  return st.close();
 }
 
 }  // extern "C"

@@ -219,6 +219,10 @@ struct RteSwArgs {
   const double *part_tau = nullptr, *part_ssa = nullptr, *part_g = nullptr;
   // McICA (ecckd_sw_fluxes_allsky_mcica): as RteLwArgs::part_mask
   const unsigned long long *part_mask = nullptr;
+  // Band window (ecckd_sw_flux_bands; fp64, with part_mask): the launch covers the g-points mask_first .. mask_first + ng - 1
+  // of the model -- tau, rayleigh, solar and the outputs are that band's own -- and g-point g of the launch sees bit
+  // mask_first + g of the mask word.  mask_window = 0: bit g (the kernels of the calls above).
+  int mask_window = 0, mask_first = 0;
 };
 
 // Two-stream longwave solver (kernels_rte_lw_2str.hip): clouds scatter.  tau / ssa / g / lev_source_* (ncol,nlay,ng),
@@ -418,6 +422,11 @@ hipError_t launch_rte_lw_split(const RteLwArgs &a, hipStream_t s);
 hipError_t launch_rte_lw_planck(const RteLwArgs &a, const double *planck, int ntp, double t0, double dt, const double *tlay,
                                 const double *tlev, const double *tsfc, hipStream_t s, double *flux_up_clear = nullptr,
                                 double *flux_dn_clear = nullptr, double *flux_up_jac = nullptr);
+// ... one output plane per band (ecckd_lw_flux_bands): a.flux_up / a.flux_dn are (ncol,nlay+1,nband), band_first[b] the first
+// 0-based g-point of band b and band_first[nband] = a.ng.  One launch; block row b solves the g-points of band b alone, in
+// the groups a launch over that band's planes would form, and reads everything that lives on g-points at the model's index
+hipError_t launch_rte_lw_planck_bands(const RteLwArgs &a, const double *planck, int ntp, double t0, double dt, const double *tlay,
+                                      const double *tlev, const double *tsfc, const unsigned short *band_first, hipStream_t s);
 // The rescaled no-scattering solver in the layer-split form (fp64, 60 layers): three exchanges per iteration.  a.ssa / a.g
 // beside a.tau and the three source arrays ...
 hipError_t launch_rte_lw_rescaled_split(const RteLwArgs &a, hipStream_t s);

@@ -96,10 +96,11 @@ __host__ __device__ constexpr int planck_stride(int ng) { return ng | 1; }   // 
 // SER3: three-term series; PLANCK: sources recomputed; SKY: 0 gas only, 1 / 2 one- / two-stream particles; MASK: McICA mask;
 // BOTH: clear and all sky; JAC: flux_up_jac; RESC: the rescaled solver; WPS: waves per SIMD the kernel is compiled for.
 template <int SEG_, int NW_, int CW_, bool SHARED_, bool SER3_, bool PLANCK_, int SKY_, bool MASK_, bool BOTH_, bool JAC_, bool RESC_,
-          int WPS_>
+          int WPS_, bool WIN_ = false>
 struct SplitForm {
   static constexpr int SEG = SEG_, NW = NW_, CW = CW_, SKY = SKY_, WPS = WPS_;
   static constexpr bool SHARED = SHARED_, SER3 = SER3_, PLANCK = PLANCK_, MASK = MASK_, BOTH = BOTH_, JAC = JAC_, RESC = RESC_;
+  static constexpr bool WIN = WIN_;                                     // band windows: blockIdx.y is the band (BandsForm)
   static constexpr int NL = SEG * NW;                                   // layers
   static constexpr int GW = 64 / CW;                                    // g-points per wave
   static constexpr int NSKY = BOTH ? 2 : 1;                             // skies per group: [0] the call's own, [1] the clear sky
@@ -119,6 +120,7 @@ struct SplitForm {
   static_assert(!RESC || (!SHARED && !BOTH && (!JAC || PLANCK) && (PLANCK ? SKY == 2 : SKY == 0)),
                 "the rescaled form reads arrays, or recomputes Planck sources and takes a two-stream band triple");
   static_assert(!SHARED || !PLANCK, "shared level sources are a property of the array form");
+  static_assert(!WIN || (PLANCK && !BOTH && !JAC && !RESC), "band windows extend the single-sky Planck-recomputing forms");
 };
 
 // The forms by the template parameters of their kernels
@@ -134,6 +136,9 @@ template <int SEG, int NW, int CW, bool SER3, int WPS>
 using RescaledForm = SplitForm<SEG, NW, CW, false, SER3, false, 0, false, false, false, true, WPS>;
 template <int SEG, int NW, int CW, bool SER3, bool MASK, bool JAC, int WPS>
 using RescaledAllskyForm = SplitForm<SEG, NW, CW, false, SER3, true, 2, MASK, false, JAC, true, WPS>;
+// the band-window form of the clear-sky (SKY = 0), all-sky and McICA kernels (ecckd_lw_flux_bands)
+template <int SEG, int NW, int CW, bool SER3, int SKY, bool MASK, int WPS>
+using BandsForm = SplitForm<SEG, NW, CW, false, SER3, true, SKY, MASK, false, false, false, WPS, true>;
 
 // LDS of a block, in doubles: per group and sky two accumulator planes [NL+1][CW] and the exchange [2][NW][3][64], behind
 // the skies of a group the Jacobian's plane, behind the groups the Planck table [ntp][planck_stride(ng)]
@@ -295,11 +300,19 @@ struct SplitExtra {
   double *flux_up_jac = nullptr;                               // JAC
 };
 
+// The g-point windows of the band form (F::WIN; ecckd_lw_flux_bands): band b covers the 0-based g-points
+// [first[b], first[b + 1]) of the model.  Block (x, b) of the grid solves band b of its tiles: the g-point groups are formed
+// from the band's first g-point, in the order a launch over that band's planes alone forms them, and everything that lives
+// on the model's g-points -- the tau plane, the Planck table, inc_flux, the band map, the mask bit -- is indexed by the
+// model's g-point.  The fluxes go to plane b of a.flux_up / a.flux_dn, (ncol,nlay+1,nband).
+struct BandWindows { unsigned short first[257]; };
+
 template <class F>
 __device__ __forceinline__ void rte_lw_split_body(const RteLwArgs &a, const PlanckTab &pt, const double *tlay, const double *tlev,
-                                                  const double *tsfc, const SplitExtra &out = SplitExtra{}) {
+                                                  const double *tsfc, const SplitExtra &out = SplitExtra{},
+                                                  const BandWindows *bw = nullptr) {
   constexpr int SEG = F::SEG, NW = F::NW, CW = F::CW, GW = F::GW, NL = F::NL, NG = F::NG, PF = F::PF, NSKY = F::NSKY;
-  constexpr bool SHARED = F::SHARED, PLANCK = F::PLANCK, MASK = F::MASK, JAC = F::JAC, RESC = F::RESC;
+  constexpr bool SHARED = F::SHARED, PLANCK = F::PLANCK, MASK = F::MASK, JAC = F::JAC, RESC = F::RESC, WIN = F::WIN;
   constexpr int SKY = F::SKY;
   using Lds = SplitLds<F>;
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
@@ -317,14 +330,29 @@ __device__ __forceinline__ void rte_lw_split_body(const RteLwArgs &a, const Plan
   [[maybe_unused]] double *acc_jac = group + Lds::kAccJac;   // (JAC)
   [[maybe_unused]] const int pstride = PLANCK ? planck_stride(a.ng) : 0;
   [[maybe_unused]] double *ptab = lds + Lds::kTable;            // (PLANCK) [ntp][pstride]
-  if constexpr (PLANCK) {
+  if constexpr (WIN) {   // the window's columns of the table alone, where the whole table has them: staging costs what the band is wide
+    const int first = bw->first[blockIdx.y], count = bw->first[blockIdx.y + 1] - first;
+    for (int i = tid; i < pt.ntp * count; i += F::THREADS) {
+      const int r = i / count, g = first + (i - r * count);
+      ptab[r * pstride + g] = pt.tab[r * pt.ng + g];
+    }
+  } else if constexpr (PLANCK) {
     for (int i = tid; i < pt.ntp * pt.ng; i += F::THREADS) {
       const int r = i / pt.ng, g = i - r * pt.ng;
       ptab[r * pstride + g] = pt.tab[i];
     }
   }
   const int cl = lane % CW, gs = lane / CW;
-  const int ncol = a.ncol, ng = a.ng;
+  // WIN: the block's window [g0, g0 + ng) of the model's g-points and its plane of the outputs; else all of them, plane 0
+  int win_first = 0, win_count = 0;
+  long win_plane = 0;
+  if constexpr (WIN) {
+    win_first = bw->first[blockIdx.y];
+    win_count = bw->first[blockIdx.y + 1] - win_first;
+    win_plane = (long)blockIdx.y * a.ncol * (NL + 1);
+  }
+  // (a.ng is read here, where the forms without windows always read it: their register figures depend on it)
+  const int ncol = a.ncol, ng = WIN ? win_count : a.ng, g0 = win_first;
   const double pi = acos(-1.);
   const double pi_f32 = (double)3.14159265359f, rpi_f32 = 1. / pi_f32;   // src/gas_optics_ecckd.f90:53 (PLANCK)
   const double tau_thresh = a.tau_thresh;
@@ -375,7 +403,7 @@ __device__ __forceinline__ void rte_lw_split_body(const RteLwArgs &a, const Plan
 
     auto pair_start = [&](int it) {
       const int g = (it / a.nmus) * GW + gs;
-      const int gg = g < ng ? g : ng - 1;
+      const int gg = g0 + (g < ng ? g : ng - 1);
       qn = cc + (long)ncol * NL * gg + (long)ncol * (lay0 + lstep * s0);
       asm volatile("" : "+v"(qn));
       if constexpr (PLANCK) {
@@ -426,7 +454,7 @@ __device__ __forceinline__ void rte_lw_split_body(const RteLwArgs &a, const Plan
       const int gi = it / a.nmus, k = it - gi * a.nmus;
       const int g = gi * GW + gs;
       const bool gact = g < ng;
-      const int gg = gact ? g : ng - 1;
+      const int gg = g0 + (gact ? g : ng - 1);
       const double D = a.Ds[k];
       if constexpr (MASK) mbit = gg & 31;   // (pair_start(it + 1), below, moves mhalf on while this iteration's slots are used up)
       const SplitLane L{lane, cl, w, s0, gs == 0, gact ? 2. * pi * a.wts[k] : 0.};
@@ -557,8 +585,8 @@ __device__ __forceinline__ void rte_lw_split_body(const RteLwArgs &a, const Plan
       const long cg = tile * CW + c;
       if (cg < ncol) {
         const long q = cg + (long)ncol * (lev0 + lstep * s);
-        a.flux_dn[q] = acc_dn[0][i];
-        a.flux_up[q] = acc_up[0][i];
+        a.flux_dn[q + win_plane] = acc_dn[0][i];
+        a.flux_up[q + win_plane] = acc_up[0][i];
         if constexpr (F::BOTH) {
           out.flux_dn_clear[q] = acc_dn[1][i];
           out.flux_up_clear[q] = acc_up[1][i];
@@ -632,6 +660,15 @@ __global__ void __launch_bounds__((RescaledAllskyForm<SEG, NW, CW, SER3, MASK, t
 rte_lw_split_rescaled_jac_kernel(const RteLwArgs a, const PlanckTab pt, const double *tlay, const double *tlev, const double *tsfc,
                                  double *flux_up_jac) {
   rte_lw_split_body<RescaledAllskyForm<SEG, NW, CW, SER3, MASK, true, 1>>(a, pt, tlay, tlev, tsfc, SplitExtra{nullptr, nullptr, flux_up_jac});
+}
+
+// The band-window form (ecckd_lw_flux_bands): the clear-sky (SKY = 0), all-sky or McICA kernel on one band of the model per
+// block row; one launch writes every band plane
+template <int SEG, int NW, int CW, bool SER3, int SKY, bool MASK, int WPS>
+__global__ void __launch_bounds__((BandsForm<SEG, NW, CW, SER3, SKY, MASK, WPS>::THREADS), WPS)
+rte_lw_split_bands_kernel(const RteLwArgs a, const PlanckTab pt, const double *tlay, const double *tlev, const double *tsfc,
+                          const BandWindows bw) {
+  rte_lw_split_body<BandsForm<SEG, NW, CW, SER3, SKY, MASK, WPS>>(a, pt, tlay, tlev, tsfc, SplitExtra{}, &bw);
 }
 
 // The fused forms walk 15 layers per wave with 4 waves per group and 32 columns per tile.  Planck-recomputing forms with two
@@ -745,6 +782,39 @@ hipError_t launch_rte_lw_planck(const RteLwArgs &a, const double *planck, int nt
         return launch_form<ClearForm<kSeg, kNW, kCW, false, SER3, true, kPlanckWps>>(rte_lw_split_kernel<kSeg, kNW, kCW, false, SER3, true, kPlanckWps>,
                                                                                      a, pt, s, tlay, tlev, tsfc);
       }
+    });
+  });
+}
+
+// launch_rte_lw_planck with one output plane per band: a.flux_up / a.flux_dn are (ncol,nlay+1,nband) and band_first[b] is the
+// first 0-based g-point of band b (band_first[nband] = a.ng; ascending, no empty band).  One launch, grid (tiles, band): a
+// block row takes the tiles by grid stride as the broadband kernel does.  The block cap of launch_form is shared among the
+// rows (at least 128 blocks each): a block stages its window of the Planck table once and walks several tiles with it.
+hipError_t launch_rte_lw_planck_bands(const RteLwArgs &a, const double *planck, int ntp, double t0, double dt, const double *tlay,
+                                      const double *tlev, const double *tsfc, const unsigned short *band_first, hipStream_t s) {
+  if (a.f32 || a.nlay != kSeg * kNW || a.ncol <= 0 || a.nband < 1 || a.nband > 256 || !band_first) return hipErrorInvalidValue;
+  if (a.part_mask && a.ng > 64) return hipErrorInvalidValue;
+  BandWindows bw{};
+  for (int b = 0; b <= a.nband; ++b) bw.first[b] = band_first[b];
+  for (int b = 0; b < a.nband; ++b)
+    if (bw.first[b + 1] <= bw.first[b] || bw.first[b + 1] > a.ng) return hipErrorInvalidValue;
+  if (bw.first[0] != 0 || bw.first[a.nband] != a.ng) return hipErrorInvalidValue;
+  const PlanckTab pt{planck, t0, dt, 1. / dt, ntp, a.ng};
+  return with_bool(a.series3, [&](auto ser3) {
+    return with_particles(a, [&](auto sky, auto mask) {
+      constexpr bool SER3 = decltype(ser3)::value, MASK = decltype(mask)::value;
+      constexpr int SKY = decltype(sky)::value;
+      using F = BandsForm<kSeg, kNW, kCW, SER3, SKY, MASK, kPlanckWps>;
+      auto k = rte_lw_split_bands_kernel<kSeg, kNW, kCW, SER3, SKY, MASK, kPlanckWps>;
+      const size_t lds = SplitLds<F>::bytes(ntp, a.ng);
+      if (lds > (size_t)kLdsBudget) return hipErrorInvalidValue;
+      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      if (e != hipSuccess) return e;
+      long blocks = (((long)a.ncol + F::CW - 1) / F::CW + F::NG - 1) / F::NG;
+      const long cap = 256L * 4 / a.nband > 128 ? 256L * 4 / a.nband : 128;
+      if (blocks > cap) blocks = cap;
+      hipLaunchKernelGGL(k, dim3((unsigned)blocks, (unsigned)a.nband), dim3(F::THREADS), lds, s, a, pt, tlay, tlev, tsfc, bw);
+      return hipGetLastError();
     });
   });
 }

@@ -86,10 +86,13 @@ __device__ __forceinline__ void acc_add(double *p, double v, bool owner) {
 // cell uses a particulate optical depth of 0 in front of the same expressions.
 // The kernels (rte_sw_kernel, rte_sw_allsky_kernel and rte_sw_mcica_kernel, below) are thin entries to this body.
 template <typename real> struct SwPart { real t, s, g; unsigned m; };
-template <typename real, int CW, bool FAST, bool CLAMP, bool DERIVE, bool ALLSKY = false, bool MASK = false>
+// WIN (with MASK; ecckd_sw_flux_bands): the launch covers a band of the model and its g-point g sees bit
+// RteSwArgs::mask_first + g of the mask word, as in rte_sw_sys_body.
+template <typename real, int CW, bool FAST, bool CLAMP, bool DERIVE, bool ALLSKY = false, bool MASK = false, bool WIN = false>
 __device__ __forceinline__ void rte_sw_body(const RteSwArgs &a) {
   static_assert(DERIVE || !ALLSKY, "the all-sky form extends the fused (DERIVE) form");
   static_assert(ALLSKY || !MASK, "a cloud mask belongs to the all-sky form");
+  static_assert(MASK || !WIN, "a band window concerns the mask bit alone");
   constexpr int GW = 64 / CW;
   // (fp32 DERIVE: the correctly rounded fp32 division of ssa makes three layers in flight spill; two do not)
   // (ALLSKY: three more values per layer in flight; with three layers the 168 registers of three waves per SIMD spill)
@@ -142,6 +145,7 @@ __device__ __forceinline__ void rte_sw_body(const RteSwArgs &a) {
       const double keep = gact ? 1. : 0.;
       const long base = cc + (long)ncol * nlay * gg;
       const int band = a.gpt2band[gg];
+      [[maybe_unused]] const int gm = WIN ? gg + a.mask_first : gg;   // MASK: the cell's bit of the mask word
       const real ray = DERIVE ? P(a.rayleigh)[gg] : real(0);
       // optical properties of layer sl (counted from the top) into prefetch slot d.  DERIVE: pssa / pg take plev at the
       // layer's two levels, turned into ssa by props() once they have arrived
@@ -152,7 +156,7 @@ __device__ __forceinline__ void rte_sw_body(const RteSwArgs &a) {
         if constexpr (ALLSKY) {
           const long qb = cc + (long)ncol * (lm + (long)nlay * band);
           pp.t = P(a.part_tau)[qb]; pp.s = P(a.part_ssa)[qb]; pp.g = P(a.part_g)[qb];
-          if constexpr (MASK) pp.m = reinterpret_cast<const unsigned *>(a.part_mask)[2 * (cc + (long)ncol * lm) + (gg >> 5)];
+          if constexpr (MASK) pp.m = reinterpret_cast<const unsigned *>(a.part_mask)[2 * (cc + (long)ncol * lm) + (gm >> 5)];
         }
         if constexpr (DERIVE) { x = P(a.plev)[cc + (long)ncol * lm]; y = P(a.plev)[cc + (long)ncol * (lm + 1)]; }
         else { x = P(a.ssa)[q]; y = P(a.g)[q]; }
@@ -163,7 +167,7 @@ __device__ __forceinline__ void rte_sw_body(const RteSwArgs &a) {
           constexpr real eps = op_eps<real>();
           const real tau_r = ((y - x) * gw) * ray;             // :313-316: the Rayleigh optical depth, tau*ssa of the gas optics
           real tp = pp.t;
-          if constexpr (MASK) tp = (pp.m >> (gg & 31)) & 1u ? tp : real(0);
+          if constexpr (MASK) tp = (pp.m >> (gm & 31)) & 1u ? tp : real(0);
           const real tsp = tp * pp.s;
           const real ts = tau_r + tsp, tau12 = ctau + tp;      // increment_2stream_by_2stream
           const real cg = (tsp * pp.g) / (ts > eps ? ts : eps);
@@ -312,6 +316,12 @@ __global__ void __launch_bounds__(64, ECCKD_SW_WAVES_PER_SIMD) rte_sw_mcica_kern
   rte_sw_body<double, CW, true, CLAMP, true, true, true>(a);
 }
 
+// ... on a band window of the model (ecckd_sw_flux_bands with a mask), under its own name
+template <int CW, bool CLAMP>
+__global__ void __launch_bounds__(64, ECCKD_SW_WAVES_PER_SIMD) rte_sw_mcica_bands_kernel(const RteSwArgs a) {
+  rte_sw_body<double, CW, true, CLAMP, true, true, true, true>(a);
+}
+
 // the single-precision all-sky forms (ecckd_sw_fluxes_allsky_f32 / _mcica_f32), each under its own name: the body forms ssa
 // and g in `real`, with the floor 3 * tiny(1._sp) of ecckd_increment_f32 (op_eps<float>) and the single-precision k floor
 template <int CW, bool CLAMP>
@@ -432,8 +442,11 @@ hipError_t launch_rte_sw(const RteSwArgs &a, hipStream_t s) {
   constexpr int CW = ECCKD_SW_CW;
   // (the all-sky form exists in the fast arithmetic mode only; ecckd_sw_fluxes_allsky refuses the rest with a message)
   if (a.allsky && (a.exact_division || !a.derive)) return hipErrorInvalidValue;
-  if (a.allsky && a.part_mask && a.ng > 64) return hipErrorInvalidValue;
-  auto k = a.allsky && a.f32 ? (a.part_mask ? (a.dir_clamp ? rte_sw_mcica_f32_kernel<CW, true> : rte_sw_mcica_f32_kernel<CW, false>)
+  if (a.allsky && a.part_mask && (a.mask_window ? a.mask_first < 0 || a.mask_first + a.ng > 64 || a.f32 : a.ng > 64))
+    return hipErrorInvalidValue;
+  auto k = a.allsky && a.part_mask && a.mask_window
+               ? (a.dir_clamp ? rte_sw_mcica_bands_kernel<CW, true> : rte_sw_mcica_bands_kernel<CW, false>)
+           : a.allsky && a.f32 ? (a.part_mask ? (a.dir_clamp ? rte_sw_mcica_f32_kernel<CW, true> : rte_sw_mcica_f32_kernel<CW, false>)
                                             : (a.dir_clamp ? rte_sw_allsky_f32_kernel<CW, true> : rte_sw_allsky_f32_kernel<CW, false>))
            : a.allsky && a.part_mask ? (a.dir_clamp ? rte_sw_mcica_kernel<CW, true> : rte_sw_mcica_kernel<CW, false>)
            : a.allsky ? (a.dir_clamp ? rte_sw_allsky_kernel<CW, true> : rte_sw_allsky_kernel<CW, false>)

@@ -155,10 +155,14 @@ __device__ __forceinline__ float rcp_chain(float x) { return rcp<true>(x); }
 // word that holds the g-point is requested per g-point next to ptau (one dword per layer, from words that stay in L2), so
 // nothing about the mask lives across g-points; the g-point is wave-uniform, so the test is one v_and and a select.
 // The kernels (rte_sw_sys_kernel, rte_sw_sys_allsky_kernel, rte_sw_sys_mcica_kernel, below) are thin entries to this body.
-template <typename real, bool FAST, bool CLAMP, bool DERIVE, bool FULL, bool ALLSKY = false, bool MASK = false>
+// WIN (with MASK; ecckd_sw_flux_bands): the launch covers a band of the model -- its g-point g is the model's
+// RteSwArgs::mask_first + g, and that is the bit of the mask word it sees.  Nothing else of the launch knows the window: the
+// optical depth, the tables and the outputs are handed over as the band's own arrays.
+template <typename real, bool FAST, bool CLAMP, bool DERIVE, bool FULL, bool ALLSKY = false, bool MASK = false, bool WIN = false>
 __device__ __forceinline__ void rte_sw_sys_body(const RteSwArgs &a) {
   static_assert(DERIVE || !ALLSKY, "the all-sky form extends the fused (DERIVE) form");
   static_assert(ALLSKY || !MASK, "a cloud mask belongs to the all-sky form");
+  static_assert(MASK || !WIN, "a band window concerns the mask bit alone");
   constexpr int LPW = kSysLPW, NW = kSysWaves;
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
   const int lane = threadIdx.x & 63;
@@ -268,7 +272,8 @@ __device__ __forceinline__ void rte_sw_sys_body(const RteSwArgs &a) {
           if (!DERIVE) { pssa[l] = at(P(a.ssa) + row); pg[l] = at(P(a.g) + row); }
           if constexpr (MASK) {
             typedef __attribute__((address_space(1))) const unsigned guint_t;
-            const unsigned *mrow = reinterpret_cast<const unsigned *>(a.part_mask + (long)ncol * (lay0 + lstep * (s0 + l))) + (g >> 5);
+            const int gm = WIN ? g + a.mask_first : g;
+            const unsigned *mrow = reinterpret_cast<const unsigned *>(a.part_mask + (long)ncol * (lay0 + lstep * (s0 + l))) + (gm >> 5);
             pmk[l] = *reinterpret_cast<guint_t *>((gcchar_t *)mrow + (unsigned)cc * 8u);
           }
         }
@@ -303,7 +308,7 @@ __device__ __forceinline__ void rte_sw_sys_body(const RteSwArgs &a) {
           if constexpr (ALLSKY) {
             constexpr real eps = op_eps<real>();
             real tp = ppt[l];
-            if constexpr (MASK) tp = (pmk[l] >> (g & 31)) & 1u ? tp : real(0);
+            if constexpr (MASK) tp = (pmk[l] >> ((WIN ? g + a.mask_first : g) & 31)) & 1u ? tp : real(0);
             const real tsp = tp * pps[l];
             const real tsc = moles[l] * ray + tsp, tau12 = ptau[l] + tp;   // increment_2stream_by_2stream
             cg = (tsp * ppg[l]) / (tsc > eps ? tsc : eps);
@@ -534,6 +539,12 @@ __global__ void __launch_bounds__(64 * kSysWaves) rte_sw_sys_mcica_kernel(const 
   rte_sw_sys_body<double, true, CLAMP, true, FULL, true, true>(a);
 }
 
+// ... on a band window of the model (ecckd_sw_flux_bands with a mask), under its own name
+template <bool CLAMP, bool FULL>
+__global__ void __launch_bounds__(64 * kSysWaves) rte_sw_sys_mcica_bands_kernel(const RteSwArgs a) {
+  rte_sw_sys_body<double, true, CLAMP, true, FULL, true, true, true>(a);
+}
+
 // the single-precision all-sky forms (ecckd_sw_fluxes_allsky_f32 / _mcica_f32), each under its own name: ssa and g are
 // formed in `real` with the floor 3 * tiny(1._sp) of ecckd_increment_f32 (op_eps<float>)
 template <bool CLAMP, bool FULL>
@@ -558,13 +569,14 @@ hipError_t launch_sys2(RteSwArgs a, long blocks, hipStream_t s) {
                        : (a.exact_division ? rte_sw_sys_kernel<real, false, false, DERIVE, FULL> : rte_sw_sys_kernel<real, true, false, DERIVE, FULL>);
   if (a.allsky) {   // (fast arithmetic mode, DERIVE: ecckd_sw_fluxes_allsky refuses the rest with a message)
     if (a.exact_division || !a.derive) return hipErrorInvalidValue;
-    if (a.part_mask && a.ng > 64) return hipErrorInvalidValue;
+    if (a.part_mask && (a.mask_window ? a.mask_first < 0 || a.mask_first + a.ng > 64 || a.f32 : a.ng > 64)) return hipErrorInvalidValue;
     if constexpr (sizeof(real) == 4) {
       k = a.dir_clamp ? rte_sw_sys_allsky_f32_kernel<true, FULL> : rte_sw_sys_allsky_f32_kernel<false, FULL>;
       if (a.part_mask) k = a.dir_clamp ? rte_sw_sys_mcica_f32_kernel<true, FULL> : rte_sw_sys_mcica_f32_kernel<false, FULL>;
     } else {
       k = a.dir_clamp ? rte_sw_sys_allsky_kernel<true, FULL> : rte_sw_sys_allsky_kernel<false, FULL>;
       if (a.part_mask) k = a.dir_clamp ? rte_sw_sys_mcica_kernel<true, FULL> : rte_sw_sys_mcica_kernel<false, FULL>;
+      if (a.part_mask && a.mask_window) k = a.dir_clamp ? rte_sw_sys_mcica_bands_kernel<true, FULL> : rte_sw_sys_mcica_bands_kernel<false, FULL>;
     }
   }
   const size_t base = (sys_lds_base(a.nlay, a.f32, a.flux_dir != nullptr) + 15) & ~(size_t)15;

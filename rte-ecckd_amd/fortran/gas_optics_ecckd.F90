@@ -57,6 +57,8 @@ module gas_optics_ecckd
     procedure, public :: sw_fluxes          !< extension: gas_optics + rte_sw in one call (fused shortwave path)
     procedure, public :: lw_fluxes_allsky   !< extension: lw_fluxes with particulate optics on the model's bands
     procedure, public :: sw_fluxes_allsky   !< extension: sw_fluxes with particulate optics on the model's bands
+    procedure, public :: lw_flux_bands      !< extension: lw_fluxes / lw_fluxes_allsky with one flux plane per band of the model
+    procedure, public :: sw_flux_bands      !< extension: sw_fluxes / sw_fluxes_allsky with one flux plane per band of the model
     procedure, public :: sw_fluxes_daylit   !< extension: sw_fluxes on the columns with mu0 > mu0_min only, zeros in the others
     procedure, public :: sample_cloud_mask  !< extension: McICA cloud mask from cloud fractions (ecckd_cloud_mask_sample)
   end type ty_gas_optics_ecckd
@@ -408,6 +410,39 @@ module gas_optics_ecckd
       type(c_ptr), value :: model
       integer(c_int) :: dev
     end function c_model_device
+    function c_lw_flux_bands(model, ncol, nlay, plev, tlay, tsfc, tlev, ngas, gas_names, vmr, cs, ls, scalar, top_at_1, nmus, &
+                             sfc_emis, inc_flux, nband_p, tau_p, ssa_p, cloud_mask, bnd_flux_up, bnd_flux_dn, flux_up, flux_dn, &
+                             memspace, stream) bind(C, name="ecckd_lw_flux_bands") result(rc)
+      import c_ptr, c_int, c_double, c_char, c_long_long
+      type(c_ptr), value :: model
+      integer(c_int), value :: ncol, nlay, ngas, top_at_1, nmus, nband_p, memspace
+      real(c_double), dimension(*), intent(in) :: plev, tlay, tsfc, tlev, sfc_emis
+      character(kind=c_char), dimension(*), intent(in) :: gas_names
+      type(c_ptr), dimension(*), intent(in) :: vmr
+      integer(c_long_long), dimension(*), intent(in) :: cs, ls
+      real(c_double), dimension(*), intent(in) :: scalar
+      type(c_ptr), value :: inc_flux, tau_p, ssa_p, cloud_mask, flux_up, flux_dn
+      real(c_double), dimension(*), intent(inout) :: bnd_flux_up, bnd_flux_dn
+      type(c_ptr), value :: stream
+      integer(c_int) :: rc
+    end function c_lw_flux_bands
+    function c_sw_flux_bands(model, ncol, nlay, plev, tlay, ngas, gas_names, vmr, cs, ls, scalar, top_at_1, mu0, toa_scale, &
+                             sfc_alb_dir, sfc_alb_dif, nband_p, tau_p, ssa_p, g_p, delta_scale, cloud_mask, bnd_flux_up, &
+                             bnd_flux_dn, bnd_flux_dir, flux_up, flux_dn, flux_dir, memspace, stream) &
+        bind(C, name="ecckd_sw_flux_bands") result(rc)
+      import c_ptr, c_int, c_double, c_char, c_long_long
+      type(c_ptr), value :: model
+      integer(c_int), value :: ncol, nlay, ngas, top_at_1, nband_p, delta_scale, memspace
+      real(c_double), dimension(*), intent(in) :: plev, tlay, mu0, sfc_alb_dir, sfc_alb_dif
+      character(kind=c_char), dimension(*), intent(in) :: gas_names
+      type(c_ptr), dimension(*), intent(in) :: vmr
+      integer(c_long_long), dimension(*), intent(in) :: cs, ls
+      real(c_double), dimension(*), intent(in) :: scalar
+      type(c_ptr), value :: toa_scale, tau_p, ssa_p, g_p, cloud_mask, bnd_flux_dir, flux_up, flux_dn, flux_dir
+      real(c_double), dimension(*), intent(inout) :: bnd_flux_up, bnd_flux_dn
+      type(c_ptr), value :: stream
+      integer(c_int) :: rc
+    end function c_sw_flux_bands
   end interface
 
   integer, parameter, public :: ECCKD_OVERLAP_MAX_RAN = 0, ECCKD_OVERLAP_EXP_RAN = 1
@@ -1294,6 +1329,247 @@ contains
     flux_dn = dn
     if (present(flux_dir)) flux_dir = dir
   end function sw_fluxes_allsky
+
+  !> Extension: lw_fluxes / lw_fluxes_allsky with per-band output (ecckd_lw_flux_bands; include/ecckd_hip.h, "Fused
+  !! per-band fluxes"): bnd_flux_up / bnd_flux_dn (ncol, nlay+1, nband) receive, per band of the model, the sum over the
+  !! band's g-points -- what gas_optics + [increment by band] + rte_lw with a ty_fluxes_byband give.  tau_p (ncol, nlay,
+  !! nband), optional: the particles, with ssa_p (absorption optical depth) or without (one-stream); cloud_mask (ncol, nlay)
+  !! with tau_p only; inc_flux (ncol, ngpt).  flux_up / flux_dn (ncol, nlay+1), optional: the sum of the planes in band
+  !! order.  Host arrays in, host fluxes out; no input is written.
+  function lw_flux_bands(this, plev, tlay, tsfc, tlev, gas_desc, top_at_1, sfc_emis, bnd_flux_up, bnd_flux_dn, tau_p, ssa_p, &
+                         n_gauss_angles, cloud_mask, inc_flux, flux_up, flux_dn) result(error_msg)
+    class(ty_gas_optics_ecckd), intent(in) :: this
+    real(wp), dimension(:,:), intent(in) :: plev, tlay, tlev
+    real(wp), dimension(:), intent(in) :: tsfc
+    type(ty_gas_concs), intent(in) :: gas_desc
+    logical, intent(in) :: top_at_1
+    real(wp), dimension(:,:), intent(in) :: sfc_emis
+    real(wp), dimension(:,:,:), intent(inout) :: bnd_flux_up, bnd_flux_dn
+    real(wp), dimension(:,:,:), intent(in), optional :: tau_p, ssa_p
+    integer, intent(in), optional :: n_gauss_angles
+    integer(c_int64_t), intent(in), optional :: cloud_mask(:,:)
+    real(wp), dimension(:,:), intent(in), optional :: inc_flux
+    real(wp), dimension(:,:), intent(inout), optional :: flux_up, flux_dn
+    character(len=128) :: error_msg
+    character(kind=c_char), dimension(:), allocatable :: names
+    type(c_ptr), dimension(:), allocatable :: ptr
+    integer(c_long_long), dimension(:), allocatable :: cs, ls
+    real(c_double), dimension(:), allocatable :: scalar
+    real(wp), dimension(:,:,:), allocatable :: bup, bdn
+    real(wp), dimension(:,:,:), allocatable, target :: taup, ssa
+    real(wp), dimension(:,:), allocatable, target :: incf, up, dn
+    integer(c_int64_t), dimension(:,:), allocatable, target :: mask
+    type(c_ptr) :: taup_c, ssa_c, mask_c, incf_c, up_c, dn_c
+    integer :: ncol, nlay, n, nmus, nband, nbp
+    integer(c_int) :: rc
+    ncol = size(tlay, 1)
+    nlay = size(tlay, 2)
+    nband = this%get_nband()
+    nmus = 1
+    if (present(n_gauss_angles)) nmus = n_gauss_angles
+    error_msg = marshal_gases(this, gas_desc, ncol, nlay, names, ptr, cs, ls, scalar)
+    if (trim(error_msg) /= "") return
+    if (size(sfc_emis, 1) /= nband .or. size(sfc_emis, 2) /= ncol) then
+      error_msg = "lw_flux_bands: sfc_emis inconsistently sized"
+      return
+    end if
+    if (any(shape(bnd_flux_up) /= [ncol, nlay + 1, nband]) .or. any(shape(bnd_flux_dn) /= [ncol, nlay + 1, nband])) then
+      error_msg = "lw_flux_bands: bnd_flux_up, bnd_flux_dn inconsistently sized"
+      return
+    end if
+    taup_c = c_null_ptr; ssa_c = c_null_ptr; mask_c = c_null_ptr; incf_c = c_null_ptr; up_c = c_null_ptr; dn_c = c_null_ptr
+    nbp = 0
+    if (present(tau_p)) then
+      if (size(tau_p, 1) /= ncol .or. size(tau_p, 2) /= nlay) then
+        error_msg = "lw_flux_bands: tau_p inconsistently sized"
+        return
+      end if
+      nbp = size(tau_p, 3)
+      allocate(taup(ncol, nlay, nbp))
+      taup = tau_p
+      if (size(taup) > 0) taup_c = c_loc(taup(1, 1, 1))
+    end if
+    if (present(ssa_p)) then
+      if (.not. present(tau_p)) then
+        error_msg = "lw_flux_bands: ssa_p and cloud_mask belong to tau_p"
+        return
+      else if (any(shape(ssa_p) /= shape(tau_p))) then
+        error_msg = "lw_flux_bands: ssa_p inconsistently sized"
+        return
+      end if
+      allocate(ssa(ncol, nlay, nbp))
+      ssa = ssa_p
+      if (size(ssa) > 0) ssa_c = c_loc(ssa(1, 1, 1))
+    end if
+    if (present(cloud_mask)) then
+      if (.not. present(tau_p)) then
+        error_msg = "lw_flux_bands: ssa_p and cloud_mask belong to tau_p"
+        return
+      else if (size(cloud_mask, 1) /= ncol .or. size(cloud_mask, 2) /= nlay) then
+        error_msg = "lw_flux_bands: cloud_mask inconsistently sized"
+        return
+      end if
+      allocate(mask(ncol, nlay))
+      mask = cloud_mask
+      if (size(mask) > 0) mask_c = c_loc(mask(1, 1))
+    end if
+    if (present(inc_flux)) then
+      if (size(inc_flux, 1) /= ncol .or. size(inc_flux, 2) /= this%get_ngpt()) then
+        error_msg = "lw_flux_bands: inc_flux inconsistently sized"
+        return
+      end if
+      allocate(incf(ncol, size(inc_flux, 2)))
+      incf = inc_flux
+      if (size(incf) > 0) incf_c = c_loc(incf(1, 1))
+    end if
+    if (present(flux_up)) then
+      allocate(up(ncol, nlay + 1))
+      if (size(up) > 0) up_c = c_loc(up(1, 1))
+    end if
+    if (present(flux_dn)) then
+      allocate(dn(ncol, nlay + 1))
+      if (size(dn) > 0) dn_c = c_loc(dn(1, 1))
+    end if
+    n = gas_desc%get_num_gases()
+    allocate(bup(ncol, nlay + 1, nband), bdn(ncol, nlay + 1, nband))
+    rc = c_lw_flux_bands(this%handle, int(ncol, c_int), int(nlay, c_int), plev, tlay, tsfc, tlev, int(n, c_int), names, ptr, cs, &
+                         ls, scalar, merge(1_c_int, 0_c_int, top_at_1), int(nmus, c_int), sfc_emis, incf_c, int(nbp, c_int), &
+                         taup_c, ssa_c, mask_c, bup, bdn, up_c, dn_c, ECCKD_HOST, c_null_ptr)
+    if (rc /= 0) then
+      error_msg = c_error_message()
+      return
+    end if
+    bnd_flux_up = bup
+    bnd_flux_dn = bdn
+    if (present(flux_up)) flux_up = up
+    if (present(flux_dn)) flux_dn = dn
+  end function lw_flux_bands
+
+  !> Extension: sw_fluxes / sw_fluxes_allsky with per-band output (ecckd_sw_flux_bands): bnd_flux_up / bnd_flux_dn and,
+  !! optionally, bnd_flux_dir (ncol, nlay+1, nband); tau_p / ssa_p / g_p (ncol, nlay, nband), all three or none, delta_scale
+  !! as in sw_fluxes_allsky (default .true.); cloud_mask with particles only; toa_scale (ncol).  flux_up / flux_dn / flux_dir
+  !! (ncol, nlay+1), optional: the sum of the planes in band order (flux_dir needs bnd_flux_dir).  Host arrays throughout.
+  function sw_flux_bands(this, plev, tlay, gas_desc, top_at_1, mu0, sfc_alb_dir, sfc_alb_dif, bnd_flux_up, bnd_flux_dn, &
+                         bnd_flux_dir, tau_p, ssa_p, g_p, delta_scale, toa_scale, cloud_mask, flux_up, flux_dn, flux_dir) &
+      result(error_msg)
+    class(ty_gas_optics_ecckd), intent(in) :: this
+    real(wp), dimension(:,:), intent(in) :: plev, tlay
+    type(ty_gas_concs), intent(in) :: gas_desc
+    logical, intent(in) :: top_at_1
+    real(wp), dimension(:), intent(in) :: mu0
+    real(wp), dimension(:,:), intent(in) :: sfc_alb_dir, sfc_alb_dif
+    real(wp), dimension(:,:,:), intent(inout) :: bnd_flux_up, bnd_flux_dn
+    real(wp), dimension(:,:,:), intent(inout), optional :: bnd_flux_dir
+    real(wp), dimension(:,:,:), intent(in), optional :: tau_p, ssa_p, g_p
+    logical, intent(in), optional :: delta_scale
+    real(wp), dimension(:), intent(in), optional :: toa_scale
+    integer(c_int64_t), intent(in), optional :: cloud_mask(:,:)
+    real(wp), dimension(:,:), intent(inout), optional :: flux_up, flux_dn, flux_dir
+    character(len=128) :: error_msg
+    character(kind=c_char), dimension(:), allocatable :: names
+    type(c_ptr), dimension(:), allocatable :: ptr
+    integer(c_long_long), dimension(:), allocatable :: cs, ls
+    real(c_double), dimension(:), allocatable :: scalar
+    real(wp), dimension(:,:,:), allocatable :: bup, bdn
+    real(wp), dimension(:,:,:), allocatable, target :: bdir, taup, ssa, asy
+    real(wp), dimension(:,:), allocatable, target :: up, dn, dir
+    real(wp), dimension(:), allocatable, target :: scale
+    integer(c_int64_t), dimension(:,:), allocatable, target :: mask
+    type(c_ptr) :: taup_c, ssa_c, asy_c, mask_c, scale_c, bdir_c, up_c, dn_c, dir_c
+    integer :: ncol, nlay, n, nband, nbp
+    integer(c_int) :: rc, ds
+    ncol = size(tlay, 1)
+    nlay = size(tlay, 2)
+    nband = this%get_nband()
+    ds = 1_c_int
+    if (present(delta_scale)) ds = merge(1_c_int, 0_c_int, delta_scale)
+    error_msg = marshal_gases(this, gas_desc, ncol, nlay, names, ptr, cs, ls, scalar)
+    if (trim(error_msg) /= "") return
+    if (size(sfc_alb_dir, 1) /= nband .or. size(sfc_alb_dir, 2) /= ncol .or. &
+        size(sfc_alb_dif, 1) /= nband .or. size(sfc_alb_dif, 2) /= ncol) then
+      error_msg = "sw_flux_bands: surface albedos inconsistently sized"
+      return
+    end if
+    if (any(shape(bnd_flux_up) /= [ncol, nlay + 1, nband]) .or. any(shape(bnd_flux_dn) /= [ncol, nlay + 1, nband])) then
+      error_msg = "sw_flux_bands: bnd_flux_up, bnd_flux_dn inconsistently sized"
+      return
+    end if
+    taup_c = c_null_ptr; ssa_c = c_null_ptr; asy_c = c_null_ptr; mask_c = c_null_ptr; scale_c = c_null_ptr
+    bdir_c = c_null_ptr; up_c = c_null_ptr; dn_c = c_null_ptr; dir_c = c_null_ptr
+    nbp = 0
+    if (present(tau_p) .or. present(ssa_p) .or. present(g_p)) then
+      if (.not. (present(tau_p) .and. present(ssa_p) .and. present(g_p))) then
+        error_msg = "sw_flux_bands: tau_p, ssa_p and g_p go together"
+        return
+      else if (size(tau_p, 1) /= ncol .or. size(tau_p, 2) /= nlay .or. any(shape(ssa_p) /= shape(tau_p)) .or. &
+               any(shape(g_p) /= shape(tau_p))) then
+        error_msg = "sw_flux_bands: tau_p, ssa_p, g_p inconsistently sized"
+        return
+      end if
+      nbp = size(tau_p, 3)
+      allocate(taup(ncol, nlay, nbp), ssa(ncol, nlay, nbp), asy(ncol, nlay, nbp))
+      taup = tau_p
+      ssa = ssa_p
+      asy = g_p
+      if (size(taup) > 0) then
+        taup_c = c_loc(taup(1, 1, 1))
+        ssa_c = c_loc(ssa(1, 1, 1))
+        asy_c = c_loc(asy(1, 1, 1))
+      end if
+    end if
+    if (present(cloud_mask)) then
+      if (nbp == 0) then
+        error_msg = "sw_flux_bands: cloud_mask belongs to particles"
+        return
+      else if (size(cloud_mask, 1) /= ncol .or. size(cloud_mask, 2) /= nlay) then
+        error_msg = "sw_flux_bands: cloud_mask inconsistently sized"
+        return
+      end if
+      allocate(mask(ncol, nlay))
+      mask = cloud_mask
+      if (size(mask) > 0) mask_c = c_loc(mask(1, 1))
+    end if
+    if (present(toa_scale)) then
+      allocate(scale(ncol))
+      scale = toa_scale
+      if (ncol > 0) scale_c = c_loc(scale(1))
+    end if
+    if (present(bnd_flux_dir)) then
+      if (any(shape(bnd_flux_dir) /= [ncol, nlay + 1, nband])) then
+        error_msg = "sw_flux_bands: bnd_flux_dir inconsistently sized"
+        return
+      end if
+      allocate(bdir(ncol, nlay + 1, nband))
+      if (size(bdir) > 0) bdir_c = c_loc(bdir(1, 1, 1))
+    end if
+    if (present(flux_up)) then
+      allocate(up(ncol, nlay + 1))
+      if (size(up) > 0) up_c = c_loc(up(1, 1))
+    end if
+    if (present(flux_dn)) then
+      allocate(dn(ncol, nlay + 1))
+      if (size(dn) > 0) dn_c = c_loc(dn(1, 1))
+    end if
+    if (present(flux_dir)) then
+      allocate(dir(ncol, nlay + 1))
+      if (size(dir) > 0) dir_c = c_loc(dir(1, 1))
+    end if
+    n = gas_desc%get_num_gases()
+    allocate(bup(ncol, nlay + 1, nband), bdn(ncol, nlay + 1, nband))
+    rc = c_sw_flux_bands(this%handle, int(ncol, c_int), int(nlay, c_int), plev, tlay, int(n, c_int), names, ptr, cs, ls, scalar, &
+                         merge(1_c_int, 0_c_int, top_at_1), mu0, scale_c, sfc_alb_dir, sfc_alb_dif, int(nbp, c_int), taup_c, ssa_c, &
+                         asy_c, ds, mask_c, bup, bdn, bdir_c, up_c, dn_c, dir_c, ECCKD_HOST, c_null_ptr)
+    if (rc /= 0) then
+      error_msg = c_error_message()
+      return
+    end if
+    bnd_flux_up = bup
+    bnd_flux_dn = bdn
+    if (present(bnd_flux_dir)) bnd_flux_dir = bdir
+    if (present(flux_up)) flux_up = up
+    if (present(flux_dn)) flux_dn = dn
+    if (present(flux_dir)) flux_dir = dir
+  end function sw_flux_bands
 
   !> Extension: the McICA cloud mask of ecckd_cloud_mask_sample (the definition is in include/ecckd_hip.h; parity with
   !! RTE-RRTMGP's mo_cloud_sampling is unpinned) for this model's g-points: cloud_frac (ncol, nlay) in the layer order of
