@@ -523,6 +523,102 @@ int ecckd_lw_fluxes_allsky_mcica(const ecckd_model_t *model, int ncol, int nlay,
                                  void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * In-cloud water variability: sampled optical-depth scaling.  A cloud mask carries one bit per g-point, so every cloudy
+ * sub-column of the McICA calls above has the layer-mean optical depth (the plane-parallel-homogeneous bias remains).  A
+ * host that knows the fractional standard deviation (FSD) of in-cloud water gets from ecckd_cloud_scaling_sample a
+ * per-g-point factor od_scaling(column, layer, g-point) of the cloud optical depth -- 0 where the g-point is clear -- and
+ * hands it to the consumers below in place of the mask; a host with a cloud generator of its own hands them ITS array.
+ * EVERY DEFINITION HERE IS THIS PROJECT'S OWN, like the sampler's: PARITY WITH ecRad AND RTE-RRTMGP IS UNPINNED.  Each line
+ * below is one correctly rounded IEEE fp64 operation (the build has contraction off), so tests/cloud_scaling_ref.py
+ * reproduces the arrays bit for bit.
+ *
+ * A scaling array is `float` (ncol,nlay,ngpt), column fastest, in the layer order of tlay, whatever the precision of the
+ * call that reads it: 4 bytes per cell against the optical depth's 8 (1e6 columns x 60 layers x 32 g-points: 7.7 GB).
+ *
+ * The scaling table (a host object, like the cloud-optics LUT): values(nfsd,nq), q fastest.  Row k belongs to the FSD
+ * fsd0 + k*dfsd, column j is the scaling of the j-th of nq equal-probability bins of the in-cloud distribution (ascending).
+ * ecckd_cloud_scaling_create refuses with a message: a null handle; nfsd < 2; nq < 1; dfsd not > 0 (or not finite, or fsd0
+ * not finite); more than 2^24 entries; null values; a non-finite or negative value.  device = -1 makes a host-only object.
+ * ecckd_cloud_scaling_lognormal (host code, no device) fills values(nfsd,nq) with the bin means of the unit-mean lognormal
+ * distribution:  sigma^2 = log(1 + f^2);  entry j = nq * (Phi(z_{j+1} - sigma) - Phi(z_j - sigma)),  z_j = Phi^-1(j/nq),
+ * z_0 = -inf, z_nq = +inf, Phi through erfc.  A row with f = 0 is all ones exactly.  The mean of a row is 1 to rounding; its
+ * standard deviation is BELOW f (0.908 for f = 1 at nq = 16: bin means under-disperse) and approaches f as nq grows.
+ * The gamma distribution is not built by the library: a host passes its own table through ecckd_cloud_scaling_create.
+ *
+ * ecckd_cloud_scaling_sample: the rank r(l,g) and "seen" (= the bit) are exactly those of ecckd_cloud_mask_sample -- the same
+ * Philox counters, key and recurrence; `mask`, if not NULL, receives that call's words.  fsd (ncol,nlay) fp64, or NULL:
+ * fsd_const serves every cell.  For a seen cell, with cf = cloud_frac(i,l), v the table, in fp64:
+ *     p = (r - (1 - cf)) / cf                     the position of the sub-column inside the cloud
+ *     j = min((int)(p * nq), nq - 1)
+ *     x = (fsd - fsd0) / dfsd
+ *     if !(x > 0):           k = 0,        w = 0      (a NaN lands here)
+ *     else if x >= nfsd - 1: k = nfsd - 2, w = 1
+ *     else:                  k = (int)x,   w = x - k
+ *     s = v[k][j] + w * (v[k+1][j] - v[k][j]);     scaling = (float)s
+ * An unseen cell gets +0.0f.  fsd is not read where the layer is clear.  Refused with a message, in this order: ngpt > 64
+ * (the ranks of a column are held at once); ngpt < 1; unknown overlap; ECCKD_OVERLAP_EXP_RAN without overlap_param; bad
+ * ncol / nlay; cloud_frac or scaling NULL; a NULL table; bad memspace; host values outside [0,1]; a host-only table or one
+ * of another device; no device.  ECCKD_DEVICE is asynchronous on `stream` and uses no scratch; ECCKD_HOST stages.
+ *
+ * ecckd_increment_scaled (+ _f32): ecckd_increment's argument list plus `scaling`.  Per g-point  t2 = tau2 * (real)scaling,
+ * then ecckd_increment's expressions on t2 -- t2*(1 - ssa2), t2*ssa2 and that product times g2 --, evaluated per g-point,
+ * not hoisted per band.  All four combinations, on g-points and by band; any number of g-points.  With a scaling of exactly
+ * 0 or 1 and finite tau2 >= 0 the result is that of ecckd_increment_masked with the corresponding bits, bit for bit; with
+ * all ones that of ecckd_increment.  scaling NULL: ecckd_increment.  Refusals: ecckd_increment's list.
+ *
+ * ecckd_lw_flux_scaled / ecckd_sw_flux_scaled: the argument lists of the _mcica calls with `const float *cloud_scaling` in
+ * place of the mask; fp64, fast arithmetic mode, ECCKD_DEVICE or ECCKD_HOST.  cloud_scaling NULL: the unmasked all-sky call.
+ * (The names avoid "_fluxes" as ecckd_lw_flux_bands does.)  Refusals: the unmasked all-sky call's list in its order.
+ *   Longwave, every layer count: gas optics into the work block, the scaled by-band increment in place, the solver of
+ *   ecckd_rte_lw_fused without particles (60 layers: the layer-split kernel on the incremented optical depth).  The fluxes
+ *   equal ecckd_gas_optics_lw_tau + ecckd_increment_scaled + ecckd_rte_lw_fused BIT FOR BIT.  Scratch: the optical depth plus
+ *   what that solver takes, ecckd_lw_flux_scaled_scratch_bytes (the figures at ecckd_lw_fluxes_clear_allsky).
+ *   Shortwave, every layer count: delta scaling of the band triple first (independent of the scaling), gas optics, then the
+ *   scaled form of the TWO-PASS solver whatever "sw_solver" says: where the McICA form selects  bit ? tau_p : 0  it
+ *   multiplies  tau_p * (double)scaling.  Agreement with gas optics + delta_scale + ecckd_increment_scaled + ecckd_rte_sw to
+ *   rounding, as for the unmasked call.  Scratch: ecckd_sw_flux_scaled_scratch_bytes -- the formula at ecckd_sw_fluxes_allsky
+ *   with the two-pass solver's term at every layer count.
+ * NOT PROVIDED: both-skies, Jacobian, per-band, daylit and float32 forms of the fused scaled calls, the layer-systolic
+ * shortwave form and an in-kernel 60-layer longwave form.  Two-stream and rescaled longwave are reachable through
+ * ecckd_increment_scaled on two-stream properties followed by the existing solvers.
+ * --------------------------------------------------------------------------------------- */
+typedef struct ecckd_cloud_scaling ecckd_cloud_scaling_t;
+int ecckd_cloud_scaling_create(int device, int nfsd, double fsd0, double dfsd, int nq, const double *values,
+                               ecckd_cloud_scaling_t **table);
+void ecckd_cloud_scaling_destroy(ecckd_cloud_scaling_t *table);
+int ecckd_cloud_scaling_get_nfsd(const ecckd_cloud_scaling_t *table);
+int ecckd_cloud_scaling_get_nq(const ecckd_cloud_scaling_t *table);
+double ecckd_cloud_scaling_get_fsd0(const ecckd_cloud_scaling_t *table);
+double ecckd_cloud_scaling_get_dfsd(const ecckd_cloud_scaling_t *table);
+int ecckd_cloud_scaling_get_values(const ecckd_cloud_scaling_t *table, double *values);
+int ecckd_cloud_scaling_lognormal(int nfsd, double fsd0, double dfsd, int nq, double *values);
+int ecckd_cloud_scaling_sample(int device, int ncol, int nlay, int ngpt, int overlap, const double *cloud_frac,
+                               const double *overlap_param, const double *fsd, double fsd_const,
+                               const ecckd_cloud_scaling_t *table, unsigned long long seed, long long col0, float *scaling,
+                               unsigned long long *mask, int memspace, void *stream);
+int ecckd_increment_scaled(int device, int ncol, int nlay, int ngpt, double *tau1, double *ssa1, double *g1, int nband,
+                           const int *band2gpt, const double *tau2, const double *ssa2, const double *g2, const float *scaling,
+                           int memspace, void *stream);
+int ecckd_increment_scaled_f32(int device, int ncol, int nlay, int ngpt, float *tau1, float *ssa1, float *g1, int nband,
+                               const int *band2gpt, const float *tau2, const float *ssa2, const float *g2, const float *scaling,
+                               int memspace, void *stream);
+size_t ecckd_lw_flux_scaled_scratch_bytes(const ecckd_model_t *model, int ncol, int nlay);
+size_t ecckd_sw_flux_scaled_scratch_bytes(const ecckd_model_t *model, int ncol, int nlay, int delta_scale);
+int ecckd_lw_flux_scaled(const ecckd_model_t *model, int ncol, int nlay, const double *plev, const double *tlay,
+                         const double *tsfc, const double *tlev, int ngas, const char *gas_names, const double *const *vmr,
+                         const long long *vmr_col_stride, const long long *vmr_lay_stride, const double *vmr_scalar,
+                         int top_at_1, int n_gauss_angles, const double *sfc_emis, const double *inc_flux, int nband_p,
+                         const double *tau_p, const double *ssa_p, const float *cloud_scaling, double *flux_up,
+                         double *flux_dn, int memspace, void *stream);
+int ecckd_sw_flux_scaled(const ecckd_model_t *model, int ncol, int nlay, const double *plev, const double *tlay, int ngas,
+                         const char *gas_names, const double *const *vmr, const long long *vmr_col_stride,
+                         const long long *vmr_lay_stride, const double *vmr_scalar, int top_at_1, const double *mu0,
+                         const double *toa_scale, const double *sfc_alb_dir, const double *sfc_alb_dif, int nband_p,
+                         const double *tau_p, const double *ssa_p, const double *g_p, int delta_scale,
+                         const float *cloud_scaling, double *flux_up, double *flux_dn, double *flux_dir, int memspace,
+                         void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * Clear-sky and all-sky fluxes from one call.  A host that reports cloud radiative effect wants, for the same columns, the
  * fluxes of ecckd_*_fluxes and those of ecckd_*_fluxes_allsky[_mcica]; called one after the other they run the gas optics
  * twice on identical inputs.  ecckd_lw_fluxes_clear_allsky / ecckd_sw_fluxes_clear_allsky run it once and then both skies:

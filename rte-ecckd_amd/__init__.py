@@ -103,13 +103,15 @@ CLOUD_DRIVER = os.path.join(FORTRAN_BUILD, "ecckd_cloud_driver")
 AEROSOL_DRIVER = os.path.join(FORTRAN_BUILD, "ecckd_aerosol_driver")
 HEATING_DRIVER = os.path.join(FORTRAN_BUILD, "ecckd_heating_driver")
 BANDS_DRIVER = os.path.join(FORTRAN_BUILD, "ecckd_bands_driver")
+SCALING_DRIVER = os.path.join(FORTRAN_BUILD, "ecckd_scaling_driver")
 _FORTRAN_MODULES = ["mo_rte_min.F90", "mo_ecckd_device.F90", "gas_optics_ecckd.F90", "mo_rte_solvers.F90", "rfmip_support.F90",
                     "mo_cloud_optics.F90", "mo_aerosol_optics.F90", "mo_heating_rates.F90"]
 _FORTRAN_PROGRAMS = [("ecckd_driver", "ecckd_driver.F90", []), ("ecckd_rfmip_lw", "ecckd_rfmip.F90", []),
                      ("ecckd_rfmip_sw", "ecckd_rfmip.F90", ["-DSHORTWAVE"]), ("ecckd_cloud_driver", "ecckd_cloud_driver.F90", []),
                      ("ecckd_aerosol_driver", "ecckd_aerosol_driver.F90", []),
                      ("ecckd_heating_driver", "ecckd_heating_driver.F90", []),
-                     ("ecckd_bands_driver", "ecckd_bands_driver.F90", [])]
+                     ("ecckd_bands_driver", "ecckd_bands_driver.F90", []),
+                     ("ecckd_scaling_driver", "ecckd_scaling_driver.F90", [])]
 
 
 def build_fortran(force=False, verbose=False):
@@ -172,6 +174,8 @@ def _fused_prototypes():
     lw_bands, sw_bands = ptrs("bnd_flux_up", "bnd_flux_dn"), ptrs("bnd_flux_up", "bnd_flux_dn", "bnd_flux_dn_dir")
     return {"ecckd_lw_flux_bands": lw + lw_bound + lw_part + mask + lw_bands + lw_out + tail,
             "ecckd_sw_flux_bands": sw + sw_bound + sw_part + mask + sw_bands + sw_out + tail,
+            "ecckd_lw_flux_scaled": lw + lw_bound + lw_part + ptrs("cloud_scaling") + lw_out + tail,
+            "ecckd_sw_flux_scaled": sw + sw_bound + sw_part + ptrs("cloud_scaling") + sw_out + tail,
             "ecckd_lw_fluxes": lw + lw_bound + lw_out + tail,
             "ecckd_lw_fluxes_allsky": lw + lw_bound + lw_part + lw_out + tail,
             "ecckd_lw_fluxes_allsky_mcica": lw + lw_bound + lw_part + mask + lw_out + tail,
@@ -239,6 +243,25 @@ def lib():
                                                               C.c_int, C.c_void_p]
         for f in ("ecckd_increment_masked", "ecckd_increment_masked_f32"):
             getattr(L, f).argtypes = [C.c_int] * 4 + [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.c_void_p]
+    if hasattr(L, "ecckd_cloud_scaling_sample"):   # (ECCKD_LIB may name an older build, which lacks them)
+        L.ecckd_cloud_scaling_create.argtypes = [C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_void_p]
+        L.ecckd_cloud_scaling_destroy.argtypes = [C.c_void_p]
+        L.ecckd_cloud_scaling_destroy.restype = None
+        for f in ("nfsd", "nq"):
+            getattr(L, "ecckd_cloud_scaling_get_" + f).argtypes = [C.c_void_p]
+        for f in ("fsd0", "dfsd"):
+            getattr(L, "ecckd_cloud_scaling_get_" + f).restype = C.c_double
+            getattr(L, "ecckd_cloud_scaling_get_" + f).argtypes = [C.c_void_p]
+        L.ecckd_cloud_scaling_get_values.argtypes = [C.c_void_p, C.c_void_p]
+        L.ecckd_cloud_scaling_lognormal.argtypes = [C.c_int, C.c_double, C.c_double, C.c_int, C.c_void_p]
+        L.ecckd_cloud_scaling_sample.argtypes = ([C.c_int] * 5 + [C.c_void_p] * 3 + [C.c_double, C.c_void_p, C.c_ulonglong,
+                                                                                  C.c_longlong, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p])
+        for f in ("ecckd_increment_scaled", "ecckd_increment_scaled_f32"):
+            getattr(L, f).argtypes = [C.c_int] * 4 + [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.c_void_p]
+        L.ecckd_lw_flux_scaled_scratch_bytes.restype = C.c_size_t
+        L.ecckd_lw_flux_scaled_scratch_bytes.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        L.ecckd_sw_flux_scaled_scratch_bytes.restype = C.c_size_t
+        L.ecckd_sw_flux_scaled_scratch_bytes.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
     if hasattr(L, "ecckd_lw_fluxes_f32_scratch_bytes"):   # (an older build lacks them: tools/bench_allsky_f32.py --parent-lib)
         L.ecckd_lw_fluxes_f32_scratch_bytes.restype = C.c_size_t
         L.ecckd_lw_fluxes_f32_scratch_bytes.argtypes = [C.c_void_p, C.c_int, C.c_int]
@@ -582,6 +605,135 @@ def sample_cloud_mask(cloud_frac, ngpt, overlap="max_ran", overlap_param=None, s
     return mask
 
 
+class _Scaling:
+    """A sampled optical-depth scaling in the mask slot of ``GasOpticsEcckd._fused``."""
+
+    def __init__(self, array):
+        self.array = array
+
+
+def _scaling_ptr(scaling, ng, nlay, ncol, space):
+    """Data pointer of an optical-depth scaling ``(ngpt, nlay, ncol)`` float32, numpy (host) or device tensor."""
+    if scaling is None:
+        return None
+    if _space_of([scaling]) != space:
+        raise TypeError("cloud_scaling: mixing host and device arrays in one call")
+    return _ptr(scaling, (ng, nlay, ncol), "cloud_scaling", True)
+
+
+class CloudScaling:
+    """The table of in-cloud water variability (``ecckd_cloud_scaling_create``; include/ecckd_hip.h, "In-cloud water
+    variability"): ``values`` ``(nfsd, nq)``, row k the scalings of the ``nq`` equal-probability bins of the in-cloud
+    distribution at the fractional standard deviation ``fsd0 + k*dfsd``.  ``device`` -1: a host-only object."""
+
+    def __init__(self):
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.finalize()
+        except Exception:
+            pass
+
+    def finalize(self):
+        if self._h:
+            lib().ecckd_cloud_scaling_destroy(self._h)
+        self._h = None
+
+    def _need(self):
+        if not self._h:
+            raise RuntimeError("CloudScaling: no table (from_table or lognormal first)")
+        return self._h
+
+    @classmethod
+    def from_table(cls, values, fsd0, dfsd, device=0):
+        """A table of the host's own (a gamma distribution, for instance).  Raises ValueError with the library's message."""
+        v = np.ascontiguousarray(values, dtype=np.float64)
+        if v.ndim != 2:
+            raise ValueError("CloudScaling.from_table: values must be (nfsd, nq)")
+        t = cls()
+        h = C.c_void_p()
+        rc = lib().ecckd_cloud_scaling_create(int(device), int(v.shape[0]), float(fsd0), float(dfsd), int(v.shape[1]),
+                                              C.c_void_p(v.ctypes.data), C.byref(h))
+        if rc:
+            raise ValueError(last_error())
+        t._h = h
+        return t
+
+    @staticmethod
+    def lognormal_values(nfsd, fsd0, dfsd, nq):
+        """``ecckd_cloud_scaling_lognormal``: the ``(nfsd, nq)`` bin means of the unit-mean lognormal distribution (host code)."""
+        v = np.zeros((max(int(nfsd), 0), max(int(nq), 0)))
+        if lib().ecckd_cloud_scaling_lognormal(int(nfsd), float(fsd0), float(dfsd), int(nq), C.c_void_p(v.ctypes.data)):
+            raise ValueError(last_error())
+        return v
+
+    @classmethod
+    def lognormal(cls, nfsd, fsd0, dfsd, nq, device=0):
+        """The table of ``lognormal_values``."""
+        return cls.from_table(cls.lognormal_values(nfsd, fsd0, dfsd, nq), fsd0, dfsd, device=device)
+
+    def get_nfsd(self):
+        return int(lib().ecckd_cloud_scaling_get_nfsd(self._need()))
+
+    def get_nq(self):
+        return int(lib().ecckd_cloud_scaling_get_nq(self._need()))
+
+    def get_fsd0(self):
+        return float(lib().ecckd_cloud_scaling_get_fsd0(self._need()))
+
+    def get_dfsd(self):
+        return float(lib().ecckd_cloud_scaling_get_dfsd(self._need()))
+
+    def get_values(self):
+        v = np.zeros((self.get_nfsd(), self.get_nq()))
+        if lib().ecckd_cloud_scaling_get_values(self._need(), C.c_void_p(v.ctypes.data)):
+            raise ValueError(last_error())
+        return v
+
+
+def sample_cloud_scaling(cloud_frac, ngpt, table, fsd, overlap="max_ran", overlap_param=None, seed=0, col0=0, device=0,
+                         return_mask=False):
+    """Sampled optical-depth scaling (``ecckd_cloud_scaling_sample``; the definition is in include/ecckd_hip.h):
+    ``cloud_frac`` ``(nlay, ncol)`` float64, ``table`` a ``CloudScaling``, ``fsd`` a ``(nlay, ncol)`` float64 array or one
+    number for every cell; ``overlap``, ``overlap_param``, ``seed``, ``col0`` as ``sample_cloud_mask``.  Returns the
+    ``(ngpt, nlay, ncol)`` float32 scaling -- numpy for numpy arrays, a device tensor (asynchronously on the current stream)
+    for device tensors --, 0 where the g-point does not see the layer's cloud; with ``return_mask`` the pair
+    ``(scaling, mask)``, the mask that of ``sample_cloud_mask``.  Raises ValueError with the library's message."""
+    nlay, ncol = cloud_frac.shape
+    code = _OVERLAP.get(overlap, overlap) if isinstance(overlap, str) else overlap
+    if not isinstance(code, int):
+        raise ValueError("sample_cloud_scaling: unknown overlap %r (one of %s)" % (overlap, sorted(_OVERLAP)))
+    fsd_array = None if np.isscalar(fsd) else fsd
+    try:
+        space = _space_of([cloud_frac, overlap_param, fsd_array])
+        cf = _ptr(cloud_frac, (nlay, ncol), "cloud_frac")
+        al = _ptr(overlap_param, (max(nlay - 1, 0), ncol), "overlap_param")
+        fp = _ptr(fsd_array, (nlay, ncol), "fsd")
+    except TypeError as e:
+        raise ValueError(str(e))
+    ngpt = int(ngpt)
+    shape = (max(ngpt, 0), nlay, ncol)
+    mask = None
+    if space == DEVICE:
+        import torch
+        scaling = torch.empty(shape, dtype=torch.float32, device=cloud_frac.device)
+        if return_mask:
+            mask = torch.empty((nlay, ncol), dtype=torch.int64, device=cloud_frac.device)
+        sp, mp, device = C.c_void_p(scaling.data_ptr()), (C.c_void_p(mask.data_ptr()) if return_mask else None), _device_of(cloud_frac)
+    else:
+        scaling = np.zeros(shape, dtype=np.float32)
+        if return_mask:
+            mask = np.zeros((nlay, ncol), dtype=np.uint64)
+        sp, mp = C.c_void_p(scaling.ctypes.data), (C.c_void_p(mask.ctypes.data) if return_mask else None)
+    rc = lib().ecckd_cloud_scaling_sample(int(device), ncol, nlay, ngpt, int(code), cf, al, fp,
+                                          0.0 if fsd_array is not None else float(fsd), table._need(),
+                                          int(seed) & (2**64 - 1), int(col0), sp, mp, space, _stream(space))
+    if rc:
+        raise ValueError(last_error())
+    return (scaling, mask) if return_mask else scaling
+
+
 # ------------------------------------------------------------------------------------------
 # column compaction: the shortwave on the daylit columns (include/ecckd_hip.h, "The shortwave on the daylit columns only")
 # ------------------------------------------------------------------------------------------
@@ -798,6 +950,12 @@ class OpticalProps1scl:
         where bit g of a word is clear, g-point g is incremented as if ``other.tau`` were 0 there.
         Returns the error message ('' = success)."""
         return _increment(self, other, band2gpt, cloud_mask)
+
+    def increment_scaled(self, other, cloud_scaling, band2gpt=None):
+        """``ecckd_increment_scaled`` (float32 containers: ``_f32``): ``increment`` by ``other`` with its optical depth
+        multiplied, per g-point, by ``cloud_scaling`` ``(ngpt, nlay, ncol)`` float32 (``sample_cloud_scaling``, or the
+        host's own); any number of g-points.  Returns the error message ('' = success)."""
+        return _increment(self, other, band2gpt, cloud_scaling=cloud_scaling)
 
 
 class OpticalProps2str(OpticalProps1scl):
@@ -1457,7 +1615,8 @@ class GasOpticsEcckd:
                 if group == "gas":
                     args[group] = self._gas_args(gas_desc, ncol, nlay, space, f32)[:6]
                 elif group == "mask":
-                    args[group] = [_mask_ptr(m, nlay, ncol, space) for m in mask]
+                    args[group] = [_scaling_ptr(m.array, ng, nlay, ncol, space) if isinstance(m, _Scaling)
+                                   else _mask_ptr(m, nlay, ncol, space) for m in mask]
                 elif group == "columns":
                     index = columns() if callable(columns) else columns
                     nday = int(index.shape[0])
@@ -1771,6 +1930,46 @@ class GasOpticsEcckd:
                                 _sw_groups(plev, tlay, top_at_1, mu0, toa_scale, sfc_alb_dir, sfc_alb_dif),
                                 _particle_slots(*triple) + (int(bool(delta_scale)),), cloud_mask, fluxes, True)
 
+    def lw_flux_scaled(self, plev, tlay, tsfc, tlev, gas_desc, top_at_1, sfc_emis, particles, fluxes, cloud_scaling,
+                       n_gauss_angles=1, inc_flux=None):
+        """``ecckd_lw_flux_scaled``: ``lw_fluxes_allsky`` with the particulate optical depth of every (layer, g-point) cell
+        multiplied by ``cloud_scaling`` ``(ngpt, nlay, ncol)`` float32 (``sample_cloud_scaling``, or the host's own; None: the
+        unmasked call) -- bit for bit ``gas_optics_tau`` + ``increment_scaled(particles, cloud_scaling, band2gpt)`` +
+        ``rte_lw_fused``, without the host owning a per-g-point float64 array.  float64, fast arithmetic mode; numpy or
+        device tensors.  Returns the error message ('' = success)."""
+        who = "lw_flux_scaled"
+        lw = _lw_groups(plev, tlay, tsfc, tlev, top_at_1, n_gauss_angles, sfc_emis, inc_flux)
+        part, out = _particle_slots(particles.tau, getattr(particles, "ssa", None)), _flux_slots(fluxes)
+        f32, mixed = _call_precision(who, _named(lw["head"], lw["boundary"], part, out))
+        if mixed or f32:
+            return mixed or _f64_only(who, "the sampled optical-depth scaling in the fused path")
+        return self._fused(lib().ecckd_lw_flux_scaled, False, ("gas", "particles", "mask"), gas_desc, particles=part,
+                           mask=(_Scaling(cloud_scaling),), outputs=out, **lw)
+
+    def sw_flux_scaled(self, plev, tlay, gas_desc, top_at_1, mu0, sfc_alb_dir, sfc_alb_dif, particles, fluxes, cloud_scaling,
+                       delta_scale=True, toa_scale=None):
+        """``ecckd_sw_flux_scaled``: ``sw_fluxes_allsky`` with the particulate optical depth of every (layer, g-point) cell --
+        after the delta scaling -- multiplied by ``cloud_scaling`` ``(ngpt, nlay, ncol)`` float32 (None: the unmasked call), in
+        the two-pass solver whatever ``"sw_solver"`` says: ``gas_optics`` + ``delta_scale`` + ``increment_scaled`` + ``rte_sw``
+        to rounding.  float64, fast arithmetic mode; numpy or device tensors.  Returns the error message ('' = success)."""
+        who = "sw_flux_scaled"
+        sw = _sw_groups(plev, tlay, top_at_1, mu0, toa_scale, sfc_alb_dir, sfc_alb_dif)
+        part = _particle_slots(particles.tau, particles.ssa, particles.g, tau_required=True)
+        out = _flux_slots(fluxes, dn_dir=True)
+        f32, mixed = _call_precision(who, _named(sw["head"], sw["boundary"], part, out))
+        if mixed or f32:
+            return mixed or _f64_only(who, "the sampled optical-depth scaling in the fused path")
+        return self._fused(lib().ecckd_sw_flux_scaled, False, ("mask", "gas", "particles"), gas_desc,
+                           particles=part + (int(bool(delta_scale)),), mask=(_Scaling(cloud_scaling),), outputs=out, **sw)
+
+    def lw_flux_scaled_scratch_bytes(self, ncol, nlay):
+        """``ecckd_lw_flux_scaled_scratch_bytes``: the stream scratch of ``lw_flux_scaled`` on device tensors."""
+        return int(lib().ecckd_lw_flux_scaled_scratch_bytes(self._need(), int(ncol), int(nlay)))
+
+    def sw_flux_scaled_scratch_bytes(self, ncol, nlay, delta_scale=True):
+        """``ecckd_sw_flux_scaled_scratch_bytes``: the stream scratch of ``sw_flux_scaled`` on device tensors."""
+        return int(lib().ecckd_sw_flux_scaled_scratch_bytes(self._need(), int(ncol), int(nlay), int(bool(delta_scale))))
+
     def lw_flux_bands_scratch_bytes(self, ncol, nlay):
         """``ecckd_lw_flux_bands_scratch_bytes``: the stream scratch of ``lw_fluxes_byband`` on device tensors."""
         return int(lib().ecckd_lw_flux_bands_scratch_bytes(self._need(), int(ncol), int(nlay)))
@@ -1809,8 +2008,9 @@ def _device_of(a):
     return 0
 
 
-def _increment(op1, op2, band2gpt, cloud_mask=None):
-    """``ecckd_increment`` / ``_f32`` (with a mask: ``ecckd_increment_masked``) on the Python containers."""
+def _increment(op1, op2, band2gpt, cloud_mask=None, cloud_scaling=None):
+    """``ecckd_increment`` / ``_f32`` (with a mask: ``ecckd_increment_masked``; with a scaling: ``ecckd_increment_scaled``)
+    on the Python containers."""
     ng, nlay, ncol = op1.tau.shape
     f32 = _is_f32(op1.tau)
     two1, two2 = isinstance(op1, OpticalProps2str), isinstance(op2, OpticalProps2str)
@@ -1826,10 +2026,14 @@ def _increment(op1, op2, band2gpt, cloud_mask=None):
         a1 = (P1(op1.tau, "tau"), P1(op1.ssa, "ssa") if two1 else None, P1(op1.g, "g") if two1 else None)
         a2 = (P2(op2.tau, "other.tau"), P2(op2.ssa, "other.ssa") if two2 else None, P2(op2.g, "other.g") if two2 else None)
         mp = _mask_ptr(cloud_mask, nlay, ncol, space)
+        sp = _scaling_ptr(cloud_scaling, ng, nlay, ncol, space)
     except (TypeError, ValueError) as e:
         return str(e)
     b2p = C.c_void_p(b2g.ctypes.data) if b2g is not None else None
-    if cloud_mask is not None:
+    if cloud_scaling is not None:
+        rc = (lib().ecckd_increment_scaled_f32 if f32 else lib().ecckd_increment_scaled)(
+            int(_device_of(op1.tau)), ncol, nlay, ng, *a1, nband, b2p, *a2, sp, space, _stream(space))
+    elif cloud_mask is not None:
         rc = (lib().ecckd_increment_masked_f32 if f32 else lib().ecckd_increment_masked)(
             int(_device_of(op1.tau)), ncol, nlay, ng, *a1, nband, b2p, *a2, mp, space, _stream(space))
     else:

@@ -192,6 +192,7 @@ struct SwDerive {
   const double *part_tau = nullptr, *part_ssa = nullptr, *part_g = nullptr;
   const unsigned long long *part_mask = nullptr;   // ecckd_sw_fluxes_allsky_mcica (RteSwArgs::part_mask), or null
   int mask_first = -1;                             // ecckd_sw_flux_bands: >= 0, the model's g-point of the launch's first (RteSwArgs::mask_first)
+  const float *part_scaling = nullptr;             // ecckd_sw_flux_scaled (RteSwArgs::part_scaling): the two-pass solver, whatever "sw_solver" says
 };
 // What a public entry point asks of the solver implementations besides its arguments.
 struct Call {
@@ -743,6 +744,15 @@ struct ecckd_cloud_lut {
   size_t off_liq[2] = {0, 0}, off_ice[2] = {0, 0}, ice_stride[2] = {0, 0};   // bytes; [0] fp64, [1] float
 };
 
+// ---- sampled optical-depth scaling: the table of in-cloud water variability (ecckd_cloud_scaling_create) ----
+// values(nfsd,nq), q fastest, on the host and -- with a device -- on the device
+struct ecckd_cloud_scaling {
+  int nfsd = 0, nq = 0, device = -1;
+  double fsd0 = 0., dfsd = 0.;
+  std::vector<double> values;
+  double *dvalues = nullptr;
+};
+
 namespace {
 
 // (value, slope) pairs of the rows of `table` (nsize, nrow), size fastest, appended to `out`: the table is rounded to
@@ -1022,9 +1032,17 @@ size_t ecckd_rte_sw_tail_scratch_bytes(int device, int ncol, int nlay, int ngpt)
 }
 // What ecckd_sw_fluxes needs behind the optical depth in its scratch block for the solver it will take (the sizing
 // rule of include/ecckd_hip.h): the layer-systolic solver's partial sums, or the two-pass solver's ring and partial sums.
-static size_t sw_fluxes_solver_bytes(int device, int ncol, int nlay, int ngpt) {
+// two_pass (ecckd_sw_flux_scaled): the two-pass solver whatever "sw_solver" says.
+static size_t sw_fluxes_solver_bytes(int device, int ncol, int nlay, int ngpt, bool two_pass = false) {
   ecckd::RteSwArgs a{};
   a.ncol = ncol; a.nlay = nlay; a.ng = ngpt;
+  if (two_pass) {
+    long first = -1;
+    size_t at = 0;
+    const size_t tail2 = g_opt.sw_tail_split.load() && device >= 0 && device < 16 ? ecckd::rte_sw_tail_plan(a, &first, &at) : 0;
+    const size_t ring2 = ecckd_rte_sw_scratch_bytes(ncol, nlay, ngpt);
+    return tail2 > ring2 ? tail2 : ring2;
+  }
   const size_t tail = ecckd_rte_sw_tail_scratch_bytes(device, ncol, nlay, ngpt);
   if (g_opt.sw_solver.load() == 0 && ecckd::rte_sw_sys_applies(a)) return tail;
   const size_t ring = ecckd_rte_sw_scratch_bytes(ncol, nlay, ngpt);
@@ -1759,11 +1777,12 @@ static int rte_sw_impl(const Call &c, int device, int ncol, int nlay, int ngpt, 
     a.toa_scale = dv->toa_scale;
     if (dv->part_tau) { a.allsky = 1; a.part_tau = dv->part_tau; a.part_ssa = dv->part_ssa; a.part_g = dv->part_g; a.part_mask = dv->part_mask; }
     if (dv->part_mask && dv->mask_first >= 0) { a.mask_window = 1; a.mask_first = dv->mask_first; }
+    if (dv->part_scaling) { a.part_scaling = dv->part_scaling; a.mask_window = 2; }
   }
   Stage st(device, memspace, stream, c.f32);
   ScratchLease lease;   // (held until the kernels of this call have been launched)
   const int cus = simd_slots(device) / 4;
-  a.use_sys = g_opt.sw_solver.load() == 0 && ecckd::rte_sw_sys_applies(a) && cus > 0;
+  a.use_sys = g_opt.sw_solver.load() == 0 && ecckd::rte_sw_sys_applies(a) && cus > 0 && a.mask_window != 2;
   if (a.use_sys) {
     // layer-systolic solver: no scratch ring; the g-point chunks of the last part-empty round go through partial sums
     if (g_opt.sw_tail_split.load()) {
@@ -2044,7 +2063,9 @@ static size_t fused_scratch_doubles(const ecckd_model *m, int ncol, int nlay) {
 // device; ssa == nullptr: one-stream particles
 static const char kMaskTooWide[] = ": a cloud mask is one 64-bit word per (column, layer): at most 64 g-points, not ";
 // mask: ecckd_lw_fluxes_allsky_mcica -- the cloud mask (ncol,nlay), in the memory space of the call, or null
-struct LwParticles { const double *tau, *ssa; const unsigned long long *mask = nullptr; };
+// scaling: ecckd_lw_flux_scaled -- the sampled optical-depth scaling (ncol,nlay,ngpt), float32, in the memory space of the
+// call, or null; with it the scaled by-band increment runs on the scratch tau at every layer count and the solver sees no particles
+struct LwParticles { const double *tau, *ssa; const unsigned long long *mask = nullptr; const float *scaling = nullptr; };
 
 // ecckd_*_fluxes_clear_allsky: where the clear-sky fluxes go (dir: shortwave only, may be null), in the memory space of the call
 struct ClearFluxes { double *up, *dn, *dir; };
@@ -2139,6 +2160,7 @@ static int lw_increment_dev(const ecckd_model *m, int ncol, int nlay, double *ta
   o.tau1 = tau; o.tau2 = pt.tau; o.ssa2 = pt.ssa; o.g2 = pt.ssa;   // (g2 marks op2 as two-stream; 1scl += 2str never reads it)
   if (ssa1) { o.ssa1 = ssa1; o.g1 = g1; o.g2 = g2; }
   o.mask = pt.mask;   // (McICA: the masked by-band increment)
+  o.scaling = pt.scaling;
   ProfScope prof("increment", stream);
   HIPCHK(ecckd::launch_increment(o, stream));
   return 0;
@@ -2307,7 +2329,8 @@ static int lw_fluxes_impl(bool f32, const ecckd_model_t *m, int ncol, int nlay, 
         d_plev = st.in(plev, n.lev); d_tlay = st.in(tlay, n.lay); d_tsfc = st.in(tsfc, n.col); d_tlev = st.in(tlev, n.lev);
         d_emis = st.in(sfc_emis, n.col_b); d_incf = st.in(inc_flux, n.col_g);
         d_gd = st.gases(gd, ncol, nlay);
-        if (pt) d_pt = LwParticles{st.in(pt->tau, n.lay_b), st.in(pt->ssa, n.lay_b), st.in(pt->mask, n.lay)};
+        if (pt) d_pt = LwParticles{st.in(pt->tau, n.lay_b), st.in(pt->ssa, n.lay_b), st.in(pt->mask, n.lay),
+                                   static_cast<const float *>(st.in_bytes(pt->scaling, n.lay_g * sizeof(float)))};
         if (clr) d_clr = ClearFluxes{st.out(clr->up, n.lev), st.out(clr->dn, n.lev), nullptr};
         d_up = st.out(flux_up, n.lev); d_dn = st.out(flux_dn, n.lev); d_jac = st.out(jac, n.lev);
         d_tau = st.work((n.lay_g + 32 + extra) * sizeof(double));
@@ -2316,7 +2339,12 @@ static int lw_fluxes_impl(bool f32, const ecckd_model_t *m, int ncol, int nlay, 
   double *d_extra = extra ? d_tau + r32(n.lay_g) : nullptr;
   const hipStream_t s = st.stream;
   if (gas_optical_depth_dev(m, false, nullptr, ncol, nlay, d_plev, d_tlay, d_gd, d_tau, false, nullptr, nullptr, nullptr, nullptr, s)) return 1;
-  if (clr) {
+  if (pt && pt->scaling) {   // ecckd_lw_flux_scaled: the scaled increment in place, then the solver without particles
+    if (clr || jx) return fail("ecckd: internal: the scaled longwave call has no both-skies or Jacobian form");
+    if (lw_increment_dev(m, ncol, nlay, d_tau, d_pt, s)) return 1;
+    if (rte_lw_fused_dev(m, ncol, nlay, top_at_1, n_gauss_angles, d_tau, d_tlay, d_tlev, d_tsfc, d_emis, d_incf, d_up, d_dn, d_extra, s))
+      return 1;
+  } else if (clr) {
     if (lw_both_skies_dev(m, ncol, nlay, top_at_1, n_gauss_angles, d_tau, d_tlay, d_tlev, d_tsfc, d_emis, d_incf, d_up, d_dn, d_extra,
                           s, d_pt, d_clr, jac_in ? d_jac : nullptr))
       return 1;
@@ -2341,6 +2369,19 @@ int ecckd_lw_fluxes(const ecckd_model_t *m, int ncol, int nlay, const double *pl
                         top_at_1, n_gauss_angles, sfc_emis, inc_flux, flux_up, flux_dn, memspace, stream);
 }
 
+// ... its part that every form shares (ecckd_lw_flux_scaled too)
+static int lw_fluxes_allsky_refusals(const ecckd_model_t *m, int nband_p, const double *tau_p, const double *tlev) {
+  if (!m) return fail("ecckd: null model");
+  if (nband_p != m->nband)
+    return fail("ecckd_lw_fluxes_allsky: nband_p = " + std::to_string(nband_p) + " but the model has " + std::to_string(m->nband) +
+                " bands (particulate properties live on the model's bands)");
+  if (!tau_p) return fail("ecckd_lw_fluxes_allsky: null argument (tau_p is required; ssa_p may be null: one-stream particles)");
+  if (g_arith.load() != 0) return fail("ecckd_lw_fluxes_allsky: needs the fast arithmetic mode (ecckd_set_arithmetic(0))");
+  if (!m->has_planck) return fail("ecckd_lw_fluxes_allsky: model has no Planck table (shortwave model?)");
+  if (!tlev) return fail("tlev is required for ecckd");
+  return 0;
+}
+
 // The one refusal list of the fused all-sky longwave calls.  cloud_mask (ecckd_lw_fluxes_allsky_mcica), or null: with a
 // mask, a model of more than 64 g-points is refused first.  Refusals that need no device come first: a host-only model
 // answers them too.
@@ -2353,13 +2394,7 @@ static int lw_fluxes_allsky_impl(bool f32, const ecckd_model_t *m, int ncol, int
                                  void *stream, const ClearFluxes *clr = nullptr, const LwJac *jx = nullptr) {
   if (!m) return fail("ecckd: null model");
   if (cloud_mask && m->ng > 64) return fail("ecckd_lw_fluxes_allsky_mcica" + std::string(kMaskTooWide) + std::to_string(m->ng));
-  if (nband_p != m->nband)
-    return fail("ecckd_lw_fluxes_allsky: nband_p = " + std::to_string(nband_p) + " but the model has " + std::to_string(m->nband) +
-                " bands (particulate properties live on the model's bands)");
-  if (!tau_p) return fail("ecckd_lw_fluxes_allsky: null argument (tau_p is required; ssa_p may be null: one-stream particles)");
-  if (g_arith.load() != 0) return fail("ecckd_lw_fluxes_allsky: needs the fast arithmetic mode (ecckd_set_arithmetic(0))");
-  if (!m->has_planck) return fail("ecckd_lw_fluxes_allsky: model has no Planck table (shortwave model?)");
-  if (!tlev) return fail("tlev is required for ecckd");
+  if (lw_fluxes_allsky_refusals(m, nband_p, tau_p, tlev)) return 1;
   if (clr) {
     if (!clr->up || !clr->dn)
       return fail("ecckd_lw_fluxes_clear_allsky: null argument (flux_up_clear and flux_dn_clear are both required)");
@@ -2847,15 +2882,16 @@ int ecckd_lw_fluxes_jac(const ecckd_model_t *m, int ncol, int nlay, const double
 // ecckd_sw_fluxes_allsky: the combined particulate optical properties on the model's bands, (ncol,nlay,nband) each, in the
 // memory space of the call; delta_scale: the library delta-scales a copy (f = g*g) first
 // mask: ecckd_sw_fluxes_allsky_mcica -- the cloud mask (ncol,nlay), in the memory space of the call, or null
-struct SwParticles { const double *tau, *ssa, *g; int delta_scale; const unsigned long long *mask = nullptr; };
+// scaling: ecckd_sw_flux_scaled -- the sampled optical-depth scaling (ncol,nlay,ngpt), float32, in the memory space of the call, or null
+struct SwParticles { const double *tau, *ssa, *g; int delta_scale; const unsigned long long *mask = nullptr; const float *scaling = nullptr; };
 
 // The work block of sw_fluxes_impl: the optical depth, the solver's room, the three scaled band planes (or none)
 struct SwWork {
   size_t tau_bytes, solver, plane;
-  SwWork(const ecckd_model *m, bool f32, int ncol, int nlay, bool scaled_planes) {
+  SwWork(const ecckd_model *m, bool f32, int ncol, int nlay, bool scaled_planes, bool two_pass = false) {
     const Counts n(ncol, nlay, m->ng, m->nband);
     tau_bytes = align256(n.lay_g * esz(f32));
-    solver = sw_fluxes_solver_bytes(m->device, ncol, nlay, m->ng);
+    solver = sw_fluxes_solver_bytes(m->device, ncol, nlay, m->ng, two_pass);
     plane = scaled_planes ? align256(n.lay_b * esz(f32)) : 0;
   }
   size_t bytes() const { return tau_bytes + solver + 3 * plane; }
@@ -2880,7 +2916,7 @@ static int sw_fluxes_impl(bool f32, const ecckd_model_t *m, int ncol, int nlay, 
   // The work block: tau between the two kernels, the solver's room behind it, and -- all-sky with delta scaling -- three
   // band planes for the scaled copy of the particles (the caller's arrays are never written).  With device arrays it is
   // the stream's scratch block, so the capture rules of stream_scratch cover all of it.
-  const SwWork work(m, f32, ncol, nlay, pt && pt->delta_scale);
+  const SwWork work(m, f32, ncol, nlay, pt && pt->delta_scale, pt && pt->scaling);
   const size_t tau_bytes = work.tau_bytes, solver = work.solver, plane = work.plane;
   Stage st(const_cast<ecckd_model *>(m), memspace, stream, f32);
   const double *d_plev = nullptr, *d_tlay = nullptr, *d_mu0 = nullptr, *d_scale = nullptr, *d_ad = nullptr, *d_af = nullptr;
@@ -2892,7 +2928,8 @@ static int sw_fluxes_impl(bool f32, const ecckd_model_t *m, int ncol, int nlay, 
         d_plev = st.in(plev, n.lev); d_tlay = st.in(tlay, n.lay); d_mu0 = st.in(mu0, n.col); d_scale = st.in(toa_scale, n.col);
         d_ad = st.in(sfc_alb_dir, n.col_b); d_af = st.in(sfc_alb_dif, n.col_b);
         d_gd = st.gases(gd, ncol, nlay);
-        if (pt) d_pt = SwParticles{st.in(pt->tau, n.lay_b), st.in(pt->ssa, n.lay_b), st.in(pt->g, n.lay_b), pt->delta_scale, st.in(pt->mask, n.lay)};
+        if (pt) d_pt = SwParticles{st.in(pt->tau, n.lay_b), st.in(pt->ssa, n.lay_b), st.in(pt->g, n.lay_b), pt->delta_scale, st.in(pt->mask, n.lay),
+                                   static_cast<const float *>(st.in_bytes(pt->scaling, n.lay_g * sizeof(float)))};
         if (clr) d_clr = ClearFluxes{st.out(clr->up, n.lev), st.out(clr->dn, n.lev), st.out(clr->dir, n.lev)};
         d_up = st.out(flux_up, n.lev); d_dn = st.out(flux_dn, n.lev); d_dir = st.out(flux_dir, n.lev);
         d_tau = st.work(work.bytes());
@@ -2917,7 +2954,7 @@ static int sw_fluxes_impl(bool f32, const ecckd_model_t *m, int ncol, int nlay, 
   };
   // ecckd_sw_fluxes_clear_allsky: the clear-sky solver of ecckd_sw_fluxes first, on the same tau and in the same room
   if (clr && solve(d_clr)) return 1;
-  if (pt) { dv.part_tau = d_pt.tau; dv.part_ssa = d_pt.ssa; dv.part_g = d_pt.g; dv.part_mask = d_pt.mask; }
+  if (pt) { dv.part_tau = d_pt.tau; dv.part_ssa = d_pt.ssa; dv.part_g = d_pt.g; dv.part_mask = d_pt.mask; dv.part_scaling = d_pt.scaling; }
   if (solve(ClearFluxes{d_up, d_dn, d_dir})) return 1;
   return st.close();
 }
@@ -2931,6 +2968,19 @@ int ecckd_sw_fluxes(const ecckd_model_t *m, int ncol, int nlay, const double *pl
                         top_at_1, mu0, toa_scale, sfc_alb_dir, sfc_alb_dif, flux_up, flux_dn, flux_dir, memspace, stream);
 }
 
+// ... its part that every form shares (ecckd_sw_flux_scaled too)
+static int sw_fluxes_allsky_refusals(const ecckd_model_t *m, int nband_p, const double *tau_p, const double *ssa_p,
+                                     const double *g_p, int delta_scale) {
+  if (!m) return fail("ecckd: null model");
+  if (nband_p != m->nband)
+    return fail("ecckd_sw_fluxes_allsky: nband_p = " + std::to_string(nband_p) + " but the model has " + std::to_string(m->nband) +
+                " bands (particulate properties live on the model's bands)");
+  if (!tau_p || !ssa_p || !g_p) return fail("ecckd_sw_fluxes_allsky: null argument (tau_p, ssa_p and g_p are all required)");
+  if (delta_scale != 0 && delta_scale != 1) return fail("ecckd_sw_fluxes_allsky: delta_scale must be 0 or 1");
+  if (g_arith.load() != 0) return fail("ecckd_sw_fluxes_allsky: needs the fast arithmetic mode (ecckd_set_arithmetic(0))");
+  return 0;
+}
+
 // The one refusal list of the fused all-sky shortwave calls; cloud_mask as in lw_fluxes_allsky_impl.  f32: the _f32 entry
 // points (float data behind the double pointers, dp()); the messages are those of the fp64 namesakes.
 static int sw_fluxes_allsky_impl(bool f32, const ecckd_model_t *m, int ncol, int nlay, const double *plev, const double *tlay, int ngas,
@@ -2942,12 +2992,7 @@ static int sw_fluxes_allsky_impl(bool f32, const ecckd_model_t *m, int ncol, int
                                  int memspace, void *stream, const ClearFluxes *clr = nullptr) {
   if (!m) return fail("ecckd: null model");
   if (cloud_mask && m->ng > 64) return fail("ecckd_sw_fluxes_allsky_mcica" + std::string(kMaskTooWide) + std::to_string(m->ng));
-  if (nband_p != m->nband)
-    return fail("ecckd_sw_fluxes_allsky: nband_p = " + std::to_string(nband_p) + " but the model has " + std::to_string(m->nband) +
-                " bands (particulate properties live on the model's bands)");
-  if (!tau_p || !ssa_p || !g_p) return fail("ecckd_sw_fluxes_allsky: null argument (tau_p, ssa_p and g_p are all required)");
-  if (delta_scale != 0 && delta_scale != 1) return fail("ecckd_sw_fluxes_allsky: delta_scale must be 0 or 1");
-  if (g_arith.load() != 0) return fail("ecckd_sw_fluxes_allsky: needs the fast arithmetic mode (ecckd_set_arithmetic(0))");
+  if (sw_fluxes_allsky_refusals(m, nband_p, tau_p, ssa_p, g_p, delta_scale)) return 1;
   if (clr) {
     if (!clr->up || !clr->dn)
       return fail("ecckd_sw_fluxes_clear_allsky: null argument (flux_up_clear and flux_dn_clear are both required; flux_dir_clear may be null)");
@@ -3307,7 +3352,7 @@ int ecckd_delta_scale_f32(int device, int ncol, int nlay, int n, float *tau, flo
 // mask: ecckd_increment_masked -- one word per (column, layer) in `memspace`, or null
 static int increment_impl(bool f32, int device, int ncol, int nlay, int ngpt, double *tau1, double *ssa1, double *g1, int nband,
                           const int *band2gpt, const double *tau2, const double *ssa2, const double *g2, int memspace,
-                          void *stream, const unsigned long long *mask = nullptr) {
+                          void *stream, const unsigned long long *mask = nullptr, const float *scaling = nullptr) {
   if (mask && ngpt > 64) return fail("ecckd_increment_masked" + std::string(kMaskTooWide) + std::to_string(ngpt));
   if (check_dims(ncol, nlay)) return 1;
   if (ngpt < 1) return fail("ecckd_increment: ngpt must be at least 1");
@@ -3341,6 +3386,7 @@ static int increment_impl(bool f32, int device, int ncol, int nlay, int ngpt, do
   Stage st(device, memspace, stream, f32);
   if (st.open([&] {
         a.mask = st.in(mask, (size_t)ncol * nlay);
+        a.scaling = static_cast<const float *>(st.in_bytes(scaling, n1 * sizeof(float)));   // (float32 in either precision)
         a.tau1 = st.inout(tau1, n1); a.ssa1 = st.inout(ssa1, n1);
         a.g1 = st.inout(g1, n1, ssa2 != nullptr);   // (g1 changes only when op2 scatters)
         a.tau2 = st.in(tau2, n2); a.ssa2 = st.in(ssa2, n2); a.g2 = st.in(g2, n2);
@@ -3373,6 +3419,19 @@ int ecckd_increment_masked_f32(int device, int ncol, int nlay, int ngpt, float *
                                const unsigned long long *mask, int memspace, void *stream) {
   return increment_impl(true, device, ncol, nlay, ngpt, dp(tau1), dp(ssa1), dp(g1), nband, band2gpt, dp(tau2), dp(ssa2), dp(g2),
                         memspace, stream, mask);
+}
+
+int ecckd_increment_scaled(int device, int ncol, int nlay, int ngpt, double *tau1, double *ssa1, double *g1, int nband,
+                           const int *band2gpt, const double *tau2, const double *ssa2, const double *g2, const float *scaling,
+                           int memspace, void *stream) {
+  return increment_impl(false, device, ncol, nlay, ngpt, tau1, ssa1, g1, nband, band2gpt, tau2, ssa2, g2, memspace, stream, nullptr,
+                        scaling);
+}
+int ecckd_increment_scaled_f32(int device, int ncol, int nlay, int ngpt, float *tau1, float *ssa1, float *g1, int nband,
+                               const int *band2gpt, const float *tau2, const float *ssa2, const float *g2, const float *scaling,
+                               int memspace, void *stream) {
+  return increment_impl(true, device, ncol, nlay, ngpt, dp(tau1), dp(ssa1), dp(g1), nband, band2gpt, dp(tau2), dp(ssa2), dp(g2),
+                        memspace, stream, nullptr, scaling);
 }
 
 // ---- cloud optics (kernels_cloud_optics.hip): water paths and effective radii to band properties ----
@@ -3706,6 +3765,196 @@ int ecckd_cloud_mask_sample(int device, int ncol, int nlay, int ngpt, int overla
     HIPCHK(ecckd::launch_cloud_mask_sample(ncol, nlay, ngpt, exp_ran, d_cf, d_al, seed, col0, d_mask, st.stream));
   }
   return st.close();
+}
+
+// ---- sampled optical-depth scaling (kernels_cloud_sampling.hip; include/ecckd_hip.h, "In-cloud water variability") ----
+
+int ecckd_cloud_scaling_create(int device, int nfsd, double fsd0, double dfsd, int nq, const double *values,
+                               ecckd_cloud_scaling_t **table) {
+  if (!table) return fail("ecckd_cloud_scaling_create: null argument (the handle)");
+  *table = nullptr;
+  if (nfsd < 2) return fail("ecckd_cloud_scaling_create: nfsd must be at least 2 (the rows are interpolated)");
+  if (nq < 1) return fail("ecckd_cloud_scaling_create: nq must be at least 1");
+  if (!(dfsd > 0.) || !std::isfinite(dfsd) || !std::isfinite(fsd0))
+    return fail("ecckd_cloud_scaling_create: dfsd must be greater than 0 (and fsd0 and dfsd finite)");
+  if ((long long)nfsd * nq > (1ll << 24)) return fail("ecckd_cloud_scaling_create: at most 2^24 table entries");
+  if (!values) return fail("ecckd_cloud_scaling_create: null argument (values)");
+  const size_t n = (size_t)nfsd * nq;
+  for (size_t i = 0; i < n; ++i)
+    if (!std::isfinite(values[i]) || values[i] < 0.)
+      return fail("ecckd_cloud_scaling_create: a scaling must be finite and not negative (entry " + std::to_string(i) + ")");
+  ecckd_cloud_scaling t;
+  t.nfsd = nfsd; t.nq = nq; t.fsd0 = fsd0; t.dfsd = dfsd;
+  t.values.assign(values, values + n);
+  if (device != -1) {   // (-1: a host-only object: getters and refusals work, the sampler fails)
+    if (check_device(device)) return 1;
+    HIPCHK(hipMalloc(reinterpret_cast<void **>(&t.dvalues), n * sizeof(double)));
+    if (hipMemcpy(t.dvalues, values, n * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
+      (void)hipFree(t.dvalues);
+      return fail("ecckd_cloud_scaling_create: copying the table to the device failed");
+    }
+    t.device = device;
+  }
+  *table = new ecckd_cloud_scaling(std::move(t));
+  return 0;
+}
+
+void ecckd_cloud_scaling_destroy(ecckd_cloud_scaling_t *t) {
+  if (!t) return;
+  if (t->device >= 0 && t->dvalues) {
+    (void)hipSetDevice(t->device);
+    (void)hipFree(t->dvalues);
+  }
+  delete t;
+}
+
+int ecckd_cloud_scaling_get_nfsd(const ecckd_cloud_scaling_t *t) { return t ? t->nfsd : 0; }
+int ecckd_cloud_scaling_get_nq(const ecckd_cloud_scaling_t *t) { return t ? t->nq : 0; }
+double ecckd_cloud_scaling_get_fsd0(const ecckd_cloud_scaling_t *t) { return t ? t->fsd0 : 0.; }
+double ecckd_cloud_scaling_get_dfsd(const ecckd_cloud_scaling_t *t) { return t ? t->dfsd : 0.; }
+int ecckd_cloud_scaling_get_values(const ecckd_cloud_scaling_t *t, double *values) {
+  if (!t || !values) return fail("ecckd_cloud_scaling_get_values: null argument");
+  std::memcpy(values, t->values.data(), t->values.size() * sizeof(double));
+  return 0;
+}
+
+// Phi(x) through erfc, and its inverse for 0 < p <= 1/2: Acklam's rational start (relative error 1.2e-9), then Halley
+// steps on Phi(z) - p until the step is below an ulp of z
+static double std_normal_cdf(double x) { return 0.5 * std::erfc(-x * 0.70710678118654752440); }
+static double std_normal_quantile_lower(double p) {
+  static const double a[6] = {-3.969683028665376e+01, 2.209460984245205e+02, -2.759285104469687e+02,
+                              1.383577518672690e+02, -3.066479806614716e+01, 2.506628277459239e+00};
+  static const double b[5] = {-5.447609879822406e+01, 1.615858368580409e+02, -1.556989798598866e+02,
+                              6.680131188771972e+01, -1.328068155288572e+01};
+  static const double c[6] = {-7.784894002430293e-03, -3.223964580411365e-01, -2.400758277161838e+00,
+                              -2.549732539343734e+00, 4.374664141464968e+00, 2.938163982698783e+00};
+  static const double d[4] = {7.784695709041462e-03, 3.224671290700398e-01, 2.445134137142996e+00, 3.754408661907416e+00};
+  double z;
+  if (p < 0.02425) {
+    const double q = std::sqrt(-2. * std::log(p));
+    z = (((((c[0] * q + c[1]) * q + c[2]) * q + c[3]) * q + c[4]) * q + c[5]) / ((((d[0] * q + d[1]) * q + d[2]) * q + d[3]) * q + 1.);
+  } else {
+    const double q = p - 0.5, r = q * q;
+    z = (((((a[0] * r + a[1]) * r + a[2]) * r + a[3]) * r + a[4]) * r + a[5]) * q /
+        (((((b[0] * r + b[1]) * r + b[2]) * r + b[3]) * r + b[4]) * r + 1.);
+  }
+  for (int it = 0; it < 4; ++it) {
+    const double e = std_normal_cdf(z) - p;
+    const double u = e * 2.50662827463100050242 * std::exp(0.5 * z * z);
+    const double step = u / (1. + 0.5 * z * u);
+    z -= step;
+    if (std::fabs(step) <= 1e-16 * std::fabs(z)) break;
+  }
+  return z;
+}
+
+int ecckd_cloud_scaling_lognormal(int nfsd, double fsd0, double dfsd, int nq, double *values) {
+  if (nfsd < 1) return fail("ecckd_cloud_scaling_lognormal: nfsd must be at least 1");
+  if (nq < 1) return fail("ecckd_cloud_scaling_lognormal: nq must be at least 1");
+  if (!(fsd0 >= 0.) || !(dfsd > 0.) || !std::isfinite(fsd0) || !std::isfinite(dfsd))
+    return fail("ecckd_cloud_scaling_lognormal: fsd0 must not be negative and dfsd must be greater than 0 (both finite)");
+  if (!values) return fail("ecckd_cloud_scaling_lognormal: null argument (values)");
+  // the bin edges z_j = Phi^-1(j / nq), j = 1 .. nq-1: the lower half solved, the upper half its mirror image
+  std::vector<double> z((size_t)nq + 1, 0.);
+  for (int j = 1; j < nq; ++j) {
+    if (2 * j < nq) z[j] = std_normal_quantile_lower((double)j / (double)nq);
+    else if (2 * j == nq) z[j] = 0.;
+    else z[j] = -std_normal_quantile_lower((double)(nq - j) / (double)nq);
+  }
+  for (int k = 0; k < nfsd; ++k) {
+    const double f = fsd0 + k * dfsd;
+    double *row = values + (size_t)k * nq;
+    if (f == 0.) {
+      for (int j = 0; j < nq; ++j) row[j] = 1.;
+      continue;
+    }
+    const double sigma = std::sqrt(std::log(1. + f * f));
+    double below = 0.;   // Phi(z_j - sigma); z_0 = -inf
+    for (int j = 0; j < nq; ++j) {
+      const double above = j + 1 < nq ? std_normal_cdf(z[j + 1] - sigma) : 1.;
+      row[j] = (double)nq * (above - below);
+      below = above;
+    }
+  }
+  return 0;
+}
+
+int ecckd_cloud_scaling_sample(int device, int ncol, int nlay, int ngpt, int overlap, const double *cloud_frac,
+                               const double *overlap_param, const double *fsd, double fsd_const,
+                               const ecckd_cloud_scaling_t *table, unsigned long long seed, long long col0, float *scaling,
+                               unsigned long long *mask, int memspace, void *stream) {
+  const std::string who = "ecckd_cloud_scaling_sample";
+  if (ngpt > 64) return fail(who + ": the ranks of at most 64 g-points are held at once, not " + std::to_string(ngpt));
+  if (ngpt < 1) return fail(who + ": ngpt must be at least 1");
+  if (overlap != ECCKD_OVERLAP_MAX_RAN && overlap != ECCKD_OVERLAP_EXP_RAN)
+    return fail(who + ": unknown overlap " + std::to_string(overlap) + " (ECCKD_OVERLAP_MAX_RAN = 0, ECCKD_OVERLAP_EXP_RAN = 1)");
+  const bool exp_ran = overlap == ECCKD_OVERLAP_EXP_RAN;
+  if (exp_ran && !overlap_param && nlay > 1) return fail(who + ": ECCKD_OVERLAP_EXP_RAN needs overlap_param");
+  if (check_dims(ncol, nlay)) return 1;
+  if (!cloud_frac || !scaling) return fail(who + ": null argument (cloud_frac and scaling are required)");
+  if (!table) return fail(who + ": null argument (the scaling table)");
+  if (memspace != ECCKD_DEVICE && memspace != ECCKD_HOST) return fail("ecckd: bad memspace");
+  const size_t n2 = (size_t)ncol * nlay, np = exp_ran && nlay > 1 ? (size_t)ncol * (nlay - 1) : 0;
+  if (memspace == ECCKD_HOST) {   // (as ecckd_cloud_mask_sample; fsd is not checked: every value has a meaning)
+    for (size_t i = 0; i < n2; ++i)
+      if (cloud_frac[i] < 0. || cloud_frac[i] > 1.) return fail(who + ": cloud fraction outside [0, 1]");
+    for (size_t i = 0; i < np; ++i)
+      if (overlap_param[i] < 0. || overlap_param[i] > 1.) return fail(who + ": overlap parameter outside [0, 1]");
+  }
+  if (table->device < 0) return fail(who + ": host-only scaling table (device -1): no GPU, no compute (there is no CPU fallback)");
+  if (table->device != device) return fail(who + ": the scaling table lives on device " + std::to_string(table->device) + ", not " + std::to_string(device));
+  if (check_device(device)) return 1;
+  if (ncol == 0) return 0;
+  Stage st(device, memspace, stream, false);
+  ecckd::CloudScalingArgs a{};
+  a.ncol = ncol; a.nlay = nlay; a.ngpt = ngpt; a.exp_ran = exp_ran ? 1 : 0;
+  a.fsd_const = fsd_const; a.nfsd = table->nfsd; a.nq = table->nq; a.fsd0 = table->fsd0; a.dfsd = table->dfsd;
+  a.values = table->dvalues; a.seed = seed; a.col0 = col0;
+  if (st.open([&] {
+        a.cloud_frac = st.in(cloud_frac, n2); a.overlap_param = st.in(np ? overlap_param : nullptr, np); a.fsd = st.in(fsd, n2);
+        a.scaling = static_cast<float *>(st.out_bytes(scaling, n2 * (size_t)ngpt * sizeof(float))); a.mask = st.out(mask, n2);
+      }))
+    return 1;
+  {
+    ProfScope prof("cloud_scaling_sample", st.stream);
+    HIPCHK(ecckd::launch_cloud_scaling_sample(a, st.stream));
+  }
+  return st.close();
+}
+
+size_t ecckd_lw_flux_scaled_scratch_bytes(const ecckd_model_t *m, int ncol, int nlay) {
+  if (!m || ncol <= 0 || nlay <= 0) return 0;
+  return ((size_t)ncol * nlay * m->ng + 32 + fused_scratch_doubles(m, ncol, nlay)) * sizeof(double);
+}
+
+size_t ecckd_sw_flux_scaled_scratch_bytes(const ecckd_model_t *m, int ncol, int nlay, int delta_scale) {
+  if (!m || ncol <= 0 || nlay <= 0) return 0;
+  return SwWork(m, false, ncol, nlay, delta_scale != 0, true).bytes();
+}
+
+int ecckd_lw_flux_scaled(const ecckd_model_t *m, int ncol, int nlay, const double *plev, const double *tlay, const double *tsfc,
+                         const double *tlev, int ngas, const char *gas_names, const double *const *vmr,
+                         const long long *vmr_col_stride, const long long *vmr_lay_stride, const double *vmr_scalar, int top_at_1,
+                         int n_gauss_angles, const double *sfc_emis, const double *inc_flux, int nband_p, const double *tau_p,
+                         const double *ssa_p, const float *cloud_scaling, double *flux_up, double *flux_dn, int memspace,
+                         void *stream) {
+  // (the refusal list of the unmasked all-sky call, in its order; a null scaling is that call)
+  if (lw_fluxes_allsky_refusals(m, nband_p, tau_p, tlev)) return 1;
+  const LwParticles pt{tau_p, ssa_p, nullptr, cloud_scaling};
+  return lw_fluxes_impl(false, m, ncol, nlay, plev, tlay, tsfc, tlev, ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar,
+                        top_at_1, n_gauss_angles, sfc_emis, inc_flux, flux_up, flux_dn, memspace, stream, &pt);
+}
+
+int ecckd_sw_flux_scaled(const ecckd_model_t *m, int ncol, int nlay, const double *plev, const double *tlay, int ngas,
+                         const char *gas_names, const double *const *vmr, const long long *vmr_col_stride,
+                         const long long *vmr_lay_stride, const double *vmr_scalar, int top_at_1, const double *mu0,
+                         const double *toa_scale, const double *sfc_alb_dir, const double *sfc_alb_dif, int nband_p,
+                         const double *tau_p, const double *ssa_p, const double *g_p, int delta_scale, const float *cloud_scaling,
+                         double *flux_up, double *flux_dn, double *flux_dir, int memspace, void *stream) {
+  if (sw_fluxes_allsky_refusals(m, nband_p, tau_p, ssa_p, g_p, delta_scale)) return 1;
+  const SwParticles pt{tau_p, ssa_p, g_p, delta_scale, nullptr, cloud_scaling};
+  return sw_fluxes_impl(false, m, ncol, nlay, plev, tlay, ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar,
+                        top_at_1, mu0, toa_scale, sfc_alb_dir, sfc_alb_dif, flux_up, flux_dn, flux_dir, memspace, stream, &pt);
 }
 
 int ecckd_sw_fluxes_f32(const ecckd_model_t *m, int ncol, int nlay, const float *plev, const float *tlay, int ngas,

@@ -217,8 +217,14 @@ struct RteSwArgs {
   // solver with the expressions of RTE-RRTMGP's increment_2stream_by_2stream (see kernels_optical_props.hip)
   int allsky = 0;
   const double *part_tau = nullptr, *part_ssa = nullptr, *part_g = nullptr;
-  // McICA (ecckd_sw_fluxes_allsky_mcica): as RteLwArgs::part_mask
-  const unsigned long long *part_mask = nullptr;
+  // McICA (ecckd_sw_fluxes_allsky_mcica): as RteLwArgs::part_mask.  In the same storage (so that the kernels of the calls
+  // above keep their argument block), mask_window = 2 (ecckd_sw_flux_scaled; two-pass solver, fp64): the sampled
+  // optical-depth scaling, float32 (ncol,nlay,ng); the cell's particulate optical depth is part_tau * scaling in front of
+  // the all-sky expressions
+  union {
+    const unsigned long long *part_mask = nullptr;
+    const float *part_scaling;
+  };
   // Band window (ecckd_sw_flux_bands; fp64, with part_mask): the launch covers the g-points mask_first .. mask_first + ng - 1
   // of the model -- tau, rayleigh, solar and the outputs are that band's own -- and g-point g of the launch sees bit
   // mask_first + g of the mask word.  mask_window = 0: bit g (the kernels of the calls above).
@@ -259,6 +265,9 @@ struct OptPropsArgs {
   // ecckd_increment_masked: one word per (column, layer), bit g clear = the cell is incremented as if tau2 were +0 there
   // (ng <= 64); null: the unmasked kernels
   const unsigned long long *mask = nullptr;
+  // ecckd_increment_scaled: float32 (ncol,nlay,ng) whatever the precision of the call; the g-point is incremented by
+  // tau2 * scaling, the products formed per g-point (any ng); null: the kernels above.  Not together with `mask`.
+  const float *scaling = nullptr;
 };
 // eps = 3 * tiny(1._wp): the floor of the denominators in those kernels (and where the all-sky solver forms ssa and g)
 template <typename real> __host__ __device__ constexpr real op_eps() {
@@ -332,6 +341,23 @@ hipError_t launch_heating_rate(const HeatingRateArgs &a, hipStream_t s);
 // cloud_frac (ncol,nlay), overlap_param (ncol,nlay-1; exp_ran only), mask (ncol,nlay); 1 <= ngpt <= 64
 hipError_t launch_cloud_mask_sample(int ncol, int nlay, int ngpt, int exp_ran, const double *cloud_frac, const double *overlap_param,
                                     unsigned long long seed, long long col0, unsigned long long *mask, hipStream_t s);
+// Sampled optical-depth scaling (same file; the definition is in include/ecckd_hip.h, ecckd_cloud_scaling_sample): the
+// ranks of launch_cloud_mask_sample, read as the position inside the cloud, through the table values(nfsd,nq) (device,
+// q fastest) at the cell's fsd(ncol,nlay) -- null: fsd_const everywhere -- to scaling (ncol,nlay,ngpt) float32; mask
+// (ncol,nlay) or null.  A table of at most kCloudOpticsLdsBytes is staged in LDS, a larger one is read through L2.
+struct CloudScalingArgs {
+  int ncol, nlay, ngpt, exp_ran;
+  const double *cloud_frac, *overlap_param, *fsd;
+  double fsd_const;
+  int nfsd, nq;
+  double fsd0, dfsd;
+  const double *values;
+  unsigned long long seed;
+  long long col0;
+  float *scaling;
+  unsigned long long *mask;
+};
+hipError_t launch_cloud_scaling_sample(const CloudScalingArgs &a, hipStream_t s);
 
 // Spectral-output solvers (kernels_rte_gpt.hip): RTE-RRTMGP's kernel-level interfaces.  LW uses tau, lay_source,
 // lev_source_*, sfc_emis(ncol,ng), sfc_src(ncol,ng), inc_flux(ncol,ng)|null, Ds/wts; SW uses tau, ssa, g, mu0(ncol),

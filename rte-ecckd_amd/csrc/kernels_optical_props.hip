@@ -28,9 +28,13 @@ constexpr int kOpMaxBlocks = 8192;   // 32 blocks of 256 threads per CU (a full 
 // MASKED (increment_masked_kernel; ecckd_increment_masked): where bit g of the cell's word a.mask(column, layer) is clear
 // the g-point is incremented as if tau2 were +0 there -- the same operations on a zero optical depth (what RTE-RRTMGP's
 // draw_samples followed by increment computes), so ssa2 / g2 are still read and multiplied.
-// The kernels (increment_kernel, increment_masked_kernel, below) are thin entries to this body.
-template <typename real, bool OP1_2STR, bool OP2_2STR, bool BYBAND, bool MASKED>
+// SCALED (increment_scaled_kernel; ecckd_increment_scaled): the g-point is incremented by t2 = tau2 * scaling(column,
+// layer, g) -- float32 whatever `real` is --, and increment's products t2 * (1 - ssa2), t2 * ssa2 and that times g2 are
+// formed per g-point from t2, not once per band; any number of g-points.
+// The kernels (increment_kernel, increment_masked_kernel, increment_scaled_kernel, below) are thin entries to this body.
+template <typename real, bool OP1_2STR, bool OP2_2STR, bool BYBAND, bool MASKED, bool SCALED = false>
 __device__ __forceinline__ void increment_body(const OptPropsArgs &a) {
+  static_assert(!(MASKED && SCALED), "a scaling of 0 is the clear bit: one or the other");
   const size_t n2 = (size_t)a.ncol * a.nlay;
   real *tau1 = reinterpret_cast<real *>(a.tau1), *ssa1 = reinterpret_cast<real *>(a.ssa1), *g1 = reinterpret_cast<real *>(a.g1);
   const real *tau2 = reinterpret_cast<const real *>(a.tau2), *ssa2 = reinterpret_cast<const real *>(a.ssa2),
@@ -56,8 +60,14 @@ __device__ __forceinline__ void increment_body(const OptPropsArgs &a) {
       for (int g = glo; g < ghi; ++g) {
         const size_t q = cell + n2 * g;
         const bool seen = MASKED ? ((word >> g) & 1ull) != 0ull : true;
-        const real t2 = seen ? t2_in : real(0), tabs2 = seen ? tabs2_in : tabs2_0;
-        const real tscat2 = seen ? tscat2_in : tscat2_0, tsg2 = seen ? tsg2_in : tsg2_0;
+        real t2 = seen ? t2_in : real(0), tabs2 = seen ? tabs2_in : tabs2_0;
+        real tscat2 = seen ? tscat2_in : tscat2_0, tsg2 = seen ? tsg2_in : tsg2_0;
+        if constexpr (SCALED) {
+          t2 = t2_in * (real)a.scaling[q];
+          tabs2 = OP2_2STR ? t2 * (real(1) - s2) : t2;
+          tscat2 = t2 * s2;
+          tsg2 = tscat2 * gg2;
+        }
         if constexpr (!OP1_2STR) {
           tau1[q] = tau1[q] + tabs2;
         } else if constexpr (!OP2_2STR) {
@@ -86,6 +96,11 @@ __global__ void __launch_bounds__(kOpBlock) increment_kernel(const OptPropsArgs 
 template <typename real, bool OP1_2STR, bool OP2_2STR, bool BYBAND>
 __global__ void __launch_bounds__(kOpBlock) increment_masked_kernel(const OptPropsArgs a) {
   increment_body<real, OP1_2STR, OP2_2STR, BYBAND, true>(a);
+}
+
+template <typename real, bool OP1_2STR, bool OP2_2STR, bool BYBAND>
+__global__ void __launch_bounds__(kOpBlock) increment_scaled_kernel(const OptPropsArgs a) {
+  increment_body<real, OP1_2STR, OP2_2STR, BYBAND, false, true>(a);
 }
 
 template <typename real, bool FORWARD>
@@ -121,6 +136,12 @@ hipError_t launch_increment_t(const OptPropsArgs &a, hipStream_t s) {
     else if (!two) k = bb ? increment_masked_kernel<real, true, false, true> : increment_masked_kernel<real, true, false, false>;
     else k = bb ? increment_masked_kernel<real, true, true, true> : increment_masked_kernel<real, true, true, false>;
   }
+  if (a.scaling) {
+    if (!one && !two) k = bb ? increment_scaled_kernel<real, false, false, true> : increment_scaled_kernel<real, false, false, false>;
+    else if (!one) k = bb ? increment_scaled_kernel<real, false, true, true> : increment_scaled_kernel<real, false, true, false>;
+    else if (!two) k = bb ? increment_scaled_kernel<real, true, false, true> : increment_scaled_kernel<real, true, false, false>;
+    else k = bb ? increment_scaled_kernel<real, true, true, true> : increment_scaled_kernel<real, true, true, false>;
+  }
   hipLaunchKernelGGL(k, dim3(op_blocks((size_t)a.ncol * a.nlay)), dim3(kOpBlock), 0, s, a);
   return hipGetLastError();
 }
@@ -143,7 +164,7 @@ hipError_t launch_delta_scale_t(size_t n, const double *tau, const double *ssa, 
 
 hipError_t launch_increment(const OptPropsArgs &a, hipStream_t s) {
   if (a.ncol <= 0 || a.nlay <= 0 || a.ng <= 0) return hipSuccess;
-  if (a.mask && a.ng > 64) return hipErrorInvalidValue;
+  if (a.mask && (a.ng > 64 || a.scaling)) return hipErrorInvalidValue;
   return a.f32 ? launch_increment_t<float>(a, s) : launch_increment_t<double>(a, s);
 }
 

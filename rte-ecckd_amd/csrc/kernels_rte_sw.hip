@@ -88,8 +88,13 @@ __device__ __forceinline__ void acc_add(double *p, double v, bool owner) {
 template <typename real> struct SwPart { real t, s, g; unsigned m; };
 // WIN (with MASK; ecckd_sw_flux_bands): the launch covers a band of the model and its g-point g sees bit
 // RteSwArgs::mask_first + g of the mask word, as in rte_sw_sys_body.
-template <typename real, int CW, bool FAST, bool CLAMP, bool DERIVE, bool ALLSKY = false, bool MASK = false, bool WIN = false>
+// SCALE (with ALLSKY, without MASK; ecckd_sw_flux_scaled): the cell's float32 optical-depth scaling (RteSwArgs::part_scaling,
+// one value per (column, layer, g-point), at the index of tau) rides in the slot of the mask half-word, as its bits; the
+// cell uses the particulate optical depth tp * scaling in front of the same expressions.
+template <typename real, int CW, bool FAST, bool CLAMP, bool DERIVE, bool ALLSKY = false, bool MASK = false, bool WIN = false,
+          bool SCALE = false>
 __device__ __forceinline__ void rte_sw_body(const RteSwArgs &a) {
+  static_assert(!SCALE || (ALLSKY && !MASK), "the scaling belongs to the all-sky form and stands in the mask's place");
   static_assert(DERIVE || !ALLSKY, "the all-sky form extends the fused (DERIVE) form");
   static_assert(ALLSKY || !MASK, "a cloud mask belongs to the all-sky form");
   static_assert(MASK || !WIN, "a band window concerns the mask bit alone");
@@ -157,6 +162,7 @@ __device__ __forceinline__ void rte_sw_body(const RteSwArgs &a) {
           const long qb = cc + (long)ncol * (lm + (long)nlay * band);
           pp.t = P(a.part_tau)[qb]; pp.s = P(a.part_ssa)[qb]; pp.g = P(a.part_g)[qb];
           if constexpr (MASK) pp.m = reinterpret_cast<const unsigned *>(a.part_mask)[2 * (cc + (long)ncol * lm) + (gm >> 5)];
+          if constexpr (SCALE) pp.m = reinterpret_cast<const unsigned *>(a.part_scaling)[q];
         }
         if constexpr (DERIVE) { x = P(a.plev)[cc + (long)ncol * lm]; y = P(a.plev)[cc + (long)ncol * (lm + 1)]; }
         else { x = P(a.ssa)[q]; y = P(a.g)[q]; }
@@ -168,6 +174,7 @@ __device__ __forceinline__ void rte_sw_body(const RteSwArgs &a) {
           const real tau_r = ((y - x) * gw) * ray;             // :313-316: the Rayleigh optical depth, tau*ssa of the gas optics
           real tp = pp.t;
           if constexpr (MASK) tp = (pp.m >> (gm & 31)) & 1u ? tp : real(0);
+          if constexpr (SCALE) tp = tp * (real)__uint_as_float(pp.m);
           const real tsp = tp * pp.s;
           const real ts = tau_r + tsp, tau12 = ctau + tp;      // increment_2stream_by_2stream
           const real cg = (tsp * pp.g) / (ts > eps ? ts : eps);
@@ -316,6 +323,12 @@ __global__ void __launch_bounds__(64, ECCKD_SW_WAVES_PER_SIMD) rte_sw_mcica_kern
   rte_sw_body<double, CW, true, CLAMP, true, true, true>(a);
 }
 
+// ... with a sampled optical-depth scaling (RteSwArgs::part_scaling) in the mask's place, under its own name
+template <int CW, bool CLAMP>
+__global__ void __launch_bounds__(64, ECCKD_SW_WAVES_PER_SIMD) rte_sw_scaled_kernel(const RteSwArgs a) {
+  rte_sw_body<double, CW, true, CLAMP, true, true, false, false, true>(a);
+}
+
 // ... on a band window of the model (ecckd_sw_flux_bands with a mask), under its own name
 template <int CW, bool CLAMP>
 __global__ void __launch_bounds__(64, ECCKD_SW_WAVES_PER_SIMD) rte_sw_mcica_bands_kernel(const RteSwArgs a) {
@@ -442,9 +455,12 @@ hipError_t launch_rte_sw(const RteSwArgs &a, hipStream_t s) {
   constexpr int CW = ECCKD_SW_CW;
   // (the all-sky form exists in the fast arithmetic mode only; ecckd_sw_fluxes_allsky refuses the rest with a message)
   if (a.allsky && (a.exact_division || !a.derive)) return hipErrorInvalidValue;
-  if (a.allsky && a.part_mask && (a.mask_window ? a.mask_first < 0 || a.mask_first + a.ng > 64 || a.f32 : a.ng > 64))
+  if (a.allsky && a.part_mask && a.mask_window != 2 && (a.mask_window ? a.mask_first < 0 || a.mask_first + a.ng > 64 || a.f32 : a.ng > 64))
     return hipErrorInvalidValue;
-  auto k = a.allsky && a.part_mask && a.mask_window
+  const bool scaled = a.mask_window == 2;   // (part_scaling in part_mask's storage)
+  if (scaled && (!a.allsky || !a.part_scaling || a.f32)) return hipErrorInvalidValue;
+  auto k = scaled ? (a.dir_clamp ? rte_sw_scaled_kernel<CW, true> : rte_sw_scaled_kernel<CW, false>)
+           : a.allsky && a.part_mask && a.mask_window
                ? (a.dir_clamp ? rte_sw_mcica_bands_kernel<CW, true> : rte_sw_mcica_bands_kernel<CW, false>)
            : a.allsky && a.f32 ? (a.part_mask ? (a.dir_clamp ? rte_sw_mcica_f32_kernel<CW, true> : rte_sw_mcica_f32_kernel<CW, false>)
                                             : (a.dir_clamp ? rte_sw_allsky_f32_kernel<CW, true> : rte_sw_allsky_f32_kernel<CW, false>))

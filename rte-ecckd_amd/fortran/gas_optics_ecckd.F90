@@ -61,6 +61,9 @@ module gas_optics_ecckd
     procedure, public :: sw_flux_bands      !< extension: sw_fluxes / sw_fluxes_allsky with one flux plane per band of the model
     procedure, public :: sw_fluxes_daylit   !< extension: sw_fluxes on the columns with mu0 > mu0_min only, zeros in the others
     procedure, public :: sample_cloud_mask  !< extension: McICA cloud mask from cloud fractions (ecckd_cloud_mask_sample)
+    procedure, public :: sample_cloud_scaling  !< extension: sampled optical-depth scaling (ecckd_cloud_scaling_sample)
+    procedure, public :: lw_flux_scaled     !< extension: lw_fluxes_allsky with a sampled optical-depth scaling (ecckd_lw_flux_scaled)
+    procedure, public :: sw_flux_scaled     !< extension: sw_fluxes_allsky with a sampled optical-depth scaling (ecckd_sw_flux_scaled)
   end type ty_gas_optics_ecckd
 
   interface
@@ -405,6 +408,72 @@ module gas_optics_ecckd
       type(c_ptr), value :: stream
       integer(c_int) :: rc
     end function c_cloud_mask_sample
+    function c_cloud_scaling_create(device, nfsd, fsd0, dfsd, nq, values, table) bind(C, name="ecckd_cloud_scaling_create") &
+        result(rc)
+      import c_ptr, c_int, c_double
+      integer(c_int), value :: device, nfsd, nq
+      real(c_double), value :: fsd0, dfsd
+      real(c_double), dimension(*), intent(in) :: values
+      type(c_ptr), intent(out) :: table
+      integer(c_int) :: rc
+    end function c_cloud_scaling_create
+    subroutine c_cloud_scaling_destroy(table) bind(C, name="ecckd_cloud_scaling_destroy")
+      import c_ptr
+      type(c_ptr), value :: table
+    end subroutine c_cloud_scaling_destroy
+    function c_cloud_scaling_lognormal(nfsd, fsd0, dfsd, nq, values) bind(C, name="ecckd_cloud_scaling_lognormal") result(rc)
+      import c_int, c_double
+      integer(c_int), value :: nfsd, nq
+      real(c_double), value :: fsd0, dfsd
+      real(c_double), dimension(*), intent(inout) :: values
+      integer(c_int) :: rc
+    end function c_cloud_scaling_lognormal
+    function c_cloud_scaling_sample(device, ncol, nlay, ngpt, overlap, cloud_frac, overlap_param, fsd, fsd_const, table, seed, &
+                                    col0, scaling, mask, memspace, stream) bind(C, name="ecckd_cloud_scaling_sample") result(rc)
+      import c_ptr, c_int, c_double, c_int64_t, c_float
+      integer(c_int), value :: device, ncol, nlay, ngpt, overlap, memspace
+      real(c_double), dimension(*), intent(in) :: cloud_frac
+      type(c_ptr), value :: overlap_param, fsd, table, mask
+      real(c_double), value :: fsd_const
+      integer(c_int64_t), value :: seed, col0           ! (seed: the bits of the C unsigned 64-bit word)
+      real(c_float), dimension(*), intent(inout) :: scaling
+      type(c_ptr), value :: stream
+      integer(c_int) :: rc
+    end function c_cloud_scaling_sample
+    function c_lw_flux_scaled(model, ncol, nlay, plev, tlay, tsfc, tlev, ngas, gas_names, vmr, cs, ls, scalar, top_at_1, nmus, &
+                              sfc_emis, inc_flux, nband_p, tau_p, ssa_p, cloud_scaling, flux_up, flux_dn, memspace, stream) &
+        bind(C, name="ecckd_lw_flux_scaled") result(rc)
+      import c_ptr, c_int, c_double, c_char, c_long_long, c_float
+      type(c_ptr), value :: model
+      integer(c_int), value :: ncol, nlay, ngas, top_at_1, nmus, nband_p, memspace
+      real(c_double), dimension(*), intent(in) :: plev, tlay, tsfc, tlev, sfc_emis, tau_p
+      character(kind=c_char), dimension(*), intent(in) :: gas_names
+      type(c_ptr), dimension(*), intent(in) :: vmr
+      integer(c_long_long), dimension(*), intent(in) :: cs, ls
+      real(c_double), dimension(*), intent(in) :: scalar
+      type(c_ptr), value :: inc_flux, ssa_p
+      real(c_float), dimension(*), intent(in) :: cloud_scaling
+      real(c_double), dimension(*), intent(inout) :: flux_up, flux_dn
+      type(c_ptr), value :: stream
+      integer(c_int) :: rc
+    end function c_lw_flux_scaled
+    function c_sw_flux_scaled(model, ncol, nlay, plev, tlay, ngas, gas_names, vmr, cs, ls, scalar, top_at_1, mu0, toa_scale, &
+                              sfc_alb_dir, sfc_alb_dif, nband_p, tau_p, ssa_p, g_p, delta_scale, cloud_scaling, flux_up, flux_dn, &
+                              flux_dir, memspace, stream) bind(C, name="ecckd_sw_flux_scaled") result(rc)
+      import c_ptr, c_int, c_double, c_char, c_long_long, c_float
+      type(c_ptr), value :: model
+      integer(c_int), value :: ncol, nlay, ngas, top_at_1, nband_p, delta_scale, memspace
+      real(c_double), dimension(*), intent(in) :: plev, tlay, mu0, sfc_alb_dir, sfc_alb_dif, tau_p, ssa_p, g_p
+      character(kind=c_char), dimension(*), intent(in) :: gas_names
+      type(c_ptr), dimension(*), intent(in) :: vmr
+      integer(c_long_long), dimension(*), intent(in) :: cs, ls
+      real(c_double), dimension(*), intent(in) :: scalar
+      type(c_ptr), value :: toa_scale, flux_dir
+      real(c_float), dimension(*), intent(in) :: cloud_scaling
+      real(c_double), dimension(*), intent(inout) :: flux_up, flux_dn
+      type(c_ptr), value :: stream
+      integer(c_int) :: rc
+    end function c_sw_flux_scaled
     function c_model_device(model) bind(C, name="ecckd_model_get_device") result(dev)
       import c_ptr, c_int
       type(c_ptr), value :: model
@@ -446,6 +515,17 @@ module gas_optics_ecckd
   end interface
 
   integer, parameter, public :: ECCKD_OVERLAP_MAX_RAN = 0, ECCKD_OVERLAP_EXP_RAN = 1
+
+  !> Extension: the table of in-cloud water variability (ecckd_cloud_scaling_create; include/ecckd_hip.h, "In-cloud water
+  !! variability"): values (nq, nfsd), row k (second index) the scalings of the nq equal-probability bins at the fractional
+  !! standard deviation fsd0 + (k-1)*dfsd.  It lives on the device of the model it is loaded for.
+  type, public :: ty_cloud_scaling
+    type(c_ptr) :: handle = c_null_ptr
+  contains
+    procedure, public :: load_lognormal => cloud_scaling_load_lognormal
+    procedure, public :: load_table => cloud_scaling_load_table
+    procedure, public :: finalize => cloud_scaling_finalize
+  end type ty_cloud_scaling
 
   public :: c_error_message, c_loc_3d, c_loc_2d
 
@@ -1615,6 +1695,285 @@ contains
     end if
     cloud_mask = words
   end function sample_cloud_mask
+
+  !> The lognormal table of ecckd_cloud_scaling_lognormal (bin means of the unit-mean distribution) on the device of `model`.
+  function cloud_scaling_load_lognormal(this, model, nfsd, fsd0, dfsd, nq) result(error_msg)
+    class(ty_cloud_scaling), intent(inout) :: this
+    class(ty_gas_optics_ecckd), intent(in) :: model
+    integer, intent(in) :: nfsd, nq
+    real(wp), intent(in) :: fsd0, dfsd
+    character(len=128) :: error_msg
+    real(c_double), dimension(:,:), allocatable :: values
+    error_msg = ""
+    allocate(values(max(nq, 1), max(nfsd, 1)))
+    if (c_cloud_scaling_lognormal(int(nfsd, c_int), real(fsd0, c_double), real(dfsd, c_double), int(nq, c_int), values) /= 0) then
+      error_msg = c_error_message()
+      return
+    end if
+    error_msg = this%load_table(model, values, fsd0, dfsd)
+  end function cloud_scaling_load_lognormal
+
+  !> A table of the host's own: values (nq, nfsd).
+  function cloud_scaling_load_table(this, model, values, fsd0, dfsd) result(error_msg)
+    class(ty_cloud_scaling), intent(inout) :: this
+    class(ty_gas_optics_ecckd), intent(in) :: model
+    real(wp), dimension(:,:), intent(in) :: values
+    real(wp), intent(in) :: fsd0, dfsd
+    character(len=128) :: error_msg
+    real(c_double), dimension(:,:), allocatable :: v
+    error_msg = ""
+    call this%finalize()
+    allocate(v(size(values, 1), size(values, 2)))
+    v = values
+    if (c_cloud_scaling_create(c_model_device(model%handle), int(size(v, 2), c_int), real(fsd0, c_double), real(dfsd, c_double), &
+                               int(size(v, 1), c_int), v, this%handle) /= 0) then
+      this%handle = c_null_ptr
+      error_msg = c_error_message()
+    end if
+  end function cloud_scaling_load_table
+
+  subroutine cloud_scaling_finalize(this)
+    class(ty_cloud_scaling), intent(inout) :: this
+    if (c_associated(this%handle)) call c_cloud_scaling_destroy(this%handle)
+    this%handle = c_null_ptr
+  end subroutine cloud_scaling_finalize
+
+  !> Extension: the sampled optical-depth scaling of ecckd_cloud_scaling_sample (the definition is in include/ecckd_hip.h;
+  !! parity with ecRad and RTE-RRTMGP is unpinned) for this model's g-points: cloud_frac, overlap, seed, col0, overlap_param
+  !! as sample_cloud_mask; fsd (ncol, nlay), or fsd_const for every cell (fsd wins).  cloud_scaling (ncol, nlay, ngpt),
+  !! single precision: 0 where the g-point does not see the layer's cloud.  cloud_mask (ncol, nlay), optional: the words of
+  !! sample_cloud_mask.
+  function sample_cloud_scaling(this, table, cloud_frac, overlap, seed, col0, cloud_scaling, fsd, fsd_const, overlap_param, &
+                                cloud_mask) result(error_msg)
+    class(ty_gas_optics_ecckd), intent(in) :: this
+    type(ty_cloud_scaling), intent(in) :: table
+    real(wp), dimension(:,:), intent(in) :: cloud_frac
+    integer, intent(in) :: overlap
+    integer(c_int64_t), intent(in) :: seed, col0
+    real(c_float), dimension(:,:,:), intent(inout) :: cloud_scaling
+    real(wp), dimension(:,:), intent(in), optional :: fsd
+    real(wp), intent(in), optional :: fsd_const
+    real(wp), dimension(:,:), intent(in), optional :: overlap_param
+    integer(c_int64_t), dimension(:,:), intent(inout), optional :: cloud_mask
+    character(len=128) :: error_msg
+    real(wp), dimension(:,:), allocatable, target :: alpha, f
+    integer(c_int64_t), dimension(:,:), allocatable, target :: words
+    real(c_float), dimension(:,:,:), allocatable :: s
+    type(c_ptr) :: alpha_p, f_p, words_p
+    real(c_double) :: fc
+    integer :: ncol, nlay, ng
+    integer(c_int) :: rc
+    error_msg = ""
+    ncol = size(cloud_frac, 1)
+    nlay = size(cloud_frac, 2)
+    ng = this%get_ngpt()
+    if (any(shape(cloud_scaling) /= [ncol, nlay, ng])) then
+      error_msg = "sample_cloud_scaling: cloud_scaling inconsistently sized"
+      return
+    end if
+    alpha_p = c_null_ptr; f_p = c_null_ptr; words_p = c_null_ptr
+    fc = 0._c_double
+    if (present(fsd_const)) fc = real(fsd_const, c_double)
+    if (present(fsd)) then
+      if (any(shape(fsd) /= shape(cloud_frac))) then
+        error_msg = "sample_cloud_scaling: fsd inconsistently sized"
+        return
+      end if
+      allocate(f(ncol, nlay))
+      f = fsd
+      if (size(f) > 0) f_p = c_loc(f(1, 1))
+    else if (.not. present(fsd_const)) then
+      error_msg = "sample_cloud_scaling: fsd or fsd_const is required"
+      return
+    end if
+    if (present(overlap_param)) then
+      if (size(overlap_param, 1) /= ncol .or. size(overlap_param, 2) /= nlay - 1) then
+        error_msg = "sample_cloud_scaling: overlap_param inconsistently sized"
+        return
+      end if
+      allocate(alpha(ncol, max(nlay - 1, 1)))
+      alpha(:, 1:nlay - 1) = overlap_param
+      alpha_p = c_loc(alpha(1, 1))
+    end if
+    if (present(cloud_mask)) then
+      if (size(cloud_mask, 1) /= ncol .or. size(cloud_mask, 2) /= nlay) then
+        error_msg = "sample_cloud_scaling: cloud_mask inconsistently sized"
+        return
+      end if
+      allocate(words(ncol, nlay))
+      if (size(words) > 0) words_p = c_loc(words(1, 1))
+    end if
+    allocate(s(ncol, nlay, ng))
+    rc = c_cloud_scaling_sample(c_model_device(this%handle), int(ncol, c_int), int(nlay, c_int), int(ng, c_int), &
+                                int(overlap, c_int), cloud_frac, alpha_p, f_p, fc, table%handle, seed, col0, s, words_p, &
+                                ECCKD_HOST, c_null_ptr)
+    if (rc /= 0) then
+      error_msg = c_error_message()
+      return
+    end if
+    cloud_scaling = s
+    if (present(cloud_mask)) cloud_mask = words
+  end function sample_cloud_scaling
+
+  !> Extension: lw_fluxes_allsky with the particulate optical depth of every (layer, g-point) cell multiplied by
+  !! cloud_scaling (ncol, nlay, ngpt), single precision (ecckd_lw_flux_scaled): what gas_optics + increment_scaled by band +
+  !! rte_lw give, bit for bit.  tau_p (ncol, nlay, nband) with ssa_p (absorption optical depth) or without (one-stream).
+  !! Host arrays in, host fluxes out; no input is written.
+  function lw_flux_scaled(this, plev, tlay, tsfc, tlev, gas_desc, top_at_1, sfc_emis, tau_p, cloud_scaling, flux_up, flux_dn, &
+                          ssa_p, n_gauss_angles, inc_flux) result(error_msg)
+    class(ty_gas_optics_ecckd), intent(in) :: this
+    real(wp), dimension(:,:), intent(in) :: plev, tlay, tlev
+    real(wp), dimension(:), intent(in) :: tsfc
+    type(ty_gas_concs), intent(in) :: gas_desc
+    logical, intent(in) :: top_at_1
+    real(wp), dimension(:,:), intent(in) :: sfc_emis
+    real(wp), dimension(:,:,:), intent(in) :: tau_p
+    real(c_float), dimension(:,:,:), intent(in) :: cloud_scaling
+    real(wp), dimension(:,:), intent(inout) :: flux_up, flux_dn
+    real(wp), dimension(:,:,:), intent(in), optional :: ssa_p
+    integer, intent(in), optional :: n_gauss_angles
+    real(wp), dimension(:,:), intent(in), optional :: inc_flux
+    character(len=128) :: error_msg
+    character(kind=c_char), dimension(:), allocatable :: names
+    type(c_ptr), dimension(:), allocatable :: ptr
+    integer(c_long_long), dimension(:), allocatable :: cs, ls
+    real(c_double), dimension(:), allocatable :: scalar
+    real(wp), dimension(:,:,:), allocatable, target :: ssa
+    real(wp), dimension(:,:), allocatable, target :: incf
+    real(wp), dimension(:,:), allocatable :: up, dn
+    type(c_ptr) :: ssa_c, incf_c
+    integer :: ncol, nlay, n, nmus
+    integer(c_int) :: rc
+    ncol = size(tlay, 1)
+    nlay = size(tlay, 2)
+    nmus = 1
+    if (present(n_gauss_angles)) nmus = n_gauss_angles
+    error_msg = marshal_gases(this, gas_desc, ncol, nlay, names, ptr, cs, ls, scalar)
+    if (trim(error_msg) /= "") return
+    if (size(sfc_emis, 1) /= this%get_nband() .or. size(sfc_emis, 2) /= ncol) then
+      error_msg = "lw_flux_scaled: sfc_emis inconsistently sized"
+      return
+    end if
+    if (size(tau_p, 1) /= ncol .or. size(tau_p, 2) /= nlay) then
+      error_msg = "lw_flux_scaled: tau_p inconsistently sized"
+      return
+    end if
+    if (any(shape(cloud_scaling) /= [ncol, nlay, this%get_ngpt()])) then
+      error_msg = "lw_flux_scaled: cloud_scaling inconsistently sized"
+      return
+    end if
+    if (any(shape(flux_up) /= [ncol, nlay + 1]) .or. any(shape(flux_dn) /= [ncol, nlay + 1])) then
+      error_msg = "lw_flux_scaled: flux_up, flux_dn inconsistently sized"
+      return
+    end if
+    ssa_c = c_null_ptr; incf_c = c_null_ptr
+    if (present(ssa_p)) then
+      if (any(shape(ssa_p) /= shape(tau_p))) then
+        error_msg = "lw_flux_scaled: ssa_p inconsistently sized"
+        return
+      end if
+      allocate(ssa(ncol, nlay, size(tau_p, 3)))
+      ssa = ssa_p
+      if (size(ssa) > 0) ssa_c = c_loc(ssa(1, 1, 1))
+    end if
+    if (present(inc_flux)) then
+      if (size(inc_flux, 1) /= ncol .or. size(inc_flux, 2) /= this%get_ngpt()) then
+        error_msg = "lw_flux_scaled: inc_flux inconsistently sized"
+        return
+      end if
+      allocate(incf(ncol, size(inc_flux, 2)))
+      incf = inc_flux
+      if (size(incf) > 0) incf_c = c_loc(incf(1, 1))
+    end if
+    n = gas_desc%get_num_gases()
+    allocate(up(ncol, nlay + 1), dn(ncol, nlay + 1))
+    rc = c_lw_flux_scaled(this%handle, int(ncol, c_int), int(nlay, c_int), plev, tlay, tsfc, tlev, int(n, c_int), names, ptr, cs, &
+                          ls, scalar, merge(1_c_int, 0_c_int, top_at_1), int(nmus, c_int), sfc_emis, incf_c, &
+                          int(size(tau_p, 3), c_int), tau_p, ssa_c, cloud_scaling, up, dn, ECCKD_HOST, c_null_ptr)
+    if (rc /= 0) then
+      error_msg = c_error_message()
+      return
+    end if
+    flux_up = up
+    flux_dn = dn
+  end function lw_flux_scaled
+
+  !> Extension: sw_fluxes_allsky with the particulate optical depth of every (layer, g-point) cell -- after the delta
+  !! scaling -- multiplied by cloud_scaling (ncol, nlay, ngpt), single precision (ecckd_sw_flux_scaled).  tau_p / ssa_p / g_p
+  !! (ncol, nlay, nband); delta_scale as in sw_fluxes_allsky (default .true.); toa_scale (ncol); flux_dir optional.
+  function sw_flux_scaled(this, plev, tlay, gas_desc, top_at_1, mu0, sfc_alb_dir, sfc_alb_dif, tau_p, ssa_p, g_p, cloud_scaling, &
+                          flux_up, flux_dn, flux_dir, delta_scale, toa_scale) result(error_msg)
+    class(ty_gas_optics_ecckd), intent(in) :: this
+    real(wp), dimension(:,:), intent(in) :: plev, tlay
+    type(ty_gas_concs), intent(in) :: gas_desc
+    logical, intent(in) :: top_at_1
+    real(wp), dimension(:), intent(in) :: mu0
+    real(wp), dimension(:,:), intent(in) :: sfc_alb_dir, sfc_alb_dif
+    real(wp), dimension(:,:,:), intent(in) :: tau_p, ssa_p, g_p
+    real(c_float), dimension(:,:,:), intent(in) :: cloud_scaling
+    real(wp), dimension(:,:), intent(inout) :: flux_up, flux_dn
+    real(wp), dimension(:,:), intent(inout), optional :: flux_dir
+    logical, intent(in), optional :: delta_scale
+    real(wp), dimension(:), intent(in), optional :: toa_scale
+    character(len=128) :: error_msg
+    character(kind=c_char), dimension(:), allocatable :: names
+    type(c_ptr), dimension(:), allocatable :: ptr
+    integer(c_long_long), dimension(:), allocatable :: cs, ls
+    real(c_double), dimension(:), allocatable :: scalar
+    real(wp), dimension(:,:), allocatable, target :: dir
+    real(wp), dimension(:,:), allocatable :: up, dn
+    real(wp), dimension(:), allocatable, target :: scale
+    type(c_ptr) :: scale_c, dir_c
+    integer :: ncol, nlay, n, nband
+    integer(c_int) :: rc, ds
+    ncol = size(tlay, 1)
+    nlay = size(tlay, 2)
+    nband = this%get_nband()
+    ds = 1_c_int
+    if (present(delta_scale)) ds = merge(1_c_int, 0_c_int, delta_scale)
+    error_msg = marshal_gases(this, gas_desc, ncol, nlay, names, ptr, cs, ls, scalar)
+    if (trim(error_msg) /= "") return
+    if (size(sfc_alb_dir, 1) /= nband .or. size(sfc_alb_dir, 2) /= ncol .or. &
+        size(sfc_alb_dif, 1) /= nband .or. size(sfc_alb_dif, 2) /= ncol) then
+      error_msg = "sw_flux_scaled: surface albedos inconsistently sized"
+      return
+    end if
+    if (size(tau_p, 1) /= ncol .or. size(tau_p, 2) /= nlay .or. any(shape(ssa_p) /= shape(tau_p)) .or. &
+        any(shape(g_p) /= shape(tau_p))) then
+      error_msg = "sw_flux_scaled: tau_p, ssa_p, g_p inconsistently sized"
+      return
+    end if
+    if (any(shape(cloud_scaling) /= [ncol, nlay, this%get_ngpt()])) then
+      error_msg = "sw_flux_scaled: cloud_scaling inconsistently sized"
+      return
+    end if
+    if (any(shape(flux_up) /= [ncol, nlay + 1]) .or. any(shape(flux_dn) /= [ncol, nlay + 1])) then
+      error_msg = "sw_flux_scaled: flux_up, flux_dn inconsistently sized"
+      return
+    end if
+    scale_c = c_null_ptr; dir_c = c_null_ptr
+    if (present(toa_scale)) then
+      allocate(scale(ncol))
+      scale = toa_scale
+      if (ncol > 0) scale_c = c_loc(scale(1))
+    end if
+    if (present(flux_dir)) then
+      allocate(dir(ncol, nlay + 1))
+      if (size(dir) > 0) dir_c = c_loc(dir(1, 1))
+    end if
+    n = gas_desc%get_num_gases()
+    allocate(up(ncol, nlay + 1), dn(ncol, nlay + 1))
+    rc = c_sw_flux_scaled(this%handle, int(ncol, c_int), int(nlay, c_int), plev, tlay, int(n, c_int), names, ptr, cs, ls, scalar, &
+                          merge(1_c_int, 0_c_int, top_at_1), mu0, scale_c, sfc_alb_dir, sfc_alb_dif, int(size(tau_p, 3), c_int), &
+                          tau_p, ssa_p, g_p, ds, cloud_scaling, up, dn, dir_c, ECCKD_HOST, c_null_ptr)
+    if (rc /= 0) then
+      error_msg = c_error_message()
+      return
+    end if
+    flux_up = up
+    flux_dn = dn
+    if (present(flux_dir)) flux_dir = dir
+  end function sw_flux_scaled
 
   function c_loc_3d(a) result(p)
     real(wp), dimension(:,:,:), intent(in), target, contiguous :: a
