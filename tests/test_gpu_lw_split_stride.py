@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 import helpers
+import stride_helpers
 import test_gpu_lw_allsky as lwt
 from rte_ecckd_amd import synthetic
 
@@ -74,22 +75,11 @@ def particles(pkg, d):
 
 
 def repeated(d, ncol, wanted):
-    """The arrays of `d` that the form reads, their columns repeated cyclically to ncol columns (on the device); the index of
-    each column's origin."""
-    import torch
-    idx = torch.arange(ncol, device=d["plev"].device) % NSMALL
-    out = {}
-    for n, v in d.items():
-        if np.isscalar(v):
-            out[n] = v
-        elif wanted(n):
-            out[n] = v.index_select(0 if n == "emis" else v.ndim - 1, idx).contiguous()
-    return out, idx
+    return stride_helpers.repeated(d, ncol, wanted, NSMALL)
 
 
 def new(d, sentinel=-1.0):
-    import torch
-    return torch.full((NLAY + 1, d["plev"].shape[-1]), sentinel, dtype=torch.float64, device=d["plev"].device)
+    return stride_helpers.new(d, NLAY, sentinel)
 
 
 def head(pkg, d):

@@ -1047,14 +1047,18 @@ def test_rte_lw_tail_split_is_bit_identical(pkg, gpu, ncol, nlay, ng, nmus, top_
 
 @pytest.mark.parametrize("ncol,nlay,ng,top_at_1,clamp", [
     (500, 60, 27, True, 0),       # fewer tiles than resident waves: every tile is a tail tile
-    (50000, 60, 27, True, 0),     # one full round of 3 072 tiles + 53 tail tiles: no split beyond one round (option without effect)
-    (9000, 60, 27, False, 0),     # 563 tiles: the largest calls that still split (partial sums below 64 MiB)
+    (50000, 60, 27, True, 0),     # 3 125 tiles on the grid of 4 096 blocks: less than one round, all of them tail tiles, yet no
+                                  # split -- the partial sums would take 489 MiB (bar 64 MiB): the option is without effect
+    (4096 * 16 + 53 * 16, 12, 6, True, 0),   # one full round of 4 096 tiles + 53 tail tiles: no split beyond one round (`full > 0`
+                                  # in rte_sw_tail_plan; option without effect), and 53 blocks take a second tile
+    (9000, 60, 27, False, 0),     # 563 tiles, bottom-up: partial sums of 88 MiB, no split either (409 tiles are the most that split)
     (1003, 37, 14, False, 1),     # other layer count, bottom-up arrays, partly empty last tile and last g-point group
 ])
 def test_rte_sw_tail_split_is_bit_identical(pkg, gpu, ncol, nlay, ng, top_at_1, clamp):
     """rte_sw, two-pass kernel (sw_solver = 1), with the tail split ("sw_tail_split", default) against whole-tile waves: the
-    same bits in flux_up, flux_dn and flux_dn_dir, in both arithmetic modes.  (The layer-systolic default sums the
-    g-points of SMALL calls in chunks, which is not bit-neutral: tests/test_gpu_round3.py.)"""
+    same bits in flux_up, flux_dn and flux_dn_dir, in both arithmetic modes.  (The layer-systolic default hands the tail
+    tiles out in chunks of ONE g-point (rte_sw_sys_plan) and adds them in order, which is bit-neutral as well:
+    tests/test_gpu_round3.py asserts it.)"""
     import torch
     pkg.set_solver_option("sw_solver", 1)
     rng = np.random.default_rng(ncol)
