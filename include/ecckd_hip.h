@@ -705,8 +705,8 @@ int ecckd_sw_fluxes_clear_allsky(const ecckd_model_t *model, int ncol, int nlay,
  * The capture rules of the stream scratch hold for both: capture after one warm-up call on the stream, or with a
  * caller-owned block (ecckd_set_stream_scratch) of the size above.
  *
- * Out of scope: the Fortran shim (fp64 throughout); ecckd_sw_fluxes_daylit; the Jacobian, rescaled and two-stream longwave
- * calls in single precision; per-band outputs; a single-precision Planck-recomputing longwave kernel (8 instead of 24 bytes
+ * Out of scope: the Fortran shim (fp64 throughout); ecckd_sw_fluxes_daylit; the Jacobian and rescaled longwave calls in single
+ * precision (the two-stream ones: "Two-stream longwave, single precision" below); per-band outputs; a single-precision Planck-recomputing longwave kernel (8 instead of 24 bytes
  * per cell between the kernels: the obvious follow-up, not measured); the in-solver addition for the fp64 general route at
  * layer counts other than 60.
  * --------------------------------------------------------------------------------------- */
@@ -944,7 +944,8 @@ int ecckd_lw_fluxes_jac(const ecckd_model_t *model, int ncol, int nlay, const do
  *   Scratch (ECCKD_DEVICE, from the stream's block), with n3 = ncol*nlay*ngpt and r32() rounding up to a multiple of 32:
  *     8*(r32(n3) + 3*n3 + r32(ncol*ngpt)) + ecckd_rte_lw_2stream_scratch_bytes(ncol, nlay, ngpt)
  *   in the order optical depth, the three Planck arrays, surface source, ring.
- * Out of scope: single precision; per-band and Jacobian outputs; both skies in one call; delta scaling inside the fused
+ * Out of scope: single precision of ecckd_lw_solver_2stream_gpt (the other two: the next block); per-band and Jacobian
+ *   outputs; both skies in one call; delta scaling inside the fused
  *   call (the host calls ecckd_delta_scale on its band triple first); ECCKD_MIXED; a tail split for small calls; a
  *   Planck-recomputing form of the solver; the Fortran type-bound rte_lw(use_2stream=).  (RTE's rescaled no-scattering
  *   alternative, use_2stream = .false. with two-stream properties, is the next block.)
@@ -964,6 +965,66 @@ int ecckd_lw_fluxes_allsky_2stream(const ecckd_model_t *model, int ncol, int nla
                                    const double *vmr_scalar, int top_at_1, const double *sfc_emis, const double *inc_flux,
                                    int nband_p, const double *tau_p, const double *ssa_p, const double *g_p,
                                    const unsigned long long *cloud_mask, double *flux_up, double *flux_dn, int memspace, void *stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Two-stream longwave, single precision.  For a host built with wp = real32: ecckd_rte_lw_2stream and
+ * ecckd_lw_fluxes_allsky_2stream with every `double` data pointer made `float` (vmr_scalar stays `const double *`, cloud_mask
+ * `const unsigned long long *`, as in the other *_f32 fused calls).  Fast arithmetic mode only; ECCKD_DEVICE or ECCKD_HOST.
+ * Per cell in float: tau, ssa, g (or the band triple), both level-source planes, sfc_emis, sfc_source, inc_flux, the ring and
+ * the flux outputs; the g-point sums and the level accumulators are double, rounded to float once when the fluxes are stored.
+ *   The float cell is NOT the fp64 block retyped: in float 1 - e2 loses its digits in a thin layer and under the k floor,
+ *   gamma1 - gamma2 loses them near ssa = 1, and the fp64 source terms cancel quantities of size dB/tau down to a result of
+ *   size tau*B (RTE's tau > 1e-8 switch means nothing at float resolution).  Every such difference is formed from its parts.
+ *   Per (column, g-point), all operations in float, in this order, D = 1.66f, pi = 3.14159274f:
+ *     level source: as above, sqrtf(lev_source_dec(j)*lev_source_inc(j-1)) in between;
+ *     gamma1 = D*(1 - 0.5*ssa*(1 + g)), gamma2 = D*0.5*ssa*(1 - g), gm = D*(1 - ssa) [= gamma1 - gamma2], gp = gamma1 + gamma2,
+ *       k = sqrtf(max(gm*gp, 1e-12)), x = tau*k, e1 = expf(-x), n1 = -expm1f(-x) [= 1 - e1], m = n1*(1 + e1) [= 1 - e2],
+ *       RT = 1/(k*(2 - m) + gamma1*m), Rdif = RT*gamma2*m, Tdif = RT*2*k*e1;
+ *     kn = k*n1*n1, A1 = RT*(kn + gm*m) [= 1 - Rdif - Tdif],
+ *       G = x < 0.7 ? e1*(x*x*(1/3))*(1 + (x*x*(1/20))*(1 + x*x*(1/42))) : m*(1/x) - 2*e1   [= 2*e1*(sinh(x)/x - 1)],
+ *       A2 = RT*(kn*(1/(tau*gp)) + k*G), dB = Bb - Bt,
+ *       tau > 1e-30: src_up = pi*(Bt*A1 + dB*A2), src_dn = pi*(Bb*A1 - dB*A2); else both 0
+ *       (to first order in tau both are pi*(gamma1-gamma2)*tau*(Bt+Bb)/2; the next order carries -+ dB);
+ *     surface, adding and fluxes as in fp64, in float: den = 1/(1 - Rdif*albedo), src = src_up + Tdif*den*(src + albedo*src_dn),
+ *       albedo = Rdif + Tdif*Tdif*albedo*den; flux_dn = (Tdif*flux_dn + Rdif*src(l+1) + src_dn)*den, flux_up = flux_dn*albedo(l+1)
+ *       + src(l+1).
+ *   1/y is the hardware reciprocal with one Newton step (as in every *_f32 solver), expf / expm1f / sqrtf are the device
+ *   library's: tests/lw_2stream_f32_ref.py restates the block in numpy float32 with IEEE operations and is the reference of
+ *   this definition, not a bit-for-bit pin of the kernel.  The threshold 0.7 is where the errors of the two forms of G cross;
+ *   the floor 1e-12 is RTE's (nothing divides by 1 - e2 any more, so float needs no higher one); 1e-30 keeps the two quotients
+ *   on normal numbers.  Distances from the fp64 calls: DESIGN.md section 3.  ssa = g = 1 (gp = 0) and an infinite tau give NaN
+ *   fluxes for that column, as in fp64 mode 0; a NaN in one column stays in that column.
+ * ecckd_rte_lw_2stream_f32: the argument list of ecckd_rte_lw_2stream.  The ring comes from the stream's block as in fp64; the
+ *   call asks for ecckd_rte_lw_2stream_scratch_bytes(ncol, nlay, ngpt) and the float ring takes the first HALF of it,
+ *   4 * 2*(nlay+1)*64 * min(ceil(ncol/16), 4096) bytes.  Refused in the order of the fp64 call, under this call's name: bad
+ *   sizes; a null required pointer; one level buffer in place of two arrays; a bad band description; too many layers;
+ *   ECCKD_MIXED; a bad memspace; then reference-order arithmetic; then the device.
+ * ecckd_lw_fluxes_allsky_2stream_f32: the argument list of ecckd_lw_fluxes_allsky_2stream.  The single-precision gas optics
+ *   writes tau and the Planck sources (float) into the work block, the float solver follows with the band triple and the mask
+ *   word as in fp64 and forms the cell's (tau, ssa, g) with the operations of ecckd_increment[_masked]_f32 by band on
+ *   (tau_gas, 0, 0).  flux_up / flux_dn equal, BIT FOR BIT on finite inputs, the composed route ecckd_gas_optics_lw_f32,
+ *   ecckd_increment[_masked]_f32 by band on (tau, ssa = 0, g = 0), ecckd_rte_lw_2stream_f32.  Capture rules as the fp64 call.
+ *   Refused in the fp64 call's order, under this call's name: cloud_mask with more than 64 g-points; nband_p different from
+ *   the model's; tau_p, ssa_p or g_p NULL; reference-order arithmetic; no Planck table; tlev NULL; ECCKD_MIXED (named here;
+ *   the fp64 call answers it as a bad memspace); a host-only model.
+ *   Scratch (ECCKD_DEVICE, from the stream's block): ecckd_lw_fluxes_allsky_2stream_f32_scratch_bytes(model, ncol, nlay) =
+ *     4*A + align256(ncol*ngpt*4) + align256(ecckd_rte_lw_2stream_scratch_bytes(ncol, nlay, ngpt)/2), A = align256(ncol*nlay*ngpt*4),
+ *   in the order tau, lay_source (written by the gas optics, never read), lev_source_inc, lev_source_dec, sfc_source, ring.
+ * Out of scope: the rescaled solver and the Jacobian in single precision; ecckd_lw_solver_2stream_gpt in float; per-band
+ *   output; both skies in one two-stream call; the Fortran shim; reference-order arithmetic in float.
+ * --------------------------------------------------------------------------------------- */
+int ecckd_rte_lw_2stream_f32(int device, int ncol, int nlay, int ngpt, int top_at_1, const float *tau, const float *ssa,
+                             const float *g, const float *lay_source, const float *lev_source_inc, const float *lev_source_dec,
+                             const float *sfc_source, int nband, const int *band2gpt, const float *sfc_emis,
+                             const float *inc_flux, float *flux_up, float *flux_dn, int memspace, void *stream);
+size_t ecckd_lw_fluxes_allsky_2stream_f32_scratch_bytes(const ecckd_model_t *model, int ncol, int nlay);
+int ecckd_lw_fluxes_allsky_2stream_f32(const ecckd_model_t *model, int ncol, int nlay, const float *plev, const float *tlay,
+                                       const float *tsfc, const float *tlev, int ngas, const char *gas_names,
+                                       const float *const *vmr, const long long *vmr_col_stride,
+                                       const long long *vmr_lay_stride, const double *vmr_scalar, int top_at_1,
+                                       const float *sfc_emis, const float *inc_flux, int nband_p, const float *tau_p,
+                                       const float *ssa_p, const float *g_p, const unsigned long long *cloud_mask,
+                                       float *flux_up, float *flux_dn, int memspace, void *stream);
 
 /* ---------------------------------------------------------------------------------------
  * Rescaled longwave: cheap cloud scattering with the Gauss quadrature.  RTE-RRTMGP's lw_solver_1rescl_GaussQuad of the v1.5

@@ -287,6 +287,10 @@ def lib():
         L.ecckd_lw_solver_2stream_gpt.argtypes = [C.c_int] * 5 + [C.c_void_p] * 11 + [C.c_int, C.c_void_p]
         L.ecckd_rte_lw_2stream_scratch_bytes.restype = C.c_size_t
         L.ecckd_rte_lw_2stream_scratch_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
+    if hasattr(L, "ecckd_rte_lw_2stream_f32"):   # (an older build lacks them: ECCKD_LIB)
+        L.ecckd_rte_lw_2stream_f32.argtypes = L.ecckd_rte_lw_2stream.argtypes
+        L.ecckd_lw_fluxes_allsky_2stream_f32_scratch_bytes.restype = C.c_size_t
+        L.ecckd_lw_fluxes_allsky_2stream_f32_scratch_bytes.argtypes = [C.c_void_p, C.c_int, C.c_int]
     if hasattr(L, "ecckd_rte_lw_rescaled"):   # (an older build lacks them: tools/bench_lw_rescaled.py --parent-lib)
         L.ecckd_rte_lw_rescaled.argtypes = [C.c_int] * 6 + [C.c_void_p] * 7 + [C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.c_void_p]
         L.ecckd_lw_solver_1rescl_gpt.argtypes = [C.c_int] * 6 + [C.c_void_p] * 13 + [C.c_int, C.c_void_p]
@@ -476,6 +480,12 @@ def _call_precision(who, named):
             return first[1], "%s: mixing float32 and float64 arrays in one call (%s is %s, %s is %s)" % (
                 who, first[0], kind(first[1]), name, kind(p))
     return (first[1] if first else False), ""
+
+
+def _entry(name, f32):
+    """The entry point ``name`` in the precision of a call: its ``_f32`` namesake for float32 arrays (``lib()`` gives the two one
+    prototype)."""
+    return getattr(lib(), name + "_f32" if f32 else name)
 
 
 def _f64_only(who, what):
@@ -1783,6 +1793,32 @@ class GasOpticsEcckd:
                            outputs=_flux_slots(fluxes) + _flux_slots(fluxes_clear or _NO_FLUXES, "_clear") + _jac_slot(flux_up_jac),
                            **_lw_groups(plev, tlay, tsfc, tlev, top_at_1, n_gauss_angles, sfc_emis, inc_flux))
 
+    def lw_fluxes_allsky_2stream(self, plev, tlay, tsfc, tlev, gas_desc, top_at_1, sfc_emis, particles, fluxes, inc_flux=None,
+                                 cloud_mask=None):
+        """``ecckd_lw_fluxes_allsky_2stream`` or its ``_f32`` namesake: all-sky longwave fluxes with scattering particles, in the
+        precision of the arrays.  float64 arrays give the bits of ``lw_fluxes_allsky(..., use_2stream=True)``;
+        float32 arrays (all of them) take the single-precision call: the fluxes of ``gas_optics`` + ``increment(particles,
+        band2gpt[, cloud_mask])`` on ``(tau, 0, 0)`` + ``rte_lw_2stream`` on float32 arrays, bit for bit.  ``particles``: a
+        two-stream object on the model's bands with ``g``; never written.  ``cloud_mask`` ``(nlay, ncol)`` as in
+        ``lw_fluxes_allsky``.  Fast arithmetic mode; numpy or device tensors.  Returns the error message ('' = success)."""
+        who = "lw_fluxes_allsky_2stream"
+        if not isinstance(particles, OpticalProps2str) or particles.g is None:
+            return who + ": the particles must be two-stream optical properties on the model's bands, with g (alloc_2str_bands)"
+        if isinstance(fluxes, FluxesByband):
+            return who + ": per-band fluxes are not implemented (broadband fluxes only)"
+        lw = _lw_groups(plev, tlay, tsfc, tlev, top_at_1, None, sfc_emis, inc_flux)
+        part, out = _particle_slots(particles.tau, particles.ssa, particles.g), _flux_slots(fluxes)
+        f32, mixed = _call_precision(who, _named(lw["head"], lw["boundary"], part, out))
+        if mixed:
+            return mixed
+        return self._fused(_entry("ecckd_lw_fluxes_allsky_2stream", f32), f32, ("gas", "particles", "mask", "head", "boundary", "outputs"),
+                           gas_desc, particles=part, mask=(cloud_mask,), outputs=out, **lw)
+
+    def lw_fluxes_allsky_2stream_f32_scratch_bytes(self, ncol, nlay):
+        """The stream scratch of ``lw_fluxes_allsky_2stream`` on float32 device tensors (the ``_scratch_bytes`` function of the
+        single-precision entry point)."""
+        return int(lib().ecckd_lw_fluxes_allsky_2stream_f32_scratch_bytes(self._need(), int(ncol), int(nlay)))
+
     def lw_fluxes_rescaled_scratch_bytes(self, ncol, nlay, with_clear=False):
         """``ecckd_lw_fluxes_rescaled_jac_scratch_bytes``: the stream scratch of ``lw_fluxes_rescaled`` on device tensors."""
         return int(lib().ecckd_lw_fluxes_rescaled_jac_scratch_bytes(self._need(), int(ncol), int(nlay), int(bool(with_clear))))
@@ -2078,6 +2114,43 @@ def _rte_lw_2stream(optical_props, top_at_1, sources, sfc_emis, fluxes, n_gauss_
     dev = _device_of(optical_props.tau) if device is None else device
     rc = lib().ecckd_rte_lw_2stream(int(dev), ncol, nlay, ng, int(bool(top_at_1)), *a3, sfc, nband, C.c_void_p(b2g.ctypes.data),
                                     *rest, space, _stream(space))
+    return last_error() if rc else ""
+
+
+def rte_lw_2stream(optical_props, top_at_1, sources, sfc_emis, fluxes, inc_flux=None, device=None):
+    """``ecckd_rte_lw_2stream`` or its ``_f32`` namesake: the two-stream longwave solver, in which clouds scatter, in the
+    precision of the arrays.  float64 arrays give the bits of ``rte_lw(..., use_2stream=True)``; float32 arrays (all of them)
+    take the single-precision solver, whose cell is defined in include/ecckd_hip.h ("Two-stream longwave, single precision":
+    fast arithmetic mode only) and whose distance from the float64 call is recorded in DESIGN.md section 3.  An
+    ``OpticalProps2str``, broadband fluxes, ``inc_flux`` ``(ngpt, ncol)`` accepted, no quadrature; ``sources.lay_source`` is
+    never read.  numpy or device tensors.  Returns the error message ('' = success)."""
+    who = "rte_lw_2stream"
+    if not isinstance(optical_props, OpticalProps2str):
+        return who + ": two-stream optical properties required (OpticalProps2str)"
+    if isinstance(fluxes, FluxesByband):
+        return who + ": per-band fluxes are not implemented (broadband fluxes only)"
+    if hasattr(sources, "separate_levels"):
+        sources.separate_levels()   # this entry point reads two separate arrays: a level buffer is copied out, once
+    lay = getattr(sources, "lay_source", None)
+    named = [("tau", optical_props.tau), ("ssa", optical_props.ssa), ("g", optical_props.g), ("lay_source", lay),
+             ("lev_source_inc", sources.lev_source_inc), ("lev_source_dec", sources.lev_source_dec),
+             ("sfc_source", sources.sfc_source), ("sfc_emis", sfc_emis), ("inc_flux", inc_flux), ("flux_up", fluxes.flux_up),
+             ("flux_dn", fluxes.flux_dn)]
+    f32, mixed = _call_precision(who, named)
+    if mixed:
+        return mixed
+    ng, nlay, ncol = optical_props.tau.shape
+    b2g = np.ascontiguousarray(optical_props.band2gpt, dtype=np.int32)
+    nband = b2g.shape[0]
+    shapes = [(ng, nlay, ncol)] * 6 + [(ng, ncol), (ncol, nband), (ng, ncol), (nlay + 1, ncol), (nlay + 1, ncol)]
+    try:
+        space = _space_of([a for _, a in named])
+        ptrs = [_ptr(a, shape, what, f32) for (what, a), shape in zip(named, shapes)]
+    except (TypeError, ValueError) as e:
+        return str(e)
+    dev = _device_of(optical_props.tau) if device is None else device
+    rc = _entry("ecckd_rte_lw_2stream", f32)(int(dev), ncol, nlay, ng, int(bool(top_at_1)), *ptrs[:7], nband, C.c_void_p(b2g.ctypes.data), *ptrs[7:], space,
+            _stream(space))
     return last_error() if rc else ""
 
 

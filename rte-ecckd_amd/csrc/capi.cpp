@@ -1944,28 +1944,33 @@ static int lw_2stream_layers_fit(int nlay) {
   return 0;
 }
 
-int ecckd_rte_lw_2stream(int device, int ncol, int nlay, int ngpt, int top_at_1, const double *tau, const double *ssa,
-                         const double *g, const double *lay_source, const double *lev_source_inc, const double *lev_source_dec,
-                         const double *sfc_source, int nband, const int *band2gpt, const double *sfc_emis, const double *inc_flux,
-                         double *flux_up, double *flux_dn, int memspace, void *stream) {
+// (f32: float arrays behind the double pointers; the same list of refusals in the same order under the call's own name)
+static int rte_lw_2stream_impl(bool f32, int device, int ncol, int nlay, int ngpt, int top_at_1, const double *tau, const double *ssa,
+                               const double *g, const double *lay_source, const double *lev_source_inc, const double *lev_source_dec,
+                               const double *sfc_source, int nband, const int *band2gpt, const double *sfc_emis,
+                               const double *inc_flux, double *flux_up, double *flux_dn, int memspace, void *stream) {
+  const std::string who = f32 ? "ecckd_rte_lw_2stream_f32" : "ecckd_rte_lw_2stream";
   (void)lay_source;   // an argument as in RTE-RRTMGP's lw_solver_2stream, which never reads it
   if (check_dims(ncol, nlay)) return 1;
   if (!tau || !ssa || !g || !lev_source_inc || !lev_source_dec || !sfc_source || !sfc_emis || !flux_up || !flux_dn)
-    return fail("ecckd_rte_lw_2stream: null argument (only lay_source and inc_flux may be null)");
-  if (refuse_level_buffer("ecckd_rte_lw_2stream", lev_source_inc, lev_source_dec, ncol, nlay, memspace)) return 1;
+    return fail(who + ": null argument (only lay_source and inc_flux may be null)");
+  LevelPair lp;
+  if (level_pair(who.c_str(), lev_source_inc, lev_source_dec, ncol, nlay, f32, memspace, false, &lp)) return 1;
   ecckd::RteLw2strArgs a{};
   if (fill_band_map(ngpt, nband, band2gpt, a.gpt2band)) return 1;
   if (lw_2stream_layers_fit(nlay)) return 1;
-  if (memspace == ECCKD_MIXED) return fail("ecckd_rte_lw_2stream: ECCKD_MIXED is not implemented (ECCKD_DEVICE or ECCKD_HOST)");
+  if (memspace == ECCKD_MIXED) return fail(who + ": ECCKD_MIXED is not implemented (ECCKD_DEVICE or ECCKD_HOST)");
   if (memspace != ECCKD_DEVICE && memspace != ECCKD_HOST) return fail("ecckd: bad memspace");
+  if (f32 && g_arith.load() != 0) return fail(who + ": needs the fast arithmetic mode (ecckd_set_arithmetic(0))");
   if (check_device(device)) return 1;
   if (ncol == 0) return 0;
   a.ncol = ncol; a.nlay = nlay; a.ng = ngpt; a.top_at_1 = top_at_1 ? 1 : 0; a.nband = nband;
   a.exact_division = g_arith.load() != 0;
   const Counts n(ncol, nlay, ngpt, nband);
-  Stage st(device, memspace, stream, false);
+  Stage st(device, memspace, stream, f32);
   ScratchLease lease;   // (held until the kernel of this call has been launched)
   void *sp = nullptr;
+  // (single precision: the ring is in floats and takes the first half of the block)
   if (stream_scratch(device, st.stream, ecckd::rte_lw_2str_scratch_bytes(ncol, nlay, ngpt), &sp, lease)) return 1;
   a.scratch = static_cast<double *>(sp);
   if (st.open([&] {
@@ -1976,10 +1981,27 @@ int ecckd_rte_lw_2stream(int device, int ncol, int nlay, int ngpt, int top_at_1,
       }))
     return 1;
   {
-    ProfScope prof("rte_lw_2stream", st.stream);
-    HIPCHK(ecckd::launch_rte_lw_2str(a, st.stream));
+    ProfScope prof(f32 ? "rte_lw_2stream_f32" : "rte_lw_2stream", st.stream);
+    HIPCHK(f32 ? ecckd::launch_rte_lw_2str_f32(a, st.stream) : ecckd::launch_rte_lw_2str(a, st.stream));
   }
   return st.close();
+}
+
+int ecckd_rte_lw_2stream(int device, int ncol, int nlay, int ngpt, int top_at_1, const double *tau, const double *ssa,
+                         const double *g, const double *lay_source, const double *lev_source_inc, const double *lev_source_dec,
+                         const double *sfc_source, int nband, const int *band2gpt, const double *sfc_emis, const double *inc_flux,
+                         double *flux_up, double *flux_dn, int memspace, void *stream) {
+  return rte_lw_2stream_impl(false, device, ncol, nlay, ngpt, top_at_1, tau, ssa, g, lay_source, lev_source_inc, lev_source_dec,
+                             sfc_source, nband, band2gpt, sfc_emis, inc_flux, flux_up, flux_dn, memspace, stream);
+}
+
+int ecckd_rte_lw_2stream_f32(int device, int ncol, int nlay, int ngpt, int top_at_1, const float *tau, const float *ssa,
+                             const float *g, const float *lay_source, const float *lev_source_inc, const float *lev_source_dec,
+                             const float *sfc_source, int nband, const int *band2gpt, const float *sfc_emis, const float *inc_flux,
+                             float *flux_up, float *flux_dn, int memspace, void *stream) {
+  return rte_lw_2stream_impl(true, device, ncol, nlay, ngpt, top_at_1, dp(tau), dp(ssa), dp(g), dp(lay_source), dp(lev_source_inc),
+                             dp(lev_source_dec), dp(sfc_source), nband, band2gpt, dp(sfc_emis), dp(inc_flux), dp(flux_up),
+                             dp(flux_dn), memspace, stream);
 }
 
 int ecckd_lw_solver_2stream_gpt(int device, int ncol, int nlay, int ngpt, int top_at_1, const double *tau, const double *ssa,
@@ -2472,34 +2494,60 @@ static int lw_allsky_2stream_dev(const ecckd_model *m, int ncol, int nlay, const
   return 0;
 }
 
-int ecckd_lw_fluxes_allsky_2stream(const ecckd_model_t *m, int ncol, int nlay, const double *plev, const double *tlay,
-                                   const double *tsfc, const double *tlev, int ngas, const char *gas_names,
-                                   const double *const *vmr, const long long *vmr_col_stride, const long long *vmr_lay_stride,
-                                   const double *vmr_scalar, int top_at_1, const double *sfc_emis, const double *inc_flux,
-                                   int nband_p, const double *tau_p, const double *ssa_p, const double *g_p,
-                                   const unsigned long long *cloud_mask, double *flux_up, double *flux_dn, int memspace,
-                                   void *stream) {
+// The work block of ecckd_lw_fluxes_allsky_2stream_f32 (..._scratch_bytes), in this order: tau, lay_source, lev_source_inc,
+// lev_source_dec (`cells` bytes each: what the single-precision gas optics writes, as in LwWorkF32), sfc_source (`sfc`), the
+// solver's ring in floats (`ring`); every part a multiple of 256 bytes
+struct Lw2strWorkF32 {
+  size_t cells, sfc, ring;
+  Lw2strWorkF32(const ecckd_model *m, int ncol, int nlay) {
+    const Counts n(ncol, nlay, m->ng, m->nband);
+    cells = align256(n.lay_g * sizeof(float));
+    sfc = align256(n.col_g * sizeof(float));
+    ring = align256(ecckd::rte_lw_2str_scratch_bytes(ncol, nlay, m->ng) / 2);
+  }
+  size_t bytes() const { return 4 * cells + sfc + ring; }
+};
+
+size_t ecckd_lw_fluxes_allsky_2stream_f32_scratch_bytes(const ecckd_model_t *m, int ncol, int nlay) {
+  if (!m || ncol <= 0 || nlay <= 0) return 0;
+  return Lw2strWorkF32(m, ncol, nlay).bytes();
+}
+
+// (f32: float arrays behind the double pointers -- the single-precision gas optics and Planck sources into the work block,
+// then the float solver; the same list of refusals in the same order under the call's own name)
+static int lw_fluxes_allsky_2stream_impl(bool f32, const ecckd_model_t *m, int ncol, int nlay, const double *plev, const double *tlay,
+                                         const double *tsfc, const double *tlev, int ngas, const char *gas_names,
+                                         const double *const *vmr, const long long *vmr_col_stride, const long long *vmr_lay_stride,
+                                         const double *vmr_scalar, int top_at_1, const double *sfc_emis, const double *inc_flux,
+                                         int nband_p, const double *tau_p, const double *ssa_p, const double *g_p,
+                                         const unsigned long long *cloud_mask, double *flux_up, double *flux_dn, int memspace,
+                                         void *stream) {
+  const std::string who = f32 ? "ecckd_lw_fluxes_allsky_2stream_f32" : "ecckd_lw_fluxes_allsky_2stream";
   if (!m) return fail("ecckd: null model");
-  if (cloud_mask && m->ng > 64) return fail("ecckd_lw_fluxes_allsky_2stream" + std::string(kMaskTooWide) + std::to_string(m->ng));
+  if (cloud_mask && m->ng > 64) return fail(who + std::string(kMaskTooWide) + std::to_string(m->ng));
   if (nband_p != m->nband)
-    return fail("ecckd_lw_fluxes_allsky_2stream: nband_p = " + std::to_string(nband_p) + " but the model has " +
+    return fail(who + ": nband_p = " + std::to_string(nband_p) + " but the model has " +
                 std::to_string(m->nband) + " bands (particulate properties live on the model's bands)");
   if (!tau_p || !ssa_p || !g_p)
-    return fail("ecckd_lw_fluxes_allsky_2stream: null argument (tau_p, ssa_p and g_p are required; one-stream particles: ecckd_lw_fluxes_allsky)");
-  if (g_arith.load() != 0) return fail("ecckd_lw_fluxes_allsky_2stream: needs the fast arithmetic mode (ecckd_set_arithmetic(0))");
-  if (!m->has_planck) return fail("ecckd_lw_fluxes_allsky_2stream: model has no Planck table (shortwave model?)");
+    return fail(who + ": null argument (tau_p, ssa_p and g_p are required; one-stream particles: ecckd_lw_fluxes_allsky)");
+  if (g_arith.load() != 0) return fail(who + ": needs the fast arithmetic mode (ecckd_set_arithmetic(0))");
+  if (!m->has_planck) return fail(who + ": model has no Planck table (shortwave model?)");
   if (!tlev) return fail("tlev is required for ecckd");
+  // (the single-precision call names ECCKD_MIXED; the fp64 call has always answered it as a bad memspace, below)
+  if (f32 && memspace == ECCKD_MIXED) return fail(who + ": ECCKD_MIXED is not implemented (ECCKD_DEVICE or ECCKD_HOST)");
   if (check_model(m) || check_gas_optics_dims(ncol, nlay)) return 1;
   if (!plev || !tlay || !tsfc || !sfc_emis || !flux_up || !flux_dn || (ngas > 0 && !gas_names))
-    return fail("ecckd_lw_fluxes_allsky_2stream: null argument");
+    return fail(who + ": null argument");
   if (lw_2stream_layers_fit(nlay)) return 1;
   if (memspace != ECCKD_DEVICE && memspace != ECCKD_HOST) return fail("ecckd: bad memspace");
   HIPCHK(hipSetDevice(m->device));
   if (ncol == 0) return 0;
   const GasDesc gd{ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar};
   const Counts n(ncol, nlay, m->ng, m->nband);
-  const size_t work_bytes = allsky_2stream_doubles(m, ncol, nlay) * sizeof(double) + ecckd::rte_lw_2str_scratch_bytes(ncol, nlay, m->ng);
-  Stage st(const_cast<ecckd_model *>(m), memspace, stream, false);
+  const Lw2strWorkF32 w(m, ncol, nlay);
+  const size_t work_bytes = f32 ? w.bytes()
+                                : allsky_2stream_doubles(m, ncol, nlay) * sizeof(double) + ecckd::rte_lw_2str_scratch_bytes(ncol, nlay, m->ng);
+  Stage st(const_cast<ecckd_model *>(m), memspace, stream, f32);
   const double *d_plev = nullptr, *d_tlay = nullptr, *d_tsfc = nullptr, *d_tlev = nullptr, *d_emis = nullptr, *d_incf = nullptr;
   const double *q_tau = nullptr, *q_ssa = nullptr, *q_g = nullptr;
   const unsigned long long *q_mask = nullptr;
@@ -2514,12 +2562,53 @@ int ecckd_lw_fluxes_allsky_2stream(const ecckd_model_t *m, int ncol, int nlay, c
         work = st.work(work_bytes);
       }))
     return 1;
+  if (f32) {
+    char *const base = reinterpret_cast<char *>(work);
+    auto at = [&](size_t off) { return reinterpret_cast<double *>(base + off); };
+    double *tau = at(0), *lay = at(w.cells), *inc = at(2 * w.cells), *dec = at(3 * w.cells), *sfc = at(4 * w.cells);
+    if (gas_optics_lw_dev(m, true, ncol, nlay, d_plev, d_tlay, d_gd, tau, PlanckSide{d_tlev, d_tsfc, lay, inc, dec, sfc}, st.stream)) return 1;
+    ecckd::RteLw2strArgs a{};
+    if (fill_band_map(m->ng, m->nband, m->band2gpt.data(), a.gpt2band)) return 1;
+    a.ncol = ncol; a.nlay = nlay; a.ng = m->ng; a.top_at_1 = top_at_1 ? 1 : 0; a.nband = m->nband;
+    a.exact_division = 0;
+    a.tau = tau; a.lev_source_inc = inc; a.lev_source_dec = dec; a.sfc_source = sfc; a.sfc_emis = d_emis; a.inc_flux = d_incf;
+    a.part_tau = q_tau; a.part_ssa = q_ssa; a.part_g = q_g; a.part_mask = q_mask;
+    a.flux_up = d_up; a.flux_dn = d_dn; a.scratch = at(4 * w.cells + w.sfc);
+    ProfScope prof("rte_lw_2stream_allsky_f32", st.stream);
+    HIPCHK(ecckd::launch_rte_lw_2str_f32(a, st.stream));
+    return st.close();
+  }
   if (gas_optical_depth_dev(m, false, nullptr, ncol, nlay, d_plev, d_tlay, d_gd, work, false, nullptr, nullptr, nullptr, nullptr, st.stream))
     return 1;
   if (lw_allsky_2stream_dev(m, ncol, nlay, d_tlay, d_tlev, d_tsfc, top_at_1, d_emis, d_incf, q_tau, q_ssa, q_g, q_mask, d_up, d_dn, work,
                             st.stream))
     return 1;
   return st.close();
+}
+
+int ecckd_lw_fluxes_allsky_2stream(const ecckd_model_t *m, int ncol, int nlay, const double *plev, const double *tlay,
+                                   const double *tsfc, const double *tlev, int ngas, const char *gas_names,
+                                   const double *const *vmr, const long long *vmr_col_stride, const long long *vmr_lay_stride,
+                                   const double *vmr_scalar, int top_at_1, const double *sfc_emis, const double *inc_flux,
+                                   int nband_p, const double *tau_p, const double *ssa_p, const double *g_p,
+                                   const unsigned long long *cloud_mask, double *flux_up, double *flux_dn, int memspace,
+                                   void *stream) {
+  return lw_fluxes_allsky_2stream_impl(false, m, ncol, nlay, plev, tlay, tsfc, tlev, ngas, gas_names, vmr, vmr_col_stride,
+                                       vmr_lay_stride, vmr_scalar, top_at_1, sfc_emis, inc_flux, nband_p, tau_p, ssa_p, g_p,
+                                       cloud_mask, flux_up, flux_dn, memspace, stream);
+}
+
+int ecckd_lw_fluxes_allsky_2stream_f32(const ecckd_model_t *m, int ncol, int nlay, const float *plev, const float *tlay,
+                                       const float *tsfc, const float *tlev, int ngas, const char *gas_names,
+                                       const float *const *vmr, const long long *vmr_col_stride, const long long *vmr_lay_stride,
+                                       const double *vmr_scalar, int top_at_1, const float *sfc_emis, const float *inc_flux,
+                                       int nband_p, const float *tau_p, const float *ssa_p, const float *g_p,
+                                       const unsigned long long *cloud_mask, float *flux_up, float *flux_dn, int memspace,
+                                       void *stream) {
+  return lw_fluxes_allsky_2stream_impl(true, m, ncol, nlay, dp(plev), dp(tlay), dp(tsfc), dp(tlev), ngas, gas_names,
+                                       reinterpret_cast<const double *const *>(vmr), vmr_col_stride, vmr_lay_stride, vmr_scalar,
+                                       top_at_1, dp(sfc_emis), dp(inc_flux), nband_p, dp(tau_p), dp(ssa_p), dp(g_p), cloud_mask,
+                                       dp(flux_up), dp(flux_dn), memspace, stream);
 }
 
 // ---- rescaled no-scattering longwave solver (RTE-RRTMGP's lw_solver_1rescl_GaussQuad): cheap cloud scattering ----

@@ -252,6 +252,10 @@ struct RteLw2strArgs {
 };
 size_t rte_lw_2str_scratch_bytes(int ncol, int nlay, int ng);
 hipError_t launch_rte_lw_2str(const RteLw2strArgs &a, hipStream_t s);
+// ... in single precision (ecckd_rte_lw_2stream_f32, ecckd_lw_fluxes_allsky_2stream_f32): float arrays behind every data
+// pointer of the same argument block, the mask excepted; fast arithmetic mode only; the ring, in floats, takes the first
+// half of rte_lw_2str_scratch_bytes
+hipError_t launch_rte_lw_2str_f32(const RteLw2strArgs &a, hipStream_t s);
 
 // Element-wise operations on optical properties (kernels_optical_props.hip): RTE-RRTMGP's delta_scale_2str_k / _f_k and
 // the increment_* kernels (by g-point and by band).  Arrays (ncol,nlay,n), column fastest; f32: float data behind the pointers.

@@ -9,7 +9,7 @@
 // ([array][level][lane], 512 B coalesced rows); top -> surface re-reads tau / ssa / g and the level sources, recomputes
 // the coefficients and propagates the fluxes.  The level source is carried from one layer to the next: one sqrt and two
 // loads per level.  Per cell and pass: tau, ssa, g, lev_source_dec, lev_source_inc (40 B), plus 16 B to and 16 B from
-// the ring: 112 B.
+// the ring: 112 B -- in single precision (real = float) 20 B, 8 B and 8 B: 56 B.
 #include <type_traits>
 
 #include "kernels.hpp"
@@ -35,6 +35,7 @@ __device__ __forceinline__ double gsum_l2(double v) {
 
 constexpr int kL2Waves = 4096;        // persistent grid, as rte_sw (three waves per SIMD resident)
 constexpr int kL2WavesPerSimd = 3;
+constexpr int kL2WavesPerSimdF32 = 2;   // (see l2_prefetch)
 constexpr int kL2CW = 16;
 
 // acc += v by the owner lane only: one fire-and-forget ds_add_f64 (see kernels_rte_sw.hip)
@@ -44,17 +45,36 @@ __device__ __forceinline__ void acc_add_l2(double *p, double v, bool owner) {
 
 // What a lane keeps in flight per layer: the cell's three properties (PART: the gas optical depth and the band triple,
 // MASK: the half of the mask word that holds the lane's g-point) and the two level-source values of the layer's far level.
-template <bool PART> struct L2Slot;
-template <> struct L2Slot<false> { double t, s, g, dec, inc; };
-template <> struct L2Slot<true> { double t, pt, ps, pg, dec, inc; unsigned m; };
+template <typename real, bool PART> struct L2Slot;
+template <typename real> struct L2Slot<real, false> { real t, s, g, dec, inc; };
+template <typename real> struct L2Slot<real, true> { real t, pt, ps, pg, dec, inc; unsigned m; };
 
+// layers in flight per lane.  fp64: 3 (PART: 2) at three waves per SIMD.  Single precision: 6 (PART: 4) at TWO waves per
+// SIMD (kL2WavesPerSimdF32).  The double accumulators in LDS bound the resident waves whatever `real` is -- 256 B per level and
+// wave: 10 waves per CU at 60 layers, 4 at 137 -- so a third wave per SIMD is rarely there to lose, and a float layer in
+// flight is half the bytes: the float kernels need twice the depth to keep as many bytes in flight per wave.  A layer in
+// flight costs 17-20 VGPRs, most of them the addresses of its loads, so that depth does not fit three waves per SIMD (depth 4
+// spills there; depth 3 / 3 / 2 fits and was measured 0-10 % slower at 60 and 137 layers: DESIGN.md section 5.5c).
+template <typename real, bool PART> constexpr int l2_prefetch() { return (PART ? 2 : 3) * (sizeof(real) == 4 ? 2 : 1); }
+
+template <typename real> __device__ __forceinline__ real l2_pi();
+template <> __device__ __forceinline__ double l2_pi<double>() { return kLw2Pi; }
+template <> __device__ __forceinline__ float l2_pi<float>() { return kLw2PiF; }
+
+// real: storage and arithmetic type of everything per cell (tau, ssa, g or the band triple, both level-source planes, the
+// ring, sfc_emis, sfc_source, inc_flux, the flux outputs: float data behind the double pointers of RteLw2strArgs); the
+// g-point sums, the LDS accumulators and the owner-lane adds are double whatever `real` is, as in rte_sw_body.
 // FAST: arithmetic mode 0.  PART / MASK: the fused all-sky call (RteLw2strArgs::part_*).
-template <int CW, bool FAST, bool PART, bool MASK>
+template <typename real, int CW, bool FAST, bool PART, bool MASK>
 __device__ __forceinline__ void rte_lw_2str_body(const RteLw2strArgs &a) {
   static_assert(PART || !MASK, "a cloud mask belongs to the all-sky form");
   constexpr int GW = 64 / CW;
-  constexpr int PF = PART ? 2 : 3;   // layers in flight per lane
+  constexpr int PF = l2_prefetch<real, PART>();
+  typedef L2Slot<real, PART> Slot;
+  typedef decltype(lw_two_stream<FAST>(real(0), real(0), real(0), real(0), real(0))) Cell;
   extern __shared__ double acc[];    // [2][nlay+1][CW]: up, dn
+  auto P = [](const double *p) { return reinterpret_cast<const real *>(p); };
+  auto Q = [](double *p) { return reinterpret_cast<real *>(p); };
   const int lane = threadIdx.x;
   const int cl = lane % CW, gs = lane / CW;
   const bool owner = gs == 0;
@@ -62,8 +82,9 @@ __device__ __forceinline__ void rte_lw_2str_body(const RteLw2strArgs &a) {
   double *acc_up = acc, *acc_dn = acc + nlev * CW;
   const long lay0 = a.top_at_1 ? 0 : nlay - 1, lev0 = a.top_at_1 ? 0 : nlay;
   const long lstep = a.top_at_1 ? 1 : -1;
-  double *sc = a.scratch + (long)blockIdx.x * (2L * nlev) * 64 + lane;
-  double *sAlb = sc, *sSrc = sc + 64L * nlev;
+  // (elements of `real`: the float ring takes the first half of what rte_lw_2str_scratch_bytes provides)
+  real *sc = Q(a.scratch) + (long)blockIdx.x * (2L * nlev) * 64 + lane;
+  real *sAlb = sc, *sSrc = sc + 64L * nlev;
   const int ngroups = (ng + GW - 1) / GW;
   const long ntiles = ((long)ncol + CW - 1) / CW;
 
@@ -81,37 +102,37 @@ __device__ __forceinline__ void rte_lw_2str_body(const RteLw2strArgs &a) {
       const long base = cc + (long)ncol * nlay * gg;
       const int band = a.gpt2band[gg];
       // layer sl (counted from the top) and the two values behind the source of level `lv` into a prefetch slot
-      auto fetch = [&](int sl, int lv, L2Slot<PART> &p) __attribute__((always_inline)) {
+      auto fetch = [&](int sl, int lv, Slot &p) __attribute__((always_inline)) {
         const long lm = lay0 + lstep * sl;
         const long q = base + (long)ncol * lm;
-        p.t = a.tau[q];
+        p.t = P(a.tau)[q];
         if constexpr (PART) {
           const long qb = cc + (long)ncol * (lm + (long)nlay * band);
-          p.pt = a.part_tau[qb]; p.ps = a.part_ssa[qb]; p.pg = a.part_g[qb];
+          p.pt = P(a.part_tau)[qb]; p.ps = P(a.part_ssa)[qb]; p.pg = P(a.part_g)[qb];
           if constexpr (MASK) p.m = reinterpret_cast<const unsigned *>(a.part_mask)[2 * (cc + (long)ncol * lm) + (gg >> 5)];
         } else {
-          p.s = a.ssa[q]; p.g = a.g[q];
+          p.s = P(a.ssa)[q]; p.g = P(a.g)[q];
         }
         const long jm = lev0 + lstep * lv;
-        p.dec = a.lev_source_dec[base + (long)ncol * (jm < nlay ? jm : nlay - 1)];
-        p.inc = a.lev_source_inc[base + (long)ncol * (jm > 0 ? jm - 1 : 0)];
+        p.dec = P(a.lev_source_dec)[base + (long)ncol * (jm < nlay ? jm : nlay - 1)];
+        p.inc = P(a.lev_source_inc)[base + (long)ncol * (jm > 0 ? jm - 1 : 0)];
       };
-      auto level = [&](int lv, const L2Slot<PART> &p) __attribute__((always_inline)) {
+      auto level = [&](int lv, const Slot &p) __attribute__((always_inline)) {
         return lw2_level_source((int)(lev0 + lstep * lv), nlay, p.dec, p.inc);
       };
-      auto cell = [&](const L2Slot<PART> &p, double Bt, double Bb) __attribute__((always_inline)) {
+      auto cell = [&](const Slot &p, real Bt, real Bb) __attribute__((always_inline)) {
         if constexpr (PART) {
-          // increment_body<double, true, true, true, MASK> of kernels_optical_props.hip on op1 = (tau_gas, +0, +0)
-          constexpr double eps = op_eps<double>();
-          double t2 = p.pt;
-          if constexpr (MASK) t2 = (p.m >> (gg & 31)) & 1u ? t2 : 0.;
-          const double tscat2 = t2 * p.ps;
-          const double tsg2 = tscat2 * p.pg;
-          const double tau12 = p.t + t2;
-          const double tscat1 = p.t * 0.;
-          const double tauscat12 = tscat1 + tscat2;
-          const double cg = (tscat1 * 0. + tsg2) / (tauscat12 > eps ? tauscat12 : eps);
-          const double cssa = tauscat12 / (tau12 > eps ? tau12 : eps);
+          // increment_body<real, true, true, true, MASK> of kernels_optical_props.hip on op1 = (tau_gas, +0, +0)
+          constexpr real eps = op_eps<real>();
+          real t2 = p.pt;
+          if constexpr (MASK) t2 = (p.m >> (gg & 31)) & 1u ? t2 : real(0);
+          const real tscat2 = t2 * p.ps;
+          const real tsg2 = tscat2 * p.pg;
+          const real tau12 = p.t + t2;
+          const real tscat1 = p.t * real(0);
+          const real tauscat12 = tscat1 + tscat2;
+          const real cg = (tscat1 * real(0) + tsg2) / (tauscat12 > eps ? tauscat12 : eps);
+          const real cssa = tauscat12 / (tau12 > eps ? tau12 : eps);
           return lw_two_stream<FAST>(tau12, cssa, cg, Bt, Bb);
         } else {
           return lw_two_stream<FAST>(p.t, p.s, p.g, Bt, Bb);
@@ -119,24 +140,24 @@ __device__ __forceinline__ void rte_lw_2str_body(const RteLw2strArgs &a) {
       };
 
       // ---- pass 1, surface -> top: coefficients, layer sources, adding ----
-      const double emis = a.sfc_emis[band + (long)a.nband * cc];
-      double albedo = 1. - emis;
-      double src = kLw2Pi * emis * a.sfc_source[cc + (long)ncol * gg];
+      const real emis = P(a.sfc_emis)[band + (long)a.nband * cc];
+      real albedo = real(1) - emis;
+      real src = l2_pi<real>() * emis * P(a.sfc_source)[cc + (long)ncol * gg];
       sAlb[64L * nlay] = albedo;
       sSrc[64L * nlay] = src;
-      L2Slot<PART> slot[PF];
+      Slot slot[PF];
       fetch(nlay - 1, nlay, slot[0]);                 // (only the surface level's two values are used)
-      double Bb = level(nlay, slot[0]);
+      real Bb = level(nlay, slot[0]);
 #pragma unroll
       for (int d = 0; d < PF; ++d) { const int sl = nlay - 1 - d > 0 ? nlay - 1 - d : 0; fetch(sl, sl, slot[d]); }
       // (fixed prefetch slots, the layer loop unrolled by the depth: see rte_sw_body)
       auto layer1 = [&](int s, auto slot_c) __attribute__((always_inline)) {
         constexpr int d = decltype(slot_c)::value;
-        const L2Slot<PART> p = slot[d];
+        const Slot p = slot[d];
         { const int sn = s - PF > 0 ? s - PF : 0; fetch(sn, sn, slot[d]); }
-        const double Bt = level(s, p);
-        const Lw2Cell c = cell(p, Bt, Bb);
-        const double den = rcp<FAST>(1. - c.Rdif * albedo);
+        const real Bt = level(s, p);
+        const Cell c = cell(p, Bt, Bb);
+        const real den = rcp<FAST>(real(1) - c.Rdif * albedo);
         src = c.src_up + c.Tdif * den * (src + albedo * c.src_dn);
         albedo = c.Rdif + c.Tdif * c.Tdif * albedo * den;
         sAlb[64L * s] = albedo;
@@ -153,15 +174,15 @@ __device__ __forceinline__ void rte_lw_2str_body(const RteLw2strArgs &a) {
       }
 
       // ---- pass 2, top -> surface: fluxes ----
-      double Bt = Bb;                                  // the source of level 0, as pass 1 left it
-      double fdn = a.inc_flux ? a.inc_flux[cc + (long)ncol * gg] : 0.;
+      real Bt = Bb;                                    // the source of level 0, as pass 1 left it
+      real fdn = a.inc_flux ? P(a.inc_flux)[cc + (long)ncol * gg] : real(0);
       {
-        const double fup = fdn * albedo + src;
-        const double vu = gsum_l2<CW>(keep * fup), vd = gsum_l2<CW>(keep * fdn);
+        const real fup = fdn * albedo + src;
+        const double vu = gsum_l2<CW>(keep * (double)fup), vd = gsum_l2<CW>(keep * (double)fdn);
         acc_add_l2(&acc_up[cl], vu, owner);
         acc_add_l2(&acc_dn[cl], vd, owner);
       }
-      double palb[PF], psrc[PF];
+      real palb[PF], psrc[PF];
 #pragma unroll
       for (int d = 0; d < PF; ++d) {
         const int sl = d < nlay ? d : nlay - 1;
@@ -170,20 +191,20 @@ __device__ __forceinline__ void rte_lw_2str_body(const RteLw2strArgs &a) {
       }
       auto layer2 = [&](int s, auto slot_c) __attribute__((always_inline)) {
         constexpr int d = decltype(slot_c)::value;
-        const double alb_next = palb[d], src_next = psrc[d];
-        const L2Slot<PART> p = slot[d];
+        const real alb_next = palb[d], src_next = psrc[d];
+        const Slot p = slot[d];
         {
           const int sn = s + PF < nlay ? s + PF : nlay - 1;
           palb[d] = sAlb[64L * (sn + 1)]; psrc[d] = sSrc[64L * (sn + 1)];
           fetch(sn, sn + 1, slot[d]);
         }
-        const double Bn = level(s + 1, p);
-        const Lw2Cell c = cell(p, Bt, Bn);
-        const double den = rcp<FAST>(1. - c.Rdif * alb_next);   // the same expression as in pass 1: same bits
+        const real Bn = level(s + 1, p);
+        const Cell c = cell(p, Bt, Bn);
+        const real den = rcp<FAST>(real(1) - c.Rdif * alb_next);   // the same expression as in pass 1: same bits
         fdn = (c.Tdif * fdn + c.Rdif * src_next + c.src_dn) * den;
-        const double fup = fdn * alb_next + src_next;
+        const real fup = fdn * alb_next + src_next;
         Bt = Bn;
-        const double vu = gsum_l2<CW>(keep * fup), vd = gsum_l2<CW>(keep * fdn);
+        const double vu = gsum_l2<CW>(keep * (double)fup), vd = gsum_l2<CW>(keep * (double)fdn);
         acc_add_l2(&acc_up[(s + 1) * CW + cl], vu, owner);
         acc_add_l2(&acc_dn[(s + 1) * CW + cl], vd, owner);
       };
@@ -200,8 +221,8 @@ __device__ __forceinline__ void rte_lw_2str_body(const RteLw2strArgs &a) {
     if (valid) {
       for (int s = gs; s < nlev; s += GW) {
         const long q = col + (long)ncol * (lev0 + lstep * s);
-        a.flux_up[q] = acc_up[s * CW + cl];
-        a.flux_dn[q] = acc_dn[s * CW + cl];
+        Q(a.flux_up)[q] = (real)acc_up[s * CW + cl];
+        Q(a.flux_dn)[q] = (real)acc_dn[s * CW + cl];
       }
     }
   }
@@ -209,17 +230,30 @@ __device__ __forceinline__ void rte_lw_2str_body(const RteLw2strArgs &a) {
 
 template <int CW, bool FAST>
 __global__ void __launch_bounds__(64, kL2WavesPerSimd) rte_lw_2str_kernel(const RteLw2strArgs a) {
-  rte_lw_2str_body<CW, FAST, false, false>(a);
+  rte_lw_2str_body<double, CW, FAST, false, false>(a);
 }
 // the fused all-sky forms (fast arithmetic mode only), under their own names so that their figures can be told apart in the
 // code object (tools/kernel_resources.py)
 template <int CW>
 __global__ void __launch_bounds__(64, kL2WavesPerSimd) rte_lw_2str_allsky_kernel(const RteLw2strArgs a) {
-  rte_lw_2str_body<CW, true, true, false>(a);
+  rte_lw_2str_body<double, CW, true, true, false>(a);
 }
 template <int CW>
 __global__ void __launch_bounds__(64, kL2WavesPerSimd) rte_lw_2str_mcica_kernel(const RteLw2strArgs a) {
-  rte_lw_2str_body<CW, true, true, true>(a);
+  rte_lw_2str_body<double, CW, true, true, true>(a);
+}
+// the single-precision forms (launch_rte_lw_2str_f32; fast arithmetic mode only), each under its own name
+template <int CW>
+__global__ void __launch_bounds__(64, kL2WavesPerSimdF32) rte_lw_2str_f32_kernel(const RteLw2strArgs a) {
+  rte_lw_2str_body<float, CW, true, false, false>(a);
+}
+template <int CW>
+__global__ void __launch_bounds__(64, kL2WavesPerSimdF32) rte_lw_2str_allsky_f32_kernel(const RteLw2strArgs a) {
+  rte_lw_2str_body<float, CW, true, true, false>(a);
+}
+template <int CW>
+__global__ void __launch_bounds__(64, kL2WavesPerSimdF32) rte_lw_2str_mcica_f32_kernel(const RteLw2strArgs a) {
+  rte_lw_2str_body<float, CW, true, true, true>(a);
 }
 
 long l2_blocks(int ncol) {
@@ -235,6 +269,18 @@ size_t rte_lw_2str_scratch_bytes(int ncol, int nlay, int ng) {
   return sizeof(double) * (size_t)(2L * (nlay + 1)) * 64 * (size_t)l2_blocks(ncol);
 }
 
+namespace {
+hipError_t launch_l2(void (*k)(const RteLw2strArgs), const RteLw2strArgs &a, hipStream_t s) {
+  constexpr int CW = kL2CW;
+  const size_t lds = sizeof(double) * 2 * (size_t)(a.nlay + 1) * CW;
+  if (lds > (size_t)kLdsBudget) return hipErrorInvalidValue;
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k, dim3((unsigned)l2_blocks(a.ncol)), dim3(64), lds, s, a);
+  return hipGetLastError();
+}
+}  // namespace
+
 hipError_t launch_rte_lw_2str(const RteLw2strArgs &a, hipStream_t s) {
   if (a.ncol <= 0) return hipSuccess;
   constexpr int CW = kL2CW;
@@ -244,12 +290,17 @@ hipError_t launch_rte_lw_2str(const RteLw2strArgs &a, hipStream_t s) {
   auto k = a.part_mask ? rte_lw_2str_mcica_kernel<CW>
            : a.part_tau ? rte_lw_2str_allsky_kernel<CW>
            : a.exact_division ? rte_lw_2str_kernel<CW, false> : rte_lw_2str_kernel<CW, true>;
-  const size_t lds = sizeof(double) * 2 * (size_t)(a.nlay + 1) * CW;
-  if (lds > (size_t)kLdsBudget) return hipErrorInvalidValue;
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k, dim3((unsigned)l2_blocks(a.ncol)), dim3(64), lds, s, a);
-  return hipGetLastError();
+  return launch_l2(k, a, s);
+}
+
+hipError_t launch_rte_lw_2str_f32(const RteLw2strArgs &a, hipStream_t s) {
+  if (a.ncol <= 0) return hipSuccess;
+  constexpr int CW = kL2CW;
+  if (!a.scratch || a.exact_division) return hipErrorInvalidValue;
+  if (a.part_tau && (!a.part_ssa || !a.part_g)) return hipErrorInvalidValue;
+  if (a.part_mask && (!a.part_tau || a.ng > 64)) return hipErrorInvalidValue;
+  auto k = a.part_mask ? rte_lw_2str_mcica_f32_kernel<CW> : a.part_tau ? rte_lw_2str_allsky_f32_kernel<CW> : rte_lw_2str_f32_kernel<CW>;
+  return launch_l2(k, a, s);
 }
 
 }  // namespace ecckd

@@ -51,5 +51,63 @@ __device__ __forceinline__ double lw2_level_source(int jm, int nlay, double dec,
   return jm == 0 ? dec : (jm == nlay ? inc : sqrt(dec * inc));
 }
 
+// ---- single precision (ecckd_rte_lw_2stream_f32; the definition is spelt in include/ecckd_hip.h) ----
+// The fp64 expressions cannot be retyped: in float 1 - e2 loses its digits in a thin layer and under the k floor, gamma1 -
+// gamma2 loses them near ssa = 1, and the source terms (Z + Bt) - Rdif (-Z + Bt) - Tdif (Z + Bb) cancel quantities of size
+// dB / tau down to a result of size tau B.  The float cell forms every such difference from its parts instead:
+//   gamma1 - gamma2 = D (1 - ssa);   1 - e1 = n1 = -expm1(-x), x = k tau;   1 - e2 = m = n1 (1 + e1);   1 + e2 = 2 - m;
+//   1 - Rdif - Tdif = A1 = RT (k n1^2 + (gamma1 - gamma2) m);
+//   Z (1 + Rdif - Tdif) - Tdif dB = dB A2,  A2 = RT (k n1^2 / (tau (gamma1 + gamma2)) + k G),  G = m / x - 2 e1;
+//   src_up = pi (Bt A1 + dB A2),  src_dn = pi (Bb A1 - dB A2)
+// -- sums of positive terms but for G = 2 e1 (sinh(x) / x - 1), which is its series below kLw2XLinF (where the errors of
+// the two forms cross: tests/test_lw_2stream_f32_host.py).  To first order in tau both sources are
+// pi (gamma1 - gamma2) tau (Bt + Bb) / 2.  The floor under the square root stays 1e-12 (nothing divides by 1 - e2 any more);
+// a layer emits where tau > 1e-30, so that the two quotients are taken of normal numbers.
+constexpr float kLw2DF = 1.66f;
+constexpr float kLw2PiF = 3.14159265358979323846f;
+constexpr float kLw2KFloorF = 1.e-12f;
+constexpr float kLw2TauMinF = 1.e-30f;
+constexpr float kLw2XLinF = 0.7f;
+
+template <typename real> struct Lw2CellT { real Rdif, Tdif, src_up, src_dn; };
+
+// FAST: rcp<true> (hardware reciprocal and one Newton step); expf / expm1f / sqrtf are the device library's in both modes
+template <bool FAST>
+__device__ __forceinline__ Lw2CellT<float> lw_two_stream(float tau, float ssa, float g, float Bt, float Bb) {
+  const float gamma1 = kLw2DF * (1.f - 0.5f * ssa * (1.f + g));
+  const float gamma2 = kLw2DF * 0.5f * ssa * (1.f - g);
+  const float gm = kLw2DF * (1.f - ssa);
+  const float gp = gamma1 + gamma2;
+  const float kk0 = gm * gp;
+  const float k = sw_sqrt<FAST>(kk0 > kLw2KFloorF ? kk0 : kLw2KFloorF);
+  const float x = tau * k;
+  const float e1 = sw_exp<FAST>(-x);
+  const float n1 = -expm1f(-x);
+  const float m = n1 * (1.f + e1);
+  const float RT = rcp<FAST>(k * (2.f - m) + gamma1 * m);
+  Lw2CellT<float> c;
+  c.Rdif = RT * gamma2 * m;
+  c.Tdif = RT * 2.f * k * e1;
+  const float kn = k * n1 * n1;
+  const float A1 = RT * (kn + gm * m);
+  const float x2 = x * x;
+  const float Gs = e1 * (x2 * (1.f / 3.f)) * (1.f + (x2 * (1.f / 20.f)) * (1.f + x2 * (1.f / 42.f)));
+  const float Gd = m * rcp<FAST>(x) - 2.f * e1;
+  const float G = x < kLw2XLinF ? Gs : Gd;
+  const float A2 = RT * (kn * rcp<FAST>(tau * gp) + k * G);
+  const float dB = Bb - Bt;
+  const float su = kLw2PiF * (Bt * A1 + dB * A2);
+  const float sd = kLw2PiF * (Bb * A1 - dB * A2);
+  const bool emits = tau > kLw2TauMinF;
+  c.src_up = emits ? su : 0.f;
+  c.src_dn = emits ? sd : 0.f;
+  return c;
+}
+
+// (sqrtf of a product that underflows gives 0: a level source below 1e-19 W m-2 sr-1, which no flux can show)
+__device__ __forceinline__ float lw2_level_source(int jm, int nlay, float dec, float inc) {
+  return jm == 0 ? dec : (jm == nlay ? inc : sqrtf(dec * inc));
+}
+
 }  // namespace
 }  // namespace ecckd
