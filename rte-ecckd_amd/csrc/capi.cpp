@@ -182,6 +182,7 @@ size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
 size_t esz(bool f32) { return f32 ? sizeof(float) : sizeof(double); }
 inline const double *dp(const float *p) { return reinterpret_cast<const double *>(p); }
 inline double *dp(float *p) { return reinterpret_cast<double *>(p); }
+inline const double *const *dp(const float *const *p) { return reinterpret_cast<const double *const *>(p); }
 
 // ecckd_sw_fluxes: the shortwave solver derives ssa / g / toa itself (RteSwArgs::derive) and works in `room` inside
 // ecckd_sw_fluxes' own scratch block (sw_fluxes_solver_bytes): the partial sums of the layer-systolic solver, or the
@@ -2081,40 +2082,284 @@ static size_t fused_scratch_doubles(const ecckd_model *m, int ncol, int nlay) {
   return 3 * n3 + (size_t)ncol * m->ng + 32 + ecckd::rte_lw_scratch_bytes(ncol, nlay, m->ng) / sizeof(double);
 }
 
-// ecckd_lw_fluxes_allsky: the combined particulate optical properties on the model's bands, (ncol,nlay,nband) each, on the
-// device; ssa == nullptr: one-stream particles
+// ---- a fused flux call is Columns + Particles + outputs ----
+// An entry point fills these structs from its own parameters, once (the _f32 ones through dp(): float data behind the double
+// pointers), and everything below it takes the structs.  Each has one member that declares its arrays to a Stage and
+// returns the image the kernels read: the only place those declarations stand, so their order is the same in every call.
+
+// The atmosphere and the boundary conditions of a longwave call, in the memory space of the call
+struct LwColumns {
+  int ncol, nlay;
+  const double *plev, *tlay, *tsfc, *tlev;
+  GasDesc gas;
+  int top_at_1, n_gauss_angles;
+  const double *sfc_emis, *inc_flux;
+  LwColumns staged(Stage &st, const Counts &n) const {
+    LwColumns d = *this;
+    d.plev = st.in(plev, n.lev); d.tlay = st.in(tlay, n.lay); d.tsfc = st.in(tsfc, n.col); d.tlev = st.in(tlev, n.lev);
+    d.sfc_emis = st.in(sfc_emis, n.col_b); d.inc_flux = st.in(inc_flux, n.col_g);
+    d.gas = st.gases(gas, ncol, nlay);
+    return d;
+  }
+  bool null_array() const { return !plev || !tlay || !tsfc || !sfc_emis || (gas.ngas > 0 && !gas.names); }
+};
+
+// ... of a shortwave call
+struct SwColumns {
+  int ncol, nlay;
+  const double *plev, *tlay;
+  GasDesc gas;
+  int top_at_1;
+  const double *mu0, *toa_scale, *sfc_alb_dir, *sfc_alb_dif;
+  SwColumns staged(Stage &st, const Counts &n) const {
+    SwColumns d = *this;
+    d.plev = st.in(plev, n.lev); d.tlay = st.in(tlay, n.lay); d.mu0 = st.in(mu0, n.col); d.toa_scale = st.in(toa_scale, n.col);
+    d.sfc_alb_dir = st.in(sfc_alb_dir, n.col_b); d.sfc_alb_dif = st.in(sfc_alb_dif, n.col_b);
+    d.gas = st.gases(gas, ncol, nlay);
+    return d;
+  }
+  bool null_array() const { return !plev || !tlay || !mu0 || !sfc_alb_dir || !sfc_alb_dif || (gas.ngas > 0 && !gas.names); }
+};
+
+// The combined particulate optical properties on the model's bands, (ncol,nlay,nband) each, in the memory space of the call;
+// tau == nullptr: no particles.  Longwave: ssa == nullptr: one-stream particles; g: the scattering solvers only.
+// mask: the McICA cloud mask (ncol,nlay), or null.  scaling: ecckd_*_flux_scaled -- the sampled optical-depth scaling
+// (ncol,nlay,ngpt), float32, or null; in the longwave the scaled by-band increment then runs on the scratch tau at every
+// layer count and the solver sees no particles.
 static const char kMaskTooWide[] = ": a cloud mask is one 64-bit word per (column, layer): at most 64 g-points, not ";
-// mask: ecckd_lw_fluxes_allsky_mcica -- the cloud mask (ncol,nlay), in the memory space of the call, or null
-// scaling: ecckd_lw_flux_scaled -- the sampled optical-depth scaling (ncol,nlay,ngpt), float32, in the memory space of the
-// call, or null; with it the scaled by-band increment runs on the scratch tau at every layer count and the solver sees no particles
-struct LwParticles { const double *tau, *ssa; const unsigned long long *mask = nullptr; const float *scaling = nullptr; };
+struct LwParticles {
+  const double *tau = nullptr, *ssa = nullptr, *g = nullptr;
+  const unsigned long long *mask = nullptr;
+  const float *scaling = nullptr;
+  LwParticles staged(Stage &st, const Counts &n) const {
+    LwParticles d;
+    d.tau = st.in(tau, n.lay_b); d.ssa = st.in(ssa, n.lay_b); d.g = st.in(g, n.lay_b);
+    d.mask = st.in(mask, n.lay);
+    d.scaling = static_cast<const float *>(st.in_bytes(scaling, n.lay_g * sizeof(float)));
+    return d;
+  }
+};
+// Shortwave: delta_scale: the library delta-scales a copy (f = g*g) first
+struct SwParticles {
+  const double *tau = nullptr, *ssa = nullptr, *g = nullptr;
+  int delta_scale = 0;
+  const unsigned long long *mask = nullptr;
+  const float *scaling = nullptr;
+  SwParticles staged(Stage &st, const Counts &n) const {
+    SwParticles d;
+    d.tau = st.in(tau, n.lay_b); d.ssa = st.in(ssa, n.lay_b); d.g = st.in(g, n.lay_b);
+    d.delta_scale = delta_scale;
+    d.mask = st.in(mask, n.lay);
+    d.scaling = static_cast<const float *>(st.in_bytes(scaling, n.lay_g * sizeof(float)));
+    return d;
+  }
+};
 
-// ecckd_*_fluxes_clear_allsky: where the clear-sky fluxes go (dir: shortwave only, may be null), in the memory space of the call
-struct ClearFluxes { double *up, *dn, *dir; };
+// One set of fluxes, (ncol,nlay+1) each -- (ncol,nlay+1,nband) for the band planes -- in the memory space of the call;
+// dir: shortwave only, may be null
+struct Fluxes {
+  double *up = nullptr, *dn = nullptr, *dir = nullptr;
+  Fluxes staged(Stage &st, size_t n) const { return Fluxes{st.out(up, n), st.out(dn, n), st.out(dir, n)}; }
+};
+// What a fused call delivers: the fluxes of the sky it computes, and -- each only where the call has it and the caller
+// names it -- the clear-sky fluxes next to them, the band planes, flux_up_jac
+struct FluxOutputs {
+  Fluxes all, clear, bands;
+  double *jac = nullptr;
+};
 
-// `both` (60-layer route with `pt` only): the dual-sky kernel, clear-sky fluxes to *both and all-sky fluxes to flux_up / flux_dn
+// first[b] = first 0-based g-point of band b, first[nband] = ngpt; the bands must tile 1..ngpt in ascending order
+static int band_windows(const ecckd_model *m, const char *who, unsigned short *first) {
+  int next = 1;
+  for (int b = 0; b < m->nband; ++b) {
+    if (m->band2gpt[2 * b] != next || m->band2gpt[2 * b + 1] < next)
+      return fail(std::string(who) + ": the model's band2gpt does not tile 1..ngpt in ascending order");
+    first[b] = (unsigned short)(next - 1);
+    next = m->band2gpt[2 * b + 1] + 1;
+  }
+  if (next != m->ng + 1) return fail(std::string(who) + ": the model's band2gpt does not tile 1..ngpt in ascending order");
+  first[m->nband] = (unsigned short)m->ng;
+  return 0;
+}
+
+static int outputs_alias(const char *who, std::initializer_list<const double *> outs) {
+  for (auto p = outs.begin(); p != outs.end(); ++p)
+    for (auto q = p + 1; q != outs.end(); ++q)
+      if (*p && *p == *q) return fail(std::string(who) + ": two outputs are the same array (each needs an array of its own)");
+  return 0;
+}
+
+// a clear-sky output that is an all-sky output as well
+static bool clear_aliases_all(const Fluxes &clear, const Fluxes &all) {
+  for (double *c : {clear.up, clear.dn, clear.dir})
+    for (double *f : {all.up, all.dn, all.dir})
+      if (c && c == f) return true;
+  return false;
+}
+
+// ---- what a fused call refuses ----
+// The words of a call in the refusals that the calls share: data only.  The shared lists below are short and linear; an
+// implementation calls them in its order, with its own checks in between, and ends with one of the three tails
+// (lw_plain_tail / sw_plain_tail, on_device, bands_tail).  What needs no device comes before check_model, so that a
+// host-only model answers it too.
+struct CallWords {
+  const char *who = nullptr;             // the call's name in the messages of its list
+  const char *who_mask = nullptr;        // ... where it refuses a mask on more than 64 g-points
+  const char *planes_tail = nullptr;     // behind `who` where a required plane is missing; null: the call names no particles
+  bool need_ssa_g = true;                // tau_p, ssa_p and g_p are required (longwave one-stream calls: tau_p alone)
+  bool nband0_clear = false;             // nband_p = 0 is the clear sky: no plane and no mask then
+  const char *no_particles_tail = nullptr;   // tau_p NULL is the clear sky: behind `who` where something of the particles' is named then
+  const char *who_clear = nullptr, *clear_tail = nullptr;   // the name and the words where flux_up_clear or flux_dn_clear is missing
+  bool clear_required = false;           // the clear-sky outputs are part of the call (else: named by giving one)
+  const char *tlev_text = "tlev is required for ecckd";
+};
+
+static int refuse(const char *who, const char *tail) { return fail(std::string(who) + tail); }
+
+// null model, a mask on more than 64 g-points, nband_p, the planes (`ssa` / `g`: as the call requires them)
+static int particles_refusals(const CallWords &w, const ecckd_model *m, int nband_p, const double *tau, const double *ssa,
+                              const double *g, const unsigned long long *mask) {
+  if (!m) return fail("ecckd: null model");
+  if (mask && m->ng > 64) return fail(w.who_mask + std::string(kMaskTooWide) + std::to_string(m->ng));
+  const bool clear_sky = w.nband0_clear && nband_p == 0;
+  if (nband_p != m->nband && !clear_sky)
+    return fail(std::string(w.who) + ": nband_p = " + std::to_string(nband_p) + " but the model has " + std::to_string(m->nband) +
+                " bands (particulate properties live on the model's bands" + (w.nband0_clear ? "; 0: clear sky)" : ")"));
+  if (!clear_sky && (!tau || (w.need_ssa_g && (!ssa || !g)))) return refuse(w.who, w.planes_tail);
+  if (clear_sky && (tau || ssa || g || mask))
+    return refuse(w.who, ": nband_p = 0 is the clear sky: the particulate planes and cloud_mask must be null");
+  return 0;
+}
+
+// the clear-sky outputs: both or (where the call allows that) neither, and none of them an all-sky output
+static int clear_refusals(const CallWords &w, const FluxOutputs &o) {
+  if (!w.clear_required && !o.clear.up && !o.clear.dn && !o.clear.dir) return 0;
+  if (!o.clear.up || !o.clear.dn) return refuse(w.who_clear, w.clear_tail);
+  if (clear_aliases_all(o.clear, o.all))
+    return refuse(w.who_clear, ": a clear-sky output must not be an all-sky output (the two sets of fluxes need arrays of their own)");
+  return 0;
+}
+
+static int jac_refusals(const char *who_jac, const FluxOutputs &o, bool with_clear = true) {
+  if (o.jac && (o.jac == o.all.up || o.jac == o.all.dn || (with_clear && (o.jac == o.clear.up || o.jac == o.clear.dn))))
+    return refuse(who_jac, ": flux_up_jac must not be another output (it needs an array of its own)");
+  return 0;
+}
+
+static int gauss_refusals(const LwColumns &c, const char *lead = "rte_lw") {
+  if (c.n_gauss_angles >= 1 && c.n_gauss_angles <= 4) return 0;
+  return refuse(lead, ": have to ask for at least one quadrature point and no more than 4");
+}
+
+// The head of every longwave list that names particles: particles, arithmetic mode, Planck table, tlev
+static int lw_head(const CallWords &w, const ecckd_model *m, const LwColumns &c, int nband_p, const LwParticles &pt) {
+  if (particles_refusals(w, m, nband_p, pt.tau, pt.ssa, pt.g, pt.mask)) return 1;
+  if (g_arith.load() != 0) return refuse(w.who, ": needs the fast arithmetic mode (ecckd_set_arithmetic(0))");
+  if (!m->has_planck) return refuse(w.who, ": model has no Planck table (shortwave model?)");
+  if (!c.tlev) return fail(w.tlev_text);
+  return 0;
+}
+
+// ... of every shortwave list that names particles: particles (tau_p NULL: the clear sky, where the call has that),
+// delta_scale, arithmetic mode
+static int sw_head(const CallWords &w, const ecckd_model *m, int nband_p, const SwParticles &pt, const FluxOutputs &o) {
+  if (w.no_particles_tail && !pt.tau) {
+    if (!m) return fail("ecckd: null model");
+    if (pt.mask && m->ng > 64) return fail(w.who_mask + std::string(kMaskTooWide) + std::to_string(m->ng));
+    if (pt.ssa || pt.g || pt.mask || o.clear.up || o.clear.dn || o.clear.dir) return refuse(w.who, w.no_particles_tail);
+  } else {
+    if (particles_refusals(w, m, nband_p, pt.tau, pt.ssa, pt.g, pt.mask)) return 1;
+    if (pt.delta_scale != 0 && pt.delta_scale != 1) return refuse(w.who, ": delta_scale must be 0 or 1");
+  }
+  if (g_arith.load() != 0) return refuse(w.who, ": needs the fast arithmetic mode (ecckd_set_arithmetic(0))");
+  return 0;
+}
+
+// Tail: behind check_model, the dimensions and the call's null arrays -- memory space, device, and *done where the call
+// has no columns and returns 0
+static int on_device(const ecckd_model *m, int ncol, int memspace, bool *done) {
+  if (memspace != ECCKD_DEVICE && memspace != ECCKD_HOST) return fail("ecckd: bad memspace");
+  HIPCHK(hipSetDevice(m->device));
+  *done = ncol == 0;
+  return 0;
+}
+
+// Tail of ecckd_{lw,sw}_flux_bands, which put their name in front of every message: memory space, the model, the
+// dimensions, null arrays, the band windows into `first`
+static int bands_tail(const char *who, const ecckd_model *m, int ncol, int nlay, bool null_array, int memspace,
+                      unsigned short *first, bool *done) {
+  if (memspace != ECCKD_DEVICE && memspace != ECCKD_HOST) return refuse(who, ": bad memspace (ECCKD_DEVICE or ECCKD_HOST)");
+  if (!m->finalized) return refuse(who, ": model is not finalized");
+  if (m->device < 0) return refuse(who, ": host-only model (device -1): no GPU, no compute (there is no CPU fallback)");
+  if (check_gas_optics_dims(ncol, nlay)) return 1;
+  if (null_array) return refuse(who, ": null argument");
+  if (band_windows(m, who, first)) return 1;
+  HIPCHK(hipSetDevice(m->device));
+  *done = ncol == 0;
+  return 0;
+}
+
+// Tail: the list of ecckd_lw_fluxes, which the all-sky forms on its solver run through behind their own (a call without
+// columns returns before the memory space is looked at).  Without tau_p nothing of the particles' may be named
+// (ecckd_lw_fluxes_jac).
+static int lw_plain_tail(const ecckd_model *m, const LwColumns &c, int nband_p, const LwParticles &pt, const FluxOutputs &o,
+                         int memspace, bool *done) {
+  if (check_model(m) || check_gas_optics_dims(c.ncol, c.nlay)) return 1;
+  if (!m->has_planck) return fail("ecckd_lw_fluxes: model has no Planck table (shortwave model?)");
+  if (gauss_refusals(c)) return 1;
+  if (c.null_array() || !o.all.up || !o.all.dn) return fail("ecckd_lw_fluxes: null argument");
+  if (!c.tlev) return fail("tlev is required for ecckd");
+  if (g_arith.load() != 0) return fail("ecckd_lw_fluxes: needs the fast arithmetic mode (ecckd_set_arithmetic(0))");
+  if (jac_refusals("ecckd_lw_fluxes_jac", o, false)) return 1;
+  if (!pt.tau && (nband_p != 0 || pt.ssa || pt.mask || o.clear.up || o.clear.dn))
+    return fail("ecckd_lw_fluxes_jac: nband_p, cloud_mask and the clear-sky outputs belong to particles: without tau_p they must be 0 / null");
+  HIPCHK(hipSetDevice(m->device));
+  *done = c.ncol == 0;
+  if (!*done && memspace != ECCKD_DEVICE && memspace != ECCKD_HOST) return fail("ecckd: bad memspace");
+  return 0;
+}
+
+// ... and that of ecckd_sw_fluxes
+static int sw_plain_tail(const ecckd_model *m, const SwColumns &c, const FluxOutputs &o, int memspace, bool *done) {
+  if (check_model(m) || check_gas_optics_dims(c.ncol, c.nlay)) return 1;
+  if (!m->has_solar) return fail("ecckd_sw_fluxes: model has no solar table (longwave model?)");
+  if (c.null_array() || !o.all.up || !o.all.dn) return fail("ecckd_sw_fluxes: null argument");
+  if (g_arith.load() != 0) return fail("ecckd_sw_fluxes: needs the fast arithmetic mode (ecckd_set_arithmetic(0))");
+  HIPCHK(hipSetDevice(m->device));
+  *done = c.ncol == 0;
+  if (!*done && memspace != ECCKD_DEVICE && memspace != ECCKD_HOST) return fail("ecckd: bad memspace");
+  return 0;
+}
+
+// The kernel arguments every longwave solver launch of a model starts from (`c`: staged)
+static int lw_solver_args(const ecckd_model *m, const LwColumns &c, bool f32, ecckd::RteLwArgs &a) {
+  if (fill_band_map(m->ng, m->nband, m->band2gpt.data(), a.gpt2band)) return 1;
+  a.ncol = c.ncol; a.nlay = c.nlay; a.ng = m->ng; a.top_at_1 = c.top_at_1 ? 1 : 0; a.nband = m->nband;
+  a.f32 = f32 ? 1 : 0;
+  fill_lw_options(a, c.n_gauss_angles, f32);
+  a.sfc_emis = c.sfc_emis; a.inc_flux = c.inc_flux;
+  return 0;
+}
+
+// `both` (60-layer route with `pt` only): the dual-sky kernel, clear-sky fluxes to *both and all-sky fluxes to `to`
 // `pt` (60-layer route only): the band planes the solver adds to tau as it reads it; the general route gets a tau that
 // launch_increment has incremented already
 // `jac_inline` (60-layer route, without `both`): the Jacobian form of the kernel, which stores flux_up_jac there as well
 // `sources` (general route only; ecckd_lw_fluxes_rescaled_jac): the Planck sources are there already, wherever the caller
 // keeps them, and `scratch` is the solver's ring alone
-static int rte_lw_fused_dev(const ecckd_model *m, int ncol, int nlay, int top_at_1, int n_gauss_angles, const double *tau,
-                            const double *tlay, const double *tlev, const double *tsfc, const double *sfc_emis,
-                            const double *inc_flux, double *flux_up, double *flux_dn, double *scratch, hipStream_t stream,
-                            const LwParticles *pt = nullptr, const ClearFluxes *both = nullptr, bool sources_in_scratch = false,
-                            double *jac_inline = nullptr, const PlanckSide *sources = nullptr) {
+static int rte_lw_fused_dev(const ecckd_model *m, const LwColumns &c, const double *tau, const Fluxes &to, double *scratch,
+                            hipStream_t stream, const LwParticles *pt = nullptr, const Fluxes *both = nullptr,
+                            bool sources_in_scratch = false, double *jac_inline = nullptr, const PlanckSide *sources = nullptr) {
+  const int ncol = c.ncol, nlay = c.nlay;
   ecckd::RteLwArgs a{};
-  if (fill_band_map(m->ng, m->nband, m->band2gpt.data(), a.gpt2band)) return 1;
-  a.ncol = ncol; a.nlay = nlay; a.ng = m->ng; a.top_at_1 = top_at_1 ? 1 : 0;
-  a.nband = m->nband;
-  fill_lw_options(a, n_gauss_angles, false);
+  if (lw_solver_args(m, c, false, a)) return 1;
   a.use_split = 1;
-  a.tau = tau; a.sfc_emis = sfc_emis; a.inc_flux = inc_flux; a.flux_up = flux_up; a.flux_dn = flux_dn;
+  a.tau = tau; a.flux_up = to.up; a.flux_dn = to.dn;
   if (fused_lw_kernels_apply(m, nlay)) {
     if (pt) { a.part_tau = pt->tau; a.part_ssa = pt->ssa; a.part_1scl = pt->ssa ? 0 : 1; a.part_mask = pt->mask; }
     ProfScope prof("rte_lw_fused", stream);
     HIPCHK(ecckd::launch_rte_lw_planck(a, m->dbuf + m->off_planck, m->ntp, m->temperature_planck[0],
-                                       m->temperature_planck[1] - m->temperature_planck[0], tlay, tlev, tsfc, stream,
+                                       m->temperature_planck[1] - m->temperature_planck[0], c.tlay, c.tlev, c.tsfc, stream,
                                        both ? both->up : nullptr, both ? both->dn : nullptr, jac_inline));
     return 0;
   }
@@ -2130,12 +2375,12 @@ static int rte_lw_fused_dev(const ecckd_model *m, int ncol, int nlay, int top_at
     lay = scratch; inc = lay + n3; dec = inc + n3; sfc = dec + n3; ring = sfc + (((size_t)ncol * m->ng + 31) & ~(size_t)31);
   }
   if (!sources && !sources_in_scratch) {   // (the all-sky pass of ecckd_lw_fluxes_clear_allsky finds the clear pass's sources there)
-    ecckd::PlanckArgs p = planck_args(m, ncol, nlay, tlay, PlanckSide{tlev, tsfc, lay, inc, dec, sfc});
+    ecckd::PlanckArgs p = planck_args(m, ncol, nlay, c.tlay, PlanckSide{c.tlev, c.tsfc, lay, inc, dec, sfc});
     ProfScope prof("planck", stream);
     HIPCHK(ecckd::launch_planck(p, stream));
   }
   a.lay_source = lay; a.lev_source_inc = inc; a.lev_source_dec = dec; a.sfc_source = sfc;
-  a.shared_levels = inc_flux ? 0 : 1;
+  a.shared_levels = c.inc_flux ? 0 : 1;
   a.use_split = 0;
   a.scratch = ecckd::rte_lw_scratch_bytes(ncol, nlay, m->ng) ? ring : nullptr;
   ProfScope prof("rte_lw", stream);
@@ -2159,28 +2404,21 @@ int ecckd_rte_lw_fused(const ecckd_model_t *m, int ncol, int nlay, int top_at_1,
   ScratchLease lease;
   const size_t extra = fused_scratch_doubles(m, ncol, nlay);
   if (extra && stream_scratch(m->device, st, extra * sizeof(double), &sp, lease)) return 1;
-  return rte_lw_fused_dev(m, ncol, nlay, top_at_1, n_gauss_angles, tau, tlay, tlev, tsfc, sfc_emis, inc_flux, flux_up,
-                          flux_dn, static_cast<double *>(sp), st);
+  const LwColumns c{ncol, nlay, nullptr, tlay, tsfc, tlev, GasDesc{}, top_at_1, n_gauss_angles, sfc_emis, inc_flux};
+  return rte_lw_fused_dev(m, c, tau, Fluxes{flux_up, flux_dn}, static_cast<double *>(sp), st);
 }
 
 // General route of the all-sky call (any layer count): tau += the particles' (absorption) optical depth by band, the
 // one-stream-op1 increment kernel of ecckd_increment on the scratch tau between gas optics and the solver
-// (ssa1 / g1 / g2: ecckd_lw_fluxes_allsky_rescaled -- the two-stream increment on (tau, ssa1, g1) with the band triple)
+// (ssa1 / g1: ecckd_lw_fluxes_allsky_rescaled -- the two-stream increment on (tau, ssa1, g1) with the band triple)
 static int lw_increment_dev(const ecckd_model *m, int ncol, int nlay, double *tau, const LwParticles &pt, hipStream_t stream,
-                            double *ssa1 = nullptr, double *g1 = nullptr, const double *g2 = nullptr) {
+                            double *ssa1 = nullptr, double *g1 = nullptr) {
   ecckd::OptPropsArgs o{};
   o.ncol = ncol; o.nlay = nlay; o.ng = m->ng; o.nband = m->nband; o.f32 = 0;
-  int next = 1;   // the increment kernel wants bands in ascending order that tile 1..ngpt, as ecckd_increment checks
-  for (int b = 0; b < m->nband; ++b) {
-    if (m->band2gpt[2 * b] != next || m->band2gpt[2 * b + 1] < next)
-      return fail("ecckd_lw_fluxes_allsky: the model's band2gpt does not tile 1..ngpt in ascending order");
-    o.band_first[b] = (unsigned short)(next - 1);
-    next = m->band2gpt[2 * b + 1] + 1;
-  }
-  if (next != m->ng + 1) return fail("ecckd_lw_fluxes_allsky: the model's band2gpt does not tile 1..ngpt in ascending order");
-  o.band_first[m->nband] = (unsigned short)m->ng;
+  // the increment kernel wants bands in ascending order that tile 1..ngpt, as ecckd_increment checks
+  if (band_windows(m, "ecckd_lw_fluxes_allsky", o.band_first)) return 1;
   o.tau1 = tau; o.tau2 = pt.tau; o.ssa2 = pt.ssa; o.g2 = pt.ssa;   // (g2 marks op2 as two-stream; 1scl += 2str never reads it)
-  if (ssa1) { o.ssa1 = ssa1; o.g1 = g1; o.g2 = g2; }
+  if (ssa1) { o.ssa1 = ssa1; o.g1 = g1; o.g2 = pt.g; }
   o.mask = pt.mask;   // (McICA: the masked by-band increment)
   o.scaling = pt.scaling;
   ProfScope prof("increment", stream);
@@ -2192,115 +2430,104 @@ static int lw_increment_dev(const ecckd_model *m, int ncol, int nlay, double *ta
 // all-sky kernel one after the other, or the dual-sky kernel ("lw_both_skies").  Any other layer count: Planck sources into
 // scratch once, the clear pass, the by-band increment in place, the solver again -- the clear pass has to see tau before
 // the increment.
-static int lw_both_skies_dev(const ecckd_model *m, int ncol, int nlay, int top_at_1, int n_gauss_angles, double *tau,
-                             const double *tlay, const double *tlev, const double *tsfc, const double *sfc_emis,
-                             const double *inc_flux, double *flux_up, double *flux_dn, double *scratch, hipStream_t stream,
-                             const LwParticles &pt, const ClearFluxes &clr, double *jac_inline = nullptr) {
-  const bool fused = fused_lw_kernels_apply(m, nlay);
+static int lw_both_skies_dev(const ecckd_model *m, const LwColumns &c, double *tau, const LwParticles &pt, const FluxOutputs &o,
+                             double *scratch, hipStream_t stream, double *jac_inline = nullptr) {
+  const bool fused = fused_lw_kernels_apply(m, c.nlay);
   // (jac_inline: the dual-sky kernel has no Jacobian form -- two launches, the all-sky one the Jacobian kernel; same fluxes)
-  if (fused && g_opt.lw_both_skies.load() == 1 && !jac_inline)
-    return rte_lw_fused_dev(m, ncol, nlay, top_at_1, n_gauss_angles, tau, tlay, tlev, tsfc, sfc_emis, inc_flux, flux_up, flux_dn,
-                            scratch, stream, &pt, &clr);
-  if (rte_lw_fused_dev(m, ncol, nlay, top_at_1, n_gauss_angles, tau, tlay, tlev, tsfc, sfc_emis, inc_flux, clr.up, clr.dn, scratch,
-                       stream))
-    return 1;
-  if (!fused && lw_increment_dev(m, ncol, nlay, tau, pt, stream)) return 1;
-  return rte_lw_fused_dev(m, ncol, nlay, top_at_1, n_gauss_angles, tau, tlay, tlev, tsfc, sfc_emis, inc_flux, flux_up, flux_dn,
-                          scratch, stream, &pt, nullptr, !fused, jac_inline);
+  if (fused && g_opt.lw_both_skies.load() == 1 && !jac_inline) return rte_lw_fused_dev(m, c, tau, o.all, scratch, stream, &pt, &o.clear);
+  if (rte_lw_fused_dev(m, c, tau, o.clear, scratch, stream)) return 1;
+  if (!fused && lw_increment_dev(m, c.ncol, c.nlay, tau, pt, stream)) return 1;
+  return rte_lw_fused_dev(m, c, tau, o.all, scratch, stream, &pt, nullptr, !fused, jac_inline);
 }
-
-// ecckd_lw_fluxes_jac: where the Jacobian goes (in the memory space of the call; null: none), and whether the call named
-// particles, a mask or clear-sky outputs without tau_p (refused behind the existing call's list)
-struct LwJac { double *jac; bool stray; };
 
 // flux_up_jac behind the flux pass(es) of a fused call, from the scratch tau: the stand-alone Jacobian kernel with the
 // surface term formed from tsfc and the Planck table.  On the 60-layer route the flux kernel has added the particles as it
 // read tau, so the Jacobian kernel does the same (`pt`); on the general route tau was incremented in place.
-static int lw_jac_dev(const ecckd_model *m, int ncol, int nlay, int top_at_1, int n_gauss_angles, const double *tau,
-                      const double *tsfc, const double *sfc_emis, const LwParticles *pt, double *jac, hipStream_t stream) {
+static int lw_jac_dev(const ecckd_model *m, const LwColumns &c, const double *tau, const LwParticles *pt, double *jac,
+                      hipStream_t stream) {
   ecckd::RteLwJacArgs j{};
   if (fill_band_map(m->ng, m->nband, m->band2gpt.data(), j.gpt2band)) return 1;
-  fill_jac_args(j, ncol, nlay, m->ng, top_at_1, n_gauss_angles, m->nband);
-  j.tau = tau; j.tsfc = tsfc; j.sfc_emis = sfc_emis; j.flux_up_jac = jac;
-  if (pt && fused_lw_kernels_apply(m, nlay)) { j.part_tau = pt->tau; j.part_ssa = pt->ssa; j.part_mask = pt->mask; }
+  fill_jac_args(j, c.ncol, c.nlay, m->ng, c.top_at_1, c.n_gauss_angles, m->nband);
+  j.tau = tau; j.tsfc = c.tsfc; j.sfc_emis = c.sfc_emis; j.flux_up_jac = jac;
+  if (pt && fused_lw_kernels_apply(m, c.nlay)) { j.part_tau = pt->tau; j.part_ssa = pt->ssa; j.part_mask = pt->mask; }
   ProfScope prof("rte_lw_jac", stream);
   HIPCHK(ecckd::launch_rte_lw_jac(j, m->dbuf + m->off_planck, m->ntp, m->temperature_planck[0],
                                   m->temperature_planck[1] - m->temperature_planck[0], stream));
   return 0;
 }
 
-static int lw_jac_aliased(const double *jac, const double *flux_up, const double *flux_dn, const ClearFluxes *clr) {
-  if (jac && (jac == flux_up || jac == flux_dn || (clr && (jac == clr->up || jac == clr->dn))))
-    return fail("ecckd_lw_fluxes_jac: flux_up_jac must not be another output (it needs an array of its own)");
-  return 0;
-}
-
-// The work block of the single-precision fused longwave calls (ecckd_lw_fluxes_f32_scratch_bytes), in this order: tau,
-// lay_source, lev_source_inc, lev_source_dec (`cells` bytes each), sfc_source (`sfc`), the ring of the overflow solver
-// (`ring`: beyond 96 layers, else nothing); every part a multiple of 256 bytes.  The partial sums of the tail split follow
-// when the block has room for them.
+// The work block of the single-precision fused longwave calls (ecckd_lw_fluxes_f32_scratch_bytes,
+// ecckd_lw_fluxes_allsky_2stream_f32_scratch_bytes), in this order: tau, lay_source, lev_source_inc, lev_source_dec (`cells`
+// bytes each: what the single-precision gas optics writes), sfc_source (`sfc`), the solver's ring (`ring_bytes`: that of the
+// overflow solver beyond 96 layers, else nothing; the two-stream solver's in floats); every part a multiple of 256 bytes.
+// The partial sums of the tail split follow when the block has room for them.
 struct LwWorkF32 {
   size_t cells, sfc, ring;
-  LwWorkF32(const ecckd_model *m, int ncol, int nlay) {
+  LwWorkF32(const ecckd_model *m, int ncol, int nlay, size_t ring_bytes) {
     const Counts n(ncol, nlay, m->ng, m->nband);
     cells = align256(n.lay_g * sizeof(float));
     sfc = align256(n.col_g * sizeof(float));
-    ring = align256(ecckd::rte_lw_scratch_bytes(ncol, nlay, m->ng));
+    ring = align256(ring_bytes);
   }
   size_t bytes() const { return 4 * cells + sfc + ring; }
+  double *at(double *work, size_t off) const { return reinterpret_cast<double *>(reinterpret_cast<char *>(work) + off); }
+  double *tau(double *work) const { return work; }
+  PlanckSide sources(double *work, const LwColumns &c) const {
+    return PlanckSide{c.tlev, c.tsfc, at(work, cells), at(work, 2 * cells), at(work, 3 * cells), at(work, 4 * cells)};
+  }
+  double *ring_at(double *work) const { return at(work, 4 * cells + sfc); }
 };
+static LwWorkF32 lw_work_f32(const ecckd_model *m, int ncol, int nlay) {
+  return LwWorkF32(m, ncol, nlay, ecckd::rte_lw_scratch_bytes(ncol, nlay, m->ng));
+}
+static LwWorkF32 lw_2stream_work_f32(const ecckd_model *m, int ncol, int nlay) {
+  return LwWorkF32(m, ncol, nlay, ecckd::rte_lw_2str_scratch_bytes(ncol, nlay, m->ng) / 2);
+}
 
-// ecckd_lw_fluxes_f32 and its all-sky forms behind the refusal lists: the single-precision gas optics writes tau and the
+// ecckd_lw_fluxes_f32 and its all-sky forms behind the refusal list: the single-precision gas optics writes tau and the
 // Planck sources (two separate level arrays) into the work block, the single-precision register-resident solver follows on
-// them at every layer count -- launch_rte_lw (clear sky), launch_rte_lw_allsky_f32 (`pt`: the particles added where the
-// solver consumes tau), or one after the other on the same arrays (`clr`).  What ecckd_gas_optics_lw_f32 [+
+// them at every layer count -- launch_rte_lw (clear sky), launch_rte_lw_allsky_f32 (particles: added where the solver
+// consumes tau), or one after the other on the same arrays (clear-sky outputs).  What ecckd_gas_optics_lw_f32 [+
 // ecckd_increment(_masked)_f32] + ecckd_rte_lw(_inc_flux)_f32 compute, bit for bit.
-static int lw_fluxes_f32_run(const ecckd_model *m, int ncol, int nlay, const double *plev, const double *tlay, const double *tsfc,
-                             const double *tlev, const GasDesc &gd, int top_at_1, int n_gauss_angles, const double *sfc_emis,
-                             const double *inc_flux, double *flux_up, double *flux_dn, int memspace, void *stream,
-                             const LwParticles *pt, const ClearFluxes *clr) {
+static int lw_fluxes_f32_run(const ecckd_model *m, const LwColumns &c, const LwParticles &pt, const FluxOutputs &o, int memspace,
+                             void *stream) {
+  const int ncol = c.ncol, nlay = c.nlay;
   const Counts n(ncol, nlay, m->ng, m->nband);
-  ecckd::RteLwArgs a{};
-  if (fill_band_map(m->ng, m->nband, m->band2gpt.data(), a.gpt2band)) return 1;
-  a.ncol = ncol; a.nlay = nlay; a.ng = m->ng; a.top_at_1 = top_at_1 ? 1 : 0; a.nband = m->nband;
-  a.f32 = 1;
-  fill_lw_options(a, n_gauss_angles, true);
-  const LwWorkF32 w(m, ncol, nlay);
+  const LwWorkF32 w = lw_work_f32(m, ncol, nlay);
   long tail_first = -1;
   size_t tail = 0;   // tail tiles one g-pair per wave (rte_lw_tail_plan); optional, same bits
+  ecckd::RteLwArgs a{};
+  if (lw_solver_args(m, c, true, a)) return 1;
   if (!w.ring && g_opt.lw_tail_split.load()) tail = ecckd::rte_lw_tail_plan(a, simd_slots(m->device), &tail_first);
   Stage st(const_cast<ecckd_model *>(m), memspace, stream, true);
-  const double *d_plev = nullptr, *d_tlay = nullptr, *d_tsfc = nullptr, *d_tlev = nullptr;
-  double *d_up = nullptr, *d_dn = nullptr, *d_work = nullptr;
-  GasDesc d_gd{};
+  LwColumns d{};
   LwParticles d_pt{};
-  ClearFluxes d_clr{};
+  FluxOutputs d_o{};
+  double *d_work = nullptr;
   bool got_tail = false;
   if (st.open([&] {
-        d_plev = st.in(plev, n.lev); d_tlay = st.in(tlay, n.lay); d_tsfc = st.in(tsfc, n.col); d_tlev = st.in(tlev, n.lev);
-        a.sfc_emis = st.in(sfc_emis, n.col_b); a.inc_flux = st.in(inc_flux, n.col_g);
-        d_gd = st.gases(gd, ncol, nlay);
-        if (pt) d_pt = LwParticles{st.in(pt->tau, n.lay_b), st.in(pt->ssa, n.lay_b), st.in(pt->mask, n.lay)};
-        if (clr) d_clr = ClearFluxes{st.out(clr->up, n.lev), st.out(clr->dn, n.lev), nullptr};
-        d_up = st.out(flux_up, n.lev); d_dn = st.out(flux_dn, n.lev);
+        d = c.staged(st, n);
+        d_pt = pt.staged(st, n);
+        d_o.clear = o.clear.staged(st, n.lev);
+        d_o.all = o.all.staged(st, n.lev);
         d_work = st.work(w.bytes(), tail, &got_tail);
       }))
     return 1;
-  char *const base = reinterpret_cast<char *>(d_work);
-  auto at = [&](size_t off) { return reinterpret_cast<double *>(base + off); };
-  double *tau = at(0), *lay = at(w.cells), *inc = at(2 * w.cells), *dec = at(3 * w.cells), *sfc = at(4 * w.cells);
+  a.sfc_emis = d.sfc_emis; a.inc_flux = d.inc_flux;   // (the staged ones)
+  const PlanckSide src = w.sources(d_work, d);
   const hipStream_t s = st.stream;
-  if (gas_optics_lw_dev(m, true, ncol, nlay, d_plev, d_tlay, d_gd, tau, PlanckSide{d_tlev, d_tsfc, lay, inc, dec, sfc}, s)) return 1;
-  a.tau = tau; a.lay_source = lay; a.lev_source_inc = inc; a.lev_source_dec = dec; a.sfc_source = sfc;
-  if (w.ring) a.scratch = at(4 * w.cells + w.sfc);
-  if (tail && got_tail) { a.partials = at(w.bytes()); a.tail_first = tail_first; }
-  if (clr) {
-    a.flux_up = d_clr.up; a.flux_dn = d_clr.dn;
+  if (gas_optics_lw_dev(m, true, ncol, nlay, d.plev, d.tlay, d.gas, w.tau(d_work), src, s)) return 1;
+  a.tau = w.tau(d_work); a.lay_source = src.lay_source; a.lev_source_inc = src.lev_inc; a.lev_source_dec = src.lev_dec;
+  a.sfc_source = src.sfc_source;
+  if (w.ring) a.scratch = w.ring_at(d_work);
+  if (tail && got_tail) { a.partials = w.at(d_work, w.bytes()); a.tail_first = tail_first; }
+  if (d_o.clear.up) {
+    a.flux_up = d_o.clear.up; a.flux_dn = d_o.clear.dn;
     ProfScope prof("rte_lw", s);
     HIPCHK(ecckd::launch_rte_lw(a, s));
   }
-  a.flux_up = d_up; a.flux_dn = d_dn;
-  if (pt) {
+  a.flux_up = d_o.all.up; a.flux_dn = d_o.all.dn;
+  if (d_pt.tau) {
     a.part_tau = d_pt.tau; a.part_ssa = d_pt.ssa; a.part_1scl = d_pt.ssa ? 0 : 1; a.part_mask = d_pt.mask;
     ProfScope prof("rte_lw_allsky_f32", s);
     HIPCHK(ecckd::launch_rte_lw_allsky_f32(a, s));
@@ -2311,122 +2538,81 @@ static int lw_fluxes_f32_run(const ecckd_model *m, int ncol, int nlay, const dou
   return st.close();
 }
 
-static int lw_fluxes_impl(bool f32, const ecckd_model_t *m, int ncol, int nlay, const double *plev, const double *tlay, const double *tsfc,
-                          const double *tlev, int ngas, const char *gas_names, const double *const *vmr,
-                          const long long *vmr_col_stride, const long long *vmr_lay_stride, const double *vmr_scalar, int top_at_1,
-                          int n_gauss_angles, const double *sfc_emis, const double *inc_flux, double *flux_up, double *flux_dn,
-                          int memspace, void *stream, const LwParticles *pt = nullptr, const ClearFluxes *clr = nullptr,
-                          const LwJac *jx = nullptr) {
-  if (check_model(m) || check_gas_optics_dims(ncol, nlay)) return 1;
-  if (!m->has_planck) return fail("ecckd_lw_fluxes: model has no Planck table (shortwave model?)");
-  if (n_gauss_angles < 1 || n_gauss_angles > 4) return fail("rte_lw: have to ask for at least one quadrature point and no more than 4");
-  if (!plev || !tlay || !tsfc || !sfc_emis || !flux_up || !flux_dn || (ngas > 0 && !gas_names)) return fail("ecckd_lw_fluxes: null argument");
-  if (!tlev) return fail("tlev is required for ecckd");
-  if (g_arith.load() != 0) return fail("ecckd_lw_fluxes: needs the fast arithmetic mode (ecckd_set_arithmetic(0))");
-  double *jac = jx ? jx->jac : nullptr;
-  if (lw_jac_aliased(jac, flux_up, flux_dn, clr)) return 1;   // (the all-sky forms have answered this already)
-  if (jx && jx->stray)
-    return fail("ecckd_lw_fluxes_jac: nband_p, cloud_mask and the clear-sky outputs belong to particles: without tau_p they must be 0 / null");
-  HIPCHK(hipSetDevice(m->device));
-  if (ncol == 0) return 0;
-  const GasDesc gd{ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar};
-  if (memspace != ECCKD_DEVICE && memspace != ECCKD_HOST) return fail("ecckd: bad memspace");
+// The fused longwave calls on the no-scattering solver: gas optical depth into the work block, then the solver pass(es) the
+// call's particles and outputs ask for
+// (`w`: the words of an all-sky form, whose list goes first; null: ecckd_lw_fluxes, and ecckd_lw_fluxes_jac without tau_p)
+static int lw_fluxes_impl(const CallWords *w, bool f32, const ecckd_model_t *m, const LwColumns &c, int nband_p, const LwParticles &pt,
+                          const FluxOutputs &o, int memspace, void *stream) {
+  bool done;
+  if (w && (lw_head(*w, m, c, nband_p, pt) || clear_refusals(*w, o) || jac_refusals("ecckd_lw_fluxes_jac", o))) return 1;
+  if (lw_plain_tail(m, c, nband_p, pt, o, memspace, &done)) return 1;
+  if (done) return 0;
   if (f32) {   // (the _f32 entry points: no Jacobian form)
-    if (jx) return fail("ecckd: internal: the single-precision fused longwave calls have no Jacobian form");
-    return lw_fluxes_f32_run(m, ncol, nlay, plev, tlay, tsfc, tlev, gd, top_at_1, n_gauss_angles, sfc_emis, inc_flux, flux_up, flux_dn,
-                             memspace, stream, pt, clr);
+    if (o.jac) return fail("ecckd: internal: the single-precision fused longwave calls have no Jacobian form");
+    return lw_fluxes_f32_run(m, c, pt, o, memspace, stream);
   }
+  const int ncol = c.ncol, nlay = c.nlay;
   const Counts n(ncol, nlay, m->ng, m->nband);
+  const bool part = pt.tau != nullptr, both = o.clear.up != nullptr;
   // the Jacobian inside the 60-layer flux kernel ("lw_jac_inline" = 1), or from the stand-alone kernel behind the flux pass
-  const bool jac_in = jac && fused_lw_kernels_apply(m, nlay) && g_opt.lw_jac_inline.load() == 1;
+  const bool jac_in = o.jac && fused_lw_kernels_apply(m, nlay) && g_opt.lw_jac_inline.load() == 1;
   // tau lives in the work block between the kernels; behind it what the general route needs (fused_scratch_doubles)
   const size_t extra = fused_scratch_doubles(m, ncol, nlay);
   Stage st(const_cast<ecckd_model *>(m), memspace, stream, false);
-  const double *d_plev = nullptr, *d_tlay = nullptr, *d_tsfc = nullptr, *d_tlev = nullptr, *d_emis = nullptr, *d_incf = nullptr;
-  double *d_up = nullptr, *d_dn = nullptr, *d_jac = nullptr, *d_tau = nullptr;
-  GasDesc d_gd{};
+  LwColumns d{};
   LwParticles d_pt{};
-  ClearFluxes d_clr{};
+  FluxOutputs d_o{};
+  double *d_tau = nullptr;
   if (st.open([&] {
-        d_plev = st.in(plev, n.lev); d_tlay = st.in(tlay, n.lay); d_tsfc = st.in(tsfc, n.col); d_tlev = st.in(tlev, n.lev);
-        d_emis = st.in(sfc_emis, n.col_b); d_incf = st.in(inc_flux, n.col_g);
-        d_gd = st.gases(gd, ncol, nlay);
-        if (pt) d_pt = LwParticles{st.in(pt->tau, n.lay_b), st.in(pt->ssa, n.lay_b), st.in(pt->mask, n.lay),
-                                   static_cast<const float *>(st.in_bytes(pt->scaling, n.lay_g * sizeof(float)))};
-        if (clr) d_clr = ClearFluxes{st.out(clr->up, n.lev), st.out(clr->dn, n.lev), nullptr};
-        d_up = st.out(flux_up, n.lev); d_dn = st.out(flux_dn, n.lev); d_jac = st.out(jac, n.lev);
+        d = c.staged(st, n);
+        d_pt = pt.staged(st, n);
+        d_o.clear = o.clear.staged(st, n.lev);
+        d_o.all = o.all.staged(st, n.lev);
+        d_o.jac = st.out(o.jac, n.lev);
         d_tau = st.work((n.lay_g + 32 + extra) * sizeof(double));
       }))
     return 1;
   double *d_extra = extra ? d_tau + r32(n.lay_g) : nullptr;
   const hipStream_t s = st.stream;
-  if (gas_optical_depth_dev(m, false, nullptr, ncol, nlay, d_plev, d_tlay, d_gd, d_tau, false, nullptr, nullptr, nullptr, nullptr, s)) return 1;
-  if (pt && pt->scaling) {   // ecckd_lw_flux_scaled: the scaled increment in place, then the solver without particles
-    if (clr || jx) return fail("ecckd: internal: the scaled longwave call has no both-skies or Jacobian form");
+  if (gas_optical_depth_dev(m, false, nullptr, ncol, nlay, d.plev, d.tlay, d.gas, d_tau, false, nullptr, nullptr, nullptr, nullptr, s)) return 1;
+  if (pt.scaling) {   // ecckd_lw_flux_scaled: the scaled increment in place, then the solver without particles
+    if (both || o.jac) return fail("ecckd: internal: the scaled longwave call has no both-skies or Jacobian form");
     if (lw_increment_dev(m, ncol, nlay, d_tau, d_pt, s)) return 1;
-    if (rte_lw_fused_dev(m, ncol, nlay, top_at_1, n_gauss_angles, d_tau, d_tlay, d_tlev, d_tsfc, d_emis, d_incf, d_up, d_dn, d_extra, s))
-      return 1;
-  } else if (clr) {
-    if (lw_both_skies_dev(m, ncol, nlay, top_at_1, n_gauss_angles, d_tau, d_tlay, d_tlev, d_tsfc, d_emis, d_incf, d_up, d_dn, d_extra,
-                          s, d_pt, d_clr, jac_in ? d_jac : nullptr))
-      return 1;
+    if (rte_lw_fused_dev(m, d, d_tau, d_o.all, d_extra, s)) return 1;
+  } else if (both) {
+    if (lw_both_skies_dev(m, d, d_tau, d_pt, d_o, d_extra, s, jac_in ? d_o.jac : nullptr)) return 1;
   } else {
-    if (pt && !fused_lw_kernels_apply(m, nlay) && lw_increment_dev(m, ncol, nlay, d_tau, d_pt, s)) return 1;
-    if (rte_lw_fused_dev(m, ncol, nlay, top_at_1, n_gauss_angles, d_tau, d_tlay, d_tlev, d_tsfc, d_emis, d_incf, d_up, d_dn, d_extra, s,
-                         pt ? &d_pt : nullptr, nullptr, false, jac_in ? d_jac : nullptr))
-      return 1;
+    if (part && !fused_lw_kernels_apply(m, nlay) && lw_increment_dev(m, ncol, nlay, d_tau, d_pt, s)) return 1;
+    if (rte_lw_fused_dev(m, d, d_tau, d_o.all, d_extra, s, part ? &d_pt : nullptr, nullptr, false, jac_in ? d_o.jac : nullptr)) return 1;
   }
   // (both skies, general route: behind the second solver pass, on the tau that pass saw)
-  if (jac && !jac_in && lw_jac_dev(m, ncol, nlay, top_at_1, n_gauss_angles, d_tau, d_tsfc, d_emis, pt ? &d_pt : nullptr, d_jac, s))
-    return 1;
+  if (o.jac && !jac_in && lw_jac_dev(m, d, d_tau, part ? &d_pt : nullptr, d_o.jac, s)) return 1;
   return st.close();
 }
+
+// the words of the all-sky forms on the no-scattering solver (clear_required: the clear-sky outputs are part of the call)
+static CallWords lw_allsky_words(bool clear_required = false) {
+  CallWords w;
+  w.who = "ecckd_lw_fluxes_allsky";
+  w.who_mask = "ecckd_lw_fluxes_allsky_mcica";
+  w.planes_tail = ": null argument (tau_p is required; ssa_p may be null: one-stream particles)";
+  w.need_ssa_g = false;
+  w.who_clear = "ecckd_lw_fluxes_clear_allsky";
+  w.clear_tail = ": null argument (flux_up_clear and flux_dn_clear are both required)";
+  w.clear_required = clear_required;
+  return w;
+}
+static const CallWords kLwAllsky = lw_allsky_words(), kLwClearAllsky = lw_allsky_words(true);
 
 int ecckd_lw_fluxes(const ecckd_model_t *m, int ncol, int nlay, const double *plev, const double *tlay, const double *tsfc,
                     const double *tlev, int ngas, const char *gas_names, const double *const *vmr,
                     const long long *vmr_col_stride, const long long *vmr_lay_stride, const double *vmr_scalar, int top_at_1,
                     int n_gauss_angles, const double *sfc_emis, const double *inc_flux, double *flux_up, double *flux_dn,
                     int memspace, void *stream) {
-  return lw_fluxes_impl(false, m, ncol, nlay, plev, tlay, tsfc, tlev, ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar,
-                        top_at_1, n_gauss_angles, sfc_emis, inc_flux, flux_up, flux_dn, memspace, stream);
-}
-
-// ... its part that every form shares (ecckd_lw_flux_scaled too)
-static int lw_fluxes_allsky_refusals(const ecckd_model_t *m, int nband_p, const double *tau_p, const double *tlev) {
-  if (!m) return fail("ecckd: null model");
-  if (nband_p != m->nband)
-    return fail("ecckd_lw_fluxes_allsky: nband_p = " + std::to_string(nband_p) + " but the model has " + std::to_string(m->nband) +
-                " bands (particulate properties live on the model's bands)");
-  if (!tau_p) return fail("ecckd_lw_fluxes_allsky: null argument (tau_p is required; ssa_p may be null: one-stream particles)");
-  if (g_arith.load() != 0) return fail("ecckd_lw_fluxes_allsky: needs the fast arithmetic mode (ecckd_set_arithmetic(0))");
-  if (!m->has_planck) return fail("ecckd_lw_fluxes_allsky: model has no Planck table (shortwave model?)");
-  if (!tlev) return fail("tlev is required for ecckd");
-  return 0;
-}
-
-// The one refusal list of the fused all-sky longwave calls.  cloud_mask (ecckd_lw_fluxes_allsky_mcica), or null: with a
-// mask, a model of more than 64 g-points is refused first.  Refusals that need no device come first: a host-only model
-// answers them too.
-static int lw_fluxes_allsky_impl(bool f32, const ecckd_model_t *m, int ncol, int nlay, const double *plev, const double *tlay,
-                                 const double *tsfc, const double *tlev, int ngas, const char *gas_names,
-                                 const double *const *vmr, const long long *vmr_col_stride, const long long *vmr_lay_stride,
-                                 const double *vmr_scalar, int top_at_1, int n_gauss_angles, const double *sfc_emis,
-                                 const double *inc_flux, int nband_p, const double *tau_p, const double *ssa_p,
-                                 const unsigned long long *cloud_mask, double *flux_up, double *flux_dn, int memspace,
-                                 void *stream, const ClearFluxes *clr = nullptr, const LwJac *jx = nullptr) {
-  if (!m) return fail("ecckd: null model");
-  if (cloud_mask && m->ng > 64) return fail("ecckd_lw_fluxes_allsky_mcica" + std::string(kMaskTooWide) + std::to_string(m->ng));
-  if (lw_fluxes_allsky_refusals(m, nband_p, tau_p, tlev)) return 1;
-  if (clr) {
-    if (!clr->up || !clr->dn)
-      return fail("ecckd_lw_fluxes_clear_allsky: null argument (flux_up_clear and flux_dn_clear are both required)");
-    if (clr->up == flux_up || clr->up == flux_dn || clr->dn == flux_up || clr->dn == flux_dn)
-      return fail("ecckd_lw_fluxes_clear_allsky: a clear-sky output must not be an all-sky output (the two sets of fluxes need arrays of their own)");
-  }
-  if (lw_jac_aliased(jx ? jx->jac : nullptr, flux_up, flux_dn, clr)) return 1;   // (before any device is asked for, as the list above)
-  const LwParticles pt{tau_p, ssa_p, cloud_mask};
-  return lw_fluxes_impl(f32, m, ncol, nlay, plev, tlay, tsfc, tlev, ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar,
-                        top_at_1, n_gauss_angles, sfc_emis, inc_flux, flux_up, flux_dn, memspace, stream, &pt, clr, jx);
+  const LwColumns c{ncol, nlay, plev, tlay, tsfc, tlev, GasDesc{ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar},
+                    top_at_1, n_gauss_angles, sfc_emis, inc_flux};
+  const FluxOutputs o{Fluxes{flux_up, flux_dn}};
+  return lw_fluxes_impl(nullptr, false, m, c, 0, LwParticles{}, o, memspace, stream);
 }
 
 int ecckd_lw_fluxes_clear_allsky(const ecckd_model_t *m, int ncol, int nlay, const double *plev, const double *tlay,
@@ -2436,10 +2622,10 @@ int ecckd_lw_fluxes_clear_allsky(const ecckd_model_t *m, int ncol, int nlay, con
                                  const double *inc_flux, int nband_p, const double *tau_p, const double *ssa_p,
                                  const unsigned long long *cloud_mask, double *flux_up, double *flux_dn, double *flux_up_clear,
                                  double *flux_dn_clear, int memspace, void *stream) {
-  const ClearFluxes clr{flux_up_clear, flux_dn_clear, nullptr};
-  return lw_fluxes_allsky_impl(false, m, ncol, nlay, plev, tlay, tsfc, tlev, ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride,
-                               vmr_scalar, top_at_1, n_gauss_angles, sfc_emis, inc_flux, nband_p, tau_p, ssa_p, cloud_mask, flux_up,
-                               flux_dn, memspace, stream, &clr);
+  const LwColumns c{ncol, nlay, plev, tlay, tsfc, tlev, GasDesc{ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar},
+                    top_at_1, n_gauss_angles, sfc_emis, inc_flux};
+  return lw_fluxes_impl(&kLwClearAllsky, false, m, c, nband_p, LwParticles{tau_p, ssa_p, nullptr, cloud_mask},
+                        FluxOutputs{Fluxes{flux_up, flux_dn}, Fluxes{flux_up_clear, flux_dn_clear}}, memspace, stream);
 }
 
 int ecckd_lw_fluxes_allsky(const ecckd_model_t *m, int ncol, int nlay, const double *plev, const double *tlay, const double *tsfc,
@@ -2448,9 +2634,12 @@ int ecckd_lw_fluxes_allsky(const ecckd_model_t *m, int ncol, int nlay, const dou
                            int top_at_1, int n_gauss_angles, const double *sfc_emis, const double *inc_flux, int nband_p,
                            const double *tau_p, const double *ssa_p, double *flux_up, double *flux_dn, int memspace,
                            void *stream) {
-  return lw_fluxes_allsky_impl(false, m, ncol, nlay, plev, tlay, tsfc, tlev, ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride,
-                               vmr_scalar, top_at_1, n_gauss_angles, sfc_emis, inc_flux, nband_p, tau_p, ssa_p, nullptr, flux_up,
-                               flux_dn, memspace, stream);
+  const LwColumns c{ncol, nlay, plev, tlay, tsfc, tlev, GasDesc{ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar},
+                    top_at_1, n_gauss_angles, sfc_emis, inc_flux};
+  LwParticles pt;
+  pt.tau = tau_p; pt.ssa = ssa_p;
+  const FluxOutputs o{Fluxes{flux_up, flux_dn}};
+  return lw_fluxes_impl(&kLwAllsky, false, m, c, nband_p, pt, o, memspace, stream);
 }
 
 int ecckd_lw_fluxes_allsky_mcica(const ecckd_model_t *m, int ncol, int nlay, const double *plev, const double *tlay,
@@ -2460,9 +2649,25 @@ int ecckd_lw_fluxes_allsky_mcica(const ecckd_model_t *m, int ncol, int nlay, con
                                  const double *inc_flux, int nband_p, const double *tau_p, const double *ssa_p,
                                  const unsigned long long *cloud_mask, double *flux_up, double *flux_dn, int memspace,
                                  void *stream) {
-  return lw_fluxes_allsky_impl(false, m, ncol, nlay, plev, tlay, tsfc, tlev, ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride,
-                               vmr_scalar, top_at_1, n_gauss_angles, sfc_emis, inc_flux, nband_p, tau_p, ssa_p, cloud_mask, flux_up,
-                               flux_dn, memspace, stream);
+  const LwColumns c{ncol, nlay, plev, tlay, tsfc, tlev, GasDesc{ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar},
+                    top_at_1, n_gauss_angles, sfc_emis, inc_flux};
+  return lw_fluxes_impl(&kLwAllsky, false, m, c, nband_p, LwParticles{tau_p, ssa_p, nullptr, cloud_mask},
+                        FluxOutputs{Fluxes{flux_up, flux_dn}}, memspace, stream);
+}
+
+// The superset of the four calls above, with flux_up_jac of the sky that flux_up holds (include/ecckd_hip.h)
+int ecckd_lw_fluxes_jac(const ecckd_model_t *m, int ncol, int nlay, const double *plev, const double *tlay, const double *tsfc,
+                        const double *tlev, int ngas, const char *gas_names, const double *const *vmr,
+                        const long long *vmr_col_stride, const long long *vmr_lay_stride, const double *vmr_scalar, int top_at_1,
+                        int n_gauss_angles, const double *sfc_emis, const double *inc_flux, int nband_p, const double *tau_p,
+                        const double *ssa_p, const unsigned long long *cloud_mask, double *flux_up, double *flux_dn,
+                        double *flux_up_clear, double *flux_dn_clear, double *flux_up_jac, int memspace, void *stream) {
+  const LwColumns c{ncol, nlay, plev, tlay, tsfc, tlev, GasDesc{ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar},
+                    top_at_1, n_gauss_angles, sfc_emis, inc_flux};
+  const LwParticles pt{tau_p, ssa_p, nullptr, cloud_mask};
+  const FluxOutputs o{Fluxes{flux_up, flux_dn}, Fluxes{flux_up_clear, flux_dn_clear}, Fluxes{}, flux_up_jac};
+  // without tau_p: the clear sky of ecckd_lw_fluxes, whose list refuses whatever else of the particles' is named
+  return lw_fluxes_impl(tau_p ? &kLwAllsky : nullptr, false, m, c, nband_p, pt, o, memspace, stream);
 }
 
 // ---- fused all-sky longwave with scattering clouds: gas optics -> Planck sources -> two-stream solver (PART / MASK) ----
@@ -2474,115 +2679,86 @@ static size_t allsky_2stream_doubles(const ecckd_model *m, int ncol, int nlay) {
   return r32(n3) + 3 * n3 + r32((size_t)ncol * m->ng);
 }
 
-// behind the gas optics, on device pointers: `work` holds tau at its start
-static int lw_allsky_2stream_dev(const ecckd_model *m, int ncol, int nlay, const double *tlay, const double *tlev, const double *tsfc,
-                                 int top_at_1, const double *sfc_emis, const double *inc_flux, const double *tau_p,
-                                 const double *ssa_p, const double *g_p, const unsigned long long *mask, double *flux_up,
-                                 double *flux_dn, double *work, hipStream_t stream) {
-  const size_t n3 = (size_t)ncol * nlay * m->ng;
-  double *tau = work, *lay = tau + r32(n3), *inc = lay + n3, *dec = inc + n3, *sfc = dec + n3, *ring = sfc + r32((size_t)ncol * m->ng);
-  if (planck_sources_dev(m, ncol, nlay, tlay, PlanckSide{tlev, tsfc, lay, inc, dec, sfc}, stream)) return 1;
-  ecckd::RteLw2strArgs a{};
+static const char kScatteringPlanesTail[] =
+    ": null argument (tau_p, ssa_p and g_p are required; one-stream particles: ecckd_lw_fluxes_allsky)";
+
+// The two-stream solver's arguments on device pointers: the optical depth, the sources of `src` (the layer source is not
+// read), the particles and where the fluxes go
+static int lw_2stream_args(const ecckd_model *m, const LwColumns &c, const LwParticles &pt, const Fluxes &to, const double *tau,
+                           const PlanckSide &src, double *ring, ecckd::RteLw2strArgs &a) {
   if (fill_band_map(m->ng, m->nband, m->band2gpt.data(), a.gpt2band)) return 1;
-  a.ncol = ncol; a.nlay = nlay; a.ng = m->ng; a.top_at_1 = top_at_1 ? 1 : 0; a.nband = m->nband;
+  a.ncol = c.ncol; a.nlay = c.nlay; a.ng = m->ng; a.top_at_1 = c.top_at_1 ? 1 : 0; a.nband = m->nband;
   a.exact_division = 0;
-  a.tau = tau; a.lev_source_inc = inc; a.lev_source_dec = dec; a.sfc_source = sfc; a.sfc_emis = sfc_emis; a.inc_flux = inc_flux;
-  a.part_tau = tau_p; a.part_ssa = ssa_p; a.part_g = g_p; a.part_mask = mask;
-  a.flux_up = flux_up; a.flux_dn = flux_dn; a.scratch = ring;
+  a.tau = tau; a.lev_source_inc = src.lev_inc; a.lev_source_dec = src.lev_dec; a.sfc_source = src.sfc_source;
+  a.sfc_emis = c.sfc_emis; a.inc_flux = c.inc_flux;
+  a.part_tau = pt.tau; a.part_ssa = pt.ssa; a.part_g = pt.g; a.part_mask = pt.mask;
+  a.flux_up = to.up; a.flux_dn = to.dn; a.scratch = ring;
+  return 0;
+}
+
+// behind the gas optics, on device pointers: `work` holds tau at its start
+static int lw_allsky_2stream_dev(const ecckd_model *m, const LwColumns &c, const LwParticles &pt, const Fluxes &to, double *work,
+                                 hipStream_t stream) {
+  const size_t n3 = (size_t)c.ncol * c.nlay * m->ng;
+  double *tau = work, *lay = tau + r32(n3), *inc = lay + n3, *dec = inc + n3, *sfc = dec + n3, *ring = sfc + r32((size_t)c.ncol * m->ng);
+  const PlanckSide src{c.tlev, c.tsfc, lay, inc, dec, sfc};
+  if (planck_sources_dev(m, c.ncol, c.nlay, c.tlay, src, stream)) return 1;
+  ecckd::RteLw2strArgs a{};
+  if (lw_2stream_args(m, c, pt, to, tau, src, ring, a)) return 1;
   ProfScope prof("rte_lw_2stream_allsky", stream);
   HIPCHK(ecckd::launch_rte_lw_2str(a, stream));
   return 0;
 }
 
-// The work block of ecckd_lw_fluxes_allsky_2stream_f32 (..._scratch_bytes), in this order: tau, lay_source, lev_source_inc,
-// lev_source_dec (`cells` bytes each: what the single-precision gas optics writes, as in LwWorkF32), sfc_source (`sfc`), the
-// solver's ring in floats (`ring`); every part a multiple of 256 bytes
-struct Lw2strWorkF32 {
-  size_t cells, sfc, ring;
-  Lw2strWorkF32(const ecckd_model *m, int ncol, int nlay) {
-    const Counts n(ncol, nlay, m->ng, m->nband);
-    cells = align256(n.lay_g * sizeof(float));
-    sfc = align256(n.col_g * sizeof(float));
-    ring = align256(ecckd::rte_lw_2str_scratch_bytes(ncol, nlay, m->ng) / 2);
-  }
-  size_t bytes() const { return 4 * cells + sfc + ring; }
-};
-
 size_t ecckd_lw_fluxes_allsky_2stream_f32_scratch_bytes(const ecckd_model_t *m, int ncol, int nlay) {
   if (!m || ncol <= 0 || nlay <= 0) return 0;
-  return Lw2strWorkF32(m, ncol, nlay).bytes();
+  return lw_2stream_work_f32(m, ncol, nlay).bytes();
 }
 
 // (f32: float arrays behind the double pointers -- the single-precision gas optics and Planck sources into the work block,
 // then the float solver; the same list of refusals in the same order under the call's own name)
-static int lw_fluxes_allsky_2stream_impl(bool f32, const ecckd_model_t *m, int ncol, int nlay, const double *plev, const double *tlay,
-                                         const double *tsfc, const double *tlev, int ngas, const char *gas_names,
-                                         const double *const *vmr, const long long *vmr_col_stride, const long long *vmr_lay_stride,
-                                         const double *vmr_scalar, int top_at_1, const double *sfc_emis, const double *inc_flux,
-                                         int nband_p, const double *tau_p, const double *ssa_p, const double *g_p,
-                                         const unsigned long long *cloud_mask, double *flux_up, double *flux_dn, int memspace,
-                                         void *stream) {
-  const std::string who = f32 ? "ecckd_lw_fluxes_allsky_2stream_f32" : "ecckd_lw_fluxes_allsky_2stream";
-  if (!m) return fail("ecckd: null model");
-  if (cloud_mask && m->ng > 64) return fail(who + std::string(kMaskTooWide) + std::to_string(m->ng));
-  if (nband_p != m->nband)
-    return fail(who + ": nband_p = " + std::to_string(nband_p) + " but the model has " +
-                std::to_string(m->nband) + " bands (particulate properties live on the model's bands)");
-  if (!tau_p || !ssa_p || !g_p)
-    return fail(who + ": null argument (tau_p, ssa_p and g_p are required; one-stream particles: ecckd_lw_fluxes_allsky)");
-  if (g_arith.load() != 0) return fail(who + ": needs the fast arithmetic mode (ecckd_set_arithmetic(0))");
-  if (!m->has_planck) return fail(who + ": model has no Planck table (shortwave model?)");
-  if (!tlev) return fail("tlev is required for ecckd");
+static int lw_fluxes_allsky_2stream_impl(bool f32, const ecckd_model_t *m, const LwColumns &c, int nband_p, const LwParticles &pt,
+                                         const Fluxes &to, int memspace, void *stream) {
+  CallWords words;
+  words.who = words.who_mask = f32 ? "ecckd_lw_fluxes_allsky_2stream_f32" : "ecckd_lw_fluxes_allsky_2stream";
+  words.planes_tail = kScatteringPlanesTail;
+  bool done;
+  if (lw_head(words, m, c, nband_p, pt)) return 1;
   // (the single-precision call names ECCKD_MIXED; the fp64 call has always answered it as a bad memspace, below)
-  if (f32 && memspace == ECCKD_MIXED) return fail(who + ": ECCKD_MIXED is not implemented (ECCKD_DEVICE or ECCKD_HOST)");
-  if (check_model(m) || check_gas_optics_dims(ncol, nlay)) return 1;
-  if (!plev || !tlay || !tsfc || !sfc_emis || !flux_up || !flux_dn || (ngas > 0 && !gas_names))
-    return fail(who + ": null argument");
-  if (lw_2stream_layers_fit(nlay)) return 1;
-  if (memspace != ECCKD_DEVICE && memspace != ECCKD_HOST) return fail("ecckd: bad memspace");
-  HIPCHK(hipSetDevice(m->device));
-  if (ncol == 0) return 0;
-  const GasDesc gd{ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar};
+  if (f32 && memspace == ECCKD_MIXED) return refuse(words.who, ": ECCKD_MIXED is not implemented (ECCKD_DEVICE or ECCKD_HOST)");
+  if (check_model(m) || check_gas_optics_dims(c.ncol, c.nlay)) return 1;
+  if (c.null_array() || !to.up || !to.dn) return refuse(words.who, ": null argument");
+  if (lw_2stream_layers_fit(c.nlay) || on_device(m, c.ncol, memspace, &done)) return 1;
+  if (done) return 0;
+  const int ncol = c.ncol, nlay = c.nlay;
   const Counts n(ncol, nlay, m->ng, m->nband);
-  const Lw2strWorkF32 w(m, ncol, nlay);
+  const LwWorkF32 w = lw_2stream_work_f32(m, ncol, nlay);
   const size_t work_bytes = f32 ? w.bytes()
                                 : allsky_2stream_doubles(m, ncol, nlay) * sizeof(double) + ecckd::rte_lw_2str_scratch_bytes(ncol, nlay, m->ng);
   Stage st(const_cast<ecckd_model *>(m), memspace, stream, f32);
-  const double *d_plev = nullptr, *d_tlay = nullptr, *d_tsfc = nullptr, *d_tlev = nullptr, *d_emis = nullptr, *d_incf = nullptr;
-  const double *q_tau = nullptr, *q_ssa = nullptr, *q_g = nullptr;
-  const unsigned long long *q_mask = nullptr;
-  double *d_up = nullptr, *d_dn = nullptr, *work = nullptr;
-  GasDesc d_gd{};
+  LwColumns d{};
+  LwParticles d_pt{};
+  Fluxes d_to{};
+  double *work = nullptr;
   if (st.open([&] {
-        d_plev = st.in(plev, n.lev); d_tlay = st.in(tlay, n.lay); d_tsfc = st.in(tsfc, n.col); d_tlev = st.in(tlev, n.lev);
-        d_emis = st.in(sfc_emis, n.col_b); d_incf = st.in(inc_flux, n.col_g);
-        d_gd = st.gases(gd, ncol, nlay);
-        q_tau = st.in(tau_p, n.lay_b); q_ssa = st.in(ssa_p, n.lay_b); q_g = st.in(g_p, n.lay_b); q_mask = st.in(cloud_mask, n.lay);
-        d_up = st.out(flux_up, n.lev); d_dn = st.out(flux_dn, n.lev);
+        d = c.staged(st, n);
+        d_pt = pt.staged(st, n);
+        d_to = to.staged(st, n.lev);
         work = st.work(work_bytes);
       }))
     return 1;
   if (f32) {
-    char *const base = reinterpret_cast<char *>(work);
-    auto at = [&](size_t off) { return reinterpret_cast<double *>(base + off); };
-    double *tau = at(0), *lay = at(w.cells), *inc = at(2 * w.cells), *dec = at(3 * w.cells), *sfc = at(4 * w.cells);
-    if (gas_optics_lw_dev(m, true, ncol, nlay, d_plev, d_tlay, d_gd, tau, PlanckSide{d_tlev, d_tsfc, lay, inc, dec, sfc}, st.stream)) return 1;
+    const PlanckSide src = w.sources(work, d);
+    if (gas_optics_lw_dev(m, true, ncol, nlay, d.plev, d.tlay, d.gas, w.tau(work), src, st.stream)) return 1;
     ecckd::RteLw2strArgs a{};
-    if (fill_band_map(m->ng, m->nband, m->band2gpt.data(), a.gpt2band)) return 1;
-    a.ncol = ncol; a.nlay = nlay; a.ng = m->ng; a.top_at_1 = top_at_1 ? 1 : 0; a.nband = m->nband;
-    a.exact_division = 0;
-    a.tau = tau; a.lev_source_inc = inc; a.lev_source_dec = dec; a.sfc_source = sfc; a.sfc_emis = d_emis; a.inc_flux = d_incf;
-    a.part_tau = q_tau; a.part_ssa = q_ssa; a.part_g = q_g; a.part_mask = q_mask;
-    a.flux_up = d_up; a.flux_dn = d_dn; a.scratch = at(4 * w.cells + w.sfc);
+    if (lw_2stream_args(m, d, d_pt, d_to, w.tau(work), src, w.ring_at(work), a)) return 1;
     ProfScope prof("rte_lw_2stream_allsky_f32", st.stream);
     HIPCHK(ecckd::launch_rte_lw_2str_f32(a, st.stream));
     return st.close();
   }
-  if (gas_optical_depth_dev(m, false, nullptr, ncol, nlay, d_plev, d_tlay, d_gd, work, false, nullptr, nullptr, nullptr, nullptr, st.stream))
+  if (gas_optical_depth_dev(m, false, nullptr, ncol, nlay, d.plev, d.tlay, d.gas, work, false, nullptr, nullptr, nullptr, nullptr, st.stream))
     return 1;
-  if (lw_allsky_2stream_dev(m, ncol, nlay, d_tlay, d_tlev, d_tsfc, top_at_1, d_emis, d_incf, q_tau, q_ssa, q_g, q_mask, d_up, d_dn, work,
-                            st.stream))
-    return 1;
+  if (lw_allsky_2stream_dev(m, d, d_pt, d_to, work, st.stream)) return 1;
   return st.close();
 }
 
@@ -2593,9 +2769,10 @@ int ecckd_lw_fluxes_allsky_2stream(const ecckd_model_t *m, int ncol, int nlay, c
                                    int nband_p, const double *tau_p, const double *ssa_p, const double *g_p,
                                    const unsigned long long *cloud_mask, double *flux_up, double *flux_dn, int memspace,
                                    void *stream) {
-  return lw_fluxes_allsky_2stream_impl(false, m, ncol, nlay, plev, tlay, tsfc, tlev, ngas, gas_names, vmr, vmr_col_stride,
-                                       vmr_lay_stride, vmr_scalar, top_at_1, sfc_emis, inc_flux, nband_p, tau_p, ssa_p, g_p,
-                                       cloud_mask, flux_up, flux_dn, memspace, stream);
+  const LwColumns c{ncol, nlay, plev, tlay, tsfc, tlev, GasDesc{ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar},
+                    top_at_1, 1, sfc_emis, inc_flux};
+  const LwParticles pt{tau_p, ssa_p, g_p, cloud_mask};
+  return lw_fluxes_allsky_2stream_impl(false, m, c, nband_p, pt, Fluxes{flux_up, flux_dn}, memspace, stream);
 }
 
 int ecckd_lw_fluxes_allsky_2stream_f32(const ecckd_model_t *m, int ncol, int nlay, const float *plev, const float *tlay,
@@ -2605,10 +2782,12 @@ int ecckd_lw_fluxes_allsky_2stream_f32(const ecckd_model_t *m, int ncol, int nla
                                        int nband_p, const float *tau_p, const float *ssa_p, const float *g_p,
                                        const unsigned long long *cloud_mask, float *flux_up, float *flux_dn, int memspace,
                                        void *stream) {
-  return lw_fluxes_allsky_2stream_impl(true, m, ncol, nlay, dp(plev), dp(tlay), dp(tsfc), dp(tlev), ngas, gas_names,
-                                       reinterpret_cast<const double *const *>(vmr), vmr_col_stride, vmr_lay_stride, vmr_scalar,
-                                       top_at_1, dp(sfc_emis), dp(inc_flux), nband_p, dp(tau_p), dp(ssa_p), dp(g_p), cloud_mask,
-                                       dp(flux_up), dp(flux_dn), memspace, stream);
+  const LwColumns c{ncol, nlay, dp(plev), dp(tlay), dp(tsfc), dp(tlev),
+                    GasDesc{ngas, gas_names, dp(vmr), vmr_col_stride, vmr_lay_stride, vmr_scalar}, top_at_1, 1, dp(sfc_emis),
+                    dp(inc_flux)};
+  LwParticles pt;
+  pt.tau = dp(tau_p); pt.ssa = dp(ssa_p); pt.g = dp(g_p); pt.mask = cloud_mask;
+  return lw_fluxes_allsky_2stream_impl(true, m, c, nband_p, pt, Fluxes{dp(flux_up), dp(flux_dn)}, memspace, stream);
 }
 
 // ---- rescaled no-scattering longwave solver (RTE-RRTMGP's lw_solver_1rescl_GaussQuad): cheap cloud scattering ----
@@ -2800,9 +2979,6 @@ size_t ecckd_lw_fluxes_allsky_rescaled_scratch_bytes(const ecckd_model_t *m, int
   return sizeof(double) * allsky_rescaled_doubles(m, ncol, nlay);
 }
 
-// ecckd_lw_fluxes_rescaled_jac: the optional outputs behind flux_dn, in the memory space of the call (each may be null)
-struct RescExtras { double *up_clear, *dn_clear, *jac; };
-
 // The work block with clear-sky outputs: behind the block of ecckd_lw_fluxes_allsky_rescaled, what the clear pass needs on
 // its general route -- at 60 layers its sources and ring (nothing where the clear-sky layer-split kernel serves the model),
 // otherwise the ring alone (the sources are the rescaled route's)
@@ -2818,86 +2994,64 @@ size_t ecckd_lw_fluxes_rescaled_jac_scratch_bytes(const ecckd_model_t *m, int nc
   return sizeof(double) * allsky_rescaled_jac_doubles(m, ncol, nlay, with_clear != 0);
 }
 
-static int lw_fluxes_allsky_rescaled_impl(const ecckd_model_t *m, int ncol, int nlay, const double *plev, const double *tlay,
-                                          const double *tsfc, const double *tlev, int ngas, const char *gas_names,
-                                          const double *const *vmr, const long long *vmr_col_stride,
-                                          const long long *vmr_lay_stride, const double *vmr_scalar, int top_at_1,
-                                          int n_gauss_angles, const double *sfc_emis, const double *inc_flux, int nband_p,
-                                          const double *tau_p, const double *ssa_p, const double *g_p,
-                                          const unsigned long long *cloud_mask, double *flux_up, double *flux_dn, int memspace,
-                                          void *stream, const RescExtras &x) {
-  if (!m) return fail("ecckd: null model");
-  if (cloud_mask && m->ng > 64) return fail("ecckd_lw_fluxes_allsky_rescaled" + std::string(kMaskTooWide) + std::to_string(m->ng));
-  if (nband_p != m->nband)
-    return fail("ecckd_lw_fluxes_allsky_rescaled: nband_p = " + std::to_string(nband_p) + " but the model has " +
-                std::to_string(m->nband) + " bands (particulate properties live on the model's bands)");
-  if (!tau_p || !ssa_p || !g_p)
-    return fail("ecckd_lw_fluxes_allsky_rescaled: null argument (tau_p, ssa_p and g_p are required; one-stream particles: ecckd_lw_fluxes_allsky)");
-  if (g_arith.load() != 0) return fail("ecckd_lw_fluxes_allsky_rescaled: needs the fast arithmetic mode (ecckd_set_arithmetic(0))");
-  if (!m->has_planck) return fail("ecckd_lw_fluxes_allsky_rescaled: model has no Planck table (shortwave model?)");
-  if (!tlev) return fail("tlev is required for ecckd");
-  if (n_gauss_angles < 1 || n_gauss_angles > 4) return fail("rte_lw: have to ask for at least one quadrature point and no more than 4");
-  // ecckd_lw_fluxes_rescaled_jac's own, behind the refusals above (which a host-only model answers too) and before the model
-  // is asked for its device
-  if ((x.up_clear != nullptr) != (x.dn_clear != nullptr))
-    return fail("ecckd_lw_fluxes_rescaled_jac: null argument (flux_up_clear and flux_dn_clear are given together or not at all)");
-  if (x.up_clear && (x.up_clear == flux_up || x.up_clear == flux_dn || x.dn_clear == flux_up || x.dn_clear == flux_dn))
-    return fail("ecckd_lw_fluxes_rescaled_jac: a clear-sky output must not be an all-sky output (the two sets of fluxes need arrays of their own)");
-  if (x.jac && (x.jac == flux_up || x.jac == flux_dn || x.jac == x.up_clear || x.jac == x.dn_clear))
-    return fail("ecckd_lw_fluxes_rescaled_jac: flux_up_jac must not be another output (it needs an array of its own)");
-  if (check_model(m) || check_gas_optics_dims(ncol, nlay)) return 1;
-  if (!plev || !tlay || !tsfc || !sfc_emis || !flux_up || !flux_dn || (ngas > 0 && !gas_names))
-    return fail("ecckd_lw_fluxes_allsky_rescaled: null argument");
-  if (memspace != ECCKD_DEVICE && memspace != ECCKD_HOST) return fail("ecckd: bad memspace");
-  HIPCHK(hipSetDevice(m->device));
-  if (ncol == 0) return 0;
-  const GasDesc gd{ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar};
+// ecckd_lw_fluxes_allsky_rescaled and ecckd_lw_fluxes_rescaled_jac (`o.clear`, `o.jac`: each may be null)
+static int lw_fluxes_allsky_rescaled_impl(const ecckd_model_t *m, const LwColumns &c, int nband_p, const LwParticles &pt,
+                                          const FluxOutputs &o, int memspace, void *stream) {
+  CallWords w;
+  w.who = w.who_mask = "ecckd_lw_fluxes_allsky_rescaled";
+  w.planes_tail = kScatteringPlanesTail;
+  // ecckd_lw_fluxes_rescaled_jac's own, behind the refusals that a host-only model answers too and before the model is
+  // asked for its device
+  w.who_clear = "ecckd_lw_fluxes_rescaled_jac";
+  w.clear_tail = ": null argument (flux_up_clear and flux_dn_clear are given together or not at all)";
+  bool done;
+  if (lw_head(w, m, c, nband_p, pt) || gauss_refusals(c) || clear_refusals(w, o) || jac_refusals(w.who_clear, o)) return 1;
+  if (check_model(m) || check_gas_optics_dims(c.ncol, c.nlay)) return 1;
+  if (c.null_array() || !o.all.up || !o.all.dn) return refuse(w.who, ": null argument");
+  if (on_device(m, c.ncol, memspace, &done)) return 1;
+  if (done) return 0;
+  const int ncol = c.ncol, nlay = c.nlay;
   const Counts n(ncol, nlay, m->ng, m->nband);
-  const bool with_clear = x.up_clear != nullptr;
+  const bool with_clear = o.clear.up != nullptr;
   const bool resc_fused = resc_fused_kernel_applies(m, nlay);
   // the Jacobian inside the 60-layer flux kernel ("lw_jac_inline" = 1, and its third accumulator plane fits next to the
   // model's Planck table), or from the stand-alone kernel behind the flux pass
-  const bool jac_in = x.jac && resc_fused && g_opt.lw_jac_inline.load() == 1 && ecckd::rte_lw_rescaled_planck_fits(m->ng, m->ntp, true);
+  const bool jac_in = o.jac && resc_fused && g_opt.lw_jac_inline.load() == 1 && ecckd::rte_lw_rescaled_planck_fits(m->ng, m->ntp, true);
   Stage st(const_cast<ecckd_model *>(m), memspace, stream, false);
-  const double *d_plev = nullptr, *d_tlay = nullptr, *d_tsfc = nullptr, *d_tlev = nullptr;
+  LwColumns d{};
   LwParticles d_pt{};
-  const double *q_g = nullptr;
-  double *work = nullptr, *d_upc = nullptr, *d_dnc = nullptr, *d_jac = nullptr;
-  GasDesc d_gd{};
-  ecckd::RteLwArgs a{};
-  if (fill_band_map(m->ng, m->nband, m->band2gpt.data(), a.gpt2band)) return 1;
-  a.ncol = ncol; a.nlay = nlay; a.ng = m->ng; a.top_at_1 = top_at_1 ? 1 : 0; a.nband = m->nband;
-  fill_lw_options(a, n_gauss_angles, false);
+  FluxOutputs d_o{};
+  double *work = nullptr;
   if (st.open([&] {
-        d_plev = st.in(plev, n.lev); d_tlay = st.in(tlay, n.lay); d_tsfc = st.in(tsfc, n.col); d_tlev = st.in(tlev, n.lev);
-        a.sfc_emis = st.in(sfc_emis, n.col_b); a.inc_flux = st.in(inc_flux, n.col_g);
-        d_gd = st.gases(gd, ncol, nlay);
-        d_pt = LwParticles{st.in(tau_p, n.lay_b), st.in(ssa_p, n.lay_b), st.in(cloud_mask, n.lay)};
-        q_g = st.in(g_p, n.lay_b);
-        a.flux_up = st.out(flux_up, n.lev); a.flux_dn = st.out(flux_dn, n.lev);
-        d_upc = st.out(x.up_clear, n.lev); d_dnc = st.out(x.dn_clear, n.lev); d_jac = st.out(x.jac, n.lev);
+        d = c.staged(st, n);
+        d_pt = LwParticles{pt.tau, pt.ssa, nullptr, pt.mask}.staged(st, n);
+        d_pt.g = st.in(pt.g, n.lay_b);   // (this call has always declared g behind the mask: its rooms stay where they were)
+        d_o.all = o.all.staged(st, n.lev);
+        d_o.clear = o.clear.staged(st, n.lev);
+        d_o.jac = st.out(o.jac, n.lev);
         work = st.work(allsky_rescaled_jac_doubles(m, ncol, nlay, with_clear) * sizeof(double));
       }))
     return 1;
+  ecckd::RteLwArgs a{};
+  if (lw_solver_args(m, d, false, a)) return 1;
+  a.flux_up = d_o.all.up; a.flux_dn = d_o.all.dn;
   const hipStream_t s = st.stream;
-  if (gas_optical_depth_dev(m, false, nullptr, ncol, nlay, d_plev, d_tlay, d_gd, work, false, nullptr, nullptr, nullptr, nullptr, s))
+  if (gas_optical_depth_dev(m, false, nullptr, ncol, nlay, d.plev, d.tlay, d.gas, work, false, nullptr, nullptr, nullptr, nullptr, s))
     return 1;
   a.tau = work;
   double *const clear_extra = work + allsky_rescaled_doubles(m, ncol, nlay);   // (with_clear: what the clear pass needs)
   if (resc_fused) {   // the band triple and the mask ride into the solver
     // the clear sky first, from the gas optical depth as it stands: the launch of ecckd_lw_fluxes
-    if (with_clear && rte_lw_fused_dev(m, ncol, nlay, top_at_1, n_gauss_angles, work, d_tlay, d_tlev, d_tsfc, a.sfc_emis, a.inc_flux,
-                                       d_upc, d_dnc, fused_scratch_doubles(m, ncol, nlay) ? clear_extra : nullptr, s))
-      return 1;
-    a.part_tau = d_pt.tau; a.part_ssa = d_pt.ssa; a.part_g = q_g; a.part_mask = d_pt.mask;
+    if (with_clear && rte_lw_fused_dev(m, d, work, d_o.clear, fused_scratch_doubles(m, ncol, nlay) ? clear_extra : nullptr, s)) return 1;
+    a.part_tau = d_pt.tau; a.part_ssa = d_pt.ssa; a.part_g = d_pt.g; a.part_mask = d_pt.mask;
     {
       ProfScope prof("rte_lw_rescaled_allsky", s);
       HIPCHK(ecckd::launch_rte_lw_rescaled_planck(a, m->dbuf + m->off_planck, m->ntp, m->temperature_planck[0],
-                                                  m->temperature_planck[1] - m->temperature_planck[0], d_tlay, d_tlev, d_tsfc, s,
-                                                  jac_in ? d_jac : nullptr));
+                                                  m->temperature_planck[1] - m->temperature_planck[0], d.tlay, d.tlev, d.tsfc, s,
+                                                  jac_in ? d_o.jac : nullptr));
     }
     // (scratch still holds the gas optical depth: the stand-alone kernel forms the cell's triple as the flux kernel did)
-    if (x.jac && !jac_in && lw_rescaled_jac_dev(a, nullptr, m, d_tsfc, d_jac, s)) return 1;
+    if (o.jac && !jac_in && lw_rescaled_jac_dev(a, nullptr, m, d.tsfc, d_o.jac, s)) return 1;
     return st.close();
   }
   // any other layer count (slow): Planck sources and the by-band increment on (tau, 0, 0) through scratch, then the
@@ -2905,19 +3059,18 @@ static int lw_fluxes_allsky_rescaled_impl(const ecckd_model_t *m, int ncol, int 
   const size_t n3 = r32(n.lay_g);
   double *ssa = work + n3, *g = ssa + n3, *lay = g + n3, *inc = lay + n3, *dec = inc + n3, *sfc = dec + n3;
   double *spec = sfc + r32((size_t)ncol * m->ng);
-  const PlanckSide src{d_tlev, d_tsfc, lay, inc, dec, sfc};
-  if (planck_sources_dev(m, ncol, nlay, d_tlay, src, s)) return 1;
+  const PlanckSide src{d.tlev, d.tsfc, lay, inc, dec, sfc};
+  if (planck_sources_dev(m, ncol, nlay, d.tlay, src, s)) return 1;
   // the clear sky before the by-band increment: the general route of ecckd_lw_fluxes on these sources
-  if (with_clear && rte_lw_fused_dev(m, ncol, nlay, top_at_1, n_gauss_angles, work, d_tlay, d_tlev, d_tsfc, a.sfc_emis, a.inc_flux, d_upc,
-                                     d_dnc, ecckd::rte_lw_scratch_bytes(ncol, nlay, m->ng) ? clear_extra : nullptr, s, nullptr, nullptr,
-                                     false, nullptr, &src))
+  if (with_clear && rte_lw_fused_dev(m, d, work, d_o.clear, ecckd::rte_lw_scratch_bytes(ncol, nlay, m->ng) ? clear_extra : nullptr, s,
+                                     nullptr, nullptr, false, nullptr, &src))
     return 1;
   HIPCHK(hipMemsetAsync(ssa, 0, 2 * n3 * sizeof(double), s));
-  if (lw_increment_dev(m, ncol, nlay, work, d_pt, s, ssa, g, q_g)) return 1;
+  if (lw_increment_dev(m, ncol, nlay, work, d_pt, s, ssa, g)) return 1;
   a.ssa = ssa; a.g = g; a.lay_source = lay; a.lev_source_inc = inc; a.lev_source_dec = dec; a.sfc_source = sfc;
   if (lw_rescaled_dev(a, spec, s)) return 1;
   // on the (tau, ssa, g) the increment left in scratch
-  if (x.jac && lw_rescaled_jac_dev(a, nullptr, m, d_tsfc, d_jac, s)) return 1;
+  if (o.jac && lw_rescaled_jac_dev(a, nullptr, m, d.tsfc, d_o.jac, s)) return 1;
   return st.close();
 }
 
@@ -2928,9 +3081,10 @@ int ecckd_lw_fluxes_allsky_rescaled(const ecckd_model_t *m, int ncol, int nlay, 
                                     const double *inc_flux, int nband_p, const double *tau_p, const double *ssa_p,
                                     const double *g_p, const unsigned long long *cloud_mask, double *flux_up, double *flux_dn,
                                     int memspace, void *stream) {
-  return lw_fluxes_allsky_rescaled_impl(m, ncol, nlay, plev, tlay, tsfc, tlev, ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride,
-                                        vmr_scalar, top_at_1, n_gauss_angles, sfc_emis, inc_flux, nband_p, tau_p, ssa_p, g_p,
-                                        cloud_mask, flux_up, flux_dn, memspace, stream, RescExtras{nullptr, nullptr, nullptr});
+  const LwColumns c{ncol, nlay, plev, tlay, tsfc, tlev, GasDesc{ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar},
+                    top_at_1, n_gauss_angles, sfc_emis, inc_flux};
+  return lw_fluxes_allsky_rescaled_impl(m, c, nband_p, LwParticles{tau_p, ssa_p, g_p, cloud_mask},
+                                        FluxOutputs{Fluxes{flux_up, flux_dn}}, memspace, stream);
 }
 
 int ecckd_lw_fluxes_rescaled_jac(const ecckd_model_t *m, int ncol, int nlay, const double *plev, const double *tlay,
@@ -2940,41 +3094,16 @@ int ecckd_lw_fluxes_rescaled_jac(const ecckd_model_t *m, int ncol, int nlay, con
                                  const double *inc_flux, int nband_p, const double *tau_p, const double *ssa_p,
                                  const double *g_p, const unsigned long long *cloud_mask, double *flux_up, double *flux_dn,
                                  double *flux_up_clear, double *flux_dn_clear, double *flux_up_jac, int memspace, void *stream) {
-  return lw_fluxes_allsky_rescaled_impl(m, ncol, nlay, plev, tlay, tsfc, tlev, ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride,
-                                        vmr_scalar, top_at_1, n_gauss_angles, sfc_emis, inc_flux, nband_p, tau_p, ssa_p, g_p,
-                                        cloud_mask, flux_up, flux_dn, memspace, stream,
-                                        RescExtras{flux_up_clear, flux_dn_clear, flux_up_jac});
-}
-
-// The superset of the four fused longwave calls, with flux_up_jac of the sky that flux_up holds (include/ecckd_hip.h)
-int ecckd_lw_fluxes_jac(const ecckd_model_t *m, int ncol, int nlay, const double *plev, const double *tlay, const double *tsfc,
-                        const double *tlev, int ngas, const char *gas_names, const double *const *vmr,
-                        const long long *vmr_col_stride, const long long *vmr_lay_stride, const double *vmr_scalar, int top_at_1,
-                        int n_gauss_angles, const double *sfc_emis, const double *inc_flux, int nband_p, const double *tau_p,
-                        const double *ssa_p, const unsigned long long *cloud_mask, double *flux_up, double *flux_dn,
-                        double *flux_up_clear, double *flux_dn_clear, double *flux_up_jac, int memspace, void *stream) {
-  const bool clear_out = flux_up_clear || flux_dn_clear;
-  if (!tau_p) {   // the clear sky of ecckd_lw_fluxes
-    const LwJac jx{flux_up_jac, nband_p != 0 || ssa_p || cloud_mask || clear_out};
-    return lw_fluxes_impl(false, m, ncol, nlay, plev, tlay, tsfc, tlev, ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar,
-                          top_at_1, n_gauss_angles, sfc_emis, inc_flux, flux_up, flux_dn, memspace, stream, nullptr, nullptr, &jx);
-  }
-  const LwJac jx{flux_up_jac, false};
-  const ClearFluxes clr{flux_up_clear, flux_dn_clear, nullptr};
-  return lw_fluxes_allsky_impl(false, m, ncol, nlay, plev, tlay, tsfc, tlev, ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride,
-                               vmr_scalar, top_at_1, n_gauss_angles, sfc_emis, inc_flux, nband_p, tau_p, ssa_p, cloud_mask, flux_up,
-                               flux_dn, memspace, stream, clear_out ? &clr : nullptr, &jx);
+  const LwColumns c{ncol, nlay, plev, tlay, tsfc, tlev, GasDesc{ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar},
+                    top_at_1, n_gauss_angles, sfc_emis, inc_flux};
+  const LwParticles pt{tau_p, ssa_p, g_p, cloud_mask};
+  const FluxOutputs o{Fluxes{flux_up, flux_dn}, Fluxes{flux_up_clear, flux_dn_clear}, Fluxes{}, flux_up_jac};
+  return lw_fluxes_allsky_rescaled_impl(m, c, nband_p, pt, o, memspace, stream);
 }
 
 // ---- fused shortwave: total optical depth only between the kernels (SURVEY 8(f) rank 4 for the shortwave) ----
 
-// ecckd_sw_fluxes_allsky: the combined particulate optical properties on the model's bands, (ncol,nlay,nband) each, in the
-// memory space of the call; delta_scale: the library delta-scales a copy (f = g*g) first
-// mask: ecckd_sw_fluxes_allsky_mcica -- the cloud mask (ncol,nlay), in the memory space of the call, or null
-// scaling: ecckd_sw_flux_scaled -- the sampled optical-depth scaling (ncol,nlay,ngpt), float32, in the memory space of the call, or null
-struct SwParticles { const double *tau, *ssa, *g; int delta_scale; const unsigned long long *mask = nullptr; const float *scaling = nullptr; };
-
-// The work block of sw_fluxes_impl: the optical depth, the solver's room, the three scaled band planes (or none)
+// The work block of sw_fluxes_run: the optical depth, the solver's room, the three scaled band planes (or none)
 struct SwWork {
   size_t tau_bytes, solver, plane;
   SwWork(const ecckd_model *m, bool f32, int ncol, int nlay, bool scaled_planes, bool two_pass = false) {
@@ -2986,114 +3115,90 @@ struct SwWork {
   size_t bytes() const { return tau_bytes + solver + 3 * plane; }
 };
 
-static int sw_fluxes_impl(bool f32, const ecckd_model_t *m, int ncol, int nlay, const double *plev, const double *tlay,
-                          int ngas, const char *gas_names, const double *const *vmr, const long long *vmr_col_stride,
-                          const long long *vmr_lay_stride, const double *vmr_scalar, int top_at_1, const double *mu0,
-                          const double *toa_scale, const double *sfc_alb_dir, const double *sfc_alb_dif, double *flux_up,
-                          double *flux_dn, double *flux_dir, int memspace, void *stream, const SwParticles *pt = nullptr,
-                          const ClearFluxes *clr = nullptr) {
-  if (check_model(m) || check_gas_optics_dims(ncol, nlay)) return 1;
-  if (!m->has_solar) return fail("ecckd_sw_fluxes: model has no solar table (longwave model?)");
-  if (!plev || !tlay || !mu0 || !sfc_alb_dir || !sfc_alb_dif || !flux_up || !flux_dn || (ngas > 0 && !gas_names))
-    return fail("ecckd_sw_fluxes: null argument");
-  if (g_arith.load() != 0) return fail("ecckd_sw_fluxes: needs the fast arithmetic mode (ecckd_set_arithmetic(0))");
-  HIPCHK(hipSetDevice(m->device));
-  if (ncol == 0) return 0;
-  const GasDesc gd{ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar};
-  if (memspace != ECCKD_DEVICE && memspace != ECCKD_HOST) return fail("ecckd: bad memspace");
+// The delta-scaled copy of the band triple (f = g*g) in three planes of `plane` bytes at `room`: the caller's arrays are
+// never written, `pt` points at the copy afterwards
+static int delta_scaled_copy(SwParticles &pt, size_t count, char *room, size_t plane, bool f32, hipStream_t stream) {
+  double *q_tau = reinterpret_cast<double *>(room), *q_ssa = reinterpret_cast<double *>(room + plane),
+         *q_g = reinterpret_cast<double *>(room + 2 * plane);
+  ProfScope prof("delta_scale", stream);
+  HIPCHK(ecckd::launch_delta_scale(count, pt.tau, pt.ssa, pt.g, nullptr, q_tau, q_ssa, q_g, f32 ? 1 : 0, stream));
+  pt.tau = q_tau; pt.ssa = q_ssa; pt.g = q_g;
+  return 0;
+}
+
+// The fused shortwave calls behind their refusals: gas optical depth into the work block, then the solver -- once, or for
+// the clear sky first where `o.clear` is named
+static int sw_fluxes_run(bool f32, const ecckd_model *m, const SwColumns &c, const SwParticles &pt, const FluxOutputs &o,
+                         int memspace, void *stream) {
+  const int ncol = c.ncol, nlay = c.nlay;
   const Counts n(ncol, nlay, m->ng, m->nband);
+  const bool part = pt.tau != nullptr, both = o.clear.up != nullptr;
   // The work block: tau between the two kernels, the solver's room behind it, and -- all-sky with delta scaling -- three
-  // band planes for the scaled copy of the particles (the caller's arrays are never written).  With device arrays it is
-  // the stream's scratch block, so the capture rules of stream_scratch cover all of it.
-  const SwWork work(m, f32, ncol, nlay, pt && pt->delta_scale, pt && pt->scaling);
-  const size_t tau_bytes = work.tau_bytes, solver = work.solver, plane = work.plane;
+  // band planes for the scaled copy of the particles.  With device arrays it is the stream's scratch block, so the
+  // capture rules of stream_scratch cover all of it.
+  const SwWork work(m, f32, ncol, nlay, part && pt.delta_scale, part && pt.scaling);
   Stage st(const_cast<ecckd_model *>(m), memspace, stream, f32);
-  const double *d_plev = nullptr, *d_tlay = nullptr, *d_mu0 = nullptr, *d_scale = nullptr, *d_ad = nullptr, *d_af = nullptr;
-  double *d_up = nullptr, *d_dn = nullptr, *d_dir = nullptr, *d_tau = nullptr;
-  GasDesc d_gd{};
+  SwColumns d{};
   SwParticles d_pt{};
-  ClearFluxes d_clr{};
+  FluxOutputs d_o{};
+  double *d_tau = nullptr;
   if (st.open([&] {
-        d_plev = st.in(plev, n.lev); d_tlay = st.in(tlay, n.lay); d_mu0 = st.in(mu0, n.col); d_scale = st.in(toa_scale, n.col);
-        d_ad = st.in(sfc_alb_dir, n.col_b); d_af = st.in(sfc_alb_dif, n.col_b);
-        d_gd = st.gases(gd, ncol, nlay);
-        if (pt) d_pt = SwParticles{st.in(pt->tau, n.lay_b), st.in(pt->ssa, n.lay_b), st.in(pt->g, n.lay_b), pt->delta_scale, st.in(pt->mask, n.lay),
-                                   static_cast<const float *>(st.in_bytes(pt->scaling, n.lay_g * sizeof(float)))};
-        if (clr) d_clr = ClearFluxes{st.out(clr->up, n.lev), st.out(clr->dn, n.lev), st.out(clr->dir, n.lev)};
-        d_up = st.out(flux_up, n.lev); d_dn = st.out(flux_dn, n.lev); d_dir = st.out(flux_dir, n.lev);
+        d = c.staged(st, n);
+        d_pt = pt.staged(st, n);
+        d_o.clear = o.clear.staged(st, n.lev);
+        d_o.all = o.all.staged(st, n.lev);
         d_tau = st.work(work.bytes());
       }))
     return 1;
-  char *const room = reinterpret_cast<char *>(d_tau) + tau_bytes;
-  if (plane) {
-    double *q_tau = reinterpret_cast<double *>(room + solver), *q_ssa = reinterpret_cast<double *>(room + solver + plane),
-           *q_g = reinterpret_cast<double *>(room + solver + 2 * plane);
-    ProfScope prof("delta_scale", st.stream);
-    HIPCHK(ecckd::launch_delta_scale(n.lay_b, d_pt.tau, d_pt.ssa, d_pt.g, nullptr, q_tau, q_ssa, q_g, f32 ? 1 : 0, st.stream));
-    d_pt.tau = q_tau; d_pt.ssa = q_ssa; d_pt.g = q_g;
-  }
+  char *const room = reinterpret_cast<char *>(d_tau) + work.tau_bytes;
+  if (work.plane && delta_scaled_copy(d_pt, n.lay_b, room + work.solver, work.plane, f32, st.stream)) return 1;
   // gas_optics_ext's tau (:449-456) without ssa / g: the total optical depth, gases + Rayleigh
-  if (gas_optical_depth_dev(m, f32, nullptr, ncol, nlay, d_plev, d_tlay, d_gd, d_tau, true, nullptr, nullptr, nullptr, nullptr, st.stream))
+  if (gas_optical_depth_dev(m, f32, nullptr, ncol, nlay, d.plev, d.tlay, d.gas, d_tau, true, nullptr, nullptr, nullptr, nullptr, st.stream))
     return 1;
-  SwDerive dv{d_plev, table(m, m->off_rayleigh, f32), table(m, m->off_solar, f32), d_scale, gw(f32),
-              solver ? reinterpret_cast<double *>(room) : nullptr};
-  auto solve = [&](const ClearFluxes &to) {   // (its arrays are on the device by now, whatever the call's memory space)
-    return rte_sw_impl(Call{f32, -1, false, &dv}, m->device, ncol, nlay, m->ng, top_at_1, d_tau, nullptr, nullptr, d_mu0, nullptr,
-                       m->nband, m->band2gpt.data(), d_ad, d_af, to.up, to.dn, to.dir, ECCKD_DEVICE, st.stream);
+  SwDerive dv{d.plev, table(m, m->off_rayleigh, f32), table(m, m->off_solar, f32), d.toa_scale, gw(f32),
+              work.solver ? reinterpret_cast<double *>(room) : nullptr};
+  auto solve = [&](const Fluxes &to) {   // (its arrays are on the device by now, whatever the call's memory space)
+    return rte_sw_impl(Call{f32, -1, false, &dv}, m->device, ncol, nlay, m->ng, d.top_at_1, d_tau, nullptr, nullptr, d.mu0, nullptr,
+                       m->nband, m->band2gpt.data(), d.sfc_alb_dir, d.sfc_alb_dif, to.up, to.dn, to.dir, ECCKD_DEVICE, st.stream);
   };
   // ecckd_sw_fluxes_clear_allsky: the clear-sky solver of ecckd_sw_fluxes first, on the same tau and in the same room
-  if (clr && solve(d_clr)) return 1;
-  if (pt) { dv.part_tau = d_pt.tau; dv.part_ssa = d_pt.ssa; dv.part_g = d_pt.g; dv.part_mask = d_pt.mask; dv.part_scaling = d_pt.scaling; }
-  if (solve(ClearFluxes{d_up, d_dn, d_dir})) return 1;
+  if (both && solve(d_o.clear)) return 1;
+  if (part) { dv.part_tau = d_pt.tau; dv.part_ssa = d_pt.ssa; dv.part_g = d_pt.g; dv.part_mask = d_pt.mask; dv.part_scaling = d_pt.scaling; }
+  if (solve(d_o.all)) return 1;
   return st.close();
 }
+
+// (`w`: the words of an all-sky form, whose list goes first; null: ecckd_sw_fluxes)
+static int sw_fluxes_impl(const CallWords *w, bool f32, const ecckd_model_t *m, const SwColumns &c, int nband_p, const SwParticles &pt,
+                          const FluxOutputs &o, int memspace, void *stream) {
+  bool done;
+  if (w && (sw_head(*w, m, nband_p, pt, o) || clear_refusals(*w, o))) return 1;
+  if (sw_plain_tail(m, c, o, memspace, &done)) return 1;
+  return done ? 0 : sw_fluxes_run(f32, m, c, pt, o, memspace, stream);
+}
+
+// the words of the all-sky forms (clear_required: the clear-sky outputs are part of the call)
+static CallWords sw_allsky_words(bool clear_required = false) {
+  CallWords w;
+  w.who = "ecckd_sw_fluxes_allsky";
+  w.who_mask = "ecckd_sw_fluxes_allsky_mcica";
+  w.planes_tail = ": null argument (tau_p, ssa_p and g_p are all required)";
+  w.who_clear = "ecckd_sw_fluxes_clear_allsky";
+  w.clear_tail = ": null argument (flux_up_clear and flux_dn_clear are both required; flux_dir_clear may be null)";
+  w.clear_required = clear_required;
+  return w;
+}
+static const CallWords kSwAllsky = sw_allsky_words(), kSwClearAllsky = sw_allsky_words(true);
 
 int ecckd_sw_fluxes(const ecckd_model_t *m, int ncol, int nlay, const double *plev, const double *tlay, int ngas,
                     const char *gas_names, const double *const *vmr, const long long *vmr_col_stride,
                     const long long *vmr_lay_stride, const double *vmr_scalar, int top_at_1, const double *mu0,
                     const double *toa_scale, const double *sfc_alb_dir, const double *sfc_alb_dif, double *flux_up,
                     double *flux_dn, double *flux_dir, int memspace, void *stream) {
-  return sw_fluxes_impl(false, m, ncol, nlay, plev, tlay, ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar,
-                        top_at_1, mu0, toa_scale, sfc_alb_dir, sfc_alb_dif, flux_up, flux_dn, flux_dir, memspace, stream);
-}
-
-// ... its part that every form shares (ecckd_sw_flux_scaled too)
-static int sw_fluxes_allsky_refusals(const ecckd_model_t *m, int nband_p, const double *tau_p, const double *ssa_p,
-                                     const double *g_p, int delta_scale) {
-  if (!m) return fail("ecckd: null model");
-  if (nband_p != m->nband)
-    return fail("ecckd_sw_fluxes_allsky: nband_p = " + std::to_string(nband_p) + " but the model has " + std::to_string(m->nband) +
-                " bands (particulate properties live on the model's bands)");
-  if (!tau_p || !ssa_p || !g_p) return fail("ecckd_sw_fluxes_allsky: null argument (tau_p, ssa_p and g_p are all required)");
-  if (delta_scale != 0 && delta_scale != 1) return fail("ecckd_sw_fluxes_allsky: delta_scale must be 0 or 1");
-  if (g_arith.load() != 0) return fail("ecckd_sw_fluxes_allsky: needs the fast arithmetic mode (ecckd_set_arithmetic(0))");
-  return 0;
-}
-
-// The one refusal list of the fused all-sky shortwave calls; cloud_mask as in lw_fluxes_allsky_impl.  f32: the _f32 entry
-// points (float data behind the double pointers, dp()); the messages are those of the fp64 namesakes.
-static int sw_fluxes_allsky_impl(bool f32, const ecckd_model_t *m, int ncol, int nlay, const double *plev, const double *tlay, int ngas,
-                                 const char *gas_names, const double *const *vmr, const long long *vmr_col_stride,
-                                 const long long *vmr_lay_stride, const double *vmr_scalar, int top_at_1, const double *mu0,
-                                 const double *toa_scale, const double *sfc_alb_dir, const double *sfc_alb_dif, int nband_p,
-                                 const double *tau_p, const double *ssa_p, const double *g_p, int delta_scale,
-                                 const unsigned long long *cloud_mask, double *flux_up, double *flux_dn, double *flux_dir,
-                                 int memspace, void *stream, const ClearFluxes *clr = nullptr) {
-  if (!m) return fail("ecckd: null model");
-  if (cloud_mask && m->ng > 64) return fail("ecckd_sw_fluxes_allsky_mcica" + std::string(kMaskTooWide) + std::to_string(m->ng));
-  if (sw_fluxes_allsky_refusals(m, nband_p, tau_p, ssa_p, g_p, delta_scale)) return 1;
-  if (clr) {
-    if (!clr->up || !clr->dn)
-      return fail("ecckd_sw_fluxes_clear_allsky: null argument (flux_up_clear and flux_dn_clear are both required; flux_dir_clear may be null)");
-    double *const all[3] = {flux_up, flux_dn, flux_dir}, *const clear[3] = {clr->up, clr->dn, clr->dir};
-    for (double *c : clear)
-      for (double *f : all)
-        if (c && c == f)
-          return fail("ecckd_sw_fluxes_clear_allsky: a clear-sky output must not be an all-sky output (the two sets of fluxes need arrays of their own)");
-  }
-  const SwParticles pt{tau_p, ssa_p, g_p, delta_scale, cloud_mask};
-  return sw_fluxes_impl(f32, m, ncol, nlay, plev, tlay, ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar,
-                        top_at_1, mu0, toa_scale, sfc_alb_dir, sfc_alb_dif, flux_up, flux_dn, flux_dir, memspace, stream, &pt, clr);
+  const SwColumns c{ncol, nlay, plev, tlay, GasDesc{ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar}, top_at_1,
+                    mu0, toa_scale, sfc_alb_dir, sfc_alb_dif};
+  const FluxOutputs o{Fluxes{flux_up, flux_dn, flux_dir}};
+  return sw_fluxes_impl(nullptr, false, m, c, 0, SwParticles{}, o, memspace, stream);
 }
 
 int ecckd_sw_fluxes_clear_allsky(const ecckd_model_t *m, int ncol, int nlay, const double *plev, const double *tlay, int ngas,
@@ -3104,10 +3209,11 @@ int ecckd_sw_fluxes_clear_allsky(const ecckd_model_t *m, int ncol, int nlay, con
                                  const unsigned long long *cloud_mask, double *flux_up, double *flux_dn, double *flux_dir,
                                  double *flux_up_clear, double *flux_dn_clear, double *flux_dir_clear, int memspace,
                                  void *stream) {
-  const ClearFluxes clr{flux_up_clear, flux_dn_clear, flux_dir_clear};
-  return sw_fluxes_allsky_impl(false, m, ncol, nlay, plev, tlay, ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar,
-                               top_at_1, mu0, toa_scale, sfc_alb_dir, sfc_alb_dif, nband_p, tau_p, ssa_p, g_p, delta_scale,
-                               cloud_mask, flux_up, flux_dn, flux_dir, memspace, stream, &clr);
+  const SwColumns c{ncol, nlay, plev, tlay, GasDesc{ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar}, top_at_1,
+                    mu0, toa_scale, sfc_alb_dir, sfc_alb_dif};
+  const SwParticles pt{tau_p, ssa_p, g_p, delta_scale, cloud_mask};
+  const FluxOutputs o{Fluxes{flux_up, flux_dn, flux_dir}, Fluxes{flux_up_clear, flux_dn_clear, flux_dir_clear}};
+  return sw_fluxes_impl(&kSwClearAllsky, false, m, c, nband_p, pt, o, memspace, stream);
 }
 
 int ecckd_sw_fluxes_allsky(const ecckd_model_t *m, int ncol, int nlay, const double *plev, const double *tlay, int ngas,
@@ -3116,9 +3222,10 @@ int ecckd_sw_fluxes_allsky(const ecckd_model_t *m, int ncol, int nlay, const dou
                            const double *toa_scale, const double *sfc_alb_dir, const double *sfc_alb_dif, int nband_p,
                            const double *tau_p, const double *ssa_p, const double *g_p, int delta_scale, double *flux_up,
                            double *flux_dn, double *flux_dir, int memspace, void *stream) {
-  return sw_fluxes_allsky_impl(false, m, ncol, nlay, plev, tlay, ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar,
-                               top_at_1, mu0, toa_scale, sfc_alb_dir, sfc_alb_dif, nband_p, tau_p, ssa_p, g_p, delta_scale, nullptr,
-                               flux_up, flux_dn, flux_dir, memspace, stream);
+  const SwColumns c{ncol, nlay, plev, tlay, GasDesc{ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar}, top_at_1,
+                    mu0, toa_scale, sfc_alb_dir, sfc_alb_dif};
+  return sw_fluxes_impl(&kSwAllsky, false, m, c, nband_p, SwParticles{tau_p, ssa_p, g_p, delta_scale},
+                        FluxOutputs{Fluxes{flux_up, flux_dn, flux_dir}}, memspace, stream);
 }
 
 int ecckd_sw_fluxes_allsky_mcica(const ecckd_model_t *m, int ncol, int nlay, const double *plev, const double *tlay, int ngas,
@@ -3128,9 +3235,10 @@ int ecckd_sw_fluxes_allsky_mcica(const ecckd_model_t *m, int ncol, int nlay, con
                                  const double *tau_p, const double *ssa_p, const double *g_p, int delta_scale,
                                  const unsigned long long *cloud_mask, double *flux_up, double *flux_dn, double *flux_dir,
                                  int memspace, void *stream) {
-  return sw_fluxes_allsky_impl(false, m, ncol, nlay, plev, tlay, ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar,
-                               top_at_1, mu0, toa_scale, sfc_alb_dir, sfc_alb_dif, nband_p, tau_p, ssa_p, g_p, delta_scale,
-                               cloud_mask, flux_up, flux_dn, flux_dir, memspace, stream);
+  const SwColumns c{ncol, nlay, plev, tlay, GasDesc{ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar}, top_at_1,
+                    mu0, toa_scale, sfc_alb_dir, sfc_alb_dif};
+  return sw_fluxes_impl(&kSwAllsky, false, m, c, nband_p, SwParticles{tau_p, ssa_p, g_p, delta_scale, cloud_mask},
+                        FluxOutputs{Fluxes{flux_up, flux_dn, flux_dir}}, memspace, stream);
 }
 
 // ---- the shortwave on the daylit columns only (kernels_columns.hip): select, gather, solve, scatter ----
@@ -3274,45 +3382,31 @@ int ecckd_sw_fluxes_daylit(const ecckd_model_t *m, int ncol, int nlay, int nday,
                            int delta_scale, const unsigned long long *cloud_mask, double *flux_up, double *flux_dn,
                            double *flux_dir, double *flux_up_clear, double *flux_dn_clear, double *flux_dir_clear, int memspace,
                            void *stream) {
-  // the refusals of sw_fluxes_allsky_impl in its order (those of the particles only with particles), then this call's own
-  if (!m) return fail("ecckd: null model");
-  const bool cloudy = tau_p != nullptr;
-  const bool clear_out = flux_up_clear || flux_dn_clear || flux_dir_clear;
-  if (cloud_mask && m->ng > 64) return fail("ecckd_sw_fluxes_daylit" + std::string(kMaskTooWide) + std::to_string(m->ng));
-  if (cloudy) {
-    if (nband_p != m->nband)
-      return fail("ecckd_sw_fluxes_daylit: nband_p = " + std::to_string(nband_p) + " but the model has " + std::to_string(m->nband) +
-                  " bands (particulate properties live on the model's bands)");
-    if (!ssa_p || !g_p) return fail("ecckd_sw_fluxes_daylit: null argument (tau_p, ssa_p and g_p are given together or not at all)");
-    if (delta_scale != 0 && delta_scale != 1) return fail("ecckd_sw_fluxes_daylit: delta_scale must be 0 or 1");
-  } else if (ssa_p || g_p || cloud_mask || clear_out) {
-    return fail("ecckd_sw_fluxes_daylit: clear sky (tau_p NULL) takes no ssa_p, g_p, cloud_mask or clear-sky outputs");
-  }
-  if (g_arith.load() != 0) return fail("ecckd_sw_fluxes_daylit: needs the fast arithmetic mode (ecckd_set_arithmetic(0))");
-  if (clear_out) {
-    if (!flux_up_clear || !flux_dn_clear)
-      return fail("ecckd_sw_fluxes_daylit: null argument (flux_up_clear and flux_dn_clear are given together or not at all; flux_dir_clear may be null)");
-    double *const all[3] = {flux_up, flux_dn, flux_dir}, *const clear[3] = {flux_up_clear, flux_dn_clear, flux_dir_clear};
-    for (double *c : clear)
-      for (double *f : all)
-        if (c && c == f)
-          return fail("ecckd_sw_fluxes_daylit: a clear-sky output must not be an all-sky output (the two sets of fluxes need arrays of their own)");
-  }
+  const SwColumns c{ncol, nlay, plev, tlay, GasDesc{ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar}, top_at_1,
+                    mu0, toa_scale, sfc_alb_dir, sfc_alb_dif};
+  const SwParticles pt{tau_p, ssa_p, g_p, delta_scale, cloud_mask};
+  const FluxOutputs o{Fluxes{flux_up, flux_dn, flux_dir}, Fluxes{flux_up_clear, flux_dn_clear, flux_dir_clear}};
+  // the refusals of the all-sky calls in their order (those of the particles only with particles), then this call's own,
+  // then those of ecckd_sw_fluxes, which sees nday columns only (and nothing at all with nday = 0)
+  CallWords w;
+  w.who = w.who_mask = w.who_clear = "ecckd_sw_fluxes_daylit";
+  w.planes_tail = ": null argument (tau_p, ssa_p and g_p are given together or not at all)";
+  w.no_particles_tail = ": clear sky (tau_p NULL) takes no ssa_p, g_p, cloud_mask or clear-sky outputs";
+  w.clear_tail = ": null argument (flux_up_clear and flux_dn_clear are given together or not at all; flux_dir_clear may be null)";
+  bool done;
+  if (sw_head(w, m, nband_p, pt, o) || clear_refusals(w, o)) return 1;
   if (nday < 0 || nday > ncol)
     return fail("ecckd_sw_fluxes_daylit: nday = " + std::to_string(nday) + " outside 0.." + std::to_string(ncol));
   if (nday > 0 && !day_index) return fail("ecckd_sw_fluxes_daylit: day_index is NULL with nday > 0");
   if (memspace == ECCKD_HOST && !column_list_ok(day_index, nday, ncol))
     return fail("ecckd_sw_fluxes_daylit: day_index must be strictly ascending and inside [0,ncol)");
-  // ... and those of sw_fluxes_impl, which sees nday columns only (and nothing at all with nday = 0)
   if (check_model(m) || check_gas_optics_dims(ncol, nlay)) return 1;
   if (!m->has_solar) return fail("ecckd_sw_fluxes_daylit: model has no solar table (longwave model?)");
-  if (!plev || !tlay || !mu0 || !sfc_alb_dir || !sfc_alb_dif || !flux_up || !flux_dn || (ngas > 0 && !gas_names))
-    return fail("ecckd_sw_fluxes_daylit: null argument");
-  if (memspace != ECCKD_DEVICE && memspace != ECCKD_HOST) return fail("ecckd: bad memspace");
-  HIPCHK(hipSetDevice(m->device));
-  if (ncol == 0) return 0;
+  if (c.null_array() || !flux_up || !flux_dn) return fail("ecckd_sw_fluxes_daylit: null argument");
+  if (on_device(m, ncol, memspace, &done)) return 1;
+  if (done) return 0;
 
-  const GasDesc gd{ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar};
+  const bool cloudy = tau_p != nullptr, clear_out = o.clear.up != nullptr;
   int ngas_arrays = 0;   // the gas arrays that differ between columns: the others are read in place
   for (int j = 0; j < ngas && nday > 0; ++j)
     if (vmr && vmr[j] && vmr_col_stride && vmr_col_stride[j] != 0) ++ngas_arrays;
@@ -3324,24 +3418,23 @@ int ecckd_sw_fluxes_daylit(const ecckd_model_t *m, int ncol, int nlay, int nday,
   const size_t inner_bytes = nday > 0 && memspace == ECCKD_DEVICE ? SwWork(m, false, nday, nlay, cloudy && delta_scale).bytes() : 0;
   Stage st(const_cast<ecckd_model *>(m), memspace, stream, false);
   const int *d_index = nullptr;
-  const double *d_plev = nullptr, *d_tlay = nullptr, *d_mu0 = nullptr, *d_scale = nullptr, *d_ad = nullptr, *d_af = nullptr;
-  GasDesc d_gd{};
+  SwColumns d{};
   SwParticles d_pt{};
-  double *d_out[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}, *d_work = nullptr;
-  double *const out[6] = {flux_up, flux_dn, flux_dir, flux_up_clear, flux_dn_clear, flux_dir_clear};
+  FluxOutputs d_o{};
+  double *d_work = nullptr;
   if (st.open([&] {
         if (nday > 0) {
           d_index = st.in(day_index, (size_t)nday);
-          d_plev = st.in(plev, n.lev); d_tlay = st.in(tlay, n.lay); d_mu0 = st.in(mu0, n.col); d_scale = st.in(toa_scale, n.col);
-          d_ad = st.in(sfc_alb_dir, n.col_b); d_af = st.in(sfc_alb_dif, n.col_b);
-          d_gd = st.gases(gd, ncol, nlay);
-          if (cloudy) d_pt = SwParticles{st.in(tau_p, n.lay_b), st.in(ssa_p, n.lay_b), st.in(g_p, n.lay_b), delta_scale, st.in(cloud_mask, n.lay)};
+          d = c.staged(st, n);
+          if (cloudy) d_pt = pt.staged(st, n);
         }
-        for (int f = 0; f < 6; ++f) d_out[f] = st.out(out[f], n.lev);
+        d_o.all = o.all.staged(st, n.lev);
+        d_o.clear = o.clear.staged(st, n.lev);
         if (nday > 0) d_work = st.work(inner_bytes + rooms.bytes());
       }))
     return 1;
   const hipStream_t s = st.stream;
+  double *const d_out[6] = {d_o.all.up, d_o.all.dn, d_o.all.dir, d_o.clear.up, d_o.clear.dn, d_o.clear.dir};
   double *g_out[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   if (nday > 0) {
     char *at = reinterpret_cast<char *>(d_work) + inner_bytes;
@@ -3356,14 +3449,14 @@ int ecckd_sw_fluxes_daylit(const ecckd_model_t *m, int ncol, int nlay, int nday,
       auto gather = [&](int ninner, int nouter, const void *src, void *dst) {
         return ecckd::launch_gather_columns(ninner, ncol, nouter, 8, nday, d_index, src, dst, s);
       };
-      HIPCHK(gather(1, nlay + 1, d_plev, g_plev));
-      HIPCHK(gather(1, nlay, d_tlay, g_tlay));
-      HIPCHK(gather(1, 1, d_mu0, g_mu0));
-      if (d_scale) HIPCHK(gather(1, 1, d_scale, g_scale));
-      HIPCHK(gather(m->nband, 1, d_ad, g_ad));
-      HIPCHK(gather(m->nband, 1, d_af, g_af));
+      HIPCHK(gather(1, nlay + 1, d.plev, g_plev));
+      HIPCHK(gather(1, nlay, d.tlay, g_tlay));
+      HIPCHK(gather(1, 1, d.mu0, g_mu0));
+      if (d.toa_scale) HIPCHK(gather(1, 1, d.toa_scale, g_scale));
+      HIPCHK(gather(m->nband, 1, d.sfc_alb_dir, g_ad));
+      HIPCHK(gather(m->nband, 1, d.sfc_alb_dif, g_af));
       for (int j = 0; j < ngas; ++j) {
-        g_vmr[j] = d_gd.vmr ? d_gd.vmr[j] : nullptr;
+        g_vmr[j] = d.gas.vmr ? d.gas.vmr[j] : nullptr;
         g_cs[j] = vmr_col_stride ? vmr_col_stride[j] : 0;
         g_ls[j] = vmr_lay_stride ? vmr_lay_stride[j] : 0;
         if (!g_vmr[j] || g_cs[j] == 0) continue;
@@ -3386,12 +3479,13 @@ int ecckd_sw_fluxes_daylit(const ecckd_model_t *m, int ncol, int nlay, int nday,
     }
     for (int f = 0; f < 6; ++f)
       if (d_out[f]) g_out[f] = take(rooms.lev);
-    const ClearFluxes g_clr{g_out[3], g_out[4], g_out[5]};
-    // the pipeline of the existing calls, unchanged, on nday columns of device arrays
-    if (sw_fluxes_impl(false, m, nday, nlay, g_plev, g_tlay, ngas, gas_names, g_vmr.data(), g_cs.data(), g_ls.data(), vmr_scalar,
-                       top_at_1, g_mu0, d_scale ? g_scale : nullptr, g_ad, g_af, g_out[0], g_out[1], g_out[2], ECCKD_DEVICE, s,
-                       cloudy ? &d_pt : nullptr, clear_out ? &g_clr : nullptr))
-      return 1;
+    // the pipeline of the plain calls, unchanged, on nday columns of device arrays
+    const SwColumns g_c{nday, nlay, g_plev, g_tlay, GasDesc{ngas, gas_names, g_vmr.data(), g_cs.data(), g_ls.data(), vmr_scalar},
+                        top_at_1, g_mu0, d.toa_scale ? g_scale : nullptr, g_ad, g_af};
+    FluxOutputs g_o;
+    g_o.all = Fluxes{g_out[0], g_out[1], g_out[2]};
+    if (clear_out) g_o.clear = Fluxes{g_out[3], g_out[4], g_out[5]};
+    if (sw_fluxes_run(false, m, g_c, cloudy ? d_pt : SwParticles{}, g_o, ECCKD_DEVICE, s)) return 1;
   }
   {
     ProfScope prof("daylit_scatter", s);
@@ -4028,10 +4122,12 @@ int ecckd_lw_flux_scaled(const ecckd_model_t *m, int ncol, int nlay, const doubl
                          const double *ssa_p, const float *cloud_scaling, double *flux_up, double *flux_dn, int memspace,
                          void *stream) {
   // (the refusal list of the unmasked all-sky call, in its order; a null scaling is that call)
-  if (lw_fluxes_allsky_refusals(m, nband_p, tau_p, tlev)) return 1;
-  const LwParticles pt{tau_p, ssa_p, nullptr, cloud_scaling};
-  return lw_fluxes_impl(false, m, ncol, nlay, plev, tlay, tsfc, tlev, ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar,
-                        top_at_1, n_gauss_angles, sfc_emis, inc_flux, flux_up, flux_dn, memspace, stream, &pt);
+  const LwColumns c{ncol, nlay, plev, tlay, tsfc, tlev, GasDesc{ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar},
+                    top_at_1, n_gauss_angles, sfc_emis, inc_flux};
+  LwParticles pt;
+  pt.tau = tau_p; pt.ssa = ssa_p; pt.scaling = cloud_scaling;
+  const FluxOutputs o{Fluxes{flux_up, flux_dn}};
+  return lw_fluxes_impl(&kLwAllsky, false, m, c, nband_p, pt, o, memspace, stream);
 }
 
 int ecckd_sw_flux_scaled(const ecckd_model_t *m, int ncol, int nlay, const double *plev, const double *tlay, int ngas,
@@ -4040,10 +4136,10 @@ int ecckd_sw_flux_scaled(const ecckd_model_t *m, int ncol, int nlay, const doubl
                          const double *toa_scale, const double *sfc_alb_dir, const double *sfc_alb_dif, int nband_p,
                          const double *tau_p, const double *ssa_p, const double *g_p, int delta_scale, const float *cloud_scaling,
                          double *flux_up, double *flux_dn, double *flux_dir, int memspace, void *stream) {
-  if (sw_fluxes_allsky_refusals(m, nband_p, tau_p, ssa_p, g_p, delta_scale)) return 1;
-  const SwParticles pt{tau_p, ssa_p, g_p, delta_scale, nullptr, cloud_scaling};
-  return sw_fluxes_impl(false, m, ncol, nlay, plev, tlay, ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar,
-                        top_at_1, mu0, toa_scale, sfc_alb_dir, sfc_alb_dif, flux_up, flux_dn, flux_dir, memspace, stream, &pt);
+  const SwColumns c{ncol, nlay, plev, tlay, GasDesc{ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar}, top_at_1,
+                    mu0, toa_scale, sfc_alb_dir, sfc_alb_dif};
+  return sw_fluxes_impl(&kSwAllsky, false, m, c, nband_p, SwParticles{tau_p, ssa_p, g_p, delta_scale, nullptr, cloud_scaling},
+                        FluxOutputs{Fluxes{flux_up, flux_dn, flux_dir}}, memspace, stream);
 }
 
 int ecckd_sw_fluxes_f32(const ecckd_model_t *m, int ncol, int nlay, const float *plev, const float *tlay, int ngas,
@@ -4051,22 +4147,17 @@ int ecckd_sw_fluxes_f32(const ecckd_model_t *m, int ncol, int nlay, const float 
                         const long long *vmr_lay_stride, const double *vmr_scalar, int top_at_1, const float *mu0,
                         const float *toa_scale, const float *sfc_alb_dir, const float *sfc_alb_dif, float *flux_up,
                         float *flux_dn, float *flux_dir, int memspace, void *stream) {
-  return sw_fluxes_impl(true, m, ncol, nlay, dp(plev), dp(tlay), ngas, gas_names, reinterpret_cast<const double *const *>(vmr),
-                        vmr_col_stride, vmr_lay_stride, vmr_scalar, top_at_1, dp(mu0), dp(toa_scale), dp(sfc_alb_dir),
-                        dp(sfc_alb_dif), dp(flux_up), dp(flux_dn), dp(flux_dir), memspace, stream);
+  const SwColumns c{ncol, nlay, dp(plev), dp(tlay), GasDesc{ngas, gas_names, dp(vmr), vmr_col_stride, vmr_lay_stride, vmr_scalar},
+                    top_at_1, dp(mu0), dp(toa_scale), dp(sfc_alb_dir), dp(sfc_alb_dif)};
+  const FluxOutputs o{Fluxes{dp(flux_up), dp(flux_dn), dp(flux_dir)}};
+  return sw_fluxes_impl(nullptr, true, m, c, 0, SwParticles{}, o, memspace, stream);
 }
 
 // ---- single-precision fused fluxes: longwave, all-sky, McICA, both skies (the *_impl functions with f32 = true) ----
 
-#define ECCKD_GAS_F32_PARAMS \
-  int ngas, const char *gas_names, const float *const *vmr, const long long *vmr_col_stride, const long long *vmr_lay_stride, \
-      const double *vmr_scalar
-#define ECCKD_GAS_F32_ARGS \
-  ngas, gas_names, reinterpret_cast<const double *const *>(vmr), vmr_col_stride, vmr_lay_stride, vmr_scalar
-
 size_t ecckd_lw_fluxes_f32_scratch_bytes(const ecckd_model_t *m, int ncol, int nlay) {
   if (!m || ncol <= 0 || nlay <= 0) return 0;
-  return LwWorkF32(m, ncol, nlay).bytes();
+  return lw_work_f32(m, ncol, nlay).bytes();
 }
 
 size_t ecckd_sw_fluxes_allsky_f32_scratch_bytes(const ecckd_model_t *m, int ncol, int nlay, int delta_scale) {
@@ -4075,75 +4166,99 @@ size_t ecckd_sw_fluxes_allsky_f32_scratch_bytes(const ecckd_model_t *m, int ncol
 }
 
 int ecckd_lw_fluxes_f32(const ecckd_model_t *m, int ncol, int nlay, const float *plev, const float *tlay, const float *tsfc,
-                        const float *tlev, ECCKD_GAS_F32_PARAMS, int top_at_1, int n_gauss_angles, const float *sfc_emis,
-                        const float *inc_flux, float *flux_up, float *flux_dn, int memspace, void *stream) {
-  return lw_fluxes_impl(true, m, ncol, nlay, dp(plev), dp(tlay), dp(tsfc), dp(tlev), ECCKD_GAS_F32_ARGS, top_at_1, n_gauss_angles,
-                        dp(sfc_emis), dp(inc_flux), dp(flux_up), dp(flux_dn), memspace, stream);
+                        const float *tlev, int ngas, const char *gas_names, const float *const *vmr,
+                        const long long *vmr_col_stride, const long long *vmr_lay_stride, const double *vmr_scalar, int top_at_1,
+                        int n_gauss_angles, const float *sfc_emis, const float *inc_flux, float *flux_up, float *flux_dn,
+                        int memspace, void *stream) {
+  const LwColumns c{ncol, nlay, dp(plev), dp(tlay), dp(tsfc), dp(tlev),
+                    GasDesc{ngas, gas_names, dp(vmr), vmr_col_stride, vmr_lay_stride, vmr_scalar}, top_at_1, n_gauss_angles,
+                    dp(sfc_emis), dp(inc_flux)};
+  const FluxOutputs o{Fluxes{dp(flux_up), dp(flux_dn)}};
+  return lw_fluxes_impl(nullptr, true, m, c, 0, LwParticles{}, o, memspace, stream);
 }
 
 int ecckd_lw_fluxes_allsky_f32(const ecckd_model_t *m, int ncol, int nlay, const float *plev, const float *tlay, const float *tsfc,
-                               const float *tlev, ECCKD_GAS_F32_PARAMS, int top_at_1, int n_gauss_angles, const float *sfc_emis,
-                               const float *inc_flux, int nband_p, const float *tau_p, const float *ssa_p, float *flux_up,
-                               float *flux_dn, int memspace, void *stream) {
-  return lw_fluxes_allsky_impl(true, m, ncol, nlay, dp(plev), dp(tlay), dp(tsfc), dp(tlev), ECCKD_GAS_F32_ARGS, top_at_1,
-                               n_gauss_angles, dp(sfc_emis), dp(inc_flux), nband_p, dp(tau_p), dp(ssa_p), nullptr, dp(flux_up),
-                               dp(flux_dn), memspace, stream);
+                               const float *tlev, int ngas, const char *gas_names, const float *const *vmr,
+                               const long long *vmr_col_stride, const long long *vmr_lay_stride, const double *vmr_scalar,
+                               int top_at_1, int n_gauss_angles, const float *sfc_emis, const float *inc_flux, int nband_p,
+                               const float *tau_p, const float *ssa_p, float *flux_up, float *flux_dn, int memspace, void *stream) {
+  const LwColumns c{ncol, nlay, dp(plev), dp(tlay), dp(tsfc), dp(tlev),
+                    GasDesc{ngas, gas_names, dp(vmr), vmr_col_stride, vmr_lay_stride, vmr_scalar}, top_at_1, n_gauss_angles,
+                    dp(sfc_emis), dp(inc_flux)};
+  LwParticles pt;
+  pt.tau = dp(tau_p); pt.ssa = dp(ssa_p);
+  const FluxOutputs o{Fluxes{dp(flux_up), dp(flux_dn)}};
+  return lw_fluxes_impl(&kLwAllsky, true, m, c, nband_p, pt, o, memspace, stream);
 }
 
 int ecckd_lw_fluxes_allsky_mcica_f32(const ecckd_model_t *m, int ncol, int nlay, const float *plev, const float *tlay,
-                                     const float *tsfc, const float *tlev, ECCKD_GAS_F32_PARAMS, int top_at_1, int n_gauss_angles,
-                                     const float *sfc_emis, const float *inc_flux, int nband_p, const float *tau_p,
-                                     const float *ssa_p, const unsigned long long *cloud_mask, float *flux_up, float *flux_dn,
-                                     int memspace, void *stream) {
-  return lw_fluxes_allsky_impl(true, m, ncol, nlay, dp(plev), dp(tlay), dp(tsfc), dp(tlev), ECCKD_GAS_F32_ARGS, top_at_1,
-                               n_gauss_angles, dp(sfc_emis), dp(inc_flux), nband_p, dp(tau_p), dp(ssa_p), cloud_mask, dp(flux_up),
-                               dp(flux_dn), memspace, stream);
+                                     const float *tsfc, const float *tlev, int ngas, const char *gas_names,
+                                     const float *const *vmr, const long long *vmr_col_stride, const long long *vmr_lay_stride,
+                                     const double *vmr_scalar, int top_at_1, int n_gauss_angles, const float *sfc_emis,
+                                     const float *inc_flux, int nband_p, const float *tau_p, const float *ssa_p,
+                                     const unsigned long long *cloud_mask, float *flux_up, float *flux_dn, int memspace,
+                                     void *stream) {
+  const LwColumns c{ncol, nlay, dp(plev), dp(tlay), dp(tsfc), dp(tlev),
+                    GasDesc{ngas, gas_names, dp(vmr), vmr_col_stride, vmr_lay_stride, vmr_scalar}, top_at_1, n_gauss_angles,
+                    dp(sfc_emis), dp(inc_flux)};
+  return lw_fluxes_impl(&kLwAllsky, true, m, c, nband_p, LwParticles{dp(tau_p), dp(ssa_p), nullptr, cloud_mask},
+                        FluxOutputs{Fluxes{dp(flux_up), dp(flux_dn)}}, memspace, stream);
 }
 
 int ecckd_lw_fluxes_clear_allsky_f32(const ecckd_model_t *m, int ncol, int nlay, const float *plev, const float *tlay,
-                                     const float *tsfc, const float *tlev, ECCKD_GAS_F32_PARAMS, int top_at_1, int n_gauss_angles,
-                                     const float *sfc_emis, const float *inc_flux, int nband_p, const float *tau_p,
-                                     const float *ssa_p, const unsigned long long *cloud_mask, float *flux_up, float *flux_dn,
-                                     float *flux_up_clear, float *flux_dn_clear, int memspace, void *stream) {
-  const ClearFluxes clr{dp(flux_up_clear), dp(flux_dn_clear), nullptr};
-  return lw_fluxes_allsky_impl(true, m, ncol, nlay, dp(plev), dp(tlay), dp(tsfc), dp(tlev), ECCKD_GAS_F32_ARGS, top_at_1,
-                               n_gauss_angles, dp(sfc_emis), dp(inc_flux), nband_p, dp(tau_p), dp(ssa_p), cloud_mask, dp(flux_up),
-                               dp(flux_dn), memspace, stream, &clr);
+                                     const float *tsfc, const float *tlev, int ngas, const char *gas_names,
+                                     const float *const *vmr, const long long *vmr_col_stride, const long long *vmr_lay_stride,
+                                     const double *vmr_scalar, int top_at_1, int n_gauss_angles, const float *sfc_emis,
+                                     const float *inc_flux, int nband_p, const float *tau_p, const float *ssa_p,
+                                     const unsigned long long *cloud_mask, float *flux_up, float *flux_dn, float *flux_up_clear,
+                                     float *flux_dn_clear, int memspace, void *stream) {
+  const LwColumns c{ncol, nlay, dp(plev), dp(tlay), dp(tsfc), dp(tlev),
+                    GasDesc{ngas, gas_names, dp(vmr), vmr_col_stride, vmr_lay_stride, vmr_scalar}, top_at_1, n_gauss_angles,
+                    dp(sfc_emis), dp(inc_flux)};
+  const LwParticles pt{dp(tau_p), dp(ssa_p), nullptr, cloud_mask};
+  const FluxOutputs o{Fluxes{dp(flux_up), dp(flux_dn)}, Fluxes{dp(flux_up_clear), dp(flux_dn_clear)}};
+  return lw_fluxes_impl(&kLwClearAllsky, true, m, c, nband_p, pt, o, memspace, stream);
 }
 
-int ecckd_sw_fluxes_allsky_f32(const ecckd_model_t *m, int ncol, int nlay, const float *plev, const float *tlay,
-                               ECCKD_GAS_F32_PARAMS, int top_at_1, const float *mu0, const float *toa_scale,
-                               const float *sfc_alb_dir, const float *sfc_alb_dif, int nband_p, const float *tau_p,
-                               const float *ssa_p, const float *g_p, int delta_scale, float *flux_up, float *flux_dn,
-                               float *flux_dir, int memspace, void *stream) {
-  return sw_fluxes_allsky_impl(true, m, ncol, nlay, dp(plev), dp(tlay), ECCKD_GAS_F32_ARGS, top_at_1, dp(mu0), dp(toa_scale),
-                               dp(sfc_alb_dir), dp(sfc_alb_dif), nband_p, dp(tau_p), dp(ssa_p), dp(g_p), delta_scale, nullptr,
-                               dp(flux_up), dp(flux_dn), dp(flux_dir), memspace, stream);
+int ecckd_sw_fluxes_allsky_f32(const ecckd_model_t *m, int ncol, int nlay, const float *plev, const float *tlay, int ngas,
+                               const char *gas_names, const float *const *vmr, const long long *vmr_col_stride,
+                               const long long *vmr_lay_stride, const double *vmr_scalar, int top_at_1, const float *mu0,
+                               const float *toa_scale, const float *sfc_alb_dir, const float *sfc_alb_dif, int nband_p,
+                               const float *tau_p, const float *ssa_p, const float *g_p, int delta_scale, float *flux_up,
+                               float *flux_dn, float *flux_dir, int memspace, void *stream) {
+  const SwColumns c{ncol, nlay, dp(plev), dp(tlay), GasDesc{ngas, gas_names, dp(vmr), vmr_col_stride, vmr_lay_stride, vmr_scalar},
+                    top_at_1, dp(mu0), dp(toa_scale), dp(sfc_alb_dir), dp(sfc_alb_dif)};
+  return sw_fluxes_impl(&kSwAllsky, true, m, c, nband_p, SwParticles{dp(tau_p), dp(ssa_p), dp(g_p), delta_scale},
+                        FluxOutputs{Fluxes{dp(flux_up), dp(flux_dn), dp(flux_dir)}}, memspace, stream);
 }
 
-int ecckd_sw_fluxes_allsky_mcica_f32(const ecckd_model_t *m, int ncol, int nlay, const float *plev, const float *tlay,
-                                     ECCKD_GAS_F32_PARAMS, int top_at_1, const float *mu0, const float *toa_scale,
-                                     const float *sfc_alb_dir, const float *sfc_alb_dif, int nband_p, const float *tau_p,
-                                     const float *ssa_p, const float *g_p, int delta_scale, const unsigned long long *cloud_mask,
-                                     float *flux_up, float *flux_dn, float *flux_dir, int memspace, void *stream) {
-  return sw_fluxes_allsky_impl(true, m, ncol, nlay, dp(plev), dp(tlay), ECCKD_GAS_F32_ARGS, top_at_1, dp(mu0), dp(toa_scale),
-                               dp(sfc_alb_dir), dp(sfc_alb_dif), nband_p, dp(tau_p), dp(ssa_p), dp(g_p), delta_scale, cloud_mask,
-                               dp(flux_up), dp(flux_dn), dp(flux_dir), memspace, stream);
+int ecckd_sw_fluxes_allsky_mcica_f32(const ecckd_model_t *m, int ncol, int nlay, const float *plev, const float *tlay, int ngas,
+                                     const char *gas_names, const float *const *vmr, const long long *vmr_col_stride,
+                                     const long long *vmr_lay_stride, const double *vmr_scalar, int top_at_1, const float *mu0,
+                                     const float *toa_scale, const float *sfc_alb_dir, const float *sfc_alb_dif, int nband_p,
+                                     const float *tau_p, const float *ssa_p, const float *g_p, int delta_scale,
+                                     const unsigned long long *cloud_mask, float *flux_up, float *flux_dn, float *flux_dir,
+                                     int memspace, void *stream) {
+  const SwColumns c{ncol, nlay, dp(plev), dp(tlay), GasDesc{ngas, gas_names, dp(vmr), vmr_col_stride, vmr_lay_stride, vmr_scalar},
+                    top_at_1, dp(mu0), dp(toa_scale), dp(sfc_alb_dir), dp(sfc_alb_dif)};
+  return sw_fluxes_impl(&kSwAllsky, true, m, c, nband_p, SwParticles{dp(tau_p), dp(ssa_p), dp(g_p), delta_scale, cloud_mask},
+                        FluxOutputs{Fluxes{dp(flux_up), dp(flux_dn), dp(flux_dir)}}, memspace, stream);
 }
 
-int ecckd_sw_fluxes_clear_allsky_f32(const ecckd_model_t *m, int ncol, int nlay, const float *plev, const float *tlay,
-                                     ECCKD_GAS_F32_PARAMS, int top_at_1, const float *mu0, const float *toa_scale,
-                                     const float *sfc_alb_dir, const float *sfc_alb_dif, int nband_p, const float *tau_p,
-                                     const float *ssa_p, const float *g_p, int delta_scale, const unsigned long long *cloud_mask,
-                                     float *flux_up, float *flux_dn, float *flux_dir, float *flux_up_clear, float *flux_dn_clear,
-                                     float *flux_dir_clear, int memspace, void *stream) {
-  const ClearFluxes clr{dp(flux_up_clear), dp(flux_dn_clear), dp(flux_dir_clear)};
-  return sw_fluxes_allsky_impl(true, m, ncol, nlay, dp(plev), dp(tlay), ECCKD_GAS_F32_ARGS, top_at_1, dp(mu0), dp(toa_scale),
-                               dp(sfc_alb_dir), dp(sfc_alb_dif), nband_p, dp(tau_p), dp(ssa_p), dp(g_p), delta_scale, cloud_mask,
-                               dp(flux_up), dp(flux_dn), dp(flux_dir), memspace, stream, &clr);
+int ecckd_sw_fluxes_clear_allsky_f32(const ecckd_model_t *m, int ncol, int nlay, const float *plev, const float *tlay, int ngas,
+                                     const char *gas_names, const float *const *vmr, const long long *vmr_col_stride,
+                                     const long long *vmr_lay_stride, const double *vmr_scalar, int top_at_1, const float *mu0,
+                                     const float *toa_scale, const float *sfc_alb_dir, const float *sfc_alb_dif, int nband_p,
+                                     const float *tau_p, const float *ssa_p, const float *g_p, int delta_scale,
+                                     const unsigned long long *cloud_mask, float *flux_up, float *flux_dn, float *flux_dir,
+                                     float *flux_up_clear, float *flux_dn_clear, float *flux_dir_clear, int memspace,
+                                     void *stream) {
+  const SwColumns c{ncol, nlay, dp(plev), dp(tlay), GasDesc{ngas, gas_names, dp(vmr), vmr_col_stride, vmr_lay_stride, vmr_scalar},
+                    top_at_1, dp(mu0), dp(toa_scale), dp(sfc_alb_dir), dp(sfc_alb_dif)};
+  const SwParticles pt{dp(tau_p), dp(ssa_p), dp(g_p), delta_scale, cloud_mask};
+  const FluxOutputs o{Fluxes{dp(flux_up), dp(flux_dn), dp(flux_dir)}, Fluxes{dp(flux_up_clear), dp(flux_dn_clear), dp(flux_dir_clear)}};
+  return sw_fluxes_impl(&kSwClearAllsky, true, m, c, nband_p, pt, o, memspace, stream);
 }
-#undef ECCKD_GAS_F32_PARAMS
-#undef ECCKD_GAS_F32_ARGS
 
 // ---- spectral (per-band) fluxes: ty_fluxes_byband of RTE-RRTMGP ----
 
@@ -4243,42 +4358,6 @@ int ecckd_rte_sw_byband_f32(int device, int ncol, int nlay, int ngpt, int top_at
 
 // ---- per-band fluxes from the fused path (include/ecckd_hip.h, "Fused per-band fluxes") ----
 
-// first[b] = first 0-based g-point of band b, first[nband] = ngpt; the bands must tile 1..ngpt in ascending order
-static int band_windows(const ecckd_model *m, const char *who, unsigned short *first) {
-  int next = 1;
-  for (int b = 0; b < m->nband; ++b) {
-    if (m->band2gpt[2 * b] != next || m->band2gpt[2 * b + 1] < next)
-      return fail(std::string(who) + ": the model's band2gpt does not tile 1..ngpt in ascending order");
-    first[b] = (unsigned short)(next - 1);
-    next = m->band2gpt[2 * b + 1] + 1;
-  }
-  if (next != m->ng + 1) return fail(std::string(who) + ": the model's band2gpt does not tile 1..ngpt in ascending order");
-  first[m->nband] = (unsigned short)m->ng;
-  return 0;
-}
-
-// The refusals the two calls share, in the order of the header; `planes_missing`: a particulate plane the call requires
-// with nband_p = nband is NULL, `planes_given`: any plane is not NULL.
-static int flux_bands_refusals(const std::string &who, const ecckd_model *m, int nband_p, bool planes_missing, bool planes_given,
-                               const unsigned long long *cloud_mask, const char *missing_text) {
-  if (!m) return fail(who + ": null model");
-  if (cloud_mask && m->ng > 64) return fail(who + std::string(kMaskTooWide) + std::to_string(m->ng));
-  if (nband_p != 0 && nband_p != m->nband)
-    return fail(who + ": nband_p = " + std::to_string(nband_p) + " but the model has " + std::to_string(m->nband) +
-                " bands (particulate properties live on the model's bands; 0: clear sky)");
-  if (nband_p != 0 && planes_missing) return fail(who + missing_text);
-  if (nband_p == 0 && (planes_given || cloud_mask))
-    return fail(who + ": nband_p = 0 is the clear sky: the particulate planes and cloud_mask must be null");
-  return 0;
-}
-
-static int flux_bands_outputs_alias(const std::string &who, std::initializer_list<const double *> outs) {
-  for (auto p = outs.begin(); p != outs.end(); ++p)
-    for (auto q = p + 1; q != outs.end(); ++q)
-      if (*p && *p == *q) return fail(who + ": two outputs are the same array (each needs an array of its own)");
-  return 0;
-}
-
 size_t ecckd_lw_flux_bands_scratch_bytes(const ecckd_model_t *m, int ncol, int nlay) {
   if (!m || ncol <= 0 || nlay <= 0) return 0;
   return ((size_t)ncol * nlay * m->ng + 32 + fused_scratch_doubles(m, ncol, nlay)) * sizeof(double);
@@ -4290,51 +4369,46 @@ int ecckd_lw_flux_bands(const ecckd_model_t *m, int ncol, int nlay, const double
                         int n_gauss_angles, const double *sfc_emis, const double *inc_flux, int nband_p, const double *tau_p,
                         const double *ssa_p, const unsigned long long *cloud_mask, double *bnd_flux_up, double *bnd_flux_dn,
                         double *flux_up, double *flux_dn, int memspace, void *stream) {
-  const std::string who = "ecckd_lw_flux_bands";
-  if (flux_bands_refusals(who, m, nband_p, !tau_p, tau_p || ssa_p, cloud_mask,
-                          ": null argument (tau_p is required with nband_p > 0; ssa_p may be null: one-stream particles)"))
-    return 1;
-  if (g_arith.load() != 0) return fail(who + ": needs the fast arithmetic mode (ecckd_set_arithmetic(0))");
-  if (!m->has_planck) return fail(who + ": model has no Planck table (shortwave model?)");
-  if (!tlev) return fail(who + ": tlev is required for ecckd");
-  if (n_gauss_angles < 1 || n_gauss_angles > 4) return fail(who + ": have to ask for at least one quadrature point and no more than 4");
-  if (!bnd_flux_up || !bnd_flux_dn) return fail(who + ": null argument (bnd_flux_up and bnd_flux_dn are required)");
-  if (flux_bands_outputs_alias(who, {bnd_flux_up, bnd_flux_dn, flux_up, flux_dn})) return 1;
-  if (memspace != ECCKD_DEVICE && memspace != ECCKD_HOST) return fail(who + ": bad memspace (ECCKD_DEVICE or ECCKD_HOST)");
-  if (!m->finalized) return fail(who + ": model is not finalized");
-  if (m->device < 0) return fail(who + ": host-only model (device -1): no GPU, no compute (there is no CPU fallback)");
-  if (check_gas_optics_dims(ncol, nlay)) return 1;
-  if (!plev || !tlay || !tsfc || !sfc_emis || (ngas > 0 && !gas_names)) return fail(who + ": null argument");
+  const LwColumns c{ncol, nlay, plev, tlay, tsfc, tlev, GasDesc{ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar},
+                    top_at_1, n_gauss_angles, sfc_emis, inc_flux};
+  const LwParticles pt{tau_p, ssa_p, nullptr, cloud_mask};
+  const FluxOutputs o{Fluxes{flux_up, flux_dn}, Fluxes{}, Fluxes{bnd_flux_up, bnd_flux_dn}};
+  CallWords w;   // (the refusals in the order of the header; this call puts its name in front of every message)
+  w.who = w.who_mask = "ecckd_lw_flux_bands";
+  w.planes_tail = ": null argument (tau_p is required with nband_p > 0; ssa_p may be null: one-stream particles)";
+  w.need_ssa_g = false;
+  w.nband0_clear = true;
+  w.tlev_text = "ecckd_lw_flux_bands: tlev is required for ecckd";
   unsigned short first[257];
-  if (band_windows(m, who.c_str(), first)) return 1;
-  HIPCHK(hipSetDevice(m->device));
-  if (ncol == 0) return 0;
-  const GasDesc gd{ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar};
+  bool done;
+  if (!m) return refuse(w.who, ": null model");
+  if (lw_head(w, m, c, nband_p, pt) || gauss_refusals(c, w.who)) return 1;
+  if (!bnd_flux_up || !bnd_flux_dn) return refuse(w.who, ": null argument (bnd_flux_up and bnd_flux_dn are required)");
+  if (outputs_alias(w.who, {bnd_flux_up, bnd_flux_dn, flux_up, flux_dn})) return 1;
+  if (bands_tail(w.who, m, ncol, nlay, c.null_array(), memspace, first, &done)) return 1;
+  if (done) return 0;
   const Counts n(ncol, nlay, m->ng, m->nband);
   const bool fused = fused_lw_kernels_apply(m, nlay);
   const size_t extra = fused_scratch_doubles(m, ncol, nlay);
   Stage st(const_cast<ecckd_model *>(m), memspace, stream, false);
-  const double *d_plev = nullptr, *d_tlay = nullptr, *d_tsfc = nullptr, *d_tlev = nullptr, *d_emis = nullptr, *d_incf = nullptr;
-  double *d_bup = nullptr, *d_bdn = nullptr, *d_up = nullptr, *d_dn = nullptr, *d_tau = nullptr;
-  GasDesc d_gd{};
+  LwColumns d{};
   LwParticles d_pt{};
+  FluxOutputs d_o{};
+  double *d_tau = nullptr;
   if (st.open([&] {
-        d_plev = st.in(plev, n.lev); d_tlay = st.in(tlay, n.lay); d_tsfc = st.in(tsfc, n.col); d_tlev = st.in(tlev, n.lev);
-        d_emis = st.in(sfc_emis, n.col_b); d_incf = st.in(inc_flux, n.col_g);
-        d_gd = st.gases(gd, ncol, nlay);
-        d_pt = LwParticles{st.in(tau_p, n.lay_b), st.in(ssa_p, n.lay_b), st.in(cloud_mask, n.lay)};
-        d_bup = st.out(bnd_flux_up, n.lev * m->nband); d_bdn = st.out(bnd_flux_dn, n.lev * m->nband);
-        d_up = st.out(flux_up, n.lev); d_dn = st.out(flux_dn, n.lev);
+        d = c.staged(st, n);
+        d_pt = pt.staged(st, n);
+        d_o.bands = o.bands.staged(st, n.lev * m->nband);
+        d_o.all = o.all.staged(st, n.lev);
         d_tau = st.work((n.lay_g + 32 + extra) * sizeof(double));
       }))
     return 1;
+  double *const d_bup = d_o.bands.up, *const d_bdn = d_o.bands.dn;
   const hipStream_t s = st.stream;
-  if (gas_optical_depth_dev(m, false, nullptr, ncol, nlay, d_plev, d_tlay, d_gd, d_tau, false, nullptr, nullptr, nullptr, nullptr, s)) return 1;
+  if (gas_optical_depth_dev(m, false, nullptr, ncol, nlay, d.plev, d.tlay, d.gas, d_tau, false, nullptr, nullptr, nullptr, nullptr, s)) return 1;
   ecckd::RteLwArgs a{};
-  if (fill_band_map(m->ng, m->nband, m->band2gpt.data(), a.gpt2band)) return 1;
-  a.ncol = ncol; a.nlay = nlay; a.ng = m->ng; a.top_at_1 = top_at_1 ? 1 : 0; a.nband = m->nband;
-  fill_lw_options(a, n_gauss_angles, false);
-  a.tau = d_tau; a.sfc_emis = d_emis; a.inc_flux = d_incf;
+  if (lw_solver_args(m, d, false, a)) return 1;
+  a.tau = d_tau;
   if (fused) {
     // 60 layers: the Planck-recomputing layer-split solver in its band-window form, one launch for all bands
     a.use_split = 1;
@@ -4342,7 +4416,7 @@ int ecckd_lw_flux_bands(const ecckd_model_t *m, int ncol, int nlay, const double
     if (d_pt.tau) { a.part_tau = d_pt.tau; a.part_ssa = d_pt.ssa; a.part_1scl = d_pt.ssa ? 0 : 1; a.part_mask = d_pt.mask; }
     ProfScope prof("rte_lw_fused_bands", s);
     HIPCHK(ecckd::launch_rte_lw_planck_bands(a, m->dbuf + m->off_planck, m->ntp, m->temperature_planck[0],
-                                             m->temperature_planck[1] - m->temperature_planck[0], d_tlay, d_tlev, d_tsfc, first, s));
+                                             m->temperature_planck[1] - m->temperature_planck[0], d.tlay, d.tlev, d.tsfc, first, s));
   } else {
     // general route: Planck sources into scratch, the by-band (masked) increment in place on the scratch optical depth,
     // then the register-resident solver once per band on that band's planes of the same arrays (a launch of its own:
@@ -4350,13 +4424,13 @@ int ecckd_lw_flux_bands(const ecckd_model_t *m, int ncol, int nlay, const double
     double *scratch = d_tau + r32(n.lay_g);
     double *lay = scratch, *inc = lay + n.lay_g, *dec = inc + n.lay_g, *sfc = dec + n.lay_g, *ring = sfc + r32(n.col_g);
     {
-      ecckd::PlanckArgs p = planck_args(m, ncol, nlay, d_tlay, PlanckSide{d_tlev, d_tsfc, lay, inc, dec, sfc});
+      ecckd::PlanckArgs p = planck_args(m, ncol, nlay, d.tlay, PlanckSide{d.tlev, d.tsfc, lay, inc, dec, sfc});
       ProfScope prof("planck", s);
       HIPCHK(ecckd::launch_planck(p, s));
     }
     if (d_pt.tau && lw_increment_dev(m, ncol, nlay, d_tau, d_pt, s)) return 1;
     a.use_split = 0;
-    a.shared_levels = d_incf ? 0 : 1;
+    a.shared_levels = d.inc_flux ? 0 : 1;
     a.scratch = ecckd::rte_lw_scratch_bytes(ncol, nlay, m->ng) ? ring : nullptr;
     ProfScope prof("rte_lw_bands", s);
     for (int b = 0; b < m->nband; ++b) {
@@ -4366,13 +4440,13 @@ int ecckd_lw_flux_bands(const ecckd_model_t *m, int ncol, int nlay, const double
       w.ng = first[b + 1] - first[b];
       w.tau = d_tau + n.lay * g0; w.lay_source = lay + n.lay * g0; w.lev_source_inc = inc + n.lay * g0;
       w.lev_source_dec = dec + n.lay * g0; w.sfc_source = sfc + n.col * g0;
-      w.inc_flux = d_incf ? d_incf + n.col * g0 : nullptr;
+      w.inc_flux = d.inc_flux ? d.inc_flux + n.col * g0 : nullptr;
       w.flux_up = d_bup + n.lev * b; w.flux_dn = d_bdn + n.lev * b;
       HIPCHK(ecckd::launch_rte_lw(w, s));
     }
   }
-  if (d_up) HIPCHK(ecckd::launch_sum_planes(d_bup, m->nband, n.lev, d_up, 0, s));
-  if (d_dn) HIPCHK(ecckd::launch_sum_planes(d_bdn, m->nband, n.lev, d_dn, 0, s));
+  if (d_o.all.up) HIPCHK(ecckd::launch_sum_planes(d_bup, m->nband, n.lev, d_o.all.up, 0, s));
+  if (d_o.all.dn) HIPCHK(ecckd::launch_sum_planes(d_bdn, m->nband, n.lev, d_o.all.dn, 0, s));
   return st.close();
 }
 
@@ -4403,72 +4477,63 @@ int ecckd_sw_flux_bands(const ecckd_model_t *m, int ncol, int nlay, const double
                         const double *tau_p, const double *ssa_p, const double *g_p, int delta_scale,
                         const unsigned long long *cloud_mask, double *bnd_flux_up, double *bnd_flux_dn, double *bnd_flux_dir,
                         double *flux_up, double *flux_dn, double *flux_dir, int memspace, void *stream) {
-  const std::string who = "ecckd_sw_flux_bands";
-  if (flux_bands_refusals(who, m, nband_p, !tau_p || !ssa_p || !g_p, tau_p || ssa_p || g_p, cloud_mask,
-                          ": null argument (tau_p, ssa_p and g_p are all required with nband_p > 0)"))
-    return 1;
-  if (delta_scale != 0 && delta_scale != 1) return fail(who + ": delta_scale must be 0 or 1");
-  if (g_arith.load() != 0) return fail(who + ": needs the fast arithmetic mode (ecckd_set_arithmetic(0))");
-  if (!m->has_solar) return fail(who + ": model has no solar table (longwave model?)");
-  if (!bnd_flux_up || !bnd_flux_dn) return fail(who + ": null argument (bnd_flux_up and bnd_flux_dn are required; bnd_flux_dir may be null)");
-  if (flux_dir && !bnd_flux_dir) return fail(who + ": flux_dir needs bnd_flux_dir");
-  if (flux_bands_outputs_alias(who, {bnd_flux_up, bnd_flux_dn, bnd_flux_dir, flux_up, flux_dn, flux_dir})) return 1;
-  if (memspace != ECCKD_DEVICE && memspace != ECCKD_HOST) return fail(who + ": bad memspace (ECCKD_DEVICE or ECCKD_HOST)");
-  if (!m->finalized) return fail(who + ": model is not finalized");
-  if (m->device < 0) return fail(who + ": host-only model (device -1): no GPU, no compute (there is no CPU fallback)");
-  if (check_gas_optics_dims(ncol, nlay)) return 1;
-  if (!plev || !tlay || !mu0 || !sfc_alb_dir || !sfc_alb_dif || (ngas > 0 && !gas_names)) return fail(who + ": null argument");
+  const SwColumns c{ncol, nlay, plev, tlay, GasDesc{ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar}, top_at_1,
+                    mu0, toa_scale, sfc_alb_dir, sfc_alb_dif};
+  const SwParticles pt{tau_p, ssa_p, g_p, delta_scale, cloud_mask};
+  const FluxOutputs o{Fluxes{flux_up, flux_dn, flux_dir}, Fluxes{}, Fluxes{bnd_flux_up, bnd_flux_dn, bnd_flux_dir}};
+  CallWords w;   // (the refusals in the order of the header; this call puts its name in front of every message)
+  w.who = w.who_mask = "ecckd_sw_flux_bands";
+  w.planes_tail = ": null argument (tau_p, ssa_p and g_p are all required with nband_p > 0)";
+  w.nband0_clear = true;
   unsigned short first[257];
-  if (band_windows(m, who.c_str(), first)) return 1;
-  HIPCHK(hipSetDevice(m->device));
-  if (ncol == 0) return 0;
-  const GasDesc gd{ngas, gas_names, vmr, vmr_col_stride, vmr_lay_stride, vmr_scalar};
+  bool done;
+  if (!m) return refuse(w.who, ": null model");
+  if (sw_head(w, m, nband_p, pt, o)) return 1;
+  if (!m->has_solar) return refuse(w.who, ": model has no solar table (longwave model?)");
+  if (!bnd_flux_up || !bnd_flux_dn) return refuse(w.who, ": null argument (bnd_flux_up and bnd_flux_dn are required; bnd_flux_dir may be null)");
+  if (flux_dir && !bnd_flux_dir) return refuse(w.who, ": flux_dir needs bnd_flux_dir");
+  if (outputs_alias(w.who, {bnd_flux_up, bnd_flux_dn, bnd_flux_dir, flux_up, flux_dn, flux_dir})) return 1;
+  if (bands_tail(w.who, m, ncol, nlay, c.null_array(), memspace, first, &done)) return 1;
+  if (done) return 0;
   const Counts n(ncol, nlay, m->ng, m->nband);
   const bool part = nband_p != 0;
   const SwBandsWork work(m, ncol, nlay, part && delta_scale);
   Stage st(const_cast<ecckd_model *>(m), memspace, stream, false);
-  const double *d_plev = nullptr, *d_tlay = nullptr, *d_mu0 = nullptr, *d_scale = nullptr, *d_ad = nullptr, *d_af = nullptr;
-  double *d_bup = nullptr, *d_bdn = nullptr, *d_bdir = nullptr, *d_up = nullptr, *d_dn = nullptr, *d_dir = nullptr, *d_tau = nullptr;
-  GasDesc d_gd{};
+  SwColumns d{};
   SwParticles d_pt{};
+  FluxOutputs d_o{};
+  double *d_tau = nullptr;
   if (st.open([&] {
-        d_plev = st.in(plev, n.lev); d_tlay = st.in(tlay, n.lay); d_mu0 = st.in(mu0, n.col); d_scale = st.in(toa_scale, n.col);
-        d_ad = st.in(sfc_alb_dir, n.col_b); d_af = st.in(sfc_alb_dif, n.col_b);
-        d_gd = st.gases(gd, ncol, nlay);
-        d_pt = SwParticles{st.in(tau_p, n.lay_b), st.in(ssa_p, n.lay_b), st.in(g_p, n.lay_b), delta_scale, st.in(cloud_mask, n.lay)};
-        d_bup = st.out(bnd_flux_up, n.lev * m->nband); d_bdn = st.out(bnd_flux_dn, n.lev * m->nband);
-        d_bdir = st.out(bnd_flux_dir, n.lev * m->nband);
-        d_up = st.out(flux_up, n.lev); d_dn = st.out(flux_dn, n.lev); d_dir = st.out(flux_dir, n.lev);
+        d = c.staged(st, n);
+        d_pt = pt.staged(st, n);
+        d_o.bands = o.bands.staged(st, n.lev * m->nband);
+        d_o.all = o.all.staged(st, n.lev);
         d_tau = st.work(work.bytes());
       }))
     return 1;
+  const Fluxes &bnd = d_o.bands;
   const hipStream_t s = st.stream;
   char *const room = reinterpret_cast<char *>(d_tau) + work.tau_bytes;
-  if (work.plane) {   // the scaled copy of the band triple, as ecckd_sw_fluxes_allsky makes it
-    double *q_tau = reinterpret_cast<double *>(room + work.solver), *q_ssa = reinterpret_cast<double *>(room + work.solver + work.plane),
-           *q_g = reinterpret_cast<double *>(room + work.solver + 2 * work.plane);
-    ProfScope prof("delta_scale", s);
-    HIPCHK(ecckd::launch_delta_scale(n.lay_b, d_pt.tau, d_pt.ssa, d_pt.g, nullptr, q_tau, q_ssa, q_g, 0, s));
-    d_pt.tau = q_tau; d_pt.ssa = q_ssa; d_pt.g = q_g;
-  }
-  if (gas_optical_depth_dev(m, false, nullptr, ncol, nlay, d_plev, d_tlay, d_gd, d_tau, true, nullptr, nullptr, nullptr, nullptr, s)) return 1;
+  // the scaled copy of the band triple, as ecckd_sw_fluxes_allsky makes it
+  if (work.plane && delta_scaled_copy(d_pt, n.lay_b, room + work.solver, work.plane, false, s)) return 1;
+  if (gas_optical_depth_dev(m, false, nullptr, ncol, nlay, d.plev, d.tlay, d.gas, d_tau, true, nullptr, nullptr, nullptr, nullptr, s)) return 1;
   // One solver launch per band on that band's planes of the optical depth, with the band's entries of the Rayleigh and solar
   // tables: the solver ecckd_sw_fluxes_allsky takes for the shape, told its band as ecckd_rte_sw_byband tells it, and -- with
   // a mask -- in its band-window form, which reads the mask bit at the model's g-point (SwDerive::mask_first).
   for (int b = 0; b < m->nband; ++b) {
     const size_t g0 = first[b];
     const int count = first[b + 1] - first[b];
-    SwDerive dv{d_plev, table(m, m->off_rayleigh, false) + g0, table(m, m->off_solar, false) + g0, d_scale, gw(false),
+    SwDerive dv{d.plev, table(m, m->off_rayleigh, false) + g0, table(m, m->off_solar, false) + g0, d.toa_scale, gw(false),
                 work.solver ? reinterpret_cast<double *>(room) : nullptr};
     if (part) { dv.part_tau = d_pt.tau; dv.part_ssa = d_pt.ssa; dv.part_g = d_pt.g; dv.part_mask = d_pt.mask; dv.mask_first = (int)g0; }
-    if (rte_sw_impl(Call{false, b, false, &dv}, m->device, ncol, nlay, count, top_at_1, d_tau + n.lay * g0, nullptr, nullptr, d_mu0,
-                    nullptr, m->nband, nullptr, d_ad, d_af, d_bup + n.lev * b, d_bdn + n.lev * b,
-                    d_bdir ? d_bdir + n.lev * b : nullptr, ECCKD_DEVICE, s))
+    if (rte_sw_impl(Call{false, b, false, &dv}, m->device, ncol, nlay, count, d.top_at_1, d_tau + n.lay * g0, nullptr, nullptr, d.mu0,
+                    nullptr, m->nband, nullptr, d.sfc_alb_dir, d.sfc_alb_dif, bnd.up + n.lev * b, bnd.dn + n.lev * b,
+                    bnd.dir ? bnd.dir + n.lev * b : nullptr, ECCKD_DEVICE, s))
       return 1;
   }
-  if (d_up) HIPCHK(ecckd::launch_sum_planes(d_bup, m->nband, n.lev, d_up, 0, s));
-  if (d_dn) HIPCHK(ecckd::launch_sum_planes(d_bdn, m->nband, n.lev, d_dn, 0, s));
-  if (d_dir) HIPCHK(ecckd::launch_sum_planes(d_bdir, m->nband, n.lev, d_dir, 0, s));
+  if (d_o.all.up) HIPCHK(ecckd::launch_sum_planes(bnd.up, m->nband, n.lev, d_o.all.up, 0, s));
+  if (d_o.all.dn) HIPCHK(ecckd::launch_sum_planes(bnd.dn, m->nband, n.lev, d_o.all.dn, 0, s));
+  if (d_o.all.dir) HIPCHK(ecckd::launch_sum_planes(bnd.dir, m->nband, n.lev, d_o.all.dir, 0, s));
   return st.close();
 }
 
